@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the fused INT4 hot path on MI355X (contract: see the task statement / DESIGN.md).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload moe|linear512|linear1]
+    python bench.py [--gpus N --steps K --warmup W] [--workload moe|linear512|linear1] [--full] [--dump-outputs DIR]
 
 A *step* is one pass of the hot path over one batch of synthetic input, inputs resident in HBM:
   moe       (default, BASELINE.json configs[2]) QuantizedMoE 8 experts 4096->11008, 512 tokens top-2
@@ -14,6 +14,12 @@ expert-sharded: E/N experts and 512/N tokens per rank, RCCL all-to-all dispatch 
 
 Rank 0 prints ONE JSON line.  `value` = algorithmic TFLOP/s of the whole job, 2*rows*K*N flops per
 step (each multiply-add counted once, however many INT8 limbs the kernel spends on it).
+
+A plain run only sets up, warms up, times the K steps and prints the line.  --full adds, after the timed
+region, the per-kernel durations and roofline, the side measurements, the output check against the oracle
+and the CPU baseline (multi-GPU: the expert-parallel parity check and phase times); the headline is the same.
+--dump-outputs DIR writes the last timed step's output; inputs are seeded, so the same arguments give the same
+inputs from run to run.
 """
 import argparse
 import json
@@ -53,7 +59,17 @@ def parse():
     ap.add_argument("--ffn", type=int, default=11008)
     ap.add_argument("--tokens", type=int, default=512)
     ap.add_argument("--top-k", type=int, default=2)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: per-kernel durations and roofline, "
+                         "the opt-in precision / float16 / routing / decode side measurements, the output check against "
+                         "the oracle, the CPU baseline, and with --gpus N the expert-parallel parity and phase times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/output.npy (float32; a fixed sample of rows "
+                         "when the whole output exceeds 64 MB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def quantize_on_device(w):
@@ -205,6 +221,22 @@ def check_outputs(out, x, P, S, Z, tpe, offs, prec, rows_per_group=3):
                          f"(tolerance {tol:g} for precision {prec!r})")
     return {"max_rel_err": worst, "rows_checked": checked, "tolerance": tol,
             "checker": "oracle/int4_oracle.c (float64 accumulation) on first / middle / last row of the sampled groups"}
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_output(out_dir, y):
+    """--dump-outputs: the [rows, N] output of the last timed step as out_dir/output.npy in float32.  An output above
+    64 MB is cut down to a fixed sample of whole rows (seed 0, ascending row order), the same for every run of a shape."""
+    import numpy as np
+    rows, n = y.shape
+    keep = max(1, (DUMP_LIMIT_BYTES - 4096) // (4 * n))
+    if rows > keep:
+        pick = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        y = y.index_select(0, torch.from_numpy(pick).to(y.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "output.npy"), y.float().cpu().numpy(), allow_pickle=False)
 
 
 def main():
@@ -375,12 +407,16 @@ def main():
         for _ in range(100):
             step()
         torch.cuda.synchronize()
+    # the wake-up loop above runs for a wall-clock time: restart the weight-set rotation so that the last timed step
+    # always sees the same weight set (its output is what --dump-outputs writes)
+    step_i[0] = 0
     for _ in range(a.warmup):
         step()
     barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - 1):
         step()
+    out_last = step()
     torch.cuda.synchronize(); barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -391,12 +427,23 @@ def main():
     total_flops = flops * (world if (a.workload != "moe" and world > 1) else 1)
     value = total_flops / (ms_per_step * 1e-3) / 1e12
 
+    # ------------------------------------------------------------------ outputs of the last timed step (--dump-outputs)
+    if a.dump_outputs:
+        y = out_last if out_last.dim() == 2 else out_last[None]
+        if world > 1:
+            y = all_gather_cat(y)                  # every rank's tokens, in token order (rank-major shards)
+        if rank == 0:
+            dump_output(a.dump_outputs, y)
+    del out_last
+
+    # Everything below up to the result line runs with --full only: a plain run times the headline and stops there.
+
     # ------------------------------------------------------------------ expert-parallel parity (outside the timed region)
     # The first rows of every rank's output must be, bit for bit (top-k <= 2: one addition per output), what ONE GPU's
     # grouped computation gives for the same tokens: every rank runs the single-GPU grouped call on the sampled rows
     # that route to ITS experts, the un-weighted rows are summed over the ranks (one contributor per row: exact) and
     # combined by the same kernel the expert-parallel step uses.  A mismatch aborts the run without a JSON line.
-    if world > 1 and a.workload == "moe":
+    if a.full and world > 1 and a.workload == "moe":
         ns = min(8, t_local)
         EL = E // world
 
@@ -431,7 +478,7 @@ def main():
 
     # ------------------------------------------------------------------ expert-parallel phases (outside the timed region)
     ep_roofline = None
-    if world > 1 and a.workload == "moe":
+    if a.full and world > 1 and a.workload == "moe":
         for ep in ep_objects:
             ep.record_phases = True
         for _ in range(max(4, min(20, a.steps))):
@@ -459,7 +506,7 @@ def main():
 
     # ------------------------------------------------------------------ per-kernel durations (HIP events on the launch stream)
     roofline = ep_roofline
-    if phases is not None and world == 1:
+    if a.full and phases is not None and world == 1:
         # How the GEMM kernel's duration is taken (HIP events on the launch stream, right after the timed region):
         #   * an event pair around ONE launch also times the launch path (marker packets either side of the dispatch:
         #     ~15 us on this stack -- the "kernel" would come out longer than the whole step), so a pair brackets a BATCH;
@@ -551,7 +598,7 @@ def main():
                                                 "frac": hbm_achieved / HBM_PEAK_GBPS, "bytes": weight_bytes}
         extra["roofline_mfma_i8"] = {"achieved": mfma_achieved, "peak": MFMA_I8_PEAK_TOPS, "unit": "TFLOP/s",
                                      "frac": mfma_achieved / MFMA_I8_PEAK_TOPS, "issued_frac": mfma_achieved * limbs / MFMA_I8_PEAK_TOPS}
-    elif world == 1:   # GEMV: one ~10 us kernel per step.  Eager launches from Python are host-bound at that
+    elif a.full and world == 1:   # GEMV: one ~10 us kernel per step.  Eager launches from Python are host-bound at that
         # size, so the kernel's average duration is taken from a hipGraph of `n` back-to-back launches
         # (each still pays the ~1.5 us dependent-launch boundary), timed with HIP events on the stream.
         n = max(20, min(a.steps, 200))
@@ -578,7 +625,7 @@ def main():
         extra.update({"gemv_kernel_ms_avg_graph": k_ms, "graph_launches": n})
 
     # ------------------------------------------------------------------ the opt-in reduced-limb modes, for the record
-    if world == 1 and a.workload == "moe" and prec in ("default", "exact") and not a.no_side_modes:
+    if a.full and world == 1 and a.workload == "moe" and prec in ("default", "exact") and not a.no_side_modes:
         def time_mode(mode):
             def step_mode():
                 P, S, Z = sets[step_i[0] % len(sets)]
@@ -646,7 +693,7 @@ def main():
 
     # ------------------------------------------------------------------ side measurement: the reference's DEFAULT routing
     # distribution ("skewed", benchmark/run_moe_benchmark.py:106; routing.py:26-93) on the same weights and step
-    if (a.workload == "moe" and world == 1 and a.routing == "balanced" and prec in ("default", "exact")
+    if (a.full and a.workload == "moe" and world == 1 and a.routing == "balanced" and prec in ("default", "exact")
             and not a.no_side_modes):
         route_s = R.simulate_routing(a.tokens, E, a.top_k, "skewed", dev, 42)
         xs, tpe_s, offs_s, _ = R.dispatch_grouped(x_tok, route_s.expert_indices, E)
@@ -683,7 +730,7 @@ def main():
     # (HBM-bound: the packed weights are read once per step whatever the row count).  decode32: 32 tokens, top-2 -> 8 rows
     # per expert on the same 8 x (4096 -> 11008) weights; linear1: QuantizedLinear 4096 -> 11008 at batch 1 (configs[0] on
     # the GPU), walking the experts' matrices of every weight set so that no call finds its weights in a cache.
-    if (a.workload == "moe" and world == 1 and a.routing == "balanced" and prec in ("default", "exact")
+    if (a.full and a.workload == "moe" and world == 1 and a.routing == "balanced" and prec in ("default", "exact")
             and not a.no_side_modes and a.tokens != 32):
         def time_side(fn, n):
             t_wake = time.perf_counter()
@@ -740,7 +787,7 @@ def main():
 
     # ------------------------------------------------------------------ output check of the timed call (A12 / VERDICT r1)
     # the same call once more, compared with the oracle on sampled rows of every group; a wrong result fails the run
-    if world == 1 and os.environ.get("FQL_BENCH_SKIP_CHECK") != "1":
+    if a.full and world == 1 and os.environ.get("FQL_BENCH_SKIP_CHECK") != "1":
         out0 = step()
         torch.cuda.synchronize()
         if a.workload == "moe":
@@ -755,7 +802,7 @@ def main():
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1 only)
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         if a.workload == "moe":
             P, S, Z = sets[0]
             cpu = cpu_baseline_moe(P, S, Z, x, tpe, offs, K, N)

@@ -11,6 +11,10 @@ from oracle import oracle as O
 from oracle import c_oracle as C
 from conftest import load_golden
 
+# a float32 matmul on this host against the golden float32 matmul recorded on another CPU (different sgemm summation
+# order): both within 1e-5 of the float64 accumulation, so within 2e-5 of each other (test_linear_outputs)
+F32_HOSTS_ATOL = F32_HOSTS_RTOL = 2e-5
+
 
 def test_f1_quantize_dequantize_bit_exact():
     g = load_golden("f1_quant_16x32")
@@ -34,9 +38,12 @@ def test_linear_outputs(name):
         assert np.array_equal(p, g["packed"]) and np.array_equal(s, g["scales"]) and np.array_equal(z, g["zero_points"])
     out = O.reference_quantized_linear(g["x"], g["packed"], g["scales"], g["zero_points"])
     assert out.shape == g["out"].shape
-    assert np.allclose(out, g["out"], atol=1e-5, rtol=1e-5)
+    # The golden float32 sums were recorded with one CPU's sgemm summation order.  The float64 accumulation is host
+    # independent and holds the golden to 1e-5; a float32 sum on another CPU is another rounding of the same value
+    # within 1e-5 of it, so it is held to the golden at twice that.
     exact = O.reference_quantized_linear(g["x"], g["packed"], g["scales"], g["zero_points"], exact=True)
-    assert np.allclose(exact, g["out"], atol=1e-4, rtol=1e-5)
+    assert np.allclose(exact, g["out"], atol=1e-5, rtol=1e-5)
+    assert np.allclose(out, g["out"], atol=F32_HOSTS_ATOL, rtol=F32_HOSTS_RTOL)
     c64 = C.linear_f64acc(g["x"], g["packed"], g["scales"], g["zero_points"])
     assert np.allclose(c64, exact, atol=1e-9, rtol=1e-12)
     cfma = C.linear_fma(g["x"], g["packed"], g["scales"], g["zero_points"])
@@ -184,5 +191,5 @@ def test_torch_op_oracle_is_pinned_too():
         args = [torch.from_numpy(np.ascontiguousarray(g[k])) for k in ("x", "packed", "scales", "zero_points")]
         out = OT.reference_quantized_linear(*args).numpy()
         assert out.shape == g["out"].shape
-        assert np.allclose(out, g["out"], atol=1e-5, rtol=1e-5)
+        assert np.allclose(out, g["out"], atol=F32_HOSTS_ATOL, rtol=F32_HOSTS_RTOL)      # see test_linear_outputs
         assert np.allclose(out, O.reference_quantized_linear(g["x"], g["packed"], g["scales"], g["zero_points"]), atol=1e-5, rtol=1e-5)
