@@ -64,6 +64,13 @@ _SYMBOLS = {
                        + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fql_moe_fwd_f8": (ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fql_linear_fwd_f8": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_linear_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "fql_linear_bwd_input_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 4
+                                 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "fql_moe_bwd_input_f32": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5
+                              + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_combine_bwd_f32": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "fql_moe_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }

@@ -161,12 +161,14 @@ __device__ __forceinline__ int act_token_rows(int p0, int rows, int *s_tok, ActL
 // Padded row p of each of the workgroup's grouped rows t0 .. t0 + rows - 1 into s_p (-1: no expert owns the row, or it is
 // past T).  Wave 0 only; lane i owns expert base + i, (off_raw, cnt_raw) are the first chunk's table entries, loaded by the
 // caller (expert_chunk_load) before its loads of x.  One ballot per row instead of a serial walk over the experts.
+// s_e (optional): the expert of each row (0 for the linear op, -1 where s_p is -1).
 // The caller synchronises before reading s_p.
 __device__ __forceinline__ void act_padded_rows(int t0, int rows, int *s_p, int off_raw, int cnt_raw,
                                                 const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs,
-                                                int E, int T, int lane)
+                                                int E, int T, int lane, int *s_e = nullptr)
 {
     if (lane < rows) s_p[lane] = (tpe == nullptr && t0 + lane < T) ? t0 + lane : -1;
+    if (s_e != nullptr && lane < rows) s_e[lane] = (tpe == nullptr && t0 + lane < T) ? 0 : -1;
     if (tpe == nullptr) return;
     int cp = 0, ct = 0;
     for (int base = 0; base < E; base += 64) {
@@ -179,6 +181,7 @@ __device__ __forceinline__ void act_padded_rows(int t0, int rows, int *s_p, int 
                 const int src = __ffsll((long long)hit) - 1;
                 const int pv = wave_bcast(xl.pad_excl + rel, src);
                 if (lane == 0) s_p[rr] = pv;
+                if (s_e != nullptr && lane == 0) s_e[rr] = base + src;
             }
         }
     }
@@ -215,11 +218,17 @@ static __device__ unsigned long long fql_trace_act[16 * 16];   // (one copy per 
 // runs it more than once synchronises in between.
 // WT: every global store goes straight to device-coherent memory (sc1): the one-launch form's consumers sit on other XCDs,
 // whose L2s are not coherent with this one's, and a release fence instead (L2 write-back) cost 10-20 us per workgroup.
-template <int L, bool VEC, int IN, bool GATE = false, bool F8OUT = false, int AR = ACT_ROWS, bool WT = false>
+// CS (float32 input only; the backward pre-pass of fql_bwd.h): every loaded element is first multiplied by the column
+// scale cs_scale[e][k] of its row's expert e (one float32 rounding), and the row's float correction
+// sum_k x[k] * cs_scale[e][k] * f[e][k], f = zp - clamp(rint(zp), -112, 112) (cs_zp = the zero points), is written to
+// the plane delta[DSETS * T + t] (the row-weight plane of the forward, unused by the backward).  The expert of each row is
+// looked up BEFORE the loads of x here (the loads need it).
+template <int L, bool VEC, int IN, bool GATE = false, bool F8OUT = false, int AR = ACT_ROWS, bool WT = false, bool CS = false>
 __device__ __forceinline__ void act_rows(
     const void *__restrict__ xin, const int32_t *__restrict__ gather, int n_src, float *__restrict__ delta,
     int32_t *__restrict__ rowsum, int8_t *__restrict__ limbs, int T, int K, int KB, int MBT, int rblocks,
-    const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs, int E, const float *__restrict__ row_weight, int t0)
+    const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs, int E, const float *__restrict__ row_weight, int t0,
+    const float *__restrict__ cs_scale = nullptr, const float *__restrict__ cs_zp = nullptr)
 {
     (void)rblocks;
     constexpr int ES = (IN == 0) ? 4 : 2;
@@ -237,6 +246,9 @@ __device__ __forceinline__ void act_rows(
     __shared__ __attribute__((aligned(16))) float s_ssq[R_][16];
     __shared__ int s_flag[R_];
     static_assert(!F8OUT || L == 1, "fp8 activations are one byte plane");
+    static_assert(!CS || (IN == 0 && !GATE && !F8OUT && !WT), "column-scaled rows: float32 input, int8 limbs");
+    __shared__ int s_e[CS ? R_ : 1];
+    __shared__ __attribute__((aligned(16))) float s_cor[CS ? R_ : 1][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     FQL_ASTAMP(0);
 
@@ -254,13 +266,24 @@ __device__ __forceinline__ void act_rows(
     const int nch = KB * 16;                      // 16-float chunks per padded row
     const int slabs = (nch + COLS_ * CH_ - 1) / (COLS_ * CH_);
     int tok = trow < T ? trow : -1;               // (-1 once the lookup finds no expert for the row either)
+    const float *csr = nullptr, *czr = nullptr;   // CS: this row's column scales / zero points
+    if constexpr (CS) {
+        if (wave == 0) act_padded_rows(t0, R_, s_p, off_raw, cnt_raw, tpe, offs, E, T, lane, s_e);
+        __syncthreads();
+        const int ce = s_e[r % (CS ? R_ : 1)] < 0 ? 0 : s_e[r % (CS ? R_ : 1)];
+        csr = cs_scale + (size_t)ce * K;
+        czr = cs_zp + (size_t)ce * K;
+    }
+    float cor = 0.0f;                             // CS: this thread's part of the row's float correction
+    auto cs_frac = [](float z) { return z - fminf(fmaxf(rintf(z), -112.0f), 112.0f); };
 
     // VEC (K % 16 == 0, x 16-byte aligned; host-checked): every load is unconditional.  A chunk past K (the
     // zero padding up to a multiple of 256) or a padding row re-reads valid data -- duplicates do not move the
     // row max -- and is masked to +0.0f in pass 2.
     v4f xv[CH_][4];
     auto chunk_ok = [&](int slab, int j) { return tok >= 0 && (slab * COLS_ * CH_ + col + COLS_ * j) * 16 < K; };
-    auto load_slab = [&](int slab) {
+    auto load_slab = [&](int slab, bool first) {
+        (void)first;
 #pragma unroll
         for (int j = 0; j < CH_; ++j) {
             const int k0 = (slab * COLS_ * CH_ + col + COLS_ * j) * 16;
@@ -277,6 +300,20 @@ __device__ __forceinline__ void act_rows(
                 } else if (IN == 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xv[j][q] = *reinterpret_cast<const v4f *>(src + 16 * q);
+                    if constexpr (CS) {
+                        const int kc = k0 < K ? k0 : 0;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const v4f s4 = *reinterpret_cast<const v4f *>(csr + kc + 4 * q);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) xv[j][q][i] = xv[j][q][i] * s4[i];
+                            if (first && k0 < K) {
+                                const v4f z4 = *reinterpret_cast<const v4f *>(czr + kc + 4 * q);
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) cor = fmaf(xv[j][q][i], cs_frac(z4[i]), cor);
+                            }
+                        }
+                    }
                 } else {                          // 16 halves = two 16-byte loads
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -297,6 +334,10 @@ __device__ __forceinline__ void act_rows(
                         float v = 0.0f;
                         if (k < K) {
                             if (IN == 0 && GATE) v = act_silu_mul(reinterpret_cast<const float *>(xr)[k], reinterpret_cast<const float *>(xr)[K + k]);
+                            else if (IN == 0 && CS) {
+                                v = reinterpret_cast<const float *>(xr)[k] * csr[k];
+                                if (first) cor = fmaf(v, cs_frac(czr[k]), cor);
+                            }
                             else if (IN == 0) v = reinterpret_cast<const float *>(xr)[k];
                             else v = act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]);
                         }
@@ -307,9 +348,9 @@ __device__ __forceinline__ void act_rows(
     };
 
     // ---- all loads of the first slab, then the padded row of every grouped row (wave 0; the others go on to the maximum)
-    load_slab(0);
+    load_slab(0, true);
     __builtin_amdgcn_sched_barrier(0);
-    if (wave == 0) act_padded_rows(t0, R_, s_p, off_raw, cnt_raw, tpe, offs, E, T, lane);
+    if (!CS && wave == 0) act_padded_rows(t0, R_, s_p, off_raw, cnt_raw, tpe, offs, E, T, lane);
     __builtin_amdgcn_sched_barrier(0);
     FQL_ASTAMP(1);
 
@@ -317,7 +358,7 @@ __device__ __forceinline__ void act_rows(
     //      integer max finds the magnitude and flags a non-finite row
     uint32_t mu = 0u;
     for (int slab = 0; slab < slabs; ++slab) {
-        if (slab > 0) load_slab(slab);
+        if (slab > 0) load_slab(slab, true);
 #pragma unroll
         for (int j = 0; j < CH_; ++j)
 #pragma unroll
@@ -353,7 +394,7 @@ __device__ __forceinline__ void act_rows(
         if (tid < R_ && tok >= 0) { delta[tok] = bad ? __builtin_nanf("") : scale; if (row_weight != nullptr) delta[(size_t)DSETS * T + tok] = row_weight[tok]; }
         long long sum8 = 0;
         for (int slab = 0; slab < slabs; ++slab) {
-            if (slabs > 1) load_slab(slab);
+            if (slabs > 1) load_slab(slab, false);
 #pragma unroll
             for (int j = 0; j < CH_; ++j) {
                 const int ch = slab * COLS_ * CH_ + col + COLS_ * j;
@@ -413,7 +454,7 @@ __device__ __forceinline__ void act_rows(
         constexpr bool RESID = decltype(resid_tag)::value;
         int8_t *base = limbs + (RESID ? (size_t)L * KB * MBT * 8192 : (size_t)0);
         for (int slab = 0; slab < slabs; ++slab) {
-            if (slabs > 1) load_slab(slab);
+            if (slabs > 1) load_slab(slab, false);
 #pragma unroll
             for (int j = 0; j < CH_; ++j) {
                 const int ch = slab * COLS_ * CH_ + col + COLS_ * j;
@@ -497,9 +538,22 @@ __device__ __forceinline__ void act_rows(
         ssq = __int_as_float(act_row16_reduce<R_>(__float_as_int(ssq), [](int a, int b) { return __float_as_int(__int_as_float(a) + __int_as_float(b)); }));
         if ((lane & 15) < R_) s_ssq[lane & 15][wave * 4 + (lane >> 4)] = ssq;
     }
+    if (CS) {
+        cor = __int_as_float(act_row16_reduce<R_>(__float_as_int(cor), [](int a, int b) { return __float_as_int(__int_as_float(a) + __int_as_float(b)); }));
+        if ((lane & 15) < R_) s_cor[(lane & 15) % (CS ? R_ : 1)][wave * 4 + (lane >> 4)] = cor;
+    }
     __syncthreads();
     if (tid < R_) {
         int flag = 0;
+        if (CS && tok >= 0) {                                                  // (fixed order, as the limb sums)
+            float tot = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const v4f q = reinterpret_cast<const v4f *>(s_cor[tid % (CS ? R_ : 1)])[i];
+                tot += (q[0] + q[1]) + (q[2] + q[3]);
+            }
+            put_f(delta + (size_t)DSETS * T + tok, tot);
+        }
         if (tok >= 0) {
 #pragma unroll
             for (int l = 0; l < L; ++l) put_i(rowsum + (size_t)l * T + tok, total_sum(tid, l));

@@ -1,0 +1,170 @@
+// libfql_int4.so, third translation unit: the input-gradient entry points (include/fql_int4.h,
+// fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32) over the kernels of fql_bwd.h.
+// Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+#include "../../include/fql_int4.h"
+#include "fql_common.h"
+#include "fql_act_quant.h"
+#include "fql_bwd.h"
+
+namespace {
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+inline int padded(int n) { return (n + FQL_KB - 1) / FQL_KB * FQL_KB; }
+// 32-row blocks of the limb workspace (as fql_int4.hip): every expert starts on a block boundary, and a tile may run
+// up to 128 rows past the last expert
+inline long long row_blocks(int T, int E) { return ((long long)T + (long long)FQL_MB * E + 128 + FQL_MB - 1) / FQL_MB; }
+
+// Limbs of the backward: 3 (default / exact), 2 (fast), 1 (int8, and fp8 layers: the gradient is never an fp8 plane)
+inline int bwd_limbs(int precision)
+{
+    if (precision == FQL_PRECISION_DEFAULT) return 3;
+    if (precision == FQL_PRECISION_INT8 || precision == FQL_PRECISION_FAST || precision == FQL_PRECISION_EXACT)
+        return precision;
+    if (precision == FQL_PRECISION_FP8) return 1;
+    return -1;
+}
+
+struct BwdWorkspace {
+    int8_t *limbs = nullptr;
+    float *delta = nullptr;      // [sets + 1][T]: delta, delta2 (residual set), the per-row float correction
+    int32_t *rowsum = nullptr;   // [sets][L][T] (written by the pre-pass; the backward GEMM does not need them)
+    size_t bytes = 0;
+};
+
+inline size_t bwd_limb_bytes(int L, int T, int E, int Np) { return (size_t)L * (Np / FQL_KB) * (size_t)row_blocks(T, E) * 8192; }
+
+inline BwdWorkspace bwd_carve(void *base, int L, int T, int E, int Np)
+{
+    BwdWorkspace w;
+    const int sets = (FQL_RES_ENABLED && L >= 2) ? 2 : 1;
+    const size_t lb = round16((size_t)sets * bwd_limb_bytes(L, T, E, Np));
+    const size_t db = round16((size_t)(sets + 1) * T * sizeof(float));
+    const size_t rb = round16((size_t)sets * L * T * sizeof(int32_t));
+    char *p = static_cast<char *>(base);
+    w.limbs = reinterpret_cast<int8_t *>(p);
+    w.delta = reinterpret_cast<float *>(p + lb);
+    w.rowsum = reinterpret_cast<int32_t *>(p + lb + db);
+    w.bytes = lb + db + rb;
+    return w;
+}
+
+inline int compute_units()
+{
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    n -= n % 8;                                              // keep vb % 8 == blockIdx % 8 (XCD grouping)
+    return n > 0 ? n : 8;
+}
+
+template <int L>
+int launch_bwd(const float *gy, const uint8_t *packed, const float *scales, const float *zps, float *gx,
+               const int32_t *tpe, const int32_t *offs, int E, int T, int K, int N, const BwdWorkspace &w, hipStream_t st)
+{
+    const int Np = padded(N);
+    const int MBT = (int)row_blocks(T, E);
+    // pre-pass: 4-row workgroups, or one row per workgroup when there are few rows in all (fql_int4.hip, launch_act_quant)
+    const bool vec = (N % 16 == 0) && aligned16(gy) && aligned16(scales) && aligned16(zps);
+    const int mblocks = (tpe == nullptr) ? (T + FQL_MB - 1) / FQL_MB : (T + FQL_MB * E) / FQL_MB;
+    const bool single = vec && (long long)mblocks * FQL_MB <= 512;
+    const int rblocks = single ? T : (T + ACT_ROWS - 1) / ACT_ROWS;
+    const int zblocks = tpe != nullptr ? (T + 255) / 256 : 0;
+    void (*pre)(const float *, float *, int32_t *, int8_t *, int, int, int, int, int, float *, int, const int32_t *,
+                const int32_t *, int, const float *, const float *) =
+        single ? act_colscale_kernel<L, true, 1> : (vec ? act_colscale_kernel<L, true, ACT_ROWS> : act_colscale_kernel<L, false, ACT_ROWS>);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(pre, dim3(rblocks + zblocks), dim3(256), 0, st, gy, w.delta, w.rowsum, w.limbs, T, N, Np / FQL_KB, MBT,
+                       rblocks, gx, K, tpe, offs, E, scales, zps);
+    if (hipGetLastError() != hipSuccess) return FQL_ERR_LAUNCH;
+
+    const int m_slots = (tpe == nullptr) ? (T + BwdCfg::BM - 1) / BwdCfg::BM : (T + BwdCfg::BM - 1) / BwdCfg::BM + E;
+    const int n_tiles = (K + BwdCfg::BN - 1) / BwdCfg::BN;
+    const long long tiles = (long long)m_slots * n_tiles;
+    const int grid = (int)(tiles < compute_units() ? tiles : compute_units());
+    const bool vw = (K % 32 == 0) && aligned16(packed);
+    auto gemm = vw ? gemm_bwd_kernel<L, true> : gemm_bwd_kernel<L, false>;
+    hipLaunchKernelGGL(gemm, dim3(grid), dim3(BwdCfg::THREADS), 0, st, w.limbs, w.delta, packed, zps, gx, tpe, offs, E, T,
+                       K, N, Np, MBT, m_slots, n_tiles);
+    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+}
+
+// Shape limits shared by the workspace query and the entry points: i32 exactness (N), 31-bit buffer offsets (limbs, weights),
+// the tile count.
+inline bool bwd_shape_ok(int L, int E, int T, int K, int N)
+{
+    if (N > FQL_BWD_MAX_N || E > 65535) return false;
+    const size_t sets = (FQL_RES_ENABLED && L >= 2) ? 2 : 1;
+    if (sets * bwd_limb_bytes(L, T, E, padded(N)) >= ((size_t)1 << 31)) return false;
+    if ((size_t)N * (size_t)(K >> 1) >= ((size_t)1 << 31)) return false;
+    const long long m_slots = ((long long)T + BwdCfg::BM - 1) / BwdCfg::BM + E;
+    return m_slots * ((K + BwdCfg::BN - 1) / BwdCfg::BN) < ((long long)1 << 31);
+}
+
+size_t bwd_workspace_bytes(int E, int T, int K, int N, int precision)
+{
+    const int L = bwd_limbs(precision);
+    if (L < 0 || E <= 0 || T <= 0 || K <= 0 || N <= 0 || (K & 1) || !bwd_shape_ok(L, E, T, K, N)) return 0;
+    return bwd_carve(nullptr, L, T, E, padded(N)).bytes;
+}
+
+int bwd_entry(const float *grad_out, const uint8_t *packed, const float *scales, const float *zps,
+              const int32_t *tpe, const int32_t *offs, float *grad_in, int E, int T, int K, int N, int precision,
+              void *ws, size_t ws_bytes, void *stream, bool grouped)
+{
+    const int L = bwd_limbs(precision);
+    if (L < 0) return FQL_ERR_BAD_PRECISION;
+    if (E < 0 || T < 0 || K < 0 || N < 0) return FQL_ERR_BAD_SHAPE;
+    if (K & 1) return FQL_ERR_ODD_K;
+    if (N > FQL_BWD_MAX_N || E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (T == 0 || K == 0) return FQL_OK;
+    if (!grad_in) return FQL_ERR_NULL_POINTER;
+    if (N > 0 && E > 0 && (!grad_out || !packed || !scales || !zps || (grouped && (!tpe || !offs))))
+        return FQL_ERR_NULL_POINTER;
+    if (N > 0 && E > 0 && !bwd_shape_ok(L, E, T, K, N)) return FQL_ERR_BAD_SHAPE;
+    if (N > 0 && E > 0) {
+        const size_t need = bwd_carve(nullptr, L, T, E, padded(N)).bytes;
+        if (!ws || !aligned16(ws) || ws_bytes < need) return FQL_ERR_WORKSPACE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (N == 0 || E == 0)                                     // empty contraction / no expert: the gradient is zero
+        return hipMemsetAsync(grad_in, 0, (size_t)T * K * sizeof(float), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    const BwdWorkspace w = bwd_carve(ws, L, T, E, padded(N));
+    switch (L) {
+    case 1: return launch_bwd<1>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    case 2: return launch_bwd<2>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    default: return launch_bwd<3>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+FQL_API size_t fql_linear_bwd_workspace_bytes(int B, int K, int N, int precision)
+{
+    return bwd_workspace_bytes(1, B, K, N, precision);
+}
+
+FQL_API int fql_linear_bwd_input_f32(const float *grad_out, const uint8_t *packed, const float *scales, const float *zps,
+                                     float *grad_in, int B, int K, int N, int precision, void *ws, size_t ws_bytes,
+                                     void *stream)
+{
+    return bwd_entry(grad_out, packed, scales, zps, nullptr, nullptr, grad_in, 1, B, K, N, precision, ws, ws_bytes, stream,
+                     false);
+}
+
+FQL_API size_t fql_moe_bwd_workspace_bytes(int E, int T, int K, int N, int precision)
+{
+    return bwd_workspace_bytes(E, T, K, N, precision);
+}
+
+FQL_API int fql_moe_bwd_input_f32(const uint8_t *packed, const float *scales, const float *zps, const float *grad_out,
+                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, float *grad_in, int E,
+                                  int T, int K, int N, int precision, void *ws, size_t ws_bytes, void *stream)
+{
+    return bwd_entry(grad_out, packed, scales, zps, tokens_per_expert, input_offsets, grad_in, E, T, K, N, precision, ws,
+                     ws_bytes, stream, true);
+}
+
+}  // extern "C"

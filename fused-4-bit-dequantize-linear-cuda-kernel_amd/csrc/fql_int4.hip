@@ -1077,6 +1077,21 @@ int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *wei
     return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
 }
 
+int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
+                        float *grad_y, float *grad_weights, int T, int top_k, int N, int rows, void *stream)
+{
+    if (T < 0 || top_k <= 0 || N < 0 || rows < 0) return FQL_ERR_BAD_SHAPE;
+    if (T == 0) return FQL_OK;
+    if (rows == 0) return FQL_ERR_BAD_SHAPE;                 // slots with no rows to point at
+    if (!pos_of_slot) return FQL_ERR_NULL_POINTER;
+    if (N > 0 && (!grad_out || !grad_y)) return FQL_ERR_NULL_POINTER;
+    if (grad_weights != nullptr && N > 0 && !y) return FQL_ERR_NULL_POINTER;
+    if (N == 0 && grad_weights == nullptr) return FQL_OK;
+    hipLaunchKernelGGL(combine_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), grad_out, y,
+                       pos_of_slot, weights, grad_y, grad_weights, T, top_k, N, rows);
+    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+}
+
 int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                           int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream)
 {

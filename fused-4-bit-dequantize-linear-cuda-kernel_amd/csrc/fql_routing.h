@@ -7,6 +7,7 @@
 //                        sorted position the token row it reads (the gather index of fql_moe_gather_fwd_f32) and
 //                        for every slot its sorted position (the un-sort index of the combine).
 //   combine_kernel       out[t][:] = sum_k w[t][k] * y[pos[t][k]][:]  (k ascending), 16-byte loads and stores.
+//   combine_bwd_kernel   its gradients to y and to w, in one launch.
 //   regroup_index_kernel expert-parallel receive side: rows arrive (source rank, local expert)-major, the GEMM
 //                        wants (local expert, source rank)-major: gather index + its inverse + the expert table.
 #pragma once
@@ -95,6 +96,39 @@ __global__ __launch_bounds__(256) void combine_kernel(
     else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) if (n + c < N) orow[c] = acc[c];
+    }
+}
+
+// Backward of combine_kernel, one workgroup per token t, no atomics (pos_of_slot is a permutation of the rows, so every
+// row of grad_y is written by exactly one slot):
+//   grad_y[pos[t][k]][:] = w[t][k] * grad_out[t][:]      (w == NULL: grad_out[t][:] itself)
+//   grad_w[t][k]         = <y[pos[t][k]][:], grad_out[t][:]>   (grad_w == NULL: skipped; fixed summation order)
+__global__ __launch_bounds__(256) void combine_bwd_kernel(
+    const float *__restrict__ gout, const float *__restrict__ y, const int32_t *__restrict__ pos_of_slot,
+    const float *__restrict__ w, float *__restrict__ gy, float *__restrict__ gw, int T, int top_k, int N, int R)
+{
+    __shared__ float s_part[4];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *go = gout + (size_t)t * N;
+    for (int k = 0; k < top_k; ++k) {
+        int p = pos_of_slot[(size_t)t * top_k + k];
+        p = p < 0 ? 0 : (p >= R ? R - 1 : p);
+        const float wk = w != nullptr ? w[(size_t)t * top_k + k] : 1.0f;
+        const float *yr = y + (size_t)p * N;
+        float *gyr = gy + (size_t)p * N;
+        float dot = 0.0f;
+        for (int n = tid; n < N; n += 256) {
+            const float g = go[n];
+            gyr[n] = w != nullptr ? wk * g : g;
+            if (gw != nullptr) dot = fmaf(yr[n], g, dot);
+        }
+        if (gw != nullptr) {
+            dot = wave_sum(dot);
+            if (lane == 0) s_part[wave] = dot;
+            __syncthreads();
+            if (tid == 0) gw[(size_t)t * top_k + k] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+            __syncthreads();
+        }
     }
 }
 

@@ -242,7 +242,15 @@ class ExpertParallelMoE:
         return (y * expert_weights.unsqueeze(-1).to(y.dtype)).sum(dim=1)
 
     def forward(self, x: torch.Tensor, expert_indices: torch.Tensor, expert_weights: torch.Tensor) -> torch.Tensor:
-        """x [t_local, K] float32, expert_indices / expert_weights [t_local, top_k] -> [t_local, N]."""
+        """x [t_local, K] float32, expert_indices / expert_weights [t_local, top_k] -> [t_local, N].
+
+        Forward-only on the GPU and across ranks: neither the collectives nor the fused gather GEMM carry a backward,
+        so an ``x`` or ``expert_weights`` that requires grad (under grad mode) is refused there rather than given a
+        partial gradient.  (A single CPU rank with a differentiable ``expert_fn`` is plain torch and differentiates.)"""
+        if (torch.is_grad_enabled() and (x.requires_grad or expert_weights.requires_grad)
+                and (self.world > 1 or x.is_cuda)):
+            raise RuntimeError("ExpertParallelMoE has no backward on the GPU or across ranks: call it under "
+                               "torch.no_grad() or on detached inputs (INTEGRATION.md section 5)")
         if self.capacity_factor is not None and self.world > 1 and x.shape[0] > 0:
             return self._forward_fixed_capacity(x, expert_indices, expert_weights)
         if x.is_cuda and self.num_experts <= 128 and x.shape[0] > 0:

@@ -248,6 +248,8 @@ class QuantizedMoEFFN(nn.Module):
         if not inputs.is_cuda:
             raise RuntimeError("QuantizedMoEFFN runs on the GPU (the product path has no CPU fallback)")
         from . import ops
+        if torch.is_grad_enabled() and inputs.requires_grad:
+            return _GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self)
         gate_up = ops.moe_forward(self.gate_up_packed, self.gate_up_scales, self.gate_up_zero_points, inputs, None,
                                   tokens_per_expert, input_offsets, precision=self.precision)
         return ops.moe_gated_forward(self.down_packed, self.down_scales, self.down_zero_points, gate_up,
@@ -256,3 +258,36 @@ class QuantizedMoEFFN(nn.Module):
     @property
     def total_memory_bytes(self) -> int:
         return sum(b.numel() * b.element_size() for b in self.buffers())
+
+
+class _GatedFFNFn(torch.autograd.Function):
+    """``QuantizedMoEFFN`` with the input gradient.  Keeps the ``gate_up`` tensor the forward materialises anyway; the
+    backward is ``dh`` on the down weights, ``dg = dh * u * silu'(g)`` and ``du = dh * silu(g)`` (torch elementwise),
+    then ``dx`` on the gate / up weights -- both GEMMs the fused kernel of csrc/fql_bwd.h."""
+
+    @staticmethod
+    def forward(ctx, inputs, tokens_per_expert, input_offsets, m):
+        from . import ops
+        gate_up = ops.moe_forward(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None,
+                                  tokens_per_expert, input_offsets, precision=m.precision)
+        out = ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up,
+                                    tokens_per_expert, input_offsets, precision=m.precision)
+        ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        gate_up, tpe, offs = ctx.saved_tensors
+        m = ctx.m
+        K = gate_up.shape[1] // 2
+        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy.to(torch.float32), tpe, offs,
+                                    precision=m.precision)
+        g, u = gate_up[:, :K], gate_up[:, K:]
+        sig = torch.sigmoid(g)
+        dgu = torch.cat([dh * u * (sig * (1.0 + g * (1.0 - sig))), dh * (g * sig)], dim=1)
+        dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
+                                    precision=m.precision)
+        return dx, None, None, None

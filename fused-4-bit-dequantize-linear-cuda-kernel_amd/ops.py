@@ -43,7 +43,10 @@ def _workspace(nbytes, device):
 
 def linear_forward(input, packed_weights, scales, zero_points, precision="default", bias=None):
     """Fused 4-bit dequantize + linear forward.  input [K] or [B,K] float32 -> [N] or [B,N].
-    ``bias`` [N] float32 (optional, not in the reference: python/module.py:84) is added in the kernels' epilogues."""
+    ``bias`` [N] float32 (optional, not in the reference: python/module.py:84) is added in the kernels' epilogues.
+    Under autograd (grad mode on, ``input`` or ``bias`` requiring grad) the input gradient runs on the GPU too."""
+    if _wants_grad(input, bias):
+        return _LinearFn.apply(input, packed_weights, scales, zero_points, bias, precision, None, False)
     squeeze = False
     if input.dim() == 1:                                   # :302-306
         input = input.unsqueeze(0)
@@ -164,6 +167,7 @@ def moe_group_forward(packed_weights, scales, zero_points, inputs, tokens_per_ex
     """Grouped per-expert INT4 GEMM with per-GROUP scales along K: ``scales`` / ``zero_points`` [E, N, K / group_size].
     Batches of 8+ rows per expert run on the INT8 matrix cores (limb accumulators folded in float32 per group), smaller
     ones on the float32 matrix-core / FMA kernels (include/fql_int4.h); rows no expert covers are zero."""
+    _forward_only("moe_group_forward", inputs)
     if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2 or packed_weights.dim() != 3:
         raise RuntimeError("inputs must be a CUDA float32 [T, K] tensor and packed_weights [E, N, K/2]")
     E, N, K2 = packed_weights.shape
@@ -201,8 +205,12 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
     tokens_per_expert / input_offsets [E] int32 on the device (consumed there, no .item()).
     ``expert_ids`` is accepted and ignored, as in the reference (csrc/moe_int4_kernel.cu:98).
     Returns [T,N] float32; rows covered by no expert are zero (reference: torch::zeros :109).
+    Under autograd (grad mode on, ``inputs`` requiring grad) the input gradient runs on the GPU too.
     """
     del expert_ids
+    if _wants_grad(inputs):
+        return _MoEFn.apply(inputs, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, precision,
+                            None, False)
     for name, t in (("packed_weights", packed_weights), ("scales", scales), ("zero_points", zero_points),
                     ("inputs", inputs), ("tokens_per_expert", tokens_per_expert),
                     ("input_offsets", input_offsets)):
@@ -255,6 +263,8 @@ def linear_forward_any(input, packed_weights, scales, zero_points, precision="de
     out_dtype = input.dtype if out_dtype is None else out_dtype
     if input.dtype not in _DTYPES or out_dtype not in _DTYPES:
         raise RuntimeError("activations and outputs must be float32, float16 or bfloat16")
+    if _wants_grad(input):
+        return _LinearFn.apply(input, packed_weights, scales, zero_points, None, precision, out_dtype, True)
     if input.dtype == torch.float32 and out_dtype == torch.float32:
         return linear_forward(input, packed_weights, scales, zero_points, precision=precision)
     x2 = input.unsqueeze(0) if input.dim() == 1 else input
@@ -292,6 +302,9 @@ def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tok
     out_dtype = inputs.dtype if out_dtype is None else out_dtype
     if inputs.dtype not in _DTYPES or out_dtype not in _DTYPES:
         raise RuntimeError("activations and outputs must be float32, float16 or bfloat16")
+    if _wants_grad(inputs):
+        return _MoEFn.apply(inputs, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, precision,
+                            out_dtype, True)
     if inputs.dtype == torch.float32 and out_dtype == torch.float32:
         return moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_per_expert, input_offsets,
                            precision=precision)
@@ -351,6 +364,7 @@ def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, t
     ``tokens`` [n_tokens, K] float32 in token order, ``row_index`` [T] int32 (e.g. from
     ``routing.dispatch_indices``).  Returns the grouped outputs [T, N]; un-sort / combine with
     ``routing.combine_grouped``.  The [T, K] gathered activations are never materialised."""
+    _forward_only("moe_gather_forward", tokens, row_weight)
     for name, t in (("packed_weights", packed_weights), ("tokens", tokens), ("row_index", row_index),
                     ("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
         if not t.is_cuda:
@@ -398,6 +412,7 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
     """Second GEMM of a gated FFN expert with the activation fused into its pre-pass:
     ``out[t] = W_e @ (silu(gate_up[t, :K]) * gate_up[t, K:])``; ``gate_up`` [T, 2K] float32 (the output of the
     fused gate|up projection), ``packed_weights`` [E, N, K/2].  The [T, K] hidden activation is never written."""
+    _forward_only("moe_gated_forward", gate_up)
     if not gate_up.is_cuda or gate_up.dtype != torch.float32 or gate_up.dim() != 2:
         raise RuntimeError("gate_up must be a CUDA float32 [T, 2K] tensor")
     T, K2 = gate_up.shape
@@ -454,7 +469,10 @@ def route_plan(expert_indices, num_experts):
 
 def combine(y, pos_of_slot, expert_weights, top_k=None):
     """out[t] = sum_k expert_weights[t, k] * y[pos_of_slot[t*top_k + k]] in one launch (routing.py:172-189).
-    ``expert_weights=None`` (with ``top_k``): the rows already carry their weights -- a pure gather-add."""
+    ``expert_weights=None`` (with ``top_k``): the rows already carry their weights -- a pure gather-add.
+    Under autograd the gradients to ``y`` and ``expert_weights`` come from one backward launch."""
+    if _wants_grad(y, expert_weights):
+        return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k)
     if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 2:
         raise RuntimeError("y must be a CUDA float32 [rows, N] tensor")
     if expert_weights is None:
@@ -692,6 +710,7 @@ def moe_forward_fp8(packed_weights, scales, zero_points, inputs_e4m3, act_scales
     """Grouped per-expert INT4 GEMM over rows that are already fp8: ``inputs_e4m3`` [T, K] torch.float8_e4m3fn
     (or its uint8 bytes), ``act_scales`` [T] float32 or None.  One fp8 MFMA pass, float32 accumulation
     (BASELINE.json configs[4]).  Returns [T, N] in ``out_dtype``; rows no expert covers are zero."""
+    _forward_only("moe_forward_fp8", inputs_e4m3, act_scales)
     x8 = _as_e4m3_bytes(inputs_e4m3, "inputs_e4m3")
     for name, t in (("packed_weights", packed_weights), ("scales", scales), ("zero_points", zero_points), ("inputs_e4m3", x8),
                     ("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
@@ -737,6 +756,7 @@ def moe_forward_fp8(packed_weights, scales, zero_points, inputs_e4m3, act_scales
 def linear_forward_fp8(x_e4m3, act_scales, packed_weights, scales, zero_points, out_dtype=torch.float32):
     """Fused 4-bit dequantize + linear over fp8 rows: ``x_e4m3`` [B, K] torch.float8_e4m3fn (or uint8 bytes),
     ``act_scales`` [B] float32 or None -> [B, N] in ``out_dtype``."""
+    _forward_only("linear_forward_fp8", x_e4m3, act_scales)
     x8 = _as_e4m3_bytes(x_e4m3, "x_e4m3")
     if not x8.is_cuda or not packed_weights.is_cuda:
         raise RuntimeError("x_e4m3 and packed_weights must be CUDA tensors")
@@ -771,3 +791,182 @@ def linear_forward_fp8(x_e4m3, act_scales, packed_weights, scales, zero_points, 
                                  ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
     _native.check(rc, "fql_linear_fwd_f8")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Backward (input and routing-weight gradients).  The weights are frozen buffers: no weight gradient is computed, and
+# the backward is once-differentiable.  Inference is untouched: the autograd wrappers below are entered only when grad
+# mode is on and an input requires grad, and their forward is the plain op (bit for bit the same values).
+# ---------------------------------------------------------------------------------------------------------------------
+
+def linear_backward_input(grad_out, packed_weights, scales, zero_points, precision="default"):
+    """``grad_in = grad_out @ W`` for the per-row INT4 weights ``W = (q - zp) * s`` ([N, K]): the transposed INT4 GEMM
+    of csrc/fql_bwd.h.  ``grad_out`` [B, N] float32 on the GPU -> [B, K] float32."""
+    if not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.dim() != 2:
+        raise RuntimeError("grad_out must be a CUDA float32 [B, N] tensor")
+    N, K2 = packed_weights.shape
+    B, K = grad_out.shape[0], 2 * K2
+    if grad_out.shape[1] != N or scales.numel() != N or zero_points.numel() != N:
+        raise RuntimeError("grad_out, scales and zero_points must have output_dim columns / elements")
+    dev = grad_out.device
+    gy = grad_out.contiguous()
+    p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
+    L = _native.lib()
+    prec = _precision(precision)
+    out = torch.empty((B, K), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_ptr = _workspace(L.fql_linear_bwd_workspace_bytes(B, K, N, prec), dev)
+        rc = L.fql_linear_bwd_input_f32(gy.data_ptr(), p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), out.data_ptr(),
+                                        B, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
+    _native.check(rc, "fql_linear_bwd_input_f32")
+    return out
+
+
+def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per_expert, input_offsets,
+                       precision="default"):
+    """Grouped ``grad_in[t] = grad_out[t] @ W_e`` for the rows of each expert's range; rows no expert covers are zero.
+    ``grad_out`` [T, N] float32, ``packed_weights`` [E, N, K/2] -> [T, K] float32."""
+    if not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.dim() != 2:
+        raise RuntimeError("grad_out must be a CUDA float32 [T, N] tensor")
+    E, N, K2 = packed_weights.shape
+    T, K = grad_out.shape[0], 2 * K2
+    if grad_out.shape[1] != N or tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N):
+        raise RuntimeError("grad_out must be [T, ffn_dim] and scales / zero_points [num_experts, ffn_dim]")
+    dev = grad_out.device
+    gy = grad_out.contiguous()
+    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
+    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
+    p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
+    L = _native.lib()
+    prec = _precision(precision)
+    out = torch.empty((T, K), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, ws_ptr = _workspace(L.fql_moe_bwd_workspace_bytes(E, T, K, N, prec), dev)
+        rc = L.fql_moe_bwd_input_f32(p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), gy.data_ptr(), tpe.data_ptr(),
+                                     offs.data_ptr(), out.data_ptr(), E, T, K, N, prec, ws_ptr,
+                                     0 if ws is None else ws.numel(), _stream_ptr(dev))
+    _native.check(rc, "fql_moe_bwd_input_f32")
+    return out
+
+
+# rows of per-group weights dequantised at a time by the unfused backward (bounds its float32 transient to
+# GROUP_BWD_CHUNK * K * 4 bytes)
+GROUP_BWD_CHUNK = 1024
+
+
+def group_backward_input(grad_out, packed_weights, scales, zero_points):
+    """Per-group weights (``scales`` [N, K / group_size]): UNFUSED backward -- GPU dequantise of GROUP_BWD_CHUNK rows
+    of W at a time, then a float32 ``torch.mm``.  The rank-1 zero-point fold of the fused kernel does not apply here."""
+    from .quantize import dequantize_weights
+    N = packed_weights.shape[0]
+    gy = grad_out.contiguous()
+    out = None
+    for n0 in range(0, N, GROUP_BWD_CHUNK):
+        n1 = min(N, n0 + GROUP_BWD_CHUNK)
+        w = dequantize_weights(packed_weights[n0:n1].contiguous(), scales[n0:n1].contiguous(),
+                               zero_points[n0:n1].contiguous())
+        part = torch.mm(gy[:, n0:n1], w)
+        out = part if out is None else out.add_(part)
+    return out
+
+
+def combine_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, need_weights=True):
+    """Gradients of ``combine``: ``(grad_y [R, N], grad_weights [T, top_k] or None)`` in one launch, no atomics.
+    Rows of ``y`` that no slot names get zero."""
+    if expert_weights is not None:
+        T, top_k = expert_weights.shape
+    else:
+        T = pos_of_slot.numel() // top_k
+    dev = y.device
+    R, N = y.shape
+    gout = grad_out.to(torch.float32).contiguous()
+    y_c = y.contiguous()
+    pos = pos_of_slot.to(device=dev, dtype=torch.int32).contiguous()
+    w = None if expert_weights is None else expert_weights.to(device=dev, dtype=torch.float32).contiguous()
+    grad_y = (torch.empty if R == T * top_k else torch.zeros)((R, N), dtype=torch.float32, device=dev)
+    grad_w = torch.empty((T, top_k), dtype=torch.float32, device=dev) if (need_weights and w is not None) else None
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_combine_bwd_f32(gout.data_ptr(), y_c.data_ptr(), pos.data_ptr(),
+                                               None if w is None else w.data_ptr(), grad_y.data_ptr(),
+                                               None if grad_w is None else grad_w.data_ptr(), T, top_k, N, R,
+                                               _stream_ptr(dev))
+    _native.check(rc, "fql_combine_bwd_f32")
+    return grad_y, grad_w
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _forward_only(name, *tensors):
+    """The ops without a backward refuse inputs that require grad (under grad mode): their output would carry no
+    grad_fn, and everything upstream of them would silently get no gradient."""
+    if _wants_grad(*tensors):
+        raise RuntimeError(f"ops.{name} has no backward (forward-only); call it under torch.no_grad() or on detached "
+                           "inputs.  The differentiable ops are linear_forward, linear_forward_any, moe_forward, "
+                           "moe_forward_any and combine (INTEGRATION.md section 5)")
+
+
+class _LinearFn(torch.autograd.Function):
+    """``linear_forward`` / ``linear_forward_any`` with an input gradient (fused, per-row weights) or the unfused
+    per-group one.  Saves the weight buffers only."""
+
+    @staticmethod
+    def forward(ctx, x, packed, scales, zps, bias, precision, out_dtype, any_dtype):
+        ctx.save_for_backward(packed, scales, zps)
+        ctx.precision, ctx.x_dtype, ctx.x_dim = precision, x.dtype, x.dim()
+        ctx.bias_grad = bias is not None and bias.requires_grad
+        if any_dtype:
+            return linear_forward_any(x, packed, scales, zps, precision=precision, out_dtype=out_dtype)
+        return linear_forward(x, packed, scales, zps, precision=precision, bias=bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        packed, scales, zps = ctx.saved_tensors
+        g2 = gy.to(torch.float32).reshape(-1, gy.shape[-1]) if gy.dim() == 1 else gy.to(torch.float32)
+        if scales.dim() == 2 and scales.shape[1] > 1:
+            gx = group_backward_input(g2, packed, scales, zps)
+        else:
+            gx = linear_backward_input(g2, packed, scales, zps, precision=ctx.precision)
+        gx = gx.reshape(-1) if ctx.x_dim == 1 else gx
+        gb = g2.sum(0) if ctx.bias_grad else None
+        return gx.to(ctx.x_dtype), None, None, None, gb, None, None, None
+
+
+class _MoEFn(torch.autograd.Function):
+    """``moe_forward`` / ``moe_forward_any`` with the grouped input gradient.  Saves the weight buffers and the expert
+    table only."""
+
+    @staticmethod
+    def forward(ctx, inputs, packed, scales, zps, tpe, offs, precision, out_dtype, any_dtype):
+        ctx.save_for_backward(packed, scales, zps, tpe, offs)
+        ctx.precision, ctx.x_dtype = precision, inputs.dtype
+        if any_dtype:
+            return moe_forward_any(packed, scales, zps, inputs, None, tpe, offs, precision=precision, out_dtype=out_dtype)
+        return moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        packed, scales, zps, tpe, offs = ctx.saved_tensors
+        gx = moe_backward_input(packed, scales, zps, gy.to(torch.float32), tpe, offs, precision=ctx.precision)
+        return gx.to(ctx.x_dtype), None, None, None, None, None, None, None, None
+
+
+class _CombineFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, pos_of_slot, expert_weights, top_k):
+        ctx.save_for_backward(y, pos_of_slot, expert_weights)
+        ctx.top_k = top_k
+        return combine(y, pos_of_slot, expert_weights, top_k)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        y, pos, w = ctx.saved_tensors
+        need_w = w is not None and ctx.needs_input_grad[2]
+        gy, gw = combine_backward(gout, y, pos, w, ctx.top_k, need_weights=need_w)
+        if gw is not None and w.dtype != torch.float32:
+            gw = gw.to(w.dtype)
+        return gy, None, gw, None

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 210 /* 0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 220 /* 0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -357,6 +357,37 @@ FQL_API int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int t
 
 FQL_API int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *weights, float *out,
                             int T, int top_k, int N, int R, void *stream);
+
+/* ---- backward (input gradients; the INT4 weights are frozen: no weight gradient) ----
+ * fql_linear_bwd_input_f32: grad_in[B][K] = grad_out[B][N] @ W, W[n][k] = (q[n][k] - zps[n]) * scales[n], on the INT8
+ *   matrix cores (csrc/fql_bwd.h): g = grad_out * scales (one float32 rounding) is split into `precision` limbs per row
+ *   exactly as the forward splits x (3 for DEFAULT / EXACT, 2 for FAST, 1 for INT8 and FP8), the weights enter as the
+ *   exact integers q - clamp(rint(zp), -112, 112), and the fractional part of non-integer zero points is applied as a
+ *   float32 correction per row.  float32 gradients only (16-bit callers convert).  Any even K, any N in
+ *   [0, FQL_BWD_MAX_N] (the i32 accumulation is exact up to 2^31 / (128 * 127) = 132104).  Every element of grad_in
+ *   is written once: deterministic, no atomics.
+ * fql_moe_bwd_input_f32: the grouped form: grad_in[t] = grad_out[t] @ W_e for the rows of expert e's range
+ *   (tokens_per_expert / input_offsets on the device, never read back), packed [E][N][K/2], scales / zps [E][N];
+ *   rows no expert covers are zeroed.
+ *   Both: B / T == 0 or K == 0 -> FQL_OK with nothing done; N == 0 (or E == 0) -> grad_in zeroed; workspace at least
+ *   fql_*_bwd_workspace_bytes(), 16-byte aligned.  Errors: FQL_ERR_BAD_PRECISION, FQL_ERR_BAD_SHAPE (negative
+ *   dimension, N > FQL_BWD_MAX_N, E > 65535, 31-bit workspace / weight offsets exceeded), FQL_ERR_ODD_K,
+ *   FQL_ERR_NULL_POINTER, FQL_ERR_WORKSPACE, FQL_ERR_LAUNCH -- in that order, all before any HIP call.
+ * fql_combine_bwd_f32: gradients of fql_combine_f32 in one launch, no atomics (pos_of_slot must be a permutation of
+ *   the rows of y that it names): grad_y[pos[t][k]] = weights[t][k] * grad_out[t] (weights == NULL: grad_out[t]);
+ *   grad_weights[t][k] = <y[pos[t][k]], grad_out[t]> (skipped when grad_weights == NULL).  Rows of grad_y no slot
+ *   names are not written. */
+#define FQL_BWD_MAX_N 132104
+FQL_API size_t fql_linear_bwd_workspace_bytes(int B, int K, int N, int precision);
+FQL_API int fql_linear_bwd_input_f32(const float *grad_out, const uint8_t *packed, const float *scales, const float *zps,
+                                     float *grad_in, int B, int K, int N, int precision, void *ws, size_t ws_bytes,
+                                     void *stream);
+FQL_API size_t fql_moe_bwd_workspace_bytes(int E, int T, int K, int N, int precision);
+FQL_API int fql_moe_bwd_input_f32(const uint8_t *packed, const float *scales, const float *zps, const float *grad_out,
+                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, float *grad_in, int E,
+                                  int T, int K, int N, int precision, void *ws, size_t ws_bytes, void *stream);
+FQL_API int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
+                                float *grad_y, float *grad_weights, int T, int top_k, int N, int rows, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
