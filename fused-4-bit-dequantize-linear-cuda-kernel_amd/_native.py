@@ -23,6 +23,7 @@ PRECISION_INT8 = 1
 PRECISION_FAST = 2
 PRECISION_EXACT = 3
 PRECISION_FP8 = 8
+LORA_RC, LORA_CR = 0, 1        # adapter weight layouts: [E][r][C] (lora_A) / [E][C][r] (lora_B)
 
 _SYMBOLS = {
     # name: (restype, argtypes)
@@ -71,6 +72,11 @@ _SYMBOLS = {
     "fql_moe_bwd_input_f32": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5
                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fql_combine_bwd_f32": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "fql_lora_shrink_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+                            + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_lora_expand_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4
+                            + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_lora_grad_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p]),
     "fql_moe_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }

@@ -1,0 +1,375 @@
+// Segmented (per-expert, ragged) low-rank adapter kernels: float32 in, float32 out, float32 VALU FMAs.
+//
+// For the rows t of expert e (rows [lo_e, hi_e), from tokens_per_expert / input_offsets on the device; one segment of
+// all T rows when the table is NULL), with rank R and a weight W_e stored [E][R][C] (FQL_LORA_RC) or [E][C][R]
+// (FQL_LORA_CR):
+//
+//   shrink  out[t][j] = scale * sum_c in[t][c] * W_e[j][c]                   [T][C] -> [T][R]
+//   expand  out[t][c] = in[t][c] + scale * sum_j V[t][j] * W_e[c][j]         [T][R] -> [T][C]   (in == out allowed)
+//   grad    D_e[c][j] = scale * sum_{t in e} P[t][c] * V[t][j]               -> [E][C][R] or [E][R][C]
+//
+// At R <= 64 all three are bandwidth-bound (2 R FLOP per streamed float), so the design is: stream the [T][C] operand
+// once with the widest load its alignment allows (VEC = 4 / 2 / 1 floats), keep 64 float32 accumulators per lane, and
+// re-read the small weight from L2.
+//
+// Determinism.  No atomics; every output element is written once by one lane, after a reduction whose order depends
+// only on the row's position inside its expert (never on T, E or the tile the row shares):
+//   * shrink: lane l of the workgroup sums the VEC-column groups l, l + 512, ... of its rows; the 64 partial sums of
+//     a wave are reduced by a fixed butterfly (each step halves the values a lane keeps), then the 8 waves in order.
+//   * expand: one lane per output element, j ascending.
+//   * grad: wave w of 8 sums the rows lo_e + w, lo_e + w + 8, ... in ascending order; the 8 partials are added by a
+//     fixed tree through LDS.  An expert's result is therefore the same bits whether it is computed in a grouped call
+//     or alone with E = 1.
+// Rows covered by no expert: shrink writes zeros, expand copies `in` (zeros when in == NULL; nothing when in place).
+#pragma once
+#include "fql_common.h"
+
+#define FQL_LORA_SHRINK_THREADS 512
+#define FQL_LORA_EXPAND_THREADS 256
+#define FQL_LORA_EXPAND_ROWS 8
+#define FQL_LORA_GRAD_THREADS 512
+#define FQL_LORA_COVER_ROWS 64      // rows per coverage workgroup (rows no expert owns)
+
+namespace lora {
+
+template <int VEC> struct vec_t;
+template <> struct vec_t<4> { typedef float4 type; };
+template <> struct vec_t<2> { typedef float2 type; };
+template <> struct vec_t<1> { typedef float type; };
+
+template <int VEC>
+__device__ __forceinline__ void load_vec(const float *p, float (&v)[VEC])
+{
+    const typename vec_t<VEC>::type t = *reinterpret_cast<const typename vec_t<VEC>::type *>(p);
+    if constexpr (VEC == 4) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else if constexpr (VEC == 2) { v[0] = t.x; v[1] = t.y; }
+    else { v[0] = t; }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_vec(float *p, const float (&v)[VEC])
+{
+    typename vec_t<VEC>::type t;
+    if constexpr (VEC == 4) { t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; }
+    else if constexpr (VEC == 2) { t.x = v[0]; t.y = v[1]; }
+    else { t = v[0]; }
+    *reinterpret_cast<typename vec_t<VEC>::type *>(p) = t;
+}
+
+// Rows [lo, hi) of expert e, clamped into [0, T) (a table that points outside the tensor never reaches memory).
+__device__ __forceinline__ void expert_rows(const int32_t *tpe, const int32_t *offs, int e, int T, int &lo, int &hi)
+{
+    const int cnt = tpe[e], off = offs[e];
+    lo = min(max(off, 0), T);
+    hi = cnt > 0 ? (int)min((long long)off + cnt, (long long)T) : lo;
+    hi = max(hi, lo);
+}
+
+// Tile slot b -> (rows [row0, row0 + n) of one expert).  Experts are dealt ceil(count / TM) consecutive slots in
+// order; slots past the last tile return false.  The scan is wave-uniform (scalar loads of the table).
+template <int TM>
+__device__ __forceinline__ bool tile_rows(const int32_t *tpe, const int32_t *offs, int E, int T, int b, int &e_out,
+                                          int &row0, int &n)
+{
+    if (tpe == nullptr) {
+        e_out = 0;
+        row0 = b * TM;
+        n = min(TM, T - row0);
+        return row0 < T;
+    }
+    int acc = 0;
+    for (int e = 0; e < E; ++e) {
+        int lo, hi;
+        expert_rows(tpe, offs, e, T, lo, hi);
+        const int tiles = (hi - lo + TM - 1) / TM;
+        if (b < acc + tiles) {
+            e_out = e;
+            row0 = lo + (b - acc) * TM;
+            n = min(TM, hi - row0);
+            return true;
+        }
+        acc += tiles;
+    }
+    return false;
+}
+
+// Coverage workgroup: flag[i] = 1 if row r0 + i belongs to some expert.  All writers store the same value.
+__device__ __forceinline__ void cover_flags(const int32_t *tpe, const int32_t *offs, int E, int T, int r0, int *flag)
+{
+    for (int i = threadIdx.x; i < FQL_LORA_COVER_ROWS; i += blockDim.x) flag[i] = 0;
+    __syncthreads();
+    for (int e = threadIdx.x; e < E; e += blockDim.x) {
+        int lo, hi;
+        expert_rows(tpe, offs, e, T, lo, hi);
+        const int a = max(lo, r0), z = min(hi, r0 + FQL_LORA_COVER_ROWS);
+        for (int r = a; r < z; ++r) flag[r - r0] = 1;
+    }
+    __syncthreads();
+}
+
+// ---- shrink: out[t][0:R] = scale * in[t][:] . W_e^T.  One workgroup = TM = 64 / R rows of one expert, 512 lanes
+//      across the columns; grid = tile slots (+ coverage workgroups when there is a table).
+template <int R, bool CR, int VEC>
+__global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
+    const float *__restrict__ in, const float *__restrict__ w, const int32_t *__restrict__ tpe,
+    const int32_t *__restrict__ offs, float *__restrict__ out, int E, int T, int C, float scale, int slots)
+{
+    constexpr int TM = 64 / R;
+    constexpr int NW = FQL_LORA_SHRINK_THREADS / FQL_WAVE;
+    __shared__ float red[NW][64];
+    __shared__ int flag[FQL_LORA_COVER_ROWS];
+    if ((int)blockIdx.x >= slots) {                              // rows no expert owns: zeros
+        const int r0 = ((int)blockIdx.x - slots) * FQL_LORA_COVER_ROWS;
+        cover_flags(tpe, offs, E, T, r0, flag);
+        for (int i = threadIdx.x; i < FQL_LORA_COVER_ROWS * R; i += blockDim.x) {
+            const int t = r0 + i / R;
+            if (t < T && !flag[i / R]) out[(size_t)t * R + i % R] = 0.f;
+        }
+        return;
+    }
+    int e, row0, n;
+    if (!tile_rows<TM>(tpe, offs, E, T, (int)blockIdx.x, e, row0, n)) return;
+    const float *we = w + (size_t)e * R * C;
+
+    float acc[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) acc[i] = 0.f;
+    const int nq = C / VEC;
+    for (int q = threadIdx.x; q < nq; q += FQL_LORA_SHRINK_THREADS) {
+        const int c = q * VEC;
+        float x[TM][VEC];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            if (i < n) load_vec<VEC>(in + (size_t)(row0 + i) * C + c, x[i]);
+            else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) x[i][v] = 0.f;
+            }
+        }
+        if constexpr (!CR) {                                     // W_e[j][c .. c + VEC)
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                float wv[VEC];
+                load_vec<VEC>(we + (size_t)j * C + c, wv);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[i * R + j] = fmaf(x[i][v], wv[v], acc[i * R + j]);
+            }
+        } else {                                                 // W_e[c + v][0 .. R)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v)
+#pragma unroll
+                for (int j = 0; j < R; j += 4) {
+                    float wv[4];
+                    load_vec<4>(we + (size_t)(c + v) * R + j, wv);
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int jj = 0; jj < 4; ++jj) acc[i * R + j + jj] = fmaf(x[i][v], wv[jj], acc[i * R + j + jj]);
+                }
+        }
+    }
+    // wave butterfly: at the step of width h, a lane keeps the half of its values selected by (lane & h) and adds the
+    // partner's copy of that half; after 6 steps lane l holds the wave's sum of value l.
+    const int lane = threadIdx.x & (FQL_WAVE - 1);
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) {
+        const bool up = (lane & h) != 0;
+#pragma unroll
+        for (int k = 0; k < h; ++k) {
+            const float keep = up ? acc[k + h] : acc[k];
+            const float send = up ? acc[k] : acc[k + h];
+            acc[k] = keep + __shfl_xor(send, h, FQL_WAVE);
+        }
+    }
+    red[threadIdx.x / FQL_WAVE][lane] = acc[0];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float s = red[0][lane];
+#pragma unroll
+        for (int k = 1; k < NW; ++k) s += red[k][lane];
+        const int i = lane / R, j = lane % R;
+        if (i < n) out[(size_t)(row0 + i) * R + j] = scale * s;
+    }
+}
+
+// ---- expand: out[t][c] = in[t][c] + scale * V[t][0:R] . W_e[c][0:R].  One workgroup = up to 8 rows of one expert x
+//      256 * VEC columns (grid.y); V of the tile is staged in LDS and read as broadcasts.
+template <int R, bool CR, int VEC>
+__global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
+    const float *__restrict__ V, const float *__restrict__ w, const int32_t *__restrict__ tpe,
+    const int32_t *__restrict__ offs, const float *in, float *out, int E, int T, int C, float scale, int slots)
+{
+    constexpr int TM = FQL_LORA_EXPAND_ROWS;
+    __shared__ __attribute__((aligned(16))) float vs[TM][R];
+    __shared__ int flag[FQL_LORA_COVER_ROWS];
+    const int c = ((int)blockIdx.y * FQL_LORA_EXPAND_THREADS + (int)threadIdx.x) * VEC;
+    if ((int)blockIdx.x >= slots) {                              // rows no expert owns: copy `in` (or zeros)
+        const int r0 = ((int)blockIdx.x - slots) * FQL_LORA_COVER_ROWS;
+        cover_flags(tpe, offs, E, T, r0, flag);
+        if (c >= C || in == out) return;
+        for (int i = 0; i < FQL_LORA_COVER_ROWS && r0 + i < T; ++i) {
+            if (flag[i]) continue;
+            float y[VEC];
+            if (in) load_vec<VEC>(in + (size_t)(r0 + i) * C + c, y);
+            else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) y[v] = 0.f;
+            }
+            store_vec<VEC>(out + (size_t)(r0 + i) * C + c, y);
+        }
+        return;
+    }
+    int e, row0, n;
+    if (!tile_rows<TM>(tpe, offs, E, T, (int)blockIdx.x, e, row0, n)) return;
+    for (int i = threadIdx.x; i < TM * R; i += FQL_LORA_EXPAND_THREADS)
+        vs[i / R][i % R] = (i / R) < n ? V[(size_t)(row0 + i / R) * R + i % R] : 0.f;
+    __syncthreads();
+    if (c >= C) return;
+    const float *we = w + (size_t)e * R * C;
+
+    float acc[TM][VEC];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[i][v] = 0.f;
+#pragma unroll 2
+    for (int j0 = 0; j0 < R; j0 += 4) {
+        float wv[4][VEC];                                        // W_e[c + v][j0 + jj]
+        if constexpr (!CR) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) load_vec<VEC>(we + (size_t)(j0 + jj) * C + c, wv[jj]);
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                float t[4];
+                load_vec<4>(we + (size_t)(c + v) * R + j0, t);
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) wv[jj][v] = t[jj];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const float4 vv = *reinterpret_cast<const float4 *>(&vs[i][j0]);
+            const float vj[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[i][v] = fmaf(vj[jj], wv[jj][v], acc[i][v]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        if (i >= n) break;
+        const size_t o = (size_t)(row0 + i) * C + c;
+        float y[VEC];
+        if (in) load_vec<VEC>(in + o, y);
+        else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) y[v] = 0.f;
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[v] = fmaf(scale, acc[i][v], y[v]);
+        store_vec<VEC>(out + o, y);
+    }
+}
+
+// ---- grad: D_e = scale * P_e^T V_e.  grid = (column blocks, E).  A lane owns VEC columns x RJ = min(R, 16) ranks (the
+//      R / RJ rank groups split the wave's lanes); the 8 waves split the expert's rows (wave w: lo + w + 8 i) and their
+//      partials meet in a fixed tree through LDS.  Experts without rows write zeros.
+template <int R, bool CR, int VEC>
+__global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
+    const float *__restrict__ P, const float *__restrict__ V, const int32_t *__restrict__ tpe,
+    const int32_t *__restrict__ offs, float *__restrict__ D, int T, int C, float scale)
+{
+    constexpr int RJ = R < 16 ? R : 16;
+    constexpr int JG = R / RJ;
+    constexpr int LPG = FQL_WAVE / JG;                           // lanes per rank group
+    constexpr int NA = VEC * RJ;                                 // accumulators per lane
+    constexpr int NW = FQL_LORA_GRAD_THREADS / FQL_WAVE;
+    constexpr int U = 4;                                         // rows in flight per wave
+    __shared__ float red[NW / 2][NA][FQL_WAVE];
+
+    const int e = blockIdx.y;
+    int lo = 0, hi = T;
+    if (tpe != nullptr) expert_rows(tpe, offs, e, T, lo, hi);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / FQL_WAVE);
+    const int lane = threadIdx.x & (FQL_WAVE - 1);
+    const int jg = lane / LPG, j0 = jg * RJ;
+    const int c = ((int)blockIdx.x * LPG + lane % LPG) * VEC;
+    const bool live = c < C;
+    const int cc = live ? c : 0;                                 // dead lanes read column 0 and never store
+
+    float acc[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) acc[i] = 0.f;
+    int t = lo + wave;
+    for (; t + (U - 1) * NW < hi; t += U * NW) {
+        float p[U][VEC], v[U][RJ];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            load_vec<VEC>(P + (size_t)(t + u * NW) * C + cc, p[u]);
+#pragma unroll
+            for (int j = 0; j < RJ; j += 4) {
+                float4 x = *reinterpret_cast<const float4 *>(V + (size_t)(t + u * NW) * R + j0 + j);
+                v[u][j] = x.x; v[u][j + 1] = x.y; v[u][j + 2] = x.z; v[u][j + 3] = x.w;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int a = 0; a < VEC; ++a)
+#pragma unroll
+                for (int j = 0; j < RJ; ++j) acc[a * RJ + j] = fmaf(p[u][a], v[u][j], acc[a * RJ + j]);
+    }
+    for (; t < hi; t += NW) {
+        float p[VEC], v[RJ];
+        load_vec<VEC>(P + (size_t)t * C + cc, p);
+#pragma unroll
+        for (int j = 0; j < RJ; j += 4) {
+            float4 x = *reinterpret_cast<const float4 *>(V + (size_t)t * R + j0 + j);
+            v[j] = x.x; v[j + 1] = x.y; v[j + 2] = x.z; v[j + 3] = x.w;
+        }
+#pragma unroll
+        for (int a = 0; a < VEC; ++a)
+#pragma unroll
+            for (int j = 0; j < RJ; ++j) acc[a * RJ + j] = fmaf(p[a], v[j], acc[a * RJ + j]);
+    }
+    // fixed tree: at width h, waves [h, 2h) hand their partials to waves [0, h)
+#pragma unroll
+    for (int h = NW / 2; h >= 1; h >>= 1) {
+        if (wave >= h && wave < 2 * h) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i) red[wave - h][i][lane] = acc[i];
+        }
+        __syncthreads();
+        if (wave < h) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i) acc[i] += red[wave][i][lane];
+        }
+        __syncthreads();
+    }
+    if (wave != 0 || !live) return;
+    float *de = D + (size_t)e * R * C;
+    if constexpr (CR) {                                          // D_e[c + a][j0 .. j0 + RJ)
+#pragma unroll
+        for (int a = 0; a < VEC; ++a)
+#pragma unroll
+            for (int j = 0; j < RJ; j += 4) {
+                const float y[4] = {scale * acc[a * RJ + j], scale * acc[a * RJ + j + 1], scale * acc[a * RJ + j + 2],
+                                    scale * acc[a * RJ + j + 3]};
+                store_vec<4>(de + (size_t)(c + a) * R + j0 + j, y);
+            }
+    } else {                                                     // D_e[j0 + j][c .. c + VEC)
+#pragma unroll
+        for (int j = 0; j < RJ; ++j) {
+            float y[VEC];
+#pragma unroll
+            for (int a = 0; a < VEC; ++a) y[a] = scale * acc[a * RJ + j];
+            store_vec<VEC>(de + (size_t)(j0 + j) * C + c, y);
+        }
+    }
+}
+
+}  // namespace lora

@@ -1,0 +1,118 @@
+"""Trainable low-rank adapters (LoRA) on the frozen INT4 layers: ``y = W_q x + (alpha / r) * B (A x)``.
+
+``LoRAQuantizedLinear`` and ``LoRAMoEINT4`` keep the base layer's buffers (and state_dict keys) unchanged and add two
+float32 parameters in PEFT's layout, ``lora_A`` [r, K] / [E, r, K] and ``lora_B`` [N, r] / [E, N, r].  They are the
+module's only parameters, so an optimiser built from ``parameters()`` trains the adapters alone.  On the GPU the adapter
+runs in the segmented kernels of csrc/fql_lora.h (ops.linear_lora_forward / ops.moe_lora_forward); on the CPU
+``LoRAQuantizedLinear`` is plain torch.  INTEGRATION.md section 6 lists what is out of scope.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn as nn
+
+from .module import QuantizedLinear
+from .moe import MoEINT4
+from .ops import LORA_RANKS
+
+
+def _check_rank(rank):
+    if rank not in LORA_RANKS:
+        raise ValueError(f"rank must be one of {LORA_RANKS}, got {rank!r}")
+
+
+class LoRAQuantizedLinear(QuantizedLinear):
+    def __init__(self, in_features: int, out_features: int, rank: int, alpha: float | None = None,
+                 precision: str = "default", bias: bool = False, group_size: int | None = None):
+        super().__init__(in_features, out_features, precision=precision, bias=bias, group_size=group_size)
+        _check_rank(rank)
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scaling = self.alpha / rank
+        self.lora_A = nn.Parameter(torch.empty(rank, in_features, dtype=torch.float32))
+        self.lora_B = nn.Parameter(torch.empty(out_features, rank, dtype=torch.float32))
+        self.reset_lora_parameters()
+
+    def reset_lora_parameters(self):
+        """PEFT's initialisation: A kaiming-uniform (a = sqrt(5)), B zeros -- a fresh adapter adds nothing."""
+        nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
+        nn.init.zeros_(self.lora_B)
+
+    @classmethod
+    def from_quantized(cls, layer: QuantizedLinear, rank: int, alpha: float | None = None) -> "LoRAQuantizedLinear":
+        """Wrap an existing ``QuantizedLinear``; the new module shares its buffers (no copy)."""
+        module = cls(layer.in_features, layer.out_features, rank, alpha, precision=layer.precision,
+                     bias=layer.bias is not None, group_size=layer.group_size)
+        module.packed_weights = layer.packed_weights
+        module.scales = layer.scales
+        module.zero_points = layer.zero_points
+        if layer.bias is not None:
+            module.bias = layer.bias
+        dev = layer.packed_weights.device
+        module.lora_A.data = module.lora_A.data.to(dev)
+        module.lora_B.data = module.lora_B.data.to(dev)
+        return module
+
+    def adapter_state_dict(self):
+        return {k: v for k, v in self.state_dict().items() if k in ("lora_A", "lora_B")}
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.is_cuda:
+            from . import ops
+            return ops.linear_lora_forward(x, self.packed_weights, self.scales, self.zero_points, self.lora_A,
+                                           self.lora_B, self.scaling, precision=self.precision, bias=self.bias)
+        return super().forward(x) + self.scaling * ((x @ self.lora_A.t()) @ self.lora_B.t())
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, rank={self.rank}, alpha={self.alpha:g}"
+
+
+class LoRAMoEINT4(MoEINT4):
+    def __init__(self, num_experts, hidden_dim, ffn_dim, rank: int, alpha: float | None = None,
+                 precision: str = "default"):
+        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision)
+        _check_rank(rank)
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scaling = self.alpha / rank
+        self.lora_A = nn.Parameter(torch.empty(num_experts, rank, hidden_dim, dtype=torch.float32))
+        self.lora_B = nn.Parameter(torch.empty(num_experts, ffn_dim, rank, dtype=torch.float32))
+        self.reset_lora_parameters()
+
+    def reset_lora_parameters(self):
+        """PEFT's initialisation per expert (fan-in = hidden_dim): A kaiming-uniform (a = sqrt(5)), B zeros."""
+        with torch.no_grad():
+            for e in range(self.num_experts):
+                nn.init.kaiming_uniform_(self.lora_A[e], a=math.sqrt(5))
+        nn.init.zeros_(self.lora_B)
+
+    @classmethod
+    def from_quantized(cls, layer: MoEINT4, rank: int, alpha: float | None = None) -> "LoRAMoEINT4":
+        """Wrap an existing ``MoEINT4``; the new module shares its buffers (no copy)."""
+        module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision)
+        module.packed_weights = layer.packed_weights
+        module.scales = layer.scales
+        module.zero_points = layer.zero_points
+        dev = layer.packed_weights.device
+        module.lora_A.data = module.lora_A.data.to(dev)
+        module.lora_B.data = module.lora_B.data.to(dev)
+        return module
+
+    def adapter_state_dict(self):
+        return {k: v for k, v in self.state_dict().items() if k in ("lora_A", "lora_B")}
+
+    def forward(self, inputs, expert_ids, tokens_per_expert, input_offsets):
+        """inputs ``[T, K]`` float32 on the GPU, rows grouped by expert -> ``[T, N]`` float32 (GPU only, as MoEINT4)."""
+        del expert_ids
+        if not inputs.is_cuda:
+            raise RuntimeError("LoRAMoEINT4 runs on the GPU only (inputs must be a CUDA tensor)")
+        from . import ops
+        return ops.moe_lora_forward(self.packed_weights, self.scales, self.zero_points, inputs, self.lora_A,
+                                    self.lora_B, self.scaling, tokens_per_expert, input_offsets,
+                                    precision=self.precision)
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "
+                f"rank={self.rank}, alpha={self.alpha:g}")

@@ -970,3 +970,287 @@ class _CombineFn(torch.autograd.Function):
         if gw is not None and w.dtype != torch.float32:
             gw = gw.to(w.dtype)
         return gy, None, gw, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Low-rank adapters (LoRA) on the INT4 layers: y = W_q x + scaling * B (A x), with float32 lora_A [r, K] / [E, r, K] and
+# lora_B [N, r] / [E, N, r] (PEFT's layout).  The segmented kernels of csrc/fql_lora.h run the adapter for every expert
+# in one launch each, from the device-side expert table of the grouped GEMM.
+# ---------------------------------------------------------------------------------------------------------------------
+
+LORA_RANKS = (4, 8, 16, 32, 64)          # ranks the kernels are built for (csrc/fql_lora.hip)
+_LORA_LAYOUTS = {"rc": _native.LORA_RC, "cr": _native.LORA_CR}
+
+
+def _lora_layout(layout):
+    try:
+        return _LORA_LAYOUTS[layout]
+    except KeyError:
+        raise ValueError(f"layout must be 'rc' ([E, r, C]) or 'cr' ([E, C, r]), got {layout!r}") from None
+
+
+def _lora_rows(t, name, dev):
+    if not t.is_cuda or t.device != dev:
+        raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise RuntimeError(f"{name} must be a float32 2-D tensor (the adapter path is float32 only)")
+    return t.contiguous()
+
+
+def _lora_table(tokens_per_expert, input_offsets, E, dev):
+    """(tpe, offs) as int32 on ``dev``, or (None, None) for one segment of all rows (E == 1)."""
+    if tokens_per_expert is None and input_offsets is None:
+        if E != 1:
+            raise RuntimeError("tokens_per_expert and input_offsets are required when there is more than one expert")
+        return None, None
+    if tokens_per_expert is None or input_offsets is None:
+        raise RuntimeError("tokens_per_expert and input_offsets must be given together")
+    for name, t in (("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+        if t.numel() != E:
+            raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
+    return (tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous(),
+            input_offsets.to(device=dev, dtype=torch.int32).contiguous())
+
+
+def _lora_weight(w, layout, C, dev, name="w"):
+    """Adapter weight [r, C] / [C, r] (one segment) or [E, r, C] / [E, C, r] -> (contiguous 16-byte aligned tensor, E, r)."""
+    if not w.is_cuda or w.device != dev:
+        raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+    if w.dtype != torch.float32 or w.dim() not in (2, 3):
+        raise RuntimeError(f"{name} must be a float32 [r, C] / [C, r] or [E, r, C] / [E, C, r] tensor")
+    w3 = w.unsqueeze(0) if w.dim() == 2 else w
+    E, a, b = w3.shape
+    r, c = (a, b) if _lora_layout(layout) == _native.LORA_RC else (b, a)
+    if c != C:
+        raise RuntimeError(f"{name} has {c} columns where the activations have {C}")
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    w3 = w3.contiguous()
+    if w3.data_ptr() % 16:
+        w3 = w3.clone()
+    return w3, E, r
+
+
+def lora_shrink(input, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
+    """Segmented ``out[t] = scale * input[t] @ W_e^T`` -> [T, r] float32: ``weight`` [E, r, C] (``layout='rc'``, e.g.
+    lora_A) or [E, C, r] (``'cr'``, e.g. lora_B), 2-D for one segment.  Rows no expert covers are zero."""
+    dev = input.device
+    x = _lora_rows(input, "input", dev)
+    T, C = x.shape
+    w, E, r = _lora_weight(weight, layout, C, dev, "weight")
+    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    out = torch.empty((T, r), dtype=torch.float32, device=dev)
+    if T == 0:
+        return out
+    if C == 0:
+        return out.zero_()
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_lora_shrink_f32(x.data_ptr(), w.data_ptr(), _lora_layout(layout),
+                                               None if tpe is None else tpe.data_ptr(),
+                                               None if offs is None else offs.data_ptr(), out.data_ptr(), E, T, C, r,
+                                               float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_shrink_f32")
+    return out
+
+
+def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=None, scale=1.0, input=None, out=None):
+    """Segmented ``out[t] = input[t] + scale * v[t] @ W_e^T`` -> [T, C] float32: ``v`` [T, r], ``weight`` [E, C, r]
+    (``layout='cr'``, e.g. lora_B) or [E, r, C] (``'rc'``, e.g. lora_A).  ``input`` None starts from zero; ``out`` may be
+    ``input`` (in place; it must then be contiguous).  Rows no expert covers get ``input`` (or zero)."""
+    dev = v.device
+    vv = _lora_rows(v, "v", dev)
+    T = vv.shape[0]
+    ref = input if input is not None else out
+    if ref is None:
+        raise RuntimeError("lora_expand needs `input` or `out` to know the number of columns")
+    C = ref.shape[-1]
+    w, E, r = _lora_weight(weight, layout, C, dev, "weight")
+    if vv.shape[1] != r:
+        raise RuntimeError(f"v has {vv.shape[1]} columns where the adapter rank is {r}")
+    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    inp = None
+    if input is not None:
+        if tuple(input.shape) != (T, C):
+            raise RuntimeError("input must be [T, C]")
+        inp = input if (out is not None and input is out) else _lora_rows(input, "input", dev)
+    if out is None:
+        out = torch.empty((T, C), dtype=torch.float32, device=dev)
+    elif (not out.is_cuda or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (T, C)
+          or not out.is_contiguous()):
+        raise RuntimeError("out must be a contiguous CUDA float32 [T, C] tensor on the inputs' device")
+    if T == 0 or C == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_lora_expand_f32(vv.data_ptr(), w.data_ptr(), _lora_layout(layout),
+                                               None if tpe is None else tpe.data_ptr(),
+                                               None if offs is None else offs.data_ptr(),
+                                               None if inp is None else inp.data_ptr(), out.data_ptr(), E, T, C, r,
+                                               float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_expand_f32")
+    return out
+
+
+def lora_grad(p, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
+    """Segment reduction ``D_e = scale * sum_{t of e} p[t]^T v[t]`` per expert: ``p`` [T, C], ``v`` [T, r] ->
+    [E, C, r] (``layout='cr'``: dB) or [E, r, C] (``'rc'``: dA).  Experts without rows get zeros."""
+    dev = p.device
+    pp = _lora_rows(p, "p", dev)
+    vv = _lora_rows(v, "v", dev)
+    T, C = pp.shape
+    r = vv.shape[1]
+    if vv.shape[0] != T:
+        raise RuntimeError("p and v must have the same number of rows")
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    E = int(num_experts)
+    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    lay = _lora_layout(layout)
+    shape = (E, C, r) if lay == _native.LORA_CR else (E, r, C)
+    if T == 0 or C == 0 or E == 0:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    d = torch.empty(shape, dtype=torch.float32, device=dev)
+    if vv.data_ptr() % 16:
+        vv = vv.clone()
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_lora_grad_f32(pp.data_ptr(), vv.data_ptr(), None if tpe is None else tpe.data_ptr(),
+                                             None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T, C, r,
+                                             float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_grad_f32")
+    return d
+
+
+def _lora_check_adapters(lora_A, lora_B, K, N, E):
+    """lora_A [r, K] / lora_B [N, r] (E == 1: 2-D) or [E, r, K] / [E, N, r]: float32 CUDA."""
+    for name, t in (("lora_A", lora_A), ("lora_B", lora_B)):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be a float32 CUDA tensor (the adapter path is float32 only)")
+    want_dim = 2 if E is None else 3
+    if lora_A.dim() != want_dim or lora_B.dim() != want_dim:
+        raise RuntimeError("lora_A / lora_B must be [r, K] / [N, r] for a linear layer, [E, r, K] / [E, N, r] for MoE")
+    r = lora_A.shape[-2]
+    if lora_A.shape[-1] != K or tuple(lora_B.shape[-2:]) != (N, r) or (E is not None and (lora_A.shape[0] != E
+                                                                                        or lora_B.shape[0] != E)):
+        raise RuntimeError(f"lora_A must be [{'E, ' if E else ''}r, {K}] and lora_B [{'E, ' if E else ''}{N}, r]")
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+
+
+def _linear_lora_apply(x2, packed, scales, zps, lora_A, lora_B, scaling, precision, bias):
+    """Base forward, then U = x A^T and y += scaling * U B^T in place.  Returns (y, U)."""
+    y = linear_forward(x2, packed, scales, zps, precision=precision, bias=bias)
+    u = lora_shrink(x2, lora_A, "rc")
+    lora_expand(u, lora_B, "cr", scale=scaling, input=y, out=y)
+    return y, u
+
+
+def linear_lora_forward(x, packed, scales, zps, lora_A, lora_B, scaling, precision="default", bias=None):
+    """INT4 linear plus a low-rank adapter: ``x @ W_q^T (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``, float32
+    ``x`` [K] or [B, K], ``lora_A`` [r, K], ``lora_B`` [N, r].  Differentiable in ``x``, ``lora_A``, ``lora_B`` and
+    ``bias`` (the INT4 weights are frozen); the backward reuses the fused input gradient of the base layer."""
+    if x.dtype != torch.float32:
+        raise RuntimeError("linear_lora_forward: x must be float32 (16-bit activations are not supported on the "
+                           "adapter path)")
+    if x.dim() not in (1, 2):
+        raise RuntimeError("x must be 1-D or 2-D")
+    K = x.shape[-1]
+    _lora_check_adapters(lora_A, lora_B, K, packed.shape[0], None)
+    if _wants_grad(x, lora_A, lora_B, bias):
+        return _LinearLoRAFn.apply(x, lora_A, lora_B, bias, packed, scales, zps, float(scaling), precision)
+    x2 = x.unsqueeze(0) if x.dim() == 1 else x
+    y, _ = _linear_lora_apply(x2, packed, scales, zps, lora_A, lora_B, float(scaling), precision, bias)
+    return y.squeeze(0) if x.dim() == 1 else y
+
+
+def moe_lora_forward(packed, scales, zps, inputs, lora_A, lora_B, scaling, tokens_per_expert, input_offsets,
+                     precision="default"):
+    """Grouped INT4 GEMM plus a per-expert low-rank adapter: for the rows t of expert e,
+    ``y[t] = inputs[t] @ W_e^T + scaling * (inputs[t] @ lora_A[e]^T) @ lora_B[e]^T``; rows no expert covers are zero.
+    ``lora_A`` [E, r, K], ``lora_B`` [E, N, r] float32.  Per-row INT4 weights only.  Differentiable in ``inputs``,
+    ``lora_A`` and ``lora_B``."""
+    if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
+        raise RuntimeError("inputs must be a CUDA float32 [T, K] tensor (the adapter path is float32 only)")
+    if packed.dim() != 3 or scales.dim() != 2:
+        raise RuntimeError("moe_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points [E, N]")
+    E, N = packed.shape[0], packed.shape[1]
+    _lora_check_adapters(lora_A, lora_B, inputs.shape[1], N, E)
+    if _wants_grad(inputs, lora_A, lora_B):
+        return _MoELoRAFn.apply(inputs, lora_A, lora_B, packed, scales, zps, tokens_per_expert, input_offsets,
+                                float(scaling), precision)
+    y, _ = _moe_lora_apply(packed, scales, zps, inputs, lora_A, lora_B, float(scaling), tokens_per_expert,
+                           input_offsets, precision)
+    return y
+
+
+def _moe_lora_apply(packed, scales, zps, inputs, lora_A, lora_B, scaling, tpe, offs, precision):
+    y = moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
+    u = lora_shrink(inputs, lora_A, "rc", tpe, offs)
+    lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y, out=y)
+    return y, u
+
+
+class _LinearLoRAFn(torch.autograd.Function):
+    """Base INT4 linear + adapter in one node.  Saves x and U = x A^T ([B, r]); nothing dequantised."""
+
+    @staticmethod
+    def forward(ctx, x, lora_A, lora_B, bias, packed, scales, zps, scaling, precision):
+        x2 = (x.unsqueeze(0) if x.dim() == 1 else x).contiguous()
+        y, u = _linear_lora_apply(x2, packed, scales, zps, lora_A, lora_B, scaling, precision, bias)
+        ctx.save_for_backward(x2, u, lora_A, lora_B, packed, scales, zps)
+        ctx.scaling, ctx.precision, ctx.x_dim = scaling, precision, x.dim()
+        return y.squeeze(0) if x.dim() == 1 else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, u, lora_A, lora_B, packed, scales, zps = ctx.saved_tensors
+        need_x, need_A, need_B, need_b = ctx.needs_input_grad[:4]
+        g = gy.to(torch.float32).reshape(-1, gy.shape[-1]).contiguous()
+        gx = gA = gB = gb = None
+        if need_x or need_A:
+            du = lora_shrink(g, lora_B, "cr", scale=ctx.scaling)                # dU = s G B
+            if need_x:
+                if scales.dim() == 2 and scales.shape[1] > 1:
+                    gx = group_backward_input(g, packed, scales, zps)
+                else:
+                    gx = linear_backward_input(g, packed, scales, zps, precision=ctx.precision)
+                lora_expand(du, lora_A, "rc", input=gx, out=gx)                 # dX += dU A
+                gx = gx.reshape(-1) if ctx.x_dim == 1 else gx
+            if need_A:
+                gA = lora_grad(x2, du, "rc")[0]                                  # dA = dU^T X
+        if need_B:
+            gB = lora_grad(g, u, "cr", scale=ctx.scaling)[0]                     # dB = s G^T U
+        if need_b:
+            gb = g.sum(0)
+        return gx, gA, gB, gb, None, None, None, None, None
+
+
+class _MoELoRAFn(torch.autograd.Function):
+    """Grouped INT4 GEMM + per-expert adapter in one node.  Saves inputs and U ([T, r]) and the expert table."""
+
+    @staticmethod
+    def forward(ctx, inputs, lora_A, lora_B, packed, scales, zps, tpe, offs, scaling, precision):
+        y, u = _moe_lora_apply(packed, scales, zps, inputs, lora_A, lora_B, scaling, tpe, offs, precision)
+        ctx.save_for_backward(inputs.contiguous(), u, lora_A, lora_B, packed, scales, zps, tpe, offs)
+        ctx.scaling, ctx.precision = scaling, precision
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, u, lora_A, lora_B, packed, scales, zps, tpe, offs = ctx.saved_tensors
+        need_x, need_A, need_B = ctx.needs_input_grad[:3]
+        E = packed.shape[0]
+        g = gy.to(torch.float32).contiguous()
+        gx = gA = gB = None
+        if need_x or need_A:
+            du = lora_shrink(g, lora_B, "cr", tpe, offs, scale=ctx.scaling)
+            if need_x:
+                gx = moe_backward_input(packed, scales, zps, g, tpe, offs, precision=ctx.precision)
+                lora_expand(du, lora_A, "rc", tpe, offs, input=gx, out=gx)
+            if need_A:
+                gA = lora_grad(x, du, "rc", E, tpe, offs)
+        if need_B:
+            gB = lora_grad(g, u, "cr", E, tpe, offs, scale=ctx.scaling)
+        return gx, gA, gB, None, None, None, None, None, None, None

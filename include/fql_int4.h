@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 220 /* 0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 230 /* 0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -388,6 +388,49 @@ FQL_API int fql_moe_bwd_input_f32(const uint8_t *packed, const float *scales, co
                                   int T, int K, int N, int precision, void *ws, size_t ws_bytes, void *stream);
 FQL_API int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
                                 float *grad_y, float *grad_weights, int T, int top_k, int N, int rows, void *stream);
+
+/* ---- low-rank adapters (LoRA) on the INT4 layers: csrc/fql_lora.h ----
+ * Segmented float32 kernels for y = W_q x + scale * B (A x), per expert e over the rows of its range.  The adapter
+ * weight of a call is `w` (or the output `d` of the gradient), stored in one of two layouts:
+ *   FQL_LORA_RC: [E][r][C] (lora_A, [r, K] per expert)        FQL_LORA_CR: [E][C][r] (lora_B, [N, r] per expert)
+ * and read as W_e[j][c] whichever way it is stored.
+ *
+ * fql_lora_shrink_f32: out[t][j] = scale * sum_c in[t][c] * W_e[j][c]            in [T][C] -> out [T][r]
+ *   (forward U = X A_e^T with w = lora_A, RC; backward dU = s G B_e with w = lora_B, CR).  Rows no expert covers
+ *   get zeros.
+ * fql_lora_expand_f32: out[t][c] = in[t][c] + scale * sum_j v[t][j] * W_e[c][j]  v [T][r] -> out [T][C]
+ *   (forward Y += s U B_e^T with w = lora_B, CR; backward dX += dU A_e with w = lora_A, RC).  in == out is allowed
+ *   (in place); in == NULL starts from zero.  Rows no expert covers are copied from `in` (zeroed when in == NULL,
+ *   left alone in place).
+ * fql_lora_grad_f32: d_e[c][j] = scale * sum_{t of e} p[t][c] * v[t][j], stored [E][C][r] (d_layout FQL_LORA_CR:
+ *   dB_e = s G_e^T U_e) or [E][r][C] (FQL_LORA_RC: dA_e = dU_e^T X_e).  Experts without rows get zeros; rows no
+ *   expert covers contribute nothing.
+ *
+ * All three: E experts, T rows, C columns (K or N), rank r in {4, 8, 16, 32, 64}; float32 operands and float32
+ * accumulation on the vector FMA units.  tokens_per_expert / input_offsets are the int32 device table of the grouped
+ * GEMM (never read back; ranges must not overlap and are clamped into [0, T)); both NULL with E == 1 is one segment
+ * of all T rows (the linear layer: no table on the device).  No atomics and no workspace: every output element is
+ * written once in a fixed order, so two runs are bitwise equal, and an expert's rows (and its d_e) equal bit for bit
+ * the E == 1 call on its rows alone.  Rows of C floats are streamed 16 bytes per lane when C % 4 == 0 and the [T][C]
+ * operands are 16-byte aligned (8 bytes when C % 2 == 0, else 4).
+ * Errors, in this order and all before any HIP call: r not in the list, a layout other than FQL_LORA_RC /
+ * FQL_LORA_CR, a negative dimension, E > 65535, or T * C, T * r or E * C * r past 2^31 -> FQL_ERR_BAD_SHAPE;
+ * T == 0 -> FQL_OK with nothing done (also C == 0 for expand and grad, and E == 0 for grad); a NULL data pointer,
+ * only one of the two table pointers, or no table with E != 1 -> FQL_ERR_NULL_POINTER; `w` (shrink, expand) or
+ * `v` and `d` (grad) not 16-byte aligned -> FQL_ERR_ALIGNMENT; FQL_ERR_LAUNCH.  The Python surface is
+ * ops.lora_shrink / lora_expand / lora_grad and the differentiable ops.linear_lora_forward / moe_lora_forward
+ * (INTEGRATION.md section 6). */
+#define FQL_LORA_RC 0
+#define FQL_LORA_CR 1
+FQL_API int fql_lora_shrink_f32(const float *in, const float *w, int w_layout, const int32_t *tokens_per_expert,
+                                const int32_t *input_offsets, float *out, int E, int T, int C, int r, float scale,
+                                void *stream);
+FQL_API int fql_lora_expand_f32(const float *v, const float *w, int w_layout, const int32_t *tokens_per_expert,
+                                const int32_t *input_offsets, const float *in, float *out, int E, int T, int C, int r,
+                                float scale, void *stream);
+FQL_API int fql_lora_grad_f32(const float *p, const float *v, const int32_t *tokens_per_expert,
+                              const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
+                              float scale, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
