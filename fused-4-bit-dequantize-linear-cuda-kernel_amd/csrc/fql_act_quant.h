@@ -445,9 +445,12 @@ __device__ __forceinline__ void act_rows(
     //      (limbs + L planes, delta2 = delta + T, rowsum2 = rowsum + L*T).  The GEMM adds
     //      delta2 * (sum_k q R - zp * rowsum2) for those rows (fql_gemm_i8.h), which takes the per-row block
     //      fixed point from 8L-1 to 16L-2 bits: one outlier channel no longer coarsens the rest of its row.
-    //      A row is flagged when the predicted relative output error of its 8L-1 bits,
-    //      sqrt(K / 12) / ||x / delta||_2, exceeds 1e-6 (L = 3) / 2.5e-4 (L = 2): half of the stated bound of
-    //      the mode (tests/helpers.py) resp. a quarter of the north-star 1e-3.  randn rows are never flagged.
+    //      A row is flagged when the predicted relative error of its 8L-1 bits, sqrt(K / 12) / ||x / delta||_2,
+    //      exceeds 1e-6 (L = 3) / 2.5e-4 (L = 2): half of the stated bound of the mode (tests/helpers.py) resp. a
+    //      quarter of the north-star 1e-3.  randn rows are never flagged.  The prediction is relative to the row's
+    //      input norm; it is the output row's relative error when that row does not cancel, and a row whose result
+    //      cancels (||x_t W|| << ||x_t|| ||W||_F / sqrt(K), e.g. a zero-point term far from the centre of q that
+    //      nearly vanishes for that row) shows it amplified by that ratio, as any rounding of the inputs would.
     constexpr bool RES = (L >= 2);
     constexpr int RBITS = 8 * L - 1;
     auto emit = [&](auto resid_tag, int (&sums)[L], float &ssq, bool store) {

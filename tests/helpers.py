@@ -147,3 +147,91 @@ def act_residual_reference(x, L):
         digits[l] = d
     delta2 = np.where(flag, delta.astype(np.float64) * 2.0 ** -rb, 0.0).astype(np.float32)
     return flag, digits, delta2, digits.sum(axis=2)
+
+
+# ---- device-side float64 references (torch only: no fql_* kernel is called) -------------------------------------------
+def dequant_f64(packed, scales, zps):
+    """float64 weights ``(q - zp) * s`` [N, K] of one INT4 matrix, on the tensors' device: ``packed`` [N, K/2] uint8
+    (byte j of a row = q[2j] | q[2j+1] << 4), ``scales`` / ``zps`` [N] (per row) or [N, G] (per group of K / G)."""
+    import torch
+    p = packed.to(torch.int16)
+    q = torch.stack((p & 15, p >> 4), dim=-1).reshape(packed.shape[0], -1).to(torch.float64)
+    s, z = scales.to(q.device, torch.float64), zps.to(q.device, torch.float64)
+    if s.dim() == 2 and s.shape[1] > 1:                      # per group along K
+        G = s.shape[1]
+        return ((q.reshape(q.shape[0], G, -1) - z[..., None]) * s[..., None]).reshape(q.shape)
+    s, z = s.reshape(-1, 1), z.reshape(-1, 1)
+    return (q - z) * s
+
+
+def row_rel_err(got, ref):
+    """max over rows t of ||got_t - ref_t|| / ||ref_t|| (float64).  A row whose reference is exactly zero must be
+    exactly zero in ``got`` (its error is then 0, otherwise inf).  Accepts numpy arrays or torch tensors."""
+    import torch
+    g = torch.as_tensor(got).to(torch.float64)
+    r = torch.as_tensor(ref).to(device=g.device, dtype=torch.float64)
+    g, r = g.reshape(g.shape[0], -1), r.reshape(r.shape[0], -1)
+    if g.shape[0] == 0:
+        return 0.0
+    num = torch.linalg.vector_norm(g - r, dim=1)
+    den = torch.linalg.vector_norm(r, dim=1)
+    zero = den == 0
+    err = torch.where(zero, torch.where(num == 0, 0.0, float("inf")).to(num), num / torch.where(zero, 1.0, den))
+    return float(err.max())
+
+
+def misaligned(t, floats):
+    """A contiguous copy of ``t`` whose data pointer sits ``floats`` elements (for float32: 1, 2 or 3 = 4, 8 or 12 bytes)
+    past a 16-byte boundary: the public ops keep it as it is (it is contiguous), so the kernels see an unaligned base."""
+    import torch
+    per16 = 16 // t.element_size()                           # elements per 16 bytes
+    buf = torch.empty(t.numel() + per16 + floats, dtype=t.dtype, device=t.device)
+    start = (-(buf.data_ptr() // t.element_size()) + floats) % per16
+    out = buf[start:start + t.numel()].view(t.shape)
+    out.copy_(t)
+    assert out.is_contiguous() and out.data_ptr() % 16 == floats * t.element_size()
+    return out
+
+
+# ---- shared by the GPU test files of the backward and adapter paths ---------------------------------------------------
+def fq():
+    import fused_int4_amd
+    return fused_int4_amd
+
+
+def ops():
+    from fused_int4_amd import ops as o
+    return o
+
+
+def rel_fro_dev(got, ref):
+    """``rel_fro`` for torch tensors on the device, in float64."""
+    import torch
+    got, ref = got.double(), ref.to(got.device).double()
+    den = torch.linalg.vector_norm(ref)
+    return float(torch.linalg.vector_norm(got - ref) / (den if den > 0 else 1.0))
+
+
+def expert_table(counts, gaps=None, tail=0, device="cuda"):
+    """(tokens_per_expert, input_offsets, T) int32 on ``device``: ``gaps[e]`` uncovered rows in front of expert e,
+    ``tail`` uncovered rows after the last."""
+    import torch
+    gaps = gaps or [0] * len(counts)
+    offs, pos = [], 0
+    for c, gp in zip(counts, gaps):
+        pos += gp
+        offs.append(pos)
+        pos += c
+    return (torch.tensor(counts, dtype=torch.int32, device=device),
+            torch.tensor(offs, dtype=torch.int32, device=device), pos + tail)
+
+
+def clipped_ranges(tokens_per_expert, input_offsets, T):
+    """The device's clipping of an expert table (csrc/fql_common.h expert_range, csrc/fql_lora.h expert_rows): rows
+    [lo, hi) of expert e with lo = clamp(offset, 0, T), hi = clamp(offset + count, lo, T) (empty for count <= 0)."""
+    out = []
+    for c, o in zip(tokens_per_expert.tolist(), input_offsets.tolist()):
+        lo = min(max(o, 0), T)
+        hi = min(max(o + c, lo), T) if c > 0 else lo
+        out.append((lo, hi))
+    return out
