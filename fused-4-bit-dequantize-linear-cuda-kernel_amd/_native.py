@@ -77,6 +77,11 @@ _SYMBOLS = {
     "fql_lora_expand_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4
                             + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
     "fql_lora_grad_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_lora_gated_shrink_f32": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+                                  + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_lora_gated_grad_f32": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5
+                                + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_swiglu_bwd_f32": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]),
     "fql_moe_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 6
                     + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }

@@ -87,7 +87,7 @@ __device__ __forceinline__ float act_widen(unsigned short h)
 // GATE (float32 input only): the source row is [gate (K) | up (K)] and the value that gets quantised is
 // silu(gate[k]) * up[k] -- the elementwise step between the two GEMMs of a gated FFN expert fused into the
 // second GEMM's pre-pass, so the [T, K] hidden activation is never materialised.
-__device__ __forceinline__ float act_silu_mul(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+// (act_silu_mul itself lives in fql_common.h: the adapter kernels of fql_lora.h form the same h from the same function.)
 
 // ---- pieces shared by the pre-pass kernels (this file and fql_act_f8.h)
 // Coverage workgroups (MoE entry points only): zero-fill the rows of `out` no expert covers, 256 rows each

@@ -122,6 +122,11 @@ __device__ __forceinline__ void store_out4(void *out, int kind, size_t row_elems
     }
 }
 
+// Hidden activation of a gated FFN expert, h = silu(g) * u.  ONE definition for every kernel that forms h on the fly:
+// the down GEMM's activation pre-pass (fql_act_quant.h, GATE) and the gated adapter loads (fql_lora.h, GATE), so the
+// adapter sees bit for bit the h the INT4 GEMM consumed.
+__device__ __forceinline__ float act_silu_mul(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+
 // Bijective XCD-aware remap of a 1-D grid: blocks b and b+8 share an XCD (round-robin dispatch),
 // so give each XCD a contiguous range of logical tile ids.  Speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk)

@@ -21,6 +21,14 @@
 //     fixed tree through LDS.  An expert's result is therefore the same bits whether it is computed in a grouped call
 //     or alone with E = 1.
 // Rows covered by no expert: shrink writes zeros, expand copies `in` (zeros when in == NULL; nothing when in place).
+//
+// GATE (shrink and grad): the streamed operand is the [T][2C] gate|up tensor of a gated FFN expert and the value that
+// enters the sums is h[t][c] = act_silu_mul(gate_up[t][c], gate_up[t][C + c]) -- the function the down GEMM's
+// activation pre-pass calls (fql_common.h), so the down adapter sees the h the INT4 GEMM consumed and the [T][C]
+// hidden activation is never written.  Only the operand load differs: tiles, lanes and reduction orders are the same
+// code, and every promise above holds for the gated variants.
+//
+// swiglu_bwd_kernel: the elementwise backward of h = silu(g) * u, one streaming pass over [T][2F] + [T][F] -> [T][2F].
 #pragma once
 #include "fql_common.h"
 
@@ -54,6 +62,22 @@ __device__ __forceinline__ void store_vec(float *p, const float (&v)[VEC])
     else if constexpr (VEC == 2) { t.x = v[0]; t.y = v[1]; }
     else { t = v[0]; }
     *reinterpret_cast<typename vec_t<VEC>::type *>(p) = t;
+}
+
+// VEC operand values of row t at column c: the floats of a [T][C] tensor, or with GATE the hidden activation formed
+// from the gate half (columns [0, C)) and the up half ([C, 2C)) of row t of a [T][2C] gate|up tensor.
+template <int VEC, bool GATE>
+__device__ __forceinline__ void load_operand(const float *p, int t, int C, int c, float (&v)[VEC])
+{
+    if constexpr (GATE) {
+        float g[VEC], u[VEC];
+        load_vec<VEC>(p + (size_t)t * 2 * C + c, g);
+        load_vec<VEC>(p + (size_t)t * 2 * C + C + c, u);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = act_silu_mul(g[i], u[i]);
+    } else {
+        load_vec<VEC>(p + (size_t)t * C + c, v);
+    }
 }
 
 // Rows [lo, hi) of expert e, clamped into [0, T) (a table that points outside the tensor never reaches memory).
@@ -108,8 +132,8 @@ __device__ __forceinline__ void cover_flags(const int32_t *tpe, const int32_t *o
 }
 
 // ---- shrink: out[t][0:R] = scale * in[t][:] . W_e^T.  One workgroup = TM = 64 / R rows of one expert, 512 lanes
-//      across the columns; grid = tile slots (+ coverage workgroups when there is a table).
-template <int R, bool CR, int VEC>
+//      across the columns; grid = tile slots (+ coverage workgroups when there is a table).  GATE: `in` is [T][2C].
+template <int R, bool CR, int VEC, bool GATE>
 __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
     const float *__restrict__ in, const float *__restrict__ w, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, float *__restrict__ out, int E, int T, int C, float scale, int slots)
@@ -140,7 +164,7 @@ __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
         float x[TM][VEC];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            if (i < n) load_vec<VEC>(in + (size_t)(row0 + i) * C + c, x[i]);
+            if (i < n) load_operand<VEC, GATE>(in, row0 + i, C, c, x[i]);
             else {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) x[i][v] = 0.f;
@@ -277,8 +301,8 @@ __global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
 
 // ---- grad: D_e = scale * P_e^T V_e.  grid = (column blocks, E).  A lane owns VEC columns x RJ = min(R, 16) ranks (the
 //      R / RJ rank groups split the wave's lanes); the 8 waves split the expert's rows (wave w: lo + w + 8 i) and their
-//      partials meet in a fixed tree through LDS.  Experts without rows write zeros.
-template <int R, bool CR, int VEC>
+//      partials meet in a fixed tree through LDS.  Experts without rows write zeros.  GATE: P is [T][2C].
+template <int R, bool CR, int VEC, bool GATE>
 __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
     const float *__restrict__ P, const float *__restrict__ V, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, float *__restrict__ D, int T, int C, float scale)
@@ -309,7 +333,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
         float p[U][VEC], v[U][RJ];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            load_vec<VEC>(P + (size_t)(t + u * NW) * C + cc, p[u]);
+            load_operand<VEC, GATE>(P, t + u * NW, C, cc, p[u]);
 #pragma unroll
             for (int j = 0; j < RJ; j += 4) {
                 float4 x = *reinterpret_cast<const float4 *>(V + (size_t)(t + u * NW) * R + j0 + j);
@@ -325,7 +349,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
     }
     for (; t < hi; t += NW) {
         float p[VEC], v[RJ];
-        load_vec<VEC>(P + (size_t)t * C + cc, p);
+        load_operand<VEC, GATE>(P, t, C, cc, p);
 #pragma unroll
         for (int j = 0; j < RJ; j += 4) {
             float4 x = *reinterpret_cast<const float4 *>(V + (size_t)t * R + j0 + j);
@@ -370,6 +394,33 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
             store_vec<VEC>(de + (size_t)(j0 + j) * C + c, y);
         }
     }
+}
+
+// ---- swiglu backward: dgu[t] = [dg | du] with sigma = 1 / (1 + exp(-g)), dg = dh u sigma (1 + g (1 - sigma)),
+//      du = dh g sigma.  One lane per VEC columns of one row, every row (no expert table: rows no expert covers carry
+//      dh = 0 and get zeros).  g very negative: expf overflows to +inf, sigma = 0 and both gradients are (signed) zero.
+#define FQL_SWIGLU_BWD_THREADS 256
+template <int VEC>
+__global__ __launch_bounds__(FQL_SWIGLU_BWD_THREADS) void swiglu_bwd_kernel(
+    const float *__restrict__ gu, const float *__restrict__ dh, float *__restrict__ dgu, int T, int F)
+{
+    const int per_row = F / VEC;
+    const long long q = (long long)blockIdx.x * FQL_SWIGLU_BWD_THREADS + threadIdx.x;
+    if (q >= (long long)T * per_row) return;
+    const int t = (int)(q / per_row), c = (int)(q % per_row) * VEC;
+    const size_t o = (size_t)t * 2 * F + c;
+    float g[VEC], u[VEC], d[VEC], dg[VEC], du[VEC];
+    load_vec<VEC>(gu + o, g);
+    load_vec<VEC>(gu + o + F, u);
+    load_vec<VEC>(dh + (size_t)t * F + c, d);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const float sig = 1.0f / (1.0f + expf(-g[i]));
+        dg[i] = d[i] * u[i] * (sig * (1.0f + g[i] * (1.0f - sig)));
+        du[i] = d[i] * (g[i] * sig);
+    }
+    store_vec<VEC>(dgu + o, dg);
+    store_vec<VEC>(dgu + o + F, du);
 }
 
 }  // namespace lora

@@ -5,6 +5,10 @@ float32 parameters in PEFT's layout, ``lora_A`` [r, K] / [E, r, K] and ``lora_B`
 module's only parameters, so an optimiser built from ``parameters()`` trains the adapters alone.  On the GPU the adapter
 runs in the segmented kernels of csrc/fql_lora.h (ops.linear_lora_forward / ops.moe_lora_forward); on the CPU
 ``LoRAQuantizedLinear`` is plain torch.  INTEGRATION.md section 6 lists what is out of scope.
+
+``LoRAQuantizedMoEFFN`` puts an adapter on each projection of the gated experts of ``QuantizedMoEFFN``: one on the
+stacked gate|up weight (one ``A`` shared by gate and up, a ``[2F, r]`` ``B``: PEFT's shape for a fused ``gate_up_proj``)
+and one on the down weight (ops.moe_ffn_lora_forward).
 """
 from __future__ import annotations
 
@@ -14,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .module import QuantizedLinear
-from .moe import MoEINT4
+from .moe import MoEINT4, QuantizedMoEFFN
 from .ops import LORA_RANKS
 
 
@@ -112,6 +116,67 @@ class LoRAMoEINT4(MoEINT4):
         return ops.moe_lora_forward(self.packed_weights, self.scales, self.zero_points, inputs, self.lora_A,
                                     self.lora_B, self.scaling, tokens_per_expert, input_offsets,
                                     precision=self.precision)
+
+    def extra_repr(self) -> str:
+        return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "
+                f"rank={self.rank}, alpha={self.alpha:g}")
+
+
+_FFN_ADAPTERS = ("gate_up_lora_A", "gate_up_lora_B", "down_lora_A", "down_lora_B")
+
+
+class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
+    """``down(silu(gate(x)) * up(x))`` per expert with ``gate_up = W_gu x + s B_gu (A_gu x)`` and
+    ``y = W_d h + s B_d (A_d h)``, ``s = alpha / rank``.  The INT4 buffers are frozen; the four adapters are the only
+    parameters."""
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
+                 precision: str = "default"):
+        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision)
+        _check_rank(rank)
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scaling = self.alpha / rank
+        E, H, F = num_experts, hidden_dim, ffn_dim
+        self.gate_up_lora_A = nn.Parameter(torch.empty(E, rank, H, dtype=torch.float32))
+        self.gate_up_lora_B = nn.Parameter(torch.empty(E, 2 * F, rank, dtype=torch.float32))
+        self.down_lora_A = nn.Parameter(torch.empty(E, rank, F, dtype=torch.float32))
+        self.down_lora_B = nn.Parameter(torch.empty(E, H, rank, dtype=torch.float32))
+        self.reset_lora_parameters()
+
+    def reset_lora_parameters(self):
+        """PEFT's initialisation per expert (fan-in = hidden_dim / ffn_dim): A kaiming-uniform (a = sqrt(5)), B zeros."""
+        with torch.no_grad():
+            for e in range(self.num_experts):
+                nn.init.kaiming_uniform_(self.gate_up_lora_A[e], a=math.sqrt(5))
+                nn.init.kaiming_uniform_(self.down_lora_A[e], a=math.sqrt(5))
+        nn.init.zeros_(self.gate_up_lora_B)
+        nn.init.zeros_(self.down_lora_B)
+
+    @classmethod
+    def from_quantized(cls, layer: QuantizedMoEFFN, rank: int, alpha: float | None = None) -> "LoRAQuantizedMoEFFN":
+        """Wrap an existing ``QuantizedMoEFFN``; the new module shares its buffers (no copy)."""
+        module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision)
+        for name, buf in layer.named_buffers():
+            setattr(module, name, buf)
+        dev = layer.gate_up_packed.device
+        for name in _FFN_ADAPTERS:
+            p = getattr(module, name)
+            p.data = p.data.to(dev)
+        return module
+
+    def adapter_state_dict(self):
+        return {k: v for k, v in self.state_dict().items() if k in _FFN_ADAPTERS}
+
+    def forward(self, inputs, tokens_per_expert, input_offsets):
+        """inputs ``[T, H]`` float32 on the GPU, rows grouped by expert -> ``[T, H]`` float32 (GPU only)."""
+        if not inputs.is_cuda:
+            raise RuntimeError("LoRAQuantizedMoEFFN runs on the GPU (the product path has no CPU fallback)")
+        from . import ops
+        return ops.moe_ffn_lora_forward(self.gate_up_packed, self.gate_up_scales, self.gate_up_zero_points,
+                                        self.down_packed, self.down_scales, self.down_zero_points, inputs,
+                                        self.gate_up_lora_A, self.gate_up_lora_B, self.down_lora_A, self.down_lora_B,
+                                        self.scaling, tokens_per_expert, input_offsets, precision=self.precision)
 
     def extra_repr(self) -> str:
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "

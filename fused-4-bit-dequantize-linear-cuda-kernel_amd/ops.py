@@ -1254,3 +1254,171 @@ class _MoELoRAFn(torch.autograd.Function):
         if need_B:
             gB = lora_grad(g, u, "cr", E, tpe, offs, scale=ctx.scaling)
         return gx, gA, gB, None, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Adapters on the gated FFN experts (QuantizedMoEFFN): y = W_d h + s B_d (A_d h), h = silu(g) * u, [g | u] = W_gu x +
+# s B_gu (A_gu x).  h is never written: the down adapter's shrink and weight gradient form it from gate_up with the
+# function the down GEMM's pre-pass uses (csrc/fql_common.h act_silu_mul), and the backward of the gate is one
+# streaming kernel.
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _gate_up_rows(gate_up, dev):
+    g = _lora_rows(gate_up, "gate_up", dev)
+    if g.shape[1] % 2:
+        raise RuntimeError("gate_up must be [T, 2C] (gate | up)")
+    return g, g.shape[0], g.shape[1] // 2
+
+
+def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
+    """``lora_shrink`` on the hidden activation of a gated FFN expert without materialising it:
+    ``out[t] = scale * (silu(gate_up[t, :C]) * gate_up[t, C:]) @ W_e^T`` -> [T, r]; ``gate_up`` [T, 2C] float32."""
+    dev = gate_up.device
+    g, T, C = _gate_up_rows(gate_up, dev)
+    w, E, r = _lora_weight(weight, layout, C, dev, "weight")
+    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    out = torch.empty((T, r), dtype=torch.float32, device=dev)
+    if T == 0:
+        return out
+    if C == 0:
+        return out.zero_()
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_lora_gated_shrink_f32(g.data_ptr(), w.data_ptr(), _lora_layout(layout),
+                                                     None if tpe is None else tpe.data_ptr(),
+                                                     None if offs is None else offs.data_ptr(), out.data_ptr(), E, T,
+                                                     C, r, float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_gated_shrink_f32")
+    return out
+
+
+def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
+    """``lora_grad`` with ``p = silu(gate_up[:, :C]) * gate_up[:, C:]`` formed on the fly: ``gate_up`` [T, 2C],
+    ``v`` [T, r] -> [E, C, r] (``layout='cr'``) or [E, r, C] (``'rc'``: dA of the down adapter)."""
+    dev = gate_up.device
+    g, T, C = _gate_up_rows(gate_up, dev)
+    vv = _lora_rows(v, "v", dev)
+    r = vv.shape[1]
+    if vv.shape[0] != T:
+        raise RuntimeError("gate_up and v must have the same number of rows")
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    E = int(num_experts)
+    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    lay = _lora_layout(layout)
+    shape = (E, C, r) if lay == _native.LORA_CR else (E, r, C)
+    if T == 0 or C == 0 or E == 0:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    d = torch.empty(shape, dtype=torch.float32, device=dev)
+    if vv.data_ptr() % 16:
+        vv = vv.clone()
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_lora_gated_grad_f32(g.data_ptr(), vv.data_ptr(),
+                                                   None if tpe is None else tpe.data_ptr(),
+                                                   None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T,
+                                                   C, r, float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_gated_grad_f32")
+    return d
+
+
+def swiglu_backward(gate_up, dh):
+    """Backward of ``h = silu(g) * u`` in one pass: ``gate_up`` [T, 2F] = [g | u] and ``dh`` [T, F] float32 ->
+    ``[dg | du]`` [T, 2F] with ``dg = dh * u * silu'(g)``, ``du = dh * silu(g)``."""
+    dev = gate_up.device
+    g, T, F = _gate_up_rows(gate_up, dev)
+    d = _lora_rows(dh, "dh", dev)
+    if tuple(d.shape) != (T, F):
+        raise RuntimeError(f"dh must be [{T}, {F}] for gate_up [{T}, {2 * F}]")
+    out = torch.empty((T, 2 * F), dtype=torch.float32, device=dev)
+    if T == 0 or F == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = _native.lib().fql_swiglu_bwd_f32(g.data_ptr(), d.data_ptr(), out.data_ptr(), T, F, _stream_ptr(dev))
+    _native.check(rc, "fql_swiglu_bwd_f32")
+    return out
+
+
+def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps, inputs,
+                         gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert,
+                         input_offsets, precision="default"):
+    """Gated INT4 FFN experts with a low-rank adapter on each projection: for the rows t of expert e,
+    ``gu = W_gu x + s B_gu (A_gu x)``, ``h = silu(gu[:F]) * gu[F:]`` (never stored), ``y = W_d h + s B_d (A_d h)``; rows
+    no expert covers are zero.  ``inputs`` [T, H] float32, stacked gate|up weights [E, 2F, H/2], down weights
+    [E, H, F/2], ``gate_up_lora_A`` [E, r, H], ``gate_up_lora_B`` [E, 2F, r], ``down_lora_A`` [E, r, F],
+    ``down_lora_B`` [E, H, r].  Per-row INT4 weights only.  Differentiable (once) in ``inputs`` and the four adapters."""
+    if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
+        raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor (the adapter path is float32 only)")
+    if gate_up_packed.dim() != 3 or gate_up_scales.dim() != 2 or down_packed.dim() != 3 or down_scales.dim() != 2:
+        raise RuntimeError("moe_ffn_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points "
+                           "[E, N]")
+    E, F2, H = gate_up_packed.shape[0], gate_up_packed.shape[1], inputs.shape[1]
+    if F2 % 2 or tuple(down_packed.shape) != (E, H, F2 // 4):
+        raise RuntimeError("gate_up_packed must be [E, 2F, H/2] and down_packed [E, H, F/2]")
+    _lora_check_adapters(gate_up_lora_A, gate_up_lora_B, H, F2, E)
+    _lora_check_adapters(down_lora_A, down_lora_B, F2 // 2, H, E)
+    if down_lora_A.shape[1] != gate_up_lora_A.shape[1]:
+        raise RuntimeError("the gate_up and down adapters must have the same rank")
+    weights = (gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps)
+    adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
+    if _wants_grad(inputs, *adapters):
+        return _MoEFFNLoRAFn.apply(inputs, *adapters, *weights, tokens_per_expert, input_offsets, float(scaling),
+                                   precision)
+    return _moe_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets,
+                               precision)[0]
+
+
+def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision):
+    """Returns (y, gate_up, U_gu, U_d): both projections with their adapters expanded in place into the base outputs."""
+    gup, gus, guz, dp, ds, dz = weights
+    A_gu, B_gu, A_d, B_d = adapters
+    gate_up = moe_forward(gup, gus, guz, inputs, None, tpe, offs, precision=precision)
+    u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
+    lora_expand(u_gu, B_gu, "cr", tpe, offs, scale=scaling, input=gate_up, out=gate_up)
+    y = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision)
+    u_d = lora_gated_shrink(gate_up, A_d, "rc", tpe, offs)
+    lora_expand(u_d, B_d, "cr", tpe, offs, scale=scaling, input=y, out=y)
+    return y, gate_up, u_gu, u_d
+
+
+class _MoEFFNLoRAFn(torch.autograd.Function):
+    """The whole gated FFN block + its two adapters in one node.  Saves inputs [T, H], gate_up [T, 2F], U_gu and U_d
+    ([T, r]), the tables and the parameters: nothing of shape [T, F]."""
+
+    @staticmethod
+    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision):
+        x = inputs.contiguous()
+        y, gate_up, u_gu, u_d = _moe_ffn_lora_apply((gup, gus, guz, dp, ds, dz), x, (A_gu, B_gu, A_d, B_d), scaling,
+                                                    tpe, offs, precision)
+        ctx.save_for_backward(x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs)
+        ctx.scaling, ctx.precision = scaling, precision
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
+        need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
+        E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
+        g = gy.to(torch.float32).contiguous()
+        gx = gAgu = gBgu = gAd = gBd = None
+        if need_Bd:
+            gBd = lora_grad(g, u_d, "cr", E, tpe, offs, scale=s)                         # dB_d = s dY^T U_d
+        through = need_x or need_Agu or need_Bgu                                        # anything upstream of h
+        if through or need_Ad:
+            du_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dU_d = s dY B_d
+            if need_Ad:
+                gAd = lora_gated_grad(gate_up, du_d, "rc", E, tpe, offs)                 # dA_d = dU_d^T h
+        if through:
+            dh = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)            # dh = dY W_d
+            lora_expand(du_d, A_d, "rc", tpe, offs, input=dh, out=dh)                    #      + dU_d A_d
+            dgu = swiglu_backward(gate_up, dh)
+            del dh
+            if need_Bgu:
+                gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
+            if need_x or need_Agu:
+                du_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dU_gu = s dgu B_gu
+                if need_x:
+                    gx = moe_backward_input(gup, gus, guz, dgu, tpe, offs, precision=prec)
+                    lora_expand(du_gu, A_gu, "rc", tpe, offs, input=gx, out=gx)          # dx = dgu W_gu + dU_gu A_gu
+                if need_Agu:
+                    gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
+        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 10

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 230 /* 0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 240 /* 0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -431,6 +431,35 @@ FQL_API int fql_lora_expand_f32(const float *v, const float *w, int w_layout, co
 FQL_API int fql_lora_grad_f32(const float *p, const float *v, const int32_t *tokens_per_expert,
                               const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
                               float scale, void *stream);
+
+/* ---- adapters on the gated FFN experts (QuantizedMoEFFN): y = W_d h + s B_d (A_d h), h = silu(g) * u ----
+ * The hidden activation h [T][C] is never stored; the down adapter reads it from gate_up = [g | u] ([T][2C], the
+ * output of the fused gate|up projection) exactly as fql_moe_gated_fwd_f32 does: both call one device function, so
+ * the adapter and the INT4 GEMM see the same bits of h.
+ *
+ * fql_lora_gated_shrink_f32: fql_lora_shrink_f32 with in[t][c] = silu(gate_up[t][c]) * gate_up[t][C + c]
+ *   (forward U_d = h A_d^T with w = down lora_A, RC).
+ * fql_lora_gated_grad_f32: fql_lora_grad_f32 with p[t][c] formed the same way (dA_d = dU_d^T h, RC).
+ *   Both: same kernels, tiles and reduction orders as the plain entry points (a compile-time flag on the operand
+ *   load), so their bitwise promises hold; same arguments, checks, order and codes, with 2 * T * C added to the
+ *   sizes that must stay below 2^31.  Both halves of a row are streamed once, 16 bytes per lane when gate_up,
+ *   gate_up + C and the pitch 2 C allow (8 when they allow 8, else 4).
+ * fql_swiglu_bwd_f32: dgate_up[t] = [dg | du] from gate_up [T][2F] and dh [T][F]:
+ *   sigma = 1 / (1 + exp(-g)), dg = dh u sigma (1 + g (1 - sigma)), du = dh g sigma.  One streaming pass over every
+ *   row (no expert table), 16-byte accesses when F % 4 == 0 and the three pointers are 16-byte aligned.  Finite for
+ *   every finite g (g very negative: sigma = 0, both gradients 0).  Errors, in this order: T < 0, F < 0 or
+ *   2 * T * F past 2^31 -> FQL_ERR_BAD_SHAPE; T == 0 or F == 0 -> FQL_OK with nothing done; a NULL pointer ->
+ *   FQL_ERR_NULL_POINTER; dgate_up == gate_up -> FQL_ERR_BAD_SHAPE (not in place); FQL_ERR_LAUNCH.
+ * All three: one launch, no workspace, no allocation, no host synchronisation, no atomics, graph-capturable.  The
+ * Python surface is ops.lora_gated_shrink / lora_gated_grad / swiglu_backward and the differentiable
+ * ops.moe_ffn_lora_forward. */
+FQL_API int fql_lora_gated_shrink_f32(const float *gate_up, const float *w, int w_layout,
+                                      const int32_t *tokens_per_expert, const int32_t *input_offsets, float *out, int E,
+                                      int T, int C, int r, float scale, void *stream);
+FQL_API int fql_lora_gated_grad_f32(const float *gate_up, const float *v, const int32_t *tokens_per_expert,
+                                    const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
+                                    float scale, void *stream);
+FQL_API int fql_swiglu_bwd_f32(const float *gate_up, const float *dh, float *dgate_up, int T, int F, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
