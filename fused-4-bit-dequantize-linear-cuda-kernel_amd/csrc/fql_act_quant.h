@@ -218,7 +218,7 @@ static __device__ unsigned long long fql_trace_act[16 * 16];   // (one copy per 
 // runs it more than once synchronises in between.
 // WT: every global store goes straight to device-coherent memory (sc1): the one-launch form's consumers sit on other XCDs,
 // whose L2s are not coherent with this one's, and a release fence instead (L2 write-back) cost 10-20 us per workgroup.
-// CS (float32 input only; the backward pre-pass of fql_bwd.h): every loaded element is first multiplied by the column
+// CS (the backward pre-pass of fql_bwd.h; any input type, widened first): every loaded element is first multiplied by the column
 // scale cs_scale[e][k] of its row's expert e (one float32 rounding), and the row's float correction
 // sum_k x[k] * cs_scale[e][k] * f[e][k], f = zp - clamp(rint(zp), -112, 112) (cs_zp = the zero points), is written to
 // the plane delta[DSETS * T + t] (the row-weight plane of the forward, unused by the backward).  The expert of each row is
@@ -246,7 +246,7 @@ __device__ __forceinline__ void act_rows(
     __shared__ __attribute__((aligned(16))) float s_ssq[R_][16];
     __shared__ int s_flag[R_];
     static_assert(!F8OUT || L == 1, "fp8 activations are one byte plane");
-    static_assert(!CS || (IN == 0 && !GATE && !F8OUT && !WT), "column-scaled rows: float32 input, int8 limbs");
+    static_assert(!CS || (!GATE && !F8OUT && !WT), "column-scaled rows: plain input, int8 limbs");
     __shared__ int s_e[CS ? R_ : 1];
     __shared__ __attribute__((aligned(16))) float s_cor[CS ? R_ : 1][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -300,20 +300,6 @@ __device__ __forceinline__ void act_rows(
                 } else if (IN == 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xv[j][q] = *reinterpret_cast<const v4f *>(src + 16 * q);
-                    if constexpr (CS) {
-                        const int kc = k0 < K ? k0 : 0;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const v4f s4 = *reinterpret_cast<const v4f *>(csr + kc + 4 * q);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) xv[j][q][i] = xv[j][q][i] * s4[i];
-                            if (first && k0 < K) {
-                                const v4f z4 = *reinterpret_cast<const v4f *>(czr + kc + 4 * q);
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) cor = fmaf(xv[j][q][i], cs_frac(z4[i]), cor);
-                            }
-                        }
-                    }
                 } else {                          // 16 halves = two 16-byte loads
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -322,6 +308,20 @@ __device__ __forceinline__ void act_rows(
                         for (int i = 0; i < 4; ++i) {
                             xv[j][2 * h + (i >> 1)][2 * (i & 1)] = act_widen<IN>((unsigned short)((uint32_t)raw[i] & 0xFFFFu));
                             xv[j][2 * h + (i >> 1)][2 * (i & 1) + 1] = act_widen<IN>((unsigned short)((uint32_t)raw[i] >> 16));
+                        }
+                    }
+                }
+                if constexpr (CS) {               // column scale (and the float correction) on the widened values
+                    const int kc = k0 < K ? k0 : 0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const v4f s4 = *reinterpret_cast<const v4f *>(csr + kc + 4 * q);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) xv[j][q][i] = xv[j][q][i] * s4[i];
+                        if (first && k0 < K) {
+                            const v4f z4 = *reinterpret_cast<const v4f *>(czr + kc + 4 * q);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) cor = fmaf(xv[j][q][i], cs_frac(z4[i]), cor);
                         }
                     }
                 }
@@ -334,12 +334,12 @@ __device__ __forceinline__ void act_rows(
                         float v = 0.0f;
                         if (k < K) {
                             if (IN == 0 && GATE) v = act_silu_mul(reinterpret_cast<const float *>(xr)[k], reinterpret_cast<const float *>(xr)[K + k]);
-                            else if (IN == 0 && CS) {
-                                v = reinterpret_cast<const float *>(xr)[k] * csr[k];
-                                if (first) cor = fmaf(v, cs_frac(czr[k]), cor);
-                            }
                             else if (IN == 0) v = reinterpret_cast<const float *>(xr)[k];
                             else v = act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]);
+                            if constexpr (CS) {
+                                v = v * csr[k];
+                                if (first) cor = fmaf(v, cs_frac(czr[k]), cor);
+                            }
                         }
                         xv[j][q][i] = v;
                     }

@@ -16,6 +16,10 @@
 // Heavy-tailed gradient rows get the pre-pass's residual limb set (delta2 = delta + T, limbs + L planes); a tile holding
 // such a row runs its contraction a second time on that set and adds delta2 * (...) for those rows only.
 //
+// Element types: grad_out may be float16 / bfloat16 (loaded as it is by the pre-pass, widened in registers) and grad_in
+// may be stored in either (one rounding to nearest even in the GEMM's epilogue); everything in between is the float32
+// path, so a 16-bit call is bit for bit the float32 call on the widened gradient, rounded once.
+//
 // Pre-pass (act_colscale_kernel): act_rows with CS = true: the limbs of g in the fragment-native layout of
 // fql_act_quant.h, contraction index n in the place of k.  The limb order (0,2,4,6,1,3,5,7) inside every aligned
 // group of 8 n is kept; the weight side follows it through the addresses of the transposed read (below).
@@ -45,17 +49,19 @@
 
 // ---- pre-pass: limbs of g = dY * s[e][:] (+ the per-row correction), coverage workgroups zero the rows of grad_in
 //      no expert owns
-template <int L, bool VEC, int AR>
+//      IN: element type of gy (FQL_DTYPE_*; 16-bit gradients are widened in registers before the multiply by s, so the
+//      limbs are the bits of the float32 call on the widened gradient); gx_es: bytes per element of gx (zero fill only)
+template <int L, bool VEC, int AR, int IN = 0>
 __global__ __launch_bounds__(256) void act_colscale_kernel(
-    const float *__restrict__ gy, float *__restrict__ delta, int32_t *__restrict__ rowsum, int8_t *__restrict__ limbs,
-    int T, int N, int KB, int MBT, int rblocks, float *__restrict__ gx, int K, const int32_t *__restrict__ tpe,
+    const void *__restrict__ gy, float *__restrict__ delta, int32_t *__restrict__ rowsum, int8_t *__restrict__ limbs,
+    int T, int N, int KB, int MBT, int rblocks, void *__restrict__ gx, int gx_es, int K, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, int E, const float *__restrict__ scales, const float *__restrict__ zps)
 {
     if ((int)blockIdx.x >= rblocks) {
-        act_zero_uncovered((int)blockIdx.x - rblocks, gx, 4, K, tpe, offs, E, T);
+        act_zero_uncovered((int)blockIdx.x - rblocks, gx, gx_es, K, tpe, offs, E, T);
         return;
     }
-    act_rows<L, VEC, 0, false, false, AR, false, true>(gy, nullptr, 0, delta, rowsum, limbs, T, N, KB, MBT, rblocks, tpe,
+    act_rows<L, VEC, IN, false, false, AR, false, true>(gy, nullptr, 0, delta, rowsum, limbs, T, N, KB, MBT, rblocks, tpe,
                                                        offs, E, nullptr, (int)blockIdx.x * AR, scales, zps);
 }
 
@@ -83,10 +89,11 @@ __device__ __forceinline__ void bwd_unpack16(uint32_t w0, uint32_t w1, uint32_t 
 
 // VW: K % 32 == 0 and a 16-byte aligned weight base, so every 16-byte chunk of a packed row is one aligned load;
 // otherwise the chunk is read byte by byte (odd K / 2: rows are not 4-byte aligned).
-template <int L, bool VW>
+// OUT: element type of `out` (FQL_DTYPE_*): the epilogue's store rounds once (store_out4, fql_common.h).
+template <int L, bool VW, int OUT = 0>
 __global__ __launch_bounds__(512, 2) void gemm_bwd_kernel(
     const int8_t *__restrict__ limbs, const float *__restrict__ delta, const uint8_t *__restrict__ packed,
-    const float *__restrict__ zps, float *__restrict__ out, const int32_t *__restrict__ tpe,
+    const float *__restrict__ zps, void *__restrict__ out, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, int E, int T, int K, int N, int Np, int MBT, int m_slots, int n_tiles)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bwd_kernel(
         // ---- epilogue: - sum_n g f, store rows t, columns k0 + (wn NF + j) 32 + 8 q' + 4 g + c
         if (row_ok) {
             const float cor = delta[(size_t)SETS * T + t];
-            const bool vec = ((K & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+            const bool vec = ((K & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0);
 #pragma unroll
             for (int j = 0; j < NF; ++j)
 #pragma unroll
@@ -296,8 +303,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bwd_kernel(
                     const int kc = k0 + (wn * NF + j) * 32 + 8 * q + 4 * g;
                     float v[4];
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = o[j][4 * q + c] - cor;
-                    if (kc < K) store_out4(out, 0, (size_t)t * K, kc, K, vec, v);
+                    for (int c = 0; c < 4; ++c) {
+                        v[c] = o[j][4 * q + c] - cor;
+                        // float16: round the float32 result, never a fused multiply-add rounded straight to float16
+                        // (v_fma_mixlo_f16 would: one rounding of the exact value, not Tensor.to(float16) of float32)
+                        if constexpr (OUT == 1) asm volatile("" : "+v"(v[c]));
+                    }
+                    if (kc < K) store_out4(out, OUT, (size_t)t * K, kc, K, vec, v);
                 }
         }
     }

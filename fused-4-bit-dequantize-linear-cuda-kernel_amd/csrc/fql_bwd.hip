@@ -1,5 +1,5 @@
 // libfql_int4.so, third translation unit: the input-gradient entry points (include/fql_int4.h,
-// fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32) over the kernels of fql_bwd.h.
+// fql_linear_bwd_input[_f32] / fql_moe_bwd_input[_f32]) over the kernels of fql_bwd.h.
 // Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
@@ -58,8 +58,12 @@ inline int compute_units()
     return n > 0 ? n : 8;
 }
 
-template <int L>
-int launch_bwd(const float *gy, const uint8_t *packed, const float *scales, const float *zps, float *gx,
+inline bool dtype_ok(int d) { return d == FQL_DTYPE_F32 || d == FQL_DTYPE_F16 || d == FQL_DTYPE_BF16; }
+inline int elem_bytes(int d) { return d == FQL_DTYPE_F32 ? 4 : 2; }
+
+// IN / OUT: element types of gy / gx (FQL_DTYPE_*)
+template <int L, int IN, int OUT>
+int launch_bwd(const void *gy, const uint8_t *packed, const float *scales, const float *zps, void *gx,
                const int32_t *tpe, const int32_t *offs, int E, int T, int K, int N, const BwdWorkspace &w, hipStream_t st)
 {
     const int Np = padded(N);
@@ -70,12 +74,13 @@ int launch_bwd(const float *gy, const uint8_t *packed, const float *scales, cons
     const bool single = vec && (long long)mblocks * FQL_MB <= 512;
     const int rblocks = single ? T : (T + ACT_ROWS - 1) / ACT_ROWS;
     const int zblocks = tpe != nullptr ? (T + 255) / 256 : 0;
-    void (*pre)(const float *, float *, int32_t *, int8_t *, int, int, int, int, int, float *, int, const int32_t *,
+    void (*pre)(const void *, float *, int32_t *, int8_t *, int, int, int, int, int, void *, int, int, const int32_t *,
                 const int32_t *, int, const float *, const float *) =
-        single ? act_colscale_kernel<L, true, 1> : (vec ? act_colscale_kernel<L, true, ACT_ROWS> : act_colscale_kernel<L, false, ACT_ROWS>);
+        single ? act_colscale_kernel<L, true, 1, IN>
+               : (vec ? act_colscale_kernel<L, true, ACT_ROWS, IN> : act_colscale_kernel<L, false, ACT_ROWS, IN>);
     (void)hipGetLastError();
     hipLaunchKernelGGL(pre, dim3(rblocks + zblocks), dim3(256), 0, st, gy, w.delta, w.rowsum, w.limbs, T, N, Np / FQL_KB, MBT,
-                       rblocks, gx, K, tpe, offs, E, scales, zps);
+                       rblocks, gx, elem_bytes(OUT), K, tpe, offs, E, scales, zps);
     if (hipGetLastError() != hipSuccess) return FQL_ERR_LAUNCH;
 
     const int m_slots = (tpe == nullptr) ? (T + BwdCfg::BM - 1) / BwdCfg::BM : (T + BwdCfg::BM - 1) / BwdCfg::BM + E;
@@ -83,7 +88,7 @@ int launch_bwd(const float *gy, const uint8_t *packed, const float *scales, cons
     const long long tiles = (long long)m_slots * n_tiles;
     const int grid = (int)(tiles < compute_units() ? tiles : compute_units());
     const bool vw = (K % 32 == 0) && aligned16(packed);
-    auto gemm = vw ? gemm_bwd_kernel<L, true> : gemm_bwd_kernel<L, false>;
+    auto gemm = vw ? gemm_bwd_kernel<L, true, OUT> : gemm_bwd_kernel<L, false, OUT>;
     hipLaunchKernelGGL(gemm, dim3(grid), dim3(BwdCfg::THREADS), 0, st, w.limbs, w.delta, packed, zps, gx, tpe, offs, E, T,
                        K, N, Np, MBT, m_slots, n_tiles);
     return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
@@ -108,15 +113,39 @@ size_t bwd_workspace_bytes(int E, int T, int K, int N, int precision)
     return bwd_carve(nullptr, L, T, E, padded(N)).bytes;
 }
 
-int bwd_entry(const float *grad_out, const uint8_t *packed, const float *scales, const float *zps,
-              const int32_t *tpe, const int32_t *offs, float *grad_in, int E, int T, int K, int N, int precision,
-              void *ws, size_t ws_bytes, void *stream, bool grouped)
+template <int L, int IN>
+int launch_bwd_out(int out_dtype, const void *gy, const uint8_t *packed, const float *scales, const float *zps, void *gx,
+                   const int32_t *tpe, const int32_t *offs, int E, int T, int K, int N, const BwdWorkspace &w, hipStream_t st)
+{
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return launch_bwd<L, IN, FQL_DTYPE_F32>(gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    case FQL_DTYPE_F16: return launch_bwd<L, IN, FQL_DTYPE_F16>(gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    default: return launch_bwd<L, IN, FQL_DTYPE_BF16>(gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    }
+}
+
+template <int L>
+int launch_bwd_types(int in_dtype, int out_dtype, const void *gy, const uint8_t *packed, const float *scales,
+                     const float *zps, void *gx, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int N,
+                     const BwdWorkspace &w, hipStream_t st)
+{
+    switch (in_dtype) {
+    case FQL_DTYPE_F32: return launch_bwd_out<L, FQL_DTYPE_F32>(out_dtype, gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    case FQL_DTYPE_F16: return launch_bwd_out<L, FQL_DTYPE_F16>(out_dtype, gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    default: return launch_bwd_out<L, FQL_DTYPE_BF16>(out_dtype, gy, packed, scales, zps, gx, tpe, offs, E, T, K, N, w, st);
+    }
+}
+
+int bwd_entry(const void *grad_out, int in_dtype, const uint8_t *packed, const float *scales, const float *zps,
+              const int32_t *tpe, const int32_t *offs, void *grad_in, int out_dtype, int E, int T, int K, int N,
+              int precision, void *ws, size_t ws_bytes, void *stream, bool grouped)
 {
     const int L = bwd_limbs(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
     if (E < 0 || T < 0 || K < 0 || N < 0) return FQL_ERR_BAD_SHAPE;
     if (K & 1) return FQL_ERR_ODD_K;
     if (N > FQL_BWD_MAX_N || E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return FQL_ERR_DTYPE;
     if (T == 0 || K == 0) return FQL_OK;
     if (!grad_in) return FQL_ERR_NULL_POINTER;
     if (N > 0 && E > 0 && (!grad_out || !packed || !scales || !zps || (grouped && (!tpe || !offs))))
@@ -128,12 +157,12 @@ int bwd_entry(const float *grad_out, const uint8_t *packed, const float *scales,
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (N == 0 || E == 0)                                     // empty contraction / no expert: the gradient is zero
-        return hipMemsetAsync(grad_in, 0, (size_t)T * K * sizeof(float), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+        return hipMemsetAsync(grad_in, 0, (size_t)T * K * elem_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
     const BwdWorkspace w = bwd_carve(ws, L, T, E, padded(N));
     switch (L) {
-    case 1: return launch_bwd<1>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
-    case 2: return launch_bwd<2>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
-    default: return launch_bwd<3>(grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    case 1: return launch_bwd_types<1>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    case 2: return launch_bwd_types<2>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    default: return launch_bwd_types<3>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
     }
 }
 
@@ -150,8 +179,16 @@ FQL_API int fql_linear_bwd_input_f32(const float *grad_out, const uint8_t *packe
                                      float *grad_in, int B, int K, int N, int precision, void *ws, size_t ws_bytes,
                                      void *stream)
 {
-    return bwd_entry(grad_out, packed, scales, zps, nullptr, nullptr, grad_in, 1, B, K, N, precision, ws, ws_bytes, stream,
-                     false);
+    return bwd_entry(grad_out, FQL_DTYPE_F32, packed, scales, zps, nullptr, nullptr, grad_in, FQL_DTYPE_F32, 1, B, K, N,
+                     precision, ws, ws_bytes, stream, false);
+}
+
+FQL_API int fql_linear_bwd_input(const void *grad_out, int grad_out_dtype, const uint8_t *packed, const float *scales,
+                                 const float *zps, void *grad_in, int grad_in_dtype, int B, int K, int N, int precision,
+                                 void *ws, size_t ws_bytes, void *stream)
+{
+    return bwd_entry(grad_out, grad_out_dtype, packed, scales, zps, nullptr, nullptr, grad_in, grad_in_dtype, 1, B, K, N,
+                     precision, ws, ws_bytes, stream, false);
 }
 
 FQL_API size_t fql_moe_bwd_workspace_bytes(int E, int T, int K, int N, int precision)
@@ -163,8 +200,17 @@ FQL_API int fql_moe_bwd_input_f32(const uint8_t *packed, const float *scales, co
                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, float *grad_in, int E,
                                   int T, int K, int N, int precision, void *ws, size_t ws_bytes, void *stream)
 {
-    return bwd_entry(grad_out, packed, scales, zps, tokens_per_expert, input_offsets, grad_in, E, T, K, N, precision, ws,
-                     ws_bytes, stream, true);
+    return bwd_entry(grad_out, FQL_DTYPE_F32, packed, scales, zps, tokens_per_expert, input_offsets, grad_in,
+                     FQL_DTYPE_F32, E, T, K, N, precision, ws, ws_bytes, stream, true);
+}
+
+FQL_API int fql_moe_bwd_input(const uint8_t *packed, const float *scales, const float *zps, const void *grad_out,
+                              int grad_out_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                              void *grad_in, int grad_in_dtype, int E, int T, int K, int N, int precision, void *ws,
+                              size_t ws_bytes, void *stream)
+{
+    return bwd_entry(grad_out, grad_out_dtype, packed, scales, zps, tokens_per_expert, input_offsets, grad_in,
+                     grad_in_dtype, E, T, K, N, precision, ws, ws_bytes, stream, true);
 }
 
 }  // extern "C"

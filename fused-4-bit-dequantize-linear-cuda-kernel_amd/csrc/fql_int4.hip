@@ -814,9 +814,21 @@ int fql_linear_fwd(const void *x, int in_dtype, const uint8_t *packed, const flo
                    int out_dtype, int B, int K, int N, int precision, void *workspace, size_t workspace_bytes,
                    void *stream)
 {
+    return fql_linear_bias_fwd(x, in_dtype, packed, scales, zps, nullptr, out, out_dtype, B, K, N, precision, workspace,
+                               workspace_bytes, stream);
+}
+
+// fql_linear_fwd with the optional bias of fql_linear_bias_fwd_f32 (the same epilogue add: the kernels take it already)
+int fql_linear_bias_fwd(const void *x, int in_dtype, const uint8_t *packed, const float *scales, const float *zps,
+                        const float *bias, void *out, int out_dtype, int B, int K, int N, int precision, void *workspace,
+                        size_t workspace_bytes, void *stream)
+{
     if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32)
-        return fql_linear_fwd_f32(static_cast<const float *>(x), packed, scales, zps, static_cast<float *>(out), B, K, N,
-                                  precision, workspace, workspace_bytes, stream);
+        return bias != nullptr
+                   ? fql_linear_bias_fwd_f32(static_cast<const float *>(x), packed, scales, zps, bias,
+                                             static_cast<float *>(out), B, K, N, precision, workspace, workspace_bytes, stream)
+                   : fql_linear_fwd_f32(static_cast<const float *>(x), packed, scales, zps, static_cast<float *>(out), B,
+                                        K, N, precision, workspace, workspace_bytes, stream);
     const int L = limbs_of(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
     if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
@@ -826,7 +838,7 @@ int fql_linear_fwd(const void *x, int in_dtype, const uint8_t *packed, const flo
     if (!x || !packed || !scales || !zps || !out) return FQL_ERR_NULL_POINTER;
     if (B <= g_gemv_max_rows || !mfma_eligible(L, B, 1, K, N, packed)) return FQL_ERR_DTYPE;   // 16-bit I/O exists on the MFMA path only
     return run_mfma(L, x, in_dtype, nullptr, 0, packed, scales, zps, out, out_dtype, nullptr, nullptr, 1, B, K, N,
-                    workspace, workspace_bytes, static_cast<hipStream_t>(stream), false, is_f8(precision));
+                    workspace, workspace_bytes, static_cast<hipStream_t>(stream), false, is_f8(precision), bias);
 }
 
 int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,

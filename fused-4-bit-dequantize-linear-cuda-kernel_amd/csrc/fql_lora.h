@@ -1,4 +1,5 @@
-// Segmented (per-expert, ragged) low-rank adapter kernels: float32 in, float32 out, float32 VALU FMAs.
+// Segmented (per-expert, ragged) low-rank adapter kernels: float32 VALU FMAs, float32 accumulators; the streamed [T][C]
+// operand is float32, float16 or bfloat16 (below, "Element types").
 //
 // For the rows t of expert e (rows [lo_e, hi_e), from tokens_per_expert / input_offsets on the device; one segment of
 // all T rows when the table is NULL), with rank R and a weight W_e stored [E][R][C] (FQL_LORA_RC) or [E][C][R]
@@ -22,7 +23,14 @@
 //     or alone with E = 1.
 // Rows covered by no expert: shrink writes zeros, expand copies `in` (zeros when in == NULL; nothing when in place).
 //
-// GATE (shrink and grad): the streamed operand is the [T][2C] gate|up tensor of a gated FFN expert and the value that
+// Element types (DT / DI / DO = FQL_DTYPE_F32 / _F16 / _BF16): the [T][C] operand -- `in` of shrink, `P` of grad, `in` and
+// `out` of expand, each on its own -- may be 16-bit.  A 16-bit element is widened in registers on load (exact) and a
+// 16-bit output is rounded once, to nearest even, on store (the helpers of fql_common.h, as Tensor.to(dtype) rounds).
+// Only the load and the store differ: VEC counts ELEMENTS, so the column-to-lane mapping, the tiles and every reduction
+// order are those of the float32 kernel at the same VEC, and a 16-bit call returns the bits of the float32 call on the
+// widened operand (rounded once, for expand).  [T][r] tensors, adapter weights and their gradients are always float32.
+//
+// GATE (shrink and grad; float32 only): the streamed operand is the [T][2C] gate|up tensor of a gated FFN expert and the value that
 // enters the sums is h[t][c] = act_silu_mul(gate_up[t][c], gate_up[t][C + c]) -- the function the down GEMM's
 // activation pre-pass calls (fql_common.h), so the down adapter sees the h the INT4 GEMM consumed and the [T][C]
 // hidden activation is never written.  Only the operand load differs: tiles, lanes and reduction orders are the same
@@ -64,19 +72,74 @@ __device__ __forceinline__ void store_vec(float *p, const float (&v)[VEC])
     *reinterpret_cast<typename vec_t<VEC>::type *>(p) = t;
 }
 
+// 16-bit elements: VEC of them in one load (8 / 4 / 2 bytes), widened / rounded in registers.
+template <int DT>
+__device__ __forceinline__ float widen16(unsigned short h)
+{
+    if constexpr (DT == 1) { _Float16 f; __builtin_memcpy(&f, &h, 2); return (float)f; }
+    else return __uint_as_float((uint32_t)h << 16);
+}
+template <int DT>
+__device__ __forceinline__ unsigned short round16(float f)
+{
+    if constexpr (DT == 1) {
+        // the float32 value first, in a register of its own: left to itself the compiler folds the preceding fma and this
+        // conversion into one v_fma_mixlo_f16, which rounds the exact fma once to float16 -- not the float32 result
+        // rounded to float16 that Tensor.to(float16) gives (the two differ in double-rounding cases)
+        asm volatile("" : "+v"(f));
+        return f32_to_f16_bits(f);
+    } else return f32_to_bf16_bits(f);
+}
+
+// VEC elements of type DT at element index i of `base` -> float32
+template <int VEC, int DT>
+__device__ __forceinline__ void load_elems(const void *base, size_t i, float (&v)[VEC])
+{
+    if constexpr (DT == 0) load_vec<VEC>(reinterpret_cast<const float *>(base) + i, v);
+    else {
+        const unsigned short *p = reinterpret_cast<const unsigned short *>(base) + i;
+        if constexpr (VEC == 4) {
+            const uint2 t = *reinterpret_cast<const uint2 *>(p);
+            v[0] = widen16<DT>((unsigned short)(t.x & 0xFFFFu)); v[1] = widen16<DT>((unsigned short)(t.x >> 16));
+            v[2] = widen16<DT>((unsigned short)(t.y & 0xFFFFu)); v[3] = widen16<DT>((unsigned short)(t.y >> 16));
+        } else if constexpr (VEC == 2) {
+            const uint32_t t = *reinterpret_cast<const uint32_t *>(p);
+            v[0] = widen16<DT>((unsigned short)(t & 0xFFFFu)); v[1] = widen16<DT>((unsigned short)(t >> 16));
+        } else { v[0] = widen16<DT>(*p); }
+    }
+}
+
+// float32 -> VEC elements of type DT at element index i of `base` (16-bit: one rounding to nearest even)
+template <int VEC, int DT>
+__device__ __forceinline__ void store_elems(void *base, size_t i, const float (&v)[VEC])
+{
+    if constexpr (DT == 0) store_vec<VEC>(reinterpret_cast<float *>(base) + i, v);
+    else {
+        unsigned short *p = reinterpret_cast<unsigned short *>(base) + i;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<uint2 *>(p) = make_uint2((uint32_t)round16<DT>(v[0]) | ((uint32_t)round16<DT>(v[1]) << 16),
+                                                       (uint32_t)round16<DT>(v[2]) | ((uint32_t)round16<DT>(v[3]) << 16));
+        } else if constexpr (VEC == 2) {
+            *reinterpret_cast<uint32_t *>(p) = (uint32_t)round16<DT>(v[0]) | ((uint32_t)round16<DT>(v[1]) << 16);
+        } else { *p = round16<DT>(v[0]); }
+    }
+}
+
 // VEC operand values of row t at column c: the floats of a [T][C] tensor, or with GATE the hidden activation formed
 // from the gate half (columns [0, C)) and the up half ([C, 2C)) of row t of a [T][2C] gate|up tensor.
-template <int VEC, bool GATE>
-__device__ __forceinline__ void load_operand(const float *p, int t, int C, int c, float (&v)[VEC])
+template <int VEC, bool GATE, int DT = 0>
+__device__ __forceinline__ void load_operand(const void *pv, int t, int C, int c, float (&v)[VEC])
 {
+    static_assert(!GATE || DT == 0, "the gated operand is float32");
     if constexpr (GATE) {
+        const float *p = reinterpret_cast<const float *>(pv);
         float g[VEC], u[VEC];
         load_vec<VEC>(p + (size_t)t * 2 * C + c, g);
         load_vec<VEC>(p + (size_t)t * 2 * C + C + c, u);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) v[i] = act_silu_mul(g[i], u[i]);
     } else {
-        load_vec<VEC>(p + (size_t)t * C + c, v);
+        load_elems<VEC, DT>(pv, (size_t)t * C + c, v);
     }
 }
 
@@ -133,9 +196,9 @@ __device__ __forceinline__ void cover_flags(const int32_t *tpe, const int32_t *o
 
 // ---- shrink: out[t][0:R] = scale * in[t][:] . W_e^T.  One workgroup = TM = 64 / R rows of one expert, 512 lanes
 //      across the columns; grid = tile slots (+ coverage workgroups when there is a table).  GATE: `in` is [T][2C].
-template <int R, bool CR, int VEC, bool GATE>
+template <int R, bool CR, int VEC, bool GATE, int DT = 0>
 __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
-    const float *__restrict__ in, const float *__restrict__ w, const int32_t *__restrict__ tpe,
+    const void *__restrict__ in, const float *__restrict__ w, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, float *__restrict__ out, int E, int T, int C, float scale, int slots)
 {
     constexpr int TM = 64 / R;
@@ -164,7 +227,7 @@ __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
         float x[TM][VEC];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            if (i < n) load_operand<VEC, GATE>(in, row0 + i, C, c, x[i]);
+            if (i < n) load_operand<VEC, GATE, DT>(in, row0 + i, C, c, x[i]);
             else {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) x[i][v] = 0.f;
@@ -220,10 +283,10 @@ __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
 
 // ---- expand: out[t][c] = in[t][c] + scale * V[t][0:R] . W_e[c][0:R].  One workgroup = up to 8 rows of one expert x
 //      256 * VEC columns (grid.y); V of the tile is staged in LDS and read as broadcasts.
-template <int R, bool CR, int VEC>
+template <int R, bool CR, int VEC, int DI = 0, int DO = 0>
 __global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
     const float *__restrict__ V, const float *__restrict__ w, const int32_t *__restrict__ tpe,
-    const int32_t *__restrict__ offs, const float *in, float *out, int E, int T, int C, float scale, int slots)
+    const int32_t *__restrict__ offs, const void *in, void *out, int E, int T, int C, float scale, int slots)
 {
     constexpr int TM = FQL_LORA_EXPAND_ROWS;
     __shared__ __attribute__((aligned(16))) float vs[TM][R];
@@ -236,12 +299,12 @@ __global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
         for (int i = 0; i < FQL_LORA_COVER_ROWS && r0 + i < T; ++i) {
             if (flag[i]) continue;
             float y[VEC];
-            if (in) load_vec<VEC>(in + (size_t)(r0 + i) * C + c, y);
+            if (in) load_elems<VEC, DI>(in, (size_t)(r0 + i) * C + c, y);
             else {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) y[v] = 0.f;
             }
-            store_vec<VEC>(out + (size_t)(r0 + i) * C + c, y);
+            store_elems<VEC, DO>(out, (size_t)(r0 + i) * C + c, y);
         }
         return;
     }
@@ -288,23 +351,23 @@ __global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
         if (i >= n) break;
         const size_t o = (size_t)(row0 + i) * C + c;
         float y[VEC];
-        if (in) load_vec<VEC>(in + o, y);
+        if (in) load_elems<VEC, DI>(in, o, y);
         else {
 #pragma unroll
             for (int v = 0; v < VEC; ++v) y[v] = 0.f;
         }
 #pragma unroll
         for (int v = 0; v < VEC; ++v) y[v] = fmaf(scale, acc[i][v], y[v]);
-        store_vec<VEC>(out + o, y);
+        store_elems<VEC, DO>(out, o, y);
     }
 }
 
 // ---- grad: D_e = scale * P_e^T V_e.  grid = (column blocks, E).  A lane owns VEC columns x RJ = min(R, 16) ranks (the
 //      R / RJ rank groups split the wave's lanes); the 8 waves split the expert's rows (wave w: lo + w + 8 i) and their
 //      partials meet in a fixed tree through LDS.  Experts without rows write zeros.  GATE: P is [T][2C].
-template <int R, bool CR, int VEC, bool GATE>
+template <int R, bool CR, int VEC, bool GATE, int DT = 0>
 __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
-    const float *__restrict__ P, const float *__restrict__ V, const int32_t *__restrict__ tpe,
+    const void *__restrict__ P, const float *__restrict__ V, const int32_t *__restrict__ tpe,
     const int32_t *__restrict__ offs, float *__restrict__ D, int T, int C, float scale)
 {
     constexpr int RJ = R < 16 ? R : 16;
@@ -333,7 +396,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
         float p[U][VEC], v[U][RJ];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            load_operand<VEC, GATE>(P, t + u * NW, C, cc, p[u]);
+            load_operand<VEC, GATE, DT>(P, t + u * NW, C, cc, p[u]);
 #pragma unroll
             for (int j = 0; j < RJ; j += 4) {
                 float4 x = *reinterpret_cast<const float4 *>(V + (size_t)(t + u * NW) * R + j0 + j);
@@ -349,7 +412,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
     }
     for (; t < hi; t += NW) {
         float p[VEC], v[RJ];
-        load_operand<VEC, GATE>(P, t, C, cc, p);
+        load_operand<VEC, GATE, DT>(P, t, C, cc, p);
 #pragma unroll
         for (int j = 0; j < RJ; j += 4) {
             float4 x = *reinterpret_cast<const float4 *>(V + (size_t)t * R + j0 + j);

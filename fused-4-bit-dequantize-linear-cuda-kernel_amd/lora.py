@@ -6,6 +6,10 @@ module's only parameters, so an optimiser built from ``parameters()`` trains the
 runs in the segmented kernels of csrc/fql_lora.h (ops.linear_lora_forward / ops.moe_lora_forward); on the CPU
 ``LoRAQuantizedLinear`` is plain torch.  INTEGRATION.md section 6 lists what is out of scope.
 
+Both take float16 / bfloat16 activations on the GPU: the kernels read ``x`` and the incoming
+gradient as they are and write ``y`` and ``x.grad`` in ``x``'s type, bit for bit the float32 module on ``x.float()``
+rounded once; ``lora_A`` / ``lora_B`` and their gradients stay float32, and the node saves ``x`` in its own type.
+
 ``LoRAQuantizedMoEFFN`` puts an adapter on each projection of the gated experts of ``QuantizedMoEFFN``: one on the
 stacked gate|up weight (one ``A`` shared by gate and up, a ``[2F, r]`` ``B``: PEFT's shape for a fused ``gate_up_proj``)
 and one on the down weight (ops.moe_ffn_lora_forward).
@@ -108,7 +112,8 @@ class LoRAMoEINT4(MoEINT4):
         return {k: v for k, v in self.state_dict().items() if k in ("lora_A", "lora_B")}
 
     def forward(self, inputs, expert_ids, tokens_per_expert, input_offsets):
-        """inputs ``[T, K]`` float32 on the GPU, rows grouped by expert -> ``[T, N]`` float32 (GPU only, as MoEINT4)."""
+        """inputs ``[T, K]`` float32 / float16 / bfloat16 on the GPU, rows grouped by expert -> ``[T, N]`` of the same
+        type (GPU only, as MoEINT4)."""
         del expert_ids
         if not inputs.is_cuda:
             raise RuntimeError("LoRAMoEINT4 runs on the GPU only (inputs must be a CUDA tensor)")

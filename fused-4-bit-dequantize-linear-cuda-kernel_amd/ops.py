@@ -256,17 +256,17 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
 _DTYPES = {torch.float32: _native.DTYPE_F32, torch.float16: _native.DTYPE_F16, torch.bfloat16: _native.DTYPE_BF16}
 
 
-def linear_forward_any(input, packed_weights, scales, zero_points, precision="default", out_dtype=None):
+def linear_forward_any(input, packed_weights, scales, zero_points, precision="default", out_dtype=None, bias=None):
     """``linear_forward`` for float32 / float16 / bfloat16 activations, output in ``out_dtype`` (default: the
-    input's).  Equal bit for bit to ``linear_forward(input.float()).to(out_dtype)``; on the MFMA path the two
-    conversion passes are fused into the kernels, elsewhere torch converts."""
+    input's).  Equal bit for bit to ``linear_forward(input.float(), bias=bias).to(out_dtype)``; on the MFMA path the
+    two conversion passes are fused into the kernels, elsewhere torch converts."""
     out_dtype = input.dtype if out_dtype is None else out_dtype
     if input.dtype not in _DTYPES or out_dtype not in _DTYPES:
         raise RuntimeError("activations and outputs must be float32, float16 or bfloat16")
-    if _wants_grad(input):
-        return _LinearFn.apply(input, packed_weights, scales, zero_points, None, precision, out_dtype, True)
+    if _wants_grad(input, bias):
+        return _LinearFn.apply(input, packed_weights, scales, zero_points, bias, precision, out_dtype, True)
     if input.dtype == torch.float32 and out_dtype == torch.float32:
-        return linear_forward(input, packed_weights, scales, zero_points, precision=precision)
+        return linear_forward(input, packed_weights, scales, zero_points, precision=precision, bias=bias)
     x2 = input.unsqueeze(0) if input.dim() == 1 else input
     prec = _precision(precision)
     L = _native.lib()
@@ -277,20 +277,25 @@ def linear_forward_any(input, packed_weights, scales, zero_points, precision="de
                                                packed_weights.data_ptr(), 0) == 1)
     if not native:
         return linear_forward(input.float().contiguous(), packed_weights, scales, zero_points,
-                              precision=precision).to(out_dtype)
+                              precision=precision, bias=bias).to(out_dtype)
     B, K = x2.shape
     N = packed_weights.shape[0]
     dev = x2.device
     if scales.numel() != N or zero_points.numel() != N or scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
         raise RuntimeError("scales and zero_points must be float32 with output_dim elements")
     scales, zero_points = scales.contiguous(), zero_points.contiguous()
+    if bias is not None:
+        if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
+            raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
+        bias = bias.contiguous()
     out = torch.empty((B, N), dtype=out_dtype, device=dev)
     with torch.cuda.device(dev):
         ws, ws_ptr = _workspace(L.fql_linear_workspace_bytes(B, K, N, prec), dev)
-        rc = L.fql_linear_fwd(x2.data_ptr(), _DTYPES[x2.dtype], packed_weights.data_ptr(), scales.data_ptr(),
-                              zero_points.data_ptr(), out.data_ptr(), _DTYPES[out_dtype], B, K, N, prec,
-                              ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_fwd")
+        rc = L.fql_linear_bias_fwd(x2.data_ptr(), _DTYPES[x2.dtype], packed_weights.data_ptr(), scales.data_ptr(),
+                                   zero_points.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(),
+                                   _DTYPES[out_dtype], B, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(),
+                                   _stream_ptr(dev))
+    _native.check(rc, "fql_linear_bias_fwd")
     return out.squeeze(0) if input.dim() == 1 else out
 
 
@@ -799,11 +804,21 @@ def linear_forward_fp8(x_e4m3, act_scales, packed_weights, scales, zero_points, 
 # mode is on and an input requires grad, and their forward is the plain op (bit for bit the same values).
 # ---------------------------------------------------------------------------------------------------------------------
 
-def linear_backward_input(grad_out, packed_weights, scales, zero_points, precision="default"):
+def _grad_dtypes(grad_out, out_dtype, rows):
+    if not grad_out.is_cuda or grad_out.dtype not in _DTYPES or grad_out.dim() != 2:
+        raise RuntimeError(f"grad_out must be a CUDA float32, float16 or bfloat16 [{rows}, N] tensor")
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    return out_dtype
+
+
+def linear_backward_input(grad_out, packed_weights, scales, zero_points, precision="default", out_dtype=None):
     """``grad_in = grad_out @ W`` for the per-row INT4 weights ``W = (q - zp) * s`` ([N, K]): the transposed INT4 GEMM
-    of csrc/fql_bwd.h.  ``grad_out`` [B, N] float32 on the GPU -> [B, K] float32."""
-    if not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.dim() != 2:
-        raise RuntimeError("grad_out must be a CUDA float32 [B, N] tensor")
+    of csrc/fql_bwd.h.  ``grad_out`` [B, N] float32 / float16 / bfloat16 on the GPU -> [B, K] ``out_dtype`` (default
+    float32).  A 16-bit ``grad_out`` is read as it is and a 16-bit result is rounded once in the kernel: bit for bit
+    ``linear_backward_input(grad_out.float()).to(out_dtype)`` with no float32 copy made."""
+    out_dtype = _grad_dtypes(grad_out, out_dtype, "B")
     N, K2 = packed_weights.shape
     B, K = grad_out.shape[0], 2 * K2
     if grad_out.shape[1] != N or scales.numel() != N or zero_points.numel() != N:
@@ -813,21 +828,22 @@ def linear_backward_input(grad_out, packed_weights, scales, zero_points, precisi
     p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
     L = _native.lib()
     prec = _precision(precision)
-    out = torch.empty((B, K), dtype=torch.float32, device=dev)
+    out = torch.empty((B, K), dtype=out_dtype, device=dev)
     with torch.cuda.device(dev):
         ws, ws_ptr = _workspace(L.fql_linear_bwd_workspace_bytes(B, K, N, prec), dev)
-        rc = L.fql_linear_bwd_input_f32(gy.data_ptr(), p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), out.data_ptr(),
-                                        B, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_bwd_input_f32")
+        rc = L.fql_linear_bwd_input(gy.data_ptr(), _DTYPES[gy.dtype], p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(),
+                                    out.data_ptr(), _DTYPES[out_dtype], B, K, N, prec, ws_ptr,
+                                    0 if ws is None else ws.numel(), _stream_ptr(dev))
+    _native.check(rc, "fql_linear_bwd_input")
     return out
 
 
 def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per_expert, input_offsets,
-                       precision="default"):
+                       precision="default", out_dtype=None):
     """Grouped ``grad_in[t] = grad_out[t] @ W_e`` for the rows of each expert's range; rows no expert covers are zero.
-    ``grad_out`` [T, N] float32, ``packed_weights`` [E, N, K/2] -> [T, K] float32."""
-    if not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.dim() != 2:
-        raise RuntimeError("grad_out must be a CUDA float32 [T, N] tensor")
+    ``grad_out`` [T, N] float32 / float16 / bfloat16, ``packed_weights`` [E, N, K/2] -> [T, K] ``out_dtype`` (default
+    float32); 16-bit types as in ``linear_backward_input``."""
+    out_dtype = _grad_dtypes(grad_out, out_dtype, "T")
     E, N, K2 = packed_weights.shape
     T, K = grad_out.shape[0], 2 * K2
     if grad_out.shape[1] != N or tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N):
@@ -839,13 +855,13 @@ def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per
     p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
     L = _native.lib()
     prec = _precision(precision)
-    out = torch.empty((T, K), dtype=torch.float32, device=dev)
+    out = torch.empty((T, K), dtype=out_dtype, device=dev)
     with torch.cuda.device(dev):
         ws, ws_ptr = _workspace(L.fql_moe_bwd_workspace_bytes(E, T, K, N, prec), dev)
-        rc = L.fql_moe_bwd_input_f32(p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), gy.data_ptr(), tpe.data_ptr(),
-                                     offs.data_ptr(), out.data_ptr(), E, T, K, N, prec, ws_ptr,
-                                     0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_bwd_input_f32")
+        rc = L.fql_moe_bwd_input(p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), gy.data_ptr(), _DTYPES[gy.dtype],
+                                 tpe.data_ptr(), offs.data_ptr(), out.data_ptr(), _DTYPES[out_dtype], E, T, K, N, prec,
+                                 ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
+    _native.check(rc, "fql_moe_bwd_input")
     return out
 
 
@@ -917,21 +933,21 @@ class _LinearFn(torch.autograd.Function):
         ctx.precision, ctx.x_dtype, ctx.x_dim = precision, x.dtype, x.dim()
         ctx.bias_grad = bias is not None and bias.requires_grad
         if any_dtype:
-            return linear_forward_any(x, packed, scales, zps, precision=precision, out_dtype=out_dtype)
+            return linear_forward_any(x, packed, scales, zps, precision=precision, out_dtype=out_dtype, bias=bias)
         return linear_forward(x, packed, scales, zps, precision=precision, bias=bias)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         packed, scales, zps = ctx.saved_tensors
-        g2 = gy.to(torch.float32).reshape(-1, gy.shape[-1]) if gy.dim() == 1 else gy.to(torch.float32)
-        if scales.dim() == 2 and scales.shape[1] > 1:
-            gx = group_backward_input(g2, packed, scales, zps)
-        else:
-            gx = linear_backward_input(g2, packed, scales, zps, precision=ctx.precision)
+        g2 = gy.reshape(-1, gy.shape[-1])
+        if scales.dim() == 2 and scales.shape[1] > 1:          # per-group weights: unfused, float32 in torch
+            gx = group_backward_input(g2.to(torch.float32), packed, scales, zps).to(ctx.x_dtype)
+        else:                                                  # gy in its own type, dX in x's: no cast pass
+            gx = linear_backward_input(g2, packed, scales, zps, precision=ctx.precision, out_dtype=ctx.x_dtype)
         gx = gx.reshape(-1) if ctx.x_dim == 1 else gx
-        gb = g2.sum(0) if ctx.bias_grad else None
-        return gx.to(ctx.x_dtype), None, None, None, gb, None, None, None
+        gb = g2.sum(0, dtype=torch.float32) if ctx.bias_grad else None
+        return gx, None, None, None, gb, None, None, None
 
 
 class _MoEFn(torch.autograd.Function):
@@ -950,8 +966,8 @@ class _MoEFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         packed, scales, zps, tpe, offs = ctx.saved_tensors
-        gx = moe_backward_input(packed, scales, zps, gy.to(torch.float32), tpe, offs, precision=ctx.precision)
-        return gx.to(ctx.x_dtype), None, None, None, None, None, None, None, None
+        gx = moe_backward_input(packed, scales, zps, gy, tpe, offs, precision=ctx.precision, out_dtype=ctx.x_dtype)
+        return gx, None, None, None, None, None, None, None, None
 
 
 class _CombineFn(torch.autograd.Function):
@@ -989,11 +1005,13 @@ def _lora_layout(layout):
         raise ValueError(f"layout must be 'rc' ([E, r, C]) or 'cr' ([E, C, r]), got {layout!r}") from None
 
 
-def _lora_rows(t, name, dev):
+def _lora_rows(t, name, dev, wide=False):
+    """A [T, r] tensor (float32), or with ``wide`` a streamed [T, C] operand (float32, float16 or bfloat16)."""
     if not t.is_cuda or t.device != dev:
         raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
-    if t.dtype != torch.float32 or t.dim() != 2:
-        raise RuntimeError(f"{name} must be a float32 2-D tensor (the adapter path is float32 only)")
+    if t.dim() != 2 or (t.dtype != torch.float32 and not (wide and t.dtype in _DTYPES)):
+        kinds = "float32, float16 or bfloat16" if wide else "float32"
+        raise RuntimeError(f"{name} must be a {kinds} 2-D tensor")
     return t.contiguous()
 
 
@@ -1035,9 +1053,10 @@ def _lora_weight(w, layout, C, dev, name="w"):
 
 def lora_shrink(input, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
     """Segmented ``out[t] = scale * input[t] @ W_e^T`` -> [T, r] float32: ``weight`` [E, r, C] (``layout='rc'``, e.g.
-    lora_A) or [E, C, r] (``'cr'``, e.g. lora_B), 2-D for one segment.  Rows no expert covers are zero."""
+    lora_A) or [E, C, r] (``'cr'``, e.g. lora_B), 2-D for one segment.  Rows no expert covers are zero.  ``input`` may
+    be float16 / bfloat16: read as it is, bit for bit the call on ``input.float()``."""
     dev = input.device
-    x = _lora_rows(input, "input", dev)
+    x = _lora_rows(input, "input", dev, wide=True)
     T, C = x.shape
     w, E, r = _lora_weight(weight, layout, C, dev, "weight")
     tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
@@ -1047,18 +1066,21 @@ def lora_shrink(input, weight, layout="rc", tokens_per_expert=None, input_offset
     if C == 0:
         return out.zero_()
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_shrink_f32(x.data_ptr(), w.data_ptr(), _lora_layout(layout),
-                                               None if tpe is None else tpe.data_ptr(),
-                                               None if offs is None else offs.data_ptr(), out.data_ptr(), E, T, C, r,
-                                               float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_shrink_f32")
+        rc = _native.lib().fql_lora_shrink(x.data_ptr(), _DTYPES[x.dtype], w.data_ptr(), _lora_layout(layout),
+                                           None if tpe is None else tpe.data_ptr(),
+                                           None if offs is None else offs.data_ptr(), out.data_ptr(), E, T, C, r,
+                                           float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_shrink")
     return out
 
 
-def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=None, scale=1.0, input=None, out=None):
-    """Segmented ``out[t] = input[t] + scale * v[t] @ W_e^T`` -> [T, C] float32: ``v`` [T, r], ``weight`` [E, C, r]
+def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=None, scale=1.0, input=None, out=None,
+                out_dtype=None):
+    """Segmented ``out[t] = input[t] + scale * v[t] @ W_e^T`` -> [T, C]: ``v`` [T, r] float32, ``weight`` [E, C, r]
     (``layout='cr'``, e.g. lora_B) or [E, r, C] (``'rc'``, e.g. lora_A).  ``input`` None starts from zero; ``out`` may be
-    ``input`` (in place; it must then be contiguous).  Rows no expert covers get ``input`` (or zero)."""
+    ``input`` (in place; it must then be contiguous).  Rows no expert covers get ``input`` (or zero).  ``input`` and
+    ``out`` may each be float32, float16 or bfloat16 (in place: one type); without ``out=`` the result has ``out_dtype``
+    (default: ``input``'s type, float32 without an input).  A 16-bit result is the float32 one rounded once."""
     dev = v.device
     vv = _lora_rows(v, "v", dev)
     T = vv.shape[0]
@@ -1074,29 +1096,36 @@ def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=No
     if input is not None:
         if tuple(input.shape) != (T, C):
             raise RuntimeError("input must be [T, C]")
-        inp = input if (out is not None and input is out) else _lora_rows(input, "input", dev)
+        inp = input if (out is not None and input is out) else _lora_rows(input, "input", dev, wide=True)
     if out is None:
-        out = torch.empty((T, C), dtype=torch.float32, device=dev)
-    elif (not out.is_cuda or out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (T, C)
-          or not out.is_contiguous()):
-        raise RuntimeError("out must be a contiguous CUDA float32 [T, C] tensor on the inputs' device")
+        if out_dtype is None:
+            out_dtype = torch.float32 if inp is None else inp.dtype
+        if out_dtype not in _DTYPES:
+            raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+        out = torch.empty((T, C), dtype=out_dtype, device=dev)
+    elif (not out.is_cuda or out.device != dev or out.dtype not in _DTYPES or tuple(out.shape) != (T, C)
+          or not out.is_contiguous() or (out_dtype is not None and out_dtype != out.dtype)):
+        raise RuntimeError("out must be a contiguous CUDA float32 / float16 / bfloat16 [T, C] tensor on the inputs' "
+                           "device (of out_dtype, when that is given)")
     if T == 0 or C == 0:
         return out
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_expand_f32(vv.data_ptr(), w.data_ptr(), _lora_layout(layout),
-                                               None if tpe is None else tpe.data_ptr(),
-                                               None if offs is None else offs.data_ptr(),
-                                               None if inp is None else inp.data_ptr(), out.data_ptr(), E, T, C, r,
-                                               float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_expand_f32")
+        rc = _native.lib().fql_lora_expand(vv.data_ptr(), w.data_ptr(), _lora_layout(layout),
+                                           None if tpe is None else tpe.data_ptr(),
+                                           None if offs is None else offs.data_ptr(),
+                                           None if inp is None else inp.data_ptr(),
+                                           _native.DTYPE_F32 if inp is None else _DTYPES[inp.dtype], out.data_ptr(),
+                                           _DTYPES[out.dtype], E, T, C, r, float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_expand")
     return out
 
 
 def lora_grad(p, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
     """Segment reduction ``D_e = scale * sum_{t of e} p[t]^T v[t]`` per expert: ``p`` [T, C], ``v`` [T, r] ->
-    [E, C, r] (``layout='cr'``: dB) or [E, r, C] (``'rc'``: dA).  Experts without rows get zeros."""
+    [E, C, r] (``layout='cr'``: dB) or [E, r, C] (``'rc'``: dA), float32.  Experts without rows get zeros.  ``p`` may be
+    float16 / bfloat16: read as it is, bit for bit the call on ``p.float()``."""
     dev = p.device
-    pp = _lora_rows(p, "p", dev)
+    pp = _lora_rows(p, "p", dev, wide=True)
     vv = _lora_rows(v, "v", dev)
     T, C = pp.shape
     r = vv.shape[1]
@@ -1114,10 +1143,11 @@ def lora_grad(p, v, layout, num_experts=1, tokens_per_expert=None, input_offsets
     if vv.data_ptr() % 16:
         vv = vv.clone()
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_grad_f32(pp.data_ptr(), vv.data_ptr(), None if tpe is None else tpe.data_ptr(),
-                                             None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T, C, r,
-                                             float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_grad_f32")
+        rc = _native.lib().fql_lora_grad(pp.data_ptr(), _DTYPES[pp.dtype], vv.data_ptr(),
+                                         None if tpe is None else tpe.data_ptr(),
+                                         None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T, C, r,
+                                         float(scale), _stream_ptr(dev))
+    _native.check(rc, "fql_lora_grad")
     return d
 
 
@@ -1125,7 +1155,9 @@ def _lora_check_adapters(lora_A, lora_B, K, N, E):
     """lora_A [r, K] / lora_B [N, r] (E == 1: 2-D) or [E, r, K] / [E, N, r]: float32 CUDA."""
     for name, t in (("lora_A", lora_A), ("lora_B", lora_B)):
         if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{name} must be a float32 CUDA tensor (the adapter path is float32 only)")
+            raise RuntimeError(f"{name} must be a float32 CUDA tensor: the adapter weights and their gradients stay "
+                               "float32 whatever the activations' type (keep them out of a module-wide .half() / "
+                               ".bfloat16(), or cast them back)")
     want_dim = 2 if E is None else 3
     if lora_A.dim() != want_dim or lora_B.dim() != want_dim:
         raise RuntimeError("lora_A / lora_B must be [r, K] / [N, r] for a linear layer, [E, r, K] / [E, N, r] for MoE")
@@ -1138,20 +1170,34 @@ def _lora_check_adapters(lora_A, lora_B, K, N, E):
 
 
 def _linear_lora_apply(x2, packed, scales, zps, lora_A, lora_B, scaling, precision, bias):
-    """Base forward, then U = x A^T and y += scaling * U B^T in place.  Returns (y, U)."""
-    y = linear_forward(x2, packed, scales, zps, precision=precision, bias=bias)
+    """Base forward, then U = x A^T and y += scaling * U B^T in place.  Returns (y, U).
+    16-bit x: the base GEMM reads x as it is and writes float32, the shrink reads x as it is, and the expand reads that
+    float32 and writes y in x's type -- one rounding, no float32 copy of x."""
+    if x2.dtype == torch.float32:
+        y = linear_forward(x2, packed, scales, zps, precision=precision, bias=bias)
+        u = lora_shrink(x2, lora_A, "rc")
+        lora_expand(u, lora_B, "cr", scale=scaling, input=y, out=y)
+        return y, u
+    if _per_group(scales):                                      # unfused branch: torch widens x
+        y32 = linear_forward(x2.float(), packed, scales, zps, precision=precision, bias=bias)
+    else:
+        y32 = linear_forward_any(x2, packed, scales, zps, precision=precision, out_dtype=torch.float32, bias=bias)
     u = lora_shrink(x2, lora_A, "rc")
-    lora_expand(u, lora_B, "cr", scale=scaling, input=y, out=y)
-    return y, u
+    return lora_expand(u, lora_B, "cr", scale=scaling, input=y32, out_dtype=x2.dtype), u
+
+
+def _per_group(scales):
+    return scales.dim() == 2 and scales.shape[1] > 1
 
 
 def linear_lora_forward(x, packed, scales, zps, lora_A, lora_B, scaling, precision="default", bias=None):
-    """INT4 linear plus a low-rank adapter: ``x @ W_q^T (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``, float32
-    ``x`` [K] or [B, K], ``lora_A`` [r, K], ``lora_B`` [N, r].  Differentiable in ``x``, ``lora_A``, ``lora_B`` and
-    ``bias`` (the INT4 weights are frozen); the backward reuses the fused input gradient of the base layer."""
-    if x.dtype != torch.float32:
-        raise RuntimeError("linear_lora_forward: x must be float32 (16-bit activations are not supported on the "
-                           "adapter path)")
+    """INT4 linear plus a low-rank adapter: ``x @ W_q^T (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``, ``x`` [K]
+    or [B, K] float32 / float16 / bfloat16, float32 ``lora_A`` [r, K] and ``lora_B`` [N, r]; the result has ``x``'s
+    type.  Differentiable in ``x``, ``lora_A``, ``lora_B`` and ``bias`` (the INT4 weights are frozen); the backward
+    reuses the fused input gradient of the base layer.  16-bit ``x``: bit for bit the float32 call on ``x.float()``
+    with ``y`` and ``x.grad`` rounded once; the adapter gradients are float32."""
+    if not x.is_cuda or x.dtype not in _DTYPES:
+        raise RuntimeError("linear_lora_forward: x must be a CUDA float32, float16 or bfloat16 tensor")
     if x.dim() not in (1, 2):
         raise RuntimeError("x must be 1-D or 2-D")
     K = x.shape[-1]
@@ -1168,9 +1214,10 @@ def moe_lora_forward(packed, scales, zps, inputs, lora_A, lora_B, scaling, token
     """Grouped INT4 GEMM plus a per-expert low-rank adapter: for the rows t of expert e,
     ``y[t] = inputs[t] @ W_e^T + scaling * (inputs[t] @ lora_A[e]^T) @ lora_B[e]^T``; rows no expert covers are zero.
     ``lora_A`` [E, r, K], ``lora_B`` [E, N, r] float32.  Per-row INT4 weights only.  Differentiable in ``inputs``,
-    ``lora_A`` and ``lora_B``."""
-    if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
-        raise RuntimeError("inputs must be a CUDA float32 [T, K] tensor (the adapter path is float32 only)")
+    ``lora_A`` and ``lora_B``.  ``inputs`` float32 / float16 / bfloat16, result in the same type (16-bit: as
+    ``linear_lora_forward``)."""
+    if not inputs.is_cuda or inputs.dtype not in _DTYPES or inputs.dim() != 2:
+        raise RuntimeError("inputs must be a CUDA float32, float16 or bfloat16 [T, K] tensor")
     if packed.dim() != 3 or scales.dim() != 2:
         raise RuntimeError("moe_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points [E, N]")
     E, N = packed.shape[0], packed.shape[1]
@@ -1184,14 +1231,19 @@ def moe_lora_forward(packed, scales, zps, inputs, lora_A, lora_B, scaling, token
 
 
 def _moe_lora_apply(packed, scales, zps, inputs, lora_A, lora_B, scaling, tpe, offs, precision):
-    y = moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
+    if inputs.dtype == torch.float32:
+        y = moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
+        u = lora_shrink(inputs, lora_A, "rc", tpe, offs)
+        lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y, out=y)
+        return y, u
+    y32 = moe_forward_any(packed, scales, zps, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
     u = lora_shrink(inputs, lora_A, "rc", tpe, offs)
-    lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y, out=y)
-    return y, u
+    return lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y32, out_dtype=inputs.dtype), u
 
 
 class _LinearLoRAFn(torch.autograd.Function):
-    """Base INT4 linear + adapter in one node.  Saves x and U = x A^T ([B, r]); nothing dequantised."""
+    """Base INT4 linear + adapter in one node.  Saves x (in its own type) and U = x A^T ([B, r] float32); nothing
+    dequantised.  gy is read in its own type; a 16-bit dX is written once, by the expand, from the float32 base dX."""
 
     @staticmethod
     def forward(ctx, x, lora_A, lora_B, bias, packed, scales, zps, scaling, precision):
@@ -1206,28 +1258,43 @@ class _LinearLoRAFn(torch.autograd.Function):
     def backward(ctx, gy):
         x2, u, lora_A, lora_B, packed, scales, zps = ctx.saved_tensors
         need_x, need_A, need_B, need_b = ctx.needs_input_grad[:4]
-        g = gy.to(torch.float32).reshape(-1, gy.shape[-1]).contiguous()
+        g = _grad_rows(gy.reshape(-1, gy.shape[-1]))
         gx = gA = gB = gb = None
         if need_x or need_A:
             du = lora_shrink(g, lora_B, "cr", scale=ctx.scaling)                # dU = s G B
             if need_x:
-                if scales.dim() == 2 and scales.shape[1] > 1:
-                    gx = group_backward_input(g, packed, scales, zps)
+                if _per_group(scales):                                          # unfused: torch widens gy here only
+                    gx = group_backward_input(g.to(torch.float32), packed, scales, zps)
                 else:
                     gx = linear_backward_input(g, packed, scales, zps, precision=ctx.precision)
-                lora_expand(du, lora_A, "rc", input=gx, out=gx)                 # dX += dU A
+                gx = _expand_into(du, lora_A, gx, x2.dtype)                     # dX += dU A
                 gx = gx.reshape(-1) if ctx.x_dim == 1 else gx
             if need_A:
                 gA = lora_grad(x2, du, "rc")[0]                                  # dA = dU^T X
         if need_B:
             gB = lora_grad(g, u, "cr", scale=ctx.scaling)[0]                     # dB = s G^T U
         if need_b:
-            gb = g.sum(0)
+            gb = g.sum(0, dtype=torch.float32)
         return gx, gA, gB, gb, None, None, None, None, None
 
 
+def _grad_rows(gy):
+    """The incoming gradient as the kernels read it: contiguous, in its own type (float32 / float16 / bfloat16)."""
+    if gy.dtype not in _DTYPES:
+        raise RuntimeError("the gradient must be float32, float16 or bfloat16")
+    return gy.contiguous()
+
+
+def _expand_into(du, lora_A, gx32, dtype, tpe=None, offs=None):
+    """dX = gx32 + dU A in ``dtype``: in place on the float32 base gradient, or one 16-bit write from it."""
+    if dtype == torch.float32:
+        return lora_expand(du, lora_A, "rc", tpe, offs, input=gx32, out=gx32)
+    return lora_expand(du, lora_A, "rc", tpe, offs, input=gx32, out_dtype=dtype)
+
+
 class _MoELoRAFn(torch.autograd.Function):
-    """Grouped INT4 GEMM + per-expert adapter in one node.  Saves inputs and U ([T, r]) and the expert table."""
+    """Grouped INT4 GEMM + per-expert adapter in one node.  Saves inputs (in their own type), U ([T, r] float32) and the
+    expert table."""
 
     @staticmethod
     def forward(ctx, inputs, lora_A, lora_B, packed, scales, zps, tpe, offs, scaling, precision):
@@ -1242,13 +1309,13 @@ class _MoELoRAFn(torch.autograd.Function):
         x, u, lora_A, lora_B, packed, scales, zps, tpe, offs = ctx.saved_tensors
         need_x, need_A, need_B = ctx.needs_input_grad[:3]
         E = packed.shape[0]
-        g = gy.to(torch.float32).contiguous()
+        g = _grad_rows(gy)
         gx = gA = gB = None
         if need_x or need_A:
             du = lora_shrink(g, lora_B, "cr", tpe, offs, scale=ctx.scaling)
             if need_x:
                 gx = moe_backward_input(packed, scales, zps, g, tpe, offs, precision=ctx.precision)
-                lora_expand(du, lora_A, "rc", tpe, offs, input=gx, out=gx)
+                gx = _expand_into(du, lora_A, gx, x.dtype, tpe, offs)
             if need_A:
                 gA = lora_grad(x, du, "rc", E, tpe, offs)
         if need_B:
@@ -1346,7 +1413,9 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
     [E, H, F/2], ``gate_up_lora_A`` [E, r, H], ``gate_up_lora_B`` [E, 2F, r], ``down_lora_A`` [E, r, F],
     ``down_lora_B`` [E, H, r].  Per-row INT4 weights only.  Differentiable (once) in ``inputs`` and the four adapters."""
     if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
-        raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor (the adapter path is float32 only)")
+        raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor: the gated FFN adapters are float32 only (16-bit "
+                           "activations need a 16-bit gate_up through the gated GEMM's pre-pass, the gated shrink / grad "
+                           "and swiglu_backward: not built yet)")
     if gate_up_packed.dim() != 3 or gate_up_scales.dim() != 2 or down_packed.dim() != 3 or down_scales.dim() != 2:
         raise RuntimeError("moe_ffn_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points "
                            "[E, N]")

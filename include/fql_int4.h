@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 240 /* 0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 250 /* 0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -316,6 +316,11 @@ FQL_API int fql_native_dtype_supported(int rows, int E, int K, int N, int precis
 FQL_API int fql_linear_fwd(const void *x, int in_dtype, const uint8_t *packed, const float *scales,
                            const float *zps, void *out, int out_dtype, int B, int K, int N, int precision,
                            void *workspace, size_t workspace_bytes, void *stream);
+/* fql_linear_fwd with the optional bias [N] of fql_linear_bias_fwd_f32 (NULL: none), added by the same epilogue: bit for
+ * bit fql_linear_bias_fwd_f32 on the widened x, rounded once to out_dtype.  Same shapes, same errors. */
+FQL_API int fql_linear_bias_fwd(const void *x, int in_dtype, const uint8_t *packed, const float *scales,
+                                const float *zps, const float *bias, void *out, int out_dtype, int B, int K, int N,
+                                int precision, void *workspace, size_t workspace_bytes, void *stream);
 
 FQL_API int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs,
                         int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
@@ -363,7 +368,8 @@ FQL_API int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const fl
  *   matrix cores (csrc/fql_bwd.h): g = grad_out * scales (one float32 rounding) is split into `precision` limbs per row
  *   exactly as the forward splits x (3 for DEFAULT / EXACT, 2 for FAST, 1 for INT8 and FP8), the weights enter as the
  *   exact integers q - clamp(rint(zp), -112, 112), and the fractional part of non-integer zero points is applied as a
- *   float32 correction per row.  float32 gradients only (16-bit callers convert).  Any even K, any N in
+ *   float32 correction per row.  float32 gradients here; fql_linear_bwd_input / fql_moe_bwd_input (below) take
+ *   float16 / bfloat16 gradients as they are, so a 16-bit caller converts nothing.  Any even K, any N in
  *   [0, FQL_BWD_MAX_N] (the i32 accumulation is exact up to 2^31 / (128 * 127) = 132104).  Every element of grad_in
  *   is written once: deterministic, no atomics.
  * fql_moe_bwd_input_f32: the grouped form: grad_in[t] = grad_out[t] @ W_e for the rows of expert e's range
@@ -376,7 +382,17 @@ FQL_API int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const fl
  * fql_combine_bwd_f32: gradients of fql_combine_f32 in one launch, no atomics (pos_of_slot must be a permutation of
  *   the rows of y that it names): grad_y[pos[t][k]] = weights[t][k] * grad_out[t] (weights == NULL: grad_out[t]);
  *   grad_weights[t][k] = <y[pos[t][k]], grad_out[t]> (skipped when grad_weights == NULL).  Rows of grad_y no slot
- *   names are not written. */
+ *   names are not written.
+ *
+ * fql_linear_bwd_input / fql_moe_bwd_input: the same two gradients with an element type (FQL_DTYPE_*) for grad_out and
+ *   one for grad_in.  The pre-pass loads a 16-bit grad_out directly and widens it in registers (exact) before the
+ *   multiply by scales[n], so the limbs are those of the float32 call on the widened gradient; the GEMM's epilogue
+ *   rounds grad_in once to nearest even on store.  Contract: bit for bit the _f32 entry point on the widened grad_out,
+ *   rounded once to grad_in_dtype as Tensor.to(dtype) rounds (float16 overflow gives inf).  No float32 copy of a [T][N]
+ *   or [T][K] tensor exists anywhere; the workspace (fql_*_bwd_workspace_bytes) is unchanged.  (float32, float32) is the
+ *   _f32 entry point.  Errors: as above, with FQL_ERR_DTYPE (an element type that is not FQL_DTYPE_F32 / _F16 / _BF16)
+ *   after FQL_ERR_BAD_PRECISION, FQL_ERR_BAD_SHAPE and FQL_ERR_ODD_K and before everything else: before the empty-call
+ *   FQL_OK, FQL_ERR_NULL_POINTER, FQL_ERR_WORKSPACE and FQL_ERR_LAUNCH. */
 #define FQL_BWD_MAX_N 132104
 FQL_API size_t fql_linear_bwd_workspace_bytes(int B, int K, int N, int precision);
 FQL_API int fql_linear_bwd_input_f32(const float *grad_out, const uint8_t *packed, const float *scales, const float *zps,
@@ -386,6 +402,13 @@ FQL_API size_t fql_moe_bwd_workspace_bytes(int E, int T, int K, int N, int preci
 FQL_API int fql_moe_bwd_input_f32(const uint8_t *packed, const float *scales, const float *zps, const float *grad_out,
                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, float *grad_in, int E,
                                   int T, int K, int N, int precision, void *ws, size_t ws_bytes, void *stream);
+FQL_API int fql_linear_bwd_input(const void *grad_out, int grad_out_dtype, const uint8_t *packed, const float *scales,
+                                 const float *zps, void *grad_in, int grad_in_dtype, int B, int K, int N, int precision,
+                                 void *ws, size_t ws_bytes, void *stream);
+FQL_API int fql_moe_bwd_input(const uint8_t *packed, const float *scales, const float *zps, const void *grad_out,
+                              int grad_out_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                              void *grad_in, int grad_in_dtype, int E, int T, int K, int N, int precision, void *ws,
+                              size_t ws_bytes, void *stream);
 FQL_API int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
                                 float *grad_y, float *grad_weights, int T, int top_k, int N, int rows, void *stream);
 
@@ -419,7 +442,25 @@ FQL_API int fql_combine_bwd_f32(const float *grad_out, const float *y, const int
  * only one of the two table pointers, or no table with E != 1 -> FQL_ERR_NULL_POINTER; `w` (shrink, expand) or
  * `v` and `d` (grad) not 16-byte aligned -> FQL_ERR_ALIGNMENT; FQL_ERR_LAUNCH.  The Python surface is
  * ops.lora_shrink / lora_expand / lora_grad and the differentiable ops.linear_lora_forward / moe_lora_forward
- * (INTEGRATION.md section 6). */
+ * (INTEGRATION.md section 6).
+ *
+ * fql_lora_shrink / fql_lora_expand / fql_lora_grad: the same three kernels with an element type (FQL_DTYPE_F32 / _F16 /
+ * _BF16) for each streamed [T][C] operand: `in` of shrink, `p` of grad, and `in` and `out` of expand, each on its own.
+ * [T][r] tensors (out of shrink, v), adapter weights and their gradients are float32, and so is every accumulator.
+ * 16-bit elements are widened in registers on load (exact) and a 16-bit `out` is rounded once, to nearest even, on
+ * store.  Contract: a call returns, bit for bit, what the _f32 entry point returns on the exactly widened operands,
+ * (expand) rounded once to out_dtype as Tensor.to(dtype) rounds -- whenever both calls take the same vector width:
+ *   vector width, in ELEMENTS: 4 when C % 4 == 0 and every [T][C] base pointer of the call is aligned to 4 of its own
+ *   elements (16 bytes float32, 8 bytes 16-bit), else 2 under the same rule (8 / 4 bytes), else 1.
+ * The width fixes the column-to-lane mapping and, for shrink, the order of the sum over c.  16-byte aligned bases on both
+ * sides always give equal widths; a 16-bit base that is only 2- or 4-byte aligned takes a narrower width than the float32
+ * call on an aligned copy and then agrees with it to rounding of the float32 sums only (expand and grad do not depend on
+ * the width: one lane per output column, fixed order over j / t).  Determinism, grouped == per-expert and the handling of
+ * uncovered rows are those of the _f32 entry points.  expand: in == out (in place) needs in_dtype == out_dtype; in_dtype is
+ * ignored when in == NULL.  (float32[, float32]) calls are forwarded to the _f32 entry points.
+ * Errors, in this order and all before any HIP call: FQL_ERR_BAD_SHAPE as above; then FQL_ERR_DTYPE: an element type
+ * outside FQL_DTYPE_*, or expand with in == out and in_dtype != out_dtype; then the empty-call FQL_OK,
+ * FQL_ERR_NULL_POINTER and FQL_ERR_ALIGNMENT as above (plus a [T][C] base not aligned to its element size), FQL_ERR_LAUNCH. */
 #define FQL_LORA_RC 0
 #define FQL_LORA_CR 1
 FQL_API int fql_lora_shrink_f32(const float *in, const float *w, int w_layout, const int32_t *tokens_per_expert,
@@ -431,6 +472,15 @@ FQL_API int fql_lora_expand_f32(const float *v, const float *w, int w_layout, co
 FQL_API int fql_lora_grad_f32(const float *p, const float *v, const int32_t *tokens_per_expert,
                               const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
                               float scale, void *stream);
+FQL_API int fql_lora_shrink(const void *in, int in_dtype, const float *w, int w_layout, const int32_t *tokens_per_expert,
+                            const int32_t *input_offsets, float *out, int E, int T, int C, int r, float scale,
+                            void *stream);
+FQL_API int fql_lora_expand(const float *v, const float *w, int w_layout, const int32_t *tokens_per_expert,
+                            const int32_t *input_offsets, const void *in, int in_dtype, void *out, int out_dtype, int E,
+                            int T, int C, int r, float scale, void *stream);
+FQL_API int fql_lora_grad(const void *p, int p_dtype, const float *v, const int32_t *tokens_per_expert,
+                          const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r, float scale,
+                          void *stream);
 
 /* ---- adapters on the gated FFN experts (QuantizedMoEFFN): y = W_d h + s B_d (A_d h), h = silu(g) * u ----
  * The hidden activation h [T][C] is never stored; the down adapter reads it from gate_up = [g | u] ([T][2C], the
