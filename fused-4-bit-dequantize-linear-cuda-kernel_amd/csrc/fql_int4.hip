@@ -1198,13 +1198,17 @@ int fql_quantize_tensor_f32(const float *w, uint8_t *packed, float *scales, floa
     return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
 }
 
+// `bias` [E][N] and `row_weight` [T] are optional.  The kernels take the bias as a pointer, but read a row's weight from the
+// plane behind delta's set(s), where the pre-pass of the product path leaves it: `row_weight` must BE that plane.
 static int gemm_i8_entry(int cfg, const int8_t *limbs, const float *delta, const int32_t *rowsum,
                          const uint8_t *packed, const float *scales, const float *zps,
-                         const int32_t *tokens_per_expert, const int32_t *input_offsets, float *out, int E, int T,
+                         const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                         const float *bias, const float *row_weight, int E, int T,
                          int K, int N, int precision, void *stream, void *scratch, size_t scratch_bytes)
 {
     const int L = limbs_of(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
+    if (!valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (E <= 0 || T < 0 || K <= 0 || N < 0) return FQL_ERR_BAD_SHAPE;
     if (K & 1) return FQL_ERR_ODD_K;
     if (T == 0 || N == 0) return FQL_OK;
@@ -1213,6 +1217,7 @@ static int gemm_i8_entry(int cfg, const int8_t *limbs, const float *delta, const
     if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
     if ((K % 32) != 0 || !aligned16(packed) || !aligned16(limbs)) return FQL_ERR_ALIGNMENT;
     if (!mfma_addressable(L, T, E, K, N)) return FQL_ERR_BAD_SHAPE;
+    if (row_weight != nullptr && row_weight != delta + (size_t)(has_residual(L, is_f8(precision)) ? 2 : 1) * T) return FQL_ERR_ALIGNMENT;
     if (is_f8(precision)) {
         if (cfg < 0) cfg = choose_cfg_f8(E, T, N, tokens_per_expert != nullptr);
         if (!valid_cfg_f8(cfg)) return FQL_ERR_BAD_SHAPE;
@@ -1224,22 +1229,21 @@ static int gemm_i8_entry(int cfg, const int8_t *limbs, const float *delta, const
     w.limbs = const_cast<int8_t *>(limbs);
     w.delta = const_cast<float *>(delta);
     w.rowsum = const_cast<int32_t *>(rowsum);
-    w.bias = nullptr;
-    w.row_weight = nullptr;
+    w.bias = bias;
+    w.row_weight = row_weight;
     w.bytes = 0;
-    // without (enough) scratch the residual pass of heavy-tailed rows is skipped: the result is then the plain 8L-1 bit one
     // without (enough) scratch the residual pass of heavy-tailed rows is skipped: the result is then the plain 8L-1 bit one
     w.scratch = (has_residual(L, is_f8(precision)) && scratch != nullptr && aligned16(scratch) && scratch_bytes >= res_scratch_bytes())
                     ? static_cast<float *>(scratch) : nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int Kp = padded_k(K), MBT = row_blocks(T, E);
     if (is_f8(precision))
-        return launch_gemm_f8(cfg, w, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
+        return launch_gemm_f8(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
     if (L == 1)
-        return launch_gemm<1>(cfg, w, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
+        return launch_gemm<1>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
     if (L == 2)
-        return launch_gemm<2>(cfg, w, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
-    return launch_gemm<3>(cfg, w, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
+        return launch_gemm<2>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
+    return launch_gemm<3>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
 }
 
 int fql_gemm_i8_f32(const int8_t *limbs, const float *delta, const int32_t *rowsum, const uint8_t *packed,
@@ -1247,8 +1251,8 @@ int fql_gemm_i8_f32(const int8_t *limbs, const float *delta, const int32_t *rows
                     const int32_t *input_offsets, float *out, int E, int T, int K, int N, int precision,
                     void *stream, void *scratch, size_t scratch_bytes)
 {
-    return gemm_i8_entry(-1, limbs, delta, rowsum, packed, scales, zps, tokens_per_expert, input_offsets, out, E, T,
-                         K, N, precision, stream, scratch, scratch_bytes);
+    return gemm_i8_entry(-1, limbs, delta, rowsum, packed, scales, zps, tokens_per_expert, input_offsets, out, FQL_DTYPE_F32,
+                         nullptr, nullptr, E, T, K, N, precision, stream, scratch, scratch_bytes);
 }
 
 // Tuning hooks (include/fql_int4_tune.h, not part of the drop-in boundary): the same call with an explicit tile configuration id.
@@ -1258,8 +1262,20 @@ FQL_API int fql_tune_gemm_i8_f32(int cfg, const int8_t *limbs, const float *delt
                                  int T, int K, int N, int precision, void *stream, void *scratch, size_t scratch_bytes)
 {
     if (!(precision == FQL_PRECISION_FP8 ? valid_cfg_f8(cfg) : valid_cfg(cfg, limbs_of(precision)))) return FQL_ERR_BAD_SHAPE;
-    return gemm_i8_entry(cfg, limbs, delta, rowsum, packed, scales, zps, tokens_per_expert, input_offsets, out, E, T,
-                         K, N, precision, stream, scratch, scratch_bytes);
+    return gemm_i8_entry(cfg, limbs, delta, rowsum, packed, scales, zps, tokens_per_expert, input_offsets, out, FQL_DTYPE_F32,
+                         nullptr, nullptr, E, T, K, N, precision, stream, scratch, scratch_bytes);
+}
+
+// ... and with the whole epilogue: output element type, optional bias [E][N], optional row weight [T] (the plane behind delta)
+FQL_API int fql_tune_gemm_i8(int cfg, const int8_t *limbs, const float *delta, const int32_t *rowsum,
+                             const uint8_t *packed, const float *scales, const float *zps,
+                             const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                             const float *bias, const float *row_weight, int E, int T, int K, int N, int precision,
+                             void *stream, void *scratch, size_t scratch_bytes)
+{
+    if (!(precision == FQL_PRECISION_FP8 ? valid_cfg_f8(cfg) : valid_cfg(cfg, limbs_of(precision)))) return FQL_ERR_BAD_SHAPE;
+    return gemm_i8_entry(cfg, limbs, delta, rowsum, packed, scales, zps, tokens_per_expert, input_offsets, out, out_dtype,
+                         bias, row_weight, E, T, K, N, precision, stream, scratch, scratch_bytes);
 }
 
 #if defined(FQL_TRACE)

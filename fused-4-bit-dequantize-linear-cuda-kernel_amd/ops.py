@@ -674,20 +674,47 @@ def gemm_i8(limbs, delta, rowsum, packed_weights, scales, zero_points, tokens_pe
 
 
 def tune_gemm_i8(cfg, limbs, delta, rowsum, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, out,
-                 E, T, K, N, precision):
-    """Phase 2 with an explicit tile configuration id (tuning / test hook, not part of the public header)."""
+                 E, T, K, N, precision, out_dtype=None, bias=None, row_weight=None):
+    """Phase 2 with an explicit tile configuration id (tuning / test hook, not part of the public header).
+    With ``out_dtype`` (the element type of ``out``), ``bias`` [E, N] or ``row_weight`` [T] the call goes to the hook that
+    reaches the whole epilogue: out = out_dtype(fl32(fl32(acc + bias) * row_weight)).  The kernels read a row's weight
+    from the plane behind delta's sets (the pre-pass of the product path puts it there), so it is appended to a copy of
+    ``delta`` here."""
     import ctypes
-    fn = _native.lib().fql_tune_gemm_i8_f32
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     prec = _precision(precision)
     dev = limbs.device
     scratch = gemm_scratch(prec, dev)
+    head = [cfg, limbs.data_ptr(), None, rowsum.data_ptr(), packed_weights.data_ptr(), scales.data_ptr(),
+            zero_points.data_ptr(), None if tokens_per_expert is None else tokens_per_expert.data_ptr(),
+            None if input_offsets is None else input_offsets.data_ptr(), out.data_ptr()]
+    tail = [E, T, K, N, prec, _stream_ptr(dev), None if scratch is None else scratch.data_ptr(),
+            0 if scratch is None else scratch.numel()]
+    tail_types = [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    if out_dtype is None and bias is None and row_weight is None:
+        fn = _native.lib().fql_tune_gemm_i8_f32
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 9 + tail_types
+        head[2] = delta.data_ptr()
+        with torch.cuda.device(dev):
+            return fn(*head, *tail)
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out.dtype != out_dtype or out_dtype not in _DTYPES:
+        raise RuntimeError("out must be a float32, float16 or bfloat16 tensor of element type out_dtype")
+    for name, t, n in (("bias", bias, E * N), ("row_weight", row_weight, T)):
+        if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous float32 tensor of {n} elements on the limbs' device")
+    rw_ptr = None
+    if row_weight is not None:
+        if delta.dim() != 2 or delta.shape != (_sets(prec), T):
+            raise RuntimeError("delta must be [sets, T] as act_quant returns it")
+        delta = torch.cat([delta, row_weight.reshape(1, T)])
+        rw_ptr = delta[_sets(prec)].data_ptr()
+    fn = _native.lib().fql_tune_gemm_i8
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p] + tail_types
+    head[2] = delta.data_ptr()
     with torch.cuda.device(dev):
-        return fn(cfg, limbs.data_ptr(), delta.data_ptr(), rowsum.data_ptr(), packed_weights.data_ptr(), scales.data_ptr(),
-                  zero_points.data_ptr(), None if tokens_per_expert is None else tokens_per_expert.data_ptr(),
-                  None if input_offsets is None else input_offsets.data_ptr(), out.data_ptr(), E, T, K, N, prec,
-                  _stream_ptr(dev), None if scratch is None else scratch.data_ptr(), 0 if scratch is None else scratch.numel())
+        return fn(*head, _DTYPES[out_dtype], None if bias is None else bias.data_ptr(), rw_ptr, *tail)
 
 
 # ------------------------------------------------------------------------------------------------ fp8 activations

@@ -4,7 +4,7 @@
  *
  * The setters change PROCESS-GLOBAL dispatch thresholds of the library: they are not thread-safe, and a process that calls
  * one no longer has the "no state between calls" property fql_int4.h promises -- use them from single-threaded tools only,
- * and restore the returned previous value.  The getters and fql_tune_gemm_i8_f32 keep no state.
+ * and restore the returned previous value.  The getters and fql_tune_gemm_i8_f32 / fql_tune_gemm_i8 keep no state.
  */
 #ifndef FQL_INT4_TUNE_H
 #define FQL_INT4_TUNE_H
@@ -21,6 +21,18 @@ FQL_API int fql_tune_gemm_i8_f32(int cfg, const int8_t *limbs, const float *delt
                                  const uint8_t *packed, const float *scales, const float *zps,
                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, float *out, int E,
                                  int T, int K, int N, int precision, void *stream, void *scratch, size_t scratch_bytes);
+/* fql_tune_gemm_i8_f32 with the rest of the epilogue: outputs of element type `out_dtype` (FQL_DTYPE_*), an optional
+ * `bias` [E][N] (one vector per expert, as the scales) and an optional `row_weight` [T], in that order:
+ * out = dtype(fl32(fl32(acc + bias) * row_weight)), one rounding per step.
+ * The kernels take the bias as a pointer but read a row's weight from the [T] plane behind delta's set(s),
+ * where the pre-pass of fql_moe_gather_scaled_fwd_f32 leaves it: a non-NULL `row_weight` must be that plane, i.e.
+ * delta + sets * T (sets = 2 for 2 / 3 limbs, else 1), or the call returns FQL_ERR_ALIGNMENT.  Uncovered rows of a
+ * grouped problem are left as they are. */
+FQL_API int fql_tune_gemm_i8(int cfg, const int8_t *limbs, const float *delta, const int32_t *rowsum,
+                             const uint8_t *packed, const float *scales, const float *zps,
+                             const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                             const float *bias, const float *row_weight, int E, int T, int K, int N, int precision,
+                             void *stream, void *scratch, size_t scratch_bytes);
 /* the id the product path picks for a shape (grouped: rows are spread over E experts) */
 FQL_API int fql_tune_chosen_cfg(int precision, int E, int T, int K, int N, int grouped);
 FQL_API int fql_tune_num_configs(void);                 /* wide ids run 0 .. this - 1; not every id is built for every precision: */
