@@ -84,9 +84,10 @@ __device__ __forceinline__ float act_widen(unsigned short h)
     return __uint_as_float((uint32_t)h << 16);
 }
 
-// GATE (float32 input only): the source row is [gate (K) | up (K)] and the value that gets quantised is
+// GATE: the source row is [gate (K) | up (K)] and the value that gets quantised is
 // silu(gate[k]) * up[k] -- the elementwise step between the two GEMMs of a gated FFN expert fused into the
 // second GEMM's pre-pass, so the [T, K] hidden activation is never materialised.
+// A 16-bit gate|up row is widened in registers first, so the limbs are those of the float32 call on the widened row.
 // (act_silu_mul itself lives in fql_common.h: the adapter kernels of fql_lora.h form the same h from the same function.)
 
 // ---- pieces shared by the pre-pass kernels (this file and fql_act_f8.h)
@@ -260,7 +261,6 @@ __device__ __forceinline__ void act_rows(
     // the expert table's first 64 entries: loaded now, scanned when the loads of x are on their way
     int off_raw = 0, cnt_raw = 0;
     if (tpe != nullptr && wave == 0) expert_chunk_load(tpe, offs, E, 0, lane, off_raw, cnt_raw);
-    static_assert(!GATE || IN == 0, "the gated pre-pass takes float32 rows");
     const char *xr = reinterpret_cast<const char *>(xin) +
                      (size_t)source_row(gather, n_src, trow < T ? trow : T - 1) * K * ES * (GATE ? 2 : 1);
     const int nch = KB * 16;                      // 16-float chunks per padded row
@@ -300,6 +300,19 @@ __device__ __forceinline__ void act_rows(
                 } else if (IN == 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xv[j][q] = *reinterpret_cast<const v4f *>(src + 16 * q);
+                } else if (GATE) {                // 16 halves of gate and 16 of up = two 16-byte loads each
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const v4i gr = *reinterpret_cast<const v4i *>(src + 16 * h);
+                        const v4i ur = *reinterpret_cast<const v4i *>(src + (size_t)K * 2 + 16 * h);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            xv[j][2 * h + (i >> 1)][2 * (i & 1)] =
+                                act_silu_mul(act_widen<IN>((unsigned short)((uint32_t)gr[i] & 0xFFFFu)), act_widen<IN>((unsigned short)((uint32_t)ur[i] & 0xFFFFu)));
+                            xv[j][2 * h + (i >> 1)][2 * (i & 1) + 1] =
+                                act_silu_mul(act_widen<IN>((unsigned short)((uint32_t)gr[i] >> 16)), act_widen<IN>((unsigned short)((uint32_t)ur[i] >> 16)));
+                        }
+                    }
                 } else {                          // 16 halves = two 16-byte loads
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -335,6 +348,7 @@ __device__ __forceinline__ void act_rows(
                         if (k < K) {
                             if (IN == 0 && GATE) v = act_silu_mul(reinterpret_cast<const float *>(xr)[k], reinterpret_cast<const float *>(xr)[K + k]);
                             else if (IN == 0) v = reinterpret_cast<const float *>(xr)[k];
+                            else if (GATE) v = act_silu_mul(act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]), act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[K + k]));
                             else v = act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]);
                             if constexpr (CS) {
                                 v = v * csr[k];

@@ -17,6 +17,7 @@
 #include "fql_quantize.h"
 #include "fql_routing.h"
 #include "fql_w4_launch.h"
+#include "fql_ffn16_launch.h"
 #include <atomic>
 #include <random>
 
@@ -237,6 +238,12 @@ int launch_act_quant(const void *x, int in_dtype, const int32_t *gather, int n_s
     const bool single = vec && mblocks * FQL_MB <= g_act_single_rows;
     const int rblocks = single ? T : (T + ACT_ROWS - 1) / ACT_ROWS;
     const int zblocks = (tpe != nullptr && out != nullptr) ? (T + 255) / 256 : 0;
+    if (gated && !f8out && in_dtype != FQL_DTYPE_F32) {     // 16-bit gate|up rows: the instantiations of fql_ffn16.hip
+        if (gather != nullptr) return FQL_ERR_DTYPE;
+        FqlActGatedArgs a{x, w.delta, w.rowsum, w.limbs, T, K, Kp / FQL_KB, MBT, rblocks, zblocks, out, dtype_bytes(out_dtype), N,
+                          tpe, offs, E, w.row_weight, st};
+        return fql_act_gated16_launch(L, single ? 0 : (vec ? 1 : 2), in_dtype, a) == 0 ? FQL_OK : FQL_ERR_LAUNCH;
+    }
     void (*kern)(const void *, const int32_t *, int, float *, int32_t *, int8_t *, int, int, int, int, int, void *, int,
                  int, const int32_t *, const int32_t *, int, const float *);
 #define FQL_ACT_PICK(l, in, gate, f8) \
@@ -1058,6 +1065,31 @@ int fql_moe_gated_fwd_f32(const uint8_t *packed, const float *scales, const floa
     if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
     return run_mfma(L, gate_up, FQL_DTYPE_F32, nullptr, 0, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert,
                     input_offsets, E, T, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), true);
+}
+
+// fql_moe_gated_fwd_f32 with an element type for gate_up and one for out: the pre-pass loads 16-bit gate|up rows as they are
+// (fql_ffn16.hip), the GEMM's epilogue rounds a 16-bit out once.
+int fql_moe_gated_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up, int in_dtype,
+                      const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E, int T,
+                      int K, int N, int precision, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32)
+        return fql_moe_gated_fwd_f32(packed, scales, zps, static_cast<const float *>(gate_up), tokens_per_expert, input_offsets,
+                                     static_cast<float *>(out), E, T, K, N, precision, workspace, workspace_bytes, stream);
+    const int L = limbs_of(precision);
+    if (L < 0 || is_f8(precision)) return FQL_ERR_BAD_PRECISION;
+    if (E <= 0 || T < 0 || K <= 0 || N < 0) return FQL_ERR_BAD_SHAPE;
+    if (K & 1) return FQL_ERR_ODD_K;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!packed || !scales || !zps || !gate_up || !out) return FQL_ERR_NULL_POINTER;
+    if ((tokens_per_expert == nullptr) != (input_offsets == nullptr)) return FQL_ERR_NULL_POINTER;
+    if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
+    if ((reinterpret_cast<uintptr_t>(gate_up) & (dtype_bytes(in_dtype) - 1)) != 0) return FQL_ERR_ALIGNMENT;
+    return run_mfma(L, gate_up, in_dtype, nullptr, 0, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E,
+                    T, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), true);
 }
 
 int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int top_k, int E, int32_t *counts,

@@ -30,7 +30,7 @@
 // order are those of the float32 kernel at the same VEC, and a 16-bit call returns the bits of the float32 call on the
 // widened operand (rounded once, for expand).  [T][r] tensors, adapter weights and their gradients are always float32.
 //
-// GATE (shrink and grad; float32 only): the streamed operand is the [T][2C] gate|up tensor of a gated FFN expert and the value that
+// GATE (shrink and grad; any element type): the streamed operand is the [T][2C] gate|up tensor of a gated FFN expert and the value that
 // enters the sums is h[t][c] = act_silu_mul(gate_up[t][c], gate_up[t][C + c]) -- the function the down GEMM's
 // activation pre-pass calls (fql_common.h), so the down adapter sees the h the INT4 GEMM consumed and the [T][C]
 // hidden activation is never written.  Only the operand load differs: tiles, lanes and reduction orders are the same
@@ -125,17 +125,16 @@ __device__ __forceinline__ void store_elems(void *base, size_t i, const float (&
     }
 }
 
-// VEC operand values of row t at column c: the floats of a [T][C] tensor, or with GATE the hidden activation formed
-// from the gate half (columns [0, C)) and the up half ([C, 2C)) of row t of a [T][2C] gate|up tensor.
+// VEC operand values of row t at column c: the elements of a [T][C] tensor, or with GATE the hidden activation formed
+// from the gate half (columns [0, C)) and the up half ([C, 2C)) of row t of a [T][2C] gate|up tensor (16-bit halves are
+// widened first: h is the float32 act_silu_mul of the widened values).
 template <int VEC, bool GATE, int DT = 0>
 __device__ __forceinline__ void load_operand(const void *pv, int t, int C, int c, float (&v)[VEC])
 {
-    static_assert(!GATE || DT == 0, "the gated operand is float32");
     if constexpr (GATE) {
-        const float *p = reinterpret_cast<const float *>(pv);
         float g[VEC], u[VEC];
-        load_vec<VEC>(p + (size_t)t * 2 * C + c, g);
-        load_vec<VEC>(p + (size_t)t * 2 * C + C + c, u);
+        load_elems<VEC, DT>(pv, (size_t)t * 2 * C + c, g);
+        load_elems<VEC, DT>(pv, (size_t)t * 2 * C + C + c, u);
 #pragma unroll
         for (int i = 0; i < VEC; ++i) v[i] = act_silu_mul(g[i], u[i]);
     } else {
@@ -484,6 +483,32 @@ __global__ __launch_bounds__(FQL_SWIGLU_BWD_THREADS) void swiglu_bwd_kernel(
     }
     store_vec<VEC>(dgu + o, dg);
     store_vec<VEC>(dgu + o + F, du);
+}
+
+// The same pass with an element type for each tensor (DG: gate_up, DD: dh, DO: dgate_up): typed loads, the float32
+// arithmetic of swiglu_bwd_kernel term for term, one rounding on the store (store_elems pins the float32 value before a
+// float16 conversion).  VEC counts elements.
+template <int VEC, int DG, int DD, int DO>
+__global__ __launch_bounds__(FQL_SWIGLU_BWD_THREADS) void swiglu_bwd_typed_kernel(
+    const void *__restrict__ gu, const void *__restrict__ dh, void *__restrict__ dgu, int T, int F)
+{
+    const int per_row = F / VEC;
+    const long long q = (long long)blockIdx.x * FQL_SWIGLU_BWD_THREADS + threadIdx.x;
+    if (q >= (long long)T * per_row) return;
+    const int t = (int)(q / per_row), c = (int)(q % per_row) * VEC;
+    const size_t o = (size_t)t * 2 * F + c;
+    float g[VEC], u[VEC], d[VEC], dg[VEC], du[VEC];
+    load_elems<VEC, DG>(gu, o, g);
+    load_elems<VEC, DG>(gu, o + F, u);
+    load_elems<VEC, DD>(dh, (size_t)t * F + c, d);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const float sig = 1.0f / (1.0f + expf(-g[i]));
+        dg[i] = d[i] * u[i] * (sig * (1.0f + g[i] * (1.0f - sig)));
+        du[i] = d[i] * (g[i] * sig);
+    }
+    store_elems<VEC, DO>(dgu, o, dg);
+    store_elems<VEC, DO>(dgu, o + F, du);
 }
 
 }  // namespace lora

@@ -12,7 +12,9 @@ rounded once; ``lora_A`` / ``lora_B`` and their gradients stay float32, and the 
 
 ``LoRAQuantizedMoEFFN`` puts an adapter on each projection of the gated experts of ``QuantizedMoEFFN``: one on the
 stacked gate|up weight (one ``A`` shared by gate and up, a ``[2F, r]`` ``B``: PEFT's shape for a fused ``gate_up_proj``)
-and one on the down weight (ops.moe_ffn_lora_forward).
+and one on the down weight (ops.moe_ffn_lora_forward).  Built with ``activation_dtype`` =
+torch.float16 / torch.bfloat16 it runs on 16-bit activations and keeps ``gate_up`` in that type (INTEGRATION.md
+section 9); by default it is the float32 layer.
 """
 from __future__ import annotations
 
@@ -133,11 +135,11 @@ _FFN_ADAPTERS = ("gate_up_lora_A", "gate_up_lora_B", "down_lora_A", "down_lora_B
 class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     """``down(silu(gate(x)) * up(x))`` per expert with ``gate_up = W_gu x + s B_gu (A_gu x)`` and
     ``y = W_d h + s B_d (A_d h)``, ``s = alpha / rank``.  The INT4 buffers are frozen; the four adapters are the only
-    parameters."""
+    parameters (float32 whatever ``activation_dtype`` is)."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
-                 precision: str = "default"):
-        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision)
+                 precision: str = "default", activation_dtype=None):
+        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision, activation_dtype=activation_dtype)
         _check_rank(rank)
         self.rank = rank
         self.alpha = float(rank if alpha is None else alpha)
@@ -159,9 +161,14 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
         nn.init.zeros_(self.down_lora_B)
 
     @classmethod
-    def from_quantized(cls, layer: QuantizedMoEFFN, rank: int, alpha: float | None = None) -> "LoRAQuantizedMoEFFN":
-        """Wrap an existing ``QuantizedMoEFFN``; the new module shares its buffers (no copy)."""
-        module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision)
+    def from_quantized(cls, layer: QuantizedMoEFFN, rank: int, alpha: float | None = None,
+                       activation_dtype=None) -> "LoRAQuantizedMoEFFN":
+        """Wrap an existing ``QuantizedMoEFFN``; the new module shares its buffers (no copy).  ``activation_dtype``
+        None keeps the wrapped layer's."""
+        if activation_dtype is None:
+            activation_dtype = layer.activation_dtype
+        module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision,
+                     activation_dtype=activation_dtype)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
         dev = layer.gate_up_packed.device
@@ -174,14 +181,16 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
         return {k: v for k, v in self.state_dict().items() if k in _FFN_ADAPTERS}
 
     def forward(self, inputs, tokens_per_expert, input_offsets):
-        """inputs ``[T, H]`` float32 on the GPU, rows grouped by expert -> ``[T, H]`` float32 (GPU only)."""
+        """inputs ``[T, H]`` float32 on the GPU, rows grouped by expert -> ``[T, H]`` float32 (GPU only); with
+        ``activation_dtype`` both have that type."""
         if not inputs.is_cuda:
             raise RuntimeError("LoRAQuantizedMoEFFN runs on the GPU (the product path has no CPU fallback)")
         from . import ops
         return ops.moe_ffn_lora_forward(self.gate_up_packed, self.gate_up_scales, self.gate_up_zero_points,
                                         self.down_packed, self.down_scales, self.down_zero_points, inputs,
                                         self.gate_up_lora_A, self.gate_up_lora_B, self.down_lora_A, self.down_lora_B,
-                                        self.scaling, tokens_per_expert, input_offsets, precision=self.precision)
+                                        self.scaling, tokens_per_expert, input_offsets, precision=self.precision,
+                                        activation_dtype=self.activation_dtype)
 
     def extra_repr(self) -> str:
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "

@@ -212,12 +212,19 @@ class QuantizedMoEFFN(nn.Module):
         so the ``[T, F]`` hidden activation never exists in memory.
 
     Weights are quantised per output row with ``quantize_weights`` (per-row scale / zero point, as
-    ``QuantizedMoEExpert.from_fp16`` does)."""
+    ``QuantizedMoEExpert.from_fp16`` does).
 
-    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, precision: str = "default"):
+    ``activation_dtype`` (None / torch.float32: the float32 layer, unchanged) = torch.float16 / torch.bfloat16 runs the
+    layer on 16-bit activations: inputs and the incoming gradient have that type, ``gate_up`` is written (and kept for
+    the backward) in it, and the output and the input gradient come back in it.  That rounds ``gate_up`` between the two
+    projections, which the float32 layer does not do: a memory-for-precision choice, so it is opt-in."""
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, precision: str = "default",
+                 activation_dtype=None):
         super().__init__()
         assert hidden_dim % 32 == 0 and ffn_dim % 32 == 0, "hidden_dim and ffn_dim must be multiples of 32"
         self.num_experts, self.hidden_dim, self.ffn_dim, self.precision = num_experts, hidden_dim, ffn_dim, precision
+        self.activation_dtype = _activation_dtype(activation_dtype, precision)
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_packed", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
         self.register_buffer("gate_up_scales", torch.zeros(E, 2 * F, dtype=torch.float32))
@@ -228,11 +235,11 @@ class QuantizedMoEFFN(nn.Module):
 
     @classmethod
     def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor],
-                     precision: str = "default") -> "QuantizedMoEFFN":
+                     precision: str = "default", activation_dtype=None) -> "QuantizedMoEFFN":
         """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` (nn.Linear weight layout)."""
         E = len(gate)
         F, H = gate[0].shape
-        m = cls(E, H, F, precision)
+        m = cls(E, H, F, precision, activation_dtype=activation_dtype)
         gu = [quantize_weights(torch.cat([g.float(), u.float()], dim=0)) for g, u in zip(gate, up)]
         dn = [quantize_weights(d.float()) for d in down]
         m.gate_up_packed = torch.stack([t[0] for t in gu])
@@ -244,10 +251,16 @@ class QuantizedMoEFFN(nn.Module):
         return m
 
     def forward(self, inputs, tokens_per_expert, input_offsets):
-        """inputs ``[T, H]`` float32 rows grouped by expert -> ``[T, H]`` float32."""
+        """inputs ``[T, H]`` float32 rows grouped by expert -> ``[T, H]`` float32 (``activation_dtype``: both in
+        that type)."""
         if not inputs.is_cuda:
             raise RuntimeError("QuantizedMoEFFN runs on the GPU (the product path has no CPU fallback)")
         from . import ops
+        if self.activation_dtype is not None:
+            ops.check_activation_rows(inputs, "inputs", self.activation_dtype)
+            if torch.is_grad_enabled() and inputs.requires_grad:
+                return _GatedFFN16Fn.apply(inputs, tokens_per_expert, input_offsets, self)
+            return _gated_ffn16(self, inputs, tokens_per_expert, input_offsets)[0]
         if torch.is_grad_enabled() and inputs.requires_grad:
             return _GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self)
         gate_up = ops.moe_forward(self.gate_up_packed, self.gate_up_scales, self.gate_up_zero_points, inputs, None,
@@ -258,6 +271,53 @@ class QuantizedMoEFFN(nn.Module):
     @property
     def total_memory_bytes(self) -> int:
         return sum(b.numel() * b.element_size() for b in self.buffers())
+
+
+def _activation_dtype(activation_dtype, precision):
+    from . import ops
+    dt = ops.activation_dtype_of(activation_dtype)
+    if dt is not None and precision in ("fp8", 8):
+        raise ValueError("precision='fp8' has no gated forward and no backward: it cannot be combined with a 16-bit "
+                         "activation_dtype")
+    return dt
+
+
+def _gated_ffn16(m, inputs, tpe, offs):
+    """(y, gate_up), both in the layer's 16-bit type: each GEMM reads its operand as it is and rounds its result once."""
+    from . import ops
+    dt = m.activation_dtype
+    gate_up = ops.moe_forward_any(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe, offs,
+                                  precision=m.precision, out_dtype=dt)
+    return ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up, tpe, offs,
+                                 precision=m.precision, out_dtype=dt), gate_up
+
+
+class _GatedFFN16Fn(torch.autograd.Function):
+    """``QuantizedMoEFFN`` on 16-bit activations with the input gradient.  Keeps ``gate_up`` in the 16-bit type; the
+    backward is ``dh`` on the down weights, ``ops.swiglu_backward`` and ``dx`` on the gate / up weights, each tensor
+    written once in that type."""
+
+    @staticmethod
+    def forward(ctx, inputs, tokens_per_expert, input_offsets, m):
+        out, gate_up = _gated_ffn16(m, inputs, tokens_per_expert, input_offsets)
+        ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        gate_up, tpe, offs = ctx.saved_tensors
+        m = ctx.m
+        dt = m.activation_dtype
+        ops.check_activation_rows(gy, "the incoming gradient", dt)
+        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
+                                    precision=m.precision, out_dtype=dt)
+        dgu = ops.swiglu_backward(gate_up, dh, out_dtype=dt)
+        dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
+                                    precision=m.precision, out_dtype=dt)
+        return dx, None, None, None
 
 
 class _GatedFFNFn(torch.autograd.Function):

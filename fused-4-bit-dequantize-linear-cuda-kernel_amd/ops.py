@@ -413,13 +413,18 @@ def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, t
 
 
 def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_expert, input_offsets,
-                      precision="default"):
+                      precision="default", out_dtype=None):
     """Second GEMM of a gated FFN expert with the activation fused into its pre-pass:
-    ``out[t] = W_e @ (silu(gate_up[t, :K]) * gate_up[t, K:])``; ``gate_up`` [T, 2K] float32 (the output of the
-    fused gate|up projection), ``packed_weights`` [E, N, K/2].  The [T, K] hidden activation is never written."""
+    ``out[t] = W_e @ (silu(gate_up[t, :K]) * gate_up[t, K:])``; ``gate_up`` [T, 2K] float32 / float16 / bfloat16 (the
+    output of the fused gate|up projection), ``packed_weights`` [E, N, K/2].  The [T, K] hidden activation is never
+    written.  The result has ``out_dtype`` (default: ``gate_up``'s type); a 16-bit ``gate_up`` is read as it is and a
+    16-bit result is rounded once: bit for bit ``moe_gated_forward(gate_up.float()).to(out_dtype)``."""
     _forward_only("moe_gated_forward", gate_up)
-    if not gate_up.is_cuda or gate_up.dtype != torch.float32 or gate_up.dim() != 2:
-        raise RuntimeError("gate_up must be a CUDA float32 [T, 2K] tensor")
+    if not gate_up.is_cuda or gate_up.dtype not in _DTYPES or gate_up.dim() != 2:
+        raise RuntimeError("gate_up must be a CUDA float32 (or float16 / bfloat16) [T, 2K] tensor")
+    out_dtype = gate_up.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
     T, K2 = gate_up.shape
     K = K2 // 2
     dev = gate_up.device
@@ -428,20 +433,31 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
     E, N = _check_grouped_weights(packed_weights, scales, zero_points, dev, K)
     if tokens_per_expert.numel() != E or input_offsets.numel() != E:
         raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
+    L = _native.lib()
+    prec = _precision(precision)
+    packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
+    typed = gate_up.dtype != torch.float32 or out_dtype != torch.float32
+    if typed and T > 0 and L.fql_native_dtype_supported(T, E, K, N, prec, packed_weights_c.data_ptr(), 1) != 1:
+        # off the 16-bit MFMA path: widen and round around the float32 entry point (the same contract)
+        return moe_gated_forward(packed_weights, scales, zero_points, gate_up.float(), tokens_per_expert, input_offsets,
+                                 precision=precision, out_dtype=torch.float32).to(out_dtype)
     gate_up = gate_up.contiguous()
     tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
     offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    L = _native.lib()
-    prec = _precision(precision)
-    out = torch.empty((T, N), dtype=torch.float32, device=dev)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
     with torch.cuda.device(dev):
         ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, prec), dev)
-        packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
-        rc = L.fql_moe_gated_fwd_f32(packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                                     zero_points_c.data_ptr(), gate_up.data_ptr(), tpe.data_ptr(),
-                                     offs.data_ptr(), out.data_ptr(), E, T, K, N, prec,
+        if not typed:
+            rc = L.fql_moe_gated_fwd_f32(packed_weights_c.data_ptr(), scales_c.data_ptr(),
+                                         zero_points_c.data_ptr(), gate_up.data_ptr(), tpe.data_ptr(),
+                                         offs.data_ptr(), out.data_ptr(), E, T, K, N, prec,
+                                         ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
+        else:
+            rc = L.fql_moe_gated_fwd(packed_weights_c.data_ptr(), scales_c.data_ptr(), zero_points_c.data_ptr(),
+                                     gate_up.data_ptr(), _DTYPES[gate_up.dtype], tpe.data_ptr(), offs.data_ptr(),
+                                     out.data_ptr(), _DTYPES[out_dtype], E, T, K, N, prec,
                                      ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_gated_fwd_f32")
+    _native.check(rc, "fql_moe_gated_fwd" if typed else "fql_moe_gated_fwd_f32")
     return out
 
 
@@ -1358,7 +1374,7 @@ class _MoELoRAFn(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 
 def _gate_up_rows(gate_up, dev):
-    g = _lora_rows(gate_up, "gate_up", dev)
+    g = _lora_rows(gate_up, "gate_up", dev, wide=True)
     if g.shape[1] % 2:
         raise RuntimeError("gate_up must be [T, 2C] (gate | up)")
     return g, g.shape[0], g.shape[1] // 2
@@ -1366,7 +1382,8 @@ def _gate_up_rows(gate_up, dev):
 
 def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
     """``lora_shrink`` on the hidden activation of a gated FFN expert without materialising it:
-    ``out[t] = scale * (silu(gate_up[t, :C]) * gate_up[t, C:]) @ W_e^T`` -> [T, r]; ``gate_up`` [T, 2C] float32."""
+    ``out[t] = scale * (silu(gate_up[t, :C]) * gate_up[t, C:]) @ W_e^T`` -> [T, r] float32; ``gate_up`` [T, 2C]
+    float32, or float16 / bfloat16 read as it is: bit for bit the call on ``gate_up.float()``."""
     dev = gate_up.device
     g, T, C = _gate_up_rows(gate_up, dev)
     w, E, r = _lora_weight(weight, layout, C, dev, "weight")
@@ -1377,17 +1394,24 @@ def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, inpu
     if C == 0:
         return out.zero_()
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_gated_shrink_f32(g.data_ptr(), w.data_ptr(), _lora_layout(layout),
+        if g.dtype == torch.float32:
+            rc = _native.lib().fql_lora_gated_shrink_f32(g.data_ptr(), w.data_ptr(), _lora_layout(layout),
+                                                         None if tpe is None else tpe.data_ptr(),
+                                                         None if offs is None else offs.data_ptr(), out.data_ptr(), E,
+                                                         T, C, r, float(scale), _stream_ptr(dev))
+        else:
+            rc = _native.lib().fql_lora_gated_shrink(g.data_ptr(), _DTYPES[g.dtype], w.data_ptr(), _lora_layout(layout),
                                                      None if tpe is None else tpe.data_ptr(),
                                                      None if offs is None else offs.data_ptr(), out.data_ptr(), E, T,
                                                      C, r, float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_gated_shrink_f32")
+    _native.check(rc, "fql_lora_gated_shrink")
     return out
 
 
 def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
     """``lora_grad`` with ``p = silu(gate_up[:, :C]) * gate_up[:, C:]`` formed on the fly: ``gate_up`` [T, 2C],
-    ``v`` [T, r] -> [E, C, r] (``layout='cr'``) or [E, r, C] (``'rc'``: dA of the down adapter)."""
+    ``v`` [T, r] -> [E, C, r] (``layout='cr'``) or [E, r, C] (``'rc'``: dA of the down adapter), float32.  ``gate_up``
+    may be float16 / bfloat16: read as it is, bit for bit the call on ``gate_up.float()``."""
     dev = gate_up.device
     g, T, C = _gate_up_rows(gate_up, dev)
     vv = _lora_rows(v, "v", dev)
@@ -1406,43 +1430,86 @@ def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, i
     if vv.data_ptr() % 16:
         vv = vv.clone()
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_gated_grad_f32(g.data_ptr(), vv.data_ptr(),
+        if g.dtype == torch.float32:
+            rc = _native.lib().fql_lora_gated_grad_f32(g.data_ptr(), vv.data_ptr(),
+                                                       None if tpe is None else tpe.data_ptr(),
+                                                       None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E,
+                                                       T, C, r, float(scale), _stream_ptr(dev))
+        else:
+            rc = _native.lib().fql_lora_gated_grad(g.data_ptr(), _DTYPES[g.dtype], vv.data_ptr(),
                                                    None if tpe is None else tpe.data_ptr(),
                                                    None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T,
                                                    C, r, float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_gated_grad_f32")
+    _native.check(rc, "fql_lora_gated_grad")
     return d
 
 
-def swiglu_backward(gate_up, dh):
-    """Backward of ``h = silu(g) * u`` in one pass: ``gate_up`` [T, 2F] = [g | u] and ``dh`` [T, F] float32 ->
-    ``[dg | du]`` [T, 2F] with ``dg = dh * u * silu'(g)``, ``du = dh * silu(g)``."""
+def swiglu_backward(gate_up, dh, out_dtype=None):
+    """Backward of ``h = silu(g) * u`` in one pass: ``gate_up`` [T, 2F] = [g | u] and ``dh`` [T, F] ->
+    ``[dg | du]`` [T, 2F] with ``dg = dh * u * silu'(g)``, ``du = dh * silu(g)``.  Each of ``gate_up``, ``dh`` and the
+    result (``out_dtype``, default ``gate_up``'s type) may be float32, float16 or bfloat16: float32 arithmetic on the
+    widened values, bit for bit ``swiglu_backward(gate_up.float(), dh.float()).to(out_dtype)``."""
     dev = gate_up.device
     g, T, F = _gate_up_rows(gate_up, dev)
-    d = _lora_rows(dh, "dh", dev)
+    d = _lora_rows(dh, "dh", dev, wide=True)
     if tuple(d.shape) != (T, F):
         raise RuntimeError(f"dh must be [{T}, {F}] for gate_up [{T}, {2 * F}]")
-    out = torch.empty((T, 2 * F), dtype=torch.float32, device=dev)
+    out_dtype = g.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    out = torch.empty((T, 2 * F), dtype=out_dtype, device=dev)
     if T == 0 or F == 0:
         return out
     with torch.cuda.device(dev):
-        rc = _native.lib().fql_swiglu_bwd_f32(g.data_ptr(), d.data_ptr(), out.data_ptr(), T, F, _stream_ptr(dev))
-    _native.check(rc, "fql_swiglu_bwd_f32")
+        if g.dtype == d.dtype == out_dtype == torch.float32:
+            rc = _native.lib().fql_swiglu_bwd_f32(g.data_ptr(), d.data_ptr(), out.data_ptr(), T, F, _stream_ptr(dev))
+        else:
+            rc = _native.lib().fql_swiglu_bwd(g.data_ptr(), _DTYPES[g.dtype], d.data_ptr(), _DTYPES[d.dtype],
+                                              out.data_ptr(), _DTYPES[out_dtype], T, F, _stream_ptr(dev))
+    _native.check(rc, "fql_swiglu_bwd")
     return out
+
+
+def activation_dtype_of(activation_dtype):
+    """The ``activation_dtype`` argument of the gated FFN layers: None / float32 (the float32 layer) or a 16-bit type."""
+    if activation_dtype is None or activation_dtype == torch.float32:
+        return None
+    if activation_dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"activation_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got "
+                         f"{activation_dtype!r}")
+    return activation_dtype
+
+
+def check_activation_rows(t, name, dt):
+    """A [T, .] tensor of a gated FFN layer built with a 16-bit ``activation_dtype``: that type, on the GPU, 2-D."""
+    if not t.is_cuda or t.dim() != 2 or t.dtype != dt:
+        raise RuntimeError(f"{name} must be a CUDA {dt} 2-D tensor: the layer was built with activation_dtype={dt}, so "
+                           f"pass {name}.to({dt}) (or build the layer without activation_dtype for float32 "
+                           f"activations); got {t.dtype}")
 
 
 def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps, inputs,
                          gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert,
-                         input_offsets, precision="default"):
+                         input_offsets, precision="default", activation_dtype=None):
     """Gated INT4 FFN experts with a low-rank adapter on each projection: for the rows t of expert e,
     ``gu = W_gu x + s B_gu (A_gu x)``, ``h = silu(gu[:F]) * gu[F:]`` (never stored), ``y = W_d h + s B_d (A_d h)``; rows
     no expert covers are zero.  ``inputs`` [T, H] float32, stacked gate|up weights [E, 2F, H/2], down weights
     [E, H, F/2], ``gate_up_lora_A`` [E, r, H], ``gate_up_lora_B`` [E, 2F, r], ``down_lora_A`` [E, r, F],
-    ``down_lora_B`` [E, H, r].  Per-row INT4 weights only.  Differentiable (once) in ``inputs`` and the four adapters."""
-    if not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
-        raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor: the gated FFN adapters are float32 only (16-bit "
-                           "activations need a 16-bit gate_up through the gated GEMM's pre-pass, the gated shrink / grad "
-                           "and swiglu_backward: not built yet)")
+    ``down_lora_B`` [E, H, r].  Per-row INT4 weights only.  Differentiable (once) in ``inputs`` and the four adapters.
+
+    ``activation_dtype`` = torch.float16 / torch.bfloat16 is the memory-for-precision form: ``inputs`` and the incoming
+    gradient have that type, ``gate_up`` is stored (and saved) in it, ``y`` and ``inputs.grad`` come back in it; the
+    adapters and their gradients stay float32.  Five tensors are rounded, once each."""
+    dt = activation_dtype_of(activation_dtype)
+    if dt is not None:
+        check_activation_rows(inputs, "inputs", dt)
+        if _precision(precision) == _native.PRECISION_FP8:
+            raise RuntimeError("precision='fp8' has no gated forward and no backward: not available with a 16-bit "
+                               "activation_dtype either")
+    elif not inputs.is_cuda or inputs.dtype != torch.float32 or inputs.dim() != 2:
+        raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor: without activation_dtype the gated FFN adapters "
+                           "are float32 only (pass activation_dtype=torch.float16 / torch.bfloat16 to run the layer on "
+                           "16-bit activations; gate_up is then rounded to that type between the two projections)")
     if gate_up_packed.dim() != 3 or gate_up_scales.dim() != 2 or down_packed.dim() != 3 or down_scales.dim() != 2:
         raise RuntimeError("moe_ffn_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points "
                            "[E, N]")
@@ -1457,15 +1524,25 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
     adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
     if _wants_grad(inputs, *adapters):
         return _MoEFFNLoRAFn.apply(inputs, *adapters, *weights, tokens_per_expert, input_offsets, float(scaling),
-                                   precision)
+                                   precision, dt)
     return _moe_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets,
-                               precision)[0]
+                               precision, dt)[0]
 
 
-def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision):
-    """Returns (y, gate_up, U_gu, U_d): both projections with their adapters expanded in place into the base outputs."""
+def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision, dt=None):
+    """Returns (y, gate_up, U_gu, U_d): both projections with their adapters expanded in place into the base outputs.
+    ``dt`` (a 16-bit type): each base GEMM reads its 16-bit operand as it is and writes float32, and the expand writes
+    that plus the adapter term once in ``dt`` -- gate_up (rounding 1) and y (rounding 2)."""
     gup, gus, guz, dp, ds, dz = weights
     A_gu, B_gu, A_d, B_d = adapters
+    if dt is not None:
+        gu32 = moe_forward_any(gup, gus, guz, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
+        u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
+        gate_up = lora_expand(u_gu, B_gu, "cr", tpe, offs, scale=scaling, input=gu32, out_dtype=dt)
+        del gu32
+        y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32)
+        u_d = lora_gated_shrink(gate_up, A_d, "rc", tpe, offs)
+        return lora_expand(u_d, B_d, "cr", tpe, offs, scale=scaling, input=y32, out_dtype=dt), gate_up, u_gu, u_d
     gate_up = moe_forward(gup, gus, guz, inputs, None, tpe, offs, precision=precision)
     u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
     lora_expand(u_gu, B_gu, "cr", tpe, offs, scale=scaling, input=gate_up, out=gate_up)
@@ -1477,15 +1554,16 @@ def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision
 
 class _MoEFFNLoRAFn(torch.autograd.Function):
     """The whole gated FFN block + its two adapters in one node.  Saves inputs [T, H], gate_up [T, 2F], U_gu and U_d
-    ([T, r]), the tables and the parameters: nothing of shape [T, F]."""
+    ([T, r]), the tables and the parameters: nothing of shape [T, F].  With a 16-bit ``dt`` inputs and gate_up are saved
+    in that type (U_gu, U_d float32): T (2H + 4F + 8r) bytes."""
 
     @staticmethod
-    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision):
+    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision, dt=None):
         x = inputs.contiguous()
         y, gate_up, u_gu, u_d = _moe_ffn_lora_apply((gup, gus, guz, dp, ds, dz), x, (A_gu, B_gu, A_d, B_d), scaling,
-                                                    tpe, offs, precision)
+                                                    tpe, offs, precision, dt)
         ctx.save_for_backward(x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs)
-        ctx.scaling, ctx.precision = scaling, precision
+        ctx.scaling, ctx.precision, ctx.act_dtype = scaling, precision, dt
         return y
 
     @staticmethod
@@ -1494,6 +1572,9 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
         x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
         need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
         E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
+        if ctx.act_dtype is not None:
+            check_activation_rows(gy, "the incoming gradient", ctx.act_dtype)
+            return _moe_ffn_lora_backward16(ctx, gy.contiguous(), ctx.act_dtype) + (None,) * 11
         g = gy.to(torch.float32).contiguous()
         gx = gAgu = gBgu = gAd = gBd = None
         if need_Bd:
@@ -1517,4 +1598,37 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
                     lora_expand(du_gu, A_gu, "rc", tpe, offs, input=gx, out=gx)          # dx = dgu W_gu + dU_gu A_gu
                 if need_Agu:
                     gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
-        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 10
+        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 11
+
+
+def _moe_ffn_lora_backward16(ctx, g, dt):
+    """The backward of the node on 16-bit activations: every kernel reads its 16-bit operand as it is; the base input
+    gradients are float32 and the expand writes dh (rounding 3) and dx (rounding 5) once in ``dt``; swiglu_backward writes
+    dgu in ``dt`` (rounding 4).  Adapter gradients are float32."""
+    x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
+    need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
+    E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
+    gx = gAgu = gBgu = gAd = gBd = None
+    if need_Bd:
+        gBd = lora_grad(g, u_d, "cr", E, tpe, offs, scale=s)                         # dB_d = s dY^T U_d
+    through = need_x or need_Agu or need_Bgu                                        # anything upstream of h
+    if through or need_Ad:
+        du_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dU_d = s dY B_d
+        if need_Ad:
+            gAd = lora_gated_grad(gate_up, du_d, "rc", E, tpe, offs)                 # dA_d = dU_d^T h
+    if through:
+        dh32 = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)          # dh = dY W_d (float32)
+        dh = lora_expand(du_d, A_d, "rc", tpe, offs, input=dh32, out_dtype=dt)       #      + dU_d A_d, in dt
+        del dh32
+        dgu = swiglu_backward(gate_up, dh, out_dtype=dt)
+        del dh
+        if need_Bgu:
+            gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
+        if need_x or need_Agu:
+            du_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dU_gu = s dgu B_gu
+            if need_x:
+                gx32 = moe_backward_input(gup, gus, guz, dgu, tpe, offs, precision=prec)
+                gx = lora_expand(du_gu, A_gu, "rc", tpe, offs, input=gx32, out_dtype=dt)   # dx = dgu W_gu + dU_gu A_gu
+            if need_Agu:
+                gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
+    return gx, gAgu, gBgu, gAd, gBd

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 250 /* 0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 260 /* 0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -510,6 +510,45 @@ FQL_API int fql_lora_gated_grad_f32(const float *gate_up, const float *v, const 
                                     const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
                                     float scale, void *stream);
 FQL_API int fql_swiglu_bwd_f32(const float *gate_up, const float *dh, float *dgate_up, int T, int F, void *stream);
+
+/* ---- the gated FFN experts on float16 / bfloat16 activations (FQL_VERSION 260) ----
+ * The four entry points above with an element type (FQL_DTYPE_F32 / _F16 / _BF16) for every [T][.] activation tensor.
+ * One contract, that of the typed adapter entry points: a call returns, bit for bit, what the _f32 entry point returns
+ * on the exactly widened operands, a 16-bit output rounded once to nearest even as Tensor.to(dtype) rounds (float16
+ * overflow gives inf).  16-bit elements are widened in registers on load; h = silu(g) * u is the float32 act_silu_mul of
+ * the widened values, so the INT4 GEMM and the down adapter still see the same bits of h.  All-float32 calls are
+ * forwarded to the _f32 entry points.
+ *
+ * fql_moe_gated_fwd: fql_moe_gated_fwd_f32 with gate_up [T][2K] of in_dtype and out [T][N] of out_dtype.  The limbs are
+ *   those of the float32 call on the widened gate_up; rows no expert covers are zeroed in out_dtype.  Workspace:
+ *   fql_moe_workspace_bytes(E, T, K, N, precision), unchanged.  Errors, in this order and all before any HIP call:
+ *   FQL_ERR_BAD_PRECISION (unknown, or FQL_PRECISION_FP8), FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0, N < 0),
+ *   FQL_ERR_ODD_K, FQL_ERR_DTYPE (an element type outside FQL_DTYPE_*), T == 0 or N == 0 -> FQL_OK with nothing done,
+ *   FQL_ERR_NULL_POINTER (a data pointer, or only one table pointer), FQL_ERR_BAD_SHAPE (no table with E != 1,
+ *   E > 65535), FQL_ERR_ALIGNMENT (K % 32 != 0, packed not 16-byte aligned, gate_up not aligned to its element),
+ *   FQL_ERR_WORKSPACE, FQL_ERR_LAUNCH.
+ * fql_lora_gated_shrink / fql_lora_gated_grad: the _f32 entry points with gate_up [T][2C] of `dtype`; out / v / d stay
+ *   float32.  The vector width, in ELEMENTS, is the widest (4, 2, 1) that gate_up, gate_up + C and the pitch 2 C all
+ *   allow at the element size, so a 16-byte aligned tensor takes the same width in every type and the tiles, the
+ *   column-to-lane mapping and every reduction order are those of the float32 kernel.  Errors: FQL_ERR_BAD_SHAPE as the
+ *   _f32 forms, then FQL_ERR_DTYPE, then the empty-call FQL_OK, FQL_ERR_NULL_POINTER, FQL_ERR_ALIGNMENT (w, or v and d,
+ *   not 16-byte aligned; gate_up not aligned to its element), FQL_ERR_LAUNCH.
+ * fql_swiglu_bwd: fql_swiglu_bwd_f32 with one element type each for gate_up, dh and dgate_up.  The arithmetic is the
+ *   float32 kernel's, term for term, on the widened values; a 16-bit dgate_up is rounded once.  Errors:
+ *   FQL_ERR_BAD_SHAPE as the _f32 form, FQL_ERR_DTYPE, the empty-call FQL_OK, FQL_ERR_NULL_POINTER, dgate_up == gate_up
+ *   -> FQL_ERR_BAD_SHAPE, a pointer not aligned to its element -> FQL_ERR_ALIGNMENT, FQL_ERR_LAUNCH. */
+FQL_API int fql_moe_gated_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up,
+                              int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                              int out_dtype, int E, int T, int K, int N, int precision, void *workspace,
+                              size_t workspace_bytes, void *stream);
+FQL_API int fql_lora_gated_shrink(const void *gate_up, int dtype, const float *w, int w_layout,
+                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, float *out, int E,
+                                  int T, int C, int r, float scale, void *stream);
+FQL_API int fql_lora_gated_grad(const void *gate_up, int dtype, const float *v, const int32_t *tokens_per_expert,
+                                const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
+                                float scale, void *stream);
+FQL_API int fql_swiglu_bwd(const void *gate_up, int dtype, const void *dh, int dh_dtype, void *dgate_up, int out_dtype,
+                           int T, int F, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
