@@ -255,18 +255,13 @@ class QuantizedMoEFFN(nn.Module):
         that type)."""
         if not inputs.is_cuda:
             raise RuntimeError("QuantizedMoEFFN runs on the GPU (the product path has no CPU fallback)")
-        from . import ops
         if self.activation_dtype is not None:
+            from . import ops
             ops.check_activation_rows(inputs, "inputs", self.activation_dtype)
-            if torch.is_grad_enabled() and inputs.requires_grad:
-                return _GatedFFN16Fn.apply(inputs, tokens_per_expert, input_offsets, self)
-            return _gated_ffn16(self, inputs, tokens_per_expert, input_offsets)[0]
         if torch.is_grad_enabled() and inputs.requires_grad:
-            return _GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self)
-        gate_up = ops.moe_forward(self.gate_up_packed, self.gate_up_scales, self.gate_up_zero_points, inputs, None,
-                                  tokens_per_expert, input_offsets, precision=self.precision)
-        return ops.moe_gated_forward(self.down_packed, self.down_scales, self.down_zero_points, gate_up,
-                                     tokens_per_expert, input_offsets, precision=self.precision)
+            fn = _GatedFFNFn if self.activation_dtype is None else _GatedFFN16Fn
+            return fn.apply(inputs, tokens_per_expert, input_offsets, self)
+        return _gated_ffn(self, inputs, tokens_per_expert, input_offsets)[0]
 
     @property
     def total_memory_bytes(self) -> int:
@@ -282,42 +277,19 @@ def _activation_dtype(activation_dtype, precision):
     return dt
 
 
-def _gated_ffn16(m, inputs, tpe, offs):
-    """(y, gate_up), both in the layer's 16-bit type: each GEMM reads its operand as it is and rounds its result once."""
+def _gated_ffn(m, inputs, tpe, offs):
+    """(y, gate_up) in the layer's activation type: the gate|up GEMM, then the down GEMM with silu(gate) * up fused into
+    its pre-pass.  On 16-bit activations each GEMM reads its operand as it is and rounds its result once."""
     from . import ops
     dt = m.activation_dtype
-    gate_up = ops.moe_forward_any(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe, offs,
-                                  precision=m.precision, out_dtype=dt)
+    if dt is None:                                          # the float32 layer takes float32 rows only
+        gate_up = ops.moe_forward(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe, offs,
+                                  precision=m.precision)
+    else:
+        gate_up = ops.moe_forward_any(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe,
+                                      offs, precision=m.precision, out_dtype=dt)
     return ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up, tpe, offs,
                                  precision=m.precision, out_dtype=dt), gate_up
-
-
-class _GatedFFN16Fn(torch.autograd.Function):
-    """``QuantizedMoEFFN`` on 16-bit activations with the input gradient.  Keeps ``gate_up`` in the 16-bit type; the
-    backward is ``dh`` on the down weights, ``ops.swiglu_backward`` and ``dx`` on the gate / up weights, each tensor
-    written once in that type."""
-
-    @staticmethod
-    def forward(ctx, inputs, tokens_per_expert, input_offsets, m):
-        out, gate_up = _gated_ffn16(m, inputs, tokens_per_expert, input_offsets)
-        ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
-        ctx.m = m
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy):
-        from . import ops
-        gate_up, tpe, offs = ctx.saved_tensors
-        m = ctx.m
-        dt = m.activation_dtype
-        ops.check_activation_rows(gy, "the incoming gradient", dt)
-        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
-                                    precision=m.precision, out_dtype=dt)
-        dgu = ops.swiglu_backward(gate_up, dh, out_dtype=dt)
-        dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
-                                    precision=m.precision, out_dtype=dt)
-        return dx, None, None, None
 
 
 class _GatedFFNFn(torch.autograd.Function):
@@ -327,11 +299,7 @@ class _GatedFFNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, tokens_per_expert, input_offsets, m):
-        from . import ops
-        gate_up = ops.moe_forward(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None,
-                                  tokens_per_expert, input_offsets, precision=m.precision)
-        out = ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up,
-                                    tokens_per_expert, input_offsets, precision=m.precision)
+        out, gate_up = _gated_ffn(m, inputs, tokens_per_expert, input_offsets)
         ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
         ctx.m = m
         return out
@@ -350,4 +318,25 @@ class _GatedFFNFn(torch.autograd.Function):
         dgu = torch.cat([dh * u * (sig * (1.0 + g * (1.0 - sig))), dh * (g * sig)], dim=1)
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
                                     precision=m.precision)
+        return dx, None, None, None
+
+
+class _GatedFFN16Fn(_GatedFFNFn):
+    """``_GatedFFNFn`` on 16-bit activations (the same forward): keeps ``gate_up`` in the 16-bit type; the backward is
+    ``dh`` on the down weights, ``ops.swiglu_backward`` and ``dx`` on the gate / up weights, each tensor written once in
+    that type."""
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        gate_up, tpe, offs = ctx.saved_tensors
+        m = ctx.m
+        dt = m.activation_dtype
+        ops.check_activation_rows(gy, "the incoming gradient", dt)
+        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
+                                    precision=m.precision, out_dtype=dt)
+        dgu = ops.swiglu_backward(gate_up, dh, out_dtype=dt)
+        dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
+                                    precision=m.precision, out_dtype=dt)
         return dx, None, None, None

@@ -6,6 +6,11 @@ csrc/quantized_linear.cpp:22-28 and the checks of csrc/quantized_linear_kernel.c
 Outputs are allocated here with torch (``torch.empty``), launches go to torch's current
 stream, nothing synchronises.  GPU tensors only -- a CPU tensor raises, exactly like the
 reference's TORCH_CHECK(input.is_cuda()).
+
+Every op is built from the same few steps (DESIGN.md "The operator boundary"): ``_expert_table`` converts and checks
+the expert table, ``_check_weights`` / ``_check_group_weights`` / ``_check_bias`` the weight operands, ``_on`` the
+device of anything else, and every launch of a product op goes through ``_launch`` (the tuning hook ``tune_gemm_i8`` and
+the size / capability queries call the library directly).
 """
 from __future__ import annotations
 
@@ -16,6 +21,7 @@ from . import _native
 _PRECISIONS = {"default": _native.PRECISION_DEFAULT, "exact": _native.PRECISION_EXACT,
                "fast": _native.PRECISION_FAST, "int8": _native.PRECISION_INT8, "fp8": _native.PRECISION_FP8,
                0: 0, 1: 1, 2: 2, 3: 3, 8: 8}
+_DTYPES = {torch.float32: _native.DTYPE_F32, torch.float16: _native.DTYPE_F16, torch.bfloat16: _native.DTYPE_BF16}
 
 
 def _planes(prec):
@@ -34,11 +40,102 @@ def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _workspace(nbytes, device):
-    if nbytes == 0:
-        return None, 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr()
+# ---------------------------------------------------------------------------------------------------------------------
+# The shared steps of every op.  A wrong-shaped, wrong-typed, CPU or foreign-device tensor must become a Python error
+# in one of the checkers, never an out-of-bounds read or a host pointer inside a kernel.
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _launch(name, dev, *args, ws_bytes=None, after=()):
+    """Call the library's ``name`` on torch's current stream of ``dev`` and raise under that name if it refuses.
+    Tensors among ``args`` are passed as tensors (or None for NULL) and become pointers here, so everything a launch
+    reads must outlive the launch by construction: this frame holds it until the call has returned.  ``ws_bytes`` (for
+    the ops that have one) allocates the workspace and appends ``workspace, workspace_bytes``; then comes the stream, then
+    ``after`` (plain values) for the one signature that goes on behind it."""
+    fn = getattr(_native.lib(), name)
+    idx = dev.index     # torch.cuda.device() and current_stream() resolve a torch.device in Python (1.7 us each), an int not
+    with torch.cuda.device(idx):
+        ptrs = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+        if ws_bytes is not None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+            ptrs += (None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel())
+        rc = fn(*ptrs, torch.cuda.current_stream(idx).cuda_stream, *after)
+    _native.check(rc, name)
+
+
+def _on(dev, **tensors):
+    """Every named tensor (None passes) lives on the GPU ``dev``."""
+    for name, t in tensors.items():
+        if t is not None and (not t.is_cuda or t.device != dev):
+            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+
+
+def _expert_table(tokens_per_expert, input_offsets, E, dev, optional=False):
+    """The device-side expert table as the kernels read it: ``(tokens_per_expert, input_offsets)``, int32 [E], contiguous,
+    on ``dev`` (consumed there, no .item()).  ``optional``: both None gives (None, None), one segment of all rows
+    (E == 1)."""
+    if optional and (tokens_per_expert is None or input_offsets is None):
+        if tokens_per_expert is not None or input_offsets is not None:
+            raise RuntimeError("tokens_per_expert and input_offsets must be given together")
+        if E != 1:
+            raise RuntimeError("tokens_per_expert and input_offsets are required when there is more than one expert")
+        return None, None
+    for name, t in (("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+        if t.numel() != E:
+            raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
+    return tokens_per_expert.to(dtype=torch.int32).contiguous(), input_offsets.to(dtype=torch.int32).contiguous()
+
+
+def _check_weights(packed_weights, scales, zero_points, dev, K=None, grouped=False):
+    """The per-row weight triple on ``dev``: ``packed_weights`` uint8 [N, K/2] with float32 ``scales`` / ``zero_points``
+    of N elements, or (``grouped``) [E, N, K/2] with [E, N].  Returns ``(packed_weights, scales, zero_points, E, N, K)``,
+    the tensors contiguous, E = 1 for one matrix."""
+    if not packed_weights.is_cuda or packed_weights.device != dev:
+        raise RuntimeError("packed_weights must be a CUDA tensor on the inputs' device")
+    if packed_weights.dtype != torch.uint8 or packed_weights.dim() != (3 if grouped else 2):
+        raise RuntimeError("packed_weights must be uint8 " + ("[num_experts, ffn_dim, hidden_dim/2]" if grouped
+                                                              else "[output_dim, input_dim/2]"))
+    N, packed_dim = packed_weights.shape[-2:]
+    E = packed_weights.shape[0] if grouped else 1
+    if K is not None and packed_dim * 2 != K:
+        raise RuntimeError("packed_weights dim 2 must be hidden_dim / 2" if grouped
+                           else "packed_weights dim 1 must be input_dim / 2")
+    for name, t in (("scales", scales), ("zero_points", zero_points)):
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
+        if t.dtype != torch.float32 or (tuple(t.shape) != (E, N) if grouped else t.numel() != N):
+            raise RuntimeError(f"{name} must be float32 " + ("[num_experts, ffn_dim]" if grouped
+                                                             else "with output_dim elements"))
+    return packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous(), E, N, 2 * packed_dim
+
+
+def _check_group_weights(packed_weights, scales, zero_points, dev, K):
+    """The per-group weight triple on ``dev``: ``packed_weights`` uint8 [N, K/2] or [E, N, K/2], float32 ``scales`` /
+    ``zero_points`` [N, K / group_size] or [E, N, K / group_size] with an even group size.  Returns
+    ``(packed_weights, scales, zero_points, group_size)``, the tensors contiguous."""
+    _on(dev, packed_weights=packed_weights, scales=scales, zero_points=zero_points)
+    if packed_weights.dtype != torch.uint8:
+        raise RuntimeError("packed_weights must be uint8")
+    if scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
+        raise RuntimeError("scales and zero_points must be float32")
+    if scales.dim() != packed_weights.dim() or scales.shape[:-1] != packed_weights.shape[:-1] \
+            or zero_points.shape != scales.shape or scales.shape[-1] == 0 or K % scales.shape[-1] != 0:
+        raise RuntimeError("per-group scales and zero_points must be [output_dim, input_dim / group_size] "
+                           "([E, N, K / group_size] for experts)")
+    group = K // scales.shape[-1]
+    if group % 2 != 0:
+        raise RuntimeError("group_size must be even")
+    return packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous(), group
+
+
+def _check_bias(bias, N, dev):
+    """``bias`` None, or float32 with N elements on ``dev`` (returned contiguous)."""
+    if bias is None:
+        return None
+    if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
+        raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
+    return bias.contiguous()
 
 
 def linear_forward(input, packed_weights, scales, zero_points, precision="default", bias=None):
@@ -51,7 +148,7 @@ def linear_forward(input, packed_weights, scales, zero_points, precision="defaul
     if input.dim() == 1:                                   # :302-306
         input = input.unsqueeze(0)
         squeeze = True
-    # device / layout / dtype checks, same order and wording as :311-335
+    # device / layout / dtype checks, same order and wording as :311-335 (hence not _check_weights)
     if not input.is_cuda:
         raise RuntimeError("input must be a CUDA tensor")
     if not packed_weights.is_cuda:
@@ -78,89 +175,39 @@ def linear_forward(input, packed_weights, scales, zero_points, precision="defaul
     N, packed_dim = packed_weights.shape
     if packed_dim != K // 2 or K % 2 != 0:
         raise RuntimeError("packed_weights dim 1 must be input_dim / 2")
-    if scales.dim() == 2 and scales.shape[1] > 1:           # per-group scales along K (float32 contraction: include/fql_int4.h)
+    dev = input.device
+    if _per_group(scales):                                  # per-group scales along K (float32 contraction: include/fql_int4.h)
         out = _linear_group_forward(input, packed_weights, scales, zero_points, bias, precision)
         return out.squeeze(0) if squeeze else out
     # not checked by the reference (silent UB there); checked here
     if scales.numel() != N or zero_points.numel() != N:
         raise RuntimeError("scales and zero_points must have output_dim elements")
-    dev = input.device
     if packed_weights.device != dev or scales.device != dev or zero_points.device != dev:
         raise RuntimeError("all tensors must be on the same device")
-    scales = scales.contiguous()
-    zero_points = zero_points.contiguous()
-    if bias is not None:
-        if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
-            raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
-        bias = bias.contiguous()
-
-    L = _native.lib()
+    bias = _check_bias(bias, N, dev)
     prec = _precision(precision)
     out = torch.empty((B, N), dtype=torch.float32, device=dev)     # :338
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_linear_workspace_bytes(B, K, N, prec), dev)
-        if bias is None:
-            rc = L.fql_linear_fwd_f32(input.data_ptr(), packed_weights.data_ptr(), scales.data_ptr(),
-                                      zero_points.data_ptr(), out.data_ptr(), B, K, N, prec,
-                                      ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-        else:
-            rc = L.fql_linear_bias_fwd_f32(input.data_ptr(), packed_weights.data_ptr(), scales.data_ptr(),
-                                           zero_points.data_ptr(), bias.data_ptr(), out.data_ptr(), B, K, N, prec,
-                                           ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_fwd_f32")
+    _launch("fql_linear_bias_fwd_f32", dev, input, packed_weights, scales.contiguous(), zero_points.contiguous(), bias,
+            out, B, K, N, prec, ws_bytes=_native.lib().fql_linear_workspace_bytes(B, K, N, prec))
     return out.squeeze(0) if squeeze else out                      # :373-375
 
 
+def _per_group(scales):
+    return scales.dim() == 2 and scales.shape[1] > 1
+
+
 def _linear_group_forward(input, packed_weights, scales, zero_points, bias, precision="default"):
-    """Per-group scales along K (``scales`` / ``zero_points`` [N, K / group_size]): fql_linear_group_fwd_f32."""
+    """Per-group scales along K (``scales`` / ``zero_points`` [N, K / group_size]): fql_linear_group_ws_fwd_f32."""
     B, K = input.shape
     N = packed_weights.shape[0]
-    if tuple(scales.shape) != tuple(zero_points.shape) or scales.shape[0] != N or K % scales.shape[1] != 0:
-        raise RuntimeError("per-group scales and zero_points must be [output_dim, input_dim / group_size]")
-    group = K // scales.shape[1]
-    if group % 2 != 0:
-        raise RuntimeError("group_size must be even")
     dev = input.device
-    for t in (packed_weights, scales, zero_points):
-        if t.device != dev:
-            raise RuntimeError("all tensors must be on the same device")
-    if packed_weights.dtype != torch.uint8 or scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
-        raise RuntimeError("packed_weights must be uint8, scales and zero_points float32")
-    if bias is not None:
-        if bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
-            raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
-        bias = bias.contiguous()
-    # (named: a temporary made by .contiguous() must outlive the launch that reads it)
-    x_c, p_c, s_c, z_c = input.contiguous(), packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
+    packed_weights, scales, zero_points, group = _check_group_weights(packed_weights, scales, zero_points, dev, K)
+    bias = _check_bias(bias, N, dev)
     out = torch.empty((B, N), dtype=torch.float32, device=dev)
     prec = _precision(precision)
-    with torch.cuda.device(dev):
-        L = _native.lib()
-        ws, ws_ptr = _workspace(L.fql_group_workspace_bytes(1, B, K, N, group, prec), dev)
-        rc = L.fql_linear_group_ws_fwd_f32(x_c.data_ptr(), p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(),
-                                           None if bias is None else bias.data_ptr(), out.data_ptr(), B, K, N,
-                                           group, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_group_ws_fwd_f32")
+    _launch("fql_linear_group_ws_fwd_f32", dev, input.contiguous(), packed_weights, scales, zero_points, bias, out,
+            B, K, N, group, prec, ws_bytes=_native.lib().fql_group_workspace_bytes(1, B, K, N, group, prec))
     return out
-
-
-def _check_group_scales(packed_weights, scales, zero_points, dev, E, N, K):
-    """Per-group constants of a grouped call: CUDA tensors on ``dev``, uint8 / float32, [E, N, K / group_size] with an even
-    group size.  Returns the group size."""
-    for name, t in (("packed_weights", packed_weights), ("scales", scales), ("zero_points", zero_points)):
-        if not t.is_cuda or t.device != dev:
-            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
-    if packed_weights.dtype != torch.uint8:
-        raise RuntimeError("packed_weights must be uint8")
-    if scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
-        raise RuntimeError("scales and zero_points must be float32")
-    if scales.dim() != 3 or tuple(scales.shape[:2]) != (E, N) or tuple(zero_points.shape) != tuple(scales.shape) \
-            or scales.shape[2] == 0 or K % scales.shape[2] != 0:
-        raise RuntimeError("per-group scales and zero_points must be [E, N, K / group_size]")
-    group = K // scales.shape[2]
-    if group % 2 != 0:
-        raise RuntimeError("group_size must be even")
-    return group
 
 
 def moe_group_forward(packed_weights, scales, zero_points, inputs, tokens_per_expert, input_offsets, precision="default"):
@@ -175,25 +222,12 @@ def moe_group_forward(packed_weights, scales, zero_points, inputs, tokens_per_ex
     if K != 2 * K2:
         raise RuntimeError("packed_weights dim 2 must be hidden_dim / 2")
     dev = inputs.device
-    group = _check_group_scales(packed_weights, scales, zero_points, dev, E, N, K)
-    for name, t in (("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
-        if not t.is_cuda or t.device != dev:
-            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
-        if t.numel() != E:
-            raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    # (named: a temporary made by .contiguous() must outlive the launch that reads it)
-    x_c, p_c, s_c, z_c = inputs.contiguous(), packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
+    packed_weights, scales, zero_points, group = _check_group_weights(packed_weights, scales, zero_points, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     out = torch.empty((T, N), dtype=torch.float32, device=dev)
     prec = _precision(precision)
-    with torch.cuda.device(dev):
-        L = _native.lib()
-        ws, ws_ptr = _workspace(L.fql_group_workspace_bytes(E, T, K, N, group, prec), dev)
-        rc = L.fql_moe_group_ws_fwd_f32(p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), x_c.data_ptr(),
-                                        tpe.data_ptr(), offs.data_ptr(), out.data_ptr(), E, T, K, N, group, prec,
-                                        ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_group_ws_fwd_f32")
+    _launch("fql_moe_group_ws_fwd_f32", dev, packed_weights, scales, zero_points, inputs.contiguous(), tpe, offs, out,
+            E, T, K, N, group, prec, ws_bytes=_native.lib().fql_group_workspace_bytes(E, T, K, N, group, prec))
     return out
 
 
@@ -211,49 +245,19 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
     if _wants_grad(inputs):
         return _MoEFn.apply(inputs, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, precision,
                             None, False)
-    for name, t in (("packed_weights", packed_weights), ("scales", scales), ("zero_points", zero_points),
-                    ("inputs", inputs), ("tokens_per_expert", tokens_per_expert),
-                    ("input_offsets", input_offsets)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-    if packed_weights.dtype != torch.uint8 or packed_weights.dim() != 3:
-        raise RuntimeError("packed_weights must be uint8 [num_experts, ffn_dim, hidden_dim/2]")
+    if not inputs.is_cuda:
+        raise RuntimeError("inputs must be a CUDA tensor")
     if inputs.dtype != torch.float32 or inputs.dim() != 2:
         raise RuntimeError("inputs must be float32 [total_tokens, hidden_dim]")
-    if scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
-        raise RuntimeError("scales and zero_points must be float32")
-    E, N, packed_dim = packed_weights.shape
     T, K = inputs.shape
-    if K % 2 != 0 or packed_dim != K // 2:
-        raise RuntimeError("packed_weights dim 2 must be hidden_dim / 2")
-    if tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N):
-        raise RuntimeError("scales and zero_points must be [num_experts, ffn_dim]")
-    if tokens_per_expert.numel() != E or input_offsets.numel() != E:
-        raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
     dev = inputs.device
-    for t in (packed_weights, scales, zero_points, tokens_per_expert, input_offsets):
-        if t.device != dev:
-            raise RuntimeError("all tensors must be on the same device")
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    packed_weights = packed_weights.contiguous()
-    inputs = inputs.contiguous()
-    scales = scales.contiguous()
-    zero_points = zero_points.contiguous()
-
-    L = _native.lib()
+    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     prec = _precision(precision)
     out = torch.empty((T, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, prec), dev)
-        rc = L.fql_moe_fwd_f32(packed_weights.data_ptr(), scales.data_ptr(), zero_points.data_ptr(),
-                               inputs.data_ptr(), tpe.data_ptr(), offs.data_ptr(), out.data_ptr(),
-                               E, T, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_fwd_f32")
+    _launch("fql_moe_fwd_f32", dev, packed_weights, scales, zero_points, inputs.contiguous(), tpe, offs, out,
+            E, T, K, N, prec, ws_bytes=_native.lib().fql_moe_workspace_bytes(E, T, K, N, prec))
     return out
-
-
-_DTYPES = {torch.float32: _native.DTYPE_F32, torch.float16: _native.DTYPE_F16, torch.bfloat16: _native.DTYPE_BF16}
 
 
 def linear_forward_any(input, packed_weights, scales, zero_points, precision="default", out_dtype=None, bias=None):
@@ -279,23 +283,12 @@ def linear_forward_any(input, packed_weights, scales, zero_points, precision="de
         return linear_forward(input.float().contiguous(), packed_weights, scales, zero_points,
                               precision=precision, bias=bias).to(out_dtype)
     B, K = x2.shape
-    N = packed_weights.shape[0]
     dev = x2.device
-    if scales.numel() != N or zero_points.numel() != N or scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
-        raise RuntimeError("scales and zero_points must be float32 with output_dim elements")
-    scales, zero_points = scales.contiguous(), zero_points.contiguous()
-    if bias is not None:
-        if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
-            raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
-        bias = bias.contiguous()
+    packed_weights, scales, zero_points, _, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K)
+    bias = _check_bias(bias, N, dev)
     out = torch.empty((B, N), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_linear_workspace_bytes(B, K, N, prec), dev)
-        rc = L.fql_linear_bias_fwd(x2.data_ptr(), _DTYPES[x2.dtype], packed_weights.data_ptr(), scales.data_ptr(),
-                                   zero_points.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(),
-                                   _DTYPES[out_dtype], B, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(),
-                                   _stream_ptr(dev))
-    _native.check(rc, "fql_linear_bias_fwd")
+    _launch("fql_linear_bias_fwd", dev, x2, _DTYPES[x2.dtype], packed_weights, scales, zero_points, bias, out,
+            _DTYPES[out_dtype], B, K, N, prec, ws_bytes=L.fql_linear_workspace_bytes(B, K, N, prec))
     return out.squeeze(0) if input.dim() == 1 else out
 
 
@@ -322,42 +315,14 @@ def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tok
     if not native:
         return moe_forward(packed_weights, scales, zero_points, inputs.float().contiguous(), expert_ids,
                            tokens_per_expert, input_offsets, precision=precision).to(out_dtype)
-    E, N, _ = packed_weights.shape
     T, K = inputs.shape
-    if tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N):
-        raise RuntimeError("scales and zero_points must be [num_experts, ffn_dim]")
-    if tokens_per_expert.numel() != E or input_offsets.numel() != E:
-        raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
     dev = inputs.device
-    inputs = inputs.contiguous()
-    packed_weights, scales, zero_points = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
+    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, prec), dev)
-        rc = L.fql_moe_fwd(packed_weights.data_ptr(), scales.data_ptr(), zero_points.data_ptr(), inputs.data_ptr(),
-                           _DTYPES[inputs.dtype], tpe.data_ptr(), offs.data_ptr(), out.data_ptr(), _DTYPES[out_dtype],
-                           E, T, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_fwd")
+    _launch("fql_moe_fwd", dev, packed_weights, scales, zero_points, inputs.contiguous(), _DTYPES[inputs.dtype], tpe,
+            offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
     return out
-
-
-def _check_grouped_weights(packed_weights, scales, zero_points, dev, K):
-    """Shape / dtype / device checks shared by the grouped wrappers: a wrong-shaped or foreign-device tensor must become a
-    Python error here, not an out-of-bounds read inside a kernel."""
-    if not packed_weights.is_cuda or packed_weights.dtype != torch.uint8 or packed_weights.dim() != 3:
-        raise RuntimeError("packed_weights must be a CUDA uint8 [num_experts, ffn_dim, hidden_dim/2] tensor")
-    E, N, packed_dim = packed_weights.shape
-    if packed_dim * 2 != K:
-        raise RuntimeError("packed_weights dim 2 must be hidden_dim / 2")
-    for name, t in (("scales", scales), ("zero_points", zero_points)):
-        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (E, N):
-            raise RuntimeError(f"{name} must be a CUDA float32 [num_experts, ffn_dim] tensor")
-    for t in (packed_weights, scales, zero_points):
-        if t.device != dev:
-            raise RuntimeError("all tensors must be on the same device")
-    return E, N
 
 
 def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, tokens_per_expert,
@@ -370,45 +335,33 @@ def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, t
     ``routing.dispatch_indices``).  Returns the grouped outputs [T, N]; un-sort / combine with
     ``routing.combine_grouped``.  The [T, K] gathered activations are never materialised."""
     _forward_only("moe_gather_forward", tokens, row_weight)
-    for name, t in (("packed_weights", packed_weights), ("tokens", tokens), ("row_index", row_index),
-                    ("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
+    if not tokens.is_cuda:
+        raise RuntimeError("tokens must be a CUDA tensor")
     if tokens.dtype != torch.float32 or tokens.dim() != 2:
         raise RuntimeError("tokens must be float32 [n_tokens, hidden_dim]")
     n_tokens, K = tokens.shape
     dev = tokens.device
-    E, N = _check_grouped_weights(packed_weights, scales, zero_points, dev, K)
+    if not row_index.is_cuda:
+        raise RuntimeError("row_index must be a CUDA tensor")
+    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
     if K % 32 != 0:
         raise RuntimeError("fused gather needs hidden_dim % 32 == 0")
-    if tokens_per_expert.numel() != E or input_offsets.numel() != E:
-        raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     T = row_index.numel()
     ri = row_index.to(device=dev, dtype=torch.int32).contiguous()
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    tokens = tokens.contiguous()
     if row_weight is not None:
         if not row_weight.is_cuda or row_weight.device != dev or row_weight.numel() != T:
             raise RuntimeError("row_weight must be a CUDA tensor with one element per grouped row")
         row_weight = row_weight.to(torch.float32).contiguous()
-    L = _native.lib()
     prec = _precision(precision)
+    ws_bytes = _native.lib().fql_moe_workspace_bytes(E, T, K, N, prec)
     out = torch.empty((T, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, prec), dev)
-        packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
-        if row_weight is None:
-            rc = L.fql_moe_gather_fwd_f32(packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                                          zero_points_c.data_ptr(), tokens.data_ptr(), ri.data_ptr(), n_tokens,
-                                          tpe.data_ptr(), offs.data_ptr(), out.data_ptr(), E, T, K, N, prec,
-                                          ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-        else:
-            rc = L.fql_moe_gather_scaled_fwd_f32(packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                                                 zero_points_c.data_ptr(), tokens.data_ptr(), ri.data_ptr(), n_tokens,
-                                                 row_weight.data_ptr(), tpe.data_ptr(), offs.data_ptr(), out.data_ptr(),
-                                                 E, T, K, N, prec, ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_gather_fwd_f32")
+    if row_weight is None:
+        _launch("fql_moe_gather_fwd_f32", dev, packed_weights, scales, zero_points, tokens.contiguous(), ri, n_tokens,
+                tpe, offs, out, E, T, K, N, prec, ws_bytes=ws_bytes)
+        return out
+    _launch("fql_moe_gather_scaled_fwd_f32", dev, packed_weights, scales, zero_points, tokens.contiguous(), ri, n_tokens,
+            row_weight, tpe, offs, out, E, T, K, N, prec, ws_bytes=ws_bytes)
     return out
 
 
@@ -430,35 +383,19 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
     dev = gate_up.device
     if K2 % 2 or K % 32:
         raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
-    E, N = _check_grouped_weights(packed_weights, scales, zero_points, dev, K)
-    if tokens_per_expert.numel() != E or input_offsets.numel() != E:
-        raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
+    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     L = _native.lib()
     prec = _precision(precision)
-    packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
     typed = gate_up.dtype != torch.float32 or out_dtype != torch.float32
-    if typed and T > 0 and L.fql_native_dtype_supported(T, E, K, N, prec, packed_weights_c.data_ptr(), 1) != 1:
-        # off the 16-bit MFMA path: widen and round around the float32 entry point (the same contract)
-        return moe_gated_forward(packed_weights, scales, zero_points, gate_up.float(), tokens_per_expert, input_offsets,
-                                 precision=precision, out_dtype=torch.float32).to(out_dtype)
-    gate_up = gate_up.contiguous()
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
+    round_to = None
+    if typed and T > 0 and L.fql_native_dtype_supported(T, E, K, N, prec, packed_weights.data_ptr(), 1) != 1:
+        # off the 16-bit MFMA path: widen and round around the float32 call (the same contract)
+        gate_up, round_to, out_dtype = gate_up.float(), out_dtype, torch.float32
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, prec), dev)
-        if not typed:
-            rc = L.fql_moe_gated_fwd_f32(packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                                         zero_points_c.data_ptr(), gate_up.data_ptr(), tpe.data_ptr(),
-                                         offs.data_ptr(), out.data_ptr(), E, T, K, N, prec,
-                                         ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-        else:
-            rc = L.fql_moe_gated_fwd(packed_weights_c.data_ptr(), scales_c.data_ptr(), zero_points_c.data_ptr(),
-                                     gate_up.data_ptr(), _DTYPES[gate_up.dtype], tpe.data_ptr(), offs.data_ptr(),
-                                     out.data_ptr(), _DTYPES[out_dtype], E, T, K, N, prec,
-                                     ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_gated_fwd" if typed else "fql_moe_gated_fwd_f32")
-    return out
+    _launch("fql_moe_gated_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(), _DTYPES[gate_up.dtype],
+            tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
+    return out if round_to is None else out.to(round_to)
 
 
 ROUTE_MAX_EXPERTS = 128
@@ -480,12 +417,23 @@ def route_plan(expert_indices, num_experts):
     offsets = torch.empty(num_experts, dtype=torch.int32, device=dev)
     token_of_sorted = torch.empty(n, dtype=torch.int32, device=dev)
     pos_of_slot = torch.empty(n, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_route_plan_i32(flat.data_ptr(), n, top_k, num_experts, counts.data_ptr(),
-                                              offsets.data_ptr(), token_of_sorted.data_ptr(), pos_of_slot.data_ptr(),
-                                              _stream_ptr(dev))
-    _native.check(rc, "fql_route_plan_i32")
+    _launch("fql_route_plan_i32", dev, flat, n, top_k, num_experts, counts, offsets, token_of_sorted, pos_of_slot)
     return counts, offsets, token_of_sorted, pos_of_slot
+
+
+def _combine_operands(y, pos_of_slot, expert_weights, top_k):
+    """``(T, top_k, pos int32, weights float32 or None)`` of ``combine`` and its backward, on ``y``'s device."""
+    if expert_weights is None:
+        if not top_k:
+            raise RuntimeError("top_k is needed when the rows carry their weights")
+        T = pos_of_slot.numel() // top_k
+    else:
+        T, top_k = expert_weights.shape
+    _on(y.device, y=y, pos_of_slot=pos_of_slot, expert_weights=expert_weights)
+    if pos_of_slot.numel() < T * top_k:
+        raise RuntimeError("pos_of_slot must have tokens * top_k elements")
+    w = None if expert_weights is None else expert_weights.to(dtype=torch.float32).contiguous()
+    return T, top_k, pos_of_slot.to(dtype=torch.int32).contiguous(), w
 
 
 def combine(y, pos_of_slot, expert_weights, top_k=None):
@@ -496,33 +444,11 @@ def combine(y, pos_of_slot, expert_weights, top_k=None):
         return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k)
     if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 2:
         raise RuntimeError("y must be a CUDA float32 [rows, N] tensor")
-    if expert_weights is None:
-        if not top_k:
-            raise RuntimeError("top_k is needed when the rows carry their weights")
-        T = pos_of_slot.numel() // top_k
-        if T > 65535:
-            raise RuntimeError("combine handles up to 65535 tokens per call")
-        dev = y.device
-        y = y.contiguous()
-        pos = pos_of_slot.to(device=dev, dtype=torch.int32).contiguous()
-        out = torch.empty((T, y.shape[1]), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _native.lib().fql_combine_f32(y.data_ptr(), pos.data_ptr(), None, out.data_ptr(), T, top_k,
-                                               y.shape[1], y.shape[0], _stream_ptr(dev))
-        _native.check(rc, "fql_combine_f32")
-        return out
-    T, top_k = expert_weights.shape
+    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
     if T > 65535:
         raise RuntimeError("combine handles up to 65535 tokens per call")
-    dev = y.device
-    y = y.contiguous()
-    w = expert_weights.to(device=dev, dtype=torch.float32).contiguous()
-    pos = pos_of_slot.to(device=dev, dtype=torch.int32).contiguous()
-    out = torch.empty((T, y.shape[1]), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_combine_f32(y.data_ptr(), pos.data_ptr(), w.data_ptr(), out.data_ptr(), T, top_k,
-                                           y.shape[1], y.shape[0], _stream_ptr(dev))
-    _native.check(rc, "fql_combine_f32")
+    out = torch.empty((T, y.shape[1]), dtype=torch.float32, device=y.device)
+    _launch("fql_combine_f32", y.device, y.contiguous(), pos, w, out, T, top_k, y.shape[1], y.shape[0])
     return out
 
 
@@ -534,49 +460,38 @@ def regroup_index(recv_counts, total_rows):
         raise RuntimeError("recv_counts must be a CUDA [ranks, local_experts] tensor")
     dev = recv_counts.device
     G, EL = recv_counts.shape
-    cnt = recv_counts.to(torch.int32).contiguous()
     tpe = torch.empty(EL, dtype=torch.int32, device=dev)
     offs = torch.empty(EL, dtype=torch.int32, device=dev)
     gather = torch.empty(max(total_rows, 1), dtype=torch.int32, device=dev)
     scatter = torch.empty(max(total_rows, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_regroup_index_i32(cnt.data_ptr(), G, EL, tpe.data_ptr(), offs.data_ptr(),
-                                                 gather.data_ptr(), scatter.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "fql_regroup_index_i32")
+    _launch("fql_regroup_index_i32", dev, recv_counts.to(torch.int32).contiguous(), G, EL, tpe, offs, gather, scatter)
     return tpe, offs, gather[:total_rows], scatter[:total_rows]
+
+
+def _quantize(weight_fp32, per_tensor):
+    if not weight_fp32.is_cuda or weight_fp32.dtype != torch.float32 or weight_fp32.dim() != 2:
+        raise RuntimeError("weight must be a CUDA float32 [N,K] tensor")
+    w = weight_fp32.contiguous()
+    N, K = w.shape
+    packed = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((N,), dtype=torch.float32, device=w.device)
+    zps = torch.empty((N,), dtype=torch.float32, device=w.device)
+    if per_tensor:                                          # + the scratch of the whole-tensor min / max reduction
+        scratch = torch.empty((2 * N,), dtype=torch.float32, device=w.device)
+        _launch("fql_quantize_tensor_f32", w.device, w, packed, scales, zps, scratch, N, K)
+    else:
+        _launch("fql_quantize_rows_f32", w.device, w, packed, scales, zps, N, K)
+    return packed, scales, zps
 
 
 def quantize_rows(weight_fp32):
     """GPU quantize_weights (python/quantize.py:38-124), bit-exact with the host arithmetic."""
-    if not weight_fp32.is_cuda or weight_fp32.dtype != torch.float32 or weight_fp32.dim() != 2:
-        raise RuntimeError("weight must be a CUDA float32 [N,K] tensor")
-    w = weight_fp32.contiguous()
-    N, K = w.shape
-    packed = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
-    scales = torch.empty((N,), dtype=torch.float32, device=w.device)
-    zps = torch.empty((N,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _native.lib().fql_quantize_rows_f32(w.data_ptr(), packed.data_ptr(), scales.data_ptr(), zps.data_ptr(),
-                                                 N, K, _stream_ptr(w.device))
-    _native.check(rc, "fql_quantize_rows_f32")
-    return packed, scales, zps
+    return _quantize(weight_fp32, per_tensor=False)
 
 
 def quantize_tensor(weight_fp32):
     """GPU per-tensor quantiser of one expert (python/moe_int4_module.py:45-76): scale / zp broadcast to [N]."""
-    if not weight_fp32.is_cuda or weight_fp32.dtype != torch.float32 or weight_fp32.dim() != 2:
-        raise RuntimeError("weight must be a CUDA float32 [N,K] tensor")
-    w = weight_fp32.contiguous()
-    N, K = w.shape
-    packed = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
-    scales = torch.empty((N,), dtype=torch.float32, device=w.device)
-    zps = torch.empty((N,), dtype=torch.float32, device=w.device)
-    scratch = torch.empty((2 * N,), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _native.lib().fql_quantize_tensor_f32(w.data_ptr(), packed.data_ptr(), scales.data_ptr(), zps.data_ptr(),
-                                                   scratch.data_ptr(), N, K, _stream_ptr(w.device))
-    _native.check(rc, "fql_quantize_tensor_f32")
-    return packed, scales, zps
+    return _quantize(weight_fp32, per_tensor=True)
 
 
 def unpack_nibbles(packed):
@@ -585,26 +500,16 @@ def unpack_nibbles(packed):
         raise RuntimeError("packed must be a CUDA uint8 tensor")
     packed = packed.contiguous()
     q = torch.empty(packed.shape[:-1] + (packed.shape[-1] * 2,), dtype=torch.uint8, device=packed.device)
-    with torch.cuda.device(packed.device):
-        rc = _native.lib().fql_unpack_u8(packed.data_ptr(), q.data_ptr(), packed.numel(),
-                                         _stream_ptr(packed.device))
-    _native.check(rc, "fql_unpack_u8")
+    _launch("fql_unpack_u8", packed.device, packed, q, packed.numel())
     return q
 
 
 def dequantize_forward(packed_weights, scales, zero_points):
     """GPU dequantize_weights: [N,K/2] u8 -> [N,K] f32 (python/quantize.py:127-173)."""
-    if not packed_weights.is_cuda:
-        raise RuntimeError("packed_weights must be a CUDA tensor")
-    packed_weights = packed_weights.contiguous()
-    N, K2 = packed_weights.shape
-    w = torch.empty((N, 2 * K2), dtype=torch.float32, device=packed_weights.device)
-    with torch.cuda.device(packed_weights.device):
-        scales_c, zero_points_c = scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
-        rc = _native.lib().fql_dequantize_f32(packed_weights.data_ptr(), scales_c.data_ptr(),
-                                              zero_points_c.data_ptr(), w.data_ptr(), N, 2 * K2,
-                                              _stream_ptr(packed_weights.device))
-    _native.check(rc, "fql_dequantize_f32")
+    dev = packed_weights.device
+    packed_weights, scales, zero_points, _, N, K = _check_weights(packed_weights, scales, zero_points, dev)
+    w = torch.empty((N, K), dtype=torch.float32, device=dev)
+    _launch("fql_dequantize_f32", dev, packed_weights, scales, zero_points, w, N, K)
     return w
 
 
@@ -624,21 +529,17 @@ def act_quant(x, precision="default", tokens_per_expert=None, input_offsets=None
     T, K = x.shape
     prec = _precision(precision)
     nl, ns = _planes(prec), _sets(prec)
-    grouped = tokens_per_expert is not None
-    E = tokens_per_expert.numel() if grouped else 1
-    L = _native.lib()
+    tpe, offs, E = None, None, 1
+    if tokens_per_expert is not None:
+        E = tokens_per_expert.numel()
+        tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, x.device)
     if out is not None:                 # reuse the buffers of an earlier call with the same shapes (timing loops)
         limbs, delta, rowsum = out
     else:
-        limbs = torch.zeros(L.fql_act_limb_bytes(T, E, K, prec), dtype=torch.int8, device=x.device)
+        limbs = torch.zeros(_native.lib().fql_act_limb_bytes(T, E, K, prec), dtype=torch.int8, device=x.device)
         delta = torch.zeros((ns, T), dtype=torch.float32, device=x.device)
         rowsum = torch.zeros((ns, nl, T), dtype=torch.int32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = L.fql_act_quant_f32(x.data_ptr(), limbs.data_ptr(), delta.data_ptr(), rowsum.data_ptr(),
-                                 tokens_per_expert.data_ptr() if grouped else None,
-                                 input_offsets.data_ptr() if grouped else None, E, T, K, prec,
-                                 _stream_ptr(x.device))
-    _native.check(rc, "fql_act_quant_f32")
+    _launch("fql_act_quant_f32", x.device, x, limbs, delta, rowsum, tpe, offs, E, T, K, prec)
     return limbs, delta, rowsum
 
 
@@ -662,30 +563,23 @@ def gemm_i8(limbs, delta, rowsum, packed_weights, scales, zero_points, tokens_pe
     """Phase 2 of the MFMA path: grouped INT4 x INT8-limb GEMM over pre-converted activations
     (``act_quant`` output, produced with the same expert arrays).  ``packed_weights`` [N,K/2] (one
     group) or [E,N,K/2] with device-side ``tokens_per_expert`` / ``input_offsets``."""
+    dev = limbs.device
+    _on(dev, limbs=limbs, delta=delta, rowsum=rowsum, out=out)
     T = delta.shape[-1]
     grouped = packed_weights.dim() == 3
-    E = packed_weights.shape[0] if grouped else 1
-    N, K2 = packed_weights.shape[-2:]
-    K = 2 * K2
+    packed_weights, scales, zero_points, E, N, K = _check_weights(packed_weights, scales, zero_points, dev, grouped=grouped)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev) if grouped else (None, None)
     prec = _precision(precision)
     if _planes(prec) != rowsum.shape[-2] or _sets(prec) != delta.shape[0]:
         raise RuntimeError("limb count does not match precision")
     if limbs.numel() < _native.lib().fql_act_limb_bytes(T, E, K, prec):
         raise RuntimeError("limbs were not produced for this T, E, K")
-    dev = limbs.device
     if out is None:
         out = torch.zeros((T, N), dtype=torch.float32, device=dev) if grouped else \
             torch.empty((T, N), dtype=torch.float32, device=dev)
-    tpe_ptr = tokens_per_expert.data_ptr() if grouped else None
-    off_ptr = input_offsets.data_ptr() if grouped else None
     scratch = gemm_scratch(prec, dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_gemm_i8_f32(limbs.data_ptr(), delta.data_ptr(), rowsum.data_ptr(),
-                                           packed_weights.data_ptr(), scales.data_ptr(), zero_points.data_ptr(),
-                                           tpe_ptr, off_ptr, out.data_ptr(), E, T, K, N, prec, _stream_ptr(dev),
-                                           None if scratch is None else scratch.data_ptr(),
-                                           0 if scratch is None else scratch.numel())
-    _native.check(rc, "fql_gemm_i8_f32")
+    _launch("fql_gemm_i8_f32", dev, limbs, delta, rowsum, packed_weights, scales, zero_points, tpe, offs, out,
+            E, T, K, N, prec, after=(None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel()))   # (cached)
     return out
 
 
@@ -753,51 +647,36 @@ def quantize_activations_fp8(x):
     return (x / scale[:, None]).to(torch.float8_e4m3fn), scale
 
 
+def _fp8_operands(x, act_scales, name, out_dtype, K_name):
+    """``(x8 uint8 [rows, K] contiguous, act_scales float32 [rows] or None)`` of the two fp8 entry points."""
+    x8 = _as_e4m3_bytes(x, name)
+    if not x8.is_cuda or x8.dim() != 2:
+        raise RuntimeError(f"{name} must be a CUDA [rows, {K_name}] tensor")
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("outputs must be float32, float16 or bfloat16")
+    if x8.shape[1] % 32 != 0:
+        raise RuntimeError(f"the fp8 path needs {K_name} % 32 == 0")
+    if act_scales is not None:
+        if act_scales.numel() != x8.shape[0]:
+            raise RuntimeError("act_scales must have one element per row")
+        act_scales = act_scales.to(device=x8.device, dtype=torch.float32).contiguous()
+    return x8.contiguous(), act_scales
+
+
 def moe_forward_fp8(packed_weights, scales, zero_points, inputs_e4m3, act_scales, tokens_per_expert, input_offsets,
                     out_dtype=torch.float32):
     """Grouped per-expert INT4 GEMM over rows that are already fp8: ``inputs_e4m3`` [T, K] torch.float8_e4m3fn
     (or its uint8 bytes), ``act_scales`` [T] float32 or None.  One fp8 MFMA pass, float32 accumulation
     (BASELINE.json configs[4]).  Returns [T, N] in ``out_dtype``; rows no expert covers are zero."""
     _forward_only("moe_forward_fp8", inputs_e4m3, act_scales)
-    x8 = _as_e4m3_bytes(inputs_e4m3, "inputs_e4m3")
-    for name, t in (("packed_weights", packed_weights), ("scales", scales), ("zero_points", zero_points), ("inputs_e4m3", x8),
-                    ("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be a CUDA tensor")
-    if packed_weights.dtype != torch.uint8 or packed_weights.dim() != 3 or x8.dim() != 2:
-        raise RuntimeError("packed_weights must be uint8 [num_experts, ffn_dim, hidden_dim/2] and inputs [total_tokens, hidden_dim]")
-    if out_dtype not in _DTYPES:
-        raise RuntimeError("outputs must be float32, float16 or bfloat16")
-    E, N, packed_dim = packed_weights.shape
+    x8, act_scales = _fp8_operands(inputs_e4m3, act_scales, "inputs_e4m3", out_dtype, "hidden_dim")
     T, K = x8.shape
-    if K % 32 != 0 or packed_dim != K // 2:
-        raise RuntimeError("the fp8 path needs hidden_dim % 32 == 0 and packed_weights dim 2 == hidden_dim / 2")
-    if tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N) or scales.dtype != torch.float32 \
-            or zero_points.dtype != torch.float32:
-        raise RuntimeError("scales and zero_points must be float32 [num_experts, ffn_dim]")
-    if tokens_per_expert.numel() != E or input_offsets.numel() != E:
-        raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
     dev = x8.device
-    if any(t.device != dev for t in (packed_weights, scales, zero_points)):
-        raise RuntimeError("all tensors must be on the same device")
-    if act_scales is not None:
-        if act_scales.numel() != T:
-            raise RuntimeError("act_scales must have one element per row")
-        act_scales = act_scales.to(device=dev, dtype=torch.float32).contiguous()
-    x8 = x8.contiguous()
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    L = _native.lib()
+    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_workspace_bytes(E, T, K, N, _native.PRECISION_FP8), dev)
-        packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
-        rc = L.fql_moe_fwd_f8(packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                              zero_points_c.data_ptr(), x8.data_ptr(),
-                              None if act_scales is None else act_scales.data_ptr(), tpe.data_ptr(), offs.data_ptr(),
-                              out.data_ptr(), _DTYPES[out_dtype], E, T, K, N, ws_ptr, 0 if ws is None else ws.numel(),
-                              _stream_ptr(dev))
-    _native.check(rc, "fql_moe_fwd_f8")
+    _launch("fql_moe_fwd_f8", dev, packed_weights, scales, zero_points, x8, act_scales, tpe, offs, out, _DTYPES[out_dtype],
+            E, T, K, N, ws_bytes=_native.lib().fql_moe_workspace_bytes(E, T, K, N, _native.PRECISION_FP8))
     return out
 
 
@@ -805,39 +684,15 @@ def linear_forward_fp8(x_e4m3, act_scales, packed_weights, scales, zero_points, 
     """Fused 4-bit dequantize + linear over fp8 rows: ``x_e4m3`` [B, K] torch.float8_e4m3fn (or uint8 bytes),
     ``act_scales`` [B] float32 or None -> [B, N] in ``out_dtype``."""
     _forward_only("linear_forward_fp8", x_e4m3, act_scales)
-    x8 = _as_e4m3_bytes(x_e4m3, "x_e4m3")
-    if not x8.is_cuda or not packed_weights.is_cuda:
-        raise RuntimeError("x_e4m3 and packed_weights must be CUDA tensors")
-    if x8.dim() != 2 or packed_weights.dim() != 2 or packed_weights.dtype != torch.uint8:
-        raise RuntimeError("x_e4m3 must be [B, K] and packed_weights uint8 [N, K/2]")
-    if out_dtype not in _DTYPES:
-        raise RuntimeError("outputs must be float32, float16 or bfloat16")
+    x8, act_scales = _fp8_operands(x_e4m3, act_scales, "x_e4m3", out_dtype, "input_dim")
     B, K = x8.shape
-    N, packed_dim = packed_weights.shape
-    if K % 32 != 0 or packed_dim != K // 2:
-        raise RuntimeError("the fp8 path needs input_dim % 32 == 0 and packed_weights dim 1 == input_dim / 2")
-    if scales.numel() != N or zero_points.numel() != N or scales.dtype != torch.float32 or zero_points.dtype != torch.float32:
-        raise RuntimeError("scales and zero_points must be float32 with output_dim elements")
     dev = x8.device
-    if any(t.device != dev for t in (packed_weights, scales, zero_points)):
-        raise RuntimeError("all tensors must be on the same device")
-    if act_scales is not None:
-        if act_scales.numel() != B:
-            raise RuntimeError("act_scales must have one element per row")
-        act_scales = act_scales.to(device=dev, dtype=torch.float32).contiguous()
-    x8 = x8.contiguous()
-    L = _native.lib()
+    packed_weights, scales, zero_points, _, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K)
     out = torch.empty((B, N), dtype=out_dtype, device=dev)
     if B == 0:
         return out
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_linear_workspace_bytes(B, K, N, _native.PRECISION_FP8), dev)
-        packed_weights_c, scales_c, zero_points_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()   # (named: must outlive the launch)
-        rc = L.fql_linear_fwd_f8(x8.data_ptr(), None if act_scales is None else act_scales.data_ptr(),
-                                 packed_weights_c.data_ptr(), scales_c.data_ptr(),
-                                 zero_points_c.data_ptr(), out.data_ptr(), _DTYPES[out_dtype], B, K, N,
-                                 ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_fwd_f8")
+    _launch("fql_linear_fwd_f8", dev, x8, act_scales, packed_weights, scales, zero_points, out, _DTYPES[out_dtype],
+            B, K, N, ws_bytes=_native.lib().fql_linear_workspace_bytes(B, K, N, _native.PRECISION_FP8))
     return out
 
 
@@ -862,22 +717,16 @@ def linear_backward_input(grad_out, packed_weights, scales, zero_points, precisi
     float32).  A 16-bit ``grad_out`` is read as it is and a 16-bit result is rounded once in the kernel: bit for bit
     ``linear_backward_input(grad_out.float()).to(out_dtype)`` with no float32 copy made."""
     out_dtype = _grad_dtypes(grad_out, out_dtype, "B")
-    N, K2 = packed_weights.shape
-    B, K = grad_out.shape[0], 2 * K2
-    if grad_out.shape[1] != N or scales.numel() != N or zero_points.numel() != N:
-        raise RuntimeError("grad_out, scales and zero_points must have output_dim columns / elements")
     dev = grad_out.device
-    gy = grad_out.contiguous()
-    p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
-    L = _native.lib()
+    packed_weights, scales, zero_points, _, N, K = _check_weights(packed_weights, scales, zero_points, dev)
+    B = grad_out.shape[0]
+    if grad_out.shape[1] != N:
+        raise RuntimeError("grad_out must have output_dim columns")
     prec = _precision(precision)
     out = torch.empty((B, K), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_linear_bwd_workspace_bytes(B, K, N, prec), dev)
-        rc = L.fql_linear_bwd_input(gy.data_ptr(), _DTYPES[gy.dtype], p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(),
-                                    out.data_ptr(), _DTYPES[out_dtype], B, K, N, prec, ws_ptr,
-                                    0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_linear_bwd_input")
+    _launch("fql_linear_bwd_input", dev, grad_out.contiguous(), _DTYPES[grad_out.dtype], packed_weights, scales,
+            zero_points, out, _DTYPES[out_dtype], B, K, N, prec,
+            ws_bytes=_native.lib().fql_linear_bwd_workspace_bytes(B, K, N, prec))
     return out
 
 
@@ -887,24 +736,17 @@ def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per
     ``grad_out`` [T, N] float32 / float16 / bfloat16, ``packed_weights`` [E, N, K/2] -> [T, K] ``out_dtype`` (default
     float32); 16-bit types as in ``linear_backward_input``."""
     out_dtype = _grad_dtypes(grad_out, out_dtype, "T")
-    E, N, K2 = packed_weights.shape
-    T, K = grad_out.shape[0], 2 * K2
-    if grad_out.shape[1] != N or tuple(scales.shape) != (E, N) or tuple(zero_points.shape) != (E, N):
-        raise RuntimeError("grad_out must be [T, ffn_dim] and scales / zero_points [num_experts, ffn_dim]")
     dev = grad_out.device
-    gy = grad_out.contiguous()
-    tpe = tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous()
-    offs = input_offsets.to(device=dev, dtype=torch.int32).contiguous()
-    p_c, s_c, z_c = packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous()
-    L = _native.lib()
+    packed_weights, scales, zero_points, E, N, K = _check_weights(packed_weights, scales, zero_points, dev, grouped=True)
+    T = grad_out.shape[0]
+    if grad_out.shape[1] != N:
+        raise RuntimeError("grad_out must be [T, ffn_dim]")
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     prec = _precision(precision)
     out = torch.empty((T, K), dtype=out_dtype, device=dev)
-    with torch.cuda.device(dev):
-        ws, ws_ptr = _workspace(L.fql_moe_bwd_workspace_bytes(E, T, K, N, prec), dev)
-        rc = L.fql_moe_bwd_input(p_c.data_ptr(), s_c.data_ptr(), z_c.data_ptr(), gy.data_ptr(), _DTYPES[gy.dtype],
-                                 tpe.data_ptr(), offs.data_ptr(), out.data_ptr(), _DTYPES[out_dtype], E, T, K, N, prec,
-                                 ws_ptr, 0 if ws is None else ws.numel(), _stream_ptr(dev))
-    _native.check(rc, "fql_moe_bwd_input")
+    _launch("fql_moe_bwd_input", dev, packed_weights, scales, zero_points, grad_out.contiguous(), _DTYPES[grad_out.dtype],
+            tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec,
+            ws_bytes=_native.lib().fql_moe_bwd_workspace_bytes(E, T, K, N, prec))
     return out
 
 
@@ -932,24 +774,14 @@ def group_backward_input(grad_out, packed_weights, scales, zero_points):
 def combine_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, need_weights=True):
     """Gradients of ``combine``: ``(grad_y [R, N], grad_weights [T, top_k] or None)`` in one launch, no atomics.
     Rows of ``y`` that no slot names get zero."""
-    if expert_weights is not None:
-        T, top_k = expert_weights.shape
-    else:
-        T = pos_of_slot.numel() // top_k
     dev = y.device
+    _on(dev, grad_out=grad_out)
+    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
     R, N = y.shape
-    gout = grad_out.to(torch.float32).contiguous()
-    y_c = y.contiguous()
-    pos = pos_of_slot.to(device=dev, dtype=torch.int32).contiguous()
-    w = None if expert_weights is None else expert_weights.to(device=dev, dtype=torch.float32).contiguous()
     grad_y = (torch.empty if R == T * top_k else torch.zeros)((R, N), dtype=torch.float32, device=dev)
     grad_w = torch.empty((T, top_k), dtype=torch.float32, device=dev) if (need_weights and w is not None) else None
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_combine_bwd_f32(gout.data_ptr(), y_c.data_ptr(), pos.data_ptr(),
-                                               None if w is None else w.data_ptr(), grad_y.data_ptr(),
-                                               None if grad_w is None else grad_w.data_ptr(), T, top_k, N, R,
-                                               _stream_ptr(dev))
-    _native.check(rc, "fql_combine_bwd_f32")
+    _launch("fql_combine_bwd_f32", dev, grad_out.to(torch.float32).contiguous(), y.contiguous(), pos, w, grad_y, grad_w,
+            T, top_k, N, R)
     return grad_y, grad_w
 
 
@@ -984,7 +816,7 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, gy):
         packed, scales, zps = ctx.saved_tensors
         g2 = gy.reshape(-1, gy.shape[-1])
-        if scales.dim() == 2 and scales.shape[1] > 1:          # per-group weights: unfused, float32 in torch
+        if _per_group(scales):                                 # per-group weights: unfused, float32 in torch
             gx = group_backward_input(g2.to(torch.float32), packed, scales, zps).to(ctx.x_dtype)
         else:                                                  # gy in its own type, dX in x's: no cast pass
             gx = linear_backward_input(g2, packed, scales, zps, precision=ctx.precision, out_dtype=ctx.x_dtype)
@@ -1058,23 +890,6 @@ def _lora_rows(t, name, dev, wide=False):
     return t.contiguous()
 
 
-def _lora_table(tokens_per_expert, input_offsets, E, dev):
-    """(tpe, offs) as int32 on ``dev``, or (None, None) for one segment of all rows (E == 1)."""
-    if tokens_per_expert is None and input_offsets is None:
-        if E != 1:
-            raise RuntimeError("tokens_per_expert and input_offsets are required when there is more than one expert")
-        return None, None
-    if tokens_per_expert is None or input_offsets is None:
-        raise RuntimeError("tokens_per_expert and input_offsets must be given together")
-    for name, t in (("tokens_per_expert", tokens_per_expert), ("input_offsets", input_offsets)):
-        if not t.is_cuda or t.device != dev:
-            raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
-        if t.numel() != E:
-            raise RuntimeError("tokens_per_expert and input_offsets must have num_experts elements")
-    return (tokens_per_expert.to(device=dev, dtype=torch.int32).contiguous(),
-            input_offsets.to(device=dev, dtype=torch.int32).contiguous())
-
-
 def _lora_weight(w, layout, C, dev, name="w"):
     """Adapter weight [r, C] / [C, r] (one segment) or [E, r, C] / [E, C, r] -> (contiguous 16-byte aligned tensor, E, r)."""
     if not w.is_cuda or w.device != dev:
@@ -1094,27 +909,67 @@ def _lora_weight(w, layout, C, dev, name="w"):
     return w3, E, r
 
 
-def lora_shrink(input, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
-    """Segmented ``out[t] = scale * input[t] @ W_e^T`` -> [T, r] float32: ``weight`` [E, r, C] (``layout='rc'``, e.g.
-    lora_A) or [E, C, r] (``'cr'``, e.g. lora_B), 2-D for one segment.  Rows no expert covers are zero.  ``input`` may
-    be float16 / bfloat16: read as it is, bit for bit the call on ``input.float()`` (INTEGRATION.md section 8)."""
-    dev = input.device
-    x = _lora_rows(input, "input", dev, wide=True)
-    T, C = x.shape
+def _gate_up_rows(gate_up, dev):
+    g = _lora_rows(gate_up, "gate_up", dev, wide=True)
+    if g.shape[1] % 2:
+        raise RuntimeError("gate_up must be [T, 2C] (gate | up)")
+    return g, g.shape[0], g.shape[1] // 2
+
+
+def _lora_shrink(rows, weight, layout, tokens_per_expert, input_offsets, scale, gated):
+    """``lora_shrink`` (rows = input [T, C]) / ``lora_gated_shrink`` (rows = gate_up [T, 2C])."""
+    dev = rows.device
+    if gated:
+        x, T, C = _gate_up_rows(rows, dev)
+    else:
+        x = _lora_rows(rows, "input", dev, wide=True)
+        T, C = x.shape
     w, E, r = _lora_weight(weight, layout, C, dev, "weight")
-    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
     out = torch.empty((T, r), dtype=torch.float32, device=dev)
     if T == 0:
         return out
     if C == 0:
         return out.zero_()
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_shrink(x.data_ptr(), _DTYPES[x.dtype], w.data_ptr(), _lora_layout(layout),
-                                           None if tpe is None else tpe.data_ptr(),
-                                           None if offs is None else offs.data_ptr(), out.data_ptr(), E, T, C, r,
-                                           float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_shrink")
+    _launch("fql_lora_gated_shrink" if gated else "fql_lora_shrink", dev, x, _DTYPES[x.dtype], w, _lora_layout(layout),
+            tpe, offs, out, E, T, C, r, float(scale))
     return out
+
+
+def _lora_grad(rows, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated):
+    """``lora_grad`` (rows = p [T, C]) / ``lora_gated_grad`` (rows = gate_up [T, 2C])."""
+    dev = rows.device
+    name = "gate_up" if gated else "p"
+    if gated:
+        pp, T, C = _gate_up_rows(rows, dev)
+    else:
+        pp = _lora_rows(rows, name, dev, wide=True)
+        T, C = pp.shape
+    vv = _lora_rows(v, "v", dev)
+    r = vv.shape[1]
+    if vv.shape[0] != T:
+        raise RuntimeError(f"{name} and v must have the same number of rows")
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    E = int(num_experts)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
+    lay = _lora_layout(layout)
+    shape = (E, C, r) if lay == _native.LORA_CR else (E, r, C)
+    if T == 0 or C == 0 or E == 0:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    d = torch.empty(shape, dtype=torch.float32, device=dev)
+    if vv.data_ptr() % 16:
+        vv = vv.clone()
+    _launch("fql_lora_gated_grad" if gated else "fql_lora_grad", dev, pp, _DTYPES[pp.dtype], vv, tpe, offs, d, lay,
+            E, T, C, r, float(scale))
+    return d
+
+
+def lora_shrink(input, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
+    """Segmented ``out[t] = scale * input[t] @ W_e^T`` -> [T, r] float32: ``weight`` [E, r, C] (``layout='rc'``, e.g.
+    lora_A) or [E, C, r] (``'cr'``, e.g. lora_B), 2-D for one segment.  Rows no expert covers are zero.  ``input`` may
+    be float16 / bfloat16: read as it is, bit for bit the call on ``input.float()`` (INTEGRATION.md section 8)."""
+    return _lora_shrink(input, weight, layout, tokens_per_expert, input_offsets, scale, gated=False)
 
 
 def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=None, scale=1.0, input=None, out=None,
@@ -1134,7 +989,7 @@ def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=No
     w, E, r = _lora_weight(weight, layout, C, dev, "weight")
     if vv.shape[1] != r:
         raise RuntimeError(f"v has {vv.shape[1]} columns where the adapter rank is {r}")
-    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
     inp = None
     if input is not None:
         if tuple(input.shape) != (T, C):
@@ -1152,14 +1007,8 @@ def lora_expand(v, weight, layout="cr", tokens_per_expert=None, input_offsets=No
                            "device (of out_dtype, when that is given)")
     if T == 0 or C == 0:
         return out
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_expand(vv.data_ptr(), w.data_ptr(), _lora_layout(layout),
-                                           None if tpe is None else tpe.data_ptr(),
-                                           None if offs is None else offs.data_ptr(),
-                                           None if inp is None else inp.data_ptr(),
-                                           _native.DTYPE_F32 if inp is None else _DTYPES[inp.dtype], out.data_ptr(),
-                                           _DTYPES[out.dtype], E, T, C, r, float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_expand")
+    _launch("fql_lora_expand", dev, vv, w, _lora_layout(layout), tpe, offs, inp,
+            _native.DTYPE_F32 if inp is None else _DTYPES[inp.dtype], out, _DTYPES[out.dtype], E, T, C, r, float(scale))
     return out
 
 
@@ -1167,31 +1016,7 @@ def lora_grad(p, v, layout, num_experts=1, tokens_per_expert=None, input_offsets
     """Segment reduction ``D_e = scale * sum_{t of e} p[t]^T v[t]`` per expert: ``p`` [T, C], ``v`` [T, r] ->
     [E, C, r] (``layout='cr'``: dB) or [E, r, C] (``'rc'``: dA), float32.  Experts without rows get zeros.  ``p`` may be
     float16 / bfloat16: read as it is, bit for bit the call on ``p.float()``."""
-    dev = p.device
-    pp = _lora_rows(p, "p", dev, wide=True)
-    vv = _lora_rows(v, "v", dev)
-    T, C = pp.shape
-    r = vv.shape[1]
-    if vv.shape[0] != T:
-        raise RuntimeError("p and v must have the same number of rows")
-    if r not in LORA_RANKS:
-        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
-    E = int(num_experts)
-    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
-    lay = _lora_layout(layout)
-    shape = (E, C, r) if lay == _native.LORA_CR else (E, r, C)
-    if T == 0 or C == 0 or E == 0:
-        return torch.zeros(shape, dtype=torch.float32, device=dev)
-    d = torch.empty(shape, dtype=torch.float32, device=dev)
-    if vv.data_ptr() % 16:
-        vv = vv.clone()
-    with torch.cuda.device(dev):
-        rc = _native.lib().fql_lora_grad(pp.data_ptr(), _DTYPES[pp.dtype], vv.data_ptr(),
-                                         None if tpe is None else tpe.data_ptr(),
-                                         None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T, C, r,
-                                         float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_grad")
-    return d
+    return _lora_grad(p, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated=False)
 
 
 def _lora_check_adapters(lora_A, lora_B, K, N, E):
@@ -1212,25 +1037,21 @@ def _lora_check_adapters(lora_A, lora_B, K, N, E):
         raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
 
 
+def _expand_into(v, weight, layout, base32, dtype, tpe=None, offs=None, scale=1.0):
+    """``base32 + scale * v W`` in ``dtype``: in place on the float32 base, or one 16-bit write from it."""
+    if dtype == torch.float32:
+        return lora_expand(v, weight, layout, tpe, offs, scale=scale, input=base32, out=base32)
+    return lora_expand(v, weight, layout, tpe, offs, scale=scale, input=base32, out_dtype=dtype)
+
+
 def _linear_lora_apply(x2, packed, scales, zps, lora_A, lora_B, scaling, precision, bias):
-    """Base forward, then U = x A^T and y += scaling * U B^T in place.  Returns (y, U).
-    16-bit x: the base GEMM reads x as it is and writes float32, the shrink reads x as it is, and the expand reads that
-    float32 and writes y in x's type -- one rounding, no float32 copy of x."""
-    if x2.dtype == torch.float32:
-        y = linear_forward(x2, packed, scales, zps, precision=precision, bias=bias)
-        u = lora_shrink(x2, lora_A, "rc")
-        lora_expand(u, lora_B, "cr", scale=scaling, input=y, out=y)
-        return y, u
-    if _per_group(scales):                                      # unfused branch: torch widens x
-        y32 = linear_forward(x2.float(), packed, scales, zps, precision=precision, bias=bias)
-    else:
-        y32 = linear_forward_any(x2, packed, scales, zps, precision=precision, out_dtype=torch.float32, bias=bias)
+    """Base forward to float32, U = x A^T, then y = base + scaling * U B^T in x's type.  Returns (y, U).
+    16-bit x: the base GEMM and the shrink read x as it is and the expand writes y once -- one rounding, no float32
+    copy of x (but on the unfused per-group branch, where torch widens x)."""
+    y32 = linear_forward_any(x2.float() if _per_group(scales) else x2, packed, scales, zps, precision=precision,
+                             out_dtype=torch.float32, bias=bias)
     u = lora_shrink(x2, lora_A, "rc")
-    return lora_expand(u, lora_B, "cr", scale=scaling, input=y32, out_dtype=x2.dtype), u
-
-
-def _per_group(scales):
-    return scales.dim() == 2 and scales.shape[1] > 1
+    return _expand_into(u, lora_B, "cr", y32, x2.dtype, scale=scaling), u
 
 
 def linear_lora_forward(x, packed, scales, zps, lora_A, lora_B, scaling, precision="default", bias=None):
@@ -1274,14 +1095,9 @@ def moe_lora_forward(packed, scales, zps, inputs, lora_A, lora_B, scaling, token
 
 
 def _moe_lora_apply(packed, scales, zps, inputs, lora_A, lora_B, scaling, tpe, offs, precision):
-    if inputs.dtype == torch.float32:
-        y = moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
-        u = lora_shrink(inputs, lora_A, "rc", tpe, offs)
-        lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y, out=y)
-        return y, u
     y32 = moe_forward_any(packed, scales, zps, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
     u = lora_shrink(inputs, lora_A, "rc", tpe, offs)
-    return lora_expand(u, lora_B, "cr", tpe, offs, scale=scaling, input=y32, out_dtype=inputs.dtype), u
+    return _expand_into(u, lora_B, "cr", y32, inputs.dtype, tpe, offs, scaling), u
 
 
 class _LinearLoRAFn(torch.autograd.Function):
@@ -1310,7 +1126,7 @@ class _LinearLoRAFn(torch.autograd.Function):
                     gx = group_backward_input(g.to(torch.float32), packed, scales, zps)
                 else:
                     gx = linear_backward_input(g, packed, scales, zps, precision=ctx.precision)
-                gx = _expand_into(du, lora_A, gx, x2.dtype)                     # dX += dU A
+                gx = _expand_into(du, lora_A, "rc", gx, x2.dtype)               # dX += dU A
                 gx = gx.reshape(-1) if ctx.x_dim == 1 else gx
             if need_A:
                 gA = lora_grad(x2, du, "rc")[0]                                  # dA = dU^T X
@@ -1326,13 +1142,6 @@ def _grad_rows(gy):
     if gy.dtype not in _DTYPES:
         raise RuntimeError("the gradient must be float32, float16 or bfloat16")
     return gy.contiguous()
-
-
-def _expand_into(du, lora_A, gx32, dtype, tpe=None, offs=None):
-    """dX = gx32 + dU A in ``dtype``: in place on the float32 base gradient, or one 16-bit write from it."""
-    if dtype == torch.float32:
-        return lora_expand(du, lora_A, "rc", tpe, offs, input=gx32, out=gx32)
-    return lora_expand(du, lora_A, "rc", tpe, offs, input=gx32, out_dtype=dtype)
 
 
 class _MoELoRAFn(torch.autograd.Function):
@@ -1358,7 +1167,7 @@ class _MoELoRAFn(torch.autograd.Function):
             du = lora_shrink(g, lora_B, "cr", tpe, offs, scale=ctx.scaling)
             if need_x:
                 gx = moe_backward_input(packed, scales, zps, g, tpe, offs, precision=ctx.precision)
-                gx = _expand_into(du, lora_A, gx, x.dtype, tpe, offs)
+                gx = _expand_into(du, lora_A, "rc", gx, x.dtype, tpe, offs)
             if need_A:
                 gA = lora_grad(x, du, "rc", E, tpe, offs)
         if need_B:
@@ -1373,75 +1182,18 @@ class _MoELoRAFn(torch.autograd.Function):
 # streaming kernel.
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _gate_up_rows(gate_up, dev):
-    g = _lora_rows(gate_up, "gate_up", dev, wide=True)
-    if g.shape[1] % 2:
-        raise RuntimeError("gate_up must be [T, 2C] (gate | up)")
-    return g, g.shape[0], g.shape[1] // 2
-
-
 def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
     """``lora_shrink`` on the hidden activation of a gated FFN expert without materialising it:
     ``out[t] = scale * (silu(gate_up[t, :C]) * gate_up[t, C:]) @ W_e^T`` -> [T, r] float32; ``gate_up`` [T, 2C]
     float32, or float16 / bfloat16 read as it is: bit for bit the call on ``gate_up.float()``."""
-    dev = gate_up.device
-    g, T, C = _gate_up_rows(gate_up, dev)
-    w, E, r = _lora_weight(weight, layout, C, dev, "weight")
-    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
-    out = torch.empty((T, r), dtype=torch.float32, device=dev)
-    if T == 0:
-        return out
-    if C == 0:
-        return out.zero_()
-    with torch.cuda.device(dev):
-        if g.dtype == torch.float32:
-            rc = _native.lib().fql_lora_gated_shrink_f32(g.data_ptr(), w.data_ptr(), _lora_layout(layout),
-                                                         None if tpe is None else tpe.data_ptr(),
-                                                         None if offs is None else offs.data_ptr(), out.data_ptr(), E,
-                                                         T, C, r, float(scale), _stream_ptr(dev))
-        else:
-            rc = _native.lib().fql_lora_gated_shrink(g.data_ptr(), _DTYPES[g.dtype], w.data_ptr(), _lora_layout(layout),
-                                                     None if tpe is None else tpe.data_ptr(),
-                                                     None if offs is None else offs.data_ptr(), out.data_ptr(), E, T,
-                                                     C, r, float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_gated_shrink")
-    return out
+    return _lora_shrink(gate_up, weight, layout, tokens_per_expert, input_offsets, scale, gated=True)
 
 
 def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
     """``lora_grad`` with ``p = silu(gate_up[:, :C]) * gate_up[:, C:]`` formed on the fly: ``gate_up`` [T, 2C],
     ``v`` [T, r] -> [E, C, r] (``layout='cr'``) or [E, r, C] (``'rc'``: dA of the down adapter), float32.  ``gate_up``
     may be float16 / bfloat16: read as it is, bit for bit the call on ``gate_up.float()``."""
-    dev = gate_up.device
-    g, T, C = _gate_up_rows(gate_up, dev)
-    vv = _lora_rows(v, "v", dev)
-    r = vv.shape[1]
-    if vv.shape[0] != T:
-        raise RuntimeError("gate_up and v must have the same number of rows")
-    if r not in LORA_RANKS:
-        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
-    E = int(num_experts)
-    tpe, offs = _lora_table(tokens_per_expert, input_offsets, E, dev)
-    lay = _lora_layout(layout)
-    shape = (E, C, r) if lay == _native.LORA_CR else (E, r, C)
-    if T == 0 or C == 0 or E == 0:
-        return torch.zeros(shape, dtype=torch.float32, device=dev)
-    d = torch.empty(shape, dtype=torch.float32, device=dev)
-    if vv.data_ptr() % 16:
-        vv = vv.clone()
-    with torch.cuda.device(dev):
-        if g.dtype == torch.float32:
-            rc = _native.lib().fql_lora_gated_grad_f32(g.data_ptr(), vv.data_ptr(),
-                                                       None if tpe is None else tpe.data_ptr(),
-                                                       None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E,
-                                                       T, C, r, float(scale), _stream_ptr(dev))
-        else:
-            rc = _native.lib().fql_lora_gated_grad(g.data_ptr(), _DTYPES[g.dtype], vv.data_ptr(),
-                                                   None if tpe is None else tpe.data_ptr(),
-                                                   None if offs is None else offs.data_ptr(), d.data_ptr(), lay, E, T,
-                                                   C, r, float(scale), _stream_ptr(dev))
-    _native.check(rc, "fql_lora_gated_grad")
-    return d
+    return _lora_grad(gate_up, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated=True)
 
 
 def swiglu_backward(gate_up, dh, out_dtype=None):
@@ -1460,13 +1212,7 @@ def swiglu_backward(gate_up, dh, out_dtype=None):
     out = torch.empty((T, 2 * F), dtype=out_dtype, device=dev)
     if T == 0 or F == 0:
         return out
-    with torch.cuda.device(dev):
-        if g.dtype == d.dtype == out_dtype == torch.float32:
-            rc = _native.lib().fql_swiglu_bwd_f32(g.data_ptr(), d.data_ptr(), out.data_ptr(), T, F, _stream_ptr(dev))
-        else:
-            rc = _native.lib().fql_swiglu_bwd(g.data_ptr(), _DTYPES[g.dtype], d.data_ptr(), _DTYPES[d.dtype],
-                                              out.data_ptr(), _DTYPES[out_dtype], T, F, _stream_ptr(dev))
-    _native.check(rc, "fql_swiglu_bwd")
+    _launch("fql_swiglu_bwd", dev, g, _DTYPES[g.dtype], d, _DTYPES[d.dtype], out, _DTYPES[out_dtype], T, F)
     return out
 
 
@@ -1526,30 +1272,23 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
         return _MoEFFNLoRAFn.apply(inputs, *adapters, *weights, tokens_per_expert, input_offsets, float(scaling),
                                    precision, dt)
     return _moe_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets,
-                               precision, dt)[0]
+                               precision)[0]
 
 
-def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision, dt=None):
-    """Returns (y, gate_up, U_gu, U_d): both projections with their adapters expanded in place into the base outputs.
-    ``dt`` (a 16-bit type): each base GEMM reads its 16-bit operand as it is and writes float32, and the expand writes
-    that plus the adapter term once in ``dt`` -- gate_up (rounding 1) and y (rounding 2)."""
+def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision):
+    """Returns (y, gate_up, U_gu, U_d), y and gate_up in ``inputs``' type: each base GEMM reads its operand as it is and
+    writes float32, and the expand adds the adapter term to that in place (float32) or writes the sum once in the 16-bit
+    type -- gate_up (rounding 1) and y (rounding 2)."""
     gup, gus, guz, dp, ds, dz = weights
     A_gu, B_gu, A_d, B_d = adapters
-    if dt is not None:
-        gu32 = moe_forward_any(gup, gus, guz, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
-        u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
-        gate_up = lora_expand(u_gu, B_gu, "cr", tpe, offs, scale=scaling, input=gu32, out_dtype=dt)
-        del gu32
-        y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32)
-        u_d = lora_gated_shrink(gate_up, A_d, "rc", tpe, offs)
-        return lora_expand(u_d, B_d, "cr", tpe, offs, scale=scaling, input=y32, out_dtype=dt), gate_up, u_gu, u_d
-    gate_up = moe_forward(gup, gus, guz, inputs, None, tpe, offs, precision=precision)
+    dt = inputs.dtype
+    gu32 = moe_forward_any(gup, gus, guz, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
     u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
-    lora_expand(u_gu, B_gu, "cr", tpe, offs, scale=scaling, input=gate_up, out=gate_up)
-    y = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision)
+    gate_up = _expand_into(u_gu, B_gu, "cr", gu32, dt, tpe, offs, scaling)
+    del gu32
+    y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32)
     u_d = lora_gated_shrink(gate_up, A_d, "rc", tpe, offs)
-    lora_expand(u_d, B_d, "cr", tpe, offs, scale=scaling, input=y, out=y)
-    return y, gate_up, u_gu, u_d
+    return _expand_into(u_d, B_d, "cr", y32, dt, tpe, offs, scaling), gate_up, u_gu, u_d
 
 
 class _MoEFFNLoRAFn(torch.autograd.Function):
@@ -1561,7 +1300,7 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
     def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision, dt=None):
         x = inputs.contiguous()
         y, gate_up, u_gu, u_d = _moe_ffn_lora_apply((gup, gus, guz, dp, ds, dz), x, (A_gu, B_gu, A_d, B_d), scaling,
-                                                    tpe, offs, precision, dt)
+                                                    tpe, offs, precision)
         ctx.save_for_backward(x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs)
         ctx.scaling, ctx.precision, ctx.act_dtype = scaling, precision, dt
         return y
@@ -1569,13 +1308,17 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
+        """Every kernel reads its operand in the type it has.  The base input gradients are float32; the expand adds the
+        adapter term in place, or (16-bit ``dt``) writes dh (rounding 3) and dx (rounding 5) once in ``dt``, as
+        swiglu_backward writes dgu (rounding 4).  Adapter gradients are float32."""
         x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
         need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
         E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
         if ctx.act_dtype is not None:
             check_activation_rows(gy, "the incoming gradient", ctx.act_dtype)
-            return _moe_ffn_lora_backward16(ctx, gy.contiguous(), ctx.act_dtype) + (None,) * 11
-        g = gy.to(torch.float32).contiguous()
+            g, dt = gy.contiguous(), ctx.act_dtype
+        else:
+            g, dt = gy.to(torch.float32).contiguous(), torch.float32
         gx = gAgu = gBgu = gAd = gBd = None
         if need_Bd:
             gBd = lora_grad(g, u_d, "cr", E, tpe, offs, scale=s)                         # dB_d = s dY^T U_d
@@ -1585,9 +1328,9 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
             if need_Ad:
                 gAd = lora_gated_grad(gate_up, du_d, "rc", E, tpe, offs)                 # dA_d = dU_d^T h
         if through:
-            dh = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)            # dh = dY W_d
-            lora_expand(du_d, A_d, "rc", tpe, offs, input=dh, out=dh)                    #      + dU_d A_d
-            dgu = swiglu_backward(gate_up, dh)
+            dh = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)            # dh = dY W_d (float32)
+            dh = _expand_into(du_d, A_d, "rc", dh, dt, tpe, offs)                        #      + dU_d A_d, in dt
+            dgu = swiglu_backward(gate_up, dh, out_dtype=dt)
             del dh
             if need_Bgu:
                 gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
@@ -1595,40 +1338,7 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
                 du_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dU_gu = s dgu B_gu
                 if need_x:
                     gx = moe_backward_input(gup, gus, guz, dgu, tpe, offs, precision=prec)
-                    lora_expand(du_gu, A_gu, "rc", tpe, offs, input=gx, out=gx)          # dx = dgu W_gu + dU_gu A_gu
+                    gx = _expand_into(du_gu, A_gu, "rc", gx, dt, tpe, offs)              # dx = dgu W_gu + dU_gu A_gu
                 if need_Agu:
                     gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
         return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 11
-
-
-def _moe_ffn_lora_backward16(ctx, g, dt):
-    """The backward of the node on 16-bit activations: every kernel reads its 16-bit operand as it is; the base input
-    gradients are float32 and the expand writes dh (rounding 3) and dx (rounding 5) once in ``dt``; swiglu_backward writes
-    dgu in ``dt`` (rounding 4).  Adapter gradients are float32."""
-    x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
-    need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
-    E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
-    gx = gAgu = gBgu = gAd = gBd = None
-    if need_Bd:
-        gBd = lora_grad(g, u_d, "cr", E, tpe, offs, scale=s)                         # dB_d = s dY^T U_d
-    through = need_x or need_Agu or need_Bgu                                        # anything upstream of h
-    if through or need_Ad:
-        du_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dU_d = s dY B_d
-        if need_Ad:
-            gAd = lora_gated_grad(gate_up, du_d, "rc", E, tpe, offs)                 # dA_d = dU_d^T h
-    if through:
-        dh32 = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)          # dh = dY W_d (float32)
-        dh = lora_expand(du_d, A_d, "rc", tpe, offs, input=dh32, out_dtype=dt)       #      + dU_d A_d, in dt
-        del dh32
-        dgu = swiglu_backward(gate_up, dh, out_dtype=dt)
-        del dh
-        if need_Bgu:
-            gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
-        if need_x or need_Agu:
-            du_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dU_gu = s dgu B_gu
-            if need_x:
-                gx32 = moe_backward_input(gup, gus, guz, dgu, tpe, offs, precision=prec)
-                gx = lora_expand(du_gu, A_gu, "rc", tpe, offs, input=gx32, out_dtype=dt)   # dx = dgu W_gu + dU_gu A_gu
-            if need_Agu:
-                gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
-    return gx, gAgu, gBgu, gAd, gBd

@@ -1,0 +1,266 @@
+"""Bit-for-bit fingerprint of the operator boundary: one fixed, seeded list of calls into ``ops`` (and the gated FFN
+modules) on tiny shapes that still reach every branch of the wrappers; for each call one line per returned tensor and,
+for the differentiable ops, per gradient: ``name  dtype  shape  sha256``.  Two checkouts that print the same lines on
+the same machine compute the same bits through the Python layer.  ``--list`` prints the call names without a GPU.
+
+Branches reached: GEMV (B = 1, 2), generic (K = 34), MFMA (B = 48, K = 64, N = 40); grouped calls on E = 3 with one empty
+expert and four uncovered tail rows; per-group scales (K = 128, group 64) at B = 2 and 48; 16-bit calls on the native
+path (K = 64) and on the widened fallback (K = 34); bias present and absent; 1-D and 2-D input; a misaligned float32 view
+as LoRA weight and as ``v`` (the ``clone()`` branches); LoRA ranks 4 and 64; C = 30, 34, 64 (vector widths 1, 2, 4);
+``lora_expand`` in place and with ``out_dtype``; ``combine`` with and without weights; the LoRA layers and the gated FFN
+in float32, float16 and bfloat16 with every gradient and with the input gradient alone."""
+import argparse
+import hashlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+E, TAIL = 3, 4
+COUNTS = [29, 0, 19]                       # one empty expert; T = 48 + TAIL rows, the last TAIL covered by no expert
+T = sum(COUNTS) + TAIL
+F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
+
+
+class Data:
+    """Every operand comes from one CPU generator (seed 0), in a fixed order, then moves to the device."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.gen = torch.Generator().manual_seed(0)
+
+    def randn(self, *shape, dtype=F32, scale=1.0):
+        return (torch.randn(shape, generator=self.gen) * scale).to(dtype).to(self.dev)
+
+    def weights(self, *shape, groups=None):
+        """(packed uint8 [..., K/2], scales, zero_points [...] or [..., groups]) of random INT4 weights [..., K]."""
+        *lead, K = shape
+        packed = torch.randint(0, 256, (*lead, K // 2), dtype=torch.uint8, generator=self.gen)
+        sz = tuple(lead) if groups is None else (*lead, groups)
+        scales = torch.rand(sz, generator=self.gen) * 0.02 + 0.002
+        zps = torch.randint(0, 16, sz, generator=self.gen).float()
+        return packed.to(self.dev), scales.to(self.dev), zps.to(self.dev)
+
+    def table(self):
+        cnt = torch.tensor(COUNTS, dtype=torch.int32)
+        return cnt.to(self.dev), (torch.cumsum(cnt, 0, dtype=torch.int32) - cnt).to(self.dev)
+
+    def misaligned(self, t):
+        """``buf[1:]`` of a float32 buffer: contiguous, 4 bytes past the allocation's alignment."""
+        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+        view = buf[1:].view(t.shape)
+        view.copy_(t)
+        return view
+
+
+def with_grads(fn, tensors, gy_of, only_first=False):
+    """Run ``fn(*leaves)`` under autograd on detached copies of ``tensors`` (all requiring grad, or the first alone) and
+    return (output, grad of each leaf that required one)."""
+    leaves = [t.detach().clone().requires_grad_(i == 0 or not only_first) for i, t in enumerate(tensors)]
+    y = fn(*leaves)
+    y.backward(gy_of(y))
+    return (y.detach(),) + tuple(t.grad for t in leaves if t.requires_grad)
+
+
+def calls(dev, fq, ops):
+    d = Data(dev)
+    tpe, offs = d.table()
+
+    # ---------------------------------------------------------------- linear: GEMV, generic, MFMA, per-group, 16-bit
+    for B, K, N in ((1, 64, 40), (2, 64, 40), (2, 34, 40), (48, 34, 40), (48, 64, 40)):
+        p, s, z = d.weights(N, K)
+        x, bias = d.randn(B, K), d.randn(N)
+        yield f"linear_forward B{B} K{K}", lambda: ops.linear_forward(x, p, s, z)
+        yield f"linear_forward B{B} K{K} bias", lambda: ops.linear_forward(x, p, s, z, bias=bias)
+        yield f"linear_forward B{B} K{K} 1-D", lambda: ops.linear_forward(x[0], p, s, z, precision="fast")
+        for dt in (F16, BF16):
+            yield f"linear_forward_any B{B} K{K} {dt}", lambda: ops.linear_forward_any(x.to(dt), p, s, z, bias=bias)
+            yield f"linear_forward_any B{B} K{K} f32->{dt}", lambda: ops.linear_forward_any(x, p, s, z, out_dtype=dt)
+        yield f"linear_forward grad B{B} K{K}", lambda: with_grads(
+            lambda x_, b_: ops.linear_forward(x_, p, s, z, bias=b_), (x, bias), torch.ones_like)
+        gy = d.randn(B, N)
+        for dt in (F32, F16, BF16):
+            yield f"linear_backward_input B{B} K{K} {dt}", lambda: ops.linear_backward_input(gy.to(dt), p, s, z, out_dtype=dt)
+    for B in (2, 48):
+        p, s, z = d.weights(40, 128, groups=2)
+        x, bias = d.randn(B, 128), d.randn(40)
+        yield f"linear_forward per-group B{B}", lambda: ops.linear_forward(x, p, s, z)
+        yield f"linear_forward per-group B{B} bias 1-D", lambda: ops.linear_forward(x[0], p, s, z, bias=bias, precision="int8")
+        yield f"linear_forward per-group grad B{B}", lambda: with_grads(
+            lambda x_, b_: ops.linear_forward(x_, p, s, z, bias=b_), (x, bias), torch.ones_like)
+    pg, sg, zg = d.weights(E, 40, 128, groups=2)
+    xg = d.randn(T, 128)
+    yield "moe_group_forward", lambda: ops.moe_group_forward(pg, sg, zg, xg, tpe, offs)
+    yield "moe_group_forward int8", lambda: ops.moe_group_forward(pg, sg, zg, xg, tpe, offs, precision="int8")
+    p, s, z = d.weights(40, 64)
+    w = d.randn(40, 64)
+    yield "quantize_rows", lambda: ops.quantize_rows(w)
+    yield "quantize_tensor", lambda: ops.quantize_tensor(w)
+    yield "unpack_nibbles", lambda: ops.unpack_nibbles(p)
+    yield "dequantize_forward", lambda: ops.dequantize_forward(p, s, z)
+
+    # ---------------------------------------------------------------- grouped: E = 3, one empty expert, 4 tail rows
+    for K in (64, 34):
+        P, S, Z = d.weights(E, 40, K)
+        x, gy = d.randn(T, K), d.randn(T, 40)
+        yield f"moe_forward K{K}", lambda: ops.moe_forward(P, S, Z, x, None, tpe, offs)
+        yield f"moe_forward K{K} exact", lambda: ops.moe_forward(P, S, Z, x, None, tpe, offs, precision="exact")
+        for dt in (F16, BF16):
+            yield f"moe_forward_any K{K} {dt}", lambda: ops.moe_forward_any(P, S, Z, x.to(dt), None, tpe, offs)
+            yield f"moe_forward_any K{K} {dt}->f32", lambda: ops.moe_forward_any(P, S, Z, x.to(dt), None, tpe, offs, out_dtype=F32)
+            yield f"moe_backward_input K{K} {dt}", lambda: ops.moe_backward_input(P, S, Z, gy.to(dt), tpe, offs, out_dtype=dt)
+            yield f"moe_forward_any grad K{K} {dt}", lambda: with_grads(
+                lambda x_: ops.moe_forward_any(P, S, Z, x_, None, tpe, offs), (x.to(dt),), torch.ones_like)
+        yield f"moe_backward_input K{K}", lambda: ops.moe_backward_input(P, S, Z, gy, tpe, offs)
+        yield f"moe_forward grad K{K}", lambda: with_grads(
+            lambda x_: ops.moe_forward(P, S, Z, x_, None, tpe, offs), (x,), torch.ones_like)
+    P, S, Z = d.weights(E, 40, 64)
+    x = d.randn(T, 64)
+    tokens, ri, rw = d.randn(16, 64), (torch.arange(T, dtype=torch.int32) % 16).to(dev), d.randn(T)
+    yield "moe_gather_forward", lambda: ops.moe_gather_forward(P, S, Z, tokens, ri, tpe, offs)
+    yield "moe_gather_forward row_weight", lambda: ops.moe_gather_forward(P, S, Z, tokens, ri, tpe, offs, row_weight=rw)
+    gu = d.randn(T, 128)
+    for dt in (F32, F16, BF16):
+        yield f"moe_gated_forward {dt}", lambda: ops.moe_gated_forward(P, S, Z, gu.to(dt), tpe, offs)
+        yield f"moe_gated_forward {dt}->f32", lambda: ops.moe_gated_forward(P, S, Z, gu.to(dt), tpe, offs, out_dtype=F32)
+        dh = d.randn(T, 64)
+        yield f"swiglu_backward {dt}", lambda: ops.swiglu_backward(gu.to(dt), dh.to(dt))
+        yield f"swiglu_backward {dt} mixed", lambda: ops.swiglu_backward(gu.to(dt), dh, out_dtype=F16)
+    x8, asc = ops.quantize_activations_fp8(x)
+    yield "moe_forward_fp8", lambda: ops.moe_forward_fp8(P, S, Z, x8, asc, tpe, offs)
+    yield "moe_forward_fp8 f16 unscaled", lambda: ops.moe_forward_fp8(P, S, Z, x8, None, tpe, offs, out_dtype=F16)
+    yield "linear_forward_fp8", lambda: ops.linear_forward_fp8(x8, asc, P[0], S[0], Z[0])
+    yield "linear_forward_fp8 bf16 unscaled", lambda: ops.linear_forward_fp8(x8, None, P[0], S[0], Z[0], out_dtype=BF16)
+    for prec in ("exact", "int8"):
+        def two_phase(prec=prec, grouped=True):
+            bufs = ops.act_quant(x, prec, tpe, offs) if grouped else ops.act_quant(x, prec)
+            out = ops.gemm_i8(*bufs, P, S, Z, tpe, offs, precision=prec) if grouped else \
+                ops.gemm_i8(*bufs, P[0], S[0], Z[0], precision=prec)
+            return bufs[1], bufs[2], out
+        yield f"act_quant + gemm_i8 grouped {prec}", two_phase
+        yield f"act_quant + gemm_i8 one group {prec}", lambda: two_phase(grouped=False)
+
+    # ---------------------------------------------------------------- routing
+    idx = torch.randint(0, E, (24, 2), generator=d.gen).to(dev)
+    yield "route_plan", lambda: ops.route_plan(idx, E)
+    y, wts = d.randn(48, 40), d.randn(24, 2)
+    pos = torch.randperm(48, generator=d.gen).to(torch.int32).to(dev)
+    yield "combine", lambda: ops.combine(y, pos, wts)
+    yield "combine unweighted", lambda: ops.combine(y, pos, None, top_k=2)
+    yield "combine grad", lambda: with_grads(lambda y_, w_: ops.combine(y_, pos, w_), (y, wts), torch.ones_like)
+    yield "combine grad unweighted", lambda: with_grads(lambda y_: ops.combine(y_, pos, None, top_k=2), (y,), torch.ones_like)
+    yield "combine_backward short y", lambda: ops.combine_backward(d.randn(24, 40), d.randn(60, 40), pos, wts)[0]
+    yield "regroup_index", lambda: ops.regroup_index(torch.tensor([[3, 0, 2], [1, 4, 0]], dtype=torch.int32, device=dev), 10)
+
+    # ---------------------------------------------------------------- LoRA kernels: ranks 4 / 64, C = 30 / 34 / 64
+    for r in (4, 64):
+        for C in (30, 34, 64):
+            A, Bw = d.randn(E, r, C, scale=0.1), d.randn(E, C, r, scale=0.1)
+            xin, v, base = d.randn(T, C), d.randn(T, r), d.randn(T, C)
+            gu2 = d.randn(T, 2 * C)
+            for dt in (F32, F16, BF16):
+                yield f"lora_shrink r{r} C{C} {dt}", lambda: ops.lora_shrink(xin.to(dt), A, "rc", tpe, offs, scale=0.5)
+                yield f"lora_grad r{r} C{C} {dt}", lambda: ops.lora_grad(xin.to(dt), v, "cr", E, tpe, offs, scale=0.5)
+                yield f"lora_gated_shrink r{r} C{C} {dt}", lambda: ops.lora_gated_shrink(gu2.to(dt), A, "rc", tpe, offs)
+                yield f"lora_gated_grad r{r} C{C} {dt}", lambda: ops.lora_gated_grad(gu2.to(dt), v, "rc", E, tpe, offs)
+                yield f"lora_expand r{r} C{C} ->{dt}", lambda: ops.lora_expand(v, Bw, "cr", tpe, offs, scale=2.0, input=base, out_dtype=dt)
+            yield f"lora_shrink r{r} C{C} cr", lambda: ops.lora_shrink(xin, Bw, "cr", tpe, offs)
+            yield f"lora_shrink r{r} C{C} one segment", lambda: ops.lora_shrink(xin, A[0], "rc")
+            yield f"lora_shrink r{r} C{C} misaligned", lambda: ops.lora_shrink(xin, d.misaligned(A), "rc", tpe, offs)
+            yield f"lora_gated_shrink r{r} C{C} misaligned", lambda: ops.lora_gated_shrink(gu2, d.misaligned(A), "rc", tpe, offs)
+            yield f"lora_grad r{r} C{C} misaligned v", lambda: ops.lora_grad(xin, d.misaligned(v), "rc", E, tpe, offs)
+            yield f"lora_gated_grad r{r} C{C} misaligned v", lambda: ops.lora_gated_grad(gu2, d.misaligned(v), "cr", E, tpe, offs)
+            yield f"lora_expand r{r} C{C} in place", lambda: ops.lora_expand(v, Bw, "cr", tpe, offs, input=(b := base.clone()), out=b)
+            yield f"lora_expand r{r} C{C} no input rc", lambda: ops.lora_expand(v, A, "rc", tpe, offs, out=torch.empty_like(base))
+            yield f"lora_expand r{r} C{C} misaligned", lambda: ops.lora_expand(d.misaligned(v), d.misaligned(Bw), "cr", tpe, offs, input=base.to(BF16))
+
+    # ---------------------------------------------------------------- the LoRA layers, f32 / f16 / bf16
+    for r in (4, 64):
+        for K, bias_on in ((64, True), (34, False)):
+            p, s, z = d.weights(40, K)
+            P, S, Z = d.weights(E, 40, K)
+            A1, B1, bias = d.randn(r, K, scale=0.1), d.randn(40, r, scale=0.1), d.randn(40)
+            A, Bm = d.randn(E, r, K, scale=0.1), d.randn(E, 40, r, scale=0.1)
+            x1, x = d.randn(2, K), d.randn(T, K)
+            for dt in (F32, F16, BF16):
+                b = bias if bias_on else None
+                yield f"linear_lora_forward r{r} K{K} {dt}", lambda: ops.linear_lora_forward(x.to(dt), p, s, z, A1, B1, 2.0, bias=b)
+                yield f"linear_lora_forward r{r} K{K} {dt} 1-D", lambda: ops.linear_lora_forward(x1[0].to(dt), p, s, z, A1, B1, 2.0, bias=b)
+                yield f"moe_lora_forward r{r} K{K} {dt}", lambda: ops.moe_lora_forward(P, S, Z, x.to(dt), A, Bm, 2.0, tpe, offs)
+                for only in (False, True):
+                    tag = "dx only" if only else "all grads"
+                    yield f"linear_lora_forward r{r} K{K} {dt} {tag}", lambda: with_grads(
+                        lambda x_, A_, B_: ops.linear_lora_forward(x_, p, s, z, A_, B_, 2.0, bias=b),
+                        (x.to(dt), A1, B1), torch.ones_like, only)
+                    yield f"moe_lora_forward r{r} K{K} {dt} {tag}", lambda: with_grads(
+                        lambda x_, A_, B_: ops.moe_lora_forward(P, S, Z, x_, A_, B_, 2.0, tpe, offs),
+                        (x.to(dt), A, Bm), torch.ones_like, only)
+        pg, sg, zg = d.weights(40, 128, groups=2)
+        A1, B1, x = d.randn(r, 128, scale=0.1), d.randn(40, r, scale=0.1), d.randn(T, 128)
+        for dt in (F32, BF16):
+            yield f"linear_lora_forward per-group r{r} {dt}", lambda: with_grads(
+                lambda x_, A_, B_: ops.linear_lora_forward(x_, pg, sg, zg, A_, B_, 2.0), (x.to(dt), A1, B1), torch.ones_like)
+
+    # ---------------------------------------------------------------- the gated FFN experts, with and without adapters
+    H, F = 64, 32
+    for r in (4, 64):
+        gup, gus, guz = d.weights(E, 2 * F, H)
+        dp, ds, dz = d.weights(E, H, F)
+        ad = [d.randn(E, r, H, scale=0.1), d.randn(E, 2 * F, r, scale=0.1), d.randn(E, r, F, scale=0.1),
+              d.randn(E, H, r, scale=0.1)]
+        x, gy = d.randn(T, H), d.randn(T, H)
+        for dt in (F32, F16, BF16):
+            act = None if dt == F32 else dt
+            m = fq.QuantizedMoEFFN(E, H, F, activation_dtype=act).to(dev)
+            for name, buf in zip(("gate_up_packed", "gate_up_scales", "gate_up_zero_points", "down_packed", "down_scales",
+                                  "down_zero_points"), (gup, gus, guz, dp, ds, dz)):
+                setattr(m, name, buf)
+
+            def layer(x_, *ad_):
+                return ops.moe_ffn_lora_forward(gup, gus, guz, dp, ds, dz, x_, *ad_, 2.0, tpe, offs, activation_dtype=act)
+            yield f"moe_ffn_lora_forward r{r} {dt}", lambda: layer(x.to(dt), *ad)
+            yield f"QuantizedMoEFFN r{r} {dt}", lambda: m(x.to(dt), tpe, offs)
+            yield f"QuantizedMoEFFN r{r} {dt} dx", lambda: with_grads(
+                lambda x_: m(x_, tpe, offs), (x.to(dt),), lambda y_: gy.to(y_.dtype))
+            for only in (False, True):
+                yield f"moe_ffn_lora_forward r{r} {dt} {'dx only' if only else 'all grads'}", lambda: with_grads(
+                    layer, (x.to(dt), *ad), lambda y_: gy.to(y_.dtype), only)
+
+
+def digest(t):
+    t = t.detach().contiguous().cpu()
+    raw = t.view(torch.uint8) if t.numel() else t.new_empty(0, dtype=torch.uint8)
+    return f"{str(t.dtype):15s} {str(tuple(t.shape)):16s} {hashlib.sha256(raw.numpy().tobytes()).hexdigest()}"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--list", action="store_true", help="print the call names only (needs no GPU)")
+    a = ap.parse_args()
+    import fused_int4_amd as fq
+    from fused_int4_amd import ops
+    if a.list:
+        dev = torch.device("meta")            # operands are shaped, never computed: the list itself needs no device
+        names = []
+        try:
+            for name, _ in calls(dev, fq, ops):
+                names.append(name)
+        finally:
+            print("\n".join(names))
+        return
+    dev = torch.device("cuda")
+    n = 0
+    for name, call in calls(dev, fq, ops):
+        out = call()
+        for i, t in enumerate(out if isinstance(out, (tuple, list)) else (out,)):
+            print(f"{name} [{i}]  " + ("None" if t is None else digest(t)))
+        n += 1
+    torch.cuda.synchronize()
+    print(f"# {n} calls")
+
+
+if __name__ == "__main__":
+    main()
