@@ -3,27 +3,13 @@
 // Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
+#include "fql_host.h"
 #include "fql_act_quant.h"
 #include "fql_bwd.h"
 
 namespace {
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-inline int padded(int n) { return (n + FQL_KB - 1) / FQL_KB * FQL_KB; }
-// 32-row blocks of the limb workspace (as fql_int4.hip): every expert starts on a block boundary, and a tile may run
-// up to 128 rows past the last expert
-inline long long row_blocks(int T, int E) { return ((long long)T + (long long)FQL_MB * E + 128 + FQL_MB - 1) / FQL_MB; }
-
-// Limbs of the backward: 3 (default / exact), 2 (fast), 1 (int8, and fp8 layers: the gradient is never an fp8 plane)
-inline int bwd_limbs(int precision)
-{
-    if (precision == FQL_PRECISION_DEFAULT) return 3;
-    if (precision == FQL_PRECISION_INT8 || precision == FQL_PRECISION_FAST || precision == FQL_PRECISION_EXACT)
-        return precision;
-    if (precision == FQL_PRECISION_FP8) return 1;
-    return -1;
-}
+using namespace fql_host;
 
 struct BwdWorkspace {
     int8_t *limbs = nullptr;
@@ -49,18 +35,6 @@ inline BwdWorkspace bwd_carve(void *base, int L, int T, int E, int Np)
     return w;
 }
 
-inline int compute_units()
-{
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    n -= n % 8;                                              // keep vb % 8 == blockIdx % 8 (XCD grouping)
-    return n > 0 ? n : 8;
-}
-
-inline bool dtype_ok(int d) { return d == FQL_DTYPE_F32 || d == FQL_DTYPE_F16 || d == FQL_DTYPE_BF16; }
-inline int elem_bytes(int d) { return d == FQL_DTYPE_F32 ? 4 : 2; }
-
 // IN / OUT: element types of gy / gx (FQL_DTYPE_*)
 template <int L, int IN, int OUT>
 int launch_bwd(const void *gy, const uint8_t *packed, const float *scales, const float *zps, void *gx,
@@ -78,20 +52,20 @@ int launch_bwd(const void *gy, const uint8_t *packed, const float *scales, const
                 const int32_t *, int, const float *, const float *) =
         single ? act_colscale_kernel<L, true, 1, IN>
                : (vec ? act_colscale_kernel<L, true, ACT_ROWS, IN> : act_colscale_kernel<L, false, ACT_ROWS, IN>);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(pre, dim3(rblocks + zblocks), dim3(256), 0, st, gy, w.delta, w.rowsum, w.limbs, T, N, Np / FQL_KB, MBT,
-                       rblocks, gx, elem_bytes(OUT), K, tpe, offs, E, scales, zps);
-    if (hipGetLastError() != hipSuccess) return FQL_ERR_LAUNCH;
+    if (const int rc = launch(pre, dim3(rblocks + zblocks), dim3(256), 0, st, gy, w.delta, w.rowsum, w.limbs, T, N, Np / FQL_KB, MBT,
+                              rblocks, gx, dtype_bytes(OUT), K, tpe, offs, E, scales, zps))
+        return rc;
 
     const int m_slots = (tpe == nullptr) ? (T + BwdCfg::BM - 1) / BwdCfg::BM : (T + BwdCfg::BM - 1) / BwdCfg::BM + E;
     const int n_tiles = (K + BwdCfg::BN - 1) / BwdCfg::BN;
     const long long tiles = (long long)m_slots * n_tiles;
-    const int grid = (int)(tiles < compute_units() ? tiles : compute_units());
+    const int cus = device_compute_units();                  // (the real count: fql_tune_set_compute_units caps the forward only)
+    const int grid = (int)(tiles < cus ? tiles : cus);
     const bool vw = (K % 32 == 0) && aligned16(packed);
     auto gemm = vw ? gemm_bwd_kernel<L, true, OUT> : gemm_bwd_kernel<L, false, OUT>;
     hipLaunchKernelGGL(gemm, dim3(grid), dim3(BwdCfg::THREADS), 0, st, w.limbs, w.delta, packed, zps, gx, tpe, offs, E, T,
                        K, N, Np, MBT, m_slots, n_tiles);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 // Shape limits shared by the workspace query and the entry points: i32 exactness (N), 31-bit buffer offsets (limbs, weights),
@@ -108,7 +82,7 @@ inline bool bwd_shape_ok(int L, int E, int T, int K, int N)
 
 size_t bwd_workspace_bytes(int E, int T, int K, int N, int precision)
 {
-    const int L = bwd_limbs(precision);
+    const int L = limbs_of(precision);
     if (L < 0 || E <= 0 || T <= 0 || K <= 0 || N <= 0 || (K & 1) || !bwd_shape_ok(L, E, T, K, N)) return 0;
     return bwd_carve(nullptr, L, T, E, padded(N)).bytes;
 }
@@ -140,12 +114,12 @@ int bwd_entry(const void *grad_out, int in_dtype, const uint8_t *packed, const f
               const int32_t *tpe, const int32_t *offs, void *grad_in, int out_dtype, int E, int T, int K, int N,
               int precision, void *ws, size_t ws_bytes, void *stream, bool grouped)
 {
-    const int L = bwd_limbs(precision);
+    const int L = limbs_of(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
     if (E < 0 || T < 0 || K < 0 || N < 0) return FQL_ERR_BAD_SHAPE;
     if (K & 1) return FQL_ERR_ODD_K;
     if (N > FQL_BWD_MAX_N || E > 65535) return FQL_ERR_BAD_SHAPE;
-    if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (T == 0 || K == 0) return FQL_OK;
     if (!grad_in) return FQL_ERR_NULL_POINTER;
     if (N > 0 && E > 0 && (!grad_out || !packed || !scales || !zps || (grouped && (!tpe || !offs))))
@@ -157,13 +131,11 @@ int bwd_entry(const void *grad_out, int in_dtype, const uint8_t *packed, const f
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (N == 0 || E == 0)                                     // empty contraction / no expert: the gradient is zero
-        return hipMemsetAsync(grad_in, 0, (size_t)T * K * elem_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+        return hipMemsetAsync(grad_in, 0, (size_t)T * K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
     const BwdWorkspace w = bwd_carve(ws, L, T, E, padded(N));
-    switch (L) {
-    case 1: return launch_bwd_types<1>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
-    case 2: return launch_bwd_types<2>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
-    default: return launch_bwd_types<3>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
-    }
+    return with_limbs(L, [&](auto l) {
+        return launch_bwd_types<decltype(l)::value>(in_dtype, out_dtype, grad_out, packed, scales, zps, grad_in, tpe, offs, E, T, K, N, w, st);
+    });
 }
 
 }  // namespace

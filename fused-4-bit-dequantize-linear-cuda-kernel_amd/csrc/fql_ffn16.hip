@@ -98,7 +98,7 @@ FQL_API int fql_lora_gated_shrink(const void *gate_up, int dtype, const float *w
 {
     int rc = shape_check(E, T, C, r, w_layout, true);
     if (rc != FQL_OK) return rc;
-    if (!dtype_ok(dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(dtype)) return FQL_ERR_DTYPE;
     if (dtype == FQL_DTYPE_F32)
         return fql_lora_gated_shrink_f32(static_cast<const float *>(gate_up), w, w_layout, tokens_per_expert,
                                          input_offsets, out, E, T, C, r, scale, stream);
@@ -118,7 +118,7 @@ FQL_API int fql_lora_gated_grad(const void *gate_up, int dtype, const float *v, 
 {
     int rc = shape_check(E, T, C, r, d_layout, true);
     if (rc != FQL_OK) return rc;
-    if (!dtype_ok(dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(dtype)) return FQL_ERR_DTYPE;
     if (dtype == FQL_DTYPE_F32)
         return fql_lora_gated_grad_f32(static_cast<const float *>(gate_up), v, tokens_per_expert, input_offsets, d,
                                        d_layout, E, T, C, r, scale, stream);
@@ -136,7 +136,7 @@ FQL_API int fql_swiglu_bwd(const void *gate_up, int dtype, const void *dh, int d
                            int T, int F, void *stream)
 {
     if (T < 0 || F < 0 || 2LL * T * F >= ((long long)1 << 31)) return FQL_ERR_BAD_SHAPE;
-    if (!dtype_ok(dtype) || !dtype_ok(dh_dtype) || !dtype_ok(out_dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(dtype) || !valid_dtype(dh_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (dtype == FQL_DTYPE_F32 && dh_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32)
         return fql_swiglu_bwd_f32(static_cast<const float *>(gate_up), static_cast<const float *>(dh),
                                   static_cast<float *>(dgate_up), T, F, stream);

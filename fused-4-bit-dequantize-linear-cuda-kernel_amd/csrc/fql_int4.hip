@@ -5,6 +5,7 @@
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
+#include "fql_host.h"
 #include "fql_act_quant.h"
 #include "fql_act_f8.h"
 #include "fql_gemm_i8.h"
@@ -22,6 +23,7 @@
 #include <random>
 
 namespace {
+using namespace fql_host;
 
 // Batches up to this many rows take the float32 GEMV kernel, larger ones the MFMA path (measured on MI355X, 4096 -> 11008,
 // product call in a hipGraph: GEMV 9.3 / 12.1 / 19.7 us at B = 1 / 2 / 3, MFMA path 16.4 / 16.5 / 16.1 us at
@@ -34,32 +36,8 @@ int g_group_mfma = 1;                  // per-group scales: the float32 matrix-c
 int g_use_w4 = 1;                      // 3 limbs, > 64 rows per group: the one-wave-per-SIMD kernel (fql_gemm_w4.h) instead of the 8-wave 128 x 192 one (A/B hook below)
 int g_act_single_rows = 512;          // pre-pass: one row per workgroup up to this many padded rows (tuning hook below)
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-inline int padded_k(int K) { return (K + FQL_KB - 1) / FQL_KB * FQL_KB; }
-// 32-row blocks of the limb workspace: every expert starts on a block boundary (<= 31 pad rows each) and a
-// tile may run up to 128 rows past the last expert.
-inline int row_blocks(int T, int E) { return (T + FQL_MB * E + 128 + FQL_MB - 1) / FQL_MB; }
-
-inline int limbs_of(int precision)
-{
-    if (precision == FQL_PRECISION_DEFAULT) return 3;
-    if (precision == FQL_PRECISION_INT8 || precision == FQL_PRECISION_FAST || precision == FQL_PRECISION_EXACT)
-        return precision;
-    if (precision == FQL_PRECISION_FP8) return 1;            // one byte plane of e4m3 values
-    return -1;
-}
 inline bool is_f8(int precision) { return precision == FQL_PRECISION_FP8; }
 
-// Per-device caches (a process may drive several GPUs): indexed by the current device, idempotent -- a race only repeats
-// the same query / attribute call.
-constexpr int FQL_MAX_DEVICES = 64;
-inline int current_device()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-    return dev < FQL_MAX_DEVICES ? dev : FQL_MAX_DEVICES - 1;
-}
 struct PerDeviceFlag {
     bool set[FQL_MAX_DEVICES] = {};
 };
@@ -74,20 +52,7 @@ inline bool ensure_lds_attr(PerDeviceFlag &flag, const void *kern, int bytes)
     return true;
 }
 int g_cu_cap = 0;              // tuning hook (tests): pretend the device has this many compute units (multiple of 8; 0 = real count)
-inline int compute_units()
-{
-    static int cached[FQL_MAX_DEVICES] = {};
-    if (g_cu_cap > 0) return g_cu_cap;
-    const int dev = current_device();
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;                                         // MI355X
-        n -= n % 8;                                          // keep vb % 8 == blockIdx % 8 (XCD grouping)
-        cached[dev] = n > 0 ? n : 8;
-    }
-    return cached[dev];
-}
+inline int compute_units() { return g_cu_cap > 0 ? g_cu_cap : device_compute_units(); }
 
 inline int compute_units_hint() { const int n = compute_units(); return n < 256 ? 256 : n; }
 
@@ -96,12 +61,7 @@ struct Workspace {            // (every member has a default: a hand-filled Work
     float *delta = nullptr;
     int32_t *rowsum = nullptr;
     float *scratch = nullptr;          // workgroup-private float32 partials of the residual pass (heavy-tailed rows), or nullptr
-    const float *bias = nullptr;       // optional per-column bias [N] added to the final outputs (not workspace memory: rides along)
-    const float *row_weight = nullptr; // optional per-row output weight [T] (caller's array: the pre-pass copies it into the plane behind delta)
     unsigned long long *flags = nullptr;   // one-launch form (fql_gemm_w4.h, FUSED): one word per group of 4 grouped rows
-    const void *fuse_x = nullptr;      // one-launch form requested: the float32 rows the GEMM kernel quantises itself (ride along, like bias)
-    const int32_t *fuse_gather = nullptr;
-    int fuse_n_src = 0;
     size_t bytes = 0;
 };
 
@@ -111,7 +71,7 @@ inline bool has_residual(int L, bool f8) { return L >= 2 && !f8; }
 // (8 waves x <= 4 fragments x 4 KiB per workgroup and CU; the small skinny-tile workgroups share a CU's budget).
 inline size_t res_scratch_bytes() { return (size_t)compute_units_hint() * 8 * 4 * 4096; }
 
-inline size_t limb_bytes(int L, int T, int E, int Kp) { return (size_t)L * (Kp / FQL_KB) * row_blocks(T, E) * 8192; }
+inline size_t limb_bytes(int L, int T, int E, int Kp) { return (size_t)L * (Kp / FQL_KB) * (size_t)row_blocks(T, E) * 8192; }
 
 inline Workspace carve(void *base, int L, int T, int E, int Kp, bool res)
 {
@@ -127,35 +87,57 @@ inline Workspace carve(void *base, int L, int T, int E, int Kp, bool res)
     w.rowsum = reinterpret_cast<int32_t *>(p + lb + db);
     w.flags = fb ? reinterpret_cast<unsigned long long *>(p + lb + db + rb) : nullptr;
     w.scratch = res ? reinterpret_cast<float *>(p + lb + db + rb + fb) : nullptr;
-    w.bias = nullptr;
-    w.row_weight = nullptr;
     w.bytes = lb + db + rb + fb + (res ? res_scratch_bytes() : 0);
     return w;
 }
 
+// One op on the matrix-core path: what the pre-pass reads, what the GEMM reads and writes, and the workspace between them.
+// An entry point fills it once; every launcher takes it by const reference.
+struct Call {
+    const void *x = nullptr;               // activation rows [n_src or T][K] ([T][2K] gate|up when gated), or the GEMM alone (NULL)
+    int in_dtype = FQL_DTYPE_F32;
+    const int32_t *gather = nullptr;       // optional: grouped row t is row gather[t] of x
+    int n_src = 0;
+    bool gated = false;                    // the pre-pass applies silu(gate) * up
+    bool f8 = false;                       // the pre-pass writes one e4m3 plane, the GEMM is the fp8 form
+    const uint8_t *packed = nullptr;
+    const float *scales = nullptr;
+    const float *zps = nullptr;
+    void *out = nullptr;
+    int out_dtype = FQL_DTYPE_F32;
+    const float *bias = nullptr;           // optional per-column bias [N] added to the final outputs
+    const float *row_weight = nullptr;     // optional per-row output weight [T] (caller's array: the pre-pass copies it into the plane behind delta)
+    const int32_t *tpe = nullptr;          // expert table (both or neither: one group of all rows)
+    const int32_t *offs = nullptr;
+    int E = 1;
+    int T = 0, K = 0, Kp = 0, MBT = 0, N = 0;
+    hipStream_t st = nullptr;
+    Workspace ws;
+
+    // (after the entry point's addressability checks: MBT is narrowed here)
+    void set_shape(int E_, int T_, int K_, int N_) { E = E_; T = T_; K = K_; N = N_; Kp = padded(K_); MBT = (int)row_blocks(T_, E_); }
+    bool grouped() const { return tpe != nullptr; }
+    int out_kind() const { return out_dtype | (row_weight != nullptr ? 8 : 0); }   // the GEMM kernels' element type + "scale rows" bit
+};
+
 // ---- MFMA tile configurations (see fql_gemm_i8.h): 8 waves as WM x WN, NF 32-column fragments per wave.
-struct TileShape { int bm, bn; };
 // X(id, WM, WN, NF, A-ring depth in k-steps, weight stages in flight)
+// (ids 4, 10, 14, 15, 16 and 17 were tuning experiments that lost and were built for no limb count: 64 x 256, a 64 x 384 variant
+//  and the 4-wave 128 x 96 / 64 x 192 / 128 x 64 tiles, 133.6 / 143.5 against 130.4 us in DESIGN.md 4.2.  The ids stay reserved.)
 #define FQL_CFG_LIST(X)                                                                                            \
     X(0, 4, 2, 3, 2, 1)        /* 128 x 192 (3 limbs: 2-step A ring is what the register budget allows) */ \
     X(1, 4, 2, 2, 4, 1)        /* 128 x 128 */ \
     X(2, 4, 2, 4, 2, 1)        /* 128 x 256 (2-limb register budget) */ \
     X(3, 4, 2, 3, 4, 1)        /* 128 x 192, 4-step A ring (2-limb register budget) */ \
-    X(4, 2, 4, 2, 4, 1)        /*  64 x 256 */ \
-    X(5, 1, 8, 1, 4, 1)        /*  32 x 256 */ \
-    X(6, 4, 1, 2, 8, 4)        /* 128 x  64, 4 waves: skinny tiles for few rows (HBM-bound: many small */ \
+    X(5, 1, 8, 1, 4, 1)        /*  32 x 256 (fp8 form only) */ \
+    X(6, 4, 1, 2, 8, 4)        /* 128 x  64, 4 waves (fp8 form only): skinny tiles for few rows (HBM-bound: many small */ \
     X(7, 2, 2, 1, 8, 4)        /*  64 x  64, 4 waves   workgroups per CU, 4 weight stages in flight, deep */ \
     X(8, 1, 2, 1, 8, 4)        /*  32 x  64, 2 waves   A ring to cover L2 latency) */ \
     X(9, 2, 4, 3, 2, 1)        /*  64 x 384: 64-row groups with the A-fragment reuse of the 128 x 192 tile */ \
-    X(10, 2, 4, 3, 4, 2)       /*  64 x 384, 2 weight stages in flight (1- and 2-limb register budgets) */ \
     X(11, 2, 4, 3, 8, 2)       /*  64 x 384, full-stage A ring (every load one stage ahead), 2 weight stages */ \
     X(12, 4, 2, 3, 8, 2)       /* 128 x 192, full-stage A ring, 2 weight stages */ \
-    X(13, 4, 1, 2, 4, 8)       /* 128 x  64, 4 waves, 8 weight stages in flight (few tall tiles: HBM-latency bound) */ \
-    X(14, 4, 1, 3, 2, 1)       /* 128 x  96, 4 waves: TWO independent workgroups per CU, one wave per SIMD each, so one */ \
-    X(15, 2, 2, 3, 2, 1)       /*  64 x 192, 4 waves   workgroup's prologue / epilogue / barrier waits sit under the other's MFMAs */ \
-    X(16, 4, 1, 3, 2, 2)       /* 128 x  96, 4 waves, 2 weight stages in flight */ \
-    X(17, 4, 1, 2, 4, 2)       /* 128 x  64, 4 waves, 4-step A ring */
-constexpr int FQL_NUM_CFG = 18;
+    X(13, 4, 1, 2, 4, 8)       /* 128 x  64, 4 waves, 8 weight stages in flight (few tall tiles: HBM-latency bound) */
+constexpr int FQL_NUM_CFG = 18;                              // one past the largest id (fql_tune_num_configs: callers walk range(n))
 // Short row groups (fql_gemm_rows32.h): 32-row tiles, K split KG ways inside the workgroup.  ids 100 + i.
 // R(i, NF, KG, A-ring depth in k-steps, weight stages in flight per wave, waves per SIMD)
 #define FQL_ROWS32_LIST(R)                                                                                         \
@@ -197,22 +179,25 @@ constexpr int FQL_NUM_ROWS16_W4 = 4;
     W(1, 3, 6, 4)              /* 3 limbs, 4-step ring */
 constexpr int FQL_NUM_W4 = 2;
 // Which wide configurations are BUILT for which limb count: the ones choose_cfg() can return for it, plus the previous
-// headline configuration (0 at 3 limbs: the bit-identity baseline of the tests and A/B tools).  The rest of the list --
-// register budgets of another limb count (up to 1273 spilled registers), tuning experiments that lost -- is not instantiated.
+// headline configuration (0 at 3 limbs: the bit-identity baseline of the tests and A/B tools).  The register budgets of
+// another limb count (up to 1273 spilled registers) are not instantiated.
 constexpr bool wide_cfg_built(int L, int id)
 {
     return L == 3 ? (id == 0 || id == 1 || id == 7 || id == 8 || id == 9 || id == 13)
          : L == 2 ? (id == 1 || id == 2 || id == 3 || id == 7 || id == 8 || id == 11 || id == 13)
                   : (id == 1 || id == 2 || id == 7 || id == 8 || id == 11 || id == 12 || id == 13);
 }
+// ... and for the fp8-activation form (gemm_i8_kernel<1, ..., F8 = true>): the ones choose_cfg_f8() can return, plus 128 x 128
+constexpr bool wide_cfg_built_f8(int id) { return id == 1 || id == 5 || id == 6 || id == 7 || id == 8 || id == 11 || id == 12; }
 inline bool valid_cfg(int cfg, int L) { return (cfg >= 300 && cfg < 300 + FQL_NUM_W4 && L == 3) || (cfg >= 0 && cfg < FQL_NUM_CFG && wide_cfg_built(L, cfg)) ||
            (cfg >= 100 && cfg < 100 + FQL_NUM_ROWS32) || (cfg >= 200 && cfg < 200 + FQL_NUM_ROWS16) || (cfg >= 220 && cfg < 220 + FQL_NUM_ROWS16_W4);
 }
+inline bool valid_cfg_f8(int cfg) { return wide_cfg_built_f8(cfg); }
 
 // The MFMA path addresses its operands through 32-bit buffer offsets.
 inline bool mfma_addressable(int L, int T, int E, int K, int N, bool f8 = false)
 {
-    const size_t a = (has_residual(L, f8) ? 2 : 1) * limb_bytes(L, T, E, padded_k(K));   // (with the residual limb set where there is one)
+    const size_t a = (has_residual(L, f8) ? 2 : 1) * limb_bytes(L, T, E, padded(K));   // (with the residual limb set where there is one)
     const size_t b = ((size_t)N + 256) * (size_t)(K >> 1);
     return a < ((size_t)1 << 31) && b < ((size_t)1 << 31);
 }
@@ -222,51 +207,56 @@ inline bool mfma_eligible(int L, int T, int E, int K, int N, const uint8_t *pack
     return (K % 32 == 0) && aligned16(packed) && mfma_addressable(L, T, E, K, N);
 }
 
-inline int dtype_bytes(int dt) { return dt == FQL_DTYPE_F32 ? 4 : 2; }
-
-template <int L>
-int launch_act_quant(const void *x, int in_dtype, const int32_t *gather, int n_src, const Workspace &w, int T, int K,
-                     int Kp, int MBT, void *out, int out_dtype, int N, const int32_t *tpe, const int32_t *offs, int E,
-                     hipStream_t st, bool gated = false, bool f8out = false)
+// The expert table comes as a pair or not at all, and without one there is one group of all rows.
+inline int table_check(const int32_t *tpe, const int32_t *offs, int E)
 {
+    if ((tpe == nullptr) != (offs == nullptr)) return FQL_ERR_NULL_POINTER;
+    if (tpe == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    return FQL_OK;
+}
+
+// The pre-pass: c.x -> limbs, delta, rowsum of c.ws (and, with a table, zeroes the rows of c.out no expert covers).
+template <int L>
+int launch_act_quant(const Call &c)
+{
+    const int T = c.T, K = c.K;
+    void *zero_out = c.grouped() ? c.out : nullptr;
     // ACT_ROWS-row workgroups over the grouped rows (each finds its rows' padded positions itself), plus (MoE entry
     // point) the workgroups that zero the rows of `out` no expert covers
-    const int mblocks = (tpe == nullptr) ? (T + FQL_MB - 1) / FQL_MB : (T + FQL_MB * E) / FQL_MB;   // (upper bound of the padded row blocks)
-    const bool vec = (K % 16 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0);
+    const int mblocks = !c.grouped() ? (T + FQL_MB - 1) / FQL_MB : (T + FQL_MB * c.E) / FQL_MB;   // (upper bound of the padded row blocks)
+    const bool vec = (K % 16 == 0) && aligned16(c.x);
     // few rows in all (at most two single-row workgroups per CU; measured: 16 rows 6.3 -> 4.6 us, 1280 padded rows 12.5 -> 16.5 us): one row per workgroup -- the pre-pass is a latency
     // chain there and a row spread over 256 threads shortens every link of it (fql_act_quant.h)
     const bool single = vec && mblocks * FQL_MB <= g_act_single_rows;
     const int rblocks = single ? T : (T + ACT_ROWS - 1) / ACT_ROWS;
-    const int zblocks = (tpe != nullptr && out != nullptr) ? (T + 255) / 256 : 0;
-    if (gated && !f8out && in_dtype != FQL_DTYPE_F32) {     // 16-bit gate|up rows: the instantiations of fql_ffn16.hip
-        if (gather != nullptr) return FQL_ERR_DTYPE;
-        FqlActGatedArgs a{x, w.delta, w.rowsum, w.limbs, T, K, Kp / FQL_KB, MBT, rblocks, zblocks, out, dtype_bytes(out_dtype), N,
-                          tpe, offs, E, w.row_weight, st};
-        return fql_act_gated16_launch(L, single ? 0 : (vec ? 1 : 2), in_dtype, a) == 0 ? FQL_OK : FQL_ERR_LAUNCH;
+    const int zblocks = zero_out != nullptr ? (T + 255) / 256 : 0;
+    if (c.gated && !c.f8 && c.in_dtype != FQL_DTYPE_F32) {     // 16-bit gate|up rows: the instantiations of fql_ffn16.hip
+        if (c.gather != nullptr) return FQL_ERR_DTYPE;
+        FqlActGatedArgs a{c.x, c.ws.delta, c.ws.rowsum, c.ws.limbs, T, K, c.Kp / FQL_KB, c.MBT, rblocks, zblocks, zero_out,
+                          dtype_bytes(c.out_dtype), c.N, c.tpe, c.offs, c.E, c.row_weight, c.st};
+        return fql_act_gated16_launch(L, single ? 0 : (vec ? 1 : 2), c.in_dtype, a) == 0 ? FQL_OK : FQL_ERR_LAUNCH;
     }
     void (*kern)(const void *, const int32_t *, int, float *, int32_t *, int8_t *, int, int, int, int, int, void *, int,
                  int, const int32_t *, const int32_t *, int, const float *);
 #define FQL_ACT_PICK(l, in, gate, f8) \
     (single ? act_fused_kernel<l, true, in, gate, f8, 1> : (vec ? act_fused_kernel<l, true, in, gate, f8> : act_fused_kernel<l, false, in, gate, f8>))
-    if (f8out) {
+    if (c.f8) {
         if constexpr (L == 1) {
-            switch (in_dtype) {
+            switch (c.in_dtype) {
             case FQL_DTYPE_F16: kern = FQL_ACT_PICK(1, 1, false, true); break;
             case FQL_DTYPE_BF16: kern = FQL_ACT_PICK(1, 2, false, true); break;
             default: kern = FQL_ACT_PICK(1, 0, false, true); break;
             }
         } else return FQL_ERR_BAD_PRECISION;
-    } else if (gated) kern = FQL_ACT_PICK(L, 0, true, false);
-    else switch (in_dtype) {
+    } else if (c.gated) kern = FQL_ACT_PICK(L, 0, true, false);
+    else switch (c.in_dtype) {
     case FQL_DTYPE_F16: kern = FQL_ACT_PICK(L, 1, false, false); break;
     case FQL_DTYPE_BF16: kern = FQL_ACT_PICK(L, 2, false, false); break;
     default: kern = FQL_ACT_PICK(L, 0, false, false); break;
     }
 #undef FQL_ACT_PICK
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(rblocks + zblocks), dim3(256), 0, st, x, gather, n_src, w.delta, w.rowsum, w.limbs,
-                       T, K, Kp / FQL_KB, MBT, rblocks, out, dtype_bytes(out_dtype), N, tpe, offs, E, w.row_weight);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launch(kern, dim3(rblocks + zblocks), dim3(256), 0, c.st, c.x, c.gather, c.n_src, c.ws.delta, c.ws.rowsum, c.ws.limbs,
+                  T, K, c.Kp / FQL_KB, c.MBT, rblocks, zero_out, dtype_bytes(c.out_dtype), c.N, c.tpe, c.offs, c.E, c.row_weight);
 }
 
 // Column tiles per row block of the wide kernel.  The fewest that cover N (every tile at most `fpt` fragments of 32
@@ -321,76 +311,78 @@ inline int balanced_n_tiles(int N, int fpt, long long m_tiles, int wgs, int frag
     return best;
 }
 
+// ---- The persistent grid of a tile kernel: BM x BN tiles walked by at most `wg_per_cu` workgroups per compute unit.
+// Balance: the kernel can also split N into `n_alt` uneven column tiles (balanced_n_tiles) and picks between the two
+// tilings from the real row-block count; frag = 0 for a kernel without that form.
+struct Balance { int frag, overhead, min_base; };            // fragment width in columns, per-tile overhead, fewest fragments per tile (< 0: one less than a full tile)
+constexpr Balance NO_BALANCE{0, 0, 0};
+constexpr Balance WIDE_BALANCE{32, 1, -1};                   // fql_gemm_i8.h (NF >= 2, integer limbs) and fql_gemm_w4.h
+constexpr Balance ROWS16_BALANCE{16, 2, 1};                  // fql_gemm_rows16.h
+struct GridPlan {
+    int n_tiles;               // the fewest column tiles that cover N ...
+    int n_alt;                 // ... and the balanced alternative (0: none)
+    int m_slots;               // upper bound of the row blocks (the real count is on the device)
+    long long worst;           // worst-case tile count
+    unsigned blocks;           // workgroups launched
+};
+inline int plan_grid(int BM, int BN, int wg_per_cu, Balance bal, const Call &c, GridPlan &p)
+{
+    const int wgs = compute_units() * wg_per_cu;
+    p.n_tiles = (c.N + BN - 1) / BN;
+    p.m_slots = !c.grouped() ? (c.T + BM - 1) / BM : c.T / BM + c.E;
+    p.n_alt = 0;
+    if (bal.frag != 0) {
+        const int groups = !c.grouped() ? 1 : c.E;
+        const long long m_even = (long long)groups * (((c.T + groups - 1) / groups + BM - 1) / BM);   // row blocks if evenly routed
+        p.n_alt = balanced_n_tiles(c.N, BN / bal.frag, m_even, wgs, bal.frag, bal.overhead, bal.min_base);
+        if (p.n_alt == p.n_tiles) p.n_alt = 0;
+    }
+    p.worst = (long long)(p.n_alt > p.n_tiles ? p.n_alt : p.n_tiles) * p.m_slots;
+    if (p.worst <= 0 || p.worst > 0x7fffffffLL) return FQL_ERR_BAD_SHAPE;
+    p.blocks = (unsigned)(p.worst > wgs ? wgs : p.worst);
+    return FQL_OK;
+}
+
+// A new tile family plugs in here: its launcher names its kernel (the LDS flag is one per instantiation: `static` in
+// the launcher template), asks plan_grid() for the grid and passes the plan on; launch_gemm() gets its id range.
 template <int L, int WM, int WN, int NF, int DEPTH, int BDEPTH, bool F8 = false>
-int launch_gemm_cfg(const Workspace &w, const uint8_t *packed, const float *scales, const float *zps,
-                    void *out, int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp,
-                    int MBT, int N, hipStream_t st)
+int launch_gemm_cfg(const Call &c)
 {
     using C = GemmCfg<L, WM, WN, NF, DEPTH, BDEPTH>;
     auto kern = gemm_i8_kernel<L, WM, WN, NF, DEPTH, BDEPTH, F8>;
     static PerDeviceFlag attr;
     if (!ensure_lds_attr(attr, reinterpret_cast<const void *>(kern), C::LDS_BYTES)) return FQL_ERR_LAUNCH;
-    (void)hipGetLastError();                                 // a stale error of another library must not read as ours
-    // persistent: the 8-wave workgroups fill a CU alone; the small skinny-tile workgroups share it 4 / 8 ways
-    const int cus = compute_units() * (C::NW >= 8 ? 1 : (C::NW == 4 ? 2 : 4));      // 2 waves per SIMD either way
-    const int m_slots = (tpe == nullptr) ? (T + C::BM - 1) / C::BM : T / C::BM + E;
-    const int groups = (tpe == nullptr) ? 1 : E;
-    const long long m_even = (long long)groups * (((T + groups - 1) / groups + C::BM - 1) / C::BM);   // row blocks if evenly routed
-    const int n_tiles = (N + C::BN - 1) / C::BN;            // the fewest column tiles that cover N ...
-    int n_alt = (NF >= 2 && !F8) ? balanced_n_tiles(N, C::BN / 32, m_even, cus) : n_tiles;   // ... and the balanced alternative;
-    if (n_alt == n_tiles) n_alt = 0;                         // the kernel picks between them from the real row-block count
-    long long blocks = (long long)(n_alt > n_tiles ? n_alt : n_tiles) * m_slots;   // worst-case tile count (real count is on the device)
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return FQL_ERR_BAD_SHAPE;
-    if (blocks > cus) blocks = cus;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::THREADS), C::LDS_BYTES, st, w.limbs, w.delta, w.rowsum,
-                       packed, scales, zps, out, out_dtype | (w.row_weight != nullptr ? 8 : 0), tpe, offs, E, T, K, Kp, MBT, N, n_tiles, m_slots, w.scratch, w.bias, n_alt);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    // persistent: the 8-wave workgroups fill a CU alone; the small skinny-tile workgroups share it 4 / 8 ways (2 waves per SIMD either way)
+    GridPlan p;
+    if (const int rc = plan_grid(C::BM, C::BN, C::NW >= 8 ? 1 : (C::NW == 4 ? 2 : 4), (NF >= 2 && !F8) ? WIDE_BALANCE : NO_BALANCE, c, p)) return rc;
+    return launch(kern, dim3(p.blocks), dim3(C::THREADS), C::LDS_BYTES, c.st, c.ws.limbs, c.ws.delta, c.ws.rowsum, c.packed, c.scales,
+                  c.zps, c.out, c.out_kind(), c.tpe, c.offs, c.E, c.T, c.K, c.Kp, c.MBT, c.N, p.n_tiles, p.m_slots, c.ws.scratch, c.bias, p.n_alt);
 }
 
 template <int L, int NF, int KG, int DEPTH, int BDEPTH, int OCC>
-int launch_rows32_cfg(const Workspace &w, const uint8_t *packed, const float *scales, const float *zps, void *out,
-                      int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp, int MBT,
-                      int N, hipStream_t st)
+int launch_rows32_cfg(const Call &c)
 {
     using C = Rows32Cfg<L, NF, KG, DEPTH, BDEPTH, OCC>;
     auto kern = gemm_i8_rows32_kernel<L, NF, KG, DEPTH, BDEPTH, OCC>;
     static PerDeviceFlag attr;
     if (!ensure_lds_attr(attr, reinterpret_cast<const void *>(kern), C::LDS_BYTES)) return FQL_ERR_LAUNCH;
-    (void)hipGetLastError();                                 // a stale error of another library must not read as ours
-    const int n_tiles = (N + C::BN - 1) / C::BN;
-    const int m_slots = (tpe == nullptr) ? (T + C::BM - 1) / C::BM : T / C::BM + E;
-    long long blocks = (long long)n_tiles * m_slots;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return FQL_ERR_BAD_SHAPE;
-    const int cus = compute_units() * C::WG_PER_CU;          // persistent: WG_PER_CU 8-wave workgroups per CU
-    if (blocks > cus) blocks = cus;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::THREADS), C::LDS_BYTES, st, w.limbs, w.delta, w.rowsum,
-                       packed, scales, zps, out, out_dtype | (w.row_weight != nullptr ? 8 : 0), tpe, offs, E, T, K, Kp, MBT, N, n_tiles, m_slots, w.scratch, w.bias);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    GridPlan p;                                              // persistent: WG_PER_CU 8-wave workgroups per CU
+    if (const int rc = plan_grid(C::BM, C::BN, C::WG_PER_CU, NO_BALANCE, c, p)) return rc;
+    return launch(kern, dim3(p.blocks), dim3(C::THREADS), C::LDS_BYTES, c.st, c.ws.limbs, c.ws.delta, c.ws.rowsum, c.packed, c.scales,
+                  c.zps, c.out, c.out_kind(), c.tpe, c.offs, c.E, c.T, c.K, c.Kp, c.MBT, c.N, p.n_tiles, p.m_slots, c.ws.scratch, c.bias);
 }
 
 template <int L, int NF, int KG, int BDEPTH, int NWAVES = 8>
-int launch_rows16_cfg(const Workspace &w, const uint8_t *packed, const float *scales, const float *zps, void *out,
-                      int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp, int MBT,
-                      int N, hipStream_t st)
+int launch_rows16_cfg(const Call &c)
 {
     using C = Rows16Cfg<L, NF, KG, BDEPTH, NWAVES>;
     auto kern = gemm_i8_rows16_kernel<L, NF, KG, BDEPTH, NWAVES>;
     static PerDeviceFlag attr;
     if (!ensure_lds_attr(attr, reinterpret_cast<const void *>(kern), C::LDS_BYTES)) return FQL_ERR_LAUNCH;
-    (void)hipGetLastError();                                 // a stale error of another library must not read as ours
-    const int n_tiles = (N + C::BN - 1) / C::BN;
-    const int m_slots = (tpe == nullptr) ? (T + C::BM - 1) / C::BM : T / C::BM + E;
-    const int cus = compute_units() * (8 / C::NW);          // persistent: one 8-wave or two 4-wave workgroups per CU
-    const int groups = (tpe == nullptr) ? 1 : E;
-    const long long m_even = (long long)groups * (((T + groups - 1) / groups + C::BM - 1) / C::BM);   // row blocks if evenly routed
-    int n_alt = balanced_n_tiles(N, C::BN / 16, m_even, cus, 16, 2, 1);     // uneven column tiles (fql_gemm_rows16.h)
-    if (n_alt == n_tiles) n_alt = 0;
-    long long blocks = (long long)(n_alt > n_tiles ? n_alt : n_tiles) * m_slots;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return FQL_ERR_BAD_SHAPE;
-    if (blocks > cus) blocks = cus;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::THREADS), C::LDS_BYTES, st, w.limbs, w.delta, w.rowsum,
-                       packed, scales, zps, out, out_dtype | (w.row_weight != nullptr ? 8 : 0), tpe, offs, E, T, K, Kp, MBT, N, n_tiles, m_slots, w.scratch, w.bias, n_alt);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    GridPlan p;                                              // persistent: one 8-wave or two 4-wave workgroups per CU
+    if (const int rc = plan_grid(C::BM, C::BN, 8 / C::NW, ROWS16_BALANCE, c, p)) return rc;
+    return launch(kern, dim3(p.blocks), dim3(C::THREADS), C::LDS_BYTES, c.st, c.ws.limbs, c.ws.delta, c.ws.rowsum, c.packed, c.scales,
+                  c.zps, c.out, c.out_kind(), c.tpe, c.offs, c.E, c.T, c.K, c.Kp, c.MBT, c.N, p.n_tiles, p.m_slots, c.ws.scratch, c.bias, p.n_alt);
 }
 
 // One launch for pre-pass + GEMM (fql_gemm_w4.h, FUSED): tuning switch, the polls a workgroup spends on another one's rows
@@ -404,120 +396,75 @@ inline unsigned long long next_fused_token()
     static std::atomic<unsigned> counter{1};
     return salt ^ (unsigned long long)counter.fetch_add(1, std::memory_order_relaxed);
 }
+// The one-wave-per-SIMD kernel: same tiles and column split as the wide kernel's 128 x 192 configuration, one workgroup per CU.
+inline int plan_w4(int L, int nf, const Call &c, GridPlan &p) { return plan_grid(128, fql_w4_bn(L, nf), 1, WIDE_BALANCE, c, p); }
 // The one-launch form keeps its tile list in the 16-entry LDS table: every workgroup must get by with one table.
-inline bool w4_fusable(int nf, const int32_t *tpe, int E, int T, int N)
+inline bool w4_fusable(int L, int nf, const Call &c)
 {
-    const int BM = 128, BN = 32 * nf;
-    const int cus = compute_units();
-    const int m_slots = (tpe == nullptr) ? (T + BM - 1) / BM : T / BM + E;
-    const int groups = (tpe == nullptr) ? 1 : E;
-    const long long m_even = (long long)groups * (((T + groups - 1) / groups + BM - 1) / BM);
-    const int n_tiles = (N + BN - 1) / BN;
-    const int n_alt = balanced_n_tiles(N, BN / 32, m_even, cus);
-    long long worst = (long long)(n_alt > n_tiles ? n_alt : n_tiles) * m_slots;
-    if (worst <= 0) return false;
-    const long long blocks = worst > cus ? cus : worst;
-    return (worst + blocks - 1) / blocks <= 16;
+    GridPlan p;
+    return plan_w4(L, nf, c, p) == FQL_OK && (p.worst + p.blocks - 1) / p.blocks <= 16;
 }
 
-// The one-wave-per-SIMD kernel: same tiles and column split as the wide kernel's 128 x 192 configuration.
-int launch_w4_cfg(int L, int nf, int depth, const Workspace &w, const uint8_t *packed, const float *scales, const float *zps,
-                  void *out, int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp, int MBT,
-                  int N, hipStream_t st)
+// `fused`: the kernel quantises the rows of c.x itself, no pre-pass launch came before (w4_fusable() said it may)
+int launch_w4_cfg(int L, int nf, int depth, const Call &c, bool fused)
 {
-    if (Kp < 2 * FQL_KB) return FQL_ERR_BAD_SHAPE;           // its pipeline runs two weight stages ahead
-    const int BM = 128, BN = fql_w4_bn(L, nf);
-    const int cus = compute_units();
-    const int m_slots = (tpe == nullptr) ? (T + BM - 1) / BM : T / BM + E;
-    const int groups = (tpe == nullptr) ? 1 : E;
-    const long long m_even = (long long)groups * (((T + groups - 1) / groups + BM - 1) / BM);
-    const int n_tiles = (N + BN - 1) / BN;
-    int n_alt = balanced_n_tiles(N, BN / 32, m_even, cus);
-    if (n_alt == n_tiles) n_alt = 0;
-    long long blocks = (long long)(n_alt > n_tiles ? n_alt : n_tiles) * m_slots;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) return FQL_ERR_BAD_SHAPE;
-    if (blocks > cus) blocks = cus;
+    if (c.Kp < 2 * FQL_KB) return FQL_ERR_BAD_SHAPE;         // its pipeline runs two weight stages ahead
+    GridPlan p;
+    if (const int rc = plan_w4(L, nf, c, p)) return rc;
     FqlW4Args a;
-    a.limbs = w.limbs; a.delta = w.delta; a.rowsum = w.rowsum;
-    a.packed = packed; a.scales = scales; a.zps = zps;
-    a.out = out; a.out_kind = out_dtype | (w.row_weight != nullptr ? 8 : 0);
-    a.tpe = tpe; a.offs = offs;
-    a.E = E; a.T = T; a.K = K; a.Kp = Kp; a.MBT = MBT; a.N = N;
-    a.n_tiles = n_tiles; a.m_slots = m_slots; a.n_alt = n_alt;
-    a.scratch = w.scratch; a.bias = w.bias;
-    a.blocks = blocks; a.stream = st;
-    if (w.fuse_x != nullptr) {                               // one launch: the kernel quantises the rows itself (w4_fusable() said it may)
+    a.limbs = c.ws.limbs; a.delta = c.ws.delta; a.rowsum = c.ws.rowsum;
+    a.packed = c.packed; a.scales = c.scales; a.zps = c.zps;
+    a.out = c.out; a.out_kind = c.out_kind();
+    a.tpe = c.tpe; a.offs = c.offs;
+    a.E = c.E; a.T = c.T; a.K = c.K; a.Kp = c.Kp; a.MBT = c.MBT; a.N = c.N;
+    a.n_tiles = p.n_tiles; a.m_slots = p.m_slots; a.n_alt = p.n_alt;
+    a.scratch = c.ws.scratch; a.bias = c.bias;
+    a.blocks = p.blocks; a.stream = c.st;
+    if (fused) {
         a.fused = true;
-        a.fz = FqlW4Fused{w.fuse_x, w.fuse_gather, w.fuse_n_src, w.row_weight, w.flags, next_fused_token(), g_fused_spin};
+        a.fz = FqlW4Fused{c.x, c.gather, c.n_src, c.row_weight, c.ws.flags, next_fused_token(), g_fused_spin};
     }
     const int rc = fql_w4_launch(L, nf, depth, a);
     return rc == 0 ? FQL_OK : (rc == -2 ? FQL_ERR_BAD_SHAPE : FQL_ERR_LAUNCH);
 }
 
 template <int L>
-int launch_gemm(int cfg, const Workspace &w, const uint8_t *packed, const float *scales, const float *zps,
-                void *out, int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp, int MBT,
-                int N, hipStream_t st)
+int launch_gemm(int cfg, const Call &c, bool fused = false)
 {
     switch (cfg) {
 #define W(i, l, nf, d)                                                                                            \
-    case 300 + i:                                                                                                 \
-        if (L != l) return FQL_ERR_BAD_SHAPE;                                                                      \
-        return launch_w4_cfg(l, nf, d, w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
+    case 300 + i: return L == l ? launch_w4_cfg(l, nf, d, c, fused) : FQL_ERR_BAD_SHAPE;
         FQL_W4_LIST(W)
 #undef W
 #define X(id, wm, wn, nf, d, bp)                                                                                  \
     case id:                                                                                                      \
-        if constexpr (wide_cfg_built(L, id))                                                                      \
-            return launch_gemm_cfg<L, wm, wn, nf, d, bp>(w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, \
-                                                         Kp, MBT, N, st);                                         \
+        if constexpr (wide_cfg_built(L, id)) return launch_gemm_cfg<L, wm, wn, nf, d, bp>(c);                     \
         else return FQL_ERR_BAD_SHAPE;
         FQL_CFG_LIST(X)
 #undef X
-#define R(i, nf, kg, d, bd, occ)                                                                                   \
-    case 100 + i:                                                                                                 \
-        return launch_rows32_cfg<L, nf, kg, d, bd, occ>(w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, \
-                                                        Kp, MBT, N, st);
+#define R(i, nf, kg, d, bd, occ) case 100 + i: return launch_rows32_cfg<L, nf, kg, d, bd, occ>(c);
         FQL_ROWS32_LIST(R)
 #undef R
-#define S(i, nf, kg, bd)                                                                                           \
-    case 200 + i:                                                                                                 \
-        return launch_rows16_cfg<L, nf, kg, bd>(w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, \
-                                                st);
+#define S(i, nf, kg, bd) case 200 + i: return launch_rows16_cfg<L, nf, kg, bd>(c);
         FQL_ROWS16_LIST(S)
 #undef S
-#define S4(i, nf, kg, bd)                                                                                          \
-    case 220 + i:                                                                                                 \
-        return launch_rows16_cfg<L, nf, kg, bd, 4>(w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, \
-                                                   N, st);
+#define S4(i, nf, kg, bd) case 220 + i: return launch_rows16_cfg<L, nf, kg, bd, 4>(c);
         FQL_ROWS16_W4_LIST(S4)
 #undef S4
     default: return FQL_ERR_BAD_SHAPE;
     }
 }
 
-// fp8-activation form of the wide kernel (gemm_i8_kernel<1, ..., F8 = true>): the configurations it is built for.
-#define FQL_F8_CFG_LIST(Y)                                                                                         \
-    Y(1, 4, 2, 2, 4, 1)        /* 128 x 128 */ \
-    Y(5, 1, 8, 1, 4, 1)        /*  32 x 256 */ \
-    Y(6, 4, 1, 2, 8, 4)        /* 128 x  64, 4 waves */ \
-    Y(7, 2, 2, 1, 8, 4)        /*  64 x  64, 4 waves */ \
-    Y(8, 1, 2, 1, 8, 4)        /*  32 x  64, 2 waves */ \
-    Y(11, 2, 4, 3, 8, 2)       /*  64 x 384, full-stage activation ring, 2 weight stages */ \
-    Y(12, 4, 2, 3, 8, 2)       /* 128 x 192, full-stage activation ring, 2 weight stages */
-inline bool valid_cfg_f8(int cfg) { return cfg == 1 || cfg == 5 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 11 || cfg == 12; }
-
-int launch_gemm_f8(int cfg, const Workspace &w, const uint8_t *packed, const float *scales, const float *zps, void *out,
-                   int out_dtype, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int Kp, int MBT, int N,
-                   hipStream_t st)
+// fp8-activation form of the wide kernel
+int launch_gemm_f8(int cfg, const Call &c)
 {
     switch (cfg) {
-#define Y(id, wm, wn, nf, d, bp)                                                                                  \
+#define X(id, wm, wn, nf, d, bp)                                                                                  \
     case id:                                                                                                      \
-        return launch_gemm_cfg<1, wm, wn, nf, d, bp, true>(w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, \
-                                                           Kp, MBT, N, st);
-        FQL_F8_CFG_LIST(Y)
-#undef Y
+        if constexpr (wide_cfg_built_f8(id)) return launch_gemm_cfg<1, wm, wn, nf, d, bp, true>(c);               \
+        else return FQL_ERR_BAD_SHAPE;
+        FQL_CFG_LIST(X)
+#undef X
     default: return FQL_ERR_BAD_SHAPE;
     }
 }
@@ -560,7 +507,7 @@ inline int choose_cfg(int L, int E, int T, int K, int N, bool grouped)
     if (m <= 64) {                                           //  64 x 384 (1 / 2 limbs: full-stage activation ring) ...
         // ... 3 limbs: the one-wave-per-SIMD kernel's 33..64-row tile class (two row blocks x two fragment halves per
         // workgroup): 79.7 vs 89.3 us at 8 x 64 rows (profiles/r03_small_groups.txt); at 32 rows the 32-row kernel stays (67 vs 70)
-        if (L == 3 && g_use_w4 && padded_k(K) >= 2 * FQL_KB) return 301;
+        if (L == 3 && g_use_w4 && padded(K) >= 2 * FQL_KB) return 301;
         return (L <= 2) ? 11 : 9;
     }
     const int mt = groups * ((m + 127) / 128);
@@ -581,49 +528,36 @@ inline int choose_cfg(int L, int E, int T, int K, int N, bool grouped)
     }
     // the same 128 x 192 tiles at one wave per SIMD (measured: 124.7 vs 134.4 us at configs[2], 182.6 vs 204.4 us under
     // skewed routing, profiles/r03_w4_vs_wide.txt); its pipeline runs two 256-k weight stages ahead
-    if (best == 0 && g_use_w4 && padded_k(K) >= 2 * FQL_KB) best = 301;
+    if (best == 0 && g_use_w4 && padded(K) >= 2 * FQL_KB) best = 301;
     return best;
 }
 
-int run_mfma(int L, const void *x, int in_dtype, const int32_t *gather, int n_src, const uint8_t *packed,
-             const float *scales, const float *zps, void *out, int out_dtype, const int32_t *tpe, const int32_t *offs,
-             int E, int T, int K, int N, void *workspace, size_t workspace_bytes, hipStream_t st, bool gated = false,
-             bool f8 = false, const float *bias = nullptr, const float *row_weight = nullptr)
+// Pre-pass + GEMM of a call whose workspace is carved.
+int run_mfma(int L, const Call &c)
 {
-    const int Kp = padded_k(K);
-    const int MBT = row_blocks(T, E);
+    if (c.f8) {                                              // float rows -> e4m3 with a per-row scale, one fp8 MFMA pass
+        if (c.gated) return FQL_ERR_BAD_PRECISION;
+        const int rc = launch_act_quant<1>(c);
+        return rc != FQL_OK ? rc : launch_gemm_f8(choose_cfg_f8(c.E, c.T, c.N, c.grouped()), c);
+    }
+    const int cfg = choose_cfg(L, c.E, c.T, c.K, c.N, c.grouped());
+    // one launch: no pre-pass, it is the GEMM kernel's first phase
+    const bool fused = L == 3 && g_fused && cfg == 301 && c.in_dtype == FQL_DTYPE_F32 && !c.gated && c.ws.flags != nullptr &&
+                       (c.K % 16 == 0) && aligned16(c.x) && w4_fusable(3, 6, c);
+    return with_limbs(L, [&](auto l) {
+        constexpr int LL = decltype(l)::value;
+        if (!fused)
+            if (const int rc = launch_act_quant<LL>(c)) return rc;
+        return launch_gemm<LL>(cfg, c, fused);
+    });
+}
+// ... of a call whose shape is set: carves the caller's workspace into the record first
+int run_mfma(int L, Call &c, void *workspace, size_t workspace_bytes)
+{
     if (workspace == nullptr || !aligned16(workspace)) return FQL_ERR_WORKSPACE;
-    Workspace w = carve(workspace, L, T, E, Kp, has_residual(L, f8));
-    if (workspace_bytes < w.bytes) return FQL_ERR_WORKSPACE;
-    w.bias = bias;
-    w.row_weight = row_weight;
-    void *zero_out = (tpe != nullptr) ? out : nullptr;
-    int rc;
-    if (f8) {                                                // float rows -> e4m3 with a per-row scale, one fp8 MFMA pass
-        if (gated) return FQL_ERR_BAD_PRECISION;
-        rc = launch_act_quant<1>(x, in_dtype, gather, n_src, w, T, K, Kp, MBT, zero_out, out_dtype, N, tpe, offs, E, st, false, true);
-        if (rc != FQL_OK) return rc;
-        return launch_gemm_f8(choose_cfg_f8(E, T, N, tpe != nullptr), w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
-    }
-    const int cfg = choose_cfg(L, E, T, K, N, tpe != nullptr);
-    if (L == 1) {
-        rc = launch_act_quant<1>(x, in_dtype, gather, n_src, w, T, K, Kp, MBT, zero_out, out_dtype, N, tpe, offs, E, st, gated);
-        if (rc != FQL_OK) return rc;
-        return launch_gemm<1>(cfg, w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
-    }
-    if (L == 2) {
-        rc = launch_act_quant<2>(x, in_dtype, gather, n_src, w, T, K, Kp, MBT, zero_out, out_dtype, N, tpe, offs, E, st, gated);
-        if (rc != FQL_OK) return rc;
-        return launch_gemm<2>(cfg, w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
-    }
-    if (g_fused && cfg == 301 && in_dtype == FQL_DTYPE_F32 && !gated && w.flags != nullptr && (K % 16 == 0) && aligned16(x) &&
-        w4_fusable(6, tpe, E, T, N)) {
-        w.fuse_x = x; w.fuse_gather = gather; w.fuse_n_src = n_src;      // no pre-pass launch: the GEMM kernel's first phase
-        return launch_gemm<3>(cfg, w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
-    }
-    rc = launch_act_quant<3>(x, in_dtype, gather, n_src, w, T, K, Kp, MBT, zero_out, out_dtype, N, tpe, offs, E, st, gated);
-    if (rc != FQL_OK) return rc;
-    return launch_gemm<3>(cfg, w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
+    c.ws = carve(workspace, L, c.T, c.E, c.Kp, has_residual(L, c.f8));
+    if (workspace_bytes < c.ws.bytes) return FQL_ERR_WORKSPACE;
+    return run_mfma(L, static_cast<const Call &>(c));
 }
 
 int run_generic(const float *x, const uint8_t *packed, const float *scales, const float *zps, float *out,
@@ -636,7 +570,7 @@ int run_generic(const float *x, const uint8_t *packed, const float *scales, cons
     }
     hipLaunchKernelGGL((fused_rows_kernel<4>), dim3((N + 3) / 4, E), dim3(256), 0, st, x, packed, scales, zps,
                        out, tpe, offs, T, K, N, bias);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 size_t gemv_lds_bytes(int B, int K) { return ((size_t)B * (K >> 5) * GEMV_SEG + (size_t)B * 4) * sizeof(float); }
@@ -654,14 +588,10 @@ int launch_gemv(const float *x, const uint8_t *packed, const float *scales, cons
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return FQL_ERR_LAUNCH;
     }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((gemv_kernel<B, GROUPED>), dim3(blocks), dim3(256), lds, st, x, packed, scales, zps, out, K, N, bias, group);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launch(gemv_kernel<B, GROUPED>, dim3(blocks), dim3(256), lds, st, x, packed, scales, zps, out, K, N, bias, group);
 }
 
 }  // namespace
-
-static bool valid_dtype(int dt) { return dt == FQL_DTYPE_F32 || dt == FQL_DTYPE_F16 || dt == FQL_DTYPE_BF16; }
 
 extern "C" {
 
@@ -683,14 +613,14 @@ const char *fql_error_string(int code)
     }
 }
 
-int fql_act_padded_k(int K) { return K > 0 ? padded_k(K) : 0; }
+int fql_act_padded_k(int K) { return K > 0 ? padded(K) : 0; }
 
 size_t fql_linear_workspace_bytes(int B, int K, int N, int precision)
 {
     (void)N;
     const int L = limbs_of(precision);
     if (L < 0 || (B <= g_gemv_max_rows && !is_f8(precision)) || B <= 0 || K <= 0 || (K % 32) != 0) return 0;   // (GEMV shapes use no workspace; fql_linear_fwd_f8 takes any B on the MFMA path)
-    Workspace w = carve(nullptr, L, B, 1, padded_k(K), has_residual(L, is_f8(precision)));
+    Workspace w = carve(nullptr, L, B, 1, padded(K), has_residual(L, is_f8(precision)));
     return w.bytes;
 }
 
@@ -699,7 +629,7 @@ size_t fql_moe_workspace_bytes(int E, int T, int K, int N, int precision)
     (void)N;
     const int L = limbs_of(precision);
     if (L < 0 || T <= 0 || E <= 0 || K <= 0 || (K % 32) != 0) return 0;
-    Workspace w = carve(nullptr, L, T, E, padded_k(K), has_residual(L, is_f8(precision)));
+    Workspace w = carve(nullptr, L, T, E, padded(K), has_residual(L, is_f8(precision)));
     return w.bytes;
 }
 
@@ -733,9 +663,14 @@ static int linear_f32_core(const float *x, const uint8_t *packed, const float *s
         }
         return run_generic(x, packed, scales, zps, out, nullptr, nullptr, 1, B, K, N, st, bias);
     }
-    if (mfma_eligible(L, B, 1, K, N, packed))
-        return run_mfma(L, x, FQL_DTYPE_F32, nullptr, 0, packed, scales, zps, out, FQL_DTYPE_F32, nullptr, nullptr, 1, B, K, N,
-                        workspace, workspace_bytes, st, false, is_f8(precision), bias);
+    if (mfma_eligible(L, B, 1, K, N, packed)) {
+        Call c;
+        c.x = x; c.f8 = is_f8(precision);
+        c.packed = packed; c.scales = scales; c.zps = zps;
+        c.out = out; c.bias = bias; c.st = st;
+        c.set_shape(1, B, K, N);
+        return run_mfma(L, c, workspace, workspace_bytes);
+    }
     return run_generic(x, packed, scales, zps, out, nullptr, nullptr, 1, B, K, N, st, bias);
 }
 
@@ -771,10 +706,15 @@ static int moe_entry(const uint8_t *packed, const float *scales, const float *zp
     }
     if (!packed || !scales || !zps || !inputs || !tokens_per_expert || !input_offsets) return FQL_ERR_NULL_POINTER;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
-    if (mfma_eligible(L, T, E, K, N, packed))
-        return run_mfma(L, inputs, FQL_DTYPE_F32, row_index, n_src, packed, scales, zps, out, FQL_DTYPE_F32,
-                        tokens_per_expert, input_offsets, E, T, K, N, workspace, workspace_bytes, st, false, is_f8(precision),
-                        nullptr, row_weight);
+    if (mfma_eligible(L, T, E, K, N, packed)) {
+        Call c;
+        c.x = inputs; c.gather = row_index; c.n_src = n_src; c.f8 = is_f8(precision);
+        c.packed = packed; c.scales = scales; c.zps = zps;
+        c.out = out; c.row_weight = row_weight; c.st = st;
+        c.tpe = tokens_per_expert; c.offs = input_offsets;
+        c.set_shape(E, T, K, N);
+        return run_mfma(L, c, workspace, workspace_bytes);
+    }
     if (row_index != nullptr || is_f8(precision) || row_weight != nullptr) return FQL_ERR_ALIGNMENT;     // the fused gather / row weights / fp8 exist on the MFMA path only
     return run_generic(inputs, packed, scales, zps, out, tokens_per_expert, input_offsets, E, T, K, N, st);
 }
@@ -844,8 +784,12 @@ int fql_linear_bias_fwd(const void *x, int in_dtype, const uint8_t *packed, cons
     if (B == 0 || N == 0) return FQL_OK;
     if (!x || !packed || !scales || !zps || !out) return FQL_ERR_NULL_POINTER;
     if (B <= g_gemv_max_rows || !mfma_eligible(L, B, 1, K, N, packed)) return FQL_ERR_DTYPE;   // 16-bit I/O exists on the MFMA path only
-    return run_mfma(L, x, in_dtype, nullptr, 0, packed, scales, zps, out, out_dtype, nullptr, nullptr, 1, B, K, N,
-                    workspace, workspace_bytes, static_cast<hipStream_t>(stream), false, is_f8(precision), bias);
+    Call c;
+    c.x = x; c.in_dtype = in_dtype; c.f8 = is_f8(precision);
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.bias = bias; c.st = static_cast<hipStream_t>(stream);
+    c.set_shape(1, B, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
 }
 
 int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
@@ -864,8 +808,13 @@ int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, co
     if (!packed || !scales || !zps || !inputs || !tokens_per_expert || !input_offsets || !out) return FQL_ERR_NULL_POINTER;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
     if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_DTYPE;
-    return run_mfma(L, inputs, in_dtype, nullptr, 0, packed, scales, zps, out, out_dtype, tokens_per_expert,
-                    input_offsets, E, T, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), false, is_f8(precision));
+    Call c;
+    c.x = inputs; c.in_dtype = in_dtype; c.f8 = is_f8(precision);
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tokens_per_expert; c.offs = input_offsets;
+    c.set_shape(E, T, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
 }
 
 // ---- rows that are already OCP e4m3 (BASELINE.json configs[4]): re-layout pre-pass + one fp8 MFMA pass
@@ -878,24 +827,25 @@ static int f8_entry(const uint8_t *packed, const float *scales, const float *zps
     if (K & 1) return FQL_ERR_ODD_K;
     if (T == 0 || N == 0) return FQL_OK;
     if (!packed || !scales || !zps || !x8 || !out) return FQL_ERR_NULL_POINTER;
-    if ((tpe == nullptr) != (offs == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tpe == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tpe, offs, E)) return rc;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
     if (!mfma_eligible(1, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;      // K % 32 == 0, 16-byte aligned weights
-    const int Kp = padded_k(K), MBT = row_blocks(T, E);
+    Call c;
+    c.x = x8; c.f8 = true;
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tpe; c.offs = offs;
+    c.set_shape(E, T, K, N);
     if (workspace == nullptr || !aligned16(workspace)) return FQL_ERR_WORKSPACE;
-    const Workspace w = carve(workspace, 1, T, E, Kp, false);
-    if (workspace_bytes < w.bytes) return FQL_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    c.ws = carve(workspace, 1, T, E, c.Kp, false);
+    if (workspace_bytes < c.ws.bytes) return FQL_ERR_WORKSPACE;
     const int mblocks = (tpe == nullptr) ? (T + FQL_MB - 1) / FQL_MB : (T + FQL_MB * E) / FQL_MB;
     const int rblocks = mblocks * (FQL_MB / ACT_ROWS);
     const int zblocks = (tpe != nullptr) ? (T + 255) / 256 : 0;
-    const int vec = ((K % 16) == 0 && (reinterpret_cast<uintptr_t>(x8) % 16) == 0) ? 1 : 0;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(act_f8_relayout_kernel, dim3(rblocks + zblocks), dim3(256), 0, st, x8, act_scales, (const int32_t *)nullptr, 0,
-                       w.delta, w.rowsum, w.limbs, T, K, Kp / FQL_KB, MBT, rblocks, out, dtype_bytes(out_dtype), N, tpe, offs, E, vec);
-    if (hipGetLastError() != hipSuccess) return FQL_ERR_LAUNCH;
-    return launch_gemm_f8(choose_cfg_f8(E, T, N, tpe != nullptr), w, packed, scales, zps, out, out_dtype, tpe, offs, E, T, K, Kp, MBT, N, st);
+    const int vec = ((K % 16) == 0 && aligned16(x8)) ? 1 : 0;
+    const int rc = launch(act_f8_relayout_kernel, dim3(rblocks + zblocks), dim3(256), 0, c.st, x8, act_scales, nullptr, 0, c.ws.delta,
+                          c.ws.rowsum, c.ws.limbs, T, K, c.Kp / FQL_KB, c.MBT, rblocks, out, dtype_bytes(out_dtype), N, tpe, offs, E, vec);
+    return rc != FQL_OK ? rc : launch_gemm_f8(choose_cfg_f8(E, T, N, tpe != nullptr), c);
 }
 
 int fql_moe_fwd_f8(const uint8_t *packed, const float *scales, const float *zps, const uint8_t *inputs_e4m3,
@@ -925,8 +875,7 @@ static int group_entry(const float *x, const uint8_t *packed, const float *scale
     if (group <= 0 || (group & 1) || K % group != 0) return FQL_ERR_BAD_SHAPE;     // even groups that tile K
     if (T == 0 || N == 0) return FQL_OK;
     if (!x || !packed || !scales || !zps || !out) return FQL_ERR_NULL_POINTER;
-    if ((tpe == nullptr) != (offs == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tpe == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tpe, offs, E)) return rc;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (K == 0) return hipMemsetAsync(out, 0, (size_t)T * N * sizeof(float), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
@@ -961,7 +910,7 @@ static int group_entry(const float *x, const uint8_t *packed, const float *scale
     else
         hipLaunchKernelGGL((fused_rows_group_kernel<4>), dim3((N + 3) / 4, E), dim3(256), 0, st, x, packed, scales, zps, out,
                            tpe, offs, T, K, N, group, bias);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 // ---- per-group scales on the INTEGER matrix cores (csrc/fql_group_i8.h): needs the activation workspace of the per-row
@@ -977,7 +926,7 @@ size_t fql_group_workspace_bytes(int E, int T, int K, int N, int group_size, int
 {
     const int L = limbs_of(precision);
     if (L < 1 || is_f8(precision) || E <= 0 || T <= 0 || K <= 0 || N <= 0 || group_size <= 0 || K % group_size != 0 || (K % 32) != 0) return 0;
-    const Workspace w = carve(nullptr, L, T, E, padded_k(K), has_residual(L, false));
+    const Workspace w = carve(nullptr, L, T, E, padded(K), has_residual(L, false));
     return round16(w.bytes) + 2 * round16((size_t)E * N * (K / group_size) * sizeof(float));
 }
 
@@ -994,26 +943,23 @@ static int group_ws_entry(const float *x, const uint8_t *packed, const float *sc
                     group_i8_eligible(L, E, T, K, N, group, x, packed, tpe != nullptr) &&
                     workspace_bytes >= fql_group_workspace_bytes(E, T, K, N, group, precision);
     if (!ok) return group_entry(x, packed, scales, zps, bias, out, tpe, offs, E, T, K, N, group, stream);   // float32 paths (and their checks)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int Kp = padded_k(K), MBT = row_blocks(T, E), G = K / group;
-    Workspace w = carve(workspace, L, T, E, Kp, has_residual(L, false));
-    float *st_t = reinterpret_cast<float *>(static_cast<char *>(workspace) + round16(w.bytes));
+    Call c;                                                  // (the pre-pass's view of the call: the GEMM below is this path's own)
+    c.x = x; c.out = out; c.tpe = tpe; c.offs = offs; c.st = static_cast<hipStream_t>(stream);
+    c.set_shape(E, T, K, N);
+    c.ws = carve(workspace, L, T, E, c.Kp, has_residual(L, false));
+    const int G = K / group;
+    float *st_t = reinterpret_cast<float *>(static_cast<char *>(workspace) + round16(c.ws.bytes));
     float *zt_t = reinterpret_cast<float *>(reinterpret_cast<char *>(st_t) + round16((size_t)E * N * G * sizeof(float)));
-    void *zero_out = (tpe != nullptr) ? out : nullptr;
-    int rc;
-    if (L == 1) rc = launch_act_quant<1>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, zero_out, FQL_DTYPE_F32, N, tpe, offs, E, st);
-    else if (L == 2) rc = launch_act_quant<2>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, zero_out, FQL_DTYPE_F32, N, tpe, offs, E, st);
-    else rc = launch_act_quant<3>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, zero_out, FQL_DTYPE_F32, N, tpe, offs, E, st);
-    if (rc != FQL_OK) return rc;
-    (void)hipGetLastError();
-    const size_t total = (size_t)E * N * G;
-    hipLaunchKernelGGL(transpose_ng_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, scales, zps, st_t, zt_t, N, G, total);
-    if (hipGetLastError() != hipSuccess) return FQL_ERR_LAUNCH;
-    const dim3 grid((N + 127) / 128, (T + FQL_MB - 1) / FQL_MB, E);
-    if (L == 1) hipLaunchKernelGGL(group_i8_kernel<1>, grid, dim3(256), 0, st, w.limbs, w.delta, packed, st_t, zt_t, out, tpe, offs, E, T, K, MBT, N, group, bias, has_residual(L, false) ? 1 : 0);
-    else if (L == 2) hipLaunchKernelGGL(group_i8_kernel<2>, grid, dim3(256), 0, st, w.limbs, w.delta, packed, st_t, zt_t, out, tpe, offs, E, T, K, MBT, N, group, bias, has_residual(L, false) ? 1 : 0);
-    else hipLaunchKernelGGL(group_i8_kernel<3>, grid, dim3(256), 0, st, w.limbs, w.delta, packed, st_t, zt_t, out, tpe, offs, E, T, K, MBT, N, group, bias, has_residual(L, false) ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return with_limbs(L, [&](auto l) {
+        constexpr int LL = decltype(l)::value;
+        if (const int rc = launch_act_quant<LL>(c)) return rc;
+        const size_t total = (size_t)E * N * G;
+        if (const int rc = launch(transpose_ng_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.st, scales, zps, st_t, zt_t, N, G, total))
+            return rc;
+        hipLaunchKernelGGL(group_i8_kernel<LL>, dim3((N + 127) / 128, (T + FQL_MB - 1) / FQL_MB, E), dim3(256), 0, c.st, c.ws.limbs, c.ws.delta,
+                           packed, st_t, zt_t, out, tpe, offs, E, T, K, c.MBT, N, group, bias, has_residual(L, false) ? 1 : 0);
+        return launched();
+    });
 }
 
 int fql_linear_group_ws_fwd_f32(const float *x, const uint8_t *packed, const float *scales, const float *zps,
@@ -1059,12 +1005,16 @@ int fql_moe_gated_fwd_f32(const uint8_t *packed, const float *scales, const floa
     if (K & 1) return FQL_ERR_ODD_K;
     if (T == 0 || N == 0) return FQL_OK;
     if (!packed || !scales || !zps || !gate_up || !out) return FQL_ERR_NULL_POINTER;
-    if ((tokens_per_expert == nullptr) != (input_offsets == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
     if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
-    return run_mfma(L, gate_up, FQL_DTYPE_F32, nullptr, 0, packed, scales, zps, out, FQL_DTYPE_F32, tokens_per_expert,
-                    input_offsets, E, T, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), true);
+    Call c;
+    c.x = gate_up; c.gated = true;
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tokens_per_expert; c.offs = input_offsets;
+    c.set_shape(E, T, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
 }
 
 // fql_moe_gated_fwd_f32 with an element type for gate_up and one for out: the pre-pass loads 16-bit gate|up rows as they are
@@ -1083,13 +1033,17 @@ int fql_moe_gated_fwd(const uint8_t *packed, const float *scales, const float *z
     if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (T == 0 || N == 0) return FQL_OK;
     if (!packed || !scales || !zps || !gate_up || !out) return FQL_ERR_NULL_POINTER;
-    if ((tokens_per_expert == nullptr) != (input_offsets == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
     if (E > 65535) return FQL_ERR_BAD_SHAPE;
     if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
     if ((reinterpret_cast<uintptr_t>(gate_up) & (dtype_bytes(in_dtype) - 1)) != 0) return FQL_ERR_ALIGNMENT;
-    return run_mfma(L, gate_up, in_dtype, nullptr, 0, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E,
-                    T, K, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), true);
+    Call c;
+    c.x = gate_up; c.in_dtype = in_dtype; c.gated = true;
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tokens_per_expert; c.offs = input_offsets;
+    c.set_shape(E, T, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
 }
 
 int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int top_k, int E, int32_t *counts,
@@ -1103,10 +1057,8 @@ int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int top_k, in
     if (!ensure_lds_attr(attr, reinterpret_cast<const void *>(route_plan_kernel),
                          (ROUTE_THREADS * ROUTE_MAX_EXPERTS + ROUTE_MAX_EXPERTS) * (int)sizeof(int)))
         return FQL_ERR_LAUNCH;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(route_plan_kernel, dim3(1), dim3(ROUTE_THREADS), lds, static_cast<hipStream_t>(stream),
-                       expert_of_slot, n_slots, top_k, E, counts, offsets, token_of_sorted, pos_of_slot);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launch(route_plan_kernel, dim3(1), dim3(ROUTE_THREADS), lds, static_cast<hipStream_t>(stream), expert_of_slot, n_slots,
+                  top_k, E, counts, offsets, token_of_sorted, pos_of_slot);
 }
 
 int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *weights, float *out, int T, int top_k,
@@ -1118,7 +1070,7 @@ int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *wei
     if (T > 65535) return FQL_ERR_BAD_SHAPE;                 // grid.y
     hipLaunchKernelGGL(combine_kernel, dim3((N + 1023) / 1024, T), dim3(256), 0, static_cast<hipStream_t>(stream), y,
                        pos_of_slot, weights, out, T, top_k, N, R);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
@@ -1133,7 +1085,7 @@ int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *po
     if (N == 0 && grad_weights == nullptr) return FQL_OK;
     hipLaunchKernelGGL(combine_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), grad_out, y,
                        pos_of_slot, weights, grad_y, grad_weights, T, top_k, N, rows);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
@@ -1144,7 +1096,7 @@ int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *to
     hipLaunchKernelGGL(regroup_index_kernel, dim3(1), dim3(256), (size_t)2 * G * EL * sizeof(int),
                        static_cast<hipStream_t>(stream), recv_counts, G, EL, tokens_per_expert, input_offsets, gather,
                        scatter);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 int fql_unpack_u8(const uint8_t *packed, uint8_t *q, size_t nbytes, void *stream)
@@ -1156,7 +1108,7 @@ int fql_unpack_u8(const uint8_t *packed, uint8_t *q, size_t nbytes, void *stream
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(unpack_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        packed, q, nbytes);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 int fql_dequantize_f32(const uint8_t *packed, const float *scales, const float *zps, float *w, int N, int K,
@@ -1168,14 +1120,14 @@ int fql_dequantize_f32(const uint8_t *packed, const float *scales, const float *
     if (!packed || !scales || !zps || !w) return FQL_ERR_NULL_POINTER;
     hipLaunchKernelGGL(dequantize_kernel, dim3((N + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), packed,
                        scales, zps, w, N, K);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 size_t fql_act_limb_bytes(int T, int E, int K, int precision)
 {
     const int L = limbs_of(precision);
     if (L < 0 || T <= 0 || E <= 0 || K <= 0) return 0;
-    return (has_residual(L, is_f8(precision)) ? 2 : 1) * limb_bytes(L, T, E, padded_k(K));
+    return (has_residual(L, is_f8(precision)) ? 2 : 1) * limb_bytes(L, T, E, padded(K));
 }
 
 size_t fql_gemm_scratch_bytes(int precision)
@@ -1193,16 +1145,13 @@ int fql_act_quant_f32(const float *x, int8_t *limbs, float *delta, int32_t *rows
     if (T < 0 || K <= 0 || E <= 0) return FQL_ERR_BAD_SHAPE;
     if (T == 0) return FQL_OK;
     if (!x || !limbs || !delta || !rowsum) return FQL_ERR_NULL_POINTER;
-    if ((tokens_per_expert == nullptr) != (input_offsets == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
     if (!aligned16(limbs)) return FQL_ERR_ALIGNMENT;
-    Workspace w;
-    w.limbs = limbs; w.delta = delta; w.rowsum = rowsum; w.scratch = nullptr; w.bias = nullptr; w.bytes = 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int Kp = padded_k(K), MBT = row_blocks(T, E);
-    if (L == 1) return launch_act_quant<1>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, nullptr, FQL_DTYPE_F32, 0, tokens_per_expert, input_offsets, E, st, false, is_f8(precision));
-    if (L == 2) return launch_act_quant<2>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, nullptr, FQL_DTYPE_F32, 0, tokens_per_expert, input_offsets, E, st);
-    return launch_act_quant<3>(x, FQL_DTYPE_F32, nullptr, 0, w, T, K, Kp, MBT, nullptr, FQL_DTYPE_F32, 0, tokens_per_expert, input_offsets, E, st);
+    Call c;
+    c.x = x; c.f8 = is_f8(precision); c.tpe = tokens_per_expert; c.offs = input_offsets; c.st = static_cast<hipStream_t>(stream);
+    c.set_shape(E, T, K, 0);
+    c.ws.limbs = limbs; c.ws.delta = delta; c.ws.rowsum = rowsum;
+    return with_limbs(L, [&](auto l) { return launch_act_quant<decltype(l)::value>(c); });
 }
 
 int fql_quantize_rows_f32(const float *w, uint8_t *packed, float *scales, float *zps, int N, int K, void *stream)
@@ -1213,7 +1162,7 @@ int fql_quantize_rows_f32(const float *w, uint8_t *packed, float *scales, float 
     if (!w || !packed || !scales || !zps) return FQL_ERR_NULL_POINTER;
     hipLaunchKernelGGL(quantize_rows_kernel, dim3(N), dim3(256), 0, static_cast<hipStream_t>(stream), w, N, K, packed,
                        scales, zps);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 int fql_quantize_tensor_f32(const float *w, uint8_t *packed, float *scales, float *zps, float *scratch, int N, int K,
@@ -1227,7 +1176,7 @@ int fql_quantize_tensor_f32(const float *w, uint8_t *packed, float *scales, floa
     hipLaunchKernelGGL(row_minmax_kernel, dim3(N), dim3(256), 0, st, w, N, K, scratch, scratch + N);
     hipLaunchKernelGGL(tensor_scale_kernel, dim3(1), dim3(256), 0, st, scratch, scratch + N, N, scales, zps);
     hipLaunchKernelGGL(quantize_given_kernel, dim3(N), dim3(256), 0, st, w, N, K, scales, zps, packed);
-    return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    return launched();
 }
 
 // `bias` [E][N] and `row_weight` [T] are optional.  The kernels take the bias as a pointer, but read a row's weight from the
@@ -1245,8 +1194,7 @@ static int gemm_i8_entry(int cfg, const int8_t *limbs, const float *delta, const
     if (K & 1) return FQL_ERR_ODD_K;
     if (T == 0 || N == 0) return FQL_OK;
     if (!limbs || !delta || !rowsum || !packed || !scales || !zps || !out) return FQL_ERR_NULL_POINTER;
-    if ((tokens_per_expert == nullptr) != (input_offsets == nullptr)) return FQL_ERR_NULL_POINTER;
-    if (tokens_per_expert == nullptr && E != 1) return FQL_ERR_BAD_SHAPE;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
     if ((K % 32) != 0 || !aligned16(packed) || !aligned16(limbs)) return FQL_ERR_ALIGNMENT;
     if (!mfma_addressable(L, T, E, K, N)) return FQL_ERR_BAD_SHAPE;
     if (row_weight != nullptr && row_weight != delta + (size_t)(has_residual(L, is_f8(precision)) ? 2 : 1) * T) return FQL_ERR_ALIGNMENT;
@@ -1257,25 +1205,19 @@ static int gemm_i8_entry(int cfg, const int8_t *limbs, const float *delta, const
         if (cfg < 0) cfg = choose_cfg(L, E, T, K, N, tokens_per_expert != nullptr);
         if (!valid_cfg(cfg, L)) return FQL_ERR_BAD_SHAPE;
     }
-    Workspace w;
-    w.limbs = const_cast<int8_t *>(limbs);
-    w.delta = const_cast<float *>(delta);
-    w.rowsum = const_cast<int32_t *>(rowsum);
-    w.bias = bias;
-    w.row_weight = row_weight;
-    w.bytes = 0;
+    Call c;
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.bias = bias; c.row_weight = row_weight;
+    c.tpe = tokens_per_expert; c.offs = input_offsets; c.st = static_cast<hipStream_t>(stream);
+    c.set_shape(E, T, K, N);
+    c.ws.limbs = const_cast<int8_t *>(limbs);
+    c.ws.delta = const_cast<float *>(delta);
+    c.ws.rowsum = const_cast<int32_t *>(rowsum);
     // without (enough) scratch the residual pass of heavy-tailed rows is skipped: the result is then the plain 8L-1 bit one
-    w.scratch = (has_residual(L, is_f8(precision)) && scratch != nullptr && aligned16(scratch) && scratch_bytes >= res_scratch_bytes())
-                    ? static_cast<float *>(scratch) : nullptr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int Kp = padded_k(K), MBT = row_blocks(T, E);
-    if (is_f8(precision))
-        return launch_gemm_f8(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
-    if (L == 1)
-        return launch_gemm<1>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
-    if (L == 2)
-        return launch_gemm<2>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
-    return launch_gemm<3>(cfg, w, packed, scales, zps, out, out_dtype, tokens_per_expert, input_offsets, E, T, K, Kp, MBT, N, st);
+    c.ws.scratch = (has_residual(L, is_f8(precision)) && scratch != nullptr && aligned16(scratch) && scratch_bytes >= res_scratch_bytes())
+                       ? static_cast<float *>(scratch) : nullptr;
+    if (is_f8(precision)) return launch_gemm_f8(cfg, c);
+    return with_limbs(L, [&](auto l) { return launch_gemm<decltype(l)::value>(cfg, c); });
 }
 
 int fql_gemm_i8_f32(const int8_t *limbs, const float *delta, const int32_t *rowsum, const uint8_t *packed,

@@ -55,7 +55,7 @@ FQL_API int fql_lora_shrink(const void *in, int in_dtype, const float *w, int w_
 {
     int rc = shape_check(E, T, C, r, w_layout);
     if (rc != FQL_OK) return rc;
-    if (!dtype_ok(in_dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(in_dtype)) return FQL_ERR_DTYPE;
     if (in_dtype == FQL_DTYPE_F32)
         return fql_lora_shrink_f32(static_cast<const float *>(in), w, w_layout, tokens_per_expert, input_offsets, out, E,
                                    T, C, r, scale, stream);
@@ -75,7 +75,7 @@ FQL_API int fql_lora_expand(const float *v, const float *w, int w_layout, const 
 {
     int rc = shape_check(E, T, C, r, w_layout);
     if (rc != FQL_OK) return rc;
-    if (!dtype_ok(out_dtype) || (in && !dtype_ok(in_dtype))) return FQL_ERR_DTYPE;
+    if (!valid_dtype(out_dtype) || (in && !valid_dtype(in_dtype))) return FQL_ERR_DTYPE;
     if (in && in == out && in_dtype != out_dtype) return FQL_ERR_DTYPE;       // in place: one element type
     const int di = in ? in_dtype : FQL_DTYPE_F32;
     if (di == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32)
@@ -98,7 +98,7 @@ FQL_API int fql_lora_grad(const void *p, int p_dtype, const float *v, const int3
 {
     int rc = shape_check(E, T, C, r, d_layout);
     if (rc != FQL_OK) return rc;
-    if (!dtype_ok(p_dtype)) return FQL_ERR_DTYPE;
+    if (!valid_dtype(p_dtype)) return FQL_ERR_DTYPE;
     if (p_dtype == FQL_DTYPE_F32)
         return fql_lora_grad_f32(static_cast<const float *>(p), v, tokens_per_expert, input_offsets, d, d_layout, E, T,
                                  C, r, scale, stream);

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
+#include "fql_host.h"
 #include "fql_lora.h"
 
 namespace lora_host {
@@ -11,7 +12,7 @@ inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintp
 
 inline bool rank_ok(int r) { return r == 4 || r == 8 || r == 16 || r == 32 || r == 64; }
 
-inline bool dtype_ok(int d) { return d == FQL_DTYPE_F32 || d == FQL_DTYPE_F16 || d == FQL_DTYPE_BF16; }
+using fql_host::valid_dtype;
 inline uintptr_t elem_bytes(int d) { return d == FQL_DTYPE_F32 ? 4 : 2; }
 
 // Widest vector, in ELEMENTS, every row of the [T][C] operands allows: 4 when C % 4 == 0 and each base is aligned to 4
@@ -43,7 +44,7 @@ inline int table_check(const int32_t *tpe, const int32_t *offs, int E)
     return FQL_OK;
 }
 
-inline int launched() { return hipGetLastError() == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH; }
+using fql_host::launched;
 
 inline int tile_slots(int T, int E, int TM, bool table) { return (T + TM - 1) / TM + (table ? E : 0); }
 inline int cover_blocks(int T, bool table) { return table ? (T + FQL_LORA_COVER_ROWS - 1) / FQL_LORA_COVER_ROWS : 0; }
