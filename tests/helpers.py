@@ -235,3 +235,87 @@ def clipped_ranges(tokens_per_expert, input_offsets, T):
         hi = min(max(o + c, lo), T) if c > 0 else lo
         out.append((lo, hi))
     return out
+
+
+# ---- guard bands (tests/test_gpu_footprint.py): a kernel that leaves its buffer lands in memory the test owns -----------
+GUARD_BYTES = 64 * 1024
+
+
+class Guarded:
+    """``nbytes`` of device memory (the interior) inside one larger uint8 allocation, with at least GUARD_BYTES of guard
+    on each side.  The interior starts ``offset`` bytes past a 256-byte boundary: 16 for a workspace, limb or scratch
+    buffer (the least the library accepts), the element size for everything else.  The guards hold ``guard_value``
+    repeated as elements of ``guard_dtype`` (a sentinel no result can be around an output; NaN, 0xFF or a huge index
+    around an input, so that a guard element that is USED shows in the values as well)."""
+
+    def __init__(self, name, nbytes, guard_dtype, guard_value, offset=16, device="cuda"):
+        import torch
+        esz = torch.empty((), dtype=guard_dtype).element_size()
+        assert offset % esz == 0 and nbytes % esz == 0 and 0 <= offset < 256, (name, offset, nbytes, esz)
+        self.name, self.nbytes = name, int(nbytes)
+        self.raw = torch.empty(2 * GUARD_BYTES + 512 + self.nbytes, dtype=torch.uint8, device=device)
+        base = self.raw.data_ptr()
+        assert base % 16 == 0
+        self.start = GUARD_BYTES + (offset - (base + GUARD_BYTES)) % 256
+        assert (base + self.start) % 256 == offset and self.start % esz == 0
+        self.end = self.start + self.nbytes
+        self.ptr = base + self.start
+        self.raw.zero_()
+        if guard_dtype == torch.int32 or guard_dtype == torch.uint8:
+            self.raw[:self.start].view(guard_dtype).fill_(guard_value)
+            self.raw[self.end:self.end + GUARD_BYTES].view(guard_dtype).fill_(guard_value)
+        else:
+            self.raw[:self.start].view(guard_dtype).fill_(float(guard_value))
+            self.raw[self.end:self.end + GUARD_BYTES].view(guard_dtype).fill_(float(guard_value))
+        self._lo = self.raw[:self.start].clone()
+        self._hi = self.raw[self.end:self.end + GUARD_BYTES].clone()
+
+    def bytes(self):
+        """The interior as uint8 [nbytes] (a view)."""
+        return self.raw[self.start:self.end]
+
+    def view(self, dtype, *shape):
+        """The interior as a tensor of ``dtype`` and ``shape`` (a view: the kernels' buffer itself)."""
+        return self.bytes().view(dtype).view(*shape)
+
+    def put(self, tensor):
+        """Copy ``tensor`` (any device) into the interior; returns the interior view of its dtype and shape."""
+        v = self.view(tensor.dtype, *tensor.shape)
+        v.copy_(tensor)
+        return v
+
+    def violations(self):
+        """None, or (first, last) changed guard byte as offsets from the start of the interior (negative: in front of
+        it; >= nbytes: behind it)."""
+        import torch
+        if torch.equal(self.raw[:self.start], self._lo) and torch.equal(self.raw[self.end:self.end + GUARD_BYTES], self._hi):
+            return None
+        lo = (self.raw[:self.start] != self._lo).nonzero().flatten() - self.start
+        hi = (self.raw[self.end:self.end + GUARD_BYTES] != self._hi).nonzero().flatten() + self.nbytes
+        bad = torch.cat((lo, hi))
+        return int(bad.min()), int(bad.max())
+
+
+def guarded_like(name, tensor, guard_value, offset=None, guard_dtype=None, device="cuda"):
+    """A Guarded buffer holding a copy of ``tensor`` (numpy or torch); ``offset`` defaults to the element size."""
+    import torch
+    t = torch.as_tensor(tensor)
+    g = Guarded(name, t.numel() * t.element_size(), guard_dtype or t.dtype, guard_value,
+                t.element_size() if offset is None else offset, device)
+    g.put(t.contiguous())
+    return g
+
+
+def assert_guards_intact(*buffers, what=""):
+    """After a synchronize: no guard byte of any buffer has changed.  The message names the buffer and the first and
+    last changed byte relative to its interior."""
+    import torch
+    if buffers and buffers[0].raw.is_cuda:
+        torch.cuda.synchronize()
+    for b in buffers:
+        v = b.violations()
+        if v is not None:
+            first, last = v
+            where = lambda o: f"{-o} bytes in front of it" if o < 0 else f"{o - b.nbytes} bytes past its end"
+            raise AssertionError(f"{what}: buffer '{b.name}' ({b.nbytes} bytes): guard changed, first byte at interior "
+                                 f"offset {first} ({where(first)}), last at {last} ({where(last)})")
