@@ -6,7 +6,7 @@ python/moe_int4_module.py and benchmark/moe_grouped_gemm/).
 """
 from .quantize import quantize_weights, dequantize_weights, reference_quantized_linear
 from .module import QuantizedLinear
-from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN
+from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN, QuantizedSparseMoEBlock
 from .lora import LoRAQuantizedLinear, LoRAMoEINT4, LoRAQuantizedMoEFFN
 from .routing import (RoutingResult, simulate_routing, balanced_routing, create_expert_inputs,
                       combine_expert_outputs, dispatch_grouped, dispatch_indices, combine_grouped)
@@ -16,5 +16,5 @@ __all__ = [
     "MoEINT4", "quantize_weights_moe", "QuantizedMoE", "QuantizedMoEExpert", "QuantizedMoEFFN",
     "RoutingResult", "simulate_routing", "balanced_routing", "create_expert_inputs",
     "combine_expert_outputs", "dispatch_grouped", "dispatch_indices", "combine_grouped",
-    "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN",
+    "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN", "QuantizedSparseMoEBlock",
 ]

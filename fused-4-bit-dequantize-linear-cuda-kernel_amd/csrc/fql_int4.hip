@@ -17,6 +17,7 @@
 #include "fql_generic.h"
 #include "fql_quantize.h"
 #include "fql_routing.h"
+#include "fql_router.h"
 #include "fql_w4_launch.h"
 #include "fql_ffn16_launch.h"
 #include <atomic>
@@ -591,6 +592,28 @@ int launch_gemv(const float *x, const uint8_t *packed, const float *scales, cons
     return launch(gemv_kernel<B, GROUPED>, dim3(blocks), dim3(256), lds, st, x, packed, scales, zps, out, K, N, bias, group);
 }
 
+// The router's group width for E experts: f(std::integral_constant<int, G>, std::integral_constant<int, NPL>) with
+// G = min(64, next_pow2(E)) lanes per token and NPL = 2 experts per lane past 64 (csrc/fql_router.h)
+template <class F>
+int with_router_group(int E, F &&f)
+{
+    using std::integral_constant;
+    if (E > 64) return f(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+    if (E > 32) return f(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    if (E > 16) return f(integral_constant<int, 32>{}, integral_constant<int, 1>{});
+    if (E > 8) return f(integral_constant<int, 16>{}, integral_constant<int, 1>{});
+    if (E > 4) return f(integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    if (E > 2) return f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    if (E > 1) return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+    return f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+}
+int router_shape_check(int dtype, int T, int E, int top_k)
+{
+    if (!valid_dtype(dtype)) return FQL_ERR_DTYPE;
+    if (T < 0 || E < 1 || E > ROUTER_MAX_EXPERTS || top_k < 1 || top_k > E || top_k > ROUTER_MAX_TOPK) return FQL_ERR_BAD_SHAPE;
+    return FQL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1086,6 +1109,33 @@ int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *po
     hipLaunchKernelGGL(combine_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), grad_out, y,
                        pos_of_slot, weights, grad_y, grad_weights, T, top_k, N, rows);
     return launched();
+}
+
+int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int renormalize, int32_t *indices,
+                        float *weights, float *probs, void *stream)
+{
+    if (const int rc = router_shape_check(logits_dtype, T, E, top_k)) return rc;
+    if (T == 0) return FQL_OK;
+    if (!logits || !indices || !weights) return FQL_ERR_NULL_POINTER;                 // probs == NULL: not wanted
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(router_topk_fwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
+                      static_cast<hipStream_t>(stream), logits, logits_dtype, T, E, top_k, renormalize, indices, weights, probs);
+    });
+}
+
+int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
+                        const float *grad_probs, void *grad_logits, int T, int E, int top_k, int renormalize, void *stream)
+{
+    if (const int rc = router_shape_check(logits_dtype, T, E, top_k)) return rc;
+    if (T == 0) return FQL_OK;
+    if (!logits || !indices || !grad_logits) return FQL_ERR_NULL_POINTER;             // either gradient may be NULL
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(router_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
+                      static_cast<hipStream_t>(stream), logits, logits_dtype, indices, grad_weights, grad_probs, grad_logits, T,
+                      E, top_k, renormalize);
+    });
 }
 
 int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,

@@ -340,3 +340,95 @@ class _GatedFFN16Fn(_GatedFFNFn):
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
                                     precision=m.precision, out_dtype=dt)
         return dx, None, None, None
+
+
+class QuantizedSparseMoEBlock(nn.Module):
+    """A Mixtral-style sparse MoE layer, hidden states in and hidden states out: a trainable float gate, the fused top-k
+    router (``ops.router_topk``), the one-launch plan, a dispatch with a deterministic backward, the INT4 gated FFN
+    experts and the one-launch combine.  ``forward`` returns ``(out, router_logits)`` as the Hugging Face Mixtral block
+    does.  Nothing is read back to the host.
+
+    ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
+    (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
+    when not given; a ``LoRAQuantizedMoEFFN`` may be passed in).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    With a 16-bit ``activation_dtype`` the expert rows are widened to float32 for the combine (which is float32 only)
+    and the output is rounded once to the activation type."""
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
+                 activation_dtype=None, renormalize: bool = True, experts=None):
+        super().__init__()
+        from . import ops
+        if num_experts < 1 or num_experts > ops.ROUTE_MAX_EXPERTS:
+            raise ValueError(f"num_experts must be in [1, {ops.ROUTE_MAX_EXPERTS}], got {num_experts}")
+        if top_k < 1 or top_k > min(num_experts, ops.ROUTER_MAX_TOPK):
+            raise ValueError(f"top_k must be in [1, min(num_experts, {ops.ROUTER_MAX_TOPK})], got {top_k}")
+        if experts is None:
+            experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
+                                      activation_dtype=activation_dtype)
+        elif (experts.num_experts, experts.hidden_dim, experts.ffn_dim) != (num_experts, hidden_dim, ffn_dim):
+            raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
+        self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
+        self.top_k, self.renormalize = top_k, bool(renormalize)
+        self.gate = nn.Linear(hidden_dim, num_experts, bias=False)
+        self.experts = experts
+        self.routing = None                  # (probs, tokens_per_expert, indices) of the last forward, for aux_loss
+
+    @classmethod
+    def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
+                     down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
+                     renormalize: bool = True) -> "QuantizedSparseMoEBlock":
+        """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
+        ``QuantizedMoEFFN.from_weights`` takes them."""
+        experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype)
+        E, H = gate_weight.shape
+        if E != experts.num_experts or H != experts.hidden_dim:
+            raise ValueError("gate_weight must be [num_experts, hidden_dim]")
+        m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
+                renormalize=renormalize, experts=experts)
+        with torch.no_grad():
+            m.gate.weight.copy_(gate_weight.float())
+        return m
+
+    def router_logits(self, x2: torch.Tensor) -> torch.Tensor:
+        w = self.gate.weight
+        return nn.functional.linear(x2, w if w.dtype == x2.dtype else w.to(x2.dtype))
+
+    def forward(self, x: torch.Tensor):
+        """``x`` [..., H] on the GPU (float32, or the experts' 16-bit ``activation_dtype``) ->
+        ``(out [..., H], router_logits [T, E])``, T the number of tokens: at most 65535 per call, the limit of
+        ``ops.combine`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax,
+        and ``self.routing = (probs, tokens_per_expert, indices)`` of this call is kept for ``aux_loss`` until the next
+        call (``probs`` is None under ``torch.no_grad()``); the weights and the output are the same bits either way.
+        ``probs`` carries its autograd graph: a loop that holds many blocks and wants no ``aux_loss`` drops it with
+        ``block.routing = None`` after the forward."""
+        if not x.is_cuda:
+            raise RuntimeError("QuantizedSparseMoEBlock runs on the GPU (the product path has no CPU fallback)")
+        from . import ops
+        x2 = x.reshape(-1, self.hidden_dim)
+        logits = self.router_logits(x2)
+        weights, indices, *probs = ops.router_topk(logits, self.top_k, self.renormalize,
+                                                   return_probs=torch.is_grad_enabled())
+        tpe, offs, token_of_sorted, pos_of_slot = ops.route_plan(indices, self.num_experts)
+        self.routing = (probs[0] if probs else None, tpe, indices)
+        rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)
+        y = self.experts(rows, tpe, offs)
+        out = ops.combine(y if y.dtype == torch.float32 else y.float(), pos_of_slot, weights)
+        return out.to(x.dtype).reshape(x.shape), logits
+
+    def aux_loss(self, probs=None, tokens_per_expert=None):
+        """The Switch / Mixtral load-balancing loss ``E * sum_e f_e * P_e``: ``f_e = tokens_per_expert[e] / T`` (the share
+        of the tokens that chose expert e, a constant) and ``P_e`` the mean router probability of e, a few torch ops.
+        Both default to what the last ``forward`` under grad mode kept (``self.routing``): no launch is repeated, and the
+        gradient reaches the router logits through the ``grad_probs`` input of the router's backward.  Or pass the
+        ``probs`` [T, E] of ``ops.router_topk(..., return_probs=True)`` and the counts of ``ops.route_plan``."""
+        if probs is None or tokens_per_expert is None:
+            kept = getattr(self, "routing", None)
+            if kept is None or (probs is None and kept[0] is None):
+                raise RuntimeError("aux_loss needs probs and tokens_per_expert, or a forward under grad mode before it")
+            probs = kept[0] if probs is None else probs
+            tokens_per_expert = kept[1] if tokens_per_expert is None else tokens_per_expert
+        f = tokens_per_expert.detach().to(torch.float32) / probs.shape[0]
+        return self.num_experts * torch.sum(f * probs.mean(dim=0))
+
+    def extra_repr(self) -> str:
+        return f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, top_k={self.top_k}, renormalize={self.renormalize}"

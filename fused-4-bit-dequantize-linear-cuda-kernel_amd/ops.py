@@ -452,6 +452,71 @@ def combine(y, pos_of_slot, expert_weights, top_k=None):
     return out
 
 
+ROUTER_MAX_TOPK = 8
+
+
+def _router_operands(logits, top_k):
+    """``(logits contiguous, T, E)`` of ``router_topk`` and its backward; the limits of csrc/fql_router.h raise here."""
+    _on(logits.device, logits=logits)
+    if logits.dim() != 2 or logits.dtype not in _DTYPES:
+        raise RuntimeError("logits must be a float32, float16 or bfloat16 [tokens, num_experts] tensor")
+    T, E = logits.shape
+    if E < 1 or E > ROUTE_MAX_EXPERTS:
+        raise RuntimeError(f"router_topk supports 1 to {ROUTE_MAX_EXPERTS} experts, got {E}")
+    if not isinstance(top_k, int) or top_k < 1 or top_k > min(E, ROUTER_MAX_TOPK):
+        raise RuntimeError(f"top_k must be an integer in [1, min(num_experts, {ROUTER_MAX_TOPK})], got {top_k!r}")
+    return logits.contiguous(), T, E
+
+
+def router_topk(logits, top_k, renormalize=True, return_probs=False):
+    """The MoE router in ONE launch (replaces softmax -> topk -> sum -> div -> to(int32)): ``logits`` [T, E] float32 /
+    float16 / bfloat16 on the GPU -> ``(weights [T, top_k] float32, indices [T, top_k] int32)``, plus ``probs`` [T, E]
+    float32 (the full softmax, for a load-balancing loss) with ``return_probs``.  Selection is on the logits, ties to the
+    lower expert id; ``renormalize`` divides the selected probabilities by their sum (Mixtral).  ``indices`` is what
+    ``route_plan`` reads, ``weights`` what ``combine`` reads.  A row with a non-finite logit gets NaN weights and indices
+    0 .. top_k-1.  Under autograd the gradients of ``weights`` and ``probs`` reach ``logits`` in one backward launch."""
+    if _wants_grad(logits):
+        out = _RouterTopkFn.apply(logits, top_k, bool(renormalize), bool(return_probs))
+        return out if return_probs else out[:2]
+    logits, T, E = _router_operands(logits, top_k)
+    dev = logits.device
+    indices = torch.empty((T, top_k), dtype=torch.int32, device=dev)
+    weights = torch.empty((T, top_k), dtype=torch.float32, device=dev)
+    probs = torch.empty((T, E), dtype=torch.float32, device=dev) if return_probs else None
+    _launch("fql_router_topk_fwd", dev, logits, _DTYPES[logits.dtype], T, E, top_k, int(bool(renormalize)), indices, weights,
+            probs)
+    return (weights, indices, probs) if return_probs else (weights, indices)
+
+
+def router_topk_backward(logits, indices, grad_weights, grad_probs, renormalize=True):
+    """Gradient of ``router_topk`` to ``logits`` (in their type, rounded once) from the gradients of ``weights`` and / or
+    ``probs`` (float32; either may be None), one launch, no atomics."""
+    top_k = indices.shape[1]
+    logits, T, E = _router_operands(logits, top_k)
+    dev = logits.device
+    _on(dev, indices=indices, grad_weights=grad_weights, grad_probs=grad_probs)
+    if tuple(indices.shape) != (T, top_k) or (grad_weights is not None and tuple(grad_weights.shape) != (T, top_k)) \
+            or (grad_probs is not None and tuple(grad_probs.shape) != (T, E)):
+        raise RuntimeError("indices and grad_weights must be [tokens, top_k], grad_probs [tokens, num_experts]")
+    gw = None if grad_weights is None else grad_weights.to(dtype=torch.float32).contiguous()
+    gp = None if grad_probs is None else grad_probs.to(dtype=torch.float32).contiguous()
+    grad_logits = torch.empty_like(logits)
+    _launch("fql_router_topk_bwd", dev, logits, _DTYPES[logits.dtype], indices.to(dtype=torch.int32).contiguous(), gw, gp,
+            grad_logits, T, E, top_k, int(bool(renormalize)))
+    return grad_logits
+
+
+def dispatch_rows(x, token_of_sorted, pos_of_slot, top_k):
+    """The differentiable dispatch: ``x[token_of_sorted]`` ([T, H] -> [T * top_k, H], rows in expert order, from the plan
+    of ``route_plan``).  Its backward is the pure gather-add form of ``combine`` over ``pos_of_slot`` (one launch, no
+    atomics: ``x.grad`` is bit-reproducible, which ``index_add_`` is not).  That kernel is float32: a 16-bit gradient is
+    widened for the call and the sum rounded back once."""
+    if _wants_grad(x):
+        return _DispatchRowsFn.apply(x, token_of_sorted, pos_of_slot, top_k)
+    _on(x.device, x=x, token_of_sorted=token_of_sorted)
+    return x.index_select(0, token_of_sorted)
+
+
 def regroup_index(recv_counts, total_rows):
     """Expert-parallel receive side: ``recv_counts`` [G, EL] (rows per source rank and local expert, in arrival
     order), ``total_rows`` = their sum (the caller knows it on the host from the all-to-all split sizes) ->
@@ -861,6 +926,40 @@ class _CombineFn(torch.autograd.Function):
         if gw is not None and w.dtype != torch.float32:
             gw = gw.to(w.dtype)
         return gy, None, gw, None
+
+
+class _RouterTopkFn(torch.autograd.Function):
+    """``router_topk`` with the gradient to the logits.  Saves the logits and the indices; the softmax is recomputed."""
+
+    @staticmethod
+    def forward(ctx, logits, top_k, renormalize, return_probs):
+        out = router_topk(logits.detach(), top_k, renormalize, return_probs)
+        ctx.save_for_backward(logits, out[1])
+        ctx.renormalize = renormalize
+        ctx.set_materialize_grads(False)                       # a gradient that does not exist arrives as None
+        ctx.mark_non_differentiable(out[1])
+        return out if return_probs else out + (None,)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_weights, _grad_indices, grad_probs):
+        logits, indices = ctx.saved_tensors
+        return router_topk_backward(logits, indices, grad_weights, grad_probs, ctx.renormalize), None, None, None
+
+
+class _DispatchRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, token_of_sorted, pos_of_slot, top_k):
+        ctx.save_for_backward(pos_of_slot)
+        ctx.top_k, ctx.x_dtype = top_k, x.dtype
+        return dispatch_rows(x.detach(), token_of_sorted, pos_of_slot, top_k)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_rows):
+        pos_of_slot, = ctx.saved_tensors
+        gx = combine(grad_rows.to(torch.float32), pos_of_slot, None, ctx.top_k)
+        return gx.to(ctx.x_dtype), None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 260 /* 0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 270 /* 0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -362,6 +362,37 @@ FQL_API int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int t
 
 FQL_API int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *weights, float *out,
                             int T, int top_k, int N, int R, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The router in front of fql_route_plan_i32 (csrc/fql_router.h): softmax over a token's logits, its top_k experts and
+ * their routing weights in one launch, and the backward of that in one launch.  No workspace.
+ *
+ * fql_router_topk_fwd: logits [T][E] contiguous, float32 / float16 / bfloat16 (logits_dtype, an FQL_DTYPE_* code; 16-bit
+ *   values are widened exactly), 1 <= E <= 128, 1 <= top_k <= min(E, 8).  Outputs: indices [T][top_k] int32 (the
+ *   expert_of_slot of fql_route_plan_i32), weights [T][top_k] float32 (the weights of fql_combine_f32) and, unless
+ *   probs == NULL, probs [T][E] float32, the full softmax.
+ *     selection: on the logits; slot j holds the j-th largest, ties go to the lower expert id
+ *                (torch.sort(-logits, stable=True).indices[:, :top_k]).
+ *     p_e = exp(l_e - m) / sum_e' exp(l_e' - m), m the row maximum, float32, accurate expf, pairwise sums.
+ *     renormalize != 0: weights[j] = p_{e_j} / sum_i p_{e_i} (Mixtral);  renormalize == 0: weights[j] = p_{e_j}.
+ *     a row with a non-finite logit: NaN weights, NaN probs, indices 0 .. top_k-1 (always valid ids in [0, E)).
+ *     a token's results depend on its own row alone (not on T or on its neighbours), and are the same bits every call.
+ * fql_router_topk_bwd: grad_logits [T][E] in the logits' element type (rounded once) from the saved logits and indices
+ *   and the incoming grad_weights [T][top_k] and / or grad_probs [T][E] (float32; either may be NULL, both NULL: zeros).
+ *   With g = grad_weights and w, p recomputed from the logits:
+ *     renormalize != 0: dl_{e_j} = w_j * (g_j - sum_i w_i g_i), exactly 0.0 for every expert no slot names;
+ *     renormalize == 0: dl_e = p_e * ([e selected] g_e - sum_j p_{e_j} g_j);
+ *     grad_probs: dl_e += p_e * (grad_probs_e - sum_e' p_e' grad_probs_e').
+ *   Fixed summation order, no atomics.  A row with a non-finite logit gets a NaN row (also with both gradients NULL).
+ * Return codes, both, in this order and all before any HIP call: FQL_ERR_DTYPE (logits_dtype); FQL_ERR_BAD_SHAPE
+ *   (T < 0, E < 1, E > 128, top_k < 1, top_k > E, top_k > 8); T == 0: FQL_OK with nothing launched;
+ *   FQL_ERR_NULL_POINTER (logits, indices, weights / grad_logits); then FQL_ERR_LAUNCH.
+ * ------------------------------------------------------------------------------------- */
+FQL_API int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int renormalize,
+                                int32_t *indices, float *weights, float *probs, void *stream);
+FQL_API int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
+                                const float *grad_probs, void *grad_logits, int T, int E, int top_k, int renormalize,
+                                void *stream);
 
 /* ---- backward (input gradients; the INT4 weights are frozen: no weight gradient) ----
  * fql_linear_bwd_input_f32: grad_in[B][K] = grad_out[B][N] @ W, W[n][k] = (q[n][k] - zps[n]) * scales[n], on the INT8
