@@ -106,6 +106,10 @@ _SYMBOLS = {
     "fql_router_topk_fwd": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4),
     "fql_router_topk_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4
                             + [ctypes.c_void_p]),
+    "fql_router_score_topk_fwd": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+                                  + [ctypes.c_int] * 4 + [ctypes.c_float] + [ctypes.c_void_p] * 4),
+    "fql_router_score_topk_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                                  + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 #include "fql_quantize.h"
 #include "fql_routing.h"
 #include "fql_router.h"
+#include "fql_router_score.h"
 #include "fql_w4_launch.h"
 #include "fql_ffn16_launch.h"
 #include <atomic>
@@ -613,6 +614,16 @@ int router_shape_check(int dtype, int T, int E, int top_k)
     if (T < 0 || E < 1 || E > ROUTER_MAX_EXPERTS || top_k < 1 || top_k > E || top_k > ROUTER_MAX_TOPK) return FQL_ERR_BAD_SHAPE;
     return FQL_OK;
 }
+// The scored router's arguments on top of router_shape_check (the backward has no groups: n_group = topk_group = 1)
+int router_score_shape_check(int dtype, int T, int E, int top_k, int scoring, int n_group, int topk_group, int group_top,
+                             float scale)
+{
+    if (const int rc = router_shape_check(dtype, T, E, top_k)) return rc;
+    if (scoring < 0 || scoring > 1 || n_group < 1 || n_group > ROUTER_MAX_GROUPS || E % n_group != 0 || topk_group < 1 ||
+        topk_group > n_group || topk_group * (E / n_group) < top_k || group_top < 1 || group_top > 2 || !std::isfinite(scale))
+        return FQL_ERR_BAD_SHAPE;
+    return FQL_OK;
+}
 
 }  // namespace
 
@@ -1135,6 +1146,37 @@ int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *ind
         return launch(router_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
                       static_cast<hipStream_t>(stream), logits, logits_dtype, indices, grad_weights, grad_probs, grad_logits, T,
                       E, top_k, renormalize);
+    });
+}
+
+int fql_router_score_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int scoring,
+                              const float *select_bias, int n_group, int topk_group, int group_top, int renormalize,
+                              float scale, int32_t *indices, float *weights, float *scores, void *stream)
+{
+    if (const int rc = router_score_shape_check(logits_dtype, T, E, top_k, scoring, n_group, topk_group, group_top, scale))
+        return rc;
+    if (T == 0) return FQL_OK;
+    if (!logits || !indices || !weights) return FQL_ERR_NULL_POINTER;     // select_bias, scores == NULL: none / not wanted
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(router_score_topk_fwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
+                      static_cast<hipStream_t>(stream), logits, logits_dtype, T, E, top_k, scoring, select_bias, n_group,
+                      topk_group, group_top, renormalize, scale, indices, weights, scores);
+    });
+}
+
+int fql_router_score_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
+                              const float *grad_scores, void *grad_logits, int T, int E, int top_k, int scoring,
+                              int renormalize, float scale, void *stream)
+{
+    if (const int rc = router_score_shape_check(logits_dtype, T, E, top_k, scoring, 1, 1, 1, scale)) return rc;
+    if (T == 0) return FQL_OK;
+    if (!logits || !indices || !grad_logits) return FQL_ERR_NULL_POINTER;             // either gradient may be NULL
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(router_score_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
+                      static_cast<hipStream_t>(stream), logits, logits_dtype, indices, grad_weights, grad_scores,
+                      grad_logits, T, E, top_k, scoring, renormalize, scale);
     });
 }
 

@@ -12,6 +12,7 @@ semantics implemented are the ones its wrapper documents and ``QuantizedMoE.forw
 """
 from __future__ import annotations
 
+import math
 from typing import List
 
 import torch
@@ -352,16 +353,35 @@ class QuantizedSparseMoEBlock(nn.Module):
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
     when not given; a ``LoRAQuantizedMoEFFN`` may be passed in).  State-dict keys: ``gate.weight`` and ``experts.*``.
     With a 16-bit ``activation_dtype`` the expert rows are widened to float32 for the combine (which is float32 only)
-    and the output is rounded once to the activation type."""
+    and the output is rounded once to the activation type.
+
+    The routing rule is Mixtral's by default.  ``scoring="sigmoid"``, ``n_group`` / ``topk_group`` / ``group_top``
+    (group-limited selection), ``routed_scaling_factor`` and ``selection_bias=True`` (a float32 buffer
+    ``gate.e_score_correction_bias`` [E] of zeros, added to the scores for the selection only and moved by
+    ``update_selection_bias``) select the rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4: any of them sends the
+    forward through ``ops.router_score_topk``; with all at their defaults it calls
+    ``ops.router_topk`` as before and the state-dict keys are unchanged."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
-                 activation_dtype=None, renormalize: bool = True, experts=None):
+                 activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
+                 n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
+                 selection_bias: bool = False):
         super().__init__()
         from . import ops
         if num_experts < 1 or num_experts > ops.ROUTE_MAX_EXPERTS:
             raise ValueError(f"num_experts must be in [1, {ops.ROUTE_MAX_EXPERTS}], got {num_experts}")
         if top_k < 1 or top_k > min(num_experts, ops.ROUTER_MAX_TOPK):
             raise ValueError(f"top_k must be in [1, min(num_experts, {ops.ROUTER_MAX_TOPK})], got {top_k}")
+        if scoring not in ("softmax", "sigmoid"):
+            raise ValueError(f"scoring must be 'softmax' or 'sigmoid', got {scoring!r}")
+        if n_group < 1 or n_group > ops.ROUTER_MAX_GROUPS or num_experts % n_group != 0:
+            raise ValueError(f"n_group must be in [1, {ops.ROUTER_MAX_GROUPS}] and divide num_experts, got {n_group}")
+        if topk_group < 1 or topk_group > n_group or topk_group * (num_experts // n_group) < top_k:
+            raise ValueError(f"topk_group must be in [1, n_group] and its groups must hold top_k experts, got {topk_group}")
+        if group_top not in (1, 2):
+            raise ValueError(f"group_top must be 1 or 2, got {group_top}")
+        if not math.isfinite(routed_scaling_factor):
+            raise ValueError("routed_scaling_factor must be finite")
         if experts is None:
             experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
                                       activation_dtype=activation_dtype)
@@ -369,25 +389,53 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
         self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
         self.top_k, self.renormalize = top_k, bool(renormalize)
+        self.scoring, self.n_group, self.topk_group, self.group_top = scoring, n_group, topk_group, group_top
+        self.routed_scaling_factor = float(routed_scaling_factor)
         self.gate = nn.Linear(hidden_dim, num_experts, bias=False)
+        if selection_bias:                   # the checkpoint's name: gate.e_score_correction_bias
+            self.gate.register_buffer("e_score_correction_bias", torch.zeros(num_experts, dtype=torch.float32))
         self.experts = experts
-        self.routing = None                  # (probs, tokens_per_expert, indices) of the last forward, for aux_loss
+        self.routing = None                  # (probs / scores, tokens_per_expert, indices) of the last forward
 
     @classmethod
     def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
                      down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
-                     renormalize: bool = True) -> "QuantizedSparseMoEBlock":
+                     renormalize: bool = True, **routing) -> "QuantizedSparseMoEBlock":
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
-        ``QuantizedMoEFFN.from_weights`` takes them."""
+        ``QuantizedMoEFFN.from_weights`` takes them.  ``routing``: the constructor's ``scoring``, ``n_group``,
+        ``topk_group``, ``group_top``, ``routed_scaling_factor`` and ``selection_bias``."""
         experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype)
         E, H = gate_weight.shape
         if E != experts.num_experts or H != experts.hidden_dim:
             raise ValueError("gate_weight must be [num_experts, hidden_dim]")
         m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
-                renormalize=renormalize, experts=experts)
+                renormalize=renormalize, experts=experts, **routing)
         with torch.no_grad():
             m.gate.weight.copy_(gate_weight.float())
         return m
+
+    @property
+    def selection_bias(self):
+        """The buffer ``gate.e_score_correction_bias`` [E], or None for a block built without ``selection_bias``."""
+        return getattr(self.gate, "e_score_correction_bias", None)
+
+    @property
+    def scored_routing(self) -> bool:
+        """Whether any routing setting differs from Mixtral's: the forward then runs ``ops.router_score_topk``."""
+        return (self.scoring != "softmax" or self.n_group != 1 or self.routed_scaling_factor != 1.0
+                or self.selection_bias is not None)
+
+    def update_selection_bias(self, rate: float) -> None:
+        """The aux-loss-free balancing step on the counts of the last forward: ``b_e += rate * sign(mean(c) - c_e)``, an
+        over-loaded expert's bias goes down and an under-loaded one's up.  A few torch ops, nothing read back."""
+        bias = self.selection_bias
+        if bias is None:
+            raise RuntimeError("update_selection_bias needs a block built with selection_bias=True")
+        if self.routing is None:
+            raise RuntimeError("update_selection_bias needs a forward before it")
+        with torch.no_grad():
+            counts = self.routing[1].to(torch.float32)
+            bias.add_(torch.sign(counts.mean() - counts), alpha=rate)
 
     def router_logits(self, x2: torch.Tensor) -> torch.Tensor:
         w = self.gate.weight
@@ -396,7 +444,7 @@ class QuantizedSparseMoEBlock(nn.Module):
     def forward(self, x: torch.Tensor):
         """``x`` [..., H] on the GPU (float32, or the experts' 16-bit ``activation_dtype``) ->
         ``(out [..., H], router_logits [T, E])``, T the number of tokens: at most 65535 per call, the limit of
-        ``ops.combine`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax,
+        ``ops.combine`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax (the sigmoids with ``scoring="sigmoid"``),
         and ``self.routing = (probs, tokens_per_expert, indices)`` of this call is kept for ``aux_loss`` until the next
         call (``probs`` is None under ``torch.no_grad()``); the weights and the output are the same bits either way.
         ``probs`` carries its autograd graph: a loop that holds many blocks and wants no ``aux_loss`` drops it with
@@ -406,8 +454,13 @@ class QuantizedSparseMoEBlock(nn.Module):
         from . import ops
         x2 = x.reshape(-1, self.hidden_dim)
         logits = self.router_logits(x2)
-        weights, indices, *probs = ops.router_topk(logits, self.top_k, self.renormalize,
-                                                   return_probs=torch.is_grad_enabled())
+        if self.scored_routing:
+            weights, indices, *probs = ops.router_score_topk(
+                logits, self.top_k, self.scoring, self.selection_bias, self.n_group, self.topk_group, self.group_top,
+                self.renormalize, self.routed_scaling_factor, return_scores=torch.is_grad_enabled())
+        else:
+            weights, indices, *probs = ops.router_topk(logits, self.top_k, self.renormalize,
+                                                       return_probs=torch.is_grad_enabled())
         tpe, offs, token_of_sorted, pos_of_slot = ops.route_plan(indices, self.num_experts)
         self.routing = (probs[0] if probs else None, tpe, indices)
         rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)
@@ -420,15 +473,27 @@ class QuantizedSparseMoEBlock(nn.Module):
         of the tokens that chose expert e, a constant) and ``P_e`` the mean router probability of e, a few torch ops.
         Both default to what the last ``forward`` under grad mode kept (``self.routing``): no launch is repeated, and the
         gradient reaches the router logits through the ``grad_probs`` input of the router's backward.  Or pass the
-        ``probs`` [T, E] of ``ops.router_topk(..., return_probs=True)`` and the counts of ``ops.route_plan``."""
+        ``probs`` [T, E] of ``ops.router_topk(..., return_probs=True)`` and the counts of ``ops.route_plan``.  With
+        ``scoring="sigmoid"`` ``P`` is taken from ``scores / scores.sum(-1, keepdim=True)``."""
         if probs is None or tokens_per_expert is None:
             kept = getattr(self, "routing", None)
             if kept is None or (probs is None and kept[0] is None):
                 raise RuntimeError("aux_loss needs probs and tokens_per_expert, or a forward under grad mode before it")
             probs = kept[0] if probs is None else probs
             tokens_per_expert = kept[1] if tokens_per_expert is None else tokens_per_expert
+        if self.scoring == "sigmoid":        # the sigmoids of a row do not sum to 1
+            probs = probs / probs.sum(dim=-1, keepdim=True)
         f = tokens_per_expert.detach().to(torch.float32) / probs.shape[0]
         return self.num_experts * torch.sum(f * probs.mean(dim=0))
 
     def extra_repr(self) -> str:
-        return f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, top_k={self.top_k}, renormalize={self.renormalize}"
+        s = f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, top_k={self.top_k}, renormalize={self.renormalize}"
+        if self.scoring != "softmax":
+            s += f", scoring={self.scoring}"
+        if self.n_group != 1:
+            s += f", n_group={self.n_group}, topk_group={self.topk_group}, group_top={self.group_top}"
+        if self.routed_scaling_factor != 1.0:
+            s += f", routed_scaling_factor={self.routed_scaling_factor}"
+        if self.selection_bias is not None:
+            s += ", selection_bias=True"
+        return s

@@ -506,6 +506,82 @@ def router_topk_backward(logits, indices, grad_weights, grad_probs, renormalize=
     return grad_logits
 
 
+ROUTER_MAX_GROUPS = 8
+_SCORINGS = {"softmax": 0, "sigmoid": 1}
+
+
+def _router_score_settings(E, top_k, scoring, n_group=1, topk_group=1, group_top=1, scale=1.0):
+    """``(scoring code, scale as a float)`` of ``router_score_topk`` and its backward; the limits of
+    csrc/fql_router_score.h raise here."""
+    try:
+        code = _SCORINGS[scoring]
+    except (KeyError, TypeError):
+        raise ValueError(f"scoring must be 'softmax' or 'sigmoid', got {scoring!r}") from None
+    if not all(isinstance(v, int) for v in (n_group, topk_group, group_top)):
+        raise RuntimeError("n_group, topk_group and group_top must be integers")
+    if n_group < 1 or n_group > ROUTER_MAX_GROUPS or E % n_group != 0:
+        raise RuntimeError(f"n_group must be in [1, {ROUTER_MAX_GROUPS}] and divide num_experts ({E}), got {n_group}")
+    if topk_group < 1 or topk_group > n_group or topk_group * (E // n_group) < top_k:
+        raise RuntimeError(f"topk_group must be in [1, n_group] and its groups must hold top_k experts, got {topk_group}")
+    if group_top not in (1, 2):
+        raise RuntimeError(f"group_top must be 1 or 2, got {group_top}")
+    scale = float(scale)
+    if scale != scale or scale in (float("inf"), float("-inf")):
+        raise RuntimeError("scale must be finite")
+    return code, scale
+
+
+def router_score_topk(logits, top_k, scoring="softmax", select_bias=None, n_group=1, topk_group=1, group_top=2,
+                      renormalize=True, scale=1.0, return_scores=False):
+    """``router_topk`` for the routing rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4, still ONE launch:
+    ``scoring`` 'softmax' or 'sigmoid'; ``select_bias`` [E] float32 (``e_score_correction_bias``) is added to the scores
+    for the selection only; the experts form ``n_group`` groups of which the ``topk_group`` best are searched, a group's
+    score being the largest (``group_top=1``, DeepSeek-V2) or the sum of the two largest (``group_top=2``, DeepSeek-V3)
+    biased scores; the weights are the unbiased scores of the chosen experts, divided by their sum (``renormalize``) and
+    multiplied by ``scale`` (``routed_scaling_factor``).  Returns ``(weights [T, top_k] float32, indices [T, top_k]
+    int32)``, plus ``scores`` [T, E] float32 with ``return_scores``.  Without a bias the selection is on the logits, ties
+    to the lower expert id; experts outside the chosen groups are never selected.  With the defaults the results are the
+    bits of ``router_topk``.  Under autograd the gradients of ``weights`` and ``scores`` reach ``logits`` in one backward
+    launch; the bias gets none."""
+    if _wants_grad(logits):
+        out = _RouterScoreTopkFn.apply(logits, top_k, scoring, select_bias, n_group, topk_group, group_top,
+                                       bool(renormalize), scale, bool(return_scores))
+        return out if return_scores else out[:2]
+    logits, T, E = _router_operands(logits, top_k)
+    code, scale = _router_score_settings(E, top_k, scoring, n_group, topk_group, group_top, scale)
+    dev = logits.device
+    _on(dev, select_bias=select_bias)
+    if select_bias is not None and (select_bias.dtype != torch.float32 or tuple(select_bias.shape) != (E,)):
+        raise RuntimeError("select_bias must be a float32 [num_experts] tensor")
+    bias = None if select_bias is None else select_bias.detach().contiguous()
+    indices = torch.empty((T, top_k), dtype=torch.int32, device=dev)
+    weights = torch.empty((T, top_k), dtype=torch.float32, device=dev)
+    scores = torch.empty((T, E), dtype=torch.float32, device=dev) if return_scores else None
+    _launch("fql_router_score_topk_fwd", dev, logits, _DTYPES[logits.dtype], T, E, top_k, code, bias, n_group, topk_group,
+            group_top, int(bool(renormalize)), scale, indices, weights, scores)
+    return (weights, indices, scores) if return_scores else (weights, indices)
+
+
+def router_score_topk_backward(logits, indices, grad_weights, grad_scores, scoring="softmax", renormalize=True, scale=1.0):
+    """Gradient of ``router_score_topk`` to ``logits`` (in their type, rounded once) from the gradients of ``weights``
+    and / or ``scores`` (float32; either may be None), one launch, no atomics.  The groups and the bias do not enter:
+    the ``indices`` say what was chosen."""
+    top_k = indices.shape[1]
+    logits, T, E = _router_operands(logits, top_k)
+    code, scale = _router_score_settings(E, top_k, scoring, scale=scale)
+    dev = logits.device
+    _on(dev, indices=indices, grad_weights=grad_weights, grad_scores=grad_scores)
+    if tuple(indices.shape) != (T, top_k) or (grad_weights is not None and tuple(grad_weights.shape) != (T, top_k)) \
+            or (grad_scores is not None and tuple(grad_scores.shape) != (T, E)):
+        raise RuntimeError("indices and grad_weights must be [tokens, top_k], grad_scores [tokens, num_experts]")
+    gw = None if grad_weights is None else grad_weights.to(dtype=torch.float32).contiguous()
+    gs = None if grad_scores is None else grad_scores.to(dtype=torch.float32).contiguous()
+    grad_logits = torch.empty_like(logits)
+    _launch("fql_router_score_topk_bwd", dev, logits, _DTYPES[logits.dtype], indices.to(dtype=torch.int32).contiguous(), gw,
+            gs, grad_logits, T, E, top_k, code, int(bool(renormalize)), scale)
+    return grad_logits
+
+
 def dispatch_rows(x, token_of_sorted, pos_of_slot, top_k):
     """The differentiable dispatch: ``x[token_of_sorted]`` ([T, H] -> [T * top_k, H], rows in expert order, from the plan
     of ``route_plan``).  Its backward is the pure gather-add form of ``combine`` over ``pos_of_slot`` (one launch, no
@@ -945,6 +1021,28 @@ class _RouterTopkFn(torch.autograd.Function):
     def backward(ctx, grad_weights, _grad_indices, grad_probs):
         logits, indices = ctx.saved_tensors
         return router_topk_backward(logits, indices, grad_weights, grad_probs, ctx.renormalize), None, None, None
+
+
+class _RouterScoreTopkFn(torch.autograd.Function):
+    """``router_score_topk`` with the gradient to the logits.  Saves the logits and the indices; the scores are
+    recomputed."""
+
+    @staticmethod
+    def forward(ctx, logits, top_k, scoring, select_bias, n_group, topk_group, group_top, renormalize, scale, return_scores):
+        out = router_score_topk(logits.detach(), top_k, scoring, select_bias, n_group, topk_group, group_top, renormalize,
+                                scale, return_scores)
+        ctx.save_for_backward(logits, out[1])
+        ctx.scoring, ctx.renormalize, ctx.scale = scoring, renormalize, scale
+        ctx.set_materialize_grads(False)                       # a gradient that does not exist arrives as None
+        ctx.mark_non_differentiable(out[1])
+        return out if return_scores else out + (None,)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_weights, _grad_indices, grad_scores):
+        logits, indices = ctx.saved_tensors
+        return (router_score_topk_backward(logits, indices, grad_weights, grad_scores, ctx.scoring, ctx.renormalize,
+                                           ctx.scale),) + (None,) * 9
 
 
 class _DispatchRowsFn(torch.autograd.Function):

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 270 /* 0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 280 /* 0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -393,6 +393,53 @@ FQL_API int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int
 FQL_API int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
                                 const float *grad_probs, void *grad_logits, int T, int E, int top_k, int renormalize,
                                 void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The scored router (csrc/fql_router_score.h): the routing rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4 in one
+ * launch, and the backward of that in one launch.  No workspace.  The thread mapping, the element types, the limits on
+ * E and top_k and the outputs are those of fql_router_topk_fwd / _bwd above.
+ *
+ * fql_router_score_topk_fwd: logits [T][E]; scoring 0 = softmax, 1 = sigmoid; select_bias [E] float32 or NULL; the
+ *   experts form n_group groups of E / n_group (1 <= n_group <= 8, E % n_group == 0) of which the topk_group best are
+ *   searched (topk_group * (E / n_group) >= top_k); group_top 1 or 2; scale finite.  Outputs: indices [T][top_k] int32,
+ *   weights [T][top_k] float32 and, unless scores == NULL, scores [T][E] float32.
+ *     scores:    softmax p_e (the bits of fql_router_topk_fwd's probs), or s_e = 1 / (1 + expf(-l_e)), float32, accurate
+ *                expf; the sigmoid saturates to exactly 1.0f and 0.0f.
+ *     key:       select_bias == NULL: the logit.  Otherwise score_e + select_bias_e, one float32 add; a NaN key counts
+ *                as -infinity (a non-finite bias is the caller's error; the ids stay in [0, E)).
+ *     groups:    (n_group > 1) group c holds the experts [c * E / n_group, (c + 1) * E / n_group); its score is the
+ *                largest (group_top == 1) or the sum of the two largest (group_top == 2; a one-member group: its single
+ *                value) of score_e + select_bias_e (bias 0 when NULL); the topk_group best groups are chosen, ties to the
+ *                lower group id.  Experts outside them are never selected (the Hugging Face code fills their keys with
+ *                0.0 instead, so that a masked expert beats a negative key; the two agree when all keys are positive).
+ *     slots:     slot j holds the j-th largest key among the allowed experts, ties (-0.0 == 0.0 included) to the lower id.
+ *     weights:   from the unbiased scores.  softmax: (p_{e_j} / sum_i p_{e_i}) * scale (renormalize != 0, the formula
+ *                of fql_router_topk_fwd) or p_{e_j} * scale.  sigmoid: (s_{e_j} / (sum_i s_{e_i} + 1e-20f)) * scale or
+ *                s_{e_j} * scale.
+ *     a row with a non-finite logit: NaN weights, NaN scores, indices 0 .. top_k-1.
+ *     scoring == 0, select_bias == NULL, n_group == 1 and scale == 1: the bits of fql_router_topk_fwd.
+ * fql_router_score_topk_bwd: grad_logits [T][E] in the logits' element type (rounded once) from the saved logits and
+ *   indices and grad_weights [T][top_k] and / or grad_scores [T][E] (float32; either may be NULL, both NULL: zeros).  The
+ *   groups and the bias do not enter (the indices are saved; the bias gets no gradient).  With g_j = scale * grad_weights_j:
+ *     softmax:   the formulas of fql_router_topk_bwd with g (scale == 1: its bits).
+ *     sigmoid:   d_e = s_e * (1 - s_e), 1 - s_e computed as the sigmoid of -l_e;  renormalize != 0, with
+ *                D = sum_i s_{e_i} + 1e-20f and u_i = s_{e_i} / D: dl_{e_j} = d_{e_j} * (g_j - sum_i u_i g_i) / D;
+ *                renormalize == 0: dl_{e_j} = d_{e_j} * g_j;  exactly 0.0 for every expert no slot names;
+ *                grad_scores: dl_e += d_e * grad_scores_e.
+ *   Fixed summation order, no atomics.  A row with a non-finite logit gets a NaN row (also with both gradients NULL).
+ * Return codes, both, in this order and all before any HIP call: FQL_ERR_DTYPE (logits_dtype); FQL_ERR_BAD_SHAPE
+ *   (T < 0, E < 1, E > 128, top_k < 1, top_k > E, top_k > 8, scoring not 0 or 1, scale not finite and, forward only:
+ *   n_group < 1, n_group > 8, E % n_group != 0, topk_group < 1, topk_group > n_group, topk_group * (E / n_group) < top_k,
+ *   group_top not 1 or 2); T == 0: FQL_OK with nothing launched; FQL_ERR_NULL_POINTER (logits, indices, weights /
+ *   grad_logits); then FQL_ERR_LAUNCH.
+ * ------------------------------------------------------------------------------------- */
+FQL_API int fql_router_score_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int scoring,
+                                      const float *select_bias, int n_group, int topk_group, int group_top,
+                                      int renormalize, float scale, int32_t *indices, float *weights, float *scores,
+                                      void *stream);
+FQL_API int fql_router_score_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices,
+                                      const float *grad_weights, const float *grad_scores, void *grad_logits, int T, int E,
+                                      int top_k, int scoring, int renormalize, float scale, void *stream);
 
 /* ---- backward (input gradients; the INT4 weights are frozen: no weight gradient) ----
  * fql_linear_bwd_input_f32: grad_in[B][K] = grad_out[B][N] @ W, W[n][k] = (q[n][k] - zps[n]) * scales[n], on the INT8
