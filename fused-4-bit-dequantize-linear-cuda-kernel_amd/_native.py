@@ -110,6 +110,10 @@ _SYMBOLS = {
                                   + [ctypes.c_int] * 4 + [ctypes.c_float] + [ctypes.c_void_p] * 4),
     "fql_router_score_topk_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
                                   + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_void_p]),
+    "fql_combine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5
+                    + [ctypes.c_void_p]),
+    "fql_combine_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
+                        + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
 }
 
 _lib = None

@@ -625,6 +625,16 @@ int router_score_shape_check(int dtype, int T, int E, int top_k, int scoring, in
     return FQL_OK;
 }
 
+// The typed combine's element types: f(std::integral_constant<int, kind>) for a code that valid_dtype() has accepted
+template <class F>
+int with_dtype(int dt, F &&f)
+{
+    if (dt == FQL_DTYPE_F16) return f(std::integral_constant<int, FQL_DTYPE_F16>{});
+    if (dt == FQL_DTYPE_BF16) return f(std::integral_constant<int, FQL_DTYPE_BF16>{});
+    return f(std::integral_constant<int, FQL_DTYPE_F32>{});
+}
+bool elem_aligned(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+
 }  // namespace
 
 extern "C" {
@@ -1120,6 +1130,62 @@ int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *po
     hipLaunchKernelGGL(combine_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), grad_out, y,
                        pos_of_slot, weights, grad_y, grad_weights, T, top_k, N, rows);
     return launched();
+}
+
+// fql_combine_f32 with an element type for y / addend and one for out, and an optional weighted addend behind the slot
+// terms (csrc/fql_routing.h, combine_any_kernel).  The order of the return codes is part of the ABI (include/fql_int4.h).
+int fql_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
+                const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream)
+{
+    if (T < 0 || top_k <= 0 || N < 0 || R < 0) return FQL_ERR_BAD_SHAPE;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!y || !pos_of_slot || !out || R == 0) return FQL_ERR_NULL_POINTER;
+    if (addend_weight != nullptr && addend == nullptr) return FQL_ERR_NULL_POINTER;
+    if (T > 65535) return FQL_ERR_BAD_SHAPE;                 // grid.y
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(out, ob) || !elem_aligned(pos_of_slot, 4) ||
+        !elem_aligned(weights, 4) || !elem_aligned(addend_weight, 4))
+        return FQL_ERR_ALIGNMENT;
+    if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32 && addend == nullptr)
+        return fql_combine_f32(static_cast<const float *>(y), pos_of_slot, weights, static_cast<float *>(out), T, top_k, N, R,
+                               stream);
+    const unsigned cols = in_dtype == FQL_DTYPE_F32 ? 1024 : 2048;       // 256 threads x 16 bytes of the input type
+    return with_dtype(in_dtype, [&](auto ik) {
+        return with_dtype(out_dtype, [&](auto ok) {
+            return launch(combine_any_kernel<ik.value, ok.value>, dim3((N + cols - 1) / cols, T), dim3(256), 0,
+                          static_cast<hipStream_t>(stream), y, pos_of_slot, weights, addend, addend_weight, out, T, top_k, N, R);
+        });
+    });
+}
+
+int fql_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
+                    const void *addend, const float *addend_weight, int in_dtype, void *grad_y, float *grad_weights,
+                    void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, void *stream)
+{
+    if (T < 0 || top_k <= 0 || N < 0 || rows < 0 || (T > 0 && rows == 0)) return FQL_ERR_BAD_SHAPE;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || (N == 0 && grad_weights == nullptr && grad_addend_weight == nullptr)) return FQL_OK;
+    if (!pos_of_slot) return FQL_ERR_NULL_POINTER;
+    if (N > 0 && (!grad_out || !grad_y)) return FQL_ERR_NULL_POINTER;
+    if (grad_weights != nullptr && N > 0 && !y) return FQL_ERR_NULL_POINTER;
+    if ((addend_weight != nullptr || grad_addend_weight != nullptr) && addend == nullptr) return FQL_ERR_NULL_POINTER;
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!elem_aligned(grad_out, ob) || !elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(grad_y, ib) ||
+        !elem_aligned(grad_addend, ib) || !elem_aligned(pos_of_slot, 4) || !elem_aligned(weights, 4) ||
+        !elem_aligned(addend_weight, 4) || !elem_aligned(grad_weights, 4) || !elem_aligned(grad_addend_weight, 4))
+        return FQL_ERR_ALIGNMENT;
+    if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32 && !addend && !addend_weight && !grad_addend &&
+        !grad_addend_weight)
+        return fql_combine_bwd_f32(static_cast<const float *>(grad_out), static_cast<const float *>(y), pos_of_slot, weights,
+                                   static_cast<float *>(grad_y), grad_weights, T, top_k, N, rows, stream);
+    return with_dtype(in_dtype, [&](auto ik) {
+        return with_dtype(out_dtype, [&](auto ok) {
+            return launch(combine_any_bwd_kernel<ik.value, ok.value>, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream),
+                          grad_out, y, pos_of_slot, weights, addend, addend_weight, grad_y, grad_weights, grad_addend,
+                          grad_addend_weight, T, top_k, N, rows);
+        });
+    });
 }
 
 int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int renormalize, int32_t *indices,

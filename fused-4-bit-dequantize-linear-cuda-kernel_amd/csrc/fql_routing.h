@@ -8,6 +8,9 @@
 //                        for every slot its sorted position (the un-sort index of the combine).
 //   combine_kernel       out[t][:] = sum_k w[t][k] * y[pos[t][k]][:]  (k ascending), 16-byte loads and stores.
 //   combine_bwd_kernel   its gradients to y and to w, in one launch.
+//   combine_any_kernel   the combine with an element type for y and one for out (float32 / float16 / bfloat16) and an
+//                        optional per-token weighted addend (a shared expert's rows) behind the slot terms.
+//   combine_any_bwd_kernel  its gradients to y, w, the addend and the addend's weight, in one launch.
 //   regroup_index_kernel expert-parallel receive side: rows arrive (source rank, local expert)-major, the GEMM
 //                        wants (local expert, source rank)-major: gather index + its inverse + the expert table.
 #pragma once
@@ -129,6 +132,201 @@ __global__ __launch_bounds__(256) void combine_bwd_kernel(
             if (tid == 0) gw[(size_t)t * top_k + k] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
             __syncthreads();
         }
+    }
+}
+
+// ---- the typed combine.  KIND is an FQL_DTYPE_* code: 0 float32, 1 float16, 2 bfloat16.  16-bit
+//      elements are widened in registers on load (exact) and rounded once, to nearest even, on store.
+template <int KIND> struct CombElem { using type = unsigned short; };
+template <> struct CombElem<0> { using type = float; };
+
+template <int KIND>
+__device__ __forceinline__ float comb_widen(typename CombElem<KIND>::type u)
+{
+    if constexpr (KIND == 0) return u;
+    else if constexpr (KIND == 1) {
+        _Float16 h;
+        __builtin_memcpy(&h, &u, 2);
+        return (float)h;
+    } else return __uint_as_float((uint32_t)u << 16);
+}
+template <int KIND>
+__device__ __forceinline__ typename CombElem<KIND>::type comb_round(float v)
+{
+    if constexpr (KIND == 0) return v;
+    else if constexpr (KIND == 1) return f32_to_f16_bits(v);
+    else return f32_to_bf16_bits(v);
+}
+
+// round(w * g) of the backward: the float32 product, rounded, THEN converted, as a multiply followed by Tensor.to does.
+// hipcc selects v_fma_mixlo_f16 for a float16 conversion of a product: that rounds the exact product once (another bit
+// where the two roundings disagree) and computes w * g + 0 (a -0 product becomes +0).  The identity lane move between the
+// multiply and the conversion keeps them two instructions.
+template <int KIND>
+__device__ __forceinline__ typename CombElem<KIND>::type comb_round_product(float w, float g)
+{
+    float p = w * g;
+    if constexpr (KIND == 1) p = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(p), 0xE4, 0xF, 0xF, false));
+    return comb_round<KIND>(p);
+}
+
+// A thread's V consecutive columns of a row move in one of three ways.  COMB_WIDE: accesses of up to 16 bytes (V elements,
+// or two halves when V float32 make 32 bytes); needs N % V == 0 and a base aligned to the access.  COMB_PAIR: accesses of
+// two elements (N even, base aligned to two elements).  COMB_SCALAR: one element at a time.  `left` = N - n columns of
+// the row remain at the thread's first one; a column past the row is loaded as 0 and never stored.
+enum { COMB_WIDE = 0, COMB_PAIR = 1, COMB_SCALAR = 2 };
+template <int KIND, int V>
+struct CombRow {
+    using E = typename CombElem<KIND>::type;
+    static constexpr int C = (V * (int)sizeof(E) > 16) ? 16 / (int)sizeof(E) : V;      // elements of one wide access
+    typedef E EC __attribute__((ext_vector_type(C)));
+    typedef E E2 __attribute__((ext_vector_type(2)));
+
+    static __device__ __forceinline__ int mode(uintptr_t base_bits, int N)
+    {
+        if (N % V == 0 && (base_bits & (C * sizeof(E) - 1)) == 0) return COMB_WIDE;
+        if (N % 2 == 0 && (base_bits & (2 * sizeof(E) - 1)) == 0) return COMB_PAIR;
+        return COMB_SCALAR;
+    }
+    static __device__ __forceinline__ void load(const E *p, int mode, int left, float (&v)[V])
+    {
+        if (mode == COMB_WIDE) {
+#pragma unroll
+            for (int c0 = 0; c0 < V; c0 += C) {
+                const EC r = *reinterpret_cast<const EC *>(p + c0);
+#pragma unroll
+                for (int c = 0; c < C; ++c) v[c0 + c] = comb_widen<KIND>(r[c]);
+            }
+        } else if (mode == COMB_PAIR) {
+#pragma unroll
+            for (int c = 0; c < V; c += 2) {
+                v[c] = v[c + 1] = 0.0f;
+                if (c < left) {
+                    const E2 r = *reinterpret_cast<const E2 *>(p + c);
+                    v[c] = comb_widen<KIND>(r[0]);
+                    v[c + 1] = comb_widen<KIND>(r[1]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < V; ++c) v[c] = c < left ? comb_widen<KIND>(p[c]) : 0.0f;
+        }
+    }
+    static __device__ __forceinline__ void store(E *p, int mode, int left, const float (&v)[V])
+    {
+        if (mode == COMB_WIDE) {
+#pragma unroll
+            for (int c0 = 0; c0 < V; c0 += C) {
+                EC r;
+#pragma unroll
+                for (int c = 0; c < C; ++c) r[c] = comb_round<KIND>(v[c0 + c]);
+                *reinterpret_cast<EC *>(p + c0) = r;
+            }
+        } else if (mode == COMB_PAIR) {
+#pragma unroll
+            for (int c = 0; c < V; c += 2)
+                if (c < left) *reinterpret_cast<E2 *>(p + c) = E2{comb_round<KIND>(v[c]), comb_round<KIND>(v[c + 1])};
+        } else {
+#pragma unroll
+            for (int c = 0; c < V; ++c) if (c < left) p[c] = comb_round<KIND>(v[c]);
+        }
+    }
+};
+
+// out[t][n] = round_out( (...((0 + y[p_0][n] * w_0) + y[p_1][n] * w_1)...) + addend[t][n] * aw[t] ): the slot terms are
+// combine_kernel's (float32, multiply then add, k ascending, pos clamped, w == NULL: 1), the addend term comes last
+// (addend == NULL: none; aw == NULL: 1, and x * 1 == x keeps the bits of "+ addend").
+// grid: (ceil(N / (V * 256)), T); one thread = V consecutive columns of one token, V = 16 bytes of the input type.
+template <int IK, int OK>
+__global__ __launch_bounds__(256) void combine_any_kernel(
+    const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot, const float *__restrict__ w,
+    const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ out_, int T, int top_k, int N, int R)
+{
+#pragma clang fp contract(off)                     // (y * w), THEN add, as combine_kernel does: never an FMA
+    constexpr int V = IK == 0 ? 4 : 8;
+    using In = CombRow<IK, V>;
+    using Out = CombRow<OK, V>;
+    const typename In::E *y = static_cast<const typename In::E *>(y_), *addend = static_cast<const typename In::E *>(addend_);
+    typename Out::E *out = static_cast<typename Out::E *>(out_);
+    const int t = blockIdx.y;
+    const int n = (blockIdx.x * 256 + threadIdx.x) * V;
+    if (n >= N) return;
+    const int left = N - n;
+    const int imode = In::mode(reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(addend), N);
+    const int omode = Out::mode(reinterpret_cast<uintptr_t>(out), N);
+    float acc[V], v[V];
+#pragma unroll
+    for (int c = 0; c < V; ++c) acc[c] = 0.0f;
+    for (int k = 0; k < top_k; ++k) {
+        int p = pos_of_slot[t * top_k + k];
+        p = p < 0 ? 0 : (p >= R ? R - 1 : p);
+        const float wk = w != nullptr ? w[t * top_k + k] : 1.0f;
+        In::load(y + (size_t)p * N + n, imode, left, v);
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[c] = acc[c] + v[c] * wk;
+    }
+    if (addend != nullptr) {
+        const float a = aw != nullptr ? aw[t] : 1.0f;
+        In::load(addend + (size_t)t * N + n, imode, left, v);
+#pragma unroll
+        for (int c = 0; c < V; ++c) acc[c] = acc[c] + v[c] * a;
+    }
+    Out::store(out + (size_t)t * N + n, omode, left, acc);
+}
+
+// Backward of combine_any_kernel, one workgroup per token t, no atomics; gout has the type OK, y / addend / gy / gaddend
+// the type IK, gw and gaw are float32.  The column-to-thread mapping and the reduction are combine_bwd_kernel's, so the
+// dot products have its bits:
+//   gy[pos[t][k]][:] = round_in(w[t][k] * gout[t][:])         (w == NULL: gout[t][:] itself)
+//   gw[t][k]         = <y[pos[t][k]][:], gout[t][:]>          (gw == NULL: skipped)
+//   gaddend[t][:]    = round_in(aw[t] * gout[t][:])           (gaddend == NULL: skipped; aw == NULL: gout[t][:] itself)
+//   gaw[t]           = <addend[t][:], gout[t][:]>             (gaw == NULL: skipped)
+template <int IK, int OK>
+__global__ __launch_bounds__(256) void combine_any_bwd_kernel(
+    const void *__restrict__ gout_, const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot,
+    const float *__restrict__ w, const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ gy_,
+    float *__restrict__ gw, void *__restrict__ gaddend_, float *__restrict__ gaw, int T, int top_k, int N, int R)
+{
+    using EI = typename CombElem<IK>::type;
+    using EO = typename CombElem<OK>::type;
+    __shared__ float s_part[4];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const EO *go = static_cast<const EO *>(gout_) + (size_t)t * N;
+    for (int k = 0; k < top_k; ++k) {
+        int p = pos_of_slot[(size_t)t * top_k + k];
+        p = p < 0 ? 0 : (p >= R ? R - 1 : p);
+        const float wk = w != nullptr ? w[(size_t)t * top_k + k] : 1.0f;
+        const EI *yr = static_cast<const EI *>(y_) + (size_t)p * N;
+        EI *gyr = static_cast<EI *>(gy_) + (size_t)p * N;
+        float dot = 0.0f;
+        for (int n = tid; n < N; n += 256) {
+            const float g = comb_widen<OK>(go[n]);
+            gyr[n] = w != nullptr ? comb_round_product<IK>(wk, g) : comb_round<IK>(g);
+            if (gw != nullptr) dot = fmaf(comb_widen<IK>(yr[n]), g, dot);
+        }
+        if (gw != nullptr) {
+            dot = wave_sum(dot);
+            if (lane == 0) s_part[wave] = dot;
+            __syncthreads();
+            if (tid == 0) gw[(size_t)t * top_k + k] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+            __syncthreads();
+        }
+    }
+    if (gaddend_ == nullptr && gaw == nullptr) return;
+    const float a = aw != nullptr ? aw[t] : 1.0f;
+    const EI *ar = static_cast<const EI *>(addend_) + (size_t)t * N;       // read only for gaw (the host checks the pair)
+    EI *gar = static_cast<EI *>(gaddend_) + (size_t)t * N;
+    float dot = 0.0f;
+    for (int n = tid; n < N; n += 256) {
+        const float g = comb_widen<OK>(go[n]);
+        if (gaddend_ != nullptr) gar[n] = aw != nullptr ? comb_round_product<IK>(a, g) : comb_round<IK>(g);
+        if (gaw != nullptr) dot = fmaf(comb_widen<IK>(ar[n]), g, dot);
+    }
+    if (gaw != nullptr) {
+        dot = wave_sum(dot);
+        if (lane == 0) s_part[wave] = dot;
+        __syncthreads();
+        if (tid == 0) gaw[t] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
     }
 }
 

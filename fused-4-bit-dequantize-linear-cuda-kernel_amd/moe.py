@@ -352,8 +352,17 @@ class QuantizedSparseMoEBlock(nn.Module):
     ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
     when not given; a ``LoRAQuantizedMoEFFN`` may be passed in).  State-dict keys: ``gate.weight`` and ``experts.*``.
-    With a 16-bit ``activation_dtype`` the expert rows are widened to float32 for the combine (which is float32 only)
-    and the output is rounded once to the activation type.
+    The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
+    to the activations' type: no cast pass either side of it.
+
+    A shared expert (DeepSeek-V2 / V3, GLM-4.5, Kimi-K2, Llama-4, Qwen-MoE) is a dense gated FFN that every token passes
+    through: ``shared_ffn_dim > 0`` builds ``shared_experts = QuantizedMoEFFN(1, hidden_dim, shared_ffn_dim)``, or pass a
+    ready one-expert module as ``shared_experts=`` (a ``LoRAQuantizedMoEFFN`` works).  It runs on the tokens as they are
+    (no dispatch) and its output enters the combine as the addend, behind the routed terms and untouched by the routing
+    weights and ``routed_scaling_factor``.  ``shared_expert_gate=True`` (Qwen2-MoE) adds a float, trainable
+    ``shared_expert_gate = nn.Linear(hidden_dim, 1, bias=False)`` run by torch like ``gate``; the shared output is then
+    weighted per token by ``sigmoid(z)``, ``z`` the layer's output widened to float32.  State-dict keys:
+    ``shared_experts.*`` and ``shared_expert_gate.weight``, absent when the feature is off.
 
     The routing rule is Mixtral's by default.  ``scoring="sigmoid"``, ``n_group`` / ``topk_group`` / ``group_top``
     (group-limited selection), ``routed_scaling_factor`` and ``selection_bias=True`` (a float32 buffer
@@ -365,7 +374,8 @@ class QuantizedSparseMoEBlock(nn.Module):
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
                  n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
-                 selection_bias: bool = False):
+                 selection_bias: bool = False, shared_ffn_dim: int = 0, shared_experts=None,
+                 shared_expert_gate: bool = False):
         super().__init__()
         from . import ops
         if num_experts < 1 or num_experts > ops.ROUTE_MAX_EXPERTS:
@@ -387,6 +397,18 @@ class QuantizedSparseMoEBlock(nn.Module):
                                       activation_dtype=activation_dtype)
         elif (experts.num_experts, experts.hidden_dim, experts.ffn_dim) != (num_experts, hidden_dim, ffn_dim):
             raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
+        if shared_ffn_dim < 0 or shared_ffn_dim % 32 != 0:
+            raise ValueError(f"shared_ffn_dim must be a non-negative multiple of 32, got {shared_ffn_dim}")
+        if shared_experts is not None:
+            if (shared_experts.num_experts, shared_experts.hidden_dim) != (1, hidden_dim):
+                raise ValueError("shared_experts must be one expert (num_experts == 1) of the block's hidden_dim")
+            if shared_ffn_dim and shared_experts.ffn_dim != shared_ffn_dim:
+                raise ValueError("shared_ffn_dim and shared_experts.ffn_dim differ")
+        elif shared_ffn_dim:
+            shared_experts = QuantizedMoEFFN(1, hidden_dim, shared_ffn_dim, precision=precision,
+                                             activation_dtype=activation_dtype)
+        if shared_expert_gate and shared_experts is None:
+            raise ValueError("shared_expert_gate=True needs a shared expert (shared_ffn_dim or shared_experts)")
         self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
         self.top_k, self.renormalize = top_k, bool(renormalize)
         self.scoring, self.n_group, self.topk_group, self.group_top = scoring, n_group, topk_group, group_top
@@ -395,23 +417,40 @@ class QuantizedSparseMoEBlock(nn.Module):
         if selection_bias:                   # the checkpoint's name: gate.e_score_correction_bias
             self.gate.register_buffer("e_score_correction_bias", torch.zeros(num_experts, dtype=torch.float32))
         self.experts = experts
+        if shared_experts is not None:       # (no attribute at all otherwise: the state-dict keys stay those of before)
+            self.shared_experts = shared_experts
+        if shared_expert_gate:
+            self.shared_expert_gate = nn.Linear(hidden_dim, 1, bias=False)
         self.routing = None                  # (probs / scores, tokens_per_expert, indices) of the last forward
 
     @classmethod
     def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
                      down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
-                     renormalize: bool = True, **routing) -> "QuantizedSparseMoEBlock":
+                     renormalize: bool = True, shared=None, shared_expert_gate_weight=None,
+                     **routing) -> "QuantizedSparseMoEBlock":
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
-        ``QuantizedMoEFFN.from_weights`` takes them.  ``routing``: the constructor's ``scoring``, ``n_group``,
-        ``topk_group``, ``group_top``, ``routed_scaling_factor`` and ``selection_bias``."""
+        ``QuantizedMoEFFN.from_weights`` takes them.  ``shared``: ``(gate [Fs, H], up [Fs, H], down [H, Fs])`` of the
+        shared expert; ``shared_expert_gate_weight`` [1, H]: the weight of its sigmoid gate.  ``routing``: the
+        constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor`` and
+        ``selection_bias``."""
         experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype)
         E, H = gate_weight.shape
         if E != experts.num_experts or H != experts.hidden_dim:
             raise ValueError("gate_weight must be [num_experts, hidden_dim]")
+        shared_experts = None
+        if shared is not None:
+            sg, su, sd = shared
+            shared_experts = QuantizedMoEFFN.from_weights([sg], [su], [sd], precision=precision,
+                                                          activation_dtype=activation_dtype)
+        if shared_expert_gate_weight is not None and tuple(shared_expert_gate_weight.shape) != (1, H):
+            raise ValueError("shared_expert_gate_weight must be [1, hidden_dim]")
         m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
-                renormalize=renormalize, experts=experts, **routing)
+                renormalize=renormalize, experts=experts, shared_experts=shared_experts,
+                shared_expert_gate=shared_expert_gate_weight is not None, **routing)
         with torch.no_grad():
             m.gate.weight.copy_(gate_weight.float())
+            if shared_expert_gate_weight is not None:
+                m.shared_expert_gate.weight.copy_(shared_expert_gate_weight.float())
         return m
 
     @property
@@ -441,10 +480,27 @@ class QuantizedSparseMoEBlock(nn.Module):
         w = self.gate.weight
         return nn.functional.linear(x2, w if w.dtype == x2.dtype else w.to(x2.dtype))
 
+    def shared_output(self, x2: torch.Tensor, x_gate=None):
+        """``(s [T, H], aw [T] float32 or None)``: the shared expert on the tokens themselves (one segment of all rows, its
+        table made on the device) and, with ``shared_expert_gate``, its per-token weight ``sigmoid(z)`` in float32, ``z``
+        computed from ``x_gate`` (default ``x2``); ``(None, None)`` for a block without a shared expert."""
+        shared = getattr(self, "shared_experts", None)
+        if shared is None:
+            return None, None
+        T = x2.shape[0]
+        s = shared(x2, torch.full((1,), T, dtype=torch.int32, device=x2.device),
+                   torch.zeros(1, dtype=torch.int32, device=x2.device))
+        gate = getattr(self, "shared_expert_gate", None)
+        if gate is None:
+            return s, None
+        w = gate.weight
+        z = nn.functional.linear(x2 if x_gate is None else x_gate, w if w.dtype == x2.dtype else w.to(x2.dtype))
+        return s, torch.sigmoid(z.to(torch.float32)).reshape(-1)
+
     def forward(self, x: torch.Tensor):
         """``x`` [..., H] on the GPU (float32, or the experts' 16-bit ``activation_dtype``) ->
         ``(out [..., H], router_logits [T, E])``, T the number of tokens: at most 65535 per call, the limit of
-        ``ops.combine`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax (the sigmoids with ``scoring="sigmoid"``),
+        ``ops.combine_any`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax (the sigmoids with ``scoring="sigmoid"``),
         and ``self.routing = (probs, tokens_per_expert, indices)`` of this call is kept for ``aux_loss`` until the next
         call (``probs`` is None under ``torch.no_grad()``); the weights and the output are the same bits either way.
         ``probs`` carries its autograd graph: a loop that holds many blocks and wants no ``aux_loss`` drops it with
@@ -453,7 +509,10 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise RuntimeError("QuantizedSparseMoEBlock runs on the GPU (the product path has no CPU fallback)")
         from . import ops
         x2 = x.reshape(-1, self.hidden_dim)
-        logits = self.router_logits(x2)
+        # Two gates read the tokens through one alias: autograd sums their input gradients there and hands x2 one gate
+        # part, so x.grad is two additions over three parts (dispatch, shared expert, gates) with or without the shared gate.
+        x_gate = x2.view_as(x2) if getattr(self, "shared_expert_gate", None) is not None else x2
+        logits = self.router_logits(x_gate)
         if self.scored_routing:
             weights, indices, *probs = ops.router_score_topk(
                 logits, self.top_k, self.scoring, self.selection_bias, self.n_group, self.topk_group, self.group_top,
@@ -465,8 +524,9 @@ class QuantizedSparseMoEBlock(nn.Module):
         self.routing = (probs[0] if probs else None, tpe, indices)
         rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)
         y = self.experts(rows, tpe, offs)
-        out = ops.combine(y if y.dtype == torch.float32 else y.float(), pos_of_slot, weights)
-        return out.to(x.dtype).reshape(x.shape), logits
+        s, aw = self.shared_output(x2, x_gate)
+        out = ops.combine_any(y, pos_of_slot, weights, addend=s, addend_weight=aw, out_dtype=x.dtype)
+        return out.reshape(x.shape), logits
 
     def aux_loss(self, probs=None, tokens_per_expert=None):
         """The Switch / Mixtral load-balancing loss ``E * sum_e f_e * P_e``: ``f_e = tokens_per_expert[e] / T`` (the share
@@ -496,4 +556,8 @@ class QuantizedSparseMoEBlock(nn.Module):
             s += f", routed_scaling_factor={self.routed_scaling_factor}"
         if self.selection_bias is not None:
             s += ", selection_bias=True"
+        if getattr(self, "shared_experts", None) is not None:
+            s += f", shared_ffn_dim={self.shared_experts.ffn_dim}"
+        if getattr(self, "shared_expert_gate", None) is not None:
+            s += ", shared_expert_gate=True"
         return s

@@ -452,6 +452,51 @@ def combine(y, pos_of_slot, expert_weights, top_k=None):
     return out
 
 
+def _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight):
+    """``_combine_operands`` for the typed combine, plus ``(addend contiguous, addend_weight float32 [T] contiguous)``."""
+    if not y.is_cuda or y.dtype not in _DTYPES or y.dim() != 2:
+        raise RuntimeError("y must be a CUDA float32, float16 or bfloat16 [rows, N] tensor")
+    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
+    _on(y.device, addend=addend, addend_weight=addend_weight)
+    if addend is None:
+        if addend_weight is not None:
+            raise RuntimeError("addend_weight needs an addend")
+        return T, top_k, pos, w, None, None
+    if addend.dtype != y.dtype or tuple(addend.shape) != (T, y.shape[1]):
+        raise RuntimeError("addend must be [tokens, N] of y's type")
+    if addend_weight is not None and (addend_weight.dtype != torch.float32 or tuple(addend_weight.shape) != (T,)):
+        raise RuntimeError("addend_weight must be float32 [tokens]")
+    return T, top_k, pos, w, addend.contiguous(), None if addend_weight is None else addend_weight.contiguous()
+
+
+def _combine_out_dtype(out_dtype, default):
+    out_dtype = default if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    return out_dtype
+
+
+def combine_any(y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None, out_dtype=None):
+    """``combine`` with element types and an addend, in one launch: ``out[t] = sum_k expert_weights[t, k] *
+    y[pos_of_slot[t*top_k + k]] + addend_weight[t] * addend[t]``.  ``y`` [R, N] float32 / float16 / bfloat16 is read as it
+    is, the sum is float32 (the slot terms exactly ``combine``'s, the addend term last) and ``out`` [T, N] is rounded once
+    to ``out_dtype`` (default ``y.dtype``): without an addend, bit for bit ``combine(y.float(), ...).to(out_dtype)``.
+    ``addend`` [T, N] of ``y``'s type (a shared expert's output) and ``addend_weight`` [T] float32 are optional
+    (``addend_weight=None``: 1).  Under autograd the gradients to ``y``, ``expert_weights``, ``addend`` and
+    ``addend_weight`` come from one backward launch (``combine_any_backward``); ``y`` and ``addend`` are saved in their
+    own type."""
+    if _wants_grad(y, expert_weights, addend, addend_weight):
+        return _CombineAnyFn.apply(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
+    T, top_k, pos, w, addend, aw = _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
+    out_dtype = _combine_out_dtype(out_dtype, y.dtype)
+    if T > 65535:
+        raise RuntimeError("combine_any handles up to 65535 tokens per call")
+    out = torch.empty((T, y.shape[1]), dtype=out_dtype, device=y.device)
+    _launch("fql_combine", y.device, y.contiguous(), _DTYPES[y.dtype], pos, w, addend, aw, out, _DTYPES[out_dtype], T, top_k,
+            y.shape[1], y.shape[0])
+    return out
+
+
 ROUTER_MAX_TOPK = 8
 
 
@@ -585,8 +630,8 @@ def router_score_topk_backward(logits, indices, grad_weights, grad_scores, scori
 def dispatch_rows(x, token_of_sorted, pos_of_slot, top_k):
     """The differentiable dispatch: ``x[token_of_sorted]`` ([T, H] -> [T * top_k, H], rows in expert order, from the plan
     of ``route_plan``).  Its backward is the pure gather-add form of ``combine`` over ``pos_of_slot`` (one launch, no
-    atomics: ``x.grad`` is bit-reproducible, which ``index_add_`` is not).  That kernel is float32: a 16-bit gradient is
-    widened for the call and the sum rounded back once."""
+    atomics: ``x.grad`` is bit-reproducible, which ``index_add_`` is not), through ``combine_any``: a 16-bit gradient is
+    read as it arrives, summed in float32 and rounded once to ``x``'s type."""
     if _wants_grad(x):
         return _DispatchRowsFn.apply(x, token_of_sorted, pos_of_slot, top_k)
     _on(x.device, x=x, token_of_sorted=token_of_sorted)
@@ -926,6 +971,27 @@ def combine_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, need_
     return grad_y, grad_w
 
 
+def combine_any_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None,
+                         need_weights=True, need_addend=True, need_addend_weight=True):
+    """Gradients of ``combine_any`` in one launch, no atomics: ``(grad_y [R, N], grad_weights [T, top_k], grad_addend
+    [T, N], grad_addend_weight [T])``, None for what does not exist or is not needed.  ``grad_out`` [T, N] float32 /
+    float16 / bfloat16 is read as it is; ``grad_y`` and ``grad_addend`` have ``y``'s type (rounded once), the two weight
+    gradients are float32.  Rows of ``y`` that no slot names get zero."""
+    T, top_k, pos, w, addend, aw = _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
+    dev = y.device
+    R, N = y.shape
+    _on(dev, grad_out=grad_out)
+    if grad_out.dtype not in _DTYPES or tuple(grad_out.shape) != (T, N):
+        raise RuntimeError("grad_out must be a float32, float16 or bfloat16 [tokens, N] tensor")
+    grad_y = (torch.empty if R == T * top_k else torch.zeros)((R, N), dtype=y.dtype, device=dev)
+    grad_w = torch.empty((T, top_k), dtype=torch.float32, device=dev) if (need_weights and w is not None) else None
+    grad_a = torch.empty((T, N), dtype=y.dtype, device=dev) if (need_addend and addend is not None) else None
+    grad_aw = torch.empty(T, dtype=torch.float32, device=dev) if (need_addend_weight and aw is not None) else None
+    _launch("fql_combine_bwd", dev, grad_out.contiguous(), _DTYPES[grad_out.dtype], y.contiguous(), pos, w, addend, aw,
+            _DTYPES[y.dtype], grad_y, grad_w, grad_a, grad_aw, T, top_k, N, R)
+    return grad_y, grad_w, grad_a, grad_aw
+
+
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
@@ -936,7 +1002,7 @@ def _forward_only(name, *tensors):
     if _wants_grad(*tensors):
         raise RuntimeError(f"ops.{name} has no backward (forward-only); call it under torch.no_grad() or on detached "
                            "inputs.  The differentiable ops are linear_forward, linear_forward_any, moe_forward, "
-                           "moe_forward_any and combine (INTEGRATION.md section 5)")
+                           "moe_forward_any, combine and combine_any (INTEGRATION.md section 5)")
 
 
 class _LinearFn(torch.autograd.Function):
@@ -1004,6 +1070,27 @@ class _CombineFn(torch.autograd.Function):
         return gy, None, gw, None
 
 
+class _CombineAnyFn(torch.autograd.Function):
+    """``combine_any`` with its four gradients from one launch.  Saves ``y`` and ``addend`` in their own type."""
+
+    @staticmethod
+    def forward(ctx, y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype):
+        ctx.save_for_backward(y, pos_of_slot, expert_weights, addend, addend_weight)
+        ctx.top_k = top_k
+        return combine_any(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        y, pos, w, addend, aw = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy, gw, ga, gaw = combine_any_backward(gout, y, pos, w, ctx.top_k, addend, aw, need_weights=need[2],
+                                               need_addend=need[4], need_addend_weight=need[5])
+        if gw is not None and w.dtype != torch.float32:
+            gw = gw.to(w.dtype)
+        return gy if need[0] else None, None, gw, None, ga, gaw, None
+
+
 class _RouterTopkFn(torch.autograd.Function):
     """``router_topk`` with the gradient to the logits.  Saves the logits and the indices; the softmax is recomputed."""
 
@@ -1056,8 +1143,9 @@ class _DispatchRowsFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_rows):
         pos_of_slot, = ctx.saved_tensors
-        gx = combine(grad_rows.to(torch.float32), pos_of_slot, None, ctx.top_k)
-        return gx.to(ctx.x_dtype), None, None, None
+        if grad_rows.dtype not in _DTYPES or ctx.x_dtype not in _DTYPES:      # (a float64 x: through float32, as before)
+            return combine(grad_rows.to(torch.float32), pos_of_slot, None, ctx.top_k).to(ctx.x_dtype), None, None, None
+        return combine_any(grad_rows, pos_of_slot, None, ctx.top_k, out_dtype=ctx.x_dtype), None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------

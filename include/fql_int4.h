@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 280 /* 0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 290 /* 0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -489,6 +489,42 @@ FQL_API int fql_moe_bwd_input(const uint8_t *packed, const float *scales, const 
                               size_t ws_bytes, void *stream);
 FQL_API int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
                                 float *grad_y, float *grad_weights, int T, int top_k, int N, int rows, void *stream);
+
+/* ---- the typed combine with an addend (FQL_VERSION 290; csrc/fql_routing.h) ----
+ * fql_combine: fql_combine_f32 with an element type (FQL_DTYPE_F32 / _F16 / _BF16) for y and one for out, and an optional
+ *   per-token weighted addend (a shared expert's rows) added behind the slot terms:
+ *     out[t][n] = round_out( (...((0 + y[p_0][n] * w_0) + y[p_1][n] * w_1)...) + addend[t][n] * addend_weight[t] )
+ *   y [R][N] and addend [T][N] (or NULL: no term) have in_dtype, out [T][N] has out_dtype, weights [T][top_k] (or NULL:
+ *   1) and addend_weight [T] (or NULL: 1, the bits of "+ addend") are float32.  The slot terms are those of
+ *   fql_combine_f32: float32, multiply then add (never an FMA), k ascending, pos_of_slot clamped into [0, R).  16-bit
+ *   elements are widened in registers (exact); a 16-bit out is rounded once to nearest even as Tensor.to rounds (float16
+ *   overflow gives inf).  So without an addend the result is bit for bit fql_combine_f32 on the widened rows, rounded
+ *   once.  T <= 65535.  (float32, float32) without an addend is fql_combine_f32 itself.
+ * fql_combine_bwd: its gradients in one launch, no atomics (pos_of_slot a permutation of the rows it names).  grad_out
+ *   [T][N] has out_dtype; grad_y [rows][N] and grad_addend [T][N] have in_dtype and are rounded once; grad_weights
+ *   [T][top_k] and grad_addend_weight [T] are float32:
+ *     grad_y[pos[t][k]] = weights[t][k] * grad_out[t] (weights == NULL: grad_out[t]); rows no slot names are not written;
+ *     grad_weights[t][k] = <y[pos[t][k]], grad_out[t]>          (NULL: skipped);
+ *     grad_addend[t] = addend_weight[t] * grad_out[t]           (NULL: skipped; addend_weight == NULL: grad_out[t]);
+ *     grad_addend_weight[t] = <addend[t], grad_out[t]>          (NULL: skipped).
+ *   Both dot products use the reduction of fql_combine_bwd_f32 (the same bits on the widened operands).  (float32,
+ *   float32) with the four addend pointers NULL is fql_combine_bwd_f32 itself.
+ * Return codes, both, in this order and all before any HIP call:
+ *   1. FQL_ERR_BAD_SHAPE: T < 0, top_k <= 0, N < 0, R / rows < 0 (backward: rows == 0 with T > 0);
+ *   2. FQL_ERR_DTYPE: in_dtype or out_dtype outside FQL_DTYPE_*;
+ *   3. the empty call, FQL_OK with nothing launched: T == 0 or N == 0 (backward: T == 0, or N == 0 with grad_weights and
+ *      grad_addend_weight both NULL);
+ *   4. FQL_ERR_NULL_POINTER: y, pos_of_slot, out NULL or R == 0 (backward: pos_of_slot; with N > 0 grad_out, grad_y, and
+ *      y when grad_weights is given); addend_weight without addend; grad_addend_weight without addend;
+ *   5. FQL_ERR_BAD_SHAPE: T > 65535 (forward only);
+ *   6. FQL_ERR_ALIGNMENT: a data pointer not aligned to its element size;
+ *   7. FQL_ERR_LAUNCH. */
+FQL_API int fql_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
+                        const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream);
+FQL_API int fql_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot,
+                            const float *weights, const void *addend, const float *addend_weight, int in_dtype,
+                            void *grad_y, float *grad_weights, void *grad_addend, float *grad_addend_weight, int T,
+                            int top_k, int N, int rows, void *stream);
 
 /* ---- low-rank adapters (LoRA) on the INT4 layers: csrc/fql_lora.h ----
  * Segmented float32 kernels for y = W_q x + scale * B (A x), per expert e over the rows of its range.  The adapter
