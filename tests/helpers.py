@@ -14,6 +14,28 @@ INT8_REL_FRO = 1.5e-2
 INT8_REL_FRO_LARGE_K = 2.5e-2
 # GEMV / generic float32 FMA paths: summation-order noise only.
 FMA_REL_FRO = 2e-6
+# the adapter (LoRA) kernels alone: float32 FMA chains, summation order only (tests/test_gpu_lora_paths.py)
+ADAPTER_TOL = FMA_REL_FRO
+
+
+def tol(base):
+    """A bound of the INT4 path with the float32 floor of the adapter sums (tests/test_gpu_lora.py)."""
+    return max(base, 1e-5)
+
+
+# the float32 adapter kernels on a 16-bit operand that takes a narrower vector width (tests/test_gpu_lora16.py)
+F32_TOL = tol(EXACT_REL_FRO)
+# input gradient (tests/test_gpu_backward_paths.py): per-row bounds, from the heavy-row flag of the pre-pass
+# (csrc/fql_act_quant.h: a row is flagged when its predicted relative error exceeds 1e-6 at L = 3 and 2.5e-4 at L = 2);
+# L = 1 has no residual set: rows without outliers only
+ROW_TOL = {3: EXACT_REL_FRO, 2: 1e-3, 1: INT8_REL_FRO_LARGE_K}
+
+
+def fro_tol(L, N):
+    """Frobenius bound of the mode; at L = 1 a contraction longer than 4096 gets the wider int8 bound."""
+    if L == 1:
+        return INT8_REL_FRO_LARGE_K if N > 4096 else INT8_REL_FRO
+    return {3: EXACT_REL_FRO, 2: FAST_REL_FRO}[L]
 
 
 def rel_fro(got, ref):
@@ -237,8 +259,48 @@ def clipped_ranges(tokens_per_expert, input_offsets, T):
     return out
 
 
-# ---- guard bands (tests/test_gpu_footprint.py): a kernel that leaves its buffer lands in memory the test owns -----------
+# ---- guard bands (tests/test_gpu_footprint*.py): a kernel that leaves its buffer lands in memory the test owns ----------
 GUARD_BYTES = 64 * 1024
+NAN = float("nan")
+SENT = -7.5                        # exact in float32, float16 and bfloat16; no result of the footprint problems
+BIG = 0x7F7F7F7F                   # a table entry or index that is used sends a kernel far away
+
+
+def footprint_table(name):
+    """(tokens_per_expert, input_offsets, T) of the footprint problems, int32 numpy, as the device gets them.  G1: experts
+    of [129, 0, 1, 65, 33] rows plus 3 uncovered (a 128-row tile plus one row, an empty expert); G1c: G1 with a last
+    count that leaves [0, T) and is clipped on the device; G2: one expert of 129 rows and sixteen of 1 (every group
+    leaves a nearly empty 32-row block: the worst case of row_blocks() and m_slots)."""
+    counts, tail = ([129] + [1] * 16, 0) if name == "G2" else ([129, 0, 1, 65, 33], 3)
+    counts = np.array(counts, np.int32)
+    offs = (np.cumsum(counts) - counts).astype(np.int32)
+    T = int(counts.sum()) + tail
+    if name == "G1c":
+        counts[-1] = 999
+        assert offs[-1] + counts[-1] > T
+    return counts, offs, T
+
+
+def bits(t):
+    import torch
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+
+
+def same_bits(a, b):
+    import torch
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
+
+
+def first_diff(a, b):
+    d = (bits(a) != bits(b)).nonzero()
+    return int(d.shape[0]), (d[0].tolist() if d.shape[0] else None)
+
+
+def heavy_rows(x, rng, step=5, factor=800.0):
+    """Two channels x 800 in every fifth row (make_moe of tests/test_gpu_w4.py): flagged by the pre-pass at 2 / 3 limbs."""
+    for t in range(0, x.shape[0], step):
+        x[t, rng.choice(x.shape[1], 2, replace=False)] *= factor
+    return x
 
 
 class Guarded:

@@ -15,25 +15,15 @@ import pytest
 import torch
 
 from conftest import ROOT  # noqa: F401
-from helpers import (EXACT_REL_FRO, FAST_REL_FRO, INT8_REL_FRO, INT8_REL_FRO_LARGE_K, act_limbs_reference,
-                     act_residual_reference, dequant_f64, expert_table, fq, misaligned, ops, rel_fro_dev, row_rel_err)
+from helpers import (EXACT_REL_FRO, ROW_TOL, act_limbs_reference, act_residual_reference, dequant_f64, expert_table, fq,
+                     fro_tol, misaligned, ops, rel_fro_dev, row_rel_err)
 from helpers import clipped_ranges as clamped
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 PREC = {3: "exact", 2: "fast", 1: "int8"}
-# per-row bounds, from the heavy-row flag of the pre-pass (csrc/fql_act_quant.h: a row is flagged when its predicted
-# relative error exceeds 1e-6 at L = 3 and 2.5e-4 at L = 2); L = 1 has no residual set: rows without outliers only
-ROW_TOL = {3: EXACT_REL_FRO, 2: 1e-3, 1: INT8_REL_FRO_LARGE_K}
 LIM = {1: 127, 2: 127 * 256 + 127, 3: 127 * 65536 + 127 * 256 + 127}
 FQL_BWD_MAX_N = 132104
-
-
-def fro_tol(L, N):
-    """Frobenius bound of the mode; at L = 1 a contraction longer than 4096 gets the wider int8 bound (helpers.py)."""
-    if L == 1:
-        return INT8_REL_FRO_LARGE_K if N > 4096 else INT8_REL_FRO
-    return {3: EXACT_REL_FRO, 2: FAST_REL_FRO}[L]
 
 
 def check(name, got, ref, L, N, rows=None, cond=None):

@@ -34,7 +34,8 @@ import pytest
 import torch
 
 from helpers import (EXACT_REL_FRO, FAST_REL_FRO, FMA_REL_FRO, INT8_REL_FRO, INT8_REL_FRO_LARGE_K, FP8_ACC_REL_FRO, rel_fro,
-                     rel_fro_dev, dequant_f64, clipped_ranges, Guarded, guarded_like, assert_guards_intact, GUARD_BYTES)
+                     rel_fro_dev, dequant_f64, clipped_ranges, Guarded, guarded_like, assert_guards_intact, GUARD_BYTES,
+                     NAN, SENT, BIG, same_bits, first_diff, heavy_rows, footprint_table)
 from oracle import oracle as O
 from oracle import c_oracle as C
 
@@ -45,9 +46,6 @@ LIMBS = {"default": 3, "exact": 3, "fast": 2, "int8": 1, "fp8": 1}
 TOL = {"default": EXACT_REL_FRO, "exact": EXACT_REL_FRO, "fast": FAST_REL_FRO, "int8": INT8_REL_FRO, "fp8": FP8_ACC_REL_FRO}
 DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 DT_NAME = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}
-NAN = float("nan")
-SENT = -7.5                        # exact in float32, float16 and bfloat16; no result of these problems
-BIG = 0x7F7F7F7F                   # a table entry or index that is used sends a kernel far away
 WS_PATTERN = 0x5A
 PREFILLS = (0x00, 0xFF, 0x7F)
 K = 544
@@ -73,26 +71,6 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def first_diff(a, b):
-    d = (bits(a) != bits(b)).nonzero()
-    return int(d.shape[0]), (d[0].tolist() if d.shape[0] else None)
-
-
-def heavy_rows(x, rng, step=5, factor=800.0):
-    """Two channels x 800 in every fifth row (make_moe of tests/test_gpu_w4.py): flagged by the pre-pass at 2 / 3 limbs."""
-    for t in range(0, x.shape[0], step):
-        x[t, rng.choice(x.shape[1], 2, replace=False)] *= factor
-    return x
-
-
 # ------------------------------------------------------------------------------ problems (built once, never modified)
 class Problem:
     pass
@@ -102,18 +80,8 @@ class Problem:
 def moe_problem(name, N=None):
     p = Problem()
     rng = np.random.default_rng({"G1": 11, "G1c": 11, "G2": 12}[name] + (N or 0))
-    if name == "G2":
-        counts, tail, p.N = [129] + [1] * 16, 0, N or 72
-    else:
-        counts, tail, p.N = [129, 0, 1, 65, 33], 3, N or 200
-    p.name, p.E, p.K = name, len(counts), K
-    counts = np.array(counts, np.int32)
-    p.offs = (np.cumsum(counts) - counts).astype(np.int32)
-    p.T = int(counts.sum()) + tail
-    p.counts = counts.copy()                                # the table the device gets ...
-    if name == "G1c":
-        p.counts[-1] = 999                                  # ... input_offsets[4] + tokens_per_expert[4] > T: clipped on the device
-        assert p.offs[-1] + p.counts[-1] > p.T
+    p.counts, p.offs, p.T = footprint_table(name)           # (the table the device gets: G1c is clipped there)
+    p.name, p.E, p.K, p.N = name, len(p.counts), K, N or (72 if name == "G2" else 200)
     ranges = clipped_ranges(torch.from_numpy(p.counts), torch.from_numpy(p.offs), p.T)
     p.ref_counts = np.array([hi - lo for lo, hi in ranges], np.int32)     # ... and the one the oracle gets
     p.ref_offs = np.array([lo for lo, hi in ranges], np.int32)

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from conftest import ROOT  # noqa: F401
-from helpers import EXACT_REL_FRO, FAST_REL_FRO, rel_fro
+from helpers import EXACT_REL_FRO, FAST_REL_FRO, rel_fro, tol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -19,10 +19,6 @@ def fq():
 def ops():
     from fused_int4_amd import ops as o
     return o
-
-
-def tol(base):
-    return max(base, 1e-5)
 
 
 def w64(packed, scales, zps):

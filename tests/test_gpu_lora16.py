@@ -9,13 +9,12 @@ import pytest
 import torch
 
 from conftest import ROOT  # noqa: F401
-from helpers import EXACT_REL_FRO, dequant_f64, expert_table, rel_fro_dev
+from helpers import F32_TOL, dequant_f64, expert_table, rel_fro_dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTYPES = [torch.float16, torch.bfloat16]
 UNIT = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-F32_TOL = max(EXACT_REL_FRO, 1e-5)                    # tests/test_gpu_lora.py: tol(EXACT_REL_FRO)
 TABLE = dict(counts=[7, 0, 33, 1, 20, 64], gaps=[0, 2, 0, 5, 0, 1], tail=3)    # empty expert, gaps, uncovered tail
 
 

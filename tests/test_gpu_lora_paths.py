@@ -11,14 +11,13 @@ import pytest
 import torch
 
 from conftest import ROOT  # noqa: F401
-from helpers import (EXACT_REL_FRO, FMA_REL_FRO, clipped_ranges, dequant_f64, expert_table, fq, misaligned,
+from helpers import (ADAPTER_TOL, EXACT_REL_FRO, FMA_REL_FRO, clipped_ranges, dequant_f64, expert_table, fq, misaligned,
                      ops, rel_fro_dev, row_rel_err)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-# adapter terms alone: float32 FMA chains (summation order only); outputs that include the INT4 GEMM: its exact-mode
-# bound as well
-ADAPTER_TOL = FMA_REL_FRO
+# adapter terms alone: float32 FMA chains (summation order only: helpers.ADAPTER_TOL); outputs that include the INT4 GEMM:
+# its exact-mode bound as well
 LAYER_TOL = EXACT_REL_FRO + FMA_REL_FRO
 
 
