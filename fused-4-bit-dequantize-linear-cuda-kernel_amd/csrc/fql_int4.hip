@@ -18,7 +18,6 @@
 #include "fql_quantize.h"
 #include "fql_routing.h"
 #include "fql_router.h"
-#include "fql_router_score.h"
 #include "fql_w4_launch.h"
 #include "fql_ffn16_launch.h"
 #include <atomic>
@@ -625,7 +624,32 @@ int router_score_shape_check(int dtype, int T, int E, int top_k, int scoring, in
     return FQL_OK;
 }
 
-// The typed combine's element types: f(std::integral_constant<int, kind>) for a code that valid_dtype() has accepted
+// One launch of the router for arguments the entry points have checked.  The plain rule (softmax, no bias, one group,
+// scale 1) takes the forward instantiation that has the other rules compiled out: the same bits, fewer registers.
+int launch_router_fwd(const void *logits, int dtype, int T, int E, int top_k, int scoring, const float *select_bias,
+                      int n_group, int topk_group, int group_top, int renormalize, float scale, int32_t *indices,
+                      float *weights, float *scores, hipStream_t st)
+{
+    const bool plain = scoring == 0 && select_bias == nullptr && n_group == 1 && scale == 1.0f;
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(plain ? router_topk_fwd_kernel<G.value, NPL.value, false> : router_topk_fwd_kernel<G.value, NPL.value, true>,
+                      dim3(blocks), dim3(ROUTER_THREADS), 0, st, logits, dtype, T, E, top_k, scoring, select_bias, n_group,
+                      topk_group, group_top, renormalize, scale, indices, weights, scores);
+    });
+}
+int launch_router_bwd(const void *logits, int dtype, const int32_t *indices, const float *grad_weights,
+                      const float *grad_scores, void *grad_logits, int T, int E, int top_k, int scoring, int renormalize,
+                      float scale, hipStream_t st)
+{
+    return with_router_group(E, [&](auto G, auto NPL) {
+        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
+        return launch(router_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0, st, logits, dtype,
+                      indices, grad_weights, grad_scores, grad_logits, T, E, top_k, scoring, renormalize, scale);
+    });
+}
+
+// The combine's element types: f(std::integral_constant<int, kind>) for a code that valid_dtype() has accepted
 template <class F>
 int with_dtype(int dt, F &&f)
 {
@@ -634,6 +658,30 @@ int with_dtype(int dt, F &&f)
     return f(std::integral_constant<int, FQL_DTYPE_F32>{});
 }
 bool elem_aligned(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+
+// One launch of the combine / of its backward for arguments the entry points have checked (T <= 65535: grid.y)
+int launch_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
+                   const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, hipStream_t st)
+{
+    const unsigned cols = in_dtype == FQL_DTYPE_F32 ? 1024 : 2048;       // 256 threads x 16 bytes of the input type
+    return with_dtype(in_dtype, [&](auto ik) {
+        return with_dtype(out_dtype, [&](auto ok) {
+            return launch(combine_kernel<ik.value, ok.value>, dim3((N + cols - 1) / cols, T), dim3(256), 0, st, y, pos_of_slot,
+                          weights, addend, addend_weight, out, T, top_k, N, R);
+        });
+    });
+}
+int launch_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
+                       const void *addend, const float *addend_weight, int in_dtype, void *grad_y, float *grad_weights,
+                       void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, hipStream_t st)
+{
+    return with_dtype(in_dtype, [&](auto ik) {
+        return with_dtype(out_dtype, [&](auto ok) {
+            return launch(combine_bwd_kernel<ik.value, ok.value>, dim3(T), dim3(256), 0, st, grad_out, y, pos_of_slot, weights,
+                          addend, addend_weight, grad_y, grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows);
+        });
+    });
+}
 
 }  // namespace
 
@@ -1112,9 +1160,8 @@ int fql_combine_f32(const float *y, const int32_t *pos_of_slot, const float *wei
     if (T == 0 || N == 0) return FQL_OK;
     if (!y || !pos_of_slot || !out || R == 0) return FQL_ERR_NULL_POINTER;      // weights == NULL: rows already weighted, pure gather-add
     if (T > 65535) return FQL_ERR_BAD_SHAPE;                 // grid.y
-    hipLaunchKernelGGL(combine_kernel, dim3((N + 1023) / 1024, T), dim3(256), 0, static_cast<hipStream_t>(stream), y,
-                       pos_of_slot, weights, out, T, top_k, N, R);
-    return launched();
+    return launch_combine(y, FQL_DTYPE_F32, pos_of_slot, weights, nullptr, nullptr, out, FQL_DTYPE_F32, T, top_k, N, R,
+                          static_cast<hipStream_t>(stream));
 }
 
 int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *pos_of_slot, const float *weights,
@@ -1127,13 +1174,12 @@ int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *po
     if (N > 0 && (!grad_out || !grad_y)) return FQL_ERR_NULL_POINTER;
     if (grad_weights != nullptr && N > 0 && !y) return FQL_ERR_NULL_POINTER;
     if (N == 0 && grad_weights == nullptr) return FQL_OK;
-    hipLaunchKernelGGL(combine_bwd_kernel, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream), grad_out, y,
-                       pos_of_slot, weights, grad_y, grad_weights, T, top_k, N, rows);
-    return launched();
+    return launch_combine_bwd(grad_out, FQL_DTYPE_F32, y, pos_of_slot, weights, nullptr, nullptr, FQL_DTYPE_F32, grad_y,
+                              grad_weights, nullptr, nullptr, T, top_k, N, rows, static_cast<hipStream_t>(stream));
 }
 
 // fql_combine_f32 with an element type for y / addend and one for out, and an optional weighted addend behind the slot
-// terms (csrc/fql_routing.h, combine_any_kernel).  The order of the return codes is part of the ABI (include/fql_int4.h).
+// terms (csrc/fql_routing.h, combine_kernel).  The order of the return codes is part of the ABI (include/fql_int4.h).
 int fql_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
                 const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream)
 {
@@ -1147,16 +1193,8 @@ int fql_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const f
     if (!elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(out, ob) || !elem_aligned(pos_of_slot, 4) ||
         !elem_aligned(weights, 4) || !elem_aligned(addend_weight, 4))
         return FQL_ERR_ALIGNMENT;
-    if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32 && addend == nullptr)
-        return fql_combine_f32(static_cast<const float *>(y), pos_of_slot, weights, static_cast<float *>(out), T, top_k, N, R,
-                               stream);
-    const unsigned cols = in_dtype == FQL_DTYPE_F32 ? 1024 : 2048;       // 256 threads x 16 bytes of the input type
-    return with_dtype(in_dtype, [&](auto ik) {
-        return with_dtype(out_dtype, [&](auto ok) {
-            return launch(combine_any_kernel<ik.value, ok.value>, dim3((N + cols - 1) / cols, T), dim3(256), 0,
-                          static_cast<hipStream_t>(stream), y, pos_of_slot, weights, addend, addend_weight, out, T, top_k, N, R);
-        });
-    });
+    return launch_combine(y, in_dtype, pos_of_slot, weights, addend, addend_weight, out, out_dtype, T, top_k, N, R,
+                          static_cast<hipStream_t>(stream));
 }
 
 int fql_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
@@ -1175,17 +1213,9 @@ int fql_combine_bwd(const void *grad_out, int out_dtype, const void *y, const in
         !elem_aligned(grad_addend, ib) || !elem_aligned(pos_of_slot, 4) || !elem_aligned(weights, 4) ||
         !elem_aligned(addend_weight, 4) || !elem_aligned(grad_weights, 4) || !elem_aligned(grad_addend_weight, 4))
         return FQL_ERR_ALIGNMENT;
-    if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32 && !addend && !addend_weight && !grad_addend &&
-        !grad_addend_weight)
-        return fql_combine_bwd_f32(static_cast<const float *>(grad_out), static_cast<const float *>(y), pos_of_slot, weights,
-                                   static_cast<float *>(grad_y), grad_weights, T, top_k, N, rows, stream);
-    return with_dtype(in_dtype, [&](auto ik) {
-        return with_dtype(out_dtype, [&](auto ok) {
-            return launch(combine_any_bwd_kernel<ik.value, ok.value>, dim3(T), dim3(256), 0, static_cast<hipStream_t>(stream),
-                          grad_out, y, pos_of_slot, weights, addend, addend_weight, grad_y, grad_weights, grad_addend,
-                          grad_addend_weight, T, top_k, N, rows);
-        });
-    });
+    return launch_combine_bwd(grad_out, out_dtype, y, pos_of_slot, weights, addend, addend_weight, in_dtype, grad_y,
+                              grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows,
+                              static_cast<hipStream_t>(stream));
 }
 
 int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int renormalize, int32_t *indices,
@@ -1194,11 +1224,8 @@ int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int 
     if (const int rc = router_shape_check(logits_dtype, T, E, top_k)) return rc;
     if (T == 0) return FQL_OK;
     if (!logits || !indices || !weights) return FQL_ERR_NULL_POINTER;                 // probs == NULL: not wanted
-    return with_router_group(E, [&](auto G, auto NPL) {
-        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
-        return launch(router_topk_fwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
-                      static_cast<hipStream_t>(stream), logits, logits_dtype, T, E, top_k, renormalize, indices, weights, probs);
-    });
+    return launch_router_fwd(logits, logits_dtype, T, E, top_k, 0, nullptr, 1, 1, 1, renormalize, 1.0f, indices, weights, probs,
+                             static_cast<hipStream_t>(stream));
 }
 
 int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
@@ -1207,12 +1234,8 @@ int fql_router_topk_bwd(const void *logits, int logits_dtype, const int32_t *ind
     if (const int rc = router_shape_check(logits_dtype, T, E, top_k)) return rc;
     if (T == 0) return FQL_OK;
     if (!logits || !indices || !grad_logits) return FQL_ERR_NULL_POINTER;             // either gradient may be NULL
-    return with_router_group(E, [&](auto G, auto NPL) {
-        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
-        return launch(router_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
-                      static_cast<hipStream_t>(stream), logits, logits_dtype, indices, grad_weights, grad_probs, grad_logits, T,
-                      E, top_k, renormalize);
-    });
+    return launch_router_bwd(logits, logits_dtype, indices, grad_weights, grad_probs, grad_logits, T, E, top_k, 0, renormalize,
+                             1.0f, static_cast<hipStream_t>(stream));
 }
 
 int fql_router_score_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int scoring,
@@ -1223,12 +1246,8 @@ int fql_router_score_topk_fwd(const void *logits, int logits_dtype, int T, int E
         return rc;
     if (T == 0) return FQL_OK;
     if (!logits || !indices || !weights) return FQL_ERR_NULL_POINTER;     // select_bias, scores == NULL: none / not wanted
-    return with_router_group(E, [&](auto G, auto NPL) {
-        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
-        return launch(router_score_topk_fwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
-                      static_cast<hipStream_t>(stream), logits, logits_dtype, T, E, top_k, scoring, select_bias, n_group,
-                      topk_group, group_top, renormalize, scale, indices, weights, scores);
-    });
+    return launch_router_fwd(logits, logits_dtype, T, E, top_k, scoring, select_bias, n_group, topk_group, group_top,
+                             renormalize, scale, indices, weights, scores, static_cast<hipStream_t>(stream));
 }
 
 int fql_router_score_topk_bwd(const void *logits, int logits_dtype, const int32_t *indices, const float *grad_weights,
@@ -1238,12 +1257,8 @@ int fql_router_score_topk_bwd(const void *logits, int logits_dtype, const int32_
     if (const int rc = router_score_shape_check(logits_dtype, T, E, top_k, scoring, 1, 1, 1, scale)) return rc;
     if (T == 0) return FQL_OK;
     if (!logits || !indices || !grad_logits) return FQL_ERR_NULL_POINTER;             // either gradient may be NULL
-    return with_router_group(E, [&](auto G, auto NPL) {
-        const unsigned blocks = (unsigned)(((long long)T + ROUTER_THREADS / G.value - 1) / (ROUTER_THREADS / G.value));
-        return launch(router_score_topk_bwd_kernel<G.value, NPL.value>, dim3(blocks), dim3(ROUTER_THREADS), 0,
-                      static_cast<hipStream_t>(stream), logits, logits_dtype, indices, grad_weights, grad_scores,
-                      grad_logits, T, E, top_k, scoring, renormalize, scale);
-    });
+    return launch_router_bwd(logits, logits_dtype, indices, grad_weights, grad_scores, grad_logits, T, E, top_k, scoring,
+                             renormalize, scale, static_cast<hipStream_t>(stream));
 }
 
 int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,

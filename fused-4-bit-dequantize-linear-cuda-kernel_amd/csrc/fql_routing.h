@@ -6,11 +6,10 @@
 //                        exclusive prefix (= tokens_per_expert / input_offsets of the grouped GEMM), for every
 //                        sorted position the token row it reads (the gather index of fql_moe_gather_fwd_f32) and
 //                        for every slot its sorted position (the un-sort index of the combine).
-//   combine_kernel       out[t][:] = sum_k w[t][k] * y[pos[t][k]][:]  (k ascending), 16-byte loads and stores.
-//   combine_bwd_kernel   its gradients to y and to w, in one launch.
-//   combine_any_kernel   the combine with an element type for y and one for out (float32 / float16 / bfloat16) and an
-//                        optional per-token weighted addend (a shared expert's rows) behind the slot terms.
-//   combine_any_bwd_kernel  its gradients to y, w, the addend and the addend's weight, in one launch.
+//   combine_kernel       out[t][:] = sum_k w[t][k] * y[pos[t][k]][:]  (k ascending) + an optional per-token weighted
+//                        addend (a shared expert's rows), with an element type for y and one for out (float32 /
+//                        float16 / bfloat16), accesses of up to 16 bytes.
+//   combine_bwd_kernel   its gradients to y, w, the addend and the addend's weight, in one launch.
 //   regroup_index_kernel expert-parallel receive side: rows arrive (source rank, local expert)-major, the GEMM
 //                        wants (local expert, source rank)-major: gather index + its inverse + the expert table.
 #pragma once
@@ -69,73 +68,7 @@ __global__ __launch_bounds__(ROUTE_THREADS) void route_plan_kernel(
     }
 }
 
-// grid: (ceil(N / (4 * 256)), T); one thread = 4 consecutive columns of one token
-__global__ __launch_bounds__(256) void combine_kernel(
-    const float *__restrict__ y, const int32_t *__restrict__ pos_of_slot, const float *__restrict__ w,
-    float *__restrict__ out, int T, int top_k, int N, int R)
-{
-#pragma clang fp contract(off)                     // (y * w), THEN add, as the reference does: never an FMA
-    const int t = blockIdx.y;
-    const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (n >= N) return;
-    const bool vec = ((N & 3) == 0) && (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < top_k; ++k) {
-        int p = pos_of_slot[t * top_k + k];
-        p = p < 0 ? 0 : (p >= R ? R - 1 : p);
-        const float wk = w != nullptr ? w[t * top_k + k] : 1.0f;     // (x * 1 == x: the gather-add form keeps the bits of pre-weighted rows)
-        const float *row = y + (size_t)p * N + n;
-        if (vec) {
-            const v4f v = *reinterpret_cast<const v4f *>(row);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] = acc[c] + v[c] * wk;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) if (n + c < N) acc[c] = acc[c] + row[c] * wk;
-        }
-    }
-    float *orow = out + (size_t)t * N + n;
-    if (vec) *reinterpret_cast<v4f *>(orow) = v4f{acc[0], acc[1], acc[2], acc[3]};
-    else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) if (n + c < N) orow[c] = acc[c];
-    }
-}
-
-// Backward of combine_kernel, one workgroup per token t, no atomics (pos_of_slot is a permutation of the rows, so every
-// row of grad_y is written by exactly one slot):
-//   grad_y[pos[t][k]][:] = w[t][k] * grad_out[t][:]      (w == NULL: grad_out[t][:] itself)
-//   grad_w[t][k]         = <y[pos[t][k]][:], grad_out[t][:]>   (grad_w == NULL: skipped; fixed summation order)
-__global__ __launch_bounds__(256) void combine_bwd_kernel(
-    const float *__restrict__ gout, const float *__restrict__ y, const int32_t *__restrict__ pos_of_slot,
-    const float *__restrict__ w, float *__restrict__ gy, float *__restrict__ gw, int T, int top_k, int N, int R)
-{
-    __shared__ float s_part[4];
-    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *go = gout + (size_t)t * N;
-    for (int k = 0; k < top_k; ++k) {
-        int p = pos_of_slot[(size_t)t * top_k + k];
-        p = p < 0 ? 0 : (p >= R ? R - 1 : p);
-        const float wk = w != nullptr ? w[(size_t)t * top_k + k] : 1.0f;
-        const float *yr = y + (size_t)p * N;
-        float *gyr = gy + (size_t)p * N;
-        float dot = 0.0f;
-        for (int n = tid; n < N; n += 256) {
-            const float g = go[n];
-            gyr[n] = w != nullptr ? wk * g : g;
-            if (gw != nullptr) dot = fmaf(yr[n], g, dot);
-        }
-        if (gw != nullptr) {
-            dot = wave_sum(dot);
-            if (lane == 0) s_part[wave] = dot;
-            __syncthreads();
-            if (tid == 0) gw[(size_t)t * top_k + k] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-            __syncthreads();
-        }
-    }
-}
-
-// ---- the typed combine.  KIND is an FQL_DTYPE_* code: 0 float32, 1 float16, 2 bfloat16.  16-bit
+// ---- the combine.  KIND is an FQL_DTYPE_* code: 0 float32, 1 float16, 2 bfloat16.  16-bit
 //      elements are widened in registers on load (exact) and rounded once, to nearest even, on store.
 template <int KIND> struct CombElem { using type = unsigned short; };
 template <> struct CombElem<0> { using type = float; };
@@ -234,15 +167,15 @@ struct CombRow {
 };
 
 // out[t][n] = round_out( (...((0 + y[p_0][n] * w_0) + y[p_1][n] * w_1)...) + addend[t][n] * aw[t] ): the slot terms are
-// combine_kernel's (float32, multiply then add, k ascending, pos clamped, w == NULL: 1), the addend term comes last
-// (addend == NULL: none; aw == NULL: 1, and x * 1 == x keeps the bits of "+ addend").
+// float32, multiply then add, k ascending, pos clamped to [0, R) (w == NULL: 1, and x * 1 == x: the gather-add form keeps
+// the bits of pre-weighted rows); the addend term comes last (addend == NULL: none; aw == NULL: 1, the bits of "+ addend").
 // grid: (ceil(N / (V * 256)), T); one thread = V consecutive columns of one token, V = 16 bytes of the input type.
 template <int IK, int OK>
-__global__ __launch_bounds__(256) void combine_any_kernel(
+__global__ __launch_bounds__(256) void combine_kernel(
     const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot, const float *__restrict__ w,
     const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ out_, int T, int top_k, int N, int R)
 {
-#pragma clang fp contract(off)                     // (y * w), THEN add, as combine_kernel does: never an FMA
+#pragma clang fp contract(off)                     // (y * w), THEN add, as the reference does: never an FMA
     constexpr int V = IK == 0 ? 4 : 8;
     using In = CombRow<IK, V>;
     using Out = CombRow<OK, V>;
@@ -274,15 +207,16 @@ __global__ __launch_bounds__(256) void combine_any_kernel(
     Out::store(out + (size_t)t * N + n, omode, left, acc);
 }
 
-// Backward of combine_any_kernel, one workgroup per token t, no atomics; gout has the type OK, y / addend / gy / gaddend
-// the type IK, gw and gaw are float32.  The column-to-thread mapping and the reduction are combine_bwd_kernel's, so the
-// dot products have its bits:
+// Backward of combine_kernel, one workgroup per token t, no atomics (pos_of_slot is a permutation of the rows, so every
+// row of gy is written by exactly one slot); gout has the type OK, y / addend / gy / gaddend the type IK, gw and gaw are
+// float32.  The dot products have a fixed summation order: fmaf over n = tid, tid + 256, ..., wave_sum, then the four
+// wave partials as (0 + 1) + (2 + 3):
 //   gy[pos[t][k]][:] = round_in(w[t][k] * gout[t][:])         (w == NULL: gout[t][:] itself)
 //   gw[t][k]         = <y[pos[t][k]][:], gout[t][:]>          (gw == NULL: skipped)
 //   gaddend[t][:]    = round_in(aw[t] * gout[t][:])           (gaddend == NULL: skipped; aw == NULL: gout[t][:] itself)
 //   gaw[t]           = <addend[t][:], gout[t][:]>             (gaw == NULL: skipped)
 template <int IK, int OK>
-__global__ __launch_bounds__(256) void combine_any_bwd_kernel(
+__global__ __launch_bounds__(256) void combine_bwd_kernel(
     const void *__restrict__ gout_, const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot,
     const float *__restrict__ w, const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ gy_,
     float *__restrict__ gw, void *__restrict__ gaddend_, float *__restrict__ gaw, int T, int top_k, int N, int R)

@@ -367,9 +367,9 @@ class QuantizedSparseMoEBlock(nn.Module):
     The routing rule is Mixtral's by default.  ``scoring="sigmoid"``, ``n_group`` / ``topk_group`` / ``group_top``
     (group-limited selection), ``routed_scaling_factor`` and ``selection_bias=True`` (a float32 buffer
     ``gate.e_score_correction_bias`` [E] of zeros, added to the scores for the selection only and moved by
-    ``update_selection_bias``) select the rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4: any of them sends the
-    forward through ``ops.router_score_topk``; with all at their defaults it calls
-    ``ops.router_topk`` as before and the state-dict keys are unchanged."""
+    ``update_selection_bias``) select the rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4 (INTEGRATION.md
+    section 11).  The forward makes one ``ops.router_score_topk`` call either way: with all at their defaults that is
+    ``ops.router_topk``, bit for bit and kernel for kernel, and the state-dict keys are unchanged."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
@@ -460,7 +460,7 @@ class QuantizedSparseMoEBlock(nn.Module):
 
     @property
     def scored_routing(self) -> bool:
-        """Whether any routing setting differs from Mixtral's: the forward then runs ``ops.router_score_topk``."""
+        """Whether any routing setting differs from Mixtral's (the router then runs its scored kernel variant)."""
         return (self.scoring != "softmax" or self.n_group != 1 or self.routed_scaling_factor != 1.0
                 or self.selection_bias is not None)
 
@@ -513,13 +513,9 @@ class QuantizedSparseMoEBlock(nn.Module):
         # part, so x.grad is two additions over three parts (dispatch, shared expert, gates) with or without the shared gate.
         x_gate = x2.view_as(x2) if getattr(self, "shared_expert_gate", None) is not None else x2
         logits = self.router_logits(x_gate)
-        if self.scored_routing:
-            weights, indices, *probs = ops.router_score_topk(
-                logits, self.top_k, self.scoring, self.selection_bias, self.n_group, self.topk_group, self.group_top,
-                self.renormalize, self.routed_scaling_factor, return_scores=torch.is_grad_enabled())
-        else:
-            weights, indices, *probs = ops.router_topk(logits, self.top_k, self.renormalize,
-                                                       return_probs=torch.is_grad_enabled())
+        weights, indices, *probs = ops.router_score_topk(
+            logits, self.top_k, self.scoring, self.selection_bias, self.n_group, self.topk_group, self.group_top,
+            self.renormalize, self.routed_scaling_factor, return_scores=torch.is_grad_enabled())
         tpe, offs, token_of_sorted, pos_of_slot = ops.route_plan(indices, self.num_experts)
         self.routing = (probs[0] if probs else None, tpe, indices)
         rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)

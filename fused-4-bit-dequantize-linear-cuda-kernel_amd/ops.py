@@ -421,8 +421,21 @@ def route_plan(expert_indices, num_experts):
     return counts, offsets, token_of_sorted, pos_of_slot
 
 
-def _combine_operands(y, pos_of_slot, expert_weights, top_k):
-    """``(T, top_k, pos int32, weights float32 or None)`` of ``combine`` and its backward, on ``y``'s device."""
+def combine(y, pos_of_slot, expert_weights, top_k=None):
+    """out[t] = sum_k expert_weights[t, k] * y[pos_of_slot[t*top_k + k]] in one launch (routing.py:172-189), on float32
+    rows: ``combine_any`` without an addend.  ``expert_weights=None`` (with ``top_k``): the rows already carry their
+    weights -- a pure gather-add.  Under autograd the gradients to ``y`` and ``expert_weights`` come from one backward
+    launch."""
+    if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 2:
+        raise RuntimeError("y must be a CUDA float32 [rows, N] tensor")
+    return combine_any(y, pos_of_slot, expert_weights, top_k)
+
+
+def _combine_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight):
+    """``(T, top_k, pos int32, weights float32 or None, addend contiguous, addend_weight float32 [T] contiguous)`` of the
+    combine and its backward, on ``y``'s device."""
+    if not y.is_cuda or y.dtype not in _DTYPES or y.dim() != 2:
+        raise RuntimeError("y must be a CUDA float32, float16 or bfloat16 [rows, N] tensor")
     if expert_weights is None:
         if not top_k:
             raise RuntimeError("top_k is needed when the rows carry their weights")
@@ -433,30 +446,7 @@ def _combine_operands(y, pos_of_slot, expert_weights, top_k):
     if pos_of_slot.numel() < T * top_k:
         raise RuntimeError("pos_of_slot must have tokens * top_k elements")
     w = None if expert_weights is None else expert_weights.to(dtype=torch.float32).contiguous()
-    return T, top_k, pos_of_slot.to(dtype=torch.int32).contiguous(), w
-
-
-def combine(y, pos_of_slot, expert_weights, top_k=None):
-    """out[t] = sum_k expert_weights[t, k] * y[pos_of_slot[t*top_k + k]] in one launch (routing.py:172-189).
-    ``expert_weights=None`` (with ``top_k``): the rows already carry their weights -- a pure gather-add.
-    Under autograd the gradients to ``y`` and ``expert_weights`` come from one backward launch."""
-    if _wants_grad(y, expert_weights):
-        return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k)
-    if not y.is_cuda or y.dtype != torch.float32 or y.dim() != 2:
-        raise RuntimeError("y must be a CUDA float32 [rows, N] tensor")
-    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
-    if T > 65535:
-        raise RuntimeError("combine handles up to 65535 tokens per call")
-    out = torch.empty((T, y.shape[1]), dtype=torch.float32, device=y.device)
-    _launch("fql_combine_f32", y.device, y.contiguous(), pos, w, out, T, top_k, y.shape[1], y.shape[0])
-    return out
-
-
-def _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight):
-    """``_combine_operands`` for the typed combine, plus ``(addend contiguous, addend_weight float32 [T] contiguous)``."""
-    if not y.is_cuda or y.dtype not in _DTYPES or y.dim() != 2:
-        raise RuntimeError("y must be a CUDA float32, float16 or bfloat16 [rows, N] tensor")
-    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
+    pos = pos_of_slot.to(dtype=torch.int32).contiguous()
     _on(y.device, addend=addend, addend_weight=addend_weight)
     if addend is None:
         if addend_weight is not None:
@@ -486,11 +476,11 @@ def combine_any(y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_
     ``addend_weight`` come from one backward launch (``combine_any_backward``); ``y`` and ``addend`` are saved in their
     own type."""
     if _wants_grad(y, expert_weights, addend, addend_weight):
-        return _CombineAnyFn.apply(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
-    T, top_k, pos, w, addend, aw = _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
+        return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
+    T, top_k, pos, w, addend, aw = _combine_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
     out_dtype = _combine_out_dtype(out_dtype, y.dtype)
     if T > 65535:
-        raise RuntimeError("combine_any handles up to 65535 tokens per call")
+        raise RuntimeError("combine handles up to 65535 tokens per call")
     out = torch.empty((T, y.shape[1]), dtype=out_dtype, device=y.device)
     _launch("fql_combine", y.device, y.contiguous(), _DTYPES[y.dtype], pos, w, addend, aw, out, _DTYPES[out_dtype], T, top_k,
             y.shape[1], y.shape[0])
@@ -519,36 +509,15 @@ def router_topk(logits, top_k, renormalize=True, return_probs=False):
     float32 (the full softmax, for a load-balancing loss) with ``return_probs``.  Selection is on the logits, ties to the
     lower expert id; ``renormalize`` divides the selected probabilities by their sum (Mixtral).  ``indices`` is what
     ``route_plan`` reads, ``weights`` what ``combine`` reads.  A row with a non-finite logit gets NaN weights and indices
-    0 .. top_k-1.  Under autograd the gradients of ``weights`` and ``probs`` reach ``logits`` in one backward launch."""
-    if _wants_grad(logits):
-        out = _RouterTopkFn.apply(logits, top_k, bool(renormalize), bool(return_probs))
-        return out if return_probs else out[:2]
-    logits, T, E = _router_operands(logits, top_k)
-    dev = logits.device
-    indices = torch.empty((T, top_k), dtype=torch.int32, device=dev)
-    weights = torch.empty((T, top_k), dtype=torch.float32, device=dev)
-    probs = torch.empty((T, E), dtype=torch.float32, device=dev) if return_probs else None
-    _launch("fql_router_topk_fwd", dev, logits, _DTYPES[logits.dtype], T, E, top_k, int(bool(renormalize)), indices, weights,
-            probs)
-    return (weights, indices, probs) if return_probs else (weights, indices)
+    0 .. top_k-1.  Under autograd the gradients of ``weights`` and ``probs`` reach ``logits`` in one backward launch.
+    This is ``router_score_topk`` at its defaults, which the library runs with the other routing rules compiled out."""
+    return router_score_topk(logits, top_k, renormalize=renormalize, return_scores=return_probs)
 
 
 def router_topk_backward(logits, indices, grad_weights, grad_probs, renormalize=True):
     """Gradient of ``router_topk`` to ``logits`` (in their type, rounded once) from the gradients of ``weights`` and / or
     ``probs`` (float32; either may be None), one launch, no atomics."""
-    top_k = indices.shape[1]
-    logits, T, E = _router_operands(logits, top_k)
-    dev = logits.device
-    _on(dev, indices=indices, grad_weights=grad_weights, grad_probs=grad_probs)
-    if tuple(indices.shape) != (T, top_k) or (grad_weights is not None and tuple(grad_weights.shape) != (T, top_k)) \
-            or (grad_probs is not None and tuple(grad_probs.shape) != (T, E)):
-        raise RuntimeError("indices and grad_weights must be [tokens, top_k], grad_probs [tokens, num_experts]")
-    gw = None if grad_weights is None else grad_weights.to(dtype=torch.float32).contiguous()
-    gp = None if grad_probs is None else grad_probs.to(dtype=torch.float32).contiguous()
-    grad_logits = torch.empty_like(logits)
-    _launch("fql_router_topk_bwd", dev, logits, _DTYPES[logits.dtype], indices.to(dtype=torch.int32).contiguous(), gw, gp,
-            grad_logits, T, E, top_k, int(bool(renormalize)))
-    return grad_logits
+    return router_score_topk_backward(logits, indices, grad_weights, grad_probs, renormalize=renormalize)
 
 
 ROUTER_MAX_GROUPS = 8
@@ -557,7 +526,7 @@ _SCORINGS = {"softmax": 0, "sigmoid": 1}
 
 def _router_score_settings(E, top_k, scoring, n_group=1, topk_group=1, group_top=1, scale=1.0):
     """``(scoring code, scale as a float)`` of ``router_score_topk`` and its backward; the limits of
-    csrc/fql_router_score.h raise here."""
+    csrc/fql_router.h raise here."""
     try:
         code = _SCORINGS[scoring]
     except (KeyError, TypeError):
@@ -585,12 +554,12 @@ def router_score_topk(logits, top_k, scoring="softmax", select_bias=None, n_grou
     biased scores; the weights are the unbiased scores of the chosen experts, divided by their sum (``renormalize``) and
     multiplied by ``scale`` (``routed_scaling_factor``).  Returns ``(weights [T, top_k] float32, indices [T, top_k]
     int32)``, plus ``scores`` [T, E] float32 with ``return_scores``.  Without a bias the selection is on the logits, ties
-    to the lower expert id; experts outside the chosen groups are never selected.  With the defaults the results are the
-    bits of ``router_topk``.  Under autograd the gradients of ``weights`` and ``scores`` reach ``logits`` in one backward
+    to the lower expert id; experts outside the chosen groups are never selected.  With the defaults this is
+    ``router_topk``.  Under autograd the gradients of ``weights`` and ``scores`` reach ``logits`` in one backward
     launch; the bias gets none."""
     if _wants_grad(logits):
-        out = _RouterScoreTopkFn.apply(logits, top_k, scoring, select_bias, n_group, topk_group, group_top,
-                                       bool(renormalize), scale, bool(return_scores))
+        out = _RouterTopkFn.apply(logits, top_k, scoring, select_bias, n_group, topk_group, group_top,
+                                  bool(renormalize), scale, bool(return_scores))
         return out if return_scores else out[:2]
     logits, T, E = _router_operands(logits, top_k)
     code, scale = _router_score_settings(E, top_k, scoring, n_group, topk_group, group_top, scale)
@@ -960,15 +929,8 @@ def group_backward_input(grad_out, packed_weights, scales, zero_points):
 def combine_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, need_weights=True):
     """Gradients of ``combine``: ``(grad_y [R, N], grad_weights [T, top_k] or None)`` in one launch, no atomics.
     Rows of ``y`` that no slot names get zero."""
-    dev = y.device
-    _on(dev, grad_out=grad_out)
-    T, top_k, pos, w = _combine_operands(y, pos_of_slot, expert_weights, top_k)
-    R, N = y.shape
-    grad_y = (torch.empty if R == T * top_k else torch.zeros)((R, N), dtype=torch.float32, device=dev)
-    grad_w = torch.empty((T, top_k), dtype=torch.float32, device=dev) if (need_weights and w is not None) else None
-    _launch("fql_combine_bwd_f32", dev, grad_out.to(torch.float32).contiguous(), y.contiguous(), pos, w, grad_y, grad_w,
-            T, top_k, N, R)
-    return grad_y, grad_w
+    return combine_any_backward(grad_out.to(torch.float32), y, pos_of_slot, expert_weights, top_k,
+                                need_weights=need_weights)[:2]
 
 
 def combine_any_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None,
@@ -977,7 +939,7 @@ def combine_any_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, a
     [T, N], grad_addend_weight [T])``, None for what does not exist or is not needed.  ``grad_out`` [T, N] float32 /
     float16 / bfloat16 is read as it is; ``grad_y`` and ``grad_addend`` have ``y``'s type (rounded once), the two weight
     gradients are float32.  Rows of ``y`` that no slot names get zero."""
-    T, top_k, pos, w, addend, aw = _combine_any_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
+    T, top_k, pos, w, addend, aw = _combine_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
     dev = y.device
     R, N = y.shape
     _on(dev, grad_out=grad_out)
@@ -1053,25 +1015,8 @@ class _MoEFn(torch.autograd.Function):
 
 
 class _CombineFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, y, pos_of_slot, expert_weights, top_k):
-        ctx.save_for_backward(y, pos_of_slot, expert_weights)
-        ctx.top_k = top_k
-        return combine(y, pos_of_slot, expert_weights, top_k)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        y, pos, w = ctx.saved_tensors
-        need_w = w is not None and ctx.needs_input_grad[2]
-        gy, gw = combine_backward(gout, y, pos, w, ctx.top_k, need_weights=need_w)
-        if gw is not None and w.dtype != torch.float32:
-            gw = gw.to(w.dtype)
-        return gy, None, gw, None
-
-
-class _CombineAnyFn(torch.autograd.Function):
-    """``combine_any`` with its four gradients from one launch.  Saves ``y`` and ``addend`` in their own type."""
+    """``combine`` / ``combine_any`` with the four gradients from one launch.  Saves ``y`` and ``addend`` in their own
+    type."""
 
     @staticmethod
     def forward(ctx, y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype):
@@ -1092,27 +1037,8 @@ class _CombineAnyFn(torch.autograd.Function):
 
 
 class _RouterTopkFn(torch.autograd.Function):
-    """``router_topk`` with the gradient to the logits.  Saves the logits and the indices; the softmax is recomputed."""
-
-    @staticmethod
-    def forward(ctx, logits, top_k, renormalize, return_probs):
-        out = router_topk(logits.detach(), top_k, renormalize, return_probs)
-        ctx.save_for_backward(logits, out[1])
-        ctx.renormalize = renormalize
-        ctx.set_materialize_grads(False)                       # a gradient that does not exist arrives as None
-        ctx.mark_non_differentiable(out[1])
-        return out if return_probs else out + (None,)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_weights, _grad_indices, grad_probs):
-        logits, indices = ctx.saved_tensors
-        return router_topk_backward(logits, indices, grad_weights, grad_probs, ctx.renormalize), None, None, None
-
-
-class _RouterScoreTopkFn(torch.autograd.Function):
-    """``router_score_topk`` with the gradient to the logits.  Saves the logits and the indices; the scores are
-    recomputed."""
+    """``router_topk`` / ``router_score_topk`` with the gradient to the logits.  Saves the logits and the indices; the
+    scores are recomputed."""
 
     @staticmethod
     def forward(ctx, logits, top_k, scoring, select_bias, n_group, topk_group, group_top, renormalize, scale, return_scores):

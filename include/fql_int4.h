@@ -395,7 +395,7 @@ FQL_API int fql_router_topk_bwd(const void *logits, int logits_dtype, const int3
                                 void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * The scored router (csrc/fql_router_score.h): the routing rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4 in one
+ * The scored router (csrc/fql_router.h): the routing rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4 in one
  * launch, and the backward of that in one launch.  No workspace.  The thread mapping, the element types, the limits on
  * E and top_k and the outputs are those of fql_router_topk_fwd / _bwd above.
  *

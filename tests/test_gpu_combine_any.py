@@ -1,6 +1,7 @@
-"""ops.combine_any / ops.combine_any_backward (csrc/fql_routing.h: combine_any_kernel, combine_any_bwd_kernel) on the GPU.
+"""ops.combine_any / ops.combine_any_backward (csrc/fql_routing.h: combine_kernel, combine_bwd_kernel) on the GPU.
 
-Every reference is built from code the typed combine does not touch, and every comparison is bit for bit:
+Every reference is built from the float32 instantiation alone (``ops.combine`` / ``ops.combine_backward``) and torch's
+own casts and arithmetic, and every comparison is bit for bit:
 
   * no addend:    ``combine_any(y, ..., out_dtype=d) == ops.combine(y.float(), ...).to(d)`` (all float32: ``ops.combine``);
   * addend:       ``(ops.combine(y.float(), ...) + addend.float() * aw[:, None]).to(d)``: torch eager multiplies and adds in

@@ -1,4 +1,4 @@
-"""The scored router (csrc/fql_router_score.h, ops.router_score_topk) on the GPU: sigmoid / softmax scores, selection
+"""The scored router (csrc/fql_router.h, ops.router_score_topk) on the GPU: sigmoid / softmax scores, selection
 bias, group-limited selection, scaling factor.
 
 Two references, neither of them the kernel:
@@ -224,12 +224,17 @@ def test_defaults_are_the_bits_of_router_topk(ops, dtype):
         w0, i0, p0 = ops.router_topk(logits, k, renormalize=renormalize, return_probs=True)
         w1, i1, p1 = ops.router_score_topk(logits, k, renormalize=renormalize, return_scores=True)
         assert torch.equal(i0, i1) and same_bits(w0, w1) and same_bits(p0, p1), (T, E, k, renormalize)
+        # every group allowed and the key still the logit: the same rule through the scored kernel variant
+        d = next((n for n in range(2, 9) if E % n == 0), 1)           # (E = 1 has no such divisor: one group)
+        w2, i2, p2 = ops.router_score_topk(logits, k, n_group=d, topk_group=d, renormalize=renormalize, return_scores=True)
+        assert torch.equal(i0, i2) and same_bits(w0, w2) and same_bits(p0, p2), (T, E, k, renormalize, d)
         g = torch.Generator().manual_seed(T + E)
         gw, gp = torch.randn(T, k, generator=g).cuda(), torch.randn(T, E, generator=g).cuda()
         for a, b in ((gw, gp), (gw, None), (None, gp)):
             d0 = ops.router_topk_backward(logits, i0, a, b, renormalize=renormalize)
             d1 = ops.router_score_topk_backward(logits, i1, a, b, "softmax", renormalize, 1.0)
-            assert same_bits(d0, d1), (T, E, k, renormalize)
+            d2 = ops.router_score_topk_backward(logits, i2, a, b, "softmax", renormalize, 1.0)
+            assert same_bits(d0, d1) and same_bits(d0, d2), (T, E, k, renormalize)
 
 
 # ----------------------------------------------------------------------------------------------------------- backward

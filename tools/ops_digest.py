@@ -8,7 +8,13 @@ expert and four uncovered tail rows; per-group scales (K = 128, group 64) at B =
 path (K = 64) and on the widened fallback (K = 34); bias present and absent; 1-D and 2-D input; a misaligned float32 view
 as LoRA weight and as ``v`` (the ``clone()`` branches); LoRA ranks 4 and 64; C = 30, 34, 64 (vector widths 1, 2, 4);
 ``lora_expand`` in place and with ``out_dtype``; ``combine`` with and without weights; the LoRA layers and the gated FFN
-in float32, float16 and bfloat16 with every gradient and with the input gradient alone."""
+in float32, float16 and bfloat16 with every gradient and with the input gradient alone; the router at every group width
+(E = 1, 2, 5, 8, 60, 128: G = 1 .. 64, one and two experts per lane), top_k 1, 2 and 8, three logit types, renormalised or
+not, with a +inf row, an all-equal row and a row of mixed 0.0 / -0.0, each backward with both gradients and with either
+alone, ``router_score_topk`` at its defaults (the plain kernel variant) and with sigmoid + bias + groups + scale (the
+scored one); ``combine_any`` on four type pairs at N = 40 (16-byte accesses), 130 (pairs) and 129 (scalars), with and
+without the addend and its weight, and the float32 ``combine`` on a misaligned ``y``; ``QuantizedSparseMoEBlock`` with
+default and with scored routing, float32 and bfloat16, every gradient."""
 import argparse
 import hashlib
 import os
@@ -229,6 +235,67 @@ def calls(dev, fq, ops):
                 yield f"moe_ffn_lora_forward r{r} {dt} {'dx only' if only else 'all grads'}", lambda: with_grads(
                     layer, (x.to(dt), *ad), lambda y_: gy.to(y_.dtype), only)
 
+
+    # ---------------------------------------------------------------- the combine: misaligned float32, typed, addend
+    for N in (40, 130):                      # y four bytes off its alignment: no 16-byte access, at N = 130 pairs for out alone
+        ym, g = d.misaligned(d.randn(48, N)), d.randn(24, N)
+        yield f"combine misaligned N{N}", lambda: ops.combine(ym, pos, wts)
+        yield f"combine_backward misaligned N{N}", lambda: ops.combine_backward(g, ym, pos, wts)
+    for N in (40, 129, 130):
+        y, add, aw, g = d.randn(48, N), d.randn(24, N), d.randn(24), d.randn(24, N)
+        for di, do in ((F32, F32), (BF16, BF16), (BF16, F32), (F32, BF16)):
+            for tag, extra in (("", ()), (" addend", (add.to(di),)), (" weighted addend", (add.to(di), aw))):
+                yield f"combine_any N{N} {di}->{do}{tag}", lambda: ops.combine_any(y.to(di), pos, wts, None, *extra, out_dtype=do)
+                yield f"combine_any grad N{N} {di}->{do}{tag}", lambda: with_grads(
+                    lambda y_, w_, *e_: ops.combine_any(y_, pos, w_, None, *e_, out_dtype=do), (y.to(di), wts, *extra),
+                    lambda o_: g.to(o_.dtype))
+
+    # ---------------------------------------------------------------- the router: every group width, special rows
+    for Er in (1, 2, 5, 8, 60, 128):
+        base = d.randn(37, Er)
+        base[0, 0] = float("inf")
+        base[1] = 0.25
+        base[2, 0::2], base[2, 1::2] = 0.0, -0.0
+        bias = d.randn(Er, scale=0.1)
+        for k in (min(Er, 2),) + ((8,) if Er >= 8 else ()):
+            gw, gp = d.randn(37, k), d.randn(37, Er)
+            for dt in (F32, F16, BF16):
+                logits = base.to(dt)
+                for rn in (True, False):
+                    tag = f"E{Er} k{k} {dt} renormalize={rn}"
+                    yield f"router_topk {tag}", lambda: ops.router_topk(logits, k, renormalize=rn, return_probs=True)
+                    yield f"router_topk_backward {tag}", lambda: [
+                        ops.router_topk_backward(logits, ops.router_topk(logits, k, rn)[1], a, b, renormalize=rn)
+                        for a, b in ((gw, gp), (gw, None), (None, gp))]
+                    yield f"router_score_topk defaults {tag}", lambda: ops.router_score_topk(
+                        logits, k, renormalize=rn, return_scores=True)
+                    if Er in (8, 128) and 2 * (Er // 4) >= k:
+                        rule = dict(scoring="sigmoid", renormalize=rn, scale=2.5)
+                        yield f"router_score_topk scored {tag}", lambda: (out := ops.router_score_topk(
+                            logits, k, select_bias=bias, n_group=4, topk_group=2, return_scores=True, **rule)) + (
+                            ops.router_score_topk_backward(logits, out[1], gw, gp, **rule),)
+
+    # ---------------------------------------------------------------- the sparse MoE block, default and scored routing
+    Eb, H, F = 4, 64, 32
+    gup, gus, guz = d.weights(Eb, 2 * F, H)
+    dp, ds, dz = d.weights(Eb, H, F)
+    gate_w, x, gy = d.randn(Eb, H), d.randn(37, H), d.randn(37, H)
+    for tag, rule in (("default", {}), ("scored", dict(scoring="sigmoid", n_group=2, topk_group=1,
+                                                       routed_scaling_factor=2.5, selection_bias=True))):
+        for dt in (F32, BF16):
+            m = fq.QuantizedSparseMoEBlock(Eb, H, F, activation_dtype=None if dt == F32 else dt, **rule).to(dev)
+            for name, buf in zip(("gate_up_packed", "gate_up_scales", "gate_up_zero_points", "down_packed", "down_scales",
+                                  "down_zero_points"), (gup, gus, guz, dp, ds, dz)):
+                setattr(m.experts, name, buf)
+            m.gate.weight.data.copy_(gate_w)
+
+            def block(m=m, dt=dt):
+                x_ = x.detach().clone().to(dt).requires_grad_(True)
+                m.gate.weight.grad = None
+                out, logits = m(x_)
+                out.backward(gy.to(out.dtype))
+                return out.detach(), logits.detach(), x_.grad, m.gate.weight.grad
+            yield f"QuantizedSparseMoEBlock {tag} {dt}", block
 
 def digest(t):
     t = t.detach().contiguous().cpu()

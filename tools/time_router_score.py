@@ -1,4 +1,4 @@
-"""Scored-router timing: ops.router_score_topk (csrc/fql_router_score.h) against the torch chain it replaces, in one
+"""Scored-router timing: ops.router_score_topk (csrc/fql_router.h) against the torch chain it replaces, in one
 process, the contenders alternated after warm-up, device events around batches of calls, medians:
   fwd_fused   ops.router_score_topk(...)                                     one launch
   fwd_torch   the Hugging Face DeepSeek-V3 chain: sigmoid, add, view, topk, sum, topk, scatter, mask, topk, gather, sum,
