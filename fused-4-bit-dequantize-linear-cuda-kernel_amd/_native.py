@@ -24,6 +24,7 @@ PRECISION_FAST = 2
 PRECISION_EXACT = 3
 PRECISION_FP8 = 8
 LORA_RC, LORA_CR = 0, 1        # adapter weight layouts: [E][r][C] (lora_A) / [E][C][r] (lora_B)
+ACT_SILU, ACT_GELU_TANH, ACT_SWIGLU_CLAMP = 0, 1, 2      # activation kinds of the gated FFN experts (FQL_ACT_*)
 
 _SYMBOLS = {
     # name: (restype, argtypes)
@@ -103,6 +104,15 @@ _SYMBOLS = {
     "fql_lora_gated_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
                             + [ctypes.c_float, ctypes.c_void_p]),
     "fql_swiglu_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]),
+    "fql_moe_glu_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+                        + [ctypes.c_int] * 7 + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_lora_glu_shrink": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                            + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_int]
+                            + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
+    "fql_lora_glu_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
+                          + [ctypes.c_float, ctypes.c_int] + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
+    "fql_glu_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2
+                    + [ctypes.c_void_p]),
     "fql_router_topk_fwd": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4),
     "fql_router_topk_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4
                             + [ctypes.c_void_p]),

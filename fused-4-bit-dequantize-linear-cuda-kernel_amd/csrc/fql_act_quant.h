@@ -89,6 +89,8 @@ __device__ __forceinline__ float act_widen(unsigned short h)
 // second GEMM's pre-pass, so the [T, K] hidden activation is never materialised.
 // A 16-bit gate|up row is widened in registers first, so the limbs are those of the float32 call on the widened row.
 // (act_silu_mul itself lives in fql_common.h: the adapter kernels of fql_lora.h form the same h from the same function.)
+// GLU (with GATE): the value is act_glu_mul(kind, alpha, limit, gate[k], up[k]) instead, the kind and its two floats
+// wave-uniform kernel arguments (act_glu_kernel): GeGLU and the clamped SwiGLU, one instantiation for both.
 
 // ---- pieces shared by the pre-pass kernels (this file and fql_act_f8.h)
 // Coverage workgroups (MoE entry points only): zero-fill the rows of `out` no expert covers, 256 rows each
@@ -224,14 +226,21 @@ static __device__ unsigned long long fql_trace_act[16 * 16];   // (one copy per 
 // sum_k x[k] * cs_scale[e][k] * f[e][k], f = zp - clamp(rint(zp), -112, 112) (cs_zp = the zero points), is written to
 // the plane delta[DSETS * T + t] (the row-weight plane of the forward, unused by the backward).  The expert of each row is
 // looked up BEFORE the loads of x here (the loads need it).
-template <int L, bool VEC, int IN, bool GATE = false, bool F8OUT = false, int AR = ACT_ROWS, bool WT = false, bool CS = false>
+template <int L, bool VEC, int IN, bool GATE = false, bool F8OUT = false, int AR = ACT_ROWS, bool WT = false, bool CS = false, bool GLU = false>
 __device__ __forceinline__ void act_rows(
     const void *__restrict__ xin, const int32_t *__restrict__ gather, int n_src, float *__restrict__ delta,
     int32_t *__restrict__ rowsum, int8_t *__restrict__ limbs, int T, int K, int KB, int MBT, int rblocks,
     const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs, int E, const float *__restrict__ row_weight, int t0,
-    const float *__restrict__ cs_scale = nullptr, const float *__restrict__ cs_zp = nullptr)
+    const float *__restrict__ cs_scale = nullptr, const float *__restrict__ cs_zp = nullptr, int act_kind = 0,
+    float act_alpha = 0.0f, float act_limit = 0.0f)
 {
     (void)rblocks;
+    static_assert(!GLU || GATE, "an activation kind needs a gate|up row");
+    // the hidden activation of a gate|up pair: silu(g) * u, or (GLU) the kind the kernel was handed (fql_common.h)
+    auto gated_h = [&](float g, float u) {
+        if constexpr (GLU) return act_glu_mul(act_kind, act_alpha, act_limit, g, u);
+        else return act_silu_mul(g, u);
+    };
     constexpr int ES = (IN == 0) ? 4 : 2;
     // row_weight (optional): per grouped row, copied into the plane behind delta's set(s) for the GEMM's epilogue
     constexpr int DSETS = (L >= 2 && !F8OUT && FQL_RES_ENABLED) ? 2 : 1;         // bytes per element of x
@@ -295,7 +304,7 @@ __device__ __forceinline__ void act_rows(
                         const v4f gq = *reinterpret_cast<const v4f *>(src + 16 * q);
                         const v4f uq = *reinterpret_cast<const v4f *>(src + (size_t)K * 4 + 16 * q);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) xv[j][q][i] = act_silu_mul(gq[i], uq[i]);
+                        for (int i = 0; i < 4; ++i) xv[j][q][i] = gated_h(gq[i], uq[i]);
                     }
                 } else if (IN == 0) {
 #pragma unroll
@@ -308,9 +317,9 @@ __device__ __forceinline__ void act_rows(
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             xv[j][2 * h + (i >> 1)][2 * (i & 1)] =
-                                act_silu_mul(act_widen<IN>((unsigned short)((uint32_t)gr[i] & 0xFFFFu)), act_widen<IN>((unsigned short)((uint32_t)ur[i] & 0xFFFFu)));
+                                gated_h(act_widen<IN>((unsigned short)((uint32_t)gr[i] & 0xFFFFu)), act_widen<IN>((unsigned short)((uint32_t)ur[i] & 0xFFFFu)));
                             xv[j][2 * h + (i >> 1)][2 * (i & 1) + 1] =
-                                act_silu_mul(act_widen<IN>((unsigned short)((uint32_t)gr[i] >> 16)), act_widen<IN>((unsigned short)((uint32_t)ur[i] >> 16)));
+                                gated_h(act_widen<IN>((unsigned short)((uint32_t)gr[i] >> 16)), act_widen<IN>((unsigned short)((uint32_t)ur[i] >> 16)));
                         }
                     }
                 } else {                          // 16 halves = two 16-byte loads
@@ -346,9 +355,9 @@ __device__ __forceinline__ void act_rows(
                         const int k = k0 + 4 * q + i;
                         float v = 0.0f;
                         if (k < K) {
-                            if (IN == 0 && GATE) v = act_silu_mul(reinterpret_cast<const float *>(xr)[k], reinterpret_cast<const float *>(xr)[K + k]);
+                            if (IN == 0 && GATE) v = gated_h(reinterpret_cast<const float *>(xr)[k], reinterpret_cast<const float *>(xr)[K + k]);
                             else if (IN == 0) v = reinterpret_cast<const float *>(xr)[k];
-                            else if (GATE) v = act_silu_mul(act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]), act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[K + k]));
+                            else if (GATE) v = gated_h(act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]), act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[K + k]));
                             else v = act_widen<IN>(reinterpret_cast<const unsigned short *>(xr)[k]);
                             if constexpr (CS) {
                                 v = v * csr[k];
@@ -621,4 +630,22 @@ __global__ __launch_bounds__(256) void act_fused_kernel(
     }
     act_rows<L, VEC, IN, GATE, F8OUT, AR>(xin, gather, n_src, delta, rowsum, limbs, T, K, KB, MBT, rblocks, tpe, offs, E, row_weight,
                                           (int)blockIdx.x * AR);
+}
+
+// The gated pre-pass for an activation kind other than silu (FQL_ACT_GELU_TANH / FQL_ACT_SWIGLU_CLAMP): act_fused_kernel<L, VEC,
+// IN, GATE = true> with the kind and its two floats as arguments.  Instantiated in fql_glu.hip only.
+template <int L, bool VEC, int IN, int AR = ACT_ROWS>
+__global__ __launch_bounds__(256) void act_glu_kernel(
+    const void *__restrict__ xin, float *__restrict__ delta, int32_t *__restrict__ rowsum, int8_t *__restrict__ limbs, int T,
+    int K, int KB, int MBT, int rblocks, void *__restrict__ out, int out_es, int N, const int32_t *__restrict__ tpe,
+    const int32_t *__restrict__ offs, int E, const float *__restrict__ row_weight, int act_kind, float act_alpha,
+    float act_limit)
+{
+    if ((int)blockIdx.x >= rblocks) {             // ---- coverage workgroups: 256 rows of `out` each
+        act_zero_uncovered((int)blockIdx.x - rblocks, out, out_es, N, tpe, offs, E, T);
+        return;
+    }
+    act_rows<L, VEC, IN, true, false, AR, false, false, true>(xin, nullptr, 0, delta, rowsum, limbs, T, K, KB, MBT, rblocks, tpe, offs, E,
+                                                              row_weight, (int)blockIdx.x * AR, nullptr, nullptr, act_kind,
+                                                              act_alpha, act_limit);
 }

@@ -122,10 +122,68 @@ __device__ __forceinline__ void store_out4(void *out, int kind, size_t row_elems
     }
 }
 
-// Hidden activation of a gated FFN expert, h = silu(g) * u.  ONE definition for every kernel that forms h on the fly:
-// the down GEMM's activation pre-pass (fql_act_quant.h, GATE) and the gated adapter loads (fql_lora.h, GATE), so the
-// adapter sees bit for bit the h the INT4 GEMM consumed.
-__device__ __forceinline__ float act_silu_mul(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
+// Hidden activation of a gated FFN expert.  ONE definition for every kernel that forms h on the fly: the down GEMM's
+// activation pre-pass (fql_act_quant.h, GATE) and the gated adapter loads (fql_lora.h, GATE), so the adapter sees bit for
+// bit the h the INT4 GEMM consumed.  The kinds (FQL_ACT_* of include/fql_int4.h) are one family,
+//     h = g' * sigma(a) * u',   evaluated as (g' / (1 + expf(-a))) * u':
+//   FQL_ACT_SILU (0)          g' = g,             u' = u,                               a = g
+//   FQL_ACT_GELU_TANH (1)     g' = g,             u' = u,                               a = g (c0 + c1 g^2)
+//   FQL_ACT_SWIGLU_CLAMP (2)  g' = min(g, limit), u' = min(max(u, -limit), limit) + 1,  a = alpha g'
+// c0 = 2 sqrt(2 / pi), c1 = 0.044715 c0.  The tanh form of GELU, 0.5 g (1 + tanh(sqrt(2 / pi) (g + 0.044715 g^3))), IS
+// g sigma(a), because 0.5 (1 + tanh z) = sigma(2 z); it is written with the sigmoid because 1 + tanh z cancels for
+// negative g (the relative error of gelu(g) grows without bound as g falls) and the family form does not.
+// The products that form a and a' are never contracted into fused multiply-adds: every kernel rounds them alike.
+// `kind`, `alpha` and `limit` are wave-uniform; with a compile-time kind the other branches fold away.
+#define FQL_ACT_KIND_SILU 0
+#define FQL_ACT_KIND_GELU_TANH 1
+#define FQL_ACT_KIND_SWIGLU_CLAMP 2
+#define FQL_GELU_C0 1.5957691216057308f
+#define FQL_GELU_C1 0.0713548162726009f
+__device__ __forceinline__ float act_glu_mul(int kind, float alpha, float limit, float g, float u)
+{
+    float gp = g, up = u, a = g;
+    if (kind == FQL_ACT_KIND_GELU_TANH) {
+        a = __fmul_rn(g, __fadd_rn(FQL_GELU_C0, __fmul_rn(FQL_GELU_C1, __fmul_rn(g, g))));
+    } else if (kind == FQL_ACT_KIND_SWIGLU_CLAMP) {
+        gp = fminf(g, limit);
+        up = __fadd_rn(fminf(fmaxf(u, -limit), limit), 1.0f);
+        a = __fmul_rn(alpha, gp);
+    }
+    return (gp / (1.0f + expf(-a))) * up;
+}
+// h = silu(g) * u: the kind of the kernels without an activation argument.
+__device__ __forceinline__ float act_silu_mul(float g, float u) { return act_glu_mul(FQL_ACT_KIND_SILU, 0.0f, 0.0f, g, u); }
+
+// The backward of act_glu_mul, ONE definition as well: with sig = 1 / (1 + expf(-a)) and a' = da / dg',
+//     dg = dh u' (sig (1 + g' a' (1 - sig))),   du = dh (g' sig);
+// a' = 1 / c0 + 3 c1 g^2 / alpha.  The clamped kind passes no gradient where the clamp is active: dg = 0 for g > limit,
+// du = 0 for u < -limit or u > limit (equality passes it, as torch.clamp's backward does).  expf overflow: sig = 0 and
+// both gradients are (signed) zeros.  The silu kind is swiglu_bwd_kernel of fql_lora.h term for term.
+__device__ __forceinline__ void act_glu_grad(int kind, float alpha, float limit, float g, float u, float dh, float &dg,
+                                             float &du)
+{
+    float gp = g, up = u, a = g, ad = 1.0f;
+    if (kind == FQL_ACT_KIND_GELU_TANH) {
+        const float gg = __fmul_rn(g, g);
+        a = __fmul_rn(g, __fadd_rn(FQL_GELU_C0, __fmul_rn(FQL_GELU_C1, gg)));
+        ad = __fadd_rn(FQL_GELU_C0, __fmul_rn(3.0f * FQL_GELU_C1, gg));
+    } else if (kind == FQL_ACT_KIND_SWIGLU_CLAMP) {
+        gp = fminf(g, limit);
+        up = __fadd_rn(fminf(fmaxf(u, -limit), limit), 1.0f);
+        a = __fmul_rn(alpha, gp);
+        ad = alpha;
+    }
+    const float sig = 1.0f / (1.0f + expf(-a));
+    // (g^2 overflows past |g| = 1.8e19: g' a' is then infinite next to a factor that is exactly 0, which stays 0)
+    const float om = 1.0f - sig;
+    const float t = om == 0.0f ? 0.0f : __fmul_rn(__fmul_rn(gp, ad), om);
+    dg = dh * up * (sig == 0.0f ? 0.0f : sig * __fadd_rn(1.0f, t));
+    du = dh * (gp * sig);
+    if (kind == FQL_ACT_KIND_SWIGLU_CLAMP) {
+        if (g > limit) dg = 0.0f;
+        if (u < -limit || u > limit) du = 0.0f;
+    }
+}
 
 // Bijective XCD-aware remap of a 1-D grid: blocks b and b+8 share an XCD (round-robin dispatch),
 // so give each XCD a contiguous range of logical tile ids.  Speed only, never correctness.

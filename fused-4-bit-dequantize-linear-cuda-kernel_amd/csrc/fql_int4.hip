@@ -20,6 +20,7 @@
 #include "fql_router.h"
 #include "fql_w4_launch.h"
 #include "fql_ffn16_launch.h"
+#include "fql_glu_launch.h"
 #include <atomic>
 #include <random>
 
@@ -100,6 +101,8 @@ struct Call {
     const int32_t *gather = nullptr;       // optional: grouped row t is row gather[t] of x
     int n_src = 0;
     bool gated = false;                    // the pre-pass applies silu(gate) * up
+    int act = FQL_ACT_SILU;                // ... or (gated) another kind of FQL_ACT_*, with its two floats
+    float act_alpha = 0.0f, act_limit = 0.0f;
     bool f8 = false;                       // the pre-pass writes one e4m3 plane, the GEMM is the fp8 form
     const uint8_t *packed = nullptr;
     const float *scales = nullptr;
@@ -231,6 +234,12 @@ int launch_act_quant(const Call &c)
     const bool single = vec && mblocks * FQL_MB <= g_act_single_rows;
     const int rblocks = single ? T : (T + ACT_ROWS - 1) / ACT_ROWS;
     const int zblocks = zero_out != nullptr ? (T + 255) / 256 : 0;
+    if (c.gated && !c.f8 && c.act != FQL_ACT_SILU) {           // another activation kind: the instantiations of fql_glu.hip
+        if (c.gather != nullptr) return FQL_ERR_DTYPE;
+        FqlActGatedArgs a{c.x, c.ws.delta, c.ws.rowsum, c.ws.limbs, T, K, c.Kp / FQL_KB, c.MBT, rblocks, zblocks, zero_out,
+                          dtype_bytes(c.out_dtype), c.N, c.tpe, c.offs, c.E, c.row_weight, c.st};
+        return fql_act_glu_launch(L, single ? 0 : (vec ? 1 : 2), c.in_dtype, a, c.act, c.act_alpha, c.act_limit) == 0 ? FQL_OK : FQL_ERR_LAUNCH;
+    }
     if (c.gated && !c.f8 && c.in_dtype != FQL_DTYPE_F32) {     // 16-bit gate|up rows: the instantiations of fql_ffn16.hip
         if (c.gather != nullptr) return FQL_ERR_DTYPE;
         FqlActGatedArgs a{c.x, c.ws.delta, c.ws.rowsum, c.ws.limbs, T, K, c.Kp / FQL_KB, c.MBT, rblocks, zblocks, zero_out,
@@ -1131,6 +1140,39 @@ int fql_moe_gated_fwd(const uint8_t *packed, const float *scales, const float *z
     if ((reinterpret_cast<uintptr_t>(gate_up) & (dtype_bytes(in_dtype) - 1)) != 0) return FQL_ERR_ALIGNMENT;
     Call c;
     c.x = gate_up; c.in_dtype = in_dtype; c.gated = true;
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tokens_per_expert; c.offs = input_offsets;
+    c.set_shape(E, T, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
+}
+
+// fql_moe_gated_fwd with an activation kind: silu is that call; the other kinds take the pre-pass of fql_glu.hip (any element
+// type, float32 included) and the same GEMM.
+int fql_moe_glu_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up, int in_dtype,
+                    const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E, int T,
+                    int K, int N, int precision, int activation, float act_alpha, float act_limit, void *workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    if (activation == FQL_ACT_SILU)
+        return fql_moe_gated_fwd(packed, scales, zps, gate_up, in_dtype, tokens_per_expert, input_offsets, out, out_dtype, E, T,
+                                 K, N, precision, workspace, workspace_bytes, stream);
+    const int L = limbs_of(precision);
+    if (L < 0 || is_f8(precision)) return FQL_ERR_BAD_PRECISION;
+    if (E <= 0 || T < 0 || K <= 0 || N < 0) return FQL_ERR_BAD_SHAPE;
+    if ((activation != FQL_ACT_GELU_TANH && activation != FQL_ACT_SWIGLU_CLAMP) || !std::isfinite(act_alpha) ||
+        !std::isfinite(act_limit) || !(act_limit > 0.0f)) return FQL_ERR_BAD_SHAPE;
+    if (K & 1) return FQL_ERR_ODD_K;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!packed || !scales || !zps || !gate_up || !out) return FQL_ERR_NULL_POINTER;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
+    if (E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
+    if ((reinterpret_cast<uintptr_t>(gate_up) & (dtype_bytes(in_dtype) - 1)) != 0) return FQL_ERR_ALIGNMENT;
+    Call c;
+    c.x = gate_up; c.in_dtype = in_dtype; c.gated = true;
+    c.act = activation; c.act_alpha = act_alpha; c.act_limit = act_limit;
     c.packed = packed; c.scales = scales; c.zps = zps;
     c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
     c.tpe = tokens_per_expert; c.offs = input_offsets;

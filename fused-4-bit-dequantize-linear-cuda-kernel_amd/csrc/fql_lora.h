@@ -37,6 +37,12 @@
 // code, and every promise above holds for the gated variants.
 //
 // swiglu_bwd_kernel: the elementwise backward of h = silu(g) * u, one streaming pass over [T][2F] + [T][F] -> [T][2F].
+//
+// Activation kinds other than silu (FQL_ACT_GELU_TANH, FQL_ACT_SWIGLU_CLAMP; instantiated in fql_glu.hip only): the gated
+// shrink and grad kernels take one more argument, ACT = GluArgs -- the kind and its two floats, wave-uniform -- and h comes
+// from act_glu_mul of fql_common.h, the function the pre-pass calls for the same kind.  The argument is a template
+// parameter pack that is empty for every kernel of before, which therefore keeps its argument list and its code; only the
+// operand load differs.  glu_bwd_kernel is swiglu_bwd_typed_kernel with (dg, du) = act_glu_grad.
 #pragma once
 #include "fql_common.h"
 
@@ -142,6 +148,19 @@ __device__ __forceinline__ void load_operand(const void *pv, int t, int C, int c
     }
 }
 
+// ... and for an activation kind other than silu (GATE only): h = act_glu_mul(kind, alpha, limit, g, u).
+struct GluArgs { int kind; float alpha, limit; };
+template <int VEC, bool GATE, int DT = 0>
+__device__ __forceinline__ void load_operand(const void *pv, int t, int C, int c, float (&v)[VEC], GluArgs act)
+{
+    static_assert(GATE, "an activation kind needs a gate|up row");
+    float g[VEC], u[VEC];
+    load_elems<VEC, DT>(pv, (size_t)t * 2 * C + c, g);
+    load_elems<VEC, DT>(pv, (size_t)t * 2 * C + C + c, u);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = act_glu_mul(act.kind, act.alpha, act.limit, g[i], u[i]);
+}
+
 // Rows [lo, hi) of expert e, clamped into [0, T) (a table that points outside the tensor never reaches memory).
 __device__ __forceinline__ void expert_rows(const int32_t *tpe, const int32_t *offs, int e, int T, int &lo, int &hi)
 {
@@ -195,10 +214,10 @@ __device__ __forceinline__ void cover_flags(const int32_t *tpe, const int32_t *o
 
 // ---- shrink: out[t][0:R] = scale * in[t][:] . W_e^T.  One workgroup = TM = 64 / R rows of one expert, 512 lanes
 //      across the columns; grid = tile slots (+ coverage workgroups when there is a table).  GATE: `in` is [T][2C].
-template <int R, bool CR, int VEC, bool GATE, int DT = 0>
+template <int R, bool CR, int VEC, bool GATE, int DT = 0, typename... ACT>
 __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
     const void *__restrict__ in, const float *__restrict__ w, const int32_t *__restrict__ tpe,
-    const int32_t *__restrict__ offs, float *__restrict__ out, int E, int T, int C, float scale, int slots)
+    const int32_t *__restrict__ offs, float *__restrict__ out, int E, int T, int C, float scale, int slots, ACT... act)
 {
     constexpr int TM = 64 / R;
     constexpr int NW = FQL_LORA_SHRINK_THREADS / FQL_WAVE;
@@ -226,7 +245,7 @@ __global__ __launch_bounds__(FQL_LORA_SHRINK_THREADS) void lora_shrink_kernel(
         float x[TM][VEC];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            if (i < n) load_operand<VEC, GATE, DT>(in, row0 + i, C, c, x[i]);
+            if (i < n) load_operand<VEC, GATE, DT>(in, row0 + i, C, c, x[i], act...);
             else {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) x[i][v] = 0.f;
@@ -364,10 +383,10 @@ __global__ __launch_bounds__(FQL_LORA_EXPAND_THREADS) void lora_expand_kernel(
 // ---- grad: D_e = scale * P_e^T V_e.  grid = (column blocks, E).  A lane owns VEC columns x RJ = min(R, 16) ranks (the
 //      R / RJ rank groups split the wave's lanes); the 8 waves split the expert's rows (wave w: lo + w + 8 i) and their
 //      partials meet in a fixed tree through LDS.  Experts without rows write zeros.  GATE: P is [T][2C].
-template <int R, bool CR, int VEC, bool GATE, int DT = 0>
+template <int R, bool CR, int VEC, bool GATE, int DT = 0, typename... ACT>
 __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
     const void *__restrict__ P, const float *__restrict__ V, const int32_t *__restrict__ tpe,
-    const int32_t *__restrict__ offs, float *__restrict__ D, int T, int C, float scale)
+    const int32_t *__restrict__ offs, float *__restrict__ D, int T, int C, float scale, ACT... act)
 {
     constexpr int RJ = R < 16 ? R : 16;
     constexpr int JG = R / RJ;
@@ -395,7 +414,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
         float p[U][VEC], v[U][RJ];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            load_operand<VEC, GATE, DT>(P, t + u * NW, C, cc, p[u]);
+            load_operand<VEC, GATE, DT>(P, t + u * NW, C, cc, p[u], act...);
 #pragma unroll
             for (int j = 0; j < RJ; j += 4) {
                 float4 x = *reinterpret_cast<const float4 *>(V + (size_t)(t + u * NW) * R + j0 + j);
@@ -411,7 +430,7 @@ __global__ __launch_bounds__(FQL_LORA_GRAD_THREADS) void lora_grad_kernel(
     }
     for (; t < hi; t += NW) {
         float p[VEC], v[RJ];
-        load_operand<VEC, GATE, DT>(P, t, C, cc, p);
+        load_operand<VEC, GATE, DT>(P, t, C, cc, p, act...);
 #pragma unroll
         for (int j = 0; j < RJ; j += 4) {
             float4 x = *reinterpret_cast<const float4 *>(V + (size_t)t * R + j0 + j);
@@ -507,6 +526,26 @@ __global__ __launch_bounds__(FQL_SWIGLU_BWD_THREADS) void swiglu_bwd_typed_kerne
         dg[i] = d[i] * u[i] * (sig * (1.0f + g[i] * (1.0f - sig)));
         du[i] = d[i] * (g[i] * sig);
     }
+    store_elems<VEC, DO>(dgu, o, dg);
+    store_elems<VEC, DO>(dgu, o + F, du);
+}
+
+// ---- the same pass for the activation kind in `act`: (dg, du) = act_glu_grad (fql_common.h), every element type.
+template <int VEC, int DG, int DD, int DO>
+__global__ __launch_bounds__(FQL_SWIGLU_BWD_THREADS) void glu_bwd_kernel(
+    const void *__restrict__ gu, const void *__restrict__ dh, void *__restrict__ dgu, int T, int F, GluArgs act)
+{
+    const int per_row = F / VEC;
+    const long long q = (long long)blockIdx.x * FQL_SWIGLU_BWD_THREADS + threadIdx.x;
+    if (q >= (long long)T * per_row) return;
+    const int t = (int)(q / per_row), c = (int)(q % per_row) * VEC;
+    const size_t o = (size_t)t * 2 * F + c;
+    float g[VEC], u[VEC], d[VEC], dg[VEC], du[VEC];
+    load_elems<VEC, DG>(gu, o, g);
+    load_elems<VEC, DG>(gu, o + F, u);
+    load_elems<VEC, DD>(dh, (size_t)t * F + c, d);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) act_glu_grad(act.kind, act.alpha, act.limit, g[i], u[i], d[i], dg[i], du[i]);
     store_elems<VEC, DO>(dgu, o, dg);
     store_elems<VEC, DO>(dgu, o + F, du);
 }

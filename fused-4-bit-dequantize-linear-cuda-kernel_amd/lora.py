@@ -138,8 +138,10 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     parameters (float32 whatever ``activation_dtype`` is)."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
-                 precision: str = "default", activation_dtype=None):
-        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision, activation_dtype=activation_dtype)
+                 precision: str = "default", activation_dtype=None, activation: str = "silu",
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0):
+        super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision, activation_dtype=activation_dtype,
+                         activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
         _check_rank(rank)
         self.rank = rank
         self.alpha = float(rank if alpha is None else alpha)
@@ -164,11 +166,12 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     def from_quantized(cls, layer: QuantizedMoEFFN, rank: int, alpha: float | None = None,
                        activation_dtype=None) -> "LoRAQuantizedMoEFFN":
         """Wrap an existing ``QuantizedMoEFFN``; the new module shares its buffers (no copy).  ``activation_dtype``
-        None keeps the wrapped layer's."""
+        None keeps the wrapped layer's.  The activation kind is the wrapped layer's."""
         if activation_dtype is None:
             activation_dtype = layer.activation_dtype
         module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision,
-                     activation_dtype=activation_dtype)
+                     activation_dtype=activation_dtype, activation=layer.activation,
+                     activation_alpha=layer.activation_alpha, activation_limit=layer.activation_limit)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
         dev = layer.gate_up_packed.device
@@ -190,8 +193,10 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
                                         self.down_packed, self.down_scales, self.down_zero_points, inputs,
                                         self.gate_up_lora_A, self.gate_up_lora_B, self.down_lora_A, self.down_lora_B,
                                         self.scaling, tokens_per_expert, input_offsets, precision=self.precision,
-                                        activation_dtype=self.activation_dtype)
+                                        activation_dtype=self.activation_dtype, activation=self.activation,
+                                        activation_alpha=self.activation_alpha,
+                                        activation_limit=self.activation_limit)
 
     def extra_repr(self) -> str:
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "
-                f"rank={self.rank}, alpha={self.alpha:g}")
+                f"rank={self.rank}, alpha={self.alpha:g}") + self._activation_repr()

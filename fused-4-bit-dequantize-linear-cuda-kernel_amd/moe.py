@@ -218,14 +218,24 @@ class QuantizedMoEFFN(nn.Module):
     ``activation_dtype`` (None / torch.float32: the float32 layer, unchanged) = torch.float16 / torch.bfloat16 runs the
     layer on 16-bit activations: inputs and the incoming gradient have that type, ``gate_up`` is written (and kept for
     the backward) in it, and the output and the input gradient come back in it.  That rounds ``gate_up`` between the two
-    projections, which the float32 layer does not do: a memory-for-precision choice, so it is opt-in."""
+    projections, which the float32 layer does not do: a memory-for-precision choice, so it is opt-in.
+
+    ``activation`` chooses the function between the two projections: ``"silu"`` (SwiGLU, the default), ``"gelu_tanh"``
+    (GeGLU, tanh form; Hugging Face's ``"gelu_pytorch_tanh"`` is accepted) or ``"swiglu_clamp"`` (gpt-oss:
+    ``min(g, limit) * sigmoid(alpha * min(g, limit)) * (clamp(u, -limit, limit) + 1)`` with ``activation_alpha`` and
+    ``activation_limit``).  It is configuration, not state: the state-dict keys and values are the same for every kind
+    (INTEGRATION.md section 13)."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, precision: str = "default",
-                 activation_dtype=None):
+                 activation_dtype=None, activation: str = "silu", activation_alpha: float = 1.702,
+                 activation_limit: float = 7.0):
         super().__init__()
         assert hidden_dim % 32 == 0 and ffn_dim % 32 == 0, "hidden_dim and ffn_dim must be multiples of 32"
         self.num_experts, self.hidden_dim, self.ffn_dim, self.precision = num_experts, hidden_dim, ffn_dim, precision
         self.activation_dtype = _activation_dtype(activation_dtype, precision)
+        from . import ops
+        self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
+            activation, activation_alpha, activation_limit)
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_packed", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
         self.register_buffer("gate_up_scales", torch.zeros(E, 2 * F, dtype=torch.float32))
@@ -236,11 +246,13 @@ class QuantizedMoEFFN(nn.Module):
 
     @classmethod
     def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor],
-                     precision: str = "default", activation_dtype=None) -> "QuantizedMoEFFN":
+                     precision: str = "default", activation_dtype=None, activation: str = "silu",
+                     activation_alpha: float = 1.702, activation_limit: float = 7.0) -> "QuantizedMoEFFN":
         """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` (nn.Linear weight layout)."""
         E = len(gate)
         F, H = gate[0].shape
-        m = cls(E, H, F, precision, activation_dtype=activation_dtype)
+        m = cls(E, H, F, precision, activation_dtype=activation_dtype, activation=activation,
+                activation_alpha=activation_alpha, activation_limit=activation_limit)
         gu = [quantize_weights(torch.cat([g.float(), u.float()], dim=0)) for g, u in zip(gate, up)]
         dn = [quantize_weights(d.float()) for d in down]
         m.gate_up_packed = torch.stack([t[0] for t in gu])
@@ -268,6 +280,22 @@ class QuantizedMoEFFN(nn.Module):
     def total_memory_bytes(self) -> int:
         return sum(b.numel() * b.element_size() for b in self.buffers())
 
+    @property
+    def activation_args(self):
+        """``(activation, activation_alpha, activation_limit)`` as the ops take them."""
+        return self.activation, self.activation_alpha, self.activation_limit
+
+    def _activation_repr(self) -> str:
+        if self.activation == "silu":
+            return ""
+        s = f", activation={self.activation}"
+        if self.activation == "swiglu_clamp":
+            s += f", activation_alpha={self.activation_alpha:g}, activation_limit={self.activation_limit:g}"
+        return s
+
+    def extra_repr(self) -> str:
+        return self._activation_repr().lstrip(", ")
+
 
 def _activation_dtype(activation_dtype, precision):
     from . import ops
@@ -290,7 +318,8 @@ def _gated_ffn(m, inputs, tpe, offs):
         gate_up = ops.moe_forward_any(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe,
                                       offs, precision=m.precision, out_dtype=dt)
     return ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up, tpe, offs,
-                                 precision=m.precision, out_dtype=dt), gate_up
+                                 precision=m.precision, out_dtype=dt, activation=m.activation,
+                                 activation_alpha=m.activation_alpha, activation_limit=m.activation_limit), gate_up
 
 
 class _GatedFFNFn(torch.autograd.Function):
@@ -314,9 +343,12 @@ class _GatedFFNFn(torch.autograd.Function):
         K = gate_up.shape[1] // 2
         dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy.to(torch.float32), tpe, offs,
                                     precision=m.precision)
-        g, u = gate_up[:, :K], gate_up[:, K:]
-        sig = torch.sigmoid(g)
-        dgu = torch.cat([dh * u * (sig * (1.0 + g * (1.0 - sig))), dh * (g * sig)], dim=1)
+        if m.activation == "silu":
+            g, u = gate_up[:, :K], gate_up[:, K:]
+            sig = torch.sigmoid(g)
+            dgu = torch.cat([dh * u * (sig * (1.0 + g * (1.0 - sig))), dh * (g * sig)], dim=1)
+        else:                                                   # the other kinds: one streaming kernel
+            dgu = ops.glu_backward(gate_up, dh, *m.activation_args)
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
                                     precision=m.precision)
         return dx, None, None, None
@@ -337,7 +369,7 @@ class _GatedFFN16Fn(_GatedFFNFn):
         ops.check_activation_rows(gy, "the incoming gradient", dt)
         dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
                                     precision=m.precision, out_dtype=dt)
-        dgu = ops.swiglu_backward(gate_up, dh, out_dtype=dt)
+        dgu = ops.glu_backward(gate_up, dh, *m.activation_args, out_dtype=dt)
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
                                     precision=m.precision, out_dtype=dt)
         return dx, None, None, None
@@ -369,15 +401,33 @@ class QuantizedSparseMoEBlock(nn.Module):
     ``gate.e_score_correction_bias`` [E] of zeros, added to the scores for the selection only and moved by
     ``update_selection_bias``) select the rules of DeepSeek-V2 / V3, GLM-4.5, Kimi-K2 and Llama-4 (INTEGRATION.md
     section 11).  The forward makes one ``ops.router_score_topk`` call either way: with all at their defaults that is
-    ``ops.router_topk``, bit for bit and kernel for kernel, and the state-dict keys are unchanged."""
+    ``ops.router_topk``, bit for bit and kernel for kernel, and the state-dict keys are unchanged.
+
+    ``activation`` (with ``activation_alpha`` / ``activation_limit``) is handed to the experts and the shared expert the
+    block builds.  A module passed in as ``experts`` / ``shared_experts`` keeps its own; an explicit block argument that
+    contradicts it raises ``ValueError``."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
                  n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
                  selection_bias: bool = False, shared_ffn_dim: int = 0, shared_experts=None,
-                 shared_expert_gate: bool = False):
+                 shared_expert_gate: bool = False, activation=None, activation_alpha=None, activation_limit=None):
         super().__init__()
         from . import ops
+        # None: not given (a built expert takes the default, a passed-in one keeps its own)
+        act_kw = {k: v for k, v in (("activation", activation), ("activation_alpha", activation_alpha),
+                                    ("activation_limit", activation_limit)) if v is not None}
+        want = ops.activation_of(**act_kw)
+
+        def check_activation(name, module):
+            have = dict(zip(("activation", "activation_alpha", "activation_limit"), module.activation_args))
+            given = dict(zip(("activation", "activation_alpha", "activation_limit"), want))
+            for k in act_kw:
+                if k != "activation" and have["activation"] != "swiglu_clamp":
+                    continue                                    # (the two floats belong to the clamped kind alone)
+                if have[k] != given[k]:
+                    raise ValueError(f"{k}={act_kw[k]!r} contradicts {name}, built with {k}={have[k]!r}: leave the "
+                                     f"block's argument out, or build {name} with it")
         if num_experts < 1 or num_experts > ops.ROUTE_MAX_EXPERTS:
             raise ValueError(f"num_experts must be in [1, {ops.ROUTE_MAX_EXPERTS}], got {num_experts}")
         if top_k < 1 or top_k > min(num_experts, ops.ROUTER_MAX_TOPK):
@@ -394,9 +444,11 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise ValueError("routed_scaling_factor must be finite")
         if experts is None:
             experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
-                                      activation_dtype=activation_dtype)
+                                      activation_dtype=activation_dtype, **act_kw)
         elif (experts.num_experts, experts.hidden_dim, experts.ffn_dim) != (num_experts, hidden_dim, ffn_dim):
             raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
+        else:
+            check_activation("experts", experts)
         if shared_ffn_dim < 0 or shared_ffn_dim % 32 != 0:
             raise ValueError(f"shared_ffn_dim must be a non-negative multiple of 32, got {shared_ffn_dim}")
         if shared_experts is not None:
@@ -404,9 +456,10 @@ class QuantizedSparseMoEBlock(nn.Module):
                 raise ValueError("shared_experts must be one expert (num_experts == 1) of the block's hidden_dim")
             if shared_ffn_dim and shared_experts.ffn_dim != shared_ffn_dim:
                 raise ValueError("shared_ffn_dim and shared_experts.ffn_dim differ")
+            check_activation("shared_experts", shared_experts)
         elif shared_ffn_dim:
             shared_experts = QuantizedMoEFFN(1, hidden_dim, shared_ffn_dim, precision=precision,
-                                             activation_dtype=activation_dtype)
+                                             activation_dtype=activation_dtype, **act_kw)
         if shared_expert_gate and shared_experts is None:
             raise ValueError("shared_expert_gate=True needs a shared expert (shared_ffn_dim or shared_experts)")
         self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
@@ -426,14 +479,17 @@ class QuantizedSparseMoEBlock(nn.Module):
     @classmethod
     def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
                      down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
-                     renormalize: bool = True, shared=None, shared_expert_gate_weight=None,
+                     renormalize: bool = True, shared=None, shared_expert_gate_weight=None, activation: str = "silu",
+                     activation_alpha: float = 1.702, activation_limit: float = 7.0,
                      **routing) -> "QuantizedSparseMoEBlock":
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
         ``QuantizedMoEFFN.from_weights`` takes them.  ``shared``: ``(gate [Fs, H], up [Fs, H], down [H, Fs])`` of the
         shared expert; ``shared_expert_gate_weight`` [1, H]: the weight of its sigmoid gate.  ``routing``: the
         constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor`` and
-        ``selection_bias``."""
-        experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype)
+        ``selection_bias``.  ``activation`` (and its two floats): the experts' and the shared expert's."""
+        act = dict(activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
+        experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype,
+                                               **act)
         E, H = gate_weight.shape
         if E != experts.num_experts or H != experts.hidden_dim:
             raise ValueError("gate_weight must be [num_experts, hidden_dim]")
@@ -441,7 +497,7 @@ class QuantizedSparseMoEBlock(nn.Module):
         if shared is not None:
             sg, su, sd = shared
             shared_experts = QuantizedMoEFFN.from_weights([sg], [su], [sd], precision=precision,
-                                                          activation_dtype=activation_dtype)
+                                                          activation_dtype=activation_dtype, **act)
         if shared_expert_gate_weight is not None and tuple(shared_expert_gate_weight.shape) != (1, H):
             raise ValueError("shared_expert_gate_weight must be [1, hidden_dim]")
         m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
@@ -556,4 +612,4 @@ class QuantizedSparseMoEBlock(nn.Module):
             s += f", shared_ffn_dim={self.shared_experts.ffn_dim}"
         if getattr(self, "shared_expert_gate", None) is not None:
             s += ", shared_expert_gate=True"
-        return s
+        return s + self.experts._activation_repr()

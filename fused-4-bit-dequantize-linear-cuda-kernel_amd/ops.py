@@ -36,6 +36,30 @@ def _precision(p):
         raise ValueError(f"precision must be 'default', 'exact', 'fast', 'int8' or 'fp8', got {p!r}") from None
 
 
+ACTIVATIONS = ("silu", "gelu_tanh", "swiglu_clamp")
+_ACTIVATIONS = {"silu": _native.ACT_SILU, "gelu_tanh": _native.ACT_GELU_TANH, "gelu_pytorch_tanh": _native.ACT_GELU_TANH,
+                "swiglu_clamp": _native.ACT_SWIGLU_CLAMP}
+
+
+def activation_of(activation="silu", activation_alpha=1.702, activation_limit=7.0):
+    """The activation arguments of the gated FFN ops and layers as ``(kind, alpha, limit)``: ``kind`` one of
+    ``ACTIVATIONS`` (``"gelu_pytorch_tanh"``, Hugging Face's name, is ``"gelu_tanh"``), ``alpha`` finite, ``limit``
+    finite and > 0 (both used by ``"swiglu_clamp"`` only; the defaults are gpt-oss's)."""
+    if not isinstance(activation, str) or activation not in _ACTIVATIONS:
+        raise ValueError(f"activation must be 'silu', 'gelu_tanh' (alias 'gelu_pytorch_tanh') or 'swiglu_clamp', got "
+                         f"{activation!r}")
+    kind = "gelu_tanh" if activation == "gelu_pytorch_tanh" else activation
+    try:
+        alpha, limit = float(activation_alpha), float(activation_limit)
+    except (TypeError, ValueError):
+        raise ValueError("activation_alpha and activation_limit must be numbers") from None
+    if alpha != alpha or alpha in (float("inf"), float("-inf")):
+        raise ValueError(f"activation_alpha must be finite, got {activation_alpha!r}")
+    if limit != limit or limit == float("inf") or not limit > 0.0:
+        raise ValueError(f"activation_limit must be finite and > 0, got {activation_limit!r}")
+    return kind, alpha, limit
+
+
 def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -366,13 +390,17 @@ def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, t
 
 
 def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_expert, input_offsets,
-                      precision="default", out_dtype=None):
+                      precision="default", out_dtype=None, activation="silu", activation_alpha=1.702,
+                      activation_limit=7.0):
     """Second GEMM of a gated FFN expert with the activation fused into its pre-pass:
     ``out[t] = W_e @ (silu(gate_up[t, :K]) * gate_up[t, K:])``; ``gate_up`` [T, 2K] float32 / float16 / bfloat16 (the
     output of the fused gate|up projection), ``packed_weights`` [E, N, K/2].  The [T, K] hidden activation is never
     written.  The result has ``out_dtype`` (default: ``gate_up``'s type); a 16-bit ``gate_up`` is read as it is and a
-    16-bit result is rounded once: bit for bit ``moe_gated_forward(gate_up.float()).to(out_dtype)``."""
+    16-bit result is rounded once: bit for bit ``moe_gated_forward(gate_up.float()).to(out_dtype)``.
+    ``activation``: ``"silu"``, ``"gelu_tanh"`` (GeGLU) or ``"swiglu_clamp"`` (gpt-oss, with ``activation_alpha`` and
+    ``activation_limit``) in place of silu(g) * u (``activation_of``)."""
     _forward_only("moe_gated_forward", gate_up)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     if not gate_up.is_cuda or gate_up.dtype not in _DTYPES or gate_up.dim() != 2:
         raise RuntimeError("gate_up must be a CUDA float32 (or float16 / bfloat16) [T, 2K] tensor")
     out_dtype = gate_up.dtype if out_dtype is None else out_dtype
@@ -393,8 +421,13 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
         # off the 16-bit MFMA path: widen and round around the float32 call (the same contract)
         gate_up, round_to, out_dtype = gate_up.float(), out_dtype, torch.float32
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    _launch("fql_moe_gated_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(), _DTYPES[gate_up.dtype],
-            tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
+    if kind == "silu":
+        _launch("fql_moe_gated_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(), _DTYPES[gate_up.dtype],
+                tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
+    else:
+        _launch("fql_moe_glu_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(), _DTYPES[gate_up.dtype],
+                tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, _ACTIVATIONS[kind], act_alpha, act_limit,
+                ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
     return out if round_to is None else out.to(round_to)
 
 
@@ -1127,8 +1160,9 @@ def _gate_up_rows(gate_up, dev):
     return g, g.shape[0], g.shape[1] // 2
 
 
-def _lora_shrink(rows, weight, layout, tokens_per_expert, input_offsets, scale, gated):
-    """``lora_shrink`` (rows = input [T, C]) / ``lora_gated_shrink`` (rows = gate_up [T, 2C])."""
+def _lora_shrink(rows, weight, layout, tokens_per_expert, input_offsets, scale, gated, act=("silu", 0.0, 0.0)):
+    """``lora_shrink`` (rows = input [T, C]) / ``lora_gated_shrink`` (rows = gate_up [T, 2C]; ``act``: what
+    ``activation_of`` returned)."""
     dev = rows.device
     if gated:
         x, T, C = _gate_up_rows(rows, dev)
@@ -1142,13 +1176,18 @@ def _lora_shrink(rows, weight, layout, tokens_per_expert, input_offsets, scale, 
         return out
     if C == 0:
         return out.zero_()
+    if gated and act[0] != "silu":
+        _launch("fql_lora_glu_shrink", dev, x, _DTYPES[x.dtype], w, _lora_layout(layout), tpe, offs, out, E, T, C, r,
+                float(scale), _ACTIVATIONS[act[0]], act[1], act[2])
+        return out
     _launch("fql_lora_gated_shrink" if gated else "fql_lora_shrink", dev, x, _DTYPES[x.dtype], w, _lora_layout(layout),
             tpe, offs, out, E, T, C, r, float(scale))
     return out
 
 
-def _lora_grad(rows, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated):
-    """``lora_grad`` (rows = p [T, C]) / ``lora_gated_grad`` (rows = gate_up [T, 2C])."""
+def _lora_grad(rows, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated, act=("silu", 0.0, 0.0)):
+    """``lora_grad`` (rows = p [T, C]) / ``lora_gated_grad`` (rows = gate_up [T, 2C]; ``act``: what ``activation_of``
+    returned)."""
     dev = rows.device
     name = "gate_up" if gated else "p"
     if gated:
@@ -1171,6 +1210,10 @@ def _lora_grad(rows, v, layout, num_experts, tokens_per_expert, input_offsets, s
     d = torch.empty(shape, dtype=torch.float32, device=dev)
     if vv.data_ptr() % 16:
         vv = vv.clone()
+    if gated and act[0] != "silu":
+        _launch("fql_lora_glu_grad", dev, pp, _DTYPES[pp.dtype], vv, tpe, offs, d, lay, E, T, C, r, float(scale),
+                _ACTIVATIONS[act[0]], act[1], act[2])
+        return d
     _launch("fql_lora_gated_grad" if gated else "fql_lora_grad", dev, pp, _DTYPES[pp.dtype], vv, tpe, offs, d, lay,
             E, T, C, r, float(scale))
     return d
@@ -1393,18 +1436,24 @@ class _MoELoRAFn(torch.autograd.Function):
 # streaming kernel.
 # ---------------------------------------------------------------------------------------------------------------------
 
-def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0):
+def lora_gated_shrink(gate_up, weight, layout="rc", tokens_per_expert=None, input_offsets=None, scale=1.0,
+                      activation="silu", activation_alpha=1.702, activation_limit=7.0):
     """``lora_shrink`` on the hidden activation of a gated FFN expert without materialising it:
     ``out[t] = scale * (silu(gate_up[t, :C]) * gate_up[t, C:]) @ W_e^T`` -> [T, r] float32; ``gate_up`` [T, 2C]
-    float32, or float16 / bfloat16 read as it is: bit for bit the call on ``gate_up.float()``."""
-    return _lora_shrink(gate_up, weight, layout, tokens_per_expert, input_offsets, scale, gated=True)
+    float32, or float16 / bfloat16 read as it is: bit for bit the call on ``gate_up.float()``.  ``activation`` (and its
+    two floats, ``activation_of``): the kind of h, the bits ``moe_gated_forward`` consumes for the same kind."""
+    return _lora_shrink(gate_up, weight, layout, tokens_per_expert, input_offsets, scale, gated=True,
+                        act=activation_of(activation, activation_alpha, activation_limit))
 
 
-def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0):
+def lora_gated_grad(gate_up, v, layout, num_experts=1, tokens_per_expert=None, input_offsets=None, scale=1.0,
+                    activation="silu", activation_alpha=1.702, activation_limit=7.0):
     """``lora_grad`` with ``p = silu(gate_up[:, :C]) * gate_up[:, C:]`` formed on the fly: ``gate_up`` [T, 2C],
     ``v`` [T, r] -> [E, C, r] (``layout='cr'``) or [E, r, C] (``'rc'``: dA of the down adapter), float32.  ``gate_up``
-    may be float16 / bfloat16: read as it is, bit for bit the call on ``gate_up.float()``."""
-    return _lora_grad(gate_up, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated=True)
+    may be float16 / bfloat16: read as it is, bit for bit the call on ``gate_up.float()``.  ``activation`` (and its two
+    floats, ``activation_of``): the kind of p."""
+    return _lora_grad(gate_up, v, layout, num_experts, tokens_per_expert, input_offsets, scale, gated=True,
+                      act=activation_of(activation, activation_alpha, activation_limit))
 
 
 def swiglu_backward(gate_up, dh, out_dtype=None):
@@ -1412,6 +1461,18 @@ def swiglu_backward(gate_up, dh, out_dtype=None):
     ``[dg | du]`` [T, 2F] with ``dg = dh * u * silu'(g)``, ``du = dh * silu(g)``.  Each of ``gate_up``, ``dh`` and the
     result (``out_dtype``, default ``gate_up``'s type) may be float32, float16 or bfloat16: float32 arithmetic on the
     widened values, bit for bit ``swiglu_backward(gate_up.float(), dh.float()).to(out_dtype)``."""
+    return _glu_backward(gate_up, dh, out_dtype, ("silu", 0.0, 0.0))
+
+
+def glu_backward(gate_up, dh, activation="silu", activation_alpha=1.702, activation_limit=7.0, out_dtype=None):
+    """``swiglu_backward`` for any activation kind (``activation_of``): with ``h = g' * sigmoid(a) * u'``,
+    ``dg = dh * u' * sig * (1 + g' a' (1 - sig))`` and ``du = dh * g' * sig``; ``"swiglu_clamp"`` passes no gradient
+    where its clamp is active.  ``"silu"`` is ``swiglu_backward``, kernel for kernel.  Element types as there: bit for
+    bit the call on the widened operands, a 16-bit result rounded once."""
+    return _glu_backward(gate_up, dh, out_dtype, activation_of(activation, activation_alpha, activation_limit))
+
+
+def _glu_backward(gate_up, dh, out_dtype, act):
     dev = gate_up.device
     g, T, F = _gate_up_rows(gate_up, dev)
     d = _lora_rows(dh, "dh", dev, wide=True)
@@ -1422,6 +1483,10 @@ def swiglu_backward(gate_up, dh, out_dtype=None):
         raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
     out = torch.empty((T, 2 * F), dtype=out_dtype, device=dev)
     if T == 0 or F == 0:
+        return out
+    if act[0] != "silu":
+        _launch("fql_glu_bwd", dev, g, _DTYPES[g.dtype], d, _DTYPES[d.dtype], out, _DTYPES[out_dtype], T, F,
+                _ACTIVATIONS[act[0]], act[1], act[2])
         return out
     _launch("fql_swiglu_bwd", dev, g, _DTYPES[g.dtype], d, _DTYPES[d.dtype], out, _DTYPES[out_dtype], T, F)
     return out
@@ -1447,7 +1512,8 @@ def check_activation_rows(t, name, dt):
 
 def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps, inputs,
                          gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert,
-                         input_offsets, precision="default", activation_dtype=None):
+                         input_offsets, precision="default", activation_dtype=None, activation="silu",
+                         activation_alpha=1.702, activation_limit=7.0):
     """Gated INT4 FFN experts with a low-rank adapter on each projection: for the rows t of expert e,
     ``gu = W_gu x + s B_gu (A_gu x)``, ``h = silu(gu[:F]) * gu[F:]`` (never stored), ``y = W_d h + s B_d (A_d h)``; rows
     no expert covers are zero.  ``inputs`` [T, H] float32, stacked gate|up weights [E, 2F, H/2], down weights
@@ -1456,7 +1522,11 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
 
     ``activation_dtype`` = torch.float16 / torch.bfloat16 is the memory-for-precision form: ``inputs`` and the incoming
     gradient have that type, ``gate_up`` is stored (and saved) in it, ``y`` and ``inputs.grad`` come back in it; the
-    adapters and their gradients stay float32.  Five tensors are rounded, once each."""
+    adapters and their gradients stay float32.  Five tensors are rounded, once each.
+
+    ``activation`` (with ``activation_alpha``, ``activation_limit``; ``activation_of``) replaces silu(g) * u by
+    another kind of h in the forward and in every gradient."""
+    act = activation_of(activation, activation_alpha, activation_limit)
     dt = activation_dtype_of(activation_dtype)
     if dt is not None:
         check_activation_rows(inputs, "inputs", dt)
@@ -1481,12 +1551,12 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
     adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
     if _wants_grad(inputs, *adapters):
         return _MoEFFNLoRAFn.apply(inputs, *adapters, *weights, tokens_per_expert, input_offsets, float(scaling),
-                                   precision, dt)
+                                   precision, dt, act)
     return _moe_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets,
-                               precision)[0]
+                               precision, act)[0]
 
 
-def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision):
+def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision, act=("silu", 1.702, 7.0)):
     """Returns (y, gate_up, U_gu, U_d), y and gate_up in ``inputs``' type: each base GEMM reads its operand as it is and
     writes float32, and the expand adds the adapter term to that in place (float32) or writes the sum once in the 16-bit
     type -- gate_up (rounding 1) and y (rounding 2)."""
@@ -1497,8 +1567,9 @@ def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision
     u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
     gate_up = _expand_into(u_gu, B_gu, "cr", gu32, dt, tpe, offs, scaling)
     del gu32
-    y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32)
-    u_d = lora_gated_shrink(gate_up, A_d, "rc", tpe, offs)
+    y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32,
+                            activation=act[0], activation_alpha=act[1], activation_limit=act[2])
+    u_d = _lora_shrink(gate_up, A_d, "rc", tpe, offs, 1.0, gated=True, act=act)
     return _expand_into(u_d, B_d, "cr", y32, dt, tpe, offs, scaling), gate_up, u_gu, u_d
 
 
@@ -1508,12 +1579,13 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
     in that type (U_gu, U_d float32): T (2H + 4F + 8r) bytes."""
 
     @staticmethod
-    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision, dt=None):
+    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision, dt=None,
+                act=("silu", 1.702, 7.0)):
         x = inputs.contiguous()
         y, gate_up, u_gu, u_d = _moe_ffn_lora_apply((gup, gus, guz, dp, ds, dz), x, (A_gu, B_gu, A_d, B_d), scaling,
-                                                    tpe, offs, precision)
+                                                    tpe, offs, precision, act)
         ctx.save_for_backward(x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs)
-        ctx.scaling, ctx.precision, ctx.act_dtype = scaling, precision, dt
+        ctx.scaling, ctx.precision, ctx.act_dtype, ctx.act = scaling, precision, dt, act
         return y
 
     @staticmethod
@@ -1537,11 +1609,11 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
         if through or need_Ad:
             du_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dU_d = s dY B_d
             if need_Ad:
-                gAd = lora_gated_grad(gate_up, du_d, "rc", E, tpe, offs)                 # dA_d = dU_d^T h
+                gAd = _lora_grad(gate_up, du_d, "rc", E, tpe, offs, 1.0, gated=True, act=ctx.act)   # dA_d = dU_d^T h
         if through:
             dh = moe_backward_input(dp, ds, dz, g, tpe, offs, precision=prec)            # dh = dY W_d (float32)
             dh = _expand_into(du_d, A_d, "rc", dh, dt, tpe, offs)                        #      + dU_d A_d, in dt
-            dgu = swiglu_backward(gate_up, dh, out_dtype=dt)
+            dgu = _glu_backward(gate_up, dh, dt, ctx.act)
             del dh
             if need_Bgu:
                 gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
@@ -1552,4 +1624,4 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
                     gx = _expand_into(du_gu, A_gu, "rc", gx, dt, tpe, offs)              # dx = dgu W_gu + dU_gu A_gu
                 if need_Agu:
                     gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
-        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 11
+        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 12

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 290 /* 0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 300 /* 0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -663,6 +663,57 @@ FQL_API int fql_lora_gated_grad(const void *gate_up, int dtype, const float *v, 
                                 float scale, void *stream);
 FQL_API int fql_swiglu_bwd(const void *gate_up, int dtype, const void *dh, int dh_dtype, void *dgate_up, int out_dtype,
                            int T, int F, void *stream);
+
+/* ---- activation kinds of the gated FFN experts (FQL_VERSION 300) ----
+ * The four typed entry points above with `int activation, float act_alpha, float act_limit` in front of `workspace` /
+ * `stream`.  All kinds are one family, h = g' * sigma(a) * u', float32 arithmetic on the widened operands, evaluated as
+ * (g' / (1.0f + expf(-a))) * u' (the library is built with -fno-fast-math):
+ *
+ *   FQL_ACT_SILU          g' = g               u' = u                                   a = g                  a' = 1
+ *   FQL_ACT_GELU_TANH     g' = g               u' = u                                   a = g (c0 + c1 g g)    a' = c0 + 3 c1 g g
+ *   FQL_ACT_SWIGLU_CLAMP  g' = min(g, limit)   u' = min(max(u, -limit), limit) + 1      a = alpha g'           a' = alpha
+ *
+ * c0 = 2 sqrt(2 / pi) = 1.5957691216057308 and c1 = 0.044715 c0 = 0.0713548162726009, each rounded once to float32.
+ * FQL_ACT_GELU_TANH is the tanh form of GELU ("gelu_pytorch_tanh"): g sigma(a) = 0.5 g (1 + tanh(sqrt(2 / pi) (g + 0.044715
+ * g^3))), since 0.5 (1 + tanh z) = sigma(2 z).  It is written with the sigmoid because 1 + tanh z cancels for negative g and
+ * the family form does not.  FQL_ACT_SWIGLU_CLAMP is gpt-oss's (alpha = 1.702, limit = 7.0 there).
+ * Backward, sig = 1.0f / (1.0f + expf(-a)): dg = dh u' (sig (1 + g' a' (1 - sig))), du = dh (g' sig); the clamped kind
+ * gives dg = 0 exactly where g > limit and du = 0 exactly where u < -limit or u > limit (equality passes the gradient, as
+ * torch.clamp's backward does).  Every finite input gives finite outputs (expf overflow: sig = 0).
+ * One device function forms h and one (dg, du) (csrc/fql_common.h) for the pre-pass, the adapter loads and the backward,
+ * so the INT4 GEMM, the down adapter and the backward see the same bits of h.
+ *
+ * activation == FQL_ACT_SILU: the call IS the entry point above (same kernels, same bits, same return codes); act_alpha and
+ * act_limit are ignored.  The other kinds run kernels of their own (csrc/fql_glu.hip; any element type, float32 included)
+ * under the 16-bit contract above: bit for bit the float32 call on the widened operands, 16-bit outputs rounded once.
+ * Errors: an activation outside FQL_ACT_*, an act_alpha that is not finite, or an act_limit that is not finite or <= 0
+ * (checked for both non-silu kinds) -> FQL_ERR_BAD_SHAPE, reported where the sibling reports its first FQL_ERR_BAD_SHAPE;
+ * every other check, its order and its code are the sibling's:
+ * fql_moe_glu_fwd: FQL_ERR_BAD_PRECISION (unknown, or FQL_PRECISION_FP8), FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0, N < 0, or
+ *   the activation arguments), FQL_ERR_ODD_K, FQL_ERR_DTYPE, T == 0 or N == 0 -> FQL_OK with nothing done,
+ *   FQL_ERR_NULL_POINTER, FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65535), FQL_ERR_ALIGNMENT, FQL_ERR_WORKSPACE,
+ *   FQL_ERR_LAUNCH.  Workspace: fql_moe_workspace_bytes(E, T, K, N, precision), unchanged.
+ * fql_lora_glu_shrink / fql_lora_glu_grad: FQL_ERR_BAD_SHAPE (rank, layout, dimensions, sizes, or the activation
+ *   arguments), FQL_ERR_DTYPE, the empty-call FQL_OK, FQL_ERR_NULL_POINTER, FQL_ERR_ALIGNMENT (w, or v and d, not 16-byte
+ *   aligned; gate_up not aligned to its element), FQL_ERR_LAUNCH.
+ * fql_glu_bwd: FQL_ERR_BAD_SHAPE (T < 0, F < 0, 2 T F past 2^31, or the activation arguments), FQL_ERR_DTYPE, the
+ *   empty-call FQL_OK, FQL_ERR_NULL_POINTER, dgate_up == gate_up -> FQL_ERR_BAD_SHAPE, a pointer not aligned to its element
+ *   -> FQL_ERR_ALIGNMENT, FQL_ERR_LAUNCH. */
+#define FQL_ACT_SILU 0
+#define FQL_ACT_GELU_TANH 1
+#define FQL_ACT_SWIGLU_CLAMP 2
+FQL_API int fql_moe_glu_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up, int in_dtype,
+                            const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                            int E, int T, int K, int N, int precision, int activation, float act_alpha, float act_limit,
+                            void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_lora_glu_shrink(const void *gate_up, int dtype, const float *w, int w_layout,
+                                const int32_t *tokens_per_expert, const int32_t *input_offsets, float *out, int E, int T,
+                                int C, int r, float scale, int activation, float act_alpha, float act_limit, void *stream);
+FQL_API int fql_lora_glu_grad(const void *gate_up, int dtype, const float *v, const int32_t *tokens_per_expert,
+                              const int32_t *input_offsets, float *d, int d_layout, int E, int T, int C, int r,
+                              float scale, int activation, float act_alpha, float act_limit, void *stream);
+FQL_API int fql_glu_bwd(const void *gate_up, int dtype, const void *dh, int dh_dtype, void *dgate_up, int out_dtype, int T,
+                        int F, int activation, float act_alpha, float act_limit, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -14,7 +14,9 @@ not, with a +inf row, an all-equal row and a row of mixed 0.0 / -0.0, each backw
 alone, ``router_score_topk`` at its defaults (the plain kernel variant) and with sigmoid + bias + groups + scale (the
 scored one); ``combine_any`` on four type pairs at N = 40 (16-byte accesses), 130 (pairs) and 129 (scalars), with and
 without the addend and its weight, and the float32 ``combine`` on a misaligned ``y``; ``QuantizedSparseMoEBlock`` with
-default and with scored routing, float32 and bfloat16, every gradient."""
+default and with scored routing, float32 and bfloat16, every gradient; and, behind all of these so that their operands are
+the ones they always were, the four gated ops, the gated FFN layers and the sparse block (with a shared expert) for
+``activation="gelu_tanh"`` and ``"swiglu_clamp"`` in the three element types."""
 import argparse
 import hashlib
 import os
@@ -296,6 +298,54 @@ def calls(dev, fq, ops):
                 out.backward(gy.to(out.dtype))
                 return out.detach(), logits.detach(), x_.grad, m.gate.weight.grad
             yield f"QuantizedSparseMoEBlock {tag} {dt}", block
+
+    # ---------------------------------------------------------------- activation kinds of the gated FFN (GeGLU, clamped SwiGLU)
+    # (behind everything else: the operands of the calls above come from the generator in the order they always did)
+    P, S, Z = d.weights(E, 40, 64)
+    gu, dh = d.randn(T, 128, scale=4.0), d.randn(T, 64)
+    A, v = d.randn(E, 4, 64, scale=0.1), d.randn(T, 4)
+    H, F, r = 64, 32, 4
+    gup, gus, guz = d.weights(E, 2 * F, H)
+    dp, ds, dz = d.weights(E, H, F)
+    ad = [d.randn(E, r, H, scale=0.1), d.randn(E, 2 * F, r, scale=0.1), d.randn(E, r, F, scale=0.1), d.randn(E, H, r, scale=0.1)]
+    x, gy = d.randn(T, H, scale=8.0), d.randn(T, H)
+    gate_w = d.randn(E, H)
+    for kind, kw in (("gelu_tanh", dict(activation="gelu_tanh")),
+                     ("swiglu_clamp", dict(activation="swiglu_clamp", activation_alpha=1.702, activation_limit=7.0))):
+        for dt in (F32, F16, BF16):
+            yield f"moe_gated_forward {kind} {dt}", lambda: ops.moe_gated_forward(P, S, Z, gu.to(dt), tpe, offs, **kw)
+            yield f"moe_gated_forward {kind} {dt}->f32", lambda: ops.moe_gated_forward(P, S, Z, gu.to(dt), tpe, offs, out_dtype=F32, **kw)
+            yield f"lora_gated_shrink {kind} {dt}", lambda: ops.lora_gated_shrink(gu.to(dt), A, "rc", tpe, offs, **kw)
+            yield f"lora_gated_grad {kind} {dt}", lambda: ops.lora_gated_grad(gu.to(dt), v, "rc", E, tpe, offs, **kw)
+            yield f"glu_backward {kind} {dt}", lambda: ops.glu_backward(gu.to(dt), dh.to(dt), **kw)
+            yield f"glu_backward {kind} {dt} mixed", lambda: ops.glu_backward(gu.to(dt), dh, out_dtype=F16, **kw)
+            act = None if dt == F32 else dt
+            m = fq.QuantizedMoEFFN(E, H, F, activation_dtype=act, **kw).to(dev)
+            for name, buf in zip(("gate_up_packed", "gate_up_scales", "gate_up_zero_points", "down_packed", "down_scales",
+                                  "down_zero_points"), (gup, gus, guz, dp, ds, dz)):
+                setattr(m, name, buf)
+
+            def layer(x_, *ad_):
+                return ops.moe_ffn_lora_forward(gup, gus, guz, dp, ds, dz, x_, *ad_, 2.0, tpe, offs, activation_dtype=act, **kw)
+            yield f"QuantizedMoEFFN {kind} {dt} dx", lambda: with_grads(
+                lambda x_: m(x_, tpe, offs), (x.to(dt),), lambda y_: gy.to(y_.dtype))
+            yield f"moe_ffn_lora_forward {kind} {dt} all grads", lambda: with_grads(
+                layer, (x.to(dt), *ad), lambda y_: gy.to(y_.dtype))
+        blk = fq.QuantizedSparseMoEBlock(E, H, F, top_k=2, shared_ffn_dim=F, **kw).to(dev)
+        for mod, sl in ((blk.experts, slice(0, E)), (blk.shared_experts, slice(0, 1))):
+            for name, buf in zip(("gate_up_packed", "gate_up_scales", "gate_up_zero_points", "down_packed", "down_scales",
+                                  "down_zero_points"), (gup, gus, guz, dp, ds, dz)):
+                setattr(mod, name, buf[sl])
+        blk.gate.weight.data.copy_(gate_w)
+
+        def glu_block(m=blk):
+            x_ = x.detach().clone().requires_grad_(True)
+            m.gate.weight.grad = None
+            out, logits = m(x_)
+            out.backward(gy)
+            return out.detach(), logits.detach(), x_.grad, m.gate.weight.grad
+        yield f"QuantizedSparseMoEBlock {kind} shared", glu_block
+
 
 def digest(t):
     t = t.detach().contiguous().cpu()
