@@ -113,6 +113,12 @@ _SYMBOLS = {
                           + [ctypes.c_float, ctypes.c_int] + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "fql_glu_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_int] * 3 + [ctypes.c_float] * 2
                     + [ctypes.c_void_p]),
+    "fql_moe_bias_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6
+                         + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_glu_bias_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_int] * 7 + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_bias_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3
+                          + [ctypes.c_void_p]),
     "fql_router_topk_fwd": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4),
     "fql_router_topk_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4
                             + [ctypes.c_void_p]),

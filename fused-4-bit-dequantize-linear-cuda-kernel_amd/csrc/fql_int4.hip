@@ -21,6 +21,7 @@
 #include "fql_w4_launch.h"
 #include "fql_ffn16_launch.h"
 #include "fql_glu_launch.h"
+#include "fql_bias_launch.h"
 #include <atomic>
 #include <random>
 
@@ -793,7 +794,8 @@ int fql_linear_bias_fwd_f32(const float *x, const uint8_t *packed, const float *
 static int moe_entry(const uint8_t *packed, const float *scales, const float *zps, const float *inputs,
                      const int32_t *row_index, int n_src, const int32_t *tokens_per_expert,
                      const int32_t *input_offsets, float *out, int E, int T, int K, int N, int precision,
-                     void *workspace, size_t workspace_bytes, void *stream, const float *row_weight = nullptr)
+                     void *workspace, size_t workspace_bytes, void *stream, const float *row_weight = nullptr,
+                     const float *bias = nullptr)            // bias [E][N]: added to expert e's rows in the epilogue
 {
     const int L = limbs_of(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
@@ -803,6 +805,7 @@ static int moe_entry(const uint8_t *packed, const float *scales, const float *zp
     if (!out) return FQL_ERR_NULL_POINTER;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (E == 0 || K == 0) {                           // nothing contributes: all rows zero
+        if (bias != nullptr) return FQL_ERR_BAD_SHAPE;    // (as linear_f32_core: not a path worth a kernel)
         return hipMemsetAsync(out, 0, (size_t)T * N * sizeof(float), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
     }
     if (!packed || !scales || !zps || !inputs || !tokens_per_expert || !input_offsets) return FQL_ERR_NULL_POINTER;
@@ -811,13 +814,13 @@ static int moe_entry(const uint8_t *packed, const float *scales, const float *zp
         Call c;
         c.x = inputs; c.gather = row_index; c.n_src = n_src; c.f8 = is_f8(precision);
         c.packed = packed; c.scales = scales; c.zps = zps;
-        c.out = out; c.row_weight = row_weight; c.st = st;
+        c.out = out; c.bias = bias; c.row_weight = row_weight; c.st = st;
         c.tpe = tokens_per_expert; c.offs = input_offsets;
         c.set_shape(E, T, K, N);
         return run_mfma(L, c, workspace, workspace_bytes);
     }
     if (row_index != nullptr || is_f8(precision) || row_weight != nullptr) return FQL_ERR_ALIGNMENT;     // the fused gather / row weights / fp8 exist on the MFMA path only
-    return run_generic(inputs, packed, scales, zps, out, tokens_per_expert, input_offsets, E, T, K, N, st);
+    return run_generic(inputs, packed, scales, zps, out, tokens_per_expert, input_offsets, E, T, K, N, st, bias);
 }
 
 int fql_moe_fwd_f32(const uint8_t *packed, const float *scales, const float *zps, const float *inputs,
@@ -893,13 +896,16 @@ int fql_linear_bias_fwd(const void *x, int in_dtype, const uint8_t *packed, cons
     return run_mfma(L, c, workspace, workspace_bytes);
 }
 
-int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
-                const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E, int T,
-                int K, int N, int precision, void *workspace, size_t workspace_bytes, void *stream)
+// fql_moe_fwd and, with a bias [E][N], fql_moe_bias_fwd: one body, the bias a member of the call record
+static int moe_typed_entry(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                           const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                           int out_dtype, int E, int T, int K, int N, int precision, void *workspace,
+                           size_t workspace_bytes, void *stream)
 {
     if (in_dtype == FQL_DTYPE_F32 && out_dtype == FQL_DTYPE_F32)
-        return fql_moe_fwd_f32(packed, scales, zps, static_cast<const float *>(inputs), tokens_per_expert, input_offsets,
-                               static_cast<float *>(out), E, T, K, N, precision, workspace, workspace_bytes, stream);
+        return moe_entry(packed, scales, zps, static_cast<const float *>(inputs), nullptr, 0, tokens_per_expert,
+                         input_offsets, static_cast<float *>(out), E, T, K, N, precision, workspace, workspace_bytes, stream,
+                         nullptr, bias);
     const int L = limbs_of(precision);
     if (L < 0) return FQL_ERR_BAD_PRECISION;
     if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
@@ -912,10 +918,28 @@ int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, co
     Call c;
     c.x = inputs; c.in_dtype = in_dtype; c.f8 = is_f8(precision);
     c.packed = packed; c.scales = scales; c.zps = zps;
-    c.out = out; c.out_dtype = out_dtype; c.st = static_cast<hipStream_t>(stream);
+    c.out = out; c.out_dtype = out_dtype; c.bias = bias; c.st = static_cast<hipStream_t>(stream);
     c.tpe = tokens_per_expert; c.offs = input_offsets;
     c.set_shape(E, T, K, N);
     return run_mfma(L, c, workspace, workspace_bytes);
+}
+
+int fql_moe_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E, int T,
+                int K, int N, int precision, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return moe_typed_entry(packed, scales, zps, inputs, in_dtype, tokens_per_expert, input_offsets, nullptr, out, out_dtype,
+                           E, T, K, N, precision, workspace, workspace_bytes, stream);
+}
+
+// fql_moe_fwd with a per-expert bias [E][N] float32 in the GEMM's epilogue (NULL: fql_moe_fwd exactly)
+int fql_moe_bias_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                     const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                     int out_dtype, int E, int T, int K, int N, int precision, void *workspace, size_t workspace_bytes,
+                     void *stream)
+{
+    return moe_typed_entry(packed, scales, zps, inputs, in_dtype, tokens_per_expert, input_offsets, bias, out, out_dtype, E,
+                           T, K, N, precision, workspace, workspace_bytes, stream);
 }
 
 // ---- rows that are already OCP e4m3 (BASELINE.json configs[4]): re-layout pre-pass + one fp8 MFMA pass
@@ -1178,6 +1202,55 @@ int fql_moe_glu_fwd(const uint8_t *packed, const float *scales, const float *zps
     c.tpe = tokens_per_expert; c.offs = input_offsets;
     c.set_shape(E, T, K, N);
     return run_mfma(L, c, workspace, workspace_bytes);
+}
+
+// fql_moe_glu_fwd with a per-expert bias [E][N] float32 in the GEMM's epilogue, for every activation kind (silu included)
+// and every element type: the checks of fql_moe_glu_fwd in its order, then the same call record plus the bias.  The record
+// decides the pre-pass as it always does (silu: the kernels of fql_act_quant.h / fql_ffn16.hip, the others: fql_glu.hip).
+int fql_moe_glu_bias_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up, int in_dtype,
+                         const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                         int out_dtype, int E, int T, int K, int N, int precision, int activation, float act_alpha,
+                         float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (bias == nullptr)
+        return fql_moe_glu_fwd(packed, scales, zps, gate_up, in_dtype, tokens_per_expert, input_offsets, out, out_dtype, E, T,
+                               K, N, precision, activation, act_alpha, act_limit, workspace, workspace_bytes, stream);
+    const int L = limbs_of(precision);
+    if (L < 0 || is_f8(precision)) return FQL_ERR_BAD_PRECISION;
+    if (E <= 0 || T < 0 || K <= 0 || N < 0) return FQL_ERR_BAD_SHAPE;
+    if (activation != FQL_ACT_SILU &&
+        ((activation != FQL_ACT_GELU_TANH && activation != FQL_ACT_SWIGLU_CLAMP) || !std::isfinite(act_alpha) ||
+         !std::isfinite(act_limit) || !(act_limit > 0.0f))) return FQL_ERR_BAD_SHAPE;
+    if (K & 1) return FQL_ERR_ODD_K;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!packed || !scales || !zps || !gate_up || !out) return FQL_ERR_NULL_POINTER;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
+    if (E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (!mfma_eligible(L, T, E, K, N, packed)) return FQL_ERR_ALIGNMENT;   // the fused activation exists on the MFMA path only
+    if ((reinterpret_cast<uintptr_t>(gate_up) & (dtype_bytes(in_dtype) - 1)) != 0) return FQL_ERR_ALIGNMENT;
+    Call c;
+    c.x = gate_up; c.in_dtype = in_dtype; c.gated = true;
+    if (activation != FQL_ACT_SILU) { c.act = activation; c.act_alpha = act_alpha; c.act_limit = act_limit; }
+    c.packed = packed; c.scales = scales; c.zps = zps;
+    c.out = out; c.out_dtype = out_dtype; c.bias = bias; c.st = static_cast<hipStream_t>(stream);
+    c.tpe = tokens_per_expert; c.offs = input_offsets;
+    c.set_shape(E, T, K, N);
+    return run_mfma(L, c, workspace, workspace_bytes);
+}
+
+// grad_bias[e][n] = sum over the rows of expert e of grad_rows[t][n] (csrc/fql_bias.hip): every output written
+int fql_moe_bias_grad(const void *grad_rows, int dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                      float *grad_bias, int E, int T, int N, void *stream)
+{
+    if (E < 0 || T < 0 || N < 0 || E > 65535 || N > 0x7fffff00) return FQL_ERR_BAD_SHAPE;
+    if (!valid_dtype(dtype)) return FQL_ERR_DTYPE;
+    if (E == 0 || N == 0) return FQL_OK;
+    if (!grad_bias || (T > 0 && !grad_rows)) return FQL_ERR_NULL_POINTER;
+    if (const int rc = table_check(tokens_per_expert, input_offsets, E)) return rc;
+    if (!elem_aligned(grad_rows, dtype_bytes(dtype)) || !elem_aligned(grad_bias, 4)) return FQL_ERR_ALIGNMENT;
+    return fql_bias_grad_launch(grad_rows, dtype, tokens_per_expert, input_offsets, grad_bias, E, T, N,
+                                static_cast<hipStream_t>(stream)) == 0 ? FQL_OK : FQL_ERR_LAUNCH;
 }
 
 int fql_route_plan_i32(const int32_t *expert_of_slot, int n_slots, int top_k, int E, int32_t *counts,

@@ -135,13 +135,16 @@ _FFN_ADAPTERS = ("gate_up_lora_A", "gate_up_lora_B", "down_lora_A", "down_lora_B
 class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     """``down(silu(gate(x)) * up(x))`` per expert with ``gate_up = W_gu x + s B_gu (A_gu x)`` and
     ``y = W_d h + s B_d (A_d h)``, ``s = alpha / rank``.  The INT4 buffers are frozen; the four adapters are the only
-    parameters (float32 whatever ``activation_dtype`` is)."""
+    parameters (float32 whatever ``activation_dtype`` is).  With ``expert_bias=True`` the layer also has the two bias
+    parameters of ``QuantizedMoEFFN`` (frozen until ``requires_grad_(True)``): ``gate_up = W_gu x + b_gu + s B_gu (A_gu x)``
+    and ``y = W_d h + b_d + s B_d (A_d h)``."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
                  precision: str = "default", activation_dtype=None, activation: str = "silu",
-                 activation_alpha: float = 1.702, activation_limit: float = 7.0):
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False):
         super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision, activation_dtype=activation_dtype,
-                         activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
+                         activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit,
+                         expert_bias=expert_bias)
         _check_rank(rank)
         self.rank = rank
         self.alpha = float(rank if alpha is None else alpha)
@@ -166,14 +169,18 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     def from_quantized(cls, layer: QuantizedMoEFFN, rank: int, alpha: float | None = None,
                        activation_dtype=None) -> "LoRAQuantizedMoEFFN":
         """Wrap an existing ``QuantizedMoEFFN``; the new module shares its buffers (no copy).  ``activation_dtype``
-        None keeps the wrapped layer's.  The activation kind is the wrapped layer's."""
+        None keeps the wrapped layer's.  The activation kind is the wrapped layer's, and so are its biases: the same
+        parameters, in the ``requires_grad`` state they have."""
         if activation_dtype is None:
             activation_dtype = layer.activation_dtype
         module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision,
                      activation_dtype=activation_dtype, activation=layer.activation,
-                     activation_alpha=layer.activation_alpha, activation_limit=layer.activation_limit)
+                     activation_alpha=layer.activation_alpha, activation_limit=layer.activation_limit,
+                     expert_bias=layer.expert_bias)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
+        if layer.expert_bias:
+            module.gate_up_bias, module.down_bias = layer.gate_up_bias, layer.down_bias
         dev = layer.gate_up_packed.device
         for name in _FFN_ADAPTERS:
             p = getattr(module, name)
@@ -195,7 +202,11 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
                                         self.scaling, tokens_per_expert, input_offsets, precision=self.precision,
                                         activation_dtype=self.activation_dtype, activation=self.activation,
                                         activation_alpha=self.activation_alpha,
-                                        activation_limit=self.activation_limit)
+                                        activation_limit=self.activation_limit, **self._bias_args())
+
+    def _bias_args(self):
+        """The biases as ``ops.moe_ffn_lora_forward`` takes them (nothing for a layer without ``expert_bias``)."""
+        return {"gate_up_bias": self.gate_up_bias, "down_bias": self.down_bias} if self.expert_bias else {}
 
     def extra_repr(self) -> str:
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, ffn_dim={self.ffn_dim}, "

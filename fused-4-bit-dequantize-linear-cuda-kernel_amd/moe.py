@@ -224,11 +224,18 @@ class QuantizedMoEFFN(nn.Module):
     (GeGLU, tanh form; Hugging Face's ``"gelu_pytorch_tanh"`` is accepted) or ``"swiglu_clamp"`` (gpt-oss:
     ``min(g, limit) * sigmoid(alpha * min(g, limit)) * (clamp(u, -limit, limit) + 1)`` with ``activation_alpha`` and
     ``activation_limit``).  It is configuration, not state: the state-dict keys and values are the same for every kind
-    (INTEGRATION.md section 13)."""
+    (INTEGRATION.md section 13).
+
+    ``expert_bias=True`` (gpt-oss) adds a bias to both projections, ``gate_up = W_gu x + b_gu`` and ``y = W_d h + b_d``,
+    each added in its GEMM's epilogue (on 16-bit activations before the one rounding): float32 ``nn.Parameter``s
+    ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H], zeros with ``requires_grad=False`` -- a loaded checkpoint is frozen
+    like the weights, ``requires_grad_(True)`` trains them (their gradient is ``ops.moe_bias_grad``, computed only
+    then).  Rows no expert covers stay zero.  A layer built without it has the state-dict keys it always had
+    (INTEGRATION.md section 14)."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, precision: str = "default",
                  activation_dtype=None, activation: str = "silu", activation_alpha: float = 1.702,
-                 activation_limit: float = 7.0):
+                 activation_limit: float = 7.0, expert_bias: bool = False):
         super().__init__()
         assert hidden_dim % 32 == 0 and ffn_dim % 32 == 0, "hidden_dim and ffn_dim must be multiples of 32"
         self.num_experts, self.hidden_dim, self.ffn_dim, self.precision = num_experts, hidden_dim, ffn_dim, precision
@@ -243,16 +250,35 @@ class QuantizedMoEFFN(nn.Module):
         self.register_buffer("down_packed", torch.zeros(E, H, F // 2, dtype=torch.uint8))
         self.register_buffer("down_scales", torch.zeros(E, H, dtype=torch.float32))
         self.register_buffer("down_zero_points", torch.zeros(E, H, dtype=torch.float32))
+        self.expert_bias = bool(expert_bias)
+        if self.expert_bias:                 # (no attribute at all otherwise: the state-dict keys stay those of before)
+            self.gate_up_bias = nn.Parameter(torch.zeros(E, 2 * F, dtype=torch.float32), requires_grad=False)
+            self.down_bias = nn.Parameter(torch.zeros(E, H, dtype=torch.float32), requires_grad=False)
 
     @classmethod
     def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor],
                      precision: str = "default", activation_dtype=None, activation: str = "silu",
-                     activation_alpha: float = 1.702, activation_limit: float = 7.0) -> "QuantizedMoEFFN":
-        """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` (nn.Linear weight layout)."""
+                     activation_alpha: float = 1.702, activation_limit: float = 7.0, gate_bias=None, up_bias=None,
+                     down_bias=None) -> "QuantizedMoEFFN":
+        """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` (nn.Linear weight layout).  ``gate_bias[e]``,
+        ``up_bias[e]``: ``[F]``; ``down_bias[e]``: ``[H]``: the per-expert biases, all three or none (then the layer has
+        no bias parameters)."""
         E = len(gate)
         F, H = gate[0].shape
+        given = [b is not None for b in (gate_bias, up_bias, down_bias)]
+        if any(given) and not all(given):
+            raise ValueError("gate_bias, up_bias and down_bias come together: pass all three or none")
+        if all(given):
+            for name, b, n in (("gate_bias", gate_bias, F), ("up_bias", up_bias, F), ("down_bias", down_bias, H)):
+                if len(b) != E or any(tuple(t.shape) != (n,) for t in b):
+                    raise ValueError(f"{name} must be a list of num_experts tensors of shape [{n}]")
         m = cls(E, H, F, precision, activation_dtype=activation_dtype, activation=activation,
-                activation_alpha=activation_alpha, activation_limit=activation_limit)
+                activation_alpha=activation_alpha, activation_limit=activation_limit, expert_bias=all(given))
+        if all(given):
+            dev = gate[0].device
+            with torch.no_grad():
+                m.gate_up_bias.data = torch.stack([torch.cat([g.float(), u.float()]) for g, u in zip(gate_bias, up_bias)]).to(dev)
+                m.down_bias.data = torch.stack([d.float() for d in down_bias]).to(dev)
         gu = [quantize_weights(torch.cat([g.float(), u.float()], dim=0)) for g, u in zip(gate, up)]
         dn = [quantize_weights(d.float()) for d in down]
         m.gate_up_packed = torch.stack([t[0] for t in gu])
@@ -271,14 +297,22 @@ class QuantizedMoEFFN(nn.Module):
         if self.activation_dtype is not None:
             from . import ops
             ops.check_activation_rows(inputs, "inputs", self.activation_dtype)
-        if torch.is_grad_enabled() and inputs.requires_grad:
+        b_gu, b_d = self.biases
+        if torch.is_grad_enabled() and (inputs.requires_grad or (self.expert_bias and (b_gu.requires_grad
+                                                                                      or b_d.requires_grad))):
             fn = _GatedFFNFn if self.activation_dtype is None else _GatedFFN16Fn
-            return fn.apply(inputs, tokens_per_expert, input_offsets, self)
+            return fn.apply(inputs, tokens_per_expert, input_offsets, self, b_gu, b_d)
         return _gated_ffn(self, inputs, tokens_per_expert, input_offsets)[0]
 
     @property
+    def biases(self):
+        """``(gate_up_bias, down_bias)``, or ``(None, None)`` for a layer built without ``expert_bias``."""
+        return (self.gate_up_bias, self.down_bias) if self.expert_bias else (None, None)
+
+    @property
     def total_memory_bytes(self) -> int:
-        return sum(b.numel() * b.element_size() for b in self.buffers())
+        return (sum(b.numel() * b.element_size() for b in self.buffers())
+                + sum(b.numel() * b.element_size() for b in self.biases if b is not None))
 
     @property
     def activation_args(self):
@@ -286,12 +320,13 @@ class QuantizedMoEFFN(nn.Module):
         return self.activation, self.activation_alpha, self.activation_limit
 
     def _activation_repr(self) -> str:
+        bias = ", expert_bias=True" if self.expert_bias else ""
         if self.activation == "silu":
-            return ""
+            return bias
         s = f", activation={self.activation}"
         if self.activation == "swiglu_clamp":
             s += f", activation_alpha={self.activation_alpha:g}, activation_limit={self.activation_limit:g}"
-        return s
+        return s + bias
 
     def extra_repr(self) -> str:
         return self._activation_repr().lstrip(", ")
@@ -311,24 +346,30 @@ def _gated_ffn(m, inputs, tpe, offs):
     its pre-pass.  On 16-bit activations each GEMM reads its operand as it is and rounds its result once."""
     from . import ops
     dt = m.activation_dtype
+    b_gu, b_d = m.biases                                    # (detached: a bias gradient is the autograd node's business)
+    bias_gu = {} if b_gu is None else {"bias": b_gu.detach()}
+    bias_d = {} if b_d is None else {"bias": b_d.detach()}
     if dt is None:                                          # the float32 layer takes float32 rows only
         gate_up = ops.moe_forward(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe, offs,
-                                  precision=m.precision)
+                                  precision=m.precision, **bias_gu)
     else:
         gate_up = ops.moe_forward_any(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, inputs, None, tpe,
-                                      offs, precision=m.precision, out_dtype=dt)
+                                      offs, precision=m.precision, out_dtype=dt, **bias_gu)
     return ops.moe_gated_forward(m.down_packed, m.down_scales, m.down_zero_points, gate_up, tpe, offs,
                                  precision=m.precision, out_dtype=dt, activation=m.activation,
-                                 activation_alpha=m.activation_alpha, activation_limit=m.activation_limit), gate_up
+                                 activation_alpha=m.activation_alpha, activation_limit=m.activation_limit,
+                                 **bias_d), gate_up
 
 
 class _GatedFFNFn(torch.autograd.Function):
     """``QuantizedMoEFFN`` with the input gradient.  Keeps the ``gate_up`` tensor the forward materialises anyway; the
     backward is ``dh`` on the down weights, ``dg = dh * u * silu'(g)`` and ``du = dh * silu(g)`` (torch elementwise),
-    then ``dx`` on the gate / up weights -- both GEMMs the fused kernel of csrc/fql_bwd.h."""
+    then ``dx`` on the gate / up weights -- both GEMMs the fused kernel of csrc/fql_bwd.h.  ``b_gu`` / ``b_d`` are the
+    layer's biases (None without ``expert_bias``): the forward reads them from ``m``, they are inputs so that autograd can
+    ask for their gradients, ``ops.moe_bias_grad`` of dgu and of gy, launched only for a bias that requires grad."""
 
     @staticmethod
-    def forward(ctx, inputs, tokens_per_expert, input_offsets, m):
+    def forward(ctx, inputs, tokens_per_expert, input_offsets, m, b_gu=None, b_d=None):
         out, gate_up = _gated_ffn(m, inputs, tokens_per_expert, input_offsets)
         ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
         ctx.m = m
@@ -341,7 +382,12 @@ class _GatedFFNFn(torch.autograd.Function):
         gate_up, tpe, offs = ctx.saved_tensors
         m = ctx.m
         K = gate_up.shape[1] // 2
-        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy.to(torch.float32), tpe, offs,
+        need_x, need_bgu, need_bd = ctx.needs_input_grad[0], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        gy = gy.to(torch.float32)
+        gbd = ops.moe_bias_grad(gy, m.num_experts, tpe, offs) if need_bd else None
+        if not (need_x or need_bgu):
+            return None, None, None, None, None, gbd
+        dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
                                     precision=m.precision)
         if m.activation == "silu":
             g, u = gate_up[:, :K], gate_up[:, K:]
@@ -349,9 +395,10 @@ class _GatedFFNFn(torch.autograd.Function):
             dgu = torch.cat([dh * u * (sig * (1.0 + g * (1.0 - sig))), dh * (g * sig)], dim=1)
         else:                                                   # the other kinds: one streaming kernel
             dgu = ops.glu_backward(gate_up, dh, *m.activation_args)
+        gbgu = ops.moe_bias_grad(dgu, m.num_experts, tpe, offs) if need_bgu else None
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
-                                    precision=m.precision)
-        return dx, None, None, None
+                                    precision=m.precision) if need_x else None
+        return dx, None, None, None, gbgu, gbd
 
 
 class _GatedFFN16Fn(_GatedFFNFn):
@@ -367,12 +414,17 @@ class _GatedFFN16Fn(_GatedFFNFn):
         m = ctx.m
         dt = m.activation_dtype
         ops.check_activation_rows(gy, "the incoming gradient", dt)
+        need_x, need_bgu, need_bd = ctx.needs_input_grad[0], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        gbd = ops.moe_bias_grad(gy, m.num_experts, tpe, offs) if need_bd else None
+        if not (need_x or need_bgu):
+            return None, None, None, None, None, gbd
         dh = ops.moe_backward_input(m.down_packed, m.down_scales, m.down_zero_points, gy, tpe, offs,
                                     precision=m.precision, out_dtype=dt)
         dgu = ops.glu_backward(gate_up, dh, *m.activation_args, out_dtype=dt)
+        gbgu = ops.moe_bias_grad(dgu, m.num_experts, tpe, offs) if need_bgu else None
         dx = ops.moe_backward_input(m.gate_up_packed, m.gate_up_scales, m.gate_up_zero_points, dgu, tpe, offs,
-                                    precision=m.precision, out_dtype=dt)
-        return dx, None, None, None
+                                    precision=m.precision, out_dtype=dt) if need_x else None
+        return dx, None, None, None, gbgu, gbd
 
 
 class QuantizedSparseMoEBlock(nn.Module):
@@ -405,13 +457,21 @@ class QuantizedSparseMoEBlock(nn.Module):
 
     ``activation`` (with ``activation_alpha`` / ``activation_limit``) is handed to the experts and the shared expert the
     block builds.  A module passed in as ``experts`` / ``shared_experts`` keeps its own; an explicit block argument that
-    contradicts it raises ``ValueError``."""
+    contradicts it raises ``ValueError``.
+
+    ``expert_bias`` (gpt-oss) is handed to the experts the block builds (``QuantizedMoEFFN(expert_bias=True)``: frozen
+    float32 parameters ``experts.gate_up_bias`` / ``experts.down_bias``); a module passed in as ``experts`` keeps its
+    own, and an explicit argument that contradicts it raises ``ValueError``.  The combine multiplies the routing weight
+    into an expert's output after its bias.  ``router_bias=True`` makes ``gate`` an ``nn.Linear(..., bias=True)``
+    (``gate.bias``, gpt-oss's ``router.bias``: float, trainable, run by torch, part of ``router_logits``).  Both off: the
+    state-dict keys of before."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
                  n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
                  selection_bias: bool = False, shared_ffn_dim: int = 0, shared_experts=None,
-                 shared_expert_gate: bool = False, activation=None, activation_alpha=None, activation_limit=None):
+                 shared_expert_gate: bool = False, activation=None, activation_alpha=None, activation_limit=None,
+                 expert_bias=None, router_bias: bool = False):
         super().__init__()
         from . import ops
         # None: not given (a built expert takes the default, a passed-in one keeps its own)
@@ -444,11 +504,15 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise ValueError("routed_scaling_factor must be finite")
         if experts is None:
             experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
-                                      activation_dtype=activation_dtype, **act_kw)
+                                      activation_dtype=activation_dtype, expert_bias=bool(expert_bias), **act_kw)
         elif (experts.num_experts, experts.hidden_dim, experts.ffn_dim) != (num_experts, hidden_dim, ffn_dim):
             raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
         else:
             check_activation("experts", experts)
+            have_bias = bool(getattr(experts, "expert_bias", False))
+            if expert_bias is not None and bool(expert_bias) != have_bias:      # None: not given, the module keeps its own
+                raise ValueError(f"expert_bias={expert_bias!r} contradicts experts, built with expert_bias={have_bias!r}: "
+                                 "leave the block's argument out, or build experts with it")
         if shared_ffn_dim < 0 or shared_ffn_dim % 32 != 0:
             raise ValueError(f"shared_ffn_dim must be a non-negative multiple of 32, got {shared_ffn_dim}")
         if shared_experts is not None:
@@ -466,7 +530,7 @@ class QuantizedSparseMoEBlock(nn.Module):
         self.top_k, self.renormalize = top_k, bool(renormalize)
         self.scoring, self.n_group, self.topk_group, self.group_top = scoring, n_group, topk_group, group_top
         self.routed_scaling_factor = float(routed_scaling_factor)
-        self.gate = nn.Linear(hidden_dim, num_experts, bias=False)
+        self.gate = nn.Linear(hidden_dim, num_experts, bias=bool(router_bias))
         if selection_bias:                   # the checkpoint's name: gate.e_score_correction_bias
             self.gate.register_buffer("e_score_correction_bias", torch.zeros(num_experts, dtype=torch.float32))
         self.experts = experts
@@ -480,19 +544,23 @@ class QuantizedSparseMoEBlock(nn.Module):
     def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
                      down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
                      renormalize: bool = True, shared=None, shared_expert_gate_weight=None, activation: str = "silu",
-                     activation_alpha: float = 1.702, activation_limit: float = 7.0,
-                     **routing) -> "QuantizedSparseMoEBlock":
+                     activation_alpha: float = 1.702, activation_limit: float = 7.0, router_bias=None, gate_bias=None,
+                     up_bias=None, down_bias=None, **routing) -> "QuantizedSparseMoEBlock":
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
         ``QuantizedMoEFFN.from_weights`` takes them.  ``shared``: ``(gate [Fs, H], up [Fs, H], down [H, Fs])`` of the
         shared expert; ``shared_expert_gate_weight`` [1, H]: the weight of its sigmoid gate.  ``routing``: the
         constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor`` and
-        ``selection_bias``.  ``activation`` (and its two floats): the experts' and the shared expert's."""
+        ``selection_bias``.  ``activation`` (and its two floats): the experts' and the shared expert's.
+        ``router_bias`` [E]: the bias of the router (``gate.bias``); ``gate_bias[e]``, ``up_bias[e]`` [F] and
+        ``down_bias[e]`` [H]: the experts' biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
         act = dict(activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
         experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype,
-                                               **act)
+                                               gate_bias=gate_bias, up_bias=up_bias, down_bias=down_bias, **act)
         E, H = gate_weight.shape
         if E != experts.num_experts or H != experts.hidden_dim:
             raise ValueError("gate_weight must be [num_experts, hidden_dim]")
+        if router_bias is not None and tuple(router_bias.shape) != (E,):
+            raise ValueError("router_bias must be [num_experts]")
         shared_experts = None
         if shared is not None:
             sg, su, sd = shared
@@ -502,9 +570,12 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise ValueError("shared_expert_gate_weight must be [1, hidden_dim]")
         m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
                 renormalize=renormalize, experts=experts, shared_experts=shared_experts,
-                shared_expert_gate=shared_expert_gate_weight is not None, **routing)
+                shared_expert_gate=shared_expert_gate_weight is not None, router_bias=router_bias is not None,
+                **routing)
         with torch.no_grad():
             m.gate.weight.copy_(gate_weight.float())
+            if router_bias is not None:
+                m.gate.bias.copy_(router_bias.float())
             if shared_expert_gate_weight is not None:
                 m.shared_expert_gate.weight.copy_(shared_expert_gate_weight.float())
         return m
@@ -533,8 +604,10 @@ class QuantizedSparseMoEBlock(nn.Module):
             bias.add_(torch.sign(counts.mean() - counts), alpha=rate)
 
     def router_logits(self, x2: torch.Tensor) -> torch.Tensor:
-        w = self.gate.weight
-        return nn.functional.linear(x2, w if w.dtype == x2.dtype else w.to(x2.dtype))
+        w, b = self.gate.weight, self.gate.bias
+        if b is not None and b.dtype != x2.dtype:
+            b = b.to(x2.dtype)
+        return nn.functional.linear(x2, w if w.dtype == x2.dtype else w.to(x2.dtype), b)
 
     def shared_output(self, x2: torch.Tensor, x_gate=None):
         """``(s [T, H], aw [T] float32 or None)``: the shared expert on the tokens themselves (one segment of all rows, its
@@ -612,4 +685,6 @@ class QuantizedSparseMoEBlock(nn.Module):
             s += f", shared_ffn_dim={self.shared_experts.ffn_dim}"
         if getattr(self, "shared_expert_gate", None) is not None:
             s += ", shared_expert_gate=True"
+        if self.gate.bias is not None:
+            s += ", router_bias=True"
         return s + self.experts._activation_repr()

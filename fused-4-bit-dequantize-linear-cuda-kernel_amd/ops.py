@@ -153,10 +153,15 @@ def _check_group_weights(packed_weights, scales, zero_points, dev, K):
     return packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous(), group
 
 
-def _check_bias(bias, N, dev):
-    """``bias`` None, or float32 with N elements on ``dev`` (returned contiguous)."""
+def _check_bias(bias, N, dev, E=None):
+    """``bias`` None, or float32 with N elements on ``dev`` (returned contiguous).  ``E``: the per-expert bias of a grouped
+    GEMM, float32 [E, N]."""
     if bias is None:
         return None
+    if E is not None:
+        if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or tuple(bias.shape) != (E, N):
+            raise RuntimeError("bias must be a float32 [num_experts, ffn_dim] tensor on the inputs' device")
+        return bias.contiguous()
     if not bias.is_cuda or bias.device != dev or bias.dtype != torch.float32 or bias.numel() != N:
         raise RuntimeError("bias must be a float32 tensor with output_dim elements on the input's device")
     return bias.contiguous()
@@ -256,19 +261,22 @@ def moe_group_forward(packed_weights, scales, zero_points, inputs, tokens_per_ex
 
 
 def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_per_expert,
-                input_offsets, precision="default"):
+                input_offsets, precision="default", bias=None):
     """Grouped per-expert INT4 GEMM over rows pre-grouped by expert.
 
     packed_weights [E,N,K/2] u8, scales/zero_points [E,N] f32, inputs [T,K] f32,
     tokens_per_expert / input_offsets [E] int32 on the device (consumed there, no .item()).
     ``expert_ids`` is accepted and ignored, as in the reference (csrc/moe_int4_kernel.cu:98).
     Returns [T,N] float32; rows covered by no expert are zero (reference: torch::zeros :109).
-    Under autograd (grad mode on, ``inputs`` requiring grad) the input gradient runs on the GPU too.
+    ``bias`` [E,N] float32 (optional, not in the reference): expert e's bias is added to the rows of expert e in the
+    kernels' epilogues; rows no expert covers stay zero.  Without it the call is what it always was.
+    Under autograd (grad mode on, ``inputs`` or ``bias`` requiring grad) the input gradient runs on the GPU too, and the
+    bias gradient is ``moe_bias_grad``.
     """
     del expert_ids
-    if _wants_grad(inputs):
+    if _wants_grad(inputs, bias):
         return _MoEFn.apply(inputs, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, precision,
-                            None, False)
+                            None, False, bias)
     if not inputs.is_cuda:
         raise RuntimeError("inputs must be a CUDA tensor")
     if inputs.dtype != torch.float32 or inputs.dim() != 2:
@@ -277,8 +285,14 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
     dev = inputs.device
     packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
     prec = _precision(precision)
     out = torch.empty((T, N), dtype=torch.float32, device=dev)
+    if bias is not None:
+        _launch("fql_moe_bias_fwd", dev, packed_weights, scales, zero_points, inputs.contiguous(), _native.DTYPE_F32, tpe,
+                offs, bias, out, _native.DTYPE_F32, E, T, K, N, prec,
+                ws_bytes=_native.lib().fql_moe_workspace_bytes(E, T, K, N, prec))
+        return out
     _launch("fql_moe_fwd_f32", dev, packed_weights, scales, zero_points, inputs.contiguous(), tpe, offs, out,
             E, T, K, N, prec, ws_bytes=_native.lib().fql_moe_workspace_bytes(E, T, K, N, prec))
     return out
@@ -317,19 +331,20 @@ def linear_forward_any(input, packed_weights, scales, zero_points, precision="de
 
 
 def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tokens_per_expert, input_offsets,
-                    precision="default", out_dtype=None):
+                    precision="default", out_dtype=None, bias=None):
     """``moe_forward`` for float32 / float16 / bfloat16 rows (the reference's MoE benches feed float16,
     benchmark/moe_grouped_gemm/moe_int4_module.py:161-165), output in ``out_dtype`` (default: the input's).
-    Equal bit for bit to ``moe_forward(inputs.float()).to(out_dtype)``."""
+    Equal bit for bit to ``moe_forward(inputs.float(), bias=bias).to(out_dtype)``: a 16-bit result is rounded once, after
+    the per-expert ``bias`` [E, N] float32 (optional)."""
     out_dtype = inputs.dtype if out_dtype is None else out_dtype
     if inputs.dtype not in _DTYPES or out_dtype not in _DTYPES:
         raise RuntimeError("activations and outputs must be float32, float16 or bfloat16")
-    if _wants_grad(inputs):
+    if _wants_grad(inputs, bias):
         return _MoEFn.apply(inputs, packed_weights, scales, zero_points, tokens_per_expert, input_offsets, precision,
-                            out_dtype, True)
+                            out_dtype, True, bias)
     if inputs.dtype == torch.float32 and out_dtype == torch.float32:
         return moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_per_expert, input_offsets,
-                           precision=precision)
+                           precision=precision, bias=bias)
     prec = _precision(precision)
     L = _native.lib()
     ok = (inputs.is_cuda and inputs.dim() == 2 and packed_weights.is_cuda and packed_weights.dim() == 3
@@ -338,12 +353,18 @@ def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tok
                                                  packed_weights.shape[1], prec, packed_weights.data_ptr(), 1) == 1
     if not native:
         return moe_forward(packed_weights, scales, zero_points, inputs.float().contiguous(), expert_ids,
-                           tokens_per_expert, input_offsets, precision=precision).to(out_dtype)
+                           tokens_per_expert, input_offsets, precision=precision, bias=bias).to(out_dtype)
     T, K = inputs.shape
     dev = inputs.device
     packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    if bias is not None:
+        _launch("fql_moe_bias_fwd", dev, packed_weights, scales, zero_points, inputs.contiguous(), _DTYPES[inputs.dtype],
+                tpe, offs, bias, out, _DTYPES[out_dtype], E, T, K, N, prec,
+                ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
+        return out
     _launch("fql_moe_fwd", dev, packed_weights, scales, zero_points, inputs.contiguous(), _DTYPES[inputs.dtype], tpe,
             offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
     return out
@@ -391,15 +412,17 @@ def moe_gather_forward(packed_weights, scales, zero_points, tokens, row_index, t
 
 def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_expert, input_offsets,
                       precision="default", out_dtype=None, activation="silu", activation_alpha=1.702,
-                      activation_limit=7.0):
+                      activation_limit=7.0, bias=None):
     """Second GEMM of a gated FFN expert with the activation fused into its pre-pass:
     ``out[t] = W_e @ (silu(gate_up[t, :K]) * gate_up[t, K:])``; ``gate_up`` [T, 2K] float32 / float16 / bfloat16 (the
     output of the fused gate|up projection), ``packed_weights`` [E, N, K/2].  The [T, K] hidden activation is never
     written.  The result has ``out_dtype`` (default: ``gate_up``'s type); a 16-bit ``gate_up`` is read as it is and a
     16-bit result is rounded once: bit for bit ``moe_gated_forward(gate_up.float()).to(out_dtype)``.
     ``activation``: ``"silu"``, ``"gelu_tanh"`` (GeGLU) or ``"swiglu_clamp"`` (gpt-oss, with ``activation_alpha`` and
-    ``activation_limit``) in place of silu(g) * u (``activation_of``)."""
-    _forward_only("moe_gated_forward", gate_up)
+    ``activation_limit``) in place of silu(g) * u (``activation_of``).
+    ``bias`` [E, N] float32 (optional): expert e's bias is added to the rows of expert e in the GEMM's epilogue, before
+    the one rounding of a 16-bit result; rows no expert covers stay zero."""
+    _forward_only("moe_gated_forward", gate_up, bias)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     if not gate_up.is_cuda or gate_up.dtype not in _DTYPES or gate_up.dim() != 2:
         raise RuntimeError("gate_up must be a CUDA float32 (or float16 / bfloat16) [T, 2K] tensor")
@@ -413,6 +436,7 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
         raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
     packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
     L = _native.lib()
     prec = _precision(precision)
     typed = gate_up.dtype != torch.float32 or out_dtype != torch.float32
@@ -421,7 +445,11 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
         # off the 16-bit MFMA path: widen and round around the float32 call (the same contract)
         gate_up, round_to, out_dtype = gate_up.float(), out_dtype, torch.float32
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    if kind == "silu":
+    if bias is not None:
+        _launch("fql_moe_glu_bias_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(),
+                _DTYPES[gate_up.dtype], tpe, offs, bias, out, _DTYPES[out_dtype], E, T, K, N, prec, _ACTIVATIONS[kind],
+                act_alpha, act_limit, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
+    elif kind == "silu":
         _launch("fql_moe_gated_fwd", dev, packed_weights, scales, zero_points, gate_up.contiguous(), _DTYPES[gate_up.dtype],
                 tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
     else:
@@ -938,6 +966,27 @@ def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per
     return out
 
 
+def moe_bias_grad(grad_rows, num_experts, tokens_per_expert=None, input_offsets=None):
+    """Gradient of a per-expert bias: ``grad_bias[e] = sum of grad_rows[t] over the rows t of expert e`` -> [E, N] float32.
+    ``grad_rows`` [T, N] float32 / float16 / bfloat16 (read as it is, widened exactly); the expert table as
+    ``moe_forward`` takes it, or none with ``num_experts == 1`` (all rows).  One launch, float32 accumulation, no atomics:
+    an expert's summation order depends on its row count alone, so the result is run-to-run identical and does not change
+    when the table is permuted.  Experts without rows get zeros (csrc/fql_bias.hip)."""
+    if not grad_rows.is_cuda or grad_rows.dtype not in _DTYPES or grad_rows.dim() != 2:
+        raise RuntimeError("grad_rows must be a CUDA float32, float16 or bfloat16 [T, N] tensor")
+    dev = grad_rows.device
+    E = int(num_experts)
+    if E < 0:
+        raise RuntimeError("num_experts must not be negative")
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
+    T, N = grad_rows.shape
+    out = torch.empty((E, N), dtype=torch.float32, device=dev)
+    if E == 0 or N == 0:
+        return out
+    _launch("fql_moe_bias_grad", dev, grad_rows.contiguous(), _DTYPES[grad_rows.dtype], tpe, offs, out, E, T, N)
+    return out
+
+
 # rows of per-group weights dequantised at a time by the unfused backward (bounds its float32 transient to
 # GROUP_BWD_CHUNK * K * 4 bytes)
 GROUP_BWD_CHUNK = 1024
@@ -1028,23 +1077,28 @@ class _LinearFn(torch.autograd.Function):
 
 
 class _MoEFn(torch.autograd.Function):
-    """``moe_forward`` / ``moe_forward_any`` with the grouped input gradient.  Saves the weight buffers and the expert
-    table only."""
+    """``moe_forward`` / ``moe_forward_any`` with the grouped input gradient and, for a per-expert ``bias`` that requires
+    grad, its gradient (``moe_bias_grad`` of the incoming gradient).  Saves the weight buffers and the expert table only."""
 
     @staticmethod
-    def forward(ctx, inputs, packed, scales, zps, tpe, offs, precision, out_dtype, any_dtype):
+    def forward(ctx, inputs, packed, scales, zps, tpe, offs, precision, out_dtype, any_dtype, bias=None):
         ctx.save_for_backward(packed, scales, zps, tpe, offs)
         ctx.precision, ctx.x_dtype = precision, inputs.dtype
         if any_dtype:
-            return moe_forward_any(packed, scales, zps, inputs, None, tpe, offs, precision=precision, out_dtype=out_dtype)
-        return moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision)
+            return moe_forward_any(packed, scales, zps, inputs, None, tpe, offs, precision=precision, out_dtype=out_dtype,
+                                   bias=bias)
+        return moe_forward(packed, scales, zps, inputs, None, tpe, offs, precision=precision, bias=bias)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         packed, scales, zps, tpe, offs = ctx.saved_tensors
-        gx = moe_backward_input(packed, scales, zps, gy, tpe, offs, precision=ctx.precision, out_dtype=ctx.x_dtype)
-        return gx, None, None, None, None, None, None, None, None
+        gx = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = moe_backward_input(packed, scales, zps, gy, tpe, offs, precision=ctx.precision, out_dtype=ctx.x_dtype)
+        if len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]:
+            gb = moe_bias_grad(_grad_rows(gy), packed.shape[0], tpe, offs)
+        return gx, None, None, None, None, None, None, None, None, gb
 
 
 class _CombineFn(torch.autograd.Function):
@@ -1513,7 +1567,7 @@ def check_activation_rows(t, name, dt):
 def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps, inputs,
                          gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert,
                          input_offsets, precision="default", activation_dtype=None, activation="silu",
-                         activation_alpha=1.702, activation_limit=7.0):
+                         activation_alpha=1.702, activation_limit=7.0, gate_up_bias=None, down_bias=None):
     """Gated INT4 FFN experts with a low-rank adapter on each projection: for the rows t of expert e,
     ``gu = W_gu x + s B_gu (A_gu x)``, ``h = silu(gu[:F]) * gu[F:]`` (never stored), ``y = W_d h + s B_d (A_d h)``; rows
     no expert covers are zero.  ``inputs`` [T, H] float32, stacked gate|up weights [E, 2F, H/2], down weights
@@ -1525,7 +1579,12 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
     adapters and their gradients stay float32.  Five tensors are rounded, once each.
 
     ``activation`` (with ``activation_alpha``, ``activation_limit``; ``activation_of``) replaces silu(g) * u by
-    another kind of h in the forward and in every gradient."""
+    another kind of h in the forward and in every gradient.
+
+    ``gate_up_bias`` [E, 2F] / ``down_bias`` [E, H] float32 (each optional): per-expert biases of the two projections,
+    ``gu = W_gu x + b_gu + s B_gu (A_gu x)`` and ``y = W_d h + b_d + s B_d (A_d h)``.  A bias is part of the base GEMM's
+    float32 result (its epilogue) and the adapter term is added after it.  Differentiable in them too
+    (``moe_bias_grad`` of dgu and of the incoming gradient), computed only for a bias that requires grad."""
     act = activation_of(activation, activation_alpha, activation_limit)
     dt = activation_dtype_of(activation_dtype)
     if dt is not None:
@@ -1549,26 +1608,29 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
         raise RuntimeError("the gate_up and down adapters must have the same rank")
     weights = (gate_up_packed, gate_up_scales, gate_up_zps, down_packed, down_scales, down_zps)
     adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
-    if _wants_grad(inputs, *adapters):
+    biases = (_check_bias(gate_up_bias, F2, inputs.device, E), _check_bias(down_bias, H, inputs.device, E))
+    if _wants_grad(inputs, *adapters, *biases):
         return _MoEFFNLoRAFn.apply(inputs, *adapters, *weights, tokens_per_expert, input_offsets, float(scaling),
-                                   precision, dt, act)
+                                   precision, dt, act, *biases)
     return _moe_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets,
-                               precision, act)[0]
+                               precision, act, biases)[0]
 
 
-def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision, act=("silu", 1.702, 7.0)):
+def _moe_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, precision, act=("silu", 1.702, 7.0),
+                        biases=(None, None)):
     """Returns (y, gate_up, U_gu, U_d), y and gate_up in ``inputs``' type: each base GEMM reads its operand as it is and
-    writes float32, and the expand adds the adapter term to that in place (float32) or writes the sum once in the 16-bit
-    type -- gate_up (rounding 1) and y (rounding 2)."""
+    writes float32 (its per-expert bias, one of ``biases``, included), and the expand adds the adapter term to that in
+    place (float32) or writes the sum once in the 16-bit type -- gate_up (rounding 1) and y (rounding 2)."""
     gup, gus, guz, dp, ds, dz = weights
     A_gu, B_gu, A_d, B_d = adapters
     dt = inputs.dtype
-    gu32 = moe_forward_any(gup, gus, guz, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32)
+    gu32 = moe_forward_any(gup, gus, guz, inputs, None, tpe, offs, precision=precision, out_dtype=torch.float32,
+                           bias=biases[0])
     u_gu = lora_shrink(inputs, A_gu, "rc", tpe, offs)
     gate_up = _expand_into(u_gu, B_gu, "cr", gu32, dt, tpe, offs, scaling)
     del gu32
     y32 = moe_gated_forward(dp, ds, dz, gate_up, tpe, offs, precision=precision, out_dtype=torch.float32,
-                            activation=act[0], activation_alpha=act[1], activation_limit=act[2])
+                            activation=act[0], activation_alpha=act[1], activation_limit=act[2], bias=biases[1])
     u_d = _lora_shrink(gate_up, A_d, "rc", tpe, offs, 1.0, gated=True, act=act)
     return _expand_into(u_d, B_d, "cr", y32, dt, tpe, offs, scaling), gate_up, u_gu, u_d
 
@@ -1580,10 +1642,10 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs, scaling, precision, dt=None,
-                act=("silu", 1.702, 7.0)):
+                act=("silu", 1.702, 7.0), b_gu=None, b_d=None):
         x = inputs.contiguous()
         y, gate_up, u_gu, u_d = _moe_ffn_lora_apply((gup, gus, guz, dp, ds, dz), x, (A_gu, B_gu, A_d, B_d), scaling,
-                                                    tpe, offs, precision, act)
+                                                    tpe, offs, precision, act, (b_gu, b_d))
         ctx.save_for_backward(x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs)
         ctx.scaling, ctx.precision, ctx.act_dtype, ctx.act = scaling, precision, dt, act
         return y
@@ -1596,16 +1658,19 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
         swiglu_backward writes dgu (rounding 4).  Adapter gradients are float32."""
         x, gate_up, u_gu, u_d, A_gu, B_gu, A_d, B_d, gup, gus, guz, dp, ds, dz, tpe, offs = ctx.saved_tensors
         need_x, need_Agu, need_Bgu, need_Ad, need_Bd = ctx.needs_input_grad[:5]
+        need_bgu, need_bd = (tuple(ctx.needs_input_grad[17:19]) + (False, False))[:2]      # the two per-expert biases
         E, s, prec = gup.shape[0], ctx.scaling, ctx.precision
         if ctx.act_dtype is not None:
             check_activation_rows(gy, "the incoming gradient", ctx.act_dtype)
             g, dt = gy.contiguous(), ctx.act_dtype
         else:
             g, dt = gy.to(torch.float32).contiguous(), torch.float32
-        gx = gAgu = gBgu = gAd = gBd = None
+        gx = gAgu = gBgu = gAd = gBd = gbgu = gbd = None
         if need_Bd:
             gBd = lora_grad(g, u_d, "cr", E, tpe, offs, scale=s)                         # dB_d = s dY^T U_d
-        through = need_x or need_Agu or need_Bgu                                        # anything upstream of h
+        if need_bd:
+            gbd = moe_bias_grad(g, E, tpe, offs)                                         # db_d = sum of dY per expert
+        through = need_x or need_Agu or need_Bgu or need_bgu                            # anything upstream of h
         if through or need_Ad:
             du_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dU_d = s dY B_d
             if need_Ad:
@@ -1617,6 +1682,8 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
             del dh
             if need_Bgu:
                 gBgu = lora_grad(dgu, u_gu, "cr", E, tpe, offs, scale=s)                 # dB_gu = s dgu^T U_gu
+            if need_bgu:
+                gbgu = moe_bias_grad(dgu, E, tpe, offs)                                  # db_gu = sum of dgu per expert
             if need_x or need_Agu:
                 du_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dU_gu = s dgu B_gu
                 if need_x:
@@ -1624,4 +1691,4 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
                     gx = _expand_into(du_gu, A_gu, "rc", gx, dt, tpe, offs)              # dx = dgu W_gu + dU_gu A_gu
                 if need_Agu:
                     gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
-        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 12
+        return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 12 + (gbgu, gbd)

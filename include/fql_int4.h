@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 300 /* 0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 310 /* 0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -714,6 +714,43 @@ FQL_API int fql_lora_glu_grad(const void *gate_up, int dtype, const float *v, co
                               float scale, int activation, float act_alpha, float act_limit, void *stream);
 FQL_API int fql_glu_bwd(const void *gate_up, int dtype, const void *dh, int dh_dtype, void *dgate_up, int out_dtype, int T,
                         int F, int activation, float act_alpha, float act_limit, void *stream);
+
+/* ---- per-expert biases of the grouped GEMM (FQL_VERSION 310) ----
+ * fql_moe_bias_fwd: fql_moe_fwd with `const float *bias` in front of `out`: [E][N] float32, expert e's bias is added to the
+ *   rows of expert e in the GEMM's epilogue, out = dtype(fl32(acc + bias[e][n])) -- the float32 result of fql_moe_fwd plus
+ *   the bias, rounded once for a 16-bit out.  Rows no expert covers stay exactly zero: the bias belongs to an expert, not
+ *   to the output.  bias == NULL: the call IS fql_moe_fwd (same kernels, same bits, same return codes).  With a bias the
+ *   checks, their order and their codes are fql_moe_fwd's (16-bit I/O off the MFMA path: FQL_ERR_DTYPE; float32 off it: the
+ *   generic kernel, which takes the bias too), but E == 0 or K == 0 is FQL_ERR_BAD_SHAPE where the float32 call writes
+ *   zeros (an empty contraction plus a bias is not a path worth a kernel; fql_linear_bias_fwd_f32 answers the same).
+ * fql_moe_glu_bias_fwd: fql_moe_glu_fwd with the same `bias` in front of `out`, for every activation kind (FQL_ACT_SILU
+ *   included) and every element type.  bias == NULL: the call IS fql_moe_glu_fwd.  With a bias the checks, their order and
+ *   their codes are those listed for fql_moe_glu_fwd above, for every kind (FQL_ACT_SILU ignores act_alpha / act_limit).
+ *   Without a table (both NULL, E == 1) the one bias row belongs to every row.
+ * fql_moe_bias_grad: the gradient of such a bias,
+ *     grad_bias[e][n] = sum over the rows t of expert e of grad_rows[t][n],
+ *   grad_rows [T][N] of `dtype` (FQL_DTYPE_*; 16-bit elements are widened exactly), grad_bias [E][N] float32.  The expert
+ *   table is fql_moe_fwd_f32's (device arrays, ranges clipped to [0, T)); both NULL with E == 1: all rows.  Every one of
+ *   the E * N outputs is written: an expert without rows gets zeros, T == 0 writes all zeros.  Any N >= 1: 16-byte loads
+ *   when grad_rows is 16-byte aligned and N * sizeof(element) is a multiple of 16, element loads otherwise.  float32
+ *   accumulation, no atomics, no workspace.  The summation order of an expert depends on its row count alone (csrc/
+ *   fql_bias.hip): not on the grid, E, the offsets, other experts' counts, the element type or the load width, so the result
+ *   is run-to-run identical and unchanged when the table is permuted.
+ *   Errors, in order: FQL_ERR_BAD_SHAPE (E < 0, T < 0, N < 0, E > 65535, N > 2^31 - 256), FQL_ERR_DTYPE, E == 0 or N == 0 ->
+ *   FQL_OK with nothing done, FQL_ERR_NULL_POINTER (grad_bias; grad_rows when T > 0; one half of the table), FQL_ERR_BAD_SHAPE
+ *   (no table with E != 1), FQL_ERR_ALIGNMENT (grad_rows not aligned to its element, grad_bias not to 4 bytes),
+ *   FQL_ERR_LAUNCH. */
+FQL_API int fql_moe_bias_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                             const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                             int out_dtype, int E, int T, int K, int N, int precision, void *workspace,
+                             size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_glu_bias_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up,
+                                 int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                 const float *bias, void *out, int out_dtype, int E, int T, int K, int N, int precision,
+                                 int activation, float act_alpha, float act_limit, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+FQL_API int fql_moe_bias_grad(const void *grad_rows, int dtype, const int32_t *tokens_per_expert,
+                              const int32_t *input_offsets, float *grad_bias, int E, int T, int N, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
