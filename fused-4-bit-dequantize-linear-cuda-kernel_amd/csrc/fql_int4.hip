@@ -669,28 +669,73 @@ int with_dtype(int dt, F &&f)
 }
 bool elem_aligned(const void *p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
 
-// One launch of the combine / of its backward for arguments the entry points have checked (T <= 65535: grid.y)
+// One launch of the combine / of its backward for arguments the entry points have checked (T <= 65535: grid.y).
+// `sparse`: the instantiation that skips a slot with pos < 0 (fql_combine_sparse / fql_combine_sparse_bwd).
 int launch_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
-                   const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, hipStream_t st)
+                   const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, hipStream_t st,
+                   bool sparse = false)
 {
     const unsigned cols = in_dtype == FQL_DTYPE_F32 ? 1024 : 2048;       // 256 threads x 16 bytes of the input type
     return with_dtype(in_dtype, [&](auto ik) {
         return with_dtype(out_dtype, [&](auto ok) {
-            return launch(combine_kernel<ik.value, ok.value>, dim3((N + cols - 1) / cols, T), dim3(256), 0, st, y, pos_of_slot,
-                          weights, addend, addend_weight, out, T, top_k, N, R);
+            return launch(sparse ? combine_kernel<ik.value, ok.value, true> : combine_kernel<ik.value, ok.value, false>,
+                          dim3((N + cols - 1) / cols, T), dim3(256), 0, st, y, pos_of_slot, weights, addend, addend_weight, out,
+                          T, top_k, N, R);
         });
     });
 }
 int launch_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
                        const void *addend, const float *addend_weight, int in_dtype, void *grad_y, float *grad_weights,
-                       void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, hipStream_t st)
+                       void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, hipStream_t st,
+                       bool sparse = false)
 {
     return with_dtype(in_dtype, [&](auto ik) {
         return with_dtype(out_dtype, [&](auto ok) {
-            return launch(combine_bwd_kernel<ik.value, ok.value>, dim3(T), dim3(256), 0, st, grad_out, y, pos_of_slot, weights,
-                          addend, addend_weight, grad_y, grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows);
+            return launch(sparse ? combine_bwd_kernel<ik.value, ok.value, true> : combine_bwd_kernel<ik.value, ok.value, false>,
+                          dim3(T), dim3(256), 0, st, grad_out, y, pos_of_slot, weights, addend, addend_weight, grad_y,
+                          grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows);
         });
     });
+}
+
+// fql_combine / fql_combine_sparse and their backwards: one set of checks, in the order include/fql_int4.h freezes
+int combine_entry(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
+                  const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream,
+                  bool sparse)
+{
+    if (T < 0 || top_k <= 0 || N < 0 || R < 0) return FQL_ERR_BAD_SHAPE;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!y || !pos_of_slot || !out || R == 0) return FQL_ERR_NULL_POINTER;
+    if (addend_weight != nullptr && addend == nullptr) return FQL_ERR_NULL_POINTER;
+    if (T > 65535) return FQL_ERR_BAD_SHAPE;                 // grid.y
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(out, ob) || !elem_aligned(pos_of_slot, 4) ||
+        !elem_aligned(weights, 4) || !elem_aligned(addend_weight, 4))
+        return FQL_ERR_ALIGNMENT;
+    return launch_combine(y, in_dtype, pos_of_slot, weights, addend, addend_weight, out, out_dtype, T, top_k, N, R,
+                          static_cast<hipStream_t>(stream), sparse);
+}
+int combine_bwd_entry(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
+                      const void *addend, const float *addend_weight, int in_dtype, void *grad_y, float *grad_weights,
+                      void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, void *stream,
+                      bool sparse)
+{
+    if (T < 0 || top_k <= 0 || N < 0 || rows < 0 || (T > 0 && rows == 0)) return FQL_ERR_BAD_SHAPE;
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || (N == 0 && grad_weights == nullptr && grad_addend_weight == nullptr)) return FQL_OK;
+    if (!pos_of_slot) return FQL_ERR_NULL_POINTER;
+    if (N > 0 && (!grad_out || !grad_y)) return FQL_ERR_NULL_POINTER;
+    if (grad_weights != nullptr && N > 0 && !y) return FQL_ERR_NULL_POINTER;
+    if ((addend_weight != nullptr || grad_addend_weight != nullptr) && addend == nullptr) return FQL_ERR_NULL_POINTER;
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!elem_aligned(grad_out, ob) || !elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(grad_y, ib) ||
+        !elem_aligned(grad_addend, ib) || !elem_aligned(pos_of_slot, 4) || !elem_aligned(weights, 4) ||
+        !elem_aligned(addend_weight, 4) || !elem_aligned(grad_weights, 4) || !elem_aligned(grad_addend_weight, 4))
+        return FQL_ERR_ALIGNMENT;
+    return launch_combine_bwd(grad_out, out_dtype, y, pos_of_slot, weights, addend, addend_weight, in_dtype, grad_y,
+                              grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows,
+                              static_cast<hipStream_t>(stream), sparse);
 }
 
 }  // namespace
@@ -1298,39 +1343,50 @@ int fql_combine_bwd_f32(const float *grad_out, const float *y, const int32_t *po
 int fql_combine(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
                 const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream)
 {
-    if (T < 0 || top_k <= 0 || N < 0 || R < 0) return FQL_ERR_BAD_SHAPE;
-    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
-    if (T == 0 || N == 0) return FQL_OK;
-    if (!y || !pos_of_slot || !out || R == 0) return FQL_ERR_NULL_POINTER;
-    if (addend_weight != nullptr && addend == nullptr) return FQL_ERR_NULL_POINTER;
-    if (T > 65535) return FQL_ERR_BAD_SHAPE;                 // grid.y
-    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
-    if (!elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(out, ob) || !elem_aligned(pos_of_slot, 4) ||
-        !elem_aligned(weights, 4) || !elem_aligned(addend_weight, 4))
-        return FQL_ERR_ALIGNMENT;
-    return launch_combine(y, in_dtype, pos_of_slot, weights, addend, addend_weight, out, out_dtype, T, top_k, N, R,
-                          static_cast<hipStream_t>(stream));
+    return combine_entry(y, in_dtype, pos_of_slot, weights, addend, addend_weight, out, out_dtype, T, top_k, N, R, stream,
+                         false);
 }
 
 int fql_combine_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot, const float *weights,
                     const void *addend, const float *addend_weight, int in_dtype, void *grad_y, float *grad_weights,
                     void *grad_addend, float *grad_addend_weight, int T, int top_k, int N, int rows, void *stream)
 {
-    if (T < 0 || top_k <= 0 || N < 0 || rows < 0 || (T > 0 && rows == 0)) return FQL_ERR_BAD_SHAPE;
-    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
-    if (T == 0 || (N == 0 && grad_weights == nullptr && grad_addend_weight == nullptr)) return FQL_OK;
-    if (!pos_of_slot) return FQL_ERR_NULL_POINTER;
-    if (N > 0 && (!grad_out || !grad_y)) return FQL_ERR_NULL_POINTER;
-    if (grad_weights != nullptr && N > 0 && !y) return FQL_ERR_NULL_POINTER;
-    if ((addend_weight != nullptr || grad_addend_weight != nullptr) && addend == nullptr) return FQL_ERR_NULL_POINTER;
-    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
-    if (!elem_aligned(grad_out, ob) || !elem_aligned(y, ib) || !elem_aligned(addend, ib) || !elem_aligned(grad_y, ib) ||
-        !elem_aligned(grad_addend, ib) || !elem_aligned(pos_of_slot, 4) || !elem_aligned(weights, 4) ||
-        !elem_aligned(addend_weight, 4) || !elem_aligned(grad_weights, 4) || !elem_aligned(grad_addend_weight, 4))
-        return FQL_ERR_ALIGNMENT;
-    return launch_combine_bwd(grad_out, out_dtype, y, pos_of_slot, weights, addend, addend_weight, in_dtype, grad_y,
-                              grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows,
-                              static_cast<hipStream_t>(stream));
+    return combine_bwd_entry(grad_out, out_dtype, y, pos_of_slot, weights, addend, addend_weight, in_dtype, grad_y,
+                             grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows, stream, false);
+}
+
+// The plan and the combine pair with slots that go nowhere (FQL_VERSION 320; include/fql_int4.h)
+int fql_route_plan_capped_i32(const int32_t *expert_of_slot, int n_slots, int top_k, int E, const uint8_t *token_mask,
+                              int capacity, int32_t *demand, int32_t *counts, int32_t *offsets, int32_t *token_of_sorted,
+                              int32_t *pos_of_slot, void *stream)
+{
+    if (n_slots < 0 || top_k <= 0 || E <= 0 || E > ROUTE_MAX_EXPERTS || capacity < 0 || n_slots % top_k != 0)
+        return FQL_ERR_BAD_SHAPE;
+    if (!demand || !counts || !offsets) return FQL_ERR_NULL_POINTER;
+    if (n_slots > 0 && (!expert_of_slot || !token_of_sorted || !pos_of_slot)) return FQL_ERR_NULL_POINTER;
+    const size_t lds = (size_t)(ROUTE_THREADS * E + E + 1) * sizeof(int);
+    static PerDeviceFlag attr;
+    if (!ensure_lds_attr(attr, reinterpret_cast<const void *>(route_plan_capped_kernel),
+                         (ROUTE_THREADS * ROUTE_MAX_EXPERTS + ROUTE_MAX_EXPERTS + 1) * (int)sizeof(int)))
+        return FQL_ERR_LAUNCH;
+    return launch(route_plan_capped_kernel, dim3(1), dim3(ROUTE_THREADS), lds, static_cast<hipStream_t>(stream), expert_of_slot,
+                  n_slots, top_k, E, token_mask, capacity, demand, counts, offsets, token_of_sorted, pos_of_slot);
+}
+
+int fql_combine_sparse(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights, const void *addend,
+                       const float *addend_weight, void *out, int out_dtype, int T, int top_k, int N, int R, void *stream)
+{
+    return combine_entry(y, in_dtype, pos_of_slot, weights, addend, addend_weight, out, out_dtype, T, top_k, N, R, stream,
+                         true);
+}
+
+int fql_combine_sparse_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot,
+                           const float *weights, const void *addend, const float *addend_weight, int in_dtype, void *grad_y,
+                           float *grad_weights, void *grad_addend, float *grad_addend_weight, int T, int top_k, int N,
+                           int rows, void *stream)
+{
+    return combine_bwd_entry(grad_out, out_dtype, y, pos_of_slot, weights, addend, addend_weight, in_dtype, grad_y,
+                             grad_weights, grad_addend, grad_addend_weight, T, top_k, N, rows, stream, true);
 }
 
 int fql_router_topk_fwd(const void *logits, int logits_dtype, int T, int E, int top_k, int renormalize, int32_t *indices,

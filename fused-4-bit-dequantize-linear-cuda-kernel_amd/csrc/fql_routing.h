@@ -6,10 +6,13 @@
 //                        exclusive prefix (= tokens_per_expert / input_offsets of the grouped GEMM), for every
 //                        sorted position the token row it reads (the gather index of fql_moe_gather_fwd_f32) and
 //                        for every slot its sorted position (the un-sort index of the combine).
+//   route_plan_capped_kernel  the same plan with a token mask and a per-expert capacity: a masked or overflowing slot
+//                        gets no row (pos_of_slot = -1), the kept rows stay compact and in expert order.
 //   combine_kernel       out[t][:] = sum_k w[t][k] * y[pos[t][k]][:]  (k ascending) + an optional per-token weighted
 //                        addend (a shared expert's rows), with an element type for y and one for out (float32 /
 //                        float16 / bfloat16), accesses of up to 16 bytes.
 //   combine_bwd_kernel   its gradients to y, w, the addend and the addend's weight, in one launch.
+//                        Both take a SPARSE flag: a slot with pos < 0 is skipped instead of clamped to row 0.
 //   regroup_index_kernel expert-parallel receive side: rows arrive (source rank, local expert)-major, the GEMM
 //                        wants (local expert, source rank)-major: gather index + its inverse + the expert table.
 #pragma once
@@ -66,6 +69,127 @@ __global__ __launch_bounds__(ROUTE_THREADS) void route_plan_kernel(
         token_of_sorted[pos] = i / top_k;
         pos_of_slot[i] = pos;
     }
+}
+
+// ---- the plan with slots that go nowhere: a token mask and a per-expert capacity.
+// Inclusive prefix sum over the 64 lanes of a wave.
+__device__ __forceinline__ int wave_scan_i(int v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// ROUTE_BATCH consecutive slots of a thread's range [.., hi), from slot i0 on: e[j] the clamped expert id, or -1 for a slot
+// that is past the range or masked out, and t[j] its token.  The loads of a batch do not depend on each other and none
+// sits behind a per-lane condition, so they are in flight together; one slot at a time, the loop pays the latency of a
+// global load (two, with a mask) per slot.  (tok, rem) = (i / top_k, i % top_k) of slot i = min(i0, hi - 1) on entry and of
+// min(i0 + ROUTE_BATCH, hi - 1) on return: the token index walks along with the slots, no division per slot, and never
+// leaves the range, so the mask byte it names exists.
+#define ROUTE_BATCH 4
+__device__ __forceinline__ void route_load_batch(const int32_t *__restrict__ expert_of_slot,
+                                                 const uint8_t *__restrict__ token_mask, int i0, int hi, int top_k, int E,
+                                                 int &tok, int &rem, int (&e)[ROUTE_BATCH], int (&t)[ROUTE_BATCH])
+{
+    uint8_t m[ROUTE_BATCH];
+#pragma unroll
+    for (int j = 0; j < ROUTE_BATCH; ++j) {
+        e[j] = expert_of_slot[i0 + j < hi ? i0 + j : hi - 1];        // past the range: a valid address, the value is dropped
+        t[j] = tok;
+        if (i0 + j + 1 < hi && ++rem == top_k) { rem = 0; ++tok; }
+    }
+    if (token_mask != nullptr) {
+#pragma unroll
+        for (int j = 0; j < ROUTE_BATCH; ++j) m[j] = token_mask[t[j]];
+    } else {
+#pragma unroll
+        for (int j = 0; j < ROUTE_BATCH; ++j) m[j] = 1;
+    }
+#pragma unroll
+    for (int j = 0; j < ROUTE_BATCH; ++j)
+        e[j] = (i0 + j >= hi || m[j] == 0) ? -1 : (e[j] < 0 ? 0 : (e[j] >= E ? E - 1 : e[j]));      // ids outside [0, E) are clamped
+}
+
+// One workgroup, the slot ownership of route_plan_kernel (thread i owns a contiguous range, threads in slot order), so
+// a slot's rank among the eligible slots of its expert is the stable order of that kernel.  The counters are laid out
+// expert-major, s_rank[e * ROUTE_THREADS + tid]: the 64 lanes of a wave touch 64 consecutive words (64 banks) whatever E
+// is.  A column (one expert, ROUTE_THREADS counters) is scanned by one wave: every lane loads the four counters of
+// threads 4 * lane .. 4 * lane + 3 in one 16-byte access, the lane sums are scanned across the wave, and the exclusive
+// prefixes go back the same way.  A slot is kept when its rank is below `cap` (0: no limit); a slot that is masked out
+// (token_mask[token] == 0) is not counted at all.
+__global__ __launch_bounds__(ROUTE_THREADS) void route_plan_capped_kernel(
+    const int32_t *__restrict__ expert_of_slot, int n_slots, int top_k, int E, const uint8_t *__restrict__ token_mask,
+    int cap, int32_t *__restrict__ demand, int32_t *__restrict__ counts, int32_t *__restrict__ offsets,
+    int32_t *__restrict__ token_of_sorted, int32_t *__restrict__ pos_of_slot)
+{
+    extern __shared__ __attribute__((aligned(16))) int s_rank[];      // [E][ROUTE_THREADS], then [E] bases, then the total
+    int *s_base = s_rank + ROUTE_THREADS * E;                            // [E]: kept rows, then their exclusive prefix
+    int *s_total = s_base + E;                                           // [1]: all kept rows
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = n_slots > 0 ? (n_slots - 1) / ROUTE_THREADS + 1 : 0;
+    const long long lo64 = (long long)tid * chunk;
+    const int lo = lo64 < n_slots ? (int)lo64 : n_slots;
+    const int hi = lo64 + chunk < n_slots ? (int)(lo64 + chunk) : n_slots;
+    const int limit = cap > 0 ? cap : 0x7fffffff;
+    for (int e = 0; e < E; ++e) s_rank[e * ROUTE_THREADS + tid] = 0;
+    int e4[ROUTE_BATCH], t4[ROUTE_BATCH];
+    int tok = lo / top_k, rem = lo - tok * top_k;
+    for (int i0 = lo; i0 < hi; i0 += ROUTE_BATCH) {
+        route_load_batch(expert_of_slot, token_mask, i0, hi, top_k, E, tok, rem, e4, t4);
+#pragma unroll
+        for (int j = 0; j < ROUTE_BATCH; ++j)
+            if (e4[j] >= 0) s_rank[e4[j] * ROUTE_THREADS + tid] += 1;
+    }
+    __syncthreads();
+    // per expert: exclusive scan over the threads, one wave per column; the total is the demand
+    for (int e = wave; e < E; e += ROUTE_THREADS / 64) {
+        int4 *col = reinterpret_cast<int4 *>(s_rank + e * ROUTE_THREADS) + lane;
+        const int4 c = *col;
+        const int sum = (c.x + c.y) + (c.z + c.w);
+        const int incl = wave_scan_i(sum, lane);
+        const int x0 = incl - sum;
+        *col = make_int4(x0, x0 + c.x, x0 + c.x + c.y, x0 + c.x + c.y + c.z);
+        if (lane == 63) {
+            const int kept = incl < limit ? incl : limit;
+            demand[e] = incl;
+            counts[e] = kept;
+            s_base[e] = kept;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {                               // exclusive prefix of the kept counts: two experts per lane (E <= 128)
+        const int e0 = 2 * lane, e1 = e0 + 1;
+        const int c0 = e0 < E ? s_base[e0] : 0, c1 = e1 < E ? s_base[e1] : 0;
+        const int incl = wave_scan_i(c0 + c1, lane);
+        const int x0 = incl - (c0 + c1);
+        if (e0 < E) { s_base[e0] = x0; offsets[e0] = x0; }
+        if (e1 < E) { s_base[e1] = x0 + c0; offsets[e1] = x0 + c0; }
+        if (lane == 63) *s_total = incl;
+    }
+    __syncthreads();
+    tok = lo / top_k, rem = lo - tok * top_k;
+    for (int i0 = lo; i0 < hi; i0 += ROUTE_BATCH) {
+        route_load_batch(expert_of_slot, token_mask, i0, hi, top_k, E, tok, rem, e4, t4);
+#pragma unroll
+        for (int j = 0; j < ROUTE_BATCH; ++j) {
+            const int i = i0 + j;
+            if (i >= hi) break;
+            int pos = -1;
+            if (e4[j] >= 0) {
+                const int rank = s_rank[e4[j] * ROUTE_THREADS + tid]++;
+                if (rank < limit) {
+                    pos = s_base[e4[j]] + rank;
+                    token_of_sorted[pos] = t4[j];
+                }
+            }
+            pos_of_slot[i] = pos;
+        }
+    }
+    // the rows behind the kept ones belong to no expert: a valid gather index, row 0
+    for (long long i = (long long)*s_total + tid; i < n_slots; i += ROUTE_THREADS) token_of_sorted[i] = 0;
 }
 
 // ---- the combine.  KIND is an FQL_DTYPE_* code: 0 float32, 1 float16, 2 bfloat16.  16-bit
@@ -170,7 +294,8 @@ struct CombRow {
 // float32, multiply then add, k ascending, pos clamped to [0, R) (w == NULL: 1, and x * 1 == x: the gather-add form keeps
 // the bits of pre-weighted rows); the addend term comes last (addend == NULL: none; aw == NULL: 1, the bits of "+ addend").
 // grid: (ceil(N / (V * 256)), T); one thread = V consecutive columns of one token, V = 16 bytes of the input type.
-template <int IK, int OK>
+// SPARSE: a slot with pos < 0 (dropped by route_plan_capped_kernel) adds nothing; neither its row nor its weight is read.
+template <int IK, int OK, bool SPARSE = false>
 __global__ __launch_bounds__(256) void combine_kernel(
     const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot, const float *__restrict__ w,
     const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ out_, int T, int top_k, int N, int R)
@@ -192,6 +317,7 @@ __global__ __launch_bounds__(256) void combine_kernel(
     for (int c = 0; c < V; ++c) acc[c] = 0.0f;
     for (int k = 0; k < top_k; ++k) {
         int p = pos_of_slot[t * top_k + k];
+        if (SPARSE && p < 0) continue;
         p = p < 0 ? 0 : (p >= R ? R - 1 : p);
         const float wk = w != nullptr ? w[t * top_k + k] : 1.0f;
         In::load(y + (size_t)p * N + n, imode, left, v);
@@ -215,7 +341,9 @@ __global__ __launch_bounds__(256) void combine_kernel(
 //   gw[t][k]         = <y[pos[t][k]][:], gout[t][:]>          (gw == NULL: skipped)
 //   gaddend[t][:]    = round_in(aw[t] * gout[t][:])           (gaddend == NULL: skipped; aw == NULL: gout[t][:] itself)
 //   gaw[t]           = <addend[t][:], gout[t][:]>             (gaw == NULL: skipped)
-template <int IK, int OK>
+// SPARSE: pos_of_slot is an injection of the kept slots into the rows; a slot with pos < 0 writes no row of gy (the
+// caller zeroes gy) and gets gw = 0.  pos is the same for the whole workgroup, so the skip is uniform.
+template <int IK, int OK, bool SPARSE = false>
 __global__ __launch_bounds__(256) void combine_bwd_kernel(
     const void *__restrict__ gout_, const void *__restrict__ y_, const int32_t *__restrict__ pos_of_slot,
     const float *__restrict__ w, const void *__restrict__ addend_, const float *__restrict__ aw, void *__restrict__ gy_,
@@ -228,6 +356,10 @@ __global__ __launch_bounds__(256) void combine_bwd_kernel(
     const EO *go = static_cast<const EO *>(gout_) + (size_t)t * N;
     for (int k = 0; k < top_k; ++k) {
         int p = pos_of_slot[(size_t)t * top_k + k];
+        if (SPARSE && p < 0) {
+            if (gw != nullptr && tid == 0) gw[(size_t)t * top_k + k] = 0.0f;
+            continue;
+        }
         p = p < 0 ? 0 : (p >= R ? R - 1 : p);
         const float wk = w != nullptr ? w[(size_t)t * top_k + k] : 1.0f;
         const EI *yr = static_cast<const EI *>(y_) + (size_t)p * N;

@@ -464,14 +464,21 @@ class QuantizedSparseMoEBlock(nn.Module):
     own, and an explicit argument that contradicts it raises ``ValueError``.  The combine multiplies the routing weight
     into an expert's output after its bias.  ``router_bias=True`` makes ``gate`` an ``nn.Linear(..., bias=True)``
     (``gate.bias``, gpt-oss's ``router.bias``: float, trainable, run by torch, part of ``router_logits``).  Both off: the
-    state-dict keys of before."""
+    state-dict keys of before.
+
+    ``capacity_factor`` (Switch, GShard, Megatron-Core's ``moe_expert_capacity_factor``) bounds the rows an expert takes in
+    a call at ``ceil(capacity_factor * T * top_k / num_experts)``, ``T`` the token rows of the call; the overflow is
+    dropped, earlier tokens win, and the routing weights are NOT renormalised after a drop.  ``forward(x, token_mask)``
+    takes a mask of the real tokens: a masked (padding) token is not routed at all.  Either one switches the forward to
+    ``ops.route_plan_capped`` and the ``skip_dropped`` dispatch and combine; with neither it is the forward of before, bit
+    for bit and launch for launch.  The state dict is unchanged."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
                  n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
                  selection_bias: bool = False, shared_ffn_dim: int = 0, shared_experts=None,
                  shared_expert_gate: bool = False, activation=None, activation_alpha=None, activation_limit=None,
-                 expert_bias=None, router_bias: bool = False):
+                 expert_bias=None, router_bias: bool = False, capacity_factor=None):
         super().__init__()
         from . import ops
         # None: not given (a built expert takes the default, a passed-in one keeps its own)
@@ -502,6 +509,13 @@ class QuantizedSparseMoEBlock(nn.Module):
             raise ValueError(f"group_top must be 1 or 2, got {group_top}")
         if not math.isfinite(routed_scaling_factor):
             raise ValueError("routed_scaling_factor must be finite")
+        if capacity_factor is not None:
+            try:
+                capacity_factor = float(capacity_factor)
+            except (TypeError, ValueError):
+                raise ValueError(f"capacity_factor must be a number > 0 or None, got {capacity_factor!r}") from None
+            if not math.isfinite(capacity_factor) or capacity_factor <= 0.0:
+                raise ValueError(f"capacity_factor must be finite and > 0, got {capacity_factor!r}")
         if experts is None:
             experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
                                       activation_dtype=activation_dtype, expert_bias=bool(expert_bias), **act_kw)
@@ -538,7 +552,10 @@ class QuantizedSparseMoEBlock(nn.Module):
             self.shared_experts = shared_experts
         if shared_expert_gate:
             self.shared_expert_gate = nn.Linear(hidden_dim, 1, bias=False)
+        self.capacity_factor = capacity_factor
         self.routing = None                  # (probs / scores, tokens_per_expert, indices) of the last forward
+        self.kept_per_expert = None          # the plan's counts of the last forward (after the drops; == routing[1] without)
+        self._token_mask = None              # the flat mask of the last forward, for aux_loss
 
     @classmethod
     def from_weights(cls, gate_weight: torch.Tensor, gate: List[torch.Tensor], up: List[torch.Tensor],
@@ -549,8 +566,8 @@ class QuantizedSparseMoEBlock(nn.Module):
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
         ``QuantizedMoEFFN.from_weights`` takes them.  ``shared``: ``(gate [Fs, H], up [Fs, H], down [H, Fs])`` of the
         shared expert; ``shared_expert_gate_weight`` [1, H]: the weight of its sigmoid gate.  ``routing``: the
-        constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor`` and
-        ``selection_bias``.  ``activation`` (and its two floats): the experts' and the shared expert's.
+        constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor``,
+        ``selection_bias`` and ``capacity_factor``.  ``activation`` (and its two floats): the experts' and the shared expert's.
         ``router_bias`` [E]: the bias of the router (``gate.bias``); ``gate_bias[e]``, ``up_bias[e]`` [F] and
         ``down_bias[e]`` [H]: the experts' biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
         act = dict(activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
@@ -626,18 +643,40 @@ class QuantizedSparseMoEBlock(nn.Module):
         z = nn.functional.linear(x2 if x_gate is None else x_gate, w if w.dtype == x2.dtype else w.to(x2.dtype))
         return s, torch.sigmoid(z.to(torch.float32)).reshape(-1)
 
-    def forward(self, x: torch.Tensor):
+    def expert_capacity(self, tokens: int):
+        """Rows an expert may take in a call of ``tokens`` token rows: ``ceil(capacity_factor * tokens * top_k /
+        num_experts)`` (at least 1), or None for a block without ``capacity_factor``.  The mask's count is not used: it
+        lives on the device."""
+        if self.capacity_factor is None:
+            return None
+        return min(max(1, math.ceil(self.capacity_factor * tokens * self.top_k / self.num_experts)), 0x7fffffff)
+
+    def forward(self, x: torch.Tensor, token_mask=None):
         """``x`` [..., H] on the GPU (float32, or the experts' 16-bit ``activation_dtype``) ->
         ``(out [..., H], router_logits [T, E])``, T the number of tokens: at most 65535 per call, the limit of
         ``ops.combine_any`` (more raises there; split the batch).  Under grad mode the router also writes the full softmax (the sigmoids with ``scoring="sigmoid"``),
         and ``self.routing = (probs, tokens_per_expert, indices)`` of this call is kept for ``aux_loss`` until the next
         call (``probs`` is None under ``torch.no_grad()``); the weights and the output are the same bits either way.
         ``probs`` carries its autograd graph: a loop that holds many blocks and wants no ``aux_loss`` drops it with
-        ``block.routing = None`` after the forward."""
+        ``block.routing = None`` after the forward.
+
+        ``token_mask`` [...] (``x``'s shape without its last dimension, bool, True for a real token): a masked token is
+        not routed, its output is its shared expert's term (zero without one) and it sends the gate and the experts no
+        gradient; ``router_logits`` still has a row for it.  With a mask or a ``capacity_factor`` the counts in
+        ``self.routing`` are the DEMAND (what the router chose among the real tokens, before any drop: what ``aux_loss``
+        and ``update_selection_bias`` balance on) and ``self.kept_per_expert`` the rows each expert took."""
         if not x.is_cuda:
             raise RuntimeError("QuantizedSparseMoEBlock runs on the GPU (the product path has no CPU fallback)")
         from . import ops
         x2 = x.reshape(-1, self.hidden_dim)
+        capped = self.capacity_factor is not None or token_mask is not None
+        mask = None
+        if token_mask is not None:
+            if not isinstance(token_mask, torch.Tensor) or not token_mask.is_cuda or token_mask.device != x.device:
+                raise RuntimeError("token_mask must be a CUDA tensor on x's device")
+            if token_mask.dtype not in (torch.bool, torch.uint8) or tuple(token_mask.shape) != tuple(x.shape[:-1]):
+                raise RuntimeError("token_mask must be a bool tensor of x's shape without its last dimension")
+            mask = token_mask.reshape(-1)
         # Two gates read the tokens through one alias: autograd sums their input gradients there and hands x2 one gate
         # part, so x.grad is two additions over three parts (dispatch, shared expert, gates) with or without the shared gate.
         x_gate = x2.view_as(x2) if getattr(self, "shared_expert_gate", None) is not None else x2
@@ -645,21 +684,43 @@ class QuantizedSparseMoEBlock(nn.Module):
         weights, indices, *probs = ops.router_score_topk(
             logits, self.top_k, self.scoring, self.selection_bias, self.n_group, self.topk_group, self.group_top,
             self.renormalize, self.routed_scaling_factor, return_scores=torch.is_grad_enabled())
-        tpe, offs, token_of_sorted, pos_of_slot = ops.route_plan(indices, self.num_experts)
-        self.routing = (probs[0] if probs else None, tpe, indices)
-        rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)
+        self._token_mask = mask
+        if not capped:
+            tpe, offs, token_of_sorted, pos_of_slot = ops.route_plan(indices, self.num_experts)
+            self.routing = (probs[0] if probs else None, tpe, indices)
+            self.kept_per_expert = tpe
+            rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k)
+            y = self.experts(rows, tpe, offs)
+            s, aw = self.shared_output(x2, x_gate)
+            out = ops.combine_any(y, pos_of_slot, weights, addend=s, addend_weight=aw, out_dtype=x.dtype)
+            return out.reshape(x.shape), logits
+        tpe, offs, token_of_sorted, pos_of_slot, demand = ops.route_plan_capped(
+            indices, self.num_experts, self.expert_capacity(x2.shape[0]), mask)
+        self.routing = (probs[0] if probs else None, demand, indices)
+        self.kept_per_expert = tpe
+        rows = ops.dispatch_rows(x2, token_of_sorted, pos_of_slot, self.top_k, skip_dropped=True)
         y = self.experts(rows, tpe, offs)
         s, aw = self.shared_output(x2, x_gate)
-        out = ops.combine_any(y, pos_of_slot, weights, addend=s, addend_weight=aw, out_dtype=x.dtype)
+        out = ops.combine_any(y, pos_of_slot, weights, addend=s, addend_weight=aw, out_dtype=x.dtype, skip_dropped=True)
         return out.reshape(x.shape), logits
 
-    def aux_loss(self, probs=None, tokens_per_expert=None):
+    def aux_loss(self, probs=None, tokens_per_expert=None, token_mask=None):
         """The Switch / Mixtral load-balancing loss ``E * sum_e f_e * P_e``: ``f_e = tokens_per_expert[e] / T`` (the share
         of the tokens that chose expert e, a constant) and ``P_e`` the mean router probability of e, a few torch ops.
         Both default to what the last ``forward`` under grad mode kept (``self.routing``): no launch is repeated, and the
         gradient reaches the router logits through the ``grad_probs`` input of the router's backward.  Or pass the
         ``probs`` [T, E] of ``ops.router_topk(..., return_probs=True)`` and the counts of ``ops.route_plan``.  With
-        ``scoring="sigmoid"`` ``P`` is taken from ``scores / scores.sum(-1, keepdim=True)``."""
+        ``scoring="sigmoid"`` ``P`` is taken from ``scores / scores.sum(-1, keepdim=True)``.
+
+        ``token_mask`` [T] (or any shape of T elements; True for a real token) leaves the padding out: ``P_e`` is the mean
+        over the real tokens only and ``f_e = tokens_per_expert[e] / n_real``, with the counts of the last forward the
+        demand among the real tokens and ``n_real = token_mask.sum()`` taken on the device (at least 1).  It defaults to
+        the mask of the last forward (none, when that forward had none), whether ``probs`` is given or not: pass the
+        ``probs`` of another call together with that call's mask (an all-true one for none; a mask that does not have one
+        element per row of ``probs`` raises ``RuntimeError``).  Without a mask the result is the one of before, bit for
+        bit."""
+        if token_mask is None:
+            token_mask = getattr(self, "_token_mask", None)
         if probs is None or tokens_per_expert is None:
             kept = getattr(self, "routing", None)
             if kept is None or (probs is None and kept[0] is None):
@@ -668,6 +729,13 @@ class QuantizedSparseMoEBlock(nn.Module):
             tokens_per_expert = kept[1] if tokens_per_expert is None else tokens_per_expert
         if self.scoring == "sigmoid":        # the sigmoids of a row do not sum to 1
             probs = probs / probs.sum(dim=-1, keepdim=True)
+        if token_mask is not None:
+            m = token_mask.reshape(-1).to(device=probs.device, dtype=torch.float32)
+            if m.numel() != probs.shape[0]:
+                raise RuntimeError("token_mask (given, or kept from the last forward) must have one element per row of probs")
+            n_real = m.sum().clamp(min=1.0)
+            f = tokens_per_expert.detach().to(torch.float32) / n_real
+            return self.num_experts * torch.sum(f * ((probs * m.unsqueeze(1)).sum(dim=0) / n_real))
         f = tokens_per_expert.detach().to(torch.float32) / probs.shape[0]
         return self.num_experts * torch.sum(f * probs.mean(dim=0))
 
@@ -687,4 +755,6 @@ class QuantizedSparseMoEBlock(nn.Module):
             s += ", shared_expert_gate=True"
         if self.gate.bias is not None:
             s += ", router_bias=True"
+        if self.capacity_factor is not None:
+            s += f", capacity_factor={self.capacity_factor}"
         return s + self.experts._activation_repr()

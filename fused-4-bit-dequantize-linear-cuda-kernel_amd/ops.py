@@ -482,6 +482,50 @@ def route_plan(expert_indices, num_experts):
     return counts, offsets, token_of_sorted, pos_of_slot
 
 
+def route_plan_capped(expert_indices, num_experts, capacity=None, token_mask=None):
+    """``route_plan`` with slots that go nowhere, in ONE launch: a token whose ``token_mask`` entry is False is not
+    routed at all, and an expert keeps at most ``capacity`` slots (None: no limit), the earliest in token order (the
+    "position" drop policy of GShard and Megatron-Core).  ``expert_indices`` [T, top_k] integer, ``token_mask`` [T] bool or
+    uint8, both on the GPU.  Returns int32 device tensors ``(tokens_per_expert [E], input_offsets [E], token_of_sorted
+    [T*top_k], pos_of_slot [T*top_k], demand [E])``: ``tokens_per_expert`` counts the KEPT slots, ``demand`` the slots the
+    router chose among the unmasked tokens before any drop; the kept rows are compact and in expert order,
+    ``token_of_sorted`` is 0 behind them and ``pos_of_slot`` is -1 for a slot that was dropped or masked (read it with the
+    ``skip_dropped=True`` forms of ``dispatch_rows`` and ``combine_any``).  Nothing is read back to the host."""
+    if not expert_indices.is_cuda or expert_indices.dim() != 2:
+        raise RuntimeError("expert_indices must be a CUDA [tokens, top_k] tensor")
+    if num_experts > ROUTE_MAX_EXPERTS:
+        raise RuntimeError(f"route_plan_capped supports up to {ROUTE_MAX_EXPERTS} experts")
+    dev = expert_indices.device
+    T, top_k = expert_indices.shape
+    if capacity is not None:
+        try:
+            whole = int(capacity) == capacity and 1 <= capacity <= 0x7fffffff
+        except (TypeError, ValueError, OverflowError):         # a string, NaN, an infinity
+            whole = False
+        if not whole:
+            raise RuntimeError(f"capacity must be an integer >= 1 (or None for no limit), got {capacity!r}")
+    mask = None
+    if token_mask is not None:
+        if not isinstance(token_mask, torch.Tensor) or not token_mask.is_cuda or token_mask.device != dev:
+            raise RuntimeError("token_mask must be a CUDA tensor on expert_indices' device")
+        if token_mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("token_mask must be a bool or uint8 tensor")
+        if token_mask.dim() != 1 or token_mask.numel() != T:
+            raise RuntimeError("token_mask must be [tokens]")
+        mask = token_mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    flat = expert_indices.reshape(-1).to(torch.int32).contiguous()
+    n = flat.numel()
+    demand = torch.empty(num_experts, dtype=torch.int32, device=dev)
+    counts = torch.empty(num_experts, dtype=torch.int32, device=dev)
+    offsets = torch.empty(num_experts, dtype=torch.int32, device=dev)
+    token_of_sorted = torch.empty(n, dtype=torch.int32, device=dev)
+    pos_of_slot = torch.empty(n, dtype=torch.int32, device=dev)
+    _launch("fql_route_plan_capped_i32", dev, flat, n, top_k, num_experts, mask, 0 if capacity is None else int(capacity),
+            demand, counts, offsets, token_of_sorted, pos_of_slot)
+    return counts, offsets, token_of_sorted, pos_of_slot, demand
+
+
 def combine(y, pos_of_slot, expert_weights, top_k=None):
     """out[t] = sum_k expert_weights[t, k] * y[pos_of_slot[t*top_k + k]] in one launch (routing.py:172-189), on float32
     rows: ``combine_any`` without an addend.  ``expert_weights=None`` (with ``top_k``): the rows already carry their
@@ -527,7 +571,8 @@ def _combine_out_dtype(out_dtype, default):
     return out_dtype
 
 
-def combine_any(y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None, out_dtype=None):
+def combine_any(y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None, out_dtype=None,
+                skip_dropped=False):
     """``combine`` with element types and an addend, in one launch: ``out[t] = sum_k expert_weights[t, k] *
     y[pos_of_slot[t*top_k + k]] + addend_weight[t] * addend[t]``.  ``y`` [R, N] float32 / float16 / bfloat16 is read as it
     is, the sum is float32 (the slot terms exactly ``combine``'s, the addend term last) and ``out`` [T, N] is rounded once
@@ -535,16 +580,20 @@ def combine_any(y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_
     ``addend`` [T, N] of ``y``'s type (a shared expert's output) and ``addend_weight`` [T] float32 are optional
     (``addend_weight=None``: 1).  Under autograd the gradients to ``y``, ``expert_weights``, ``addend`` and
     ``addend_weight`` come from one backward launch (``combine_any_backward``); ``y`` and ``addend`` are saved in their
-    own type."""
+    own type.  ``skip_dropped=True`` (the plan of ``route_plan_capped``): a slot with ``pos_of_slot < 0`` adds nothing
+    (its row and its weight are not read) where the default clamps it to row 0; under autograd it gets a zero weight
+    gradient and sends ``y`` nothing."""
     if _wants_grad(y, expert_weights, addend, addend_weight):
+        if skip_dropped:
+            return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype, True)
         return _CombineFn.apply(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
     T, top_k, pos, w, addend, aw = _combine_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
     out_dtype = _combine_out_dtype(out_dtype, y.dtype)
     if T > 65535:
         raise RuntimeError("combine handles up to 65535 tokens per call")
     out = torch.empty((T, y.shape[1]), dtype=out_dtype, device=y.device)
-    _launch("fql_combine", y.device, y.contiguous(), _DTYPES[y.dtype], pos, w, addend, aw, out, _DTYPES[out_dtype], T, top_k,
-            y.shape[1], y.shape[0])
+    _launch("fql_combine_sparse" if skip_dropped else "fql_combine", y.device, y.contiguous(), _DTYPES[y.dtype], pos, w,
+            addend, aw, out, _DTYPES[out_dtype], T, top_k, y.shape[1], y.shape[0])
     return out
 
 
@@ -657,12 +706,15 @@ def router_score_topk_backward(logits, indices, grad_weights, grad_scores, scori
     return grad_logits
 
 
-def dispatch_rows(x, token_of_sorted, pos_of_slot, top_k):
+def dispatch_rows(x, token_of_sorted, pos_of_slot, top_k, skip_dropped=False):
     """The differentiable dispatch: ``x[token_of_sorted]`` ([T, H] -> [T * top_k, H], rows in expert order, from the plan
     of ``route_plan``).  Its backward is the pure gather-add form of ``combine`` over ``pos_of_slot`` (one launch, no
     atomics: ``x.grad`` is bit-reproducible, which ``index_add_`` is not), through ``combine_any``: a 16-bit gradient is
-    read as it arrives, summed in float32 and rounded once to ``x``'s type."""
+    read as it arrives, summed in float32 and rounded once to ``x``'s type.  ``skip_dropped=True`` (the plan of
+    ``route_plan_capped``): the backward is the sparse gather-add, a slot with ``pos_of_slot < 0`` sends ``x`` nothing."""
     if _wants_grad(x):
+        if skip_dropped:
+            return _DispatchRowsFn.apply(x, token_of_sorted, pos_of_slot, top_k, True)
         return _DispatchRowsFn.apply(x, token_of_sorted, pos_of_slot, top_k)
     _on(x.device, x=x, token_of_sorted=token_of_sorted)
     return x.index_select(0, token_of_sorted)
@@ -1016,23 +1068,26 @@ def combine_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, need_
 
 
 def combine_any_backward(grad_out, y, pos_of_slot, expert_weights, top_k=None, addend=None, addend_weight=None,
-                         need_weights=True, need_addend=True, need_addend_weight=True):
+                         need_weights=True, need_addend=True, need_addend_weight=True, skip_dropped=False):
     """Gradients of ``combine_any`` in one launch, no atomics: ``(grad_y [R, N], grad_weights [T, top_k], grad_addend
     [T, N], grad_addend_weight [T])``, None for what does not exist or is not needed.  ``grad_out`` [T, N] float32 /
     float16 / bfloat16 is read as it is; ``grad_y`` and ``grad_addend`` have ``y``'s type (rounded once), the two weight
-    gradients are float32.  Rows of ``y`` that no slot names get zero."""
+    gradients are float32.  Rows of ``y`` that no slot names get zero.  ``skip_dropped=True``: the backward of
+    ``combine_any(..., skip_dropped=True)``; a slot with ``pos_of_slot < 0`` gets a zero weight gradient and names no row
+    (``grad_y`` is allocated as zeros)."""
     T, top_k, pos, w, addend, aw = _combine_operands(y, pos_of_slot, expert_weights, top_k, addend, addend_weight)
     dev = y.device
     R, N = y.shape
     _on(dev, grad_out=grad_out)
     if grad_out.dtype not in _DTYPES or tuple(grad_out.shape) != (T, N):
         raise RuntimeError("grad_out must be a float32, float16 or bfloat16 [tokens, N] tensor")
-    grad_y = (torch.empty if R == T * top_k else torch.zeros)((R, N), dtype=y.dtype, device=dev)
+    grad_y = (torch.empty if R == T * top_k and not skip_dropped else torch.zeros)((R, N), dtype=y.dtype, device=dev)
     grad_w = torch.empty((T, top_k), dtype=torch.float32, device=dev) if (need_weights and w is not None) else None
     grad_a = torch.empty((T, N), dtype=y.dtype, device=dev) if (need_addend and addend is not None) else None
     grad_aw = torch.empty(T, dtype=torch.float32, device=dev) if (need_addend_weight and aw is not None) else None
-    _launch("fql_combine_bwd", dev, grad_out.contiguous(), _DTYPES[grad_out.dtype], y.contiguous(), pos, w, addend, aw,
-            _DTYPES[y.dtype], grad_y, grad_w, grad_a, grad_aw, T, top_k, N, R)
+    _launch("fql_combine_sparse_bwd" if skip_dropped else "fql_combine_bwd", dev, grad_out.contiguous(),
+            _DTYPES[grad_out.dtype], y.contiguous(), pos, w, addend, aw, _DTYPES[y.dtype], grad_y, grad_w, grad_a, grad_aw,
+            T, top_k, N, R)
     return grad_y, grad_w, grad_a, grad_aw
 
 
@@ -1106,10 +1161,10 @@ class _CombineFn(torch.autograd.Function):
     type."""
 
     @staticmethod
-    def forward(ctx, y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype):
+    def forward(ctx, y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype, skip_dropped=False):
         ctx.save_for_backward(y, pos_of_slot, expert_weights, addend, addend_weight)
-        ctx.top_k = top_k
-        return combine_any(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype)
+        ctx.top_k, ctx.skip_dropped = top_k, skip_dropped
+        return combine_any(y, pos_of_slot, expert_weights, top_k, addend, addend_weight, out_dtype, skip_dropped)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -1117,10 +1172,11 @@ class _CombineFn(torch.autograd.Function):
         y, pos, w, addend, aw = ctx.saved_tensors
         need = ctx.needs_input_grad
         gy, gw, ga, gaw = combine_any_backward(gout, y, pos, w, ctx.top_k, addend, aw, need_weights=need[2],
-                                               need_addend=need[4], need_addend_weight=need[5])
+                                               need_addend=need[4], need_addend_weight=need[5],
+                                               skip_dropped=ctx.skip_dropped)
         if gw is not None and w.dtype != torch.float32:
             gw = gw.to(w.dtype)
-        return gy if need[0] else None, None, gw, None, ga, gaw, None
+        return (gy if need[0] else None, None, gw, None, ga, gaw, None) + (None,) * (len(need) - 7)
 
 
 class _RouterTopkFn(torch.autograd.Function):
@@ -1147,18 +1203,23 @@ class _RouterTopkFn(torch.autograd.Function):
 
 class _DispatchRowsFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, token_of_sorted, pos_of_slot, top_k):
+    def forward(ctx, x, token_of_sorted, pos_of_slot, top_k, skip_dropped=False):
         ctx.save_for_backward(pos_of_slot)
-        ctx.top_k, ctx.x_dtype = top_k, x.dtype
+        ctx.top_k, ctx.x_dtype, ctx.skip_dropped = top_k, x.dtype, skip_dropped
         return dispatch_rows(x.detach(), token_of_sorted, pos_of_slot, top_k)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_rows):
         pos_of_slot, = ctx.saved_tensors
+        rest = (None,) * (len(ctx.needs_input_grad) - 1)
         if grad_rows.dtype not in _DTYPES or ctx.x_dtype not in _DTYPES:      # (a float64 x: through float32, as before)
-            return combine(grad_rows.to(torch.float32), pos_of_slot, None, ctx.top_k).to(ctx.x_dtype), None, None, None
-        return combine_any(grad_rows, pos_of_slot, None, ctx.top_k, out_dtype=ctx.x_dtype), None, None, None
+            g32 = grad_rows.to(torch.float32)
+            if ctx.skip_dropped:
+                return (combine_any(g32, pos_of_slot, None, ctx.top_k, skip_dropped=True).to(ctx.x_dtype),) + rest
+            return (combine(g32, pos_of_slot, None, ctx.top_k).to(ctx.x_dtype),) + rest
+        return (combine_any(grad_rows, pos_of_slot, None, ctx.top_k, out_dtype=ctx.x_dtype,
+                            skip_dropped=ctx.skip_dropped),) + rest
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 310 /* 0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 320 /* 0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -751,6 +751,46 @@ FQL_API int fql_moe_glu_bias_fwd(const uint8_t *packed, const float *scales, con
                                  void *stream);
 FQL_API int fql_moe_bias_grad(const void *grad_rows, int dtype, const int32_t *tokens_per_expert,
                               const int32_t *input_offsets, float *grad_bias, int E, int T, int N, void *stream);
+
+/* ---- slots that go nowhere: expert capacity and a token mask (FQL_VERSION 320; INTEGRATION.md section 15, DESIGN.md
+ *      section 23; csrc/fql_routing.h) ----
+ * fql_route_plan_capped_i32: fql_route_plan_i32 with a token mask and a per-expert capacity.  Expert ids are clamped into
+ *   [0, E), E <= 128.  Slot i belongs to token i / top_k and is ELIGIBLE when token_mask is NULL or
+ *   token_mask[i / top_k] != 0 (token_mask: [n_slots / top_k] bytes on the device).  demand[e] is the number of eligible
+ *   slots of expert e: the router's choice before any drop.  The eligible slots of an expert are walked in ascending slot
+ *   order (the stable order of fql_route_plan_i32); a slot is KEPT when its rank in that order is < capacity, or when
+ *   capacity == 0 (no limit): earlier tokens win, the "position" drop policy of GShard and Megatron-Core.
+ *     counts[e]  = min(demand[e], capacity) kept slots, offsets[] their exclusive prefix: the kept rows are compact and in
+ *                  expert order, S = sum of the counts <= n_slots;
+ *     token_of_sorted[0, S) the token of each kept row; token_of_sorted[S, n_slots) = 0 (a valid gather index; no expert
+ *                  covers those rows, so the grouped GEMM writes zeros there);
+ *     pos_of_slot[i] the kept row of slot i, or -1 for a dropped or masked slot.
+ *   With token_mask == NULL and capacity == 0 every output equals fql_route_plan_i32's, and demand == counts.  One
+ *   workgroup, no atomics: the result is deterministic.  n_slots == 0 writes demand, counts and offsets as zeros.
+ *   Return codes, in this order:
+ *     1. FQL_ERR_BAD_SHAPE: n_slots < 0, top_k <= 0, E outside [1, 128], capacity < 0, n_slots % top_k != 0;
+ *     2. FQL_ERR_NULL_POINTER: demand, counts or offsets NULL; with n_slots > 0 expert_of_slot, token_of_sorted or
+ *        pos_of_slot NULL (token_mask may be NULL);
+ *     3. FQL_ERR_LAUNCH.
+ * fql_combine_sparse: fql_combine that SKIPS a slot with pos_of_slot < 0 where fql_combine clamps it to row 0: the slot
+ *   adds nothing, and neither its row of y nor its weight is read.  pos_of_slot >= R is clamped to R - 1 as there.  A token
+ *   whose slots are all dropped gets its addend term alone, or zeros.  For finite y the result is bit for bit fql_combine
+ *   on the same inputs with the negative positions set to 0 and the dropped slots' weights set to 0 (the accumulator starts
+ *   at +0 and cannot become -0).
+ * fql_combine_sparse_bwd: fql_combine_bwd for it.  pos_of_slot is an injection of the kept slots into the rows.  A dropped
+ *   slot writes no row of grad_y and gets grad_weights == 0; rows no kept slot names are not written, so the caller hands
+ *   in a zeroed grad_y.  On the kept slots, and for the addend's two gradients, the bits are fql_combine_bwd's.
+ *   Arguments, return codes and their order: those of fql_combine / fql_combine_bwd above. */
+FQL_API int fql_route_plan_capped_i32(const int32_t *expert_of_slot, int n_slots, int top_k, int E, const uint8_t *token_mask,
+                                      int capacity, int32_t *demand, int32_t *counts, int32_t *offsets,
+                                      int32_t *token_of_sorted, int32_t *pos_of_slot, void *stream);
+FQL_API int fql_combine_sparse(const void *y, int in_dtype, const int32_t *pos_of_slot, const float *weights,
+                               const void *addend, const float *addend_weight, void *out, int out_dtype, int T, int top_k,
+                               int N, int R, void *stream);
+FQL_API int fql_combine_sparse_bwd(const void *grad_out, int out_dtype, const void *y, const int32_t *pos_of_slot,
+                                   const float *weights, const void *addend, const float *addend_weight, int in_dtype,
+                                   void *grad_y, float *grad_weights, void *grad_addend, float *grad_addend_weight, int T,
+                                   int top_k, int N, int rows, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
