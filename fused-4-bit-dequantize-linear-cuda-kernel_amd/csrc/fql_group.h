@@ -17,6 +17,7 @@
 // lane's 32 k inside one group.
 #pragma once
 #include "fql_common.h"
+#include "fql_act_quant.h"
 
 // KSPLIT (a few dozen rows per group: the op is a weight stream and a 64 x 64 tile per workgroup leaves CUs idle and
 // waves padding): the workgroup is ONE 32 x 32 block and its four waves take a quarter of K each, summed through LDS.
@@ -126,4 +127,34 @@ __global__ __launch_bounds__(256) void group_mfma_kernel(
             store_out4(out, 0, (size_t)t * N, nq, N, vec, o);
         }
 #endif
+}
+
+// ---- staging for the typed grouped entry points OFF the integer path (fql_moe_group_fwd / fql_moe_group_glu_fwd): the
+//      float32 kernels above and of fql_generic.h take float32 rows and write float32 rows, so a typed call widens its
+//      rows (or forms the hidden activation of gate|up rows, act_glu_mul) into the workspace first and rounds the float32
+//      result into `out` afterwards.  Streaming, one element per thread and step; every row is written, covered or not.
+// src: [T][K] of type IN, or (GATE) [T][2K] = gate | up -> dst [T][K] float32
+template <int IN, bool GATE>
+__global__ __launch_bounds__(256) void group_stage_rows_kernel(const void *__restrict__ src, float *__restrict__ dst, int K,
+                                                               size_t total, int kind, float alpha, float limit)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        auto at = [&](size_t j) -> float {
+            if (IN == 0) return reinterpret_cast<const float *>(src)[j];
+            return act_widen<IN>(reinterpret_cast<const unsigned short *>(src)[j]);
+        };
+        if (GATE) {
+            const size_t t = i / (size_t)K, k = i - t * (size_t)K;
+            dst[i] = act_glu_mul(kind, alpha, limit, at(t * 2 * (size_t)K + k), at(t * 2 * (size_t)K + K + k));
+        } else dst[i] = at(i);
+    }
+}
+// src float32 -> dst float16 (kind 1) / bfloat16 (kind 2), rounded to nearest even
+__global__ __launch_bounds__(256) void group_round_rows_kernel(const float *__restrict__ src, unsigned short *__restrict__ dst,
+                                                               size_t total, int kind)
+{
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride)
+        dst[i] = kind == 1 ? f32_to_f16_bits(src[i]) : f32_to_bf16_bits(src[i]);
 }

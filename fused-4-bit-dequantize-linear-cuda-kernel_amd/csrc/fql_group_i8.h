@@ -15,6 +15,9 @@
 // 2 v + (lane >> 5) of the row's 128-byte stage segment for step 2 v + b, the pairing the pre-pass's layout assumes --
 // unpacked in registers.  Steps 2 v and 2 v + 1 together cover k = 64 v .. 64 v + 63 of a stage, so groups are multiples
 // of 64.  Scales / zero points are read from a [E][G][N] transpose (one small kernel per call) as 16-byte loads.
+// The activation rows may be float16 / bfloat16, gate|up rows or both (the pre-pass of fql_act_quant.h takes them as the
+// per-row path's does) and the result float16 / bfloat16 (out_kind): everything in between is the float32 path, so a
+// 16-bit call is bit for bit the float32 call on the widened operand, rounded once.
 #pragma once
 #include "fql_common.h"
 
@@ -36,9 +39,9 @@ __global__ __launch_bounds__(256) void transpose_ng_kernel(const float *__restri
 template <int L>
 __global__ __launch_bounds__(256) void group_i8_kernel(
     const int8_t *__restrict__ limbs, const float *__restrict__ delta, const uint8_t *__restrict__ packed,
-    const float *__restrict__ scales_t, const float *__restrict__ zps_t, float *__restrict__ out,
+    const float *__restrict__ scales_t, const float *__restrict__ zps_t, void *__restrict__ out,
     const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs, int E, int T, int K, int MBT, int N, int group,
-    const float *__restrict__ bias, int has_res)
+    const float *__restrict__ bias, int has_res, int out_kind)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int e = blockIdx.z;
@@ -182,10 +185,11 @@ __global__ __launch_bounds__(256) void group_i8_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) res[r] = (set == 0) ? f[r] * dset : res[r] + f[r] * dset;
   }
-    // ---- lane owns row t, registers 4 q .. 4 q + 3 are 4 consecutive columns
+    // ---- lane owns row t, registers 4 q .. 4 q + 3 are 4 consecutive columns; out_kind: element type of `out`
+    //      (FQL_DTYPE_*), a 16-bit result rounded once, after the bias (store_out4, fql_common.h)
     if (rl >= cnt) return;
     const int n_q = n_blk + 4 * g2;
-    const bool vec = ((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+    const bool vec = ((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & (out_kind == 0 ? 15 : 7)) == 0);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int nq = n_q + 8 * q;
@@ -194,8 +198,10 @@ __global__ __launch_bounds__(256) void group_i8_kernel(
         for (int c = 0; c < 4; ++c) {
             o[c] = res[4 * q + c];
             if (bias != nullptr && nq + c < N) o[c] += bias[(size_t)e * N + nq + c];
+            // float16: round the float32 result, never a fused multiply-add rounded straight to float16 (fql_bwd.h, epilogue)
+            asm volatile("" : "+v"(o[c]));
         }
-        store_out4(out, 0, (size_t)t * N, nq, N, vec, o);
+        store_out4(out, out_kind, (size_t)t * N, nq, N, vec, o);
     }
 #endif
 }

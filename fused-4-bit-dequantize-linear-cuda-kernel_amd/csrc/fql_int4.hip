@@ -1100,6 +1100,26 @@ size_t fql_group_workspace_bytes(int E, int T, int K, int N, int group_size, int
     return round16(w.bytes) + 2 * round16((size_t)E * N * (K / group_size) * sizeof(float));
 }
 
+// The integer path of the per-group entry points for a call record that names the rows (their type, gate|up, activation),
+// the output (its type), the bias and the table: the per-row path's pre-pass, the [E][G][N] transpose of the constants behind
+// the limb workspace, then group_i8_kernel.  `workspace` holds fql_group_workspace_bytes() bytes.
+static int run_group_i8(int L, Call &c, const float *scales, const float *zps, int group, void *workspace)
+{
+    c.ws = carve(workspace, L, c.T, c.E, c.Kp, has_residual(L, false));
+    const int E = c.E, T = c.T, K = c.K, N = c.N, G = K / group;
+    float *st_t = reinterpret_cast<float *>(static_cast<char *>(workspace) + round16(c.ws.bytes));
+    float *zt_t = reinterpret_cast<float *>(reinterpret_cast<char *>(st_t) + round16((size_t)E * N * G * sizeof(float)));
+    return with_limbs(L, [&](auto l) {
+        constexpr int LL = decltype(l)::value;
+        if (const int rc = launch_act_quant<LL>(c)) return rc;
+        const size_t total = (size_t)E * N * G;
+        if (const int rc = launch(transpose_ng_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.st, scales, zps, st_t, zt_t, N, G, total))
+            return rc;
+        return launch(group_i8_kernel<LL>, dim3((N + 127) / 128, (T + FQL_MB - 1) / FQL_MB, E), dim3(256), 0, c.st, c.ws.limbs, c.ws.delta,
+                      c.packed, st_t, zt_t, c.out, c.tpe, c.offs, E, T, K, c.MBT, N, group, c.bias, has_residual(L, false) ? 1 : 0, c.out_dtype);
+    });
+}
+
 static int group_ws_entry(const float *x, const uint8_t *packed, const float *scales, const float *zps, const float *bias,
                           float *out, const int32_t *tpe, const int32_t *offs, int E, int T, int K, int N, int group,
                           int precision, void *workspace, size_t workspace_bytes, void *stream)
@@ -1113,23 +1133,98 @@ static int group_ws_entry(const float *x, const uint8_t *packed, const float *sc
                     group_i8_eligible(L, E, T, K, N, group, x, packed, tpe != nullptr) &&
                     workspace_bytes >= fql_group_workspace_bytes(E, T, K, N, group, precision);
     if (!ok) return group_entry(x, packed, scales, zps, bias, out, tpe, offs, E, T, K, N, group, stream);   // float32 paths (and their checks)
-    Call c;                                                  // (the pre-pass's view of the call: the GEMM below is this path's own)
-    c.x = x; c.out = out; c.tpe = tpe; c.offs = offs; c.st = static_cast<hipStream_t>(stream);
+    Call c;                                                  // (the pre-pass's view of the call: the GEMM is this path's own)
+    c.x = x; c.packed = packed; c.out = out; c.bias = bias; c.tpe = tpe; c.offs = offs; c.st = static_cast<hipStream_t>(stream);
     c.set_shape(E, T, K, N);
-    c.ws = carve(workspace, L, T, E, c.Kp, has_residual(L, false));
-    const int G = K / group;
-    float *st_t = reinterpret_cast<float *>(static_cast<char *>(workspace) + round16(c.ws.bytes));
-    float *zt_t = reinterpret_cast<float *>(reinterpret_cast<char *>(st_t) + round16((size_t)E * N * G * sizeof(float)));
-    return with_limbs(L, [&](auto l) {
-        constexpr int LL = decltype(l)::value;
-        if (const int rc = launch_act_quant<LL>(c)) return rc;
-        const size_t total = (size_t)E * N * G;
-        if (const int rc = launch(transpose_ng_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.st, scales, zps, st_t, zt_t, N, G, total))
-            return rc;
-        hipLaunchKernelGGL(group_i8_kernel<LL>, dim3((N + 127) / 128, (T + FQL_MB - 1) / FQL_MB, E), dim3(256), 0, c.st, c.ws.limbs, c.ws.delta,
-                           packed, st_t, zt_t, out, tpe, offs, E, T, K, c.MBT, N, group, bias, has_residual(L, false) ? 1 : 0);
-        return launched();
-    });
+    return run_group_i8(L, c, scales, zps, group, workspace);
+}
+
+// ---- the typed grouped entry points for per-group scales (fql_moe_group_fwd / fql_moe_group_glu_fwd): float32 / float16 /
+//      bfloat16 rows or gate|up rows in, a per-expert bias, any of the three types out.  On the integer path (the
+//      eligibility of group_ws_entry) the pre-pass takes the rows as they are and forms h on the fly, as it does for the
+//      per-row GEMM, and group_i8_kernel rounds once after the bias.  Off it the float32 kernels of group_entry run between
+//      two staging kernels (fql_group.h): widened rows / the float32 h and a float32 result live in the workspace.
+size_t fql_moe_group_typed_workspace_bytes(int E, int T, int K, int N, int group_size, int precision)
+{
+    const int L = limbs_of(precision);
+    if (L < 1 || is_f8(precision) || E <= 0 || T <= 0 || K <= 0 || N <= 0 || group_size <= 0 || K % group_size != 0) return 0;
+    const size_t stage = round16((size_t)T * K * sizeof(float)) + round16((size_t)T * N * sizeof(float));
+    const size_t i8 = fql_group_workspace_bytes(E, T, K, N, group_size, precision);
+    return stage > i8 ? stage : i8;
+}
+
+static int group_typed_entry(const uint8_t *packed, const float *scales, const float *zps, const void *x, int in_dtype,
+                             bool gated, int act, float act_alpha, float act_limit, const int32_t *tpe, const int32_t *offs,
+                             const float *bias, void *out, int out_dtype, int E, int T, int K, int N, int group, int precision,
+                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int L = limbs_of(precision);
+    if (L < 0 || is_f8(precision)) return FQL_ERR_BAD_PRECISION;
+    if (E <= 0 || T < 0 || K <= 0 || N < 0) return FQL_ERR_BAD_SHAPE;
+    if (gated && act != FQL_ACT_SILU &&
+        ((act != FQL_ACT_GELU_TANH && act != FQL_ACT_SWIGLU_CLAMP) || !std::isfinite(act_alpha) || !std::isfinite(act_limit) ||
+         !(act_limit > 0.0f))) return FQL_ERR_BAD_SHAPE;
+    if (K & 1) return FQL_ERR_ODD_K;
+    if (group <= 0 || (group & 1) || K % group != 0) return FQL_ERR_BAD_SHAPE;     // even groups that tile K
+    if (!valid_dtype(in_dtype) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (T == 0 || N == 0) return FQL_OK;
+    if (!packed || !scales || !zps || !x || !out) return FQL_ERR_NULL_POINTER;
+    if (const int rc = table_check(tpe, offs, E)) return rc;
+    if (E > 65535) return FQL_ERR_BAD_SHAPE;
+    if (!elem_aligned(x, dtype_bytes(in_dtype)) || !elem_aligned(out, dtype_bytes(out_dtype))) return FQL_ERR_ALIGNMENT;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool i8 = workspace != nullptr && aligned16(workspace) && group_i8_eligible(L, E, T, K, N, group, x, packed, tpe != nullptr) &&
+                    workspace_bytes >= fql_group_workspace_bytes(E, T, K, N, group, precision);
+    if (i8) {
+        Call c;
+        c.x = x; c.in_dtype = in_dtype; c.gated = gated;
+        if (gated && act != FQL_ACT_SILU) { c.act = act; c.act_alpha = act_alpha; c.act_limit = act_limit; }
+        c.packed = packed; c.out = out; c.out_dtype = out_dtype; c.bias = bias; c.tpe = tpe; c.offs = offs; c.st = st;
+        c.set_shape(E, T, K, N);
+        return run_group_i8(L, c, scales, zps, group, workspace);
+    }
+    // float32 kernels: stage what they cannot read or write themselves
+    const bool stage_x = gated || in_dtype != FQL_DTYPE_F32, stage_o = out_dtype != FQL_DTYPE_F32;
+    const size_t xb = stage_x ? round16((size_t)T * K * sizeof(float)) : 0, ob = stage_o ? round16((size_t)T * N * sizeof(float)) : 0;
+    if (xb + ob > 0 && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < xb + ob)) return FQL_ERR_WORKSPACE;
+    float *xf = stage_x ? static_cast<float *>(workspace) : const_cast<float *>(static_cast<const float *>(x));
+    float *of = stage_o ? reinterpret_cast<float *>(static_cast<char *>(workspace) + xb) : static_cast<float *>(out);
+    auto blocks = [](size_t total) { const size_t b = (total + 255) / 256; return dim3((unsigned)(b < 65536 ? b : 65536)); };
+    if (stage_x) {
+        const size_t total = (size_t)T * K;
+        const int rc = with_dtype(in_dtype, [&](auto d) {
+            constexpr int IN = decltype(d)::value;
+            return gated ? launch(group_stage_rows_kernel<IN, true>, blocks(total), dim3(256), 0, st, x, xf, K, total, act, act_alpha, act_limit)
+                         : launch(group_stage_rows_kernel<IN, false>, blocks(total), dim3(256), 0, st, x, xf, K, total, act, act_alpha, act_limit);
+        });
+        if (rc) return rc;
+    }
+    if (const int rc = group_entry(xf, packed, scales, zps, bias, of, tpe, offs, E, T, K, N, group, stream)) return rc;
+    if (stage_o) {
+        const size_t total = (size_t)T * N;
+        return launch(group_round_rows_kernel, blocks(total), dim3(256), 0, st, of, static_cast<unsigned short *>(out), total, out_dtype);
+    }
+    return FQL_OK;
+}
+
+int fql_moe_group_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                      const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                      int out_dtype, int E, int T, int K, int N, int group_size, int precision, void *workspace,
+                      size_t workspace_bytes, void *stream)
+{
+    return group_typed_entry(packed, scales, zps, inputs, in_dtype, false, FQL_ACT_SILU, 0.0f, 0.0f, tokens_per_expert,
+                             input_offsets, bias, out, out_dtype, E, T, K, N, group_size, precision, workspace, workspace_bytes,
+                             stream);
+}
+
+int fql_moe_group_glu_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up, int in_dtype,
+                          const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                          int out_dtype, int E, int T, int K, int N, int group_size, int precision, int activation,
+                          float act_alpha, float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return group_typed_entry(packed, scales, zps, gate_up, in_dtype, true, activation, act_alpha, act_limit, tokens_per_expert,
+                             input_offsets, bias, out, out_dtype, E, T, K, N, group_size, precision, workspace, workspace_bytes,
+                             stream);
 }
 
 int fql_linear_group_ws_fwd_f32(const float *x, const uint8_t *packed, const float *scales, const float *zps,

@@ -137,14 +137,15 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
     ``y = W_d h + s B_d (A_d h)``, ``s = alpha / rank``.  The INT4 buffers are frozen; the four adapters are the only
     parameters (float32 whatever ``activation_dtype`` is).  With ``expert_bias=True`` the layer also has the two bias
     parameters of ``QuantizedMoEFFN`` (frozen until ``requires_grad_(True)``): ``gate_up = W_gu x + b_gu + s B_gu (A_gu x)``
-    and ``y = W_d h + b_d + s B_d (A_d h)``."""
+    and ``y = W_d h + b_d + s B_d (A_d h)``.  ``group_size``: per-group INT4 scales, as ``QuantizedMoEFFN`` takes it."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
                  precision: str = "default", activation_dtype=None, activation: str = "silu",
-                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False):
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
+                 group_size=None):
         super().__init__(num_experts, hidden_dim, ffn_dim, precision=precision, activation_dtype=activation_dtype,
                          activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit,
-                         expert_bias=expert_bias)
+                         expert_bias=expert_bias, group_size=group_size)
         _check_rank(rank)
         self.rank = rank
         self.alpha = float(rank if alpha is None else alpha)
@@ -176,7 +177,7 @@ class LoRAQuantizedMoEFFN(QuantizedMoEFFN):
         module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, precision=layer.precision,
                      activation_dtype=activation_dtype, activation=layer.activation,
                      activation_alpha=layer.activation_alpha, activation_limit=layer.activation_limit,
-                     expert_bias=layer.expert_bias)
+                     expert_bias=layer.expert_bias, group_size=layer.group_size)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
         if layer.expert_bias:

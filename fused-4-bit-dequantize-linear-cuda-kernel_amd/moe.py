@@ -231,11 +231,18 @@ class QuantizedMoEFFN(nn.Module):
     ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H], zeros with ``requires_grad=False`` -- a loaded checkpoint is frozen
     like the weights, ``requires_grad_(True)`` trains them (their gradient is ``ops.moe_bias_grad``, computed only
     then).  Rows no expert covers stay zero.  A layer built without it has the state-dict keys it always had
-    (INTEGRATION.md section 14)."""
+    (INTEGRATION.md section 14).
+
+    ``group_size`` (None: per output row) quantises both projections per group of that many consecutive inputs, the
+    layout of GPTQ / AWQ-style checkpoints (``quantize_weights(group_size=)``): the scale and zero-point buffers keep their
+    names and become ``[E, 2F, H / group_size]`` and ``[E, H, F / group_size]``.  One value serves both projections; it
+    must be even and divide ``hidden_dim`` and ``ffn_dim``.  A value that gives one group (``hidden_dim == ffn_dim ==
+    group_size``) is the per-row layer.  Forward and backward run the per-group kernels (INTEGRATION.md section 16);
+    ``precision="fp8"`` is not available with it."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, precision: str = "default",
                  activation_dtype=None, activation: str = "silu", activation_alpha: float = 1.702,
-                 activation_limit: float = 7.0, expert_bias: bool = False):
+                 activation_limit: float = 7.0, expert_bias: bool = False, group_size=None):
         super().__init__()
         assert hidden_dim % 32 == 0 and ffn_dim % 32 == 0, "hidden_dim and ffn_dim must be multiples of 32"
         self.num_experts, self.hidden_dim, self.ffn_dim, self.precision = num_experts, hidden_dim, ffn_dim, precision
@@ -244,12 +251,16 @@ class QuantizedMoEFFN(nn.Module):
         self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
             activation, activation_alpha, activation_limit)
         E, H, F = num_experts, hidden_dim, ffn_dim
+        self.group_size = gs = _group_size(group_size, H, F)
+        if gs is not None and precision in ("fp8", 8):
+            raise ValueError("precision='fp8' is not available with group_size")
+        groups_gu, groups_d = ((), ()) if gs is None else ((H // gs,), (F // gs,))
         self.register_buffer("gate_up_packed", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
-        self.register_buffer("gate_up_scales", torch.zeros(E, 2 * F, dtype=torch.float32))
-        self.register_buffer("gate_up_zero_points", torch.zeros(E, 2 * F, dtype=torch.float32))
+        self.register_buffer("gate_up_scales", torch.zeros(E, 2 * F, *groups_gu, dtype=torch.float32))
+        self.register_buffer("gate_up_zero_points", torch.zeros(E, 2 * F, *groups_gu, dtype=torch.float32))
         self.register_buffer("down_packed", torch.zeros(E, H, F // 2, dtype=torch.uint8))
-        self.register_buffer("down_scales", torch.zeros(E, H, dtype=torch.float32))
-        self.register_buffer("down_zero_points", torch.zeros(E, H, dtype=torch.float32))
+        self.register_buffer("down_scales", torch.zeros(E, H, *groups_d, dtype=torch.float32))
+        self.register_buffer("down_zero_points", torch.zeros(E, H, *groups_d, dtype=torch.float32))
         self.expert_bias = bool(expert_bias)
         if self.expert_bias:                 # (no attribute at all otherwise: the state-dict keys stay those of before)
             self.gate_up_bias = nn.Parameter(torch.zeros(E, 2 * F, dtype=torch.float32), requires_grad=False)
@@ -259,10 +270,10 @@ class QuantizedMoEFFN(nn.Module):
     def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor],
                      precision: str = "default", activation_dtype=None, activation: str = "silu",
                      activation_alpha: float = 1.702, activation_limit: float = 7.0, gate_bias=None, up_bias=None,
-                     down_bias=None) -> "QuantizedMoEFFN":
+                     down_bias=None, group_size=None) -> "QuantizedMoEFFN":
         """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` (nn.Linear weight layout).  ``gate_bias[e]``,
         ``up_bias[e]``: ``[F]``; ``down_bias[e]``: ``[H]``: the per-expert biases, all three or none (then the layer has
-        no bias parameters)."""
+        no bias parameters).  ``group_size``: quantise per group along the inputs (``quantize_weights(group_size=)``)."""
         E = len(gate)
         F, H = gate[0].shape
         given = [b is not None for b in (gate_bias, up_bias, down_bias)]
@@ -273,20 +284,22 @@ class QuantizedMoEFFN(nn.Module):
                 if len(b) != E or any(tuple(t.shape) != (n,) for t in b):
                     raise ValueError(f"{name} must be a list of num_experts tensors of shape [{n}]")
         m = cls(E, H, F, precision, activation_dtype=activation_dtype, activation=activation,
-                activation_alpha=activation_alpha, activation_limit=activation_limit, expert_bias=all(given))
+                activation_alpha=activation_alpha, activation_limit=activation_limit, expert_bias=all(given),
+                group_size=group_size)
         if all(given):
             dev = gate[0].device
             with torch.no_grad():
                 m.gate_up_bias.data = torch.stack([torch.cat([g.float(), u.float()]) for g, u in zip(gate_bias, up_bias)]).to(dev)
                 m.down_bias.data = torch.stack([d.float() for d in down_bias]).to(dev)
-        gu = [quantize_weights(torch.cat([g.float(), u.float()], dim=0)) for g, u in zip(gate, up)]
-        dn = [quantize_weights(d.float()) for d in down]
+        gs = m.group_size                    # (a projection with one group comes back per row: the buffer's shape holds)
+        gu = [quantize_weights(torch.cat([g.float(), u.float()], dim=0), group_size=gs) for g, u in zip(gate, up)]
+        dn = [quantize_weights(d.float(), group_size=gs) for d in down]
         m.gate_up_packed = torch.stack([t[0] for t in gu])
-        m.gate_up_scales = torch.stack([t[1] for t in gu])
-        m.gate_up_zero_points = torch.stack([t[2] for t in gu])
+        m.gate_up_scales = torch.stack([t[1] for t in gu]).reshape(m.gate_up_scales.shape)
+        m.gate_up_zero_points = torch.stack([t[2] for t in gu]).reshape(m.gate_up_zero_points.shape)
         m.down_packed = torch.stack([t[0] for t in dn])
-        m.down_scales = torch.stack([t[1] for t in dn])
-        m.down_zero_points = torch.stack([t[2] for t in dn])
+        m.down_scales = torch.stack([t[1] for t in dn]).reshape(m.down_scales.shape)
+        m.down_zero_points = torch.stack([t[2] for t in dn]).reshape(m.down_zero_points.shape)
         return m
 
     def forward(self, inputs, tokens_per_expert, input_offsets):
@@ -321,6 +334,8 @@ class QuantizedMoEFFN(nn.Module):
 
     def _activation_repr(self) -> str:
         bias = ", expert_bias=True" if self.expert_bias else ""
+        if self.group_size is not None:
+            bias += f", group_size={self.group_size}"
         if self.activation == "silu":
             return bias
         s = f", activation={self.activation}"
@@ -330,6 +345,18 @@ class QuantizedMoEFFN(nn.Module):
 
     def extra_repr(self) -> str:
         return self._activation_repr().lstrip(", ")
+
+
+def _group_size(group_size, hidden_dim, ffn_dim):
+    """The ``group_size`` argument of the gated FFN layers: None (per row), or an even divisor of both dimensions; the one
+    value that gives a single group in both projections is per row too."""
+    if group_size is None:
+        return None
+    if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size <= 0 or group_size % 2 != 0 \
+            or hidden_dim % group_size != 0 or ffn_dim % group_size != 0:
+        raise ValueError(f"group_size must be even and divide hidden_dim ({hidden_dim}) and ffn_dim ({ffn_dim}), got "
+                         f"{group_size!r}")
+    return None if group_size == hidden_dim == ffn_dim else group_size
 
 
 def _activation_dtype(activation_dtype, precision):
@@ -471,14 +498,18 @@ class QuantizedSparseMoEBlock(nn.Module):
     dropped, earlier tokens win, and the routing weights are NOT renormalised after a drop.  ``forward(x, token_mask)``
     takes a mask of the real tokens: a masked (padding) token is not routed at all.  Either one switches the forward to
     ``ops.route_plan_capped`` and the ``skip_dropped`` dispatch and combine; with neither it is the forward of before, bit
-    for bit and launch for launch.  The state dict is unchanged."""
+    for bit and launch for launch.  The state dict is unchanged.
+
+    ``group_size`` (per-group INT4 scales, ``QuantizedMoEFFN``'s) is handed to the experts and the shared expert the block
+    builds; a module passed in keeps its own, and an explicit argument that contradicts it raises ``ValueError``
+    (INTEGRATION.md section 16)."""
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, top_k: int = 2, precision: str = "default",
                  activation_dtype=None, renormalize: bool = True, experts=None, scoring: str = "softmax",
                  n_group: int = 1, topk_group: int = 1, group_top: int = 2, routed_scaling_factor: float = 1.0,
                  selection_bias: bool = False, shared_ffn_dim: int = 0, shared_experts=None,
                  shared_expert_gate: bool = False, activation=None, activation_alpha=None, activation_limit=None,
-                 expert_bias=None, router_bias: bool = False, capacity_factor=None):
+                 expert_bias=None, router_bias: bool = False, capacity_factor=None, group_size=None):
         super().__init__()
         from . import ops
         # None: not given (a built expert takes the default, a passed-in one keeps its own)
@@ -495,6 +526,10 @@ class QuantizedSparseMoEBlock(nn.Module):
                 if have[k] != given[k]:
                     raise ValueError(f"{k}={act_kw[k]!r} contradicts {name}, built with {k}={have[k]!r}: leave the "
                                      f"block's argument out, or build {name} with it")
+            have_gs = getattr(module, "group_size", None)
+            if group_size is not None and _group_size(group_size, module.hidden_dim, module.ffn_dim) != have_gs:
+                raise ValueError(f"group_size={group_size!r} contradicts {name}, built with group_size={have_gs!r}: leave "
+                                 f"the block's argument out, or build {name} with it")
         if num_experts < 1 or num_experts > ops.ROUTE_MAX_EXPERTS:
             raise ValueError(f"num_experts must be in [1, {ops.ROUTE_MAX_EXPERTS}], got {num_experts}")
         if top_k < 1 or top_k > min(num_experts, ops.ROUTER_MAX_TOPK):
@@ -518,7 +553,8 @@ class QuantizedSparseMoEBlock(nn.Module):
                 raise ValueError(f"capacity_factor must be finite and > 0, got {capacity_factor!r}")
         if experts is None:
             experts = QuantizedMoEFFN(num_experts, hidden_dim, ffn_dim, precision=precision,
-                                      activation_dtype=activation_dtype, expert_bias=bool(expert_bias), **act_kw)
+                                      activation_dtype=activation_dtype, expert_bias=bool(expert_bias),
+                                      group_size=group_size, **act_kw)
         elif (experts.num_experts, experts.hidden_dim, experts.ffn_dim) != (num_experts, hidden_dim, ffn_dim):
             raise ValueError("experts must have the block's num_experts, hidden_dim and ffn_dim")
         else:
@@ -537,7 +573,7 @@ class QuantizedSparseMoEBlock(nn.Module):
             check_activation("shared_experts", shared_experts)
         elif shared_ffn_dim:
             shared_experts = QuantizedMoEFFN(1, hidden_dim, shared_ffn_dim, precision=precision,
-                                             activation_dtype=activation_dtype, **act_kw)
+                                             activation_dtype=activation_dtype, group_size=group_size, **act_kw)
         if shared_expert_gate and shared_experts is None:
             raise ValueError("shared_expert_gate=True needs a shared expert (shared_ffn_dim or shared_experts)")
         self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
@@ -562,17 +598,19 @@ class QuantizedSparseMoEBlock(nn.Module):
                      down: List[torch.Tensor], top_k: int = 2, precision: str = "default", activation_dtype=None,
                      renormalize: bool = True, shared=None, shared_expert_gate_weight=None, activation: str = "silu",
                      activation_alpha: float = 1.702, activation_limit: float = 7.0, router_bias=None, gate_bias=None,
-                     up_bias=None, down_bias=None, **routing) -> "QuantizedSparseMoEBlock":
+                     up_bias=None, down_bias=None, group_size=None, **routing) -> "QuantizedSparseMoEBlock":
         """``gate_weight`` [E, H] (the router); ``gate[e]``, ``up[e]`` [F, H] and ``down[e]`` [H, F] as
         ``QuantizedMoEFFN.from_weights`` takes them.  ``shared``: ``(gate [Fs, H], up [Fs, H], down [H, Fs])`` of the
         shared expert; ``shared_expert_gate_weight`` [1, H]: the weight of its sigmoid gate.  ``routing``: the
         constructor's ``scoring``, ``n_group``, ``topk_group``, ``group_top``, ``routed_scaling_factor``,
         ``selection_bias`` and ``capacity_factor``.  ``activation`` (and its two floats): the experts' and the shared expert's.
         ``router_bias`` [E]: the bias of the router (``gate.bias``); ``gate_bias[e]``, ``up_bias[e]`` [F] and
-        ``down_bias[e]`` [H]: the experts' biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
+        ``down_bias[e]`` [H]: the experts' biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none).
+        ``group_size``: per-group quantisation of the experts and the shared expert."""
         act = dict(activation=activation, activation_alpha=activation_alpha, activation_limit=activation_limit)
         experts = QuantizedMoEFFN.from_weights(gate, up, down, precision=precision, activation_dtype=activation_dtype,
-                                               gate_bias=gate_bias, up_bias=up_bias, down_bias=down_bias, **act)
+                                               gate_bias=gate_bias, up_bias=up_bias, down_bias=down_bias,
+                                               group_size=group_size, **act)
         E, H = gate_weight.shape
         if E != experts.num_experts or H != experts.hidden_dim:
             raise ValueError("gate_weight must be [num_experts, hidden_dim]")
@@ -582,13 +620,13 @@ class QuantizedSparseMoEBlock(nn.Module):
         if shared is not None:
             sg, su, sd = shared
             shared_experts = QuantizedMoEFFN.from_weights([sg], [su], [sd], precision=precision,
-                                                          activation_dtype=activation_dtype, **act)
+                                                          activation_dtype=activation_dtype, group_size=group_size, **act)
         if shared_expert_gate_weight is not None and tuple(shared_expert_gate_weight.shape) != (1, H):
             raise ValueError("shared_expert_gate_weight must be [1, hidden_dim]")
         m = cls(E, H, experts.ffn_dim, top_k=top_k, precision=precision, activation_dtype=activation_dtype,
                 renormalize=renormalize, experts=experts, shared_experts=shared_experts,
                 shared_expert_gate=shared_expert_gate_weight is not None, router_bias=router_bias is not None,
-                **routing)
+                group_size=group_size, **routing)
         with torch.no_grad():
             m.gate.weight.copy_(gate_weight.float())
             if router_bias is not None:

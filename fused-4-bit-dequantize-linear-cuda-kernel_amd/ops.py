@@ -111,20 +111,26 @@ def _expert_table(tokens_per_expert, input_offsets, E, dev, optional=False):
     return tokens_per_expert.to(dtype=torch.int32).contiguous(), input_offsets.to(dtype=torch.int32).contiguous()
 
 
-def _check_weights(packed_weights, scales, zero_points, dev, K=None, grouped=False):
-    """The per-row weight triple on ``dev``: ``packed_weights`` uint8 [N, K/2] with float32 ``scales`` / ``zero_points``
-    of N elements, or (``grouped``) [E, N, K/2] with [E, N].  Returns ``(packed_weights, scales, zero_points, E, N, K)``,
-    the tensors contiguous, E = 1 for one matrix."""
+def _check_packed(packed_weights, dev, K=None, grouped=False):
+    """``packed_weights`` uint8 [N, K/2] (``grouped``: [E, N, K/2]) on ``dev``, K / 2 matching ``K`` when given.  Returns
+    ``(E, N, K / 2)``."""
     if not packed_weights.is_cuda or packed_weights.device != dev:
         raise RuntimeError("packed_weights must be a CUDA tensor on the inputs' device")
     if packed_weights.dtype != torch.uint8 or packed_weights.dim() != (3 if grouped else 2):
         raise RuntimeError("packed_weights must be uint8 " + ("[num_experts, ffn_dim, hidden_dim/2]" if grouped
                                                               else "[output_dim, input_dim/2]"))
     N, packed_dim = packed_weights.shape[-2:]
-    E = packed_weights.shape[0] if grouped else 1
     if K is not None and packed_dim * 2 != K:
         raise RuntimeError("packed_weights dim 2 must be hidden_dim / 2" if grouped
                            else "packed_weights dim 1 must be input_dim / 2")
+    return (packed_weights.shape[0] if grouped else 1), N, packed_dim
+
+
+def _check_weights(packed_weights, scales, zero_points, dev, K=None, grouped=False):
+    """The per-row weight triple on ``dev``: ``packed_weights`` uint8 [N, K/2] with float32 ``scales`` / ``zero_points``
+    of N elements, or (``grouped``) [E, N, K/2] with [E, N].  Returns ``(packed_weights, scales, zero_points, E, N, K)``,
+    the tensors contiguous, E = 1 for one matrix."""
+    E, N, packed_dim = _check_packed(packed_weights, dev, K, grouped)
     for name, t in (("scales", scales), ("zero_points", zero_points)):
         if not t.is_cuda or t.device != dev:
             raise RuntimeError(f"{name} must be a CUDA tensor on the inputs' device")
@@ -151,6 +157,51 @@ def _check_group_weights(packed_weights, scales, zero_points, dev, K):
     if group % 2 != 0:
         raise RuntimeError("group_size must be even")
     return packed_weights.contiguous(), scales.contiguous(), zero_points.contiguous(), group
+
+
+def _expert_group(scales):
+    """Whether the experts' ``scales`` are per group along K: [E, N, K / group_size] with more than one group."""
+    return isinstance(scales, torch.Tensor) and scales.dim() == 3 and scales.shape[-1] > 1
+
+
+def _expert_weights(packed_weights, scales, zero_points, dev, K=None):
+    """The weight triple of the grouped ops: per row (``_check_weights(grouped=True)``) or, with 3-D ``scales``, per group
+    along K (``_check_group_weights``).  A last dimension of 1 is per-row and is passed on as [E, N].  Returns
+    ``(packed_weights, scales, zero_points, E, N, K, group_size)``, ``group_size`` None for per-row weights."""
+    if _expert_group(scales):
+        E, N, packed_dim = _check_packed(packed_weights, dev, K, grouped=True)
+        return (*_check_group_weights(packed_weights, scales, zero_points, dev, 2 * packed_dim)[:3], E, N, 2 * packed_dim,
+                2 * packed_dim // scales.shape[-1])
+    if isinstance(scales, torch.Tensor) and scales.dim() == 3 and isinstance(zero_points, torch.Tensor) \
+            and zero_points.dim() == 3 and zero_points.shape[-1] == 1:
+        scales, zero_points = scales[..., 0], zero_points[..., 0]
+    return (*_check_weights(packed_weights, scales, zero_points, dev, K, grouped=True), None)
+
+
+def _moe_group_launch(packed_weights, scales, zero_points, rows, tpe, offs, bias, out_dtype, E, N, K, group, precision,
+                      act=None):
+    """The grouped GEMM on per-group weights: ``fql_moe_group_fwd`` on ``rows`` [T, K], or (``act``: the triple of
+    ``activation_of``) ``fql_moe_group_glu_fwd`` on gate|up rows [T, 2K].  Rows and result in any of the three types; the
+    library stages what its float32 kernels need (include/fql_int4.h), torch touches no [T, .] tensor here."""
+    prec = _group_precision(precision)
+    T, dev = rows.shape[0], rows.device
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    ws_bytes = _native.lib().fql_moe_group_typed_workspace_bytes(E, T, K, N, group, prec)
+    if act is None:
+        _launch("fql_moe_group_fwd", dev, packed_weights, scales, zero_points, rows.contiguous(), _DTYPES[rows.dtype], tpe,
+                offs, bias, out, _DTYPES[out_dtype], E, T, K, N, group, prec, ws_bytes=ws_bytes)
+    else:
+        _launch("fql_moe_group_glu_fwd", dev, packed_weights, scales, zero_points, rows.contiguous(), _DTYPES[rows.dtype],
+                tpe, offs, bias, out, _DTYPES[out_dtype], E, T, K, N, group, prec, _ACTIVATIONS[act[0]], act[1], act[2],
+                ws_bytes=ws_bytes)
+    return out
+
+
+def _group_precision(precision):
+    prec = _precision(precision)
+    if prec == _native.PRECISION_FP8:
+        raise RuntimeError("precision='fp8' is not available with per-group weights")
+    return prec
 
 
 def _check_bias(bias, N, dev, E=None):
@@ -264,7 +315,8 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
                 input_offsets, precision="default", bias=None):
     """Grouped per-expert INT4 GEMM over rows pre-grouped by expert.
 
-    packed_weights [E,N,K/2] u8, scales/zero_points [E,N] f32, inputs [T,K] f32,
+    packed_weights [E,N,K/2] u8, scales/zero_points [E,N] f32 (or per group along K: [E,N,K/group_size], the layout
+    of ``quantize_weights(group_size=)``), inputs [T,K] f32,
     tokens_per_expert / input_offsets [E] int32 on the device (consumed there, no .item()).
     ``expert_ids`` is accepted and ignored, as in the reference (csrc/moe_int4_kernel.cu:98).
     Returns [T,N] float32; rows covered by no expert are zero (reference: torch::zeros :109).
@@ -283,9 +335,12 @@ def moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_
         raise RuntimeError("inputs must be float32 [total_tokens, hidden_dim]")
     T, K = inputs.shape
     dev = inputs.device
-    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    packed_weights, scales, zero_points, E, N, _, group = _expert_weights(packed_weights, scales, zero_points, dev, K)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     bias = _check_bias(bias, N, dev, E)
+    if group is not None:
+        return _moe_group_launch(packed_weights, scales, zero_points, inputs, tpe, offs, bias, torch.float32, E, N, K,
+                                 group, precision)
     prec = _precision(precision)
     out = torch.empty((T, N), dtype=torch.float32, device=dev)
     if bias is not None:
@@ -345,6 +400,15 @@ def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tok
     if inputs.dtype == torch.float32 and out_dtype == torch.float32:
         return moe_forward(packed_weights, scales, zero_points, inputs, expert_ids, tokens_per_expert, input_offsets,
                            precision=precision, bias=bias)
+    if _expert_group(scales):                               # per-group weights: the library takes every type and shape
+        if not inputs.is_cuda or inputs.dim() != 2:
+            raise RuntimeError("inputs must be a CUDA [total_tokens, hidden_dim] tensor")
+        T, K = inputs.shape
+        dev = inputs.device
+        packed_weights, scales, zero_points, E, N, _, group = _expert_weights(packed_weights, scales, zero_points, dev, K)
+        tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+        return _moe_group_launch(packed_weights, scales, zero_points, inputs, tpe, offs, _check_bias(bias, N, dev, E),
+                                 out_dtype, E, N, K, group, precision)
     prec = _precision(precision)
     L = _native.lib()
     ok = (inputs.is_cuda and inputs.dim() == 2 and packed_weights.is_cuda and packed_weights.dim() == 3
@@ -356,7 +420,7 @@ def moe_forward_any(packed_weights, scales, zero_points, inputs, expert_ids, tok
                            tokens_per_expert, input_offsets, precision=precision, bias=bias).to(out_dtype)
     T, K = inputs.shape
     dev = inputs.device
-    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    packed_weights, scales, zero_points, E, N, _, _ = _expert_weights(packed_weights, scales, zero_points, dev, K)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
@@ -421,7 +485,9 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
     ``activation``: ``"silu"``, ``"gelu_tanh"`` (GeGLU) or ``"swiglu_clamp"`` (gpt-oss, with ``activation_alpha`` and
     ``activation_limit``) in place of silu(g) * u (``activation_of``).
     ``bias`` [E, N] float32 (optional): expert e's bias is added to the rows of expert e in the GEMM's epilogue, before
-    the one rounding of a 16-bit result; rows no expert covers stay zero."""
+    the one rounding of a 16-bit result; rows no expert covers stay zero.
+    Per-group ``scales`` / ``zero_points`` [E, N, K / group_size] take ``fql_moe_group_glu_fwd``: h stays out of memory on
+    the integer path only (K % 256 == 0, group_size % 64 == 0, 8+ rows per expert)."""
     _forward_only("moe_gated_forward", gate_up, bias)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     if not gate_up.is_cuda or gate_up.dtype not in _DTYPES or gate_up.dim() != 2:
@@ -434,9 +500,12 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
     dev = gate_up.device
     if K2 % 2 or K % 32:
         raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
-    packed_weights, scales, zero_points, E, N, _ = _check_weights(packed_weights, scales, zero_points, dev, K, grouped=True)
+    packed_weights, scales, zero_points, E, N, _, group = _expert_weights(packed_weights, scales, zero_points, dev, K)
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     bias = _check_bias(bias, N, dev, E)
+    if group is not None:
+        return _moe_group_launch(packed_weights, scales, zero_points, gate_up, tpe, offs, bias, out_dtype, E, N, K, group,
+                                 precision, act=(kind, act_alpha, act_limit))
     L = _native.lib()
     prec = _precision(precision)
     typed = gate_up.dtype != torch.float32 or out_dtype != torch.float32
@@ -1002,16 +1071,24 @@ def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per
                        precision="default", out_dtype=None):
     """Grouped ``grad_in[t] = grad_out[t] @ W_e`` for the rows of each expert's range; rows no expert covers are zero.
     ``grad_out`` [T, N] float32 / float16 / bfloat16, ``packed_weights`` [E, N, K/2] -> [T, K] ``out_dtype`` (default
-    float32); 16-bit types as in ``linear_backward_input``."""
+    float32); 16-bit types as in ``linear_backward_input``.  Per-group ``scales`` / ``zero_points``
+    [E, N, K / group_size] take the float32 matrix-core kernel of csrc/fql_group_bwd.h (``precision`` does not enter it):
+    a fixed summation order, so the grouped call equals the one-expert calls bit for bit."""
     out_dtype = _grad_dtypes(grad_out, out_dtype, "T")
     dev = grad_out.device
-    packed_weights, scales, zero_points, E, N, K = _check_weights(packed_weights, scales, zero_points, dev, grouped=True)
+    packed_weights, scales, zero_points, E, N, K, group = _expert_weights(packed_weights, scales, zero_points, dev)
     T = grad_out.shape[0]
     if grad_out.shape[1] != N:
         raise RuntimeError("grad_out must be [T, ffn_dim]")
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
-    prec = _precision(precision)
     out = torch.empty((T, K), dtype=out_dtype, device=dev)
+    if group is not None:                                   # per-group weights: csrc/fql_group_bwd.h (float32 contraction)
+        _group_precision(precision)
+        _launch("fql_moe_group_bwd_input", dev, packed_weights, scales, zero_points, grad_out.contiguous(),
+                _DTYPES[grad_out.dtype], tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, group,
+                ws_bytes=_native.lib().fql_moe_group_bwd_workspace_bytes(E, T, K, N, group))
+        return out
+    prec = _precision(precision)
     _launch("fql_moe_bwd_input", dev, packed_weights, scales, zero_points, grad_out.contiguous(), _DTYPES[grad_out.dtype],
             tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec,
             ws_bytes=_native.lib().fql_moe_bwd_workspace_bytes(E, T, K, N, prec))
@@ -1633,7 +1710,8 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
     ``gu = W_gu x + s B_gu (A_gu x)``, ``h = silu(gu[:F]) * gu[F:]`` (never stored), ``y = W_d h + s B_d (A_d h)``; rows
     no expert covers are zero.  ``inputs`` [T, H] float32, stacked gate|up weights [E, 2F, H/2], down weights
     [E, H, F/2], ``gate_up_lora_A`` [E, r, H], ``gate_up_lora_B`` [E, 2F, r], ``down_lora_A`` [E, r, F],
-    ``down_lora_B`` [E, H, r].  Per-row INT4 weights only.  Differentiable (once) in ``inputs`` and the four adapters.
+    ``down_lora_B`` [E, H, r].  Scales / zero points per row [E, N] or per group [E, N, K / group_size].  Differentiable
+    (once) in ``inputs`` and the four adapters.
 
     ``activation_dtype`` = torch.float16 / torch.bfloat16 is the memory-for-precision form: ``inputs`` and the incoming
     gradient have that type, ``gate_up`` is stored (and saved) in it, ``y`` and ``inputs.grad`` come back in it; the
@@ -1657,9 +1735,9 @@ def moe_ffn_lora_forward(gate_up_packed, gate_up_scales, gate_up_zps, down_packe
         raise RuntimeError("inputs must be a CUDA float32 [T, H] tensor: without activation_dtype the gated FFN adapters "
                            "are float32 only (pass activation_dtype=torch.float16 / torch.bfloat16 to run the layer on "
                            "16-bit activations; gate_up is then rounded to that type between the two projections)")
-    if gate_up_packed.dim() != 3 or gate_up_scales.dim() != 2 or down_packed.dim() != 3 or down_scales.dim() != 2:
+    if gate_up_packed.dim() != 3 or down_packed.dim() != 3:
         raise RuntimeError("moe_ffn_lora_forward takes per-row INT4 weights: packed [E, N, K/2], scales / zero_points "
-                           "[E, N]")
+                           "[E, N] (or per-group ones: [E, N, K / group_size])")
     E, F2, H = gate_up_packed.shape[0], gate_up_packed.shape[1], inputs.shape[1]
     if F2 % 2 or tuple(down_packed.shape) != (E, H, F2 // 4):
         raise RuntimeError("gate_up_packed must be [E, 2F, H/2] and down_packed [E, H, F/2]")

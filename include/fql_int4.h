@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 320 /* 0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 330 /* 0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -228,6 +228,63 @@ FQL_API int fql_moe_group_ws_fwd_f32(const uint8_t *packed, const float *scales,
                                      const int32_t *input_offsets, float *out, int E, int T, int K, int N,
                                      int group_size, int precision, void *workspace, size_t workspace_bytes,
                                      void *stream);
+
+/* The grouped call with per-group scales as the per-row grouped entry points take theirs: rows of any element type, a
+ * per-expert bias, a fused activation, a result of any element type (FQL_DTYPE_*), and the input gradient.
+ *
+ * fql_moe_group_fwd:     out[t][n] = sum_k x[t][k] * W_e[n][k] (+ bias[e][n]) over the rows t of expert e,
+ *                        W_e[n][k] = (q[e][n][k] - zps[e][n][k / group_size]) * scales[e][n][k / group_size].
+ * fql_moe_group_glu_fwd: the same on h[t][k] = act(gate_up[t][k], gate_up[t][K + k]), gate_up [T][2K], `activation` one of
+ *                        FQL_ACT_* with act_alpha / act_limit (ignored for FQL_ACT_SILU) as fql_moe_glu_fwd takes them.
+ *   scales, zps [E][N][K / group_size] float32; bias [E][N] float32 or NULL; inputs / gate_up in_dtype, out out_dtype.
+ *   Rows no expert covers are zero.  tokens_per_expert / input_offsets: both, or both NULL with E == 1 (one segment).
+ *   A 16-bit call is bit for bit the float32 call on the widened operand, rounded once (after the bias).
+ *   Workspace: fql_moe_group_typed_workspace_bytes(E, T, K, N, group_size, precision), 16-byte aligned.
+ *   INTEGER PATH (K % 256 == 0, group_size % 64 == 0, 8 or more rows per expert on average, 16-byte aligned packed, N >= 4):
+ *   the activation pre-pass of the per-row path reads the rows as they are and forms h on the fly, csrc/fql_group_i8.h
+ *   contracts on the INT8 matrix cores and rounds once: h is never stored.  Only this path keeps h out of memory.
+ *   EVERY OTHER SHAPE: the float32 kernels of fql_moe_group_fwd_f32.  The entry widens 16-bit rows, or writes the
+ *   float32 h, into the workspace ([T][K] float32), and a 16-bit result is written as float32 into the workspace
+ *   ([T][N]) and rounded from there: two streaming kernels around the GEMM, `precision` does not enter the arithmetic.
+ *   Return codes, in this order: FQL_ERR_BAD_PRECISION (unknown, or FQL_PRECISION_FP8); FQL_ERR_BAD_SHAPE (E <= 0, T < 0,
+ *   K <= 0, N < 0; glu: an unknown activation, or for a kind other than silu a non-finite act_alpha / act_limit or
+ *   act_limit <= 0); FQL_ERR_ODD_K; FQL_ERR_BAD_SHAPE (group_size <= 0, odd, or not dividing K); FQL_ERR_DTYPE; T == 0 or
+ *   N == 0: FQL_OK with nothing launched; FQL_ERR_NULL_POINTER (packed, scales, zps, inputs, out; one of the table's two
+ *   arrays alone); FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65535); FQL_ERR_ALIGNMENT (inputs / out not aligned to
+ *   their element); FQL_ERR_WORKSPACE (off the integer path, when something is staged: NULL, misaligned or short);
+ *   FQL_ERR_LAUNCH.
+ *
+ * fql_moe_group_bwd_input: grad_in[t][k] = sum_n grad_out[t][n] * W_e[n][k] (csrc/fql_group_bwd.h): the weights
+ *   dequantised in registers and staged through LDS, the contraction on the float32 matrix-core instruction.  grad_out
+ *   [T][N] of grad_out_dtype is read as it is and widened in registers, grad_in [T][K] of grad_in_dtype is rounded once: a
+ *   16-bit call is bit for bit the float32 call on the widened gradient, rounded once.  No atomics; every element of
+ *   grad_in is written once, rows no expert covers as zeros by the same launch.  The sum over n runs in a fixed order
+ *   (64 n at a time, inside them n0 + s then n0 + 32 + s for s = 0 .. 31), so a row's result depends on its own gradient
+ *   row and its expert's weights only: the grouped call equals E one-expert calls on the same rows bit for bit, run to run
+ *   and under any permutation of the table.  K % 64 == 0, group_size % 32 == 0 and 16-byte aligned packed / grad_out /
+ *   grad_in: the tiled kernel; anything else one wave per row with the same order (correct, not tuned).
+ *   fql_moe_group_bwd_workspace_bytes is 0 today (the kernels keep nothing between them) and the workspace may be NULL;
+ *   both are part of the signature so that a cached transpose of the constants can move in later.
+ *   Return codes, in this order: FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K < 0, N < 0); FQL_ERR_ODD_K; FQL_ERR_BAD_SHAPE
+ *   (group_size <= 0, odd, or not dividing K); FQL_ERR_DTYPE; T == 0 or K == 0: FQL_OK with nothing launched;
+ *   FQL_ERR_NULL_POINTER (grad_in; with N > 0 grad_out, packed, scales, zps; one of the table's two arrays alone);
+ *   FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65534); FQL_ERR_ALIGNMENT (a base not aligned to its element);
+ *   N == 0: grad_in is zeroed; FQL_ERR_LAUNCH. */
+FQL_API size_t fql_moe_group_typed_workspace_bytes(int E, int T, int K, int N, int group_size, int precision);
+FQL_API int fql_moe_group_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *inputs, int in_dtype,
+                              const int32_t *tokens_per_expert, const int32_t *input_offsets, const float *bias, void *out,
+                              int out_dtype, int E, int T, int K, int N, int group_size, int precision, void *workspace,
+                              size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_group_glu_fwd(const uint8_t *packed, const float *scales, const float *zps, const void *gate_up,
+                                  int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                  const float *bias, void *out, int out_dtype, int E, int T, int K, int N, int group_size,
+                                  int precision, int activation, float act_alpha, float act_limit, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+FQL_API size_t fql_moe_group_bwd_workspace_bytes(int E, int T, int K, int N, int group_size);
+FQL_API int fql_moe_group_bwd_input(const uint8_t *packed, const float *scales, const float *zps, const void *grad_out,
+                                    int grad_out_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                    void *grad_in, int grad_in_dtype, int E, int T, int K, int N, int group_size,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Format helpers on the device (same unpack code path as the GEMM kernels; bit-exact).
