@@ -1,0 +1,118 @@
+// libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd) over the kernels of
+// fql_gemm_mx4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+#include "../../include/fql_int4.h"
+#include "fql_common.h"
+#include "fql_host.h"
+#include "fql_gemm_mx4.h"
+
+#include <cmath>
+
+namespace {
+
+using namespace fql_host;
+
+struct Mx4Call {
+    const uint8_t *blocks, *scales;
+    const void *rows;                 // [T][K] of in_dtype
+    const float *bias;
+    const int32_t *tpe, *offs;
+    void *out;
+    int E, T, K, N;
+};
+
+template <int IN, int OUT>
+int launch_mx4(const Mx4Call &c, hipStream_t st)
+{
+    using C = Mx4Cfg;                                        // (one more z-slice zeroes the rows no expert covers)
+    return launch(mx4_kernel<IN, OUT>, dim3((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1),
+                  dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+}
+
+template <int IN>
+int launch_mx4_out(int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return launch_mx4<IN, FQL_DTYPE_F32>(c, st);
+    case FQL_DTYPE_F16: return launch_mx4<IN, FQL_DTYPE_F16>(c, st);
+    default: return launch_mx4<IN, FQL_DTYPE_BF16>(c, st);
+    }
+}
+
+int launch_mx4_in(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    return in_dtype == FQL_DTYPE_F32 ? launch_mx4_out<FQL_DTYPE_F32>(out_dtype, c, st)
+                                     : launch_mx4_out<FQL_DTYPE_BF16>(out_dtype, c, st);
+}
+
+size_t mx4_h_bytes(int T, int K) { return round16((size_t)T * K * 2); }
+
+// The checks both entry points share, in the documented order; `rows` is inputs or gate_up.  FQL_OK with *empty set: an
+// empty call, nothing to launch.
+int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool act_ok, bool *empty)
+{
+    *empty = false;
+    if (c.E <= 0 || c.T < 0 || c.K <= 0 || c.N < 0 || !act_ok) return FQL_ERR_BAD_SHAPE;
+    if (c.K & 1) return FQL_ERR_ODD_K;
+    if (c.K % 32 != 0) return FQL_ERR_BAD_SHAPE;                      // one scale per 32 inputs
+    if ((in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
+    if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
+    if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
+    if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
+    if (c.E > 65534) return FQL_ERR_BAD_SHAPE;                        // (the grid's z: the experts and the coverage slice)
+    if ((c.T + Mx4Cfg::BT - 1) / Mx4Cfg::BT > 65535) return FQL_ERR_BAD_SHAPE;
+    if ((long long)c.T * (in_cols / 8) / 256 >= 0x7FFFFFFFLL) return FQL_ERR_BAD_SHAPE;
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
+        (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
+    return FQL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+FQL_API size_t fql_moe_mx4_workspace_bytes(int E, int T, int K, int N, int gated)
+{
+    (void)E; (void)N;
+    if (!gated || T <= 0 || K <= 0) return 0;
+    return mx4_h_bytes(T, K);                                         // h [T][K] bfloat16
+}
+
+FQL_API int fql_moe_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                            const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                            int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    const Mx4Call c{blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_mx4_in(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    bool act_ok = activation == FQL_ACT_SILU || activation == FQL_ACT_GELU_TANH || activation == FQL_ACT_SWIGLU_CLAMP;
+    if (act_ok && activation != FQL_ACT_SILU)
+        act_ok = std::isfinite(act_alpha) && std::isfinite(act_limit) && act_limit > 0.0f;
+    Mx4Call c{blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, act_ok, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    if (!workspace || !aligned16(workspace) || workspace_bytes < mx4_h_bytes(T, K)) return FQL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned short *hbuf = static_cast<unsigned short *>(workspace);
+    const dim3 grid((unsigned)(((long long)T * (K / 8) + 255) / 256));
+    const int lrc = in_dtype == FQL_DTYPE_F32
+        ? launch(mx4_glu_kernel<FQL_DTYPE_F32>, grid, dim3(256), 0, st, gate_up, hbuf, T, K, activation, act_alpha, act_limit)
+        : launch(mx4_glu_kernel<FQL_DTYPE_BF16>, grid, dim3(256), 0, st, gate_up, hbuf, T, K, activation, act_alpha, act_limit);
+    if (lrc != FQL_OK) return lrc;
+    c.rows = hbuf;
+    return launch_mx4_in(FQL_DTYPE_BF16, out_dtype, c, st);
+}
+
+}  // extern "C"

@@ -454,6 +454,145 @@ class _GatedFFN16Fn(_GatedFFNFn):
         return dx, None, None, None, gbgu, gbd
 
 
+class MXFP4MoEFFN(nn.Module):
+    """Gated FFN experts on OCP MXFP4 weights (the format gpt-oss ships its experts in), inference only:
+    ``down( act(gate(x), up(x)) )`` per expert, rows pre-grouped by expert, the same ``forward`` as ``QuantizedMoEFFN``.
+
+    The weights are uint8 buffers in the checkpoint's own encoding, never re-quantised: ``gate_up_blocks`` [E, 2F, H/2] and
+    ``down_blocks`` [E, H, F/2] hold two e2m1 codes a byte (even input in the low nibble), ``gate_up_scales`` [E, 2F, H/32]
+    and ``down_scales`` [E, H, F/32] one E8M0 power-of-two scale per 32 consecutive inputs.  Rows 0 .. F-1 of ``gate_up``
+    are the gate, F .. 2F-1 the up projection (``from_mxfp4(interleaved=True)`` converts gpt-oss's alternating order).
+    ``expert_bias=True`` adds float32 ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H], as in ``QuantizedMoEFFN``.
+
+    Both GEMMs are ``ops.moe_forward_mxfp4`` / ``ops.moe_gated_forward_mxfp4``: the weights are exact in bfloat16, the
+    activations are rounded once to bfloat16 (float32 inputs) or read as they are (bfloat16), the sums are float32.
+    ``activation_dtype=torch.bfloat16`` takes bfloat16 inputs, keeps ``gate_up`` in bfloat16 and returns bfloat16; the
+    default takes float32 and keeps ``gate_up`` in float32.  There is no backward on this format: a forward under grad mode
+    on an input that requires grad raises ``RuntimeError``.  ``QuantizedSparseMoEBlock(experts=MXFP4MoEFFN(...))`` works
+    under ``torch.no_grad()``."""
+
+    group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, activation: str = "silu",
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
+                 activation_dtype=None):
+        super().__init__()
+        if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0:
+            raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 (one scale per 32 inputs)")
+        if activation_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("activation_dtype must be None, torch.float32 or torch.bfloat16 (float16 rows are refused: "
+                             "rounding them to bfloat16 would lose three bits)")
+        from . import ops
+        self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
+        self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
+            activation, activation_alpha, activation_limit)
+        self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
+        E, H, F = num_experts, hidden_dim, ffn_dim
+        self.register_buffer("gate_up_blocks", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
+        self.register_buffer("gate_up_scales", torch.full((E, 2 * F, H // 32), 127, dtype=torch.uint8))
+        self.register_buffer("down_blocks", torch.zeros(E, H, F // 2, dtype=torch.uint8))
+        self.register_buffer("down_scales", torch.full((E, H, F // 32), 127, dtype=torch.uint8))
+        self.expert_bias = bool(expert_bias)
+        if self.expert_bias:
+            self.gate_up_bias = nn.Parameter(torch.zeros(E, 2 * F, dtype=torch.float32), requires_grad=False)
+            self.down_bias = nn.Parameter(torch.zeros(E, H, dtype=torch.float32), requires_grad=False)
+
+    @classmethod
+    def from_mxfp4(cls, gate_up_blocks, gate_up_scales, down_blocks, down_scales, gate_up_bias=None, down_bias=None,
+                   interleaved: bool = False, **kwargs) -> "MXFP4MoEFFN":
+        """Tensors already in the format: ``gate_up_blocks`` [E, 2F, H/2] (or [E, 2F, H/32, 16], the checkpoint's block
+        dimension, flattened here), ``gate_up_scales`` [E, 2F, H/32], ``down_blocks`` [E, H, F/2] (or [E, H, F/32, 16]),
+        ``down_scales`` [E, H, F/32], all uint8; ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H] (both or none).
+        ``interleaved=True``: rows 0, 2, 4, ... of ``gate_up`` are the gate and 1, 3, 5, ... the up projection (gpt-oss's
+        order); they are de-interleaved once, the bias included.  ``kwargs``: the constructor's activation arguments and
+        ``activation_dtype``."""
+        def flat(name, b, s):
+            if b.dtype != torch.uint8 or s.dtype != torch.uint8:
+                raise ValueError(f"{name}_blocks and {name}_scales must be uint8")
+            if b.dim() == 4 and b.shape[-1] == 16:
+                b = b.reshape(b.shape[0], b.shape[1], -1)
+            if b.dim() != 3 or s.dim() != 3 or tuple(s.shape) != (b.shape[0], b.shape[1], b.shape[2] // 16) or b.shape[2] % 16:
+                raise ValueError(f"{name}_blocks must be [E, N, K/2] (or [E, N, K/32, 16]) and {name}_scales [E, N, K/32]")
+            return b, s
+        gub, gus = flat("gate_up", gate_up_blocks, gate_up_scales)
+        db, ds = flat("down", down_blocks, down_scales)
+        E, F2, H = gub.shape[0], gub.shape[1], gub.shape[2] * 2
+        if F2 % 2 or tuple(db.shape) != (E, H, F2 // 4):
+            raise ValueError("gate_up must be [E, 2F, H/2] and down [E, H, F/2] of the same E, H and F")
+        if (gate_up_bias is None) != (down_bias is None):
+            raise ValueError("gate_up_bias and down_bias come together: pass both or none")
+        if gate_up_bias is not None and (tuple(gate_up_bias.shape) != (E, F2) or tuple(down_bias.shape) != (E, H)):
+            raise ValueError("gate_up_bias must be [E, 2F] and down_bias [E, H]")
+        if interleaved:
+            split = lambda t: torch.cat([t[:, 0::2], t[:, 1::2]], dim=1)
+            gub, gus = split(gub), split(gus)
+            gate_up_bias = None if gate_up_bias is None else split(gate_up_bias)
+        m = cls(E, H, F2 // 2, expert_bias=gate_up_bias is not None, **kwargs)
+        m.gate_up_blocks, m.gate_up_scales = gub.contiguous().clone(), gus.contiguous().clone()
+        m.down_blocks, m.down_scales = db.contiguous().clone(), ds.contiguous().clone()
+        if gate_up_bias is not None:
+            with torch.no_grad():
+                m.gate_up_bias.data = gate_up_bias.detach().float().contiguous().clone()
+                m.down_bias.data = down_bias.detach().float().contiguous().clone()
+        return m
+
+    @classmethod
+    def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor], gate_bias=None,
+                     up_bias=None, down_bias=None, **kwargs) -> "MXFP4MoEFFN":
+        """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` float weights, quantised with
+        ``quantize.quantize_mxfp4``; the biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
+        from .quantize import quantize_mxfp4
+        given = [b is not None for b in (gate_bias, up_bias, down_bias)]
+        if any(given) and not all(given):
+            raise ValueError("gate_bias, up_bias and down_bias come together: pass all three or none")
+        gub, gus = quantize_mxfp4(torch.stack([torch.cat([g.float(), u.float()], dim=0) for g, u in zip(gate, up)]))
+        db, ds = quantize_mxfp4(torch.stack([d.float() for d in down]))
+        b_gu = torch.stack([torch.cat([g.float(), u.float()]) for g, u in zip(gate_bias, up_bias)]) if all(given) else None
+        b_d = torch.stack([d.float() for d in down_bias]) if all(given) else None
+        return cls.from_mxfp4(gub, gus, db, ds, gate_up_bias=b_gu, down_bias=b_d, **kwargs)
+
+    def forward(self, inputs, tokens_per_expert, input_offsets):
+        """inputs ``[T, H]`` float32 (``activation_dtype=torch.bfloat16``: bfloat16) rows grouped by expert -> ``[T, H]`` of
+        the same type."""
+        if not inputs.is_cuda:
+            raise RuntimeError("MXFP4MoEFFN runs on the GPU (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and inputs.requires_grad:
+            raise RuntimeError("MXFP4MoEFFN is inference-only: the MXFP4 format has no backward.  Run it under "
+                               "torch.no_grad(), or on a detached input")
+        from . import ops
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
+        if inputs.dim() != 2 or inputs.dtype != dt:
+            raise RuntimeError(f"MXFP4MoEFFN: inputs must be a 2-D {dt} tensor (the layer's activation_dtype), got "
+                               f"{inputs.dtype}")
+        b_gu, b_d = self.biases
+        b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
+        gate_up = ops.moe_forward_mxfp4(self.gate_up_blocks, self.gate_up_scales, inputs, tokens_per_expert, input_offsets,
+                                        bias=b_gu, out_dtype=dt)
+        return ops.moe_gated_forward_mxfp4(self.down_blocks, self.down_scales, gate_up, tokens_per_expert, input_offsets,
+                                           activation=self.activation, activation_alpha=self.activation_alpha,
+                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt)
+
+    @property
+    def biases(self):
+        """``(gate_up_bias, down_bias)``, or ``(None, None)`` for a layer built without ``expert_bias``."""
+        return (self.gate_up_bias, self.down_bias) if self.expert_bias else (None, None)
+
+    @property
+    def total_memory_bytes(self) -> int:
+        return (sum(b.numel() * b.element_size() for b in self.buffers())
+                + sum(b.numel() * b.element_size() for b in self.biases if b is not None))
+
+    @property
+    def activation_args(self):
+        """``(activation, activation_alpha, activation_limit)`` as the ops take them."""
+        return self.activation, self.activation_alpha, self.activation_limit
+
+    _activation_repr = QuantizedMoEFFN._activation_repr
+
+    def extra_repr(self) -> str:
+        return ("format=mxfp4" + self._activation_repr())
+
+
 class QuantizedSparseMoEBlock(nn.Module):
     """A Mixtral-style sparse MoE layer, hidden states in and hidden states out: a trainable float gate, the fused top-k
     router (``ops.router_topk``), the one-launch plan, a dispatch with a deterministic backward, the INT4 gated FFN
@@ -462,7 +601,7 @@ class QuantizedSparseMoEBlock(nn.Module):
 
     ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
-    when not given; a ``LoRAQuantizedMoEFFN`` may be passed in).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or under ``torch.no_grad()`` an ``MXFP4MoEFFN``).  State-dict keys: ``gate.weight`` and ``experts.*``.
     The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
     to the activations' type: no cast pass either side of it.
 

@@ -8,7 +8,7 @@ stream, nothing synchronises.  GPU tensors only -- a CPU tensor raises, exactly 
 reference's TORCH_CHECK(input.is_cuda()).
 
 Every op is built from the same few steps (DESIGN.md "The operator boundary"): ``_expert_table`` converts and checks
-the expert table, ``_check_weights`` / ``_check_group_weights`` / ``_check_bias`` the weight operands, ``_on`` the
+the expert table, ``_check_weights`` / ``_check_group_weights`` / ``_check_mxfp4`` / ``_check_bias`` the weight operands, ``_on`` the
 device of anything else, and every launch of a product op goes through ``_launch`` (the tuning hook ``tune_gemm_i8`` and
 the size / capability queries call the library directly).
 """
@@ -526,6 +526,63 @@ def moe_gated_forward(packed_weights, scales, zero_points, gate_up, tokens_per_e
                 tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, prec, _ACTIVATIONS[kind], act_alpha, act_limit,
                 ws_bytes=L.fql_moe_workspace_bytes(E, T, K, N, prec))
     return out if round_to is None else out.to(round_to)
+
+
+def _check_mxfp4(blocks, scales, dev, K):
+    """The MXFP4 weight pair on ``dev``: ``blocks`` uint8 [E, N, K/2] (two e2m1 codes a byte, even k in the low nibble)
+    and ``scales`` uint8 [E, N, K/32] (E8M0), K matching the rows' and a multiple of 32.  Returns
+    ``(blocks, scales, E, N)``, the tensors contiguous."""
+    _on(dev, blocks=blocks, scales=scales)
+    if blocks.dtype != torch.uint8 or blocks.dim() != 3 or scales.dtype != torch.uint8 or scales.dim() != 3:
+        raise RuntimeError("blocks must be uint8 [num_experts, N, K/2] and scales uint8 [num_experts, N, K/32]")
+    E, N, half = blocks.shape
+    if K % 32 != 0 or half * 2 != K or tuple(scales.shape) != (E, N, K // 32):
+        raise RuntimeError("blocks must be [num_experts, N, K/2] and scales [num_experts, N, K/32] with K % 32 == 0 the "
+                           "rows' width")
+    return blocks.contiguous(), scales.contiguous(), E, N
+
+
+def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offsets, bias, out_dtype, gated, act=()):
+    if not rows.is_cuda or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    dev, T = rows.device, rows.shape[0]
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    _launch("fql_moe_mx4_glu_fwd" if gated else "fql_moe_mx4_fwd", dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype],
+            bias, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
+            ws_bytes=_native.lib().fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated)))
+    return out
+
+
+def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, bias=None, out_dtype=None):
+    """The grouped GEMM on OCP MXFP4 expert weights: ``out[t] = W_e @ bf16(inputs[t]) (+ bias[e])`` over the rows of expert
+    e.  ``blocks`` uint8 [E, N, K/2], ``scales`` uint8 [E, N, K/32] (``quantize.quantize_mxfp4``); ``inputs`` [T, K] float32
+    (rounded once to bfloat16) or bfloat16; ``bias`` [E, N] float32 (optional), added before the one rounding to
+    ``out_dtype`` (default: the inputs' type).  The weights are exact in bfloat16 and the contraction accumulates in
+    float32 on the bfloat16 matrix cores; rows no expert covers are zero.  Forward only."""
+    _forward_only("moe_forward_mxfp4", inputs, bias)
+    K = inputs.shape[1] if inputs.dim() == 2 else 0
+    return _mxfp4_launch("moe_forward_mxfp4", blocks, scales, inputs, K, tokens_per_expert, input_offsets, bias, out_dtype, False)
+
+
+def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_offsets, activation="silu",
+                            activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None):
+    """The down projection of a gated FFN expert on MXFP4 weights: ``out[t] = W_e @ bf16(act(gate_up[t, :K], gate_up[t, K:]))
+    (+ bias[e])``, ``gate_up`` [T, 2K] float32 or bfloat16, ``blocks`` [E, N, K/2].  The activation (``activation_of``) is
+    evaluated in float32 and rounded once to bfloat16 by a streaming pre-pass into the op's workspace: no [T, K] tensor is
+    handed back.  Forward only."""
+    _forward_only("moe_gated_forward_mxfp4", gate_up, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    if gate_up.dim() != 2 or gate_up.shape[1] % 64 != 0:
+        raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
+    return _mxfp4_launch("moe_gated_forward_mxfp4", blocks, scales, gate_up, gate_up.shape[1] // 2, tokens_per_expert,
+                         input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit))
 
 
 ROUTE_MAX_EXPERTS = 128

@@ -11,6 +11,9 @@ Format: ``packed[n, j] = (q[n, 2j+1] << 4) | q[n, 2j]`` (uint8, ``[N, K/2]``),
 ``w[n, k] = (q[n, k] - zero_points[n]) * scales[n]`` with float32 ``scales``/``zero_points`` of
 shape ``[N]``.  These run on whatever device the tensors live on; on a GPU,
 ``dequantize_weights`` uses the HIP kernel of the extension.
+
+A second frozen format for the MoE experts, OCP MXFP4 (``quantize_mxfp4`` / ``dequantize_mxfp4``, pure torch): the same
+byte layout with e2m1 codes in the nibbles and one E8M0 power-of-two scale byte per 32 consecutive inputs.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 __all__ = ["quantize_weights", "dequantize_weights", "reference_quantized_linear",
-           "pack_nibbles", "unpack_nibbles"]
+           "pack_nibbles", "unpack_nibbles", "quantize_mxfp4", "dequantize_mxfp4", "MXFP4_VALUES"]
 
 
 def pack_nibbles(q: torch.Tensor) -> torch.Tensor:
@@ -93,3 +96,54 @@ def reference_quantized_linear(input: torch.Tensor, packed_weights: torch.Tensor
     they go to the fused HIP kernels via :mod:`ops`.
     """
     return F.linear(input, dequantize_weights(packed_weights, scales, zero_points))
+
+
+# ---- OCP MXFP4: e2m1 elements, two to a byte (even k in the low nibble), one E8M0 scale byte per 32 consecutive inputs
+
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+MXFP4_BLOCK = 32
+
+
+def quantize_mxfp4(weight: torch.Tensor):
+    """``[..., N, K]`` (K % 32 == 0) -> ``(blocks uint8 [..., N, K/2], scales uint8 [..., N, K/32])`` by the OCP MX rule:
+    per block of 32 consecutive inputs ``shared = floor(log2(amax)) - 2`` (2 = e2m1's largest exponent), clamped to
+    [-127, 127], scale code ``shared + 127``; the elements are ``x / 2^shared`` rounded to nearest even on the e2m1 grid
+    and saturated to +-6, the sign kept (a negative value that rounds to zero is code 8).  An all-zero block gets scale
+    code 127 and zero elements.  A non-finite weight raises ``ValueError``."""
+    if weight.dim() < 2 or weight.shape[-1] % MXFP4_BLOCK != 0:
+        raise ValueError("weight must be [..., N, K] with K % 32 == 0")
+    if not bool(torch.isfinite(weight).all()):
+        raise ValueError("quantize_mxfp4: the weights must be finite")
+    K = weight.shape[-1]
+    x = weight.detach().to(torch.float64).reshape(*weight.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = x.abs().amax(dim=-1, keepdim=True)
+    _, ex = torch.frexp(amax)                                   # amax = m * 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    shared = torch.where(amax == 0, torch.zeros_like(ex), ex - 1 - 2).clamp(-127, 127)
+    v = torch.ldexp(x.abs(), -shared)                           # exact in float64
+    q = torch.where(v < 2, torch.round(v * 2) / 2, torch.where(v < 4, torch.round(v), torch.round(v / 2) * 2)).clamp(max=6.0)
+    mag = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4)).to(torch.uint8)
+    codes = (mag | (torch.signbit(x).to(torch.uint8) << 3)).reshape(*weight.shape[:-1], K)
+    scales = (shared + 127).to(torch.uint8).reshape(*weight.shape[:-1], K // MXFP4_BLOCK)
+    return pack_nibbles(codes), scales
+
+
+def mxfp4_scale_values(scales: torch.Tensor) -> torch.Tensor:
+    """E8M0 codes (uint8) -> float32: ``2^(s - 127)`` for 0 .. 254 (code 0 is the float32 subnormal 2^-127), NaN for 255."""
+    s = scales.to(torch.int32)
+    bits = torch.where(s == 0, torch.full_like(s, 0x00400000), s << 23)
+    bits = torch.where(s == 255, torch.full_like(s, 0x7FC00000), bits)
+    return bits.view(torch.float32)
+
+
+def dequantize_mxfp4(blocks: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """``(blocks [..., N, K/2], scales [..., N, K/32])`` uint8 -> ``[..., N, K]`` float32: the 16-entry table times the
+    block's scale.  Exact, up to float32's own range (scale code 254 with |code| >= 2 is infinite)."""
+    if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError("blocks and scales must be uint8")
+    K = blocks.shape[-1] * 2
+    if K % MXFP4_BLOCK != 0 or tuple(scales.shape) != tuple(blocks.shape[:-1]) + (K // MXFP4_BLOCK,):
+        raise ValueError("blocks must be [..., N, K/2] and scales [..., N, K/32]")
+    codes = torch.stack([blocks & 0x0F, blocks >> 4], dim=-1).reshape(*blocks.shape[:-1], K)
+    table = torch.tensor(MXFP4_VALUES, dtype=torch.float32, device=blocks.device)
+    w = table[codes.long()].reshape(*blocks.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return (w * mxfp4_scale_values(scales).unsqueeze(-1)).reshape(*blocks.shape[:-1], K)

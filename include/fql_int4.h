@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 330 /* 0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 340 /* 0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -848,6 +848,47 @@ FQL_API int fql_combine_sparse_bwd(const void *grad_out, int out_dtype, const vo
                                    const float *weights, const void *addend, const float *addend_weight, int in_dtype,
                                    void *grad_y, float *grad_weights, void *grad_addend, float *grad_addend_weight, int T,
                                    int top_k, int N, int rows, void *stream);
+
+/* ---- OCP MXFP4 expert weights, forward only (FQL_VERSION 340; INTEGRATION.md section 17, DESIGN.md section 25;
+ *      csrc/fql_gemm_mx4.h) ----
+ * A second frozen 4-bit weight format for the grouped GEMM, the one gpt-oss ships its experts in:
+ *   blocks      [E][N][K / 2] uint8, two e2m1 codes a byte, even k in the low nibble (the INT4 byte layout).  Codes 0 .. 7 are
+ *               0, 0.5, 1, 1.5, 2, 3, 4, 6; codes 8 .. 15 their negatives (8 is -0);
+ *   scales_e8m0 [E][N][K / 32] uint8: code s in 0 .. 254 is 2^(s - 127) for weight row n and inputs 32 b .. 32 b + 31, code 255
+ *               is NaN (the whole block, zeros included).
+ * fql_moe_mx4_fwd:     out[t][n] = sum_k bf16(x[t][k]) * W_e[n][k] (+ bias[e][n]) over the rows t of expert e; inputs [T][K]
+ *                      float32 (rounded once to bfloat16, to nearest even) or bfloat16 (read as they are).
+ * fql_moe_mx4_glu_fwd: the same on h[t][k] = bf16(act(gate_up[t][k], gate_up[t][K + k])), gate_up [T][2K] float32 or bfloat16,
+ *                      h evaluated in float32 (act_glu_mul, the kinds of FQL_ACT_*) and rounded once, by a streaming pre-pass
+ *                      into the workspace ([T][K] bfloat16): the caller never holds it.
+ *   The weights are exact in bfloat16; the contraction runs on v_mfma_f32_32x32x16_bf16 with float32 accumulation in a fixed
+ *   order (64 k a stage, four instructions of 16 k each), so a row's result depends on its own activation row and its
+ *   expert's weights only: the grouped call equals E one-expert calls bit for bit, under any permutation of the table and
+ *   run to run.  bias [E][N] float32 or NULL is added in the epilogue, then comes the one rounding to out_dtype (float32,
+ *   bfloat16 or float16).  No atomics; every element of out [T][N] is written once, rows no expert covers as zeros by the
+ *   same launch.  tokens_per_expert / input_offsets: both, or both NULL with E == 1 (one segment).
+ *   Non-finite values: a non-finite activation (or h) makes its whole output row NaN; a scale code 255 makes exactly the
+ *   outputs of its weight row NaN, for the rows of its expert.  A weight below 2^-126 in magnitude (scale codes 0 and 1 with
+ *   the smallest element codes) may be flushed to zero, and one of 2^128 or more (scale code 254 with |code| >= 2) is
+ *   infinite, as it is in float32.
+ *   float16 inputs are refused (FQL_ERR_DTYPE): rounding them to bfloat16 would silently lose three bits.
+ *   Workspace: fql_moe_mx4_workspace_bytes(E, T, K, N, gated): 0 for fql_moe_mx4_fwd (gated == 0; the arguments may be NULL
+ *   / 0), the [T][K] bfloat16 h for fql_moe_mx4_glu_fwd (gated != 0), 16-byte aligned.
+ *   Return codes, in this order and all before any HIP call: FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0, N < 0; glu: an unknown
+ *   activation, or for a kind other than silu a non-finite act_alpha / act_limit or act_limit <= 0); FQL_ERR_ODD_K;
+ *   FQL_ERR_BAD_SHAPE (K % 32 != 0); FQL_ERR_DTYPE (in_dtype not FQL_DTYPE_F32 / _BF16, out_dtype outside FQL_DTYPE_*);
+ *   T == 0 or N == 0: FQL_OK with nothing launched; FQL_ERR_NULL_POINTER (blocks, scales_e8m0, inputs / gate_up, out; one of
+ *   the table's two arrays alone); FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65534, T > 4194240); FQL_ERR_ALIGNMENT
+ *   (blocks not 16-byte aligned; inputs / gate_up / out not aligned to their element, bias not to 4 bytes);
+ *   FQL_ERR_WORKSPACE (glu: NULL, misaligned or short); FQL_ERR_LAUNCH. */
+FQL_API size_t fql_moe_mx4_workspace_bytes(int E, int T, int K, int N, int gated);
+FQL_API int fql_moe_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                            const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                            int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                float act_limit, void *workspace, size_t workspace_bytes, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
