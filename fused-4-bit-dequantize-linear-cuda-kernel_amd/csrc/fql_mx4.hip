@@ -1,9 +1,10 @@
-// libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd) over the kernels of
-// fql_gemm_mx4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
+// fql_moe_mx4_bwd_input) over the kernels of fql_gemm_mx4.h and fql_gemm_mx4_bwd.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
 #include "fql_host.h"
 #include "fql_gemm_mx4.h"
+#include "fql_gemm_mx4_bwd.h"
 
 #include <cmath>
 
@@ -42,6 +43,25 @@ int launch_mx4_in(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
 {
     return in_dtype == FQL_DTYPE_F32 ? launch_mx4_out<FQL_DTYPE_F32>(out_dtype, c, st)
                                      : launch_mx4_out<FQL_DTYPE_BF16>(out_dtype, c, st);
+}
+
+// The input gradient: c.rows is grad_out [T][N], c.out grad_in [T][K].
+template <int IN, int OUT>
+int launch_mx4_bwd(const Mx4Call &c, hipStream_t st)
+{
+    using C = Mx4BwdCfg;                                     // (one more z-slice zeroes the rows no expert covers)
+    return launch(mx4_bwd_kernel<IN, OUT>, dim3((c.K + C::BK - 1) / C::BK, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1),
+                  dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+}
+
+template <int IN>
+int launch_mx4_bwd_out(int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return launch_mx4_bwd<IN, FQL_DTYPE_F32>(c, st);
+    case FQL_DTYPE_F16: return launch_mx4_bwd<IN, FQL_DTYPE_F16>(c, st);
+    default: return launch_mx4_bwd<IN, FQL_DTYPE_BF16>(c, st);
+    }
 }
 
 size_t mx4_h_bytes(int T, int K) { return round16((size_t)T * K * 2); }
@@ -113,6 +133,27 @@ FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m
     if (lrc != FQL_OK) return lrc;
     c.rows = hbuf;
     return launch_mx4_in(FQL_DTYPE_BF16, out_dtype, c, st);
+}
+
+FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *grad_out, int in_dtype,
+                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
+                                  int out_dtype, int E, int T, int K, int N, void *stream)
+{
+    static_assert(Mx4BwdCfg::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the forward's row tile");
+    const Mx4Call c{blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, true, &empty);
+    if (rc != FQL_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty) {
+        if (T == 0) return FQL_OK;
+        // N == 0: the gradient of an empty contraction.  grad_in [T][K] is zeros and no other operand is read.
+        if (!grad_in) return FQL_ERR_NULL_POINTER;
+        (void)hipGetLastError();
+        return hipMemsetAsync(grad_in, 0, (size_t)T * K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    }
+    return in_dtype == FQL_DTYPE_F32 ? launch_mx4_bwd_out<FQL_DTYPE_F32>(out_dtype, c, st)
+                                     : launch_mx4_bwd_out<FQL_DTYPE_BF16>(out_dtype, c, st);
 }
 
 }  // extern "C"

@@ -454,8 +454,42 @@ class _GatedFFN16Fn(_GatedFFNFn):
         return dx, None, None, None, gbgu, gbd
 
 
+class _MXFP4GatedFFNFn(torch.autograd.Function):
+    """``MXFP4MoEFFN(input_grad=True)`` with the input gradient, modelled on ``_GatedFFN16Fn``.  Keeps ``gate_up`` in the
+    layer's type (float32 or bfloat16); the backward is ``dh`` on the down weights (``ops.moe_backward_input_mxfp4``),
+    ``ops.glu_backward`` for every activation kind and ``dx`` on the gate / up weights, each tensor written once in that
+    type.  ``b_gu`` / ``b_d`` are inputs so that autograd can ask for their gradients: ``ops.moe_bias_grad`` of dgu and of
+    gy, launched only for a bias that requires grad."""
+
+    @staticmethod
+    def forward(ctx, inputs, tokens_per_expert, input_offsets, m, b_gu=None, b_d=None):
+        out, gate_up = m._ffn(inputs, tokens_per_expert, input_offsets)
+        ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        gate_up, tpe, offs = ctx.saved_tensors
+        m = ctx.m
+        dt = gate_up.dtype
+        ops.check_activation_rows(gy, "the incoming gradient", dt)
+        need_x, need_bgu, need_bd = ctx.needs_input_grad[0], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        gbd = ops.moe_bias_grad(gy, m.num_experts, tpe, offs) if need_bd else None
+        if not (need_x or need_bgu):
+            return None, None, None, None, None, gbd
+        dh = ops.moe_backward_input_mxfp4(m.down_blocks, m.down_scales, gy, tpe, offs, out_dtype=dt)
+        dgu = ops.glu_backward(gate_up, dh, *m.activation_args, out_dtype=dt)
+        gbgu = ops.moe_bias_grad(dgu, m.num_experts, tpe, offs) if need_bgu else None
+        dx = ops.moe_backward_input_mxfp4(m.gate_up_blocks, m.gate_up_scales, dgu, tpe, offs, out_dtype=dt) \
+            if need_x else None
+        return dx, None, None, None, gbgu, gbd
+
+
 class MXFP4MoEFFN(nn.Module):
-    """Gated FFN experts on OCP MXFP4 weights (the format gpt-oss ships its experts in), inference only:
+    """Gated FFN experts on OCP MXFP4 weights (the format gpt-oss ships its experts in), frozen:
     ``down( act(gate(x), up(x)) )`` per expert, rows pre-grouped by expert, the same ``forward`` as ``QuantizedMoEFFN``.
 
     The weights are uint8 buffers in the checkpoint's own encoding, never re-quantised: ``gate_up_blocks`` [E, 2F, H/2] and
@@ -467,15 +501,23 @@ class MXFP4MoEFFN(nn.Module):
     Both GEMMs are ``ops.moe_forward_mxfp4`` / ``ops.moe_gated_forward_mxfp4``: the weights are exact in bfloat16, the
     activations are rounded once to bfloat16 (float32 inputs) or read as they are (bfloat16), the sums are float32.
     ``activation_dtype=torch.bfloat16`` takes bfloat16 inputs, keeps ``gate_up`` in bfloat16 and returns bfloat16; the
-    default takes float32 and keeps ``gate_up`` in float32.  There is no backward on this format: a forward under grad mode
-    on an input that requires grad raises ``RuntimeError``.  ``QuantizedSparseMoEBlock(experts=MXFP4MoEFFN(...))`` works
-    under ``torch.no_grad()``."""
+    default takes float32 and keeps ``gate_up`` in float32.
+
+    ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
+    ``RuntimeError``, and ``QuantizedSparseMoEBlock(experts=MXFP4MoEFFN(...))`` works under ``torch.no_grad()``.
+    ``input_grad=True`` makes the layer differentiable in its input and, for biases that ``requires_grad``, in its biases
+    (the weights stay frozen): under grad mode the forward (the same kernels, the same bits) keeps ``gate_up`` and the
+    backward is ``dh = ops.moe_backward_input_mxfp4`` on the down weights, ``ops.glu_backward``, then ``dx`` on the gate /
+    up weights, every tensor in the layer's activation type.  The gradient is straight-through across the forward's two
+    bfloat16 roundings, of ``x`` and of ``h``: it is the gradient of the function without them, evaluated at the
+    forward's values, and the backward rounds its own operands (``gy``, ``dgu``) once to bfloat16 in the same way.  The
+    keyword is configuration, not state: the state-dict keys do not change."""
 
     group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, activation: str = "silu",
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
-                 activation_dtype=None):
+                 activation_dtype=None, input_grad: bool = False):
         super().__init__()
         if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0:
             raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 (one scale per 32 inputs)")
@@ -487,6 +529,7 @@ class MXFP4MoEFFN(nn.Module):
         self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
             activation, activation_alpha, activation_limit)
         self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
+        self.input_grad = bool(input_grad)
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_blocks", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
         self.register_buffer("gate_up_scales", torch.full((E, 2 * F, H // 32), 127, dtype=torch.uint8))
@@ -504,8 +547,8 @@ class MXFP4MoEFFN(nn.Module):
         dimension, flattened here), ``gate_up_scales`` [E, 2F, H/32], ``down_blocks`` [E, H, F/2] (or [E, H, F/32, 16]),
         ``down_scales`` [E, H, F/32], all uint8; ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H] (both or none).
         ``interleaved=True``: rows 0, 2, 4, ... of ``gate_up`` are the gate and 1, 3, 5, ... the up projection (gpt-oss's
-        order); they are de-interleaved once, the bias included.  ``kwargs``: the constructor's activation arguments and
-        ``activation_dtype``."""
+        order); they are de-interleaved once, the bias included.  ``kwargs``: the constructor's activation arguments,
+        ``activation_dtype`` and ``input_grad``."""
         def flat(name, b, s):
             if b.dtype != torch.uint8 or s.dtype != torch.uint8:
                 raise ValueError(f"{name}_blocks and {name}_scales must be uint8")
@@ -556,21 +599,31 @@ class MXFP4MoEFFN(nn.Module):
         the same type."""
         if not inputs.is_cuda:
             raise RuntimeError("MXFP4MoEFFN runs on the GPU (the product path has no CPU fallback)")
-        if torch.is_grad_enabled() and inputs.requires_grad:
+        if not self.input_grad and torch.is_grad_enabled() and inputs.requires_grad:
             raise RuntimeError("MXFP4MoEFFN is inference-only: the MXFP4 format has no backward.  Run it under "
-                               "torch.no_grad(), or on a detached input")
-        from . import ops
+                               "torch.no_grad(), or on a detached input (or build the layer with input_grad=True)")
         dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
         if inputs.dim() != 2 or inputs.dtype != dt:
             raise RuntimeError(f"MXFP4MoEFFN: inputs must be a 2-D {dt} tensor (the layer's activation_dtype), got "
                                f"{inputs.dtype}")
         b_gu, b_d = self.biases
+        if self.input_grad and torch.is_grad_enabled() and (
+                inputs.requires_grad or (b_gu is not None and (b_gu.requires_grad or b_d.requires_grad))):
+            return _MXFP4GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self, b_gu, b_d)
+        return self._ffn(inputs, tokens_per_expert, input_offsets)[0]
+
+    def _ffn(self, inputs, tokens_per_expert, input_offsets):
+        """(y, gate_up) in the layer's activation type, on detached biases (their gradient is the autograd node's
+        business)."""
+        from . import ops
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
+        b_gu, b_d = self.biases
         b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
-        gate_up = ops.moe_forward_mxfp4(self.gate_up_blocks, self.gate_up_scales, inputs, tokens_per_expert, input_offsets,
-                                        bias=b_gu, out_dtype=dt)
+        gate_up = ops.moe_forward_mxfp4(self.gate_up_blocks, self.gate_up_scales, inputs.detach(), tokens_per_expert,
+                                        input_offsets, bias=b_gu, out_dtype=dt)
         return ops.moe_gated_forward_mxfp4(self.down_blocks, self.down_scales, gate_up, tokens_per_expert, input_offsets,
                                            activation=self.activation, activation_alpha=self.activation_alpha,
-                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt)
+                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt), gate_up
 
     @property
     def biases(self):
@@ -590,7 +643,7 @@ class MXFP4MoEFFN(nn.Module):
     _activation_repr = QuantizedMoEFFN._activation_repr
 
     def extra_repr(self) -> str:
-        return ("format=mxfp4" + self._activation_repr())
+        return ("format=mxfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else ""))
 
 
 class QuantizedSparseMoEBlock(nn.Module):
@@ -601,7 +654,8 @@ class QuantizedSparseMoEBlock(nn.Module):
 
     ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
-    when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or under ``torch.no_grad()`` an ``MXFP4MoEFFN``).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or an ``MXFP4MoEFFN``: built with ``input_grad=True`` it trains the
+    router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``).  State-dict keys: ``gate.weight`` and ``experts.*``.
     The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
     to the activations' type: no cast pass either side of it.
 

@@ -1152,6 +1152,32 @@ def moe_backward_input(packed_weights, scales, zero_points, grad_out, tokens_per
     return out
 
 
+def moe_backward_input_mxfp4(blocks, scales, grad_out, tokens_per_expert, input_offsets, out_dtype=None):
+    """Grouped ``grad_in[t] = bf16(grad_out[t]) @ W_e`` on OCP MXFP4 expert weights, for the rows of each expert's range;
+    rows no expert covers are zero.  ``blocks`` uint8 [E, N, K/2] and ``scales`` uint8 [E, N, K/32] as
+    ``moe_forward_mxfp4`` takes them; ``grad_out`` [T, N] float32 (rounded once to bfloat16) or bfloat16 -> [T, K]
+    ``out_dtype`` (default float32), rounded once.  The transposed bfloat16 matrix-core GEMM of csrc/fql_gemm_mx4_bwd.h: the
+    weights are exact, the accumulation is float32 in a fixed order, so the grouped call equals the one-expert calls bit
+    for bit.  The table as ``moe_forward`` takes it, or none with one expert (all rows).  A non-finite element of a
+    gradient row makes that whole row of the result NaN."""
+    # (types and shapes first, then the devices: the argument errors read the same with or without a GPU)
+    if grad_out.dim() != 2 or grad_out.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("ops.moe_backward_input_mxfp4: grad_out must be a float32 or bfloat16 [T, N] tensor (float16 is "
+                           "refused: rounding it to bfloat16 would lose three bits; cast it yourself)")
+    if blocks.dtype != torch.uint8 or blocks.dim() != 3 or scales.dtype != torch.uint8 or scales.dim() != 3:
+        raise RuntimeError("blocks must be uint8 [num_experts, N, K/2] and scales uint8 [num_experts, N, K/32]")
+    if grad_out.shape[1] != blocks.shape[1]:
+        raise RuntimeError("grad_out must be [T, N] for blocks [num_experts, N, K/2]")
+    out_dtype = _grad_dtypes(grad_out, out_dtype, "T")
+    dev, T, K = grad_out.device, grad_out.shape[0], 2 * blocks.shape[2]
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
+    out = torch.empty((T, K), dtype=out_dtype, device=dev)
+    _launch("fql_moe_mx4_bwd_input", dev, blocks, scales, grad_out.contiguous(), _DTYPES[grad_out.dtype], tpe, offs, out,
+            _DTYPES[out_dtype], E, T, K, N)
+    return out
+
+
 def moe_bias_grad(grad_rows, num_experts, tokens_per_expert=None, input_offsets=None):
     """Gradient of a per-expert bias: ``grad_bias[e] = sum of grad_rows[t] over the rows t of expert e`` -> [E, N] float32.
     ``grad_rows`` [T, N] float32 / float16 / bfloat16 (read as it is, widened exactly); the expert table as

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 340 /* 0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 350 /* 0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -889,6 +889,30 @@ FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m
                                 const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
                                 void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
                                 float act_limit, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the input gradient of the MXFP4 expert weights (FQL_VERSION 350; INTEGRATION.md section 17, DESIGN.md section 26;
+ *      csrc/fql_gemm_mx4_bwd.h) ----
+ * fql_moe_mx4_bwd_input: grad_in[t][k] = sum_n bf16(grad_out[t][n]) * W_e[n][k] over the rows t of expert e, on the blocks and
+ *   scales_e8m0 of the forward entries.  grad_out [T][N] float32 (rounded once to bfloat16, to nearest even) or bfloat16 (read
+ *   as it is); float16 is refused as in the forward.  grad_in [T][K] of out_dtype (float32, bfloat16 or float16), rounded once.
+ *   The transposed grouped GEMM on v_mfma_f32_32x32x16_bf16 with float32 accumulation in a fixed order (64 n a stage, four
+ *   instructions of 16 n each): a row's result depends on its own gradient row and its expert's weights only, so the grouped
+ *   call equals E one-expert calls bit for bit, under any permutation of the table and run to run.  No atomics, no
+ *   workspace; every element of grad_in is written once, rows no expert covers as zeros by the same launch.  The table as in
+ *   the forward (both arrays, or both NULL with E == 1).
+ *   Non-finite values: a non-finite element of a gradient row makes that whole row of grad_in NaN; a scale code 255 makes
+ *   grad_in NaN for exactly the 32 k of its block, on the rows of its expert.
+ *   grad_out and grad_in need the alignment of their element only (16-byte aligned operands take the wide loads / stores).
+ *   Return codes, in this order and all before any HIP call: FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0, N < 0); FQL_ERR_ODD_K;
+ *   FQL_ERR_BAD_SHAPE (K % 32 != 0); FQL_ERR_DTYPE (in_dtype not FQL_DTYPE_F32 / _BF16, out_dtype outside FQL_DTYPE_*);
+ *   T == 0: FQL_OK with nothing launched; N == 0 (T > 0): the gradient of an empty contraction, grad_in [T][K] is set to zeros
+ *   and nothing else is read or checked: FQL_ERR_NULL_POINTER (grad_in), else FQL_OK; FQL_ERR_NULL_POINTER (blocks,
+ *   scales_e8m0, grad_out, grad_in; one of the table's two arrays alone); FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65534,
+ *   T > 4194240); FQL_ERR_ALIGNMENT (blocks not 16-byte aligned; grad_out / grad_in not aligned to their element);
+ *   FQL_ERR_LAUNCH. */
+FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *grad_out, int in_dtype,
+                                  const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
+                                  int out_dtype, int E, int T, int K, int N, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
