@@ -397,17 +397,22 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(
         const __amdgpu_buffer_rsrc_t rsZ = __builtin_amdgcn_make_buffer_rsrc((void *)(zps + (size_t)tp.e * N), 0, N * 4, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsBi = __builtin_amdgcn_make_buffer_rsrc(
             (void *)(bias != nullptr ? bias + (size_t)tp.e * N : scales), 0, bias != nullptr ? N * 4 : 0, 0x00020000);
+        // BN is a multiple of the wave size, so the 64 elements a wave fetches in one round belong to ONE of the three
+        // arrays: the descriptor is picked per wave (scalar selects) and a round is ONE load whose result goes to LDS as
+        // it is (park_sz).  (Three loads per round, one per array and two of them out of bounds, OR-ed together: the OR
+        // is a use of the loads right where they are issued -- a vmcnt(0) wait at the start of every visit, behind the
+        // epilogue's stores and the weight stage in flight, ~730 cycles -- and the per-lane scalar offset made every
+        // one of the nine loads a waterfall loop.)
+        static_assert(C::BN % 64 == 0, "a wave's 64 elements of a scale / zero-point / bias round lie in one array");
+        const int so = tp.ok ? 0 : OOB;
 #pragma unroll
         for (int i = 0; i < C::SZN; ++i) {
-            const int idx = tid + i * C::THREADS;
-            const int arr = idx < C::BN ? 0 : (idx < 2 * C::BN ? 1 : 2);
-            const int col = idx - arr * C::BN;
-            const int so = (tp.ok && idx < 3 * C::BN) ? 0 : OOB;
-            const int vo = (tp.n0 + col) * 4;
-            const int vs = __builtin_amdgcn_raw_buffer_load_b32(rsS, arr == 0 ? vo : OOB, so, 0);
-            const int vz = __builtin_amdgcn_raw_buffer_load_b32(rsZ, arr == 1 ? vo : OOB, so, 0);
-            const int vb = __builtin_amdgcn_raw_buffer_load_b32(rsBi, arr == 2 ? vo : OOB, so, 0);
-            szr[i] = __builtin_bit_cast(float, vs | vz | vb);
+            const int idx0 = wave * 64 + i * C::THREADS;     // (wave-uniform) first element of this wave's round
+            const int arr = idx0 < C::BN ? 0 : (idx0 < 2 * C::BN ? 1 : 2);
+            const __amdgpu_buffer_rsrc_t rsX = arr == 0 ? rsS : (arr == 1 ? rsZ : rsBi);
+            const int col = idx0 - arr * C::BN + lane;
+            const int vo = idx0 < 3 * C::BN ? (tp.n0 + col) * 4 : OOB;
+            szr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, vo, so, 0));
         }
     };
     // (the zero points are parked NEGATED: the epilogue's fmaf(-zp, rowsum, acc) then needs no sign flip per use)
@@ -570,8 +575,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(
         int rsi[L];
 #pragma unroll
         for (int l = 0; l < L; ++l) rsi[l] = __builtin_amdgcn_raw_buffer_load_b32(rsR, (L * tsel + l * T + t) * 4, 0, 0);
-        const int d2bits = RES ? __builtin_amdgcn_raw_buffer_load_b32(rsD, (T + t) * 4, 0, 0) : 0;
-        const bool addp = RES && (d2bits & 0x7fffffff) != 0;
+        // (what the epilogue makes of d2bits is computed there, from an opaque copy: a compare here is a use of the load
+        //  where it is issued, and with it a wait for every vector-memory operation in flight)
+        int d2bits = RES ? __builtin_amdgcn_raw_buffer_load_b32(rsD, (T + t) * 4, 0, 0) : 0;
         const float rw = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsD, row_scaled ? ((RES ? 2 : 1) * T + t) * 4 : OOB, 0, 0));
         issue_sz(nxt);
 
@@ -801,6 +807,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(
         // The accumulators are read in ONE place per path (per-mode copies of a loop get their common accumulator reads
         // hoisted in front of the branch: all 288 at once).
         const int mode = (!RES || (!rpass && cur.ad == 0)) ? 0 : (rpass ? 1 : 2);
+        asm volatile("" : "+v"(d2bits));
+        const bool addp = RES && (d2bits & 0x7fffffff) != 0;
         const bool vec = ((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & (out_kind == 0 ? 15 : 7)) == 0);
         float rs[L];
 #pragma unroll
@@ -862,7 +870,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(
                             for (int c = 0; c < 4; ++c) o[q][c] *= rw;
                     }
                 }
-                if (fast) {
+                // (expected: the block layout keeps this path in line with the arithmetic -- with the general path laid out
+                //  first, every fragment jumped ~2000 instructions away and back: 1300 -> 1550 cycles per fragment)
+                if (__builtin_expect(fast, 1)) {
                     // (buffer stores: ONE 32-bit offset register per lane, fragment and quad in the scalar offset -- 64-bit
                     //  store pointers kept across the fragments were spilled, and every scratch reload is a vmcnt(0) wait
                     //  behind the next tile's prefetch)
