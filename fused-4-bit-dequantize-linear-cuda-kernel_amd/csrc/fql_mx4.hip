@@ -1,10 +1,12 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
-// fql_moe_mx4_bwd_input) over the kernels of fql_gemm_mx4.h and fql_gemm_mx4_bwd.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_moe_mx4_bwd_input, and the fp8-row entries fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8) over the kernels of
+// fql_gemm_mx4.h, fql_gemm_mx4_bwd.h and fql_gemm_mx4_f8.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
 #include "fql_host.h"
 #include "fql_gemm_mx4.h"
 #include "fql_gemm_mx4_bwd.h"
+#include "fql_gemm_mx4_f8.h"
 
 #include <cmath>
 
@@ -19,6 +21,7 @@ struct Mx4Call {
     const int32_t *tpe, *offs;
     void *out;
     int E, T, K, N;
+    const float *act_scale = nullptr;  // [T] or NULL (the fp8-row kernel only)
 };
 
 template <int IN, int OUT>
@@ -67,14 +70,14 @@ int launch_mx4_bwd_out(int out_dtype, const Mx4Call &c, hipStream_t st)
 size_t mx4_h_bytes(int T, int K) { return round16((size_t)T * K * 2); }
 
 // The checks both entry points share, in the documented order; `rows` is inputs or gate_up.  FQL_OK with *empty set: an
-// empty call, nothing to launch.
-int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool act_ok, bool *empty)
+// empty call, nothing to launch.  e4m3_rows: the rows are bytes (in_dtype is not looked at).
+int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool act_ok, bool *empty, bool e4m3_rows = false)
 {
     *empty = false;
     if (c.E <= 0 || c.T < 0 || c.K <= 0 || c.N < 0 || !act_ok) return FQL_ERR_BAD_SHAPE;
     if (c.K & 1) return FQL_ERR_ODD_K;
     if (c.K % 32 != 0) return FQL_ERR_BAD_SHAPE;                      // one scale per 32 inputs
-    if ((in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if ((!e4m3_rows && in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
     if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
     if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
@@ -82,10 +85,47 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool a
     if (c.E > 65534) return FQL_ERR_BAD_SHAPE;                        // (the grid's z: the experts and the coverage slice)
     if ((c.T + Mx4Cfg::BT - 1) / Mx4Cfg::BT > 65535) return FQL_ERR_BAD_SHAPE;
     if ((long long)c.T * (in_cols / 8) / 256 >= 0x7FFFFFFFLL) return FQL_ERR_BAD_SHAPE;
-    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    const int ib = e4m3_rows ? 1 : dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
     return FQL_OK;
+}
+
+// ---- the fp8-row path (fql_gemm_mx4_f8.h): c.rows is [T][K] e4m3 bytes
+int launch_mx4_f8(int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    using C = Mx4F8Cfg;                                      // (one more z-slice zeroes the rows no expert covers)
+    static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the bfloat16 kernel's row tile");
+    const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1);
+    auto go = [&](auto kern) {
+        return launch(kern, grid, dim3(C::THREADS), 0, st, c.blocks, c.scales, static_cast<const uint8_t *>(c.rows), c.act_scale,
+                      c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+    };
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return go(mx4_f8_kernel<FQL_DTYPE_F32>);
+    case FQL_DTYPE_F16: return go(mx4_f8_kernel<FQL_DTYPE_F16>);
+    default: return go(mx4_f8_kernel<FQL_DTYPE_BF16>);
+    }
+}
+
+size_t mx4_q8_bytes(int T, int K) { return round16((size_t)T * K); }      // the e4m3 rows; act_scale [T] lies behind them
+
+// Quantise c.rows (float rows [T][K], or gated: gate_up [T][2 K]) into the workspace, then the GEMM on the bytes.
+int mx4_q8_run(Mx4Call c, int in_dtype, int out_dtype, bool gated, int activation, float act_alpha, float act_limit,
+               void *workspace, size_t workspace_bytes, hipStream_t st)
+{
+    if (!workspace || !aligned16(workspace) || workspace_bytes < mx4_q8_bytes(c.T, c.K) + round16((size_t)c.T * 4))
+        return FQL_ERR_WORKSPACE;
+    uint8_t *q = static_cast<uint8_t *>(workspace);
+    float *as = reinterpret_cast<float *>(q + mx4_q8_bytes(c.T, c.K));
+    const dim3 grid((unsigned)((c.T + 3) / 4));
+    auto go = [&](auto kern) { return launch(kern, grid, dim3(256), 0, st, c.rows, q, as, c.T, c.K, activation, act_alpha, act_limit); };
+    const int lrc = in_dtype == FQL_DTYPE_F32 ? (gated ? go(mx4_q8_kernel<FQL_DTYPE_F32, true>) : go(mx4_q8_kernel<FQL_DTYPE_F32, false>))
+                                              : (gated ? go(mx4_q8_kernel<FQL_DTYPE_BF16, true>) : go(mx4_q8_kernel<FQL_DTYPE_BF16, false>));
+    if (lrc != FQL_OK) return lrc;
+    c.rows = q;
+    c.act_scale = as;
+    return launch_mx4_f8(out_dtype, c, st);
 }
 
 }  // namespace
@@ -154,6 +194,56 @@ FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e
     }
     return in_dtype == FQL_DTYPE_F32 ? launch_mx4_bwd_out<FQL_DTYPE_F32>(out_dtype, c, st)
                                      : launch_mx4_bwd_out<FQL_DTYPE_BF16>(out_dtype, c, st);
+}
+
+FQL_API size_t fql_moe_mx4_f8_workspace_bytes(int E, int T, int K, int N, int mode)
+{
+    (void)E; (void)N;
+    if ((mode != 1 && mode != 2) || T <= 0 || K <= 0) return 0;
+    return mx4_q8_bytes(T, K) + round16((size_t)T * 4);               // e4m3 rows [T][K], act_scale [T]
+}
+
+FQL_API int fql_moe_mx4_fwd_f8(const uint8_t *blocks, const uint8_t *scales_e8m0, const uint8_t *inputs_e4m3,
+                               const float *act_scale, const float *bias, const int32_t *tokens_per_expert,
+                               const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    Mx4Call c{blocks, scales_e8m0, inputs_e4m3, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    c.act_scale = act_scale;
+    bool empty;
+    const int rc = mx4_check(c, 0, out_dtype, K, true, &empty, true);
+    if (rc != FQL_OK || empty) return rc;
+    if (reinterpret_cast<uintptr_t>(act_scale) & 3) return FQL_ERR_ALIGNMENT;
+    return launch_mx4_f8(out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_fwd_q8(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                               int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const Mx4Call c{blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return mx4_q8_run(c, in_dtype, out_dtype, false, FQL_ACT_SILU, 0.0f, 0.0f, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_glu_fwd_q8(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                   float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    bool act_ok = activation == FQL_ACT_SILU || activation == FQL_ACT_GELU_TANH || activation == FQL_ACT_SWIGLU_CLAMP;
+    if (act_ok && activation != FQL_ACT_SILU)
+        act_ok = std::isfinite(act_alpha) && std::isfinite(act_limit) && act_limit > 0.0f;
+    const Mx4Call c{blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, act_ok, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return mx4_q8_run(c, in_dtype, out_dtype, true, activation, act_alpha, act_limit, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -511,14 +511,24 @@ class MXFP4MoEFFN(nn.Module):
     up weights, every tensor in the layer's activation type.  The gradient is straight-through across the forward's two
     bfloat16 roundings, of ``x`` and of ``h``: it is the gradient of the function without them, evaluated at the
     forward's values, and the backward rounds its own operands (``gy``, ``dgu``) once to bfloat16 in the same way.  The
-    keyword is configuration, not state: the state-dict keys do not change."""
+    keyword is configuration, not state: the state-dict keys do not change.
+
+    ``precision="fp8"`` (default ``"bf16"``) runs both GEMMs on the block-scaled FP4 matrix cores instead: the rows (``x``,
+    then the float32 ``h``) are quantised per row to OCP e4m3 by a fused pre-pass and contracted with the packed weights
+    and their E8M0 scales as they lie in the checkpoint (``ops.moe_forward_mxfp4(..., precision="fp8")``).  The mode is
+    inference only: it has no backward, so ``input_grad=True`` with it raises ``ValueError``.  Configuration as well: the
+    state-dict keys do not change."""
 
     group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, activation: str = "silu",
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
-                 activation_dtype=None, input_grad: bool = False):
+                 activation_dtype=None, input_grad: bool = False, precision: str = "bf16"):
         super().__init__()
+        if precision not in ("bf16", "fp8"):
+            raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
+        if precision == "fp8" and input_grad:
+            raise ValueError("precision='fp8' has no backward: it cannot be combined with input_grad=True")
         if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0:
             raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 (one scale per 32 inputs)")
         if activation_dtype not in (None, torch.float32, torch.bfloat16):
@@ -530,6 +540,7 @@ class MXFP4MoEFFN(nn.Module):
             activation, activation_alpha, activation_limit)
         self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
         self.input_grad = bool(input_grad)
+        self.precision = precision
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_blocks", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
         self.register_buffer("gate_up_scales", torch.full((E, 2 * F, H // 32), 127, dtype=torch.uint8))
@@ -548,7 +559,7 @@ class MXFP4MoEFFN(nn.Module):
         ``down_scales`` [E, H, F/32], all uint8; ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H] (both or none).
         ``interleaved=True``: rows 0, 2, 4, ... of ``gate_up`` are the gate and 1, 3, 5, ... the up projection (gpt-oss's
         order); they are de-interleaved once, the bias included.  ``kwargs``: the constructor's activation arguments,
-        ``activation_dtype`` and ``input_grad``."""
+        ``activation_dtype``, ``input_grad`` and ``precision``."""
         def flat(name, b, s):
             if b.dtype != torch.uint8 or s.dtype != torch.uint8:
                 raise ValueError(f"{name}_blocks and {name}_scales must be uint8")
@@ -620,10 +631,11 @@ class MXFP4MoEFFN(nn.Module):
         b_gu, b_d = self.biases
         b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
         gate_up = ops.moe_forward_mxfp4(self.gate_up_blocks, self.gate_up_scales, inputs.detach(), tokens_per_expert,
-                                        input_offsets, bias=b_gu, out_dtype=dt)
+                                        input_offsets, bias=b_gu, out_dtype=dt, precision=self.precision)
         return ops.moe_gated_forward_mxfp4(self.down_blocks, self.down_scales, gate_up, tokens_per_expert, input_offsets,
                                            activation=self.activation, activation_alpha=self.activation_alpha,
-                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt), gate_up
+                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt,
+                                           precision=self.precision), gate_up
 
     @property
     def biases(self):
@@ -643,7 +655,8 @@ class MXFP4MoEFFN(nn.Module):
     _activation_repr = QuantizedMoEFFN._activation_repr
 
     def extra_repr(self) -> str:
-        return ("format=mxfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else ""))
+        return ("format=mxfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else "")
+                + (", precision=fp8" if self.precision == "fp8" else ""))
 
 
 class QuantizedSparseMoEBlock(nn.Module):

@@ -542,7 +542,14 @@ def _check_mxfp4(blocks, scales, dev, K):
     return blocks.contiguous(), scales.contiguous(), E, N
 
 
-def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offsets, bias, out_dtype, gated, act=()):
+def _mxfp4_precision(precision):
+    """``precision`` of the MXFP4 ops: "bf16" (the default) or "fp8" -> True for fp8."""
+    if precision not in ("bf16", "fp8"):
+        raise ValueError(f"precision must be 'bf16' or 'fp8' for MXFP4 weights, got {precision!r}")
+    return precision == "fp8"
+
+
+def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offsets, bias, out_dtype, gated, act=(), fp8=False):
     if not rows.is_cuda or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
                            "it to bfloat16 would lose three bits; cast it yourself)")
@@ -554,35 +561,50 @@ def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offset
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
     bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
-    _launch("fql_moe_mx4_glu_fwd" if gated else "fql_moe_mx4_fwd", dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype],
-            bias, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
-            ws_bytes=_native.lib().fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated)))
+    L = _native.lib()
+    if fp8:         # the quantising pre-pass, then the block-scaled fp4 x fp8 GEMM (csrc/fql_gemm_mx4_f8.h)
+        entry, ws = ("fql_moe_mx4_glu_fwd_q8" if gated else "fql_moe_mx4_fwd_q8",
+                     L.fql_moe_mx4_f8_workspace_bytes(E, T, K, N, 2 if gated else 1))
+    else:
+        entry, ws = "fql_moe_mx4_glu_fwd" if gated else "fql_moe_mx4_fwd", L.fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated))
+    _launch(entry, dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype], bias, tpe, offs, out, _DTYPES[out_dtype],
+            E, T, K, N, *act, ws_bytes=ws)
     return out
 
 
-def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, bias=None, out_dtype=None):
+def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, bias=None, out_dtype=None, precision="bf16"):
     """The grouped GEMM on OCP MXFP4 expert weights: ``out[t] = W_e @ bf16(inputs[t]) (+ bias[e])`` over the rows of expert
     e.  ``blocks`` uint8 [E, N, K/2], ``scales`` uint8 [E, N, K/32] (``quantize.quantize_mxfp4``); ``inputs`` [T, K] float32
     (rounded once to bfloat16) or bfloat16; ``bias`` [E, N] float32 (optional), added before the one rounding to
     ``out_dtype`` (default: the inputs' type).  The weights are exact in bfloat16 and the contraction accumulates in
-    float32 on the bfloat16 matrix cores; rows no expert covers are zero.  Forward only."""
+    float32 on the bfloat16 matrix cores; rows no expert covers are zero.  Forward only.
+
+    ``precision="fp8"`` is the opt-in mode on the block-scaled FP4 matrix cores: the rows are quantised per row to OCP e4m3
+    (``quantize_activations_fp8``'s rule, inside a fused pre-pass) and contracted with the packed weights and their E8M0
+    scales as they are: ``out[t] = act_scale[t] * (W_e @ e4m3(inputs[t] / act_scale[t])) (+ bias[e])``."""
     _forward_only("moe_forward_mxfp4", inputs, bias)
+    fp8 = _mxfp4_precision(precision)
     K = inputs.shape[1] if inputs.dim() == 2 else 0
-    return _mxfp4_launch("moe_forward_mxfp4", blocks, scales, inputs, K, tokens_per_expert, input_offsets, bias, out_dtype, False)
+    return _mxfp4_launch("moe_forward_mxfp4", blocks, scales, inputs, K, tokens_per_expert, input_offsets, bias, out_dtype, False,
+                         fp8=fp8)
 
 
 def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_offsets, activation="silu",
-                            activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None):
+                            activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None, precision="bf16"):
     """The down projection of a gated FFN expert on MXFP4 weights: ``out[t] = W_e @ bf16(act(gate_up[t, :K], gate_up[t, K:]))
     (+ bias[e])``, ``gate_up`` [T, 2K] float32 or bfloat16, ``blocks`` [E, N, K/2].  The activation (``activation_of``) is
     evaluated in float32 and rounded once to bfloat16 by a streaming pre-pass into the op's workspace: no [T, K] tensor is
-    handed back.  Forward only."""
+    handed back.  Forward only.
+
+    ``precision="fp8"``: the float32 ``h = act(...)`` is quantised per row to e4m3 by the pre-pass instead (never stored as
+    floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``."""
     _forward_only("moe_gated_forward_mxfp4", gate_up, bias)
+    fp8 = _mxfp4_precision(precision)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     if gate_up.dim() != 2 or gate_up.shape[1] % 64 != 0:
         raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
     return _mxfp4_launch("moe_gated_forward_mxfp4", blocks, scales, gate_up, gate_up.shape[1] // 2, tokens_per_expert,
-                         input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit))
+                         input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit), fp8=fp8)
 
 
 ROUTE_MAX_EXPERTS = 128
@@ -1071,6 +1093,26 @@ def moe_forward_fp8(packed_weights, scales, zero_points, inputs_e4m3, act_scales
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     _launch("fql_moe_fwd_f8", dev, packed_weights, scales, zero_points, x8, act_scales, tpe, offs, out, _DTYPES[out_dtype],
             E, T, K, N, ws_bytes=_native.lib().fql_moe_workspace_bytes(E, T, K, N, _native.PRECISION_FP8))
+    return out
+
+
+def moe_forward_mxfp4_fp8(blocks, scales, inputs_e4m3, act_scales, tokens_per_expert, input_offsets, bias=None,
+                          out_dtype=torch.float32):
+    """The grouped GEMM on OCP MXFP4 expert weights over rows that are already fp8, on the block-scaled FP4 matrix cores:
+    ``out[t] = act_scales[t] * (W_e @ e4m3(inputs_e4m3[t])) (+ bias[e])``.  ``blocks`` / ``scales`` as ``moe_forward_mxfp4``
+    takes them; ``inputs_e4m3`` [T, K] torch.float8_e4m3fn (or its uint8 bytes), ``act_scales`` [T] float32 or None (= 1);
+    ``bias`` [E, N] float32 (optional).  Returns [T, N] in ``out_dtype``; rows no expert covers are zero.  Forward only
+    (INTEGRATION.md section 17)."""
+    _forward_only("moe_forward_mxfp4_fp8", inputs_e4m3, act_scales, bias)
+    x8, act_scales = _fp8_operands(inputs_e4m3, act_scales, "inputs_e4m3", out_dtype, "hidden_dim")
+    T, K = x8.shape
+    dev = x8.device
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    _launch("fql_moe_mx4_fwd_f8", dev, blocks, scales, x8, act_scales, bias, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N,
+            ws_bytes=_native.lib().fql_moe_mx4_f8_workspace_bytes(E, T, K, N, 0))
     return out
 
 

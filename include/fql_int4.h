@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 350 /* 0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 360 /* 0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -913,6 +913,54 @@ FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m
 FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *grad_out, int in_dtype,
                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
                                   int out_dtype, int E, int T, int K, int N, void *stream);
+
+/* ---- MXFP4 expert weights over fp8 rows, on the block-scaled FP4 matrix cores (FQL_VERSION 360; INTEGRATION.md section 17,
+ *      DESIGN.md section 27; csrc/fql_gemm_mx4_f8.h) ----
+ * The opt-in second mode of the MXFP4 forward; the bfloat16 entries above and their bits are unchanged.
+ *   out[t][n] = act_scale[t] * ( sum_k e4m3(x8[t][k]) * W_e[n][k] ) (+ bias[e][n]),   blocks / scales_e8m0 as above.
+ * The packed bytes and the E8M0 bytes go to v_mfma_scale_f32_32x32x64_f8f6f4 as they lie in memory (fp4 A operand with its
+ * block scale), the activation rows are OCP e4m3 bytes (0x7F / 0xFF: NaN) in the B operand with scale code 127; nothing is
+ * dequantised.  float32 accumulation inside the instruction, 128 k a stage in ascending k, two instructions of 64 k each,
+ * one accumulator per output: a row's result depends on its own bytes, its act_scale and its expert's weights only, so
+ * the grouped call equals E one-expert calls bit for bit, under any permutation of the table and run to run.  Epilogue in
+ * float32: act_scale[t] * acc (one multiplication; NULL: acc as it is), with a bias fma(act_scale[t], acc, bias[e][n])
+ * (one rounding), then the one rounding to out_dtype.  No atomics; every element of out [T][N] is written once, rows no
+ * expert covers as zeros by the same launch.  Any K % 32 == 0, any N >= 1.
+ * fql_moe_mx4_fwd_f8:     inputs_e4m3 [T][K] bytes, act_scale [T] float32 or NULL (= 1).  No workspace (mode 0: 0 bytes, the
+ *                         arguments may be NULL / 0).
+ * fql_moe_mx4_fwd_q8:     inputs [T][K] float32 or bfloat16 (widened), quantised per row by a streaming pre-pass into the
+ *                         workspace (mode 1): scale = max|x| / 448 in float32 (1 for an all-zero row), byte = e4m3(x / scale)
+ *                         with a float32 division, to nearest even; then the call above on those bytes and scales.
+ * fql_moe_mx4_glu_fwd_q8: the same on h[t][k] = act(gate_up[t][k], gate_up[t][K + k]) evaluated in float32 (act_glu_mul, the
+ *                         kinds of FQL_ACT_*) from gate_up [T][2K] float32 or bfloat16 (mode 2); h itself is never stored.
+ *   Non-finite values: an e4m3 NaN byte or a NaN act_scale makes exactly that output row NaN; a float row (or h) with a
+ *   non-finite element gets a NaN scale, hence a NaN output row; a scale code 255 makes exactly the outputs of its weight row
+ *   NaN, for the rows of its expert.  Scale codes 0 and 254 are 2^-127 and 2^127 as the instruction applies them (measured:
+ *   1.0 * 2^-127 comes back as the float32 subnormal 0x00400000, nothing is flushed inside the instruction; sums past the
+ *   float32 range are infinite).
+ *   float16 rows are refused (FQL_ERR_DTYPE) as in fql_moe_mx4_fwd.
+ *   Workspace: fql_moe_mx4_f8_workspace_bytes(E, T, K, N, mode), mode 0 (rows already e4m3): 0; mode 1 (float rows) and 2
+ *   (gated): the e4m3 rows [T][K] and act_scale [T], each rounded up to 16 bytes; 16-byte aligned.
+ *   Return codes, in this order and all before any HIP call (fql_moe_mx4_fwd's): FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0,
+ *   N < 0; glu: an unknown activation, or for a kind other than silu a non-finite act_alpha / act_limit or act_limit <= 0);
+ *   FQL_ERR_ODD_K; FQL_ERR_BAD_SHAPE (K % 32 != 0); FQL_ERR_DTYPE (q8: in_dtype not FQL_DTYPE_F32 / _BF16; all: out_dtype
+ *   outside FQL_DTYPE_*); T == 0 or N == 0: FQL_OK with nothing launched; FQL_ERR_NULL_POINTER (blocks, scales_e8m0, the rows,
+ *   out; one of the table's two arrays alone); FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65534, T > 4194240);
+ *   FQL_ERR_ALIGNMENT (blocks not 16-byte aligned; float rows / out not aligned to their element, bias and act_scale not to
+ *   4 bytes; the e4m3 rows need none, 16-byte aligned ones take the wide loads); FQL_ERR_WORKSPACE (q8: NULL, misaligned or
+ *   short); FQL_ERR_LAUNCH. */
+FQL_API size_t fql_moe_mx4_f8_workspace_bytes(int E, int T, int K, int N, int mode);
+FQL_API int fql_moe_mx4_fwd_f8(const uint8_t *blocks, const uint8_t *scales_e8m0, const uint8_t *inputs_e4m3,
+                               const float *act_scale, const float *bias, const int32_t *tokens_per_expert,
+                               const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                               void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_fwd_q8(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                               int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_glu_fwd_q8(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                   float act_limit, void *workspace, size_t workspace_bytes, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
