@@ -1,12 +1,14 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
-// fql_moe_mx4_bwd_input, and the fp8-row entries fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8) over the kernels of
-// fql_gemm_mx4.h, fql_gemm_mx4_bwd.h and fql_gemm_mx4_f8.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_moe_mx4_bwd_input, the fp8-row entries fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 and the MXFP4-row entries
+// fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 / fql_mx4_quantize_rows) over the kernels of fql_gemm_mx4.h,
+// fql_gemm_mx4_bwd.h, fql_gemm_mx4_f8.h and fql_gemm_mx4_f4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "fql_common.h"
 #include "fql_host.h"
 #include "fql_gemm_mx4.h"
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_mx4_f8.h"
+#include "fql_gemm_mx4_f4.h"
 
 #include <cmath>
 
@@ -22,7 +24,10 @@ struct Mx4Call {
     void *out;
     int E, T, K, N;
     const float *act_scale = nullptr;  // [T] or NULL (the fp8-row kernel only)
+    const uint8_t *row_scales = nullptr;  // [T][K / 32] E8M0 (the MXFP4-row kernel only)
 };
+
+enum { ROWS_FLOAT = 0, ROWS_E4M3 = 1, ROWS_MXFP4 = 2 };   // what c.rows holds
 
 template <int IN, int OUT>
 int launch_mx4(const Mx4Call &c, hipStream_t st)
@@ -70,9 +75,11 @@ int launch_mx4_bwd_out(int out_dtype, const Mx4Call &c, hipStream_t st)
 size_t mx4_h_bytes(int T, int K) { return round16((size_t)T * K * 2); }
 
 // The checks both entry points share, in the documented order; `rows` is inputs or gate_up.  FQL_OK with *empty set: an
-// empty call, nothing to launch.  e4m3_rows: the rows are bytes (in_dtype is not looked at).
-int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool act_ok, bool *empty, bool e4m3_rows = false)
+// empty call, nothing to launch.  rows_kind other than ROWS_FLOAT: the rows are bytes (in_dtype is not looked at); ROWS_MXFP4:
+// packed rows [T][K / 2], 16-byte aligned, with c.row_scales.
+int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool act_ok, bool *empty, int rows_kind = ROWS_FLOAT)
 {
+    const bool e4m3_rows = rows_kind != ROWS_FLOAT;
     *empty = false;
     if (c.E <= 0 || c.T < 0 || c.K <= 0 || c.N < 0 || !act_ok) return FQL_ERR_BAD_SHAPE;
     if (c.K & 1) return FQL_ERR_ODD_K;
@@ -80,6 +87,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool a
     if ((!e4m3_rows && in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
     if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
+    if (rows_kind == ROWS_MXFP4 && !c.row_scales) return FQL_ERR_NULL_POINTER;
     if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
     if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
     if (c.E > 65534) return FQL_ERR_BAD_SHAPE;                        // (the grid's z: the experts and the coverage slice)
@@ -88,6 +96,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool a
     const int ib = e4m3_rows ? 1 : dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
+    if (rows_kind == ROWS_MXFP4 && !aligned16(c.rows)) return FQL_ERR_ALIGNMENT;
     return FQL_OK;
 }
 
@@ -126,6 +135,57 @@ int mx4_q8_run(Mx4Call c, int in_dtype, int out_dtype, bool gated, int activatio
     c.rows = q;
     c.act_scale = as;
     return launch_mx4_f8(out_dtype, c, st);
+}
+
+// ---- the MXFP4-row path (fql_gemm_mx4_f4.h): c.rows is [T][K / 2] packed e2m1, c.row_scales [T][K / 32] E8M0
+int launch_mx4_f4(int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    using C = Mx4F4Cfg;                                      // (one more z-slice zeroes the rows no expert covers)
+    static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the bfloat16 kernel's row tile");
+    const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1);
+    auto go = [&](auto kern) {
+        return launch(kern, grid, dim3(C::THREADS), 0, st, c.blocks, c.scales, static_cast<const uint8_t *>(c.rows), c.row_scales,
+                      c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+    };
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return go(mx4_f4_kernel<FQL_DTYPE_F32>);
+    case FQL_DTYPE_F16: return go(mx4_f4_kernel<FQL_DTYPE_F16>);
+    default: return go(mx4_f4_kernel<FQL_DTYPE_BF16>);
+    }
+}
+
+size_t mx4_q4_bytes(int T, int K) { return round16((size_t)T * (K / 2)); }   // the packed rows; their scale bytes lie behind them
+
+bool mx4_act_ok(int activation, float act_alpha, float act_limit)
+{
+    bool act_ok = activation == FQL_ACT_SILU || activation == FQL_ACT_GELU_TANH || activation == FQL_ACT_SWIGLU_CLAMP;
+    if (act_ok && activation != FQL_ACT_SILU)
+        act_ok = std::isfinite(act_alpha) && std::isfinite(act_limit) && act_limit > 0.0f;
+    return act_ok;
+}
+
+// rows (float rows [T][K], or gated: gate_up [T][2 K]) -> qb [T][K / 2], qs [T][K / 32] (mx4_q4_kernel)
+int launch_mx4_q4(const void *rows, int in_dtype, bool gated, int activation, float act_alpha, float act_limit, uint8_t *qb,
+                  uint8_t *qs, int T, int K, hipStream_t st)
+{
+    const dim3 grid((unsigned)(((long long)T * (K / 8) + 255) / 256));
+    auto go = [&](auto kern) { return launch(kern, grid, dim3(256), 0, st, rows, qb, qs, T, K, activation, act_alpha, act_limit); };
+    return in_dtype == FQL_DTYPE_F32 ? (gated ? go(mx4_q4_kernel<FQL_DTYPE_F32, true>) : go(mx4_q4_kernel<FQL_DTYPE_F32, false>))
+                                     : (gated ? go(mx4_q4_kernel<FQL_DTYPE_BF16, true>) : go(mx4_q4_kernel<FQL_DTYPE_BF16, false>));
+}
+
+// Quantise c.rows into the workspace, then the GEMM on the packed rows.
+int mx4_q4_run(Mx4Call c, int in_dtype, int out_dtype, bool gated, int activation, float act_alpha, float act_limit,
+               void *workspace, size_t workspace_bytes, hipStream_t st)
+{
+    if (!workspace || !aligned16(workspace) || workspace_bytes < mx4_q4_bytes(c.T, c.K) + round16((size_t)c.T * (c.K / 32)))
+        return FQL_ERR_WORKSPACE;
+    uint8_t *qb = static_cast<uint8_t *>(workspace), *qs = qb + mx4_q4_bytes(c.T, c.K);
+    const int lrc = launch_mx4_q4(c.rows, in_dtype, gated, activation, act_alpha, act_limit, qb, qs, c.T, c.K, st);
+    if (lrc != FQL_OK) return lrc;
+    c.rows = qb;
+    c.row_scales = qs;
+    return launch_mx4_f4(out_dtype, c, st);
 }
 
 }  // namespace
@@ -212,7 +272,7 @@ FQL_API int fql_moe_mx4_fwd_f8(const uint8_t *blocks, const uint8_t *scales_e8m0
     Mx4Call c{blocks, scales_e8m0, inputs_e4m3, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
     c.act_scale = act_scale;
     bool empty;
-    const int rc = mx4_check(c, 0, out_dtype, K, true, &empty, true);
+    const int rc = mx4_check(c, 0, out_dtype, K, true, &empty, ROWS_E4M3);
     if (rc != FQL_OK || empty) return rc;
     if (reinterpret_cast<uintptr_t>(act_scale) & 3) return FQL_ERR_ALIGNMENT;
     return launch_mx4_f8(out_dtype, c, static_cast<hipStream_t>(stream));
@@ -244,6 +304,65 @@ FQL_API int fql_moe_mx4_glu_fwd_q8(const uint8_t *blocks, const uint8_t *scales_
     if (rc != FQL_OK || empty) return rc;
     return mx4_q8_run(c, in_dtype, out_dtype, true, activation, act_alpha, act_limit, workspace, workspace_bytes,
                       static_cast<hipStream_t>(stream));
+}
+
+FQL_API size_t fql_moe_mx4_f4_workspace_bytes(int E, int T, int K, int N, int mode)
+{
+    (void)E; (void)N;
+    if ((mode != 1 && mode != 2) || T <= 0 || K <= 0) return 0;
+    return mx4_q4_bytes(T, K) + round16((size_t)T * (K / 32));        // packed rows [T][K / 2], their scales [T][K / 32]
+}
+
+FQL_API int fql_moe_mx4_fwd_f4(const uint8_t *blocks, const uint8_t *scales_e8m0, const uint8_t *in_blocks,
+                               const uint8_t *in_scales_e8m0, const float *bias, const int32_t *tokens_per_expert,
+                               const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    Mx4Call c{blocks, scales_e8m0, in_blocks, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    c.row_scales = in_scales_e8m0;
+    bool empty;
+    const int rc = mx4_check(c, 0, out_dtype, K, true, &empty, ROWS_MXFP4);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_mx4_f4(out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_fwd_q4(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                               int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const Mx4Call c{blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return mx4_q4_run(c, in_dtype, out_dtype, false, FQL_ACT_SILU, 0.0f, 0.0f, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_glu_fwd_q4(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                   float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const Mx4Call c{blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, K, mx4_act_ok(activation, act_alpha, act_limit), &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return mx4_q4_run(c, in_dtype, out_dtype, true, activation, act_alpha, act_limit, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_mx4_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
+                                  uint8_t *out_blocks, uint8_t *out_scales, int T, int K, void *stream)
+{
+    // mx4_check on a call record with one expert, one column and no table: out_blocks stands for both `blocks` (non-NULL,
+    // 16-byte aligned) and `out`, out_scales for `scales`; the documented order is fql_moe_mx4_fwd's.
+    const Mx4Call c{out_blocks, out_scales, rows, nullptr, nullptr, nullptr, out_blocks, 1, T, K, 1};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, FQL_DTYPE_F32, K, !gated || mx4_act_ok(activation, act_alpha, act_limit), &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_mx4_q4(rows, in_dtype, gated != 0, activation, act_alpha, act_limit, out_blocks, out_scales, T, K,
+                         static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -517,7 +517,11 @@ class MXFP4MoEFFN(nn.Module):
     then the float32 ``h``) are quantised per row to OCP e4m3 by a fused pre-pass and contracted with the packed weights
     and their E8M0 scales as they lie in the checkpoint (``ops.moe_forward_mxfp4(..., precision="fp8")``).  The mode is
     inference only: it has no backward, so ``input_grad=True`` with it raises ``ValueError``.  Configuration as well: the
-    state-dict keys do not change."""
+    state-dict keys do not change.
+
+    ``precision="fp4"`` (W4A4) quantises the rows to MXFP4 as well, per block of 32 by ``quantize.quantize_mxfp4``'s rule
+    (``ops.quantize_rows_mxfp4``), and contracts e2m1 with e2m1: half the activation traffic of the fp8 mode again, at the
+    format's price (about 1.1e-1 relative on the rows against 3e-2 for e4m3).  Inference only and configuration, as fp8."""
 
     group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
 
@@ -525,10 +529,10 @@ class MXFP4MoEFFN(nn.Module):
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
                  activation_dtype=None, input_grad: bool = False, precision: str = "bf16"):
         super().__init__()
-        if precision not in ("bf16", "fp8"):
-            raise ValueError(f"precision must be 'bf16' or 'fp8', got {precision!r}")
-        if precision == "fp8" and input_grad:
-            raise ValueError("precision='fp8' has no backward: it cannot be combined with input_grad=True")
+        if precision not in ("bf16", "fp8", "fp4"):
+            raise ValueError(f"precision must be 'bf16', 'fp8' or 'fp4', got {precision!r}")
+        if precision != "bf16" and input_grad:
+            raise ValueError(f"precision='{precision}' has no backward: it cannot be combined with input_grad=True")
         if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0:
             raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 (one scale per 32 inputs)")
         if activation_dtype not in (None, torch.float32, torch.bfloat16):
@@ -656,7 +660,7 @@ class MXFP4MoEFFN(nn.Module):
 
     def extra_repr(self) -> str:
         return ("format=mxfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else "")
-                + (", precision=fp8" if self.precision == "fp8" else ""))
+                + (f", precision={self.precision}" if self.precision != "bf16" else ""))
 
 
 class QuantizedSparseMoEBlock(nn.Module):

@@ -543,13 +543,14 @@ def _check_mxfp4(blocks, scales, dev, K):
 
 
 def _mxfp4_precision(precision):
-    """``precision`` of the MXFP4 ops: "bf16" (the default) or "fp8" -> True for fp8."""
-    if precision not in ("bf16", "fp8"):
-        raise ValueError(f"precision must be 'bf16' or 'fp8' for MXFP4 weights, got {precision!r}")
-    return precision == "fp8"
+    """``precision`` of the MXFP4 ops, validated: "bf16" (the default), "fp8" or "fp4"."""
+    if precision not in ("bf16", "fp8", "fp4"):
+        raise ValueError(f"precision must be 'bf16', 'fp8' or 'fp4' for MXFP4 weights, got {precision!r}")
+    return precision
 
 
-def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offsets, bias, out_dtype, gated, act=(), fp8=False):
+def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offsets, bias, out_dtype, gated, act=(),
+                  precision="bf16"):
     if not rows.is_cuda or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
                            "it to bfloat16 would lose three bits; cast it yourself)")
@@ -562,9 +563,12 @@ def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offset
     bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     L = _native.lib()
-    if fp8:         # the quantising pre-pass, then the block-scaled fp4 x fp8 GEMM (csrc/fql_gemm_mx4_f8.h)
+    if precision == "fp8":      # the quantising pre-pass, then the block-scaled fp4 x fp8 GEMM (csrc/fql_gemm_mx4_f8.h)
         entry, ws = ("fql_moe_mx4_glu_fwd_q8" if gated else "fql_moe_mx4_fwd_q8",
                      L.fql_moe_mx4_f8_workspace_bytes(E, T, K, N, 2 if gated else 1))
+    elif precision == "fp4":    # the MXFP4 quantiser, then the block-scaled fp4 x fp4 GEMM (csrc/fql_gemm_mx4_f4.h)
+        entry, ws = ("fql_moe_mx4_glu_fwd_q4" if gated else "fql_moe_mx4_fwd_q4",
+                     L.fql_moe_mx4_f4_workspace_bytes(E, T, K, N, 2 if gated else 1))
     else:
         entry, ws = "fql_moe_mx4_glu_fwd" if gated else "fql_moe_mx4_fwd", L.fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated))
     _launch(entry, dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype], bias, tpe, offs, out, _DTYPES[out_dtype],
@@ -581,12 +585,16 @@ def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, 
 
     ``precision="fp8"`` is the opt-in mode on the block-scaled FP4 matrix cores: the rows are quantised per row to OCP e4m3
     (``quantize_activations_fp8``'s rule, inside a fused pre-pass) and contracted with the packed weights and their E8M0
-    scales as they are: ``out[t] = act_scale[t] * (W_e @ e4m3(inputs[t] / act_scale[t])) (+ bias[e])``."""
+    scales as they are: ``out[t] = act_scale[t] * (W_e @ e4m3(inputs[t] / act_scale[t])) (+ bias[e])``.
+
+    ``precision="fp4"`` (W4A4) quantises the rows to MXFP4 themselves, per block of 32 by ``quantize.quantize_mxfp4``'s rule
+    (``quantize_rows_mxfp4``, inside a fused pre-pass), and contracts e2m1 with e2m1, each side with its E8M0 scales:
+    ``out[t] = W_e @ mxfp4(inputs[t]) (+ bias[e])``.  The format error of the rows is about 1.1e-1 (relative Frobenius)."""
     _forward_only("moe_forward_mxfp4", inputs, bias)
-    fp8 = _mxfp4_precision(precision)
+    precision = _mxfp4_precision(precision)
     K = inputs.shape[1] if inputs.dim() == 2 else 0
     return _mxfp4_launch("moe_forward_mxfp4", blocks, scales, inputs, K, tokens_per_expert, input_offsets, bias, out_dtype, False,
-                         fp8=fp8)
+                         precision=precision)
 
 
 def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_offsets, activation="silu",
@@ -597,14 +605,16 @@ def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_of
     handed back.  Forward only.
 
     ``precision="fp8"``: the float32 ``h = act(...)`` is quantised per row to e4m3 by the pre-pass instead (never stored as
-    floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``."""
+    floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``.  ``precision="fp4"``: ``h`` is
+    evaluated once in float32 and quantised to MXFP4 per block of 32 (``quantize_rows_mxfp4(gate_up, activation=...)``)."""
     _forward_only("moe_gated_forward_mxfp4", gate_up, bias)
-    fp8 = _mxfp4_precision(precision)
+    precision = _mxfp4_precision(precision)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     if gate_up.dim() != 2 or gate_up.shape[1] % 64 != 0:
         raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0")
     return _mxfp4_launch("moe_gated_forward_mxfp4", blocks, scales, gate_up, gate_up.shape[1] // 2, tokens_per_expert,
-                         input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit), fp8=fp8)
+                         input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit),
+                         precision=precision)
 
 
 ROUTE_MAX_EXPERTS = 128
@@ -1113,6 +1123,57 @@ def moe_forward_mxfp4_fp8(blocks, scales, inputs_e4m3, act_scales, tokens_per_ex
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     _launch("fql_moe_mx4_fwd_f8", dev, blocks, scales, x8, act_scales, bias, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N,
             ws_bytes=_native.lib().fql_moe_mx4_f8_workspace_bytes(E, T, K, N, 0))
+    return out
+
+
+def quantize_rows_mxfp4(rows, activation=None, activation_alpha=1.702, activation_limit=7.0):
+    """Rows to MXFP4 on the GPU, the quantiser of ``precision="fp4"`` on its own: ``rows`` [T, K] float32 or bfloat16 (CUDA,
+    K % 32 == 0) -> ``(blocks uint8 [T, K/2], scales uint8 [T, K/32])``, bit for bit ``quantize.quantize_mxfp4`` for every
+    finite input.  A block that holds an inf or a NaN gets zero codes and scale code 255 (a NaN output row of the GEMM).
+    With ``activation`` given, ``rows`` is ``gate_up`` [T, 2K] and what is quantised is ``h = act(gate_up[:, :K],
+    gate_up[:, K:])`` (``activation_of``), evaluated once in float32.  Forward only."""
+    _forward_only("quantize_rows_mxfp4", rows)
+    gated = activation is not None
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit) if gated else ("silu", 0.0, 0.0)
+    if not rows.is_cuda or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("ops.quantize_rows_mxfp4: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: "
+                           "cast it yourself)")
+    T, width = rows.shape
+    if width % (64 if gated else 32) != 0 or width == 0:
+        raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0" if gated else "rows must be [T, K] with K % 32 == 0")
+    K = width // 2 if gated else width
+    dev = rows.device
+    blocks = torch.empty((T, K // 2), dtype=torch.uint8, device=dev)
+    scales = torch.empty((T, K // 32), dtype=torch.uint8, device=dev)
+    _launch("fql_mx4_quantize_rows", dev, rows.contiguous(), _DTYPES[rows.dtype], int(gated), _ACTIVATIONS[kind], act_alpha,
+            act_limit, blocks, scales, T, K)
+    return blocks, scales
+
+
+def moe_forward_mxfp4_fp4(blocks, scales, in_blocks, in_scales, tokens_per_expert, input_offsets, bias=None,
+                          out_dtype=torch.float32):
+    """The grouped GEMM on OCP MXFP4 expert weights over rows that are already MXFP4 (W4A4), both operands e2m1 with their
+    E8M0 block scales on the block-scaled FP4 matrix cores: ``out[t] = W_e @ X[t] (+ bias[e])``.  ``blocks`` / ``scales`` as
+    ``moe_forward_mxfp4`` takes them; ``in_blocks`` uint8 [T, K/2] and ``in_scales`` uint8 [T, K/32] in the same layout
+    (``quantize_rows_mxfp4`` or ``quantize.quantize_mxfp4``); ``bias`` [E, N] float32 (optional).  Returns [T, N] in
+    ``out_dtype``; rows no expert covers are zero; an ``in_scales`` byte of 255 makes its row NaN.  Forward only
+    (INTEGRATION.md section 17)."""
+    _forward_only("moe_forward_mxfp4_fp4", bias)
+    for name, t in (("in_blocks", in_blocks), ("in_scales", in_scales)):
+        if not t.is_cuda or t.dim() != 2 or t.dtype != torch.uint8:
+            raise RuntimeError(f"ops.moe_forward_mxfp4_fp4: {name} must be a CUDA uint8 2-D tensor")
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    T, K = in_blocks.shape[0], in_blocks.shape[1] * 2
+    dev = in_blocks.device
+    if K % 32 != 0 or in_scales.device != dev or tuple(in_scales.shape) != (T, K // 32):
+        raise RuntimeError("in_blocks must be [T, K/2] and in_scales [T, K/32] with K % 32 == 0, on one device")
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    _launch("fql_moe_mx4_fwd_f4", dev, blocks, scales, in_blocks.contiguous(), in_scales.contiguous(), bias, tpe, offs, out,
+            _DTYPES[out_dtype], E, T, K, N, ws_bytes=_native.lib().fql_moe_mx4_f4_workspace_bytes(E, T, K, N, 0))
     return out
 
 
