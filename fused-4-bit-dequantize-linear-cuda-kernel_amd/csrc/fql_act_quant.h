@@ -94,13 +94,14 @@ __device__ __forceinline__ float act_widen(unsigned short h)
 
 // ---- pieces shared by the pre-pass kernels (this file and fql_act_f8.h)
 // Coverage workgroups (MoE entry points only): zero-fill the rows of `out` no expert covers, 256 rows each
-// (reference semantics: torch::zeros, csrc/moe_int4_kernel.cu:109).
+// (reference semantics: torch::zeros, csrc/moe_int4_kernel.cu:109).  ROWS: the threads of the workgroup, one row each.
+template <int ROWS = 256>
 __device__ __forceinline__ void act_zero_uncovered(int block, void *__restrict__ out, int out_es, int N,
                                                    const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs,
                                                    int E, int T)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    const int t = block * 256 + tid;
+    const int t = block * ROWS + tid;
     bool covered = false;
     int cp = 0, ct = 0;
     for (int base = 0; base < E; base += 64) {

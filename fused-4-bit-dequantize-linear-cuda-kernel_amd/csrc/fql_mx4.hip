@@ -1,11 +1,13 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
 // fql_moe_mx4_bwd_input, the fp8-row entries fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 and the MXFP4-row entries
 // fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 / fql_mx4_quantize_rows) over the kernels of fql_gemm_mx4.h,
-// fql_gemm_mx4_bwd.h, fql_gemm_mx4_f8.h and fql_gemm_mx4_f4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h, fql_gemm_mx4_f8.h and fql_gemm_mx4_f4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
+#include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
 #include "fql_host.h"
 #include "fql_gemm_mx4.h"
+#include "fql_gemm_mx4_decode.h"
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_mx4_f8.h"
 #include "fql_gemm_mx4_f4.h"
@@ -29,11 +31,27 @@ struct Mx4Call {
 
 enum { ROWS_FLOAT = 0, ROWS_E4M3 = 1, ROWS_MXFP4 = 2 };   // what c.rows holds
 
+// The bfloat16 forward has two kernels that return the same bits (fql_gemm_mx4_decode.h): the 64 x 128 tile and, for few
+// rows, the one-wave decode kernel.  The per-expert counts stay on the device, so T alone decides.
+#define FQL_MX4_DECODE_MAX_ROWS 512    /* rows (T) up to which the decode kernel runs: the largest count of the sweep at which it wins */
+int g_mx4_decode_max_rows = FQL_MX4_DECODE_MAX_ROWS;
+
+bool mx4_use_decode(int T)
+{
+    return T > 0 && T <= g_mx4_decode_max_rows && (T + Mx4DecodeCfg::BT - 1) / Mx4DecodeCfg::BT <= 65535;
+}
+
 template <int IN, int OUT>
 int launch_mx4(const Mx4Call &c, hipStream_t st)
 {
-    using C = Mx4Cfg;                                        // (one more z-slice zeroes the rows no expert covers)
-    return launch(mx4_kernel<IN, OUT>, dim3((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1),
+    const unsigned z = c.tpe != nullptr ? c.E + 1 : 1;       // (one more z-slice zeroes the rows no expert covers)
+    if (mx4_use_decode(c.T)) {
+        using D = Mx4DecodeCfg;
+        return launch(mx4_decode_kernel<IN, OUT>, dim3((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, z), dim3(D::THREADS), 0,
+                      st, c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+    }
+    using C = Mx4Cfg;
+    return launch(mx4_kernel<IN, OUT>, dim3((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, z),
                   dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
 }
 
@@ -363,6 +381,19 @@ FQL_API int fql_mx4_quantize_rows(const void *rows, int in_dtype, int gated, int
     if (rc != FQL_OK || empty) return rc;
     return launch_mx4_q4(rows, in_dtype, gated != 0, activation, act_alpha, act_limit, out_blocks, out_scales, T, K,
                          static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_tune_set_mx4_decode_max_rows(int rows)
+{
+    const int old = g_mx4_decode_max_rows;
+    if (rows >= 0) g_mx4_decode_max_rows = rows;
+    return old;
+}
+
+FQL_API int fql_tune_mx4_kernel(int E, int T, int K, int N)
+{
+    (void)E; (void)K; (void)N;
+    return mx4_use_decode(T) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -501,7 +501,8 @@ class MXFP4MoEFFN(nn.Module):
     Both GEMMs are ``ops.moe_forward_mxfp4`` / ``ops.moe_gated_forward_mxfp4``: the weights are exact in bfloat16, the
     activations are rounded once to bfloat16 (float32 inputs) or read as they are (bfloat16), the sums are float32.
     ``activation_dtype=torch.bfloat16`` takes bfloat16 inputs, keeps ``gate_up`` in bfloat16 and returns bfloat16; the
-    default takes float32 and keeps ``gate_up`` in float32.
+    default takes float32 and keeps ``gate_up`` in float32.  A small batch (few routed rows: decode) takes the library's
+    decode kernel for both GEMMs instead of the 64-row tile; it returns the same bits, so nothing else changes.
 
     ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
     ``RuntimeError``, and ``QuantizedSparseMoEBlock(experts=MXFP4MoEFFN(...))`` works under ``torch.no_grad()``.

@@ -582,6 +582,8 @@ def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, 
     (rounded once to bfloat16) or bfloat16; ``bias`` [E, N] float32 (optional), added before the one rounding to
     ``out_dtype`` (default: the inputs' type).  The weights are exact in bfloat16 and the contraction accumulates in
     float32 on the bfloat16 matrix cores; rows no expert covers are zero.  Forward only.
+    Small batches (T up to the library's decode threshold) take a decode kernel that streams the weights once with one
+    wave per 32 weight rows instead of the 64-row tile; the two return the same bits, so the result does not depend on T.
 
     ``precision="fp8"`` is the opt-in mode on the block-scaled FP4 matrix cores: the rows are quantised per row to OCP e4m3
     (``quantize_activations_fp8``'s rule, inside a fused pre-pass) and contracted with the packed weights and their E8M0
@@ -602,7 +604,8 @@ def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_of
     """The down projection of a gated FFN expert on MXFP4 weights: ``out[t] = W_e @ bf16(act(gate_up[t, :K], gate_up[t, K:]))
     (+ bias[e])``, ``gate_up`` [T, 2K] float32 or bfloat16, ``blocks`` [E, N, K/2].  The activation (``activation_of``) is
     evaluated in float32 and rounded once to bfloat16 by a streaming pre-pass into the op's workspace: no [T, K] tensor is
-    handed back.  Forward only.
+    handed back.  Forward only.  Behind the pre-pass, small batches take the decode kernel of
+    ``moe_forward_mxfp4`` with the same bits as the tile kernel.
 
     ``precision="fp8"``: the float32 ``h = act(...)`` is quantised per row to e4m3 by the pre-pass instead (never stored as
     floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``.  ``precision="fp4"``: ``h`` is

@@ -52,6 +52,10 @@ FQL_API int fql_tune_set_act_single_rows(int rows);      /* pre-pass: one row pe
 FQL_API int fql_tune_set_group_mfma(int on);             /* per-group scales: float32 matrix-core kernel for batches */
 FQL_API int fql_tune_set_group_i8(int on);               /* per-group scales: INT8 matrix-core kernel where eligible */
 FQL_API int fql_tune_set_group_i8_min_rows(int rows);    /* ... from this many rows per group on */
+FQL_API int fql_tune_set_mx4_decode_max_rows(int rows);  /* MXFP4 bfloat16 forward: rows (T) up to which the decode kernel runs; 0: always the tile kernel, INT_MAX: the decode kernel wherever its grid allows, a negative value changes nothing (same bits either way: fql_int4.h, FQL_VERSION 380) */
+
+/* 0: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
+FQL_API int fql_tune_mx4_kernel(int E, int T, int K, int N);
 
 #ifdef __cplusplus
 }
