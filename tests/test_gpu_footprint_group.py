@@ -4,7 +4,9 @@ on fql_moe_group_fwd, fql_moe_group_glu_fwd and fql_moe_group_bwd_input, through
 Every pointer of a call is the interior of a helpers.Guarded buffer: the output between SENT (and SENT inside before the
 call), rows / gradient, scales, zps and bias between NaN, the expert table between BIG (a slot past the table that is used
 sends a kernel far away), the packed weights between 0xFF, the workspace at exactly fql_moe_group_typed_workspace_bytes(),
-16 bytes past a 256-byte boundary, between 0x5A (the backward's query is 0: it gets NULL).  Every case asserts that all
+16 bytes past a 256-byte boundary, between 0x5A (the backward's query is 0: it gets NULL).  The forward entries run once per
+stale workspace content (PREFILLS: 0x00, 0xFF -- a NaN in every format the workspace holds -- and 0x7F) and must return the
+same bits each time: a replayed graph finds there what the previous launch left.  Every case asserts that all
 guards are intact, that the rows no expert covers are zero (they held SENT), and that the result is bit for bit what the
 public op returns on plain tensors.  The problems are those of tests/test_gpu_group_moe_ops.py and test_gpu_group_bwd.py:
 the integer path (rows [40, 0, 9] + 2, K = 512, N = 136 and 70), the float32 kernels with both staging kernels (rows
@@ -20,6 +22,7 @@ pytestmark = pytest.mark.gpu
 DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 ACT = {"silu": 0, "gelu_tanh": 1, "swiglu_clamp": 2}
 ALPHA, LIMIT = 1.702, 7.0
+PREFILLS = (0x00, 0xFF, 0x7F)                            # (tests/test_gpu_footprint.py; 0xFF: NaN in every format)
 TYPES = [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.float16, torch.float32)]
 TYPE_IDS = ["f32-f32", "bf16-bf16", "f16-f32"]
 
@@ -73,19 +76,28 @@ def test_forward_entries_stay_inside_their_buffers(lib, path, N, group, kind, di
     assert nbytes > 0
     ws = Guarded("workspace", nbytes, torch.uint8, 0x5A, offset=16)
     if kind is None:
-        rc = lib.fql_moe_group_fwd(pk.ptr, sc.ptr, zp.ptr, rw.ptr, DT[din], cnt.ptr, off.ptr, bias.ptr, out.ptr, DT[dout], E, T,
-                                   K, N, group, 0, ws.ptr, nbytes, stream())
         want = ops().moe_forward_any(p["P"], p["S"], p["Z"], rows, None, p["tpe"], p["offs"], out_dtype=dout, bias=p["bias"])
     else:
-        rc = lib.fql_moe_group_glu_fwd(pk.ptr, sc.ptr, zp.ptr, rw.ptr, DT[din], cnt.ptr, off.ptr, bias.ptr, out.ptr, DT[dout],
-                                       E, T, K, N, group, 0, ACT[kind], ALPHA, LIMIT, ws.ptr, nbytes, stream())
         want = ops().moe_gated_forward(p["P"], p["S"], p["Z"], rows, p["tpe"], p["offs"], out_dtype=dout, bias=p["bias"],
                                        activation=kind, activation_alpha=ALPHA, activation_limit=LIMIT)
-    assert rc == 0
-    assert_guards_intact(pk, sc, zp, rw, cnt, off, bias, out, ws, what=f"group fwd {kind} N={N} group={group}")
     got = out.view(dout, T, N)
-    assert uncovered_rows_are_zero(p, got)
-    assert same_bits(got, want)
+    results = []
+    for fill in PREFILLS:                                   # what an earlier launch may have left in the workspace
+        ws.bytes().fill_(fill)
+        got.fill_(SENT)
+        if kind is None:
+            rc = lib.fql_moe_group_fwd(pk.ptr, sc.ptr, zp.ptr, rw.ptr, DT[din], cnt.ptr, off.ptr, bias.ptr, out.ptr, DT[dout], E,
+                                       T, K, N, group, 0, ws.ptr, nbytes, stream())
+        else:
+            rc = lib.fql_moe_group_glu_fwd(pk.ptr, sc.ptr, zp.ptr, rw.ptr, DT[din], cnt.ptr, off.ptr, bias.ptr, out.ptr,
+                                           DT[dout], E, T, K, N, group, 0, ACT[kind], ALPHA, LIMIT, ws.ptr, nbytes, stream())
+        assert rc == 0
+        assert_guards_intact(pk, sc, zp, rw, cnt, off, bias, out, ws,
+                             what=f"group fwd {kind} N={N} group={group} workspace {fill:#04x}")
+        assert uncovered_rows_are_zero(p, got), hex(fill)
+        assert same_bits(got, want), hex(fill)
+        results.append(got.clone())
+    assert all(same_bits(r, results[0]) for r in results[1:])
 
 
 @pytest.mark.parametrize("din,dout", TYPES, ids=TYPE_IDS)

@@ -29,6 +29,7 @@ ACT = {"silu": 0, "gelu_tanh": 1, "swiglu_clamp": 2}
 COUNTS, TAIL = [0, 1, 33, 70], 2
 KS, NS = [32, 96, 288], [8, 40, 136]
 KINDS = ["silu", "gelu_tanh", "swiglu_clamp"]
+PREFILLS = (0x00, 0xFF, 0x7F)     # stale workspace bytes (tests/test_gpu_footprint.py); 0xFF is a NaN as bfloat16
 
 # relative Frobenius error of the float32 result against the float64 product of the same rounded inputs: the largest value
 # the tests below printed on an MI355X, and the bound the tests assert (4 x, below 2^-9 as the contract demands)
@@ -285,7 +286,8 @@ def test_block_with_mxfp4_experts_against_torch():
 @pytest.mark.parametrize("N", [40, 201])
 def test_entries_stay_inside_their_buffers(N, dout, gated):
     """Every pointer is the interior of a guarded buffer; out sits 4 bytes off a 16-byte boundary inside SENT.  Only
-    [T, N] changes, the guards stay, uncovered rows are zero and the bits are the public op's."""
+    [T, N] changes, the guards stay, uncovered rows are zero and the bits are the public op's.  The gated entry runs once
+    per stale workspace content (PREFILLS) and must return those bits each time."""
     from fused_int4_amd import _native
     lib = _native.lib()
     K = 96
@@ -308,11 +310,18 @@ def test_entries_stay_inside_their_buffers(N, dout, gated):
     if gated:
         assert nbytes == (T * K * 2 + 15) // 16 * 16
         ws = Guarded("workspace", nbytes, torch.uint8, 0x5A, offset=16)
-        rc = lib.fql_moe_mx4_glu_fwd(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
-                                     ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
         want = ops().moe_gated_forward_mxfp4(p["blocks"], p["scales"], rows, p["tpe"], p["offs"], bias=p["bias"],
                                              out_dtype=dout, **act_kw("swiglu_clamp"))
         bufs = (bl, sc, rw, bias, cnt, off, out, ws)
+        for fill in PREFILLS:                      # what an earlier launch may have left in the workspace: the same bits
+            ws.bytes().fill_(fill)
+            out.view(dout, T, N).fill_(SENT)
+            rc = lib.fql_moe_mx4_glu_fwd(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
+                                         ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
+            assert rc == 0
+            assert_guards_intact(*bufs, what=f"mx4 fwd gated N={N} {dout} workspace {fill:#04x}")
+            assert torch.count_nonzero(out.view(dout, T, N)[T - TAIL:]) == 0, hex(fill)
+            assert same_bits(out.view(dout, T, N), want), hex(fill)
     else:
         assert nbytes == 0
         rc = lib.fql_moe_mx4_fwd(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N, None, 0, st)

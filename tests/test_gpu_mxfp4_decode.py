@@ -24,6 +24,7 @@ DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 COUNTS, TAIL = [0, 1, 5, 32, 33], 2
 KS, NS = [32, 96, 288], [8, 37, 40, 136]
 KINDS = ["silu", "gelu_tanh", "swiglu_clamp"]
+PREFILLS = (0x00, 0xFF, 0x7F)     # stale workspace bytes (tests/test_gpu_footprint.py); 0xFF is a NaN as bfloat16
 # relative Frobenius error of the float32 result against the float64 product of the same rounded inputs: the bound
 # tests/test_gpu_mxfp4.py asserts for this arithmetic (4 x the 6.6e-8 it measured); the bits are the same, so is the bound
 SAME_INPUT_BOUND = 2.64e-7
@@ -233,7 +234,8 @@ def test_decode_grouped_equals_one_expert_calls_permutation_and_rerun(force, K, 
 def test_decode_kernel_stays_inside_its_buffers(force, K, N, din, dout, gated):
     """Every pointer is the interior of a guarded buffer.  The rows start one element past a 256-byte boundary (the
     element loads) and so does out (the element stores); blocks keeps the 16 bytes the library asks for.  Only [T, N]
-    changes, the guards stay, uncovered rows are zero and the bits are the public op's under the tile kernel."""
+    changes, the guards stay, uncovered rows are zero and the bits are the public op's under the tile kernel.  The gated
+    entry then runs once per stale workspace content (PREFILLS) and must return those bits each time."""
     p = problem(K, N)
     E, T = p["E"], p["T"]
     assert T == 73
@@ -273,6 +275,16 @@ def test_decode_kernel_stays_inside_its_buffers(force, K, N, din, dout, gated):
     got = out.view(dout, T, N)
     assert torch.count_nonzero(got[T - TAIL:]) == 0
     assert same_bits(got, want)
+    if gated:                                       # what an earlier launch may have left in the workspace: the same bits
+        for fill in PREFILLS:
+            ws.bytes().fill_(fill)
+            got.fill_(SENT)
+            rc = lib().fql_moe_mx4_glu_fwd(bl.ptr, sc.ptr, rw.ptr, DT[din], bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K,
+                                           N, 2, 1.702, 7.0, ws.ptr, nbytes, st)
+            assert rc == 0
+            assert_guards_intact(*bufs, what=f"mx4 decode gated K={K} N={N} {din} {dout} workspace {fill:#04x}")
+            assert torch.count_nonzero(got[T - TAIL:]) == 0, hex(fill)
+            assert same_bits(got, want), hex(fill)
 
 
 # ---- 5. the dispatch, end to end

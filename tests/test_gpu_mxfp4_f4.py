@@ -33,6 +33,7 @@ ACT = {"silu": 0, "gelu_tanh": 1, "swiglu_clamp": 2}
 COUNTS, TAIL = [0, 1, 33, 70], 2
 KS, NS = [32, 96, 256, 288], [8, 40, 136]
 KINDS = ["silu", "gelu_tanh", "swiglu_clamp"]
+PREFILLS = (0x00, 0xFF, 0x7F)     # stale workspace bytes (tests/test_gpu_footprint.py); 0xFF is a NaN as an E8M0 scale
 
 SAME_INPUT_BOUND = 3.0e-5         # the fp8 path's asserted bound (tests/test_gpu_mxfp4_f8.py), as it stands
 SAME_INPUT_MEASURED = 3.5e-8      # (K = 256, N = 8; 0 at K = 32, where one block is one exact sum, .. 3.5e-8 over the twelve shapes)
@@ -434,7 +435,8 @@ def test_block_with_fp4_mxfp4_experts_against_torch():
 def test_entries_stay_inside_their_buffers(N, dout, entry):
     """Every pointer is the interior of a guarded buffer; out sits 4 bytes off a 16-byte boundary inside SENT and the
     workspace has exactly the reported size.  Only [T, N] (and the workspace, but not its padding) changes, the guards stay,
-    the operands are unchanged, uncovered rows are zero and the bits are the public op's."""
+    the operands are unchanged, uncovered rows are zero and the bits are the public op's.  The two entries with a workspace
+    run on 0x5A and then once per stale workspace content of PREFILLS, with the same bits and the same workspace each time."""
     from fused_int4_amd import _native
     lib = _native.lib()
     K = 96
@@ -469,16 +471,18 @@ def test_entries_stay_inside_their_buffers(N, dout, entry):
         if entry == "q4":
             rows = p["x"]
             rw = guarded_like("rows", rows, NAN, offset=row_off)
-            rc = lib.fql_moe_mx4_fwd_q4(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
-                                        ws.ptr, nbytes, st)
+            call = lambda: lib.fql_moe_mx4_fwd_q4(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
+                                                  ws.ptr, nbytes, st)
+            rc = call()
             want = runq(p, rows, bias=True, out_dtype=dout)
             hb, hs = ops().quantize_rows_mxfp4(rows)
         else:
             g = torch.Generator().manual_seed(3)
             rows = torch.randn(T, 2 * K, generator=g).to(DEV)
             rw = guarded_like("rows", rows, NAN, offset=row_off)
-            rc = lib.fql_moe_mx4_glu_fwd_q4(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
-                                            ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
+            call = lambda: lib.fql_moe_mx4_glu_fwd_q4(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
+                                                      ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
+            rc = call()
             want = ops().moe_gated_forward_mxfp4(p["blocks"], p["scales"], rows, p["tpe"], p["offs"], bias=p["bias"],
                                                  out_dtype=dout, precision="fp4", **act_kw("swiglu_clamp"))
             hb, hs = ops().quantize_rows_mxfp4(rows, **act_kw("swiglu_clamp"))
@@ -496,6 +500,16 @@ def test_entries_stay_inside_their_buffers(N, dout, entry):
     got = out.view(dout, T, N)
     assert torch.count_nonzero(got[T - TAIL:]) == 0
     assert same_bits(got, want)
+    if entry != "f4":                               # what an earlier launch may have left in the workspace: the same bits
+        for fill in PREFILLS:
+            w.fill_(fill)
+            got.fill_(SENT)
+            assert call() == 0
+            assert_guards_intact(*bufs, what=f"mx4 f4 {entry} N={N} {dout} workspace {fill:#04x}")
+            assert torch.equal(w[:used_b], hb.flatten()) and torch.equal(w[first:first + used_s], hs.flatten()), hex(fill)
+            assert bool((w[used_b:first] == fill).all()) and bool((w[first + used_s:] == fill).all()), hex(fill)
+            assert torch.count_nonzero(got[T - TAIL:]) == 0, hex(fill)
+            assert same_bits(got, want), hex(fill)
 
 
 @pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])

@@ -35,6 +35,7 @@ ACT = {"silu": 0, "gelu_tanh": 1, "swiglu_clamp": 2}
 COUNTS, TAIL = [0, 1, 33, 70], 2
 KS, NS = [32, 96, 256, 288], [8, 40, 136]
 KINDS = ["silu", "gelu_tanh", "swiglu_clamp"]
+PREFILLS = (0x00, 0xFF, 0x7F)     # stale workspace bytes (tests/test_gpu_footprint.py); 0xFF is a NaN as e4m3 and as float32
 
 # relative Frobenius error of the float32 result against the float64 product of the same e4m3 values: the largest value
 # the tests below printed on an MI355X, and the bound they assert (4 x; it may not exceed the project's FP8_ACC_REL_FRO)
@@ -372,7 +373,8 @@ def test_block_with_fp8_mxfp4_experts_against_torch():
 def test_entries_stay_inside_their_buffers(N, dout, entry):
     """Every pointer is the interior of a guarded buffer; out sits 4 bytes off a 16-byte boundary inside SENT and the
     workspace has exactly the reported size.  Only [T, N] (and the workspace) changes, the guards stay, the operands are
-    unchanged, uncovered rows are zero and the bits are the public op's."""
+    unchanged, uncovered rows are zero and the bits are the public op's.  The two entries with a workspace then run once per
+    stale workspace content (PREFILLS) and must return those bits each time."""
     from fused_int4_amd import _native
     lib = _native.lib()
     K = 96
@@ -405,15 +407,17 @@ def test_entries_stay_inside_their_buffers(N, dout, entry):
         if entry == "q8":
             rows = p["x"]
             rw = guarded_like("rows", rows, NAN, offset=row_off)
-            rc = lib.fql_moe_mx4_fwd_q8(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
-                                        ws.ptr, nbytes, st)
+            call = lambda: lib.fql_moe_mx4_fwd_q8(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
+                                                  ws.ptr, nbytes, st)
+            rc = call()
             want = runq(p, rows, bias=True, out_dtype=dout)
         else:
             g = torch.Generator().manual_seed(3)
             rows = torch.randn(T, 2 * K, generator=g).to(DEV)
             rw = guarded_like("rows", rows, NAN, offset=row_off)
-            rc = lib.fql_moe_mx4_glu_fwd_q8(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
-                                            ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
+            call = lambda: lib.fql_moe_mx4_glu_fwd_q8(bl.ptr, sc.ptr, rw.ptr, 0, bias.ptr, cnt.ptr, off.ptr, out.ptr, DT[dout], E, T, K, N,
+                                                      ACT["swiglu_clamp"], ALPHA, LIMIT, ws.ptr, nbytes, st)
+            rc = call()
             want = ops().moe_gated_forward_mxfp4(p["blocks"], p["scales"], rows, p["tpe"], p["offs"], bias=p["bias"],
                                                  out_dtype=dout, precision="fp8", **act_kw("swiglu_clamp"))
         bufs, ops_in = (bl, sc, rw, bias, cnt, off, out, ws), ((rw, rows),)
@@ -425,3 +429,11 @@ def test_entries_stay_inside_their_buffers(N, dout, entry):
     got = out.view(dout, T, N)
     assert torch.count_nonzero(got[T - TAIL:]) == 0
     assert same_bits(got, want)
+    if entry != "f8":                               # what an earlier launch may have left in the workspace: the same bits
+        for fill in PREFILLS:
+            ws.bytes().fill_(fill)
+            got.fill_(SENT)
+            assert call() == 0
+            assert_guards_intact(*bufs, what=f"mx4 f8 {entry} N={N} {dout} workspace {fill:#04x}")
+            assert torch.count_nonzero(got[T - TAIL:]) == 0, hex(fill)
+            assert same_bits(got, want), hex(fill)
