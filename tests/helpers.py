@@ -381,3 +381,100 @@ def assert_guards_intact(*buffers, what=""):
             where = lambda o: f"{-o} bytes in front of it" if o < 0 else f"{o - b.nbytes} bytes past its end"
             raise AssertionError(f"{what}: buffer '{b.name}' ({b.nbytes} bytes): guard changed, first byte at interior "
                                  f"offset {first} ({where(first)}), last at {last} ({where(last)})")
+
+
+# ---- operands past 2 GiB and 4 GiB (tests/test_gpu_large_tensors.py): a 32-bit offset that wraps stays in memory the test owns
+B31 = 1 << 31
+B32 = 1 << 32
+
+
+def bit_pattern(dtype, value):
+    """(integer dtype of the same width, integer) whose bits are ``value`` as one element of ``dtype``."""
+    import torch
+    one = torch.empty(1, dtype=dtype)
+    one.fill_(value)
+    idt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[one.element_size()]
+    return idt, int(one.view(idt)[0])
+
+
+class BigGuarded:
+    """``Guarded`` for an operand of more than 2^31 bytes: the guard IN FRONT of the interior is 2^31 bytes (plus the
+    alignment), the one behind it GUARD_BYTES.  A byte offset in [2^31, 2^32) that is truncated to a signed 32-bit value
+    lands at most 2^31 bytes in front of the base, inside the front guard; one in [2^32, 2^33) truncated to an unsigned
+    32-bit value lands inside the interior itself (which is larger than 2^32 bytes then).  Both guards hold ``poison`` as
+    elements of ``dtype`` (NaN around float inputs, 0xFF around packed weights and E8M0 scales, SENT around outputs), so a
+    wrapped load returns poison, a wrapped store breaks the pattern, and neither leaves memory the test owns.  The
+    interior starts 16 bytes past a 256-byte boundary (every vector width the kernels pick stays legal) and is NOT
+    initialised: the caller fills it.  The guards are checked against the pattern in 256 MiB pieces (no second copy)."""
+    PIECE = 1 << 28
+
+    def __init__(self, name, nbytes, dtype, poison, front=B31, device="cuda"):
+        import torch
+        self.idt, self.pattern = bit_pattern(dtype, poison)
+        esz = torch.empty((), dtype=dtype).element_size()
+        assert nbytes % esz == 0 and front % 256 == 0
+        self.name, self.nbytes, self.dtype, self.front, self.esz = name, int(nbytes), dtype, int(front), esz
+        self.raw = torch.empty(self.front + 512 + self.nbytes + GUARD_BYTES, dtype=torch.uint8, device=device)
+        base = self.raw.data_ptr()
+        assert base % 16 == 0
+        self.start = self.front + (16 - (base + self.front)) % 256
+        self.end = self.start + self.nbytes
+        self.ptr = base + self.start
+        assert self.ptr % 256 == 16 and self.start >= self.front and self.end + GUARD_BYTES <= self.raw.numel()
+        self.raw[:self.start].view(self.idt).fill_(self.pattern)
+        self.raw[self.end:self.end + GUARD_BYTES].view(self.idt).fill_(self.pattern)
+
+    def bytes(self):
+        return self.raw[self.start:self.end]
+
+    def view(self, *shape):
+        """The interior as a tensor of the operand's dtype and ``shape`` (a view: the kernels' buffer itself)."""
+        return self.bytes().view(self.dtype).view(*shape)
+
+    def at(self, byte_offset, n):
+        """``n`` elements at ``byte_offset`` from the START OF THE INTERIOR, which may be negative (the front guard)."""
+        a = self.start + byte_offset
+        assert 0 <= a and a + n * self.esz <= self.raw.numel() and byte_offset % self.esz == 0
+        return self.raw[a:a + n * self.esz].view(self.dtype)
+
+    def violations(self):
+        """None, or (first, last) changed guard byte as offsets from the start of the interior."""
+        bad = []
+        for lo, hi, rel in ((0, self.start, -self.start), (self.end, self.end + GUARD_BYTES, self.nbytes - self.end)):
+            for a in range(lo, hi, self.PIECE):
+                b = min(a + self.PIECE, hi)
+                diff = self.raw[a:b].view(self.idt) != self.pattern
+                if bool(diff.any()):
+                    w = diff.nonzero().flatten() * self.raw[a:b].view(self.idt).element_size()
+                    bad += [int(w.min()) + a + rel, int(w.max()) + a + rel]
+                del diff
+        return (min(bad), max(bad)) if bad else None
+
+
+def wrapped_offsets(byte_offset):
+    """Where a byte offset lands when a kernel truncates it to 32 bits: ``(unsigned, signed)`` -- ``offset mod 2^32``, and
+    that value read as a signed int (negative for a remainder of 2^31 or more: in front of the base).  Either is None
+    where it equals the offset itself (nothing to tell apart)."""
+    u = byte_offset % B32
+    s = u - B32 if u >= B31 else u
+    return (u if u != byte_offset else None), (s if s != byte_offset else None)
+
+
+def row_groups(T, row_bytes):
+    """The four row groups of the large-operand tests, as (lo, hi) pairs: 33 rows at the start, 70 rows around the row in
+    which the byte offset crosses 2^31, 70 around the one that crosses 2^32 (left out when the operand ends before it),
+    33 rows ending 2 rows before T.  Asserts that they are disjoint, in order, and that the straddling rows straddle."""
+    g = [(0, 33)]
+    for b in (B31, B32):
+        r = b // row_bytes
+        if (r + 36) * row_bytes <= (T - 35) * row_bytes:
+            assert r * row_bytes < b < (r + 1) * row_bytes, "the row stride divides the boundary: no row straddles it"
+            g.append((r - 35, r + 35))
+    g.append((T - 35, T - 2))
+    assert all(a[1] < b[0] for a, b in zip(g, g[1:])) and g[-1][1] * row_bytes <= T * row_bytes, g
+    return g
+
+
+def free_gib():
+    import torch
+    return torch.cuda.mem_get_info()[0] / 2 ** 30
