@@ -169,6 +169,8 @@ _SYMBOLS = {
                               + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "fql_tune_set_mx4_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_mx4_kernel": (ctypes.c_int, [ctypes.c_int] * 4),
+    "fql_tune_set_mx4_scaled_decode_max_rows": (ctypes.c_int, [ctypes.c_int] * 2),
+    "fql_tune_mx4_scaled_kernel": (ctypes.c_int, [ctypes.c_int] * 5),
     "fql_combine_sparse_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
                                + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
 }

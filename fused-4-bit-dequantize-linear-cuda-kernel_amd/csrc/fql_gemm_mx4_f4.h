@@ -86,6 +86,26 @@ __host__ __device__ inline uint32_t mx4_e2m1_code(uint32_t bits, int c)
     return sign | (hv < 4u ? hv : hv < 8u ? (hv >> 1) + 2u : (hv >> 2) + 4u);
 }
 
+// The epilogue of one 32-n block (columns nb0 .. nb0 + 31) of the lane's row t, shared by mx4_f4_kernel and the decode
+// kernel (fql_gemm_mx4_sdecode.h): registers 4q .. 4q+3 of acc are n = nb0 + 8 q + 4 h + (0 .. 3).
+template <int OUT>
+__device__ __forceinline__ void mx4_f4_epilogue(const v16f &acc, void *__restrict__ out, int t, int N, int nb0, int h, bool vec,
+                                                const float *__restrict__ brow)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int nc = nb0 + 8 * q + 4 * h;
+        if (nc >= N) continue;
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            v[c] = acc[4 * q + c];
+            if (brow != nullptr && nc + c < N) v[c] = __fadd_rn(v[c], brow[nc + c]);
+        }
+        store_out4(out, OUT, (size_t)t * N, nc, N, vec, v);
+    }
+}
+
 // OUT: element type of out, rounded once in the epilogue.
 template <int OUT>
 __global__ __launch_bounds__(256) void mx4_f4_kernel(
@@ -219,19 +239,7 @@ __global__ __launch_bounds__(256) void mx4_f4_kernel(
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int nc = n0 + 32 * (nb + b) + 8 * q + 4 * h;
-            if (nc >= N) continue;
-            float v[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                v[c] = acc[b][4 * q + c];
-                if (brow != nullptr && nc + c < N) v[c] = __fadd_rn(v[c], brow[nc + c]);
-            }
-            store_out4(out, OUT, (size_t)t * N, nc, N, vec, v);
-        }
+    for (int b = 0; b < 2; ++b) mx4_f4_epilogue<OUT>(acc[b], out, t, N, n0 + 32 * (nb + b), h, vec, brow);
 #endif
 }
 

@@ -58,6 +58,27 @@ struct Mx4F8Cfg {
     static constexpr int THREADS = 256;
 };
 
+// The epilogue of one 32-n block (columns nb0 .. nb0 + 31) of the lane's row t, shared by mx4_f8_kernel and the decode
+// kernel (fql_gemm_mx4_sdecode.h): registers 4q .. 4q+3 of acc are n = nb0 + 8 q + 4 h + (0 .. 3).
+template <int OUT>
+__device__ __forceinline__ void mx4_f8_epilogue(const v16f &acc, void *__restrict__ out, int t, int N, int nb0, int h, bool vec,
+                                                const float *__restrict__ brow, const float *__restrict__ act_scale, float as)
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int nc = nb0 + 8 * q + 4 * h;
+        if (nc >= N) continue;
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float a = acc[4 * q + c];
+            if (brow != nullptr && nc + c < N) v[c] = __fmaf_rn(as, a, brow[nc + c]);
+            else v[c] = act_scale == nullptr ? a : __fmul_rn(as, a);
+        }
+        store_out4(out, OUT, (size_t)t * N, nc, N, vec, v);
+    }
+}
+
 // OUT: element type of out, rounded once in the epilogue.
 template <int OUT>
 __global__ __launch_bounds__(256) void mx4_f8_kernel(
@@ -196,20 +217,7 @@ __global__ __launch_bounds__(256) void mx4_f8_kernel(
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
     const float as = act_scale == nullptr ? 1.0f : act_scale[t];
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int nc = n0 + 32 * (nb + b) + 8 * q + 4 * h;
-            if (nc >= N) continue;
-            float v[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float a = acc[b][4 * q + c];
-                if (brow != nullptr && nc + c < N) v[c] = __fmaf_rn(as, a, brow[nc + c]);
-                else v[c] = act_scale == nullptr ? a : __fmul_rn(as, a);
-            }
-            store_out4(out, OUT, (size_t)t * N, nc, N, vec, v);
-        }
+    for (int b = 0; b < 2; ++b) mx4_f8_epilogue<OUT>(acc[b], out, t, N, n0 + 32 * (nb + b), h, vec, brow, act_scale, as);
 #endif
 }
 

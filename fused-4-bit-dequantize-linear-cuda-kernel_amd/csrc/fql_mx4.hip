@@ -1,7 +1,7 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h, fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
 // fql_moe_mx4_bwd_input, the fp8-row entries fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 and the MXFP4-row entries
 // fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 / fql_mx4_quantize_rows) over the kernels of fql_gemm_mx4.h,
-// fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h, fql_gemm_mx4_f8.h and fql_gemm_mx4_f4.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h, fql_gemm_mx4_f8.h, fql_gemm_mx4_f4.h and fql_gemm_mx4_sdecode.h.  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -11,6 +11,7 @@
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_mx4_f8.h"
 #include "fql_gemm_mx4_f4.h"
+#include "fql_gemm_mx4_sdecode.h"
 
 #include <cmath>
 
@@ -39,6 +40,35 @@ int g_mx4_decode_max_rows = FQL_MX4_DECODE_MAX_ROWS;
 bool mx4_use_decode(int T)
 {
     return T > 0 && T <= g_mx4_decode_max_rows && (T + Mx4DecodeCfg::BT - 1) / Mx4DecodeCfg::BT <= 65535;
+}
+
+// The two block-scaled precisions have the same pair of kernels (fql_gemm_mx4_sdecode.h), each with a threshold of its own:
+// index 0 the fp8 rows (mode 1 of the hooks), index 1 the MXFP4 rows (mode 2).
+#define FQL_MX4_F8_DECODE_MAX_ROWS 8   /* rows (T) up to which the fp8-row decode kernel runs: the largest count of the sweep up to which it wins at every point of both shapes */
+#define FQL_MX4_F4_DECODE_MAX_ROWS 8   /* ... the MXFP4-row decode kernel: the same rule, the same count */
+int g_mx4_scaled_decode_max_rows[2] = {FQL_MX4_F8_DECODE_MAX_ROWS, FQL_MX4_F4_DECODE_MAX_ROWS};
+
+bool mx4_scaled_use_decode(int rows_kind, int T)
+{
+    return T > 0 && T <= g_mx4_scaled_decode_max_rows[rows_kind - ROWS_E4M3] &&
+           (T + Mx4SDecodeCfg::BT - 1) / Mx4SDecodeCfg::BT <= 65535;
+}
+
+// The decode kernel of either block-scaled precision: c.rows is what launch_mx4_f8 / launch_mx4_f4 take.
+template <int ROWS>
+int launch_mx4_sdecode(int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    using D = Mx4SDecodeCfg;                                 // (one more z-slice zeroes the rows no expert covers)
+    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, c.tpe != nullptr ? c.E + 1 : 1);
+    auto go = [&](auto kern) {
+        return launch(kern, grid, dim3(D::THREADS), 0, st, c.blocks, c.scales, static_cast<const uint8_t *>(c.rows), c.row_scales,
+                      c.act_scale, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+    };
+    switch (out_dtype) {
+    case FQL_DTYPE_F32: return go(mx4_sdecode_kernel<ROWS, FQL_DTYPE_F32>);
+    case FQL_DTYPE_F16: return go(mx4_sdecode_kernel<ROWS, FQL_DTYPE_F16>);
+    default: return go(mx4_sdecode_kernel<ROWS, FQL_DTYPE_BF16>);
+    }
 }
 
 template <int IN, int OUT>
@@ -121,6 +151,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, int in_cols, bool a
 // ---- the fp8-row path (fql_gemm_mx4_f8.h): c.rows is [T][K] e4m3 bytes
 int launch_mx4_f8(int out_dtype, const Mx4Call &c, hipStream_t st)
 {
+    if (mx4_scaled_use_decode(ROWS_E4M3, c.T)) return launch_mx4_sdecode<ROWS_E4M3>(out_dtype, c, st);
     using C = Mx4F8Cfg;                                      // (one more z-slice zeroes the rows no expert covers)
     static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the bfloat16 kernel's row tile");
     const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1);
@@ -158,6 +189,7 @@ int mx4_q8_run(Mx4Call c, int in_dtype, int out_dtype, bool gated, int activatio
 // ---- the MXFP4-row path (fql_gemm_mx4_f4.h): c.rows is [T][K / 2] packed e2m1, c.row_scales [T][K / 32] E8M0
 int launch_mx4_f4(int out_dtype, const Mx4Call &c, hipStream_t st)
 {
+    if (mx4_scaled_use_decode(ROWS_MXFP4, c.T)) return launch_mx4_sdecode<ROWS_MXFP4>(out_dtype, c, st);
     using C = Mx4F4Cfg;                                      // (one more z-slice zeroes the rows no expert covers)
     static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the bfloat16 kernel's row tile");
     const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT, c.tpe != nullptr ? c.E + 1 : 1);
@@ -394,6 +426,21 @@ FQL_API int fql_tune_mx4_kernel(int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
     return mx4_use_decode(T) ? 1 : 0;
+}
+
+FQL_API int fql_tune_set_mx4_scaled_decode_max_rows(int mode, int rows)
+{
+    if (mode != 1 && mode != 2) return -1;
+    const int old = g_mx4_scaled_decode_max_rows[mode - 1];
+    if (rows >= 0) g_mx4_scaled_decode_max_rows[mode - 1] = rows;
+    return old;
+}
+
+FQL_API int fql_tune_mx4_scaled_kernel(int mode, int E, int T, int K, int N)
+{
+    (void)E; (void)K; (void)N;
+    if (mode != 1 && mode != 2) return -1;
+    return mx4_scaled_use_decode(mode == 1 ? ROWS_E4M3 : ROWS_MXFP4, T) ? 1 : 0;
 }
 
 }  // extern "C"

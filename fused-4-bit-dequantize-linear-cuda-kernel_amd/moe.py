@@ -502,7 +502,9 @@ class MXFP4MoEFFN(nn.Module):
     activations are rounded once to bfloat16 (float32 inputs) or read as they are (bfloat16), the sums are float32.
     ``activation_dtype=torch.bfloat16`` takes bfloat16 inputs, keeps ``gate_up`` in bfloat16 and returns bfloat16; the
     default takes float32 and keeps ``gate_up`` in float32.  A small batch (few routed rows: decode) takes the library's
-    decode kernel for both GEMMs instead of the 64-row tile; it returns the same bits, so nothing else changes.
+    decode kernel for both GEMMs instead of the 64-row tile; it returns the same bits, so nothing else changes.  That
+    holds in every ``precision``: ``"fp8"`` and ``"fp4"`` have a decode kernel of their own behind their pre-pass, each
+    with a threshold set from a measurement.
 
     ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
     ``RuntimeError``, and ``QuantizedSparseMoEBlock(experts=MXFP4MoEFFN(...))`` works under ``torch.no_grad()``.

@@ -584,6 +584,7 @@ def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, 
     float32 on the bfloat16 matrix cores; rows no expert covers are zero.  Forward only.
     Small batches (T up to the library's decode threshold) take a decode kernel that streams the weights once with one
     wave per 32 weight rows instead of the 64-row tile; the two return the same bits, so the result does not depend on T.
+    Every precision has such a pair (each with a threshold of its own, set from a measurement), behind its pre-pass.
 
     ``precision="fp8"`` is the opt-in mode on the block-scaled FP4 matrix cores: the rows are quantised per row to OCP e4m3
     (``quantize_activations_fp8``'s rule, inside a fused pre-pass) and contracted with the packed weights and their E8M0
@@ -605,7 +606,7 @@ def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_of
     (+ bias[e])``, ``gate_up`` [T, 2K] float32 or bfloat16, ``blocks`` [E, N, K/2].  The activation (``activation_of``) is
     evaluated in float32 and rounded once to bfloat16 by a streaming pre-pass into the op's workspace: no [T, K] tensor is
     handed back.  Forward only.  Behind the pre-pass, small batches take the decode kernel of
-    ``moe_forward_mxfp4`` with the same bits as the tile kernel.
+    ``moe_forward_mxfp4`` with the same bits as the tile kernel, in every precision.
 
     ``precision="fp8"``: the float32 ``h = act(...)`` is quantised per row to e4m3 by the pre-pass instead (never stored as
     floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``.  ``precision="fp4"``: ``h`` is
@@ -1115,7 +1116,8 @@ def moe_forward_mxfp4_fp8(blocks, scales, inputs_e4m3, act_scales, tokens_per_ex
     ``out[t] = act_scales[t] * (W_e @ e4m3(inputs_e4m3[t])) (+ bias[e])``.  ``blocks`` / ``scales`` as ``moe_forward_mxfp4``
     takes them; ``inputs_e4m3`` [T, K] torch.float8_e4m3fn (or its uint8 bytes), ``act_scales`` [T] float32 or None (= 1);
     ``bias`` [E, N] float32 (optional).  Returns [T, N] in ``out_dtype``; rows no expert covers are zero.  Forward only
-    (INTEGRATION.md section 17)."""
+    (INTEGRATION.md section 17).  Small batches (T up to the library's fp8 decode threshold) take a one-wave decode
+    kernel that returns the same bits as the tile kernel: the result does not depend on T."""
     _forward_only("moe_forward_mxfp4_fp8", inputs_e4m3, act_scales, bias)
     x8, act_scales = _fp8_operands(inputs_e4m3, act_scales, "inputs_e4m3", out_dtype, "hidden_dim")
     T, K = x8.shape
@@ -1160,7 +1162,8 @@ def moe_forward_mxfp4_fp4(blocks, scales, in_blocks, in_scales, tokens_per_exper
     ``moe_forward_mxfp4`` takes them; ``in_blocks`` uint8 [T, K/2] and ``in_scales`` uint8 [T, K/32] in the same layout
     (``quantize_rows_mxfp4`` or ``quantize.quantize_mxfp4``); ``bias`` [E, N] float32 (optional).  Returns [T, N] in
     ``out_dtype``; rows no expert covers are zero; an ``in_scales`` byte of 255 makes its row NaN.  Forward only
-    (INTEGRATION.md section 17)."""
+    (INTEGRATION.md section 17).  Small batches (T up to the library's fp4 decode threshold) take a one-wave decode
+    kernel that returns the same bits as the tile kernel: the result does not depend on T."""
     _forward_only("moe_forward_mxfp4_fp4", bias)
     for name, t in (("in_blocks", in_blocks), ("in_scales", in_scales)):
         if not t.is_cuda or t.dim() != 2 or t.dtype != torch.uint8:

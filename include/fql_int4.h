@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 380 /* 0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 390 /* 0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -900,9 +900,23 @@ FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m
  *   The two kernels return THE SAME BITS for every element of out: both issue v_mfma_f32_32x32x16_bf16 with the weights as the
  *   A operand over k0 = 0, 16, 32, ... on an accumulator that starts at zero, feed it the same dequantised weights and the same
  *   rounded rows, and share the epilogue.  So the guarantee above (a row's result depends on its own row and its expert's
- *   weights only, not on T, E or the table) holds across the threshold.  The fp8 / MXFP4-row modes and the input gradient
- *   have the tile form only.  fql_int4_tune.h: fql_tune_set_mx4_decode_max_rows / fql_tune_mx4_kernel force and report the
+ *   weights only, not on T, E or the table) holds across the threshold.  The input gradient has the tile form only (the
+ *   fp8 / MXFP4-row modes have their own decode kernel: FQL_VERSION 390, below).  fql_int4_tune.h: fql_tune_set_mx4_decode_max_rows / fql_tune_mx4_kernel force and report the
  *   choice (tools and tests). */
+
+/* ---- the decode kernels of the fp8-row and MXFP4-row precisions (FQL_VERSION 390; INTEGRATION.md section 17, DESIGN.md
+ *      section 32; csrc/fql_gemm_mx4_sdecode.h) ----
+ * fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 and fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 (the quantising ones behind their
+ * pre-pass, which is unchanged) run one of two kernels as well: the 64-row x 128-column tile of FQL_VERSION 360 / 370, or, when
+ * T is at most a threshold built into the library per precision (FQL_MX4_F8_DECODE_MAX_ROWS / FQL_MX4_F4_DECODE_MAX_ROWS in
+ * csrc/fql_mx4.hip, set from a measurement; 0 disables it) and ceil(T / 32) <= 65535, a decode kernel in which one wave streams
+ * 32 weight rows of one expert over all of K for a block of up to 32 rows.  Only T decides.  Signatures, checks, return codes,
+ * workspace sizes and the non-finite rules are unchanged.
+ *   The two kernels return THE SAME BITS for every element of out: both issue ceil(K / 64) v_mfma_scale_f32_32x32x64_f8f6f4 in
+ *   ascending k on an accumulator that starts at zero, the weights as A, the rows as B, every lane with the same bytes and the
+ *   same scale bytes, and share the epilogue.  So a row's result does not depend on T across the threshold either.  The
+ *   thresholds are independent of each other and of the bfloat16 one.  fql_int4_tune.h: the hooks with `scaled` in their names
+ *   force and report the choice (tools and tests). */
 
 /* ---- the input gradient of the MXFP4 expert weights (FQL_VERSION 350; INTEGRATION.md section 17, DESIGN.md section 26;
  *      csrc/fql_gemm_mx4_bwd.h) ----

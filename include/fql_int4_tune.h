@@ -57,6 +57,14 @@ FQL_API int fql_tune_set_mx4_decode_max_rows(int rows);  /* MXFP4 bfloat16 forwa
 /* 0: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
 FQL_API int fql_tune_mx4_kernel(int E, int T, int K, int N);
 
+/* The same pair for the block-scaled precisions (fql_int4.h, FQL_VERSION 390).  mode: 1 the fp8-row entries (fql_moe_mx4_fwd_f8 /
+ * _fwd_q8 / _glu_fwd_q8), 2 the MXFP4-row ones (_fwd_f4 / _fwd_q4 / _glu_fwd_q4); each mode has a threshold of its own, and neither
+ * moves with fql_tune_set_mx4_decode_max_rows.  The setter returns the mode's previous value (a negative `rows` changes nothing);
+ * an unknown mode changes nothing and returns -1 from both. */
+FQL_API int fql_tune_set_mx4_scaled_decode_max_rows(int mode, int rows);
+/* 0: the mode's entries would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
+FQL_API int fql_tune_mx4_scaled_kernel(int mode, int E, int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

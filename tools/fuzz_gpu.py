@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep of the product calls against the C oracle (run on a GPU box; not part of the test
 suite: tests/ holds the fixed cases).  Exercises every dispatch branch: GEMV, generic, wide / short-row / decode
-tiles, grouped and dense, the three precisions and the 16-bit I/O."""
+tiles, grouped and dense, the three precisions and the 16-bit I/O, and the tile / decode kernel pair of the MXFP4
+experts' fp8 and fp4 precisions (forced either way, compared bit for bit)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -78,6 +79,28 @@ for case in range(n_cases):
         rg = rel(outg, refg)
         worst[f"group/{prec if int_path else 'f32'}"] = max(worst.get(f"group/{prec if int_path else 'f32'}", 0.0), rg)
         assert rg < tolg, ("per-group", case, rg, Bg, Ng, Kg, group, prec)
+    if case % 8 == 3:                      # MXFP4 experts, the block-scaled precisions: the tile and the decode kernel, same bits
+        L = fq._native.lib()
+        mode = 1 + (case // 8) % 2         # 1: fp8 rows, 2: MXFP4 rows
+        Em, Km, Nm = int(rng.choice([1, 3, 8, 33])), 32 * int(rng.integers(1, 24)), int(rng.choice([5, 32, 37, 96, 130, 264]))
+        cm = rng.integers(0, int(rng.choice([3, 17, 40, 70])), size=Em).astype(np.int32)
+        om = (np.cumsum(cm) - cm).astype(np.int32)
+        Tm = int(cm.sum()) + int(rng.integers(0, 4))
+        if Tm:
+            d = lambda a: torch.from_numpy(a).cuda()
+            bm = d(rng.integers(0, 256, size=(Em, Nm, Km // 2)).astype(np.uint8))
+            sm = d(rng.integers(110, 135, size=(Em, Nm, Km // 32)).astype(np.uint8))
+            xm = d(rng.standard_normal((Tm, Km)).astype(np.float32))
+            bias = d(rng.standard_normal((Em, Nm)).astype(np.float32)) if case % 16 < 8 else None
+            old = L.fql_tune_set_mx4_scaled_decode_max_rows(mode, -1)
+            res = []
+            for rows in (0, 2 ** 31 - 1):
+                L.fql_tune_set_mx4_scaled_decode_max_rows(mode, rows)
+                assert L.fql_tune_mx4_scaled_kernel(mode, Em, Tm, Km, Nm) == (rows > 0)
+                res.append(ops.moe_forward_mxfp4(bm, sm, xm, d(cm), d(om), bias=bias, precision=("fp8", "fp4")[mode - 1]))
+            L.fql_tune_set_mx4_scaled_decode_max_rows(mode, old)
+            assert torch.equal(res[0].view(torch.int32), res[1].view(torch.int32)), ("mxfp4 scaled", case, mode, Em, Tm, Km, Nm, cm)
+            worst[f"mxfp4-{('fp8', 'fp4')[mode - 1]}/tile!=decode"] = 0.0
     mfma = (K % 32 == 0) and (grouped or x.shape[0] > 2)
     tol = TOL[prec] if mfma else 2e-6
     if mfma and prec == "int8" and out.size < 2000:
