@@ -37,64 +37,17 @@
 //     word it writes has an exponent field of 255, and the epilogue writes NaN across a flagged row.
 //   * RANGE.  2^(s - 127) * |e2m1| below 2^-126 (scale codes 0 and 1 with the smallest codes) may be flushed to zero.
 //   * No atomics, every element is written once.  With a table the launch carries one more z-slice whose workgroups zero
-//     the rows of out that no expert covers (act_zero_uncovered, fql_act_quant.h).
+//     the rows of out that no expert covers (mx4_group_begin, fql_mx4_common.h).
 //
-// mx4_glu_kernel: the streaming pre-pass of the gated form.  h[t][k] = act_glu_mul(gate_up[t][k], gate_up[t][F + k]) in
-// float32 from the float32 or bfloat16 row, rounded once to bfloat16 into the caller's workspace [T][F]; mx4_kernel then
-// reads h as a bfloat16 operand.  (Forming h on load would evaluate expf once per 128-column block of the output: 23 times
-// at gpt-oss's N = 2880.)
+// The gated form runs mx4_glu_kernel (fql_mx4_quant.h) first and reads its bfloat16 h [T][K] as x.
 #pragma once
-#include "fql_common.h"
-#include "fql_act_quant.h"
-
-#ifndef FQL_MX4_CVT
-#define FQL_MX4_CVT 1          // 1: v_cvt_scalef32_pk_bf16_fp4 (two codes an instruction); 0: integer arithmetic
-#endif
-
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+#include "fql_mx4_common.h"
 
 struct Mx4Cfg {
     static constexpr int BT = 64, BN = 128, BK = 64;   // rows, columns and contraction depth of a stage
     static constexpr int PITCH = BK + 8;               // bfloat16 elements of an image row (144 bytes)
     static constexpr int THREADS = 256;
 };
-
-// bfloat16 bits of e2m1 code c (4 bits, sign included) times 2^(s - 127); base = (s - 1) << 7.  Code 1 (0.5) is e2m1's
-// one subnormal: exponent field s - 1, mantissa 0; codes 2 .. 7 are (mag << 6) above that.  A field below 1 is flushed
-// to zero, one above 254 is infinity.
-__device__ __forceinline__ uint32_t mx4_elem_bits(uint32_t c, int base)
-{
-    const uint32_t mag = c & 7u;
-    int v = base + (mag == 1u ? 0 : (int)(mag << 6));
-    v = v < 128 ? 0 : (v > 0x7F80 ? 0x7F80 : v);
-    if (mag == 0u) v = 0;
-    return (uint32_t)v | ((c & 8u) << 12);
-}
-
-// The two codes of byte `B` of w as one word of two bfloat16 (low nibble = even k in the low half), times the scale of
-// code sc (< 255: the caller handles NaN).
-template <int B>
-__device__ __forceinline__ uint32_t mx4_pair(uint32_t w, int sc)
-{
-#if FQL_MX4_CVT
-    const float scale = __uint_as_float(sc == 0 ? 0x00400000u : (uint32_t)sc << 23);
-    const v2bf p = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, B);
-    return __builtin_bit_cast(uint32_t, p);
-#else
-    const uint32_t byte = (w >> (8 * B)) & 0xFFu;
-    const int base = (sc - 1) * 128;
-    return mx4_elem_bits(byte & 0xFu, base) | (mx4_elem_bits(byte >> 4, base) << 16);
-#endif
-}
-
-// two float32 -> one word of two bfloat16, to nearest even (lo in the low half)
-__device__ __forceinline__ uint32_t mx4_pack_bf16(float lo, float hi)
-{
-    uint32_t r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
 
 // IN: element type of x (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of out, rounded once in the epilogue.
 // (54 KiB of LDS: two workgroups a compute unit.)
@@ -106,20 +59,13 @@ __global__ __launch_bounds__(256) void mx4_kernel(
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4Cfg;
-    if ((int)blockIdx.z == E) {                                    // (with a table only) the rows no expert covers
-        const int blk = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        if ((long long)blk * 256 < T) act_zero_uncovered(blk, out, OUT == 0 ? 4 : 2, N, tpe, offs, E, T);
-        return;
-    }
+    int row_lo, cnt, t_blk;
+    if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     __shared__ __attribute__((aligned(16))) unsigned short image[2][C::BN][C::PITCH];      // weights, bfloat16
     __shared__ __attribute__((aligned(16))) unsigned short ximage[2][C::BT][C::PITCH];     // activation rows, bfloat16
     __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite activation
 
     const int e = blockIdx.z;
-    int row_lo = 0, cnt = T;
-    if (tpe != nullptr) expert_range(tpe, offs, e, T, row_lo, cnt);
-    const int t_blk = (int)blockIdx.y * C::BT;
-    if (t_blk >= cnt) return;                                      // (uniform per workgroup)
     const int n0 = (int)blockIdx.x * C::BN;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -189,24 +135,15 @@ __global__ __launch_bounds__(256) void mx4_kernel(
     };
     auto store_stage = [&](const Stage &st, int buf) {             // registers -> the two LDS images (bfloat16, natural k order)
         const uint32_t words[4] = {st.wq.x, st.wq.y, st.wq.z, st.wq.w};
-        const bool nan = st.sc == 255;
-        const int s = nan ? 127 : st.sc;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {                              // dword i of the piece is k = kp + 8 i .. + 7
-            uint4 o;
-            o.x = mx4_pair<0>(words[i], s);
-            o.y = mx4_pair<1>(words[i], s);
-            o.z = mx4_pair<2>(words[i], s);
-            o.w = mx4_pair<3>(words[i], s);
-            if (nan) o = make_uint4(0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u);
-            *reinterpret_cast<uint4 *>(&image[buf][sn][32 * sp + 8 * i]) = o;
-        }
+        for (int i = 0; i < 4; ++i)                                // dword i of the piece is k = kp + 8 i .. + 7
+            *reinterpret_cast<uint4 *>(&image[buf][sn][32 * sp + 8 * i]) = mx4_dequant8(words[i], st.sc);
         uint32_t xw[8], bad = 0u;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if constexpr (IN == 0) xw[i] = mx4_pack_bf16(st.x[2 * i], st.x[2 * i + 1]);
             else xw[i] = st.x[i];
-            bad |= (xw[i] & 0x7F807F80u) + 0x00800080u;            // (0x7F80 + 0x80 = 0x8000 in a half; no carry between them)
+            bad |= mx4_nonfinite2(xw[i]);
         }
         *reinterpret_cast<uint4 *>(&ximage[buf][xs][16 * xq]) = make_uint4(xw[0], xw[1], xw[2], xw[3]);
         *reinterpret_cast<uint4 *>(&ximage[buf][xs][16 * xq + 8]) = make_uint4(xw[4], xw[5], xw[6], xw[7]);
@@ -274,58 +211,5 @@ __global__ __launch_bounds__(256) void mx4_kernel(
             }
             store_out4(out, OUT, (size_t)t * N, nc, N, vec, v);
         }
-#endif
-}
-
-// h[t][k] = bf16(act_glu_mul(gate_up[t][k], gate_up[t][F + k])): one thread = 8 consecutive k of one row (F % 32 == 0)
-template <int IN>
-__global__ __launch_bounds__(256) void mx4_glu_kernel(const void *__restrict__ gate_up, unsigned short *__restrict__ hbuf,
-                                                      int T, int F, int kind, float alpha, float limit)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int per_row = F >> 3;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)T * per_row) return;
-    const int t = (int)(idx / per_row), k = (int)(idx % per_row) * 8;
-    const int es = IN == 0 ? 4 : 2;
-    const char *row = reinterpret_cast<const char *>(gate_up) + (size_t)t * 2 * F * es;
-    const bool vec = (reinterpret_cast<uintptr_t>(gate_up) & 15) == 0;
-    float g[8], u[8];
-    if (IN == 0) {
-        const float *gp = reinterpret_cast<const float *>(row) + k, *up = gp + F;
-        if (vec) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const v4f a = *reinterpret_cast<const v4f *>(gp + 4 * i), b = *reinterpret_cast<const v4f *>(up + 4 * i);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { g[4 * i + c] = a[c]; u[4 * i + c] = b[c]; }
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) { g[c] = gp[c]; u[c] = up[c]; }
-        }
-    } else {
-        const unsigned short *gp = reinterpret_cast<const unsigned short *>(row) + k, *up = gp + F;
-        if (vec) {
-            const uint4 a = *reinterpret_cast<const uint4 *>(gp), b = *reinterpret_cast<const uint4 *>(up);
-            const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                g[2 * c] = __uint_as_float(aw[c] << 16); g[2 * c + 1] = __uint_as_float(aw[c] & 0xFFFF0000u);
-                u[2 * c] = __uint_as_float(bw[c] << 16); u[2 * c + 1] = __uint_as_float(bw[c] & 0xFFFF0000u);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) { g[c] = act_widen<2>(gp[c]); u[c] = act_widen<2>(up[c]); }
-        }
-    }
-    uint4 o;
-    uint32_t w[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        w[c] = (uint32_t)f32_to_bf16_bits(act_glu_mul(kind, alpha, limit, g[2 * c], u[2 * c])) |
-               ((uint32_t)f32_to_bf16_bits(act_glu_mul(kind, alpha, limit, g[2 * c + 1], u[2 * c + 1])) << 16);
-    o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
-    *reinterpret_cast<uint4 *>(hbuf + (size_t)t * F + k) = o;      // (workspace: 16-byte aligned, F % 8 == 0)
 #endif
 }

@@ -69,20 +69,13 @@ __global__ __launch_bounds__(256) void mx4_bwd_kernel(
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4BwdCfg;
-    if ((int)blockIdx.z == E) {                                    // (with a table only) the rows no expert covers
-        const int blk = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-        if ((long long)blk * 256 < T) act_zero_uncovered(blk, dx, OUT == 0 ? 4 : 2, K, tpe, offs, E, T);
-        return;
-    }
+    int row_lo, cnt, t_blk;
+    if (!mx4_group_begin<C::THREADS, OUT>(dx, K, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     __shared__ __attribute__((aligned(16))) unsigned char image[2][C::BN * C::BK * 2];     // weights, bfloat16, swizzled
     __shared__ __attribute__((aligned(16))) unsigned short yimage[2][C::BT][C::YPITCH];    // gradient rows, bfloat16
     __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite gradient
 
     const int e = blockIdx.z;
-    int row_lo = 0, cnt = T;
-    if (tpe != nullptr) expert_range(tpe, offs, e, T, row_lo, cnt);
-    const int t_blk = (int)blockIdx.y * C::BT;
-    if (t_blk >= cnt) return;                                      // (uniform per workgroup)
     const int kbase = (int)blockIdx.x * C::BK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -166,24 +159,15 @@ __global__ __launch_bounds__(256) void mx4_bwd_kernel(
         uint32_t words[4] = {st.wq.x, st.wq.y, st.wq.z, st.wq.w};
         if (wrot & 1) { const uint32_t a = words[0], b = words[2]; words[0] = words[1]; words[1] = a; words[2] = words[3]; words[3] = b; }
         if (wrot & 2) { const uint32_t a = words[0], b = words[1]; words[0] = words[2]; words[2] = a; words[1] = words[3]; words[3] = b; }
-        const bool nan = st.sc == 255;
-        const int s = nan ? 127 : st.sc;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {                              // (words[j] is dword j ^ wrot now)
-            uint4 o;
-            o.x = mx4_pair<0>(words[j], s);
-            o.y = mx4_pair<1>(words[j], s);
-            o.z = mx4_pair<2>(words[j], s);
-            o.w = mx4_pair<3>(words[j], s);
-            if (nan) o = make_uint4(0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u, 0x7FC07FC0u);
-            *reinterpret_cast<uint4 *>(&image[buf][w_off[j]]) = o;
-        }
+        for (int j = 0; j < 4; ++j)                                // (words[j] is dword j ^ wrot now)
+            *reinterpret_cast<uint4 *>(&image[buf][w_off[j]]) = mx4_dequant8(words[j], st.sc);
         uint32_t yw[8], bad = 0u;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if constexpr (IN == 0) yw[i] = mx4_pack_bf16(st.y[2 * i], st.y[2 * i + 1]);
             else yw[i] = st.y[i];
-            bad |= (yw[i] & 0x7F807F80u) + 0x00800080u;            // (0x7F80 + 0x80 = 0x8000 in a half; no carry between them)
+            bad |= mx4_nonfinite2(yw[i]);
         }
         *reinterpret_cast<uint4 *>(&yimage[buf][ys][16 * yq]) = make_uint4(yw[0], yw[1], yw[2], yw[3]);
         *reinterpret_cast<uint4 *>(&yimage[buf][ys][16 * yq + 8]) = make_uint4(yw[4], yw[5], yw[6], yw[7]);

@@ -130,6 +130,7 @@ __device__ __forceinline__ void mx4_decode_body(
         const uint32_t words[4] = {lo[0], hi[0], lo[1], hi[1]};
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
+            // (mx4_dequant8, spelled out: through the function the compiler arranges this loop otherwise, 5 % more instructions)
             const int code = (int)sc[s >> 1];
             const bool nan = code == 255;
             const int sv = nan ? 127 : code;
@@ -144,7 +145,7 @@ __device__ __forceinline__ void mx4_decode_body(
             for (int i = 0; i < 4; ++i) {
                 if constexpr (IN == 0) xw[i] = mx4_pack_bf16(sl.x[s][2 * i], sl.x[s][2 * i + 1]);
                 else xw[i] = sl.x[s][i];
-                bad |= (xw[i] & 0x7F807F80u) + 0x00800080u;        // (0x7F80 + 0x80 = 0x8000 in a half; no carry between them)
+                bad |= mx4_nonfinite2(xw[i]);
             }
             const uint4 xb = make_uint4(xw[0], xw[1], xw[2], xw[3]);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, xb), acc, 0, 0, 0);
@@ -235,16 +236,9 @@ __global__ __launch_bounds__(64) void mx4_decode_kernel(
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4DecodeCfg;
-    if ((int)blockIdx.z == E) {                                    // (with a table only) the rows no expert covers
-        const long long blk = (long long)blockIdx.y * gridDim.x + blockIdx.x;
-        if (blk * C::THREADS < T) act_zero_uncovered<C::THREADS>((int)blk, out, OUT == 0 ? 4 : 2, N, tpe, offs, E, T);   // (64 rows a workgroup)
-        return;
-    }
+    int row_lo, cnt, t_blk;
+    if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     const int e = blockIdx.z;
-    int row_lo = 0, cnt = T;
-    if (tpe != nullptr) expert_range(tpe, offs, e, T, row_lo, cnt);
-    const int t_blk = (int)blockIdx.y * C::BT;
-    if (t_blk >= cnt) return;                                      // (uniform per workgroup)
     if ((reinterpret_cast<uintptr_t>(x) & 15) == 0)
         mx4_decode_body<IN, OUT, true, IN == 0 ? C::DEPTH_F32 : C::DEPTH_BF16, IN == 0 ? C::GROUP_F32 : C::GROUP_BF16>(blocks, scales, x, bias, out, e, row_lo, cnt, t_blk, K, N);
     else

@@ -1,22 +1,22 @@
-// The decode form of mx4_f8_kernel (fql_gemm_mx4_f8.h) and mx4_f4_kernel (fql_gemm_mx4_f4.h): the block-scaled grouped GEMM
-// on MXFP4 expert weights for a FEW rows an expert, as fql_gemm_mx4_decode.h is the decode form of mx4_kernel.
+// The decode form of mx4_scaled_kernel (fql_gemm_mx4_scaled.h): the block-scaled grouped GEMM on MXFP4 expert weights for a
+// FEW rows an expert, as fql_gemm_mx4_decode.h is the decode form of mx4_kernel.
 //
 // mx4_sdecode_kernel<ROWS, OUT>: ROWS = 1: e4m3 rows [T][K] with act_scale [T]; ROWS = 2: MXFP4 rows [T][K / 2] with
 // in_scales [T][K / 32].  Workgroup = ONE wave = 32 weight rows n of one expert x one block of up to 32 rows t, for all of
 // K.  No LDS, no barrier.  grid = (ceil(N / 32), ceil(T / 32), E (+ 1 with a table)); the workgroups of an expert without
 // rows in that block leave at once, a count above 32 is the next row block's, so the kernel is right for every T.
-//   * THE SAME BITS AS THE TILE KERNELS.  An element of the instruction's result depends on its own A row, its own B column,
+//   * THE SAME BITS AS THE TILE KERNEL.  An element of the instruction's result depends on its own A row, its own B column,
 //     their scales and its own accumulator only, so what has to agree is the sequence of instructions and what a lane feeds
 //     them, and it does: ceil(K / 64) v_mfma_scale_f32_32x32x64_f8f6f4 in ascending k on one accumulator that starts at
 //     zero, the weights as A (cbsz = 4), the rows as B (blgp = 0 with scale code 127, or blgp = 4 with the row's scale
 //     byte), lane (r = lane & 31, h = lane >> 5) supplying block 2 s + h of packed row n_r with its scale byte and, of row
 //     t_r, the bytes k0 + 16 h .. + 15 and k0 + 32 + 16 h .. + 15 (e4m3) or block 2 s + h with its scale byte (MXFP4).  The
-//     tile kernels pick the scale byte out of a 16-bit register with op_sel; here it is byte 0 of its own register: the
+//     tile kernel picks the scale byte out of a 16-bit register with op_sel; here it is byte 0 of its own register: the
 //     same byte.  K % 64 == 32 ends, as there, with one instruction whose absent block is zero codes with scale code 127
-//     on either side and zero row bytes past K; an instruction wholly past K is not issued.  The epilogues are the tile
-//     kernels' own functions (mx4_f8_epilogue / mx4_f4_epilogue).
+//     on either side and zero row bytes past K; an instruction wholly past K is not issued.  The epilogue is the tile
+//     kernel's own function (mx4_scaled_epilogue).
 //   * Nothing is exchanged and nothing is converted: the 16 bytes a lane loads of a packed row ARE its operand (the operand
-//     map in the header of fql_gemm_mx4_f8.h), so a wave's weight load is 32 rows x 32 contiguous bytes with every byte
+//     map in the header of fql_gemm_mx4_scaled.h), so a wave's weight load is 32 rows x 32 contiguous bytes with every byte
 //     used, and a slot's work is one matrix instruction.  Scale code 255 and e4m3 NaN bytes are the instruction's business.
 //   * Rows.  The lane loads its own fragment of row t_r from global memory (L2: the rows are a few KiB).  Rows past the
 //     expert's count read its last row, weight rows past N read row N - 1; neither is stored.  Loads are unconditional.
@@ -26,8 +26,7 @@
 //     measured that form).  The odd last block of K % 64 == 32 is loaded first of all and used last.
 //   * e4m3 rows whose base is not 16-byte aligned take the same kernel with byte loads and a ring of one slot.
 #pragma once
-#include "fql_gemm_mx4_f8.h"
-#include "fql_gemm_mx4_f4.h"
+#include "fql_gemm_mx4_scaled.h"
 
 #ifndef FQL_MX4_SDECODE_DEPTH
 #define FQL_MX4_SDECODE_DEPTH 8   // ring slots (A/B knob)
@@ -167,15 +166,11 @@ __device__ __forceinline__ void mx4_sdecode_body(
     if (!row_ok) return;
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
-    if constexpr (ROWS == 1) {
-        const float as = act_scale == nullptr ? 1.0f : act_scale[t];
-        mx4_f8_epilogue<OUT>(acc, out, t, N, n0, h, vec, brow, act_scale, as);
-    } else {
-        mx4_f4_epilogue<OUT>(acc, out, t, N, n0, h, vec, brow);
-    }
+    const float as = ROWS == 2 || act_scale == nullptr ? 1.0f : act_scale[t];
+    mx4_scaled_epilogue<ROWS, OUT>(acc, out, t, N, n0, h, vec, brow, act_scale, as);
 }
 
-// ROWS: 1 e4m3 rows (xscales unused), 2 MXFP4 rows (act_scale unused); OUT as the tile kernels'.
+// ROWS, OUT as the tile kernel's.
 template <int ROWS, int OUT>
 __global__ __launch_bounds__(64) void mx4_sdecode_kernel(
     const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ scales, const uint8_t *__restrict__ x,
@@ -184,16 +179,9 @@ __global__ __launch_bounds__(64) void mx4_sdecode_kernel(
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4SDecodeCfg;
-    if ((int)blockIdx.z == E) {                                    // (with a table only) the rows no expert covers
-        const long long blk = (long long)blockIdx.y * gridDim.x + blockIdx.x;
-        if (blk * C::THREADS < T) act_zero_uncovered<C::THREADS>((int)blk, out, OUT == 0 ? 4 : 2, N, tpe, offs, E, T);   // (64 rows a workgroup)
-        return;
-    }
+    int row_lo, cnt, t_blk;
+    if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     const int e = blockIdx.z;
-    int row_lo = 0, cnt = T;
-    if (tpe != nullptr) expert_range(tpe, offs, e, T, row_lo, cnt);
-    const int t_blk = (int)blockIdx.y * C::BT;
-    if (t_blk >= cnt) return;                                      // (uniform per workgroup)
     if (ROWS == 2 || (reinterpret_cast<uintptr_t>(x) & 15) == 0)
         mx4_sdecode_body<ROWS, OUT, true, C::DEPTH, C::GROUP>(blocks, scales, x, xscales, act_scale, bias, out, e, row_lo, cnt, t_blk, K, N);
     else if constexpr (ROWS == 1)

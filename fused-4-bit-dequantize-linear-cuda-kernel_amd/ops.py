@@ -563,10 +563,10 @@ def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offset
     bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     L = _native.lib()
-    if precision == "fp8":      # the quantising pre-pass, then the block-scaled fp4 x fp8 GEMM (csrc/fql_gemm_mx4_f8.h)
+    if precision == "fp8":      # the quantising pre-pass, then the block-scaled fp4 x fp8 GEMM (csrc/fql_gemm_mx4_scaled.h)
         entry, ws = ("fql_moe_mx4_glu_fwd_q8" if gated else "fql_moe_mx4_fwd_q8",
                      L.fql_moe_mx4_f8_workspace_bytes(E, T, K, N, 2 if gated else 1))
-    elif precision == "fp4":    # the MXFP4 quantiser, then the block-scaled fp4 x fp4 GEMM (csrc/fql_gemm_mx4_f4.h)
+    elif precision == "fp4":    # the MXFP4 quantiser, then the block-scaled fp4 x fp4 GEMM (csrc/fql_gemm_mx4_scaled.h)
         entry, ws = ("fql_moe_mx4_glu_fwd_q4" if gated else "fql_moe_mx4_fwd_q4",
                      L.fql_moe_mx4_f4_workspace_bytes(E, T, K, N, 2 if gated else 1))
     else:

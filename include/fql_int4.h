@@ -943,7 +943,7 @@ FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e
                                   int out_dtype, int E, int T, int K, int N, void *stream);
 
 /* ---- MXFP4 expert weights over fp8 rows, on the block-scaled FP4 matrix cores (FQL_VERSION 360; INTEGRATION.md section 17,
- *      DESIGN.md section 27; csrc/fql_gemm_mx4_f8.h) ----
+ *      DESIGN.md section 27; csrc/fql_gemm_mx4_scaled.h) ----
  * The opt-in second mode of the MXFP4 forward; the bfloat16 entries above and their bits are unchanged.
  *   out[t][n] = act_scale[t] * ( sum_k e4m3(x8[t][k]) * W_e[n][k] ) (+ bias[e][n]),   blocks / scales_e8m0 as above.
  * The packed bytes and the E8M0 bytes go to v_mfma_scale_f32_32x32x64_f8f6f4 as they lie in memory (fp4 A operand with its
@@ -991,7 +991,7 @@ FQL_API int fql_moe_mx4_glu_fwd_q8(const uint8_t *blocks, const uint8_t *scales_
                                    float act_limit, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- MXFP4 expert weights over MXFP4 rows: both operands e2m1 with E8M0 block scales (FQL_VERSION 370; INTEGRATION.md
- *      section 17; csrc/fql_gemm_mx4_f4.h) ----
+ *      section 17; csrc/fql_gemm_mx4_scaled.h) ----
  * The opt-in third mode of the MXFP4 forward (W4A4); the entries above and their bits are unchanged.
  *   out[t][n] = sum_k X[t][k] * W_e[n][k] (+ bias[e][n]),  X[t][k] = e2m1(in_blocks) * 2^(in_scales_e8m0[t][k / 32] - 127).
  * The rows lie in the weights' own layout: in_blocks [T][K / 2] (even k in the low nibble), in_scales_e8m0 [T][K / 32].  Both

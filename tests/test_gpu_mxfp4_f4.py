@@ -1,5 +1,5 @@
 """MXFP4 expert weights over MXFP4 rows on the GPU (W4A4): ops.quantize_rows_mxfp4, ops.moe_forward_mxfp4_fp4 and
-``precision="fp4"`` of ops.moe_forward_mxfp4 / ops.moe_gated_forward_mxfp4 (csrc/fql_gemm_mx4_f4.h:
+``precision="fp4"`` of ops.moe_forward_mxfp4 / ops.moe_gated_forward_mxfp4 (csrc/fql_gemm_mx4_scaled.h:
 v_mfma_scale_f32_32x32x64_f8f6f4 with both operands e2m1 and their E8M0 scales), the layer MXFP4MoEFFN(precision="fp4") and
 the sparse block on it.  The reference for the rule is quantize.quantize_mxfp4 / dequantize_mxfp4 with float64 products.
 

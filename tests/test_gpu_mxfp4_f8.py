@@ -1,5 +1,5 @@
 """MXFP4 expert weights over fp8 rows on the GPU: ops.moe_forward_mxfp4_fp8 and ``precision="fp8"`` of
-ops.moe_forward_mxfp4 / ops.moe_gated_forward_mxfp4 (csrc/fql_gemm_mx4_f8.h: v_mfma_scale_f32_32x32x64_f8f6f4 on the packed
+ops.moe_forward_mxfp4 / ops.moe_gated_forward_mxfp4 (csrc/fql_gemm_mx4_scaled.h: v_mfma_scale_f32_32x32x64_f8f6f4 on the packed
 e2m1 bytes, their E8M0 scales and e4m3 activation rows), the layer MXFP4MoEFFN(precision="fp8") and the sparse block on it.
 
 Shapes: K in {32, 96, 256, 288} = 1, 3, 8 and 9 scale blocks (half an instruction; a half-filled second instruction; two

@@ -1,7 +1,7 @@
 """The decode kernels of the fp8-row and MXFP4-row precisions of the MXFP4 experts (csrc/fql_gemm_mx4_sdecode.h) on the GPU.
 The six entries pick the kernel from T; here fql_tune_set_mx4_scaled_decode_max_rows forces either kernel per mode.
 
-The contract is that the decode kernel returns THE SAME BITS as the tile kernel of its mode (mx4_f8_kernel / mx4_f4_kernel),
+The contract is that the decode kernel returns THE SAME BITS as the tile kernel of its mode (mx4_scaled_kernel<1 | 2, OUT>),
 so the main tests compare the two; the exactness tests stand without the tile kernel, so a mistake the two share cannot
 hide.
 

@@ -1,5 +1,5 @@
 // Probe of the fp4 (e2m1) A operand of v_mfma_scale_f32_32x32x64_f8f6f4 against an e4m3 B operand (cbsz = 4, blgp = 0), for
-// the MXFP4 fp8-row path (csrc/fql_gemm_mx4_f8.h).  One instruction on asymmetric exact data; every hypothesis is scored by
+// the MXFP4 fp8-row path (csrc/fql_gemm_mx4_scaled.h).  One instruction on asymmetric exact data; every hypothesis is scored by
 // its count of mismatching outputs, so exactly one line per question reads "0 / 1024":
 //   1. which (row, k) each nibble of a lane's 16 bytes holds, and how those 32 k pair with the 32 bytes of the B operand;
 //   2. which lane's scale byte applies to which row and block, and what op_sel selects;
@@ -7,7 +7,7 @@
 // hipcc --offload-arch=gfx950 -O3 -o mfma_f4_probe mfma_f4_probe.hip && ./mfma_f4_probe
 //
 // ./mfma_f4_probe f4f4: the same instruction with BOTH operands fp4 (cbsz = 4, blgp = 4), for the MXFP4-row path
-// (csrc/fql_gemm_mx4_f4.h), in the same style.  The A operand's map is the one measured above; the questions are B's:
+// (csrc/fql_gemm_mx4_scaled.h), in the same style.  The A operand's map is the one measured above; the questions are B's:
 //   1. which (column, k) each nibble of a B lane's 16 bytes holds;
 //   2. which byte of the B scale register op_sel selects, which lane's, and which block it scales;
 //   3. what B scale codes 0, 254 and 255 return, and whether 255 makes exactly the 32 outputs of its column NaN.

@@ -16,7 +16,11 @@ scored one); ``combine_any`` on four type pairs at N = 40 (16-byte accesses), 13
 without the addend and its weight, and the float32 ``combine`` on a misaligned ``y``; ``QuantizedSparseMoEBlock`` with
 default and with scored routing, float32 and bfloat16, every gradient; and, behind all of these so that their operands are
 the ones they always were, the four gated ops, the gated FFN layers and the sparse block (with a shared expert) for
-``activation="gelu_tanh"`` and ``"swiglu_clamp"`` in the three element types."""
+``activation="gelu_tanh"`` and ``"swiglu_clamp"`` in the three element types; and behind those the MXFP4 experts at K = 96
+(K % 64 == 32) and N = 40 on the same grouped table: ``moe_forward_mxfp4`` and ``moe_gated_forward_mxfp4`` in the three
+precisions, ``moe_forward_mxfp4_fp8`` and ``moe_forward_mxfp4_fp4``, float32 and bfloat16 rows, with and without a bias, each
+once on its decode kernel and once on its tile kernel (forced through the tuning hooks), then ``quantize_rows_mxfp4`` plain
+and gated and ``moe_backward_input_mxfp4``."""
 import argparse
 import hashlib
 import os
@@ -345,6 +349,54 @@ def calls(dev, fq, ops):
             out.backward(gy)
             return out.detach(), logits.detach(), x_.grad, m.gate.weight.grad
         yield f"QuantizedSparseMoEBlock {kind} shared", glu_block
+
+    # ---------------------------------------------------------------- the MXFP4 experts (behind everything else, as above)
+    # K = 96: K % 64 == 32, a half-filled last matrix instruction of the block-scaled kernels; N = 40: a partial 32-n block.
+    # Every forward runs once on its decode kernel and once on its tile kernel, forced through the tuning hooks.
+    K, N = 96, 40
+    Pm = torch.randint(0, 256, (E, N, K // 2), dtype=torch.uint8, generator=d.gen).to(dev)
+    Sm = torch.randint(118, 133, (E, N, K // 32), dtype=torch.uint8, generator=d.gen).to(dev)
+    x, gu, gy, biasm = d.randn(T, K), d.randn(T, 2 * K, scale=2.0), d.randn(T, N), d.randn(E, N)
+    x8, asc = ops.quantize_activations_fp8(x)
+    glu = dict(activation="swiglu_clamp", activation_alpha=1.702, activation_limit=7.0)
+
+    def forced(which, call):
+        def run():
+            from fused_int4_amd import _native
+            lib, rows = _native.lib(), 2 ** 31 - 1 if which == "decode" else 0
+            old = [lib.fql_tune_set_mx4_decode_max_rows(rows)] + [lib.fql_tune_set_mx4_scaled_decode_max_rows(m, rows) for m in (1, 2)]
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_mx4_decode_max_rows(old[0])
+                for m in (1, 2):
+                    lib.fql_tune_set_mx4_scaled_decode_max_rows(m, old[m])
+        return run
+
+    for which in ("decode", "tile"):
+        for btag, b in (("", None), (" bias", biasm)):
+            for dt in (F32, BF16):
+                for prec in ("bf16", "fp8", "fp4"):
+                    tag = f"{prec} {dt}{btag} {which}"
+                    yield f"moe_forward_mxfp4 {tag}", forced(which, lambda: ops.moe_forward_mxfp4(
+                        Pm, Sm, x.to(dt), tpe, offs, bias=b, precision=prec))
+                    yield f"moe_gated_forward_mxfp4 {tag}", forced(which, lambda: ops.moe_gated_forward_mxfp4(
+                        Pm, Sm, gu.to(dt), tpe, offs, bias=b, precision=prec, **glu))
+                    yield f"moe_forward_mxfp4 {tag} ->f16", forced(which, lambda: ops.moe_forward_mxfp4(
+                        Pm, Sm, x.to(dt), tpe, offs, bias=b, out_dtype=F16, precision=prec))
+            yield f"moe_forward_mxfp4_fp8{btag} {which}", forced(which, lambda: ops.moe_forward_mxfp4_fp8(
+                Pm, Sm, x8, asc, tpe, offs, bias=b))
+            yield f"moe_forward_mxfp4_fp8 bf16 unscaled{btag} {which}", forced(which, lambda: ops.moe_forward_mxfp4_fp8(
+                Pm, Sm, x8, None, tpe, offs, bias=b, out_dtype=BF16))
+            yield f"moe_forward_mxfp4_fp4{btag} {which}", forced(which, lambda: ops.moe_forward_mxfp4_fp4(
+                Pm, Sm, *ops.quantize_rows_mxfp4(x), tpe, offs, bias=b))
+            yield f"moe_forward_mxfp4_fp4 f16{btag} {which}", forced(which, lambda: ops.moe_forward_mxfp4_fp4(
+                Pm, Sm, *ops.quantize_rows_mxfp4(x), tpe, offs, bias=b, out_dtype=F16))
+    for dt in (F32, BF16):                   # (one kernel each: nothing to force)
+        yield f"quantize_rows_mxfp4 {dt}", lambda: ops.quantize_rows_mxfp4(x.to(dt))
+        yield f"quantize_rows_mxfp4 gated {dt}", lambda: ops.quantize_rows_mxfp4(gu.to(dt), **glu)
+        for do in (F32, BF16):
+            yield f"moe_backward_input_mxfp4 {dt}->{do}", lambda: ops.moe_backward_input_mxfp4(Pm, Sm, gy.to(dt), tpe, offs, out_dtype=do)
 
 
 def digest(t):

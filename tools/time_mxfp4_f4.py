@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the fp4 mode of the MXFP4 grouped ops (csrc/fql_gemm_mx4_f4.h: the block-scaled fp4 x fp4 matrix-core kernel and
+"""Time the fp4 mode of the MXFP4 grouped ops (csrc/fql_gemm_mx4_scaled.h: the block-scaled fp4 x fp4 matrix-core kernel and
 its MXFP4 quantiser) against the fp8 mode and the bfloat16 path of the same shape in the same job.
 
 The four shapes of DESIGN.md section 27's table, 1024 routed rows spread evenly: the gpt-oss-like ones (32 experts,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the fp8 mode of the MXFP4 grouped ops (csrc/fql_gemm_mx4_f8.h: the block-scaled fp4 x fp8 matrix-core kernel and
+"""Time the fp8 mode of the MXFP4 grouped ops (csrc/fql_gemm_mx4_scaled.h: the block-scaled fp4 x fp8 matrix-core kernel and
 its quantising pre-pass) against the bfloat16-path op of the same shape in the same job.
 
 The four shapes of DESIGN.md section 25, 1024 routed rows spread evenly: the gpt-oss-like ones (32 experts, 2880 -> 5760
