@@ -5,7 +5,7 @@ Drop-in for the Python surface of samy19980109/Fused-4-bit-Dequantize-Linear-CUD
 python/moe_int4_module.py and benchmark/moe_grouped_gemm/).
 """
 from .quantize import (quantize_weights, dequantize_weights, reference_quantized_linear, quantize_mxfp4,
-                       dequantize_mxfp4)
+                       dequantize_mxfp4, quantize_mxfp6, dequantize_mxfp6)
 from .module import QuantizedLinear
 from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN, QuantizedSparseMoEBlock, \
     MXFP4MoEFFN
@@ -19,5 +19,5 @@ __all__ = [
     "RoutingResult", "simulate_routing", "balanced_routing", "create_expert_inputs",
     "combine_expert_outputs", "dispatch_grouped", "dispatch_indices", "combine_grouped",
     "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN", "QuantizedSparseMoEBlock",
-    "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN",
+    "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN", "quantize_mxfp6", "dequantize_mxfp6",
 ]

@@ -1,20 +1,28 @@
 // Grouped GEMM on OCP MXFP4 expert weights on the block-scaled matrix cores, over fp8 (OCP e4m3) activation rows with one
-// float32 scale a row (ROWS = 1: include/fql_int4.h, fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8) or
-// over MXFP4 activation rows (ROWS = 2: fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4):
+// float32 scale a row (ROWS = 1: include/fql_int4.h, fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8),
+// over MXFP4 activation rows (ROWS = 2: fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4) or over MXFP6 (e2m3)
+// activation rows (ROWS = 3: fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6):
 //
 //   ROWS 1: out[t][n] = act_scale[t] * ( sum_k e4m3(x8[t][k]) * e2m1(code[e][n][k]) * 2^(s[e][n][k / 32] - 127) ) (+ bias[e][n])
 //   ROWS 2: out[t][n] = sum_k e2m1(xc[t][k]) 2^(xs[t][k / 32] - 127) * e2m1(code[e][n][k]) 2^(s[e][n][k / 32] - 127)  (+ bias[e][n])
+//   ROWS 3: the same with e2m3(xc[t][k]): x [T][3 K / 4], element i of block b in bits 6 i .. 6 i + 5 of the 24 bytes at 24 b
+//           (one little-endian 192-bit integer), code = sign << 5 | exponent << 3 | mantissa (bias 1), xscales [T][K / 32]
 //
 // blocks [E][N][K / 2] and scales [E][N][K / 32] as fql_gemm_mx4.h reads them; MXFP4 rows are in the SAME layout, x [T][K / 2]
 // (even k in the low nibble) and xscales [T][K / 32].  Nothing is dequantised: the packed bytes are the fp4 A operand of
 // v_mfma_scale_f32_32x32x64_f8f6f4 (cbsz = 4) and the checkpoint's E8M0 byte is its A scale; the rows are the B operand, e4m3
-// bytes (blgp = 0) with scale code 127 or packed e2m1 (blgp = 4) with their own scale byte.  The operand map, as
-// tools/micro/mfma_f4_probe.hip measured it (profiles/mfma_f4_probe.txt, profiles/mfma_f4f4_probe.txt), lane = (r = lane & 31,
-// h = lane >> 5):
+// bytes (blgp = 0) with scale code 127, packed e2m1 (blgp = 4) or packed e2m3 (blgp = 2) with their own scale byte.  The
+// operand map, as tools/micro/mfma_f4_probe.hip measured it (profiles/mfma_f4_probe.txt, profiles/mfma_f4f4_probe.txt,
+// profiles/mfma_f6_probe.txt), lane = (r = lane & 31, h = lane >> 5):
 //   * fp4 A: the lane's 16 bytes (registers 0 .. 3; 4 .. 7 are ignored) are row r, k = 32 h .. 32 h + 31 in memory order, the
 //     low nibble of a byte first: exactly the bytes of one scale block of a packed row.
 //   * e4m3 B: the lane's bytes 0 .. 15 are column r, k = 16 h .. 16 h + 15, bytes 16 .. 31 are k = 32 + 16 h .. + 15.
 //   * fp4 B mirrors fp4 A (column r, one scale block of a packed row; registers 4 .. 7 ignored): the two operands share slots.
+//   * e2m3 B: the lane's 24 bytes (registers 0 .. 5; 6 and 7 are ignored) are column r, k = 32 h + J in bits 6 J .. 6 J + 5 of
+//     the 24 bytes read as one little-endian integer: exactly the bytes of one scale block of an MXFP6 row, so the public
+//     layout is the instruction's and nothing is reordered.  Its scale is byte op_sel of the lane's own B scale register;
+//     scale code 255 makes the 32 outputs of its column NaN (zero codes on both sides included) and no other, codes 0 and
+//     254 are 2^-127 (the float32 subnormal comes back) and 2^127.
 //   * scale A / scale B: byte op_sel (each side has its own selector) of the lane's scale register scales the lane's own 32
 //     nibbles (row / column r, block h).
 //   * scale code 255 makes the outputs of its row NaN (zero codes included), an e4m3 NaN byte (0x7F / 0xFF) or a B scale
@@ -35,7 +43,10 @@
 //     thread p copies the ONE piece (row p >> 2, block p & 3) and its scale byte; x is 16-byte aligned and K % 32 == 0, so
 //     every piece is one aligned 16-byte load.  Rows are clamped into the expert's range: loads are unconditional.  All of
 //     it is written to LDS as loaded, double buffered: 2 x (8 + 8) KiB and 1 KiB of scale bytes (33 KiB) with e4m3 rows,
-//     2 x (8 + 4) KiB and 1.5 KiB (25.5 KiB) with MXFP4 rows; one workgroup barrier a stage.  Pieces past N or K are zero
+//     2 x (8 + 4) KiB and 1.5 KiB (25.5 KiB) with MXFP4 rows; one workgroup barrier a stage.  MXFP6 rows: 64 t x 96 bytes,
+//     thread p copies the ONE block (row p >> 2, block p & 3) of 24 bytes as three 8-byte words and its scale byte: x is
+//     8-byte aligned and a row is a multiple of 24 bytes, so every word is one aligned 8-byte load whatever K % 64 is (rows
+//     are 16-byte aligned only when K % 64 == 0: there is one form, not two); 2 x (8 + 6.75) KiB and 1.5 KiB (31 KiB).  Pieces past N or K are zero
 //     codes with scale code 127 on either side (their scale byte is not read; an absent block is never NaN) and zero e4m3
 //     bytes; K % 32 == 0 is all the kernel asks, so a half-filled last instruction (K % 64 == 32) and a partial last stage
 //     are the normal case (gpt-oss: K = 2880 = 22.5 stages).  An instruction whose 64 k lie past K entirely is not issued.
@@ -44,10 +55,17 @@
 //     rows of a fragment at the same c.  Four 64-byte rows fill a 256-byte bank row: row i of the group lies at byte
 //     64 (i & 3) + 16 (c ^ ((i >> 2) & 3)), and (i & 3, (i >> 2) & 3) takes 16 distinct values; two 128-byte rows fill one,
 //     and (t & 1, (t >> 1) & 7) does the same.  Either way the group covers the 16 slots once: conflict free.
+//   * MXFP6 image: word j (of 3) of block c (of 4) of row t is the uint2 at [j][c][t] of a plane of 64 + 8 rows, i.e. at byte
+//     576 (4 j + c) + 8 t of the buffer.  A ds_read_b64 is served in halves of 32 lanes; a half reads word j of block 2 s + h
+//     of 32 consecutive rows, 256 contiguous bytes = every bank once: conflict free.  A ds_write_b64 half is threads p .. p + 31
+//     = 8 consecutive rows x 4 blocks: block c lands at bank 16 (c + (t >> 3)) + 2 (t & 7) + (0, 1) mod 64 (576 bytes = 144 banks = 16 mod 64:
+//     that is what the 8 rows of padding are for; unpadded the four blocks would meet in the same 16 banks, 4-way), so the
+//     half covers the 64 banks once: conflict free.
 //   * A operand of instruction s (k = k0 + 64 s .. + 63): slot 2 s + h of row 32 b + r: one ds_read_b128.  Scale bytes lie in
 //     LDS as [h][row][s], so one 16-bit read per fragment and stage gives the lane both, byte s selected by op_sel.
 //   * B operand, shared by the wave's two n blocks: e4m3 slots 4 s + h and 4 s + 2 + h of row t, two ds_read_b128; MXFP4 slot
-//     2 s + h of row t, one, with the row's scale bytes read like the weights'.
+//     2 s + h of row t, one, with the row's scale bytes read like the weights'; MXFP6 the three words of block 2 s + h of row
+//     t, three ds_read_b64, the scale bytes as with MXFP4 rows.
 //   * The loads of a stage are issued TWO stages ahead of their use, into two register sets that alternate.
 //   * FIXED ORDER.  Stages in ascending k, instruction 0 then 1 inside a stage, one accumulator per output.  A row's
 //     result depends on its own bytes, its scales and its expert's weights only: the grouped call equals E one-expert calls
@@ -55,7 +73,7 @@
 //     covers (mx4_group_begin).
 //   * EPILOGUE, float32 (mx4_scaled_epilogue).  e4m3 rows: v = act_scale[t] * acc (one multiplication; act_scale == NULL:
 //     v = acc), with a bias v = fma(act_scale[t], acc, bias[e][n]) (one rounding); a NaN act_scale makes the whole row NaN
-//     (NaN * 0 is NaN).  MXFP4 rows: v = acc, with a bias v = acc + bias[e][n] (one addition).  Then the one rounding to
+//     (NaN * 0 is NaN).  MXFP4 and MXFP6 rows: v = acc, with a bias v = acc + bias[e][n] (one addition).  Then the one rounding to
 //     out's type (store_out4).
 #pragma once
 #include "fql_mx4_common.h"
@@ -91,8 +109,8 @@ __device__ __forceinline__ void mx4_scaled_epilogue(const v16f &acc, void *__res
     }
 }
 
-// ROWS: 1 e4m3 rows x [T][K] (xscales unused), 2 MXFP4 rows x [T][K / 2] (act_scale unused); OUT: element type of out,
-// rounded once in the epilogue.
+// ROWS: 1 e4m3 rows x [T][K] (xscales unused), 2 MXFP4 rows x [T][K / 2], 3 MXFP6 rows x [T][3 K / 4] (act_scale unused);
+// OUT: element type of out, rounded once in the epilogue.
 template <int ROWS, int OUT>
 __global__ __launch_bounds__(256) void mx4_scaled_kernel(
     const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ scales, const uint8_t *__restrict__ x,
@@ -101,13 +119,15 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4ScaledCfg;
-    constexpr int XS = ROWS == 1 ? 8 : 4;                          // 16-byte slots of an activation row of a stage
+    constexpr int XS = ROWS == 1 ? 8 : 4;                          // 16-byte slots of an activation row of a stage (ROWS 1, 2)
+    constexpr int XP = C::BT + 8;                                  // rows of a plane of the MXFP6 image, padded by 64 bytes
     int row_lo, cnt, t_blk;
     if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     __shared__ __attribute__((aligned(16))) uint4 wimg[2][C::BN][4];   // packed weight rows, 128 k = 64 bytes, slots swizzled
     __shared__ __attribute__((aligned(16))) uint4 ximg[2][C::BT][XS];  // activation rows as loaded, slots swizzled
     __shared__ __attribute__((aligned(4))) uint8_t simg[2][2][C::BN][2];   // E8M0 bytes: [h][n][s] = block 2 s + h of the stage (read in pairs)
-    __shared__ __attribute__((aligned(4))) uint8_t ximgs[2][2][C::BT][2];  // MXFP4 rows only (never referenced otherwise): theirs, [h][t][s]
+    __shared__ __attribute__((aligned(4))) uint8_t ximgs[2][2][C::BT][2];  // MXFP4 / MXFP6 rows only (never referenced otherwise): theirs, [h][t][s]
+    __shared__ __attribute__((aligned(8))) uint2 ximg6[2][3][4][XP];       // MXFP6 rows only: word j of block c of row t at [j][c][t]
 
     const int e = blockIdx.z;
     const int n0 = (int)blockIdx.x * C::BN;
@@ -123,6 +143,7 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
     // tile, slot xq) or the MXFP4 piece (row sn of the tile, block sc).  Rows are clamped into the expert's range.
     const int sn = tid >> 2, sc = tid & 3, xr = tid >> 3, xq = tid & 7;
     const uint8_t *wbase[2], *sbase[2], *xbase[ROWS == 1 ? 2 : 1], *xsbase = nullptr;
+    const int K34 = 3 * (K >> 2);                                  // bytes of an MXFP6 row
     bool n_ok[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -140,11 +161,17 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
         xbase[0] = x + tx * K2 + 16 * sc;
         xsbase = xscales + tx * KB + sc;
     }
+    if constexpr (ROWS == 3) {
+        const size_t tx = (size_t)(row_lo + (t_blk + sn < cnt ? t_blk + sn : cnt - 1));
+        xbase[0] = x + tx * K34 + 24 * sc;
+        xsbase = xscales + tx * KB + sc;
+    }
     const bool vec_x = (reinterpret_cast<uintptr_t>(x) & 15) == 0; // (e4m3 rows; K % 32 == 0: every row starts on a 16-byte boundary then)
 
     struct Stage {                                                 // what a thread holds of one stage between load and use
         uint4 w[2], x[ROWS == 1 ? 2 : 1];
-        int s[2], xs;                                              // (xs: MXFP4 rows only)
+        uint2 x6[3];                                               // (MXFP6 rows only: the three 8-byte words of the block)
+        int s[2], xs;                                              // (xs: MXFP4 / MXFP6 rows only)
     };
     auto load_stage = [&](Stage &st, int k0) {
         const bool k_ok = k0 + 32 * sc < K;
@@ -179,6 +206,16 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
                 st.xs = xsbase[k0 >> 5];
             }
         }
+        if constexpr (ROWS == 3) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) st.x6[j] = make_uint2(0u, 0u);
+            if (k_ok) {
+                const uint2 *p = reinterpret_cast<const uint2 *>(xbase[0] + 3 * (k0 >> 2));
+#pragma unroll
+                for (int j = 0; j < 3; ++j) st.x6[j] = p[j];
+                st.xs = xsbase[k0 >> 5];
+            }
+        }
     };
     auto store_stage = [&](const Stage &st, int buf) {             // registers -> LDS, bytes as loaded
 #pragma unroll
@@ -190,6 +227,11 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
         }
         if constexpr (ROWS == 2) {
             ximg[buf][sn][sc ^ ((sn >> 2) & 3)] = st.x[0];
+            ximgs[buf][sc & 1][sn][sc >> 1] = (uint8_t)st.xs;
+        }
+        if constexpr (ROWS == 3) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ximg6[buf][j][sc][sn] = st.x6[j];
             ximgs[buf][sc & 1][sn][sc >> 1] = (uint8_t)st.xs;
         }
     };
@@ -209,9 +251,12 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
             const int xsw = (tr >> 1) & 7;
             const uint4 x0 = ximg[buf][tr][(4 * s + h) ^ xsw], x1 = ximg[buf][tr][(4 * s + 2 + h) ^ xsw];
             bv = v8i{(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
-        } else {
+        } else if constexpr (ROWS == 2) {
             const uint4 x0 = ximg[buf][tr][(2 * s + h) ^ ((tr >> 2) & 3)];
             bv = v8i{(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, 0, 0, 0, 0};
+        } else {
+            const uint2 x0 = ximg6[buf][0][2 * s + h][tr], x1 = ximg6[buf][1][2 * s + h][tr], x2 = ximg6[buf][2][2 * s + h][tr];
+            bv = v8i{(int)x0.x, (int)x0.y, (int)x1.x, (int)x1.y, (int)x2.x, (int)x2.y, 0, 0};
         }
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
@@ -219,7 +264,8 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
             const uint4 a = wimg[buf][n][(2 * s + h) ^ ((n >> 2) & 3)];
             const v8i av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0};
             if constexpr (ROWS == 1) acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[b], 4, 0, s, sw[b], 0, 0x7F7F7F7F);
-            else acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[b], 4, 4, s, sw[b], s, sx);
+            else if constexpr (ROWS == 2) acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[b], 4, 4, s, sw[b], s, sx);
+            else acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc[b], 4, 2, s, sw[b], s, sx);
         }
     };
 
@@ -232,7 +278,7 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
 #pragma unroll
         for (int b = 0; b < 2; ++b)
             sw[b] = *reinterpret_cast<const unsigned short *>(&simg[buf][h][32 * (nb + b) + r][0]);
-        if constexpr (ROWS == 2) sx = *reinterpret_cast<const unsigned short *>(&ximgs[buf][h][tr][0]);
+        if constexpr (ROWS != 1) sx = *reinterpret_cast<const unsigned short *>(&ximgs[buf][h][tr][0]);
         step(std::integral_constant<int, 0>{}, buf, sw, sx);
         if (k0 + 64 < K) step(std::integral_constant<int, 1>{}, buf, sw, sx);
         if (k0 + C::BK < K) store_stage(other, (it + 1) & 1);      // (last read one stage ago, behind that stage's barrier)
@@ -254,7 +300,7 @@ __global__ __launch_bounds__(256) void mx4_scaled_kernel(
     if (!row_ok) return;
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
-    const float as = ROWS == 2 || act_scale == nullptr ? 1.0f : act_scale[t];
+    const float as = ROWS != 1 || act_scale == nullptr ? 1.0f : act_scale[t];
 #pragma unroll
     for (int b = 0; b < 2; ++b) mx4_scaled_epilogue<ROWS, OUT>(acc[b], out, t, N, n0 + 32 * (nb + b), h, vec, brow, act_scale, as);
 #endif

@@ -2,7 +2,8 @@
 // FEW rows an expert, as fql_gemm_mx4_decode.h is the decode form of mx4_kernel.
 //
 // mx4_sdecode_kernel<ROWS, OUT>: ROWS = 1: e4m3 rows [T][K] with act_scale [T]; ROWS = 2: MXFP4 rows [T][K / 2] with
-// in_scales [T][K / 32].  Workgroup = ONE wave = 32 weight rows n of one expert x one block of up to 32 rows t, for all of
+// in_scales [T][K / 32]; ROWS = 3: MXFP6 rows [T][3 K / 4] with in_scales [T][K / 32] (blgp = 2; a lane's fragment is the 24
+// bytes of block 2 s + h, three 8-byte loads: a row is 8-byte aligned whatever K is; 12 registers a ring slot).  Workgroup = ONE wave = 32 weight rows n of one expert x one block of up to 32 rows t, for all of
 // K.  No LDS, no barrier.  grid = (ceil(N / 32), ceil(T / 32), E (+ 1 with a table)); the workgroups of an expert without
 // rows in that block leave at once, a count above 32 is the next row block's, so the kernel is right for every T.
 //   * THE SAME BITS AS THE TILE KERNEL.  An element of the instruction's result depends on its own A row, its own B column,
@@ -45,7 +46,8 @@ struct Mx4SDecodeSlot {
     uint4 wq;                                          // the 16 bytes of scale block 2 s + h of the packed weight row
     uint8_t sc;                                        // its scale code
     uint4 x[ROWS == 1 ? 2 : 1];                        // e4m3: k0 + 16 h .. + 15 and k0 + 32 + 16 h .. + 15; MXFP4: block 2 s + h
-    uint8_t xs;                                        // MXFP4 rows: that block's scale code
+    uint2 x6[ROWS == 3 ? 3 : 1];                       // MXFP6: the three 8-byte words of block 2 s + h (x is not used then)
+    uint8_t xs;                                        // MXFP4 / MXFP6 rows: that block's scale code
 };
 
 // VEC: the rows' base is 16-byte aligned (every row and every fragment is, then: K % 32 == 0; MXFP4 rows always are).
@@ -56,7 +58,7 @@ __device__ __forceinline__ void mx4_sdecode_body(
     void *__restrict__ out, int e, int row_lo, int cnt, int t_blk, int K, int N)
 {
     static_assert(DEPTH % GROUP == 0, "the ring is refilled in whole groups");
-    static_assert(ROWS == 1 || VEC, "packed rows are 16-byte aligned");
+    static_assert(ROWS == 1 || VEC, "packed rows are 16-byte aligned (MXFP4) or read in 8-byte words (MXFP6)");
     using Slot = Mx4SDecodeSlot<ROWS>;
     const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
     const int n0 = (int)blockIdx.x * Mx4SDecodeCfg::BN;
@@ -68,8 +70,8 @@ __device__ __forceinline__ void mx4_sdecode_body(
     const uint8_t *sbase = scales + wrow * KB;
     const bool row_ok = t_blk + r < cnt;
     const int t = row_lo + (row_ok ? t_blk + r : cnt - 1);
-    const uint8_t *xrow = x + (size_t)t * (ROWS == 1 ? K : K2);
-    const uint8_t *xsrow = ROWS == 2 ? xscales + (size_t)t * KB : nullptr;
+    const uint8_t *xrow = x + (size_t)t * (ROWS == 1 ? K : ROWS == 2 ? K2 : 3 * (K >> 2));
+    const uint8_t *xsrow = ROWS != 1 ? xscales + (size_t)t * KB : nullptr;
 
     auto load16 = [&](const uint8_t *p) {
         if constexpr (VEC) {
@@ -91,8 +93,13 @@ __device__ __forceinline__ void mx4_sdecode_body(
             if constexpr (decltype(BOTH)::value) sl.x[1] = load16(xrow + 64 * s + 32 + 16 * hx);
             else sl.x[1] = make_uint4(0u, 0u, 0u, 0u);
             sl.xs = 127;
-        } else {
+        } else if constexpr (ROWS == 2) {
             sl.x[0] = *reinterpret_cast<const uint4 *>(xrow + 32 * s + 16 * hx);
+            sl.xs = xsrow[2 * s + hx];
+        } else {                                                   // (a block is 24 bytes at a multiple of 8: three 8-byte loads)
+            const uint2 *p = reinterpret_cast<const uint2 *>(xrow + 48 * s + 24 * hx);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) sl.x6[j] = p[j];
             sl.xs = xsrow[2 * s + hx];
         }
     };
@@ -107,9 +114,12 @@ __device__ __forceinline__ void mx4_sdecode_body(
             const v8i bv = {(int)sl.x[0].x, (int)sl.x[0].y, (int)sl.x[0].z, (int)sl.x[0].w,
                             (int)sl.x[1].x, (int)sl.x[1].y, (int)sl.x[1].z, (int)sl.x[1].w};
             acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 0, 0, (int)sl.sc, 0, 0x7F7F7F7F);
-        } else {
+        } else if constexpr (ROWS == 2) {
             const v8i bv = {(int)sl.x[0].x, (int)sl.x[0].y, (int)sl.x[0].z, (int)sl.x[0].w, 0, 0, 0, 0};
             acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 4, 0, (int)sl.sc, 0, (int)sl.xs);
+        } else {
+            const v8i bv = {(int)sl.x6[0].x, (int)sl.x6[0].y, (int)sl.x6[1].x, (int)sl.x6[1].y, (int)sl.x6[2].x, (int)sl.x6[2].y, 0, 0};
+            acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 2, 0, (int)sl.sc, 0, (int)sl.xs);
         }
     };
 
@@ -158,6 +168,11 @@ __device__ __forceinline__ void mx4_sdecode_body(
             tail.wq = make_uint4(0u, 0u, 0u, 0u);
             tail.sc = 127;
             if constexpr (ROWS == 2) { tail.x[0] = make_uint4(0u, 0u, 0u, 0u); tail.xs = 127; }
+            if constexpr (ROWS == 3) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) tail.x6[j] = make_uint2(0u, 0u);
+                tail.xs = 127;
+            }
         }
         consume(tail);
     }
@@ -166,7 +181,7 @@ __device__ __forceinline__ void mx4_sdecode_body(
     if (!row_ok) return;
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
-    const float as = ROWS == 2 || act_scale == nullptr ? 1.0f : act_scale[t];
+    const float as = ROWS != 1 || act_scale == nullptr ? 1.0f : act_scale[t];
     mx4_scaled_epilogue<ROWS, OUT>(acc, out, t, N, n0, h, vec, brow, act_scale, as);
 }
 
@@ -182,7 +197,7 @@ __global__ __launch_bounds__(64) void mx4_sdecode_kernel(
     int row_lo, cnt, t_blk;
     if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
     const int e = blockIdx.z;
-    if (ROWS == 2 || (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+    if (ROWS != 1 || (reinterpret_cast<uintptr_t>(x) & 15) == 0)
         mx4_sdecode_body<ROWS, OUT, true, C::DEPTH, C::GROUP>(blocks, scales, x, xscales, act_scale, bias, out, e, row_lo, cnt, t_blk, K, N);
     else if constexpr (ROWS == 1)
         mx4_sdecode_body<ROWS, OUT, false, 1, 1>(blocks, scales, x, xscales, act_scale, bias, out, e, row_lo, cnt, t_blk, K, N);

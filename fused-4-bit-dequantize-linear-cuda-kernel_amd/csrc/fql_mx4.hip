@@ -1,8 +1,8 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h): the bfloat16 entries fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
 // fql_moe_mx4_bwd_input (fql_gemm_mx4.h, fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h), the block-scaled entries on fp8 rows
-// fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 and on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 (one tile and one
-// decode kernel for both, fql_gemm_mx4_scaled.h and fql_gemm_mx4_sdecode.h) and the row pre-passes with fql_mx4_quantize_rows
-// (fql_mx4_quant.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8, on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 and on MXFP6 rows
+// fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
+// fql_gemm_mx4_sdecode.h) and the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -28,10 +28,10 @@ struct Mx4Call {
     void *out;
     int E, T, K, N;
     const float *act_scale = nullptr;  // [T] or NULL (fp8 rows only)
-    const uint8_t *row_scales = nullptr;  // [T][K / 32] E8M0 (MXFP4 rows only)
+    const uint8_t *row_scales = nullptr;  // [T][K / 32] E8M0 (MXFP4 and MXFP6 rows only)
 };
 
-enum { ROWS_FLOAT = 0, ROWS_E4M3 = 1, ROWS_MXFP4 = 2 };   // what c.rows holds; 1 and 2 are the kernels' ROWS and the hooks' mode
+enum { ROWS_FLOAT = 0, ROWS_E4M3 = 1, ROWS_MXFP4 = 2, ROWS_MXFP6 = 3 };   // what c.rows holds; 1 .. 3 are the kernels' ROWS, 1 and 2 the scaled hooks' mode
 
 // f(std::integral_constant<int, OUT>) for the element type of a call's output (valid_dtype() has been checked)
 template <class F>
@@ -63,12 +63,14 @@ dim3 mx4_grid(const Mx4Call &c, int cols, int bc, int bt)
 #define FQL_MX4_DECODE_MAX_ROWS 512    /* rows (T) up to which the decode kernel runs: the largest count of the sweep at which it wins */
 #define FQL_MX4_F8_DECODE_MAX_ROWS 8   /* rows (T) up to which the fp8-row decode kernel runs: the largest count of the sweep up to which it wins at every point of both shapes */
 #define FQL_MX4_F4_DECODE_MAX_ROWS 8   /* ... the MXFP4-row decode kernel: the same rule, the same count */
-int g_mx4_decode_max_rows[3] = {FQL_MX4_DECODE_MAX_ROWS, FQL_MX4_F8_DECODE_MAX_ROWS, FQL_MX4_F4_DECODE_MAX_ROWS};   // by rows kind
+#define FQL_MX4_F6_DECODE_MAX_ROWS 8   /* ... the MXFP6-row decode kernel: the same rule */
+int g_mx4_decode_max_rows[4] = {FQL_MX4_DECODE_MAX_ROWS, FQL_MX4_F8_DECODE_MAX_ROWS, FQL_MX4_F4_DECODE_MAX_ROWS,
+                                FQL_MX4_F6_DECODE_MAX_ROWS};   // by rows kind
 
 bool mx4_use_decode(int rows_kind, int T)
 {
     static_assert(Mx4DecodeCfg::BT == Mx4SDecodeCfg::BT, "one bound on the grid's y for both decode kernels");
-    return T > 0 && T <= g_mx4_decode_max_rows[rows_kind] && (T + Mx4DecodeCfg::BT - 1) / Mx4DecodeCfg::BT <= 65535;
+    return T > 0 && T <= g_mx4_decode_max_rows[rows_kind] && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;   // (no overflow at a hook's T = INT_MAX)
 }
 
 // The bfloat16 forward: c.rows is [T][K] float32 or bfloat16.
@@ -88,7 +90,7 @@ int launch_mx4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
 }
 
 // The block-scaled forward: c.rows is [T][K] e4m3 bytes with c.act_scale (ROWS_E4M3), or [T][K / 2] packed e2m1 with
-// c.row_scales (ROWS_MXFP4).
+// c.row_scales (ROWS_MXFP4), or [T][3 K / 4] packed e2m3 with c.row_scales (ROWS_MXFP6).
 template <int ROWS>
 int launch_mx4_scaled(int out_dtype, const Mx4Call &c, hipStream_t st)
 {
@@ -107,7 +109,8 @@ int launch_mx4_scaled(int out_dtype, const Mx4Call &c, hipStream_t st)
 
 // The checks every entry point shares, in the documented order; `rows` is inputs or gate_up.  FQL_OK with *empty set: an
 // empty call, nothing to launch.  rows_kind other than ROWS_FLOAT: the rows are bytes (in_dtype is not looked at); ROWS_MXFP4:
-// packed rows [T][K / 2], 16-byte aligned, with c.row_scales.
+// packed rows [T][K / 2], 16-byte aligned, with c.row_scales; ROWS_MXFP6: packed rows [T][3 K / 4], 8-byte aligned (a row is a
+// multiple of 24 bytes, so every block of every row is), with c.row_scales.
 int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *empty, int rows_kind = ROWS_FLOAT)
 {
     const bool byte_rows = rows_kind != ROWS_FLOAT;
@@ -118,7 +121,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     if ((!byte_rows && in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
     if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
     if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
-    if (rows_kind == ROWS_MXFP4 && !c.row_scales) return FQL_ERR_NULL_POINTER;
+    if ((rows_kind == ROWS_MXFP4 || rows_kind == ROWS_MXFP6) && !c.row_scales) return FQL_ERR_NULL_POINTER;
     if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
     if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
     if (c.E > 65534) return FQL_ERR_BAD_SHAPE;                        // (the grid's z: the experts and the coverage slice)
@@ -128,6 +131,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
     if (rows_kind == ROWS_MXFP4 && !aligned16(c.rows)) return FQL_ERR_ALIGNMENT;
+    if (rows_kind == ROWS_MXFP6 && (reinterpret_cast<uintptr_t>(c.rows) & 7)) return FQL_ERR_ALIGNMENT;
     return FQL_OK;
 }
 
@@ -152,7 +156,8 @@ const Mx4Act kMx4Plain{false, FQL_ACT_SILU, 0.0f, 0.0f};
 // [T][K / 2], then their scales [T][K / 32].  mx4_ws_rows: the bytes of the rows, what lies behind them starts there.
 size_t mx4_ws_rows(int rows_kind, int T, int K)
 {
-    return round16(rows_kind == ROWS_FLOAT ? (size_t)T * K * 2 : rows_kind == ROWS_E4M3 ? (size_t)T * K : (size_t)T * (K / 2));
+    return round16(rows_kind == ROWS_FLOAT ? (size_t)T * K * 2 : rows_kind == ROWS_E4M3 ? (size_t)T * K :
+                   rows_kind == ROWS_MXFP4 ? (size_t)T * (K / 2) : (size_t)T * (K / 4) * 3);
 }
 size_t mx4_ws_bytes(int rows_kind, int T, int K)
 {
@@ -160,7 +165,8 @@ size_t mx4_ws_bytes(int rows_kind, int T, int K)
 }
 
 // The pre-pass that writes rows of kind ROWS: rows (float rows [T][K], or gated: gate_up [T][2 K]) -> q, with `side` what
-// goes with them (act_scale, the rows' scale bytes; none with bfloat16 rows, which exist gated only).
+// goes with them (act_scale, the rows' scale bytes; none with bfloat16 rows, which exist gated only).  Packed MXFP6 rows are
+// [T][3 K / 4].
 template <int ROWS>
 int launch_mx4_quant(const void *rows, int in_dtype, const Mx4Act &a, void *q, void *side, int T, int K, hipStream_t st)
 {
@@ -173,6 +179,9 @@ int launch_mx4_quant(const void *rows, int in_dtype, const Mx4Act &a, void *q, v
                 return launch(mx4_glu_kernel<IN>, grid, dim3(256), 0, st, rows, static_cast<unsigned short *>(q), T, K, a.kind, a.alpha, a.limit);
             else if constexpr (ROWS == ROWS_E4M3)
                 return launch(mx4_q8_kernel<IN, GATED>, grid, dim3(256), 0, st, rows, static_cast<uint8_t *>(q), static_cast<float *>(side),
+                              T, K, a.kind, a.alpha, a.limit);
+            else if constexpr (ROWS == ROWS_MXFP6)
+                return launch(mx4_q6_kernel<IN, GATED>, grid, dim3(256), 0, st, rows, static_cast<uint8_t *>(q), static_cast<uint8_t *>(side),
                               T, K, a.kind, a.alpha, a.limit);
             else
                 return launch(mx4_q4_kernel<IN, GATED>, grid, dim3(256), 0, st, rows, static_cast<uint8_t *>(q), static_cast<uint8_t *>(side),
@@ -342,6 +351,40 @@ FQL_API int fql_moe_mx4_glu_fwd_q4(const uint8_t *blocks, const uint8_t *scales_
                                      out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
 }
 
+FQL_API size_t fql_moe_mx4_f6_workspace_bytes(int E, int T, int K, int N, int mode)
+{
+    (void)E; (void)N;
+    if ((mode != 1 && mode != 2) || T <= 0 || K <= 0) return 0;
+    return mx4_ws_bytes(ROWS_MXFP6, T, K);                            // packed rows [T][3 K / 4], their scales [T][K / 32]
+}
+
+FQL_API int fql_moe_mx4_fwd_f6(const uint8_t *blocks, const uint8_t *scales_e8m0, const uint8_t *in_codes,
+                               const uint8_t *in_scales_e8m0, const float *bias, const int32_t *tokens_per_expert,
+                               const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    return mx4_scaled_fwd<ROWS_MXFP6>({blocks, scales_e8m0, in_codes, bias, tokens_per_expert, input_offsets, out, E, T, K, N, nullptr,
+                                       in_scales_e8m0}, out_dtype, stream);
+}
+
+FQL_API int fql_moe_mx4_fwd_q6(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                               int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mx4_quant_fwd<ROWS_MXFP6>({blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, in_dtype,
+                                     out_dtype, kMx4Plain, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_mx4_glu_fwd_q6(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                   float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mx4_quant_fwd<ROWS_MXFP6>({blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, in_dtype,
+                                     out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+}
+
 FQL_API int fql_mx4_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
                                   uint8_t *out_blocks, uint8_t *out_scales, int T, int K, void *stream)
 {
@@ -353,6 +396,18 @@ FQL_API int fql_mx4_quantize_rows(const void *rows, int in_dtype, int gated, int
     const int rc = mx4_check(c, in_dtype, FQL_DTYPE_F32, a.ok(), &empty);
     if (rc != FQL_OK || empty) return rc;
     return launch_mx4_quant<ROWS_MXFP4>(rows, in_dtype, a, out_blocks, out_scales, T, K, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_mx6_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
+                                  uint8_t *out_codes, uint8_t *out_scales, int T, int K, void *stream)
+{
+    // as fql_mx4_quantize_rows: out_codes stands for `blocks` (non-NULL, 16-byte aligned) and `out`, out_scales for `scales`
+    const Mx4Call c{out_codes, out_scales, rows, nullptr, nullptr, nullptr, out_codes, 1, T, K, 1};
+    const Mx4Act a{gated != 0, activation, act_alpha, act_limit};
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, FQL_DTYPE_F32, a.ok(), &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_mx4_quant<ROWS_MXFP6>(rows, in_dtype, a, out_codes, out_scales, T, K, static_cast<hipStream_t>(stream));
 }
 
 FQL_API int fql_tune_set_mx4_decode_max_rows(int rows)
@@ -381,6 +436,19 @@ FQL_API int fql_tune_mx4_scaled_kernel(int mode, int E, int T, int K, int N)
     (void)E; (void)K; (void)N;
     if (mode != ROWS_E4M3 && mode != ROWS_MXFP4) return -1;
     return mx4_use_decode(mode, T) ? 1 : 0;
+}
+
+FQL_API int fql_tune_set_mx4_f6_decode_max_rows(int rows)
+{
+    const int old = g_mx4_decode_max_rows[ROWS_MXFP6];
+    if (rows >= 0) g_mx4_decode_max_rows[ROWS_MXFP6] = rows;
+    return old;
+}
+
+FQL_API int fql_tune_mx4_f6_kernel(int E, int T, int K, int N)
+{
+    (void)E; (void)K; (void)N;
+    return mx4_use_decode(ROWS_MXFP6, T) ? 1 : 0;
 }
 
 }  // extern "C"

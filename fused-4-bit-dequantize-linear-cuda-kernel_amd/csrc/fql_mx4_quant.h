@@ -1,6 +1,6 @@
 // The row pre-passes of the MXFP4 expert kernels (include/fql_int4.h; DESIGN.md sections 25, 27, 28): each turns float32 or
 // bfloat16 rows [T][K], or (GATED) act_glu_mul(gate_up[t][k], gate_up[t][K + k]) of gate_up [T][2 K] in float32, into the
-// operand its GEMM reads, in the caller's workspace.  The two quantisers share one loader, mx4_load8.
+// operand its GEMM reads, in the caller's workspace.  The three quantisers share one loader, mx4_load8.
 //
 // mx4_glu_kernel: the streaming pre-pass of the gated bfloat16 form.  h[t][k] = act_glu_mul(gate_up[t][k], gate_up[t][F + k])
 // rounded once to bfloat16 into [T][F]; mx4_kernel then reads h as a bfloat16 operand.  (Forming h on load would evaluate
@@ -18,6 +18,9 @@
 // included: no float32 operation whose result could be flushed or rounded twice).  Each lane stores one dword of codes
 // (a quad: 16 contiguous bytes = one block), lane 0 of the quad the scale byte.  A block with a non-finite value gets zero
 // codes and scale code 255.  GATED: v is evaluated once.
+//
+// mx4_q6_kernel: MXFP6 (e2m3) rows, quantize.quantize_mxfp6's rule bit for bit in the same way (mx4_e2m3_code; the scale code
+// is mx4_q4_kernel's: both formats' largest exponent is 2); the comment at the kernel has the packing.
 #pragma once
 #include "fql_common.h"
 #include "fql_act_quant.h"
@@ -244,5 +247,85 @@ __global__ __launch_bounds__(256) void mx4_q4_kernel(const void *__restrict__ ro
     }
     *reinterpret_cast<uint32_t *>(qb + (size_t)t * (K >> 1) + (k >> 1)) = word;
     if ((threadIdx.x & 3) == 0) qs[(size_t)t * (K >> 5) + (k >> 5)] = (uint8_t)code;
+#endif
+}
+
+// e2m3 code (sign << 5 | exponent << 3 | mantissa, bias 1) of the float32 with bits `bits` (finite) under scale code c of
+// its own block, as mx4_e2m1_code: to nearest even on the grid whose step is 1/8 below 2, 1/4 below 4 and 1/2 above,
+// saturated at 7.5 (7.75 is a tie that goes up to 8 and saturates), the sign kept.  F is in units of 2^-22, so the three
+// steps are 2^19, 2^20 and 2^21 units.
+__host__ __device__ inline uint32_t mx4_e2m3_code(uint32_t bits, int c)
+{
+    const uint32_t sign = (bits >> 26) & 32u, ex = (bits >> 23) & 255u, man = bits & 0x7FFFFFu;
+    const uint32_t M = ex ? (man | 0x800000u) : man;
+    const int sh = (int)(ex ? ex : 1u) - 1 - c;                    // (<= 1: the block's own maximum has ex - c <= 2)
+    uint32_t F, sticky = 0u;
+    if (sh >= 0) F = M << sh;
+    else if (sh > -32) { F = M >> -sh; sticky = (M & ((1u << -sh) - 1u)) != 0u; }
+    else { F = 0u; sticky = M != 0u; }
+    const int s = F >= (1u << 24) ? 21 : F >= (1u << 23) ? 20 : 19;
+    uint32_t q = F >> s;
+    const uint32_t rem = F & ((1u << s) - 1u), half = 1u << (s - 1);
+    if (rem > half || (rem == half && (sticky || (q & 1u)))) ++q;
+    uint32_t ev = q << (s - 19);                                   // eight times the rounded value: 0 .. 64
+    if (ev > 60u) ev = 60u;
+    return sign | (ev < 16u ? ev : ev < 32u ? (ev >> 1) + 8u : (ev >> 2) + 16u);
+}
+
+// rows [T][K] (GATED: gate_up [T][2 K]) of float32 (IN == 0) or bfloat16 -> qc [T][3 K / 4] packed e2m3 (MXFP6: element i of
+// block b is bits 6 i .. 6 i + 5 of the 24 bytes at 24 b, little endian), qs [T][K / 32] E8M0: quantize.quantize_mxfp6's rule
+// bit for bit for every finite input, mx4_q4_kernel's skeleton.  One thread 8 consecutive k = 48 bits of its block; lane j of
+// a quad then holds bits 48 j .. 48 j + 47, and lanes 0 .. 2 each store one 8-byte word of the block, (P_j >> 16 j) |
+// (P_(j + 1) << (48 - 16 j)), with the next lane's bits from two __shfl_down.  qc is 8-byte aligned at least (every entry
+// asks for 16) and a block starts at a multiple of 24 bytes of it, so the stores are aligned.  A block with a non-finite
+// value gets zero codes and scale code 255.
+template <int IN, bool GATED>
+__global__ __launch_bounds__(256) void mx4_q6_kernel(const void *__restrict__ rows, uint8_t *__restrict__ qc,
+                                                     uint8_t *__restrict__ qs, int T, int K, int kind, float alpha, float limit)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int per_row = K >> 3;
+    const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (item >= (long long)T * per_row) return;                    // (whole quads: T * K / 8 is a multiple of 4)
+    const long long t = item / per_row;
+    const int k = (int)(item - t * per_row) * 8;
+    constexpr int es = IN == 0 ? 4 : 2;
+    const char *row = reinterpret_cast<const char *>(rows) + (size_t)t * (GATED ? 2 : 1) * K * es;
+    const bool vec = (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
+    float v[8];
+    mx4_load8<IN>(row + (size_t)k * es, vec, v);
+    if constexpr (GATED) {
+        float u[8];
+        mx4_load8<IN>(row + (size_t)(K + k) * es, vec, u);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = act_glu_mul(kind, alpha, limit, v[c], u[c]);
+    }
+    uint32_t mu = 0u;                                              // max |v| as bits (an exponent field of 255 wins)
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t u = __float_as_uint(v[c]) & 0x7FFFFFFFu;
+        mu = u > mu ? u : mu;
+    }
+#pragma unroll
+    for (int o = 1; o < 4; o <<= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)mu, o, 64);
+        mu = other > mu ? other : mu;
+    }
+    const bool bad = mu >= 0x7F800000u;
+    const int code = bad ? 255 : mx4_block_scale_code(mu);
+    unsigned long long P = 0ull;
+    if (!bad) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) P |= (unsigned long long)mx4_e2m3_code(__float_as_uint(v[c]), code) << (6 * c);
+    }
+    const int j = threadIdx.x & 3;
+    const uint32_t nlo = (uint32_t)__shfl_down((int)(uint32_t)P, 1, 64), nhi = (uint32_t)__shfl_down((int)(uint32_t)(P >> 32), 1, 64);
+    const unsigned long long Pn = ((unsigned long long)nhi << 32) | nlo;
+    if (j < 3) {
+        const unsigned long long w = (P >> (16 * j)) | (Pn << (48 - 16 * j));
+        *reinterpret_cast<uint2 *>(qc + (size_t)t * (3 * (K >> 2)) + 24 * (k >> 5) + 8 * j) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    } else {
+        qs[(size_t)t * (K >> 5) + (k >> 5)] = (uint8_t)code;
+    }
 #endif
 }

@@ -524,7 +524,11 @@ class MXFP4MoEFFN(nn.Module):
 
     ``precision="fp4"`` (W4A4) quantises the rows to MXFP4 as well, per block of 32 by ``quantize.quantize_mxfp4``'s rule
     (``ops.quantize_rows_mxfp4``), and contracts e2m1 with e2m1: half the activation traffic of the fp8 mode again, at the
-    format's price (about 1.1e-1 relative on the rows against 3e-2 for e4m3).  Inference only and configuration, as fp8."""
+    format's price (about 1.1e-1 relative on the rows against 3e-2 for e4m3).  Inference only and configuration, as fp8.
+
+    ``precision="fp6"`` quantises the rows to MXFP6 instead (e2m3 elements, per block of 32 by ``quantize.quantize_mxfp6``'s
+    rule, ``ops.quantize_rows_mxfp6``) and contracts e2m1 with e2m3 at the matrix rate of the fp4 mode: three quarters of the
+    fp8 mode's row bytes at about its error (2.8e-2 relative on Gaussian rows).  Inference only and configuration, as fp8."""
 
     group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
 
@@ -532,8 +536,8 @@ class MXFP4MoEFFN(nn.Module):
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
                  activation_dtype=None, input_grad: bool = False, precision: str = "bf16"):
         super().__init__()
-        if precision not in ("bf16", "fp8", "fp4"):
-            raise ValueError(f"precision must be 'bf16', 'fp8' or 'fp4', got {precision!r}")
+        if precision not in ("bf16", "fp8", "fp6", "fp4"):
+            raise ValueError(f"precision must be 'bf16', 'fp8', 'fp6' or 'fp4', got {precision!r}")
         if precision != "bf16" and input_grad:
             raise ValueError(f"precision='{precision}' has no backward: it cannot be combined with input_grad=True")
         if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0:

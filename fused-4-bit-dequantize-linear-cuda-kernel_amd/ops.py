@@ -543,9 +543,9 @@ def _check_mxfp4(blocks, scales, dev, K):
 
 
 def _mxfp4_precision(precision):
-    """``precision`` of the MXFP4 ops, validated: "bf16" (the default), "fp8" or "fp4"."""
-    if precision not in ("bf16", "fp8", "fp4"):
-        raise ValueError(f"precision must be 'bf16', 'fp8' or 'fp4' for MXFP4 weights, got {precision!r}")
+    """``precision`` of the MXFP4 ops, validated: "bf16" (the default), "fp8", "fp6" or "fp4"."""
+    if precision not in ("bf16", "fp8", "fp6", "fp4"):
+        raise ValueError(f"precision must be 'bf16', 'fp8', 'fp6' or 'fp4' for MXFP4 weights, got {precision!r}")
     return precision
 
 
@@ -569,6 +569,9 @@ def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offset
     elif precision == "fp4":    # the MXFP4 quantiser, then the block-scaled fp4 x fp4 GEMM (csrc/fql_gemm_mx4_scaled.h)
         entry, ws = ("fql_moe_mx4_glu_fwd_q4" if gated else "fql_moe_mx4_fwd_q4",
                      L.fql_moe_mx4_f4_workspace_bytes(E, T, K, N, 2 if gated else 1))
+    elif precision == "fp6":    # the MXFP6 quantiser, then the block-scaled fp4 x e2m3 GEMM (csrc/fql_gemm_mx4_scaled.h)
+        entry, ws = ("fql_moe_mx4_glu_fwd_q6" if gated else "fql_moe_mx4_fwd_q6",
+                     L.fql_moe_mx4_f6_workspace_bytes(E, T, K, N, 2 if gated else 1))
     else:
         entry, ws = "fql_moe_mx4_glu_fwd" if gated else "fql_moe_mx4_fwd", L.fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated))
     _launch(entry, dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype], bias, tpe, offs, out, _DTYPES[out_dtype],
@@ -592,7 +595,11 @@ def moe_forward_mxfp4(blocks, scales, inputs, tokens_per_expert, input_offsets, 
 
     ``precision="fp4"`` (W4A4) quantises the rows to MXFP4 themselves, per block of 32 by ``quantize.quantize_mxfp4``'s rule
     (``quantize_rows_mxfp4``, inside a fused pre-pass), and contracts e2m1 with e2m1, each side with its E8M0 scales:
-    ``out[t] = W_e @ mxfp4(inputs[t]) (+ bias[e])``.  The format error of the rows is about 1.1e-1 (relative Frobenius)."""
+    ``out[t] = W_e @ mxfp4(inputs[t]) (+ bias[e])``.  The format error of the rows is about 1.1e-1 (relative Frobenius).
+
+    ``precision="fp6"`` quantises the rows to MXFP6 (e2m3 elements, per block of 32 by ``quantize.quantize_mxfp6``'s rule:
+    ``quantize_rows_mxfp6``, inside a fused pre-pass) and contracts e2m1 with e2m3 at the same matrix rate as ``"fp4"``:
+    ``out[t] = W_e @ mxfp6(inputs[t]) (+ bias[e])``.  The format error of Gaussian rows is about 2.8e-2."""
     _forward_only("moe_forward_mxfp4", inputs, bias)
     precision = _mxfp4_precision(precision)
     K = inputs.shape[1] if inputs.dim() == 2 else 0
@@ -610,7 +617,8 @@ def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_of
 
     ``precision="fp8"``: the float32 ``h = act(...)`` is quantised per row to e4m3 by the pre-pass instead (never stored as
     floats) and contracted on the block-scaled FP4 matrix cores, as in ``moe_forward_mxfp4``.  ``precision="fp4"``: ``h`` is
-    evaluated once in float32 and quantised to MXFP4 per block of 32 (``quantize_rows_mxfp4(gate_up, activation=...)``)."""
+    evaluated once in float32 and quantised to MXFP4 per block of 32 (``quantize_rows_mxfp4(gate_up, activation=...)``);
+    ``precision="fp6"``: the same with MXFP6 rows (``quantize_rows_mxfp6(gate_up, activation=...)``)."""
     _forward_only("moe_gated_forward_mxfp4", gate_up, bias)
     precision = _mxfp4_precision(precision)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
@@ -1180,6 +1188,63 @@ def moe_forward_mxfp4_fp4(blocks, scales, in_blocks, in_scales, tokens_per_exper
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     _launch("fql_moe_mx4_fwd_f4", dev, blocks, scales, in_blocks.contiguous(), in_scales.contiguous(), bias, tpe, offs, out,
             _DTYPES[out_dtype], E, T, K, N, ws_bytes=_native.lib().fql_moe_mx4_f4_workspace_bytes(E, T, K, N, 0))
+    return out
+
+
+def quantize_rows_mxfp6(rows, activation=None, activation_alpha=1.702, activation_limit=7.0):
+    """Rows to MXFP6 (e2m3) on the GPU, the quantiser of ``precision="fp6"`` on its own: ``rows`` [T, K] float32 or bfloat16
+    (CUDA, K % 32 == 0) -> ``(codes uint8 [T, 3K/4], scales uint8 [T, K/32])``, bit for bit ``quantize.quantize_mxfp6`` for
+    every finite input.  A block that holds an inf or a NaN gets zero codes and scale code 255 (a NaN output row of the
+    GEMM).  With ``activation`` given, ``rows`` is ``gate_up`` [T, 2K] and what is quantised is ``h = act(gate_up[:, :K],
+    gate_up[:, K:])`` (``activation_of``), evaluated once in float32.  Forward only."""
+    _forward_only("quantize_rows_mxfp6", rows)
+    gated = activation is not None
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit) if gated else ("silu", 0.0, 0.0)
+    if not rows.is_cuda or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("ops.quantize_rows_mxfp6: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: "
+                           "cast it yourself)")
+    T, width = rows.shape
+    if width % (64 if gated else 32) != 0 or width == 0:
+        raise RuntimeError("gate_up must be [T, 2K] with K % 32 == 0" if gated else "rows must be [T, K] with K % 32 == 0")
+    K = width // 2 if gated else width
+    dev = rows.device
+    codes = torch.empty((T, K // 4 * 3), dtype=torch.uint8, device=dev)
+    scales = torch.empty((T, K // 32), dtype=torch.uint8, device=dev)
+    _launch("fql_mx6_quantize_rows", dev, rows.contiguous(), _DTYPES[rows.dtype], int(gated), _ACTIVATIONS[kind], act_alpha,
+            act_limit, codes, scales, T, K)
+    return codes, scales
+
+
+def moe_forward_mxfp4_fp6(blocks, scales, in_codes, in_scales, tokens_per_expert, input_offsets, bias=None,
+                          out_dtype=torch.float32):
+    """The grouped GEMM on OCP MXFP4 expert weights over rows that are already MXFP6 (e2m3 elements with E8M0 block scales)
+    on the block-scaled matrix cores, at the FP4 rate: ``out[t] = W_e @ X[t] (+ bias[e])``.  ``blocks`` / ``scales`` as
+    ``moe_forward_mxfp4`` takes them; ``in_codes`` uint8 [T, 3K/4] (``quantize.pack_mxfp6``'s layout) and ``in_scales`` uint8
+    [T, K/32] (``quantize_rows_mxfp6`` or ``quantize.quantize_mxfp6``); ``bias`` [E, N] float32 (optional).  Returns [T, N]
+    in ``out_dtype``; rows no expert covers are zero; an ``in_scales`` byte of 255 makes its row NaN.  ``in_codes`` must be
+    8-byte aligned (a contiguous tensor that is not is copied).  Forward only.  Small batches
+    (T up to the library's fp6 decode threshold) take a one-wave decode kernel that returns the same bits as the tile
+    kernel: the result does not depend on T."""
+    _forward_only("moe_forward_mxfp4_fp6", bias)
+    for name, t in (("in_codes", in_codes), ("in_scales", in_scales)):
+        if not t.is_cuda or t.dim() != 2 or t.dtype != torch.uint8:
+            raise RuntimeError(f"ops.moe_forward_mxfp4_fp6: {name} must be a CUDA uint8 2-D tensor")
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    T = in_codes.shape[0]
+    dev = in_codes.device
+    if in_codes.shape[1] % 24 != 0 or in_scales.device != dev or tuple(in_scales.shape) != (T, in_codes.shape[1] // 24):
+        raise RuntimeError("in_codes must be [T, 3K/4] and in_scales [T, K/32] with K % 32 == 0, on one device")
+    K = in_codes.shape[1] // 3 * 4
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    bias = _check_bias(bias, N, dev, E)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    in_codes = in_codes.contiguous()
+    if in_codes.data_ptr() % 8 != 0:
+        in_codes = in_codes.clone()
+    _launch("fql_moe_mx4_fwd_f6", dev, blocks, scales, in_codes, in_scales.contiguous(), bias, tpe, offs, out,
+            _DTYPES[out_dtype], E, T, K, N, ws_bytes=_native.lib().fql_moe_mx4_f6_workspace_bytes(E, T, K, N, 0))
     return out
 
 

@@ -13,7 +13,8 @@ shape ``[N]``.  These run on whatever device the tensors live on; on a GPU,
 ``dequantize_weights`` uses the HIP kernel of the extension.
 
 A second frozen format for the MoE experts, OCP MXFP4 (``quantize_mxfp4`` / ``dequantize_mxfp4``, pure torch): the same
-byte layout with e2m1 codes in the nibbles and one E8M0 power-of-two scale byte per 32 consecutive inputs.
+byte layout with e2m1 codes in the nibbles and one E8M0 power-of-two scale byte per 32 consecutive inputs.  Activation rows
+can also be OCP MXFP6 (``quantize_mxfp6`` / ``dequantize_mxfp6``): e2m3 codes, 32 of them in 24 bytes, the same scales.
 """
 from __future__ import annotations
 
@@ -21,7 +22,8 @@ import torch
 import torch.nn.functional as F
 
 __all__ = ["quantize_weights", "dequantize_weights", "reference_quantized_linear",
-           "pack_nibbles", "unpack_nibbles", "quantize_mxfp4", "dequantize_mxfp4", "MXFP4_VALUES"]
+           "pack_nibbles", "unpack_nibbles", "quantize_mxfp4", "dequantize_mxfp4", "MXFP4_VALUES",
+           "pack_mxfp6", "unpack_mxfp6", "quantize_mxfp6", "dequantize_mxfp6", "MXFP6_VALUES"]
 
 
 def pack_nibbles(q: torch.Tensor) -> torch.Tensor:
@@ -147,3 +149,68 @@ def dequantize_mxfp4(blocks: torch.Tensor, scales: torch.Tensor) -> torch.Tensor
     table = torch.tensor(MXFP4_VALUES, dtype=torch.float32, device=blocks.device)
     w = table[codes.long()].reshape(*blocks.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
     return (w * mxfp4_scale_values(scales).unsqueeze(-1)).reshape(*blocks.shape[:-1], K)
+
+
+# ---- OCP MXFP6 (e2m3) rows: 32 six-bit codes in 24 bytes, one E8M0 scale byte per 32 consecutive inputs
+
+# code = sign << 5 | exponent << 3 | mantissa, bias 1: subnormals m / 8, largest value 7.5, no inf or NaN
+MXFP6_VALUES = tuple((-1.0 if c & 32 else 1.0) * ((c & 7) / 8 if (c >> 3) & 3 == 0 else (1 + (c & 7) / 8) * 2.0 ** (((c >> 3) & 3) - 1))
+                     for c in range(64))
+
+
+def pack_mxfp6(codes: torch.Tensor) -> torch.Tensor:
+    """[..., K] uint8 codes in 0..63 (K % 32 == 0) -> [..., 3K/4] bytes: element i of block b is bits 6 i .. 6 i + 5 of the
+    24 bytes at 24 b read as one little-endian integer.  Four codes fill three bytes."""
+    if codes.dtype != torch.uint8 or codes.shape[-1] % MXFP4_BLOCK != 0:
+        raise ValueError("codes must be uint8 [..., K] with K % 32 == 0")
+    c = codes.reshape(*codes.shape[:-1], -1, 4).to(torch.int32)
+    word = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)
+    out = torch.stack([word & 255, (word >> 8) & 255, word >> 16], dim=-1).to(torch.uint8)
+    return out.reshape(*codes.shape[:-1], codes.shape[-1] // 4 * 3)
+
+
+def unpack_mxfp6(packed: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`pack_mxfp6`: [..., 3K/4] bytes -> [..., K] uint8 codes."""
+    if packed.dtype != torch.uint8 or packed.shape[-1] % 24 != 0:
+        raise ValueError("packed must be uint8 [..., 3K/4] with K % 32 == 0")
+    b = packed.reshape(*packed.shape[:-1], -1, 3).to(torch.int32)
+    word = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    out = torch.stack([word & 63, (word >> 6) & 63, (word >> 12) & 63, word >> 18], dim=-1).to(torch.uint8)
+    return out.reshape(*packed.shape[:-1], packed.shape[-1] // 3 * 4)
+
+
+def quantize_mxfp6(x: torch.Tensor):
+    """``[..., T, K]`` (K % 32 == 0) -> ``(codes uint8 [..., T, 3K/4], scales uint8 [..., T, K/32])`` by the OCP MX rule with
+    e2m3 elements: per block of 32 consecutive inputs ``shared = floor(log2(amax)) - 2`` (2 = e2m3's largest exponent),
+    clamped to [-127, 127], scale code ``shared + 127``; the elements are ``x / 2^shared`` rounded to nearest even on the
+    e2m3 grid (steps of 1/8 below 2, 1/4 below 4, 1/2 above) and saturated to +-7.5, the sign kept (a negative value that
+    rounds to zero is code 32).  An all-zero block gets scale code 127 and zero elements.  A non-finite input raises
+    ``ValueError``.  Computed in float64."""
+    if x.dim() < 2 or x.shape[-1] % MXFP4_BLOCK != 0:
+        raise ValueError("x must be [..., T, K] with K % 32 == 0")
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("quantize_mxfp6: the values must be finite")
+    K = x.shape[-1]
+    v64 = x.detach().to(torch.float64).reshape(*x.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = v64.abs().amax(dim=-1, keepdim=True)
+    _, ex = torch.frexp(amax)                                   # amax = m * 2^ex, m in [0.5, 1): floor(log2) = ex - 1
+    shared = torch.where(amax == 0, torch.zeros_like(ex), ex - 1 - 2).clamp(-127, 127)
+    v = torch.ldexp(v64.abs(), -shared)                         # exact in float64
+    q = torch.where(v < 2, torch.round(v * 8) / 8, torch.where(v < 4, torch.round(v * 4) / 4, torch.round(v * 2) / 2)).clamp(max=7.5)
+    mag = torch.where(q < 2, q * 8, torch.where(q < 4, q * 4 + 8, q * 2 + 16)).to(torch.uint8)
+    codes = (mag | (torch.signbit(v64).to(torch.uint8) << 5)).reshape(*x.shape[:-1], K)
+    scales = (shared + 127).to(torch.uint8).reshape(*x.shape[:-1], K // MXFP4_BLOCK)
+    return pack_mxfp6(codes), scales
+
+
+def dequantize_mxfp6(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """``(codes [..., T, 3K/4], scales [..., T, K/32])`` uint8 -> ``[..., T, K]`` float32: the 64-entry table times the
+    block's scale.  Exact, up to float32's own range."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError("codes and scales must be uint8")
+    if codes.shape[-1] % 24 != 0 or tuple(scales.shape) != tuple(codes.shape[:-1]) + (codes.shape[-1] // 24,):
+        raise ValueError("codes must be [..., T, 3K/4] and scales [..., T, K/32]")
+    K = codes.shape[-1] // 3 * 4
+    table = torch.tensor(MXFP6_VALUES, dtype=torch.float32, device=codes.device)
+    w = table[unpack_mxfp6(codes).long()].reshape(*codes.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return (w * mxfp4_scale_values(scales).unsqueeze(-1)).reshape(*codes.shape[:-1], K)

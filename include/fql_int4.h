@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 390 /* 0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 400 /* 0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1043,6 +1043,60 @@ FQL_API int fql_moe_mx4_glu_fwd_q4(const uint8_t *blocks, const uint8_t *scales_
                                    float act_limit, void *workspace, size_t workspace_bytes, void *stream);
 FQL_API int fql_mx4_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
                                   uint8_t *out_blocks, uint8_t *out_scales, int T, int K, void *stream);
+
+/* ---- MXFP4 expert weights over MXFP6 rows: e2m3 rows with E8M0 block scales (FQL_VERSION 400; INTEGRATION.md section 17,
+ *      DESIGN.md section 34; csrc/fql_gemm_mx4_scaled.h) ----
+ * The opt-in fourth mode of the MXFP4 forward; the entries above and their bits are unchanged.
+ *   out[t][n] = sum_k X[t][k] * W_e[n][k] (+ bias[e][n]),  X[t][k] = e2m3(in_codes) * 2^(in_scales_e8m0[t][k / 32] - 127).
+ * The row format: in_codes [T][3 K / 4]; block b of row t is the 24 bytes at 24 b of the row, and element i of the block
+ * (k = 32 b + i) is bits 6 i .. 6 i + 5 of those 24 bytes read as one little-endian 192-bit integer.  A code is sign << 5 |
+ * exponent << 3 | mantissa: e2m3 with bias 1, subnormals m / 8, largest value 7.5, no inf or NaN.  in_scales_e8m0 [T][K / 32]
+ * as for MXFP4 rows.  A block goes to v_mfma_scale_f32_32x32x64_f8f6f4 as it lies in memory (weights cbsz = 4, rows blgp = 2,
+ * each with its scale byte; measured, profiles/mfma_f6_probe.txt); the instruction runs at the rate of the MXFP4-row mode.
+ * Order, accumulation, epilogue, the table, the decode form and the independence of rows are those of the MXFP4-row entries
+ * (FQL_VERSION 370 / 390): the grouped call equals E one-expert calls bit for bit and the tile and decode kernels return the
+ * same bits.  Any K % 32 == 0, any N >= 1.
+ * fql_moe_mx4_fwd_f6:     rows already MXFP6.  No workspace (mode 0: 0 bytes, the arguments may be NULL / 0).
+ * fql_moe_mx4_fwd_q6:     inputs [T][K] float32 or bfloat16 (widened), quantised by a streaming pre-pass into the workspace
+ *                         (mode 1) by the rule below; then the call above on those bytes.
+ * fql_moe_mx4_glu_fwd_q6: the same on h[t][k] = act(gate_up[t][k], gate_up[t][K + k]) evaluated once in float32 from gate_up
+ *                         [T][2K] float32 or bfloat16 (mode 2); h itself is never stored.
+ * fql_mx6_quantize_rows:  the quantiser alone: rows [T][K] (gated != 0: gate_up [T][2K] with the activation arguments, which
+ *                         are not looked at otherwise) -> out_codes [T][3 K / 4], out_scales [T][K / 32].
+ *   The rule (quantize_mxfp6 of the Python package bit for bit, for every finite input, float32 subnormals included): per
+ *   block of 32 consecutive k, shared = floor(log2(max|v|)) - 2 clamped to [-127, 127], scale code shared + 127 (127 for an
+ *   all-zero block); elements v / 2^shared to nearest even on the e2m3 grid, saturated at +-7.5, the sign kept (a negative
+ *   value that rounds to zero is code 32).
+ *   Non-finite values: a block of a row that holds an inf or a NaN gets zero codes and scale code 255.  A scale code 255 on
+ *   the activation side makes exactly that output row NaN, on the weight side exactly the outputs of its weight row, for the
+ *   rows of its expert.  Scale codes 0 and 254 are 2^-127 and 2^127 on both sides; sums past the float32 range are infinite.
+ *   float16 rows are refused (FQL_ERR_DTYPE) as in fql_moe_mx4_fwd.
+ *   Workspace: fql_moe_mx4_f6_workspace_bytes(E, T, K, N, mode), mode 0 (rows already MXFP6): 0; mode 1 (float rows) and 2
+ *   (gated): the codes [T][3 K / 4] and their scales [T][K / 32], each rounded up to 16 bytes; 16-byte aligned.  0 for T or K
+ *   of 0.
+ *   Return codes, in this order and all before any HIP call (fql_moe_mx4_fwd's): FQL_ERR_BAD_SHAPE (E <= 0, T < 0, K <= 0,
+ *   N < 0; glu / gated: an unknown activation, or for a kind other than silu a non-finite act_alpha / act_limit or
+ *   act_limit <= 0); FQL_ERR_ODD_K; FQL_ERR_BAD_SHAPE (K % 32 != 0); FQL_ERR_DTYPE (q6 and quantize_rows: in_dtype not
+ *   FQL_DTYPE_F32 / _BF16; the GEMMs: out_dtype outside FQL_DTYPE_*); T == 0 or N == 0: FQL_OK with nothing launched;
+ *   FQL_ERR_NULL_POINTER (blocks, scales_e8m0, the rows, out; f6: in_scales_e8m0; one of the table's two arrays alone;
+ *   quantize_rows: rows, out_codes, out_scales); FQL_ERR_BAD_SHAPE (no table with E != 1, E > 65534, T > 4194240);
+ *   FQL_ERR_ALIGNMENT (blocks not 16-byte aligned; float rows / out not aligned to their element, bias not to 4 bytes; f6:
+ *   in_codes not 8-byte aligned (a row is a multiple of 24 bytes, so every block then is), in_scales_e8m0 needs none;
+ *   quantize_rows: out_codes not 16-byte aligned); FQL_ERR_WORKSPACE (q6: NULL, misaligned or short); FQL_ERR_LAUNCH. */
+FQL_API size_t fql_moe_mx4_f6_workspace_bytes(int E, int T, int K, int N, int mode);
+FQL_API int fql_moe_mx4_fwd_f6(const uint8_t *blocks, const uint8_t *scales_e8m0, const uint8_t *in_codes,
+                               const uint8_t *in_scales_e8m0, const float *bias, const int32_t *tokens_per_expert,
+                               const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                               void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_fwd_q6(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out,
+                               int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_glu_fwd_q6(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                   float act_limit, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_mx6_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
+                                  uint8_t *out_codes, uint8_t *out_scales, int T, int K, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -65,6 +65,12 @@ FQL_API int fql_tune_set_mx4_scaled_decode_max_rows(int mode, int rows);
 /* 0: the mode's entries would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
 FQL_API int fql_tune_mx4_scaled_kernel(int mode, int E, int T, int K, int N);
 
+/* The pair of the MXFP6-row entries (fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6; fql_int4.h, FQL_VERSION 400), with a threshold of
+ * its own.  (Mode 3 of the pair above stays an unknown mode.)  The setter returns the previous value; a negative `rows` changes nothing. */
+FQL_API int fql_tune_set_mx4_f6_decode_max_rows(int rows);
+/* 0: those entries would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
+FQL_API int fql_tune_mx4_f6_kernel(int E, int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

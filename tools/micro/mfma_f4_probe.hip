@@ -11,6 +11,12 @@
 //   1. which (column, k) each nibble of a B lane's 16 bytes holds;
 //   2. which byte of the B scale register op_sel selects, which lane's, and which block it scales;
 //   3. what B scale codes 0, 254 and 255 return, and whether 255 makes exactly the 32 outputs of its column NaN.
+//
+// ./mfma_f4_probe f4f6: the fp4 A operand against a 6-bit B operand (cbsz = 4, blgp = 2: e2m3), for the MXFP6-row path
+// (csrc/fql_gemm_mx4_scaled.h).  B is six registers a lane, 192 bits = 32 fields of 6.  The questions are B's again:
+//   1. which (column, k) the field at bits 6 J .. 6 J + 5 of a B lane's 24 bytes (one little-endian integer) holds;
+//   2. which byte of the B scale register op_sel selects, which lane's, and which block it scales;
+//   3. what B scale codes 0, 254 and 255 return, and whether 255 makes exactly the 32 outputs of its column NaN.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -121,10 +127,12 @@ static void derive_map(int pair[2][32], bool hi_first)
 }
 
 static int main_f4f4();
+static int main_f4f6();
 
 int main(int argc, char **argv)
 {
     if (argc > 1 && !strcmp(argv[1], "f4f4")) return main_f4f4();
+    if (argc > 1 && !strcmp(argv[1], "f4f6")) return main_f4f6();
     srand(11);
     int pair[2][32];
     derive_map(pair, false);
@@ -334,6 +342,182 @@ static int main_f4f4()
         if (!zero_b) b[0] = 0x02;
         sb[lane] = scode * 0x01010101u;
         const std::vector<float> D = run44(a, b, sa, sb, 0, 0);
+        int nans = 0, nan_col = 0;
+        for (int l = 0; l < 64; ++l) for (int r = 0; r < 16; ++r)
+            if (std::isnan(D[l * 16 + r])) { ++nans; nan_col += (l & 31) == (lane & 31); }
+        uint32_t bits0;
+        memcpy(&bits0, &D[0], 4);
+        printf("%-62s D[row0][col0] = %g (0x%08x)  D[row0][col1] = %g   NaNs %d (in the column of the code: %d)\n", name, D[0], bits0,
+               D[16], nans, nan_col);
+    };
+    special("B scale 127, B[col 0][k 0] = 1", 127, false, false, 0);
+    special("B scale 0,   B[col 0][k 0] = 1", 0, false, false, 0);
+    special("B scale 1,   B[col 0][k 0] = 1", 1, false, false, 0);
+    special("B scale 254, B[col 0][k 0] = 1", 254, false, false, 0);
+    special("B scale 255, B[col 0][k 0] = 1", 255, false, false, 0);
+    special("B scale 255, B col 0 all zero codes", 255, true, false, 0);
+    special("B scale 255, B col 0 all zero codes, A all zero codes", 255, true, true, 0);
+    special("B scale 255 in lane 37 (col 5, half 1), all codes zero", 255, true, true, 37);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fp4 x e2m3 (cbsz = 4, blgp = 2).  a: 64 lanes x 16 bytes (registers 4 .. 7 are `junk`), b: 64 lanes x 24 bytes (registers
+// 6 and 7 are `junk`); sa, sb: one dword of four scale bytes a lane for each side.
+template <int OPA, int OPB>
+__global__ void one46(const uint8_t *a, const uint8_t *b, const uint32_t *sa, const uint32_t *sb, float *d, int junk)
+{
+    const int l = threadIdx.x;
+    v8i av, bv;
+    for (int i = 0; i < 4; ++i) { av[i] = ((const int *)a)[l * 4 + i]; av[4 + i] = junk; }
+    for (int i = 0; i < 6; ++i) bv[i] = ((const int *)b)[l * 6 + i];
+    bv[6] = junk; bv[7] = junk;
+    v16f acc;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 4, 2, OPA, (int)sa[l], OPB, (int)sb[l]);
+    for (int r = 0; r < 16; ++r) d[l * 16 + r] = acc[r];
+}
+
+static std::vector<float> run46(const std::vector<uint8_t> &A, const std::vector<uint8_t> &B, const std::vector<uint32_t> &SA,
+                                const std::vector<uint32_t> &SB, int opb, int junk)
+{
+    uint8_t *da, *db; uint32_t *dsa, *dsb; float *dd;
+    hipMalloc(&da, 1024); hipMalloc(&db, 1536); hipMalloc(&dsa, 256); hipMalloc(&dsb, 256); hipMalloc(&dd, 64 * 16 * 4);
+    hipMemcpy(da, A.data(), 1024, hipMemcpyHostToDevice); hipMemcpy(db, B.data(), 1536, hipMemcpyHostToDevice);
+    hipMemcpy(dsa, SA.data(), 256, hipMemcpyHostToDevice); hipMemcpy(dsb, SB.data(), 256, hipMemcpyHostToDevice);
+    switch (opb) {
+    case 0: hipLaunchKernelGGL((one46<1, 0>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, dd, junk); break;
+    case 1: hipLaunchKernelGGL((one46<2, 1>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, dd, junk); break;
+    case 2: hipLaunchKernelGGL((one46<3, 2>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, dd, junk); break;
+    default: hipLaunchKernelGGL((one46<0, 3>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, dd, junk); break;
+    }
+    std::vector<float> D(64 * 16);
+    if (hipMemcpy(D.data(), dd, 64 * 16 * 4, hipMemcpyDeviceToHost) != hipSuccess) { printf("HIP error\n"); exit(1); }
+    hipFree(da); hipFree(db); hipFree(dsa); hipFree(dsb); hipFree(dd);
+    return D;
+}
+
+static float e2m3_to_float(int c)
+{
+    const int e = (c >> 3) & 3, m = c & 7;
+    const float v = e == 0 ? m / 8.0f : ldexpf(1.0f + m / 8.0f, e - 1);
+    return (c & 32) ? -v : v;
+}
+// field J (bits 6 J .. 6 J + 5 of the 24 bytes at p read as one little-endian integer)
+static int get6(const uint8_t *p, int J)
+{
+    const int bit = 6 * J, w = p[bit >> 3] | (bit + 8 < 192 ? p[(bit >> 3) + 1] << 8 : 0);
+    return (w >> (bit & 7)) & 63;
+}
+static void set6(uint8_t *p, int J, int c)
+{
+    const int bit = 6 * J, lo = bit & 7;
+    p[bit >> 3] = (uint8_t)((p[bit >> 3] & ~(63 << lo)) | (c << lo));
+    if (lo > 2) p[(bit >> 3) + 1] = (uint8_t)((p[(bit >> 3) + 1] & ~(63 >> (8 - lo))) | (c >> (8 - lo)));
+}
+
+// A as measured.  B hypothesis: field J of lane (col, h) is k = bmap[h][J]; its scale is byte sbyte of lane
+//   0: 32 h + col (the lane's own)  1: col  2: 32 + col  3: 32 (k >> 5) + col (the lane of k's block).
+static int score46(const std::vector<float> &D, const std::vector<uint8_t> &A, const std::vector<uint8_t> &B,
+                   const std::vector<uint32_t> &SA, const std::vector<uint32_t> &SB, int opa, const int bmap[2][32],
+                   int lane_rule, int sbyte)
+{
+    int bad = 0;
+    for (int l = 0; l < 64; ++l) for (int r = 0; r < 16; ++r) {
+        const int col = l & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+        double av[64], bv[64];
+        for (int H = 0; H < 2; ++H) for (int J = 0; J < 32; ++J) {
+            const uint8_t ab = A[(H * 32 + row) * 16 + (J >> 1)];
+            av[32 * H + J] = ldexp((double)e2m1_to_float((J & 1) ? ab >> 4 : ab & 15), (int)((SA[H * 32 + row] >> (8 * opa)) & 255) - 127);
+            const int k = bmap[H][J];
+            const int sl = lane_rule == 0 ? H * 32 + col : lane_rule == 1 ? col : lane_rule == 2 ? 32 + col : 32 * (k >> 5) + col;
+            bv[k] = ldexp((double)e2m3_to_float(get6(&B[(H * 32 + col) * 24], J)), (int)((SB[sl] >> (8 * sbyte)) & 255) - 127);
+        }
+        double ref = 0;
+        for (int k = 0; k < 64; ++k) ref += av[k] * bv[k];
+        if (ref != (double)D[l * 16 + r]) ++bad;
+    }
+    return bad;
+}
+
+// One-hot map of B, as derive_bmap: A row i holds 1.0 at k = 32 H + i alone; B column c holds 1.0 (e2m3 code 8) in field
+// J = c of its lane of half h alone.  D[row i][col c] is 1 exactly where field c of a B lane of half h is k = 32 H + i; any
+// other value (a field that straddles the instruction's own boundaries reads as another number) marks the field -2.
+static void derive_bmap6(int bmap[2][32])
+{
+    const std::vector<uint32_t> S(64, 0x7F7F7F7Fu);
+    for (int h = 0; h < 2; ++h) for (int J = 0; J < 32; ++J) bmap[h][J] = -1;
+    for (int h = 0; h < 2; ++h) for (int H = 0; H < 2; ++H) {
+        std::vector<uint8_t> A(1024, 0), B(1536, 0);
+        for (int i = 0; i < 32; ++i) A[(H * 32 + i) * 16 + (i >> 1)] = (uint8_t)(0x02 << (4 * (i & 1)));
+        for (int c = 0; c < 32; ++c) set6(&B[(h * 32 + c) * 24], c, 8);
+        const std::vector<float> D = run46(A, B, S, S, 0, 0);
+        for (int l = 0; l < 64; ++l) for (int r = 0; r < 16; ++r) {
+            const int col = l & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+            if (D[l * 16 + r] == 1.0f) bmap[h][col] = bmap[h][col] == -1 ? 32 * H + row : -2;       // (-2: met twice)
+            else if (D[l * 16 + r] != 0.0f) bmap[h][col] = -2;
+        }
+    }
+}
+
+static int main_f4f6()
+{
+    srand(37);
+    int bmap[2][32];
+    derive_bmap6(bmap);
+    for (int h = 0; h < 2; ++h) {
+        printf("e2m3 B lane half %d, field J (bits 6 J .. 6 J + 5 of the lane's 24 bytes, little endian) is k:", h);
+        for (int J = 0; J < 32; ++J) {
+            if (J % 16 == 0) printf("\n   ");
+            if (bmap[h][J] < 0) printf(" J%-2d->?? ", J); else printf(" J%-2d->%-2d", J, bmap[h][J]);
+        }
+        printf("\n");
+    }
+    bool mirror = true;
+    for (int h = 0; h < 2; ++h) for (int J = 0; J < 32; ++J) {
+        mirror = mirror && bmap[h][J] == 32 * h + J;
+        if (bmap[h][J] < 0) bmap[h][J] = 32 * h + J;
+    }
+    printf("B lane (r, h) holds column r, k = 32 h + J in field J: %s\n", mirror ? "yes" : "NO");
+
+    // every code on both sides (16 of e2m1, 64 of e2m3); a different scale code 125 .. 129 in every byte of every lane's two
+    // scale registers.  A product is a multiple of 2^-4, a scaled one of 2^-8, and 64 of them stay below 2^24 of those:
+    // every float32 sum is exact in any order.
+    std::vector<uint8_t> A(1024), B(1536);
+    std::vector<uint32_t> SA(64), SB(64);
+    for (auto &v : A) v = (uint8_t)(rand() & 255);
+    for (auto &v : B) v = (uint8_t)(rand() & 255);
+    for (auto &v : SA) { v = 0; for (int i = 0; i < 4; ++i) v |= (uint32_t)(125 + rand() % 5) << (8 * i); }
+    for (auto &v : SB) { v = 0; for (int i = 0; i < 4; ++i) v |= (uint32_t)(125 + rand() % 5) << (8 * i); }
+    static const char *rules[4] = {"lane 32 h + col", "lane col", "lane 32 + col", "lane 32 (k >> 5) + col"};
+    for (int opb = 0; opb < 4; ++opb) {
+        const int opa = (opb + 1) & 3;
+        const std::vector<float> D = run46(A, B, SA, SB, opb, 0x5A5A5A5A);
+        int best = 1025;
+        for (int rule = 0; rule < 4; ++rule) for (int sb = 0; sb < 4; ++sb) {
+            if (mirror && rule == 3) continue;                    // (the same hypothesis as rule 0 under this map)
+            const int bad = score46(D, A, B, SA, SB, opa, bmap, rule, sb);
+            if (bad < best) best = bad;
+            if (bad < 64)
+                printf("op_sel A %d B %d: B scale = byte %d of %-22s mismatches %4d / 1024\n", opa, opb, sb, rules[rule], bad);
+        }
+        printf("op_sel A %d B %d: best hypothesis has %d mismatches\n", opa, opb, best);
+        if (opb == 0) {
+            const std::vector<float> D2 = run46(A, B, SA, SB, 0, 0x13572468);
+            int diff = 0;
+            for (int i = 0; i < 1024; ++i) diff += D[i] != D2[i];
+            printf("registers 4 .. 7 of the fp4 operand and 6, 7 of the e2m3 operand changed: %d outputs differ\n", diff);
+        }
+    }
+
+    // specials: B = 1.0 (code 8) in field 0 of lane `col 0, half 0` only, zero elsewhere; A = 1.0 everywhere, unit scales;
+    // the B scale code under test in every byte of one lane's B scale register
+    auto special = [&](const char *name, uint32_t scode, bool zero_b, bool zero_a, int lane) {
+        std::vector<uint8_t> a(1024, zero_a ? 0x00 : 0x22), b(1536, 0);
+        std::vector<uint32_t> sa(64, 0x7F7F7F7Fu), sb(64, 0x7F7F7F7Fu);
+        if (!zero_b) set6(&b[0], 0, 8);
+        sb[lane] = scode * 0x01010101u;
+        const std::vector<float> D = run46(a, b, sa, sb, 0, 0);
         int nans = 0, nan_col = 0;
         for (int l = 0; l < 64; ++l) for (int r = 0; r < 16; ++r)
             if (std::isnan(D[l * 16 + r])) { ++nans; nan_col += (l & 31) == (lane & 31); }

@@ -20,7 +20,8 @@ the ones they always were, the four gated ops, the gated FFN layers and the spar
 (K % 64 == 32) and N = 40 on the same grouped table: ``moe_forward_mxfp4`` and ``moe_gated_forward_mxfp4`` in the three
 precisions, ``moe_forward_mxfp4_fp8`` and ``moe_forward_mxfp4_fp4``, float32 and bfloat16 rows, with and without a bias, each
 once on its decode kernel and once on its tile kernel (forced through the tuning hooks), then ``quantize_rows_mxfp4`` plain
-and gated and ``moe_backward_input_mxfp4``."""
+and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision="fp6"``, ``moe_forward_mxfp4_fp6`` and
+``quantize_rows_mxfp6``."""
 import argparse
 import hashlib
 import os
@@ -397,6 +398,37 @@ def calls(dev, fq, ops):
         yield f"quantize_rows_mxfp4 gated {dt}", lambda: ops.quantize_rows_mxfp4(gu.to(dt), **glu)
         for do in (F32, BF16):
             yield f"moe_backward_input_mxfp4 {dt}->{do}", lambda: ops.moe_backward_input_mxfp4(Pm, Sm, gy.to(dt), tpe, offs, out_dtype=do)
+
+    # the MXFP6-row precision, behind the lines above (their order and their random draws are unchanged): the same K = 96,
+    # N = 40, decode and tile forced in turn through its own hook
+    def forced6(which, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = lib.fql_tune_set_mx4_f6_decode_max_rows(2 ** 31 - 1 if which == "decode" else 0)
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_mx4_f6_decode_max_rows(old)
+        return run
+
+    for which in ("decode", "tile"):
+        for btag, b in (("", None), (" bias", biasm)):
+            for dt in (F32, BF16):
+                tag = f"fp6 {dt}{btag} {which}"
+                yield f"moe_forward_mxfp4 {tag}", forced6(which, lambda: ops.moe_forward_mxfp4(
+                    Pm, Sm, x.to(dt), tpe, offs, bias=b, precision="fp6"))
+                yield f"moe_gated_forward_mxfp4 {tag}", forced6(which, lambda: ops.moe_gated_forward_mxfp4(
+                    Pm, Sm, gu.to(dt), tpe, offs, bias=b, precision="fp6", **glu))
+                yield f"moe_forward_mxfp4 {tag} ->f16", forced6(which, lambda: ops.moe_forward_mxfp4(
+                    Pm, Sm, x.to(dt), tpe, offs, bias=b, out_dtype=F16, precision="fp6"))
+            yield f"moe_forward_mxfp4_fp6{btag} {which}", forced6(which, lambda: ops.moe_forward_mxfp4_fp6(
+                Pm, Sm, *ops.quantize_rows_mxfp6(x), tpe, offs, bias=b))
+            yield f"moe_forward_mxfp4_fp6 f16{btag} {which}", forced6(which, lambda: ops.moe_forward_mxfp4_fp6(
+                Pm, Sm, *ops.quantize_rows_mxfp6(x), tpe, offs, bias=b, out_dtype=F16))
+    for dt in (F32, BF16):
+        yield f"quantize_rows_mxfp6 {dt}", lambda: ops.quantize_rows_mxfp6(x.to(dt))
+        yield f"quantize_rows_mxfp6 gated {dt}", lambda: ops.quantize_rows_mxfp6(gu.to(dt), **glu)
 
 
 def digest(t):
