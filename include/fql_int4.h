@@ -867,6 +867,10 @@ FQL_API int fql_combine_sparse_bwd(const void *grad_out, int out_dtype, const vo
  *   run to run.  bias [E][N] float32 or NULL is added in the epilogue, then comes the one rounding to out_dtype (float32,
  *   bfloat16 or float16).  No atomics; every element of out [T][N] is written once, rows no expert covers as zeros by the
  *   same launch.  tokens_per_expert / input_offsets: both, or both NULL with E == 1 (one segment).
+ *   The table contract of every fql_moe_mx4_* entry (forward in each precision, fql_moe_mx4_bwd_input) is fql_moe_fwd_f32's:
+ *   raw int32 (offset, count) pairs in any order, clipped on the device to [0, T] (a count <= 0 or an offset past T is an
+ *   empty expert); the clipped ranges must not overlap; rows no expert covers are zero in the result, and as
+ *   inputs they never enter a covered row's result, whatever they hold.
  *   Non-finite values: a non-finite activation (or h) makes its whole output row NaN; a scale code 255 makes exactly the
  *   outputs of its weight row NaN, for the rows of its expert.  A weight below 2^-126 in magnitude (scale codes 0 and 1 with
  *   the smallest element codes) may be flushed to zero, and one of 2^128 or more (scale code 254 with |code| >= 2) is

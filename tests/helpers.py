@@ -259,6 +259,67 @@ def clipped_ranges(tokens_per_expert, input_offsets, T):
     return out
 
 
+# ---- hostile and large expert tables (tests/test_gpu_mxfp4_tables.py) --------------------------------------------------
+INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+HOSTILE_TABLES = ("e65", "e130-descending", "e128-decode", "clipped", "gaps-descending", "all-empty", "one-expert-inside")
+E128_OWNERS = ((3, 5), (17, 0), (42, 7), (63, 2), (64, 1), (77, 6), (100, 3), (127, 4))   # (expert, its one row) of e128-decode
+
+
+def hostile_table(name):
+    """(tokens_per_expert, input_offsets, T, ranges) of one of HOSTILE_TABLES: the raw int32 values as CPU tensors, as the
+    device gets them, and ``clipped_ranges`` of them.  The ranges are asserted to lie in [0, T] and not to overlap.
+
+    e65: 65 experts, rows [0 1] . [e0: 1] [e63: 33] . . [e64: 3] . (a dot: a row no expert covers); the others are empty.
+    e130-descending: expert e owns the one row T - 2 - e of T = 132.  e128-decode: T = 8, the experts of E128_OWNERS own
+    one row each in a scrambled order, the 120 others are empty at offsets all over [0, T].  clipped: T = 40 with negative
+    offsets and counts, a count past T, an offset past T and both int32 extremes.  gaps-descending: counts [33, 0, 70, 1]
+    laid out from the last expert to the first with 3 rows in front, 5 between neighbours and 2 behind.  all-empty: three
+    empty experts over 5 rows.  one-expert-inside: one expert on [1, 34) of 35 rows."""
+    import torch
+    if name == "e65":
+        counts = [1] + [0] * 62 + [33, 3]
+        gaps = [2] + [0] * 63 + [2]
+        tpe, offs, T = expert_table(counts, gaps=gaps, tail=1, device="cpu")
+    elif name == "e130-descending":
+        T = 132
+        tpe, offs = torch.ones(130, dtype=torch.int32), torch.tensor([T - 2 - e for e in range(130)], dtype=torch.int32)
+    elif name == "e128-decode":
+        T = 8
+        tpe, offs = torch.zeros(128, dtype=torch.int32), torch.tensor([(5 * e) % 9 for e in range(128)], dtype=torch.int32)
+        for e, row in E128_OWNERS:
+            tpe[e], offs[e] = 1, row
+    elif name == "clipped":
+        T = 40
+        pairs = [(-3, 5), (2, 0), (10, -4), (30, 999), (50, 3), (INT32_MAX, INT32_MAX), (INT32_MIN, INT32_MAX)]
+        offs = torch.tensor([o for o, _ in pairs], dtype=torch.int32)
+        tpe = torch.tensor([c for _, c in pairs], dtype=torch.int32)
+    elif name == "gaps-descending":
+        rev_t, rev_o, T = expert_table([1, 70, 0, 33], gaps=[3, 5, 5, 5], tail=2, device="cpu")
+        tpe, offs = rev_t.flip(0).contiguous(), rev_o.flip(0).contiguous()
+    elif name == "all-empty":
+        T = 5
+        tpe, offs = torch.zeros(3, dtype=torch.int32), torch.tensor([0, 2, 5], dtype=torch.int32)
+    elif name == "one-expert-inside":
+        T = 35
+        tpe, offs = torch.tensor([T - 2], dtype=torch.int32), torch.tensor([1], dtype=torch.int32)
+    else:
+        raise KeyError(name)
+    ranges = clipped_ranges(tpe, offs, T)
+    taken = sorted((lo, hi) for lo, hi in ranges if hi > lo)
+    assert all(0 <= lo <= hi <= T for lo, hi in ranges), name
+    assert all(a[1] <= b[0] for a, b in zip(taken, taken[1:])), f"{name}: overlapping ranges are outside the contract"
+    return tpe, offs, T, ranges
+
+
+def uncovered_mask(ranges, T):
+    """bool [T]: the rows no range of ``ranges`` holds."""
+    import torch
+    mask = torch.ones(T, dtype=torch.bool)
+    for lo, hi in ranges:
+        mask[lo:hi] = False
+    return mask
+
+
 # ---- guard bands (tests/test_gpu_footprint*.py): a kernel that leaves its buffer lands in memory the test owns ----------
 GUARD_BYTES = 64 * 1024
 NAN = float("nan")
