@@ -31,6 +31,9 @@
 //   * FIXED ORDER.  Stage k0 = 0, 64, ... ; inside a stage step s = 0 .. 3 contracts k0 + 16 s .. + 15 with one instruction.
 //     A row's result is that sequence over its own activation row and its expert's weights: it does not depend on the
 //     other rows of its tile, on T, E or the table, so the grouped call equals E one-expert calls bit for bit.
+//     With LORA (below) one adapter stage follows the last weight stage: steps s with 16 s < r contract j = 16 s .. + 15 of
+//     the shrunk row and the adapter matrix.  A row's result is then that sequence over its own rows of x and v and its
+//     expert's W and B, and nothing else.
 //   * NON-FINITE.  A scale code 255 makes the 32 weights of its block NaN (zeros included), hence NaN in every output of
 //     that weight row for the rows of that expert.  A non-finite activation must make its whole output row NaN (the
 //     project's convention); Inf * w is only NaN where w == 0, so the staging thread flags the row in LDS when a bfloat16
@@ -38,6 +41,19 @@
 //   * RANGE.  2^(s - 127) * |e2m1| below 2^-126 (scale codes 0 and 1 with the smallest codes) may be flushed to zero.
 //   * No atomics, every element is written once.  With a table the launch carries one more z-slice whose workgroups zero
 //     the rows of out that no expert covers (mx4_group_begin, fql_mx4_common.h).
+//
+//   * LORA (mx4_kernel<IN, OUT, Mx4Lora>; fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd): a low-rank adapter
+//     fused in as one more stage of the same loop,
+//       out[t][n] = round_OUT( sum_k bf16(x[t][k]) W_e[n][k] + sum_{j < r} bf16(v[t][j]) bf16(B[e][n][j]) + bias[e][n] ),
+//     v [T][r] float32 the caller's shrunk rows (scale included), B [E][N][r] float32, r in {4, 8, 16, 32, 64}.  B has the
+//     weight image's layout [n][k] and v the activation image's, so behind the loop's last barrier the staging thread of
+//     weight row sn, piece sp packs B[e][n0 + sn][32 sp .. + 31] into image[0] (zeros past N or r) and the staging thread
+//     of row xs, quarter xq packs v[tx][16 xq .. + 15] into ximage[0] (zeros from r on), both rounded to bfloat16 as x is;
+//     one barrier, then the steps.  Both images are written in full: nothing stale of a weight stage is contracted.  v
+//     feeds the same exponent-field test as x: a non-finite v[t][j] makes the whole output row NaN.  B is not screened:
+//     what a non-finite B gives is what the arithmetic gives, as with scale code 255.  r * 4 is a multiple of 16, so the
+//     16-byte loads hold whenever the base pointers are 16-byte aligned; element loads otherwise.  No LDS beyond the two
+//     images, and the kernel without the flag is the code it was.
 //
 // The gated form runs mx4_glu_kernel (fql_mx4_quant.h) first and reads its bfloat16 h [T][K] as x.
 #pragma once
@@ -49,15 +65,37 @@ struct Mx4Cfg {
     static constexpr int THREADS = 256;
 };
 
+// Four float32 of an adapter operand (p is a multiple of four elements into its tensor) as two words of two bfloat16.
+__device__ __forceinline__ void mx4_lora_pack4(const float *__restrict__ p, bool vec, bool ok, uint32_t &w0, uint32_t &w1)
+{
+    v4f f = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ok) {
+        if (vec) f = *reinterpret_cast<const v4f *>(p);
+        else { f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; f[3] = p[3]; }
+    }
+    w0 = mx4_pack_bf16(f[0], f[1]);
+    w1 = mx4_pack_bf16(f[2], f[3]);
+}
+
+// The operands of the adapter stage, the one kernel argument more of the LORA form: rows [T][rank] float32 (v, or dv in the
+// input gradient), w the adapter matrix (B [E][N][rank], or A [E][rank][K] there).
+struct Mx4Lora {
+    const float *rows, *w;
+    int rank;
+};
+
 // IN: element type of x (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of out, rounded once in the epilogue.
-// (54 KiB of LDS: two workgroups a compute unit.)
-template <int IN, int OUT>
+// LA: nothing (mx4_kernel<IN, OUT>: the signature, the code and the bits it always had), or Mx4Lora: the compile-time LORA
+// flag, set by the argument that carries what it needs.  (54 KiB of LDS: two workgroups a compute unit.)
+template <int IN, int OUT, class... LA>
 __global__ __launch_bounds__(256) void mx4_kernel(
     const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ scales, const void *__restrict__ x,
     const float *__restrict__ bias, void *__restrict__ out, const int32_t *__restrict__ tpe,
-    const int32_t *__restrict__ offs, int E, int T, int K, int N)
+    const int32_t *__restrict__ offs, int E, int T, int K, int N, LA... lora)
 {
+    static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool LORA = sizeof...(LA) == 1;
     using C = Mx4Cfg;
     int row_lo, cnt, t_blk;
     if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
@@ -189,8 +227,48 @@ __global__ __launch_bounds__(256) void mx4_kernel(
         if (k0 + C::BK < K) run_stage(s1, s0, k0 + C::BK, it + 1);
     }
 
+    if constexpr (LORA) {
+        // The adapter stage.  Every thread is behind the last stage's barrier, which no store followed: both pairs of images
+        // are free.  Pair 0 is written in full (zeros past N and from `rank` on), then one barrier, then the steps.
+        const Mx4Lora la{lora...};
+        const int rank = la.rank;
+        const float *vrow = la.rows + (size_t)tx * rank;
+        const float *brow = la.w + wrow * rank;
+        const bool vec_v = (reinterpret_cast<uintptr_t>(la.rows) & 15) == 0, vec_b = (reinterpret_cast<uintptr_t>(la.w) & 15) == 0;
+        uint32_t xw[8], bad = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // v[tx][16 xq + 4 i .. + 3]
+            const int j = 16 * xq + 4 * i;
+            mx4_lora_pack4(vrow + j, vec_v, j < rank, xw[2 * i], xw[2 * i + 1]);
+            bad |= mx4_nonfinite2(xw[2 * i]) | mx4_nonfinite2(xw[2 * i + 1]);
+        }
+        *reinterpret_cast<uint4 *>(&ximage[0][xs][16 * xq]) = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+        *reinterpret_cast<uint4 *>(&ximage[0][xs][16 * xq + 8]) = make_uint4(xw[4], xw[5], xw[6], xw[7]);
+        if (bad & 0x80008000u) row_bad[xs] = 1;                    // (read behind the barrier below)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // B[e][n0 + sn][32 sp + 8 i .. + 7]
+            const int j = 32 * sp + 8 * i;
+            uint4 w;
+            mx4_lora_pack4(brow + j, vec_b, n_ok && j < rank, w.x, w.y);
+            mx4_lora_pack4(brow + j + 4, vec_b, n_ok && j + 4 < rank, w.z, w.w);
+            *reinterpret_cast<uint4 *>(&image[0][sn][j]) = w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (16 * s >= rank) break;                             // (uniform)
+            const uint4 xb = *reinterpret_cast<const uint4 *>(&ximage[0][tr][16 * s + 8 * h]);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const uint4 a = *reinterpret_cast<const uint4 *>(&image[0][32 * (nb + b) + r][16 * s + 8 * h]);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, xb),
+                                                                 acc[b], 0, 0, 0);
+            }
+        }
+    }
+
     // D[i][j]: i = n (A), j = t (B): the lane owns row t, registers 4q .. 4q+3 are n = 8 q + 4 h + (0 .. 3) of the block.
-    // (Every write of row_bad lies behind a barrier of the loop.)
+    // (Every write of row_bad lies behind a barrier of the loop or of the adapter stage.)
     const uint32_t bad = row_bad[tr] != 0 ? 0x8000u : 0u;
     if (!row_ok) return;
     const bool row_nan = (bad & 0x80008000u) != 0u;

@@ -1,5 +1,6 @@
 // libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h): the bfloat16 entries fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
-// fql_moe_mx4_bwd_input (fql_gemm_mx4.h, fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h), the block-scaled entries on fp8 rows
+// fql_moe_mx4_bwd_input (fql_gemm_mx4.h, fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h) and their adapter forms fql_moe_mx4_lora_fwd /
+// fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input (the LORA flag of the two tile kernels), the block-scaled entries on fp8 rows
 // fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8, on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 and on MXFP6 rows
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
 // fql_gemm_mx4_sdecode.h) and the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
@@ -29,7 +30,18 @@ struct Mx4Call {
     int E, T, K, N;
     const float *act_scale = nullptr;  // [T] or NULL (fp8 rows only)
     const uint8_t *row_scales = nullptr;  // [T][K / 32] E8M0 (MXFP4 and MXFP6 rows only)
+    bool lora = false;                 // an adapter entry (bfloat16 kernels only): the three below are its operands
+    const float *lora_rows = nullptr;  // [T][rank]: v (forward) or dv (input gradient)
+    const float *lora_w = nullptr;     // [E][N][rank] B (forward) or [E][rank][K] A (input gradient)
+    int rank = 0;
 };
+
+// c with the operands of an adapter entry
+Mx4Call with_lora(Mx4Call c, const float *rows, const float *w, int rank)
+{
+    c.lora = true; c.lora_rows = rows; c.lora_w = w; c.rank = rank;
+    return c;
+}
 
 enum { ROWS_FLOAT = 0, ROWS_E4M3 = 1, ROWS_MXFP4 = 2, ROWS_MXFP6 = 3 };   // what c.rows holds; 1 .. 3 are the kernels' ROWS, 1 and 2 the scaled hooks' mode
 
@@ -73,11 +85,19 @@ bool mx4_use_decode(int rows_kind, int T)
     return T > 0 && T <= g_mx4_decode_max_rows[rows_kind] && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;   // (no overflow at a hook's T = INT_MAX)
 }
 
-// The bfloat16 forward: c.rows is [T][K] float32 or bfloat16.
+// The bfloat16 forward: c.rows is [T][K] float32 or bfloat16.  An adapter call always takes the tile kernel (training: the
+// decode kernel has no adapter form).
 int launch_mx4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
 {
     using C = Mx4Cfg;
     using D = Mx4DecodeCfg;
+    if (c.lora)
+        return with_in_dtype(in_dtype, [&](auto in) {
+            return with_out_dtype(out_dtype, [&](auto o) {
+                return launch(mx4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, c.N, C::BN, C::BT), dim3(C::THREADS), 0, st,
+                              c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, Mx4Lora{c.lora_rows, c.lora_w, c.rank});
+            });
+        });
     const bool decode = mx4_use_decode(ROWS_FLOAT, c.T);
     const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
     return with_in_dtype(in_dtype, [&](auto in) {
@@ -119,8 +139,10 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     if (c.K & 1) return FQL_ERR_ODD_K;
     if (c.K % 32 != 0) return FQL_ERR_BAD_SHAPE;                      // one scale per 32 inputs
     if ((!byte_rows && in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (c.lora && c.rank != 4 && c.rank != 8 && c.rank != 16 && c.rank != 32 && c.rank != 64) return FQL_ERR_BAD_SHAPE;
     if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
     if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
+    if (c.lora && (!c.lora_rows || !c.lora_w)) return FQL_ERR_NULL_POINTER;
     if ((rows_kind == ROWS_MXFP4 || rows_kind == ROWS_MXFP6) && !c.row_scales) return FQL_ERR_NULL_POINTER;
     if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
     if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
@@ -130,6 +152,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     const int ib = byte_rows ? 1 : dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
+    if ((reinterpret_cast<uintptr_t>(c.lora_rows) & 3) || (reinterpret_cast<uintptr_t>(c.lora_w) & 3)) return FQL_ERR_ALIGNMENT;   // (NULL without an adapter)
     if (rows_kind == ROWS_MXFP4 && !aligned16(c.rows)) return FQL_ERR_ALIGNMENT;
     if (rows_kind == ROWS_MXFP6 && (reinterpret_cast<uintptr_t>(c.rows) & 7)) return FQL_ERR_ALIGNMENT;
     return FQL_OK;
@@ -279,6 +302,51 @@ FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e
         return with_out_dtype(out_dtype, [&](auto o) {
             return launch(mx4_bwd_kernel<decltype(in)::value, decltype(o)::value>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows, c.out,
                           c.tpe, c.offs, c.E, c.T, c.K, c.N);
+        });
+    });
+}
+
+FQL_API int fql_moe_mx4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                                 const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                 const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E,
+                                 int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    const Mx4Call c = with_lora({blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, lora_rows, lora_B, rank);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_mx4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_mx4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                     const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                     const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                                     int E, int T, int K, int N, int activation, float act_alpha, float act_limit,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mx4_quant_fwd<ROWS_FLOAT>(with_lora({blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                               lora_rows, lora_B, rank), in_dtype, out_dtype, {true, activation, act_alpha, act_limit},
+                                     workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_mx4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *grad_out, int in_dtype,
+                                       const float *lora_rows, const float *lora_A, int rank, const int32_t *tokens_per_expert,
+                                       const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
+                                       void *stream)
+{
+    using C = Mx4BwdCfg;
+    const Mx4Call c = with_lora({blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N}, lora_rows,
+                                lora_A, rank);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK) return rc;
+    if (empty) return T == 0 ? FQL_OK : FQL_ERR_BAD_SHAPE;            // (N == 0 with rows: dv A alone is not this entry's business)
+    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(mx4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0,
+                          static_cast<hipStream_t>(stream), c.blocks, c.scales, c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N,
+                          Mx4Lora{c.lora_rows, c.lora_w, c.rank});
         });
     });
 }

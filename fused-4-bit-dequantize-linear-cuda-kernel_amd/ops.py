@@ -2088,3 +2088,216 @@ class _MoEFFNLoRAFn(torch.autograd.Function):
                 if need_Agu:
                     gAgu = lora_grad(x, du_gu, "rc", E, tpe, offs)                       # dA_gu = dU_gu^T x
         return (gx, gAgu, gBgu, gAd, gBd) + (None,) * 12 + (gbgu, gbd)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Adapters on the MXFP4 experts (MXFP4MoEFFN), fused into the bfloat16 GEMMs: the adapter term is one more contraction
+# stage of the tile kernel (csrc/fql_gemm_mx4.h, csrc/fql_gemm_mx4_bwd.h), so no float32 [T, C]
+# base result is written for an expand pass to read back.  The shrunk rows carry the scale: v = s A x, dv = s dY B.
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _mxfp4_lora_launch(name, entry, blocks, scales, rows, cols, v, w, w_shape, tokens_per_expert, input_offsets, bias,
+                       out_dtype, K, act=(), gated=False):
+    """The three adapter entries.  ``rows`` [T, cols] float32 / bfloat16, ``v`` [T, r] float32, ``w`` float32 of
+    ``w_shape(E, r)``.  Types and shapes first, then the devices: the argument errors read the same without a GPU."""
+    if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: the rows must be a float32 or bfloat16 2-D tensor (float16 is refused: rounding it "
+                           "to bfloat16 would lose three bits; cast it yourself)")
+    if blocks.dtype != torch.uint8 or blocks.dim() != 3 or scales.dtype != torch.uint8 or scales.dim() != 3:
+        raise RuntimeError("blocks must be uint8 [num_experts, N, K/2] and scales uint8 [num_experts, N, K/32]")
+    if K % 32 != 0 or tuple(scales.shape) != (blocks.shape[0], blocks.shape[1], K // 32):
+        raise RuntimeError("blocks must be [num_experts, N, K/2] and scales [num_experts, N, K/32] with K % 32 == 0")
+    if rows.shape[1] != cols:
+        raise RuntimeError(f"ops.{name}: the rows must have {cols} columns for blocks {list(blocks.shape)}")
+    T, E = rows.shape[0], blocks.shape[0]
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[0] != T:
+        raise RuntimeError(f"ops.{name}: the shrunk rows must be a float32 [T, r] tensor with the rows' T")
+    r = v.shape[1]
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    if w.dtype != torch.float32 or tuple(w.shape) != w_shape(E, r):
+        raise RuntimeError(f"ops.{name}: the adapter matrix must be a float32 {list(w_shape(E, r))} tensor (the adapter "
+                           "weights stay float32 whatever the activations' type)")
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not rows.is_cuda:
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA tensor")
+    dev = rows.device
+    blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
+    _on(dev, lora_rows=v, lora_weight=w)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
+    out_cols = K if entry == "fql_moe_mx4_lora_bwd_input" else N
+    out = torch.empty((T, out_cols), dtype=out_dtype, device=dev)
+    if T == 0 or out_cols == 0:
+        return out
+    if entry == "fql_moe_mx4_lora_bwd_input":
+        if N == 0:
+            raise RuntimeError(f"ops.{name}: blocks with no rows (N == 0) have no adapter form")
+        _launch(entry, dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype], v.contiguous(), w.contiguous(), r, tpe,
+                offs, out, _DTYPES[out_dtype], E, T, K, N)
+        return out
+    bias = _check_bias(bias, N, dev, E)
+    _launch(entry, dev, blocks, scales, rows.contiguous(), _DTYPES[rows.dtype], v.contiguous(), w.contiguous(), r, bias, tpe,
+            offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
+            ws_bytes=_native.lib().fql_moe_mx4_workspace_bytes(E, T, K, N, int(gated)))
+    return out
+
+
+def moe_forward_mxfp4_lora(blocks, scales, inputs, v, lora_B, tokens_per_expert, input_offsets, bias=None, out_dtype=None):
+    """``moe_forward_mxfp4`` (bfloat16 precision) with a low-rank adapter fused in: for the rows t of expert e,
+    ``out[t] = W_e @ bf16(inputs[t]) + bf16(lora_B[e]) @ bf16(v[t]) (+ bias[e])``, rounded once to ``out_dtype``.  ``v``
+    [T, r] float32 are the shrunk rows with the scale in them (``lora_shrink(inputs, lora_A, scale=s)``), ``lora_B``
+    [E, N, r] float32, r in ``LORA_RANKS``.  The adapter is one more contraction stage of the tile kernel
+    (csrc/fql_gemm_mx4.h): the operands are rounded to bfloat16 on their way into LDS as ``inputs`` are, the order is
+    fixed, and a row's result depends on its own rows of ``inputs`` and ``v`` and its expert's weights only.  With
+    ``lora_B`` zero the result is ``moe_forward_mxfp4``'s bit for bit.  A non-finite ``v[t]`` makes row t NaN.  Always the
+    tile kernel (no decode form).  Forward only: ``moe_ffn_lora_forward_mxfp4`` is the differentiable form."""
+    _forward_only("moe_forward_mxfp4_lora", inputs, v, lora_B, bias)
+    return _mxfp4_lora_launch("moe_forward_mxfp4_lora", "fql_moe_mx4_lora_fwd", blocks, scales, inputs, 2 * blocks.shape[-1],
+                              v, lora_B, lambda E, r: (E, blocks.shape[1], r), tokens_per_expert, input_offsets, bias,
+                              out_dtype, 2 * blocks.shape[-1])
+
+
+def moe_gated_forward_mxfp4_lora(blocks, scales, gate_up, v, lora_B, tokens_per_expert, input_offsets, activation="silu",
+                                 activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None):
+    """``moe_gated_forward_mxfp4`` (bfloat16 precision) with the adapter stage of ``moe_forward_mxfp4_lora``:
+    ``out[t] = W_e @ h[t] + bf16(lora_B[e]) @ bf16(v[t]) (+ bias[e])`` with ``h = bf16(act(gate_up[t, :K], gate_up[t, K:]))``
+    from the same streaming pre-pass; ``v`` [T, r] float32 (``lora_gated_shrink(gate_up, lora_A, scale=s, ...)``),
+    ``lora_B`` [E, N, r] float32."""
+    _forward_only("moe_gated_forward_mxfp4_lora", gate_up, v, lora_B, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _mxfp4_lora_launch("moe_gated_forward_mxfp4_lora", "fql_moe_mx4_glu_lora_fwd", blocks, scales, gate_up,
+                              4 * blocks.shape[-1], v, lora_B, lambda E, r: (E, blocks.shape[1], r), tokens_per_expert,
+                              input_offsets, bias, out_dtype, 2 * blocks.shape[-1],
+                              act=(_ACTIVATIONS[kind], act_alpha, act_limit), gated=True)
+
+
+def moe_backward_input_mxfp4_lora(blocks, scales, grad_out, dv, lora_A, tokens_per_expert, input_offsets, out_dtype=None):
+    """``moe_backward_input_mxfp4`` with the adapter's share fused in: ``grad_in[t] = bf16(grad_out[t]) @ W_e +
+    bf16(dv[t]) @ bf16(lora_A[e])`` -> [T, K] ``out_dtype`` (default float32), rounded once.  ``dv`` [T, r] float32
+    (``lora_shrink(grad_out, lora_B, "cr", scale=s)``), ``lora_A`` [E, r, K] float32.  One more contraction stage of the
+    transposed kernel (csrc/fql_gemm_mx4_bwd.h); with ``lora_A`` zero the result is ``moe_backward_input_mxfp4``'s bit for
+    bit, and a non-finite ``dv[t]`` makes row t NaN."""
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    return _mxfp4_lora_launch("moe_backward_input_mxfp4_lora", "fql_moe_mx4_lora_bwd_input", blocks, scales, grad_out,
+                              blocks.shape[1] if blocks.dim() == 3 else -1, dv, lora_A,
+                              lambda E, r: (E, r, 2 * blocks.shape[-1]), tokens_per_expert, input_offsets, None, out_dtype,
+                              2 * blocks.shape[-1])
+
+
+def moe_ffn_lora_forward_mxfp4(gate_up_blocks, gate_up_scales, down_blocks, down_scales, inputs, gate_up_lora_A,
+                               gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert, input_offsets,
+                               activation_dtype=None, activation="silu", activation_alpha=1.702, activation_limit=7.0,
+                               gate_up_bias=None, down_bias=None):
+    """Gated FFN experts on MXFP4 weights with a low-rank adapter on each projection, fused into the GEMMs: for the rows t
+    of expert e, ``gu = W_gu x + b_gu + B_gu v_gu`` with ``v_gu = s A_gu x``, ``h = act(gu)`` (never stored),
+    ``y = W_d h + b_d + B_d v_d`` with ``v_d = s A_d h``.  ``inputs`` [T, H] float32, or bfloat16 with
+    ``activation_dtype=torch.bfloat16`` (``gate_up`` is then kept in bfloat16 and ``y`` comes back in it); blocks / scales
+    as ``MXFP4MoEFFN`` holds them; ``gate_up_lora_A`` [E, r, H], ``gate_up_lora_B`` [E, 2F, r], ``down_lora_A`` [E, r, F],
+    ``down_lora_B`` [E, H, r] float32.  Differentiable (once) in ``inputs``, the four adapters and the two biases; the
+    weights are frozen.  Every operand of a contraction is rounded once to bfloat16 and the gradient is straight-through
+    across those roundings, as ``MXFP4MoEFFN(input_grad=True)``'s is.  No float32 [T, C] temporary exists with bfloat16
+    activations, and nothing of shape [T, F] is saved."""
+    act = activation_of(activation, activation_alpha, activation_limit)
+    if activation_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError("activation_dtype must be None, torch.float32 or torch.bfloat16 (float16 rows are refused: "
+                         "rounding them to bfloat16 would lose three bits)")
+    dt = torch.float32 if activation_dtype is None else activation_dtype
+    if inputs.dim() != 2 or inputs.dtype != dt:
+        raise RuntimeError(f"inputs must be a 2-D {dt} tensor (activation_dtype), got {inputs.dtype}")
+    for name, t in (("gate_up_blocks", gate_up_blocks), ("gate_up_scales", gate_up_scales), ("down_blocks", down_blocks),
+                    ("down_scales", down_scales)):
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise RuntimeError(f"{name} must be a uint8 3-D tensor (MXFP4MoEFFN's buffers)")
+    E, F2, H = gate_up_blocks.shape[0], gate_up_blocks.shape[1], inputs.shape[1]
+    if F2 % 2 or gate_up_blocks.shape[2] * 2 != H or tuple(down_blocks.shape) != (E, H, F2 // 4):
+        raise RuntimeError("gate_up_blocks must be [E, 2F, H/2] and down_blocks [E, H, F/2] for inputs [T, H]")
+    for name, t, shape in (("gate_up_lora_A", gate_up_lora_A, (E, H)), ("gate_up_lora_B", gate_up_lora_B, (E, F2)),
+                           ("down_lora_A", down_lora_A, (E, F2 // 2)), ("down_lora_B", down_lora_B, (E, H))):
+        if t.dtype != torch.float32 or t.dim() != 3:
+            raise RuntimeError(f"{name} must be a float32 3-D tensor: the adapter weights and their gradients stay float32 "
+                               "whatever the activations' type")
+        got = (t.shape[0], t.shape[2] if name.endswith("A") else t.shape[1])
+        if got != shape:
+            raise RuntimeError("the adapters must be gate_up_lora_A [E, r, H], gate_up_lora_B [E, 2F, r], down_lora_A "
+                               f"[E, r, F] and down_lora_B [E, H, r]; {name} is {list(t.shape)}")
+    r = gate_up_lora_A.shape[1]
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    if gate_up_lora_B.shape[2] != r or down_lora_A.shape[1] != r or down_lora_B.shape[2] != r:
+        raise RuntimeError("the gate_up and down adapters must have the same rank")
+    if not inputs.is_cuda:
+        raise RuntimeError("inputs must be a CUDA tensor (the product path has no CPU fallback)")
+    weights = (gate_up_blocks, gate_up_scales, down_blocks, down_scales)
+    adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
+    biases = (_check_bias(gate_up_bias, F2, inputs.device, E), _check_bias(down_bias, H, inputs.device, E))
+    if _wants_grad(inputs, *adapters, *biases):
+        return _MXFP4FFNLoRAFn.apply(inputs, *adapters, *biases, *weights, tokens_per_expert, input_offsets, float(scaling),
+                                     act)
+    return _mxfp4_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets, act, biases)[0]
+
+
+def _mxfp4_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, act, biases):
+    """Returns (y, gate_up, v_gu, v_d), y and gate_up in ``inputs``' type.  Four launches and the gated pre-pass: the two
+    shrinks (scale included) and the two GEMMs with their adapter stage."""
+    gub, gus, db, ds = weights
+    A_gu, B_gu, A_d, B_d = (a.detach() for a in adapters)
+    b_gu, b_d = (None if b is None else b.detach() for b in biases)
+    x, dt = inputs.detach(), inputs.dtype
+    v_gu = lora_shrink(x, A_gu, "rc", tpe, offs, scale=scaling)
+    gate_up = moe_forward_mxfp4_lora(gub, gus, x, v_gu, B_gu, tpe, offs, bias=b_gu, out_dtype=dt)
+    v_d = _lora_shrink(gate_up, A_d, "rc", tpe, offs, scaling, gated=True, act=act)
+    y = moe_gated_forward_mxfp4_lora(db, ds, gate_up, v_d, B_d, tpe, offs, activation=act[0], activation_alpha=act[1],
+                                     activation_limit=act[2], bias=b_d, out_dtype=dt)
+    return y, gate_up, v_gu, v_d
+
+
+class _MXFP4FFNLoRAFn(torch.autograd.Function):
+    """The gated MXFP4 FFN block + its two adapters in one node, modelled on ``_MoEFFNLoRAFn`` and ``_MXFP4GatedFFNFn``.
+    Saves inputs [T, H] and gate_up [T, 2F] in the layer's type, v_gu and v_d ([T, r] float32, the scale in them), the
+    table and the parameters: nothing of shape [T, F].  Every [T, C] tensor of the backward (dh, dgu, dx) is written once,
+    in the layer's type, by the kernel that forms it."""
+
+    @staticmethod
+    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, b_gu, b_d, gub, gus, db, ds, tpe, offs, scaling, act):
+        x = inputs.contiguous()
+        y, gate_up, v_gu, v_d = _mxfp4_ffn_lora_apply((gub, gus, db, ds), x, (A_gu, B_gu, A_d, B_d), scaling, tpe, offs, act,
+                                                      (b_gu, b_d))
+        ctx.save_for_backward(x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, gub, gus, db, ds, tpe, offs)
+        ctx.scaling, ctx.act = scaling, act
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, gub, gus, db, ds, tpe, offs = ctx.saved_tensors
+        need_x, need_Agu, need_Bgu, need_Ad, need_Bd, need_bgu, need_bd = ctx.needs_input_grad[:7]
+        E, s, dt = gub.shape[0], ctx.scaling, gate_up.dtype
+        check_activation_rows(gy, "the incoming gradient", dt)
+        g = gy.contiguous()
+        gx = gAgu = gBgu = gAd = gBd = gbgu = gbd = None
+        if need_Bd:
+            gBd = lora_grad(g, v_d, "cr", E, tpe, offs)                                  # dB_d = dY^T v_d (s is in v_d)
+        if need_bd:
+            gbd = moe_bias_grad(g, E, tpe, offs)                                         # db_d = sum of dY per expert
+        through = need_x or need_Agu or need_Bgu or need_bgu                            # anything upstream of h
+        if through or need_Ad:
+            dv_d = lora_shrink(g, B_d, "cr", tpe, offs, scale=s)                         # dv_d = s dY B_d
+            if need_Ad:
+                gAd = _lora_grad(gate_up, dv_d, "rc", E, tpe, offs, 1.0, gated=True, act=ctx.act)   # dA_d = dv_d^T h
+        if through:
+            dh = moe_backward_input_mxfp4_lora(db, ds, g, dv_d, A_d, tpe, offs, out_dtype=dt)       # dh = dY W_d + dv_d A_d
+            dgu = _glu_backward(gate_up, dh, dt, ctx.act)
+            del dh
+            if need_Bgu:
+                gBgu = lora_grad(dgu, v_gu, "cr", E, tpe, offs)                          # dB_gu = dgu^T v_gu
+            if need_bgu:
+                gbgu = moe_bias_grad(dgu, E, tpe, offs)                                  # db_gu = sum of dgu per expert
+            if need_x or need_Agu:
+                dv_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dv_gu = s dgu B_gu
+                if need_x:
+                    gx = moe_backward_input_mxfp4_lora(gub, gus, dgu, dv_gu, A_gu, tpe, offs, out_dtype=dt)
+                if need_Agu:
+                    gAgu = lora_grad(x, dv_gu, "rc", E, tpe, offs)                       # dA_gu = dv_gu^T x
+        return (gx, gAgu, gBgu, gAd, gBd, gbgu, gbd) + (None,) * 8

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 400 /* 0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 410 /* 0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1101,6 +1101,43 @@ FQL_API int fql_moe_mx4_glu_fwd_q6(const uint8_t *blocks, const uint8_t *scales_
                                    float act_limit, void *workspace, size_t workspace_bytes, void *stream);
 FQL_API int fql_mx6_quantize_rows(const void *rows, int in_dtype, int gated, int activation, float act_alpha, float act_limit,
                                   uint8_t *out_codes, uint8_t *out_scales, int T, int K, void *stream);
+
+/* ---- low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs (FQL_VERSION 410; INTEGRATION.md
+ *      section 17; csrc/fql_gemm_mx4.h, csrc/fql_gemm_mx4_bwd.h) ----
+ * The adapter forms of fql_moe_mx4_fwd, fql_moe_mx4_glu_fwd and fql_moe_mx4_bwd_input: the adapter term is one more
+ * contraction stage of the same kernel, behind the last weight stage, so no float32 [T][N] result is written and read back.
+ * fql_moe_mx4_lora_fwd:       out[t][n] = sum_k bf16(x[t][k]) W_e[n][k] + sum_{j < rank} bf16(v[t][j]) bf16(B[e][n][j]) (+ bias[e][n])
+ * fql_moe_mx4_glu_lora_fwd:   the same on h = bf16(act(gate_up)) (fql_moe_mx4_glu_fwd's pre-pass and workspace, unchanged)
+ * fql_moe_mx4_lora_bwd_input: grad_in[t][k] = sum_n bf16(grad_out[t][n]) W_e[n][k] + sum_{j < rank} bf16(dv[t][j]) bf16(A[e][j][k])
+ *   lora_rows [T][rank] float32: the caller's shrunk rows, v = s A x in the forward, dv = s grad_out B in the gradient (the
+ *   entries take no scale); lora_B [E][N][rank] and lora_A [E][rank][K] float32, PEFT's layouts; rank one of 4, 8, 16, 32, 64.
+ *   The adapter operands are rounded once to bfloat16 (to nearest even) on their way into LDS, as the rows are.  The order is
+ *   fixed: the weight stages ascending as in the base entries, then j = 0 .. in steps of 16, so a row's result depends on its
+ *   own rows of x and v and its expert's W and B only, and the grouped call equals E one-expert calls bit for bit.  With
+ *   lora_B (lora_A) all zeros and finite lora_rows the result is the base entry's, bit for bit.
+ *   These entries always run the 64-row tile kernel (no decode form: they are for training); everything else (the table, the
+ *   zeroed rows no expert covers, the bias, the one rounding to out_dtype, scale code 255) is the base entry's.
+ *   Non-finite values: a non-finite element of a row of lora_rows makes that whole row of the result NaN, as a non-finite x
+ *   / grad_out does; lora_B / lora_A are not screened, a non-finite element gives what the arithmetic gives.
+ *   lora_rows and the adapter matrix need 4-byte alignment only (16-byte aligned ones take the wide loads).
+ *   Return codes: the base entry's, in its order, with FQL_ERR_BAD_SHAPE for a rank outside the five behind the dtype check
+ *   (before T == 0 / N == 0 returns FQL_OK with nothing launched), FQL_ERR_NULL_POINTER for a NULL lora_rows or adapter matrix
+ *   with the other pointers and FQL_ERR_ALIGNMENT for one not aligned to 4 bytes, all before any HIP call.
+ *   fql_moe_mx4_lora_bwd_input with N == 0 and T > 0 is FQL_ERR_BAD_SHAPE (the base entry's empty contraction has no adapter
+ *   form). */
+FQL_API int fql_moe_mx4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                                 const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                 const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E,
+                                 int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                     const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                     const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype,
+                                     int E, int T, int K, int N, int activation, float act_alpha, float act_limit,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_mx4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *grad_out, int in_dtype,
+                                       const float *lora_rows, const float *lora_A, int rank, const int32_t *tokens_per_expert,
+                                       const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
+                                       void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);
