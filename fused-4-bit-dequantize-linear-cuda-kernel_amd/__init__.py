@@ -9,6 +9,7 @@ from .quantize import (quantize_weights, dequantize_weights, reference_quantized
 from .module import QuantizedLinear
 from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN, QuantizedSparseMoEBlock, \
     MXFP4MoEFFN
+from .mxfp4_linear import MXFP4Linear
 from .lora import LoRAQuantizedLinear, LoRAMoEINT4, LoRAQuantizedMoEFFN, LoRAMXFP4MoEFFN
 from .routing import (RoutingResult, simulate_routing, balanced_routing, create_expert_inputs,
                       combine_expert_outputs, dispatch_grouped, dispatch_indices, combine_grouped)
@@ -19,5 +20,5 @@ __all__ = [
     "RoutingResult", "simulate_routing", "balanced_routing", "create_expert_inputs",
     "combine_expert_outputs", "dispatch_grouped", "dispatch_indices", "combine_grouped",
     "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN", "LoRAMXFP4MoEFFN", "QuantizedSparseMoEBlock",
-    "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN", "quantize_mxfp6", "dequantize_mxfp6",
+    "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN", "quantize_mxfp6", "dequantize_mxfp6", "MXFP4Linear",
 ]

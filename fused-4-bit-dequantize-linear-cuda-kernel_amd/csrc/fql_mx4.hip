@@ -3,13 +3,15 @@
 // fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input (the LORA flag of the two tile kernels), the block-scaled entries on fp8 rows
 // fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8, on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 and on MXFP6 rows
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
-// fql_gemm_mx4_sdecode.h) and the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
+// linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
 #include "fql_host.h"
 #include "fql_gemm_mx4.h"
 #include "fql_gemm_mx4_decode.h"
+#include "fql_gemm_mx4_linear.h"
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_mx4_scaled.h"
 #include "fql_gemm_mx4_sdecode.h"
@@ -248,6 +250,94 @@ int mx4_scaled_fwd(const Mx4Call &c, int out_dtype, void *stream)
     return launch_mx4_scaled<ROWS>(out_dtype, c, static_cast<hipStream_t>(stream));
 }
 
+// ---- the dense linear layer (fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd): E = 1, no table, and with split_k set and few rows
+//      the decode kernel cut along K (fql_gemm_mx4_linear.h) ----
+#define FQL_MX4_LINEAR_DECODE_MAX_ROWS 16   /* rows (T) up to which the split form runs: the largest count of the sweep up to which it beats both grouped kernels at every shape whose S is above 1 */
+#define FQL_MX4_LINEAR_MAX_SLICES 16
+#define FQL_MX4_LINEAR_FILL_WAVES 640       /* the waves S(K, N) asks for: 2.5 a compute unit, from the S sweep of the same section */
+int g_mx4_linear_decode_max_rows = FQL_MX4_LINEAR_DECODE_MAX_ROWS;
+int g_mx4_linear_slices = 0;           // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_mx4_linear_slices)
+
+// S(K, N): the slices of the split form, a pure function of the weights' shape (never of T or the device).  The smallest
+// S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >= FQL_MX4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 whole
+// pairs, so that no slice of the policy's is empty.  (The rule the work started from asked for 1024, a wave a SIMD; the
+// sweep's winners at one row are what 640 gives on all five shapes: 4, 8, 4, 1, 4.  Past that the partial sums' traffic
+// and the second launch cost more than the shorter K loop saves, and N = 28672 has 896 waves without help.)
+int mx4_linear_policy_slices(int K, int N)
+{
+    const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
+    int S = 1;
+    while (S < FQL_MX4_LINEAR_MAX_SLICES && waves * S < FQL_MX4_LINEAR_FILL_WAVES) S *= 2;
+    const int P = K / 64;
+    while (S > 1 && S > P) S /= 2;
+    return S;
+}
+
+// The slices a call with split_k set runs now: 1 means no split form (the call goes the split_k == 0 way).
+int mx4_linear_slices(int T, int K, int N)
+{
+    if (T <= 0 || T > g_mx4_linear_decode_max_rows || (T - 1) / Mx4DecodeCfg::BT + 1 > 65535) return 1;
+    return g_mx4_linear_slices != 0 ? g_mx4_linear_slices : mx4_linear_policy_slices(K, N);
+}
+
+// The partial sums of the split form: [16][T][N] float32, sized for the largest S so that the hook cannot outgrow it.
+size_t mx4_linear_partial_bytes(int T, int N, int split_k)
+{
+    if (!split_k || T <= 0 || N <= 0 || T > g_mx4_linear_decode_max_rows) return 0;
+    return (size_t)FQL_MX4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
+}
+size_t mx4_linear_h_bytes(int T, int K, int gated) { return gated && T > 0 && K > 0 ? mx4_ws_bytes(ROWS_FLOAT, T, K) : 0; }
+
+// The two launches of the split form: the sliced decode kernel into partial [S][T][N], then the reduce kernel.
+int launch_mx4_linear_split(int in_dtype, int out_dtype, const Mx4Call &c, int S, float *partial, hipStream_t st)
+{
+    using D = Mx4DecodeCfg;
+    using R = Mx4LinearReduceCfg;
+    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
+    const int rc = with_in_dtype(in_dtype, [&](auto in) {
+        return launch(mx4_linear_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.blocks, c.scales, c.rows, partial,
+                      c.T, c.K, c.N);
+    });
+    if (rc != FQL_OK) return rc;
+    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
+    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
+    return with_out_dtype(out_dtype, [&](auto o) {
+        constexpr int OUT = decltype(o)::value;
+        auto go = [&](auto s) {
+            return launch(mx4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.bias, c.out, c.T, c.N);
+        };
+        switch (S) {
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 4: return go(std::integral_constant<int, 4>{});
+        case 8: return go(std::integral_constant<int, 8>{});
+        default: return go(std::integral_constant<int, 16>{});
+        }
+    });
+}
+
+// Both linear entries: the checks of mx4_check with E = 1 and no table, the workspace, then the launches.
+int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, int split_k, void *workspace, size_t workspace_bytes,
+                   void *stream)
+{
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, a.ok(), &empty);
+    if (rc != FQL_OK || empty) return rc;
+    const size_t h_bytes = mx4_linear_h_bytes(c.T, c.K, a.gated);
+    const size_t need = h_bytes + mx4_linear_partial_bytes(c.T, c.N, split_k);
+    if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    if (a.gated) {
+        const int lrc = launch_mx4_quant<ROWS_FLOAT>(c.rows, in_dtype, a, ws, nullptr, c.T, c.K, st);
+        if (lrc != FQL_OK) return lrc;
+        c.rows = ws;
+        in_dtype = FQL_DTYPE_BF16;
+    }
+    const int S = split_k ? mx4_linear_slices(c.T, c.K, c.N) : 1;
+    if (S > 1) return launch_mx4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
+    return launch_mx4(in_dtype, out_dtype, c, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,6 +566,48 @@ FQL_API int fql_mx6_quantize_rows(const void *rows, int in_dtype, int gated, int
     const int rc = mx4_check(c, in_dtype, FQL_DTYPE_F32, a.ok(), &empty);
     if (rc != FQL_OK || empty) return rc;
     return launch_mx4_quant<ROWS_MXFP6>(rows, in_dtype, a, out_codes, out_scales, T, K, static_cast<hipStream_t>(stream));
+}
+
+FQL_API size_t fql_linear_mx4_workspace_bytes(int T, int K, int N, int gated, int split_k)
+{
+    return mx4_linear_h_bytes(T, K, gated) + mx4_linear_partial_bytes(T, N, split_k);   // h [T][K] bfloat16 | partial [16][T][N] float32
+}
+
+FQL_API int fql_linear_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, void *out, int out_dtype, int T, int K, int N, int split_k, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    return mx4_linear_fwd({blocks, scales_e8m0, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, in_dtype, out_dtype, kMx4Plain,
+                          split_k, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, void *out, int out_dtype, int T, int K, int N, int activation,
+                                   float act_alpha, float act_limit, int split_k, void *workspace, size_t workspace_bytes,
+                                   void *stream)
+{
+    return mx4_linear_fwd({blocks, scales_e8m0, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, in_dtype, out_dtype,
+                          {true, activation, act_alpha, act_limit}, split_k, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows)
+{
+    const int old = g_mx4_linear_decode_max_rows;
+    if (rows >= 0) g_mx4_linear_decode_max_rows = rows;
+    return old;
+}
+
+FQL_API int fql_tune_set_mx4_linear_slices(int slices)
+{
+    const int old = g_mx4_linear_slices;
+    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_mx4_linear_slices = slices;
+    return old;
+}
+
+FQL_API int fql_tune_mx4_linear_kernel(int T, int K, int N)
+{
+    const int S = mx4_linear_slices(T, K, N);
+    return (S << 8) | (S > 1 ? 2 : mx4_use_decode(ROWS_FLOAT, T) ? 1 : 0);
 }
 
 FQL_API int fql_tune_set_mx4_decode_max_rows(int rows)

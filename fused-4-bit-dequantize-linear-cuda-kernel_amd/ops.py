@@ -559,7 +559,7 @@ def _mxfp4_launch(name, blocks, scales, rows, K, tokens_per_expert, input_offset
         raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
     dev, T = rows.device, rows.shape[0]
     blocks, scales, E, N = _check_mxfp4(blocks, scales, dev, K)
-    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)   # (none: one expert, all rows)
     bias = _check_bias(bias, N, dev, E)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     L = _native.lib()
@@ -627,6 +627,84 @@ def moe_gated_forward_mxfp4(blocks, scales, gate_up, tokens_per_expert, input_of
     return _mxfp4_launch("moe_gated_forward_mxfp4", blocks, scales, gate_up, gate_up.shape[1] // 2, tokens_per_expert,
                          input_offsets, bias, out_dtype, True, act=(_ACTIVATIONS[kind], act_alpha, act_limit),
                          precision=precision)
+
+
+def _mxfp4_linear_launch(name, blocks, scales, rows, cols, bias, out_dtype, gated, act, precision, split_k):
+    """The two dense MXFP4 ops.  ``rows`` [T, cols] float32 / bfloat16, ``blocks`` [N, K/2], ``scales`` [N, K/32],
+    ``bias`` [N] float32 or None.  Types and shapes first, then the devices: the argument errors read the same without a
+    GPU."""
+    precision = _mxfp4_precision(precision)
+    if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    if blocks.dtype != torch.uint8 or blocks.dim() != 2 or scales.dtype != torch.uint8 or scales.dim() != 2:
+        raise RuntimeError("blocks must be uint8 [N, K/2] and scales uint8 [N, K/32]")
+    N, K = blocks.shape[0], 2 * blocks.shape[1]
+    if K % 32 != 0 or tuple(scales.shape) != (N, K // 32):
+        raise RuntimeError("blocks must be [N, K/2] and scales [N, K/32] with K % 32 == 0")
+    if rows.shape[1] != cols(K):
+        raise RuntimeError(f"ops.{name}: the rows must have {cols(K)} columns for blocks {list(blocks.shape)}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,)):
+        raise RuntimeError("bias must be a float32 [N] tensor")
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not rows.is_cuda:
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA tensor")
+    dev, T = rows.device, rows.shape[0]
+    _on(dev, blocks=blocks, scales=scales, bias=bias)
+    if precision != "bf16":     # the block-scaled precisions have no split form: the grouped op on the one-expert view
+        return _mxfp4_launch(name, blocks[None], scales[None], rows, K, None, None, None if bias is None else bias[None],
+                             out_dtype, gated, act=act, precision=precision)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    split = int(bool(split_k))
+    _launch("fql_linear_mx4_glu_fwd" if gated else "fql_linear_mx4_fwd", dev, blocks.contiguous(), scales.contiguous(),
+            rows.contiguous(), _DTYPES[rows.dtype], None if bias is None else bias.contiguous(), out, _DTYPES[out_dtype],
+            T, K, N, *act, split, ws_bytes=_native.lib().fql_linear_mx4_workspace_bytes(T, K, N, int(gated), split))
+    return out
+
+
+def linear_forward_mxfp4(blocks, scales, x, bias=None, out_dtype=None, precision="bf16", split_k=True):
+    """A dense linear layer on OCP MXFP4 weights: ``out[t] = W @ bf16(x[t]) (+ bias)``.  ``blocks`` uint8 [N, K/2] and
+    ``scales`` uint8 [N, K/32] (``quantize.quantize_mxfp4``, or a checkpoint's tensors); ``x`` [T, K] float32 (rounded
+    once to bfloat16) or bfloat16; ``bias`` [N] float32 (optional), added before the one rounding to ``out_dtype``
+    (default: ``x``'s type).  Forward only (``linear_backward_input_mxfp4`` is the input gradient).
+
+    ``split_k=False`` is ``moe_forward_mxfp4`` on the one-expert view ``blocks[None]`` without a table: the same kernels,
+    the same bits.  ``split_k=True`` (the default) lets a small batch (T up to the library's threshold, on shapes for
+    which the library's S(K, N) is above 1) run the decode kernel once per slice of K, S slices side by side, and sum the
+    float32 partial results in a fixed order in a second launch: a dense matrix at a few rows has no other axis to fill
+    the chip from.  A row's result then depends on its own row and the weights only, not on T or its position, and is
+    the same run to run; it is not the tile kernel's bit pattern, so a row's bits may change as T crosses the threshold
+    (both are within the float32 bound of the exact product).  INTEGRATION.md section 17.
+
+    ``precision="fp8"``, ``"fp6"`` and ``"fp4"`` are ``moe_forward_mxfp4``'s block-scaled modes on the one-expert view;
+    there is no split form there, and ``split_k`` is not looked at."""
+    _forward_only("linear_forward_mxfp4", x, bias)
+    return _mxfp4_linear_launch("linear_forward_mxfp4", blocks, scales, x, lambda K: K, bias, out_dtype, False, (), precision,
+                                split_k)
+
+
+def linear_gated_forward_mxfp4(blocks, scales, gate_up, activation="silu", activation_alpha=1.702, activation_limit=7.0,
+                               bias=None, out_dtype=None, precision="bf16", split_k=True):
+    """The down projection of a dense gated MLP on MXFP4 weights: ``out[t] = W @ bf16(act(gate_up[t, :K], gate_up[t, K:]))
+    (+ bias)``, ``gate_up`` [T, 2K] float32 or bfloat16, ``blocks`` [N, K/2].  ``moe_gated_forward_mxfp4``'s streaming
+    pre-pass into the op's workspace, then ``linear_forward_mxfp4``'s kernels on the bfloat16 ``h``, with the same
+    ``split_k``.  The block-scaled precisions go through ``moe_gated_forward_mxfp4`` on the one-expert view: no split form
+    there."""
+    _forward_only("linear_gated_forward_mxfp4", gate_up, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _mxfp4_linear_launch("linear_gated_forward_mxfp4", blocks, scales, gate_up, lambda K: 2 * K, bias, out_dtype, True,
+                                (_ACTIVATIONS[kind], act_alpha, act_limit), precision, split_k)
+
+
+def linear_backward_input_mxfp4(blocks, scales, grad_out, out_dtype=None):
+    """``grad_in[t] = bf16(grad_out[t]) @ W`` on dense MXFP4 weights ``blocks`` [N, K/2] / ``scales`` [N, K/32]:
+    ``moe_backward_input_mxfp4`` on the one-expert view without a table.  ``grad_out`` [T, N] float32 or bfloat16 -> [T, K]
+    ``out_dtype`` (default float32)."""
+    if blocks.dim() != 2 or scales.dim() != 2:
+        raise RuntimeError("blocks must be uint8 [N, K/2] and scales uint8 [N, K/32]")
+    return moe_backward_input_mxfp4(blocks[None], scales[None], grad_out, None, None, out_dtype=out_dtype)
 
 
 ROUTE_MAX_EXPERTS = 128

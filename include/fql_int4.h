@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 410 /* 0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 420 /* 0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1138,6 +1138,50 @@ FQL_API int fql_moe_mx4_lora_bwd_input(const uint8_t *blocks, const uint8_t *sca
                                        const float *lora_rows, const float *lora_A, int rank, const int32_t *tokens_per_expert,
                                        const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
                                        void *stream);
+
+/* ---- a dense MXFP4 linear layer, with a split-K decode form (FQL_VERSION 420; INTEGRATION.md section 17, DESIGN.md
+ *      section 36; csrc/fql_gemm_mx4_linear.h) ----
+ * One MXFP4 matrix, no experts: blocks [N][K / 2] and scales_e8m0 [N][K / 32] in the encoding of fql_moe_mx4_fwd.
+ * fql_linear_mx4_fwd:     out[t][n] = sum_k bf16(x[t][k]) * W[n][k] (+ bias[n]); inputs [T][K] float32 or bfloat16, bias [N]
+ *                         float32 or NULL, out [T][N] of out_dtype, rounded once.
+ * fql_linear_mx4_glu_fwd: the same on h = bf16(act(gate_up[t][k], gate_up[t][K + k])), gate_up [T][2K], by
+ *                         fql_moe_mx4_glu_fwd's pre-pass into the workspace.
+ *   split_k == 0 is exactly fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd with E = 1 and no table: the same launchers, the same
+ *   choice between the decode and the tile kernel, the same bits, and the guarantee stated there at every T.
+ *   split_k != 0 applies when 0 < T <= a threshold built into the library (FQL_MX4_LINEAR_DECODE_MAX_ROWS in csrc/fql_mx4.hip,
+ *   set from a measurement) and S(K, N) > 1.  S, the number of slices, is a pure function of K and N, one of 1, 2, 4, 8, 16:
+ *   never of T, of the device or of any state but the tuning hook.  Then the decode kernel runs once per slice of K
+ *   (slice s takes the 64-k pairs [s * ceil(P / S), min(P, (s + 1) * ceil(P / S))), P = K / 64, in ascending order on an
+ *   accumulator that starts at zero; the odd block of K % 64 == 32 is the last slice's) into float32 partial sums in the
+ *   workspace, and a second launch on the same stream computes
+ *       out[t][n] = round( (((p_0 + p_1) + p_2) + ... + p_{S-1}) + bias[n] )
+ *   in float32, in that order, with one rounding.  No atomics; launches are the only synchronisation.  Every other call
+ *   with split_k set takes the split_k == 0 path.
+ *   THE CONTRACT with split_k set: a row's result depends on its own row, the weights, K and N.  It does not depend on T
+ *   or on the row's position; it is run-to-run identical, and every T up to the threshold gives the same bits.  It is NOT
+ *   the tile kernel's bit pattern (the float32 sums are associated otherwise), so a row's bits may change as T crosses the
+ *   threshold; both sides are within the float32 bound of DESIGN.md section 25 of the exact product.  split_k == 0 keeps
+ *   that section's guarantee at every T.
+ *   Non-finite values, float16 rows, scale codes 0, 1, 254 and 255: fql_moe_mx4_fwd's rules in both forms (a slice whose
+ *   part of a row is non-finite stores NaN for the whole partial row, so the sum carries the rule).
+ *   Workspace: fql_linear_mx4_workspace_bytes(T, K, N, gated, split_k), 16-byte aligned: the [T][K] bfloat16 h of a gated
+ *   call (fql_moe_mx4_workspace_bytes' layout), then, with split_k set and 0 < T <= the threshold, 16 * T * N float32 of
+ *   partial sums (sized for the largest S whatever S(K, N) is).  0 bytes when neither applies; then workspace may be NULL.
+ *   Return codes, in fql_moe_mx4_fwd's order with E = 1 and all before any HIP call: FQL_ERR_BAD_SHAPE (T < 0, K <= 0, N < 0;
+ *   glu: the activation); FQL_ERR_ODD_K; FQL_ERR_BAD_SHAPE (K % 32 != 0); FQL_ERR_DTYPE; T == 0 or N == 0: FQL_OK with nothing
+ *   launched; FQL_ERR_NULL_POINTER (blocks, scales_e8m0, inputs / gate_up, out); FQL_ERR_BAD_SHAPE (T > 4194240);
+ *   FQL_ERR_ALIGNMENT (blocks not 16-byte aligned; inputs / gate_up / out not aligned to their element, bias not to 4
+ *   bytes); FQL_ERR_WORKSPACE (a non-empty workspace NULL, misaligned or short); FQL_ERR_LAUNCH.
+ *   The input gradient is fql_moe_mx4_bwd_input with E = 1 and no table.  fql_int4_tune.h: fql_tune_set_mx4_linear_decode_max_rows,
+ *   fql_tune_set_mx4_linear_slices and fql_tune_mx4_linear_kernel force and report the choice (tools and tests). */
+FQL_API size_t fql_linear_mx4_workspace_bytes(int T, int K, int N, int gated, int split_k);
+FQL_API int fql_linear_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
+                               const float *bias, void *out, int out_dtype, int T, int K, int N, int split_k, void *workspace,
+                               size_t workspace_bytes, void *stream);
+FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
+                                   const float *bias, void *out, int out_dtype, int T, int K, int N, int activation,
+                                   float act_alpha, float act_limit, int split_k, void *workspace, size_t workspace_bytes,
+                                   void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -71,6 +71,17 @@ FQL_API int fql_tune_set_mx4_f6_decode_max_rows(int rows);
 /* 0: those entries would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
 FQL_API int fql_tune_mx4_f6_kernel(int E, int T, int K, int N);
 
+/* The dense MXFP4 linear entries (fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd; fql_int4.h, FQL_VERSION 420) with split_k set.
+ * fql_tune_set_mx4_linear_decode_max_rows: rows (T) up to which the split form runs; 0 never; returns the previous value, a
+ * negative `rows` changes nothing.  fql_linear_mx4_workspace_bytes follows it. */
+FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows);
+/* The slices S of the split form: 0 the library's policy S(K, N), or one of 1 / 2 / 4 / 8 / 16 to force S for every shape
+ * (1: no split form).  Any other value changes nothing.  Returns the previous value. */
+FQL_API int fql_tune_set_mx4_linear_slices(int slices);
+/* What a call with split_k set would run on this shape now: (S << 8) | form, form 0 the 64 x 128 tile kernel, 1 the grouped
+ * decode kernel (both with S = 1: the split_k == 0 path), 2 the split form with S slices.  Keeps no state. */
+FQL_API int fql_tune_mx4_linear_kernel(int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

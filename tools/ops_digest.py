@@ -21,7 +21,9 @@ the ones they always were, the four gated ops, the gated FFN layers and the spar
 precisions, ``moe_forward_mxfp4_fp8`` and ``moe_forward_mxfp4_fp4``, float32 and bfloat16 rows, with and without a bias, each
 once on its decode kernel and once on its tile kernel (forced through the tuning hooks), then ``quantize_rows_mxfp4`` plain
 and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision="fp6"``, ``moe_forward_mxfp4_fp6`` and
-``quantize_rows_mxfp6``."""
+``quantize_rows_mxfp6``; and behind those the dense MXFP4 linear ops on one expert's matrix and 16 rows:
+``linear_forward_mxfp4`` and ``linear_gated_forward_mxfp4`` with the tile kernel, the grouped decode kernel and the split
+form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``."""
 import argparse
 import hashlib
 import os
@@ -429,6 +431,39 @@ def calls(dev, fq, ops):
     for dt in (F32, BF16):
         yield f"quantize_rows_mxfp6 {dt}", lambda: ops.quantize_rows_mxfp6(x.to(dt))
         yield f"quantize_rows_mxfp6 gated {dt}", lambda: ops.quantize_rows_mxfp6(gu.to(dt), **glu)
+
+    # the dense MXFP4 linear ops, behind the lines above (no new random draw: expert 0's matrix, the first 16 rows): the same
+    # K = 96 (one pair and the odd block) and N = 40, each form forced in turn: the tile kernel and the grouped decode
+    # kernel through split_k=False, then the split form at 2 and at 16 slices
+    def forced_linear(which, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = (lib.fql_tune_set_mx4_decode_max_rows(0 if which == "tile" else 2 ** 31 - 1),
+                   lib.fql_tune_set_mx4_linear_decode_max_rows(2 ** 31 - 1),
+                   lib.fql_tune_set_mx4_linear_slices({"split2": 2, "split16": 16}.get(which, 1)))
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_mx4_decode_max_rows(old[0])
+                lib.fql_tune_set_mx4_linear_decode_max_rows(old[1])
+                lib.fql_tune_set_mx4_linear_slices(old[2])
+        return run
+
+    Pl, Sl, bl = Pm[0], Sm[0], biasm[0]
+    for which in ("tile", "decode", "split2", "split16"):
+        split = which.startswith("split")
+        for btag, b in (("", None), (" bias", bl)):
+            for dt in (F32, BF16):
+                tag = f"{dt}{btag} {which}"
+                yield f"linear_forward_mxfp4 {tag}", forced_linear(which, lambda: ops.linear_forward_mxfp4(
+                    Pl, Sl, x[:16].to(dt), bias=b, split_k=split))
+                yield f"linear_gated_forward_mxfp4 {tag}", forced_linear(which, lambda: ops.linear_gated_forward_mxfp4(
+                    Pl, Sl, gu[:16].to(dt), bias=b, split_k=split, **glu))
+                yield f"linear_forward_mxfp4 {tag} ->f16", forced_linear(which, lambda: ops.linear_forward_mxfp4(
+                    Pl, Sl, x[:16].to(dt), bias=b, out_dtype=F16, split_k=split))
+    for dt in (F32, BF16):
+        yield f"linear_backward_input_mxfp4 {dt}", lambda: ops.linear_backward_input_mxfp4(Pl, Sl, gy[:16].to(dt))
 
 
 def digest(t):
