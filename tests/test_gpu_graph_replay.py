@@ -24,7 +24,14 @@ expert) is captured once and replayed while its routing changes by itself: new t
 a mask with one real token.  The block is held to its tests' dense float64 sum over the same expert module and, because a
 stale table inside that module would be shared by both sides, to float64 torch on the dequantised weights as well.
 
-Every family asserts the kernel id the library reports for its shape (fql_tune_chosen_cfg / fql_tune_mx4_kernel): if a
+The MXFP4 experts run in every precision under BOTH kernel forms pinned (bf16, fp8, fp4 and fp6 rows; the unpinned fp8
+and fp4 families stay as they were), the fused adapter entries (ops.moe_forward_mxfp4_lora / moe_gated_forward_mxfp4_lora /
+moe_backward_input_mxfp4_lora, with NaN shrunk rows where a scene leaves a row uncovered) go through the same scenes, the
+block also wraps LoRAMXFP4MoEFFN experts, and the dense ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4, which have
+no expert table, replay their split form (two launches and a partial-sum workspace) over changing rows.
+
+Every family asserts the kernel id the library reports for its shape (fql_tune_chosen_cfg / fql_tune_mx4_kernel /
+fql_tune_mx4_scaled_kernel / fql_tune_mx4_f6_kernel / fql_tune_mx4_linear_kernel; the adapter entries have one form): if a
 heuristic change moves the call, the test says so instead of silently testing another kernel.  test_gpu_side_stream.py
 runs the same families on side streams."""
 import functools
@@ -34,22 +41,27 @@ import pytest
 import torch
 
 from glu_reference import ALPHA, LIMIT, act_kw, hidden64
-from helpers import (EXACT_REL_FRO, FAST_REL_FRO, FMA_REL_FRO, FP8_ACC_SCALED_REL_FRO, SENT, clipped_ranges, dequant_f64,
-                     expert_table, first_diff, fq, heavy_rows, ops, rel_fro_dev, same_bits)
+from helpers import (EXACT_REL_FRO, FAST_REL_FRO, FMA_REL_FRO, FP8_ACC_SCALED_REL_FRO, NAN, SENT, clipped_ranges, dequant_f64,
+                     expert_table, first_diff, fq, heavy_rows, ops, rel_fro_dev, same_bits, uncovered_mask)
 from test_gpu_expert_bias_layers import FFN_REL_FRO
 from test_gpu_group_bwd import TABLES as BWD_TABLES, problem as group_bwd_problem
 from test_gpu_group_moe_ops import FL, I8, problem as group_problem
 from test_gpu_mxfp4 import GATED_BOUND as MX4_GATED_BOUND
 from test_gpu_mxfp4_decode import SAME_INPUT_BOUND as MX4_BOUND, problem as mx4_problem
 from test_gpu_mxfp4_f4 import SAME_INPUT_BOUND as MX4_Q_BOUND, q_host
+from test_gpu_mxfp4_f6 import SAME_INPUT_BOUND as MX6_BOUND, q_host as q6_host
 from test_gpu_mxfp4_f8 import quantise
+from test_gpu_mxfp4_linear import gaussian_bound as linear_bound, own_hidden as linear_own_hidden, problem as linear_problem
+from test_gpu_mxfp4_lora import SAME_INPUT_BOUND as LORA_BASE_BOUND, bound as lora_bound
 from test_route_capped_cpu import plan_reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 INT_MAX = 2 ** 31 - 1
 BLOCK_REL = 4e-6                    # the block against its dense float64 sum (tests/test_gpu_sparse_moe_block_capped.py REL)
-assert MX4_BOUND == 2.64e-7 and MX4_Q_BOUND == 3e-5
+assert MX4_BOUND == 2.64e-7 and MX4_Q_BOUND == 3e-5 and MX6_BOUND == 3e-5 and LORA_BASE_BOUND == MX4_BOUND
+MX4_MODE = {"fp8": 1, "fp4": 2}     # the mode of fql_tune_set_mx4_scaled_decode_max_rows / fql_tune_mx4_scaled_kernel
+FORM = {"tile": 0, "decode": 1}     # what fql_tune_mx4_kernel / _scaled_kernel / _f6_kernel report
 
 
 def lib():
@@ -59,21 +71,40 @@ def lib():
 
 @pytest.fixture
 def tune():
-    """tune(mx4="decode" | "tile", w4=0 | 1): the library's kernel choice for this test; its own comes back afterwards."""
+    """tune(mx4="decode" | "tile", w4=0 | 1, scaled=("fp8" | "fp4", "decode" | "tile"), f6="decode" | "tile",
+    linear=(rows of the split range, slices S)): the library's kernel choice for this test; its own comes back afterwards."""
     L = lib()
+    rows_of = {"decode": INT_MAX, "tile": 0}
     decode = L.fql_tune_set_mx4_decode_max_rows(-1)                  # (a negative value changes nothing)
+    scaled_was = {mode: L.fql_tune_set_mx4_scaled_decode_max_rows(mode, -1) for mode in MX4_MODE.values()}
+    f6_was = L.fql_tune_set_mx4_f6_decode_max_rows(-1)
+    lin_rows = L.fql_tune_set_mx4_linear_decode_max_rows(-1)
+    lin_slices = L.fql_tune_set_mx4_linear_slices(0)
+    L.fql_tune_set_mx4_linear_slices(lin_slices)
     w4 = L.fql_tune_set_w4(1)
     L.fql_tune_set_w4(w4)
 
-    def use(mx4=None, w4=None):
+    def use(mx4=None, w4=None, scaled=None, f6=None, linear=None):
         if mx4 is not None:
-            L.fql_tune_set_mx4_decode_max_rows({"decode": INT_MAX, "tile": 0}[mx4])
+            L.fql_tune_set_mx4_decode_max_rows(rows_of[mx4])
         if w4 is not None:
             L.fql_tune_set_w4(w4)
+        if scaled is not None:
+            L.fql_tune_set_mx4_scaled_decode_max_rows(MX4_MODE[scaled[0]], rows_of[scaled[1]])
+        if f6 is not None:
+            L.fql_tune_set_mx4_f6_decode_max_rows(rows_of[f6])
+        if linear is not None:
+            L.fql_tune_set_mx4_linear_decode_max_rows(linear[0])
+            L.fql_tune_set_mx4_linear_slices(linear[1])
     try:
         yield use
     finally:
         L.fql_tune_set_mx4_decode_max_rows(decode)
+        for mode, rows in scaled_was.items():
+            L.fql_tune_set_mx4_scaled_decode_max_rows(mode, rows)
+        L.fql_tune_set_mx4_f6_decode_max_rows(f6_was)
+        L.fql_tune_set_mx4_linear_decode_max_rows(lin_rows)
+        L.fql_tune_set_mx4_linear_slices(lin_slices)
         L.fql_tune_set_w4(w4)
 
 
@@ -362,9 +393,21 @@ def mx4_W(p):
     return dequantize_mxfp4(p["blocks"].cpu(), p["scales"].cpu()).double().to(DEV)
 
 
+def mx4_form(precision, kernel, E, T, K, N):
+    """(kernel() of a Family, the arguments of the tune fixture) that pin ``precision`` to the "tile" or the "decode" form."""
+    want = FORM[kernel]
+    if precision == "bf16":
+        return (lambda: (lib().fql_tune_mx4_kernel(E, T, K, N), want)), dict(mx4=kernel)
+    if precision == "fp6":
+        return (lambda: (lib().fql_tune_mx4_f6_kernel(E, T, K, N), want)), dict(f6=kernel)
+    return (lambda: (lib().fql_tune_mx4_scaled_kernel(MX4_MODE[precision], E, T, K, N), want)), dict(scaled=(precision, kernel))
+
+
 def mx4_forward(K, N, precision, kernel=None):
     """precision "bf16" (forced to the tile or the decode kernel): integer rows in [-4, 4] and scale codes in [125, 129],
-    the float32 result is exact; "fp8" / "fp4": randn rows against the float64 product of the same quantised values."""
+    the float32 result is exact; "fp8" / "fp4" / "fp6" (``kernel`` None: whatever form the library picks, not asserted):
+    randn rows against the float64 product of the values the host rule of the precision makes of them
+    (tests/test_gpu_mxfp4_f8.py quantise, tests/test_gpu_mxfp4_f4.py and tests/test_gpu_mxfp4_f6.py q_host)."""
     exact = precision == "bf16"
     p = mx4_problem(K, N, lo=125, hi=129, integer=True) if exact else mx4_problem(K, N)
     E, T, W = p["E"], p["T"], mx4_W(p)
@@ -379,32 +422,44 @@ def mx4_forward(K, N, precision, kernel=None):
                                        precision=precision)
 
     def reference(rows, ranges):
-        x64 = rows[0].double() if exact else (quantise(rows[0]) if precision == "fp8" else q_host(rows[0]))[2].to(DEV)
+        host = {"fp8": quantise, "fp4": q_host, "fp6": q6_host}
+        x64 = rows[0].double() if exact else host[precision](rows[0])[2].to(DEV)
         ref = grouped64(x64, lambda e: W[e].t(), ranges, N, p["bias"])
         assert not exact or float(ref.abs().max()) < 2 ** 15        # (every partial sum then fits float32 exactly)
         return ref
 
-    which = None if kernel is None else (lambda: (lib().fql_tune_mx4_kernel(E, T, K, N), {"tile": 0, "decode": 1}[kernel]))
-    return Family(E, T, MX4_RAGGED, make_rows, call, reference, None if exact else MX4_Q_BOUND, which,
-                  None if kernel is None else dict(mx4=kernel))
+    which, pin = (None, None) if kernel is None else mx4_form(precision, kernel, E, T, K, N)
+    bound = None if exact else (MX6_BOUND if precision == "fp6" else MX4_Q_BOUND)
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, bound, which, pin)
 
 
-def mx4_gated(K, N, kernel):
+def mx4_gated(K, N, kernel, precision="bf16"):
+    """"bf16": against the bfloat16-rounded float64 h.  "fp6": h goes through the gated MXFP6 quantiser, whose float32 h
+    lands on the other e2m3 neighbour of the float64 h for a code in a thousand (tests/test_gpu_mxfp4_f6.py holds it to
+    quantize_mxfp6 of the float64 h within GATED_CODE_CAP), one step of 2^-4 of that element; so the reference is the
+    float64 product of the values of ops.quantize_rows_mxfp6's own codes (dequantize_mxfp6 on the host), at the same-value
+    bound of that file: the GEMM, its table and its workspace are what a replay can get wrong."""
     p = mx4_problem(K, N)
     E, T, W = p["E"], p["T"], mx4_W(p)
+    kw = {} if precision == "bf16" else dict(precision=precision)
 
     def make_rows(seed):
         return ((2.0 * torch.randn(T, 2 * K, generator=gen(seed, K, N, 1))).to(DEV),)
 
     def call(gate_up, tpe, offs):
         return ops().moe_gated_forward_mxfp4(p["blocks"], p["scales"], gate_up, tpe, offs, bias=p["bias"],
-                                             out_dtype=torch.float32, **act_kw("swiglu_clamp"))
+                                             out_dtype=torch.float32, **kw, **act_kw("swiglu_clamp"))
 
-    def reference(rows, ranges):                                     # the bfloat16-rounded float64 h (tests/test_gpu_mxfp4.py)
-        h = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double()
+    def reference(rows, ranges):
+        if precision == "fp6":
+            from fused_int4_amd.quantize import dequantize_mxfp6
+            hc, hs = ops().quantize_rows_mxfp6(rows[0], **act_kw("swiglu_clamp"))
+            h = dequantize_mxfp6(hc.cpu(), hs.cpu()).double().to(DEV)
+        else:                                                        # the bfloat16-rounded float64 h (tests/test_gpu_mxfp4.py)
+            h = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double()
         return grouped64(h, lambda e: W[e].t(), ranges, N, p["bias"])
-    return Family(E, T, MX4_RAGGED, make_rows, call, reference, MX4_GATED_BOUND,
-                  lambda: (lib().fql_tune_mx4_kernel(E, T, K, N), {"tile": 0, "decode": 1}[kernel]), dict(mx4=kernel))
+    which, pin = mx4_form(precision, kernel, E, T, K, N)
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, MX6_BOUND if precision == "fp6" else MX4_GATED_BOUND, which, pin)
 
 
 def mx4_backward(K, N):
@@ -420,6 +475,67 @@ def mx4_backward(K, N):
     def reference(rows, ranges):
         return grouped64(rows[0].bfloat16().double(), lambda e: W[e], ranges, K)
     return Family(E, T, MX4_RAGGED, make_rows, call, reference, MX4_BOUND)
+
+
+def scene_uncovered(E, T, ragged):
+    """seed of a scene's rows -> bool [T], the rows no expert of that scene covers (S0 and S7 share seed and table)."""
+    return {seed: uncovered_mask(clipped_ranges(tpe, offs, T), T) for _, tpe, offs, seed in scenes(E, T, ragged)}
+
+
+def mx4_lora(K, N, r, kind):
+    """The adapter stage fused into the MXFP4 GEMMs (tests/test_gpu_mxfp4_lora.py): ``kind`` "fwd" (rows (x, v)), "glu"
+    ((gate_up, v)) or "bwd" ((gy, dv)); the adapter matrix B [E, N, r] / A [E, r, K] is fixed.  "fwd" and "bwd": that file's
+    integer recipe, rows and shrunk rows in [-4, 4], adapter integers in [-2, 2], scale codes 125 .. 129: every product is a
+    multiple of 2^-3 and every sum stays below 2^17 (asserted), so the float32 result is the float64 reference.  "glu":
+    Gaussian data against the float64 sum of both products on the bfloat16-rounded operands, at MX4_GATED_BOUND scaled by
+    that file's rule for K + r terms.  The shrunk rows of the rows a scene leaves uncovered are NaN (S3 .. S6): an adapter
+    row read under the wrong t shows.  The adapter entries have one kernel form (no decode kernel, nothing to report)."""
+    exact = kind != "glu"
+    p = mx4_problem(K, N, lo=125, hi=129, integer=True) if exact else mx4_problem(K, N)
+    E, T, W = p["E"], p["T"], mx4_W(p)
+    assert (E, T) == (5, 73)
+    uncovered = scene_uncovered(E, T, MX4_RAGGED)
+    assert all(bool(uncovered[s].any()) for s in (3, 4, 5)) and not bool(uncovered[0].any())   # (S6's clipped count takes the tail)
+    g0 = gen(0, K, N, r, 7)
+    C = N if kind == "bwd" else K                                   # the contraction of the base product
+    if exact:
+        M = torch.randint(-2, 3, (E, r, K) if kind == "bwd" else (E, N, r), generator=g0).float().to(DEV)
+    else:                                                            # sized so that the adapter term is of the base term's size
+        M = torch.randn(E, N, r, generator=g0).to(DEV) * (W.square().mean(dim=2, keepdim=True).sqrt() * (C / r) ** 0.5).float()
+    M64 = M.bfloat16().double()
+
+    def make_rows(seed):
+        g = gen(seed, K, N, r, len(kind))
+        if kind == "glu":
+            rows, v = 2.0 * torch.randn(T, 2 * K, generator=g), torch.randn(T, r, generator=g)
+        else:
+            rows, v = torch.randint(-4, 5, (T, C), generator=g).float(), torch.randint(-4, 5, (T, r), generator=g).float()
+        v[uncovered[seed]] = NAN
+        return rows.to(DEV), v.to(DEV)
+
+    def call(rows, v, tpe, offs):
+        if kind == "fwd":
+            return ops().moe_forward_mxfp4_lora(p["blocks"], p["scales"], rows, v, M, tpe, offs, bias=p["bias"],
+                                                out_dtype=torch.float32)
+        if kind == "glu":
+            return ops().moe_gated_forward_mxfp4_lora(p["blocks"], p["scales"], rows, v, M, tpe, offs, bias=p["bias"],
+                                                      out_dtype=torch.float32, **act_kw("swiglu_clamp"))
+        return ops().moe_backward_input_mxfp4_lora(p["blocks"], p["scales"], rows, v, M, tpe, offs)
+
+    def reference(rows, ranges):
+        x64 = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double() if kind == "glu" else rows[0].double()
+        v64 = rows[1].bfloat16().double()
+        if kind == "bwd":
+            ref = grouped64(x64, lambda e: W[e], ranges, K) + grouped64(v64, lambda e: M64[e], ranges, K)
+        else:
+            base = grouped64(x64, lambda e: W[e].t(), ranges, N, p["bias"])
+            ref = base + grouped64(v64, lambda e: M64[e].t(), ranges, N)
+            assert not ranges or torch.equal(ref, base) == all(hi <= lo for lo, hi in ranges)     # (the adapter matters)
+        assert bool(torch.isfinite(ref).all()) and (not exact or float(ref.abs().max()) < 2 ** 17)
+        return ref
+
+    bound = None if exact else MX4_GATED_BOUND * lora_bound(K, r) / LORA_BASE_BOUND
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, bound)
 
 
 # ---- the families, by name (tests/test_gpu_side_stream.py takes its cases from here)
@@ -469,11 +585,99 @@ for _K, _N in ((288, 136), (96, 37)):
         f"mx4-K{_K}-N{_N}-glu-decode": functools.partial(mx4_gated, _K, _N, "decode"),
         f"mx4-K{_K}-N{_N}-bwd": functools.partial(mx4_backward, _K, _N),
     })
+    for _prec in ("fp8", "fp4", "fp6"):                             # the block-scaled precisions, both forms pinned
+        for _form in ("tile", "decode"):
+            FAMILIES[f"mx4-K{_K}-N{_N}-{_prec}-{_form}"] = functools.partial(mx4_forward, _K, _N, _prec, _form)
+    FAMILIES[f"mx4-K{_K}-N{_N}-fp6-glu-decode"] = functools.partial(mx4_gated, _K, _N, "decode", "fp6")
+for _K, _N, _r in ((288, 136, 16), (96, 37, 64)):                   # (r = 16: one 16-j step of the adapter stage, 64: all four)
+    for _kind in ("fwd", "glu", "bwd"):
+        FAMILIES[f"mx4-lora-{_kind}-K{_K}-N{_N}-r{_r}"] = functools.partial(mx4_lora, _K, _N, _r, _kind)
 
 
 @pytest.mark.parametrize("name", list(FAMILIES))
 def test_one_graph_serves_every_routing(tune, name):
     replay_scenes(FAMILIES[name](), tune)
+
+
+# ---- the dense MXFP4 linear op: no expert table; two launches (three when gated) and a partial-sum workspace
+
+LINEAR_T, LINEAR_N = 2, 136
+LINEAR_CASES = {"plain-K288-S4": (288, 4, False), "gated-K288-S4": (288, 4, True), "plain-K96-S16": (96, 16, False)}
+
+
+def linear_case(name, tune):
+    """(call(rows) -> [T, N] float32, make_rows(seed), reference(rows) -> float64, bound or None) of one of LINEAR_CASES,
+    with the split range opened and S forced (the kernel the library then reports is asserted).  Plain: the integer recipe
+    of tests/test_gpu_mxfp4_linear.py, rows in [-4, 4], scale codes 125 .. 129, a bias in [-8, 8], every sum below 2^17
+    (asserted): the float32 result is the float64 reference whatever the order of the S partial sums.  Gated: Gaussian
+    gate | up rows; the reference is the float64 product of the bfloat16 h the grouped gated op itself forms (that file's
+    own_hidden, asserted here to lie within one bfloat16 rounding of the float64 h), at that file's Gaussian bound.  At
+    K = 96 there is one pair of blocks and an odd one: S = 16 leaves fourteen slices with nothing to do."""
+    K, S, gated = LINEAR_CASES[name]
+    T, N = LINEAR_T, LINEAR_N
+    tune(linear=(128, S))
+    got = lib().fql_tune_mx4_linear_kernel(T, K, N)
+    assert (got >> 8, got & 0xFF) == (S, 2), f"the library reports (S, form) = {(got >> 8, got & 0xFF)}, the test is written for {(S, 2)}"
+    p = linear_problem(K, N, integer=not gated)
+    W, bias64 = p["W"].to(DEV), p["bias"].double()
+
+    def make_rows(seed):
+        g = gen(seed, K, N, S)
+        return (2.0 * torch.randn(T, 2 * K, generator=g) if gated else torch.randint(-4, 5, (T, K), generator=g).float()).to(DEV)
+
+    def call(rows):
+        if gated:
+            return ops().linear_gated_forward_mxfp4(p["blocks"], p["scales"], rows, bias=p["bias"], out_dtype=torch.float32,
+                                                    split_k=True, **act_kw("swiglu_clamp"))
+        return ops().linear_forward_mxfp4(p["blocks"], p["scales"], rows, bias=p["bias"], out_dtype=torch.float32, split_k=True)
+
+    def reference(rows):
+        if not gated:
+            ref = rows.double() @ W.T + bias64
+            assert float(ref.abs().max()) < 2 ** 17
+            return ref
+        h, h64 = linear_own_hidden(rows, "swiglu_clamp").double(), hidden64("swiglu_clamp", rows, ALPHA, LIMIT)
+        assert bool(((h - h64).abs() <= 2.0 ** -8 * h64.abs() + 2.0 ** -126).all())
+        return h @ W.T + bias64
+    return call, make_rows, reference, linear_bound(K) if gated else None
+
+
+@pytest.mark.parametrize("name", list(LINEAR_CASES))
+def test_dense_linear_split_form_replays(tune, name):
+    """ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4(split_k=True) at T = 2, N = 136, captured once and replayed
+    over four row sets, the last equal to the first, with SENT in the output before each replay.  The split form is
+    mx4_linear_decode_kernel into partial[S][T][N] and then mx4_linear_reduce_kernel, behind the pre-pass that writes h in
+    the gated entry; the launch boundaries are the only synchronisation and the workspace lives in the graph's pool.  A
+    launch that left the capture stream is a capture error or a node missing from the graph, which shows as SENT or as the
+    previous row set's sums."""
+    call, make_rows, reference, bound = linear_case(name, tune)
+    static = make_rows(0).clone()
+    graph, out, _ = capture(call, [static])
+    try:
+        first = None
+        for i, seed in enumerate((0, 1, 2, 0)):
+            rows = make_rows(seed)
+            static.copy_(rows)
+            out.fill_(SENT)
+            graph.replay()
+            torch.cuda.synchronize()
+            got = out.clone()
+            eager = call(rows.clone())
+            assert same_bits(got, eager), (i, first_diff(got, eager))
+            ref = reference(rows)
+            if bound is None:
+                assert torch.equal(got.double(), ref), f"replay {i}: not the exact integer result"
+            else:
+                err = rel_fro_dev(got, ref)
+                print(f"dense linear {name} replay {i}: rel_fro {err:.3e} (bound {bound:.2e})")
+                assert err <= bound, (i, err)
+            if i == 0:
+                first = got
+            elif i < 3:
+                assert not same_bits(got, first)                     # (the row sets are different problems)
+        assert same_bits(got, first), "the first row set again does not carry the bits of its first replay"
+    finally:
+        del graph
 
 
 # ---- the scratch of the two-phase API, first taken inside a capture
@@ -522,6 +726,7 @@ def test_first_gemm_i8_inside_a_capture_then_eager_then_replay():
 # ---- the whole block: the routing changes by itself
 
 BE, BH, BF, BTOPK = 4, 64, 96, 2
+BRANK = 16                          # the rank of the "mxfp4-lora" block's adapters
 
 
 def block_weights():
@@ -533,13 +738,22 @@ def block_weights():
 
 
 def build_block(kind, capped):
-    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared" or "mxfp4" experts (swiglu_clamp with
-    expert biases); ``capped``: capacity_factor = 1 (the forward then takes a token mask too)."""
+    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared", "mxfp4" or "mxfp4-lora" experts
+    (swiglu_clamp with expert biases; "mxfp4-lora": LoRAMXFP4MoEFFN of rank BRANK around the same MXFP4 experts, with random
+    values in BOTH B matrices -- a fresh adapter has B = 0 and would test nothing); ``capped``: capacity_factor = 1 (the
+    forward then takes a token mask too)."""
     w = block_weights()
     factor = 1.0 if capped else None
-    if kind == "mxfp4":
+    if kind in ("mxfp4", "mxfp4-lora"):
         experts = fq().MXFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
-                                                down_bias=w["db"], **act_kw("swiglu_clamp"))
+                                                down_bias=w["db"], input_grad=kind == "mxfp4-lora", **act_kw("swiglu_clamp"))
+        if kind == "mxfp4-lora":
+            torch.manual_seed(43)                                    # (the adapters' A)
+            experts = fq().LoRAMXFP4MoEFFN.from_layer(experts, BRANK, alpha=2.0 * BRANK)
+            g = torch.Generator().manual_seed(44)
+            with torch.no_grad():
+                experts.gate_up_lora_B.copy_(torch.randn(experts.gate_up_lora_B.shape, generator=g) * 0.2)
+                experts.down_lora_B.copy_(torch.randn(experts.down_lora_B.shape, generator=g) * 0.2)
         m = fq().QuantizedSparseMoEBlock(BE, BH, BF, top_k=BTOPK, experts=experts, router_bias=True, capacity_factor=factor)
         with torch.no_grad():
             m.gate.weight.copy_(w["gate_w"])
@@ -572,10 +786,15 @@ def block_reference(m, x, mask):
     return out, idx, terms.abs().sum(dim=1) + (0 if s is None else s.double().abs()), keep, w
 
 
-def ffn64(mod, e, x64, mx4):
+def ffn64(mod, e, x64, mx4, raw64=None):
     """float64 [T, H]: expert ``e`` of a gated FFN module on every row of ``x64``, on its dequantised weights, with no
     kernel of the library and no expert table: gate_up (+ bias), swiglu_clamp, down (+ bias).  ``mx4``: the roundings of
-    tests/test_gpu_mxfp4.py's block reference (gate_up kept in float32, h rounded to bfloat16)."""
+    tests/test_gpu_mxfp4.py's block reference (gate_up kept in float32, h rounded to bfloat16).  A module with adapters
+    (``raw64``: the rows before their rounding to bfloat16) adds the two adapter terms with the kernels' roundings: the
+    shrunk rows v = s A x (ops.lora_shrink on the unrounded rows) and v = s A h (ops.lora_gated_shrink on the float32 h)
+    kept in float32, then v and B rounded to bfloat16 on their way into the GEMM."""
+    lora = hasattr(mod, "gate_up_lora_A")
+    term = lambda rows, A, B: (mod.scaling * (rows @ A[e].double().t())).float().bfloat16().double() @ B[e].bfloat16().double().t()
     if mx4:
         from fused_int4_amd.quantize import dequantize_mxfp4
         Wgu = dequantize_mxfp4(mod.gate_up_blocks[e:e + 1].cpu(), mod.gate_up_scales[e:e + 1].cpu())[0].double().to(DEV)
@@ -585,8 +804,11 @@ def ffn64(mod, e, x64, mx4):
         Wd = dequant_f64(mod.down_packed[e], mod.down_scales[e], mod.down_zero_points[e])
     b_gu, b_d = getattr(mod, "gate_up_bias", None), getattr(mod, "down_bias", None)
     gu = x64 @ Wgu.t() + (0 if b_gu is None else b_gu[e].double())
+    if lora:
+        gu = gu + term(raw64, mod.gate_up_lora_A.detach(), mod.gate_up_lora_B.detach())
     h = hidden64("swiglu_clamp", gu.float() if mx4 else gu, ALPHA, LIMIT)
-    return (h.bfloat16().double() if mx4 else h) @ Wd.t() + (0 if b_d is None else b_d[e].double())
+    y = (h.bfloat16().double() if mx4 else h) @ Wd.t() + (0 if b_d is None else b_d[e].double())
+    return y + term(h, mod.down_lora_A.detach(), mod.down_lora_B.detach()) if lora else y
 
 
 def block_float64(m, x, idx, keep, w, mx4):
@@ -594,7 +816,7 @@ def block_float64(m, x, idx, keep, w, mx4):
     x64 = x.bfloat16().double() if mx4 else x.double()
     out = torch.zeros(x.shape[0], BH, dtype=torch.float64, device=DEV)
     for e in range(BE):
-        y = ffn64(m.experts, e, x64, mx4)
+        y = ffn64(m.experts, e, x64, mx4, x.double())
         for k in range(BTOPK):
             sel = (idx[:, k] == e) & keep[:, k]
             out[sel] += w[sel, k].double().unsqueeze(-1) * y[sel]
@@ -604,12 +826,16 @@ def block_float64(m, x, idx, keep, w, mx4):
 
 @pytest.mark.parametrize("T", [3, 130])
 @pytest.mark.parametrize("kind,capped", [("int4", False), ("int4", True), ("int4-shared", True), ("mxfp4", False),
-                                         ("mxfp4", True)],
-                         ids=["int4", "int4-capped", "int4-shared-capped", "mxfp4", "mxfp4-capped"])
+                                         ("mxfp4", True), ("mxfp4-lora", False), ("mxfp4-lora", True)],
+                         ids=["int4", "int4-capped", "int4-shared-capped", "mxfp4", "mxfp4-capped", "mxfp4-lora",
+                              "mxfp4-lora-capped"])
 def test_block_replays_under_changing_routing(tune, kind, capped, T):
     """QuantizedSparseMoEBlock under torch.no_grad(), captured once; then new tokens, the router bias overwritten in place
-    so that every token picks experts 2 and 0, a mask with one real token (the capped blocks) and the first scene again."""
-    m, mx4 = build_block(kind, capped), kind == "mxfp4"
+    so that every token picks experts 2 and 0, a mask with one real token (the capped blocks) and the first scene again.
+    "mxfp4-lora": the same MXFP4 experts inside LoRAMXFP4MoEFFN with both B matrices random (its output is asserted once to
+    differ from the "mxfp4" block's); the pure-float64 check adds the two adapter terms with the kernels' roundings
+    (ffn64) and is held to the MXFP4 block's own bound, MX4_GATED_BOUND, unscaled."""
+    m, mx4 = build_block(kind, capped), kind in ("mxfp4", "mxfp4-lora")
     bias0 =m.gate.bias.detach().clone()
     same_two = torch.tensor([60.0, -60.0, 120.0, -60.0], device=DEV)      # (the logits without it stay within +-20)
     xs = [torch.randn(T, BH, generator=gen(i, T)).to(DEV) for i in range(3)]
@@ -658,6 +884,11 @@ def test_block_replays_under_changing_routing(tune, kind, capped, T):
                     assert not got[~mask].any(), name                # a masked token's output is zero
                 if name == "first":
                     first = (got, got_logits)
+                    if kind == "mxfp4-lora":                         # (the adapters matter: not the wrapped experts' output)
+                        plain = build_block("mxfp4", capped)
+                        other = plain(x.clone(), token_mask=mask.clone())[0] if capped else plain(x.clone())[0]
+                        print(f"block {kind} capped={capped} T={T}: rel_fro to the mxfp4 block's output {rel_fro_dev(got, other):.3e}")
+                        assert other.shape == got.shape and not same_bits(got, other)
             assert same_bits(got, first[0]) and same_bits(got_logits, first[1])
         finally:
             del graph

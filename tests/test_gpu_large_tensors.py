@@ -1041,9 +1041,10 @@ def test_mxfp4_rows_past_4_gib(lib, gated):
 
 
 # ======================================================================= MXFP4 fp8 / fp4 / gated kernels: large WEIGHTS
-@pytest.mark.parametrize("prec,gated", [("fp8", False), ("fp4", False), ("bf16", True), ("fp8", True), ("fp4", True)])
+@pytest.mark.parametrize("prec,gated", [("fp8", False), ("fp4", False), ("bf16", True), ("fp8", True), ("fp4", True),
+                                        ("fp6", False), ("fp6", True)])
 def test_mxfp4_modes_large_weights(lib, prec, gated):
-    """The fp8-row, fp4-row and gated MXFP4 kernels on E * N * K/2 > 2^32 bytes of blocks: rows to expert 0, the two
+    """The fp8-row, fp4-row, fp6-row and gated MXFP4 kernels on E * N * K/2 > 2^32 bytes of blocks: rows to expert 0, the two
     straddling experts and E - 1, 0xFF everywhere else.  Bit for bit the same op on the four experts alone."""
     need(9)                                                   # (plain bfloat16: test_mxfp4_forward_large_weights)
     K, N, E = 512, 264, 65534
@@ -1075,6 +1076,166 @@ def test_mxfp4_modes_large_weights(lib, prec, gated):
     assert same_bits(got, want), f"mxfp4 {prec} gated={gated}: the far experts' rows differ from the four experts alone"
     assert int(torch.count_nonzero(got[223:])) == 0
     assert_guards_intact(buf, what="large MXFP4 weights, fp8 / fp4 / gated")
+    del blocks, buf
+
+
+# ======================================================================= MXFP4 experts with a fused adapter: large ADAPTERS
+LORA_R = 64
+
+
+def lora_large_shape(entry):
+    """(K, N, E, blocks' bytes an expert, adapter's bytes an expert, the experts that get rows) of the adapter cases.
+    "fwd": B [E, N, r] float32 with N = 264, r = 64 is 67584 bytes an expert, exactly the blocks' N * K/2 at K = 512, so
+    both operands pass 2^31 and 2^32 inside the same experts.  "bwd": A [E, r, K] float32 with K = 544 is 139264 bytes an
+    expert and the blocks are 71808: neither divides a boundary, and the two operands straddle in different experts, all
+    of which get rows.  Needs no GPU."""
+    N, E = 264, 65534
+    K = 512 if entry == "fwd" else 544
+    wb, ab = N * K // 2, (N if entry == "fwd" else K) * LORA_R * 4
+    assert (wb, ab) == ((67584, 67584) if entry == "fwd" else (71808, 139264))
+    experts = sorted({0, B31 // ab, B32 // ab, B31 // wb, B32 // wb, E - 1})
+    for unit in (wb, ab):
+        assert B31 % unit and B32 % unit and E * unit > B32 + 64 * unit
+        for top in (B31, B32):
+            e = top // unit
+            assert e in experts and e * unit < top < (e + 1) * unit and 0 < e < E - 1       # expert e straddles the boundary
+    assert len(experts) == (4 if entry == "fwd" else 6)
+    return K, N, E, wb, ab, experts
+
+
+def lora_large_groups(n):
+    """n row groups (33 rows, 70 rows ..., 33 rows; 5 uncovered rows between neighbours, 2 behind) and T."""
+    groups, pos = [], 0
+    for size in [33] + [70] * (n - 2) + [33]:
+        groups.append((pos, pos + size))
+        pos += size + 5
+    return groups, pos - 3
+
+
+@pytest.mark.parametrize("entry", ["fwd", "bwd"])
+def test_mxfp4_lora_large_adapters(lib, entry):
+    """ops.moe_forward_mxfp4_lora with B [E, N, 64] and ops.moe_backward_input_mxfp4_lora with A [E, 64, K] past 2^32 bytes,
+    on blocks past 2^32 bytes (``lora_large_shape``): rows go to expert 0, every expert in which either operand crosses 2^31
+    or 2^32, and E - 1.  Every other expert's adapter is NaN and its blocks and scales are 0xFF; the shrunk rows of the rows
+    no expert covers are NaN.  The integer recipe of tests/test_gpu_mxfp4_lora.py (rows and shrunk rows in [-4, 4], adapter
+    integers in [-2, 2], scale codes 125 .. 129): the float32 result IS the float64 reference.  The adapter entries have one
+    kernel form (the tile kernel; the library has no choice to report)."""
+    from fused_int4_amd.quantize import dequantize_mxfp4
+    K, N, E, wb, ab, experts = lora_large_shape(entry)
+    need(14 if entry == "fwd" else 19)
+    torch.cuda.reset_peak_memory_stats()
+    r = LORA_R
+    buf = BigGuarded("blocks", E * wb, torch.uint8, 0xFF)
+    blocks = buf.view(E, N, K // 2)
+    blocks.fill_(0xFF)
+    scales = torch.full((E, N, K // 32), 0xFF, dtype=torch.uint8, device=DEV)
+    abuf = BigGuarded("adapter", E * ab, torch.float32, NAN)
+    M = abuf.view(E, N, r) if entry == "fwd" else abuf.view(E, r, K)
+    M.fill_(NAN)
+    g = torch.Generator(device=DEV).manual_seed(24)
+    for e in experts:
+        blocks[e] = torch.randint(0, 256, (N, K // 2), generator=g, device=DEV, dtype=torch.uint8)
+        scales[e] = torch.randint(125, 130, (N, K // 32), generator=g, device=DEV, dtype=torch.uint8)
+        M[e] = torch.randint(-2, 3, tuple(M.shape[1:]), generator=g, device=DEV).float()
+    groups, T = lora_large_groups(len(experts))
+    tpe, offs = table_of(groups, E=E, experts=experts, T=T)
+    C = K if entry == "fwd" else N                            # the contraction of the base product
+    x = torch.randint(-4, 5, (T, C), generator=g, device=DEV).float()
+    v = torch.full((T, r), NAN, device=DEV)
+    for lo, hi in groups:
+        v[lo:hi] = torch.randint(-4, 5, (hi - lo, r), generator=g, device=DEV).float()
+    last = M.shape[2] * 4                                     # the bytes of the last row of an expert's adapter matrix
+    assert sum(input_wrap_is_visible(buf, (e + 1) * wb - K // 2, K // 2) for e in experts) >= len(experts) - 1
+    assert sum(input_wrap_is_visible(abuf, (e + 1) * ab - last, last // 4) for e in experts) >= len(experts) - 1
+    Ws = [dequantize_mxfp4(blocks[e:e + 1].cpu(), scales[e:e + 1].cpu())[0].double().to(DEV) for e in experts]
+    if entry == "fwd":
+        refs = [x[lo:hi].double() @ W.T + v[lo:hi].double() @ M[e].double().T for W, e, (lo, hi) in zip(Ws, experts, groups)]
+        got = ops().moe_forward_mxfp4_lora(blocks, scales, x, v, M, tpe, offs, out_dtype=torch.float32)
+    else:
+        refs = [x[lo:hi].double() @ W + v[lo:hi].double() @ M[e].double() for W, e, (lo, hi) in zip(Ws, experts, groups)]
+        got = ops().moe_backward_input_mxfp4_lora(blocks, scales, x, v, M, tpe, offs)
+    torch.cuda.synchronize()
+    print(f"mxfp4 lora {entry} large adapters: E={E} experts {experts} T={T}, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    assert all(float(ref.abs().max()) < 2 ** 17 for ref in refs)          # (multiples of 2^-3: every partial sum is exact)
+    check_rows(got, groups, refs, 0.0, f"mxfp4 lora {entry}", exact=True)
+    assert_guards_intact(buf, abuf, what=f"large MXFP4 adapters, {entry}")
+    del blocks, M, buf, abuf
+
+
+# ======================================================================= the dense MXFP4 linear op: a large MATRIX
+def linear_large_shape():
+    """(K, N, row stride in bytes, the live ranges of weight rows) of the dense case: K = 4128 gives rows of 2064 bytes,
+    which divide neither 2^31 nor 2^32; N is the smallest multiple of 4 with N * 2064 > 2^32 + 64 * 2064; 40 weight rows
+    are live at the start, around the row that crosses 2^31, around the row that crosses 2^32 and at the end.  Needs no
+    GPU."""
+    K = 4128
+    stride = K // 2
+    assert stride == 2064 and B31 % stride and B32 % stride
+    N = (B32 // stride + 64) // 4 * 4 + 4
+    assert N % 4 == 0 and N * stride > B32 + 64 * stride and (N - 4) * stride <= B32 + 64 * stride
+    r31, r32 = B31 // stride, B32 // stride
+    assert r31 * stride < B31 < (r31 + 1) * stride and r32 * stride < B32 < (r32 + 1) * stride
+    live = [(0, 40), (r31 - 20, r31 + 20), (r32 - 20, r32 + 20), (N - 40, N)]
+    assert all(a[1] < b[0] for a, b in zip(live, live[1:]))
+    return K, N, stride, live
+
+
+def test_mxfp4_linear_large_matrix(lib):
+    """ops.linear_forward_mxfp4 on ONE matrix [N, K/2] past 2^32 bytes (``linear_large_shape``): T = 2 integer rows in
+    [-4, 4], scale codes 125 .. 129 on the live weight rows, 0xFF blocks and scale bytes (NaN) on every other row, so that
+    the live output columns are the float64 reference exactly (every sum below 4128 x 4 x 24 < 2^19, in multiples of 2^-3)
+    and every other column is NaN.  ``split_k=False`` under both grouped kernels, then the split form forced to S = 4
+    (mx4_linear_decode_kernel's wrow * K2 and (slice * T + t) * N, mx4_linear_reduce_kernel's s * plane), each with the
+    kernel the library reports asserted.  The scales [N, 129] (270 MB) stay below 2^31 bytes and need no guard."""
+    from fused_int4_amd.quantize import dequantize_mxfp4
+    K, N, stride, live = linear_large_shape()
+    need(8)
+    torch.cuda.reset_peak_memory_stats()
+    T = 2
+    buf = BigGuarded("blocks", N * stride, torch.uint8, 0xFF)
+    blocks = buf.view(N, stride)
+    blocks.fill_(0xFF)
+    scales = torch.full((N, K // 32), 0xFF, dtype=torch.uint8, device=DEV)
+    assert scales.numel() < B31
+    g = torch.Generator(device=DEV).manual_seed(34)
+    for lo, hi in live:
+        blocks[lo:hi] = torch.randint(0, 256, (hi - lo, stride), generator=g, device=DEV, dtype=torch.uint8)
+        scales[lo:hi] = torch.randint(125, 130, (hi - lo, K // 32), generator=g, device=DEV, dtype=torch.uint8)
+    x = torch.randint(-4, 5, (T, K), generator=g, device=DEV).float()
+    bias = torch.randint(-8, 9, (N,), generator=g, device=DEV).float()
+    assert sum(input_wrap_is_visible(buf, (hi - 1) * stride, stride) for lo, hi in live) >= 3    # each range's last row
+    cols = torch.cat([torch.arange(lo, hi) for lo, hi in live]).to(DEV)
+    W = dequantize_mxfp4(blocks[cols].cpu(), scales[cols].cpu()).double().to(DEV)
+    ref = x.double() @ W.T + bias[cols].double()
+    assert float(ref.abs().max()) < 2 ** 19
+    dead = torch.ones(N, dtype=torch.bool, device=DEV)
+    dead[cols] = False
+
+    def check(got, what):
+        torch.cuda.synchronize()
+        assert got.dtype == torch.float32 and tuple(got.shape) == (T, N), what
+        assert torch.equal(got[:, cols].double(), ref), f"{what}: a live column is not the exact integer result"
+        assert bool(torch.isnan(got[:, dead]).all()), f"{what}: a column of a 0xFF weight row is not NaN"
+
+    hooks = (lib.fql_tune_set_mx4_decode_max_rows, lib.fql_tune_set_mx4_linear_decode_max_rows, lib.fql_tune_set_mx4_linear_slices)
+    old = [hooks[0](-1), hooks[1](-1), hooks[2](0)]
+    try:
+        for kernel in ("tile", "decode"):
+            hooks[0](0 if kernel == "tile" else 512)
+            assert lib.fql_tune_mx4_kernel(1, T, K, N) == MX4_KERNEL[kernel], kernel
+            check(ops().linear_forward_mxfp4(blocks, scales, x, bias=bias, out_dtype=torch.float32, split_k=False), kernel)
+        hooks[1](128)
+        hooks[2](4)
+        assert lib.fql_tune_mx4_linear_kernel(T, K, N) == (4 << 8) | 2
+        assert lib.fql_linear_mx4_workspace_bytes(T, K, N, 0, 1) == 16 * T * N * 4       # (sized for 16 slices; S = 4 uses 67 MB)
+        check(ops().linear_forward_mxfp4(blocks, scales, x, bias=bias, out_dtype=torch.float32, split_k=True), "split form, S = 4")
+    finally:
+        for hook, value in zip(hooks, old):
+            hook(value)
+    print(f"mxfp4 linear large matrix: N={N} K={K}, {N * stride / 2 ** 30:.2f} GiB of blocks, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    assert_guards_intact(buf, what="large dense MXFP4 matrix")
     del blocks, buf
 
 

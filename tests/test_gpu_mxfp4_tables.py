@@ -37,7 +37,14 @@ multiple of 2^-4 (2^-5 for the e4m3 bytes, whose sums are at most twice as large
 float64 reference bit for bit whatever the adder does; a bfloat16 result is one rounding of it.  The backward uses the
 same grid for grad_out (an exponent per element), and its sums over N <= 136 stay below 2^16 (asserted).
 
-Input rows no expert covers are NaN in every operand (float rows, scale code 255, NaN act_scale and NaN e4m3 bytes).
+The fused adapter entries (ops.moe_forward_mxfp4_lora / moe_gated_forward_mxfp4_lora / moe_backward_input_mxfp4_lora: the
+LORA stage of mx4_kernel and mx4_bwd_kernel) index the shrunk rows v[t] and the adapter matrix B[e] / A[e] by the same
+clamped row and expert as the base product, so they run through the same tables with the same operand set enlarged: v
+and dv [T, r] integers in [-4, 4], B [E, N, r] and A [E, r, K] integers in [-2, 2], r = 4 at K = 96 (less than one 16-j
+step) and 64 at K = 288 (all four).  The adapter adds at most 64 x 4 x 2 = 2^9 to a sum, which keeps the sums below
+2^17 and 2^16 (asserted on the enlarged references).
+
+Input rows no expert covers are NaN in every operand (float rows, the shrunk rows v and dv, scale code 255, NaN act_scale and NaN e4m3 bytes).
 By the code, a lane past an expert's count re-reads that expert's last row (row_lo + cnt - 1: the clamp of tx / ty / t
 in all five kernels), so an uncovered row is never an operand of a covered one; a kernel that read "the next row"
 instead would put a NaN into a covered row here.  Uncovered output rows are checked as bits (-0.0 or a NaN payload is
@@ -58,6 +65,7 @@ FORMS = ["tile", "decode"]
 CASES = [(t, 96, 40) for t in HOSTILE_TABLES] + [(t, 288, 136) for t in ("e65", "gaps-descending")]
 CASE_IDS = [f"{t}-K{K}-N{N}" for t, K, N in CASES]
 GRID = [0, 1, 2, 3, 4, 6]
+LORA_RANK = {96: 4, 288: 64}                                           # the adapters' rank at each K of CASES
 E2M1_CODE, E2M3_CODE = [0, 2, 4, 5, 6, 7], [0, 8, 16, 20, 24, 28]      # the codes of GRID's magnitudes
 
 
@@ -142,16 +150,30 @@ def problem(table, K, N):
         ref_bwd[lo:hi] = grad[lo:hi].double() @ W[e]
     assert float(ref.abs().max()) < 2 ** 17 and float(ref_b.abs().max()) < 2 ** 17 and float(ref_bwd.abs().max()) < 2 ** 16
     assert torch.equal(ref * 16, (ref * 16).round()) and torch.equal(ref_bwd * 16, (ref_bwd * 16).round())
+    # the adapter operands (a generator of their own: the operands above keep their values) and the enlarged references
+    r = LORA_RANK[K]
+    ga = torch.Generator().manual_seed(100003 * HOSTILE_TABLES.index(table) + 1000 * K + N + 500009)
+    v, dv = torch.randint(-4, 5, (T, r), generator=ga).float(), torch.randint(-4, 5, (T, r), generator=ga).float()
+    B, A = torch.randint(-2, 3, (E, N, r), generator=ga).float(), torch.randint(-2, 3, (E, r, K), generator=ga).float()
+    ref_lora, ref_lora_bwd = ref.clone(), ref_bwd.clone()
+    for e, (lo, hi) in enumerate(ranges):
+        ref_lora[lo:hi] += v[lo:hi].double() @ B[e].double().T
+        ref_lora_bwd[lo:hi] += dv[lo:hi].double() @ A[e].double()
+    ref_lora_b = ref_lora + (ref_b - ref)
+    assert max(float(ref_lora.abs().max()), float(ref_lora_b.abs().max())) < 2 ** 17 and float(ref_lora_bwd.abs().max()) < 2 ** 16
+    assert bool(unc.all()) or not (torch.equal(ref_lora, ref) or torch.equal(ref_lora_bwd, ref_bwd))   # (the adapter matters)
     # the rows no expert covers are NaN in every operand
     xs_nan, x8b = xs.clone(), x8.view(torch.uint8).clone()
-    for t in (x, grad, xr, gate_up, a8):
+    for t in (x, grad, xr, gate_up, a8, v, dv):
         t[unc] = NAN
     xs_nan[unc] = 255
     x8b[unc] = 0x7F
     dev = lambda *ts: [t.to(DEV) for t in ts]
-    p = dict(table=table, E=E, T=T, K=K, N=N, ranges=ranges, unc=unc, tpe_cpu=tpe, offs_cpu=offs, ref=ref, ref_b=ref_b, ref_bwd=ref_bwd)
-    for name, t in zip(("tpe", "offs", "blocks", "scales", "bias", "x", "xb4", "xb6", "xs", "x8", "a8", "grad", "xr", "gate_up"),
-                       dev(tpe, offs, blocks, scales, bias, x, xb4, xb6, xs_nan, x8b, a8, grad, xr, gate_up)):
+    p = dict(table=table, E=E, T=T, K=K, N=N, r=r, ranges=ranges, unc=unc, tpe_cpu=tpe, offs_cpu=offs, ref=ref, ref_b=ref_b,
+             ref_bwd=ref_bwd, ref_lora=ref_lora, ref_lora_b=ref_lora_b, ref_lora_bwd=ref_lora_bwd)
+    for name, t in zip(("tpe", "offs", "blocks", "scales", "bias", "x", "xb4", "xb6", "xs", "x8", "a8", "grad", "xr", "gate_up",
+                        "v", "dv", "B", "A"),
+                       dev(tpe, offs, blocks, scales, bias, x, xb4, xb6, xs_nan, x8b, a8, grad, xr, gate_up, v, dv, B, A)):
         p[name] = t
     return p
 
@@ -297,7 +319,57 @@ def test_grouped_equals_one_expert_calls(table, K, N, precision, form, force):
     check_grouped_is_one_expert_calls(p, precision)
 
 
-# ---- 3. a decode step of a 128-expert model under the library's own thresholds
+# ---- 3. the fused adapter entries: v[t] and B[e] / A[e] under the same clamped row and expert
+
+@pytest.mark.parametrize("table,K,N", CASES, ids=CASE_IDS)
+def test_lora_forward_and_backward_are_the_float64_reference(table, K, N):
+    """ops.moe_forward_mxfp4_lora (with and without bias) and ops.moe_backward_input_mxfp4_lora on the exact operands, from
+    float32 and bfloat16 rows, a float32 and a bfloat16 result: the float32 result is the float64 reference bit for bit, a
+    bfloat16 result one rounding of it, uncovered rows are zero bits although their x, v and dv are NaN, and the table
+    tensors are unchanged."""
+    p = problem(table, K, N)
+    w, t = (p["blocks"], p["scales"]), (p["tpe"], p["offs"])
+    for rows_dtype in (torch.float32, torch.bfloat16):
+        for out_dtype in (torch.float32, torch.bfloat16):
+            for bias in (False, True):
+                got = ops().moe_forward_mxfp4_lora(*w, p["x"].to(rows_dtype), p["v"], p["B"], *t, bias=p["bias"] if bias else None,
+                                                   out_dtype=out_dtype)
+                assert got.dtype == out_dtype and got.shape == (p["T"], N)
+                assert_is_reference(p, got, p["ref_lora_b"] if bias else p["ref_lora"], (table, "lora fwd", rows_dtype, bias, out_dtype))
+            got = ops().moe_backward_input_mxfp4_lora(*w, p["grad"].to(rows_dtype), p["dv"], p["A"], *t, out_dtype=out_dtype)
+            assert got.dtype == out_dtype and got.shape == (p["T"], K)
+            assert_is_reference(p, got, p["ref_lora_bwd"], (table, "lora bwd", rows_dtype, out_dtype))
+
+
+@pytest.mark.parametrize("table,K,N", CASES, ids=CASE_IDS)
+def test_lora_grouped_equals_one_expert_calls(table, K, N):
+    """The three adapter entries (the gated one on the seeded random gate | up rows, swiglu_clamp): the grouped call has the
+    bits of one call per expert on that expert's clipped slice of the rows and of v / dv with that expert's B / A,
+    scattered into zeros."""
+    p = problem(table, K, N)
+    o = ops()
+    entries = [("fwd", "x", "v", "B", lambda b, s, r, v, m, t, f, bias: o.moe_forward_mxfp4_lora(b, s, r, v, m, t, f, bias=bias,
+                                                                                              out_dtype=torch.float32)),
+               ("gated", "gate_up", "v", "B", lambda b, s, r, v, m, t, f, bias: o.moe_gated_forward_mxfp4_lora(
+                   b, s, r, v, m, t, f, bias=bias, out_dtype=torch.float32, **act_kw("swiglu_clamp"))),
+               ("bwd", "grad", "dv", "A", lambda b, s, r, v, m, t, f, bias: o.moe_backward_input_mxfp4_lora(b, s, r, v, m, t, f))]
+    for name, rows, vk, mk, op in entries:
+        got = op(p["blocks"], p["scales"], p[rows], p[vk], p[mk], p["tpe"], p["offs"], p["bias"])
+        assert table_intact(p), name
+        assert got.dtype == torch.float32 and got.shape == (p["T"], K if name == "bwd" else N)
+        want = torch.zeros_like(got)
+        for e, (lo, hi) in enumerate(p["ranges"]):
+            if hi > lo:
+                want[lo:hi] = op(p["blocks"][e:e + 1], p["scales"][e:e + 1], p[rows][lo:hi].contiguous(), p[vk][lo:hi].contiguous(),
+                                 p[mk][e:e + 1], *whole_table(hi - lo), p["bias"][e:e + 1])
+        assert bool(torch.isfinite(want).all()), name                                # (the slices hold no uncovered row)
+        assert same_bits(got, want), (table, name, (bits(got) != bits(want)).nonzero()[:4].tolist())
+        assert uncovered_all_zero_bits(p, got), name
+        if bool((~p["unc"]).any()):
+            assert float(got.abs().max()) > 0
+
+
+# ---- 4. a decode step of a 128-expert model under the library's own thresholds
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_e128_decode_step_under_the_default_dispatch(precision):

@@ -9,19 +9,26 @@ all-zero table is a legal one, scene S5, so a launch that reads it early compute
 The default stream then waits for the side stream and the result must be bit for bit the default-stream result.  A launch
 that went to another stream reads NaN, an empty table or unwritten memory; the test can miss such a mistake, but it cannot
 fail without one.  The last test issues the same op on two side streams with different tables before synchronising
-either, and checks both: what two overlapping launches must not share (a workspace, the scratch of ops.gemm_i8)."""
+either, and checks both: what two overlapping launches must not share (a workspace, the scratch of ops.gemm_i8).
+
+The dense ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4 have no table and therefore no family: their split form
+(a decode launch into a partial-sum workspace, a reduce launch, and the gated pre-pass in front of both) has a test of its
+own at the end, on one side stream and on two at once."""
 import pytest
 import torch
 
 from helpers import first_diff, same_bits
-from test_gpu_graph_replay import DEV, FAMILIES, build_block, gen, scenes, tune  # noqa: F401  (tune: the fixture)
+from test_gpu_graph_replay import (DEV, FAMILIES, LINEAR_CASES, build_block, gen, linear_case, scenes,  # noqa: F401
+                                   tune)                           # (tune: the fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = ["int4-small-T232-bf16", "int4-stream-T1600-f32", "int4-small-T100-fast", "int4-small-T100-fp8", "int4-gated-T100",
          "int4-gather-T232", "int4-two-phase-T100", "int4-bwd-tiled-vec", "group-i8", "group-float-glu", "group-bwd-rows-g48",
          "mx4-K288-N136-tile", "mx4-K288-N136-decode", "mx4-K96-N37-fp8", "mx4-K96-N37-fp4", "mx4-K288-N136-glu-decode",
-         "mx4-K288-N136-bwd"]
-TWO_STREAMS = ["int4-small-T100-fast", "int4-two-phase-T100", "group-i8-glu", "mx4-K288-N136-glu-tile", "mx4-K96-N37-fp4"]
+         "mx4-K288-N136-bwd", "mx4-K288-N136-fp6-tile", "mx4-K96-N37-fp6-glu-decode", "mx4-K288-N136-fp8-decode",
+         "mx4-K96-N37-fp4-decode", "mx4-lora-fwd-K288-N136-r16", "mx4-lora-glu-K96-N37-r64", "mx4-lora-bwd-K288-N136-r16"]
+TWO_STREAMS = ["int4-small-T100-fast", "int4-two-phase-T100", "group-i8-glu", "mx4-K288-N136-glu-tile", "mx4-K96-N37-fp4",
+               "mx4-lora-glu-K288-N136-r16", "mx4-K288-N136-fp6-decode"]
 
 
 def poisoned_like(t):
@@ -103,5 +110,42 @@ def test_two_side_streams_with_different_tables(tune, name):
     assert same_bits(got_a, want_a), ("S3", first_diff(got_a, want_a))
     assert same_bits(got_b, want_b), ("S1", first_diff(got_b, want_b))
     assert not same_bits(want_a, want_b)
+    torch.cuda.synchronize()
+    del keep_a, keep_b
+
+
+# ---- the dense MXFP4 linear op: the split form's two launches, and the gated entry's pre-pass in front of them
+
+@pytest.mark.parametrize("name", list(LINEAR_CASES))
+def test_dense_linear_split_form_on_side_streams(tune, name):
+    """ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4(split_k=True) with S forced (test_gpu_graph_replay.linear_case):
+    mx4_linear_decode_kernel writes partial[S][T][N] and mx4_linear_reduce_kernel sums it, the gated entry writes h in
+    front of both; the launch boundaries on ONE stream are their only synchronisation.  First on one side stream with
+    poisoned input buffers, then on two side streams at once with different rows: every result carries the default-stream
+    bits.  A reduce launch (or the gated pre-pass) that went to another stream than the decode kernel runs while the side
+    stream is still busy with the matmuls: it sums a workspace nobody has written, or the decode kernel reads an h that
+    is not there yet."""
+    call, make_rows, _, _ = linear_case(name, tune)
+    a, b = make_rows(1), make_rows(2)
+    want_a, want_b = call(a.clone()), call(b.clone())
+    assert float(want_a.abs().max()) > 0 and not same_bits(want_a, want_b)
+    for _ in range(2):
+        busy = busy_matrix()
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        got, keep, busy = enqueue(call, [a], side, busy)
+        torch.cuda.current_stream().wait_stream(side)
+        assert same_bits(got, want_a), first_diff(got, want_a)
+        torch.cuda.synchronize()
+        del keep
+    busy_a, busy_b = busy_matrix(), busy_matrix()
+    torch.cuda.synchronize()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    got_a, keep_a, busy_a = enqueue(call, [a], sa, busy_a)
+    got_b, keep_b, busy_b = enqueue(call, [b], sb, busy_b)
+    torch.cuda.current_stream().wait_stream(sa)
+    torch.cuda.current_stream().wait_stream(sb)
+    assert same_bits(got_a, want_a), ("a", first_diff(got_a, want_a))
+    assert same_bits(got_b, want_b), ("b", first_diff(got_b, want_b))
     torch.cuda.synchronize()
     del keep_a, keep_b
