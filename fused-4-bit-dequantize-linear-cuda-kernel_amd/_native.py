@@ -199,6 +199,18 @@ _SYMBOLS = {
     "fql_tune_set_mx4_linear_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_set_mx4_linear_slices": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_mx4_linear_kernel": (ctypes.c_int, [ctypes.c_int] * 3),
+    "fql_moe_nvfp4_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "fql_moe_nvfp4_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
+                          + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_nvfp4_glu_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6
+                              + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_linear_nvfp4_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "fql_linear_nvfp4_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4
+                             + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_linear_nvfp4_glu_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5
+                                 + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_tune_set_nvfp4_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
+    "fql_tune_nvfp4_kernel": (ctypes.c_int, [ctypes.c_int] * 4),
     "fql_combine_sparse_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
                                + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
 }

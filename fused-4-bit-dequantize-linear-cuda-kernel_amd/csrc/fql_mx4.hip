@@ -4,7 +4,8 @@
 // fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8, on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 and on MXFP6 rows
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
 // fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
-// linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
+// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -16,6 +17,7 @@
 #include "fql_gemm_mx4_scaled.h"
 #include "fql_gemm_mx4_sdecode.h"
 #include "fql_mx4_quant.h"
+#include "fql_gemm_nvfp4.h"
 
 #include <cmath>
 
@@ -36,7 +38,16 @@ struct Mx4Call {
     const float *lora_rows = nullptr;  // [T][rank]: v (forward) or dv (input gradient)
     const float *lora_w = nullptr;     // [E][N][rank] B (forward) or [E][rank][K] A (input gradient)
     int rank = 0;
+    bool nvfp4 = false;                // an NVFP4 entry: `scales` is [E][N][K / 16] e4m3 bytes, and
+    const float *gscale = nullptr;     // [E] float32 or NULL (1): the per-tensor scales
 };
+
+// c as the call of an NVFP4 entry
+Mx4Call with_nvfp4(Mx4Call c, const float *global_scale)
+{
+    c.nvfp4 = true; c.gscale = global_scale;
+    return c;
+}
 
 // c with the operands of an adapter entry
 Mx4Call with_lora(Mx4Call c, const float *rows, const float *w, int rank)
@@ -111,6 +122,36 @@ int launch_mx4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
     });
 }
 
+// The NVFP4 forward (fql_gemm_nvfp4.h): the same pair of kernels, the same bits from both, a threshold of its own.
+#define FQL_NVFP4_DECODE_MAX_ROWS 512  /* rows (T) up to which the decode kernel runs: the largest count of the sweep up to which it wins at every point of both shapes */
+int g_nvfp4_decode_max_rows = FQL_NVFP4_DECODE_MAX_ROWS;
+
+bool nvfp4_use_decode(int T)
+{
+    return T > 0 && T <= g_nvfp4_decode_max_rows && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;
+}
+
+int launch_nvfp4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    using C = Mx4Cfg;
+    using D = Mx4DecodeCfg;
+    const bool decode = nvfp4_use_decode(c.T);
+    const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
+    return with_in_dtype(in_dtype, [&](auto in) {
+        return with_out_dtype(out_dtype, [&](auto o) {
+            constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
+            return launch(decode ? nv4_decode_kernel<IN, OUT> : nv4_kernel<IN, OUT>, grid, dim3(decode ? D::THREADS : C::THREADS), 0, st,
+                          c.blocks, c.scales, c.gscale, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+        });
+    });
+}
+
+// The bfloat16 GEMM of a call with float rows, by the format of its weights.
+int launch_float_rows(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
+{
+    return c.nvfp4 ? launch_nvfp4(in_dtype, out_dtype, c, st) : launch_mx4(in_dtype, out_dtype, c, st);
+}
+
 // The block-scaled forward: c.rows is [T][K] e4m3 bytes with c.act_scale (ROWS_E4M3), or [T][K / 2] packed e2m1 with
 // c.row_scales (ROWS_MXFP4), or [T][3 K / 4] packed e2m3 with c.row_scales (ROWS_MXFP6).
 template <int ROWS>
@@ -155,6 +196,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
     if ((reinterpret_cast<uintptr_t>(c.lora_rows) & 3) || (reinterpret_cast<uintptr_t>(c.lora_w) & 3)) return FQL_ERR_ALIGNMENT;   // (NULL without an adapter)
+    if (reinterpret_cast<uintptr_t>(c.gscale) & 3) return FQL_ERR_ALIGNMENT;                                                        // (NULL but for NVFP4)
     if (rows_kind == ROWS_MXFP4 && !aligned16(c.rows)) return FQL_ERR_ALIGNMENT;
     if (rows_kind == ROWS_MXFP6 && (reinterpret_cast<uintptr_t>(c.rows) & 7)) return FQL_ERR_ALIGNMENT;
     return FQL_OK;
@@ -231,7 +273,7 @@ int mx4_quant_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, void 
     if (lrc != FQL_OK) return lrc;
     c.rows = q;
     if constexpr (ROWS == ROWS_FLOAT) {
-        return launch_mx4(FQL_DTYPE_BF16, out_dtype, c, st);
+        return launch_float_rows(FQL_DTYPE_BF16, out_dtype, c, st);
     } else {
         if constexpr (ROWS == ROWS_E4M3) c.act_scale = reinterpret_cast<const float *>(side);
         else c.row_scales = side;
@@ -335,7 +377,7 @@ int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, int 
     }
     const int S = split_k ? mx4_linear_slices(c.T, c.K, c.N) : 1;
     if (S > 1) return launch_mx4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
-    return launch_mx4(in_dtype, out_dtype, c, st);
+    return launch_float_rows(in_dtype, out_dtype, c, st);
 }
 
 }  // namespace
@@ -588,6 +630,71 @@ FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_
 {
     return mx4_linear_fwd({blocks, scales_e8m0, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, in_dtype, out_dtype,
                           {true, activation, act_alpha, act_limit}, split_k, workspace, workspace_bytes, stream);
+}
+
+FQL_API size_t fql_moe_nvfp4_workspace_bytes(int E, int T, int K, int N, int gated)
+{
+    return fql_moe_mx4_workspace_bytes(E, T, K, N, gated);            // h [T][K] bfloat16, as the MXFP4 entries'
+}
+
+FQL_API int fql_moe_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                              int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                              void *out, int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                              void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    const Mx4Call c = with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, global_scale);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_nvfp4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *gate_up,
+                                  int in_dtype, const float *bias, const int32_t *tokens_per_expert,
+                                  const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                                  int activation, float act_alpha, float act_limit, void *workspace, size_t workspace_bytes,
+                                  void *stream)
+{
+    return mx4_quant_fwd<ROWS_FLOAT>(with_nvfp4({blocks, scales_e4m3, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                                global_scale), in_dtype, out_dtype, {true, activation, act_alpha, act_limit},
+                                     workspace, workspace_bytes, stream);
+}
+
+FQL_API size_t fql_linear_nvfp4_workspace_bytes(int T, int K, int N, int gated)
+{
+    (void)N;
+    return mx4_linear_h_bytes(T, K, gated);                           // h [T][K] bfloat16
+}
+
+FQL_API int fql_linear_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                 int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N, void *workspace,
+                                 size_t workspace_bytes, void *stream)
+{
+    return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
+                          out_dtype, kMx4Plain, 0, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_linear_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                     const void *gate_up, int in_dtype, const float *bias, void *out, int out_dtype, int T, int K,
+                                     int N, int activation, float act_alpha, float act_limit, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
+                          out_dtype, {true, activation, act_alpha, act_limit}, 0, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows)
+{
+    const int old = g_nvfp4_decode_max_rows;
+    if (rows >= 0) g_nvfp4_decode_max_rows = rows;
+    return old;
+}
+
+FQL_API int fql_tune_nvfp4_kernel(int E, int T, int K, int N)
+{
+    (void)E; (void)K; (void)N;
+    return nvfp4_use_decode(T) ? 1 : 0;
 }
 
 FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows)

@@ -670,6 +670,144 @@ class MXFP4MoEFFN(nn.Module):
                 + (f", precision={self.precision}" if self.precision != "bf16" else ""))
 
 
+class NVFP4MoEFFN(nn.Module):
+    """Gated FFN experts on NVFP4 weights (the format of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen and inference
+    only: ``down( act(gate(x), up(x)) )`` per expert, rows pre-grouped by expert, the same ``forward`` as
+    ``MXFP4MoEFFN``.
+
+    The buffers are the checkpoint's tensors, never re-quantised: ``gate_up_blocks`` uint8 [E, 2F, H/2] and ``down_blocks``
+    [E, H, F/2] hold two e2m1 codes a byte (even input in the low nibble), ``gate_up_scales`` [E, 2F, H/16] and
+    ``down_scales`` [E, H, F/16] one e4m3fn scale byte per 16 consecutive inputs, ``gate_up_global`` and ``down_global``
+    float32 [E] the per-tensor scales.  The global scales MULTIPLY (ModelOpt's ``weight_scale_2``); compressed-tensors
+    stores the reciprocal (``weight_global_scale``): invert it before ``from_nvfp4``.  Rows 0 .. F-1 of ``gate_up`` are the
+    gate, F .. 2F-1 the up projection (``from_nvfp4(interleaved=True)`` converts an alternating order).
+    ``expert_bias=True`` adds float32 ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H], as in ``MXFP4MoEFFN``.
+
+    Both GEMMs are ``ops.moe_forward_nvfp4`` / ``ops.moe_gated_forward_nvfp4``: the weights are exact in bfloat16, the
+    activations are rounded once to bfloat16 (float32 inputs) or read as they are (``activation_dtype=torch.bfloat16``),
+    the sums are float32, and a small batch takes the decode kernel with the same bits.  A forward under grad mode on an
+    input that requires grad raises ``RuntimeError``, as ``MXFP4MoEFFN(input_grad=False)`` does (INTEGRATION.md
+    section 18)."""
+
+    group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
+    input_grad = False
+    precision = "bf16"
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, activation: str = "silu",
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
+                 activation_dtype=None):
+        super().__init__()
+        if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0 or num_experts <= 0:
+            raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 and num_experts positive")
+        if activation_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("activation_dtype must be None, torch.float32 or torch.bfloat16 (float16 rows are refused: "
+                             "rounding them to bfloat16 would lose three bits)")
+        from . import ops
+        self.num_experts, self.hidden_dim, self.ffn_dim = num_experts, hidden_dim, ffn_dim
+        self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
+            activation, activation_alpha, activation_limit)
+        self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
+        E, H, F = num_experts, hidden_dim, ffn_dim
+        self.register_buffer("gate_up_blocks", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
+        self.register_buffer("gate_up_scales", torch.full((E, 2 * F, H // 16), 0x38, dtype=torch.uint8))
+        self.register_buffer("gate_up_global", torch.ones(E, dtype=torch.float32))
+        self.register_buffer("down_blocks", torch.zeros(E, H, F // 2, dtype=torch.uint8))
+        self.register_buffer("down_scales", torch.full((E, H, F // 16), 0x38, dtype=torch.uint8))
+        self.register_buffer("down_global", torch.ones(E, dtype=torch.float32))
+        self.expert_bias = bool(expert_bias)
+        if self.expert_bias:
+            self.gate_up_bias = nn.Parameter(torch.zeros(E, 2 * F, dtype=torch.float32), requires_grad=False)
+            self.down_bias = nn.Parameter(torch.zeros(E, H, dtype=torch.float32), requires_grad=False)
+
+    @classmethod
+    def from_nvfp4(cls, gate_up_blocks, gate_up_scales, gate_up_global, down_blocks, down_scales, down_global,
+                   gate_up_bias=None, down_bias=None, interleaved: bool = False, **kwargs) -> "NVFP4MoEFFN":
+        """Tensors already in the format: ``gate_up_blocks`` [E, 2F, H/2], ``gate_up_scales`` [E, 2F, H/16] and
+        ``down_blocks`` [E, H, F/2], ``down_scales`` [E, H, F/16], all uint8 (a ``float8_e4m3fn`` scale tensor is viewed
+        as its bytes); ``gate_up_global`` / ``down_global`` float32 [E], or None for ones; ``gate_up_bias`` [E, 2F] and
+        ``down_bias`` [E, H] (both or none).  ``interleaved=True``: rows 0, 2, 4, ... of ``gate_up`` are the gate and
+        1, 3, 5, ... the up projection; they are de-interleaved once, the bias included.  ``kwargs``: the constructor's
+        activation arguments and ``activation_dtype``."""
+        def check(name, b, s, g):
+            if s.dtype == torch.float8_e4m3fn:
+                s = s.view(torch.uint8)
+            if b.dtype != torch.uint8 or s.dtype != torch.uint8:
+                raise ValueError(f"{name}_blocks and {name}_scales must be uint8")
+            if b.dim() != 3 or s.dim() != 3 or b.shape[2] % 16 or tuple(s.shape) != (b.shape[0], b.shape[1], b.shape[2] // 8):
+                raise ValueError(f"{name}_blocks must be [E, N, K/2] with K % 32 == 0 and {name}_scales [E, N, K/16]")
+            if g is None:
+                g = torch.ones(b.shape[0], dtype=torch.float32, device=b.device)
+            if not isinstance(g, torch.Tensor) or g.numel() != b.shape[0]:
+                raise ValueError(f"{name}_global must hold one float32 value per expert")
+            return b, s, g.detach().to(torch.float32).reshape(-1)
+        gub, gus, gug = check("gate_up", gate_up_blocks, gate_up_scales, gate_up_global)
+        db, ds, dg = check("down", down_blocks, down_scales, down_global)
+        E, F2, H = gub.shape[0], gub.shape[1], gub.shape[2] * 2
+        if F2 % 2 or tuple(db.shape) != (E, H, F2 // 4):
+            raise ValueError("gate_up must be [E, 2F, H/2] and down [E, H, F/2] of the same E, H and F")
+        if (gate_up_bias is None) != (down_bias is None):
+            raise ValueError("gate_up_bias and down_bias come together: pass both or none")
+        if gate_up_bias is not None and (tuple(gate_up_bias.shape) != (E, F2) or tuple(down_bias.shape) != (E, H)):
+            raise ValueError("gate_up_bias must be [E, 2F] and down_bias [E, H]")
+        if interleaved:
+            split = lambda t: torch.cat([t[:, 0::2], t[:, 1::2]], dim=1)
+            gub, gus = split(gub), split(gus)
+            gate_up_bias = None if gate_up_bias is None else split(gate_up_bias)
+        m = cls(E, H, F2 // 2, expert_bias=gate_up_bias is not None, **kwargs)
+        m.gate_up_blocks, m.gate_up_scales, m.gate_up_global = gub.contiguous().clone(), gus.contiguous().clone(), gug.clone()
+        m.down_blocks, m.down_scales, m.down_global = db.contiguous().clone(), ds.contiguous().clone(), dg.clone()
+        if gate_up_bias is not None:
+            with torch.no_grad():
+                m.gate_up_bias.data = gate_up_bias.detach().float().contiguous().clone()
+                m.down_bias.data = down_bias.detach().float().contiguous().clone()
+        return m
+
+    @classmethod
+    def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor], gate_bias=None,
+                     up_bias=None, down_bias=None, **kwargs) -> "NVFP4MoEFFN":
+        """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` float weights, quantised with
+        ``quantize.quantize_nvfp4`` (one global scale per expert and projection); the biases as
+        ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
+        from .quantize import quantize_nvfp4
+        given = [b is not None for b in (gate_bias, up_bias, down_bias)]
+        if any(given) and not all(given):
+            raise ValueError("gate_bias, up_bias and down_bias come together: pass all three or none")
+        gu = quantize_nvfp4(torch.stack([torch.cat([g.float(), u.float()], dim=0) for g, u in zip(gate, up)]))
+        d = quantize_nvfp4(torch.stack([t.float() for t in down]))
+        b_gu = torch.stack([torch.cat([g.float(), u.float()]) for g, u in zip(gate_bias, up_bias)]) if all(given) else None
+        b_d = torch.stack([t.float() for t in down_bias]) if all(given) else None
+        return cls.from_nvfp4(*gu, *d, gate_up_bias=b_gu, down_bias=b_d, **kwargs)
+
+    def forward(self, inputs, tokens_per_expert, input_offsets):
+        """inputs ``[T, H]`` float32 (``activation_dtype=torch.bfloat16``: bfloat16) rows grouped by expert -> ``[T, H]`` of
+        the same type."""
+        if not inputs.is_cuda:
+            raise RuntimeError("NVFP4MoEFFN runs on the GPU (the product path has no CPU fallback)")
+        if torch.is_grad_enabled() and inputs.requires_grad:
+            raise RuntimeError("NVFP4MoEFFN is inference-only: the NVFP4 format has no backward.  Run it under "
+                               "torch.no_grad(), or on a detached input")
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
+        if inputs.dim() != 2 or inputs.dtype != dt:
+            raise RuntimeError(f"NVFP4MoEFFN: inputs must be a 2-D {dt} tensor (the layer's activation_dtype), got "
+                               f"{inputs.dtype}")
+        from . import ops
+        b_gu, b_d = self.biases
+        b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
+        gate_up = ops.moe_forward_nvfp4(self.gate_up_blocks, self.gate_up_scales, self.gate_up_global, inputs.detach(),
+                                        tokens_per_expert, input_offsets, bias=b_gu, out_dtype=dt)
+        return ops.moe_gated_forward_nvfp4(self.down_blocks, self.down_scales, self.down_global, gate_up, tokens_per_expert,
+                                           input_offsets, activation=self.activation, activation_alpha=self.activation_alpha,
+                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt)
+
+    biases = MXFP4MoEFFN.biases
+    total_memory_bytes = MXFP4MoEFFN.total_memory_bytes
+    activation_args = MXFP4MoEFFN.activation_args
+    _activation_repr = QuantizedMoEFFN._activation_repr
+
+    def extra_repr(self) -> str:
+        return "format=nvfp4" + self._activation_repr()
+
+
 class QuantizedSparseMoEBlock(nn.Module):
     """A Mixtral-style sparse MoE layer, hidden states in and hidden states out: a trainable float gate, the fused top-k
     router (``ops.router_topk``), the one-launch plan, a dispatch with a deterministic backward, the INT4 gated FFN
@@ -679,7 +817,8 @@ class QuantizedSparseMoEBlock(nn.Module):
     ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
     when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or an ``MXFP4MoEFFN``: built with ``input_grad=True`` it trains the
-    router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``; or an ``NVFP4MoEFFN``,
+    inference only).  State-dict keys: ``gate.weight`` and ``experts.*``.
     The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
     to the activations' type: no cast pass either side of it.
 

@@ -1,0 +1,94 @@
+"""``NVFP4Linear``: a dense ``nn.Linear`` on NVFP4 weights (the encoding of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen
+and inference only (csrc/fql_gemm_nvfp4.h)."""
+import torch
+import torch.nn as nn
+
+
+class NVFP4Linear(nn.Module):
+    """``y = (x @ W.T) * global_scale (+ bias)`` on frozen NVFP4 weights, any leading dimensions as ``nn.Linear``.
+
+    Buffers in the checkpoint's own encoding, never re-quantised: ``blocks`` uint8 [N, K/2] (two e2m1 codes a byte, even
+    input in the low nibble), ``scales`` uint8 [N, K/16] (one e4m3fn scale byte per 16 consecutive inputs),
+    ``global_scale`` float32 [1] (the per-tensor scale; it MULTIPLIES, as ModelOpt's ``weight_scale_2`` does --
+    compressed-tensors stores the reciprocal, ``weight_global_scale``: invert it before ``from_nvfp4``) and, with
+    ``bias=True``, a float32 ``bias`` [N].  K = ``in_features`` (a multiple of 32), N = ``out_features``.
+
+    On the GPU the forward is ``ops.linear_forward_nvfp4``: inputs float32 (rounded once to bfloat16) or bfloat16 (float16
+    is refused), ``W`` without the global scale exact in bfloat16, float32 sums, then ``* global_scale``, then ``+ bias``,
+    two float32 steps, and the result in the inputs' type.  It is bit for bit ``ops.moe_forward_nvfp4`` on one expert;
+    there is no split-K form.  On the CPU the forward is the definition,
+    ``(bf16(x) @ dequantize_nvfp4(blocks, scales).T) * global_scale (+ bias)`` in float32.
+
+    Inference only: a forward under grad mode on an input that requires grad raises ``RuntimeError``.  The state-dict keys
+    are ``blocks``, ``scales``, ``global_scale`` (and ``bias``)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = False):
+        super().__init__()
+        if in_features <= 0 or in_features % 32 != 0 or out_features <= 0:
+            raise ValueError("in_features must be a positive multiple of 32 and out_features positive")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("blocks", torch.zeros(out_features, in_features // 2, dtype=torch.uint8))
+        self.register_buffer("scales", torch.full((out_features, in_features // 16), 0x38, dtype=torch.uint8))
+        self.register_buffer("global_scale", torch.ones(1, dtype=torch.float32))
+        if bias:
+            self.register_buffer("bias", torch.zeros(out_features, dtype=torch.float32))
+        else:
+            self.register_buffer("bias", None)
+
+    @classmethod
+    def from_nvfp4(cls, blocks, scales, global_scale=None, bias=None) -> "NVFP4Linear":
+        """The checkpoint's tensors as they are: ``blocks`` uint8 [N, K/2], ``scales`` uint8 [N, K/16] (a
+        ``float8_e4m3fn`` tensor is viewed as its bytes), ``global_scale`` one float32 value or None for 1, ``bias`` [N]
+        or None."""
+        if scales.dtype == torch.float8_e4m3fn:
+            scales = scales.view(torch.uint8)
+        if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+            raise ValueError("blocks and scales must be uint8")
+        if blocks.dim() != 2 or scales.dim() != 2 or blocks.shape[1] % 16 or tuple(scales.shape) != (blocks.shape[0], blocks.shape[1] // 8):
+            raise ValueError("blocks must be [N, K/2] with K % 32 == 0 and scales [N, K/16]")
+        N, K = blocks.shape[0], 2 * blocks.shape[1]
+        if bias is not None and tuple(bias.shape) != (N,):
+            raise ValueError("bias must be [N]")
+        if global_scale is not None:
+            global_scale = torch.as_tensor(global_scale, dtype=torch.float32)
+            if global_scale.numel() != 1:
+                raise ValueError("global_scale must hold one value")
+        m = cls(K, N, bias=bias is not None)
+        m.blocks, m.scales = blocks.contiguous().clone(), scales.contiguous().clone()
+        if global_scale is not None:
+            m.global_scale = global_scale.detach().reshape(1).clone().to(blocks.device)
+        if bias is not None:
+            m.bias = bias.detach().float().contiguous().clone()
+        return m
+
+    @classmethod
+    def from_linear(cls, linear: nn.Linear) -> "NVFP4Linear":
+        """Quantise an ``nn.Linear`` with ``quantize.quantize_nvfp4``; its bias is kept (float32)."""
+        from .quantize import quantize_nvfp4
+        blocks, scales, gs = quantize_nvfp4(linear.weight.detach().float())
+        return cls.from_nvfp4(blocks, scales, gs, bias=None if linear.bias is None else linear.bias.detach())
+
+    def forward(self, x):
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError("ops.linear_forward_nvfp4: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is "
+                               "refused: rounding it to bfloat16 would lose three bits; cast it yourself)")
+        if x.dim() < 1 or x.shape[-1] != self.in_features:
+            raise RuntimeError(f"NVFP4Linear: the last dimension of the input must be in_features = {self.in_features}, got "
+                               f"{list(x.shape)}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("NVFP4Linear is inference-only: the NVFP4 format has no backward.  Run it under "
+                               "torch.no_grad(), or on a detached input")
+        lead = x.shape[:-1]
+        if not x.is_cuda:
+            from .quantize import dequantize_nvfp4
+            y = (x.detach().bfloat16().float() @ dequantize_nvfp4(self.blocks, self.scales).T) * self.global_scale
+            if self.bias is not None:
+                y = y + self.bias
+            return y.to(x.dtype)
+        from . import ops
+        x2 = x.reshape(-1, self.in_features)
+        y = ops.linear_forward_nvfp4(self.blocks, self.scales, self.global_scale, x2, bias=self.bias, out_dtype=x2.dtype)
+        return y.reshape(*lead, self.out_features)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=nvfp4"

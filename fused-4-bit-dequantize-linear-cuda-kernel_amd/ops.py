@@ -707,6 +707,103 @@ def linear_backward_input_mxfp4(blocks, scales, grad_out, out_dtype=None):
     return moe_backward_input_mxfp4(blocks[None], scales[None], grad_out, None, None, out_dtype=out_dtype)
 
 
+def _nvfp4_launch(name, blocks, scales, global_scale, rows, cols, tokens_per_expert, input_offsets, bias, out_dtype, gated,
+                  act=(), dense=False):
+    """The four NVFP4 ops.  ``rows`` [T, cols(K)] float32 / bfloat16; grouped: ``blocks`` [E, N, K/2], ``scales`` [E, N, K/16],
+    ``global_scale`` float32 [E] or None, ``bias`` [E, N]; ``dense``: ``blocks`` [N, K/2], ``scales`` [N, K/16],
+    ``global_scale`` float32 with one element or None, ``bias`` [N], no table.  Types and shapes first, then the devices:
+    the argument errors read the same without a GPU."""
+    if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    wd = 2 if dense else 3
+    shape = "[N, K/2] and scales_e4m3 uint8 [N, K/16]" if dense else "[num_experts, N, K/2] and scales_e4m3 uint8 [num_experts, N, K/16]"
+    if blocks.dtype != torch.uint8 or blocks.dim() != wd or scales.dtype != torch.uint8 or scales.dim() != wd:
+        raise RuntimeError(f"blocks must be uint8 {shape}")
+    E = 1 if dense else blocks.shape[0]
+    N, K = blocks.shape[-2], 2 * blocks.shape[-1]
+    if K % 32 != 0 or tuple(scales.shape) != tuple(blocks.shape[:-1]) + (K // 16,):
+        raise RuntimeError(f"blocks must be uint8 {shape} with K % 32 == 0")
+    if rows.shape[1] != cols(K):
+        raise RuntimeError(f"ops.{name}: the rows must have {cols(K)} columns for blocks {list(blocks.shape)}")
+    if global_scale is not None and (not isinstance(global_scale, torch.Tensor) or global_scale.dtype != torch.float32
+                                     or global_scale.numel() != E or global_scale.dim() > 1):
+        raise RuntimeError(f"global_scale must be a float32 tensor of {E} element(s) (one per expert), or None")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != ((N,) if dense else (E, N))):
+        raise RuntimeError("bias must be a float32 [N] tensor" if dense else "bias must be a float32 [num_experts, N] tensor")
+    out_dtype = rows.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not rows.is_cuda:
+        raise RuntimeError(f"ops.{name}: the rows must be a CUDA tensor")
+    dev, T = rows.device, rows.shape[0]
+    _on(dev, blocks=blocks, scales_e4m3=scales, global_scale=global_scale, bias=bias)
+    out = torch.empty((T, N), dtype=out_dtype, device=dev)
+    L = _native.lib()
+    gs = None if global_scale is None else global_scale.contiguous()
+    b = None if bias is None else bias.contiguous()
+    if dense:
+        _launch("fql_linear_nvfp4_glu_fwd" if gated else "fql_linear_nvfp4_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
+                rows.contiguous(), _DTYPES[rows.dtype], b, out, _DTYPES[out_dtype], T, K, N, *act,
+                ws_bytes=L.fql_linear_nvfp4_workspace_bytes(T, K, N, int(gated)))
+        return out
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)   # (none: one expert, all rows)
+    _launch("fql_moe_nvfp4_glu_fwd" if gated else "fql_moe_nvfp4_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
+            rows.contiguous(), _DTYPES[rows.dtype], b, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
+            ws_bytes=L.fql_moe_nvfp4_workspace_bytes(E, T, K, N, int(gated)))
+    return out
+
+
+def moe_forward_nvfp4(blocks, scales_e4m3, global_scale, inputs, tokens_per_expert, input_offsets, bias=None, out_dtype=None):
+    """The grouped GEMM on NVFP4 expert weights (ModelOpt's ``-FP4`` / ``-NVFP4`` exports):
+    ``out[t] = (W_e @ bf16(inputs[t])) * global_scale[e] (+ bias[e])`` over the rows of expert e.  ``blocks`` uint8
+    [E, N, K/2] (two e2m1 codes a byte, even k in the low nibble), ``scales_e4m3`` uint8 [E, N, K/16] (the e4m3fn value
+    of the byte scales 16 consecutive inputs), ``global_scale`` float32 [E] or None for 1 (``quantize.quantize_nvfp4``, or
+    a checkpoint's ``weight`` / ``weight_scale`` / ``weight_scale_2``).  ``global_scale`` MULTIPLIES, as ModelOpt's
+    ``weight_scale_2`` does; compressed-tensors stores the reciprocal (``weight_global_scale``): invert it first.
+    ``inputs`` [T, K] float32 (rounded once to bfloat16) or bfloat16, K % 32 == 0; ``bias`` [E, N] float32.  The weights
+    without the global scale are exact in bfloat16; the sums are float32 on the bfloat16 matrix cores; the multiply by
+    ``global_scale`` and the addition of the bias are two float32 steps, then one rounding to ``out_dtype`` (default:
+    the inputs' type).  Rows no expert covers are zero; both table arguments may be None with one expert.  A small
+    batch takes a decode kernel that returns the same bits as the tile kernel.  Forward only (INTEGRATION.md
+    section 18)."""
+    _forward_only("moe_forward_nvfp4", inputs, bias)
+    return _nvfp4_launch("moe_forward_nvfp4", blocks, scales_e4m3, global_scale, inputs, lambda K: K, tokens_per_expert,
+                         input_offsets, bias, out_dtype, False)
+
+
+def moe_gated_forward_nvfp4(blocks, scales_e4m3, global_scale, gate_up, tokens_per_expert, input_offsets, activation="silu",
+                            activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None):
+    """The down projection of a gated FFN expert on NVFP4 weights: ``moe_forward_nvfp4`` on
+    ``bf16(act(gate_up[t, :K], gate_up[t, K:]))``, ``gate_up`` [T, 2K] float32 or bfloat16, by ``moe_gated_forward_mxfp4``'s
+    streaming pre-pass into the op's workspace.  Forward only."""
+    _forward_only("moe_gated_forward_nvfp4", gate_up, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _nvfp4_launch("moe_gated_forward_nvfp4", blocks, scales_e4m3, global_scale, gate_up, lambda K: 2 * K,
+                         tokens_per_expert, input_offsets, bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit))
+
+
+def linear_forward_nvfp4(blocks, scales_e4m3, global_scale, x, bias=None, out_dtype=None):
+    """A dense linear layer on NVFP4 weights: ``out[t] = (W @ bf16(x[t])) * global_scale (+ bias)``.  ``blocks`` uint8
+    [N, K/2], ``scales_e4m3`` uint8 [N, K/16], ``global_scale`` float32 with one element or None, ``bias`` [N] float32.
+    Exactly ``moe_forward_nvfp4`` on the one-expert view without a table: the same kernels, the same bits.  There is no
+    split-K form."""
+    _forward_only("linear_forward_nvfp4", x, bias)
+    return _nvfp4_launch("linear_forward_nvfp4", blocks, scales_e4m3, global_scale, x, lambda K: K, None, None, bias, out_dtype,
+                         False, dense=True)
+
+
+def linear_gated_forward_nvfp4(blocks, scales_e4m3, global_scale, gate_up, activation="silu", activation_alpha=1.702,
+                               activation_limit=7.0, bias=None, out_dtype=None):
+    """The down projection of a dense gated MLP on NVFP4 weights: ``linear_forward_nvfp4`` on
+    ``bf16(act(gate_up[t, :K], gate_up[t, K:]))``, ``gate_up`` [T, 2K], by the streaming pre-pass of
+    ``moe_gated_forward_nvfp4``."""
+    _forward_only("linear_gated_forward_nvfp4", gate_up, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _nvfp4_launch("linear_gated_forward_nvfp4", blocks, scales_e4m3, global_scale, gate_up, lambda K: 2 * K, None, None,
+                         bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit), dense=True)
+
+
 ROUTE_MAX_EXPERTS = 128
 
 

@@ -15,6 +15,9 @@ shape ``[N]``.  These run on whatever device the tensors live on; on a GPU,
 A second frozen format for the MoE experts, OCP MXFP4 (``quantize_mxfp4`` / ``dequantize_mxfp4``, pure torch): the same
 byte layout with e2m1 codes in the nibbles and one E8M0 power-of-two scale byte per 32 consecutive inputs.  Activation rows
 can also be OCP MXFP6 (``quantize_mxfp6`` / ``dequantize_mxfp6``): e2m3 codes, 32 of them in 24 bytes, the same scales.
+
+A third frozen format, NVFP4 (``quantize_nvfp4`` / ``dequantize_nvfp4``, pure torch): the MXFP4 byte layout and code table
+with one OCP e4m3 scale byte per 16 consecutive inputs and one float32 scale per tensor.
 """
 from __future__ import annotations
 
@@ -23,7 +26,8 @@ import torch.nn.functional as F
 
 __all__ = ["quantize_weights", "dequantize_weights", "reference_quantized_linear",
            "pack_nibbles", "unpack_nibbles", "quantize_mxfp4", "dequantize_mxfp4", "MXFP4_VALUES",
-           "pack_mxfp6", "unpack_mxfp6", "quantize_mxfp6", "dequantize_mxfp6", "MXFP6_VALUES"]
+           "pack_mxfp6", "unpack_mxfp6", "quantize_mxfp6", "dequantize_mxfp6", "MXFP6_VALUES",
+           "quantize_nvfp4", "dequantize_nvfp4", "nvfp4_scale_values", "NVFP4_BLOCK"]
 
 
 def pack_nibbles(q: torch.Tensor) -> torch.Tensor:
@@ -149,6 +153,90 @@ def dequantize_mxfp4(blocks: torch.Tensor, scales: torch.Tensor) -> torch.Tensor
     table = torch.tensor(MXFP4_VALUES, dtype=torch.float32, device=blocks.device)
     w = table[codes.long()].reshape(*blocks.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
     return (w * mxfp4_scale_values(scales).unsqueeze(-1)).reshape(*blocks.shape[:-1], K)
+
+
+# ---- NVFP4: e2m1 elements in the MXFP4 byte layout, one OCP e4m3fn scale byte per 16 consecutive inputs, one float32
+#      scale per tensor (ModelOpt's weight / weight_scale / weight_scale_2)
+
+NVFP4_BLOCK = 16
+_E2M1_MAX, _E4M3_MAX = 6.0, 448.0
+
+
+def nvfp4_scale_values(scales: torch.Tensor) -> torch.Tensor:
+    """e4m3fn bytes (uint8) -> float32, by the definition: sign, four exponent bits of bias 7, three mantissa bits;
+    exponent field 0 is the subnormal ``m * 2^-9``; 0x7F and 0xFF are NaN; the largest value is 448."""
+    if scales.dtype != torch.uint8:
+        raise ValueError("scales must be uint8")
+    s = scales.to(torch.int32)
+    ex, m = (s >> 3) & 15, (s & 7).to(torch.float32)
+    mag = torch.where(ex == 0, m * 2.0 ** -9, torch.ldexp(1.0 + m / 8.0, ex - 7))
+    v = torch.where((s & 0x80) != 0, -mag, mag)
+    return torch.where((s & 0x7F) == 0x7F, torch.full_like(v, float("nan")), v)
+
+
+def _leading_scale(global_scale, lead, device):
+    """``global_scale`` (None: 1) as a float32 tensor that broadcasts over ``[*lead, N, blocks, 16]``."""
+    if global_scale is None:
+        return torch.ones((), dtype=torch.float32, device=device)
+    g = torch.as_tensor(global_scale, dtype=torch.float32, device=device)
+    want = 1
+    for d in lead:
+        want *= d
+    if g.numel() != want:
+        raise ValueError(f"global_scale must hold one value per leading matrix ({want}), got {list(g.shape)}")
+    return g.reshape(*lead, 1, 1, 1)
+
+
+def quantize_nvfp4(weight: torch.Tensor, global_scale=None):
+    """``[..., N, K]`` (K % 16 == 0) -> ``(blocks uint8 [..., N, K/2], scales uint8 [..., N, K/16], global_scale float32)``
+    by ModelOpt's rule.  ``global_scale`` has one value per leading matrix (``[E]`` for ``[E, N, K]``, ``[1]`` for
+    ``[N, K]``); when not given it is ``amax(|W|) / (6 * 448)`` of each matrix, and 1 for an all-zero one.  The block scale
+    is ``block_amax / (6 * global_scale)`` in float32, clamped to 448 and then rounded to e4m3fn to nearest even (a cast of
+    a value above 464 would give NaN: the clamp comes first).  The codes are ``w / (scale * global_scale)``, ``scale`` the
+    rounded one, rounded to e2m1 by ``quantize_mxfp4``'s element rule; a zero block scale gives zero codes.
+    ``global_scale`` multiplies, as ModelOpt's ``weight_scale_2`` does; compressed-tensors checkpoints store its
+    reciprocal (``weight_global_scale``): invert it before handing it to this library."""
+    if weight.dim() < 2 or weight.shape[-1] % NVFP4_BLOCK != 0:
+        raise ValueError("weight must be [..., N, K] with K % 16 == 0")
+    if not bool(torch.isfinite(weight).all()):
+        raise ValueError("quantize_nvfp4: the weights must be finite")
+    lead, K = tuple(weight.shape[:-2]), weight.shape[-1]
+    w = weight.detach().to(torch.float32)
+    if global_scale is None:
+        amax = w.abs().amax(dim=(-2, -1)) if w.numel() else torch.zeros(lead)
+        gs = torch.where(amax == 0, torch.ones_like(amax), amax / (_E2M1_MAX * _E4M3_MAX)).to(torch.float32)
+    else:
+        gs = torch.as_tensor(global_scale, dtype=torch.float32, device=w.device).reshape(lead)
+        if not bool((torch.isfinite(gs) & (gs > 0)).all()):
+            raise ValueError("quantize_nvfp4: global_scale must be finite and positive")
+    x = w.reshape(*weight.shape[:-1], K // NVFP4_BLOCK, NVFP4_BLOCK)
+    g = gs.reshape(*lead, 1, 1, 1)
+    block_scale = (x.abs().amax(dim=-1, keepdim=True) / (_E2M1_MAX * g)).clamp(max=_E4M3_MAX)
+    scales = block_scale.to(torch.float8_e4m3fn).view(torch.uint8)
+    dq = nvfp4_scale_values(scales).to(torch.float64) * g.to(torch.float64)          # what a code is multiplied by
+    v = torch.where(dq == 0, torch.zeros_like(dq), x.abs().to(torch.float64) / torch.where(dq == 0, torch.ones_like(dq), dq))
+    q = torch.where(v < 2, torch.round(v * 2) / 2, torch.where(v < 4, torch.round(v), torch.round(v / 2) * 2)).clamp(max=6.0)
+    mag = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4)).to(torch.uint8)
+    sign = torch.where(dq == 0, torch.zeros_like(mag), torch.signbit(x).to(torch.uint8) << 3)
+    codes = (mag | sign).reshape(*weight.shape[:-1], K)
+    return pack_nibbles(codes), scales.reshape(*weight.shape[:-1], K // NVFP4_BLOCK), gs.reshape(-1) if lead else gs.reshape(1)
+
+
+def dequantize_nvfp4(blocks: torch.Tensor, scales: torch.Tensor, global_scale=None) -> torch.Tensor:
+    """``(blocks [..., N, K/2], scales [..., N, K/16])`` uint8 -> ``[..., N, K]`` float32: the 16-entry e2m1 table times
+    the block's e4m3 scale (exact: at most six significant bits), then times ``global_scale`` (one value per leading
+    matrix; None: 1, nothing more is rounded)."""
+    if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError("blocks and scales must be uint8")
+    K = blocks.shape[-1] * 2
+    if blocks.dim() < 2 or K % NVFP4_BLOCK != 0 or tuple(scales.shape) != tuple(blocks.shape[:-1]) + (K // NVFP4_BLOCK,):
+        raise ValueError("blocks must be [..., N, K/2] and scales [..., N, K/16]")
+    codes = torch.stack([blocks & 0x0F, blocks >> 4], dim=-1).reshape(*blocks.shape[:-1], K)
+    table = torch.tensor(MXFP4_VALUES, dtype=torch.float32, device=blocks.device)
+    w = table[codes.long()].reshape(*blocks.shape[:-1], K // NVFP4_BLOCK, NVFP4_BLOCK) * nvfp4_scale_values(scales).unsqueeze(-1)
+    if global_scale is not None:
+        w = w * _leading_scale(global_scale, tuple(blocks.shape[:-2]), blocks.device)
+    return w.reshape(*blocks.shape[:-1], K)
 
 
 # ---- OCP MXFP6 (e2m3) rows: 32 six-bit codes in 24 bytes, one E8M0 scale byte per 32 consecutive inputs

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 420 /* 0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 430 /* 0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1182,6 +1182,53 @@ FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_
                                    const float *bias, void *out, int out_dtype, int T, int K, int N, int activation,
                                    float act_alpha, float act_limit, int split_k, void *workspace, size_t workspace_bytes,
                                    void *stream);
+
+/* ---- NVFP4 weights, grouped and dense, forward only (FQL_VERSION 430; INTEGRATION.md section 18, DESIGN.md section 38;
+ *      csrc/fql_gemm_nvfp4.h) ----
+ * The format of ModelOpt's "-FP4" / "-NVFP4" exports, as it lies in the checkpoint:
+ *   blocks       [E][N][K / 2] uint8: two e2m1 codes a byte, even k in the low nibble (fql_moe_mx4_fwd's layout and code table:
+ *                0 .. 7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6 and 8 .. 15 their negatives);
+ *   scales_e4m3  [E][N][K / 16] uint8: byte b is the OCP e4m3fn value of those bits (bias 7, subnormals, largest value 448, 0x7F
+ *                and 0xFF NaN, the sign bit honoured as arithmetic gives it); it scales weight row n, inputs 16 b .. 16 b + 15;
+ *   global_scale [E] float32, or NULL for 1: it MULTIPLIES (ModelOpt's weight_scale_2; compressed-tensors stores the reciprocal).
+ *   W_e[n][k] = e2m1(code) * e4m3(scale byte), exact in bfloat16, and
+ *   out[t][n] = round_OUT( fl32( fl32(acc * global_scale[e]) + bias[e][n] ) ),   acc = sum_k bf16(x[t][k]) * W_e[n][k]
+ *   with float32 accumulation on v_mfma_f32_32x32x16_bf16 in fql_moe_mx4_fwd's fixed order (k ascending, 16 a step, an
+ *   accumulator that starts at zero).  The multiply comes first, then the add, two roundings, never an FMA; with neither a
+ *   global scale nor a bias the result is acc.  K % 32 == 0, any N >= 1.  inputs [T][K] float32 (rounded once to bfloat16) or
+ *   bfloat16; float16 rows are refused (FQL_ERR_DTYPE).
+ * fql_moe_nvfp4_fwd:     the grouped GEMM.  The table contract is fql_moe_fwd_f32's: raw pairs in any order, clipped, rows no
+ *                        expert covers are zero; both table pointers NULL with E == 1 is one segment of all rows.
+ * fql_moe_nvfp4_glu_fwd: the same on h = bf16(act(gate_up[t][k], gate_up[t][K + k])), gate_up [T][2K], by fql_moe_mx4_glu_fwd's
+ *                        pre-pass into the workspace (fql_moe_nvfp4_workspace_bytes(E, T, K, N, 1): h [T][K] bfloat16, its layout).
+ * fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd: one matrix blocks [N][K / 2], scales_e4m3 [N][K / 16], global_scale [1] or
+ *                        NULL, bias [N], no table: exactly the grouped launchers with E = 1.  There is no split-K form.
+ *                        Workspace: fql_linear_nvfp4_workspace_bytes(T, K, N, gated).
+ *   Two kernels, the 64 x 128 tile and a one-wave decode kernel, return THE SAME BITS for every element; T alone chooses
+ *   (T <= FQL_NVFP4_DECODE_MAX_ROWS in csrc/fql_mx4.hip; fql_int4_tune.h: fql_tune_set_nvfp4_decode_max_rows /
+ *   fql_tune_nvfp4_kernel).  No atomics, every element written once; the grouped call equals E one-expert calls bit for bit.
+ *   NON-FINITE: a NaN scale byte makes its 16 weights NaN, zeros included, so every output of that weight row is NaN for the
+ *   rows of that expert only; a non-finite activation makes exactly its own output row NaN; global_scale is not screened.
+ *   Return codes: fql_moe_mx4_fwd's, in its order (global_scale not 4-byte aligned: FQL_ERR_ALIGNMENT); the glu and the
+ *   gated linear entries then FQL_ERR_WORKSPACE. */
+FQL_API size_t fql_moe_nvfp4_workspace_bytes(int E, int T, int K, int N, int gated);
+FQL_API int fql_moe_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                              int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                              void *out, int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                              void *stream);
+FQL_API int fql_moe_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *gate_up,
+                                  int in_dtype, const float *bias, const int32_t *tokens_per_expert,
+                                  const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                                  int activation, float act_alpha, float act_limit, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+FQL_API size_t fql_linear_nvfp4_workspace_bytes(int T, int K, int N, int gated);
+FQL_API int fql_linear_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                 int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+FQL_API int fql_linear_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                     const void *gate_up, int in_dtype, const float *bias, void *out, int out_dtype, int T, int K,
+                                     int N, int activation, float act_alpha, float act_limit, void *workspace,
+                                     size_t workspace_bytes, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -82,6 +82,13 @@ FQL_API int fql_tune_set_mx4_linear_slices(int slices);
  * decode kernel (both with S = 1: the split_k == 0 path), 2 the split form with S slices.  Keeps no state. */
 FQL_API int fql_tune_mx4_linear_kernel(int T, int K, int N);
 
+/* The pair of the NVFP4 entries (fql_moe_nvfp4_fwd / _glu_fwd and fql_linear_nvfp4_fwd / _glu_fwd; fql_int4.h, FQL_VERSION 430),
+ * with a threshold of its own: rows (T) up to which the decode kernel runs; 0: always the tile kernel, INT_MAX: the decode
+ * kernel wherever its grid allows.  Returns the previous value; a negative `rows` changes nothing.  Same bits either way. */
+FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows);
+/* 0: those entries would run the 64 x 128 tile kernel on this shape now, 1: the decode kernel.  Keeps no state. */
+FQL_API int fql_tune_nvfp4_kernel(int E, int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -465,6 +465,41 @@ def calls(dev, fq, ops):
     for dt in (F32, BF16):
         yield f"linear_backward_input_mxfp4 {dt}", lambda: ops.linear_backward_input_mxfp4(Pl, Sl, gy[:16].to(dt))
 
+    # the NVFP4 ops, behind the lines above (their random draws come last): the MXFP4 code bytes under e4m3 scale bytes of
+    # every finite magnitude and both signs and one global scale per expert, the same K = 96, N = 40 and table, decode and
+    # tile forced in turn through their own hook; the dense ops on expert 0's matrix and the first 16 rows
+    Sn = torch.randint(0, 0x7F, (E, N, K // 16), dtype=torch.uint8, generator=d.gen)
+    Sn = (Sn | (torch.randint(0, 2, (E, N, K // 16), dtype=torch.uint8, generator=d.gen) << 7)).to(dev)
+    Gn = (torch.rand(E, generator=d.gen) + 0.5).to(dev)
+
+    def forced_nv(which, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = lib.fql_tune_set_nvfp4_decode_max_rows(2 ** 31 - 1 if which == "decode" else 0)
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_nvfp4_decode_max_rows(old)
+        return run
+
+    for which in ("decode", "tile"):
+        for btag, b in (("", None), (" bias", biasm)):
+            for dt in (F32, BF16):
+                tag = f"{dt}{btag} {which}"
+                yield f"moe_forward_nvfp4 {tag}", forced_nv(which, lambda: ops.moe_forward_nvfp4(Pm, Sn, Gn, x.to(dt), tpe, offs, bias=b))
+                yield f"moe_forward_nvfp4 no global {tag}", forced_nv(which, lambda: ops.moe_forward_nvfp4(
+                    Pm, Sn, None, x.to(dt), tpe, offs, bias=b))
+                yield f"moe_gated_forward_nvfp4 {tag}", forced_nv(which, lambda: ops.moe_gated_forward_nvfp4(
+                    Pm, Sn, Gn, gu.to(dt), tpe, offs, bias=b, **glu))
+                yield f"moe_forward_nvfp4 {tag} ->f16", forced_nv(which, lambda: ops.moe_forward_nvfp4(
+                    Pm, Sn, Gn, x.to(dt), tpe, offs, bias=b, out_dtype=F16))
+                bd = None if b is None else b[0]
+                yield f"linear_forward_nvfp4 {tag}", forced_nv(which, lambda: ops.linear_forward_nvfp4(
+                    Pm[0], Sn[0], Gn[:1], x[:16].to(dt), bias=bd))
+                yield f"linear_gated_forward_nvfp4 {tag}", forced_nv(which, lambda: ops.linear_gated_forward_nvfp4(
+                    Pm[0], Sn[0], Gn[:1], gu[:16].to(dt), bias=bd, **glu))
+
 
 def digest(t):
     t = t.detach().contiguous().cpu()
