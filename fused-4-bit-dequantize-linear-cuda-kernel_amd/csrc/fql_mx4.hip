@@ -5,7 +5,7 @@
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
 // fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
 // linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
-// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -18,6 +18,7 @@
 #include "fql_gemm_mx4_sdecode.h"
 #include "fql_mx4_quant.h"
 #include "fql_gemm_nvfp4.h"
+#include "fql_gemm_nvfp4_bwd.h"
 
 #include <cmath>
 
@@ -682,6 +683,31 @@ FQL_API int fql_linear_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scale
 {
     return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
                           out_dtype, {true, activation, act_alpha, act_limit}, 0, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_nvfp4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *grad_out,
+                                    int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
+                                    int out_dtype, int E, int T, int K, int N, void *stream)
+{
+    using C = Mx4BwdCfg;
+    const Mx4Call c = with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N}, global_scale);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty) {
+        if (T == 0) return FQL_OK;
+        // N == 0: the gradient of an empty contraction.  grad_in [T][K] is zeros and no other operand is read.
+        if (!grad_in) return FQL_ERR_NULL_POINTER;
+        (void)hipGetLastError();
+        return hipMemsetAsync(grad_in, 0, (size_t)T * K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    }
+    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(nv4_bwd_kernel<decltype(in)::value, decltype(o)::value>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0, st, c.blocks, c.scales, c.gscale,
+                          c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+        });
+    });
 }
 
 FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows)

@@ -670,10 +670,41 @@ class MXFP4MoEFFN(nn.Module):
                 + (f", precision={self.precision}" if self.precision != "bf16" else ""))
 
 
+class _NVFP4GatedFFNFn(torch.autograd.Function):
+    """``NVFP4MoEFFN(input_grad=True)`` with the input gradient, modelled on ``_MXFP4GatedFFNFn``: ``dh`` on the down weights
+    (``ops.moe_backward_input_nvfp4``), ``ops.glu_backward`` for every activation kind and ``dx`` on the gate / up weights,
+    each tensor written once in the layer's activation type; ``ops.moe_bias_grad`` only for a bias that requires grad."""
+
+    @staticmethod
+    def forward(ctx, inputs, tokens_per_expert, input_offsets, m, b_gu=None, b_d=None):
+        out, gate_up = m._ffn(inputs, tokens_per_expert, input_offsets)
+        ctx.save_for_backward(gate_up, tokens_per_expert, input_offsets)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        gate_up, tpe, offs = ctx.saved_tensors
+        m = ctx.m
+        dt = gate_up.dtype
+        ops.check_activation_rows(gy, "the incoming gradient", dt)
+        need_x, need_bgu, need_bd = ctx.needs_input_grad[0], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        gbd = ops.moe_bias_grad(gy, m.num_experts, tpe, offs) if need_bd else None
+        if not (need_x or need_bgu):
+            return None, None, None, None, None, gbd
+        dh = ops.moe_backward_input_nvfp4(m.down_blocks, m.down_scales, m.down_global, gy, tpe, offs, out_dtype=dt)
+        dgu = ops.glu_backward(gate_up, dh, *m.activation_args, out_dtype=dt)
+        gbgu = ops.moe_bias_grad(dgu, m.num_experts, tpe, offs) if need_bgu else None
+        dx = ops.moe_backward_input_nvfp4(m.gate_up_blocks, m.gate_up_scales, m.gate_up_global, dgu, tpe, offs,
+                                          out_dtype=dt) if need_x else None
+        return dx, None, None, None, gbgu, gbd
+
+
 class NVFP4MoEFFN(nn.Module):
-    """Gated FFN experts on NVFP4 weights (the format of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen and inference
-    only: ``down( act(gate(x), up(x)) )`` per expert, rows pre-grouped by expert, the same ``forward`` as
-    ``MXFP4MoEFFN``.
+    """Gated FFN experts on NVFP4 weights (the format of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen:
+    ``down( act(gate(x), up(x)) )`` per expert, rows pre-grouped by expert, the same ``forward`` as ``MXFP4MoEFFN``.
 
     The buffers are the checkpoint's tensors, never re-quantised: ``gate_up_blocks`` uint8 [E, 2F, H/2] and ``down_blocks``
     [E, H, F/2] hold two e2m1 codes a byte (even input in the low nibble), ``gate_up_scales`` [E, 2F, H/16] and
@@ -685,17 +716,22 @@ class NVFP4MoEFFN(nn.Module):
 
     Both GEMMs are ``ops.moe_forward_nvfp4`` / ``ops.moe_gated_forward_nvfp4``: the weights are exact in bfloat16, the
     activations are rounded once to bfloat16 (float32 inputs) or read as they are (``activation_dtype=torch.bfloat16``),
-    the sums are float32, and a small batch takes the decode kernel with the same bits.  A forward under grad mode on an
-    input that requires grad raises ``RuntimeError``, as ``MXFP4MoEFFN(input_grad=False)`` does (INTEGRATION.md
-    section 18)."""
+    the sums are float32, and a small batch takes the decode kernel with the same bits.
+
+    ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
+    ``RuntimeError``, as ``MXFP4MoEFFN(input_grad=False)`` does.  ``input_grad=True`` makes the layer differentiable in its
+    input and, for biases that ``requires_grad``, in its biases (the weights stay frozen): under grad mode the forward (the
+    same kernels, the same bits) keeps ``gate_up`` and the backward is ``dh = ops.moe_backward_input_nvfp4`` on the down
+    weights, ``ops.glu_backward``, then ``dx`` on the gate / up weights, every tensor in the layer's activation type.  The
+    gradient is straight-through across the forward's two bfloat16 roundings, as ``MXFP4MoEFFN``'s is.  The keyword is
+    configuration, not state: the state-dict keys do not change."""
 
     group_size = None                        # (what the block reads: the scale blocks are the format's, not an option)
-    input_grad = False
     precision = "bf16"
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, activation: str = "silu",
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
-                 activation_dtype=None):
+                 activation_dtype=None, input_grad: bool = False):
         super().__init__()
         if hidden_dim % 32 != 0 or ffn_dim % 32 != 0 or hidden_dim <= 0 or ffn_dim <= 0 or num_experts <= 0:
             raise ValueError("hidden_dim and ffn_dim must be positive multiples of 32 and num_experts positive")
@@ -707,6 +743,7 @@ class NVFP4MoEFFN(nn.Module):
         self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
             activation, activation_alpha, activation_limit)
         self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
+        self.input_grad = bool(input_grad)
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_blocks", torch.zeros(E, 2 * F, H // 2, dtype=torch.uint8))
         self.register_buffer("gate_up_scales", torch.full((E, 2 * F, H // 16), 0x38, dtype=torch.uint8))
@@ -727,7 +764,7 @@ class NVFP4MoEFFN(nn.Module):
         as its bytes); ``gate_up_global`` / ``down_global`` float32 [E], or None for ones; ``gate_up_bias`` [E, 2F] and
         ``down_bias`` [E, H] (both or none).  ``interleaved=True``: rows 0, 2, 4, ... of ``gate_up`` are the gate and
         1, 3, 5, ... the up projection; they are de-interleaved once, the bias included.  ``kwargs``: the constructor's
-        activation arguments and ``activation_dtype``."""
+        activation arguments, ``activation_dtype`` and ``input_grad``."""
         def check(name, b, s, g):
             if s.dtype == torch.float8_e4m3fn:
                 s = s.view(torch.uint8)
@@ -783,21 +820,31 @@ class NVFP4MoEFFN(nn.Module):
         the same type."""
         if not inputs.is_cuda:
             raise RuntimeError("NVFP4MoEFFN runs on the GPU (the product path has no CPU fallback)")
-        if torch.is_grad_enabled() and inputs.requires_grad:
+        if not self.input_grad and torch.is_grad_enabled() and inputs.requires_grad:
             raise RuntimeError("NVFP4MoEFFN is inference-only: the NVFP4 format has no backward.  Run it under "
-                               "torch.no_grad(), or on a detached input")
+                               "torch.no_grad(), or on a detached input (or build the layer with input_grad=True)")
         dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
         if inputs.dim() != 2 or inputs.dtype != dt:
             raise RuntimeError(f"NVFP4MoEFFN: inputs must be a 2-D {dt} tensor (the layer's activation_dtype), got "
                                f"{inputs.dtype}")
+        b_gu, b_d = self.biases
+        if self.input_grad and torch.is_grad_enabled() and (
+                inputs.requires_grad or (b_gu is not None and (b_gu.requires_grad or b_d.requires_grad))):
+            return _NVFP4GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self, b_gu, b_d)
+        return self._ffn(inputs, tokens_per_expert, input_offsets)[0]
+
+    def _ffn(self, inputs, tokens_per_expert, input_offsets):
+        """(y, gate_up) in the layer's activation type, on detached biases (their gradient is the autograd node's
+        business)."""
         from . import ops
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
         b_gu, b_d = self.biases
         b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
         gate_up = ops.moe_forward_nvfp4(self.gate_up_blocks, self.gate_up_scales, self.gate_up_global, inputs.detach(),
                                         tokens_per_expert, input_offsets, bias=b_gu, out_dtype=dt)
         return ops.moe_gated_forward_nvfp4(self.down_blocks, self.down_scales, self.down_global, gate_up, tokens_per_expert,
                                            input_offsets, activation=self.activation, activation_alpha=self.activation_alpha,
-                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt)
+                                           activation_limit=self.activation_limit, bias=b_d, out_dtype=dt), gate_up
 
     biases = MXFP4MoEFFN.biases
     total_memory_bytes = MXFP4MoEFFN.total_memory_bytes
@@ -805,7 +852,7 @@ class NVFP4MoEFFN(nn.Module):
     _activation_repr = QuantizedMoEFFN._activation_repr
 
     def extra_repr(self) -> str:
-        return "format=nvfp4" + self._activation_repr()
+        return "format=nvfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else "")
 
 
 class QuantizedSparseMoEBlock(nn.Module):
@@ -818,7 +865,7 @@ class QuantizedSparseMoEBlock(nn.Module):
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
     when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or an ``MXFP4MoEFFN``: built with ``input_grad=True`` it trains the
     router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``; or an ``NVFP4MoEFFN``,
-    inference only).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    with the same ``input_grad`` keyword and the same rule).  State-dict keys: ``gate.weight`` and ``experts.*``.
     The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
     to the activations' type: no cast pass either side of it.
 

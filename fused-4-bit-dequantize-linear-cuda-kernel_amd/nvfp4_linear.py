@@ -1,7 +1,24 @@
 """``NVFP4Linear``: a dense ``nn.Linear`` on NVFP4 weights (the encoding of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen
-and inference only (csrc/fql_gemm_nvfp4.h)."""
+(csrc/fql_gemm_nvfp4.h, csrc/fql_gemm_nvfp4_bwd.h; DESIGN.md sections 38 and 39)."""
 import torch
 import torch.nn as nn
+
+
+class _NVFP4LinearFn(torch.autograd.Function):
+    """``NVFP4Linear(input_grad=True)``: the forward's kernels, and ``ops.linear_backward_input_nvfp4`` for ``x.grad`` (the
+    weights and the bias are frozen).  Straight-through across the forward's bfloat16 rounding of ``x``."""
+
+    @staticmethod
+    def forward(ctx, x2, m):
+        ctx.m = m
+        return m._rows(x2.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        from . import ops
+        m = ctx.m
+        return ops.linear_backward_input_nvfp4(m.blocks, m.scales, m.global_scale, gy.contiguous(), out_dtype=gy.dtype), None
 
 
 class NVFP4Linear(nn.Module):
@@ -19,14 +36,17 @@ class NVFP4Linear(nn.Module):
     there is no split-K form.  On the CPU the forward is the definition,
     ``(bf16(x) @ dequantize_nvfp4(blocks, scales).T) * global_scale (+ bias)`` in float32.
 
-    Inference only: a forward under grad mode on an input that requires grad raises ``RuntimeError``.  The state-dict keys
-    are ``blocks``, ``scales``, ``global_scale`` (and ``bias``)."""
+    ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
+    ``RuntimeError``.  ``input_grad=True`` gives ``x.grad`` through ``ops.linear_backward_input_nvfp4`` (on the GPU only),
+    straight-through across the bfloat16 rounding of ``x``.  It is configuration, not state: the
+    state-dict keys are ``blocks``, ``scales``, ``global_scale`` (and ``bias``)."""
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = False):
+    def __init__(self, in_features: int, out_features: int, bias: bool = False, input_grad: bool = False):
         super().__init__()
         if in_features <= 0 or in_features % 32 != 0 or out_features <= 0:
             raise ValueError("in_features must be a positive multiple of 32 and out_features positive")
         self.in_features, self.out_features = in_features, out_features
+        self.input_grad = bool(input_grad)
         self.register_buffer("blocks", torch.zeros(out_features, in_features // 2, dtype=torch.uint8))
         self.register_buffer("scales", torch.full((out_features, in_features // 16), 0x38, dtype=torch.uint8))
         self.register_buffer("global_scale", torch.ones(1, dtype=torch.float32))
@@ -36,10 +56,10 @@ class NVFP4Linear(nn.Module):
             self.register_buffer("bias", None)
 
     @classmethod
-    def from_nvfp4(cls, blocks, scales, global_scale=None, bias=None) -> "NVFP4Linear":
+    def from_nvfp4(cls, blocks, scales, global_scale=None, bias=None, **kwargs) -> "NVFP4Linear":
         """The checkpoint's tensors as they are: ``blocks`` uint8 [N, K/2], ``scales`` uint8 [N, K/16] (a
         ``float8_e4m3fn`` tensor is viewed as its bytes), ``global_scale`` one float32 value or None for 1, ``bias`` [N]
-        or None."""
+        or None.  ``kwargs``: ``input_grad``."""
         if scales.dtype == torch.float8_e4m3fn:
             scales = scales.view(torch.uint8)
         if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
@@ -53,7 +73,7 @@ class NVFP4Linear(nn.Module):
             global_scale = torch.as_tensor(global_scale, dtype=torch.float32)
             if global_scale.numel() != 1:
                 raise ValueError("global_scale must hold one value")
-        m = cls(K, N, bias=bias is not None)
+        m = cls(K, N, bias=bias is not None, **kwargs)
         m.blocks, m.scales = blocks.contiguous().clone(), scales.contiguous().clone()
         if global_scale is not None:
             m.global_scale = global_scale.detach().reshape(1).clone().to(blocks.device)
@@ -62,11 +82,16 @@ class NVFP4Linear(nn.Module):
         return m
 
     @classmethod
-    def from_linear(cls, linear: nn.Linear) -> "NVFP4Linear":
-        """Quantise an ``nn.Linear`` with ``quantize.quantize_nvfp4``; its bias is kept (float32)."""
+    def from_linear(cls, linear: nn.Linear, **kwargs) -> "NVFP4Linear":
+        """Quantise an ``nn.Linear`` with ``quantize.quantize_nvfp4``; its bias is kept (float32).  ``kwargs``:
+        ``input_grad``."""
         from .quantize import quantize_nvfp4
         blocks, scales, gs = quantize_nvfp4(linear.weight.detach().float())
-        return cls.from_nvfp4(blocks, scales, gs, bias=None if linear.bias is None else linear.bias.detach())
+        return cls.from_nvfp4(blocks, scales, gs, bias=None if linear.bias is None else linear.bias.detach(), **kwargs)
+
+    def _rows(self, x2):
+        from . import ops
+        return ops.linear_forward_nvfp4(self.blocks, self.scales, self.global_scale, x2, bias=self.bias, out_dtype=x2.dtype)
 
     def forward(self, x):
         if x.dtype not in (torch.float32, torch.bfloat16):
@@ -75,20 +100,23 @@ class NVFP4Linear(nn.Module):
         if x.dim() < 1 or x.shape[-1] != self.in_features:
             raise RuntimeError(f"NVFP4Linear: the last dimension of the input must be in_features = {self.in_features}, got "
                                f"{list(x.shape)}")
-        if torch.is_grad_enabled() and x.requires_grad:
+        wants = torch.is_grad_enabled() and x.requires_grad
+        if wants and not self.input_grad:
             raise RuntimeError("NVFP4Linear is inference-only: the NVFP4 format has no backward.  Run it under "
-                               "torch.no_grad(), or on a detached input")
+                               "torch.no_grad(), or on a detached input (or build the layer with input_grad=True)")
         lead = x.shape[:-1]
         if not x.is_cuda:
             from .quantize import dequantize_nvfp4
+            if wants:
+                raise RuntimeError("NVFP4Linear: the input gradient runs on the GPU only")
             y = (x.detach().bfloat16().float() @ dequantize_nvfp4(self.blocks, self.scales).T) * self.global_scale
             if self.bias is not None:
                 y = y + self.bias
             return y.to(x.dtype)
-        from . import ops
         x2 = x.reshape(-1, self.in_features)
-        y = ops.linear_forward_nvfp4(self.blocks, self.scales, self.global_scale, x2, bias=self.bias, out_dtype=x2.dtype)
+        y = _NVFP4LinearFn.apply(x2, self) if wants else self._rows(x2)
         return y.reshape(*lead, self.out_features)
 
     def extra_repr(self) -> str:
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=nvfp4"
+        return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=nvfp4"
+                + (", input_grad=True" if self.input_grad else ""))

@@ -1527,6 +1527,61 @@ def moe_backward_input_mxfp4(blocks, scales, grad_out, tokens_per_expert, input_
     return out
 
 
+def _nvfp4_backward_input(name, blocks, scales, global_scale, grad_out, tokens_per_expert, input_offsets, out_dtype, dense):
+    """Both NVFP4 input gradients, ``_nvfp4_launch``'s order of checks: types and shapes first, then the devices."""
+    if grad_out.dim() != 2 or grad_out.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: grad_out must be a float32 or bfloat16 [T, N] tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    wd = 2 if dense else 3
+    shape = "[N, K/2] and scales_e4m3 uint8 [N, K/16]" if dense else "[num_experts, N, K/2] and scales_e4m3 uint8 [num_experts, N, K/16]"
+    if blocks.dtype != torch.uint8 or blocks.dim() != wd or scales.dtype != torch.uint8 or scales.dim() != wd:
+        raise RuntimeError(f"blocks must be uint8 {shape}")
+    E = 1 if dense else blocks.shape[0]
+    N, K = blocks.shape[-2], 2 * blocks.shape[-1]
+    if K % 32 != 0 or tuple(scales.shape) != tuple(blocks.shape[:-1]) + (K // 16,):
+        raise RuntimeError(f"blocks must be uint8 {shape} with K % 32 == 0")
+    if grad_out.shape[1] != N:
+        raise RuntimeError(f"ops.{name}: grad_out must be [T, N] for blocks {list(blocks.shape)}")
+    if global_scale is not None and (not isinstance(global_scale, torch.Tensor) or global_scale.dtype != torch.float32
+                                     or global_scale.numel() != E or global_scale.dim() > 1):
+        raise RuntimeError(f"global_scale must be a float32 tensor of {E} element(s) (one per expert), or None")
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not grad_out.is_cuda:
+        raise RuntimeError(f"ops.{name}: grad_out must be a CUDA tensor")
+    dev, T = grad_out.device, grad_out.shape[0]
+    _on(dev, blocks=blocks, scales_e4m3=scales, global_scale=global_scale)
+    tpe, offs = (None, None) if dense else _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
+    out = torch.empty((T, K), dtype=out_dtype, device=dev)
+    _launch("fql_moe_nvfp4_bwd_input", dev, blocks.contiguous(), scales.contiguous(),
+            None if global_scale is None else global_scale.contiguous(), grad_out.contiguous(), _DTYPES[grad_out.dtype], tpe, offs,
+            out, _DTYPES[out_dtype], E, T, K, N)
+    return out
+
+
+def moe_backward_input_nvfp4(blocks, scales_e4m3, global_scale, grad_out, tokens_per_expert, input_offsets, out_dtype=None):
+    """Grouped ``grad_in[t] = (bf16(grad_out[t]) @ W_e) * global_scale[e]`` on NVFP4 expert weights, for the rows of each
+    expert's range; rows no expert covers are zero.  ``blocks`` uint8 [E, N, K/2], ``scales_e4m3`` uint8 [E, N, K/16] and
+    ``global_scale`` float32 [E] or None (1) as ``moe_forward_nvfp4`` takes them; ``grad_out`` [T, N] float32 (rounded once
+    to bfloat16) or bfloat16 -> [T, K] ``out_dtype`` (default float32), rounded once.  The transposed bfloat16 matrix-core
+    GEMM of csrc/fql_gemm_nvfp4_bwd.h: the weights without the global scale are exact, the accumulation is float32 in a
+    fixed order, so the grouped call equals the one-expert calls bit for bit.  The table as ``moe_forward`` takes it, or
+    none with one expert (all rows).  A non-finite element of a gradient row makes that whole row of the result NaN; a
+    NaN scale byte makes its 16 columns NaN on the rows of its expert."""
+    return _nvfp4_backward_input("moe_backward_input_nvfp4", blocks, scales_e4m3, global_scale, grad_out, tokens_per_expert,
+                                 input_offsets, out_dtype, False)
+
+
+def linear_backward_input_nvfp4(blocks, scales_e4m3, global_scale, grad_out, out_dtype=None):
+    """``grad_in[t] = (bf16(grad_out[t]) @ W) * global_scale`` on dense NVFP4 weights ``blocks`` [N, K/2] / ``scales_e4m3``
+    [N, K/16] / ``global_scale`` float32 with one element or None: ``moe_backward_input_nvfp4`` on the one-expert view
+    without a table, the same kernel, the same bits.  ``grad_out`` [T, N] float32 or bfloat16 -> [T, K] ``out_dtype``
+    (default float32)."""
+    return _nvfp4_backward_input("linear_backward_input_nvfp4", blocks, scales_e4m3, global_scale, grad_out, None, None,
+                                 out_dtype, True)
+
+
 def moe_bias_grad(grad_rows, num_experts, tokens_per_expert=None, input_offsets=None):
     """Gradient of a per-expert bias: ``grad_bias[e] = sum of grad_rows[t] over the rows t of expert e`` -> [E, N] float32.
     ``grad_rows`` [T, N] float32 / float16 / bfloat16 (read as it is, widened exactly); the expert table as

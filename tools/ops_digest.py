@@ -23,7 +23,8 @@ once on its decode kernel and once on its tile kernel (forced through the tuning
 and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision="fp6"``, ``moe_forward_mxfp4_fp6`` and
 ``quantize_rows_mxfp6``; and behind those the dense MXFP4 linear ops on one expert's matrix and 16 rows:
 ``linear_forward_mxfp4`` and ``linear_gated_forward_mxfp4`` with the tile kernel, the grouped decode kernel and the split
-form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``."""
+form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``; then the NVFP4 forward ops, decode and
+tile, and last ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands."""
 import argparse
 import hashlib
 import os
@@ -499,6 +500,15 @@ def calls(dev, fq, ops):
                     Pm[0], Sn[0], Gn[:1], x[:16].to(dt), bias=bd))
                 yield f"linear_gated_forward_nvfp4 {tag}", forced_nv(which, lambda: ops.linear_gated_forward_nvfp4(
                     Pm[0], Sn[0], Gn[:1], gu[:16].to(dt), bias=bd, **glu))
+
+    # the NVFP4 input gradient, behind the lines above (no new random draw: the MXFP4 lines' gy on the NVFP4 operands); one
+    # kernel, nothing to force; the dense op on expert 0's matrix and the first 16 rows
+    for dt in (F32, BF16):
+        for do in (F32, BF16):
+            yield f"moe_backward_input_nvfp4 {dt}->{do}", lambda: ops.moe_backward_input_nvfp4(
+                Pm, Sn, Gn, gy.to(dt), tpe, offs, out_dtype=do)
+        yield f"moe_backward_input_nvfp4 no global {dt}", lambda: ops.moe_backward_input_nvfp4(Pm, Sn, None, gy.to(dt), tpe, offs)
+        yield f"linear_backward_input_nvfp4 {dt}", lambda: ops.linear_backward_input_nvfp4(Pm[0], Sn[0], Gn[:1], gy[:16].to(dt))
 
 
 def digest(t):
