@@ -30,8 +30,14 @@ moe_backward_input_mxfp4_lora, with NaN shrunk rows where a scene leaves a row u
 block also wraps LoRAMXFP4MoEFFN experts, and the dense ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4, which have
 no expert table, replay their split form (two launches and a partial-sum workspace) over changing rows.
 
+The NVFP4 experts (ops.moe_forward_nvfp4 / moe_gated_forward_nvfp4 under both kernel forms pinned, and
+ops.moe_backward_input_nvfp4) go through the same scenes with a global scale per expert and a bias, at K = 288 and 96 and,
+for the plain forward, at K = 608, where the decode kernel's load ring consumes a refilled slot; the dense
+ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 replay over changing rows, and the block also wraps NVFP4MoEFFN.
+
 Every family asserts the kernel id the library reports for its shape (fql_tune_chosen_cfg / fql_tune_mx4_kernel /
-fql_tune_mx4_scaled_kernel / fql_tune_mx4_f6_kernel / fql_tune_mx4_linear_kernel; the adapter entries have one form): if a
+fql_tune_mx4_scaled_kernel / fql_tune_mx4_f6_kernel / fql_tune_mx4_linear_kernel / fql_tune_nvfp4_kernel; the adapter entries
+and the backwards have one form): if a
 heuristic change moves the call, the test says so instead of silently testing another kernel.  test_gpu_side_stream.py
 runs the same families on side streams."""
 import functools
@@ -53,6 +59,7 @@ from test_gpu_mxfp4_f6 import SAME_INPUT_BOUND as MX6_BOUND, q_host as q6_host
 from test_gpu_mxfp4_f8 import quantise
 from test_gpu_mxfp4_linear import gaussian_bound as linear_bound, own_hidden as linear_own_hidden, problem as linear_problem
 from test_gpu_mxfp4_lora import SAME_INPUT_BOUND as LORA_BASE_BOUND, bound as lora_bound
+from test_gpu_nvfp4 import GATED_BOUND as NV4_GATED_BOUND, NARROW as NV4_NARROW, epilogue as nv4_epilogue, problem as nv4_problem
 from test_route_capped_cpu import plan_reference
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +67,7 @@ DEV = "cuda"
 INT_MAX = 2 ** 31 - 1
 BLOCK_REL = 4e-6                    # the block against its dense float64 sum (tests/test_gpu_sparse_moe_block_capped.py REL)
 assert MX4_BOUND == 2.64e-7 and MX4_Q_BOUND == 3e-5 and MX6_BOUND == 3e-5 and LORA_BASE_BOUND == MX4_BOUND
+assert NV4_GATED_BOUND == 4 * 1.7e-5
 MX4_MODE = {"fp8": 1, "fp4": 2}     # the mode of fql_tune_set_mx4_scaled_decode_max_rows / fql_tune_mx4_scaled_kernel
 FORM = {"tile": 0, "decode": 1}     # what fql_tune_mx4_kernel / _scaled_kernel / _f6_kernel report
 
@@ -72,19 +80,21 @@ def lib():
 @pytest.fixture
 def tune():
     """tune(mx4="decode" | "tile", w4=0 | 1, scaled=("fp8" | "fp4", "decode" | "tile"), f6="decode" | "tile",
-    linear=(rows of the split range, slices S)): the library's kernel choice for this test; its own comes back afterwards."""
+    linear=(rows of the split range, slices S), nvfp4="decode" | "tile"): the library's kernel choice for this test; its
+    own comes back afterwards."""
     L = lib()
     rows_of = {"decode": INT_MAX, "tile": 0}
     decode = L.fql_tune_set_mx4_decode_max_rows(-1)                  # (a negative value changes nothing)
     scaled_was = {mode: L.fql_tune_set_mx4_scaled_decode_max_rows(mode, -1) for mode in MX4_MODE.values()}
     f6_was = L.fql_tune_set_mx4_f6_decode_max_rows(-1)
     lin_rows = L.fql_tune_set_mx4_linear_decode_max_rows(-1)
+    nvfp4_was = L.fql_tune_set_nvfp4_decode_max_rows(-1)
     lin_slices = L.fql_tune_set_mx4_linear_slices(0)
     L.fql_tune_set_mx4_linear_slices(lin_slices)
     w4 = L.fql_tune_set_w4(1)
     L.fql_tune_set_w4(w4)
 
-    def use(mx4=None, w4=None, scaled=None, f6=None, linear=None):
+    def use(mx4=None, w4=None, scaled=None, f6=None, linear=None, nvfp4=None):
         if mx4 is not None:
             L.fql_tune_set_mx4_decode_max_rows(rows_of[mx4])
         if w4 is not None:
@@ -96,6 +106,8 @@ def tune():
         if linear is not None:
             L.fql_tune_set_mx4_linear_decode_max_rows(linear[0])
             L.fql_tune_set_mx4_linear_slices(linear[1])
+        if nvfp4 is not None:
+            L.fql_tune_set_nvfp4_decode_max_rows(rows_of[nvfp4])
     try:
         yield use
     finally:
@@ -105,6 +117,7 @@ def tune():
         L.fql_tune_set_mx4_f6_decode_max_rows(f6_was)
         L.fql_tune_set_mx4_linear_decode_max_rows(lin_rows)
         L.fql_tune_set_mx4_linear_slices(lin_slices)
+        L.fql_tune_set_nvfp4_decode_max_rows(nvfp4_was)
         L.fql_tune_set_w4(w4)
 
 
@@ -538,6 +551,92 @@ def mx4_lora(K, N, r, kind):
     return Family(E, T, MX4_RAGGED, make_rows, call, reference, bound)
 
 
+# ---- NVFP4
+
+NV4_COUNTS, NV4_TAIL = (0, 1, 5, 32, 33), 2          # MX4_RAGGED as test_gpu_nvfp4.problem takes it: E = 5, T = 73
+
+
+def nv4_weights(K, N, integer):
+    """test_gpu_nvfp4.problem on E = 5, T = 73: random codes, scale bytes 0x30 .. 0x47, a power-of-two global scale that
+    differs between neighbouring experts, a bias (integers with ``integer``).  Returns (p, W float64 [E, N, K] on the
+    device, WITHOUT the global scale)."""
+    p = (nv4_problem(K, N, counts=NV4_COUNTS, tail=NV4_TAIL, scale_range=NV4_NARROW, integer=True) if integer else
+         nv4_problem(K, N, counts=NV4_COUNTS, tail=NV4_TAIL, scale_range=NV4_NARROW, seed=7))
+    assert (p["E"], p["T"]) == (5, 73) and len(set(p["gs"].tolist())) == 5
+    return p, p["W"].to(DEV)
+
+
+def nv4_grouped64(rows64, W_of, ranges, C, gs, bias=None):
+    """float64 [T, C]: the contract of csrc/fql_gemm_nvfp4.h on a float64 sum, fl32(fl32(fl32(acc) * gs[e]) + bias[e]), over
+    the rows of expert e, zero elsewhere."""
+    out = torch.zeros(rows64.shape[0], C, dtype=torch.float64, device=rows64.device)
+    for e, (lo, hi) in enumerate(ranges):
+        if hi > lo:
+            out[lo:hi] = nv4_epilogue(rows64[lo:hi] @ W_of(e), gs[e], None if bias is None else bias[e])
+    return out
+
+
+def nv4_form(kernel, E, T, K, N):
+    return (lambda: (lib().fql_tune_nvfp4_kernel(E, T, K, N), FORM[kernel])), dict(nvfp4=kernel)
+
+
+def nv4_forward(K, N, kernel):
+    """ops.moe_forward_nvfp4 with the global scales and a bias, forced to the tile or the decode kernel, on the integer
+    recipe of tests/test_gpu_nvfp4.py (rows in [-4, 4]; every sum below 2^16, asserted): the float32 result is exact."""
+    p, W = nv4_weights(K, N, True)
+    E, T = p["E"], p["T"]
+
+    def make_rows(seed):
+        return (torch.randint(-4, 5, (T, K), generator=gen(seed, K, N, 11)).float().to(DEV),)
+
+    def call(x, tpe, offs):
+        return ops().moe_forward_nvfp4(p["blocks"], p["scales"], p["gs"], x, tpe, offs, bias=p["bias"], out_dtype=torch.float32)
+
+    def reference(rows, ranges):
+        assert float(grouped64(rows[0].double(), lambda e: W[e].t(), ranges, N).abs().max()) < 2 ** 16
+        return nv4_grouped64(rows[0].double(), lambda e: W[e].t(), ranges, N, p["gs"], p["bias"])
+    which, pin = nv4_form(kernel, E, T, K, N)
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, None, which, pin)
+
+
+def nv4_gated(K, N, kernel):
+    """ops.moe_gated_forward_nvfp4 on Gaussian gate | up rows against the float64 product of the bfloat16-rounded float64 h,
+    at tests/test_gpu_nvfp4.py's GATED_BOUND."""
+    p, W = nv4_weights(K, N, False)
+    E, T = p["E"], p["T"]
+
+    def make_rows(seed):
+        return ((2.0 * torch.randn(T, 2 * K, generator=gen(seed, K, N, 12))).to(DEV),)
+
+    def call(gate_up, tpe, offs):
+        return ops().moe_gated_forward_nvfp4(p["blocks"], p["scales"], p["gs"], gate_up, tpe, offs, bias=p["bias"],
+                                             out_dtype=torch.float32, **act_kw("swiglu_clamp"))
+
+    def reference(rows, ranges):
+        h = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double()
+        return nv4_grouped64(h, lambda e: W[e].t(), ranges, N, p["gs"], p["bias"])
+    which, pin = nv4_form(kernel, E, T, K, N)
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, NV4_GATED_BOUND, which, pin)
+
+
+def nv4_backward(K, N):
+    """ops.moe_backward_input_nvfp4 with the global scales on integer gradients in [-4, 4] (every sum below 2^15, asserted):
+    the float32 result is exact."""
+    p, W = nv4_weights(K, N, True)
+    E, T = p["E"], p["T"]
+
+    def make_rows(seed):
+        return (torch.randint(-4, 5, (T, N), generator=gen(seed, K, N, 13)).float().to(DEV),)
+
+    def call(gy, tpe, offs):
+        return ops().moe_backward_input_nvfp4(p["blocks"], p["scales"], p["gs"], gy, tpe, offs)
+
+    def reference(rows, ranges):
+        assert float(grouped64(rows[0].double(), lambda e: W[e], ranges, K).abs().max()) < 2 ** 15
+        return nv4_grouped64(rows[0].double(), lambda e: W[e], ranges, K, p["gs"])
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, None)
+
+
 # ---- the families, by name (tests/test_gpu_side_stream.py takes its cases from here)
 
 SMALL = dict(E=4, K=512, N=136)                   # wide_tiles < 128: the small regime of choose_cfg (csrc/fql_int4.hip)
@@ -592,6 +691,13 @@ for _K, _N in ((288, 136), (96, 37)):
 for _K, _N, _r in ((288, 136, 16), (96, 37, 64)):                   # (r = 16: one 16-j step of the adapter stage, 64: all four)
     for _kind in ("fwd", "glu", "bwd"):
         FAMILIES[f"mx4-lora-{_kind}-K{_K}-N{_N}-r{_r}"] = functools.partial(mx4_lora, _K, _N, _r, _kind)
+for _K, _N in ((288, 136), (96, 37), (608, 37)):                    # (K = 608: the decode ring's steady state, 9 pairs)
+    for _form in ("tile", "decode"):
+        FAMILIES[f"nv4-K{_K}-N{_N}-{_form}"] = functools.partial(nv4_forward, _K, _N, _form)
+for _K, _N in ((288, 136), (96, 37)):
+    for _form in ("tile", "decode"):
+        FAMILIES[f"nv4-K{_K}-N{_N}-glu-{_form}"] = functools.partial(nv4_gated, _K, _N, _form)
+    FAMILIES[f"nv4-K{_K}-N{_N}-bwd"] = functools.partial(nv4_backward, _K, _N)
 
 
 @pytest.mark.parametrize("name", list(FAMILIES))
@@ -680,6 +786,76 @@ def test_dense_linear_split_form_replays(tune, name):
         del graph
 
 
+# ---- the dense NVFP4 linear op: no expert table; the grouped launchers with E = 1 (the gated entry: a pre-pass in front)
+
+NV4_LINEAR_T, NV4_LINEAR_K, NV4_LINEAR_N = 5, 96, 37
+
+
+def nv4_linear_case(gated):
+    """(call(rows) -> [T, N] float32, make_rows(seed), reference(rows) -> float64, bound or None): expert 3's matrix, global
+    scale and bias of the grouped NVFP4 families as a dense layer.  Plain: the integer recipe, exact.  Gated: Gaussian
+    gate | up rows against the bfloat16-rounded float64 h at NV4_GATED_BOUND."""
+    T, K, N = NV4_LINEAR_T, NV4_LINEAR_K, NV4_LINEAR_N
+    p, W = nv4_weights(K, N, not gated)
+    e = 3
+    blocks, scales, gs, bias = p["blocks"][e], p["scales"][e], p["gs"][e:e + 1], p["bias"][e]
+
+    def make_rows(seed):
+        g = gen(seed, K, N, 14 + gated)
+        return (2.0 * torch.randn(T, 2 * K, generator=g) if gated else torch.randint(-4, 5, (T, K), generator=g).float()).to(DEV)
+
+    def call(rows):
+        if gated:
+            return ops().linear_gated_forward_nvfp4(blocks, scales, gs, rows, bias=bias, out_dtype=torch.float32,
+                                                    **act_kw("swiglu_clamp"))
+        return ops().linear_forward_nvfp4(blocks, scales, gs, rows, bias=bias, out_dtype=torch.float32)
+
+    def reference(rows):
+        x64 = hidden64("swiglu_clamp", rows, ALPHA, LIMIT).bfloat16().double() if gated else rows.double()
+        acc = x64 @ W[e].t()
+        assert gated or float(acc.abs().max()) < 2 ** 16
+        return nv4_epilogue(acc, gs[0], bias)
+    return call, make_rows, reference, NV4_GATED_BOUND if gated else None
+
+
+@pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])
+def test_dense_nvfp4_linear_replays(gated):
+    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 at K = 96, N = 37, T = 5, captured once and replayed over four
+    row sets, the last equal to the first, with SENT in the output before each replay: each replay is the eager result bit
+    for bit, the reference (exactly, plain; within the gated bound), and has overwritten every SENT.  The gated entry's
+    pre-pass writes h into a workspace of the graph's pool in front of the GEMM; a launch that left the capture stream is a
+    capture error or a node missing from the graph, which shows as SENT or as the previous row set's result."""
+    call, make_rows, reference, bound = nv4_linear_case(gated)
+    static = make_rows(0).clone()
+    graph, out, _ = capture(call, [static])
+    try:
+        first = None
+        for i, seed in enumerate((0, 1, 2, 0)):
+            rows = make_rows(seed)
+            static.copy_(rows)
+            out.fill_(SENT)
+            graph.replay()
+            torch.cuda.synchronize()
+            got = out.clone()
+            eager = call(rows.clone())
+            assert same_bits(got, eager), (i, first_diff(got, eager))
+            ref = reference(rows)
+            assert torch.equal(got == SENT, ref.float() == SENT), f"replay {i}: an element still holds the sentinel"
+            if bound is None:
+                assert torch.equal(got.double(), ref), f"replay {i}: not the exact integer result"
+            else:
+                err = rel_fro_dev(got, ref)
+                print(f"dense nvfp4 linear gated replay {i}: rel_fro {err:.3e} (bound {bound:.2e})")
+                assert err <= bound, (i, err)
+            if i == 0:
+                first = got
+            elif i < 3:
+                assert not same_bits(got, first)                     # (the row sets are different problems)
+        assert same_bits(got, first), "the first row set again does not carry the bits of its first replay"
+    finally:
+        del graph
+
+
 # ---- the scratch of the two-phase API, first taken inside a capture
 
 def test_first_gemm_i8_inside_a_capture_then_eager_then_replay():
@@ -738,15 +914,21 @@ def block_weights():
 
 
 def build_block(kind, capped):
-    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared", "mxfp4" or "mxfp4-lora" experts
-    (swiglu_clamp with expert biases; "mxfp4-lora": LoRAMXFP4MoEFFN of rank BRANK around the same MXFP4 experts, with random
+    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared", "mxfp4", "mxfp4-lora" or "nvfp4" experts
+    (swiglu_clamp with expert biases; "nvfp4": NVFP4MoEFFN, whose from_weights gives every expert global scales of its own;
+    "mxfp4-lora": LoRAMXFP4MoEFFN of rank BRANK around the same MXFP4 experts, with random
     values in BOTH B matrices -- a fresh adapter has B = 0 and would test nothing); ``capped``: capacity_factor = 1 (the
     forward then takes a token mask too)."""
     w = block_weights()
     factor = 1.0 if capped else None
-    if kind in ("mxfp4", "mxfp4-lora"):
-        experts = fq().MXFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
-                                                down_bias=w["db"], input_grad=kind == "mxfp4-lora", **act_kw("swiglu_clamp"))
+    if kind in ("mxfp4", "mxfp4-lora", "nvfp4"):
+        if kind == "nvfp4":
+            experts = fq().NVFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
+                                                    down_bias=w["db"], **act_kw("swiglu_clamp"))
+            assert len(set(experts.gate_up_global.tolist())) > 1 and len(set(experts.down_global.tolist())) > 1
+        else:
+            experts = fq().MXFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
+                                                    down_bias=w["db"], input_grad=kind == "mxfp4-lora", **act_kw("swiglu_clamp"))
         if kind == "mxfp4-lora":
             torch.manual_seed(43)                                    # (the adapters' A)
             experts = fq().LoRAMXFP4MoEFFN.from_layer(experts, BRANK, alpha=2.0 * BRANK)
@@ -789,13 +971,20 @@ def block_reference(m, x, mask):
 def ffn64(mod, e, x64, mx4, raw64=None):
     """float64 [T, H]: expert ``e`` of a gated FFN module on every row of ``x64``, on its dequantised weights, with no
     kernel of the library and no expert table: gate_up (+ bias), swiglu_clamp, down (+ bias).  ``mx4``: the roundings of
-    tests/test_gpu_mxfp4.py's block reference (gate_up kept in float32, h rounded to bfloat16).  A module with adapters
+    tests/test_gpu_mxfp4.py's block reference (gate_up kept in float32, h rounded to bfloat16); NVFP4 experts (a module with
+    ``gate_up_global``) are dequantize_nvfp4 times the expert's global scale, in float64.  A module with adapters
     (``raw64``: the rows before their rounding to bfloat16) adds the two adapter terms with the kernels' roundings: the
     shrunk rows v = s A x (ops.lora_shrink on the unrounded rows) and v = s A h (ops.lora_gated_shrink on the float32 h)
     kept in float32, then v and B rounded to bfloat16 on their way into the GEMM."""
     lora = hasattr(mod, "gate_up_lora_A")
     term = lambda rows, A, B: (mod.scaling * (rows @ A[e].double().t())).float().bfloat16().double() @ B[e].bfloat16().double().t()
-    if mx4:
+    if mx4 and hasattr(mod, "gate_up_global"):
+        from fused_int4_amd.quantize import dequantize_nvfp4
+        Wgu = dequantize_nvfp4(mod.gate_up_blocks[e:e + 1].cpu(), mod.gate_up_scales[e:e + 1].cpu())[0].double().to(DEV) \
+            * mod.gate_up_global[e].double()
+        Wd = dequantize_nvfp4(mod.down_blocks[e:e + 1].cpu(), mod.down_scales[e:e + 1].cpu())[0].double().to(DEV) \
+            * mod.down_global[e].double()
+    elif mx4:
         from fused_int4_amd.quantize import dequantize_mxfp4
         Wgu = dequantize_mxfp4(mod.gate_up_blocks[e:e + 1].cpu(), mod.gate_up_scales[e:e + 1].cpu())[0].double().to(DEV)
         Wd = dequantize_mxfp4(mod.down_blocks[e:e + 1].cpu(), mod.down_scales[e:e + 1].cpu())[0].double().to(DEV)
@@ -826,16 +1015,19 @@ def block_float64(m, x, idx, keep, w, mx4):
 
 @pytest.mark.parametrize("T", [3, 130])
 @pytest.mark.parametrize("kind,capped", [("int4", False), ("int4", True), ("int4-shared", True), ("mxfp4", False),
-                                         ("mxfp4", True), ("mxfp4-lora", False), ("mxfp4-lora", True)],
+                                         ("mxfp4", True), ("mxfp4-lora", False), ("mxfp4-lora", True), ("nvfp4", False),
+                                         ("nvfp4", True)],
                          ids=["int4", "int4-capped", "int4-shared-capped", "mxfp4", "mxfp4-capped", "mxfp4-lora",
-                              "mxfp4-lora-capped"])
+                              "mxfp4-lora-capped", "nvfp4", "nvfp4-capped"])
 def test_block_replays_under_changing_routing(tune, kind, capped, T):
     """QuantizedSparseMoEBlock under torch.no_grad(), captured once; then new tokens, the router bias overwritten in place
     so that every token picks experts 2 and 0, a mask with one real token (the capped blocks) and the first scene again.
     "mxfp4-lora": the same MXFP4 experts inside LoRAMXFP4MoEFFN with both B matrices random (its output is asserted once to
     differ from the "mxfp4" block's); the pure-float64 check adds the two adapter terms with the kernels' roundings
-    (ffn64) and is held to the MXFP4 block's own bound, MX4_GATED_BOUND, unscaled."""
-    m, mx4 = build_block(kind, capped), kind in ("mxfp4", "mxfp4-lora")
+    (ffn64) and is held to the MXFP4 block's own bound, MX4_GATED_BOUND, unscaled.  "nvfp4": NVFP4MoEFFN experts; the
+    pure-float64 check multiplies the dequantised weights by the experts' global scales and is held to the same unscaled
+    MX4_GATED_BOUND (DESIGN.md section 40 has the measured values: no constant of its own)."""
+    m, mx4 = build_block(kind, capped), kind in ("mxfp4", "mxfp4-lora", "nvfp4")
     bias0 =m.gate.bias.detach().clone()
     same_two = torch.tensor([60.0, -60.0, 120.0, -60.0], device=DEV)      # (the logits without it stay within +-20)
     xs = [torch.randn(T, BH, generator=gen(i, T)).to(DEV) for i in range(3)]

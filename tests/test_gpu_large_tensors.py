@@ -1351,3 +1351,204 @@ def test_sparse_moe_block_large_weights(kind):
     assert bool(torch.isfinite(out).all()) and err < bound
     assert_guards_intact(*bufs, what="block weights")
     del m, experts, bufs, v
+
+
+# ======================================================================= NVFP4 experts: large WEIGHTS, SCALES and ROWS
+NV4_KERNEL = {"tile": 0, "decode": 1}                        # what fql_tune_nvfp4_kernel reports
+NV4_DECODE_ROWS = 512                                        # the decode threshold the "decode" cases set
+
+
+def nv4_fill(blocks, scales, experts, g):
+    """The integer recipe of tests/test_gpu_nvfp4.py on ``experts`` of an all-0xFF operand set (NaN scale bytes): random
+    codes, scale bytes 0x30 .. 0x47, a power-of-two global scale per expert (2^-2, 2^-1, ...), NaN on every other expert.
+    Returns (global_scale [E] on the device, [W float64 [N, K] without the global scale, on the device])."""
+    from fused_int4_amd.quantize import dequantize_nvfp4
+    E, N = blocks.shape[0], blocks.shape[1]
+    gs = torch.full((E,), NAN, device=DEV)
+    for i, e in enumerate(experts):
+        blocks[e] = torch.randint(0, 256, blocks.shape[1:], generator=g, device=DEV, dtype=torch.uint8)
+        scales[e] = torch.randint(0x30, 0x48, scales.shape[1:], generator=g, device=DEV, dtype=torch.uint8)
+        gs[e] = 2.0 ** (i - 2)
+    Ws = [dequantize_nvfp4(blocks[e:e + 1].cpu(), scales[e:e + 1].cpu())[0].double().to(DEV) for e in experts]
+    return gs, Ws
+
+
+def nv4_exact_refs(rows, Ws, gs, experts, groups, transposed, limit):
+    """float64 references of the forward (rows @ W^T) or the backward (rows @ W) with the one float32 step * global_scale;
+    every sum is asserted below ``limit`` (exact in float32: the products are multiples of 2^-5)."""
+    refs = []
+    for W, e, (lo, hi) in zip(Ws, experts, groups):
+        acc = rows[lo:hi].double() @ (W if transposed else W.T)
+        assert float(acc.abs().max()) < limit
+        refs.append((acc.float() * gs[e]).double())
+    return refs
+
+
+def nv4_forced(lib, kernel, shape, call):
+    """``call()`` with the NVFP4 decode threshold set for ``kernel``; asserts what the library reports for ``shape``."""
+    old = lib.fql_tune_set_nvfp4_decode_max_rows(-1)        # (a negative value changes nothing)
+    lib.fql_tune_set_nvfp4_decode_max_rows(0 if kernel == "tile" else NV4_DECODE_ROWS)
+    try:
+        reported = lib.fql_tune_nvfp4_kernel(*shape)
+        got = call()
+        torch.cuda.synchronize()
+    finally:
+        lib.fql_tune_set_nvfp4_decode_max_rows(old)
+    assert reported == NV4_KERNEL[kernel], (kernel, reported)
+    return got
+
+
+@pytest.mark.parametrize("kernel", ["tile", "decode"])
+def test_nvfp4_large_weights(lib, kernel):
+    """test_mxfp4_forward_large_weights for NVFP4: E * N * K/2 > 2^32 bytes of blocks (and E * N * K/16 = 0.52 GiB of scale
+    bytes), rows to expert 0, the two experts whose blocks straddle 2^31 and 2^32, and E - 1; every other expert holds 0xFF
+    codes, 0xFF scale bytes (NaN) and a NaN global scale.  The integer recipe: the float32 result IS the float64
+    reference.  Both forward kernels; the input gradient on the same operands rides with the tile case."""
+    need(10)
+    K, N, E = 512, 264, 65534
+    wb = N * K // 2
+    assert E * wb > B32 and B31 % wb and B32 % wb
+    experts = [0, B31 // wb, B32 // wb, E - 1]
+    buf = BigGuarded("blocks", E * wb, torch.uint8, 0xFF)
+    blocks = buf.view(E, N, K // 2)
+    blocks.fill_(0xFF)
+    scales = torch.full((E, N, K // 16), 0xFF, dtype=torch.uint8, device=DEV)
+    g = torch.Generator(device=DEV).manual_seed(24)
+    gs, Ws = nv4_fill(blocks, scales, experts, g)
+    groups = [(0, 33), (40, 110), (113, 183), (190, 223)]
+    T = 225
+    tpe, offs = table_of(groups, E=E, experts=experts, T=T)
+    x = torch.randint(-4, 5, (T, K), generator=g, device=DEV).float()
+    assert sum(input_wrap_is_visible(buf, (e + 1) * wb - K // 2, K // 2) for e in experts) >= 3   # each expert's last row
+    refs = nv4_exact_refs(x, Ws, gs, experts, groups, False, 2 ** 16)
+    got = nv4_forced(lib, kernel, (E, T, K, N),
+                     lambda: ops().moe_forward_nvfp4(blocks, scales, gs, x, tpe, offs, out_dtype=torch.float32))
+    check_rows(got, groups, refs, 0.0, f"nvfp4 {kernel}", exact=True)
+    if kernel == "tile":                                    # the input gradient on the same operands (one kernel), as exact
+        gy = torch.randint(-4, 5, (T, N), generator=g, device=DEV).float()
+        grefs = nv4_exact_refs(gy, Ws, gs, experts, groups, True, 2 ** 15)
+        gx = ops().moe_backward_input_nvfp4(blocks, scales, gs, gy, tpe, offs)
+        check_rows(gx, groups, grefs, 0.0, "nvfp4 input gradient", exact=True)
+    assert_guards_intact(buf, what="large NVFP4 weights")
+    del blocks, buf
+
+
+def test_nvfp4_scales_past_2_gib(lib):
+    """The scale operand [E][N][K / 16] past 2^31 bytes: E = 65534, K = 512, N = 1032 is 33024 scale bytes an expert
+    (2^8 x 129: 2^31 is no multiple of it, nor are 2^31 and 2^32 of the 264192 block bytes an expert), 2.016 GiB of scale
+    bytes in a BigGuarded buffer and 16.1 GiB of blocks in a plain one (their own edges are test_nvfp4_large_weights'): the
+    test holds 20.2 GiB.  Rows go to expert 0, the expert whose scale bytes straddle offset 2^31 and E - 1, 73 rows in all;
+    everything else is 0xFF, NaN scale bytes and NaN global scales included, so a scale row fetched at a wrapped offset
+    (the front guard, 0xFF) is a NaN in the result.  The integer recipe: both forward kernels and the input gradient are
+    the float64 reference exactly.  Scale offsets past 2^32 would need 32 GiB of blocks with E <= 65534 and are not
+    tested."""
+    need(21)
+    K, N, E = 512, 1032, 65534
+    wb, sb = N * K // 2, N * K // 16
+    assert E * sb > B31 and B31 % sb and B31 % wb and B32 % wb and E * sb < B32
+    experts = [0, B31 // sb, E - 1]
+    assert experts[1] * sb < B31 < (experts[1] + 1) * sb
+    blocks = torch.empty(E, N, K // 2, dtype=torch.uint8, device=DEV)
+    blocks.fill_(0xFF)
+    sbuf = BigGuarded("scales", E * sb, torch.uint8, 0xFF)
+    scales = sbuf.view(E, N, K // 16)
+    scales.fill_(0xFF)
+    g = torch.Generator(device=DEV).manual_seed(25)
+    gs, Ws = nv4_fill(blocks, scales, experts, g)
+    groups = [(0, 33), (34, 68), (69, 72)]
+    T = 73
+    tpe, offs = table_of(groups, E=E, experts=experts, T=T)
+    x = torch.randint(-4, 5, (T, K), generator=g, device=DEV).float()
+    assert sum(input_wrap_is_visible(sbuf, (e + 1) * sb - K // 16, K // 16) for e in experts[1:]) == 2   # their last rows
+    refs = nv4_exact_refs(x, Ws, gs, experts, groups, False, 2 ** 16)
+    for kernel in ("tile", "decode"):
+        got = nv4_forced(lib, kernel, (E, T, K, N),
+                         lambda: ops().moe_forward_nvfp4(blocks, scales, gs, x, tpe, offs, out_dtype=torch.float32))
+        check_rows(got, groups, refs, 0.0, f"nvfp4 scales past 2 GiB, {kernel}", exact=True)
+        del got
+    gy = torch.randint(-2, 3, (T, N), generator=g, device=DEV).float()       # (|sum| <= 1032 x 2 x 22.5 < 2^16)
+    grefs = nv4_exact_refs(gy, Ws, gs, experts, groups, True, 2 ** 16)
+    gx = ops().moe_backward_input_nvfp4(blocks, scales, gs, gy, tpe, offs)
+    check_rows(gx, groups, grefs, 0.0, "nvfp4 scales past 2 GiB, input gradient", exact=True)
+    assert_guards_intact(sbuf, what="NVFP4 scales past 2 GiB")
+    del blocks, scales, sbuf
+
+
+@pytest.mark.parametrize("case", ["plain", "gated", "bwd-dy", "bwd-dx"])
+def test_nvfp4_rows_past_4_gib(lib, case):
+    """[T, 288] (gated: gate | up rows [T, 320]) float32 past 2^32 bytes: into the forward, into the gated forward's
+    pre-pass, as the gradient dY into the backward (N = 288, K = 32), and as the result dX out of it (K = 288, N = 8, into a
+    guarded buffer full of SENT through the C entry).  T is far above any decode threshold: the tile kernel, asserted.  Each
+    result is bit for bit the same op on a compact copy of the four row groups (the small-shape tests tie that to the
+    reference: tests/test_gpu_nvfp4.py, test_gpu_nvfp4_bwd.py); rows no expert covers are zero and the guards intact."""
+    need(10)
+    E = 4
+    L = ops()
+    gw = torch.Generator().manual_seed(26)
+
+    def weights(N, K):
+        return (torch.randint(0, 256, (E, N, K // 2), generator=gw, dtype=torch.uint8).to(DEV),
+                torch.randint(0x30, 0x48, (E, N, K // 16), generator=gw, dtype=torch.uint8).to(DEV),
+                torch.tensor([0.5, 2.0, 0.25, 4.0], device=DEV))
+
+    if case == "bwd-dx":
+        K, N = ROWS_K, 8
+        T = B32 // (K * 4) + 4096
+        assert T * K * 4 > B32 and (T + 63) // 64 <= 65535
+        groups = row_groups(T, K * 4)
+        assert len(groups) == 4
+        blocks, scales, gs = weights(N, K)
+        gy = torch.randn(T, N, generator=torch.Generator(device=DEV).manual_seed(90), device=DEV)
+        tpe, offs = table_of(groups)
+        small, g2, (tpe2, offs2) = compact_of(gy, groups)
+        want = L.moe_backward_input_nvfp4(blocks, scales, gs, small, tpe2, offs2)
+        assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+        ob = BigGuarded("grad_in", T * K * 4, torch.float32, SENT)
+        out = ob.view(T, K)
+        step = 1 << 20
+        for a in range(0, T, step):
+            out[a:a + step] = SENT
+        assert output_wrap_is_visible(groups, K * 4, ob) >= 0
+        assert lib.fql_tune_nvfp4_kernel(E, T, K, N) == 0
+        rc = lib.fql_moe_nvfp4_bwd_input(blocks.data_ptr(), scales.data_ptr(), gs.data_ptr(), gy.data_ptr(), DT[torch.float32],
+                                         tpe.data_ptr(), offs.data_ptr(), ob.ptr, DT[torch.float32], E, T, K, N,
+                                         torch.cuda.current_stream().cuda_stream)
+        assert rc == OK
+        torch.cuda.synchronize()
+        nz = 0
+        for (lo, hi), (a, b) in zip(groups, g2):
+            assert same_bits(out[lo:hi].contiguous(), want[a:b].contiguous()), (case, lo)
+            nz += int(torch.count_nonzero(out[lo:hi]))
+        assert int(torch.count_nonzero(out)) == nz, "nvfp4 bwd-dx: a row no expert covers is not zero"
+        assert_guards_intact(ob, what="dX out of the NVFP4 backward")
+        del out, ob
+        return
+
+    width = 2 * 160 if case == "gated" else ROWS_K
+    xb, x, groups, g = big_rows(86 + ["plain", "gated", "bwd-dy"].index(case), width)
+    T = x.shape[0]
+    tpe, offs = table_of(groups)
+    small, g2, (tpe2, offs2) = compact_of(x, groups)
+    if case == "bwd-dy":
+        K, N = 32, width
+        blocks, scales, gs = weights(N, K)
+        run = lambda rows, t, o: L.moe_backward_input_nvfp4(blocks, scales, gs, rows, t, o)
+    elif case == "gated":
+        K, N = width // 2, 40
+        blocks, scales, gs = weights(N, K)
+        run = lambda rows, t, o: L.moe_gated_forward_nvfp4(blocks, scales, gs, rows, t, o, activation="swiglu_clamp",
+                                                           out_dtype=torch.float32)
+    else:
+        K, N = width, 40
+        blocks, scales, gs = weights(N, K)
+        run = lambda rows, t, o: L.moe_forward_nvfp4(blocks, scales, gs, rows, t, o, out_dtype=torch.float32)
+    assert lib.fql_tune_nvfp4_kernel(E, T, K, N) == 0
+    got, want = run(x, tpe, offs), run(small, tpe2, offs2)
+    assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+    nz = 0
+    for (lo, hi), (a, b) in zip(groups, g2):
+        assert same_bits(got[lo:hi].contiguous(), want[a:b].contiguous()), (case, lo)
+        nz += int(torch.count_nonzero(got[lo:hi]))
+    assert int(torch.count_nonzero(got)) == nz, f"nvfp4 {case}: a row no expert covers is not zero"
+    assert_guards_intact(xb, what=f"rows into the NVFP4 {case} entry")
+    del got, x, xb

@@ -3,8 +3,11 @@
 experts under grad mode.
 
 N is the contraction here.  N in {8, 40, 136, 201}: half of a 16-n step, a partial first stage, two stages plus an 8-n tail,
-an odd N on the element-load path.  K in {32, 96, 288}: one 32-k piece (two scale blocks), a partial 128-k tile, a third k
-tile of one piece.  The table is test_gpu_nvfp4.py's ([0, 1, 33, 70] rows plus 2 uncovered), and E = 1 with one row and no
+an odd N on the element-load path; N in {64, 128}: exactly one and exactly two 64-n stages, the two sizes at which
+``n0 + BN < N`` and ``n0 + 2 * BN < N`` of nv4_bwd_kernel change value with no partial stage behind them (at 64 the second
+Stage is never read and nothing is stored behind the one contraction).  K in {32, 96, 288}: one 32-k piece (two scale blocks),
+a partial 128-k tile, a third k tile of one piece; K in {128, 384}: one and three WHOLE 128-k output tiles (no piece of the
+last tile is absent).  The table is test_gpu_nvfp4.py's ([0, 1, 33, 70] rows plus 2 uncovered), and E = 1 with one row and no
 table.  The weights, scale bytes and global scales come from test_gpu_nvfp4.problem (the scale bytes are drawn per
 16-block: the two halves of a staging thread's 32-k piece differ).
 
@@ -13,9 +16,9 @@ then the one float32 step * global_scale[e].
 
 MEASURED (MI355X; printed by the tests with -s) and the bounds:
   * float32 dX on Gaussian dY, scale bytes over the whole finite range and both signs, against that reference, relative
-    Frobenius error: 1.4e-8 .. 9.9e-8 over the twelve shapes and both dY types (SAME_INPUT_MEASURED_BWD: 9.912e-8 at K = 288,
-    N = 201, float32 dY); the bound asserted is the forward's own SAME_INPUT_BOUND = 3.92e-7, imported (the same
-    instruction, the same accumulation, a contraction no longer than its 288).
+    Frobenius error: 1.4e-8 .. 9.9e-8 over the thirty shapes and both dY types (SAME_INPUT_MEASURED_BWD: 9.912e-8 at K = 288,
+    N = 201, float32 dY; K in {128, 384} and N in {64, 128} measure 2.8e-8 .. 9.8e-8); the bound asserted is the forward's
+    own SAME_INPUT_BOUND = 3.92e-7, imported (the same instruction, the same accumulation, a contraction no longer than its 288).
   * a bfloat16 dX adds its one rounding, 2^-9 (a bound on every finite normal element, hence on the norm): measured
     1.59e-3 .. 1.68e-3; a float16 dX 2^-11, taken on scale bytes 0x30 .. 0x47 (the whole range leaves float16's): measured
     2.05e-4 (K = 96, N = 40) and 2.08e-4 (K = 288, N = 201).
@@ -43,11 +46,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 COUNTS, TAIL = [0, 1, 33, 70], 2
-KS, NS = [32, 96, 288], [8, 40, 136, 201]
+KS, NS = [32, 96, 128, 288, 384], [8, 40, 64, 128, 136, 201]
 F16_OUT = 2.0 ** -11
 
 # relative Frobenius error of the float32 dX against the reference above: the largest value the tests printed on an MI355X
-SAME_INPUT_MEASURED_BWD = 9.912e-8  # (K = 288, N = 201, float32 dY; 1.4e-8 .. 9.9e-8 over the twelve shapes)
+SAME_INPUT_MEASURED_BWD = 9.912e-8  # (K = 288, N = 201, float32 dY; 1.4e-8 .. 9.9e-8 over the thirty shapes)
 assert SAME_INPUT_MEASURED_BWD <= SAME_INPUT_BOUND
 # relative Frobenius error of x.grad / the bias gradients (layer) and of x.grad / gate.weight.grad / gate.bias.grad (block)
 # against the float64 reference, the largest value printed on an MI355X per activation type
@@ -169,7 +172,7 @@ def test_float16_output(K, N):
 
 # ---- 3. independence, bit for bit
 
-@pytest.mark.parametrize("K,N", [(288, 136), (96, 201)])
+@pytest.mark.parametrize("K,N", [(288, 136), (96, 201), (128, 64), (384, 128)])
 def test_grouped_equals_one_expert_calls_permutation_and_rerun(K, N):
     p = problem(K, N)
     got = run(p)
@@ -266,8 +269,7 @@ def test_empty_contraction_is_zeros_and_float16_is_refused():
 
 @pytest.mark.parametrize("dout", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
 @pytest.mark.parametrize("din", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("N", [40, 201])
-@pytest.mark.parametrize("K", [96, 288])
+@pytest.mark.parametrize("K,N", [(96, 40), (96, 201), (288, 40), (288, 201), (128, 64)])
 def test_entry_stays_inside_its_buffers(K, N, din, dout):
     """Every pointer is the interior of a guarded buffer; grad_in sits 4 bytes off a 16-byte boundary inside SENT and
     grad_out 4 bytes off one inside NaN; the scale bytes start at an odd address and end exactly at their last byte in

@@ -13,22 +13,24 @@ either, and checks both: what two overlapping launches must not share (a workspa
 
 The dense ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4 have no table and therefore no family: their split form
 (a decode launch into a partial-sum workspace, a reduce launch, and the gated pre-pass in front of both) has a test of its
-own at the end, on one side stream and on two at once."""
+own at the end, on one side stream and on two at once; so do the dense ops.linear_forward_nvfp4 /
+linear_gated_forward_nvfp4 (the grouped launchers with one expert; the gated entry's pre-pass in front of the GEMM)."""
 import pytest
 import torch
 
 from helpers import first_diff, same_bits
-from test_gpu_graph_replay import (DEV, FAMILIES, LINEAR_CASES, build_block, gen, linear_case, scenes,  # noqa: F401
-                                   tune)                           # (tune: the fixture)
+from test_gpu_graph_replay import (DEV, FAMILIES, LINEAR_CASES, build_block, gen, linear_case, nv4_linear_case,  # noqa: F401
+                                   scenes, tune)                   # (tune: the fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = ["int4-small-T232-bf16", "int4-stream-T1600-f32", "int4-small-T100-fast", "int4-small-T100-fp8", "int4-gated-T100",
          "int4-gather-T232", "int4-two-phase-T100", "int4-bwd-tiled-vec", "group-i8", "group-float-glu", "group-bwd-rows-g48",
          "mx4-K288-N136-tile", "mx4-K288-N136-decode", "mx4-K96-N37-fp8", "mx4-K96-N37-fp4", "mx4-K288-N136-glu-decode",
          "mx4-K288-N136-bwd", "mx4-K288-N136-fp6-tile", "mx4-K96-N37-fp6-glu-decode", "mx4-K288-N136-fp8-decode",
-         "mx4-K96-N37-fp4-decode", "mx4-lora-fwd-K288-N136-r16", "mx4-lora-glu-K96-N37-r64", "mx4-lora-bwd-K288-N136-r16"]
+         "mx4-K96-N37-fp4-decode", "mx4-lora-fwd-K288-N136-r16", "mx4-lora-glu-K96-N37-r64", "mx4-lora-bwd-K288-N136-r16",
+         "nv4-K288-N136-tile", "nv4-K96-N37-decode", "nv4-K608-N37-decode", "nv4-K288-N136-glu-decode", "nv4-K96-N37-bwd"]
 TWO_STREAMS = ["int4-small-T100-fast", "int4-two-phase-T100", "group-i8-glu", "mx4-K288-N136-glu-tile", "mx4-K96-N37-fp4",
-               "mx4-lora-glu-K288-N136-r16", "mx4-K288-N136-fp6-decode"]
+               "mx4-lora-glu-K288-N136-r16", "mx4-K288-N136-fp6-decode", "nv4-K288-N136-glu-tile", "nv4-K96-N37-bwd"]
 
 
 def poisoned_like(t):
@@ -126,6 +128,19 @@ def test_dense_linear_split_form_on_side_streams(tune, name):
     stream is still busy with the matmuls: it sums a workspace nobody has written, or the decode kernel reads an h that
     is not there yet."""
     call, make_rows, _, _ = linear_case(name, tune)
+    dense_on_side_streams(call, make_rows)
+
+
+@pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])
+def test_dense_nvfp4_linear_on_side_streams(gated):
+    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 (test_gpu_graph_replay.nv4_linear_case: K = 96, N = 37, T = 5)
+    as the MXFP4 dense ops above: one side stream with poisoned input buffers, then two at once with different rows (the
+    gated entry: a workspace per stream)."""
+    call, make_rows, _, _ = nv4_linear_case(gated)
+    dense_on_side_streams(call, make_rows)
+
+
+def dense_on_side_streams(call, make_rows):
     a, b = make_rows(1), make_rows(2)
     want_a, want_b = call(a.clone()), call(b.clone())
     assert float(want_a.abs().max()) > 0 and not same_bits(want_a, want_b)
