@@ -11,8 +11,8 @@ from .module import QuantizedLinear
 from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN, QuantizedSparseMoEBlock, \
     MXFP4MoEFFN, NVFP4MoEFFN
 from .mxfp4_linear import MXFP4Linear
-from .nvfp4_linear import NVFP4Linear
-from .lora import LoRAQuantizedLinear, LoRAMoEINT4, LoRAQuantizedMoEFFN, LoRAMXFP4MoEFFN
+from .nvfp4_linear import NVFP4Linear, LoRANVFP4Linear
+from .lora import LoRAQuantizedLinear, LoRAMoEINT4, LoRAQuantizedMoEFFN, LoRAMXFP4MoEFFN, LoRANVFP4MoEFFN
 from .routing import (RoutingResult, simulate_routing, balanced_routing, create_expert_inputs,
                       combine_expert_outputs, dispatch_grouped, dispatch_indices, combine_grouped)
 
@@ -23,5 +23,5 @@ __all__ = [
     "combine_expert_outputs", "dispatch_grouped", "dispatch_indices", "combine_grouped",
     "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN", "LoRAMXFP4MoEFFN", "QuantizedSparseMoEBlock",
     "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN", "quantize_mxfp6", "dequantize_mxfp6", "MXFP4Linear",
-    "quantize_nvfp4", "dequantize_nvfp4", "nvfp4_scale_values", "NVFP4MoEFFN", "NVFP4Linear",
+    "quantize_nvfp4", "dequantize_nvfp4", "nvfp4_scale_values", "NVFP4MoEFFN", "NVFP4Linear", "LoRANVFP4MoEFFN", "LoRANVFP4Linear",
 ]

@@ -211,6 +211,19 @@ _SYMBOLS = {
                                  + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "fql_moe_nvfp4_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3
                                 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "fql_moe_nvfp4_lora_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int]
+                               + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5
+                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_nvfp4_glu_lora_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int]
+                                   + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 6 + [ctypes.c_float] * 2
+                                   + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_nvfp4_lora_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int]
+                                     + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "fql_linear_nvfp4_lora_fwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int]
+                                  + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4
+                                  + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_linear_nvfp4_lora_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int]
+                                        + [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "fql_tune_set_nvfp4_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_nvfp4_kernel": (ctypes.c_int, [ctypes.c_int] * 4),
     "fql_combine_sparse_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]

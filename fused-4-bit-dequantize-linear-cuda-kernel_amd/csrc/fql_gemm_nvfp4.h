@@ -26,6 +26,18 @@
 // EPILOGUE (nv4_epilogue, both kernels).  global_scale[e] is read once per workgroup; a result is multiplied by it, then
 // the bias is added, two float32 roundings, never an FMA.  Without a global scale and a bias the result is acc's bits.
 // NON-FINITE: as mx4_kernel (the row flag); global_scale is not screened.
+//
+// LORA (nv4_kernel<IN, OUT, Mx4Lora>; fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_linear_nvfp4_lora_fwd, DESIGN.md
+// section 41): mx4_kernel's adapter stage, one more contraction stage behind the last weight stage's barrier,
+//   out[t][n] = round_OUT( fl32( S + bias[e][n] ) ),   S = fl32(acc * global_scale[e]) (+) sum_{j < r} bf16(v[t][j]) bf16(B[e][n][j])
+// with (+) the matrix instruction accumulating onto its C operand in ascending j, 16 a step.  THE GLOBAL SCALE belongs to
+// the weights alone, so it cannot stay in the epilogue, where the accumulator also holds the adapter term: the LORA form
+// multiplies the 32 accumulator registers by it behind the last weight stage (one __fmul_rn each, contraction off, only
+// with a global scale), the steps accumulate onto the scaled value and nv4_epilogue is called without the multiply.  With
+// B = 0 the steps add +0, so the result is the base kernel's (but for the sign of a zero under a negative scale).
+// The stage writes pair 0 of the images in full (zeros past N and from r on), so nothing stale of a weight stage, a NaN
+// block under byte 0x7F included, meets a zero; v feeds the row flag, B is not screened.  nv4_kernel<IN, OUT> is the code
+// it was; the decode kernel has no adapter form.
 #pragma once
 #include "fql_gemm_mx4_decode.h"
 
@@ -82,14 +94,17 @@ __device__ __forceinline__ void nv4_epilogue(const v16f &acc, void *__restrict__
 }
 
 // IN: element type of x (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of out, rounded once in the epilogue.
-// (54 KiB of LDS, as mx4_kernel: two workgroups a compute unit.)
-template <int IN, int OUT>
+// LA: nothing (nv4_kernel<IN, OUT>: the signature, the code and the bits it always had), or Mx4Lora: the compile-time LORA
+// flag, set by the argument that carries what it needs.  (54 KiB of LDS, as mx4_kernel: two workgroups a compute unit.)
+template <int IN, int OUT, class... LA>
 __global__ __launch_bounds__(256) void nv4_kernel(
     const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ scales, const float *__restrict__ gscale,
     const void *__restrict__ x, const float *__restrict__ bias, void *__restrict__ out, const int32_t *__restrict__ tpe,
-    const int32_t *__restrict__ offs, int E, int T, int K, int N)
+    const int32_t *__restrict__ offs, int E, int T, int K, int N, LA... lora)
 {
+    static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool LORA = sizeof...(LA) == 1;
     using C = Mx4Cfg;
     int row_lo, cnt, t_blk;
     if (!mx4_group_begin<C::THREADS, OUT>(out, N, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
@@ -224,15 +239,65 @@ __global__ __launch_bounds__(256) void nv4_kernel(
         if (k0 + C::BK < K) run_stage(s1, s0, k0 + C::BK, it + 1);
     }
 
+    if constexpr (LORA) {
+        // global_scale belongs to the weights alone: the finished weight sum is multiplied here, one rounding a register
+        // and never an FMA, the adapter steps accumulate onto the scaled value and the epilogue multiplies no more.
+        if (has_gs) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[b][q] = __fmul_rn(acc[b][q], gs);
+        }
+        // The adapter stage (mx4_kernel's).  Every thread is behind the last stage's barrier, which no store followed:
+        // both pairs of images are free.  Pair 0 is written in full (zeros past N and from `rank` on), so nothing of a
+        // weight stage, a NaN block included, meets a zero; then one barrier, then the steps.
+        const Mx4Lora la{lora...};
+        const int rank = la.rank;
+        const float *vrow = la.rows + (size_t)tx * rank;
+        const float *brow = la.w + wrow * rank;
+        const bool vec_v = (reinterpret_cast<uintptr_t>(la.rows) & 15) == 0, vec_b = (reinterpret_cast<uintptr_t>(la.w) & 15) == 0;
+        uint32_t xw[8], bad = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // v[tx][16 xq + 4 i .. + 3]
+            const int j = 16 * xq + 4 * i;
+            mx4_lora_pack4(vrow + j, vec_v, j < rank, xw[2 * i], xw[2 * i + 1]);
+            bad |= mx4_nonfinite2(xw[2 * i]) | mx4_nonfinite2(xw[2 * i + 1]);
+        }
+        *reinterpret_cast<uint4 *>(&ximage[0][xs][16 * xq]) = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+        *reinterpret_cast<uint4 *>(&ximage[0][xs][16 * xq + 8]) = make_uint4(xw[4], xw[5], xw[6], xw[7]);
+        if (bad & 0x80008000u) row_bad[xs] = 1;                    // (read behind the barrier below)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // B[e][n0 + sn][32 sp + 8 i .. + 7]
+            const int j = 32 * sp + 8 * i;
+            uint4 w;
+            mx4_lora_pack4(brow + j, vec_b, n_ok && j < rank, w.x, w.y);
+            mx4_lora_pack4(brow + j + 4, vec_b, n_ok && j + 4 < rank, w.z, w.w);
+            *reinterpret_cast<uint4 *>(&image[0][sn][j]) = w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (16 * s >= rank) break;                             // (uniform)
+            const uint4 xb = *reinterpret_cast<const uint4 *>(&ximage[0][tr][16 * s + 8 * h]);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const uint4 a = *reinterpret_cast<const uint4 *>(&image[0][32 * (nb + b) + r][16 * s + 8 * h]);
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, xb),
+                                                                 acc[b], 0, 0, 0);
+            }
+        }
+    }
+
     // D[i][j]: i = n (A), j = t (B): the lane owns row t, registers 4q .. 4q+3 are n = 8 q + 4 h + (0 .. 3) of the block.
-    // (Every write of row_bad lies behind a barrier of the loop.)
+    // (Every write of row_bad lies behind a barrier of the loop or of the adapter stage.)
     const bool row_nan = row_bad[tr] != 0;
     if (!row_ok) return;
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
     const float *brow = bias == nullptr ? nullptr : bias + (size_t)e * N;
 #pragma unroll
     for (int b = 0; b < 2; ++b)
-        nv4_epilogue<OUT>(acc[b], out, t, N, n0 + 32 * (nb + b), h, vec, brow, has_gs, gs, row_nan);
+        nv4_epilogue<OUT>(acc[b], out, t, N, n0 + 32 * (nb + b), h, vec, brow, !LORA && has_gs, gs, row_nan);
 #endif
 }
 

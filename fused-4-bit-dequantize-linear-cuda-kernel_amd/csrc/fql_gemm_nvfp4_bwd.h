@@ -23,18 +23,28 @@
 //   * NON-FINITE.  The row flag as mx4_bwd_kernel's.  A NaN scale byte (0x7F, 0xFF) makes its 16 weights NaN (nv4_scale),
 //     hence dX NaN for exactly those 16 k on the rows of that expert; a negative byte negates its block.  global_scale is
 //     not screened.
+//   * LORA (nv4_bwd_kernel<IN, OUT, Mx4Lora>; fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_bwd_input, DESIGN.md section
+//     41): mx4_bwd_kernel's adapter stage behind the last weight stage,
+//       dX[t][k] = round_OUT( S' ),   S' = fl32(acc * global_scale[e]) (+) sum_{j < r} bf16(dv[t][j]) bf16(A[e][j][k]).
+//     The global scale scales the weight term only: the LORA form multiplies the accumulator registers by it behind the last
+//     weight stage (one __fmul_rn each, never an FMA) and the epilogue multiplies no more.  The stage writes pair 0 of the
+//     images in full, through the same mx4_bwd_off and store rotation; a uniform trip count, no per-lane exit, EXEC all
+//     ones at every transposed read.  nv4_bwd_kernel<IN, OUT> is the code it was.
 #pragma once
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_nvfp4.h"
 
 // IN: element type of dY (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of dX, rounded once in the epilogue.
-template <int IN, int OUT>
+// LA: nothing (nv4_bwd_kernel<IN, OUT>: the signature, the code and the bits it always had), or Mx4Lora: the LORA flag.
+template <int IN, int OUT, class... LA>
 __global__ __launch_bounds__(256) void nv4_bwd_kernel(
     const uint8_t *__restrict__ blocks, const uint8_t *__restrict__ scales, const float *__restrict__ gscale,
     const void *__restrict__ dy, void *__restrict__ dx, const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs,
-    int E, int T, int K, int N)
+    int E, int T, int K, int N, LA... lora)
 {
+    static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool LORA = sizeof...(LA) == 1;
     using C = Mx4BwdCfg;
     int row_lo, cnt, t_blk;
     if (!mx4_group_begin<C::THREADS, OUT>(dx, K, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
@@ -199,6 +209,62 @@ __global__ __launch_bounds__(256) void nv4_bwd_kernel(
         if (n0 + C::BN < N) run_stage(s1, s0, n0 + C::BN, it + 1);
     }
 
+    if constexpr (LORA) {
+        // global_scale belongs to the weights alone: the finished weight sum is multiplied here, one rounding a register
+        // and never an FMA, the adapter steps accumulate onto the scaled value and the epilogue multiplies no more.
+        if (has_gs) {
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[b][q] = __fmul_rn(acc[b][q], gs);
+        }
+        // The adapter stage (mx4_bwd_kernel's).  Every thread is behind the last stage's barrier, which no store followed:
+        // pair 0 of the images is free.  It is written in full, zeros from row `rank` on, past K and from column `rank` of
+        // dv on, so nothing of a weight stage, a NaN block included, meets a zero; then one barrier, then the steps.  Every
+        // condition around a transposed read is uniform.
+        const Mx4Lora la{lora...};
+        const int rank = la.rank;
+        const float *vrow = la.rows + (size_t)ty * rank;
+        const bool a_ok = k_ok && sn < rank;
+        const float *arow = la.w + ((size_t)e * rank + (a_ok ? sn : 0)) * K + (a_ok ? kp : 0);
+        const bool vec_v = (reinterpret_cast<uintptr_t>(la.rows) & 15) == 0, vec_a = (reinterpret_cast<uintptr_t>(la.w) & 15) == 0;
+        uint32_t yw[8], bad = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // dv[ty][16 yq + 4 i .. + 3]
+            const int j = 16 * yq + 4 * i;
+            mx4_lora_pack4(vrow + j, vec_v, j < rank, yw[2 * i], yw[2 * i + 1]);
+            bad |= mx4_nonfinite2(yw[2 * i]) | mx4_nonfinite2(yw[2 * i + 1]);
+        }
+        *reinterpret_cast<uint4 *>(&yimage[0][ys][16 * yq]) = make_uint4(yw[0], yw[1], yw[2], yw[3]);
+        *reinterpret_cast<uint4 *>(&yimage[0][ys][16 * yq + 8]) = make_uint4(yw[4], yw[5], yw[6], yw[7]);
+        if (bad & 0x80008000u) row_bad[ys] = 1;                    // (read behind the barrier below)
+        uint4 ch[4];                                               // chunk 4 sp + i of image row sn: A[e][sn][kp + 8 i .. + 7]
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            mx4_lora_pack4(arow + 8 * i, vec_a, a_ok, ch[i].x, ch[i].y);
+            mx4_lora_pack4(arow + 8 * i + 4, vec_a, a_ok, ch[i].z, ch[i].w);
+        }
+        if (wrot & 1) { const uint4 a = ch[0], b = ch[2]; ch[0] = ch[1]; ch[1] = a; ch[2] = ch[3]; ch[3] = b; }
+        if (wrot & 2) { const uint4 a = ch[0], b = ch[1]; ch[0] = ch[2]; ch[2] = a; ch[1] = ch[3]; ch[3] = b; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)                                // (ch[j] is chunk j ^ wrot now: store_stage's rotation)
+            *reinterpret_cast<uint4 *>(&image[0][w_off[j]]) = ch[j];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (16 * s >= rank) break;                             // (uniform)
+            const uint4 yb = *reinterpret_cast<const uint4 *>(&yimage[0][tr][16 * s + 8 * h]);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const mx4_v4s lo = mx4_tr_read(image[0] + a_off[b][0] + 4096 * s);
+                const mx4_v4s hi = mx4_tr_read(image[0] + a_off[b][1] + 4096 * s);
+                const v8bf a = __builtin_bit_cast(v8bf, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(v8bf, yb), acc[b], 0, 0, 0);
+            }
+        }
+    }
+
     // D[i][j]: i = k (A), j = t (B): the lane owns row t, registers 4q .. 4q+3 are k = 8 q + 4 h + (0 .. 3) of the block.
     // (Every write of row_bad lies behind a barrier.)
     const bool row_nan = row_bad[tr] != 0;
@@ -214,7 +280,7 @@ __global__ __launch_bounds__(256) void nv4_bwd_kernel(
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 v[c] = acc[b][4 * q + c];
-                if (has_gs) v[c] = __fmul_rn(v[c], gs);
+                if (!LORA && has_gs) v[c] = __fmul_rn(v[c], gs);
                 if (row_nan) v[c] = __uint_as_float(0x7FC00000u);
             }
             store_out4(dx, OUT, (size_t)t * K, kc, K, vec, v);

@@ -5,7 +5,8 @@
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
 // fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
 // linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
-// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h)
+// with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -136,6 +137,14 @@ int launch_nvfp4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
 {
     using C = Mx4Cfg;
     using D = Mx4DecodeCfg;
+    if (c.lora)                                                       // (always the tile kernel, as launch_mx4's adapter call)
+        return with_in_dtype(in_dtype, [&](auto in) {
+            return with_out_dtype(out_dtype, [&](auto o) {
+                return launch(nv4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, c.N, C::BN, C::BT), dim3(C::THREADS), 0, st,
+                              c.blocks, c.scales, c.gscale, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N,
+                              Mx4Lora{c.lora_rows, c.lora_w, c.rank});
+            });
+        });
     const bool decode = nvfp4_use_decode(c.T);
     const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
     return with_in_dtype(in_dtype, [&](auto in) {
@@ -708,6 +717,69 @@ FQL_API int fql_moe_nvfp4_bwd_input(const uint8_t *blocks, const uint8_t *scales
                           c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
         });
     });
+}
+
+FQL_API int fql_moe_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                   int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E,
+                                   int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
+{
+    (void)workspace; (void)workspace_bytes;
+    const Mx4Call c = with_lora(with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                           global_scale), lora_rows, lora_B, rank);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_nvfp4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_moe_nvfp4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                       const void *gate_up, int in_dtype, const float *lora_rows, const float *lora_B, int rank,
+                                       const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                       void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                       float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mx4_quant_fwd<ROWS_FLOAT>(with_lora(with_nvfp4({blocks, scales_e4m3, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                                          global_scale), lora_rows, lora_B, rank), in_dtype, out_dtype,
+                                     {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                         const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A, int rank,
+                                         const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
+                                         int out_dtype, int E, int T, int K, int N, void *stream)
+{
+    using C = Mx4BwdCfg;
+    const Mx4Call c = with_lora(with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N},
+                                           global_scale), lora_rows, lora_A, rank);
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK) return rc;
+    if (empty) return T == 0 ? FQL_OK : FQL_ERR_BAD_SHAPE;            // (N == 0 with rows: dv A alone is not this entry's business)
+    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(nv4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0,
+                          static_cast<hipStream_t>(stream), c.blocks, c.scales, c.gscale, c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K,
+                          c.N, Mx4Lora{c.lora_rows, c.lora_w, c.rank});
+        });
+    });
+}
+
+FQL_API int fql_linear_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                      int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                      void *out, int out_dtype, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                                      void *stream)
+{
+    return mx4_linear_fwd(with_lora(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
+                                    lora_rows, lora_B, rank), in_dtype, out_dtype, kMx4Plain, 0, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                            const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A,
+                                            int rank, void *grad_in, int out_dtype, int T, int K, int N, void *stream)
+{
+    return fql_moe_nvfp4_lora_bwd_input(blocks, scales_e4m3, global_scale, grad_out, in_dtype, lora_rows, lora_A, rank, nullptr,
+                                        nullptr, grad_in, out_dtype, 1, T, K, N, stream);
 }
 
 FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows)

@@ -18,7 +18,8 @@ section 9); by default it is the float32 layer.
 
 ``LoRAMXFP4MoEFFN`` is the same pair of adapters on the MXFP4 experts of ``MXFP4MoEFFN``, with the adapter term fused into
 the bfloat16 GEMMs as one more contraction stage (ops.moe_ffn_lora_forward_mxfp4, INTEGRATION.md section 17, DESIGN.md
-section 35).
+section 35).  ``LoRANVFP4MoEFFN`` is that layer on the NVFP4 experts of ``NVFP4MoEFFN`` (ops.moe_ffn_lora_forward_nvfp4,
+INTEGRATION.md section 18); the dense ``LoRANVFP4Linear`` lives in nvfp4_linear.py.
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from .module import QuantizedLinear
-from .moe import MoEINT4, MXFP4MoEFFN, QuantizedMoEFFN
+from .moe import MoEINT4, MXFP4MoEFFN, NVFP4MoEFFN, QuantizedMoEFFN
 from .ops import LORA_RANKS
 
 
@@ -292,6 +293,77 @@ class LoRAMXFP4MoEFFN(MXFP4MoEFFN):
                                               self.down_lora_B, self.scaling, tokens_per_expert, input_offsets,
                                               activation_dtype=self.activation_dtype, activation=self.activation,
                                               activation_alpha=self.activation_alpha,
+                                              activation_limit=self.activation_limit, gate_up_bias=b_gu, down_bias=b_d)
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, rank={self.rank}, alpha={self.alpha:g}"
+
+
+class LoRANVFP4MoEFFN(NVFP4MoEFFN):
+    """``NVFP4MoEFFN`` with a trainable low-rank adapter on each projection: ``gate_up = g_gu (W_gu x) + b_gu + s B_gu (A_gu x)``
+    and ``y = g_d (W_d h) + b_d + s B_d (A_d h)``, ``s = alpha / rank``, ``g`` the per-expert global scales (they scale the
+    weight term only).  The NVFP4 buffers are frozen and keep the checkpoint's encoding; the four float32 adapters
+    (``LoRAQuantizedMoEFFN``'s names, shapes and PEFT initialisation) are the only parameters besides the biases of
+    ``expert_bias=True`` (frozen until ``requires_grad_(True)``).  ``activation_dtype`` None / float32 or bfloat16, every
+    activation kind, as in the base layer; ``input_grad`` is always on.  The layer is differentiable in its input, the
+    adapters and the biases (``ops.moe_ffn_lora_forward_nvfp4``); the adapter term rides in the two GEMMs as one more
+    contraction stage, its operands rounded to bfloat16 as the rows are (the adapters' master copies stay float32).  A
+    fresh layer (``B = 0``) returns ``NVFP4MoEFFN``'s bits.  GPU only."""
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, rank: int, alpha: float | None = None,
+                 activation: str = "silu", activation_alpha: float = 1.702, activation_limit: float = 7.0,
+                 expert_bias: bool = False, activation_dtype=None, input_grad: bool = True):
+        del input_grad                                                                 # (always on: the layer is for training)
+        super().__init__(num_experts, hidden_dim, ffn_dim, activation=activation, activation_alpha=activation_alpha,
+                         activation_limit=activation_limit, expert_bias=expert_bias, activation_dtype=activation_dtype,
+                         input_grad=True)
+        _check_rank(rank)
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scaling = self.alpha / rank
+        E, H, F = num_experts, hidden_dim, ffn_dim
+        self.gate_up_lora_A = nn.Parameter(torch.empty(E, rank, H, dtype=torch.float32))
+        self.gate_up_lora_B = nn.Parameter(torch.empty(E, 2 * F, rank, dtype=torch.float32))
+        self.down_lora_A = nn.Parameter(torch.empty(E, rank, F, dtype=torch.float32))
+        self.down_lora_B = nn.Parameter(torch.empty(E, H, rank, dtype=torch.float32))
+        self.reset_lora_parameters()
+
+    reset_lora_parameters = LoRAQuantizedMoEFFN.reset_lora_parameters
+    _adapters_to = LoRAMXFP4MoEFFN._adapters_to
+    adapter_state_dict = LoRAMXFP4MoEFFN.adapter_state_dict
+
+    @classmethod
+    def from_nvfp4(cls, *args, **kwargs) -> "LoRANVFP4MoEFFN":
+        """``NVFP4MoEFFN.from_nvfp4`` with ``rank=`` (and ``alpha=``) among the keywords (``from_weights`` takes them the
+        same way); the adapters are created on the device of the blocks."""
+        module = super().from_nvfp4(*args, **kwargs)
+        return module._adapters_to(module.gate_up_blocks.device)
+
+    @classmethod
+    def from_layer(cls, layer: NVFP4MoEFFN, rank: int, alpha: float | None = None) -> "LoRANVFP4MoEFFN":
+        """Wrap an existing ``NVFP4MoEFFN``; the new module shares its buffers (no copy) and its biases, the same
+        parameters in the ``requires_grad`` state they have.  The activation kind and type are the wrapped layer's."""
+        module = cls(layer.num_experts, layer.hidden_dim, layer.ffn_dim, rank, alpha, activation=layer.activation,
+                     activation_alpha=layer.activation_alpha, activation_limit=layer.activation_limit,
+                     expert_bias=layer.expert_bias, activation_dtype=layer.activation_dtype)
+        for name, buf in layer.named_buffers():
+            setattr(module, name, buf)
+        if layer.expert_bias:
+            module.gate_up_bias, module.down_bias = layer.gate_up_bias, layer.down_bias
+        return module._adapters_to(layer.gate_up_blocks.device)
+
+    def forward(self, inputs, tokens_per_expert, input_offsets):
+        """inputs ``[T, H]`` float32 (``activation_dtype=torch.bfloat16``: bfloat16) on the GPU, rows grouped by expert ->
+        ``[T, H]`` of the same type."""
+        if not inputs.is_cuda:
+            raise RuntimeError("LoRANVFP4MoEFFN runs on the GPU (the product path has no CPU fallback)")
+        from . import ops
+        b_gu, b_d = self.biases
+        return ops.moe_ffn_lora_forward_nvfp4(self.gate_up_blocks, self.gate_up_scales, self.gate_up_global, self.down_blocks,
+                                              self.down_scales, self.down_global, inputs, self.gate_up_lora_A,
+                                              self.gate_up_lora_B, self.down_lora_A, self.down_lora_B, self.scaling,
+                                              tokens_per_expert, input_offsets, activation_dtype=self.activation_dtype,
+                                              activation=self.activation, activation_alpha=self.activation_alpha,
                                               activation_limit=self.activation_limit, gate_up_bias=b_gu, down_bias=b_d)
 
     def extra_repr(self) -> str:

@@ -1,5 +1,8 @@
 """``NVFP4Linear``: a dense ``nn.Linear`` on NVFP4 weights (the encoding of ModelOpt's ``-FP4`` / ``-NVFP4`` exports), frozen
-(csrc/fql_gemm_nvfp4.h, csrc/fql_gemm_nvfp4_bwd.h; DESIGN.md sections 38 and 39)."""
+(csrc/fql_gemm_nvfp4.h, csrc/fql_gemm_nvfp4_bwd.h; DESIGN.md sections 38 and 39), and ``LoRANVFP4Linear``, the same layer with
+a trainable low-rank adapter fused into its two GEMMs."""
+import math
+
 import torch
 import torch.nn as nn
 
@@ -120,3 +123,67 @@ class NVFP4Linear(nn.Module):
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=nvfp4"
                 + (", input_grad=True" if self.input_grad else ""))
+
+
+class LoRANVFP4Linear(NVFP4Linear):
+    """``NVFP4Linear`` with a trainable low-rank adapter: ``y = (x @ W.T) * global_scale (+ bias) + s * (x @ lora_A.T) @
+    lora_B.T``, ``s = alpha / rank``, any leading dimensions.  The NVFP4 buffers (and the bias) are frozen; ``lora_A`` [r, K]
+    and ``lora_B`` [N, r] float32, ``LoRAQuantizedLinear``'s shapes and PEFT initialisation, are the only parameters, so the
+    state-dict keys are the base layer's plus ``lora_A`` and ``lora_B``.  The adapter term rides in the forward GEMM and in
+    the input gradient as one more contraction stage (``ops.linear_lora_forward_nvfp4``); a fresh layer (``B = 0``) returns
+    ``NVFP4Linear``'s bits.  The adapter path runs on the GPU only."""
+
+    def __init__(self, in_features: int, out_features: int, rank: int, alpha: float | None = None, bias: bool = False,
+                 input_grad: bool = True):
+        del input_grad                                                                 # (always on: the layer is for training)
+        super().__init__(in_features, out_features, bias=bias, input_grad=True)
+        from .ops import LORA_RANKS
+        if rank not in LORA_RANKS:
+            raise ValueError(f"rank must be one of {LORA_RANKS}, got {rank!r}")
+        self.rank = rank
+        self.alpha = float(rank if alpha is None else alpha)
+        self.scaling = self.alpha / rank
+        self.lora_A = nn.Parameter(torch.empty(rank, in_features, dtype=torch.float32))
+        self.lora_B = nn.Parameter(torch.empty(out_features, rank, dtype=torch.float32))
+        self.reset_lora_parameters()
+
+    def reset_lora_parameters(self):
+        """PEFT's initialisation: A kaiming-uniform (a = sqrt(5)), B zeros -- a fresh adapter adds nothing."""
+        nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
+        nn.init.zeros_(self.lora_B)
+
+    def _adapters_to(self, dev):
+        self.lora_A.data, self.lora_B.data = self.lora_A.data.to(dev), self.lora_B.data.to(dev)
+        return self
+
+    @classmethod
+    def from_nvfp4(cls, *args, **kwargs) -> "LoRANVFP4Linear":
+        """``NVFP4Linear.from_nvfp4`` with ``rank=`` (and ``alpha=``) among the keywords (``from_linear`` takes them the
+        same way); the adapters are created on the device of the blocks."""
+        module = super().from_nvfp4(*args, **kwargs)
+        return module._adapters_to(module.blocks.device)
+
+    @classmethod
+    def from_layer(cls, layer: NVFP4Linear, rank: int, alpha: float | None = None) -> "LoRANVFP4Linear":
+        """Wrap an existing ``NVFP4Linear``; the new module shares its buffers (no copy)."""
+        module = cls(layer.in_features, layer.out_features, rank, alpha, bias=layer.bias is not None)
+        for name, buf in layer.named_buffers():
+            setattr(module, name, buf)
+        return module._adapters_to(layer.blocks.device)
+
+    def adapter_state_dict(self):
+        return {k: v for k, v in self.state_dict().items() if k in ("lora_A", "lora_B")}
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("LoRANVFP4Linear runs on the GPU (the adapter path has no CPU fallback)")
+        if x.dim() < 1 or x.shape[-1] != self.in_features:
+            raise RuntimeError(f"LoRANVFP4Linear: the last dimension of the input must be in_features = {self.in_features}, "
+                               f"got {list(x.shape)}")
+        from . import ops
+        y = ops.linear_lora_forward_nvfp4(x.reshape(-1, self.in_features), self.blocks, self.scales, self.global_scale,
+                                          self.lora_A, self.lora_B, self.scaling, bias=self.bias)
+        return y.reshape(*x.shape[:-1], self.out_features)
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, rank={self.rank}, alpha={self.alpha:g}"

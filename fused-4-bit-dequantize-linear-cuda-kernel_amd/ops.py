@@ -707,9 +707,25 @@ def linear_backward_input_mxfp4(blocks, scales, grad_out, out_dtype=None):
     return moe_backward_input_mxfp4(blocks[None], scales[None], grad_out, None, None, out_dtype=out_dtype)
 
 
+def _nvfp4_lora_operands(name, lora, T, w_shape):
+    """The adapter operands of an NVFP4 adapter op, ``lora`` = (the shrunk rows [T, r] float32, the adapter matrix float32
+    of ``w_shape(r)``): types and shapes, as ``_mxfp4_lora_launch`` checks them.  Returns the rank."""
+    v, w = lora
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 2 or v.shape[0] != T:
+        raise RuntimeError(f"ops.{name}: the shrunk rows must be a float32 [T, r] tensor with the rows' T")
+    r = v.shape[1]
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or tuple(w.shape) != w_shape(r):
+        raise RuntimeError(f"ops.{name}: the adapter matrix must be a float32 {list(w_shape(r))} tensor (the adapter "
+                           "weights stay float32 whatever the activations' type)")
+    return r
+
+
 def _nvfp4_launch(name, blocks, scales, global_scale, rows, cols, tokens_per_expert, input_offsets, bias, out_dtype, gated,
-                  act=(), dense=False):
-    """The four NVFP4 ops.  ``rows`` [T, cols(K)] float32 / bfloat16; grouped: ``blocks`` [E, N, K/2], ``scales`` [E, N, K/16],
+                  act=(), dense=False, lora=None):
+    """The four NVFP4 ops and, with ``lora`` = (v [T, r], lora_B [E, N, r] / dense [N, r]), their adapter forms (the ``_lora``
+    entries: always the tile kernel; there is no gated dense one).  ``rows`` [T, cols(K)] float32 / bfloat16; grouped: ``blocks`` [E, N, K/2], ``scales`` [E, N, K/16],
     ``global_scale`` float32 [E] or None, ``bias`` [E, N]; ``dense``: ``blocks`` [N, K/2], ``scales`` [N, K/16],
     ``global_scale`` float32 with one element or None, ``bias`` [N], no table.  Types and shapes first, then the devices:
     the argument errors read the same without a GPU."""
@@ -731,25 +747,35 @@ def _nvfp4_launch(name, blocks, scales, global_scale, rows, cols, tokens_per_exp
         raise RuntimeError(f"global_scale must be a float32 tensor of {E} element(s) (one per expert), or None")
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != ((N,) if dense else (E, N))):
         raise RuntimeError("bias must be a float32 [N] tensor" if dense else "bias must be a float32 [num_experts, N] tensor")
+    T = rows.shape[0]
+    extra, tag = (), ""
+    if lora is not None:
+        if dense and gated:
+            raise RuntimeError(f"ops.{name}: the gated dense NVFP4 op has no adapter form")
+        r = _nvfp4_lora_operands(name, lora, T, lambda r: (N, r) if dense else (E, N, r))
+        tag = "_lora"
     out_dtype = rows.dtype if out_dtype is None else out_dtype
     if out_dtype not in _DTYPES:
         raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
     if not rows.is_cuda:
         raise RuntimeError(f"ops.{name}: the rows must be a CUDA tensor")
-    dev, T = rows.device, rows.shape[0]
+    dev = rows.device
     _on(dev, blocks=blocks, scales_e4m3=scales, global_scale=global_scale, bias=bias)
+    if lora is not None:
+        _on(dev, lora_rows=lora[0], lora_weight=lora[1])
+        extra = (lora[0].contiguous(), lora[1].contiguous(), r)
     out = torch.empty((T, N), dtype=out_dtype, device=dev)
     L = _native.lib()
     gs = None if global_scale is None else global_scale.contiguous()
     b = None if bias is None else bias.contiguous()
     if dense:
-        _launch("fql_linear_nvfp4_glu_fwd" if gated else "fql_linear_nvfp4_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
-                rows.contiguous(), _DTYPES[rows.dtype], b, out, _DTYPES[out_dtype], T, K, N, *act,
+        _launch(f"fql_linear_nvfp4_glu{tag}_fwd" if gated else f"fql_linear_nvfp4{tag}_fwd", dev, blocks.contiguous(),
+                scales.contiguous(), gs, rows.contiguous(), _DTYPES[rows.dtype], *extra, b, out, _DTYPES[out_dtype], T, K, N, *act,
                 ws_bytes=L.fql_linear_nvfp4_workspace_bytes(T, K, N, int(gated)))
         return out
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)   # (none: one expert, all rows)
-    _launch("fql_moe_nvfp4_glu_fwd" if gated else "fql_moe_nvfp4_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
-            rows.contiguous(), _DTYPES[rows.dtype], b, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
+    _launch(f"fql_moe_nvfp4_glu{tag}_fwd" if gated else f"fql_moe_nvfp4{tag}_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
+            rows.contiguous(), _DTYPES[rows.dtype], *extra, b, tpe, offs, out, _DTYPES[out_dtype], E, T, K, N, *act,
             ws_bytes=L.fql_moe_nvfp4_workspace_bytes(E, T, K, N, int(gated)))
     return out
 
@@ -1527,8 +1553,10 @@ def moe_backward_input_mxfp4(blocks, scales, grad_out, tokens_per_expert, input_
     return out
 
 
-def _nvfp4_backward_input(name, blocks, scales, global_scale, grad_out, tokens_per_expert, input_offsets, out_dtype, dense):
-    """Both NVFP4 input gradients, ``_nvfp4_launch``'s order of checks: types and shapes first, then the devices."""
+def _nvfp4_backward_input(name, blocks, scales, global_scale, grad_out, tokens_per_expert, input_offsets, out_dtype, dense,
+                          lora=None):
+    """Both NVFP4 input gradients, ``_nvfp4_launch``'s order of checks: types and shapes first, then the devices.  With
+    ``lora`` = (dv [T, r], lora_A [E, r, K] / dense [r, K]) their adapter forms."""
     if grad_out.dim() != 2 or grad_out.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: grad_out must be a float32 or bfloat16 [T, N] tensor (float16 is refused: rounding "
                            "it to bfloat16 would lose three bits; cast it yourself)")
@@ -1545,18 +1573,32 @@ def _nvfp4_backward_input(name, blocks, scales, global_scale, grad_out, tokens_p
     if global_scale is not None and (not isinstance(global_scale, torch.Tensor) or global_scale.dtype != torch.float32
                                      or global_scale.numel() != E or global_scale.dim() > 1):
         raise RuntimeError(f"global_scale must be a float32 tensor of {E} element(s) (one per expert), or None")
+    T = grad_out.shape[0]
+    if lora is not None:
+        r = _nvfp4_lora_operands(name, lora, T, lambda r: (r, K) if dense else (E, r, K))
     out_dtype = torch.float32 if out_dtype is None else out_dtype
     if out_dtype not in _DTYPES:
         raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
     if not grad_out.is_cuda:
         raise RuntimeError(f"ops.{name}: grad_out must be a CUDA tensor")
-    dev, T = grad_out.device, grad_out.shape[0]
+    dev = grad_out.device
     _on(dev, blocks=blocks, scales_e4m3=scales, global_scale=global_scale)
     tpe, offs = (None, None) if dense else _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)
     out = torch.empty((T, K), dtype=out_dtype, device=dev)
-    _launch("fql_moe_nvfp4_bwd_input", dev, blocks.contiguous(), scales.contiguous(),
-            None if global_scale is None else global_scale.contiguous(), grad_out.contiguous(), _DTYPES[grad_out.dtype], tpe, offs,
-            out, _DTYPES[out_dtype], E, T, K, N)
+    gs = None if global_scale is None else global_scale.contiguous()
+    if lora is None:
+        _launch("fql_moe_nvfp4_bwd_input", dev, blocks.contiguous(), scales.contiguous(), gs, grad_out.contiguous(),
+                _DTYPES[grad_out.dtype], tpe, offs, out, _DTYPES[out_dtype], E, T, K, N)
+        return out
+    _on(dev, lora_rows=lora[0], lora_weight=lora[1])
+    if T == 0:
+        return out
+    if N == 0:
+        raise RuntimeError(f"ops.{name}: blocks with no rows (N == 0) have no adapter form")
+    table, shape = ((), (T, K, N)) if dense else ((tpe, offs), (E, T, K, N))
+    _launch("fql_linear_nvfp4_lora_bwd_input" if dense else "fql_moe_nvfp4_lora_bwd_input", dev, blocks.contiguous(),
+            scales.contiguous(), gs, grad_out.contiguous(), _DTYPES[grad_out.dtype], lora[0].contiguous(), lora[1].contiguous(), r,
+            *table, out, _DTYPES[out_dtype], *shape)
     return out
 
 
@@ -2416,6 +2458,24 @@ def moe_backward_input_mxfp4_lora(blocks, scales, grad_out, dv, lora_A, tokens_p
                               2 * blocks.shape[-1])
 
 
+def _check_ffn_adapters(adapters, E, H, F2):
+    """The four adapters of a gated FP4 FFN block: float32 [E, r, H], [E, 2F, r], [E, r, F], [E, H, r] of one rank."""
+    names = ("gate_up_lora_A", "gate_up_lora_B", "down_lora_A", "down_lora_B")
+    for name, t, shape in zip(names, adapters, ((E, H), (E, F2), (E, F2 // 2), (E, H))):
+        if t.dtype != torch.float32 or t.dim() != 3:
+            raise RuntimeError(f"{name} must be a float32 3-D tensor: the adapter weights and their gradients stay float32 "
+                               "whatever the activations' type")
+        got = (t.shape[0], t.shape[2] if name.endswith("A") else t.shape[1])
+        if got != shape:
+            raise RuntimeError("the adapters must be gate_up_lora_A [E, r, H], gate_up_lora_B [E, 2F, r], down_lora_A "
+                               f"[E, r, F] and down_lora_B [E, H, r]; {name} is {list(t.shape)}")
+    r = adapters[0].shape[1]
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    if adapters[1].shape[2] != r or adapters[2].shape[1] != r or adapters[3].shape[2] != r:
+        raise RuntimeError("the gate_up and down adapters must have the same rank")
+
+
 def moe_ffn_lora_forward_mxfp4(gate_up_blocks, gate_up_scales, down_blocks, down_scales, inputs, gate_up_lora_A,
                                gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert, input_offsets,
                                activation_dtype=None, activation="silu", activation_alpha=1.702, activation_limit=7.0,
@@ -2443,67 +2503,69 @@ def moe_ffn_lora_forward_mxfp4(gate_up_blocks, gate_up_scales, down_blocks, down
     E, F2, H = gate_up_blocks.shape[0], gate_up_blocks.shape[1], inputs.shape[1]
     if F2 % 2 or gate_up_blocks.shape[2] * 2 != H or tuple(down_blocks.shape) != (E, H, F2 // 4):
         raise RuntimeError("gate_up_blocks must be [E, 2F, H/2] and down_blocks [E, H, F/2] for inputs [T, H]")
-    for name, t, shape in (("gate_up_lora_A", gate_up_lora_A, (E, H)), ("gate_up_lora_B", gate_up_lora_B, (E, F2)),
-                           ("down_lora_A", down_lora_A, (E, F2 // 2)), ("down_lora_B", down_lora_B, (E, H))):
-        if t.dtype != torch.float32 or t.dim() != 3:
-            raise RuntimeError(f"{name} must be a float32 3-D tensor: the adapter weights and their gradients stay float32 "
-                               "whatever the activations' type")
-        got = (t.shape[0], t.shape[2] if name.endswith("A") else t.shape[1])
-        if got != shape:
-            raise RuntimeError("the adapters must be gate_up_lora_A [E, r, H], gate_up_lora_B [E, 2F, r], down_lora_A "
-                               f"[E, r, F] and down_lora_B [E, H, r]; {name} is {list(t.shape)}")
-    r = gate_up_lora_A.shape[1]
-    if r not in LORA_RANKS:
-        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
-    if gate_up_lora_B.shape[2] != r or down_lora_A.shape[1] != r or down_lora_B.shape[2] != r:
-        raise RuntimeError("the gate_up and down adapters must have the same rank")
+    _check_ffn_adapters((gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B), E, H, F2)
     if not inputs.is_cuda:
         raise RuntimeError("inputs must be a CUDA tensor (the product path has no CPU fallback)")
-    weights = (gate_up_blocks, gate_up_scales, down_blocks, down_scales)
     adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
     biases = (_check_bias(gate_up_bias, F2, inputs.device, E), _check_bias(down_bias, H, inputs.device, E))
+    return _fp4_ffn_lora(_MXFP4FFNLoRAFn, _MXFP4_LORA_OPS, (gate_up_blocks, gate_up_scales), (down_blocks, down_scales), inputs,
+                         adapters, biases, float(scaling), tokens_per_expert, input_offsets, act)
+
+
+# The three adapter ops of a weight format by name (forward, gated forward, input gradient), looked up in this module when
+# they run.  Each takes its format's weight operands first, then what the MXFP4 ops take.
+_MXFP4_LORA_OPS = ("moe_forward_mxfp4_lora", "moe_gated_forward_mxfp4_lora", "moe_backward_input_mxfp4_lora")
+_NVFP4_LORA_OPS = ("moe_forward_nvfp4_lora", "moe_gated_forward_nvfp4_lora", "moe_backward_input_nvfp4_lora")
+
+
+def _fp4_ffn_lora(node, fmt, w_gu, w_d, inputs, adapters, biases, scaling, tpe, offs, act):
+    """The gated FFN block with its adapters on the weights ``w_gu`` / ``w_d`` (tuples, the format's operands) through the
+    ops ``fmt`` names: the autograd ``node`` when something wants a gradient, the plain launches otherwise."""
     if _wants_grad(inputs, *adapters, *biases):
-        return _MXFP4FFNLoRAFn.apply(inputs, *adapters, *biases, *weights, tokens_per_expert, input_offsets, float(scaling),
-                                     act)
-    return _mxfp4_ffn_lora_apply(weights, inputs, adapters, float(scaling), tokens_per_expert, input_offsets, act, biases)[0]
+        return node.apply(inputs, *adapters, *biases, w_gu, w_d, tpe, offs, scaling, act, fmt)
+    return _fp4_ffn_lora_apply(fmt, w_gu, w_d, inputs, adapters, scaling, tpe, offs, act, biases)[0]
 
 
-def _mxfp4_ffn_lora_apply(weights, inputs, adapters, scaling, tpe, offs, act, biases):
+def _fp4_ffn_lora_apply(fmt, w_gu, w_d, inputs, adapters, scaling, tpe, offs, act, biases):
     """Returns (y, gate_up, v_gu, v_d), y and gate_up in ``inputs``' type.  Four launches and the gated pre-pass: the two
     shrinks (scale included) and the two GEMMs with their adapter stage."""
-    gub, gus, db, ds = weights
+    forward, gated_forward = globals()[fmt[0]], globals()[fmt[1]]
     A_gu, B_gu, A_d, B_d = (a.detach() for a in adapters)
     b_gu, b_d = (None if b is None else b.detach() for b in biases)
     x, dt = inputs.detach(), inputs.dtype
     v_gu = lora_shrink(x, A_gu, "rc", tpe, offs, scale=scaling)
-    gate_up = moe_forward_mxfp4_lora(gub, gus, x, v_gu, B_gu, tpe, offs, bias=b_gu, out_dtype=dt)
+    gate_up = forward(*w_gu, x, v_gu, B_gu, tpe, offs, bias=b_gu, out_dtype=dt)
     v_d = _lora_shrink(gate_up, A_d, "rc", tpe, offs, scaling, gated=True, act=act)
-    y = moe_gated_forward_mxfp4_lora(db, ds, gate_up, v_d, B_d, tpe, offs, activation=act[0], activation_alpha=act[1],
-                                     activation_limit=act[2], bias=b_d, out_dtype=dt)
+    y = gated_forward(*w_d, gate_up, v_d, B_d, tpe, offs, activation=act[0], activation_alpha=act[1],
+                      activation_limit=act[2], bias=b_d, out_dtype=dt)
     return y, gate_up, v_gu, v_d
 
 
-class _MXFP4FFNLoRAFn(torch.autograd.Function):
-    """The gated MXFP4 FFN block + its two adapters in one node, modelled on ``_MoEFFNLoRAFn`` and ``_MXFP4GatedFFNFn``.
+class _FP4FFNLoRAFn(torch.autograd.Function):
+    """The gated FP4 FFN block + its two adapters in one node, modelled on ``_MoEFFNLoRAFn`` and ``_MXFP4GatedFFNFn``.  The
+    node is format-neutral: ``w_gu`` / ``w_d`` are each projection's weight operands as a tuple and ``fmt`` the table of op
+    names (``_MXFP4_LORA_OPS`` or ``_NVFP4_LORA_OPS``); ``_MXFP4FFNLoRAFn`` and ``_NVFP4FFNLoRAFn`` below are this class.
     Saves inputs [T, H] and gate_up [T, 2F] in the layer's type, v_gu and v_d ([T, r] float32, the scale in them), the
     table and the parameters: nothing of shape [T, F].  Every [T, C] tensor of the backward (dh, dgu, dx) is written once,
     in the layer's type, by the kernel that forms it."""
 
     @staticmethod
-    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, b_gu, b_d, gub, gus, db, ds, tpe, offs, scaling, act):
+    def forward(ctx, inputs, A_gu, B_gu, A_d, B_d, b_gu, b_d, w_gu, w_d, tpe, offs, scaling, act, fmt):
         x = inputs.contiguous()
-        y, gate_up, v_gu, v_d = _mxfp4_ffn_lora_apply((gub, gus, db, ds), x, (A_gu, B_gu, A_d, B_d), scaling, tpe, offs, act,
-                                                      (b_gu, b_d))
-        ctx.save_for_backward(x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, gub, gus, db, ds, tpe, offs)
-        ctx.scaling, ctx.act = scaling, act
+        y, gate_up, v_gu, v_d = _fp4_ffn_lora_apply(fmt, w_gu, w_d, x, (A_gu, B_gu, A_d, B_d), scaling, tpe, offs, act,
+                                                    (b_gu, b_d))
+        ctx.save_for_backward(x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, tpe, offs, *w_gu, *w_d)
+        ctx.scaling, ctx.act, ctx.fmt, ctx.operands = scaling, act, fmt, len(w_gu)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, gub, gus, db, ds, tpe, offs = ctx.saved_tensors
+        x, gate_up, v_gu, v_d, A_gu, B_gu, A_d, B_d, tpe, offs, *w = ctx.saved_tensors
+        w_gu, w_d = w[:ctx.operands], w[ctx.operands:]
+        backward_input = globals()[ctx.fmt[2]]
         need_x, need_Agu, need_Bgu, need_Ad, need_Bd, need_bgu, need_bd = ctx.needs_input_grad[:7]
-        E, s, dt = gub.shape[0], ctx.scaling, gate_up.dtype
+        E, s, dt = A_gu.shape[0], ctx.scaling, gate_up.dtype
         check_activation_rows(gy, "the incoming gradient", dt)
         g = gy.contiguous()
         gx = gAgu = gBgu = gAd = gBd = gbgu = gbd = None
@@ -2517,7 +2579,7 @@ class _MXFP4FFNLoRAFn(torch.autograd.Function):
             if need_Ad:
                 gAd = _lora_grad(gate_up, dv_d, "rc", E, tpe, offs, 1.0, gated=True, act=ctx.act)   # dA_d = dv_d^T h
         if through:
-            dh = moe_backward_input_mxfp4_lora(db, ds, g, dv_d, A_d, tpe, offs, out_dtype=dt)       # dh = dY W_d + dv_d A_d
+            dh = backward_input(*w_d, g, dv_d, A_d, tpe, offs, out_dtype=dt)             # dh = dY W_d + dv_d A_d
             dgu = _glu_backward(gate_up, dh, dt, ctx.act)
             del dh
             if need_Bgu:
@@ -2527,7 +2589,167 @@ class _MXFP4FFNLoRAFn(torch.autograd.Function):
             if need_x or need_Agu:
                 dv_gu = lora_shrink(dgu, B_gu, "cr", tpe, offs, scale=s)                 # dv_gu = s dgu B_gu
                 if need_x:
-                    gx = moe_backward_input_mxfp4_lora(gub, gus, dgu, dv_gu, A_gu, tpe, offs, out_dtype=dt)
+                    gx = backward_input(*w_gu, dgu, dv_gu, A_gu, tpe, offs, out_dtype=dt)
                 if need_Agu:
                     gAgu = lora_grad(x, dv_gu, "rc", E, tpe, offs)                       # dA_gu = dv_gu^T x
-        return (gx, gAgu, gBgu, gAd, gBd, gbgu, gbd) + (None,) * 8
+        return (gx, gAgu, gBgu, gAd, gBd, gbgu, gbd) + (None,) * 7
+
+
+_MXFP4FFNLoRAFn = _NVFP4FFNLoRAFn = _FP4FFNLoRAFn     # the node of either format: what differs is ``fmt`` and the weight tuples
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Adapters on the NVFP4 weights (NVFP4MoEFFN, NVFP4Linear), fused into the two NVFP4 tile kernels as the MXFP4 ones are
+# (csrc/fql_gemm_nvfp4.h, csrc/fql_gemm_nvfp4_bwd.h).  global_scale scales the weight term only.
+# ---------------------------------------------------------------------------------------------------------------------
+
+def moe_forward_nvfp4_lora(blocks, scales_e4m3, global_scale, inputs, v, lora_B, tokens_per_expert, input_offsets, bias=None,
+                           out_dtype=None):
+    """``moe_forward_nvfp4`` with a low-rank adapter fused in: for the rows t of expert e,
+    ``out[t] = (W_e @ bf16(inputs[t])) * global_scale[e] + bf16(lora_B[e]) @ bf16(v[t]) (+ bias[e])``, rounded once to
+    ``out_dtype``.  ``v`` [T, r] float32 are the shrunk rows with the scale in them (``lora_shrink(inputs, lora_A,
+    scale=s)``), ``lora_B`` [E, N, r] float32, r in ``LORA_RANKS``.  The adapter is one more contraction stage of the tile
+    kernel (csrc/fql_gemm_nvfp4.h).  ``global_scale`` multiplies the finished weight sum (one float32 rounding) BEFORE the
+    adapter stage accumulates onto it, so it never touches the adapter term.  With ``lora_B`` zero the result equals
+    ``moe_forward_nvfp4``'s for any ``global_scale`` and bias; the only possible difference is the sign of a zero when
+    ``global_scale[e] < 0`` (the stage adds +0 to a -0).  A row's result depends on its own rows of ``inputs`` and ``v``
+    and its expert's weights, ``lora_B`` and scale only.  A non-finite ``v[t]`` makes row t NaN.  Always the tile kernel
+    (no decode form).  Forward only: ``moe_ffn_lora_forward_nvfp4`` is the differentiable form."""
+    _forward_only("moe_forward_nvfp4_lora", inputs, v, lora_B, bias)
+    return _nvfp4_launch("moe_forward_nvfp4_lora", blocks, scales_e4m3, global_scale, inputs, lambda K: K, tokens_per_expert,
+                         input_offsets, bias, out_dtype, False, lora=(v, lora_B))
+
+
+def moe_gated_forward_nvfp4_lora(blocks, scales_e4m3, global_scale, gate_up, v, lora_B, tokens_per_expert, input_offsets,
+                                 activation="silu", activation_alpha=1.702, activation_limit=7.0, bias=None, out_dtype=None):
+    """``moe_gated_forward_nvfp4`` with the adapter stage of ``moe_forward_nvfp4_lora``: the same op on
+    ``h = bf16(act(gate_up[t, :K], gate_up[t, K:]))`` from the same streaming pre-pass; ``v`` [T, r] float32
+    (``lora_gated_shrink(gate_up, lora_A, scale=s, ...)``), ``lora_B`` [E, N, r] float32."""
+    _forward_only("moe_gated_forward_nvfp4_lora", gate_up, v, lora_B, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _nvfp4_launch("moe_gated_forward_nvfp4_lora", blocks, scales_e4m3, global_scale, gate_up, lambda K: 2 * K,
+                         tokens_per_expert, input_offsets, bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit),
+                         lora=(v, lora_B))
+
+
+def moe_backward_input_nvfp4_lora(blocks, scales_e4m3, global_scale, grad_out, dv, lora_A, tokens_per_expert, input_offsets,
+                                  out_dtype=None):
+    """``moe_backward_input_nvfp4`` with the adapter's share fused in: ``grad_in[t] = (bf16(grad_out[t]) @ W_e) *
+    global_scale[e] + bf16(dv[t]) @ bf16(lora_A[e])`` -> [T, K] ``out_dtype`` (default float32), rounded once.  ``dv`` [T, r]
+    float32 (``lora_shrink(grad_out, lora_B, "cr", scale=s)``), ``lora_A`` [E, r, K] float32.  One more contraction stage of
+    the transposed kernel (csrc/fql_gemm_nvfp4_bwd.h); ``global_scale`` multiplies the weight sum in front of it.  With
+    ``lora_A`` zero the result equals ``moe_backward_input_nvfp4``'s (but for the sign of a zero when ``global_scale[e] < 0``),
+    and a non-finite ``dv[t]`` makes row t NaN."""
+    return _nvfp4_backward_input("moe_backward_input_nvfp4_lora", blocks, scales_e4m3, global_scale, grad_out, tokens_per_expert,
+                                 input_offsets, out_dtype, False, lora=(dv, lora_A))
+
+
+def linear_forward_nvfp4_lora(blocks, scales_e4m3, global_scale, x, v, lora_B, bias=None, out_dtype=None):
+    """``linear_forward_nvfp4`` with the adapter stage: ``out[t] = (W @ bf16(x[t])) * global_scale + bf16(lora_B) @ bf16(v[t])
+    (+ bias)``; ``v`` [T, r] float32, ``lora_B`` [N, r] float32.  Exactly ``moe_forward_nvfp4_lora`` on the one-expert view
+    without a table.  Forward only: ``linear_lora_forward_nvfp4`` is the differentiable form."""
+    _forward_only("linear_forward_nvfp4_lora", x, v, lora_B, bias)
+    return _nvfp4_launch("linear_forward_nvfp4_lora", blocks, scales_e4m3, global_scale, x, lambda K: K, None, None, bias,
+                         out_dtype, False, dense=True, lora=(v, lora_B))
+
+
+def linear_backward_input_nvfp4_lora(blocks, scales_e4m3, global_scale, grad_out, dv, lora_A, out_dtype=None):
+    """``linear_backward_input_nvfp4`` with the adapter's share: ``grad_in[t] = (bf16(grad_out[t]) @ W) * global_scale +
+    bf16(dv[t]) @ bf16(lora_A)``; ``dv`` [T, r] float32, ``lora_A`` [r, K] float32.  ``moe_backward_input_nvfp4_lora`` on the
+    one-expert view without a table."""
+    return _nvfp4_backward_input("linear_backward_input_nvfp4_lora", blocks, scales_e4m3, global_scale, grad_out, None, None,
+                                 out_dtype, True, lora=(dv, lora_A))
+
+
+def moe_ffn_lora_forward_nvfp4(gate_up_blocks, gate_up_scales, gate_up_global, down_blocks, down_scales, down_global, inputs,
+                               gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B, scaling, tokens_per_expert,
+                               input_offsets, activation_dtype=None, activation="silu", activation_alpha=1.702,
+                               activation_limit=7.0, gate_up_bias=None, down_bias=None):
+    """``moe_ffn_lora_forward_mxfp4`` on NVFP4 weights: ``gu = g_gu (W_gu x) + b_gu + B_gu v_gu`` with ``v_gu = s A_gu x``,
+    ``h = act(gu)`` (never stored), ``y = g_d (W_d h) + b_d + B_d v_d`` with ``v_d = s A_d h``; blocks / scales / global
+    scales as ``NVFP4MoEFFN`` holds them (``gate_up_global`` / ``down_global`` float32 [E] or None), the adapters and
+    everything else as there.  Differentiable (once) in ``inputs``, the four adapters and the two biases; the weights are
+    frozen and the gradient is straight-through across the bfloat16 roundings.  No float32 [T, C] temporary exists with
+    bfloat16 activations, and nothing of shape [T, F] is saved."""
+    act = activation_of(activation, activation_alpha, activation_limit)
+    if activation_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError("activation_dtype must be None, torch.float32 or torch.bfloat16 (float16 rows are refused: "
+                         "rounding them to bfloat16 would lose three bits)")
+    dt = torch.float32 if activation_dtype is None else activation_dtype
+    if inputs.dim() != 2 or inputs.dtype != dt:
+        raise RuntimeError(f"inputs must be a 2-D {dt} tensor (activation_dtype), got {inputs.dtype}")
+    for name, t in (("gate_up_blocks", gate_up_blocks), ("gate_up_scales", gate_up_scales), ("down_blocks", down_blocks),
+                    ("down_scales", down_scales)):
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise RuntimeError(f"{name} must be a uint8 3-D tensor (NVFP4MoEFFN's buffers)")
+    E, F2, H = gate_up_blocks.shape[0], gate_up_blocks.shape[1], inputs.shape[1]
+    if F2 % 2 or gate_up_blocks.shape[2] * 2 != H or tuple(down_blocks.shape) != (E, H, F2 // 4):
+        raise RuntimeError("gate_up_blocks must be [E, 2F, H/2] and down_blocks [E, H, F/2] for inputs [T, H]")
+    adapters = (gate_up_lora_A, gate_up_lora_B, down_lora_A, down_lora_B)
+    _check_ffn_adapters(adapters, E, H, F2)
+    if not inputs.is_cuda:
+        raise RuntimeError("inputs must be a CUDA tensor (the product path has no CPU fallback)")
+    biases = (_check_bias(gate_up_bias, F2, inputs.device, E), _check_bias(down_bias, H, inputs.device, E))
+    return _fp4_ffn_lora(_NVFP4FFNLoRAFn, _NVFP4_LORA_OPS, (gate_up_blocks, gate_up_scales, gate_up_global),
+                         (down_blocks, down_scales, down_global), inputs, adapters, biases, float(scaling), tokens_per_expert,
+                         input_offsets, act)
+
+
+def linear_lora_forward_nvfp4(x, blocks, scales_e4m3, global_scale, lora_A, lora_B, scaling, bias=None):
+    """A dense NVFP4 linear layer plus a low-rank adapter, fused: ``y = (bf16(x) @ W^T) * global_scale + bf16(v) @
+    bf16(lora_B)^T (+ bias)`` with ``v = scaling * x @ lora_A^T``.  ``x`` [T, K] float32 or bfloat16, ``lora_A`` [r, K] and
+    ``lora_B`` [N, r] float32; the result has ``x``'s type.  Differentiable (once) in ``x``, ``lora_A`` and ``lora_B``; the
+    NVFP4 weights and the bias are frozen, and the gradient is straight-through across the bfloat16 roundings."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError("ops.linear_lora_forward_nvfp4: x must be a float32 or bfloat16 [T, K] tensor (float16 is refused: "
+                           "rounding it to bfloat16 would lose three bits; cast it yourself)")
+    for name, t in (("lora_A", lora_A), ("lora_B", lora_B)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2:
+            raise RuntimeError(f"{name} must be a float32 2-D tensor: lora_A [r, K] and lora_B [N, r]")
+    r = lora_A.shape[0]
+    if r not in LORA_RANKS:
+        raise RuntimeError(f"LoRA rank must be one of {LORA_RANKS}, got {r}")
+    if lora_A.shape[1] != x.shape[1] or lora_B.shape[1] != r or blocks.dim() != 2 or lora_B.shape[0] != blocks.shape[0]:
+        raise RuntimeError(f"lora_A must be [r, {x.shape[1]}] and lora_B [N, r] for blocks [N, K/2]")
+    if not x.is_cuda:
+        raise RuntimeError("ops.linear_lora_forward_nvfp4: x must be a CUDA tensor (the adapter path has no CPU fallback)")
+    if _wants_grad(x, lora_A, lora_B):
+        return _NVFP4LinearLoRAFn.apply(x, lora_A, lora_B, blocks, scales_e4m3, global_scale, bias, float(scaling))
+    return _nvfp4_linear_lora_apply(x, blocks, scales_e4m3, global_scale, lora_A, lora_B, float(scaling), bias)[0]
+
+
+def _nvfp4_linear_lora_apply(x, blocks, scales, gs, lora_A, lora_B, scaling, bias):
+    """(y, v): the shrink (scale included) and the GEMM with its adapter stage."""
+    x = x.detach()
+    v = lora_shrink(x, lora_A.detach(), "rc", scale=scaling)
+    return linear_forward_nvfp4_lora(blocks, scales, gs, x, v, lora_B.detach(), bias=bias, out_dtype=x.dtype), v
+
+
+class _NVFP4LinearLoRAFn(torch.autograd.Function):
+    """Dense NVFP4 linear + adapter in one node.  Saves x (in its own type) and v = s x A^T ([T, r] float32)."""
+
+    @staticmethod
+    def forward(ctx, x, lora_A, lora_B, blocks, scales, gs, bias, scaling):
+        x2 = x.contiguous()
+        y, v = _nvfp4_linear_lora_apply(x2, blocks, scales, gs, lora_A, lora_B, scaling, bias)
+        ctx.save_for_backward(x2, v, lora_A, lora_B, blocks, scales, gs)
+        ctx.scaling = scaling
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, v, lora_A, lora_B, blocks, scales, gs = ctx.saved_tensors
+        need_x, need_A, need_B = ctx.needs_input_grad[:3]
+        check_activation_rows(gy, "the incoming gradient", x2.dtype)
+        g = gy.contiguous()
+        gx = gA = gB = None
+        if need_B:
+            gB = lora_grad(g, v, "cr")[0]                                                # dB = dY^T v (s is in v)
+        if need_x or need_A:
+            dv = lora_shrink(g, lora_B, "cr", scale=ctx.scaling)                         # dv = s dY B
+            if need_A:
+                gA = lora_grad(x2, dv, "rc")[0]                                          # dA = dv^T x
+            if need_x:
+                gx = linear_backward_input_nvfp4_lora(blocks, scales, gs, g, dv, lora_A, out_dtype=x2.dtype)   # dX = dY W g + dv A
+        return gx, gA, gB, None, None, None, None, None

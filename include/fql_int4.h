@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 440 /* 0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 450 /* 0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1252,6 +1252,51 @@ FQL_API int fql_moe_nvfp4_bwd_input(const uint8_t *blocks, const uint8_t *scales
                                     const void *grad_out, int in_dtype, const int32_t *tokens_per_expert,
                                     const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
                                     void *stream);
+
+/* ---- low-rank adapters on the NVFP4 weights, fused into the NVFP4 tile kernels (FQL_VERSION 450; INTEGRATION.md
+ *      section 18; csrc/fql_gemm_nvfp4.h, csrc/fql_gemm_nvfp4_bwd.h) ----
+ * The adapter forms of fql_moe_nvfp4_fwd, fql_moe_nvfp4_glu_fwd, fql_moe_nvfp4_bwd_input and of the dense entries: the adapter
+ * term is one more contraction stage of the same kernel, behind the last weight stage, as in the fql_moe_mx4_lora_* entries.
+ *   forward   out[t][n] = round_OUT( fl32( S + bias[e][n] ) ),  S  = fl32(accW * g_e)  (+) sum_{j < rank} bf16(v[t][j]) bf16(B[e][n][j])
+ *   backward  dX[t][k]  = round_OUT( S' ),                      S' = fl32(accW' * g_e) (+) sum_{j < rank} bf16(dv[t][j]) bf16(A[e][j][k])
+ *   accW / accW' are the base entries' accumulators (the same instructions on ascending k / n, from zero), g_e = global_scale[e]
+ *   (NULL: 1, no multiply), (+) is the matrix instruction accumulating onto its C operand in ascending j, 16 a step.
+ *   global_scale scales the WEIGHT term only: the accumulator is multiplied by it (one float32 rounding a register, never an
+ *   FMA) behind the last weight stage and in front of the adapter stage; the epilogue then adds the bias and rounds.
+ *   With lora_B (lora_A) all zeros and finite lora_rows the result equals the base entry's for any global_scale and bias (the
+ *   only possible difference is the sign of a zero when g_e < 0: the adapter stage adds +0 to a -0).
+ * fql_moe_nvfp4_glu_lora_fwd: the same on h = bf16(act(gate_up)) (fql_moe_nvfp4_glu_fwd's pre-pass and workspace, unchanged).
+ * fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input: one matrix, global_scale [1] or NULL, no table: exactly the grouped
+ *   launchers with E = 1.
+ *   lora_rows [T][rank] float32, lora_B [E][N][rank], lora_A [E][rank][K] float32, rank one of 4, 8, 16, 32, 64: as
+ *   fql_moe_mx4_lora_fwd's, with its rounding, order, non-finite rule (a non-finite element of a row of lora_rows makes
+ *   exactly that row of the result NaN; the adapter matrices and global_scale are not screened) and alignment (4 bytes).
+ *   A NaN scale byte gives what it gives in the base entries: the adapter stage overwrites the LDS images in full.
+ *   These entries always run the 64-row tile kernels (no decode form: they are for training).  The grouped call equals E
+ *   one-expert calls bit for bit; a row's result depends on its own rows of x and v and its expert's W, B and g only.
+ *   Return codes: the base entry's, in its order, with the adapter checks of fql_moe_mx4_lora_fwd in their places
+ *   (FQL_ERR_BAD_SHAPE for the rank behind the dtype check, FQL_ERR_NULL_POINTER, FQL_ERR_ALIGNMENT), all before any HIP call.
+ *   The two input gradients with N == 0 and T > 0 are FQL_ERR_BAD_SHAPE. */
+FQL_API int fql_moe_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                   int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, void *out, int out_dtype, int E,
+                                   int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_nvfp4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                       const void *gate_up, int in_dtype, const float *lora_rows, const float *lora_B, int rank,
+                                       const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                       void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                       float act_limit, void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_moe_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                         const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A, int rank,
+                                         const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
+                                         int out_dtype, int E, int T, int K, int N, void *stream);
+FQL_API int fql_linear_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                      int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                      void *out, int out_dtype, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                            const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A,
+                                            int rank, void *grad_in, int out_dtype, int T, int K, int N, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -24,7 +24,8 @@ and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision=
 ``quantize_rows_mxfp6``; and behind those the dense MXFP4 linear ops on one expert's matrix and 16 rows:
 ``linear_forward_mxfp4`` and ``linear_gated_forward_mxfp4`` with the tile kernel, the grouped decode kernel and the split
 form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``; then the NVFP4 forward ops, decode and
-tile, and last ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands."""
+tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands, and last the five NVFP4 adapter
+ops (``moe_forward_nvfp4_lora`` and its kin) on them."""
 import argparse
 import hashlib
 import os
@@ -509,6 +510,29 @@ def calls(dev, fq, ops):
                 Pm, Sn, Gn, gy.to(dt), tpe, offs, out_dtype=do)
         yield f"moe_backward_input_nvfp4 no global {dt}", lambda: ops.moe_backward_input_nvfp4(Pm, Sn, None, gy.to(dt), tpe, offs)
         yield f"linear_backward_input_nvfp4 {dt}", lambda: ops.linear_backward_input_nvfp4(Pm[0], Sn[0], Gn[:1], gy[:16].to(dt))
+
+    # the five NVFP4 adapter ops, behind the lines above (their random draws come last): r = 8, v / dv [T, r], B [E, N, r] and
+    # A [E, r, K] on the same operands and table; always the tile kernel; the dense ops on expert 0's matrices, the first 16 rows
+    Rn = 8
+    vn, dvn = d.randn(x.shape[0], Rn).to(dev), d.randn(x.shape[0], Rn).to(dev)
+    Bn, An = (d.randn(E, N, Rn) * 0.1).to(dev), (d.randn(E, Rn, K) * 0.1).to(dev)
+    for btag, b in (("", None), (" bias", biasm)):
+        for dt in (F32, BF16):
+            for do in (F32, BF16):
+                tag = f"{dt}->{do}{btag}"
+                yield f"moe_forward_nvfp4_lora {tag}", lambda: ops.moe_forward_nvfp4_lora(
+                    Pm, Sn, Gn, x.to(dt), vn, Bn, tpe, offs, bias=b, out_dtype=do)
+                yield f"moe_gated_forward_nvfp4_lora {tag}", lambda: ops.moe_gated_forward_nvfp4_lora(
+                    Pm, Sn, Gn, gu.to(dt), vn, Bn, tpe, offs, bias=b, out_dtype=do, **glu)
+                yield f"linear_forward_nvfp4_lora {tag}", lambda: ops.linear_forward_nvfp4_lora(
+                    Pm[0], Sn[0], Gn[:1], x[:16].to(dt), vn[:16].contiguous(), Bn[0], bias=None if b is None else b[0], out_dtype=do)
+    for dt in (F32, BF16):
+        for do in (F32, BF16):
+            yield f"moe_backward_input_nvfp4_lora {dt}->{do}", lambda: ops.moe_backward_input_nvfp4_lora(
+                Pm, Sn, Gn, gy.to(dt), dvn, An, tpe, offs, out_dtype=do)
+            yield f"linear_backward_input_nvfp4_lora {dt}->{do}", lambda: ops.linear_backward_input_nvfp4_lora(
+                Pm[0], Sn[0], Gn[:1], gy[:16].to(dt), dvn[:16].contiguous(), An[0], out_dtype=do)
+        yield f"moe_forward_nvfp4_lora no global {dt}", lambda: ops.moe_forward_nvfp4_lora(Pm, Sn, None, x.to(dt), vn, Bn, tpe, offs)
 
 
 def digest(t):
