@@ -34,6 +34,10 @@ The NVFP4 experts (ops.moe_forward_nvfp4 / moe_gated_forward_nvfp4 under both ke
 ops.moe_backward_input_nvfp4) go through the same scenes with a global scale per expert and a bias, at K = 288 and 96 and,
 for the plain forward, at K = 608, where the decode kernel's load ring consumes a refilled slot; the dense
 ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 replay over changing rows, and the block also wraps NVFP4MoEFFN.
+The NVFP4 adapter entries (ops.moe_forward_nvfp4_lora / moe_gated_forward_nvfp4_lora / moe_backward_input_nvfp4_lora, with
+NaN shrunk rows where a scene leaves a row uncovered and global scales that are not 1) go through the same scenes, the dense
+ops.linear_forward_nvfp4_lora / linear_backward_input_nvfp4_lora replay beside the dense base ops, and the block also wraps
+LoRANVFP4MoEFFN.
 
 Every family asserts the kernel id the library reports for its shape (fql_tune_chosen_cfg / fql_tune_mx4_kernel /
 fql_tune_mx4_scaled_kernel / fql_tune_mx4_f6_kernel / fql_tune_mx4_linear_kernel / fql_tune_nvfp4_kernel; the adapter entries
@@ -637,6 +641,87 @@ def nv4_backward(K, N):
     return Family(E, T, MX4_RAGGED, make_rows, call, reference, None)
 
 
+NV4_LORA_GS = (0.5, 2.0, 0.25, 4.0, 0.125)            # the adapter families' global scales: none is 1, neighbours differ
+
+
+def nv4_lora_exact64(base64, add64, g, bias64=None):
+    """float64 (base64 * g + add64 + bias64) of the integer recipe of tests/test_gpu_nvfp4_lora.py, with that file's
+    exactness condition asserted from the operands alone: every weight term is a multiple of g * 2^-5 (integer x code / 2 x
+    scale byte / 16), every other term an integer, and the sum of the absolute values of all terms of one output (``base64``
+    and ``add64`` are (value, that sum) pairs) stays below 2^24 of that unit, so a float32 sum is exact in any order."""
+    unit = min(g * 2.0 ** -5, 1.0)
+    mass = base64[1] * g + add64[1] + (0 if bias64 is None else bias64.abs())
+    assert float(mass.max()) < 2.0 ** 24 * unit
+    return base64[0] * g + add64[0] + (0 if bias64 is None else bias64)
+
+
+def nv4_lora(K, N, r, kind):
+    """The adapter stage fused into the NVFP4 GEMMs (tests/test_gpu_nvfp4_lora.py): ``kind`` "fwd" (rows (x, v)), "glu"
+    ((gate_up, v)) or "bwd" ((gy, dv)); the adapter matrix B [E, N, r] / A [E, r, K] is fixed, the global scales are
+    NV4_LORA_GS and scale the weight term ONLY, the forward kinds have a bias.  "fwd" and "bwd": that file's integer recipe,
+    rows and shrunk rows in [-4, 4], adapter integers in [-2, 2], scale bytes 0x30 .. 0x47, an integer bias; its exactness
+    condition is asserted per scene (nv4_lora_exact64), so the float32 result is the float64 definition.  "glu": Gaussian data
+    against the float64 product of the bfloat16-rounded float64 h times g plus the float64 adapter term on the
+    bfloat16-rounded v and B, at NV4_GATED_BOUND scaled as mx4_lora scales MX4_GATED_BOUND, by max(1, (K + r) / 288).  The
+    shrunk rows of the rows a scene leaves uncovered are NaN (S3 .. S6).  The adapter entries have one kernel form."""
+    exact = kind != "glu"
+    p, W = nv4_weights(K, N, exact)
+    E, T = p["E"], p["T"]
+    gs = torch.tensor(NV4_LORA_GS, device=DEV)
+    assert all(g != 1.0 for g in NV4_LORA_GS) and all(a != b for a, b in zip(NV4_LORA_GS, NV4_LORA_GS[1:])) and len(NV4_LORA_GS) == E
+    uncovered = scene_uncovered(E, T, MX4_RAGGED)
+    assert all(bool(uncovered[s].any()) for s in (3, 4, 5)) and not bool(uncovered[0].any())
+    g0 = gen(0, K, N, r, 17)
+    C = N if kind == "bwd" else K                                   # the contraction of the base product
+    if exact:
+        M = torch.randint(-2, 3, (E, r, K) if kind == "bwd" else (E, N, r), generator=g0).float().to(DEV)
+    else:                                                            # sized so that the adapter term is of the base term's size
+        rms = (W * gs.double().view(E, 1, 1)).square().mean(dim=2, keepdim=True).sqrt()
+        M = torch.randn(E, N, r, generator=g0).to(DEV) * (rms * (C / r) ** 0.5).float()
+    M64 = M.bfloat16().double()
+
+    def make_rows(seed):
+        g = gen(seed, K, N, r, 17 + len(kind))
+        if kind == "glu":
+            rows, v = 2.0 * torch.randn(T, 2 * K, generator=g), torch.randn(T, r, generator=g)
+        else:
+            rows, v = torch.randint(-4, 5, (T, C), generator=g).float(), torch.randint(-4, 5, (T, r), generator=g).float()
+        v[uncovered[seed]] = NAN
+        return rows.to(DEV), v.to(DEV)
+
+    def call(rows, v, tpe, offs):
+        w = (p["blocks"], p["scales"], gs)
+        if kind == "fwd":
+            return ops().moe_forward_nvfp4_lora(*w, rows, v, M, tpe, offs, bias=p["bias"], out_dtype=torch.float32)
+        if kind == "glu":
+            return ops().moe_gated_forward_nvfp4_lora(*w, rows, v, M, tpe, offs, bias=p["bias"], out_dtype=torch.float32,
+                                                      **act_kw("swiglu_clamp"))
+        return ops().moe_backward_input_nvfp4_lora(*w, rows, v, M, tpe, offs)
+
+    def reference(rows, ranges):
+        x64 = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double() if kind == "glu" else rows[0].double()
+        v64 = rows[1].bfloat16().double()
+        out = torch.zeros(T, K if kind == "bwd" else N, dtype=torch.float64, device=DEV)
+        changed = False
+        for e, (lo, hi) in enumerate(ranges):
+            if hi <= lo:
+                continue
+            We, Me = (W[e], M64[e]) if kind == "bwd" else (W[e].t(), M64[e].t())
+            base, add = x64[lo:hi] @ We, v64[lo:hi] @ Me
+            bias64 = None if kind == "bwd" else p["bias"][e].double()
+            if exact:
+                out[lo:hi] = nv4_lora_exact64((base, x64[lo:hi].abs() @ We.abs()), (add, v64[lo:hi].abs() @ Me.abs()),
+                                              NV4_LORA_GS[e], bias64)
+            else:
+                out[lo:hi] = base * NV4_LORA_GS[e] + add + bias64
+            changed = changed or bool(add.count_nonzero())
+        assert bool(torch.isfinite(out).all()) and changed == any(hi > lo for lo, hi in ranges)   # (the adapter matters)
+        return out
+
+    bound = None if exact else NV4_GATED_BOUND * lora_bound(K, r) / LORA_BASE_BOUND
+    return Family(E, T, MX4_RAGGED, make_rows, call, reference, bound)
+
+
 # ---- the families, by name (tests/test_gpu_side_stream.py takes its cases from here)
 
 SMALL = dict(E=4, K=512, N=136)                   # wide_tiles < 128: the small regime of choose_cfg (csrc/fql_int4.hip)
@@ -698,6 +783,9 @@ for _K, _N in ((288, 136), (96, 37)):
     for _form in ("tile", "decode"):
         FAMILIES[f"nv4-K{_K}-N{_N}-glu-{_form}"] = functools.partial(nv4_gated, _K, _N, _form)
     FAMILIES[f"nv4-K{_K}-N{_N}-bwd"] = functools.partial(nv4_backward, _K, _N)
+for _K, _N, _r in ((288, 136, 16), (96, 37, 64)):                   # (the MXFP4 adapter families' shapes)
+    for _kind in ("fwd", "glu", "bwd"):
+        FAMILIES[f"nv4-lora-{_kind}-K{_K}-N{_N}-r{_r}"] = functools.partial(nv4_lora, _K, _N, _r, _kind)
 
 
 @pytest.mark.parametrize("name", list(FAMILIES))
@@ -791,18 +879,48 @@ def test_dense_linear_split_form_replays(tune, name):
 NV4_LINEAR_T, NV4_LINEAR_K, NV4_LINEAR_N = 5, 96, 37
 
 
-def nv4_linear_case(gated):
-    """(call(rows) -> [T, N] float32, make_rows(seed), reference(rows) -> float64, bound or None): expert 3's matrix, global
-    scale and bias of the grouped NVFP4 families as a dense layer.  Plain: the integer recipe, exact.  Gated: Gaussian
-    gate | up rows against the bfloat16-rounded float64 h at NV4_GATED_BOUND."""
+NV4_LINEAR_RANK = {"lora-fwd": 8, "lora-bwd": 32}      # (the two ranks the grouped adapter families do not run)
+
+
+def nv4_linear_case(kind):
+    """(call(*rows) -> [T, N] float32 ([T, K]: "lora-bwd"), make_rows(seed) -> the tuple of row tensors, reference(rows) ->
+    float64, bound or None) of ``kind`` "plain", "gated", "lora-fwd" or "lora-bwd": expert 3's matrix, global scale and bias
+    of the grouped NVFP4 families as a dense layer.  Plain: the integer recipe, exact.  Gated: Gaussian gate | up rows
+    against the bfloat16-rounded float64 h at NV4_GATED_BOUND.  The adapter entries (ops.linear_forward_nvfp4_lora with the
+    bias on rows (x, v), ops.linear_backward_input_nvfp4_lora on (gy, dv)): the integer recipe of nv4_lora with the global
+    scale NV4_LORA_GS[3] on the weight term only, exact (nv4_lora_exact64)."""
     T, K, N = NV4_LINEAR_T, NV4_LINEAR_K, NV4_LINEAR_N
+    gated = kind == "gated"
     p, W = nv4_weights(K, N, not gated)
     e = 3
     blocks, scales, gs, bias = p["blocks"][e], p["scales"][e], p["gs"][e:e + 1], p["bias"][e]
+    if kind in NV4_LINEAR_RANK:
+        r, bwd = NV4_LINEAR_RANK[kind], kind == "lora-bwd"
+        C, g_e = (N if bwd else K), NV4_LORA_GS[e]
+        gs = torch.tensor([g_e], device=DEV)
+        M = torch.randint(-2, 3, (r, K) if bwd else (N, r), generator=gen(0, K, N, r, 19)).float().to(DEV)
+        We, Me = (W[e], M.double()) if bwd else (W[e].t(), M.double().t())
+
+        def make_rows(seed):
+            g = gen(seed, K, N, r, 20 + bwd)
+            return torch.randint(-4, 5, (T, C), generator=g).float().to(DEV), torch.randint(-4, 5, (T, r), generator=g).float().to(DEV)
+
+        def call(rows, v):
+            if bwd:
+                return ops().linear_backward_input_nvfp4_lora(blocks, scales, gs, rows, v, M)
+            return ops().linear_forward_nvfp4_lora(blocks, scales, gs, rows, v, M, bias=bias, out_dtype=torch.float32)
+
+        def reference(rows):
+            x64, v64 = rows[0].double(), rows[1].double()
+            add = v64 @ Me
+            assert bool(add.count_nonzero())                         # (the adapter matters)
+            return nv4_lora_exact64((x64 @ We, x64.abs() @ We.abs()), (add, v64.abs() @ Me.abs()), g_e,
+                                    None if bwd else bias.double())
+        return call, make_rows, reference, None
 
     def make_rows(seed):
         g = gen(seed, K, N, 14 + gated)
-        return (2.0 * torch.randn(T, 2 * K, generator=g) if gated else torch.randint(-4, 5, (T, K), generator=g).float()).to(DEV)
+        return ((2.0 * torch.randn(T, 2 * K, generator=g) if gated else torch.randint(-4, 5, (T, K), generator=g).float()).to(DEV),)
 
     def call(rows):
         if gated:
@@ -811,33 +929,35 @@ def nv4_linear_case(gated):
         return ops().linear_forward_nvfp4(blocks, scales, gs, rows, bias=bias, out_dtype=torch.float32)
 
     def reference(rows):
-        x64 = hidden64("swiglu_clamp", rows, ALPHA, LIMIT).bfloat16().double() if gated else rows.double()
+        x64 = hidden64("swiglu_clamp", rows[0], ALPHA, LIMIT).bfloat16().double() if gated else rows[0].double()
         acc = x64 @ W[e].t()
         assert gated or float(acc.abs().max()) < 2 ** 16
         return nv4_epilogue(acc, gs[0], bias)
     return call, make_rows, reference, NV4_GATED_BOUND if gated else None
 
 
-@pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])
-def test_dense_nvfp4_linear_replays(gated):
-    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 at K = 96, N = 37, T = 5, captured once and replayed over four
-    row sets, the last equal to the first, with SENT in the output before each replay: each replay is the eager result bit
-    for bit, the reference (exactly, plain; within the gated bound), and has overwritten every SENT.  The gated entry's
+@pytest.mark.parametrize("kind", ["plain", "gated", "lora-fwd", "lora-bwd"])
+def test_dense_nvfp4_linear_replays(kind):
+    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 and the adapter entries ops.linear_forward_nvfp4_lora (r = 8) /
+    linear_backward_input_nvfp4_lora (r = 32) at K = 96, N = 37, T = 5, captured once and replayed over four row sets, the
+    last equal to the first, with SENT in the output before each replay: each replay is the eager result bit for bit, the
+    reference (exactly, but for the gated entry: within its bound), and has overwritten every SENT.  The gated entry's
     pre-pass writes h into a workspace of the graph's pool in front of the GEMM; a launch that left the capture stream is a
     capture error or a node missing from the graph, which shows as SENT or as the previous row set's result."""
-    call, make_rows, reference, bound = nv4_linear_case(gated)
-    static = make_rows(0).clone()
-    graph, out, _ = capture(call, [static])
+    call, make_rows, reference, bound = nv4_linear_case(kind)
+    static = [t.clone() for t in make_rows(0)]
+    graph, out, _ = capture(call, static)
     try:
         first = None
         for i, seed in enumerate((0, 1, 2, 0)):
             rows = make_rows(seed)
-            static.copy_(rows)
+            for s, t in zip(static, rows):
+                s.copy_(t)
             out.fill_(SENT)
             graph.replay()
             torch.cuda.synchronize()
             got = out.clone()
-            eager = call(rows.clone())
+            eager = call(*[t.clone() for t in rows])
             assert same_bits(got, eager), (i, first_diff(got, eager))
             ref = reference(rows)
             assert torch.equal(got == SENT, ref.float() == SENT), f"replay {i}: an element still holds the sentinel"
@@ -902,7 +1022,7 @@ def test_first_gemm_i8_inside_a_capture_then_eager_then_replay():
 # ---- the whole block: the routing changes by itself
 
 BE, BH, BF, BTOPK = 4, 64, 96, 2
-BRANK = 16                          # the rank of the "mxfp4-lora" block's adapters
+BRANK = 16                          # the rank of the "mxfp4-lora" and "nvfp4-lora" blocks' adapters
 
 
 def block_weights():
@@ -914,24 +1034,25 @@ def block_weights():
 
 
 def build_block(kind, capped):
-    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared", "mxfp4", "mxfp4-lora" or "nvfp4" experts
-    (swiglu_clamp with expert biases; "nvfp4": NVFP4MoEFFN, whose from_weights gives every expert global scales of its own;
-    "mxfp4-lora": LoRAMXFP4MoEFFN of rank BRANK around the same MXFP4 experts, with random
-    values in BOTH B matrices -- a fresh adapter has B = 0 and would test nothing); ``capped``: capacity_factor = 1 (the
-    forward then takes a token mask too)."""
+    """E = 4, H = 64, F = 96, top-2, a router bias; ``kind``: "int4", "int4-shared", "mxfp4", "mxfp4-lora", "nvfp4" or
+    "nvfp4-lora" experts (swiglu_clamp with expert biases; "nvfp4": NVFP4MoEFFN, whose from_weights gives every expert global
+    scales of its own; "mxfp4-lora" / "nvfp4-lora": LoRAMXFP4MoEFFN / LoRANVFP4MoEFFN of rank BRANK around the same MXFP4 /
+    NVFP4 experts, with random values in BOTH B matrices -- a fresh adapter has B = 0 and would test nothing); ``capped``:
+    capacity_factor = 1 (the forward then takes a token mask too)."""
     w = block_weights()
     factor = 1.0 if capped else None
-    if kind in ("mxfp4", "mxfp4-lora", "nvfp4"):
-        if kind == "nvfp4":
+    if kind in ("mxfp4", "mxfp4-lora", "nvfp4", "nvfp4-lora"):
+        if kind in ("nvfp4", "nvfp4-lora"):
             experts = fq().NVFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
-                                                    down_bias=w["db"], **act_kw("swiglu_clamp"))
+                                                    down_bias=w["db"], input_grad=kind == "nvfp4-lora", **act_kw("swiglu_clamp"))
             assert len(set(experts.gate_up_global.tolist())) > 1 and len(set(experts.down_global.tolist())) > 1
         else:
             experts = fq().MXFP4MoEFFN.from_weights(w["gate"], w["up"], w["down"], gate_bias=w["gb"], up_bias=w["ub"],
                                                     down_bias=w["db"], input_grad=kind == "mxfp4-lora", **act_kw("swiglu_clamp"))
-        if kind == "mxfp4-lora":
+        if kind in ("mxfp4-lora", "nvfp4-lora"):
             torch.manual_seed(43)                                    # (the adapters' A)
-            experts = fq().LoRAMXFP4MoEFFN.from_layer(experts, BRANK, alpha=2.0 * BRANK)
+            wrap = fq().LoRAMXFP4MoEFFN if kind == "mxfp4-lora" else fq().LoRANVFP4MoEFFN
+            experts = wrap.from_layer(experts, BRANK, alpha=2.0 * BRANK)
             g = torch.Generator().manual_seed(44)
             with torch.no_grad():
                 experts.gate_up_lora_B.copy_(torch.randn(experts.gate_up_lora_B.shape, generator=g) * 0.2)
@@ -1016,9 +1137,9 @@ def block_float64(m, x, idx, keep, w, mx4):
 @pytest.mark.parametrize("T", [3, 130])
 @pytest.mark.parametrize("kind,capped", [("int4", False), ("int4", True), ("int4-shared", True), ("mxfp4", False),
                                          ("mxfp4", True), ("mxfp4-lora", False), ("mxfp4-lora", True), ("nvfp4", False),
-                                         ("nvfp4", True)],
+                                         ("nvfp4", True), ("nvfp4-lora", False), ("nvfp4-lora", True)],
                          ids=["int4", "int4-capped", "int4-shared-capped", "mxfp4", "mxfp4-capped", "mxfp4-lora",
-                              "mxfp4-lora-capped", "nvfp4", "nvfp4-capped"])
+                              "mxfp4-lora-capped", "nvfp4", "nvfp4-capped", "nvfp4-lora", "nvfp4-lora-capped"])
 def test_block_replays_under_changing_routing(tune, kind, capped, T):
     """QuantizedSparseMoEBlock under torch.no_grad(), captured once; then new tokens, the router bias overwritten in place
     so that every token picks experts 2 and 0, a mask with one real token (the capped blocks) and the first scene again.
@@ -1026,8 +1147,10 @@ def test_block_replays_under_changing_routing(tune, kind, capped, T):
     differ from the "mxfp4" block's); the pure-float64 check adds the two adapter terms with the kernels' roundings
     (ffn64) and is held to the MXFP4 block's own bound, MX4_GATED_BOUND, unscaled.  "nvfp4": NVFP4MoEFFN experts; the
     pure-float64 check multiplies the dequantised weights by the experts' global scales and is held to the same unscaled
-    MX4_GATED_BOUND (DESIGN.md section 40 has the measured values: no constant of its own)."""
-    m, mx4 = build_block(kind, capped), kind in ("mxfp4", "mxfp4-lora", "nvfp4")
+    MX4_GATED_BOUND (DESIGN.md section 40 has the measured values: no constant of its own).  "nvfp4-lora": those NVFP4
+    experts inside LoRANVFP4MoEFFN, both B matrices random (the output is asserted once to differ from the "nvfp4"
+    block's); ffn64 applies the global scales to the weight term and not to the adapter terms; the same unscaled bound."""
+    m, mx4 = build_block(kind, capped), kind in ("mxfp4", "mxfp4-lora", "nvfp4", "nvfp4-lora")
     bias0 =m.gate.bias.detach().clone()
     same_two = torch.tensor([60.0, -60.0, 120.0, -60.0], device=DEV)      # (the logits without it stay within +-20)
     xs = [torch.randn(T, BH, generator=gen(i, T)).to(DEV) for i in range(3)]
@@ -1076,10 +1199,10 @@ def test_block_replays_under_changing_routing(tune, kind, capped, T):
                     assert not got[~mask].any(), name                # a masked token's output is zero
                 if name == "first":
                     first = (got, got_logits)
-                    if kind == "mxfp4-lora":                         # (the adapters matter: not the wrapped experts' output)
-                        plain = build_block("mxfp4", capped)
+                    if kind in ("mxfp4-lora", "nvfp4-lora"):         # (the adapters matter: not the wrapped experts' output)
+                        plain = build_block(kind[:-5], capped)
                         other = plain(x.clone(), token_mask=mask.clone())[0] if capped else plain(x.clone())[0]
-                        print(f"block {kind} capped={capped} T={T}: rel_fro to the mxfp4 block's output {rel_fro_dev(got, other):.3e}")
+                        print(f"block {kind} capped={capped} T={T}: rel_fro to the {kind[:-5]} block's output {rel_fro_dev(got, other):.3e}")
                         assert other.shape == got.shape and not same_bits(got, other)
             assert same_bits(got, first[0]) and same_bits(got_logits, first[1])
         finally:

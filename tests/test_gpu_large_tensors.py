@@ -1552,3 +1552,66 @@ def test_nvfp4_rows_past_4_gib(lib, case):
     assert int(torch.count_nonzero(got)) == nz, f"nvfp4 {case}: a row no expert covers is not zero"
     assert_guards_intact(xb, what=f"rows into the NVFP4 {case} entry")
     del got, x, xb
+
+
+# ======================================================================= NVFP4 experts with a fused adapter: large ADAPTERS
+@pytest.mark.parametrize("entry", ["fwd", "bwd"])
+def test_nvfp4_lora_large_adapters(lib, entry):
+    """test_mxfp4_lora_large_adapters for NVFP4: ops.moe_forward_nvfp4_lora with B [E, N, 64] and
+    ops.moe_backward_input_nvfp4_lora with A [E, 64, K] past 2^32 bytes, on blocks past 2^32 bytes (``lora_large_shape``:
+    the same shapes, the smallest that cross both boundaries): rows go to expert 0, every expert in which either operand
+    crosses 2^31 or 2^32, and E - 1.  Every other expert's adapter is NaN, its blocks are 0xFF, its scale bytes 0xFF (NaN)
+    and its global scale NaN; the shrunk rows of the rows no expert covers are NaN.  The scale bytes [E, N, K / 16] are twice
+    the MXFP4 ones (0.52 and 0.55 GiB instead of 0.26 and 0.27): the test holds 12.9 and 17.6 GiB of its own, and in the
+    whole suite's process, beside what earlier files keep cached, it printed peaks of 14.93 and 19.60 GiB on an MI355X (its
+    twin 14.67 and 19.33), which is what ``need`` gets, rounded up.  The integer recipe of
+    tests/test_gpu_nvfp4_lora.py (rows and shrunk rows in [-4, 4], adapter integers in [-2, 2], scale bytes 0x30 .. 0x47, a
+    power-of-two global scale that differs between neighbouring live experts and scales the weight term only): a weight
+    term is a multiple of g * 2^-5, an adapter term an integer, and the sum of the absolute values of all terms of one
+    output is asserted below 2^24 of that unit, so the float32 result IS the float64 reference.  The adapter entries have
+    one kernel form (the tile kernel; the library has no choice to report)."""
+    K, N, E, wb, ab, experts = lora_large_shape(entry)
+    need(15 if entry == "fwd" else 20)
+    torch.cuda.reset_peak_memory_stats()
+    r = LORA_R
+    buf = BigGuarded("blocks", E * wb, torch.uint8, 0xFF)
+    blocks = buf.view(E, N, K // 2)
+    blocks.fill_(0xFF)
+    scales = torch.full((E, N, K // 16), 0xFF, dtype=torch.uint8, device=DEV)
+    abuf = BigGuarded("adapter", E * ab, torch.float32, NAN)
+    M = abuf.view(E, N, r) if entry == "fwd" else abuf.view(E, r, K)
+    M.fill_(NAN)
+    g = torch.Generator(device=DEV).manual_seed(27)
+    gs, Ws = nv4_fill(blocks, scales, experts, g)
+    live = [float(gs[e]) for e in experts]
+    assert all(a != b for a, b in zip(live, live[1:])) and int(torch.isnan(gs).sum()) == E - len(experts)
+    for e in experts:
+        M[e] = torch.randint(-2, 3, tuple(M.shape[1:]), generator=g, device=DEV).float()
+    groups, T = lora_large_groups(len(experts))
+    tpe, offs = table_of(groups, E=E, experts=experts, T=T)
+    C = K if entry == "fwd" else N                            # the contraction of the base product
+    x = torch.randint(-4, 5, (T, C), generator=g, device=DEV).float()
+    v = torch.full((T, r), NAN, device=DEV)
+    for lo, hi in groups:
+        v[lo:hi] = torch.randint(-4, 5, (hi - lo, r), generator=g, device=DEV).float()
+    last = M.shape[2] * 4                                     # the bytes of the last row of an expert's adapter matrix
+    assert sum(input_wrap_is_visible(buf, (e + 1) * wb - K // 2, K // 2) for e in experts) >= len(experts) - 1
+    assert sum(input_wrap_is_visible(abuf, (e + 1) * ab - last, last // 4) for e in experts) >= len(experts) - 1
+    refs = []
+    for W, e, ge, (lo, hi) in zip(Ws, experts, live, groups):
+        We, Me = (W.T, M[e].double().T) if entry == "fwd" else (W, M[e].double())
+        x64, v64 = x[lo:hi].double(), v[lo:hi].double()
+        mass = (x64.abs() @ We.abs()) * ge + v64.abs() @ Me.abs()
+        assert float(mass.max()) < 2.0 ** 24 * min(ge * 2.0 ** -5, 1.0)    # (every partial sum is exact in float32)
+        refs.append((x64 @ We) * ge + v64 @ Me)
+        assert bool((v64 @ Me).count_nonzero())               # (the adapter matters)
+    if entry == "fwd":
+        got = ops().moe_forward_nvfp4_lora(blocks, scales, gs, x, v, M, tpe, offs, out_dtype=torch.float32)
+    else:
+        got = ops().moe_backward_input_nvfp4_lora(blocks, scales, gs, x, v, M, tpe, offs)
+    torch.cuda.synchronize()
+    print(f"nvfp4 lora {entry} large adapters: E={E} experts {experts} T={T}, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    check_rows(got, groups, refs, 0.0, f"nvfp4 lora {entry}", exact=True)
+    assert_guards_intact(buf, abuf, what=f"large NVFP4 adapters, {entry}")
+    del blocks, M, buf, abuf

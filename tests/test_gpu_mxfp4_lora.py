@@ -3,7 +3,8 @@ moe_backward_input_mxfp4_lora (the LORA flag of csrc/fql_gemm_mx4.h and csrc/fql
 the layer LoRAMXFP4MoEFFN and QuantizedSparseMoEBlock with such experts.
 
 Shapes: K in {32, 96, 288} and N in {8, 40, 136, 201} as in tests/test_gpu_mxfp4.py and tests/test_gpu_mxfp4_bwd.py (N = 201:
-an odd width, the element stores), r in {4, 16, 64} (less than one 16-j step, exactly one, all four), section 25's table of
+an odd width, the element stores), r over all of ops.LORA_RANKS (4: less than one 16-j step; 8: two of a lane's pack4 groups
+and still less than a step; 16: exactly one; 32: the early exit after exactly two; 64: all four), section 25's table of
 [0, 1, 33, 70] rows plus 2 uncovered, and E = 1 with one row and no table.
 
 BOUNDS.  The float32 result against the float64 product of the same bfloat16-rounded operands: section 25 asserts 2.64e-7 for
@@ -33,7 +34,7 @@ DEV = "cuda"
 DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 ACT = {"silu": 0, "gelu_tanh": 1, "swiglu_clamp": 2}
 TAIL = 2
-KS, NS, RS = [32, 96, 288], [8, 40, 136, 201], [4, 16, 64]
+KS, NS, RS = [32, 96, 288], [8, 40, 136, 201], [4, 8, 16, 32, 64]
 KINDS = ["silu", "gelu_tanh", "swiglu_clamp"]
 KEEP = object()                    # "the problem's own table" (None means no table)
 
@@ -106,6 +107,10 @@ def run_bwd(p, gy=None, dv=None, A=None, out_dtype=None, tpe=KEEP, offs=KEEP):
 
 
 # ---- the lane map, bit for bit
+
+def test_every_accepted_rank_is_tested():
+    assert tuple(RS) == tuple(ops().LORA_RANKS)                                      # a rank added later cannot go untested
+
 
 @pytest.mark.parametrize("r", RS)
 @pytest.mark.parametrize("N", NS)
@@ -272,7 +277,7 @@ def test_grouped_equals_one_expert_calls_and_other_experts_rows_do_not_matter(K,
 
 # ---- accuracy on Gaussian data
 
-@pytest.mark.parametrize("K,N,r", [(288, 136, 64), (288, 201, 16), (96, 40, 4), (32, 8, 64)])
+@pytest.mark.parametrize("K,N,r", [(288, 136, 64), (288, 201, 16), (96, 40, 4), (32, 8, 64), (288, 136, 32), (96, 40, 8)])
 def test_gaussian_data_against_the_same_rounded_operands(K, N, r):
     p, q = fwd_problem(K, N, r), bwd_problem(K, N, r)
     b = bound(K, r)
@@ -295,7 +300,7 @@ def test_gaussian_data_against_the_same_rounded_operands(K, N, r):
 
 # ---- non-finite values
 
-@pytest.mark.parametrize("r", [4, 64])
+@pytest.mark.parametrize("r", [4, 32, 64])
 def test_inf_and_nan_shrunk_rows_are_nan_across_exactly_their_rows(r):
     p, q = fwd_problem(288, 136, r), bwd_problem(288, 136, r)
     t_inf = p["offs"].tolist()[3] + 40                                               # a row of the second 32-row wave
@@ -316,9 +321,10 @@ def test_inf_and_nan_shrunk_rows_are_nan_across_exactly_their_rows(r):
 # ---- guard bands
 
 @pytest.mark.parametrize("dout", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("off", [16, 4], ids=["aligned", "off4"])
-def test_entries_stay_inside_their_buffers(off, dout):
-    """N = 201, K = 96, r = 4, a table whose last count leaves [0, T) and is clipped on the device.  Every pointer is the
+@pytest.mark.parametrize("off,r", [(16, 4), (4, 4), (16, 32), (4, 32)], ids=["aligned", "off4", "aligned-r32", "off4-r32"])
+def test_entries_stay_inside_their_buffers(off, r, dout):
+    """N = 201, K = 96, r = 4 or 32 (a lane's second 32-j half of B is then zeros, not a fetch of the next row or of the
+    guard), a table whose last count leaves [0, T) and is clipped on the device.  Every pointer is the
     interior of a guarded buffer: SENT around out, NaN around v, B and A, which end flush against their guard (Guarded puts
     the guard right behind the last element), so a read of v[t][16 xq + 15 >= r], of a B row past N or of an A row past r
     would fetch NaN and show in the values; a write outside [T, N] changes a guard.  ``off``: the adapter operands 16-byte
@@ -326,7 +332,7 @@ def test_entries_stay_inside_their_buffers(off, dout):
     access inside: this test does not provoke anything, it checks that the result is the public op's and the guards stay."""
     from fused_int4_amd import _native
     lib = _native.lib()
-    K, N, r = 96, 201, 4
+    K, N = 96, 201
     p, q = fwd_problem(K, N, r), bwd_problem(K, N, r)
     E, T = p["E"], p["T"]
     tpe = p["tpe"].clone()

@@ -17,7 +17,16 @@ two or by another random row.  The rows no expert covers are NaN in every input;
 The gated entry has no exact recipe (its h is rounded to bfloat16): Gaussian gate | up rows against the float64 product of
 the bfloat16-rounded float64 h at test_gpu_nvfp4.GATED_BOUND, as that file's gated test; the rows are first moved off
 the points where that rounding is not defined at float32's resolution (near_a_bfloat16_tie).  After every call the two table
-tensors equal their host copies."""
+tensors equal their host copies.
+
+The fused adapter entries (ops.moe_forward_nvfp4_lora / moe_gated_forward_nvfp4_lora / moe_backward_input_nvfp4_lora: the LORA
+stage of nv4_kernel and nv4_bwd_kernel) index the shrunk rows v[t] / dv[t] by the absolute row and B[e] / A[e] by the expert,
+next to the base kernels' own indexing, so they run through the same nine cases with the operand set enlarged as in
+tests/test_gpu_mxfp4_tables.py: v and dv [T, r] integers in [-4, 4] (NaN on the rows no expert covers), B [E, N, r] and
+A [E, r, K] integers in [-2, 2], r = that file's LORA_RANK (4 at K = 96, 64 at K = 288).  The global scale applies to the
+weight term only: S = acc * g_e + sum_j v[t][j] B[e][n][j].  A weight term is a multiple of g_e * 2^-5 and every other term
+an integer; the sum of the absolute values of all terms of one output is asserted below 2^24 of that unit where the
+problem is built, so the float32 result is the float64 reference bit for bit."""
 import functools
 
 import pytest
@@ -25,7 +34,7 @@ import torch
 
 from glu_reference import ALPHA, LIMIT, act_kw, hidden64
 from helpers import NAN, bits, ops, rel_fro_dev, same_bits
-from test_gpu_mxfp4_tables import CASE_IDS, CASES, table_intact, uncovered_all_zero_bits, whole_table
+from test_gpu_mxfp4_tables import CASE_IDS, CASES, LORA_RANK, table_intact, uncovered_all_zero_bits, whole_table
 from test_gpu_nvfp4 import FORMS, GATED_BOUND, epilogue, force, lib, table_problem  # noqa: F401  (force: the fixture)
 from test_gpu_nvfp4_bwd import table_problem as bwd_table_problem
 
@@ -79,7 +88,41 @@ def problem(table, K, N):
     gate_up[p["unc"]] = NAN
     p.update(blocks=blocks, scales=scales, gs=gs, x=x, tpe=tpe, offs=offs, gy=b["args"][3], ref_bwd=b["ref"],
              gate_up=gate_up.to(DEV), ref_glu=ref_glu)
+    p.update(lora_operands(p, table))
     return p
+
+
+def lora_operands(p, table):
+    """The adapter operands of one case (a generator of their own) on the device and the float64 references ``ref_lora`` /
+    ``ref_lora_b`` [T, N] and ``ref_lora_bwd`` [T, K]: acc * g_e + the adapter term (+ bias), zero outside every clipped
+    range, with the exactness condition of the module docstring asserted."""
+    T, E, K, N, r = p["T"], p["E"], p["K"], p["N"], LORA_RANK[p["K"]]
+    ga = torch.Generator().manual_seed(7919 * T + K + N + 500009 + len(table))
+    v, dv = torch.randint(-4, 5, (T, r), generator=ga).float(), torch.randint(-4, 5, (T, r), generator=ga).float()
+    B, A = torch.randint(-2, 3, (E, N, r), generator=ga).float(), torch.randint(-2, 3, (E, r, K), generator=ga).float()
+    x, gy, gs, bias = p["x"].cpu().double(), p["gy"].cpu().double(), p["gs"].cpu().double(), p["bias"].cpu().double()
+    assert all(float(a) != float(b) for a, b in zip(gs[:-1], gs[1:]))                # neighbours differ
+    assert torch.equal(torch.log2(gs), torch.log2(gs).round())                       # powers of two
+    ref, ref_b, ref_bwd = (torch.zeros(T, N, dtype=torch.float64), torch.zeros(T, N, dtype=torch.float64),
+                           torch.zeros(T, K, dtype=torch.float64))
+    moved = moved_bwd = False
+    for e, (lo, hi) in enumerate(p["ranges"]):
+        if hi <= lo:
+            continue
+        W, g, limit = p["W"][e], float(gs[e]), 2.0 ** 24 * min(float(gs[e]) * 2.0 ** -5, 1.0)
+        add, add_bwd = v[lo:hi].double() @ B[e].double().T, dv[lo:hi].double() @ A[e].double()
+        ref[lo:hi] = (x[lo:hi] @ W.T) * g + add
+        ref_b[lo:hi] = ref[lo:hi] + bias[e]
+        ref_bwd[lo:hi] = (gy[lo:hi] @ W) * g + add_bwd
+        mass = (x[lo:hi].abs() @ W.abs().T) * g + v[lo:hi].double().abs() @ B[e].double().abs().T + bias[e].abs()
+        mass_bwd = (gy[lo:hi].abs() @ W.abs()) * g + dv[lo:hi].double().abs() @ A[e].double().abs()
+        assert float(mass.max()) < limit and float(mass_bwd.max()) < limit
+        moved, moved_bwd = moved or bool(add.count_nonzero()), moved_bwd or bool(add_bwd.count_nonzero())
+    assert bool(torch.isfinite(ref_b).all()) and bool(torch.isfinite(ref_bwd).all())
+    assert bool(p["unc"].all()) or (moved and moved_bwd)                             # (the adapter matters)
+    v[p["unc"]] = NAN
+    dv[p["unc"]] = NAN
+    return dict(r=r, v=v.to(DEV), dv=dv.to(DEV), B=B.to(DEV), A=A.to(DEV), ref_lora=ref, ref_lora_b=ref_b, ref_lora_bwd=ref_bwd)
 
 
 def assert_is_reference(p, got, ref, what):
@@ -195,7 +238,57 @@ def test_grouped_backward_equals_one_expert_calls(table, K, N):
     check_grouped_is_one_expert_calls(p, backward, p["gy"], "bwd")
 
 
-# ---- 5. a decode step of a 128-expert model under the library's own threshold
+# ---- 5. the fused adapter entries: v[t] and B[e] / A[e] beside the base kernels' own indexing
+
+@pytest.mark.parametrize("table,K,N", CASES, ids=CASE_IDS)
+def test_lora_forward_and_backward_are_the_float64_reference(table, K, N):
+    """ops.moe_forward_nvfp4_lora (with and without bias) and ops.moe_backward_input_nvfp4_lora on the exact operands, from
+    float32 and bfloat16 rows, a float32 and a bfloat16 result: the float32 result is the float64 reference bit for bit, a
+    bfloat16 result one rounding of it, uncovered rows are zero bits although their x, dY, v and dv are NaN, and the table
+    tensors are unchanged.  The global scale differs between neighbouring experts and scales the weight term only."""
+    p = problem(table, K, N)
+    w, t = (p["blocks"], p["scales"], p["gs"]), (p["tpe"], p["offs"])
+    for din in (torch.float32, torch.bfloat16):
+        for dout in (torch.float32, torch.bfloat16):
+            for bias in (False, True):
+                got = ops().moe_forward_nvfp4_lora(*w, p["x"].to(din), p["v"], p["B"], *t, bias=p["bias"] if bias else None,
+                                                   out_dtype=dout)
+                assert got.dtype == dout
+                assert_is_reference(p, got, p["ref_lora_b"] if bias else p["ref_lora"], (table, "lora fwd", din, bias, dout))
+            got = ops().moe_backward_input_nvfp4_lora(*w, p["gy"].to(din), p["dv"], p["A"], *t, out_dtype=dout)
+            assert got.dtype == dout
+            assert_is_reference(p, got, p["ref_lora_bwd"], (table, "lora bwd", din, dout))
+
+
+@pytest.mark.parametrize("table,K,N", CASES, ids=CASE_IDS)
+def test_lora_grouped_equals_one_expert_calls(table, K, N):
+    """The three adapter entries (the gated one on the Gaussian gate | up rows, swiglu_clamp): the grouped call has the bits
+    of one call per expert on that expert's clipped slice of the rows and of v / dv with that expert's B / A and global
+    scale, scattered into zeros."""
+    p = problem(table, K, N)
+    o = ops()
+    entries = [("fwd", "x", "v", "B", lambda w, r, v, m, t, bias: o.moe_forward_nvfp4_lora(*w, r, v, m, *t, bias=bias,
+                                                                                        out_dtype=torch.float32)),
+               ("gated", "gate_up", "v", "B", lambda w, r, v, m, t, bias: o.moe_gated_forward_nvfp4_lora(
+                   *w, r, v, m, *t, bias=bias, out_dtype=torch.float32, **act_kw(KIND))),
+               ("bwd", "gy", "dv", "A", lambda w, r, v, m, t, bias: o.moe_backward_input_nvfp4_lora(*w, r, v, m, *t))]
+    for name, rows, vk, mk, op in entries:
+        got = op((p["blocks"], p["scales"], p["gs"]), p[rows], p[vk], p[mk], (p["tpe"], p["offs"]), p["bias"])
+        assert table_intact(p), name
+        assert got.dtype == torch.float32 and got.shape == (p["T"], K if name == "bwd" else N)
+        want = torch.zeros_like(got)
+        for e, (lo, hi) in enumerate(p["ranges"]):
+            if hi > lo:
+                want[lo:hi] = op((p["blocks"][e:e + 1], p["scales"][e:e + 1], p["gs"][e:e + 1]), p[rows][lo:hi].contiguous(),
+                                 p[vk][lo:hi].contiguous(), p[mk][e:e + 1], whole_table(hi - lo), p["bias"][e:e + 1])
+        assert bool(torch.isfinite(want).all()), name                                # (the slices hold no uncovered row)
+        assert same_bits(got, want), (table, name, (bits(got) != bits(want)).nonzero()[:4].tolist())
+        assert uncovered_all_zero_bits(p, got), name
+        if bool((~p["unc"]).any()):
+            assert float(got.abs().max()) > 0
+
+
+# ---- 6. a decode step of a 128-expert model under the library's own threshold
 
 def test_e128_decode_step_under_the_default_dispatch():
     """T = 8 rows over 128 experts with no threshold forced: the library reports the decode kernel, and the checks hold

@@ -14,7 +14,8 @@ either, and checks both: what two overlapping launches must not share (a workspa
 The dense ops.linear_forward_mxfp4 / linear_gated_forward_mxfp4 have no table and therefore no family: their split form
 (a decode launch into a partial-sum workspace, a reduce launch, and the gated pre-pass in front of both) has a test of its
 own at the end, on one side stream and on two at once; so do the dense ops.linear_forward_nvfp4 /
-linear_gated_forward_nvfp4 (the grouped launchers with one expert; the gated entry's pre-pass in front of the GEMM)."""
+linear_gated_forward_nvfp4 (the grouped launchers with one expert; the gated entry's pre-pass in front of the GEMM) and
+the dense adapter entries ops.linear_forward_nvfp4_lora / linear_backward_input_nvfp4_lora."""
 import pytest
 import torch
 
@@ -28,9 +29,11 @@ CASES = ["int4-small-T232-bf16", "int4-stream-T1600-f32", "int4-small-T100-fast"
          "mx4-K288-N136-tile", "mx4-K288-N136-decode", "mx4-K96-N37-fp8", "mx4-K96-N37-fp4", "mx4-K288-N136-glu-decode",
          "mx4-K288-N136-bwd", "mx4-K288-N136-fp6-tile", "mx4-K96-N37-fp6-glu-decode", "mx4-K288-N136-fp8-decode",
          "mx4-K96-N37-fp4-decode", "mx4-lora-fwd-K288-N136-r16", "mx4-lora-glu-K96-N37-r64", "mx4-lora-bwd-K288-N136-r16",
-         "nv4-K288-N136-tile", "nv4-K96-N37-decode", "nv4-K608-N37-decode", "nv4-K288-N136-glu-decode", "nv4-K96-N37-bwd"]
+         "nv4-K288-N136-tile", "nv4-K96-N37-decode", "nv4-K608-N37-decode", "nv4-K288-N136-glu-decode", "nv4-K96-N37-bwd",
+         "nv4-lora-fwd-K288-N136-r16", "nv4-lora-glu-K96-N37-r64", "nv4-lora-bwd-K288-N136-r16"]
 TWO_STREAMS = ["int4-small-T100-fast", "int4-two-phase-T100", "group-i8-glu", "mx4-K288-N136-glu-tile", "mx4-K96-N37-fp4",
-               "mx4-lora-glu-K288-N136-r16", "mx4-K288-N136-fp6-decode", "nv4-K288-N136-glu-tile", "nv4-K96-N37-bwd"]
+               "mx4-lora-glu-K288-N136-r16", "mx4-K288-N136-fp6-decode", "nv4-K288-N136-glu-tile", "nv4-K96-N37-bwd",
+               "nv4-lora-glu-K288-N136-r16", "nv4-lora-bwd-K96-N37-r64"]
 
 
 def poisoned_like(t):
@@ -131,24 +134,27 @@ def test_dense_linear_split_form_on_side_streams(tune, name):
     dense_on_side_streams(call, make_rows)
 
 
-@pytest.mark.parametrize("gated", [False, True], ids=["plain", "gated"])
-def test_dense_nvfp4_linear_on_side_streams(gated):
-    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 (test_gpu_graph_replay.nv4_linear_case: K = 96, N = 37, T = 5)
-    as the MXFP4 dense ops above: one side stream with poisoned input buffers, then two at once with different rows (the
-    gated entry: a workspace per stream)."""
-    call, make_rows, _, _ = nv4_linear_case(gated)
+@pytest.mark.parametrize("kind", ["plain", "gated", "lora-fwd", "lora-bwd"])
+def test_dense_nvfp4_linear_on_side_streams(kind):
+    """ops.linear_forward_nvfp4 / linear_gated_forward_nvfp4 and the adapter entries ops.linear_forward_nvfp4_lora /
+    linear_backward_input_nvfp4_lora (test_gpu_graph_replay.nv4_linear_case: K = 96, N = 37, T = 5) as the MXFP4 dense ops
+    above: one side stream with poisoned input buffers, then two at once with different rows (the gated entry: a workspace
+    per stream)."""
+    call, make_rows, _, _ = nv4_linear_case(kind)
     dense_on_side_streams(call, make_rows)
 
 
 def dense_on_side_streams(call, make_rows):
-    a, b = make_rows(1), make_rows(2)
-    want_a, want_b = call(a.clone()), call(b.clone())
+    """``make_rows(seed)``: one tensor or the tuple of the call's row tensors."""
+    as_list = lambda rows: list(rows) if isinstance(rows, tuple) else [rows]
+    a, b = as_list(make_rows(1)), as_list(make_rows(2))
+    want_a, want_b = call(*[t.clone() for t in a]), call(*[t.clone() for t in b])
     assert float(want_a.abs().max()) > 0 and not same_bits(want_a, want_b)
     for _ in range(2):
         busy = busy_matrix()
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
-        got, keep, busy = enqueue(call, [a], side, busy)
+        got, keep, busy = enqueue(call, a, side, busy)
         torch.cuda.current_stream().wait_stream(side)
         assert same_bits(got, want_a), first_diff(got, want_a)
         torch.cuda.synchronize()
@@ -156,8 +162,8 @@ def dense_on_side_streams(call, make_rows):
     busy_a, busy_b = busy_matrix(), busy_matrix()
     torch.cuda.synchronize()
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
-    got_a, keep_a, busy_a = enqueue(call, [a], sa, busy_a)
-    got_b, keep_b, busy_b = enqueue(call, [b], sb, busy_b)
+    got_a, keep_a, busy_a = enqueue(call, a, sa, busy_a)
+    got_b, keep_b, busy_b = enqueue(call, b, sb, busy_b)
     torch.cuda.current_stream().wait_stream(sa)
     torch.cuda.current_stream().wait_stream(sb)
     assert same_bits(got_a, want_a), ("a", first_diff(got_a, want_a))
