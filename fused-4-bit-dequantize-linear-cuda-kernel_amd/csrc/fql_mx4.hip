@@ -5,7 +5,8 @@
 // fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
 // fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
 // linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
-// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h)
+// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h),
+// the split-K decode form of the dense NVFP4 entries fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd (fql_gemm_nvfp4_linear.h),
 // with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
@@ -20,6 +21,7 @@
 #include "fql_mx4_quant.h"
 #include "fql_gemm_nvfp4.h"
 #include "fql_gemm_nvfp4_bwd.h"
+#include "fql_gemm_nvfp4_linear.h"
 
 #include <cmath>
 
@@ -388,6 +390,92 @@ int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, int 
     const int S = split_k ? mx4_linear_slices(c.T, c.K, c.N) : 1;
     if (S > 1) return launch_mx4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
     return launch_float_rows(in_dtype, out_dtype, c, st);
+}
+
+// ---- the split-K decode form of the dense NVFP4 layer (fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd;
+//      fql_gemm_nvfp4_linear.h) ----
+#define FQL_NVFP4_LINEAR_DECODE_MAX_ROWS 32 /* rows (T) up to which the split form runs: the largest count of the sweep (1, 16, 32, 64) up to which it beats both grouped kernels by more than the windows' ranges at every shape whose S is above 1: at 64 rows 2880 -> 5120 loses at its eight slices */
+#define FQL_NVFP4_LINEAR_MAX_SLICES 16
+#define FQL_NVFP4_LINEAR_FILL_WAVES 720     /* the waves S(K, N) asks for: MXFP4's 640 gives 2880 -> 5120 four slices where eight win at one row; 720 is the largest value that keeps 4096 -> 2880 at eight (the S sweep of the same section) */
+int g_nvfp4_linear_decode_max_rows = FQL_NVFP4_LINEAR_DECODE_MAX_ROWS;
+int g_nvfp4_linear_slices = 0;         // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_nvfp4_linear_slices)
+
+// S(K, N): a pure function of the weights' shape (never of T or the device).  The smallest S of {1, 2, 4, 8, 16} with
+// ceil(N / 32) * S >= FQL_NVFP4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 whole pairs, so that no slice of the
+// policy's is empty.
+int nv4_linear_policy_slices(int K, int N)
+{
+    const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
+    int S = 1;
+    while (S < FQL_NVFP4_LINEAR_MAX_SLICES && waves * S < FQL_NVFP4_LINEAR_FILL_WAVES) S *= 2;
+    const int P = K / 64;
+    while (S > 1 && S > P) S /= 2;
+    return S;
+}
+
+// The slices a call of a split entry runs now: 1 means no split form (the call is the plain entry's).
+int nv4_linear_slices(int T, int K, int N)
+{
+    if (T <= 0 || T > g_nvfp4_linear_decode_max_rows || (T - 1) / Mx4DecodeCfg::BT + 1 > 65535) return 1;
+    return g_nvfp4_linear_slices != 0 ? g_nvfp4_linear_slices : nv4_linear_policy_slices(K, N);
+}
+
+// The partial sums: [16][T][N] float32, sized for the largest S so that the slice hook cannot outgrow it.
+size_t nv4_linear_partial_bytes(int T, int N)
+{
+    if (T <= 0 || N <= 0 || T > g_nvfp4_linear_decode_max_rows) return 0;
+    return (size_t)FQL_NVFP4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
+}
+
+// The two launches: the sliced decode kernel into partial [S][T][N], then the reduce kernel.
+int launch_nv4_linear_split(int in_dtype, int out_dtype, const Mx4Call &c, int S, float *partial, hipStream_t st)
+{
+    using D = Mx4DecodeCfg;
+    using R = Nv4LinearReduceCfg;
+    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
+    const int rc = with_in_dtype(in_dtype, [&](auto in) {
+        return launch(nv4_linear_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.blocks, c.scales, c.rows, partial,
+                      c.T, c.K, c.N);
+    });
+    if (rc != FQL_OK) return rc;
+    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
+    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
+    return with_out_dtype(out_dtype, [&](auto o) {
+        constexpr int OUT = decltype(o)::value;
+        auto go = [&](auto s) {
+            return launch(nv4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.gscale, c.bias,
+                          c.out, c.T, c.N);
+        };
+        switch (S) {
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 4: return go(std::integral_constant<int, 4>{});
+        case 8: return go(std::integral_constant<int, 8>{});
+        default: return go(std::integral_constant<int, 16>{});
+        }
+    });
+}
+
+// Both split entries: mx4_linear_fwd's checks in its order (the workspace last, everything before any HIP call), the
+// pre-pass of a gated call, then the split form where it applies and the plain entry's launch everywhere else.
+int nv4_linear_split_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, void *workspace, size_t workspace_bytes, void *stream)
+{
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, a.ok(), &empty);
+    if (rc != FQL_OK || empty) return rc;
+    const size_t h_bytes = mx4_linear_h_bytes(c.T, c.K, a.gated);
+    const size_t need = h_bytes + nv4_linear_partial_bytes(c.T, c.N);
+    if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    if (a.gated) {
+        const int lrc = launch_mx4_quant<ROWS_FLOAT>(c.rows, in_dtype, a, ws, nullptr, c.T, c.K, st);
+        if (lrc != FQL_OK) return lrc;
+        c.rows = ws;
+        in_dtype = FQL_DTYPE_BF16;
+    }
+    const int S = nv4_linear_slices(c.T, c.K, c.N);
+    if (S > 1) return launch_nv4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
+    return launch_nvfp4(in_dtype, out_dtype, c, st);
 }
 
 }  // namespace
@@ -793,6 +881,48 @@ FQL_API int fql_tune_nvfp4_kernel(int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
     return nvfp4_use_decode(T) ? 1 : 0;
+}
+
+FQL_API size_t fql_linear_nvfp4_split_workspace_bytes(int T, int K, int N, int gated)
+{
+    return mx4_linear_h_bytes(T, K, gated) + nv4_linear_partial_bytes(T, N);   // h [T][K] bfloat16 | partial [16][T][N] float32
+}
+
+FQL_API int fql_linear_nvfp4_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                       int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N,
+                                       void *workspace, size_t workspace_bytes, void *stream)
+{
+    return nv4_linear_split_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
+                                in_dtype, out_dtype, kMx4Plain, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_linear_nvfp4_glu_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                           const void *gate_up, int in_dtype, const float *bias, void *out, int out_dtype, int T,
+                                           int K, int N, int activation, float act_alpha, float act_limit, void *workspace,
+                                           size_t workspace_bytes, void *stream)
+{
+    return nv4_linear_split_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
+                                in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_tune_set_nvfp4_linear_decode_max_rows(int rows)
+{
+    const int old = g_nvfp4_linear_decode_max_rows;
+    if (rows >= 0) g_nvfp4_linear_decode_max_rows = rows;
+    return old;
+}
+
+FQL_API int fql_tune_set_nvfp4_linear_slices(int slices)
+{
+    const int old = g_nvfp4_linear_slices;
+    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_nvfp4_linear_slices = slices;
+    return old;
+}
+
+FQL_API int fql_tune_nvfp4_linear_kernel(int T, int K, int N)
+{
+    const int S = nv4_linear_slices(T, K, N);
+    return (S << 8) | (S > 1 ? 2 : nvfp4_use_decode(T) ? 1 : 0);
 }
 
 FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows)

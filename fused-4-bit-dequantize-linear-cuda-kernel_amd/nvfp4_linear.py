@@ -35,21 +35,26 @@ class NVFP4Linear(nn.Module):
 
     On the GPU the forward is ``ops.linear_forward_nvfp4``: inputs float32 (rounded once to bfloat16) or bfloat16 (float16
     is refused), ``W`` without the global scale exact in bfloat16, float32 sums, then ``* global_scale``, then ``+ bias``,
-    two float32 steps, and the result in the inputs' type.  It is bit for bit ``ops.moe_forward_nvfp4`` on one expert;
-    there is no split-K form.  On the CPU the forward is the definition,
+    two float32 steps, and the result in the inputs' type.  It is bit for bit ``ops.moe_forward_nvfp4`` on one expert.
+    ``split_k=True`` passes ``split_k`` to the op: a small batch then runs the split-K decode form.
+    With it a row's bits depend on its own row, the weights, K and N, not on T or the row's position, and are run-to-run
+    identical; they are not the tile kernel's bit pattern, so a row's bits may change as T crosses the library's
+    threshold.  On the CPU the forward is the definition,
     ``(bf16(x) @ dequantize_nvfp4(blocks, scales).T) * global_scale (+ bias)`` in float32.
 
     ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
     ``RuntimeError``.  ``input_grad=True`` gives ``x.grad`` through ``ops.linear_backward_input_nvfp4`` (on the GPU only),
-    straight-through across the bfloat16 rounding of ``x``.  It is configuration, not state: the
-    state-dict keys are ``blocks``, ``scales``, ``global_scale`` (and ``bias``)."""
+    straight-through across the bfloat16 rounding of ``x``; ``split_k`` does not change the
+    backward.  Both are configuration, not state: the state-dict keys are ``blocks``, ``scales``, ``global_scale`` (and
+    ``bias``)."""
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = False, input_grad: bool = False):
+    def __init__(self, in_features: int, out_features: int, bias: bool = False, input_grad: bool = False, split_k: bool = False):
         super().__init__()
         if in_features <= 0 or in_features % 32 != 0 or out_features <= 0:
             raise ValueError("in_features must be a positive multiple of 32 and out_features positive")
         self.in_features, self.out_features = in_features, out_features
         self.input_grad = bool(input_grad)
+        self.split_k = bool(split_k)
         self.register_buffer("blocks", torch.zeros(out_features, in_features // 2, dtype=torch.uint8))
         self.register_buffer("scales", torch.full((out_features, in_features // 16), 0x38, dtype=torch.uint8))
         self.register_buffer("global_scale", torch.ones(1, dtype=torch.float32))
@@ -62,7 +67,7 @@ class NVFP4Linear(nn.Module):
     def from_nvfp4(cls, blocks, scales, global_scale=None, bias=None, **kwargs) -> "NVFP4Linear":
         """The checkpoint's tensors as they are: ``blocks`` uint8 [N, K/2], ``scales`` uint8 [N, K/16] (a
         ``float8_e4m3fn`` tensor is viewed as its bytes), ``global_scale`` one float32 value or None for 1, ``bias`` [N]
-        or None.  ``kwargs``: ``input_grad``."""
+        or None.  ``kwargs``: ``input_grad``, ``split_k``."""
         if scales.dtype == torch.float8_e4m3fn:
             scales = scales.view(torch.uint8)
         if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
@@ -87,14 +92,15 @@ class NVFP4Linear(nn.Module):
     @classmethod
     def from_linear(cls, linear: nn.Linear, **kwargs) -> "NVFP4Linear":
         """Quantise an ``nn.Linear`` with ``quantize.quantize_nvfp4``; its bias is kept (float32).  ``kwargs``:
-        ``input_grad``."""
+        ``input_grad``, ``split_k``."""
         from .quantize import quantize_nvfp4
         blocks, scales, gs = quantize_nvfp4(linear.weight.detach().float())
         return cls.from_nvfp4(blocks, scales, gs, bias=None if linear.bias is None else linear.bias.detach(), **kwargs)
 
     def _rows(self, x2):
         from . import ops
-        return ops.linear_forward_nvfp4(self.blocks, self.scales, self.global_scale, x2, bias=self.bias, out_dtype=x2.dtype)
+        return ops.linear_forward_nvfp4(self.blocks, self.scales, self.global_scale, x2, bias=self.bias, out_dtype=x2.dtype,
+                                        split_k=self.split_k)
 
     def forward(self, x):
         if x.dtype not in (torch.float32, torch.bfloat16):
@@ -122,7 +128,7 @@ class NVFP4Linear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=nvfp4"
-                + (", input_grad=True" if self.input_grad else ""))
+                + (", input_grad=True" if self.input_grad else "") + (", split_k=True" if self.split_k else ""))
 
 
 class LoRANVFP4Linear(NVFP4Linear):

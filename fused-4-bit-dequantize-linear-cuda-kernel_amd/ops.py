@@ -723,12 +723,13 @@ def _nvfp4_lora_operands(name, lora, T, w_shape):
 
 
 def _nvfp4_launch(name, blocks, scales, global_scale, rows, cols, tokens_per_expert, input_offsets, bias, out_dtype, gated,
-                  act=(), dense=False, lora=None):
+                  act=(), dense=False, lora=None, split_k=False):
     """The four NVFP4 ops and, with ``lora`` = (v [T, r], lora_B [E, N, r] / dense [N, r]), their adapter forms (the ``_lora``
     entries: always the tile kernel; there is no gated dense one).  ``rows`` [T, cols(K)] float32 / bfloat16; grouped: ``blocks`` [E, N, K/2], ``scales`` [E, N, K/16],
     ``global_scale`` float32 [E] or None, ``bias`` [E, N]; ``dense``: ``blocks`` [N, K/2], ``scales`` [N, K/16],
-    ``global_scale`` float32 with one element or None, ``bias`` [N], no table.  Types and shapes first, then the devices:
-    the argument errors read the same without a GPU."""
+    ``global_scale`` float32 with one element or None, ``bias`` [N], no table; ``split_k`` (dense, no adapter): the split
+    entries (``fql_linear_nvfp4_split_fwd`` / ``_glu_split_fwd``).  Types and shapes first, then the devices: the argument
+    errors read the same without a GPU."""
     if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: the rows must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
                            "it to bfloat16 would lose three bits; cast it yourself)")
@@ -769,9 +770,12 @@ def _nvfp4_launch(name, blocks, scales, global_scale, rows, cols, tokens_per_exp
     gs = None if global_scale is None else global_scale.contiguous()
     b = None if bias is None else bias.contiguous()
     if dense:
+        if split_k and lora is None:
+            tag = "_split"
+        ws_bytes = (L.fql_linear_nvfp4_split_workspace_bytes if tag == "_split" else L.fql_linear_nvfp4_workspace_bytes)(T, K, N, int(gated))
         _launch(f"fql_linear_nvfp4_glu{tag}_fwd" if gated else f"fql_linear_nvfp4{tag}_fwd", dev, blocks.contiguous(),
                 scales.contiguous(), gs, rows.contiguous(), _DTYPES[rows.dtype], *extra, b, out, _DTYPES[out_dtype], T, K, N, *act,
-                ws_bytes=L.fql_linear_nvfp4_workspace_bytes(T, K, N, int(gated)))
+                ws_bytes=ws_bytes)
         return out
     tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)   # (none: one expert, all rows)
     _launch(f"fql_moe_nvfp4_glu{tag}_fwd" if gated else f"fql_moe_nvfp4{tag}_fwd", dev, blocks.contiguous(), scales.contiguous(), gs,
@@ -809,25 +813,34 @@ def moe_gated_forward_nvfp4(blocks, scales_e4m3, global_scale, gate_up, tokens_p
                          tokens_per_expert, input_offsets, bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit))
 
 
-def linear_forward_nvfp4(blocks, scales_e4m3, global_scale, x, bias=None, out_dtype=None):
+def linear_forward_nvfp4(blocks, scales_e4m3, global_scale, x, bias=None, out_dtype=None, split_k=False):
     """A dense linear layer on NVFP4 weights: ``out[t] = (W @ bf16(x[t])) * global_scale (+ bias)``.  ``blocks`` uint8
     [N, K/2], ``scales_e4m3`` uint8 [N, K/16], ``global_scale`` float32 with one element or None, ``bias`` [N] float32.
-    Exactly ``moe_forward_nvfp4`` on the one-expert view without a table: the same kernels, the same bits.  There is no
-    split-K form."""
+
+    ``split_k=False`` (the default) is exactly ``moe_forward_nvfp4`` on the one-expert view without a table: the same
+    kernels, the same bits.  ``split_k=True`` lets a small batch (T up to the library's threshold, on shapes for which the
+    library's S(K, N) is above 1) run the one-wave decode kernel once per slice of K, S slices side by side, and a second
+    launch sums the float32 partial results in a fixed order, multiplies by ``global_scale`` and adds the bias (two
+    float32 steps, as everywhere).  Every other call with ``split_k=True`` takes the ``split_k=False`` path.  THE
+    CONTRACT with ``split_k``: a row's bits depend on its own row, the weights, K and N; they do not depend on T or on
+    the row's position, and they are run-to-run identical.  They are not the tile kernel's bit pattern (the float32 sums
+    are associated otherwise), so a row's bits may change as T crosses the threshold; both sides are within the float32
+    bound of the exact product.  INTEGRATION.md section 18."""
     _forward_only("linear_forward_nvfp4", x, bias)
     return _nvfp4_launch("linear_forward_nvfp4", blocks, scales_e4m3, global_scale, x, lambda K: K, None, None, bias, out_dtype,
-                         False, dense=True)
+                         False, dense=True, split_k=split_k)
 
 
 def linear_gated_forward_nvfp4(blocks, scales_e4m3, global_scale, gate_up, activation="silu", activation_alpha=1.702,
-                               activation_limit=7.0, bias=None, out_dtype=None):
+                               activation_limit=7.0, bias=None, out_dtype=None, split_k=False):
     """The down projection of a dense gated MLP on NVFP4 weights: ``linear_forward_nvfp4`` on
     ``bf16(act(gate_up[t, :K], gate_up[t, K:]))``, ``gate_up`` [T, 2K], by the streaming pre-pass of
-    ``moe_gated_forward_nvfp4``."""
+    ``moe_gated_forward_nvfp4``, with the same ``split_k`` and its contract: a row's bits depend on its row, the weights,
+    K and N, not on T or the row's position; run-to-run identical; not the tile kernel's bit pattern."""
     _forward_only("linear_gated_forward_nvfp4", gate_up, bias)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     return _nvfp4_launch("linear_gated_forward_nvfp4", blocks, scales_e4m3, global_scale, gate_up, lambda K: 2 * K, None, None,
-                         bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit), dense=True)
+                         bias, out_dtype, True, (_ACTIVATIONS[kind], act_alpha, act_limit), dense=True, split_k=split_k)
 
 
 ROUTE_MAX_EXPERTS = 128

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 450 /* 0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 460 /* 0.4.6: a split-K decode form of the dense NVFP4 linear layer: fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd / fql_linear_nvfp4_split_workspace_bytes.  0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1202,7 +1202,8 @@ FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_
  * fql_moe_nvfp4_glu_fwd: the same on h = bf16(act(gate_up[t][k], gate_up[t][K + k])), gate_up [T][2K], by fql_moe_mx4_glu_fwd's
  *                        pre-pass into the workspace (fql_moe_nvfp4_workspace_bytes(E, T, K, N, 1): h [T][K] bfloat16, its layout).
  * fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd: one matrix blocks [N][K / 2], scales_e4m3 [N][K / 16], global_scale [1] or
- *                        NULL, bias [N], no table: exactly the grouped launchers with E = 1.  There is no split-K form.
+ *                        NULL, bias [N], no table: exactly the grouped launchers with E = 1.  The split-K decode form has
+ *                        entries of its own (fql_linear_nvfp4_split_fwd, FQL_VERSION 460, below).
  *                        Workspace: fql_linear_nvfp4_workspace_bytes(T, K, N, gated).
  *   Two kernels, the 64 x 128 tile and a one-wave decode kernel, return THE SAME BITS for every element; T alone chooses
  *   (T <= FQL_NVFP4_DECODE_MAX_ROWS in csrc/fql_mx4.hip; fql_int4_tune.h: fql_tune_set_nvfp4_decode_max_rows /
@@ -1297,6 +1298,41 @@ FQL_API int fql_linear_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scal
 FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
                                             const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A,
                                             int rank, void *grad_in, int out_dtype, int T, int K, int N, void *stream);
+
+/* ---- a split-K decode form of the dense NVFP4 linear layer (FQL_VERSION 460; INTEGRATION.md section 18, DESIGN.md section 43;
+ *      csrc/fql_gemm_nvfp4_linear.h) ----
+ * fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd take the argument lists of fql_linear_nvfp4_fwd / _glu_fwd.
+ *   The split form applies when 0 < T <= a threshold built into the library (FQL_NVFP4_LINEAR_DECODE_MAX_ROWS in
+ *   csrc/fql_mx4.hip, set from a measurement) and S(K, N) > 1.  S, the number of slices, is a pure function of K and N, one
+ *   of 1, 2, 4, 8, 16, at most max(1, K / 64): never of T, of the device or of any state but the tuning hook.  Every other
+ *   call is exactly fql_linear_nvfp4_fwd / _glu_fwd: the same launchers, the same bits.
+ *   Then the one-wave decode kernel runs once per slice of K (slice s takes the 64-k pairs
+ *   [s * ceil(P / S), min(P, (s + 1) * ceil(P / S))), P = K / 64, in ascending order on an accumulator that starts at zero;
+ *   the odd piece of K % 64 == 32 is the last slice's) into float32 partial sums in the workspace, and a second launch on
+ *   the same stream computes
+ *       out[t][n] = round_OUT( fl32( fl32( (((p_0 + p_1) + p_2) + ... + p_{S-1}) * global_scale ) + bias[n] ) )
+ *   in float32, in that order: the multiply, then the add, never an FMA; without a global scale and a bias the result is the
+ *   sum's bits.  No atomics; launches are the only synchronisation; the calls can be captured into a graph.
+ *   THE CONTRACT: a row's result depends on its own row, the weights, K and N.  It does not depend on T or on the row's
+ *   position; it is run-to-run identical, and every T up to the threshold gives the same bits.  It is NOT the tile kernel's
+ *   bit pattern (the float32 sums are associated otherwise), so a row's bits may change as T crosses the threshold; both
+ *   sides are within the float32 bound of DESIGN.md section 25 of the exact product.
+ *   NON-FINITE: fql_moe_nvfp4_fwd's rules (a slice whose part of a row is non-finite stores NaN for the whole partial row,
+ *   a NaN scale byte is a NaN weight block, and the sum carries both).
+ *   Workspace: fql_linear_nvfp4_split_workspace_bytes(T, K, N, gated), 16-byte aligned: the [T][K] bfloat16 h of a gated call
+ *   (fql_moe_nvfp4_workspace_bytes' layout), then, for 0 < T <= the threshold, 16 * T * N float32 of partial sums (sized for
+ *   the largest S whatever S(K, N) is).  0 bytes when neither applies; then workspace may be NULL.
+ *   Return codes: fql_linear_nvfp4_fwd's, in its order (mx4_check's with E = 1), FQL_ERR_WORKSPACE last, all before any HIP
+ *   call; then FQL_ERR_LAUNCH.  fql_int4_tune.h: fql_tune_set_nvfp4_linear_decode_max_rows, fql_tune_set_nvfp4_linear_slices
+ *   and fql_tune_nvfp4_linear_kernel force and report the choice (tools and tests). */
+FQL_API size_t fql_linear_nvfp4_split_workspace_bytes(int T, int K, int N, int gated);
+FQL_API int fql_linear_nvfp4_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
+                                       int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+FQL_API int fql_linear_nvfp4_glu_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
+                                           const void *gate_up, int in_dtype, const float *bias, void *out, int out_dtype, int T,
+                                           int K, int N, int activation, float act_alpha, float act_limit, void *workspace,
+                                           size_t workspace_bytes, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

@@ -25,7 +25,8 @@ and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision=
 ``linear_forward_mxfp4`` and ``linear_gated_forward_mxfp4`` with the tile kernel, the grouped decode kernel and the split
 form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``; then the NVFP4 forward ops, decode and
 tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands, and last the five NVFP4 adapter
-ops (``moe_forward_nvfp4_lora`` and its kin) on them."""
+ops (``moe_forward_nvfp4_lora`` and its kin) on them, and the two dense NVFP4 ops with ``split_k=True`` at 2 and at 16 forced
+slices."""
 import argparse
 import hashlib
 import os
@@ -533,6 +534,29 @@ def calls(dev, fq, ops):
             yield f"linear_backward_input_nvfp4_lora {dt}->{do}", lambda: ops.linear_backward_input_nvfp4_lora(
                 Pm[0], Sn[0], Gn[:1], gy[:16].to(dt), dvn[:16].contiguous(), An[0], out_dtype=do)
         yield f"moe_forward_nvfp4_lora no global {dt}", lambda: ops.moe_forward_nvfp4_lora(Pm, Sn, None, x.to(dt), vn, Bn, tpe, offs)
+
+    # the split-K decode form of the two dense NVFP4 ops, behind everything above (no new random draws): 2 and 16 slices
+    # forced in turn (K = 96 is one pair and the odd piece, so most of the 16 have nothing to do)
+    def forced_split(slices, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = lib.fql_tune_set_nvfp4_linear_decode_max_rows(64), lib.fql_tune_set_nvfp4_linear_slices(slices)
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_nvfp4_linear_decode_max_rows(old[0])
+                lib.fql_tune_set_nvfp4_linear_slices(old[1])
+        return run
+
+    for slices in (2, 16):
+        for btag, b in (("", None), (" bias", biasm[0])):
+            for dt in (F32, BF16):
+                tag = f"{dt}{btag} split S={slices}"
+                yield f"linear_forward_nvfp4 {tag}", forced_split(slices, lambda: ops.linear_forward_nvfp4(
+                    Pm[0], Sn[0], Gn[:1], x[:16].to(dt), bias=b, split_k=True))
+                yield f"linear_gated_forward_nvfp4 {tag}", forced_split(slices, lambda: ops.linear_gated_forward_nvfp4(
+                    Pm[0], Sn[0], Gn[:1], gu[:16].to(dt), bias=b, split_k=True, **glu))
 
 
 def digest(t):
