@@ -7,7 +7,8 @@
 // linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
 // fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h),
 // the split-K decode form of the dense NVFP4 entries fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd (fql_gemm_nvfp4_linear.h),
-// with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels),
+// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -22,6 +23,8 @@
 #include "fql_gemm_nvfp4.h"
 #include "fql_gemm_nvfp4_bwd.h"
 #include "fql_gemm_nvfp4_linear.h"
+#include "fql_gemm_lut4.h"
+#include "fql_gemm_lut4_bwd.h"
 
 #include <cmath>
 
@@ -478,6 +481,42 @@ int nv4_linear_split_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a
     return launch_nvfp4(in_dtype, out_dtype, c, st);
 }
 
+// ---- 4-bit code-book weights, dense (fql_linear_lut4_fwd / fql_linear_lut4_bwd_input; fql_gemm_lut4.h, fql_gemm_lut4_bwd.h,
+//      DESIGN.md section 44) ----
+struct Lut4Call {
+    const uint8_t *codes;
+    const float *absmax, *book;        // book: [16] or NULL (the NF4 table)
+    int block;
+    const void *rows;                  // inputs [T][K] (forward) or grad_out [T][N] (input gradient)
+    const float *bias;
+    void *out;                         // out [T][N] or grad_in [T][K]
+    int T, K, N;
+};
+
+// mx4_check's order for one dense matrix: shapes, the row and result types, the empty call, NULL pointers, the grid, then
+// alignment.  bt: the row tile of the kernel that will run; `bwd`: N == 0 is not empty (grad_in is zeros; nothing but the
+// result is dereferenced then).  *bshift = log2(block).
+int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd, bool *empty, int *bshift)
+{
+    *empty = false;
+    if (c.T < 0 || c.K <= 0 || c.N < 0) return FQL_ERR_BAD_SHAPE;
+    if (c.K & 1) return FQL_ERR_ODD_K;
+    if (c.K % 64 != 0) return FQL_ERR_BAD_SHAPE;
+    if (c.block < 64 || (c.block & (c.block - 1)) != 0 || c.K % c.block != 0) return FQL_ERR_BAD_SHAPE;
+    if ((in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (c.T == 0 || (c.N == 0 && !bwd)) { *empty = true; return FQL_OK; }
+    if (!c.out || (c.N != 0 && (!c.codes || !c.absmax || !c.rows))) return FQL_ERR_NULL_POINTER;
+    if ((c.T + bt - 1) / bt > 65535) return FQL_ERR_BAD_SHAPE;
+    const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
+    if (!aligned16(c.codes) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
+        (reinterpret_cast<uintptr_t>(c.bias) & 3) || (reinterpret_cast<uintptr_t>(c.absmax) & 3) ||
+        (reinterpret_cast<uintptr_t>(c.book) & 3)) return FQL_ERR_ALIGNMENT;
+    int s = 6;
+    while ((1 << s) < c.block) ++s;
+    *bshift = s;
+    return FQL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -868,6 +907,43 @@ FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t
 {
     return fql_moe_nvfp4_lora_bwd_input(blocks, scales_e4m3, global_scale, grad_out, in_dtype, lora_rows, lora_A, rank, nullptr,
                                         nullptr, grad_in, out_dtype, 1, T, K, N, stream);
+}
+
+FQL_API int fql_linear_lut4_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N, void *stream)
+{
+    using C = Lut4Cfg;
+    const Lut4Call c{codes, absmax, code_book, block, inputs, bias, out, T, K, N};
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, false, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    const dim3 grid((N + C::BN - 1) / C::BN, (T + C::BT - 1) / C::BT);
+    return with_in_dtype(in_dtype, [&](auto in) {
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(lut4_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, static_cast<hipStream_t>(stream),
+                          c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N);
+        });
+    });
+}
+
+FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
+                                      const void *grad_out, int in_dtype, void *grad_in, int out_dtype, int T, int K, int N,
+                                      void *stream)
+{
+    using C = Mx4BwdCfg;
+    const Lut4Call c{codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N};
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    const dim3 grid((K + C::BK - 1) / C::BK, (T + C::BT - 1) / C::BT);   // (N == 0: no stage exists, every tile stores zeros)
+    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, static_cast<hipStream_t>(stream),
+                          c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N);
+        });
+    });
 }
 
 FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows)

@@ -2766,3 +2766,120 @@ class _NVFP4LinearLoRAFn(torch.autograd.Function):
             if need_x:
                 gx = linear_backward_input_nvfp4_lora(blocks, scales, gs, g, dv, lora_A, out_dtype=x2.dtype)   # dX = dY W g + dv A
         return gx, gA, gB, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4-bit code-book weights ("LUT4"; NF4 of bitsandbytes / QLoRA), dense (csrc/fql_gemm_lut4.h, csrc/fql_gemm_lut4_bwd.h;
+# DESIGN.md section 44)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias, out_dtype, default_dtype):
+    """Both code-book ops, section 14's order: types and shapes first, then the devices.  ``rows`` [T, cols(K, N)] float32 /
+    bfloat16; the result is [T, K + N - cols(K, N)]."""
+    what = "the rows" if bias is not False else "grad_out"
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: {what} must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or absmax.dtype != torch.float32 or absmax.dim() != 2:
+        raise RuntimeError("codes must be uint8 [N, K/2] and absmax float32 [N, K/block]")
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    if not isinstance(block, int) or block < 64 or block & (block - 1) or K % 64 != 0 or K % block != 0:
+        raise RuntimeError("block must be a power of two of at least 64 with K % block == 0, and K % 64 == 0")
+    if tuple(absmax.shape) != (N, K // block):
+        raise RuntimeError(f"absmax must be float32 [N, K/block] = [{N}, {K // block}] for codes {list(codes.shape)}")
+    if rows.shape[1] != cols(K, N):
+        raise RuntimeError(f"ops.{name}: {what} must have {cols(K, N)} columns for codes {list(codes.shape)}")
+    if code_book is not None and (not isinstance(code_book, torch.Tensor) or code_book.dtype != torch.float32
+                                  or tuple(code_book.shape) != (16,)):
+        raise RuntimeError("code_book must be a float32 [16] tensor, or None for the NF4 table")
+    if bias is not None and bias is not False and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,)):
+        raise RuntimeError("bias must be a float32 [N] tensor")
+    out_dtype = default_dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not rows.is_cuda:
+        raise RuntimeError(f"ops.{name}: {what} must be a CUDA tensor")
+    dev = rows.device
+    _on(dev, codes=codes, absmax=absmax, code_book=code_book, bias=None if bias is False else bias)
+    T = rows.shape[0]
+    out = torch.empty((T, K + N - cols(K, N)), dtype=out_dtype, device=dev)
+    book = None if code_book is None else code_book.contiguous()
+    b = () if bias is False else (None if bias is None else bias.contiguous(),)
+    _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *b, out,
+            _DTYPES[out_dtype], T, K, N)
+    return out
+
+
+def linear_forward_lut4(codes, absmax, x, code_book=None, block=64, bias=None, out_dtype=None):
+    """A dense linear layer on 4-bit code-book weights in bitsandbytes' encoding (NF4 by default):
+    ``out[t] = W @ bf16(x[t]) (+ bias)``, ``W[n, k] = bf16(fl32(code_book[c(n, k)] * absmax[n, k // block]))``.  ``codes`` uint8
+    [N, K/2], input ``2i`` in the HIGH nibble of byte ``i`` (the opposite of this library's other 4-bit buffers);
+    ``absmax`` float32 [N, K/block], ``block`` a power of two >= 64 dividing K, K % 64 == 0; ``code_book`` float32 [16] or
+    None for ``quantize.NF4_CODE_BOOK``; ``bias`` float32 [N].  ``x`` [T, K] float32 (rounded once to bfloat16) or bfloat16.
+    The weight's one rounding to bfloat16 is part of the definition (it is ``dequantize_4bit`` to bfloat16); the sums are
+    float32 on the bfloat16 matrix cores, then the bias, then one rounding to ``out_dtype`` (default: ``x``'s type).  A
+    non-finite element of a row makes that row of the result NaN.  Forward only."""
+    _forward_only("linear_forward_lut4", x, bias)
+    return _lut4_launch("linear_forward_lut4", "fql_linear_lut4_fwd", codes, absmax, x, lambda K, N: K, code_book, block, bias,
+                        out_dtype, x.dtype if isinstance(x, torch.Tensor) else None)
+
+
+def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64, out_dtype=None):
+    """``grad_in[t] = bf16(grad_out[t]) @ W`` on the operands of ``linear_forward_lut4`` (no transposed copy): ``grad_out``
+    [T, N] float32 (rounded once to bfloat16) or bfloat16 -> [T, K] ``out_dtype`` (default float32), float32 sums over
+    ascending n, run-to-run identical."""
+    return _lut4_launch("linear_backward_input_lut4", "fql_linear_lut4_bwd_input", codes, absmax, grad_out, lambda K, N: N,
+                        code_book, block, False, out_dtype, torch.float32)
+
+
+def _lut4_lora_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bias):
+    """Base forward to float32, u = x A^T, then y = base + scaling * u B^T in x's type, one rounding.  Returns (y, u)."""
+    y32 = linear_forward_lut4(codes, absmax, x2, book, block, bias=bias, out_dtype=torch.float32)
+    u = lora_shrink(x2, lora_A, "rc")
+    return _expand_into(u, lora_B, "cr", y32, x2.dtype, scale=scaling), u
+
+
+def linear_lora_forward_lut4(x, codes, absmax, lora_A, lora_B, scaling, code_book=None, block=64, bias=None):
+    """``linear_forward_lut4`` plus a low-rank adapter, ``y = W bf16(x) (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``,
+    composed from the two code-book ops and ``lora_shrink`` / ``lora_expand`` / ``lora_grad`` in one autograd node (no
+    fused adapter stage).  ``x`` [T, K] float32 or bfloat16, float32 ``lora_A`` [r, K] and ``lora_B`` [N, r]; the result
+    has ``x``'s type, rounded once.  Differentiable in ``x``, ``lora_A`` and ``lora_B``; the code-book weights and the bias
+    are frozen.  With ``lora_B == 0`` the result is ``linear_forward_lut4``'s bits."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+        raise RuntimeError("ops.linear_lora_forward_lut4: x must be a CUDA float32 or bfloat16 [T, K] tensor")
+    _lora_check_adapters(lora_A, lora_B, x.shape[1], codes.shape[0], None)
+    if _wants_grad(x, lora_A, lora_B):
+        return _LUT4LinearLoRAFn.apply(x, lora_A, lora_B, codes, absmax, code_book, block, bias, float(scaling))
+    return _lut4_lora_apply(x.contiguous(), codes, absmax, code_book, block, lora_A, lora_B, float(scaling), bias)[0]
+
+
+class _LUT4LinearLoRAFn(torch.autograd.Function):
+    """Code-book linear + adapter in one node.  Saves x (in its own type) and u = x A^T ([T, r] float32); nothing
+    dequantised.  A 16-bit dX is written once, by the expand, from the float32 base dX."""
+
+    @staticmethod
+    def forward(ctx, x, lora_A, lora_B, codes, absmax, book, block, bias, scaling):
+        x2 = x.detach().contiguous()
+        y, u = _lut4_lora_apply(x2, codes, absmax, book, block, lora_A.detach(), lora_B.detach(), scaling, bias)
+        ctx.save_for_backward(x2, u, lora_A, lora_B, codes, absmax)
+        ctx.book, ctx.block, ctx.scaling = book, block, scaling
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, u, lora_A, lora_B, codes, absmax = ctx.saved_tensors
+        need_x, need_A, need_B = ctx.needs_input_grad[:3]
+        check_activation_rows(gy, "the incoming gradient", x2.dtype)
+        g = gy.contiguous()
+        gx = gA = gB = None
+        if need_x or need_A:
+            du = lora_shrink(g, lora_B, "cr", scale=ctx.scaling)                         # du = s dY B
+            if need_x:
+                gx = linear_backward_input_lut4(codes, absmax, g, ctx.book, ctx.block)   # dX = dY W (float32)
+                gx = _expand_into(du, lora_A, "rc", gx, x2.dtype)                        # dX += du A, one rounding
+            if need_A:
+                gA = lora_grad(x2, du, "rc")[0]                                          # dA = du^T x
+        if need_B:
+            gB = lora_grad(g, u, "cr", scale=ctx.scaling)[0]                             # dB = s dY^T u
+        return gx, gA, gB, None, None, None, None, None, None

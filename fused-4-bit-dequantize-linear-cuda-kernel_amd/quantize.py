@@ -302,3 +302,79 @@ def dequantize_mxfp6(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     table = torch.tensor(MXFP6_VALUES, dtype=torch.float32, device=codes.device)
     w = table[unpack_mxfp6(codes).long()].reshape(*codes.shape[:-1], K // MXFP4_BLOCK, MXFP4_BLOCK)
     return (w * mxfp4_scale_values(scales).unsqueeze(-1)).reshape(*codes.shape[:-1], K)
+
+
+# ---- 4-bit code-book weights ("LUT4"): a code is an index into a table of 16 float32 values, one float32 absmax per block
+#      of B consecutive inputs.  NF4 of bitsandbytes (QLoRA, ``load_in_4bit``, the ``*-bnb-4bit`` checkpoints) is the named table.
+
+# the decimal strings bitsandbytes documents, taken as float32
+NF4_CODE_BOOK = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635,
+                 -0.18477343022823334, -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725,
+                 0.24611230194568634, 0.33791524171829224, 0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0)
+LUT4_BLOCK = 64
+
+
+def _lut4_book(code_book, device):
+    book = torch.as_tensor(NF4_CODE_BOOK if code_book is None else code_book, dtype=torch.float32, device=device)
+    if tuple(book.shape) != (16,):
+        raise ValueError("code_book must hold 16 values")
+    return book
+
+
+def _lut4_block(block, K):
+    if block < 64 or block & (block - 1) or K % 64 != 0 or K % block != 0:
+        raise ValueError("block must be a power of two of at least 64 with K % block == 0, and K % 64 == 0")
+
+
+def quantize_lut4(weight: torch.Tensor, code_book=None, block: int = LUT4_BLOCK):
+    """``[N, K]`` -> ``(codes uint8 [N, K/2], absmax float32 [N, K/block])`` in bitsandbytes' encoding: ``absmax`` is the
+    block's largest magnitude, a code is the index of the table entry nearest to ``w / absmax`` (float32), input ``2i`` in
+    the HIGH nibble of byte ``i`` and input ``2i + 1`` in the low one.  A tie goes to the lower code, and an all-zero block
+    divides by 1; equality with bitsandbytes' own quantiser on exact midpoints is not claimed (it searches a tree of rounded
+    thresholds).  ``code_book``: 16 values (default ``NF4_CODE_BOOK``)."""
+    if weight.dim() != 2:
+        raise ValueError("weight must be [N, K]")
+    N, K = weight.shape
+    _lut4_block(block, K)
+    if not bool(torch.isfinite(weight).all()):
+        raise ValueError("quantize_lut4: the weights must be finite")
+    book = _lut4_book(code_book, weight.device)
+    w = weight.detach().to(torch.float32).reshape(N, K // block, block)
+    absmax = w.abs().amax(dim=-1)
+    v = w / torch.where(absmax == 0, torch.ones_like(absmax), absmax).unsqueeze(-1)
+    c = (v.unsqueeze(-1) - book).abs().argmin(dim=-1).to(torch.uint8).reshape(N, K // 2, 2)   # (argmin: the first of equals)
+    return (c[..., 0] << 4) | c[..., 1], absmax
+
+
+quantize_nf4 = quantize_lut4
+
+
+def dequantize_lut4(codes: torch.Tensor, absmax: torch.Tensor, code_book=None, block: int = LUT4_BLOCK) -> torch.Tensor:
+    """``(codes uint8 [N, K/2], absmax float32 [N, K/block])`` -> ``[N, K]`` bfloat16, the definition of the kernels' weight:
+    ``bf16(fl32(code_book[c] * absmax))``, one float32 multiply and one rounding to nearest even (what bitsandbytes'
+    ``dequantize_4bit`` to bfloat16 gives)."""
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or absmax.dtype != torch.float32:
+        raise ValueError("codes must be uint8 [N, K/2] and absmax float32 [N, K/block]")
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    _lut4_block(block, K)
+    if tuple(absmax.shape) != (N, K // block):
+        raise ValueError("codes must be uint8 [N, K/2] and absmax float32 [N, K/block]")
+    book = _lut4_book(code_book, codes.device)
+    c = torch.stack([codes >> 4, codes & 0x0F], dim=-1).reshape(N, K // block, block)
+    return (book[c.long()] * absmax.unsqueeze(-1)).reshape(N, K).bfloat16()
+
+
+def bnb_nested_absmax(absmax_u8: torch.Tensor, code256: torch.Tensor, nested_absmax: torch.Tensor, offset,
+                      nested_block: int = 256) -> torch.Tensor:
+    """The float32 ``absmax`` of a double-quantised bitsandbytes checkpoint, once, at load:
+    ``code256[absmax_u8[i]] * nested_absmax[i // nested_block] + offset`` in float32, ``i`` the flat block index (the
+    result is flat: view it as ``[N, K/block]``).  ``absmax_u8`` uint8, ``code256`` float32 [256] (``quant_state``'s
+    ``nested_quant_map``), ``nested_absmax`` float32, ``offset`` one float32 value."""
+    if absmax_u8.dtype != torch.uint8 or code256.numel() != 256:
+        raise ValueError("absmax_u8 must be uint8 and code256 must hold 256 values")
+    flat = absmax_u8.reshape(-1)
+    i = torch.arange(flat.numel(), device=flat.device) // nested_block
+    if nested_absmax.numel() != (flat.numel() + nested_block - 1) // nested_block:
+        raise ValueError("nested_absmax must hold one value per nested_block statistics")
+    off = torch.as_tensor(offset, dtype=torch.float32, device=flat.device).reshape(())
+    return code256.to(torch.float32).reshape(-1)[flat.long()] * nested_absmax.to(torch.float32).reshape(-1)[i] + off

@@ -558,6 +558,17 @@ def calls(dev, fq, ops):
                 yield f"linear_gated_forward_nvfp4 {tag}", forced_split(slices, lambda: ops.linear_gated_forward_nvfp4(
                     Pm[0], Sn[0], Gn[:1], gu[:16].to(dt), bias=b, split_k=True, **glu))
 
+    # the two dense code-book (NF4) ops, behind everything above: their draws come last, so no earlier line moves.  K = 192
+    # (three pairs of stages), N = 40, rows past one 256-row tile; NF4 and a table of its own under block = 64
+    Kl, Nl, Tl = 192, 40, 260
+    codes = torch.randint(0, 256, (Nl, Kl // 2), dtype=torch.uint8, generator=d.gen).to(dev)
+    absmax = (torch.rand(Nl, Kl // 64, generator=d.gen) + 0.5).to(dev)
+    xl, gl, bl, book = d.randn(Tl, Kl), d.randn(Tl, Nl), d.randn(Nl), d.randn(16)
+    for btag, bk in (("nf4", None), ("own table", book)):
+        for dt in (F32, BF16):
+            yield f"linear_forward_lut4 {btag} {dt}", lambda: ops.linear_forward_lut4(codes, absmax, xl.to(dt), bk, 64, bias=bl)
+            yield f"linear_backward_input_lut4 {btag} {dt}", lambda: ops.linear_backward_input_lut4(codes, absmax, gl.to(dt), bk, 64, out_dtype=dt)
+
 
 def digest(t):
     t = t.detach().contiguous().cpu()

@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Time the two dense code-book (NF4) ops (ops.linear_forward_lut4 / ops.linear_backward_input_lut4)
+next to their nearest existing kernels, ops.linear_forward_nvfp4 / ops.linear_backward_input_nvfp4 (the same bytes per weight
+within 1/16, the same matrix instruction), on the same shapes in the same job.
+
+Dense 4096 -> 11008 and 4096 -> 4096 at 256, 1024 and 4096 rows, bfloat16 rows and results.  Method of DESIGN.md section 29
+without the graph: every variant runs over rotating weight sets (as many as it takes for the bytes touched between two uses
+of one set to exceed the 256 MiB Infinity Cache, at most --max-sets), the variants' windows alternate in the same job, a
+window is --calls calls between two device events, and the median of --repeats windows is printed with the window-to-window
+range.  No ratio is fixed in advance: the report states what was found.  It goes to stdout and to --out
+(profiles/lut4_timing.txt)."""
+import argparse, os, statistics, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from fused_int4_amd import ops
+
+MALL = 256 << 20
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, nargs="*", default=[256, 1024, 4096])
+ap.add_argument("--repeats", type=int, default=9)
+ap.add_argument("--calls", type=int, default=24)
+ap.add_argument("--max-sets", type=int, default=6)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lut4_timing.txt"))
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+g = torch.Generator(device=dev).manual_seed(0)
+report = []
+
+
+def say(line):
+    print(line, flush=True)
+    report.append(line)
+
+
+def shape(K, N, T):
+    sets = min(max(2, -(-MALL // (N * K // 2)) + 1), a.max_sets)
+    lut, nv = [], []
+    for _ in range(sets):
+        codes = torch.randint(0, 256, (N, K // 2), device=dev, generator=g, dtype=torch.uint8)
+        lut.append((codes, torch.rand(N, K // 64, device=dev, generator=g) + 0.5))
+        nv.append((codes, torch.randint(0x30, 0x48, (N, K // 16), device=dev, generator=g, dtype=torch.uint8), None))
+    x = torch.randn(T, K, device=dev, generator=g).bfloat16()
+    gy = torch.randn(T, N, device=dev, generator=g).bfloat16()
+    bf = torch.bfloat16
+    variants = {
+        "lut4 forward": lambda i: ops.linear_forward_lut4(*lut[i], x),
+        "nvfp4 forward": lambda i: ops.linear_forward_nvfp4(*nv[i], x),
+        "lut4 input gradient": lambda i: ops.linear_backward_input_lut4(*lut[i], gy, out_dtype=bf),
+        "nvfp4 input gradient": lambda i: ops.linear_backward_input_nvfp4(*nv[i], gy, out_dtype=bf),
+    }
+    times = {v: [] for v in variants}
+    with torch.no_grad():
+        for fn in variants.values():                            # warm up every variant on every set
+            for i in range(sets):
+                fn(i)
+        torch.cuda.synchronize()
+        for _ in range(a.repeats):
+            for v, fn in variants.items():                      # alternating: the variants share whatever else happens
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for c in range(a.calls):
+                    fn(c % sets)
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) / a.calls * 1e3)
+    res = {v: (statistics.median(t), max(t) - min(t)) for v, t in times.items()}
+    say(f"K={K} N={N} T={T}: bfloat16 rows and results, {sets} weight sets, median of {a.repeats} windows of {a.calls} calls")
+    for v, (us, rng) in res.items():
+        say(f"  {v:22s} {us:9.1f} us/call   (range {rng:6.1f})   {2.0 * T * K * N / us / 1e6:7.1f} TFLOP/s")
+    for kind in ("forward", "input gradient"):
+        new, old = res[f"lut4 {kind}"], res[f"nvfp4 {kind}"]
+        say(f"  lut4 / nvfp4 {kind} = {new[0] / old[0]:.3f} "
+            f"({'beyond' if abs(new[0] - old[0]) > max(new[1], old[1]) else 'within'} the ranges)")
+    del lut, nv
+    torch.cuda.empty_cache()
+
+
+for K, N in ((4096, 11008), (4096, 4096)):
+    for T in a.rows:
+        shape(K, N, T)
+os.makedirs(os.path.dirname(a.out), exist_ok=True)
+with open(a.out, "w") as f:
+    f.write("\n".join(report) + "\n")
