@@ -32,7 +32,8 @@
 //   * Epilogue: nv4_epilogue without a global scale (acc + bias, one float32 addition, then the one rounding to OUT).
 //   * NON-FINITE: mx4_kernel's row flag (a non-finite activation makes exactly its output row NaN); absmax and the table
 //     are not screened, plain arithmetic decides.
-// Out of scope: a decode / split-K form for a few rows, a grouped form (bitsandbytes quantises nn.Linear only).
+// A few rows take the split-K decode form of fql_gemm_lut4_decode.h.  Out of scope: a grouped form (bitsandbytes quantises
+// nn.Linear only).
 //
 // Compiled without the packed float32 instructions (the target attribute below), contraction off in the conversion.
 #pragma once

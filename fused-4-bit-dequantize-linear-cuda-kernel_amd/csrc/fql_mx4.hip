@@ -8,7 +8,7 @@
 // fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h),
 // the split-K decode form of the dense NVFP4 entries fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd (fql_gemm_nvfp4_linear.h),
 // with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels),
-// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h) with the split-K decode form fql_linear_lut4_split_fwd (fql_gemm_lut4_decode.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -25,6 +25,7 @@
 #include "fql_gemm_nvfp4_linear.h"
 #include "fql_gemm_lut4.h"
 #include "fql_gemm_lut4_bwd.h"
+#include "fql_gemm_lut4_decode.h"
 
 #include <cmath>
 
@@ -517,6 +518,85 @@ int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd,
     return FQL_OK;
 }
 
+// ---- the split-K decode form of the dense code-book layer (fql_linear_lut4_split_fwd; fql_gemm_lut4_decode.h, DESIGN.md
+//      section 45) ----
+#define FQL_LUT4_LINEAR_DECODE_MAX_ROWS 64 /* rows (T) up to which the decode form runs: the largest count of the sweep (1, 8, 16, 32, 64, 128) at which it beats the tile kernel by more than the windows' ranges on every shape; at 128 rows 8192 -> 28672 ties at its two slices */
+#define FQL_LUT4_LINEAR_MAX_SLICES 16
+#define FQL_LUT4_LINEAR_FILL_WAVES 1280     /* the waves S(K, N) asks for: every value in (1024, 1376] gives each of the five swept shapes the S that won its one-row sweep (16, 4, 16, 8, 2); 1280 is five waves a compute unit (the same section) */
+int g_lut4_linear_decode_max_rows = FQL_LUT4_LINEAR_DECODE_MAX_ROWS;
+int g_lut4_linear_slices = 0;          // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_lut4_linear_slices)
+
+// S(K, N), shaped as nv4_linear_policy_slices: the smallest S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >=
+// FQL_LUT4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 pairs, so that no slice of the policy's is empty.
+int lut4_linear_policy_slices(int K, int N)
+{
+    const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
+    int S = 1;
+    while (S < FQL_LUT4_LINEAR_MAX_SLICES && waves * S < FQL_LUT4_LINEAR_FILL_WAVES) S *= 2;
+    const int P = K / 64;
+    while (S > 1 && S > P) S /= 2;
+    return S;
+}
+
+// The decode form runs up to the row threshold, at S = 1 as well (there is no one-wave kernel to fall back on).
+bool lut4_use_decode(int T)
+{
+    return T > 0 && T <= g_lut4_linear_decode_max_rows && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;
+}
+
+int lut4_linear_slices(int K, int N)
+{
+    return g_lut4_linear_slices != 0 ? g_lut4_linear_slices : lut4_linear_policy_slices(K, N);
+}
+
+// The partial sums: [16][T][N] float32, sized for the largest S so that the slice hook cannot outgrow it.
+size_t lut4_linear_partial_bytes(int T, int N)
+{
+    if (N <= 0 || !lut4_use_decode(T)) return 0;
+    return (size_t)FQL_LUT4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
+}
+
+int launch_lut4_tile(int in_dtype, int out_dtype, const Lut4Call &c, int bshift, hipStream_t st)
+{
+    using C = Lut4Cfg;
+    const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT);
+    return with_in_dtype(in_dtype, [&](auto in) {
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(lut4_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st,
+                          c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N);
+        });
+    });
+}
+
+// The two launches: the sliced decode kernel into partial [S][T][N], then the reduce kernel (S = 1 included).
+int launch_lut4_split(int in_dtype, int out_dtype, const Lut4Call &c, int bshift, int S, float *partial, hipStream_t st)
+{
+    using D = Mx4DecodeCfg;
+    using R = Nv4LinearReduceCfg;
+    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
+    const int rc = with_in_dtype(in_dtype, [&](auto in) {
+        return launch(lut4_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.codes, c.absmax, c.book, c.rows, partial,
+                      bshift, c.T, c.K, c.N);
+    });
+    if (rc != FQL_OK) return rc;
+    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
+    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
+    return with_out_dtype(out_dtype, [&](auto o) {
+        constexpr int OUT = decltype(o)::value;
+        auto go = [&](auto s) {
+            return launch(lut4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.bias, c.out, c.T,
+                          c.N);
+        };
+        switch (S) {
+        case 1: return go(std::integral_constant<int, 1>{});
+        case 2: return go(std::integral_constant<int, 2>{});
+        case 4: return go(std::integral_constant<int, 4>{});
+        case 8: return go(std::integral_constant<int, 8>{});
+        default: return go(std::integral_constant<int, 16>{});
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -918,13 +998,48 @@ FQL_API int fql_linear_lut4_fwd(const uint8_t *codes, const float *absmax, const
     int bshift = 6;
     const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, false, &empty, &bshift);
     if (rc != FQL_OK || empty) return rc;
-    const dim3 grid((N + C::BN - 1) / C::BN, (T + C::BT - 1) / C::BT);
-    return with_in_dtype(in_dtype, [&](auto in) {
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(lut4_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, static_cast<hipStream_t>(stream),
-                          c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N);
-        });
-    });
+    return launch_lut4_tile(in_dtype, out_dtype, c, bshift, static_cast<hipStream_t>(stream));
+}
+
+FQL_API size_t fql_linear_lut4_split_workspace_bytes(int T, int K, int N)
+{
+    (void)K;
+    return lut4_linear_partial_bytes(T, N);                               // partial [16][T][N] float32
+}
+
+FQL_API int fql_linear_lut4_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                      int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N,
+                                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    const Lut4Call c{codes, absmax, code_book, block, inputs, bias, out, T, K, N};
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, Lut4Cfg::BT, false, &empty, &bshift);   // (a decode grid's y is within it)
+    if (rc != FQL_OK || empty) return rc;
+    const size_t need = lut4_linear_partial_bytes(T, N);
+    if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!lut4_use_decode(T)) return launch_lut4_tile(in_dtype, out_dtype, c, bshift, st);
+    return launch_lut4_split(in_dtype, out_dtype, c, bshift, lut4_linear_slices(K, N), static_cast<float *>(workspace), st);
+}
+
+FQL_API int fql_tune_set_lut4_linear_decode_max_rows(int rows)
+{
+    const int old = g_lut4_linear_decode_max_rows;
+    if (rows >= 0) g_lut4_linear_decode_max_rows = rows;
+    return old;
+}
+
+FQL_API int fql_tune_set_lut4_linear_slices(int slices)
+{
+    const int old = g_lut4_linear_slices;
+    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_lut4_linear_slices = slices;
+    return old;
+}
+
+FQL_API int fql_tune_lut4_linear_kernel(int T, int K, int N)
+{
+    return lut4_use_decode(T) ? (lut4_linear_slices(K, N) << 8) | 2 : (1 << 8);
 }
 
 FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,

@@ -43,16 +43,22 @@ class NF4Linear(nn.Module):
     ``input_grad=False`` (the default) is inference only: a forward under grad mode on an input that requires grad raises
     ``RuntimeError``.  ``input_grad=True`` gives ``x.grad`` through ``ops.linear_backward_input_lut4`` (on the GPU only),
     straight-through across the bfloat16 rounding of ``x``.  It is configuration, not state: the state-dict keys are
-    ``codes``, ``absmax``, ``code_book`` (and ``bias``)."""
+    ``codes``, ``absmax``, ``code_book`` (and ``bias``).
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = False, input_grad: bool = False, block: int = 64):
+    ``split_k=True`` (configuration as well; the default is False and the tile kernel's bits) is for generation: up to the
+    library's row threshold the forward is the split-K decode form of ``ops.linear_forward_lut4(split_k=True)``.  A row's
+    bits then depend on its own row, the weights, K and N, not on the batch or the row's position, and are run-to-run
+    identical; they are not the tile kernel's bits, so a row may change as the batch crosses the threshold."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = False, input_grad: bool = False, block: int = 64,
+                 split_k: bool = False):
         super().__init__()
         if block < 64 or block & (block - 1):
             raise ValueError("block must be a power of two of at least 64")
         if in_features <= 0 or in_features % 64 != 0 or in_features % block != 0 or out_features <= 0:
             raise ValueError("in_features must be a positive multiple of 64 and of block, and out_features positive")
         self.in_features, self.out_features, self.block = in_features, out_features, block
-        self.input_grad = bool(input_grad)
+        self.input_grad, self.split_k = bool(input_grad), bool(split_k)
         self.register_buffer("codes", torch.full((out_features, in_features // 2), 0x77, dtype=torch.uint8))   # (NF4's zero)
         self.register_buffer("absmax", torch.ones(out_features, in_features // block, dtype=torch.float32))
         self.register_buffer("code_book", torch.tensor(NF4_CODE_BOOK, dtype=torch.float32))
@@ -65,7 +71,7 @@ class NF4Linear(nn.Module):
     def from_bnb(cls, codes, absmax, block: int = 64, code_book=None, bias=None, **kwargs) -> "NF4Linear":
         """bitsandbytes' tensors as they are: ``codes`` uint8 [N, K/2] and ``absmax`` float32 [N, K/block]; its packed
         ``[N*K/2, 1]`` / flat weight and flat ``[N*K/block]`` statistics are viewed, given ``out_features=`` among the
-        keywords.  ``code_book`` 16 values or None for NF4, ``bias`` [N] or None.  ``kwargs``: ``input_grad``."""
+        keywords.  ``code_book`` 16 values or None for NF4, ``bias`` [N] or None.  ``kwargs``: ``input_grad``, ``split_k``."""
         N = kwargs.pop("out_features", None)
         if codes.dtype != torch.uint8 or absmax.dtype != torch.float32:
             raise ValueError("codes must be uint8 and absmax float32")
@@ -95,14 +101,15 @@ class NF4Linear(nn.Module):
 
     @classmethod
     def from_linear(cls, linear: nn.Linear, block: int = 64, code_book=None, **kwargs) -> "NF4Linear":
-        """Quantise an ``nn.Linear`` with ``quantize.quantize_lut4``; its bias is kept (float32).  ``kwargs``: ``input_grad``."""
+        """Quantise an ``nn.Linear`` with ``quantize.quantize_lut4``; its bias is kept (float32).  ``kwargs``: ``input_grad``, ``split_k``."""
         from .quantize import quantize_lut4
         codes, absmax = quantize_lut4(linear.weight.detach().float(), code_book, block)
         return cls.from_bnb(codes, absmax, block, code_book, bias=None if linear.bias is None else linear.bias.detach(), **kwargs)
 
     def _rows(self, x2):
         from . import ops
-        return ops.linear_forward_lut4(self.codes, self.absmax, x2, self.code_book, self.block, bias=self.bias, out_dtype=x2.dtype)
+        return ops.linear_forward_lut4(self.codes, self.absmax, x2, self.code_book, self.block, bias=self.bias, out_dtype=x2.dtype,
+                                       split_k=self.split_k)
 
     def forward(self, x):
         if x.dtype not in (torch.float32, torch.bfloat16):
@@ -130,7 +137,7 @@ class NF4Linear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, format=lut4, "
-                f"block={self.block}" + (", input_grad=True" if self.input_grad else ""))
+                f"block={self.block}" + (", input_grad=True" if self.input_grad else "") + (", split_k=True" if self.split_k else ""))
 
 
 class LoRANF4Linear(NF4Linear):
@@ -142,9 +149,9 @@ class LoRANF4Linear(NF4Linear):
     adapter stage.  A fresh layer (``B = 0``) returns ``NF4Linear``'s bits.  The adapter path runs on the GPU only."""
 
     def __init__(self, in_features: int, out_features: int, rank: int, alpha: float | None = None, bias: bool = False,
-                 input_grad: bool = True, block: int = 64):
+                 input_grad: bool = True, block: int = 64, split_k: bool = False):
         del input_grad                                                                 # (always on: the layer is for training)
-        super().__init__(in_features, out_features, bias=bias, input_grad=True, block=block)
+        super().__init__(in_features, out_features, bias=bias, input_grad=True, block=block, split_k=split_k)
         from .ops import LORA_RANKS
         if rank not in LORA_RANKS:
             raise ValueError(f"rank must be one of {LORA_RANKS}, got {rank!r}")
@@ -174,7 +181,8 @@ class LoRANF4Linear(NF4Linear):
     @classmethod
     def from_layer(cls, layer: NF4Linear, rank: int, alpha: float | None = None) -> "LoRANF4Linear":
         """Wrap an existing ``NF4Linear``; the new module shares its buffers (no copy)."""
-        module = cls(layer.in_features, layer.out_features, rank, alpha, bias=layer.bias is not None, block=layer.block)
+        module = cls(layer.in_features, layer.out_features, rank, alpha, bias=layer.bias is not None, block=layer.block,
+                     split_k=layer.split_k)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
         return module._adapters_to(layer.codes.device)
@@ -190,7 +198,7 @@ class LoRANF4Linear(NF4Linear):
                                f"got {list(x.shape)}")
         from . import ops
         y = ops.linear_lora_forward_lut4(x.reshape(-1, self.in_features), self.codes, self.absmax, self.lora_A, self.lora_B,
-                                         self.scaling, self.code_book, self.block, bias=self.bias)
+                                         self.scaling, self.code_book, self.block, bias=self.bias, split_k=self.split_k)
         return y.reshape(*x.shape[:-1], self.out_features)
 
     def extra_repr(self) -> str:

@@ -2773,9 +2773,10 @@ class _NVFP4LinearLoRAFn(torch.autograd.Function):
 # DESIGN.md section 44)
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias, out_dtype, default_dtype):
+def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias, out_dtype, default_dtype, split_k=False):
     """Both code-book ops, section 14's order: types and shapes first, then the devices.  ``rows`` [T, cols(K, N)] float32 /
-    bfloat16; the result is [T, K + N - cols(K, N)]."""
+    bfloat16; the result is [T, K + N - cols(K, N)].  ``split_k`` (forward): the split entry, ``fql_linear_lut4_split_fwd``,
+    with its workspace allocated here as ``_nvfp4_launch`` allocates its own."""
     what = "the rows" if bias is not False else "grad_out"
     if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: {what} must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
@@ -2805,12 +2806,13 @@ def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias,
     out = torch.empty((T, K + N - cols(K, N)), dtype=out_dtype, device=dev)
     book = None if code_book is None else code_book.contiguous()
     b = () if bias is False else (None if bias is None else bias.contiguous(),)
+    ws_bytes = _native.lib().fql_linear_lut4_split_workspace_bytes(T, K, N) if split_k else None
     _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *b, out,
-            _DTYPES[out_dtype], T, K, N)
+            _DTYPES[out_dtype], T, K, N, ws_bytes=ws_bytes)
     return out
 
 
-def linear_forward_lut4(codes, absmax, x, code_book=None, block=64, bias=None, out_dtype=None):
+def linear_forward_lut4(codes, absmax, x, code_book=None, block=64, bias=None, out_dtype=None, split_k=False):
     """A dense linear layer on 4-bit code-book weights in bitsandbytes' encoding (NF4 by default):
     ``out[t] = W @ bf16(x[t]) (+ bias)``, ``W[n, k] = bf16(fl32(code_book[c(n, k)] * absmax[n, k // block]))``.  ``codes`` uint8
     [N, K/2], input ``2i`` in the HIGH nibble of byte ``i`` (the opposite of this library's other 4-bit buffers);
@@ -2818,10 +2820,19 @@ def linear_forward_lut4(codes, absmax, x, code_book=None, block=64, bias=None, o
     None for ``quantize.NF4_CODE_BOOK``; ``bias`` float32 [N].  ``x`` [T, K] float32 (rounded once to bfloat16) or bfloat16.
     The weight's one rounding to bfloat16 is part of the definition (it is ``dequantize_4bit`` to bfloat16); the sums are
     float32 on the bfloat16 matrix cores, then the bias, then one rounding to ``out_dtype`` (default: ``x``'s type).  A
-    non-finite element of a row makes that row of the result NaN.  Forward only."""
+    non-finite element of a row makes that row of the result NaN.  Forward only.
+
+    ``split_k=False`` (the default) is the 256-row tile kernel at every T.  ``split_k=True`` lets a small batch (T up to the
+    library's threshold) run a one-wave decode kernel on S(K, N) slices of K side by side, each code converted once, and a
+    second launch sums the float32 partial results in a fixed order and adds the bias; above the threshold the call is the
+    ``split_k=False`` launch and its bits.  THE CONTRACT with ``split_k``: a row's bits depend on its own row, the weights, K
+    and N; they do not depend on T or on the row's position, and they are run-to-run identical.  They are not the tile
+    kernel's bit pattern (the float32 sums are associated otherwise), so a row's bits may change as T crosses the
+    threshold; both sides are within the float32 bound of the exact product."""
     _forward_only("linear_forward_lut4", x, bias)
-    return _lut4_launch("linear_forward_lut4", "fql_linear_lut4_fwd", codes, absmax, x, lambda K, N: K, code_book, block, bias,
-                        out_dtype, x.dtype if isinstance(x, torch.Tensor) else None)
+    return _lut4_launch("linear_forward_lut4", "fql_linear_lut4_split_fwd" if split_k else "fql_linear_lut4_fwd", codes, absmax, x,
+                        lambda K, N: K, code_book, block, bias, out_dtype, x.dtype if isinstance(x, torch.Tensor) else None,
+                        split_k=bool(split_k))
 
 
 def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64, out_dtype=None):
@@ -2832,25 +2843,26 @@ def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64
                         code_book, block, False, out_dtype, torch.float32)
 
 
-def _lut4_lora_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bias):
+def _lut4_lora_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bias, split_k=False):
     """Base forward to float32, u = x A^T, then y = base + scaling * u B^T in x's type, one rounding.  Returns (y, u)."""
-    y32 = linear_forward_lut4(codes, absmax, x2, book, block, bias=bias, out_dtype=torch.float32)
+    y32 = linear_forward_lut4(codes, absmax, x2, book, block, bias=bias, out_dtype=torch.float32, split_k=split_k)
     u = lora_shrink(x2, lora_A, "rc")
     return _expand_into(u, lora_B, "cr", y32, x2.dtype, scale=scaling), u
 
 
-def linear_lora_forward_lut4(x, codes, absmax, lora_A, lora_B, scaling, code_book=None, block=64, bias=None):
+def linear_lora_forward_lut4(x, codes, absmax, lora_A, lora_B, scaling, code_book=None, block=64, bias=None, split_k=False):
     """``linear_forward_lut4`` plus a low-rank adapter, ``y = W bf16(x) (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``,
     composed from the two code-book ops and ``lora_shrink`` / ``lora_expand`` / ``lora_grad`` in one autograd node (no
     fused adapter stage).  ``x`` [T, K] float32 or bfloat16, float32 ``lora_A`` [r, K] and ``lora_B`` [N, r]; the result
     has ``x``'s type, rounded once.  Differentiable in ``x``, ``lora_A`` and ``lora_B``; the code-book weights and the bias
-    are frozen.  With ``lora_B == 0`` the result is ``linear_forward_lut4``'s bits."""
+    are frozen.  With ``lora_B == 0`` the result is ``linear_forward_lut4``'s bits.  ``split_k`` is passed on to the base
+    forward (its contract is ``linear_forward_lut4``'s); the adapter and the backward are the same either way."""
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
         raise RuntimeError("ops.linear_lora_forward_lut4: x must be a CUDA float32 or bfloat16 [T, K] tensor")
     _lora_check_adapters(lora_A, lora_B, x.shape[1], codes.shape[0], None)
     if _wants_grad(x, lora_A, lora_B):
-        return _LUT4LinearLoRAFn.apply(x, lora_A, lora_B, codes, absmax, code_book, block, bias, float(scaling))
-    return _lut4_lora_apply(x.contiguous(), codes, absmax, code_book, block, lora_A, lora_B, float(scaling), bias)[0]
+        return _LUT4LinearLoRAFn.apply(x, lora_A, lora_B, codes, absmax, code_book, block, bias, float(scaling), bool(split_k))
+    return _lut4_lora_apply(x.contiguous(), codes, absmax, code_book, block, lora_A, lora_B, float(scaling), bias, bool(split_k))[0]
 
 
 class _LUT4LinearLoRAFn(torch.autograd.Function):
@@ -2858,9 +2870,9 @@ class _LUT4LinearLoRAFn(torch.autograd.Function):
     dequantised.  A 16-bit dX is written once, by the expand, from the float32 base dX."""
 
     @staticmethod
-    def forward(ctx, x, lora_A, lora_B, codes, absmax, book, block, bias, scaling):
+    def forward(ctx, x, lora_A, lora_B, codes, absmax, book, block, bias, scaling, split_k=False):
         x2 = x.detach().contiguous()
-        y, u = _lut4_lora_apply(x2, codes, absmax, book, block, lora_A.detach(), lora_B.detach(), scaling, bias)
+        y, u = _lut4_lora_apply(x2, codes, absmax, book, block, lora_A.detach(), lora_B.detach(), scaling, bias, split_k)
         ctx.save_for_backward(x2, u, lora_A, lora_B, codes, absmax)
         ctx.book, ctx.block, ctx.scaling = book, block, scaling
         return y
@@ -2882,4 +2894,4 @@ class _LUT4LinearLoRAFn(torch.autograd.Function):
                 gA = lora_grad(x2, du, "rc")[0]                                          # dA = du^T x
         if need_B:
             gB = lora_grad(g, u, "cr", scale=ctx.scaling)[0]                             # dB = s dY^T u
-        return gx, gA, gB, None, None, None, None, None, None
+        return gx, gA, gB, None, None, None, None, None, None, None

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 470 /* 0.4.7: 4-bit code-book weights (NF4 of bitsandbytes / QLoRA), dense: fql_linear_lut4_fwd / fql_linear_lut4_bwd_input.  0.4.6: a split-K decode form of the dense NVFP4 linear layer: fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd / fql_linear_nvfp4_split_workspace_bytes.  0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 480 /* 0.4.8: a split-K decode form of the dense code-book (NF4) layer: fql_linear_lut4_split_fwd / fql_linear_lut4_split_workspace_bytes.  0.4.7: 4-bit code-book weights (NF4 of bitsandbytes / QLoRA), dense: fql_linear_lut4_fwd / fql_linear_lut4_bwd_input.  0.4.6: a split-K decode form of the dense NVFP4 linear layer: fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd / fql_linear_nvfp4_split_workspace_bytes.  0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1353,12 +1353,36 @@ FQL_API int fql_linear_nvfp4_glu_split_fwd(const uint8_t *blocks, const uint8_t 
  * N == 0) returns FQL_OK with nothing launched; FQL_ERR_NULL_POINTER (codes, absmax, the rows, the result);
  * FQL_ERR_BAD_SHAPE (a grid dimension above 65535); FQL_ERR_ALIGNMENT (codes 16 bytes, absmax / code_book / bias 4, the rows
  * and the result their element).  Then FQL_ERR_LAUNCH.  fql_linear_lut4_bwd_input with N == 0 and T > 0 writes zeros.
- * No workspace.  There is no decode / split-K form and no grouped form. */
+ * No workspace.  The decode / split-K form has an entry of its own (fql_linear_lut4_split_fwd, FQL_VERSION 480, below); there
+ * is no grouped form. */
 FQL_API int fql_linear_lut4_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
                                 int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N, void *stream);
 FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
                                       const void *grad_out, int in_dtype, void *grad_in, int out_dtype, int T, int K, int N,
                                       void *stream);
+
+/* ---- a split-K decode form of the dense code-book layer (FQL_VERSION 480; INTEGRATION.md section 19, DESIGN.md section 45;
+ *      csrc/fql_gemm_lut4_decode.h) ----
+ * fql_linear_lut4_split_fwd takes fql_linear_lut4_fwd's argument list plus (workspace, workspace_bytes), the same W and the
+ * same return codes in the same order, then FQL_ERR_WORKSPACE (NULL, not 16-byte aligned or smaller than
+ * fql_linear_lut4_split_workspace_bytes(T, K, N)) as the last check, everything before any HIP call.
+ *   T up to a threshold built into the library (FQL_LUT4_LINEAR_DECODE_MAX_ROWS in csrc/fql_mx4.hip): a one-wave kernel on a
+ *   grid of (ceil(N / 32), ceil(T / 32), S) writes float32 partial sums of S slices of K (P = K / 64 pairs; slice s is pairs
+ *   [s ceil(P / S), min(P, (s + 1) ceil(P / S))) over ascending k from zero) to the workspace, and a second launch gives
+ *     out[t][n] = round_OUT( fl32( (((p_0 + p_1) + ...) + p_{S-1}) + bias[n] ) ),
+ *   float32, the order fixed, every element written once.  S = S(K, N) in {1, 2, 4, 8, 16} is a pure function of the weights'
+ *   shape; S = 1 runs the same two kernels.  No atomics, no flags, nothing but the two launches on `stream`; capturable.
+ *   THE CONTRACT: a row's bits depend on its own row, the weights, K and N; not on T, not on the row's position; they are run
+ *   to run identical.  They are NOT fql_linear_lut4_fwd's bits (the float32 sums are associated otherwise): a row may
+ *   change as T crosses the threshold.  Both are within the float32 bound of the exact product.
+ *   NON-FINITE: as fql_linear_lut4_fwd (a slice whose part of a row is non-finite stores NaN for that partial row).
+ *   T above the threshold: fql_linear_lut4_fwd's launch and bits; the workspace is not used and its size is 0 then.
+ * Workspace: [16][T][N] float32 up to the threshold, whatever S.  fql_int4_tune.h: fql_tune_set_lut4_linear_decode_max_rows /
+ * fql_tune_set_lut4_linear_slices / fql_tune_lut4_linear_kernel force and report the form. */
+FQL_API size_t fql_linear_lut4_split_workspace_bytes(int T, int K, int N);
+FQL_API int fql_linear_lut4_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                      int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

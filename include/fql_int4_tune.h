@@ -100,6 +100,17 @@ FQL_API int fql_tune_set_nvfp4_linear_slices(int slices);
  * kernel (both with S = 1: fql_linear_nvfp4_fwd's path), 2 the split form with S slices.  Keeps no state. */
 FQL_API int fql_tune_nvfp4_linear_kernel(int T, int K, int N);
 
+/* The split entry of the dense code-book (NF4) layer (fql_linear_lut4_split_fwd; fql_int4.h, FQL_VERSION 480).
+ * fql_tune_set_lut4_linear_decode_max_rows: rows (T) up to which the decode form runs; 0 never; returns the previous value, a
+ * negative `rows` changes nothing.  fql_linear_lut4_split_workspace_bytes follows it. */
+FQL_API int fql_tune_set_lut4_linear_decode_max_rows(int rows);
+/* The slices S of the decode form: 0 the library's policy S(K, N), or one of 1 / 2 / 4 / 8 / 16 to force S for every shape
+ * (1 is one slice of the same two kernels).  Any other value changes nothing.  Returns the previous value. */
+FQL_API int fql_tune_set_lut4_linear_slices(int slices);
+/* What the split entry would run on this shape now: (S << 8) | form, form 0 the 256-row tile kernel (S = 1:
+ * fql_linear_lut4_fwd's path), 2 the decode form with S slices.  Keeps no state. */
+FQL_API int fql_tune_lut4_linear_kernel(int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,8 @@ and gated and ``moe_backward_input_mxfp4``; last the same lines for ``precision=
 form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``; then the NVFP4 forward ops, decode and
 tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands, and last the five NVFP4 adapter
 ops (``moe_forward_nvfp4_lora`` and its kin) on them, and the two dense NVFP4 ops with ``split_k=True`` at 2 and at 16 forced
-slices."""
+slices; then the two code-book (NF4) ops and, last, ``linear_forward_lut4(split_k=True)`` at the policy's S and at 2 and 16
+forced slices."""
 import argparse
 import hashlib
 import os
@@ -568,6 +569,25 @@ def calls(dev, fq, ops):
         for dt in (F32, BF16):
             yield f"linear_forward_lut4 {btag} {dt}", lambda: ops.linear_forward_lut4(codes, absmax, xl.to(dt), bk, 64, bias=bl)
             yield f"linear_backward_input_lut4 {btag} {dt}", lambda: ops.linear_backward_input_lut4(codes, absmax, gl.to(dt), bk, 64, out_dtype=dt)
+
+    # the split-K decode form of the code-book forward, behind every earlier call (no new draws): the policy's S, then 2 and
+    # 16 forced slices (K = 192 is three pairs: uneven and empty slices), 16 rows
+    def forced_lut4(slices, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = lib.fql_tune_set_lut4_linear_slices(slices)
+            try:
+                return call()
+            finally:
+                lib.fql_tune_set_lut4_linear_slices(old)
+        return run
+
+    for slices in (0, 2, 16):
+        for btag, bk in (("nf4", None), ("own table", book)):
+            for dt in (F32, BF16):
+                yield f"linear_forward_lut4 {btag} {dt} split S={slices or 'policy'}", forced_lut4(slices, lambda: ops.linear_forward_lut4(
+                    codes, absmax, xl[:16].to(dt), bk, 64, bias=bl, split_k=True))
 
 
 def digest(t):
