@@ -238,6 +238,11 @@ _SYMBOLS = {
                             + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "fql_linear_lut4_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
                                   + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "fql_linear_lut4_lora_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                                 + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "fql_linear_lut4_lora_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                                       + [ctypes.c_void_p] * 2 + [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 4
+                                       + [ctypes.c_void_p]),
     "fql_linear_lut4_split_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "fql_linear_lut4_split_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2
                                   + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

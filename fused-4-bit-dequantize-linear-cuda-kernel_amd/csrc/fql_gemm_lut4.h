@@ -35,6 +35,22 @@
 // A few rows take the split-K decode form of fql_gemm_lut4_decode.h.  Out of scope: a grouped form (bitsandbytes quantises
 // nn.Linear only).
 //
+// LORA (lut4_kernel<IN, OUT, Mx4Lora>; fql_linear_lut4_lora_fwd): the adapter as one more contraction
+// stage behind the K loop's last barrier,
+//   out[t][n] = round_OUT( fl32( S + bias[n] ) ),   S = acc (+) sum_{j < r} bf16(v[t][j]) bf16(B[n][j])
+// with (+) the matrix instruction accumulating onto its C operand in ascending j, 16 a step.  No store follows the loop's
+// last barrier, so both pairs of images are free, and a pair holds 32 columns of j:
+//   * Staging thread (sn, sp) packs B[n0 + sn][32 p + 16 sp .. + 15] into image[p][sn][16 sp ..], zeros past N and from r
+//     on; thread (xs, xq) packs v[tx][32 p + 16 xq .. + 15] of its XR rows xs + 128 i (clamped to T - 1, as x) into
+//     ximage[p], zeros from r on; the packed words of v feed the row flag, B is not screened.  p = 0 for r <= 32; r = 64
+//     writes p = 1 in the same pass.  A pair that is written is written in full (all 32 columns of all rows), so nothing
+//     of a weight stage is contracted a second time, and a pair that is not written is not read.
+//   * ONE barrier for every rank, then the steps s = 0 .. 3 with 16 s < r on pair s >> 1, columns 16 (s & 1) .. + 15: the
+//     K loop's own 2 x 4 fragment loop, eight matrix instructions a step.  A dead wave stages and meets the barrier.
+//   * 16-byte loads of v / B when their base is 16-byte aligned (4 r is a multiple of 16), element loads otherwise.
+//   * No LDS beyond the kernel's, no global scale (nothing moves in front of the stage), nv4_epilogue as it is.  With
+//     B = 0 the steps add +0 to every register: the base kernel's bits.  lut4_kernel<IN, OUT> is the code it was.
+//
 // Compiled without the packed float32 instructions (the target attribute below), contraction off in the conversion.
 #pragma once
 #include "fql_gemm_nvfp4.h"
@@ -81,13 +97,17 @@ __device__ __forceinline__ uint4 lut4_dequant8(uint32_t w, float am, const float
 }
 
 // The kernel's body (inlined into lut4_kernel, which carries the target attribute and the LDS: as nv4_linear_decode_body).
-template <int IN, int OUT>
+// LA: nothing, or Mx4Lora: the compile-time LORA flag, set by the argument that carries what it needs.
+template <int IN, int OUT, class... LA>
 __device__ __forceinline__ void lut4_body(
     unsigned short (&image)[2][Lut4Cfg::BN][Lut4Cfg::PITCH], unsigned short (&ximage)[2][Lut4Cfg::BT][Lut4Cfg::PITCH],
     float (&lut)[16], int (&row_bad)[Lut4Cfg::BT],
     const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
-    const void *__restrict__ x, const float *__restrict__ bias, void *__restrict__ out, int bshift, int T, int K, int N)
+    const void *__restrict__ x, const float *__restrict__ bias, void *__restrict__ out, int bshift, int T, int K, int N,
+    LA... lora)
 {
+    static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
+    constexpr bool LORA = sizeof...(LA) == 1;
     using C = Lut4Cfg;
     const int n0 = (int)blockIdx.x * C::BN, t_blk = (int)blockIdx.y * C::BT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -211,8 +231,70 @@ __device__ __forceinline__ void lut4_body(
         __syncthreads();
     }
 
+    if constexpr (LORA) {
+        // The adapter stage.  Every thread is behind the loop's last barrier, which no store followed: both pairs of images
+        // are free.  Pair p takes columns j = 32 p .. 32 p + 31 of B and of v, written in full (zeros past N and from
+        // `rank` on); pair 1 only for rank 64 (uniform).  One barrier, then the steps.
+        const Mx4Lora la{lora...};
+        const int rank = la.rank;
+        const float *brow = la.w + wrow * rank;
+        const bool vec_v = (reinterpret_cast<uintptr_t>(la.rows) & 15) == 0, vec_b = (reinterpret_cast<uintptr_t>(la.w) & 15) == 0;
+        const float *vrow[C::XR];
+#pragma unroll
+        for (int i = 0; i < C::XR; ++i) {
+            const int tx = t_blk + xs + 128 * i < T ? t_blk + xs + 128 * i : T - 1;
+            vrow[i] = la.rows + (size_t)tx * rank;
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            if (32 * p >= rank) break;                             // (uniform)
+            uint32_t bw[8];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {                          // B[n0 + sn][32 p + 16 sp + 4 i .. + 3]
+                const int j = 32 * p + 16 * sp + 4 * i;
+                mx4_lora_pack4(brow + j, vec_b, n_ok && j < rank, bw[2 * i], bw[2 * i + 1]);
+            }
+            *reinterpret_cast<uint4 *>(&image[p][sn][16 * sp]) = make_uint4(bw[0], bw[1], bw[2], bw[3]);
+            *reinterpret_cast<uint4 *>(&image[p][sn][16 * sp + 8]) = make_uint4(bw[4], bw[5], bw[6], bw[7]);
+#pragma unroll
+            for (int i = 0; i < C::XR; ++i) {
+                uint32_t xw[8], bad = 0u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {                      // v[tx][32 p + 16 xq + 4 q .. + 3]
+                    const int j = 32 * p + 16 * xq + 4 * q;
+                    mx4_lora_pack4(vrow[i] + j, vec_v, j < rank, xw[2 * q], xw[2 * q + 1]);
+                    bad |= mx4_nonfinite2(xw[2 * q]) | mx4_nonfinite2(xw[2 * q + 1]);
+                }
+                *reinterpret_cast<uint4 *>(&ximage[p][xs + 128 * i][16 * xq]) = make_uint4(xw[0], xw[1], xw[2], xw[3]);
+                *reinterpret_cast<uint4 *>(&ximage[p][xs + 128 * i][16 * xq + 8]) = make_uint4(xw[4], xw[5], xw[6], xw[7]);
+                if (bad & 0x80008000u) row_bad[xs + 128 * i] = 1;   // (read behind the barrier below)
+            }
+        }
+        __syncthreads();
+        if (wave_live) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (16 * s >= rank) break;                         // (uniform)
+                const unsigned short(*cur)[C::PITCH] = image[s >> 1];
+                const unsigned short(*xcur)[C::PITCH] = ximage[s >> 1];
+                const int c0 = 16 * (s & 1) + 8 * h;
+                uint4 xb[2];
+#pragma unroll
+                for (int a = 0; a < 2; ++a) xb[a] = *reinterpret_cast<const uint4 *>(&xcur[C::WT * wave + 32 * a + r][c0]);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const uint4 wa = *reinterpret_cast<const uint4 *>(&cur[32 * b + r][c0]);
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, wa), __builtin_bit_cast(v8bf, xb[a]),
+                                                                            acc[a][b], 0, 0, 0);
+                }
+            }
+        }
+    }
+
     // D[i][j]: i = n (A), j = t (B): the lane owns row t, registers 4q .. 4q+3 are n = 8 q + 4 h + (0 .. 3) of the block.
-    // (Every write of row_bad lies behind a barrier of the loop.)
+    // (Every write of row_bad lies behind a barrier of the loop or of the adapter stage.)
     if (!wave_live) return;
     const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (OUT == 0 ? 15 : 7)) == 0;
 #pragma unroll
@@ -227,11 +309,12 @@ __device__ __forceinline__ void lut4_body(
 }
 
 // IN: element type of x (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of out, rounded once in the epilogue.
-// bshift = log2(B).
-template <int IN, int OUT>
+// bshift = log2(B).  LA: nothing (lut4_kernel<IN, OUT>: the signature, the code and the bits it always had), or Mx4Lora.
+template <int IN, int OUT, class... LA>
 __global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
-    const void *__restrict__ x, const float *__restrict__ bias, void *__restrict__ out, int bshift, int T, int K, int N)
+    const void *__restrict__ x, const float *__restrict__ bias, void *__restrict__ out, int bshift, int T, int K, int N,
+    LA... lora)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Lut4Cfg;
@@ -239,6 +322,6 @@ __global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short ximage[2][C::BT][C::PITCH];     // activation rows, bfloat16
     __shared__ float lut[16];
     __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite activation
-    lut4_body<IN, OUT>(image, ximage, lut, row_bad, codes, absmax, book, x, bias, out, bshift, T, K, N);
+    lut4_body<IN, OUT, LA...>(image, ximage, lut, row_bad, codes, absmax, book, x, bias, out, bshift, T, K, N, lora...);
 #endif
 }

@@ -16,20 +16,29 @@
 //     is written, so the contraction sees finished bfloat16 weights.  The store rotation permutes dwords under one scale:
 //     nothing travels with them.
 //   * Absent pieces (n >= N, or k >= K in the last tile) are ZEROS in the image, whatever code 0 means in the table.
-//   * No global scale, no adapter stage: the epilogue is the one rounding to OUT.
+//   * No global scale: the epilogue is the one rounding to OUT.
 //   * EXEC, NON-FINITE: as nv4_bwd_kernel (uniform trip counts, no per-lane exit before the epilogue; the row flag).
+//   * LORA (lut4_bwd_kernel<IN, OUT, Mx4Lora>; fql_linear_lut4_lora_bwd_input): nv4_bwd_kernel's adapter
+//     stage behind the last weight stage,
+//       dX[t][k] = round_OUT( S' ),   S' = acc (+) sum_{j < r} bf16(dv[t][j]) bf16(A[j][k]).
+//     A[j][kbase .. + 127], j < 64, goes into pair 0 of the weight image through the same mx4_bwd_off and store rotation
+//     (zeros for j >= r and k >= K), dv into the gradient image (zeros from r on); one barrier, then the steps with
+//     16 s < r.  Nothing moves in front of the stage (there is no global scale); lut4_bwd_kernel<IN, OUT> is the code it was.
 #pragma once
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_lut4.h"
 
 // The kernel's body (inlined into lut4_bwd_kernel, which carries the target attribute and the LDS).
-template <int IN, int OUT>
+// LA: nothing, or Mx4Lora: the compile-time LORA flag, set by the argument that carries what it needs.
+template <int IN, int OUT, class... LA>
 __device__ __forceinline__ void lut4_bwd_body(
     unsigned char (&image)[2][Mx4BwdCfg::BN * Mx4BwdCfg::BK * 2], unsigned short (&yimage)[2][Mx4BwdCfg::BT][Mx4BwdCfg::YPITCH],
     float (&lut)[16], int (&row_bad)[Mx4BwdCfg::BT],
     const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
-    const void *__restrict__ dy, void *__restrict__ dx, int bshift, int T, int K, int N)
+    const void *__restrict__ dy, void *__restrict__ dx, int bshift, int T, int K, int N, LA... lora)
 {
+    static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
+    constexpr bool LORA = sizeof...(LA) == 1;
     using C = Mx4BwdCfg;
     const int t_blk = (int)blockIdx.y * C::BT;
     const int kbase = (int)blockIdx.x * C::BK;
@@ -183,6 +192,53 @@ __device__ __forceinline__ void lut4_bwd_body(
         if (n0 + C::BN < N) run_stage(s1, s0, n0 + C::BN, it + 1);
     }
 
+    if constexpr (LORA) {
+        // The adapter stage (nv4_bwd_kernel's, without a global scale).  Every thread is behind the last stage's barrier,
+        // which no store followed: pair 0 of the images is free.  It is written in full, zeros from row `rank` on, past K
+        // and from column `rank` of dv on, so nothing of a weight stage meets a zero; then one barrier, then the steps.
+        // Every condition around a transposed read is uniform.
+        const Mx4Lora la{lora...};
+        const int rank = la.rank;
+        const float *vrow = la.rows + (size_t)ty * rank;
+        const bool a_ok = k_ok && sn < rank;
+        const float *arow = la.w + (size_t)(a_ok ? sn : 0) * K + (a_ok ? kp : 0);
+        const bool vec_v = (reinterpret_cast<uintptr_t>(la.rows) & 15) == 0, vec_a = (reinterpret_cast<uintptr_t>(la.w) & 15) == 0;
+        uint32_t yw[8], bad = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                              // dv[ty][16 yq + 4 i .. + 3]
+            const int j = 16 * yq + 4 * i;
+            mx4_lora_pack4(vrow + j, vec_v, j < rank, yw[2 * i], yw[2 * i + 1]);
+            bad |= mx4_nonfinite2(yw[2 * i]) | mx4_nonfinite2(yw[2 * i + 1]);
+        }
+        *reinterpret_cast<uint4 *>(&yimage[0][ys][16 * yq]) = make_uint4(yw[0], yw[1], yw[2], yw[3]);
+        *reinterpret_cast<uint4 *>(&yimage[0][ys][16 * yq + 8]) = make_uint4(yw[4], yw[5], yw[6], yw[7]);
+        if (bad & 0x80008000u) row_bad[ys] = 1;                    // (read behind the barrier below)
+        uint4 ch[4];                                               // chunk 4 sp + i of image row sn: A[sn][kp + 8 i .. + 7]
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            mx4_lora_pack4(arow + 8 * i, vec_a, a_ok, ch[i].x, ch[i].y);
+            mx4_lora_pack4(arow + 8 * i + 4, vec_a, a_ok, ch[i].z, ch[i].w);
+        }
+        if (wrot & 1) { const uint4 a = ch[0], b = ch[2]; ch[0] = ch[1]; ch[1] = a; ch[2] = ch[3]; ch[3] = b; }
+        if (wrot & 2) { const uint4 a = ch[0], b = ch[1]; ch[0] = ch[2]; ch[2] = a; ch[1] = ch[3]; ch[3] = b; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)                                // (ch[j] is chunk j ^ wrot now: store_stage's rotation)
+            *reinterpret_cast<uint4 *>(&image[0][w_off[j]]) = ch[j];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (16 * s >= rank) break;                             // (uniform)
+            const uint4 yb = *reinterpret_cast<const uint4 *>(&yimage[0][tr][16 * s + 8 * h]);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const mx4_v4s lo = mx4_tr_read(image[0] + a_off[b][0] + 4096 * s);
+                const mx4_v4s hi = mx4_tr_read(image[0] + a_off[b][1] + 4096 * s);
+                const v8bf a = __builtin_bit_cast(v8bf, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(v8bf, yb), acc[b], 0, 0, 0);
+            }
+        }
+    }
+
     // D[i][j]: i = k (A), j = t (B): the lane owns row t, registers 4q .. 4q+3 are k = 8 q + 4 h + (0 .. 3) of the block.
     // (Every write of row_bad lies behind a barrier.)
     const bool row_nan = row_bad[tr] != 0;
@@ -202,10 +258,11 @@ __device__ __forceinline__ void lut4_bwd_body(
 }
 
 // IN: element type of dY (FQL_DTYPE_F32 or FQL_DTYPE_BF16); OUT: element type of dX.  bshift = log2(B).
-template <int IN, int OUT>
+// LA: nothing (lut4_bwd_kernel<IN, OUT>: the signature, the code and the bits it always had), or Mx4Lora.
+template <int IN, int OUT, class... LA>
 __global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_bwd_kernel(
     const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
-    const void *__restrict__ dy, void *__restrict__ dx, int bshift, int T, int K, int N)
+    const void *__restrict__ dy, void *__restrict__ dx, int bshift, int T, int K, int N, LA... lora)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     using C = Mx4BwdCfg;
@@ -213,6 +270,6 @@ __global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_bwd_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short yimage[2][C::BT][C::YPITCH];    // gradient rows, bfloat16
     __shared__ float lut[16];
     __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite gradient
-    lut4_bwd_body<IN, OUT>(image, yimage, lut, row_bad, codes, absmax, book, dy, dx, bshift, T, K, N);
+    lut4_bwd_body<IN, OUT, LA...>(image, yimage, lut, row_bad, codes, absmax, book, dy, dx, bshift, T, K, N, lora...);
 #endif
 }

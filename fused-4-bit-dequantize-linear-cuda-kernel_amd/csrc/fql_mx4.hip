@@ -8,7 +8,7 @@
 // fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h),
 // the split-K decode form of the dense NVFP4 entries fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd (fql_gemm_nvfp4_linear.h),
 // with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels),
-// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h) with the split-K decode form fql_linear_lut4_split_fwd (fql_gemm_lut4_decode.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h) with their adapter forms fql_linear_lut4_lora_fwd / fql_linear_lut4_lora_bwd_input (the LORA flag of the two code-book tile kernels) and the split-K decode form fql_linear_lut4_split_fwd (fql_gemm_lut4_decode.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -492,11 +492,23 @@ struct Lut4Call {
     const float *bias;
     void *out;                         // out [T][N] or grad_in [T][K]
     int T, K, N;
+    bool lora = false;                 // an adapter entry (the tile kernels only): the three below are its operands
+    const float *lora_rows = nullptr;  // [T][rank]: v (forward) or dv (input gradient)
+    const float *lora_w = nullptr;     // [N][rank] B (forward) or [rank][K] A (input gradient)
+    int rank = 0;
 };
 
-// mx4_check's order for one dense matrix: shapes, the row and result types, the empty call, NULL pointers, the grid, then
-// alignment.  bt: the row tile of the kernel that will run; `bwd`: N == 0 is not empty (grad_in is zeros; nothing but the
-// result is dereferenced then).  *bshift = log2(block).
+// c with the operands of an adapter entry
+Lut4Call with_lora(Lut4Call c, const float *rows, const float *w, int rank)
+{
+    c.lora = true; c.lora_rows = rows; c.lora_w = w; c.rank = rank;
+    return c;
+}
+
+// mx4_check's order for one dense matrix: shapes, the row and result types, (an adapter entry: the rank), the empty call,
+// NULL pointers (the adapter operands with the others), the grid, then alignment.  bt: the row tile of the kernel that will
+// run; `bwd`: N == 0 is not empty (grad_in is zeros; nothing but the result is dereferenced then; an adapter entry refuses
+// it after this check).  *bshift = log2(block).
 int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd, bool *empty, int *bshift)
 {
     *empty = false;
@@ -505,13 +517,17 @@ int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd,
     if (c.K % 64 != 0) return FQL_ERR_BAD_SHAPE;
     if (c.block < 64 || (c.block & (c.block - 1)) != 0 || c.K % c.block != 0) return FQL_ERR_BAD_SHAPE;
     if ((in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
+    if (c.lora && c.rank != 4 && c.rank != 8 && c.rank != 16 && c.rank != 32 && c.rank != 64) return FQL_ERR_BAD_SHAPE;
     if (c.T == 0 || (c.N == 0 && !bwd)) { *empty = true; return FQL_OK; }
+    if (c.lora && c.N == 0) return FQL_ERR_BAD_SHAPE;                 // (the input gradient: dv A alone is not this entry's business)
     if (!c.out || (c.N != 0 && (!c.codes || !c.absmax || !c.rows))) return FQL_ERR_NULL_POINTER;
+    if (c.lora && (!c.lora_rows || !c.lora_w)) return FQL_ERR_NULL_POINTER;
     if ((c.T + bt - 1) / bt > 65535) return FQL_ERR_BAD_SHAPE;
     const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.codes) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3) || (reinterpret_cast<uintptr_t>(c.absmax) & 3) ||
         (reinterpret_cast<uintptr_t>(c.book) & 3)) return FQL_ERR_ALIGNMENT;
+    if ((reinterpret_cast<uintptr_t>(c.lora_rows) & 3) || (reinterpret_cast<uintptr_t>(c.lora_w) & 3)) return FQL_ERR_ALIGNMENT;   // (NULL without an adapter)
     int s = 6;
     while ((1 << s) < c.block) ++s;
     *bshift = s;
@@ -560,6 +576,14 @@ int launch_lut4_tile(int in_dtype, int out_dtype, const Lut4Call &c, int bshift,
 {
     using C = Lut4Cfg;
     const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT);
+    if (c.lora)                                                       // (the same tile and grid, the adapter stage behind the K loop)
+        return with_in_dtype(in_dtype, [&](auto in) {
+            return with_out_dtype(out_dtype, [&](auto o) {
+                return launch(lut4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, grid, dim3(C::THREADS), 0, st,
+                              c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N,
+                              Mx4Lora{c.lora_rows, c.lora_w, c.rank});
+            });
+        });
     return with_in_dtype(in_dtype, [&](auto in) {
         return with_out_dtype(out_dtype, [&](auto o) {
             return launch(lut4_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st,
@@ -1057,6 +1081,39 @@ FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax,
         return with_out_dtype(out_dtype, [&](auto o) {
             return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, static_cast<hipStream_t>(stream),
                           c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N);
+        });
+    });
+}
+
+// The adapter forms of the two code-book tile kernels: no workspace, no tune hook, never the decode form.
+FQL_API int fql_linear_lut4_lora_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                     int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
+                                     void *out, int out_dtype, int T, int K, int N, void *stream)
+{
+    const Lut4Call c = with_lora(Lut4Call{codes, absmax, code_book, block, inputs, bias, out, T, K, N}, lora_rows, lora_B, rank);
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, Lut4Cfg::BT, false, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_lut4_tile(in_dtype, out_dtype, c, bshift, static_cast<hipStream_t>(stream));
+}
+
+FQL_API int fql_linear_lut4_lora_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
+                                           const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A,
+                                           int rank, void *grad_in, int out_dtype, int T, int K, int N, void *stream)
+{
+    using C = Mx4BwdCfg;
+    const Lut4Call c = with_lora(Lut4Call{codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N}, lora_rows, lora_A, rank);
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);   // (N == 0 with rows: refused there)
+    if (rc != FQL_OK || empty) return rc;
+    const dim3 grid((K + C::BK - 1) / C::BK, (T + C::BT - 1) / C::BT);
+    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, grid, dim3(C::THREADS), 0,
+                          static_cast<hipStream_t>(stream), c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N,
+                          Mx4Lora{c.lora_rows, c.lora_w, c.rank});
         });
     });
 }

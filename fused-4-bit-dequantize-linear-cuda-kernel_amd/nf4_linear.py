@@ -1,6 +1,7 @@
 """``NF4Linear``: a dense ``nn.Linear`` on 4-bit code-book weights in bitsandbytes' own encoding (NF4 of QLoRA, Hugging Face
 ``load_in_4bit``, the ``*-bnb-4bit`` checkpoints), frozen (csrc/fql_gemm_lut4.h, csrc/fql_gemm_lut4_bwd.h; DESIGN.md section
-44), and ``LoRANF4Linear``, the same layer with a trainable low-rank adapter composed from the existing adapter ops."""
+44), and ``LoRANF4Linear``, the same layer with a trainable low-rank adapter, composed from the existing adapter ops or, with
+``fused=True``, run as one more contraction stage of the two tile kernels."""
 import math
 
 import torch
@@ -145,13 +146,22 @@ class LoRANF4Linear(NF4Linear):
     ``s = alpha / rank``, any leading dimensions.  The code-book buffers (and the bias) are frozen; ``lora_A`` [r, K] and
     ``lora_B`` [N, r] float32, PEFT's initialisation, are the only parameters, so the state-dict keys are the base layer's
     plus ``lora_A`` and ``lora_B``.  Composed from ``ops.linear_forward_lut4`` / ``linear_backward_input_lut4`` and
-    ``ops.lora_shrink`` / ``lora_expand`` / ``lora_grad`` in one autograd node (``ops.linear_lora_forward_lut4``): no fused
-    adapter stage.  A fresh layer (``B = 0``) returns ``NF4Linear``'s bits.  The adapter path runs on the GPU only."""
+    ``ops.lora_shrink`` / ``lora_expand`` / ``lora_grad`` in one autograd node (``ops.linear_lora_forward_lut4``).  A fresh
+    layer (``B = 0``) returns ``NF4Linear``'s bits.  The adapter path runs on the GPU only.
+
+    ``fused=True`` (configuration, not state; the default is False and the composed route's bits) runs the adapter inside
+    the tile kernels: ``v = s * x @ lora_A.T`` by ``ops.lora_shrink``, then ``ops.linear_forward_lut4_lora`` in one launch, and
+    ``ops.linear_backward_input_lut4_lora`` for ``x.grad``; no float32 [T, N] or [T, K] tensor exists.  That route rounds
+    ``v``, ``lora_B``, ``dv`` and ``lora_A`` once to bfloat16 on their way into the matrix cores.  It has no ``split_k`` form:
+    the two together raise ``ValueError``."""
 
     def __init__(self, in_features: int, out_features: int, rank: int, alpha: float | None = None, bias: bool = False,
-                 input_grad: bool = True, block: int = 64, split_k: bool = False):
+                 input_grad: bool = True, block: int = 64, split_k: bool = False, fused: bool = False):
         del input_grad                                                                 # (always on: the layer is for training)
+        if fused and split_k:
+            raise ValueError("fused=True runs the tile kernel's adapter stage; it has no split_k form")
         super().__init__(in_features, out_features, bias=bias, input_grad=True, block=block, split_k=split_k)
+        self.fused = bool(fused)
         from .ops import LORA_RANKS
         if rank not in LORA_RANKS:
             raise ValueError(f"rank must be one of {LORA_RANKS}, got {rank!r}")
@@ -173,16 +183,16 @@ class LoRANF4Linear(NF4Linear):
 
     @classmethod
     def from_bnb(cls, *args, **kwargs) -> "LoRANF4Linear":
-        """``NF4Linear.from_bnb`` with ``rank=`` (and ``alpha=``) among the keywords (``from_linear`` takes them the same
-        way); the adapters are created on the device of the codes."""
+        """``NF4Linear.from_bnb`` with ``rank=`` (and ``alpha=``, ``fused=``) among the keywords (``from_linear`` takes them
+        the same way); the adapters are created on the device of the codes."""
         module = super().from_bnb(*args, **kwargs)
         return module._adapters_to(module.codes.device)
 
     @classmethod
-    def from_layer(cls, layer: NF4Linear, rank: int, alpha: float | None = None) -> "LoRANF4Linear":
+    def from_layer(cls, layer: NF4Linear, rank: int, alpha: float | None = None, fused: bool = False) -> "LoRANF4Linear":
         """Wrap an existing ``NF4Linear``; the new module shares its buffers (no copy)."""
         module = cls(layer.in_features, layer.out_features, rank, alpha, bias=layer.bias is not None, block=layer.block,
-                     split_k=layer.split_k)
+                     split_k=layer.split_k, fused=fused)
         for name, buf in layer.named_buffers():
             setattr(module, name, buf)
         return module._adapters_to(layer.codes.device)
@@ -198,8 +208,9 @@ class LoRANF4Linear(NF4Linear):
                                f"got {list(x.shape)}")
         from . import ops
         y = ops.linear_lora_forward_lut4(x.reshape(-1, self.in_features), self.codes, self.absmax, self.lora_A, self.lora_B,
-                                         self.scaling, self.code_book, self.block, bias=self.bias, split_k=self.split_k)
+                                         self.scaling, self.code_book, self.block, bias=self.bias, split_k=self.split_k,
+                                         fused=self.fused)
         return y.reshape(*x.shape[:-1], self.out_features)
 
     def extra_repr(self) -> str:
-        return f"{super().extra_repr()}, rank={self.rank}, alpha={self.alpha:g}"
+        return f"{super().extra_repr()}, rank={self.rank}, alpha={self.alpha:g}" + (", fused=True" if self.fused else "")

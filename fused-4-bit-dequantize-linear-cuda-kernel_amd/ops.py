@@ -2773,10 +2773,13 @@ class _NVFP4LinearLoRAFn(torch.autograd.Function):
 # DESIGN.md section 44)
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias, out_dtype, default_dtype, split_k=False):
-    """Both code-book ops, section 14's order: types and shapes first, then the devices.  ``rows`` [T, cols(K, N)] float32 /
-    bfloat16; the result is [T, K + N - cols(K, N)].  ``split_k`` (forward): the split entry, ``fql_linear_lut4_split_fwd``,
-    with its workspace allocated here as ``_nvfp4_launch`` allocates its own."""
+def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias, out_dtype, default_dtype, split_k=False,
+                 lora=None):
+    """Both code-book ops and, with ``lora`` = (the shrunk rows [T, r], the adapter matrix: ``lora_B`` [N, r] forward,
+    ``lora_A`` [r, K] input gradient), their adapter forms (``entry`` is the ``_lora`` entry then).  Section 14's order: types
+    and shapes first, then the devices.  ``rows`` [T, cols(K, N)] float32 / bfloat16; the result is [T, K + N - cols(K, N)].
+    ``split_k`` (forward): the split entry, ``fql_linear_lut4_split_fwd``, with its workspace allocated here as
+    ``_nvfp4_launch`` allocates its own."""
     what = "the rows" if bias is not False else "grad_out"
     if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: {what} must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
@@ -2795,6 +2798,10 @@ def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias,
         raise RuntimeError("code_book must be a float32 [16] tensor, or None for the NF4 table")
     if bias is not None and bias is not False and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,)):
         raise RuntimeError("bias must be a float32 [N] tensor")
+    T = rows.shape[0]
+    extra = ()
+    if lora is not None:
+        r = _nvfp4_lora_operands(name, lora, T, (lambda r: (r, K)) if bias is False else (lambda r: (N, r)))
     out_dtype = default_dtype if out_dtype is None else out_dtype
     if out_dtype not in _DTYPES:
         raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
@@ -2802,13 +2809,15 @@ def _lut4_launch(name, entry, codes, absmax, rows, cols, code_book, block, bias,
         raise RuntimeError(f"ops.{name}: {what} must be a CUDA tensor")
     dev = rows.device
     _on(dev, codes=codes, absmax=absmax, code_book=code_book, bias=None if bias is False else bias)
-    T = rows.shape[0]
+    if lora is not None:
+        _on(dev, lora_rows=lora[0], lora_weight=lora[1])
+        extra = (lora[0].contiguous(), lora[1].contiguous(), r)
     out = torch.empty((T, K + N - cols(K, N)), dtype=out_dtype, device=dev)
     book = None if code_book is None else code_book.contiguous()
     b = () if bias is False else (None if bias is None else bias.contiguous(),)
     ws_bytes = _native.lib().fql_linear_lut4_split_workspace_bytes(T, K, N) if split_k else None
-    _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *b, out,
-            _DTYPES[out_dtype], T, K, N, ws_bytes=ws_bytes)
+    _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *extra, *b,
+            out, _DTYPES[out_dtype], T, K, N, ws_bytes=ws_bytes)
     return out
 
 
@@ -2843,6 +2852,26 @@ def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64
                         code_book, block, False, out_dtype, torch.float32)
 
 
+def linear_forward_lut4_lora(codes, absmax, x, v, lora_B, code_book=None, block=64, bias=None, out_dtype=None):
+    """``linear_forward_lut4`` with the adapter fused into the tile kernel as one more contraction stage:
+    ``out[t] = W @ bf16(x[t]) + bf16(lora_B) @ bf16(v[t]) (+ bias)``, float32 sums (the adapter's sixteen columns a step
+    behind the weights'), one rounding to ``out_dtype`` (default: ``x``'s type).  ``v`` [T, r] float32, the caller's shrunk
+    rows (``scaling * x @ lora_A^T``); ``lora_B`` [N, r] float32; r one of ``LORA_RANKS``.  ``v`` and ``lora_B`` are rounded
+    once to bfloat16.  A non-finite element of a row of ``x`` or ``v`` makes that row NaN; with ``lora_B == 0`` the result is
+    ``linear_forward_lut4``'s bits.  Always the tile kernel.  Forward only."""
+    _forward_only("linear_forward_lut4_lora", x, v, lora_B, bias)
+    return _lut4_launch("linear_forward_lut4_lora", "fql_linear_lut4_lora_fwd", codes, absmax, x, lambda K, N: K, code_book, block,
+                        bias, out_dtype, x.dtype if isinstance(x, torch.Tensor) else None, lora=(v, lora_B))
+
+
+def linear_backward_input_lut4_lora(codes, absmax, grad_out, dv, lora_A, code_book=None, block=64, out_dtype=None):
+    """``linear_backward_input_lut4`` with the adapter's share fused in: ``grad_in[t] = bf16(grad_out[t]) @ W + bf16(dv[t]) @
+    bf16(lora_A)``; ``dv`` [T, r] float32 (``scaling * grad_out @ lora_B``), ``lora_A`` [r, K] float32 -> [T, K]
+    ``out_dtype`` (default float32).  With ``lora_A == 0`` the result is ``linear_backward_input_lut4``'s bits."""
+    return _lut4_launch("linear_backward_input_lut4_lora", "fql_linear_lut4_lora_bwd_input", codes, absmax, grad_out,
+                        lambda K, N: N, code_book, block, False, out_dtype, torch.float32, lora=(dv, lora_A))
+
+
 def _lut4_lora_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bias, split_k=False):
     """Base forward to float32, u = x A^T, then y = base + scaling * u B^T in x's type, one rounding.  Returns (y, u)."""
     y32 = linear_forward_lut4(codes, absmax, x2, book, block, bias=bias, out_dtype=torch.float32, split_k=split_k)
@@ -2850,16 +2879,29 @@ def _lut4_lora_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bi
     return _expand_into(u, lora_B, "cr", y32, x2.dtype, scale=scaling), u
 
 
-def linear_lora_forward_lut4(x, codes, absmax, lora_A, lora_B, scaling, code_book=None, block=64, bias=None, split_k=False):
+def linear_lora_forward_lut4(x, codes, absmax, lora_A, lora_B, scaling, code_book=None, block=64, bias=None, split_k=False,
+                             fused=False):
     """``linear_forward_lut4`` plus a low-rank adapter, ``y = W bf16(x) (+ bias) + scaling * (x @ lora_A^T) @ lora_B^T``,
     composed from the two code-book ops and ``lora_shrink`` / ``lora_expand`` / ``lora_grad`` in one autograd node (no
     fused adapter stage).  ``x`` [T, K] float32 or bfloat16, float32 ``lora_A`` [r, K] and ``lora_B`` [N, r]; the result
     has ``x``'s type, rounded once.  Differentiable in ``x``, ``lora_A`` and ``lora_B``; the code-book weights and the bias
     are frozen.  With ``lora_B == 0`` the result is ``linear_forward_lut4``'s bits.  ``split_k`` is passed on to the base
-    forward (its contract is ``linear_forward_lut4``'s); the adapter and the backward are the same either way."""
+    forward (its contract is ``linear_forward_lut4``'s); the adapter and the backward are the same either way.
+
+    ``fused=True`` runs the adapter inside the two tile kernels instead (``linear_forward_lut4_lora`` /
+    ``linear_backward_input_lut4_lora``, the node of ``linear_lora_forward_nvfp4``'s shape): ``v = scaling * x @ lora_A^T``
+    by ``lora_shrink``, then one launch for ``y``; no float32 [T, N] or [T, K] tensor exists.  That route rounds ``v``,
+    ``lora_B``, ``dv`` and ``lora_A`` once to bfloat16 on their way into the matrix cores, so its bits are not the composed
+    route's (the default, unchanged).  ``fused`` with ``split_k`` raises ``ValueError``: the stage lives in the tile kernel."""
+    if fused and split_k:
+        raise ValueError("ops.linear_lora_forward_lut4: fused=True runs the tile kernel's adapter stage; it has no split_k form")
     if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
         raise RuntimeError("ops.linear_lora_forward_lut4: x must be a CUDA float32 or bfloat16 [T, K] tensor")
     _lora_check_adapters(lora_A, lora_B, x.shape[1], codes.shape[0], None)
+    if fused:
+        if _wants_grad(x, lora_A, lora_B):
+            return _LUT4LinearLoRAFusedFn.apply(x, lora_A, lora_B, codes, absmax, code_book, block, bias, float(scaling))
+        return _lut4_lora_fused_apply(x.contiguous(), codes, absmax, code_book, block, lora_A, lora_B, float(scaling), bias)[0]
     if _wants_grad(x, lora_A, lora_B):
         return _LUT4LinearLoRAFn.apply(x, lora_A, lora_B, codes, absmax, code_book, block, bias, float(scaling), bool(split_k))
     return _lut4_lora_apply(x.contiguous(), codes, absmax, code_book, block, lora_A, lora_B, float(scaling), bias, bool(split_k))[0]
@@ -2895,3 +2937,41 @@ class _LUT4LinearLoRAFn(torch.autograd.Function):
         if need_B:
             gB = lora_grad(g, u, "cr", scale=ctx.scaling)[0]                             # dB = s dY^T u
         return gx, gA, gB, None, None, None, None, None, None, None
+
+
+def _lut4_lora_fused_apply(x, codes, absmax, book, block, lora_A, lora_B, scaling, bias):
+    """(y, v): the shrink (scale included) and the tile kernel with its adapter stage."""
+    x = x.detach()
+    v = lora_shrink(x, lora_A.detach(), "rc", scale=scaling)
+    return linear_forward_lut4_lora(codes, absmax, x, v, lora_B.detach(), book, block, bias=bias, out_dtype=x.dtype), v
+
+
+class _LUT4LinearLoRAFusedFn(torch.autograd.Function):
+    """Code-book linear + fused adapter in one node (``_NVFP4LinearLoRAFn``'s shape).  Saves x (in its own type) and
+    v = s x A^T ([T, r] float32): nothing of shape [T, N], nothing dequantised."""
+
+    @staticmethod
+    def forward(ctx, x, lora_A, lora_B, codes, absmax, book, block, bias, scaling):
+        x2 = x.detach().contiguous()
+        y, v = _lut4_lora_fused_apply(x2, codes, absmax, book, block, lora_A, lora_B, scaling, bias)
+        ctx.save_for_backward(x2, v, lora_A, lora_B, codes, absmax)
+        ctx.book, ctx.block, ctx.scaling = book, block, scaling
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x2, v, lora_A, lora_B, codes, absmax = ctx.saved_tensors
+        need_x, need_A, need_B = ctx.needs_input_grad[:3]
+        check_activation_rows(gy, "the incoming gradient", x2.dtype)
+        g = gy.contiguous()
+        gx = gA = gB = None
+        if need_B:
+            gB = lora_grad(g, v, "cr")[0]                                                # dB = dY^T v (s is in v)
+        if need_x or need_A:
+            dv = lora_shrink(g, lora_B, "cr", scale=ctx.scaling)                         # dv = s dY B
+            if need_A:
+                gA = lora_grad(x2, dv, "rc")[0]                                          # dA = dv^T x
+            if need_x:
+                gx = linear_backward_input_lut4_lora(codes, absmax, g, dv, lora_A, ctx.book, ctx.block, out_dtype=x2.dtype)
+        return gx, gA, gB, None, None, None, None, None, None

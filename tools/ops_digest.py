@@ -27,7 +27,7 @@ form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``;
 tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands, and last the five NVFP4 adapter
 ops (``moe_forward_nvfp4_lora`` and its kin) on them, and the two dense NVFP4 ops with ``split_k=True`` at 2 and at 16 forced
 slices; then the two code-book (NF4) ops and, last, ``linear_forward_lut4(split_k=True)`` at the policy's S and at 2 and 16
-forced slices."""
+forced slices; last of all ``linear_forward_lut4_lora`` / ``linear_backward_input_lut4_lora`` at ranks 4, 32 and 64."""
 import argparse
 import hashlib
 import os
@@ -588,6 +588,17 @@ def calls(dev, fq, ops):
             for dt in (F32, BF16):
                 yield f"linear_forward_lut4 {btag} {dt} split S={slices or 'policy'}", forced_lut4(slices, lambda: ops.linear_forward_lut4(
                     codes, absmax, xl[:16].to(dt), bk, 64, bias=bl, split_k=True))
+
+    # the two fused adapter forms of the code-book tile kernels, behind every earlier call (their draws come last): r = 4 (a
+    # partial step), 32 (the full pair of images) and 64 (the second pair)
+    for r in (4, 32, 64):
+        vl, Bl, dvl, Al = d.randn(Tl, r), d.randn(Nl, r), d.randn(Tl, r), d.randn(r, Kl)
+        for btag, bk in (("nf4", None), ("own table", book)):
+            for dt in (F32, BF16):
+                yield f"linear_forward_lut4_lora r={r} {btag} {dt}", lambda: ops.linear_forward_lut4_lora(
+                    codes, absmax, xl.to(dt), vl, Bl, bk, 64, bias=bl)
+                yield f"linear_backward_input_lut4_lora r={r} {btag} {dt}", lambda: ops.linear_backward_input_lut4_lora(
+                    codes, absmax, gl.to(dt), dvl, Al, bk, 64, out_dtype=dt)
 
 
 def digest(t):
