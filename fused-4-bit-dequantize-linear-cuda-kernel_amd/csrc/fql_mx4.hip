@@ -1,14 +1,21 @@
-// libfql_int4.so, the MXFP4 expert weights (include/fql_int4.h): the bfloat16 entries fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd /
-// fql_moe_mx4_bwd_input (fql_gemm_mx4.h, fql_gemm_mx4_decode.h, fql_gemm_mx4_bwd.h) and their adapter forms fql_moe_mx4_lora_fwd /
-// fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input (the LORA flag of the two tile kernels), the block-scaled entries on fp8 rows
-// fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8, on MXFP4 rows fql_moe_mx4_fwd_f4 / _fwd_q4 / _glu_fwd_q4 and on MXFP6 rows
-// fql_moe_mx4_fwd_f6 / _fwd_q6 / _glu_fwd_q6 (one tile and one decode kernel for the three, fql_gemm_mx4_scaled.h and
-// fql_gemm_mx4_sdecode.h), the row pre-passes with fql_mx4_quantize_rows / fql_mx6_quantize_rows (fql_mx4_quant.h) and the dense
-// linear entries fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd with their split-K decode form (fql_gemm_mx4_linear.h), and the NVFP4 entries
-// fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd (fql_gemm_nvfp4.h) and fql_moe_nvfp4_bwd_input (fql_gemm_nvfp4_bwd.h),
-// the split-K decode form of the dense NVFP4 entries fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd (fql_gemm_nvfp4_linear.h),
-// with their adapter forms fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input and fql_linear_nvfp4_lora_fwd / _lora_bwd_input (the LORA flag of the two NVFP4 tile kernels),
-// and the dense 4-bit code-book (NF4) entries fql_linear_lut4_fwd / fql_linear_lut4_bwd_input (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h) with their adapter forms fql_linear_lut4_lora_fwd / fql_linear_lut4_lora_bwd_input (the LORA flag of the two code-book tile kernels) and the split-K decode form fql_linear_lut4_split_fwd (fql_gemm_lut4_decode.h).  Host-side validation and launches only, as in fql_int4.hip: no allocation, no synchronisation.
+// libfql_int4.so, the 4-bit float weight families (include/fql_int4.h).  Host-side validation and launches only, as in
+// fql_int4.hip: no allocation, no synchronisation.  DESIGN.md section 47 describes how the host code below is shared.
+//
+//   family                      entries                                                          kernels
+//   MXFP4 experts, float rows   fql_moe_mx4_fwd / _glu_fwd / _bwd_input                          fql_gemm_mx4.h, fql_gemm_mx4_decode.h,
+//     with an adapter           fql_moe_mx4_lora_fwd / _glu_lora_fwd / _lora_bwd_input           fql_gemm_mx4_bwd.h (LORA: a flag of the tile kernels)
+//   MXFP4 experts, scaled rows  fql_moe_mx4_fwd_f8 / _fwd_q8 / _glu_fwd_q8 (fp8 rows),           fql_gemm_mx4_scaled.h, fql_gemm_mx4_sdecode.h
+//                               _fwd_f4 / _fwd_q4 / _glu_fwd_q4 (MXFP4), _f6 / _q6 (MXFP6)       (one tile and one decode kernel for the three)
+//   row pre-passes              fql_mx4_quantize_rows / fql_mx6_quantize_rows                    fql_mx4_quant.h
+//   MXFP4 dense                 fql_linear_mx4_fwd / _glu_fwd (split_k: the split-K decode form) fql_gemm_mx4_linear.h
+//   NVFP4 experts and dense     fql_moe_nvfp4_fwd / _glu_fwd / _bwd_input,                       fql_gemm_nvfp4.h, fql_gemm_nvfp4_bwd.h
+//                               fql_linear_nvfp4_fwd / _glu_fwd
+//     with an adapter           fql_moe_nvfp4_lora_fwd / _glu_lora_fwd / _lora_bwd_input,        (LORA: a flag of the two tile kernels)
+//                               fql_linear_nvfp4_lora_fwd / _lora_bwd_input
+//     split-K decode form       fql_linear_nvfp4_split_fwd / _glu_split_fwd                      fql_gemm_nvfp4_linear.h
+//   code book (NF4), dense      fql_linear_lut4_fwd / _bwd_input                                 fql_gemm_lut4.h, fql_gemm_lut4_bwd.h
+//     with an adapter           fql_linear_lut4_lora_fwd / _lora_bwd_input                       (LORA: a flag of the two tile kernels)
+//     split-K decode form       fql_linear_lut4_split_fwd                                        fql_gemm_lut4_decode.h
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -33,6 +40,37 @@ namespace {
 
 using namespace fql_host;
 
+// The operands of an adapter entry (the tile kernels only), the same in every family's call record.
+struct LoraOperands {
+    bool on = false;                   // an adapter entry: the three below are its operands
+    const float *rows = nullptr;       // [T][rank]: v (forward) or dv (input gradient)
+    const float *w = nullptr;          // [E][N][rank] B (forward) or [E][rank][K] A (input gradient); dense: E = 1
+    int rank = 0;
+};
+
+// c (an Mx4Call or a Lut4Call) with the operands of an adapter entry
+template <class Call>
+Call with_lora(Call c, const float *rows, const float *w, int rank)
+{
+    c.lora = {true, rows, w, rank};
+    return c;
+}
+
+// The three tests of an adapter's operands; mx4_check and lut4_check each place them in their documented order.
+bool lora_rank_bad(const LoraOperands &l) { return l.on && l.rank != 4 && l.rank != 8 && l.rank != 16 && l.rank != 32 && l.rank != 64; }
+bool lora_null(const LoraOperands &l) { return l.on && (!l.rows || !l.w); }
+bool lora_misaligned(const LoraOperands &l)                          // (both NULL without an adapter)
+{
+    return (reinterpret_cast<uintptr_t>(l.rows) & 3) || (reinterpret_cast<uintptr_t>(l.w) & 3);
+}
+
+// f(), or f(Mx4Lora) for an adapter call: the one kernel argument more of a tile kernel's LORA form
+template <class F>
+int with_lora_arg(const LoraOperands &l, F &&f)
+{
+    return l.on ? f(Mx4Lora{l.rows, l.w, l.rank}) : f();
+}
+
 struct Mx4Call {
     const uint8_t *blocks, *scales;
     const void *rows;                 // [T][K] of in_dtype
@@ -42,10 +80,7 @@ struct Mx4Call {
     int E, T, K, N;
     const float *act_scale = nullptr;  // [T] or NULL (fp8 rows only)
     const uint8_t *row_scales = nullptr;  // [T][K / 32] E8M0 (MXFP4 and MXFP6 rows only)
-    bool lora = false;                 // an adapter entry (bfloat16 kernels only): the three below are its operands
-    const float *lora_rows = nullptr;  // [T][rank]: v (forward) or dv (input gradient)
-    const float *lora_w = nullptr;     // [E][N][rank] B (forward) or [E][rank][K] A (input gradient)
-    int rank = 0;
+    LoraOperands lora;                 // (bfloat16 kernels only)
     bool nvfp4 = false;                // an NVFP4 entry: `scales` is [E][N][K / 16] e4m3 bytes, and
     const float *gscale = nullptr;     // [E] float32 or NULL (1): the per-tensor scales
 };
@@ -54,13 +89,6 @@ struct Mx4Call {
 Mx4Call with_nvfp4(Mx4Call c, const float *global_scale)
 {
     c.nvfp4 = true; c.gscale = global_scale;
-    return c;
-}
-
-// c with the operands of an adapter entry
-Mx4Call with_lora(Mx4Call c, const float *rows, const float *w, int rank)
-{
-    c.lora = true; c.lora_rows = rows; c.lora_w = w; c.rank = rank;
     return c;
 }
 
@@ -82,6 +110,12 @@ int with_in_dtype(int in_dtype, F &&f)
 {
     return in_dtype == FQL_DTYPE_F32 ? f(std::integral_constant<int, FQL_DTYPE_F32>{}) : f(std::integral_constant<int, FQL_DTYPE_BF16>{});
 }
+// ... and f(in, out) for both: the nest around every kernel with the two element types as template arguments
+template <class F>
+int with_dtypes(int in_dtype, int out_dtype, F &&f)
+{
+    return with_in_dtype(in_dtype, [&](auto in) { return with_out_dtype(out_dtype, [&](auto o) { return f(in, o); }); });
+}
 
 // The grid of a grouped kernel with tiles of bt rows x bc columns of out [T][cols]: one more z-slice zeroes the rows no
 // expert covers.
@@ -99,73 +133,40 @@ dim3 mx4_grid(const Mx4Call &c, int cols, int bc, int bt)
 #define FQL_MX4_F6_DECODE_MAX_ROWS 8   /* ... the MXFP6-row decode kernel: the same rule */
 int g_mx4_decode_max_rows[4] = {FQL_MX4_DECODE_MAX_ROWS, FQL_MX4_F8_DECODE_MAX_ROWS, FQL_MX4_F4_DECODE_MAX_ROWS,
                                 FQL_MX4_F6_DECODE_MAX_ROWS};   // by rows kind
-
-bool mx4_use_decode(int rows_kind, int T)
-{
-    static_assert(Mx4DecodeCfg::BT == Mx4SDecodeCfg::BT, "one bound on the grid's y for both decode kernels");
-    return T > 0 && T <= g_mx4_decode_max_rows[rows_kind] && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;   // (no overflow at a hook's T = INT_MAX)
-}
-
-// The bfloat16 forward: c.rows is [T][K] float32 or bfloat16.  An adapter call always takes the tile kernel (training: the
-// decode kernel has no adapter form).
-int launch_mx4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
-{
-    using C = Mx4Cfg;
-    using D = Mx4DecodeCfg;
-    if (c.lora)
-        return with_in_dtype(in_dtype, [&](auto in) {
-            return with_out_dtype(out_dtype, [&](auto o) {
-                return launch(mx4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, c.N, C::BN, C::BT), dim3(C::THREADS), 0, st,
-                              c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-            });
-        });
-    const bool decode = mx4_use_decode(ROWS_FLOAT, c.T);
-    const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
-    return with_in_dtype(in_dtype, [&](auto in) {
-        return with_out_dtype(out_dtype, [&](auto o) {
-            constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
-            return launch(decode ? mx4_decode_kernel<IN, OUT> : mx4_kernel<IN, OUT>, grid, dim3(decode ? D::THREADS : C::THREADS), 0, st,
-                          c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
-        });
-    });
-}
-
 // The NVFP4 forward (fql_gemm_nvfp4.h): the same pair of kernels, the same bits from both, a threshold of its own.
 #define FQL_NVFP4_DECODE_MAX_ROWS 512  /* rows (T) up to which the decode kernel runs: the largest count of the sweep up to which it wins at every point of both shapes */
 int g_nvfp4_decode_max_rows = FQL_NVFP4_DECODE_MAX_ROWS;
 
-bool nvfp4_use_decode(int T)
+// The row-threshold predicate of every decode kernel, one-wave or split: all of them run on row tiles of Mx4DecodeCfg::BT.
+bool decode_rows(int max_rows, int T)
 {
-    return T > 0 && T <= g_nvfp4_decode_max_rows && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;
+    static_assert(Mx4DecodeCfg::BT == Mx4SDecodeCfg::BT, "one bound on the grid's y for both decode kernels");
+    return T > 0 && T <= max_rows && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;   // (no overflow at a hook's T = INT_MAX)
 }
 
-int launch_nvfp4(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
+// The bfloat16 GEMM of a call with float rows (float32 or bfloat16), MXFP4 or NVFP4 weights by c.nvfp4.  An adapter call
+// always takes the tile kernel (training: the decode kernel has no adapter form).
+int launch_float_rows(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
 {
     using C = Mx4Cfg;
     using D = Mx4DecodeCfg;
-    if (c.lora)                                                       // (always the tile kernel, as launch_mx4's adapter call)
-        return with_in_dtype(in_dtype, [&](auto in) {
-            return with_out_dtype(out_dtype, [&](auto o) {
-                return launch(nv4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, c.N, C::BN, C::BT), dim3(C::THREADS), 0, st,
-                              c.blocks, c.scales, c.gscale, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N,
-                              Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-            });
-        });
-    const bool decode = nvfp4_use_decode(c.T);
+    const bool decode = !c.lora.on && decode_rows(c.nvfp4 ? g_nvfp4_decode_max_rows : g_mx4_decode_max_rows[ROWS_FLOAT], c.T);
     const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
-    return with_in_dtype(in_dtype, [&](auto in) {
-        return with_out_dtype(out_dtype, [&](auto o) {
-            constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
-            return launch(decode ? nv4_decode_kernel<IN, OUT> : nv4_kernel<IN, OUT>, grid, dim3(decode ? D::THREADS : C::THREADS), 0, st,
-                          c.blocks, c.scales, c.gscale, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
+    const dim3 block(decode ? D::THREADS : C::THREADS);
+    // one launch per kernel signature: the NVFP4 kernels take the per-tensor scales behind the block scales
+    auto mx = [&](auto kern, auto... la) {
+        return launch(kern, grid, block, 0, st, c.blocks, c.scales, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, la...);
+    };
+    auto nv = [&](auto kern, auto... la) {
+        return launch(kern, grid, block, 0, st, c.blocks, c.scales, c.gscale, c.rows, c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, la...);
+    };
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
+        if (decode) return c.nvfp4 ? nv(nv4_decode_kernel<IN, OUT>) : mx(mx4_decode_kernel<IN, OUT>);
+        return with_lora_arg(c.lora, [&](auto... la) {
+            return c.nvfp4 ? nv(nv4_kernel<IN, OUT, decltype(la)...>, la...) : mx(mx4_kernel<IN, OUT, decltype(la)...>, la...);
         });
     });
-}
-
-// The bfloat16 GEMM of a call with float rows, by the format of its weights.
-int launch_float_rows(int in_dtype, int out_dtype, const Mx4Call &c, hipStream_t st)
-{
-    return c.nvfp4 ? launch_nvfp4(in_dtype, out_dtype, c, st) : launch_mx4(in_dtype, out_dtype, c, st);
 }
 
 // The block-scaled forward: c.rows is [T][K] e4m3 bytes with c.act_scale (ROWS_E4M3), or [T][K / 2] packed e2m1 with
@@ -176,7 +177,7 @@ int launch_mx4_scaled(int out_dtype, const Mx4Call &c, hipStream_t st)
     using C = Mx4ScaledCfg;
     using D = Mx4SDecodeCfg;
     static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the bfloat16 kernel's row tile");
-    const bool decode = mx4_use_decode(ROWS, c.T);
+    const bool decode = decode_rows(g_mx4_decode_max_rows[ROWS], c.T);
     const dim3 grid = decode ? mx4_grid(c, c.N, D::BN, D::BT) : mx4_grid(c, c.N, C::BN, C::BT);
     return with_out_dtype(out_dtype, [&](auto o) {
         constexpr int OUT = decltype(o)::value;
@@ -198,10 +199,10 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     if (c.K & 1) return FQL_ERR_ODD_K;
     if (c.K % 32 != 0) return FQL_ERR_BAD_SHAPE;                      // one scale per 32 inputs
     if ((!byte_rows && in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
-    if (c.lora && c.rank != 4 && c.rank != 8 && c.rank != 16 && c.rank != 32 && c.rank != 64) return FQL_ERR_BAD_SHAPE;
+    if (lora_rank_bad(c.lora)) return FQL_ERR_BAD_SHAPE;
     if (c.T == 0 || c.N == 0) { *empty = true; return FQL_OK; }
     if (!c.blocks || !c.scales || !c.rows || !c.out) return FQL_ERR_NULL_POINTER;
-    if (c.lora && (!c.lora_rows || !c.lora_w)) return FQL_ERR_NULL_POINTER;
+    if (lora_null(c.lora)) return FQL_ERR_NULL_POINTER;
     if ((rows_kind == ROWS_MXFP4 || rows_kind == ROWS_MXFP6) && !c.row_scales) return FQL_ERR_NULL_POINTER;
     if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
     if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
@@ -211,7 +212,7 @@ int mx4_check(const Mx4Call &c, int in_dtype, int out_dtype, bool act_ok, bool *
     const int ib = byte_rows ? 1 : dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.blocks) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3)) return FQL_ERR_ALIGNMENT;
-    if ((reinterpret_cast<uintptr_t>(c.lora_rows) & 3) || (reinterpret_cast<uintptr_t>(c.lora_w) & 3)) return FQL_ERR_ALIGNMENT;   // (NULL without an adapter)
+    if (lora_misaligned(c.lora)) return FQL_ERR_ALIGNMENT;
     if (reinterpret_cast<uintptr_t>(c.gscale) & 3) return FQL_ERR_ALIGNMENT;                                                        // (NULL but for NVFP4)
     if (rows_kind == ROWS_MXFP4 && !aligned16(c.rows)) return FQL_ERR_ALIGNMENT;
     if (rows_kind == ROWS_MXFP6 && (reinterpret_cast<uintptr_t>(c.rows) & 7)) return FQL_ERR_ALIGNMENT;
@@ -274,6 +275,15 @@ int launch_mx4_quant(const void *rows, int in_dtype, const Mx4Act &a, void *q, v
     });
 }
 
+// A grouped entry on float rows with nothing before the GEMM: the checks, the launch.
+int mx4_float_fwd(const Mx4Call &c, int in_dtype, int out_dtype, void *stream)
+{
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_float_rows(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+}
+
 // An entry that runs a pre-pass into the workspace and then the GEMM on what it wrote: the checks, the workspace, the two
 // launches.
 template <int ROWS>
@@ -308,166 +318,161 @@ int mx4_scaled_fwd(const Mx4Call &c, int out_dtype, void *stream)
     return launch_mx4_scaled<ROWS>(out_dtype, c, static_cast<hipStream_t>(stream));
 }
 
-// ---- the dense linear layer (fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd): E = 1, no table, and with split_k set and few rows
-//      the decode kernel cut along K (fql_gemm_mx4_linear.h) ----
+// The input gradient of a grouped entry, MXFP4 or NVFP4 weights, with or without an adapter: c.rows is grad_out [T][N],
+// c.out grad_in [T][K].
+int mx4_bwd_input(const Mx4Call &c, int in_dtype, int out_dtype, void *stream)
+{
+    using C = Mx4BwdCfg;
+    static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the forward's row tile");
+    bool empty;
+    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
+    if (rc != FQL_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (empty) {
+        if (c.T == 0) return FQL_OK;
+        if (c.lora.on) return FQL_ERR_BAD_SHAPE;                      // (N == 0 with rows: dv A alone is not this entry's business)
+        // N == 0: the gradient of an empty contraction.  grad_in [T][K] is zeros and no other operand is read.
+        if (!c.out) return FQL_ERR_NULL_POINTER;
+        (void)hipGetLastError();
+        return hipMemsetAsync(c.out, 0, (size_t)c.T * c.K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    }
+    const dim3 grid = mx4_grid(c, c.K, C::BK, C::BT);
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
+        return with_lora_arg(c.lora, [&](auto... la) {
+            return c.nvfp4 ? launch(nv4_bwd_kernel<IN, OUT, decltype(la)...>, grid, dim3(C::THREADS), 0, st, c.blocks, c.scales, c.gscale,
+                                    c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, la...)
+                           : launch(mx4_bwd_kernel<IN, OUT, decltype(la)...>, grid, dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows,
+                                    c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N, la...);
+        });
+    });
+}
+
+// ---- the split-K decode form of the three dense layers: with few rows, the decode kernel cut along K into S slices of
+//      partial sums and a reduce kernel (fql_gemm_mx4_linear.h, fql_gemm_nvfp4_linear.h, fql_gemm_lut4_decode.h).  One
+//      policy, a record of its three numbers per family ----
+#define FQL_LINEAR_MAX_SLICES 16
 #define FQL_MX4_LINEAR_DECODE_MAX_ROWS 16   /* rows (T) up to which the split form runs: the largest count of the sweep up to which it beats both grouped kernels at every shape whose S is above 1 */
-#define FQL_MX4_LINEAR_MAX_SLICES 16
 #define FQL_MX4_LINEAR_FILL_WAVES 640       /* the waves S(K, N) asks for: 2.5 a compute unit, from the S sweep of the same section */
-int g_mx4_linear_decode_max_rows = FQL_MX4_LINEAR_DECODE_MAX_ROWS;
-int g_mx4_linear_slices = 0;           // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_mx4_linear_slices)
+#define FQL_NVFP4_LINEAR_DECODE_MAX_ROWS 32 /* rows (T) up to which the split form runs: the largest count of the sweep (1, 16, 32, 64) up to which it beats both grouped kernels by more than the windows' ranges at every shape whose S is above 1: at 64 rows 2880 -> 5120 loses at its eight slices (DESIGN.md section 43) */
+#define FQL_NVFP4_LINEAR_FILL_WAVES 720     /* the waves S(K, N) asks for: MXFP4's 640 gives 2880 -> 5120 four slices where eight win at one row; 720 is the largest value that keeps 4096 -> 2880 at eight (the S sweep of the same section) */
+#define FQL_LUT4_LINEAR_DECODE_MAX_ROWS 64 /* rows (T) up to which the decode form runs: the largest count of the sweep (1, 8, 16, 32, 64, 128) at which it beats the tile kernel by more than the windows' ranges on every shape; at 128 rows 8192 -> 28672 ties at its two slices (DESIGN.md section 45) */
+#define FQL_LUT4_LINEAR_FILL_WAVES 1280     /* the waves S(K, N) asks for: every value in (1024, 1376] gives each of the five swept shapes the S that won its one-row sweep (16, 4, 16, 8, 2); 1280 is five waves a compute unit (the same section) */
+struct SplitPolicy {
+    int max_rows;                      // rows (T) up to which the split form runs (fql_tune_set_*_linear_decode_max_rows)
+    int forced;                        // 0: S(K, N) below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_*_linear_slices)
+    int fill_waves;                    // the waves S(K, N) asks for
+};
+SplitPolicy g_mx4_linear{FQL_MX4_LINEAR_DECODE_MAX_ROWS, 0, FQL_MX4_LINEAR_FILL_WAVES};
+SplitPolicy g_nvfp4_linear{FQL_NVFP4_LINEAR_DECODE_MAX_ROWS, 0, FQL_NVFP4_LINEAR_FILL_WAVES};
+SplitPolicy g_lut4_linear{FQL_LUT4_LINEAR_DECODE_MAX_ROWS, 0, FQL_LUT4_LINEAR_FILL_WAVES};
 
 // S(K, N): the slices of the split form, a pure function of the weights' shape (never of T or the device).  The smallest
-// S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >= FQL_MX4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 whole
-// pairs, so that no slice of the policy's is empty.  (The rule the work started from asked for 1024, a wave a SIMD; the
-// sweep's winners at one row are what 640 gives on all five shapes: 4, 8, 4, 1, 4.  Past that the partial sums' traffic
-// and the second launch cost more than the shorter K loop saves, and N = 28672 has 896 waves without help.)
-int mx4_linear_policy_slices(int K, int N)
+// S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >= fill_waves, capped at max(1, P) with P = K / 64 whole pairs, so that no
+// slice of the policy's is empty.  (The rule the MXFP4 work started from asked for 1024, a wave a SIMD; the sweep's winners
+// at one row are what 640 gives on all five shapes: 4, 8, 4, 1, 4.  Past that the partial sums' traffic and the second
+// launch cost more than the shorter K loop saves, and N = 28672 has 896 waves without help.)
+int policy_slices(int fill_waves, int K, int N)
 {
     const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
     int S = 1;
-    while (S < FQL_MX4_LINEAR_MAX_SLICES && waves * S < FQL_MX4_LINEAR_FILL_WAVES) S *= 2;
+    while (S < FQL_LINEAR_MAX_SLICES && waves * S < fill_waves) S *= 2;
     const int P = K / 64;
     while (S > 1 && S > P) S /= 2;
     return S;
 }
 
-// The slices a call with split_k set runs now: 1 means no split form (the call goes the split_k == 0 way).
-int mx4_linear_slices(int T, int K, int N)
+// The slices a call that asks for the split form runs now.  Past the row threshold: 1.  The MXFP4 and NVFP4 layers run the
+// split form above one slice and their grouped pair of kernels at 1; the code-book layer has no one-wave kernel to fall
+// back on and runs the decode form up to the threshold at S = 1 as well, so T never changes its S.
+int slices(const SplitPolicy &p, int T, int K, int N)
 {
-    if (T <= 0 || T > g_mx4_linear_decode_max_rows || (T - 1) / Mx4DecodeCfg::BT + 1 > 65535) return 1;
-    return g_mx4_linear_slices != 0 ? g_mx4_linear_slices : mx4_linear_policy_slices(K, N);
+    if (!decode_rows(p.max_rows, T)) return 1;
+    return p.forced != 0 ? p.forced : policy_slices(p.fill_waves, K, N);
 }
 
-// The partial sums of the split form: [16][T][N] float32, sized for the largest S so that the hook cannot outgrow it.
-size_t mx4_linear_partial_bytes(int T, int N, int split_k)
+// The partial sums of the split form: [16][T][N] float32, sized for the largest S so that the slice hook cannot outgrow it.
+size_t partial_bytes(const SplitPolicy &p, int T, int N)
 {
-    if (!split_k || T <= 0 || N <= 0 || T > g_mx4_linear_decode_max_rows) return 0;
-    return (size_t)FQL_MX4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
+    if (T <= 0 || N <= 0 || T > p.max_rows) return 0;
+    return (size_t)FQL_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
 }
 size_t mx4_linear_h_bytes(int T, int K, int gated) { return gated && T > 0 && K > 0 ? mx4_ws_bytes(ROWS_FLOAT, T, K) : 0; }
 
-// The two launches of the split form: the sliced decode kernel into partial [S][T][N], then the reduce kernel.
-int launch_mx4_linear_split(int in_dtype, int out_dtype, const Mx4Call &c, int S, float *partial, hipStream_t st)
+// What fql_tune_{mx4,nvfp4}_linear_kernel report: slices << 8 | the kernel (2 the split form, 1 the one-wave decode kernel of
+// the grouped pair, 0 its tile kernel).
+int linear_kernel_code(const SplitPolicy &p, int grouped_max_rows, int T, int K, int N)
 {
-    using D = Mx4DecodeCfg;
-    using R = Mx4LinearReduceCfg;
-    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
-    const int rc = with_in_dtype(in_dtype, [&](auto in) {
-        return launch(mx4_linear_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.blocks, c.scales, c.rows, partial,
-                      c.T, c.K, c.N);
-    });
-    if (rc != FQL_OK) return rc;
-    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
-    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
-    return with_out_dtype(out_dtype, [&](auto o) {
-        constexpr int OUT = decltype(o)::value;
-        auto go = [&](auto s) {
-            return launch(mx4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.bias, c.out, c.T, c.N);
-        };
-        switch (S) {
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        case 8: return go(std::integral_constant<int, 8>{});
-        default: return go(std::integral_constant<int, 16>{});
-        }
-    });
+    const int S = slices(p, T, K, N);
+    return (S << 8) | (S > 1 ? 2 : decode_rows(grouped_max_rows, T) ? 1 : 0);
 }
 
-// Both linear entries: the checks of mx4_check with E = 1 and no table, the workspace, then the launches.
-int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, int split_k, void *workspace, size_t workspace_bytes,
-                   void *stream)
+// f(std::integral_constant<int, S>) for a slice count of {MIN_S, .., 16}: the reduce kernels have S as a template argument,
+// and only the code-book one exists at S = 1.
+template <int MIN_S, class F>
+int with_slices(int S, F &&f)
 {
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, a.ok(), &empty);
-    if (rc != FQL_OK || empty) return rc;
-    const size_t h_bytes = mx4_linear_h_bytes(c.T, c.K, a.gated);
-    const size_t need = h_bytes + mx4_linear_partial_bytes(c.T, c.N, split_k);
-    if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    uint8_t *ws = static_cast<uint8_t *>(workspace);
-    if (a.gated) {
-        const int lrc = launch_mx4_quant<ROWS_FLOAT>(c.rows, in_dtype, a, ws, nullptr, c.T, c.K, st);
-        if (lrc != FQL_OK) return lrc;
-        c.rows = ws;
-        in_dtype = FQL_DTYPE_BF16;
+    if constexpr (MIN_S == 1)
+        if (S == 1) return f(std::integral_constant<int, 1>{});
+    switch (S) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
     }
-    const int S = split_k ? mx4_linear_slices(c.T, c.K, c.N) : 1;
-    if (S > 1) return launch_mx4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
-    return launch_float_rows(in_dtype, out_dtype, c, st);
 }
 
-// ---- the split-K decode form of the dense NVFP4 layer (fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd;
-//      fql_gemm_nvfp4_linear.h) ----
-#define FQL_NVFP4_LINEAR_DECODE_MAX_ROWS 32 /* rows (T) up to which the split form runs: the largest count of the sweep (1, 16, 32, 64) up to which it beats both grouped kernels by more than the windows' ranges at every shape whose S is above 1: at 64 rows 2880 -> 5120 loses at its eight slices (DESIGN.md section 43) */
-#define FQL_NVFP4_LINEAR_MAX_SLICES 16
-#define FQL_NVFP4_LINEAR_FILL_WAVES 720     /* the waves S(K, N) asks for: MXFP4's 640 gives 2880 -> 5120 four slices where eight win at one row; 720 is the largest value that keeps 4096 -> 2880 at eight (the S sweep of the same section) */
-int g_nvfp4_linear_decode_max_rows = FQL_NVFP4_LINEAR_DECODE_MAX_ROWS;
-int g_nvfp4_linear_slices = 0;         // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_nvfp4_linear_slices)
-
-// S(K, N): a pure function of the weights' shape (never of T or the device).  The smallest S of {1, 2, 4, 8, 16} with
-// ceil(N / 32) * S >= FQL_NVFP4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 whole pairs, so that no slice of the
-// policy's is empty.
-int nv4_linear_policy_slices(int K, int N)
-{
-    const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
-    int S = 1;
-    while (S < FQL_NVFP4_LINEAR_MAX_SLICES && waves * S < FQL_NVFP4_LINEAR_FILL_WAVES) S *= 2;
-    const int P = K / 64;
-    while (S > 1 && S > P) S /= 2;
-    return S;
-}
-
-// The slices a call of a split entry runs now: 1 means no split form (the call is the plain entry's).
-int nv4_linear_slices(int T, int K, int N)
-{
-    if (T <= 0 || T > g_nvfp4_linear_decode_max_rows || (T - 1) / Mx4DecodeCfg::BT + 1 > 65535) return 1;
-    return g_nvfp4_linear_slices != 0 ? g_nvfp4_linear_slices : nv4_linear_policy_slices(K, N);
-}
-
-// The partial sums: [16][T][N] float32, sized for the largest S so that the slice hook cannot outgrow it.
-size_t nv4_linear_partial_bytes(int T, int N)
-{
-    if (T <= 0 || N <= 0 || T > g_nvfp4_linear_decode_max_rows) return 0;
-    return (size_t)FQL_NVFP4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
-}
-
-// The two launches: the sliced decode kernel into partial [S][T][N], then the reduce kernel.
-int launch_nv4_linear_split(int in_dtype, int out_dtype, const Mx4Call &c, int S, float *partial, hipStream_t st)
+// The two launches of the split form: decode(in, grid, block) is a family's sliced decode kernel into partial [S][T][N],
+// reduce(out, s, grid, block) its reduce kernel.  (Three reduce kernels, not one: DESIGN.md section 45.)
+template <int MIN_S, class Decode, class Reduce>
+int launch_split(int in_dtype, int out_dtype, int T, int N, int S, Decode &&decode, Reduce &&reduce)
 {
     using D = Mx4DecodeCfg;
     using R = Nv4LinearReduceCfg;
-    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
-    const int rc = with_in_dtype(in_dtype, [&](auto in) {
-        return launch(nv4_linear_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.blocks, c.scales, c.rows, partial,
-                      c.T, c.K, c.N);
-    });
+    static_assert(Mx4LinearReduceCfg::THREADS == R::THREADS && Mx4LinearReduceCfg::ROWS == R::ROWS && Mx4LinearReduceCfg::COLS == R::COLS,
+                  "one reduce grid for the three families");
+    const dim3 grid((N + D::BN - 1) / D::BN, (T + D::BT - 1) / D::BT, S);
+    const int rc = with_in_dtype(in_dtype, [&](auto in) { return decode(in, grid, dim3(D::THREADS)); });
     if (rc != FQL_OK) return rc;
-    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
-    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
+    const int row_blocks = (T + R::ROWS - 1) / R::ROWS;
+    const dim3 rgrid((N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
     return with_out_dtype(out_dtype, [&](auto o) {
-        constexpr int OUT = decltype(o)::value;
-        auto go = [&](auto s) {
-            return launch(nv4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.gscale, c.bias,
-                          c.out, c.T, c.N);
-        };
-        switch (S) {
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        case 8: return go(std::integral_constant<int, 8>{});
-        default: return go(std::integral_constant<int, 16>{});
-        }
+        return with_slices<MIN_S>(S, [&](auto s) { return reduce(o, s, rgrid, dim3(R::THREADS)); });
     });
 }
 
-// Both split entries: mx4_linear_fwd's checks in its order (the workspace last, everything before any HIP call), the
-// pre-pass of a gated call, then the split form where it applies and the plain entry's launch everywhere else.
-int nv4_linear_split_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, void *workspace, size_t workspace_bytes, void *stream)
+// The split form of the MXFP4 and NVFP4 layers, S > 1.
+int launch_linear_split(int in_dtype, int out_dtype, const Mx4Call &c, int S, float *partial, hipStream_t st)
+{
+    if (c.nvfp4)
+        return launch_split<2>(in_dtype, out_dtype, c.T, c.N, S,
+            [&](auto in, dim3 grid, dim3 block) {
+                return launch(nv4_linear_decode_kernel<decltype(in)::value>, grid, block, 0, st, c.blocks, c.scales, c.rows, partial, c.T, c.K, c.N);
+            },
+            [&](auto o, auto s, dim3 grid, dim3 block) {
+                return launch(nv4_linear_reduce_kernel<decltype(o)::value, decltype(s)::value>, grid, block, 0, st, partial, c.gscale, c.bias,
+                              c.out, c.T, c.N);
+            });
+    return launch_split<2>(in_dtype, out_dtype, c.T, c.N, S,
+        [&](auto in, dim3 grid, dim3 block) {
+            return launch(mx4_linear_decode_kernel<decltype(in)::value>, grid, block, 0, st, c.blocks, c.scales, c.rows, partial, c.T, c.K, c.N);
+        },
+        [&](auto o, auto s, dim3 grid, dim3 block) {
+            return launch(mx4_linear_reduce_kernel<decltype(o)::value, decltype(s)::value>, grid, block, 0, st, partial, c.bias, c.out, c.T, c.N);
+        });
+}
+
+// Every dense MXFP4 and NVFP4 entry: the checks of mx4_check with E = 1 and no table, the workspace (last, everything before
+// any HIP call), the pre-pass of a gated call, then the split form where `split` (NULL: an entry without one, or split_k
+// == 0) asks for more than one slice and the grouped pair of kernels everywhere else.
+int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, const SplitPolicy *split, void *workspace,
+                   size_t workspace_bytes, void *stream)
 {
     bool empty;
     const int rc = mx4_check(c, in_dtype, out_dtype, a.ok(), &empty);
     if (rc != FQL_OK || empty) return rc;
     const size_t h_bytes = mx4_linear_h_bytes(c.T, c.K, a.gated);
-    const size_t need = h_bytes + nv4_linear_partial_bytes(c.T, c.N);
+    const size_t need = h_bytes + (split ? partial_bytes(*split, c.T, c.N) : 0);
     if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t *ws = static_cast<uint8_t *>(workspace);
@@ -477,13 +482,13 @@ int nv4_linear_split_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a
         c.rows = ws;
         in_dtype = FQL_DTYPE_BF16;
     }
-    const int S = nv4_linear_slices(c.T, c.K, c.N);
-    if (S > 1) return launch_nv4_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
-    return launch_nvfp4(in_dtype, out_dtype, c, st);
+    const int S = split ? slices(*split, c.T, c.K, c.N) : 1;
+    if (S > 1) return launch_linear_split(in_dtype, out_dtype, c, S, reinterpret_cast<float *>(ws + h_bytes), st);
+    return launch_float_rows(in_dtype, out_dtype, c, st);
 }
 
-// ---- 4-bit code-book weights, dense (fql_linear_lut4_fwd / fql_linear_lut4_bwd_input; fql_gemm_lut4.h, fql_gemm_lut4_bwd.h,
-//      DESIGN.md section 44) ----
+// ---- 4-bit code-book weights, dense (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h, fql_gemm_lut4_decode.h; DESIGN.md sections 44
+//      to 46) ----
 struct Lut4Call {
     const uint8_t *codes;
     const float *absmax, *book;        // book: [16] or NULL (the NF4 table)
@@ -492,23 +497,13 @@ struct Lut4Call {
     const float *bias;
     void *out;                         // out [T][N] or grad_in [T][K]
     int T, K, N;
-    bool lora = false;                 // an adapter entry (the tile kernels only): the three below are its operands
-    const float *lora_rows = nullptr;  // [T][rank]: v (forward) or dv (input gradient)
-    const float *lora_w = nullptr;     // [N][rank] B (forward) or [rank][K] A (input gradient)
-    int rank = 0;
+    LoraOperands lora;
 };
-
-// c with the operands of an adapter entry
-Lut4Call with_lora(Lut4Call c, const float *rows, const float *w, int rank)
-{
-    c.lora = true; c.lora_rows = rows; c.lora_w = w; c.rank = rank;
-    return c;
-}
 
 // mx4_check's order for one dense matrix: shapes, the row and result types, (an adapter entry: the rank), the empty call,
 // NULL pointers (the adapter operands with the others), the grid, then alignment.  bt: the row tile of the kernel that will
 // run; `bwd`: N == 0 is not empty (grad_in is zeros; nothing but the result is dereferenced then; an adapter entry refuses
-// it after this check).  *bshift = log2(block).
+// it here).  *bshift = log2(block).
 int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd, bool *empty, int *bshift)
 {
     *empty = false;
@@ -517,108 +512,94 @@ int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd,
     if (c.K % 64 != 0) return FQL_ERR_BAD_SHAPE;
     if (c.block < 64 || (c.block & (c.block - 1)) != 0 || c.K % c.block != 0) return FQL_ERR_BAD_SHAPE;
     if ((in_dtype != FQL_DTYPE_F32 && in_dtype != FQL_DTYPE_BF16) || !valid_dtype(out_dtype)) return FQL_ERR_DTYPE;
-    if (c.lora && c.rank != 4 && c.rank != 8 && c.rank != 16 && c.rank != 32 && c.rank != 64) return FQL_ERR_BAD_SHAPE;
+    if (lora_rank_bad(c.lora)) return FQL_ERR_BAD_SHAPE;
     if (c.T == 0 || (c.N == 0 && !bwd)) { *empty = true; return FQL_OK; }
-    if (c.lora && c.N == 0) return FQL_ERR_BAD_SHAPE;                 // (the input gradient: dv A alone is not this entry's business)
+    if (c.lora.on && c.N == 0) return FQL_ERR_BAD_SHAPE;              // (the input gradient: dv A alone is not this entry's business)
     if (!c.out || (c.N != 0 && (!c.codes || !c.absmax || !c.rows))) return FQL_ERR_NULL_POINTER;
-    if (c.lora && (!c.lora_rows || !c.lora_w)) return FQL_ERR_NULL_POINTER;
+    if (lora_null(c.lora)) return FQL_ERR_NULL_POINTER;
     if ((c.T + bt - 1) / bt > 65535) return FQL_ERR_BAD_SHAPE;
     const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.codes) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3) || (reinterpret_cast<uintptr_t>(c.absmax) & 3) ||
         (reinterpret_cast<uintptr_t>(c.book) & 3)) return FQL_ERR_ALIGNMENT;
-    if ((reinterpret_cast<uintptr_t>(c.lora_rows) & 3) || (reinterpret_cast<uintptr_t>(c.lora_w) & 3)) return FQL_ERR_ALIGNMENT;   // (NULL without an adapter)
+    if (lora_misaligned(c.lora)) return FQL_ERR_ALIGNMENT;
     int s = 6;
     while ((1 << s) < c.block) ++s;
     *bshift = s;
     return FQL_OK;
 }
 
-// ---- the split-K decode form of the dense code-book layer (fql_linear_lut4_split_fwd; fql_gemm_lut4_decode.h, DESIGN.md
-//      section 45) ----
-#define FQL_LUT4_LINEAR_DECODE_MAX_ROWS 64 /* rows (T) up to which the decode form runs: the largest count of the sweep (1, 8, 16, 32, 64, 128) at which it beats the tile kernel by more than the windows' ranges on every shape; at 128 rows 8192 -> 28672 ties at its two slices (DESIGN.md section 45) */
-#define FQL_LUT4_LINEAR_MAX_SLICES 16
-#define FQL_LUT4_LINEAR_FILL_WAVES 1280     /* the waves S(K, N) asks for: every value in (1024, 1376] gives each of the five swept shapes the S that won its one-row sweep (16, 4, 16, 8, 2); 1280 is five waves a compute unit (the same section) */
-int g_lut4_linear_decode_max_rows = FQL_LUT4_LINEAR_DECODE_MAX_ROWS;
-int g_lut4_linear_slices = 0;          // 0: the policy below; 1 / 2 / 4 / 8 / 16: forced (fql_tune_set_lut4_linear_slices)
-
-// S(K, N), shaped as nv4_linear_policy_slices: the smallest S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >=
-// FQL_LUT4_LINEAR_FILL_WAVES, capped at max(1, P) with P = K / 64 pairs, so that no slice of the policy's is empty.
-int lut4_linear_policy_slices(int K, int N)
-{
-    const long long waves = ((long long)N + Mx4DecodeCfg::BN - 1) / Mx4DecodeCfg::BN;
-    int S = 1;
-    while (S < FQL_LUT4_LINEAR_MAX_SLICES && waves * S < FQL_LUT4_LINEAR_FILL_WAVES) S *= 2;
-    const int P = K / 64;
-    while (S > 1 && S > P) S /= 2;
-    return S;
-}
-
-// The decode form runs up to the row threshold, at S = 1 as well (there is no one-wave kernel to fall back on).
-bool lut4_use_decode(int T)
-{
-    return T > 0 && T <= g_lut4_linear_decode_max_rows && (T - 1) / Mx4DecodeCfg::BT + 1 <= 65535;
-}
-
-int lut4_linear_slices(int K, int N)
-{
-    return g_lut4_linear_slices != 0 ? g_lut4_linear_slices : lut4_linear_policy_slices(K, N);
-}
-
-// The partial sums: [16][T][N] float32, sized for the largest S so that the slice hook cannot outgrow it.
-size_t lut4_linear_partial_bytes(int T, int N)
-{
-    if (N <= 0 || !lut4_use_decode(T)) return 0;
-    return (size_t)FQL_LUT4_LINEAR_MAX_SLICES * sizeof(float) * (size_t)T * (size_t)N;
-}
-
+// The tile kernel; an adapter call runs the same tile and grid, the adapter stage behind the K loop.
 int launch_lut4_tile(int in_dtype, int out_dtype, const Lut4Call &c, int bshift, hipStream_t st)
 {
     using C = Lut4Cfg;
     const dim3 grid((c.N + C::BN - 1) / C::BN, (c.T + C::BT - 1) / C::BT);
-    if (c.lora)                                                       // (the same tile and grid, the adapter stage behind the K loop)
-        return with_in_dtype(in_dtype, [&](auto in) {
-            return with_out_dtype(out_dtype, [&](auto o) {
-                return launch(lut4_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, grid, dim3(C::THREADS), 0, st,
-                              c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N,
-                              Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-            });
-        });
-    return with_in_dtype(in_dtype, [&](auto in) {
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(lut4_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st,
-                          c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N);
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        return with_lora_arg(c.lora, [&](auto... la) {
+            return launch(lut4_kernel<decltype(in)::value, decltype(o)::value, decltype(la)...>, grid, dim3(C::THREADS), 0, st,
+                          c.codes, c.absmax, c.book, c.rows, c.bias, c.out, bshift, c.T, c.K, c.N, la...);
         });
     });
 }
 
-// The two launches: the sliced decode kernel into partial [S][T][N], then the reduce kernel (S = 1 included).
+// The forward on the tile kernel, with or without an adapter: no workspace, no tune hook, never the decode form.
+int lut4_tile_fwd(const Lut4Call &c, int in_dtype, int out_dtype, void *stream)
+{
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, Lut4Cfg::BT, false, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    return launch_lut4_tile(in_dtype, out_dtype, c, bshift, static_cast<hipStream_t>(stream));
+}
+
+// The input gradient, with or without an adapter (N == 0 with rows: lut4_check refuses the adapter entry): c.rows is
+// grad_out [T][N], c.out grad_in [T][K].
+int lut4_bwd_input(const Lut4Call &c, int in_dtype, int out_dtype, void *stream)
+{
+    using C = Mx4BwdCfg;
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    const dim3 grid((c.K + C::BK - 1) / C::BK, (c.T + C::BT - 1) / C::BT);   // (N == 0: no stage exists, every tile stores zeros)
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        return with_lora_arg(c.lora, [&](auto... la) {
+            return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value, decltype(la)...>, grid, dim3(C::THREADS), 0,
+                          static_cast<hipStream_t>(stream), c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N, la...);
+        });
+    });
+}
+
+// The code-book layer's partial sums: none where the decode form does not run, the grid's bound on T included.
+size_t lut4_partial_bytes(int T, int N) { return decode_rows(g_lut4_linear.max_rows, T) ? partial_bytes(g_lut4_linear, T, N) : 0; }
+
+// The decode form of the code-book layer (S = 1 included).
 int launch_lut4_split(int in_dtype, int out_dtype, const Lut4Call &c, int bshift, int S, float *partial, hipStream_t st)
 {
-    using D = Mx4DecodeCfg;
-    using R = Nv4LinearReduceCfg;
-    const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, S);
-    const int rc = with_in_dtype(in_dtype, [&](auto in) {
-        return launch(lut4_decode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.codes, c.absmax, c.book, c.rows, partial,
-                      bshift, c.T, c.K, c.N);
-    });
-    if (rc != FQL_OK) return rc;
-    const int row_blocks = (c.T + R::ROWS - 1) / R::ROWS;
-    const dim3 rgrid((c.N + R::COLS - 1) / R::COLS, row_blocks < 65535 ? row_blocks : 65535);
-    return with_out_dtype(out_dtype, [&](auto o) {
-        constexpr int OUT = decltype(o)::value;
-        auto go = [&](auto s) {
-            return launch(lut4_linear_reduce_kernel<OUT, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial, c.bias, c.out, c.T,
+    return launch_split<1>(in_dtype, out_dtype, c.T, c.N, S,
+        [&](auto in, dim3 grid, dim3 block) {
+            return launch(lut4_decode_kernel<decltype(in)::value>, grid, block, 0, st, c.codes, c.absmax, c.book, c.rows, partial, bshift,
+                          c.T, c.K, c.N);
+        },
+        [&](auto o, auto s, dim3 grid, dim3 block) {
+            return launch(lut4_linear_reduce_kernel<decltype(o)::value, decltype(s)::value>, grid, block, 0, st, partial, c.bias, c.out, c.T,
                           c.N);
-        };
-        switch (S) {
-        case 1: return go(std::integral_constant<int, 1>{});
-        case 2: return go(std::integral_constant<int, 2>{});
-        case 4: return go(std::integral_constant<int, 4>{});
-        case 8: return go(std::integral_constant<int, 8>{});
-        default: return go(std::integral_constant<int, 16>{});
-        }
-    });
+        });
+}
+
+// The two bodies of the fql_tune_set_* hooks: a negative threshold, or a slice count outside {0, 1, 2, 4, 8, 16}, changes
+// nothing; the value before the call comes back.
+int replace_rows(int &slot, int rows)
+{
+    const int old = slot;
+    if (rows >= 0) slot = rows;
+    return old;
+}
+int replace_slices(int &slot, int slices)
+{
+    const int old = slot;
+    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) slot = slices;
+    return old;
 }
 
 }  // namespace
@@ -637,11 +618,7 @@ FQL_API int fql_moe_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, c
                             int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    const Mx4Call c{blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N};
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_mx4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+    return mx4_float_fwd({blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_moe_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
@@ -657,26 +634,8 @@ FQL_API int fql_moe_mx4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e
                                   const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
                                   int out_dtype, int E, int T, int K, int N, void *stream)
 {
-    using C = Mx4BwdCfg;
-    static_assert(C::BT == Mx4Cfg::BT, "mx4_check bounds the grid's y by the forward's row tile");
-    const Mx4Call c{blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N};
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (empty) {
-        if (T == 0) return FQL_OK;
-        // N == 0: the gradient of an empty contraction.  grad_in [T][K] is zeros and no other operand is read.
-        if (!grad_in) return FQL_ERR_NULL_POINTER;
-        (void)hipGetLastError();
-        return hipMemsetAsync(grad_in, 0, (size_t)T * K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
-    }
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(mx4_bwd_kernel<decltype(in)::value, decltype(o)::value>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0, st, c.blocks, c.scales, c.rows, c.out,
-                          c.tpe, c.offs, c.E, c.T, c.K, c.N);
-        });
-    });
+    return mx4_bwd_input({blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N}, in_dtype,
+                         out_dtype, stream);
 }
 
 FQL_API int fql_moe_mx4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
@@ -685,11 +644,8 @@ FQL_API int fql_moe_mx4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8
                                  int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    const Mx4Call c = with_lora({blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, lora_rows, lora_B, rank);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_mx4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+    return mx4_float_fwd(with_lora(Mx4Call{blocks, scales_e8m0, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                   lora_rows, lora_B, rank), in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_moe_mx4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
@@ -698,7 +654,7 @@ FQL_API int fql_moe_mx4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scale
                                      int E, int T, int K, int N, int activation, float act_alpha, float act_limit,
                                      void *workspace, size_t workspace_bytes, void *stream)
 {
-    return mx4_quant_fwd<ROWS_FLOAT>(with_lora({blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+    return mx4_quant_fwd<ROWS_FLOAT>(with_lora(Mx4Call{blocks, scales_e8m0, gate_up, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
                                                lora_rows, lora_B, rank), in_dtype, out_dtype, {true, activation, act_alpha, act_limit},
                                      workspace, workspace_bytes, stream);
 }
@@ -708,20 +664,8 @@ FQL_API int fql_moe_mx4_lora_bwd_input(const uint8_t *blocks, const uint8_t *sca
                                        const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
                                        void *stream)
 {
-    using C = Mx4BwdCfg;
-    const Mx4Call c = with_lora({blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N}, lora_rows,
-                                lora_A, rank);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK) return rc;
-    if (empty) return T == 0 ? FQL_OK : FQL_ERR_BAD_SHAPE;            // (N == 0 with rows: dv A alone is not this entry's business)
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(mx4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0,
-                          static_cast<hipStream_t>(stream), c.blocks, c.scales, c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N,
-                          Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-        });
-    });
+    return mx4_bwd_input(with_lora(Mx4Call{blocks, scales_e8m0, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N},
+                                   lora_rows, lora_A, rank), in_dtype, out_dtype, stream);
 }
 
 FQL_API size_t fql_moe_mx4_f8_workspace_bytes(int E, int T, int K, int N, int mode)
@@ -853,7 +797,7 @@ FQL_API int fql_mx6_quantize_rows(const void *rows, int in_dtype, int gated, int
 
 FQL_API size_t fql_linear_mx4_workspace_bytes(int T, int K, int N, int gated, int split_k)
 {
-    return mx4_linear_h_bytes(T, K, gated) + mx4_linear_partial_bytes(T, N, split_k);   // h [T][K] bfloat16 | partial [16][T][N] float32
+    return mx4_linear_h_bytes(T, K, gated) + (split_k ? partial_bytes(g_mx4_linear, T, N) : 0);   // h [T][K] bfloat16 | partial [16][T][N] float32
 }
 
 FQL_API int fql_linear_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *inputs, int in_dtype,
@@ -861,7 +805,7 @@ FQL_API int fql_linear_mx4_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0
                                size_t workspace_bytes, void *stream)
 {
     return mx4_linear_fwd({blocks, scales_e8m0, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, in_dtype, out_dtype, kMx4Plain,
-                          split_k, workspace, workspace_bytes, stream);
+                          split_k ? &g_mx4_linear : nullptr, workspace, workspace_bytes, stream);
 }
 
 FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e8m0, const void *gate_up, int in_dtype,
@@ -870,7 +814,7 @@ FQL_API int fql_linear_mx4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_
                                    void *stream)
 {
     return mx4_linear_fwd({blocks, scales_e8m0, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, in_dtype, out_dtype,
-                          {true, activation, act_alpha, act_limit}, split_k, workspace, workspace_bytes, stream);
+                          {true, activation, act_alpha, act_limit}, split_k ? &g_mx4_linear : nullptr, workspace, workspace_bytes, stream);
 }
 
 FQL_API size_t fql_moe_nvfp4_workspace_bytes(int E, int T, int K, int N, int gated)
@@ -884,11 +828,8 @@ FQL_API int fql_moe_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3,
                               void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    const Mx4Call c = with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, global_scale);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_nvfp4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+    return mx4_float_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N}, global_scale),
+                         in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_moe_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *gate_up,
@@ -913,7 +854,7 @@ FQL_API int fql_linear_nvfp4_fwd(const uint8_t *blocks, const uint8_t *scales_e4
                                  size_t workspace_bytes, void *stream)
 {
     return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
-                          out_dtype, kMx4Plain, 0, workspace, workspace_bytes, stream);
+                          out_dtype, kMx4Plain, nullptr, workspace, workspace_bytes, stream);
 }
 
 FQL_API int fql_linear_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
@@ -922,32 +863,15 @@ FQL_API int fql_linear_nvfp4_glu_fwd(const uint8_t *blocks, const uint8_t *scale
                                      size_t workspace_bytes, void *stream)
 {
     return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
-                          out_dtype, {true, activation, act_alpha, act_limit}, 0, workspace, workspace_bytes, stream);
+                          out_dtype, {true, activation, act_alpha, act_limit}, nullptr, workspace, workspace_bytes, stream);
 }
 
 FQL_API int fql_moe_nvfp4_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *grad_out,
                                     int in_dtype, const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
                                     int out_dtype, int E, int T, int K, int N, void *stream)
 {
-    using C = Mx4BwdCfg;
-    const Mx4Call c = with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N}, global_scale);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (empty) {
-        if (T == 0) return FQL_OK;
-        // N == 0: the gradient of an empty contraction.  grad_in [T][K] is zeros and no other operand is read.
-        if (!grad_in) return FQL_ERR_NULL_POINTER;
-        (void)hipGetLastError();
-        return hipMemsetAsync(grad_in, 0, (size_t)T * K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
-    }
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(nv4_bwd_kernel<decltype(in)::value, decltype(o)::value>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0, st, c.blocks, c.scales, c.gscale,
-                          c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K, c.N);
-        });
-    });
+    return mx4_bwd_input(with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N},
+                                    global_scale), in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_moe_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
@@ -956,12 +880,8 @@ FQL_API int fql_moe_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_
                                    int T, int K, int N, void *workspace, size_t workspace_bytes, void *stream)
 {
     (void)workspace; (void)workspace_bytes;
-    const Mx4Call c = with_lora(with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
-                                           global_scale), lora_rows, lora_B, rank);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_nvfp4(in_dtype, out_dtype, c, static_cast<hipStream_t>(stream));
+    return mx4_float_fwd(with_lora(with_nvfp4({blocks, scales_e4m3, inputs, bias, tokens_per_expert, input_offsets, out, E, T, K, N},
+                                              global_scale), lora_rows, lora_B, rank), in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_moe_nvfp4_glu_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
@@ -980,20 +900,8 @@ FQL_API int fql_moe_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *s
                                          const int32_t *tokens_per_expert, const int32_t *input_offsets, void *grad_in,
                                          int out_dtype, int E, int T, int K, int N, void *stream)
 {
-    using C = Mx4BwdCfg;
-    const Mx4Call c = with_lora(with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N},
-                                           global_scale), lora_rows, lora_A, rank);
-    bool empty;
-    const int rc = mx4_check(c, in_dtype, out_dtype, true, &empty);
-    if (rc != FQL_OK) return rc;
-    if (empty) return T == 0 ? FQL_OK : FQL_ERR_BAD_SHAPE;            // (N == 0 with rows: dv A alone is not this entry's business)
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(nv4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, mx4_grid(c, K, C::BK, C::BT), dim3(C::THREADS), 0,
-                          static_cast<hipStream_t>(stream), c.blocks, c.scales, c.gscale, c.rows, c.out, c.tpe, c.offs, c.E, c.T, c.K,
-                          c.N, Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-        });
-    });
+    return mx4_bwd_input(with_lora(with_nvfp4({blocks, scales_e4m3, grad_out, nullptr, tokens_per_expert, input_offsets, grad_in, E, T, K, N},
+                                              global_scale), lora_rows, lora_A, rank), in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_linear_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
@@ -1002,7 +910,7 @@ FQL_API int fql_linear_nvfp4_lora_fwd(const uint8_t *blocks, const uint8_t *scal
                                       void *stream)
 {
     return mx4_linear_fwd(with_lora(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
-                                    lora_rows, lora_B, rank), in_dtype, out_dtype, kMx4Plain, 0, workspace, workspace_bytes, stream);
+                                    lora_rows, lora_B, rank), in_dtype, out_dtype, kMx4Plain, nullptr, workspace, workspace_bytes, stream);
 }
 
 FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
@@ -1016,19 +924,13 @@ FQL_API int fql_linear_nvfp4_lora_bwd_input(const uint8_t *blocks, const uint8_t
 FQL_API int fql_linear_lut4_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
                                 int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N, void *stream)
 {
-    using C = Lut4Cfg;
-    const Lut4Call c{codes, absmax, code_book, block, inputs, bias, out, T, K, N};
-    bool empty;
-    int bshift = 6;
-    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, false, &empty, &bshift);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_lut4_tile(in_dtype, out_dtype, c, bshift, static_cast<hipStream_t>(stream));
+    return lut4_tile_fwd({codes, absmax, code_book, block, inputs, bias, out, T, K, N}, in_dtype, out_dtype, stream);
 }
 
 FQL_API size_t fql_linear_lut4_split_workspace_bytes(int T, int K, int N)
 {
     (void)K;
-    return lut4_linear_partial_bytes(T, N);                               // partial [16][T][N] float32
+    return lut4_partial_bytes(T, N);                                      // partial [16][T][N] float32
 }
 
 FQL_API int fql_linear_lut4_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
@@ -1040,108 +942,64 @@ FQL_API int fql_linear_lut4_split_fwd(const uint8_t *codes, const float *absmax,
     int bshift = 6;
     const int rc = lut4_check(c, in_dtype, out_dtype, Lut4Cfg::BT, false, &empty, &bshift);   // (a decode grid's y is within it)
     if (rc != FQL_OK || empty) return rc;
-    const size_t need = lut4_linear_partial_bytes(T, N);
+    const size_t need = lut4_partial_bytes(T, N);
     if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!lut4_use_decode(T)) return launch_lut4_tile(in_dtype, out_dtype, c, bshift, st);
-    return launch_lut4_split(in_dtype, out_dtype, c, bshift, lut4_linear_slices(K, N), static_cast<float *>(workspace), st);
+    if (!decode_rows(g_lut4_linear.max_rows, T)) return launch_lut4_tile(in_dtype, out_dtype, c, bshift, st);
+    return launch_lut4_split(in_dtype, out_dtype, c, bshift, slices(g_lut4_linear, T, K, N), static_cast<float *>(workspace), st);
 }
 
-FQL_API int fql_tune_set_lut4_linear_decode_max_rows(int rows)
-{
-    const int old = g_lut4_linear_decode_max_rows;
-    if (rows >= 0) g_lut4_linear_decode_max_rows = rows;
-    return old;
-}
-
-FQL_API int fql_tune_set_lut4_linear_slices(int slices)
-{
-    const int old = g_lut4_linear_slices;
-    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_lut4_linear_slices = slices;
-    return old;
-}
+FQL_API int fql_tune_set_lut4_linear_decode_max_rows(int rows) { return replace_rows(g_lut4_linear.max_rows, rows); }
+FQL_API int fql_tune_set_lut4_linear_slices(int slices) { return replace_slices(g_lut4_linear.forced, slices); }
 
 FQL_API int fql_tune_lut4_linear_kernel(int T, int K, int N)
 {
-    return lut4_use_decode(T) ? (lut4_linear_slices(K, N) << 8) | 2 : (1 << 8);
+    return decode_rows(g_lut4_linear.max_rows, T) ? (slices(g_lut4_linear, T, K, N) << 8) | 2 : (1 << 8);
 }
 
 FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
                                       const void *grad_out, int in_dtype, void *grad_in, int out_dtype, int T, int K, int N,
                                       void *stream)
 {
-    using C = Mx4BwdCfg;
-    const Lut4Call c{codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N};
-    bool empty;
-    int bshift = 6;
-    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);
-    if (rc != FQL_OK || empty) return rc;
-    const dim3 grid((K + C::BK - 1) / C::BK, (T + C::BT - 1) / C::BT);   // (N == 0: no stage exists, every tile stores zeros)
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, static_cast<hipStream_t>(stream),
-                          c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N);
-        });
-    });
+    return lut4_bwd_input({codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N}, in_dtype, out_dtype, stream);
 }
 
-// The adapter forms of the two code-book tile kernels: no workspace, no tune hook, never the decode form.
+// The adapter forms of the two code-book tile kernels.
 FQL_API int fql_linear_lut4_lora_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
                                      int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
                                      void *out, int out_dtype, int T, int K, int N, void *stream)
 {
-    const Lut4Call c = with_lora(Lut4Call{codes, absmax, code_book, block, inputs, bias, out, T, K, N}, lora_rows, lora_B, rank);
-    bool empty;
-    int bshift = 6;
-    const int rc = lut4_check(c, in_dtype, out_dtype, Lut4Cfg::BT, false, &empty, &bshift);
-    if (rc != FQL_OK || empty) return rc;
-    return launch_lut4_tile(in_dtype, out_dtype, c, bshift, static_cast<hipStream_t>(stream));
+    return lut4_tile_fwd(with_lora(Lut4Call{codes, absmax, code_book, block, inputs, bias, out, T, K, N}, lora_rows, lora_B, rank),
+                         in_dtype, out_dtype, stream);
 }
 
 FQL_API int fql_linear_lut4_lora_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
                                            const void *grad_out, int in_dtype, const float *lora_rows, const float *lora_A,
                                            int rank, void *grad_in, int out_dtype, int T, int K, int N, void *stream)
 {
-    using C = Mx4BwdCfg;
-    const Lut4Call c = with_lora(Lut4Call{codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N}, lora_rows, lora_A, rank);
-    bool empty;
-    int bshift = 6;
-    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);   // (N == 0 with rows: refused there)
-    if (rc != FQL_OK || empty) return rc;
-    const dim3 grid((K + C::BK - 1) / C::BK, (T + C::BT - 1) / C::BT);
-    return with_in_dtype(in_dtype, [&](auto in) {                     // c.rows is grad_out [T][N], c.out grad_in [T][K]
-        return with_out_dtype(out_dtype, [&](auto o) {
-            return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value, Mx4Lora>, grid, dim3(C::THREADS), 0,
-                          static_cast<hipStream_t>(stream), c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N,
-                          Mx4Lora{c.lora_rows, c.lora_w, c.rank});
-        });
-    });
+    return lut4_bwd_input(with_lora(Lut4Call{codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N}, lora_rows, lora_A, rank),
+                          in_dtype, out_dtype, stream);
 }
 
-FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows)
-{
-    const int old = g_nvfp4_decode_max_rows;
-    if (rows >= 0) g_nvfp4_decode_max_rows = rows;
-    return old;
-}
+FQL_API int fql_tune_set_nvfp4_decode_max_rows(int rows) { return replace_rows(g_nvfp4_decode_max_rows, rows); }
 
 FQL_API int fql_tune_nvfp4_kernel(int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
-    return nvfp4_use_decode(T) ? 1 : 0;
+    return decode_rows(g_nvfp4_decode_max_rows, T) ? 1 : 0;
 }
 
 FQL_API size_t fql_linear_nvfp4_split_workspace_bytes(int T, int K, int N, int gated)
 {
-    return mx4_linear_h_bytes(T, K, gated) + nv4_linear_partial_bytes(T, N);   // h [T][K] bfloat16 | partial [16][T][N] float32
+    return mx4_linear_h_bytes(T, K, gated) + partial_bytes(g_nvfp4_linear, T, N);   // h [T][K] bfloat16 | partial [16][T][N] float32
 }
 
 FQL_API int fql_linear_nvfp4_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale, const void *inputs,
                                        int in_dtype, const float *bias, void *out, int out_dtype, int T, int K, int N,
                                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    return nv4_linear_split_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
-                                in_dtype, out_dtype, kMx4Plain, workspace, workspace_bytes, stream);
+    return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, inputs, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
+                          out_dtype, kMx4Plain, &g_nvfp4_linear, workspace, workspace_bytes, stream);
 }
 
 FQL_API int fql_linear_nvfp4_glu_split_fwd(const uint8_t *blocks, const uint8_t *scales_e4m3, const float *global_scale,
@@ -1149,89 +1007,45 @@ FQL_API int fql_linear_nvfp4_glu_split_fwd(const uint8_t *blocks, const uint8_t 
                                            int K, int N, int activation, float act_alpha, float act_limit, void *workspace,
                                            size_t workspace_bytes, void *stream)
 {
-    return nv4_linear_split_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale),
-                                in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+    return mx4_linear_fwd(with_nvfp4({blocks, scales_e4m3, gate_up, bias, nullptr, nullptr, out, 1, T, K, N}, global_scale), in_dtype,
+                          out_dtype, {true, activation, act_alpha, act_limit}, &g_nvfp4_linear, workspace, workspace_bytes, stream);
 }
 
-FQL_API int fql_tune_set_nvfp4_linear_decode_max_rows(int rows)
-{
-    const int old = g_nvfp4_linear_decode_max_rows;
-    if (rows >= 0) g_nvfp4_linear_decode_max_rows = rows;
-    return old;
-}
+FQL_API int fql_tune_set_nvfp4_linear_decode_max_rows(int rows) { return replace_rows(g_nvfp4_linear.max_rows, rows); }
+FQL_API int fql_tune_set_nvfp4_linear_slices(int slices) { return replace_slices(g_nvfp4_linear.forced, slices); }
+FQL_API int fql_tune_nvfp4_linear_kernel(int T, int K, int N) { return linear_kernel_code(g_nvfp4_linear, g_nvfp4_decode_max_rows, T, K, N); }
 
-FQL_API int fql_tune_set_nvfp4_linear_slices(int slices)
-{
-    const int old = g_nvfp4_linear_slices;
-    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_nvfp4_linear_slices = slices;
-    return old;
-}
+FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows) { return replace_rows(g_mx4_linear.max_rows, rows); }
+FQL_API int fql_tune_set_mx4_linear_slices(int slices) { return replace_slices(g_mx4_linear.forced, slices); }
+FQL_API int fql_tune_mx4_linear_kernel(int T, int K, int N) { return linear_kernel_code(g_mx4_linear, g_mx4_decode_max_rows[ROWS_FLOAT], T, K, N); }
 
-FQL_API int fql_tune_nvfp4_linear_kernel(int T, int K, int N)
-{
-    const int S = nv4_linear_slices(T, K, N);
-    return (S << 8) | (S > 1 ? 2 : nvfp4_use_decode(T) ? 1 : 0);
-}
-
-FQL_API int fql_tune_set_mx4_linear_decode_max_rows(int rows)
-{
-    const int old = g_mx4_linear_decode_max_rows;
-    if (rows >= 0) g_mx4_linear_decode_max_rows = rows;
-    return old;
-}
-
-FQL_API int fql_tune_set_mx4_linear_slices(int slices)
-{
-    const int old = g_mx4_linear_slices;
-    if (slices == 0 || slices == 1 || slices == 2 || slices == 4 || slices == 8 || slices == 16) g_mx4_linear_slices = slices;
-    return old;
-}
-
-FQL_API int fql_tune_mx4_linear_kernel(int T, int K, int N)
-{
-    const int S = mx4_linear_slices(T, K, N);
-    return (S << 8) | (S > 1 ? 2 : mx4_use_decode(ROWS_FLOAT, T) ? 1 : 0);
-}
-
-FQL_API int fql_tune_set_mx4_decode_max_rows(int rows)
-{
-    const int old = g_mx4_decode_max_rows[ROWS_FLOAT];
-    if (rows >= 0) g_mx4_decode_max_rows[ROWS_FLOAT] = rows;
-    return old;
-}
+FQL_API int fql_tune_set_mx4_decode_max_rows(int rows) { return replace_rows(g_mx4_decode_max_rows[ROWS_FLOAT], rows); }
 
 FQL_API int fql_tune_mx4_kernel(int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
-    return mx4_use_decode(ROWS_FLOAT, T) ? 1 : 0;
+    return decode_rows(g_mx4_decode_max_rows[ROWS_FLOAT], T) ? 1 : 0;
 }
 
 FQL_API int fql_tune_set_mx4_scaled_decode_max_rows(int mode, int rows)
 {
     if (mode != ROWS_E4M3 && mode != ROWS_MXFP4) return -1;
-    const int old = g_mx4_decode_max_rows[mode];
-    if (rows >= 0) g_mx4_decode_max_rows[mode] = rows;
-    return old;
+    return replace_rows(g_mx4_decode_max_rows[mode], rows);
 }
 
 FQL_API int fql_tune_mx4_scaled_kernel(int mode, int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
     if (mode != ROWS_E4M3 && mode != ROWS_MXFP4) return -1;
-    return mx4_use_decode(mode, T) ? 1 : 0;
+    return decode_rows(g_mx4_decode_max_rows[mode], T) ? 1 : 0;
 }
 
-FQL_API int fql_tune_set_mx4_f6_decode_max_rows(int rows)
-{
-    const int old = g_mx4_decode_max_rows[ROWS_MXFP6];
-    if (rows >= 0) g_mx4_decode_max_rows[ROWS_MXFP6] = rows;
-    return old;
-}
+FQL_API int fql_tune_set_mx4_f6_decode_max_rows(int rows) { return replace_rows(g_mx4_decode_max_rows[ROWS_MXFP6], rows); }
 
 FQL_API int fql_tune_mx4_f6_kernel(int E, int T, int K, int N)
 {
     (void)E; (void)K; (void)N;
-    return mx4_use_decode(ROWS_MXFP6, T) ? 1 : 0;
+    return decode_rows(g_mx4_decode_max_rows[ROWS_MXFP6], T) ? 1 : 0;
 }
 
 }  // extern "C"
