@@ -9,7 +9,7 @@ from .quantize import (quantize_weights, dequantize_weights, reference_quantized
                        nvfp4_scale_values, NF4_CODE_BOOK, quantize_lut4, quantize_nf4, dequantize_lut4, bnb_nested_absmax)
 from .module import QuantizedLinear
 from .moe import MoEINT4, quantize_weights_moe, QuantizedMoE, QuantizedMoEExpert, QuantizedMoEFFN, QuantizedSparseMoEBlock, \
-    MXFP4MoEFFN, NVFP4MoEFFN
+    MXFP4MoEFFN, NVFP4MoEFFN, NF4MoEFFN
 from .mxfp4_linear import MXFP4Linear
 from .nvfp4_linear import NVFP4Linear, LoRANVFP4Linear
 from .nf4_linear import NF4Linear, LoRANF4Linear
@@ -24,6 +24,6 @@ __all__ = [
     "combine_expert_outputs", "dispatch_grouped", "dispatch_indices", "combine_grouped",
     "LoRAQuantizedLinear", "LoRAMoEINT4", "LoRAQuantizedMoEFFN", "LoRAMXFP4MoEFFN", "QuantizedSparseMoEBlock",
     "quantize_mxfp4", "dequantize_mxfp4", "MXFP4MoEFFN", "quantize_mxfp6", "dequantize_mxfp6", "MXFP4Linear",
-    "quantize_nvfp4", "dequantize_nvfp4", "nvfp4_scale_values", "NVFP4MoEFFN", "NVFP4Linear", "LoRANVFP4MoEFFN", "LoRANVFP4Linear",
+    "quantize_nvfp4", "dequantize_nvfp4", "nvfp4_scale_values", "NVFP4MoEFFN", "NF4MoEFFN", "NVFP4Linear", "LoRANVFP4MoEFFN", "LoRANVFP4Linear",
     "NF4_CODE_BOOK", "quantize_lut4", "quantize_nf4", "dequantize_lut4", "bnb_nested_absmax", "NF4Linear", "LoRANF4Linear",
 ]

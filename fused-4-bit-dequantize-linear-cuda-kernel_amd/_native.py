@@ -246,6 +246,13 @@ _SYMBOLS = {
     "fql_linear_lut4_split_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "fql_linear_lut4_split_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 2
                                   + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_lut4_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "fql_moe_lut4_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                         + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "fql_moe_lut4_glu_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                             + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_lut4_bwd_input": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                               + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "fql_tune_set_lut4_linear_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_set_lut4_linear_slices": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_lut4_linear_kernel": (ctypes.c_int, [ctypes.c_int] * 3),

@@ -32,8 +32,8 @@
 //   * Epilogue: nv4_epilogue without a global scale (acc + bias, one float32 addition, then the one rounding to OUT).
 //   * NON-FINITE: mx4_kernel's row flag (a non-finite activation makes exactly its output row NaN); absmax and the table
 //     are not screened, plain arithmetic decides.
-// A few rows take the split-K decode form of fql_gemm_lut4_decode.h.  Out of scope: a grouped form (bitsandbytes quantises
-// nn.Linear only).
+// A few rows take the split-K decode form of fql_gemm_lut4_decode.h.  The grouped form over an expert table (stacked NF4
+// experts) has a shorter tile of its own, lut4_group_kernel in fql_gemm_lut4_group.h: experts do not have 256 rows.
 //
 // LORA (lut4_kernel<IN, OUT, Mx4Lora>; fql_linear_lut4_lora_fwd): the adapter as one more contraction
 // stage behind the K loop's last barrier,

@@ -24,42 +24,56 @@
 //     A[j][kbase .. + 127], j < 64, goes into pair 0 of the weight image through the same mx4_bwd_off and store rotation
 //     (zeros for j >= r and k >= K), dv into the gradient image (zeros from r on); one barrier, then the steps with
 //     16 s < r.  Nothing moves in front of the stage (there is no global scale); lut4_bwd_kernel<IN, OUT> is the code it was.
+//   * GROUPED (lut4_group_bwd_kernel, at the end of this file; fql_moe_lut4_bwd_input): the same body
+//     with the compile-time GROUP flag, on an expert's rows and matrices behind mx4_group_begin.
 #pragma once
 #include "fql_gemm_mx4_bwd.h"
 #include "fql_gemm_lut4.h"
 
-// The kernel's body (inlined into lut4_bwd_kernel, which carries the target attribute and the LDS).
-// LA: nothing, or Mx4Lora: the compile-time LORA flag, set by the argument that carries what it needs.
-template <int IN, int OUT, class... LA>
+// The rows a workgroup works on: segment e (the expert; 0: the one dense matrix) holds rows lo .. lo + cnt - 1 of dY / dX, the
+// workgroup's tile starts at row t_blk of the segment (t_blk < cnt).
+struct Lut4Rows {
+    int e, lo, cnt, t_blk;
+};
+
+// The kernel's body (inlined into lut4_bwd_kernel and lut4_group_bwd_kernel, which carry the target attribute and the LDS).
+// LA: nothing, or Mx4Lora: the compile-time LORA flag, set by the argument that carries what it needs.  GROUP: the grouped
+// kernel's form (rows: the expert's segment); without it rows.cnt is T and the code is the dense kernel's as it always was.
+template <int IN, int OUT, bool GROUP, class... LA>
 __device__ __forceinline__ void lut4_bwd_body(
     unsigned char (&image)[2][Mx4BwdCfg::BN * Mx4BwdCfg::BK * 2], unsigned short (&yimage)[2][Mx4BwdCfg::BT][Mx4BwdCfg::YPITCH],
     float (&lut)[16], int (&row_bad)[Mx4BwdCfg::BT],
     const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
-    const void *__restrict__ dy, void *__restrict__ dx, int bshift, int T, int K, int N, LA... lora)
+    const void *__restrict__ dy, void *__restrict__ dx, int bshift, const Lut4Rows rows, int K, int N, LA... lora)
 {
     static_assert(sizeof...(LA) == 0 || (sizeof...(LA) == 1 && (std::is_same<LA, Mx4Lora>::value && ...)), "LA: nothing or Mx4Lora");
     constexpr bool LORA = sizeof...(LA) == 1;
     using C = Mx4BwdCfg;
-    const int t_blk = (int)blockIdx.y * C::BT;
+    const int T = rows.cnt;                                        // (GROUP: the rows of the expert's segment)
+    const int t_blk = GROUP ? rows.t_blk : (int)blockIdx.y * C::BT;
     const int kbase = (int)blockIdx.x * C::BK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int kb = (wave & 1) * 2;                                 // first of this wave's two 32-k blocks
     const int tr = (wave >> 1) * 32 + r;                           // this lane's row inside the tile
     const bool row_ok = t_blk + tr < T;
-    const int t = t_blk + tr;
+    const int t = GROUP ? rows.lo + t_blk + tr : t_blk + tr;
     const int K2 = K >> 1, KB = K >> bshift;
     constexpr int es = IN == 0 ? 4 : 2;
 
     // staging roles of this thread.  Weights: row sn of the stage, 16-byte piece sp (32 k, one absmax block).  Gradients:
-    // row ys of the tile (clamped to T - 1: loads are unconditional), the 16 n of quarter yq.
+    // row ys of the tile (clamped into the segment's range: loads are unconditional), the 16 n of quarter yq.
     const int sn = tid >> 2, sp = tid & 3;
     const int kp = kbase + 32 * sp;
     const bool k_ok = kp < K;                                      // (K % 64 == 0: kp + 31 < K then)
     const uint8_t *wbase = codes + (kp >> 1);
     const float *abase = absmax + (k_ok ? kp >> bshift : 0);
+    if constexpr (GROUP) {                                         // the expert's matrix (size_t: E N K / 2 passes 4 GiB)
+        wbase += (size_t)rows.e * N * K2;
+        abase += (size_t)rows.e * N * KB;
+    }
     const int ys = tid >> 2, yq = tid & 3;
-    const int ty = t_blk + ys < T ? t_blk + ys : T - 1;
+    const int ty = (GROUP ? rows.lo : 0) + (t_blk + ys < T ? t_blk + ys : T - 1);
     const char *yrow = reinterpret_cast<const char *>(dy) + (size_t)ty * N * es;
     // (16-byte loads: every row starts on a 16-byte boundary and ends on a piece boundary)
     const bool vec_y = (reinterpret_cast<uintptr_t>(dy) & 15) == 0 && ((size_t)N * es) % 16 == 0;
@@ -270,6 +284,31 @@ __global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_bwd_kernel(
     __shared__ __attribute__((aligned(16))) unsigned short yimage[2][C::BT][C::YPITCH];    // gradient rows, bfloat16
     __shared__ float lut[16];
     __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite gradient
-    lut4_bwd_body<IN, OUT, LA...>(image, yimage, lut, row_bad, codes, absmax, book, dy, dx, bshift, T, K, N, lora...);
+    lut4_bwd_body<IN, OUT, false, LA...>(image, yimage, lut, row_bad, codes, absmax, book, dy, dx, bshift, Lut4Rows{0, 0, T, 0}, K, N,
+                                         lora...);
+#endif
+}
+
+// The grouped form (fql_moe_lut4_bwd_input): dX[t][k] = round_OUT( sum_n bf16(dY[t][n]) * W_e[n][k] ) over
+// the rows t of expert e, codes [E][N][K / 2], absmax [E][N][K / B], one table.  The same body on the expert's rows and the
+// expert's base (size_t offsets), behind mx4_group_begin: grid = (ceil(K / 128), ceil(T / 64), E (+ 1 with a table)), rows no
+// expert covers are zeros, a row block past the expert's count returns before its first barrier.  The 64 t x 128 k tile is
+// expert-sized already.  The grouped call equals E one-expert calls (lut4_bwd_kernel) bit for bit.
+template <int IN, int OUT>
+__global__ __launch_bounds__(256) FQL_LUT4_TARGET void lut4_group_bwd_kernel(
+    const uint8_t *__restrict__ codes, const float *__restrict__ absmax, const float *__restrict__ book,
+    const void *__restrict__ dy, void *__restrict__ dx, const int32_t *__restrict__ tpe, const int32_t *__restrict__ offs,
+    int bshift, int E, int T, int K, int N)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    using C = Mx4BwdCfg;
+    int row_lo, cnt, t_blk;
+    if (!mx4_group_begin<C::THREADS, OUT>(dx, K, tpe, offs, E, T, C::BT, row_lo, cnt, t_blk)) return;
+    __shared__ __attribute__((aligned(16))) unsigned char image[2][C::BN * C::BK * 2];     // weights, bfloat16, swizzled
+    __shared__ __attribute__((aligned(16))) unsigned short yimage[2][C::BT][C::YPITCH];    // gradient rows, bfloat16
+    __shared__ float lut[16];
+    __shared__ int row_bad[C::BT];                                 // != 0: the row holds a non-finite gradient
+    lut4_bwd_body<IN, OUT, true>(image, yimage, lut, row_bad, codes, absmax, book, dy, dx, bshift,
+                           Lut4Rows{(int)blockIdx.z, row_lo, cnt, t_blk}, K, N);
 #endif
 }

@@ -16,6 +16,7 @@
 //   code book (NF4), dense      fql_linear_lut4_fwd / _bwd_input                                 fql_gemm_lut4.h, fql_gemm_lut4_bwd.h
 //     with an adapter           fql_linear_lut4_lora_fwd / _lora_bwd_input                       (LORA: a flag of the two tile kernels)
 //     split-K decode form       fql_linear_lut4_split_fwd                                        fql_gemm_lut4_decode.h
+//   code book (NF4), grouped    fql_moe_lut4_fwd / _glu_fwd / _bwd_input                         fql_gemm_lut4_group.h, fql_gemm_lut4_bwd.h
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -33,6 +34,7 @@
 #include "fql_gemm_lut4.h"
 #include "fql_gemm_lut4_bwd.h"
 #include "fql_gemm_lut4_decode.h"
+#include "fql_gemm_lut4_group.h"
 
 #include <cmath>
 
@@ -487,8 +489,8 @@ int mx4_linear_fwd(Mx4Call c, int in_dtype, int out_dtype, const Mx4Act &a, cons
     return launch_float_rows(in_dtype, out_dtype, c, st);
 }
 
-// ---- 4-bit code-book weights, dense (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h, fql_gemm_lut4_decode.h; DESIGN.md sections 44
-//      to 46) ----
+// ---- 4-bit code-book weights, dense and grouped (fql_gemm_lut4.h, fql_gemm_lut4_bwd.h, fql_gemm_lut4_decode.h,
+//      fql_gemm_lut4_group.h; DESIGN.md sections 44 to 46 and 48) ----
 struct Lut4Call {
     const uint8_t *codes;
     const float *absmax, *book;        // book: [16] or NULL (the NF4 table)
@@ -498,16 +500,28 @@ struct Lut4Call {
     void *out;                         // out [T][N] or grad_in [T][K]
     int T, K, N;
     LoraOperands lora;
+    bool grouped = false;              // a grouped entry: codes [E][N][K / 2], absmax [E][N][K / block], bias [E][N], and
+    const int32_t *tpe = nullptr, *offs = nullptr;   // the expert table (both NULL with E == 1: one segment of all rows)
+    int E = 1;
+    bool act_ok = true;                // (a gated grouped entry) the activation's arguments are valid
 };
+
+// c as the call of a grouped entry
+Lut4Call with_experts(Lut4Call c, const int32_t *tpe, const int32_t *offs, int E)
+{
+    c.grouped = true; c.tpe = tpe; c.offs = offs; c.E = E;
+    return c;
+}
 
 // mx4_check's order for one dense matrix: shapes, the row and result types, (an adapter entry: the rank), the empty call,
 // NULL pointers (the adapter operands with the others), the grid, then alignment.  bt: the row tile of the kernel that will
 // run; `bwd`: N == 0 is not empty (grad_in is zeros; nothing but the result is dereferenced then; an adapter entry refuses
-// it here).  *bshift = log2(block).
+// it here).  *bshift = log2(block).  A grouped call adds mx4_check's tests of E, the activation and the expert table, each
+// where mx4_check has it; a dense call (E = 1, no table) passes them all.
 int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd, bool *empty, int *bshift)
 {
     *empty = false;
-    if (c.T < 0 || c.K <= 0 || c.N < 0) return FQL_ERR_BAD_SHAPE;
+    if (c.E <= 0 || c.T < 0 || c.K <= 0 || c.N < 0 || !c.act_ok) return FQL_ERR_BAD_SHAPE;
     if (c.K & 1) return FQL_ERR_ODD_K;
     if (c.K % 64 != 0) return FQL_ERR_BAD_SHAPE;
     if (c.block < 64 || (c.block & (c.block - 1)) != 0 || c.K % c.block != 0) return FQL_ERR_BAD_SHAPE;
@@ -517,7 +531,11 @@ int lut4_check(const Lut4Call &c, int in_dtype, int out_dtype, int bt, bool bwd,
     if (c.lora.on && c.N == 0) return FQL_ERR_BAD_SHAPE;              // (the input gradient: dv A alone is not this entry's business)
     if (!c.out || (c.N != 0 && (!c.codes || !c.absmax || !c.rows))) return FQL_ERR_NULL_POINTER;
     if (lora_null(c.lora)) return FQL_ERR_NULL_POINTER;
+    if ((c.tpe == nullptr) != (c.offs == nullptr)) return FQL_ERR_NULL_POINTER;
+    if (c.tpe == nullptr && c.E != 1) return FQL_ERR_BAD_SHAPE;
+    if (c.E > 65534) return FQL_ERR_BAD_SHAPE;                        // (the grid's z: the experts and the coverage slice)
     if ((c.T + bt - 1) / bt > 65535) return FQL_ERR_BAD_SHAPE;
+    if (c.grouped && (long long)c.T * (c.K / 8) / 256 >= 0x7FFFFFFFLL) return FQL_ERR_BAD_SHAPE;   // (the pre-pass's grid, as mx4_check)
     const int ib = dtype_bytes(in_dtype), ob = dtype_bytes(out_dtype);
     if (!aligned16(c.codes) || (reinterpret_cast<uintptr_t>(c.rows) & (ib - 1)) || (reinterpret_cast<uintptr_t>(c.out) & (ob - 1)) ||
         (reinterpret_cast<uintptr_t>(c.bias) & 3) || (reinterpret_cast<uintptr_t>(c.absmax) & 3) ||
@@ -567,6 +585,58 @@ int lut4_bwd_input(const Lut4Call &c, int in_dtype, int out_dtype, void *stream)
             return launch(lut4_bwd_kernel<decltype(in)::value, decltype(o)::value, decltype(la)...>, grid, dim3(C::THREADS), 0,
                           static_cast<hipStream_t>(stream), c.codes, c.absmax, c.book, c.rows, c.out, bshift, c.T, c.K, c.N, la...);
         });
+    });
+}
+
+// The grid of a grouped code-book kernel with tiles of bt rows x bc columns of the result [T][cols]: mx4_grid's.
+dim3 lut4_group_grid(const Lut4Call &c, int cols, int bc, int bt)
+{
+    return dim3((cols + bc - 1) / bc, (c.T + bt - 1) / bt, c.tpe != nullptr ? c.E + 1 : 1);
+}
+
+// The grouped forward (fql_gemm_lut4_group.h), plain or gated: the checks, (gated) the workspace and mx4_glu_kernel's
+// pre-pass into it, the 128-row tile kernel.  One kernel at every T: nothing is switchable, so there is no tuning hook.
+int lut4_group_fwd(Lut4Call c, int in_dtype, int out_dtype, const Mx4Act &a, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using C = Lut4GroupCfg;
+    bool empty;
+    int bshift = 6;
+    c.act_ok = a.ok();
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, false, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (a.gated) {
+        if (!workspace || !aligned16(workspace) || workspace_bytes < mx4_ws_bytes(ROWS_FLOAT, c.T, c.K)) return FQL_ERR_WORKSPACE;
+        const int lrc = launch_mx4_quant<ROWS_FLOAT>(c.rows, in_dtype, a, workspace, nullptr, c.T, c.K, st);
+        if (lrc != FQL_OK) return lrc;
+        c.rows = workspace;
+        in_dtype = FQL_DTYPE_BF16;
+    }
+    const dim3 grid = lut4_group_grid(c, c.N, C::BN, C::BT);
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        return launch(lut4_group_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st, c.codes, c.absmax,
+                      c.book, c.rows, c.bias, c.out, c.tpe, c.offs, bshift, c.E, c.T, c.K, c.N);
+    });
+}
+
+// The grouped input gradient: c.rows is grad_out [T][N], c.out grad_in [T][K].  N == 0 with rows: grad_in is zeros (one
+// memset; no other operand is read).
+int lut4_group_bwd_input(const Lut4Call &c, int in_dtype, int out_dtype, void *stream)
+{
+    using C = Mx4BwdCfg;
+    bool empty;
+    int bshift = 6;
+    const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, true, &empty, &bshift);
+    if (rc != FQL_OK || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (c.N == 0) {
+        (void)hipGetLastError();
+        return hipMemsetAsync(c.out, 0, (size_t)c.T * c.K * dtype_bytes(out_dtype), st) == hipSuccess ? FQL_OK : FQL_ERR_LAUNCH;
+    }
+    const dim3 grid = lut4_group_grid(c, c.K, C::BK, C::BT);
+    return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
+        return launch(lut4_group_bwd_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st, c.codes,
+                      c.absmax, c.book, c.rows, c.out, c.tpe, c.offs, bshift, c.E, c.T, c.K, c.N);
     });
 }
 
@@ -965,6 +1035,37 @@ FQL_API int fql_linear_lut4_bwd_input(const uint8_t *codes, const float *absmax,
 }
 
 // The adapter forms of the two code-book tile kernels.
+FQL_API size_t fql_moe_lut4_workspace_bytes(int E, int T, int K, int N, int gated)
+{
+    return fql_moe_mx4_workspace_bytes(E, T, K, N, gated);            // h [T][K] bfloat16, as the MXFP4 entries'
+}
+
+FQL_API int fql_moe_lut4_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                             int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                             void *out, int out_dtype, int E, int T, int K, int N, void *stream)
+{
+    return lut4_group_fwd(with_experts({codes, absmax, code_book, block, inputs, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
+                          in_dtype, out_dtype, kMx4Plain, nullptr, 0, stream);
+}
+
+FQL_API int fql_moe_lut4_glu_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *gate_up,
+                                 int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                 void *out, int out_dtype, int E, int T, int K, int N, int activation, float act_alpha,
+                                 float act_limit, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return lut4_group_fwd(with_experts({codes, absmax, code_book, block, gate_up, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
+                          in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,
+                                   const void *grad_out, int in_dtype, const int32_t *tokens_per_expert,
+                                   const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
+                                   void *stream)
+{
+    return lut4_group_bwd_input(with_experts({codes, absmax, code_book, block, grad_out, nullptr, grad_in, T, K, N}, tokens_per_expert,
+                                             input_offsets, E), in_dtype, out_dtype, stream);
+}
+
 FQL_API int fql_linear_lut4_lora_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
                                      int in_dtype, const float *lora_rows, const float *lora_B, int rank, const float *bias,
                                      void *out, int out_dtype, int T, int K, int N, void *stream)

@@ -671,7 +671,7 @@ class MXFP4MoEFFN(nn.Module):
 
 
 class _NVFP4GatedFFNFn(torch.autograd.Function):
-    """``NVFP4MoEFFN(input_grad=True)`` with the input gradient, modelled on ``_MXFP4GatedFFNFn``: ``dh`` on the down weights
+    """``NVFP4MoEFFN(input_grad=True)`` (and ``NF4MoEFFN``, through the layer's ``_backward_input``) with the input gradient, modelled on ``_MXFP4GatedFFNFn``: ``dh`` on the down weights
     (``ops.moe_backward_input_nvfp4``), ``ops.glu_backward`` for every activation kind and ``dx`` on the gate / up weights,
     each tensor written once in the layer's activation type; ``ops.moe_bias_grad`` only for a bias that requires grad."""
 
@@ -694,11 +694,10 @@ class _NVFP4GatedFFNFn(torch.autograd.Function):
         gbd = ops.moe_bias_grad(gy, m.num_experts, tpe, offs) if need_bd else None
         if not (need_x or need_bgu):
             return None, None, None, None, None, gbd
-        dh = ops.moe_backward_input_nvfp4(m.down_blocks, m.down_scales, m.down_global, gy, tpe, offs, out_dtype=dt)
+        dh = m._backward_input(True, gy, tpe, offs, dt)
         dgu = ops.glu_backward(gate_up, dh, *m.activation_args, out_dtype=dt)
         gbgu = ops.moe_bias_grad(dgu, m.num_experts, tpe, offs) if need_bgu else None
-        dx = ops.moe_backward_input_nvfp4(m.gate_up_blocks, m.gate_up_scales, m.gate_up_global, dgu, tpe, offs,
-                                          out_dtype=dt) if need_x else None
+        dx = m._backward_input(False, dgu, tpe, offs, dt) if need_x else None
         return dx, None, None, None, gbgu, gbd
 
 
@@ -846,6 +845,13 @@ class NVFP4MoEFFN(nn.Module):
                                            input_offsets, activation=self.activation, activation_alpha=self.activation_alpha,
                                            activation_limit=self.activation_limit, bias=b_d, out_dtype=dt), gate_up
 
+    def _backward_input(self, down: bool, grad, tokens_per_expert, input_offsets, dt):
+        """The node's two input gradients: ``grad`` through the down weights (``dh``) or the gate / up weights (``dx``)."""
+        from . import ops
+        w = (self.down_blocks, self.down_scales, self.down_global) if down else \
+            (self.gate_up_blocks, self.gate_up_scales, self.gate_up_global)
+        return ops.moe_backward_input_nvfp4(*w, grad, tokens_per_expert, input_offsets, out_dtype=dt)
+
     biases = MXFP4MoEFFN.biases
     total_memory_bytes = MXFP4MoEFFN.total_memory_bytes
     activation_args = MXFP4MoEFFN.activation_args
@@ -853,6 +859,182 @@ class NVFP4MoEFFN(nn.Module):
 
     def extra_repr(self) -> str:
         return "format=nvfp4" + self._activation_repr() + (", input_grad=True" if self.input_grad else "")
+
+
+class NF4MoEFFN(nn.Module):
+    """Gated FFN experts on 4-bit code-book weights in bitsandbytes' encoding (NF4: the expert projections of the
+    ``*-bnb-4bit`` checkpoints of Mixtral, Qwen-MoE and others), frozen: ``down( act(gate(x), up(x)) )`` per expert, rows
+    pre-grouped by expert, the same ``forward`` as ``NVFP4MoEFFN``.
+
+    The buffers are bitsandbytes' tensors stacked over the experts, never re-quantised and never reordered:
+    ``gate_up_codes`` uint8 [E, 2F, H/2] and ``down_codes`` [E, H, F/2] (input ``2i`` in the HIGH nibble of byte ``i``),
+    ``gate_up_absmax`` float32 [E, 2F, H/block] and ``down_absmax`` [E, H, F/block], and one ``code_book`` float32 [16] (the
+    NF4 table unless given).  Rows 0 .. F-1 of ``gate_up`` are the gate, F .. 2F-1 the up projection.  H and F are
+    multiples of 64 and of ``block`` (a power of two >= 64).  ``expert_bias=True`` adds float32 ``gate_up_bias`` [E, 2F] and
+    ``down_bias`` [E, H], as in ``MXFP4MoEFFN``.
+
+    Both GEMMs are ``ops.moe_forward_lut4`` / ``ops.moe_gated_forward_lut4``: a weight is
+    ``bf16(code_book[c] * absmax)`` (``dequantize_4bit`` to bfloat16), the activations are rounded once to bfloat16
+    (float32 inputs) or read as they are (``activation_dtype=torch.bfloat16``), the sums are float32, and a row's bits are
+    those ``NF4Linear`` gives it on its expert's matrices.  GPU only.
+
+    ``input_grad`` as ``NVFP4MoEFFN``'s: False (the default) is inference only; True makes the layer differentiable in its
+    input and, for biases that ``requires_grad``, in its biases (``ops.moe_backward_input_lut4`` on the down weights,
+    ``ops.glu_backward``, then on the gate / up weights; straight-through across the forward's two bfloat16 roundings).  It is
+    configuration, not state."""
+
+    group_size = None                        # (what the block reads: the absmax blocks are the format's, not an option)
+    precision = "bf16"
+
+    def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, block: int = 64, activation: str = "silu",
+                 activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
+                 activation_dtype=None, input_grad: bool = False):
+        super().__init__()
+        if block < 64 or block & (block - 1):
+            raise ValueError("block must be a power of two of at least 64")
+        if num_experts <= 0 or hidden_dim <= 0 or ffn_dim <= 0 or hidden_dim % 64 or ffn_dim % 64 or hidden_dim % block \
+                or ffn_dim % block:
+            raise ValueError("hidden_dim and ffn_dim must be positive multiples of 64 and of block, and num_experts positive")
+        if activation_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("activation_dtype must be None, torch.float32 or torch.bfloat16 (float16 rows are refused: "
+                             "rounding them to bfloat16 would lose three bits)")
+        from . import ops
+        from .quantize import NF4_CODE_BOOK
+        self.num_experts, self.hidden_dim, self.ffn_dim, self.block = num_experts, hidden_dim, ffn_dim, block
+        self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
+            activation, activation_alpha, activation_limit)
+        self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
+        self.input_grad = bool(input_grad)
+        E, H, F = num_experts, hidden_dim, ffn_dim
+        self.register_buffer("gate_up_codes", torch.full((E, 2 * F, H // 2), 0x77, dtype=torch.uint8))   # (NF4's zero)
+        self.register_buffer("gate_up_absmax", torch.ones(E, 2 * F, H // block, dtype=torch.float32))
+        self.register_buffer("down_codes", torch.full((E, H, F // 2), 0x77, dtype=torch.uint8))
+        self.register_buffer("down_absmax", torch.ones(E, H, F // block, dtype=torch.float32))
+        self.register_buffer("code_book", torch.tensor(NF4_CODE_BOOK, dtype=torch.float32))
+        self.expert_bias = bool(expert_bias)
+        if self.expert_bias:
+            self.gate_up_bias = nn.Parameter(torch.zeros(E, 2 * F, dtype=torch.float32), requires_grad=False)
+            self.down_bias = nn.Parameter(torch.zeros(E, H, dtype=torch.float32), requires_grad=False)
+
+    @classmethod
+    def from_bnb(cls, gate_up_codes, gate_up_absmax, down_codes, down_absmax, block: int = 64, code_book=None,
+                 gate_up_bias=None, down_bias=None, **kwargs) -> "NF4MoEFFN":
+        """Stacked tensors already in the format: ``gate_up_codes`` uint8 [E, 2F, H/2], ``gate_up_absmax`` float32
+        [E, 2F, H/block], ``down_codes`` [E, H, F/2], ``down_absmax`` [E, H, F/block]; ``code_book`` 16 values or None for
+        NF4; ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H] (both or none).  ``kwargs``: the constructor's activation
+        arguments, ``activation_dtype`` and ``input_grad``."""
+        for name, c, a in (("gate_up", gate_up_codes, gate_up_absmax), ("down", down_codes, down_absmax)):
+            if c.dtype != torch.uint8 or a.dtype != torch.float32 or c.dim() != 3 or a.dim() != 3:
+                raise ValueError(f"{name}_codes must be uint8 [E, N, K/2] and {name}_absmax float32 [E, N, K/block]")
+            if block < 64 or block & (block - 1) or (2 * c.shape[2]) % block or \
+                    tuple(a.shape) != (c.shape[0], c.shape[1], 2 * c.shape[2] // block):
+                raise ValueError(f"{name}_absmax must be [E, N, K/block] for {name}_codes [E, N, K/2], block a power of two >= 64 "
+                                 "dividing K")
+        E, F2, H = gate_up_codes.shape[0], gate_up_codes.shape[1], gate_up_codes.shape[2] * 2
+        if F2 % 2 or tuple(down_codes.shape) != (E, H, F2 // 4):
+            raise ValueError("gate_up must be [E, 2F, H/2] and down [E, H, F/2] of the same E, H and F")
+        if (gate_up_bias is None) != (down_bias is None):
+            raise ValueError("gate_up_bias and down_bias come together: pass both or none")
+        if gate_up_bias is not None and (tuple(gate_up_bias.shape) != (E, F2) or tuple(down_bias.shape) != (E, H)):
+            raise ValueError("gate_up_bias must be [E, 2F] and down_bias [E, H]")
+        m = cls(E, H, F2 // 2, block=block, expert_bias=gate_up_bias is not None, **kwargs)
+        m.gate_up_codes, m.gate_up_absmax = gate_up_codes.contiguous().clone(), gate_up_absmax.contiguous().clone()
+        m.down_codes, m.down_absmax = down_codes.contiguous().clone(), down_absmax.contiguous().clone()
+        if code_book is not None:
+            book = torch.as_tensor(code_book, dtype=torch.float32)
+            if tuple(book.shape) != (16,):
+                raise ValueError("code_book must hold 16 values")
+            m.code_book = book.detach().clone().to(gate_up_codes.device)
+        else:
+            m.code_book = m.code_book.to(gate_up_codes.device)
+        if gate_up_bias is not None:
+            with torch.no_grad():
+                m.gate_up_bias.data = gate_up_bias.detach().float().contiguous().clone()
+                m.down_bias.data = down_bias.detach().float().contiguous().clone()
+        return m
+
+    @classmethod
+    def from_bnb_experts(cls, gate, up, down, hidden_dim: int, ffn_dim: int, block: int = 64, **kwargs) -> "NF4MoEFFN":
+        """Three lists of E ``(codes, absmax)`` pairs as bitsandbytes stores an ``nn.Linear`` each: ``gate[e]`` / ``up[e]``
+        are [F, H] projections, ``down[e]`` [H, F].  A flat or ``[N*K/2, 1]`` weight and flat statistics are viewed (nested
+        statistics go through ``quantize.bnb_nested_absmax`` first, by the caller).  The gate is concatenated over up along
+        N: byte concatenation, since a row is a whole number of blocks.  ``kwargs``: ``from_bnb``'s other arguments."""
+        H, F = hidden_dim, ffn_dim
+        if not (len(gate) == len(up) == len(down)) or not gate:
+            raise ValueError("gate, up and down must be lists of the same positive length (one pair per expert)")
+
+        def view(pair, N, K):
+            c, a = pair
+            if c.dtype != torch.uint8 or a.dtype != torch.float32 or c.numel() != N * K // 2 or a.numel() != N * (K // block):
+                raise ValueError(f"an expert projection must be uint8 codes of {N} x {K} / 2 bytes and float32 absmax of "
+                                 f"{N} x {K} / {block} values")
+            return c.reshape(N, K // 2), a.reshape(N, K // block)
+        gu = [[torch.cat(t) for t in zip(view(g, F, H), view(u, F, H))] for g, u in zip(gate, up)]
+        d = [view(p, H, F) for p in down]
+        return cls.from_bnb(torch.stack([c for c, _ in gu]), torch.stack([a for _, a in gu]), torch.stack([c for c, _ in d]),
+                            torch.stack([a for _, a in d]), block=block, **kwargs)
+
+    @classmethod
+    def from_weights(cls, gate: List[torch.Tensor], up: List[torch.Tensor], down: List[torch.Tensor], gate_bias=None,
+                     up_bias=None, down_bias=None, block: int = 64, **kwargs) -> "NF4MoEFFN":
+        """``gate[e]``, ``up[e]``: ``[F, H]``; ``down[e]``: ``[H, F]`` float weights, quantised with ``quantize.quantize_nf4``;
+        the biases as ``QuantizedMoEFFN.from_weights`` takes them (all three or none)."""
+        from .quantize import quantize_nf4
+        given = [b is not None for b in (gate_bias, up_bias, down_bias)]
+        if any(given) and not all(given):
+            raise ValueError("gate_bias, up_bias and down_bias come together: pass all three or none")
+        gu = quantize_nf4(torch.stack([torch.cat([g.float(), u.float()], dim=0) for g, u in zip(gate, up)]), block=block)
+        d = quantize_nf4(torch.stack([t.float() for t in down]), block=block)
+        b_gu = torch.stack([torch.cat([g.float(), u.float()]) for g, u in zip(gate_bias, up_bias)]) if all(given) else None
+        b_d = torch.stack([t.float() for t in down_bias]) if all(given) else None
+        return cls.from_bnb(*gu, *d, block=block, gate_up_bias=b_gu, down_bias=b_d, **kwargs)
+
+    def forward(self, inputs, tokens_per_expert, input_offsets):
+        """inputs ``[T, H]`` float32 (``activation_dtype=torch.bfloat16``: bfloat16) rows grouped by expert -> ``[T, H]`` of
+        the same type."""
+        if not inputs.is_cuda:
+            raise RuntimeError("NF4MoEFFN runs on the GPU (the product path has no CPU fallback)")
+        if not self.input_grad and torch.is_grad_enabled() and inputs.requires_grad:
+            raise RuntimeError("NF4MoEFFN is inference-only as built.  Run it under torch.no_grad(), or on a detached input "
+                               "(or build the layer with input_grad=True)")
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
+        if inputs.dim() != 2 or inputs.dtype != dt:
+            raise RuntimeError(f"NF4MoEFFN: inputs must be a 2-D {dt} tensor (the layer's activation_dtype), got "
+                               f"{inputs.dtype}")
+        b_gu, b_d = self.biases
+        if self.input_grad and torch.is_grad_enabled() and (
+                inputs.requires_grad or (b_gu is not None and (b_gu.requires_grad or b_d.requires_grad))):
+            return _NVFP4GatedFFNFn.apply(inputs, tokens_per_expert, input_offsets, self, b_gu, b_d)
+        return self._ffn(inputs, tokens_per_expert, input_offsets)[0]
+
+    def _ffn(self, inputs, tokens_per_expert, input_offsets):
+        """(y, gate_up) in the layer's activation type, on detached biases (their gradient is the autograd node's
+        business)."""
+        from . import ops
+        dt = torch.float32 if self.activation_dtype is None else self.activation_dtype
+        b_gu, b_d = self.biases
+        b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
+        gate_up = ops.moe_forward_lut4(self.gate_up_codes, self.gate_up_absmax, inputs.detach(), tokens_per_expert, input_offsets,
+                                       self.code_book, self.block, bias=b_gu, out_dtype=dt)
+        return ops.moe_gated_forward_lut4(self.down_codes, self.down_absmax, gate_up, tokens_per_expert, input_offsets,
+                                          activation=self.activation, activation_alpha=self.activation_alpha,
+                                          activation_limit=self.activation_limit, code_book=self.code_book, block=self.block,
+                                          bias=b_d, out_dtype=dt), gate_up
+
+    def _backward_input(self, down: bool, grad, tokens_per_expert, input_offsets, dt):
+        """The node's two input gradients (``_NVFP4GatedFFNFn``): through the down weights, or the gate / up weights."""
+        from . import ops
+        codes, absmax = (self.down_codes, self.down_absmax) if down else (self.gate_up_codes, self.gate_up_absmax)
+        return ops.moe_backward_input_lut4(codes, absmax, grad, tokens_per_expert, input_offsets, self.code_book, self.block,
+                                           out_dtype=dt)
+
+    biases = MXFP4MoEFFN.biases
+    total_memory_bytes = MXFP4MoEFFN.total_memory_bytes
+    activation_args = MXFP4MoEFFN.activation_args
+    _activation_repr = QuantizedMoEFFN._activation_repr
+
+    def extra_repr(self) -> str:
+        return (f"format=nf4, block={self.block}" + self._activation_repr() + (", input_grad=True" if self.input_grad else ""))
 
 
 class QuantizedSparseMoEBlock(nn.Module):
@@ -864,8 +1046,8 @@ class QuantizedSparseMoEBlock(nn.Module):
     ``gate`` is an ``nn.Linear(hidden_dim, num_experts, bias=False)``: float, trainable, not quantised, run by torch
     (its weight is cast to the activations' type when they differ).  ``experts`` is a ``QuantizedMoEFFN`` (built here
     when not given; a ``LoRAQuantizedMoEFFN`` may be passed in, or an ``MXFP4MoEFFN``: built with ``input_grad=True`` it trains the
-    router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``; or an ``NVFP4MoEFFN``,
-    with the same ``input_grad`` keyword and the same rule).  State-dict keys: ``gate.weight`` and ``experts.*``.
+    router and everything upstream under grad mode, without it the block runs under ``torch.no_grad()``; or an ``NVFP4MoEFFN``
+    or an ``NF4MoEFFN``, with the same ``input_grad`` keyword and the same rule).  State-dict keys: ``gate.weight`` and ``experts.*``.
     The combine (``ops.combine_any``) reads the expert rows in their own type, sums in float32 and rounds the output once
     to the activations' type: no cast pass either side of it.
 

@@ -2852,6 +2852,83 @@ def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64
                         code_book, block, False, out_dtype, torch.float32)
 
 
+def _lut4_moe_launch(name, entry, codes, absmax, rows, cols, tokens_per_expert, input_offsets, code_book, block, bias, out_dtype,
+                     default_dtype, act=None):
+    """The three grouped code-book ops (csrc/fql_gemm_lut4_group.h, csrc/fql_gemm_lut4_bwd.h), section
+    14's order as ``_lut4_launch``: types and shapes first, then the devices.  ``codes`` [E, N, K/2], ``absmax`` [E, N,
+    K/block], ``bias`` [E, N] (False: the op has none, the input gradient); ``rows`` [T, cols(K, N)] float32 / bfloat16, the
+    result [T, N] (``bias`` not False) or [T, K].  ``act``: the gated entry's (kind, alpha, limit), with its workspace."""
+    what = "the rows" if bias is not False else "grad_out"
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"ops.{name}: {what} must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
+                           "it to bfloat16 would lose three bits; cast it yourself)")
+    if codes.dtype != torch.uint8 or codes.dim() != 3 or absmax.dtype != torch.float32 or absmax.dim() != 3:
+        raise RuntimeError("codes must be uint8 [num_experts, N, K/2] and absmax float32 [num_experts, N, K/block]")
+    E, N, K = codes.shape[0], codes.shape[1], 2 * codes.shape[2]
+    if not isinstance(block, int) or block < 64 or block & (block - 1) or K % 64 != 0 or K % block != 0:
+        raise RuntimeError("block must be a power of two of at least 64 with K % block == 0, and K % 64 == 0")
+    if tuple(absmax.shape) != (E, N, K // block):
+        raise RuntimeError(f"absmax must be float32 [num_experts, N, K/block] = [{E}, {N}, {K // block}] for codes {list(codes.shape)}")
+    if rows.shape[1] != cols(K, N):
+        raise RuntimeError(f"ops.{name}: {what} must have {cols(K, N)} columns for codes {list(codes.shape)}")
+    if code_book is not None and (not isinstance(code_book, torch.Tensor) or code_book.dtype != torch.float32
+                                  or tuple(code_book.shape) != (16,)):
+        raise RuntimeError("code_book must be a float32 [16] tensor, or None for the NF4 table")
+    if bias is not None and bias is not False and (bias.dtype != torch.float32 or tuple(bias.shape) != (E, N)):
+        raise RuntimeError("bias must be a float32 [num_experts, N] tensor")
+    T = rows.shape[0]
+    out_dtype = default_dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPES:
+        raise RuntimeError("out_dtype must be float32, float16 or bfloat16")
+    if not rows.is_cuda:
+        raise RuntimeError(f"ops.{name}: {what} must be a CUDA tensor")
+    dev = rows.device
+    _on(dev, codes=codes, absmax=absmax, code_book=code_book, bias=None if bias is False else bias)
+    tpe, offs = _expert_table(tokens_per_expert, input_offsets, E, dev, optional=True)   # (none: one expert, all rows)
+    out = torch.empty((T, K if bias is False else N), dtype=out_dtype, device=dev)
+    book = None if code_book is None else code_book.contiguous()
+    b = () if bias is False else (None if bias is None else bias.contiguous(),)
+    tail, ws_bytes = ((), None) if act is None else (act, _native.lib().fql_moe_lut4_workspace_bytes(E, T, K, N, 1))
+    _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *b, tpe, offs,
+            out, _DTYPES[out_dtype], E, T, K, N, *tail, ws_bytes=ws_bytes)
+    return out
+
+
+def moe_forward_lut4(codes, absmax, inputs, tokens_per_expert, input_offsets, code_book=None, block=64, bias=None, out_dtype=None):
+    """The grouped GEMM on 4-bit code-book expert weights (NF4 by default: the experts of a ``*-bnb-4bit`` MoE checkpoint,
+    stacked): ``out[t] = W_e @ bf16(inputs[t]) (+ bias[e])`` over the rows of expert e, ``W_e`` as ``linear_forward_lut4``
+    defines it on ``codes[e]`` uint8 [N, K/2] (bitsandbytes' nibble order) and ``absmax[e]`` float32 [N, K/block].
+    ``code_book`` float32 [16] or None is one table for all experts; ``bias`` float32 [E, N].  ``inputs`` [T, K] float32
+    (rounded once to bfloat16) or bfloat16; the result is ``out_dtype`` (default: the inputs' type), rounded once.  A row's
+    bits are those ``linear_forward_lut4`` gives it on its expert's slices, so the grouped call equals E one-expert calls
+    bit for bit; rows no expert covers are zero; both table arguments may be None with one expert.  One 128-row tile
+    kernel at every T (csrc/fql_gemm_lut4_group.h).  Forward only."""
+    _forward_only("moe_forward_lut4", inputs, bias)
+    return _lut4_moe_launch("moe_forward_lut4", "fql_moe_lut4_fwd", codes, absmax, inputs, lambda K, N: K, tokens_per_expert,
+                            input_offsets, code_book, block, bias, out_dtype, inputs.dtype if isinstance(inputs, torch.Tensor) else None)
+
+
+def moe_gated_forward_lut4(codes, absmax, gate_up, tokens_per_expert, input_offsets, activation="silu", activation_alpha=1.702,
+                           activation_limit=7.0, code_book=None, block=64, bias=None, out_dtype=None):
+    """The down projection of a gated FFN expert on code-book weights: ``moe_forward_lut4`` on
+    ``bf16(act(gate_up[t, :K], gate_up[t, K:]))``, ``gate_up`` [T, 2K] float32 or bfloat16, by ``moe_gated_forward_mxfp4``'s
+    streaming pre-pass into the op's workspace.  Forward only."""
+    _forward_only("moe_gated_forward_lut4", gate_up, bias)
+    kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
+    return _lut4_moe_launch("moe_gated_forward_lut4", "fql_moe_lut4_glu_fwd", codes, absmax, gate_up, lambda K, N: 2 * K,
+                            tokens_per_expert, input_offsets, code_book, block, bias, out_dtype,
+                            gate_up.dtype if isinstance(gate_up, torch.Tensor) else None, act=(_ACTIVATIONS[kind], act_alpha, act_limit))
+
+
+def moe_backward_input_lut4(codes, absmax, grad_out, tokens_per_expert, input_offsets, code_book=None, block=64, out_dtype=None):
+    """Grouped ``grad_in[t] = bf16(grad_out[t]) @ W_e`` on the operands of ``moe_forward_lut4`` (no transposed copy), for
+    the rows of each expert's range; rows no expert covers are zero.  ``grad_out`` [T, N] float32 (rounded once to
+    bfloat16) or bfloat16 -> [T, K] ``out_dtype`` (default float32), float32 sums over ascending n; the grouped call
+    equals E ``linear_backward_input_lut4`` calls bit for bit."""
+    return _lut4_moe_launch("moe_backward_input_lut4", "fql_moe_lut4_bwd_input", codes, absmax, grad_out, lambda K, N: N,
+                            tokens_per_expert, input_offsets, code_book, block, False, out_dtype, torch.float32)
+
+
 def linear_forward_lut4_lora(codes, absmax, x, v, lora_B, code_book=None, block=64, bias=None, out_dtype=None):
     """``linear_forward_lut4`` with the adapter fused into the tile kernel as one more contraction stage:
     ``out[t] = W @ bf16(x[t]) + bf16(lora_B) @ bf16(v[t]) (+ bias)``, float32 sums (the adapter's sixteen columns a step

@@ -331,9 +331,13 @@ def quantize_lut4(weight: torch.Tensor, code_book=None, block: int = LUT4_BLOCK)
     block's largest magnitude, a code is the index of the table entry nearest to ``w / absmax`` (float32), input ``2i`` in
     the HIGH nibble of byte ``i`` and input ``2i + 1`` in the low one.  A tie goes to the lower code, and an all-zero block
     divides by 1; equality with bitsandbytes' own quantiser on exact midpoints is not claimed (it searches a tree of rounded
-    thresholds).  ``code_book``: 16 values (default ``NF4_CODE_BOOK``)."""
-    if weight.dim() != 2:
-        raise ValueError("weight must be [N, K]")
+    thresholds).  ``code_book``: 16 values (default ``NF4_CODE_BOOK``).  Leading dimensions (``[E, N, K]``, stacked experts)
+    are kept: every row is quantised on its own."""
+    if weight.dim() < 2:
+        raise ValueError("weight must be [N, K] (or [..., N, K])")
+    if weight.dim() > 2:
+        codes, absmax = quantize_lut4(weight.reshape(-1, weight.shape[-1]), code_book, block)
+        return codes.reshape(*weight.shape[:-1], -1), absmax.reshape(*weight.shape[:-1], -1)
     N, K = weight.shape
     _lut4_block(block, K)
     if not bool(torch.isfinite(weight).all()):
@@ -352,7 +356,10 @@ quantize_nf4 = quantize_lut4
 def dequantize_lut4(codes: torch.Tensor, absmax: torch.Tensor, code_book=None, block: int = LUT4_BLOCK) -> torch.Tensor:
     """``(codes uint8 [N, K/2], absmax float32 [N, K/block])`` -> ``[N, K]`` bfloat16, the definition of the kernels' weight:
     ``bf16(fl32(code_book[c] * absmax))``, one float32 multiply and one rounding to nearest even (what bitsandbytes'
-    ``dequantize_4bit`` to bfloat16 gives)."""
+    ``dequantize_4bit`` to bfloat16 gives).  Leading dimensions (``[E, N, K/2]`` / ``[E, N, K/block]``) are kept."""
+    if codes.dim() > 2 and absmax.shape[:-1] == codes.shape[:-1]:
+        w = dequantize_lut4(codes.reshape(-1, codes.shape[-1]), absmax.reshape(-1, absmax.shape[-1]), code_book, block)
+        return w.reshape(*codes.shape[:-1], -1)
     if codes.dtype != torch.uint8 or codes.dim() != 2 or absmax.dtype != torch.float32:
         raise ValueError("codes must be uint8 [N, K/2] and absmax float32 [N, K/block]")
     N, K = codes.shape[0], 2 * codes.shape[1]

@@ -27,7 +27,8 @@ form at 2 and at 16 slices forced in turn, then ``linear_backward_input_mxfp4``;
 tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the same operands, and last the five NVFP4 adapter
 ops (``moe_forward_nvfp4_lora`` and its kin) on them, and the two dense NVFP4 ops with ``split_k=True`` at 2 and at 16 forced
 slices; then the two code-book (NF4) ops and, last, ``linear_forward_lut4(split_k=True)`` at the policy's S and at 2 and 16
-forced slices; last of all ``linear_forward_lut4_lora`` / ``linear_backward_input_lut4_lora`` at ranks 4, 32 and 64."""
+forced slices; then ``linear_forward_lut4_lora`` / ``linear_backward_input_lut4_lora`` at ranks 4, 32 and 64; last of all the
+three grouped code-book ops (``moe_forward_lut4`` and its kin)."""
 import argparse
 import hashlib
 import os
@@ -599,6 +600,21 @@ def calls(dev, fq, ops):
                     codes, absmax, xl.to(dt), vl, Bl, bk, 64, bias=bl)
                 yield f"linear_backward_input_lut4_lora r={r} {btag} {dt}", lambda: ops.linear_backward_input_lut4_lora(
                     codes, absmax, gl.to(dt), dvl, Al, bk, 64, out_dtype=dt)
+
+    # the three grouped code-book ops, behind every earlier call (their draws come last): E = 3 with an empty expert, one row
+    # past the 128-row tile and a partial block, listed in reverse order with a gap of uncovered rows
+    Eg, Tg = 3, 170
+    gcodes = torch.randint(0, 256, (Eg, Nl, Kl // 2), dtype=torch.uint8, generator=d.gen).to(dev)
+    gabsmax = (torch.rand(Eg, Nl, Kl // 64, generator=d.gen) + 0.5).to(dev)
+    xg, gg, gug, bg = d.randn(Tg, Kl), d.randn(Tg, Nl), d.randn(Tg, 2 * Kl), d.randn(Eg, Nl)
+    tpg, ofg = (torch.tensor(v, dtype=torch.int32).to(dev) for v in ([0, 129, 33], [5, 38, 0]))
+    for btag, bk in (("nf4", None), ("own table", book)):
+        for dt in (F32, BF16):
+            yield f"moe_forward_lut4 {btag} {dt}", lambda: ops.moe_forward_lut4(gcodes, gabsmax, xg.to(dt), tpg, ofg, bk, 64, bias=bg)
+            yield f"moe_gated_forward_lut4 {btag} {dt}", lambda: ops.moe_gated_forward_lut4(
+                gcodes, gabsmax, gug.to(dt), tpg, ofg, code_book=bk, block=64, bias=bg, **glu)
+            yield f"moe_backward_input_lut4 {btag} {dt}", lambda: ops.moe_backward_input_lut4(
+                gcodes, gabsmax, gg.to(dt), tpg, ofg, bk, 64, out_dtype=dt)
 
 
 def digest(t):
