@@ -256,6 +256,16 @@ _SYMBOLS = {
     "fql_tune_set_lut4_linear_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_set_lut4_linear_slices": (ctypes.c_int, [ctypes.c_int]),
     "fql_tune_lut4_linear_kernel": (ctypes.c_int, [ctypes.c_int] * 3),
+    "fql_moe_lut4_split_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "fql_moe_lut4_split_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                               + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_moe_lut4_glu_split_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                                   + [ctypes.c_int] * 6 + [ctypes.c_float] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "fql_tune_set_lut4_group_decode_max_rows": (ctypes.c_int, [ctypes.c_int]),
+    "fql_tune_lut4_group_kernel": (ctypes.c_int, [ctypes.c_int]),
+    "fql_tune_set_lut4_group_split_max_rows": (ctypes.c_int, [ctypes.c_int]),
+    "fql_tune_set_lut4_group_slices": (ctypes.c_int, [ctypes.c_int]),
+    "fql_tune_lut4_group_split_kernel": (ctypes.c_int, [ctypes.c_int] * 3),
     "fql_combine_sparse_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
                                + [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
 }

@@ -31,7 +31,8 @@
 //     two workgroups share a compute unit: one converts while the other contracts (__launch_bounds__(256, 2)).
 //   * Weight and absmax offsets are size_t: E N K / 2 passes 4 GiB at real sizes.
 // The gated form runs mx4_glu_kernel (fql_mx4_quant.h) first and reads its bfloat16 h [T][K] as x.
-// Out of scope: a one-wave decode form for few rows an expert, adapter forms, a per-expert table.
+// For few rows an expert the host runs the one-wave decode kernel of fql_gemm_lut4_group_decode.h instead: the same bits.
+// Out of scope: adapter forms, a per-expert table.
 #pragma once
 #include "fql_gemm_lut4.h"
 

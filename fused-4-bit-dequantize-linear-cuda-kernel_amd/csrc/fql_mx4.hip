@@ -17,6 +17,7 @@
 //     with an adapter           fql_linear_lut4_lora_fwd / _lora_bwd_input                       (LORA: a flag of the two tile kernels)
 //     split-K decode form       fql_linear_lut4_split_fwd                                        fql_gemm_lut4_decode.h
 //   code book (NF4), grouped    fql_moe_lut4_fwd / _glu_fwd / _bwd_input                         fql_gemm_lut4_group.h, fql_gemm_lut4_bwd.h
+//     decode forms              (the same entries, by T) / fql_moe_lut4_split_fwd / _glu_split_fwd  fql_gemm_lut4_group_decode.h
 #include "../../include/fql_int4.h"
 #include "../../include/fql_int4_tune.h"
 #include "fql_common.h"
@@ -35,6 +36,7 @@
 #include "fql_gemm_lut4_bwd.h"
 #include "fql_gemm_lut4_decode.h"
 #include "fql_gemm_lut4_group.h"
+#include "fql_gemm_lut4_group_decode.h"
 
 #include <cmath>
 
@@ -368,6 +370,13 @@ struct SplitPolicy {
 SplitPolicy g_mx4_linear{FQL_MX4_LINEAR_DECODE_MAX_ROWS, 0, FQL_MX4_LINEAR_FILL_WAVES};
 SplitPolicy g_nvfp4_linear{FQL_NVFP4_LINEAR_DECODE_MAX_ROWS, 0, FQL_NVFP4_LINEAR_FILL_WAVES};
 SplitPolicy g_lut4_linear{FQL_LUT4_LINEAR_DECODE_MAX_ROWS, 0, FQL_LUT4_LINEAR_FILL_WAVES};
+// The grouped code-book experts' split form (fql_gemm_lut4_group_decode.h): S(K, N) cannot see how many experts are live.
+#define FQL_LUT4_GROUP_SPLIT_MAX_ROWS 2     /* rows (T) up to which the split entries run the sliced form: the sweep has the split form at one token only (T = 2 at top-2 of 8 experts, T = 6 at top-6 of 64), and at T = 6 the 64 x 1408 -> 2048 shape ties the one-wave kernel at its sixteen slices; at T = 2 every shape whose S is above 1 wins by more than the windows' ranges */
+#define FQL_LUT4_GROUP_FILL_WAVES 704       /* the waves S(K, N) asks for: every value in (688, 896] gives the four 8-expert shapes their one-token winners or a tie with them (4, 1, 8, 8); 704, the smallest multiple of 32 in it, is what costs the 64-expert shapes least (8 and 16 where 4 wins: S cannot see that six experts are live; the same section) */
+SplitPolicy g_lut4_group{FQL_LUT4_GROUP_SPLIT_MAX_ROWS, 0, FQL_LUT4_GROUP_FILL_WAVES};
+// The grouped code-book forward: the 128-row tile and, for few rows, the one-wave decode kernel; the same bits from both.
+#define FQL_LUT4_GROUP_DECODE_MAX_ROWS 96   /* rows (T) up to which the decode kernel runs: the largest count of the sweep (2 .. 1024) below the first at which it does not beat the tile by more than the two windows' ranges at every shape: at 128 rows 11008 -> 4096 is within them */
+int g_lut4_group_decode_max_rows = FQL_LUT4_GROUP_DECODE_MAX_ROWS;
 
 // S(K, N): the slices of the split form, a pure function of the weights' shape (never of T or the device).  The smallest
 // S of {1, 2, 4, 8, 16} with ceil(N / 32) * S >= fill_waves, capped at max(1, P) with P = K / 64 whole pairs, so that no
@@ -594,28 +603,58 @@ dim3 lut4_group_grid(const Lut4Call &c, int cols, int bc, int bt)
     return dim3((cols + bc - 1) / bc, (c.T + bt - 1) / bt, c.tpe != nullptr ? c.E + 1 : 1);
 }
 
-// The grouped forward (fql_gemm_lut4_group.h), plain or gated: the checks, (gated) the workspace and mx4_glu_kernel's
-// pre-pass into it, the 128-row tile kernel.  One kernel at every T: nothing is switchable, so there is no tuning hook.
-int lut4_group_fwd(Lut4Call c, int in_dtype, int out_dtype, const Mx4Act &a, void *workspace, size_t workspace_bytes, void *stream)
+// The grouped forward (fql_gemm_lut4_group.h, fql_gemm_lut4_group_decode.h), plain or gated: the checks, the workspace (gated:
+// h; a split entry up to its row threshold: the partial sums behind it), mx4_glu_kernel's pre-pass, then
+//   * `split` (an entry that has one) and T within its threshold: the sliced decode kernel on S(K, N) slices, S = 1
+//     included, and the reduce kernel;
+//   * else the one-wave decode kernel up to g_lut4_group_decode_max_rows rows and the 128-row tile past it: the same bits.
+// lut4_check receives the tile's row block whichever kernel runs, so its grid bound and order do not move.
+int lut4_group_fwd(Lut4Call c, int in_dtype, int out_dtype, const Mx4Act &a, const SplitPolicy *split, void *workspace,
+                   size_t workspace_bytes, void *stream)
 {
     using C = Lut4GroupCfg;
+    using D = Mx4DecodeCfg;
     bool empty;
     int bshift = 6;
     c.act_ok = a.ok();
     const int rc = lut4_check(c, in_dtype, out_dtype, C::BT, false, &empty, &bshift);
     if (rc != FQL_OK || empty) return rc;
+    const bool sliced = split != nullptr && decode_rows(split->max_rows, c.T);
+    if (sliced && (long long)c.E * FQL_LINEAR_MAX_SLICES > 65535) return FQL_ERR_BAD_SHAPE;   // (the sliced grid's z = E * S)
+    const size_t h_bytes = a.gated ? mx4_ws_bytes(ROWS_FLOAT, c.T, c.K) : 0;                  // (a multiple of 16: K % 64 == 0)
+    const size_t need = h_bytes + (sliced ? partial_bytes(*split, c.T, c.N) : 0);
+    if (need != 0 && (!workspace || !aligned16(workspace) || workspace_bytes < need)) return FQL_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a.gated) {
-        if (!workspace || !aligned16(workspace) || workspace_bytes < mx4_ws_bytes(ROWS_FLOAT, c.T, c.K)) return FQL_ERR_WORKSPACE;
         const int lrc = launch_mx4_quant<ROWS_FLOAT>(c.rows, in_dtype, a, workspace, nullptr, c.T, c.K, st);
         if (lrc != FQL_OK) return lrc;
         c.rows = workspace;
         in_dtype = FQL_DTYPE_BF16;
     }
-    const dim3 grid = lut4_group_grid(c, c.N, C::BN, C::BT);
+    if (sliced) {
+        using R = Lut4GroupReduceCfg;
+        const int S = slices(*split, c.T, c.K, c.N);
+        float *partial = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + h_bytes);
+        const dim3 grid((c.N + D::BN - 1) / D::BN, (c.T + D::BT - 1) / D::BT, c.E * S);
+        const int drc = with_in_dtype(in_dtype, [&](auto in) {
+            return launch(lut4_group_sdecode_kernel<decltype(in)::value>, grid, dim3(D::THREADS), 0, st, c.codes, c.absmax, c.book, c.rows,
+                          partial, c.tpe, c.offs, bshift, S, c.T, c.K, c.N);
+        });
+        if (drc != FQL_OK) return drc;
+        const dim3 rgrid = lut4_group_grid(c, c.N, R::COLS, R::BT);
+        return with_out_dtype(out_dtype, [&](auto o) {
+            return with_slices<1>(S, [&](auto s) {
+                return launch(lut4_group_reduce_kernel<decltype(o)::value, decltype(s)::value>, rgrid, dim3(R::THREADS), 0, st, partial,
+                              c.bias, c.out, c.tpe, c.offs, c.E, c.T, c.N);
+            });
+        });
+    }
+    const bool decode = decode_rows(g_lut4_group_decode_max_rows, c.T);
+    const dim3 grid = decode ? lut4_group_grid(c, c.N, D::BN, D::BT) : lut4_group_grid(c, c.N, C::BN, C::BT);
     return with_dtypes(in_dtype, out_dtype, [&](auto in, auto o) {
-        return launch(lut4_group_kernel<decltype(in)::value, decltype(o)::value>, grid, dim3(C::THREADS), 0, st, c.codes, c.absmax,
-                      c.book, c.rows, c.bias, c.out, c.tpe, c.offs, bshift, c.E, c.T, c.K, c.N);
+        constexpr int IN = decltype(in)::value, OUT = decltype(o)::value;
+        return launch(decode ? lut4_group_decode_kernel<IN, OUT> : lut4_group_kernel<IN, OUT>, grid, dim3(decode ? D::THREADS : C::THREADS),
+                      0, st, c.codes, c.absmax, c.book, c.rows, c.bias, c.out, c.tpe, c.offs, bshift, c.E, c.T, c.K, c.N);
     });
 }
 
@@ -1045,7 +1084,7 @@ FQL_API int fql_moe_lut4_fwd(const uint8_t *codes, const float *absmax, const fl
                              void *out, int out_dtype, int E, int T, int K, int N, void *stream)
 {
     return lut4_group_fwd(with_experts({codes, absmax, code_book, block, inputs, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
-                          in_dtype, out_dtype, kMx4Plain, nullptr, 0, stream);
+                          in_dtype, out_dtype, kMx4Plain, nullptr, nullptr, 0, stream);
 }
 
 FQL_API int fql_moe_lut4_glu_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *gate_up,
@@ -1054,7 +1093,44 @@ FQL_API int fql_moe_lut4_glu_fwd(const uint8_t *codes, const float *absmax, cons
                                  float act_limit, void *workspace, size_t workspace_bytes, void *stream)
 {
     return lut4_group_fwd(with_experts({codes, absmax, code_book, block, gate_up, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
-                          in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, workspace, workspace_bytes, stream);
+                          in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The split forms of the two grouped forwards: the workspace is the gated h [T][K] bfloat16, then the
+// partial sums [16][T][N] float32 where the sliced form runs.
+FQL_API size_t fql_moe_lut4_split_workspace_bytes(int E, int T, int K, int N, int gated)
+{
+    return fql_moe_lut4_workspace_bytes(E, T, K, N, gated) + (decode_rows(g_lut4_group.max_rows, T) ? partial_bytes(g_lut4_group, T, N) : 0);
+}
+
+FQL_API int fql_moe_lut4_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                   int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                                   void *stream)
+{
+    return lut4_group_fwd(with_experts({codes, absmax, code_book, block, inputs, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
+                          in_dtype, out_dtype, kMx4Plain, &g_lut4_group, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_moe_lut4_glu_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block,
+                                       const void *gate_up, int in_dtype, const float *bias, const int32_t *tokens_per_expert,
+                                       const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                                       int activation, float act_alpha, float act_limit, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return lut4_group_fwd(with_experts({codes, absmax, code_book, block, gate_up, bias, out, T, K, N}, tokens_per_expert, input_offsets, E),
+                          in_dtype, out_dtype, {true, activation, act_alpha, act_limit}, &g_lut4_group, workspace, workspace_bytes, stream);
+}
+
+FQL_API int fql_tune_set_lut4_group_decode_max_rows(int rows) { return replace_rows(g_lut4_group_decode_max_rows, rows); }
+FQL_API int fql_tune_lut4_group_kernel(int T) { return decode_rows(g_lut4_group_decode_max_rows, T) ? 1 : 0; }
+FQL_API int fql_tune_set_lut4_group_split_max_rows(int rows) { return replace_rows(g_lut4_group.max_rows, rows); }
+FQL_API int fql_tune_set_lut4_group_slices(int slices) { return replace_slices(g_lut4_group.forced, slices); }
+
+// slices << 8 | the kernel a split entry runs: 2 the sliced form, 1 the one-wave decode kernel, 0 the tile
+FQL_API int fql_tune_lut4_group_split_kernel(int T, int K, int N)
+{
+    return decode_rows(g_lut4_group.max_rows, T) ? (slices(g_lut4_group, T, K, N) << 8) | 2 : (1 << 8) | fql_tune_lut4_group_kernel(T);
 }
 
 FQL_API int fql_moe_lut4_bwd_input(const uint8_t *codes, const float *absmax, const float *code_book, int block,

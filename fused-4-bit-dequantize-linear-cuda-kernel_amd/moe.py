@@ -881,15 +881,22 @@ class NF4MoEFFN(nn.Module):
     ``input_grad`` as ``NVFP4MoEFFN``'s: False (the default) is inference only; True makes the layer differentiable in its
     input and, for biases that ``requires_grad``, in its biases (``ops.moe_backward_input_lut4`` on the down weights,
     ``ops.glu_backward``, then on the gate / up weights; straight-through across the forward's two bfloat16 roundings).  It is
-    configuration, not state."""
+    configuration, not state.
+
+    ``split_k=True`` (generation) runs both GEMMs with ``split_k=True``: up to the library's row threshold the split-K
+    decode form, whose bits do not depend on the batch or the routing but are not the default's (``ops.moe_forward_lut4``).
+    Configuration, not state.  The split form has no backward: together with ``input_grad=True`` it raises ``ValueError``."""
 
     group_size = None                        # (what the block reads: the absmax blocks are the format's, not an option)
     precision = "bf16"
 
     def __init__(self, num_experts: int, hidden_dim: int, ffn_dim: int, block: int = 64, activation: str = "silu",
                  activation_alpha: float = 1.702, activation_limit: float = 7.0, expert_bias: bool = False,
-                 activation_dtype=None, input_grad: bool = False):
+                 activation_dtype=None, input_grad: bool = False, split_k: bool = False):
         super().__init__()
+        if split_k and input_grad:
+            raise ValueError("NF4MoEFFN: split_k=True is the generation path and has no backward; build a layer with "
+                             "input_grad=True without it")
         if block < 64 or block & (block - 1):
             raise ValueError("block must be a power of two of at least 64")
         if num_experts <= 0 or hidden_dim <= 0 or ffn_dim <= 0 or hidden_dim % 64 or ffn_dim % 64 or hidden_dim % block \
@@ -904,7 +911,7 @@ class NF4MoEFFN(nn.Module):
         self.activation, self.activation_alpha, self.activation_limit = ops.activation_of(
             activation, activation_alpha, activation_limit)
         self.activation_dtype = None if activation_dtype == torch.float32 else activation_dtype
-        self.input_grad = bool(input_grad)
+        self.input_grad, self.split_k = bool(input_grad), bool(split_k)
         E, H, F = num_experts, hidden_dim, ffn_dim
         self.register_buffer("gate_up_codes", torch.full((E, 2 * F, H // 2), 0x77, dtype=torch.uint8))   # (NF4's zero)
         self.register_buffer("gate_up_absmax", torch.ones(E, 2 * F, H // block, dtype=torch.float32))
@@ -922,7 +929,7 @@ class NF4MoEFFN(nn.Module):
         """Stacked tensors already in the format: ``gate_up_codes`` uint8 [E, 2F, H/2], ``gate_up_absmax`` float32
         [E, 2F, H/block], ``down_codes`` [E, H, F/2], ``down_absmax`` [E, H, F/block]; ``code_book`` 16 values or None for
         NF4; ``gate_up_bias`` [E, 2F] and ``down_bias`` [E, H] (both or none).  ``kwargs``: the constructor's activation
-        arguments, ``activation_dtype`` and ``input_grad``."""
+        arguments, ``activation_dtype``, ``input_grad`` and ``split_k``."""
         for name, c, a in (("gate_up", gate_up_codes, gate_up_absmax), ("down", down_codes, down_absmax)):
             if c.dtype != torch.uint8 or a.dtype != torch.float32 or c.dim() != 3 or a.dim() != 3:
                 raise ValueError(f"{name}_codes must be uint8 [E, N, K/2] and {name}_absmax float32 [E, N, K/block]")
@@ -1015,11 +1022,11 @@ class NF4MoEFFN(nn.Module):
         b_gu, b_d = self.biases
         b_gu, b_d = (None, None) if b_gu is None else (b_gu.detach(), b_d.detach())
         gate_up = ops.moe_forward_lut4(self.gate_up_codes, self.gate_up_absmax, inputs.detach(), tokens_per_expert, input_offsets,
-                                       self.code_book, self.block, bias=b_gu, out_dtype=dt)
+                                       self.code_book, self.block, bias=b_gu, out_dtype=dt, split_k=self.split_k)
         return ops.moe_gated_forward_lut4(self.down_codes, self.down_absmax, gate_up, tokens_per_expert, input_offsets,
                                           activation=self.activation, activation_alpha=self.activation_alpha,
                                           activation_limit=self.activation_limit, code_book=self.code_book, block=self.block,
-                                          bias=b_d, out_dtype=dt), gate_up
+                                          bias=b_d, out_dtype=dt, split_k=self.split_k), gate_up
 
     def _backward_input(self, down: bool, grad, tokens_per_expert, input_offsets, dt):
         """The node's two input gradients (``_NVFP4GatedFFNFn``): through the down weights, or the gate / up weights."""
@@ -1034,7 +1041,8 @@ class NF4MoEFFN(nn.Module):
     _activation_repr = QuantizedMoEFFN._activation_repr
 
     def extra_repr(self) -> str:
-        return (f"format=nf4, block={self.block}" + self._activation_repr() + (", input_grad=True" if self.input_grad else ""))
+        return (f"format=nf4, block={self.block}" + self._activation_repr() + (", input_grad=True" if self.input_grad else "")
+                + (", split_k=True" if self.split_k else ""))
 
 
 class QuantizedSparseMoEBlock(nn.Module):

@@ -2853,11 +2853,12 @@ def linear_backward_input_lut4(codes, absmax, grad_out, code_book=None, block=64
 
 
 def _lut4_moe_launch(name, entry, codes, absmax, rows, cols, tokens_per_expert, input_offsets, code_book, block, bias, out_dtype,
-                     default_dtype, act=None):
+                     default_dtype, act=None, split_k=False):
     """The three grouped code-book ops (csrc/fql_gemm_lut4_group.h, csrc/fql_gemm_lut4_bwd.h), section
     14's order as ``_lut4_launch``: types and shapes first, then the devices.  ``codes`` [E, N, K/2], ``absmax`` [E, N,
     K/block], ``bias`` [E, N] (False: the op has none, the input gradient); ``rows`` [T, cols(K, N)] float32 / bfloat16, the
-    result [T, N] (``bias`` not False) or [T, K].  ``act``: the gated entry's (kind, alpha, limit), with its workspace."""
+    result [T, N] (``bias`` not False) or [T, K].  ``act``: the gated entry's (kind, alpha, limit), with its workspace.
+    ``split_k`` (the forwards): ``entry``'s ``_split`` twin, its workspace sized by ``fql_moe_lut4_split_workspace_bytes``."""
     what = "the rows" if bias is not False else "grad_out"
     if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"ops.{name}: {what} must be a CUDA float32 or bfloat16 2-D tensor (float16 is refused: rounding "
@@ -2889,35 +2890,48 @@ def _lut4_moe_launch(name, entry, codes, absmax, rows, cols, tokens_per_expert, 
     book = None if code_book is None else code_book.contiguous()
     b = () if bias is False else (None if bias is None else bias.contiguous(),)
     tail, ws_bytes = ((), None) if act is None else (act, _native.lib().fql_moe_lut4_workspace_bytes(E, T, K, N, 1))
+    if split_k:
+        entry = entry[:-len("fwd")] + "split_fwd"
+        ws_bytes = _native.lib().fql_moe_lut4_split_workspace_bytes(E, T, K, N, int(act is not None))
     _launch(entry, dev, codes.contiguous(), absmax.contiguous(), book, block, rows.contiguous(), _DTYPES[rows.dtype], *b, tpe, offs,
             out, _DTYPES[out_dtype], E, T, K, N, *tail, ws_bytes=ws_bytes)
     return out
 
 
-def moe_forward_lut4(codes, absmax, inputs, tokens_per_expert, input_offsets, code_book=None, block=64, bias=None, out_dtype=None):
+def moe_forward_lut4(codes, absmax, inputs, tokens_per_expert, input_offsets, code_book=None, block=64, bias=None, out_dtype=None,
+                     split_k=False):
     """The grouped GEMM on 4-bit code-book expert weights (NF4 by default: the experts of a ``*-bnb-4bit`` MoE checkpoint,
     stacked): ``out[t] = W_e @ bf16(inputs[t]) (+ bias[e])`` over the rows of expert e, ``W_e`` as ``linear_forward_lut4``
     defines it on ``codes[e]`` uint8 [N, K/2] (bitsandbytes' nibble order) and ``absmax[e]`` float32 [N, K/block].
     ``code_book`` float32 [16] or None is one table for all experts; ``bias`` float32 [E, N].  ``inputs`` [T, K] float32
     (rounded once to bfloat16) or bfloat16; the result is ``out_dtype`` (default: the inputs' type), rounded once.  A row's
     bits are those ``linear_forward_lut4`` gives it on its expert's slices, so the grouped call equals E one-expert calls
-    bit for bit; rows no expert covers are zero; both table arguments may be None with one expert.  One 128-row tile
-    kernel at every T (csrc/fql_gemm_lut4_group.h).  Forward only."""
+    bit for bit; rows no expert covers are zero; both table arguments may be None with one expert.  Two kernels
+    return those bits, picked from T: a 128-row tile (csrc/fql_gemm_lut4_group.h) and, for few rows, a one-wave decode kernel
+    (csrc/fql_gemm_lut4_group_decode.h).  Forward only.
+
+    ``split_k=True`` lets a small batch (T up to the library's threshold) run the decode kernel on S(K, N) slices of K side
+    by side; a second launch sums the float32 partial results in a fixed order, adds the bias and zeroes the uncovered rows.
+    Above the threshold the call is the ``split_k=False`` launch and its bits.  THE CONTRACT with ``split_k``: a row's bits
+    depend on its own row, its expert's weights, K and N; not on T, the routing or the row's position; run-to-run identical.
+    They are not the default's bit pattern unless S is 1; both are within the float32 bound of the exact product."""
     _forward_only("moe_forward_lut4", inputs, bias)
     return _lut4_moe_launch("moe_forward_lut4", "fql_moe_lut4_fwd", codes, absmax, inputs, lambda K, N: K, tokens_per_expert,
-                            input_offsets, code_book, block, bias, out_dtype, inputs.dtype if isinstance(inputs, torch.Tensor) else None)
+                            input_offsets, code_book, block, bias, out_dtype, inputs.dtype if isinstance(inputs, torch.Tensor) else None,
+                            split_k=bool(split_k))
 
 
 def moe_gated_forward_lut4(codes, absmax, gate_up, tokens_per_expert, input_offsets, activation="silu", activation_alpha=1.702,
-                           activation_limit=7.0, code_book=None, block=64, bias=None, out_dtype=None):
+                           activation_limit=7.0, code_book=None, block=64, bias=None, out_dtype=None, split_k=False):
     """The down projection of a gated FFN expert on code-book weights: ``moe_forward_lut4`` on
     ``bf16(act(gate_up[t, :K], gate_up[t, K:]))``, ``gate_up`` [T, 2K] float32 or bfloat16, by ``moe_gated_forward_mxfp4``'s
-    streaming pre-pass into the op's workspace.  Forward only."""
+    streaming pre-pass into the op's workspace.  ``split_k`` as ``moe_forward_lut4``'s.  Forward only."""
     _forward_only("moe_gated_forward_lut4", gate_up, bias)
     kind, act_alpha, act_limit = activation_of(activation, activation_alpha, activation_limit)
     return _lut4_moe_launch("moe_gated_forward_lut4", "fql_moe_lut4_glu_fwd", codes, absmax, gate_up, lambda K, N: 2 * K,
                             tokens_per_expert, input_offsets, code_book, block, bias, out_dtype,
-                            gate_up.dtype if isinstance(gate_up, torch.Tensor) else None, act=(_ACTIVATIONS[kind], act_alpha, act_limit))
+                            gate_up.dtype if isinstance(gate_up, torch.Tensor) else None, act=(_ACTIVATIONS[kind], act_alpha, act_limit),
+                            split_k=bool(split_k))
 
 
 def moe_backward_input_lut4(codes, absmax, grad_out, tokens_per_expert, input_offsets, code_book=None, block=64, out_dtype=None):

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FQL_VERSION 500 /* 0.5.0: grouped 4-bit code-book (NF4) expert weights: fql_moe_lut4_fwd / fql_moe_lut4_glu_fwd / fql_moe_lut4_bwd_input / fql_moe_lut4_workspace_bytes.  0.4.9: low-rank adapters on the code-book (NF4) weights, fused into the two code-book tile kernels: fql_linear_lut4_lora_fwd / fql_linear_lut4_lora_bwd_input.  0.4.8: a split-K decode form of the dense code-book (NF4) layer: fql_linear_lut4_split_fwd / fql_linear_lut4_split_workspace_bytes.  0.4.7: 4-bit code-book weights (NF4 of bitsandbytes / QLoRA), dense: fql_linear_lut4_fwd / fql_linear_lut4_bwd_input.  0.4.6: a split-K decode form of the dense NVFP4 linear layer: fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd / fql_linear_nvfp4_split_workspace_bytes.  0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
+#define FQL_VERSION 510 /* 0.5.1: decode forms of the grouped code-book (NF4) experts: a one-wave kernel picked from T with the tile kernel's bits (no new entry point) and a split-K form: fql_moe_lut4_split_fwd / fql_moe_lut4_glu_split_fwd / fql_moe_lut4_split_workspace_bytes.  0.5.0: grouped 4-bit code-book (NF4) expert weights: fql_moe_lut4_fwd / fql_moe_lut4_glu_fwd / fql_moe_lut4_bwd_input / fql_moe_lut4_workspace_bytes.  0.4.9: low-rank adapters on the code-book (NF4) weights, fused into the two code-book tile kernels: fql_linear_lut4_lora_fwd / fql_linear_lut4_lora_bwd_input.  0.4.8: a split-K decode form of the dense code-book (NF4) layer: fql_linear_lut4_split_fwd / fql_linear_lut4_split_workspace_bytes.  0.4.7: 4-bit code-book weights (NF4 of bitsandbytes / QLoRA), dense: fql_linear_lut4_fwd / fql_linear_lut4_bwd_input.  0.4.6: a split-K decode form of the dense NVFP4 linear layer: fql_linear_nvfp4_split_fwd / fql_linear_nvfp4_glu_split_fwd / fql_linear_nvfp4_split_workspace_bytes.  0.4.5: low-rank adapters on the NVFP4 weights, fused into the two NVFP4 tile kernels, grouped and dense: fql_moe_nvfp4_lora_fwd / fql_moe_nvfp4_glu_lora_fwd / fql_moe_nvfp4_lora_bwd_input / fql_linear_nvfp4_lora_fwd / fql_linear_nvfp4_lora_bwd_input.  0.4.4: the input gradient of the NVFP4 weights, grouped (the dense one is its one-expert view): fql_moe_nvfp4_bwd_input.  0.4.3: NVFP4 weights (e2m1 codes, one e4m3 scale per 16 inputs, one float32 scale per tensor) on the bfloat16 matrix cores, grouped and dense: fql_moe_nvfp4_fwd / fql_moe_nvfp4_glu_fwd / fql_linear_nvfp4_fwd / fql_linear_nvfp4_glu_fwd / fql_moe_nvfp4_workspace_bytes / fql_linear_nvfp4_workspace_bytes.  0.4.2: a dense MXFP4 linear layer with a split-K decode form: fql_linear_mx4_fwd / fql_linear_mx4_glu_fwd / fql_linear_mx4_workspace_bytes.  0.4.1: low-rank adapters on the MXFP4 expert weights, fused into the bfloat16 GEMMs as one more contraction stage: fql_moe_mx4_lora_fwd / fql_moe_mx4_glu_lora_fwd / fql_moe_mx4_lora_bwd_input.  0.4.0: MXFP6 rows for the MXFP4 experts: fql_moe_mx4_fwd_f6 / fql_moe_mx4_fwd_q6 / fql_moe_mx4_glu_fwd_q6 / fql_moe_mx4_f6_workspace_bytes / fql_mx6_quantize_rows.  0.3.9: decode kernels for the fp8-row and MXFP4-row precisions of the MXFP4 experts, picked from T, the same bits as their tile kernels; no new entry point.  0.3.8: a decode kernel for the bfloat16 MXFP4 forward (few rows an expert), picked from T, the same bits as the tile kernel; no new entry point.  0.3.7: MXFP4 expert weights over MXFP4 rows (both operands e2m1 with E8M0 block scales): fql_moe_mx4_fwd_f4 / fql_moe_mx4_fwd_q4 / fql_moe_mx4_glu_fwd_q4 / fql_moe_mx4_f4_workspace_bytes / fql_mx4_quantize_rows.  0.3.6: MXFP4 expert weights on the block-scaled FP4 matrix cores over fp8 rows: fql_moe_mx4_fwd_f8 / fql_moe_mx4_fwd_q8 / fql_moe_mx4_glu_fwd_q8 / fql_moe_mx4_f8_workspace_bytes.  0.3.5: the input gradient of the MXFP4 expert weights: fql_moe_mx4_bwd_input.  0.3.4: OCP MXFP4 expert weights, forward only: fql_moe_mx4_fwd / fql_moe_mx4_glu_fwd / fql_moe_mx4_workspace_bytes.  0.3.3: per-group scales through the typed grouped entry points and their input gradient: fql_moe_group_fwd / fql_moe_group_glu_fwd / fql_moe_group_bwd_input (+ their workspace queries).  0.3.2: expert capacity and a token mask: fql_route_plan_capped_i32 / fql_combine_sparse / fql_combine_sparse_bwd.  0.3.1: per-expert biases of the grouped GEMM and their gradient: fql_moe_bias_fwd / fql_moe_glu_bias_fwd / fql_moe_bias_grad.  0.3.0: activation kinds of the gated FFN experts (GeGLU, clamped SwiGLU): fql_moe_glu_fwd / fql_lora_glu_shrink / fql_lora_glu_grad / fql_glu_bwd.  0.2.9: the typed combine with an addend: fql_combine / fql_combine_bwd.  0.2.8: the scored router: fql_router_score_topk_fwd / fql_router_score_topk_bwd.  0.2.7: the router: fql_router_topk_fwd / fql_router_topk_bwd.  0.2.6: the gated FFN experts on float16 / bfloat16 activations: fql_moe_gated_fwd / fql_lora_gated_shrink / fql_lora_gated_grad / fql_swiglu_bwd.  0.2.4: adapters on the gated FFN experts: fql_lora_gated_shrink_f32 / fql_lora_gated_grad_f32 / fql_swiglu_bwd_f32.  0.2.3: low-rank adapter entry points fql_lora_shrink_f32 / fql_lora_expand_f32 / fql_lora_grad_f32.  0.2.2: input-gradient entry points fql_linear_bwd_input_f32 / fql_moe_bwd_input_f32 (+ their workspace queries) and fql_combine_bwd_f32.  0.2.1: fql_moe_gather_scaled_fwd_f32, fql_combine_f32 with NULL weights; the 3-limb workspace grew by one flag word per 4 rows (size it with fql_*_workspace_bytes, as always).  0.2.0: fp8 activations; residual limb set for heavy-tailed rows (two-phase buffers doubled) */
 
 #if defined(__GNUC__)
 #define FQL_API __attribute__((visibility("default")))
@@ -1421,8 +1421,9 @@ FQL_API int fql_linear_lut4_lora_bwd_input(const uint8_t *codes, const float *ab
  * THE CONTRACT: the bits of a row are those fql_linear_lut4_fwd / fql_linear_lut4_bwd_input give that row on that expert's
  *   matrix (the same conversion, the same products in the same order on v_mfma_f32_32x32x16_bf16, from zero, the same one
  *   addition and one rounding): the grouped call equals E one-expert calls bit for bit.  No atomics, every element written
- *   once, run-to-run identical.  One kernel at every T (a 128-row x 128-column tile forward, 64 x 128 backward): no decode
- *   form, no tuning hook.
+ *   once, run-to-run identical.  The forward has two kernels that return the same bits (FQL_VERSION 510): a 128-row x
+ *   128-column tile and, for few rows (T <= FQL_LUT4_GROUP_DECODE_MAX_ROWS in csrc/fql_mx4.hip), a one-wave decode kernel;
+ *   fql_int4_tune.h: fql_tune_set_lut4_group_decode_max_rows / fql_tune_lut4_group_kernel.  The backward is one 64 x 128 tile.
  * The table contract is fql_moe_nvfp4_fwd's: raw (tokens_per_expert, input_offsets) pairs in any order, clipped to [0, T]; rows
  *   no expert covers are zeros; both table pointers NULL with E == 1 is one segment of all rows.
  * NON-FINITE: as fql_linear_lut4_fwd (a non-finite element makes exactly its row of the result NaN).
@@ -1444,6 +1445,32 @@ FQL_API int fql_moe_lut4_bwd_input(const uint8_t *codes, const float *absmax, co
                                    const void *grad_out, int in_dtype, const int32_t *tokens_per_expert,
                                    const int32_t *input_offsets, void *grad_in, int out_dtype, int E, int T, int K, int N,
                                    void *stream);
+
+/* ---- the split-K decode form of the grouped code-book forward (FQL_VERSION 510; DESIGN.md section 49;
+ *      csrc/fql_gemm_lut4_group_decode.h) ----
+ * fql_moe_lut4_split_fwd / fql_moe_lut4_glu_split_fwd: fql_moe_lut4_fwd / fql_moe_lut4_glu_fwd with a workspace.  Up to the split
+ * form's row threshold (T; fql_int4_tune.h) a one-wave kernel runs S(K, N) slices of K side by side (S of 1, 2, 4, 8, 16, a
+ * function of K and N only: never of T, E or the table) into float32 partial sums [S][T][N], and a second launch computes
+ *   out[t][n] = round_OUT( fl32( (((p_0 + p_1) + ...) + p_{S-1}) + bias[e][n] ) )
+ * in that fixed order, every element once, no atomics, and zeroes the rows no expert covers.  Past the threshold the call is the
+ * plain entry's launch and bits.  THE CONTRACT: a row's bits depend on its own row, its expert's weights, K and N; not on T, the
+ * routing or the row's position; run-to-run identical.  They are not the plain entries' bit pattern (the float32 sums are
+ * associated otherwise; at S = 1 they are), both within the float32 bound of the exact product.  A non-finite element makes
+ * exactly its row NaN.
+ * workspace: fql_moe_lut4_split_workspace_bytes(E, T, K, N, gated) bytes, 16-byte aligned: h [T][K] bfloat16 (gated), then the
+ * partial sums [16][T][N] float32 (up to the threshold; sized for the largest S).
+ * Return codes: the plain entries', in their order; then FQL_ERR_BAD_SHAPE where the sliced form would run and E * 16 exceeds
+ * the grid's 65535; then FQL_ERR_WORKSPACE (NULL, misaligned or short), all before any HIP call; then FQL_ERR_LAUNCH. */
+FQL_API size_t fql_moe_lut4_split_workspace_bytes(int E, int T, int K, int N, int gated);
+FQL_API int fql_moe_lut4_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block, const void *inputs,
+                                   int in_dtype, const float *bias, const int32_t *tokens_per_expert, const int32_t *input_offsets,
+                                   void *out, int out_dtype, int E, int T, int K, int N, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+FQL_API int fql_moe_lut4_glu_split_fwd(const uint8_t *codes, const float *absmax, const float *code_book, int block,
+                                       const void *gate_up, int in_dtype, const float *bias, const int32_t *tokens_per_expert,
+                                       const int32_t *input_offsets, void *out, int out_dtype, int E, int T, int K, int N,
+                                       int activation, float act_alpha, float act_limit, void *workspace, size_t workspace_bytes,
+                                       void *stream);
 
 FQL_API int fql_regroup_index_i32(const int32_t *recv_counts, int G, int EL, int32_t *tokens_per_expert,
                                   int32_t *input_offsets, int32_t *gather, int32_t *scatter, void *stream);

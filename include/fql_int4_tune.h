@@ -111,6 +111,23 @@ FQL_API int fql_tune_set_lut4_linear_slices(int slices);
  * fql_linear_lut4_fwd's path), 2 the decode form with S slices.  Keeps no state. */
 FQL_API int fql_tune_lut4_linear_kernel(int T, int K, int N);
 
+/* The pair of the grouped code-book (NF4) forward (fql_moe_lut4_fwd / _glu_fwd; fql_int4.h, FQL_VERSION 510): rows (T) up to which
+ * the one-wave decode kernel runs; 0: always the 128-row tile, INT_MAX: the decode kernel wherever its grid allows; returns the
+ * previous value, a negative `rows` changes nothing (the same bits either way). */
+FQL_API int fql_tune_set_lut4_group_decode_max_rows(int rows);
+/* 1: the decode kernel, 0: the tile kernel.  Keeps no state. */
+FQL_API int fql_tune_lut4_group_kernel(int T);
+/* The split entries of the grouped code-book forward (fql_moe_lut4_split_fwd / _glu_split_fwd): rows (T) up to which the sliced
+ * form runs; 0 never; returns the previous value, a negative `rows` changes nothing.  fql_moe_lut4_split_workspace_bytes
+ * follows it. */
+FQL_API int fql_tune_set_lut4_group_split_max_rows(int rows);
+/* The slices S of the sliced form: 0 the library's policy S(K, N), or one of 1 / 2 / 4 / 8 / 16 to force S for every shape.
+ * Any other value changes nothing.  Returns the previous value. */
+FQL_API int fql_tune_set_lut4_group_slices(int slices);
+/* What a split entry would run on this shape now: (S << 8) | form, form 2 the sliced form with S slices, else S = 1 and the
+ * plain entry's kernel (1 the one-wave decode kernel, 0 the tile).  Keeps no state. */
+FQL_API int fql_tune_lut4_group_split_kernel(int T, int K, int N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,8 @@ tile, then ``moe_backward_input_nvfp4`` / ``linear_backward_input_nvfp4`` on the
 ops (``moe_forward_nvfp4_lora`` and its kin) on them, and the two dense NVFP4 ops with ``split_k=True`` at 2 and at 16 forced
 slices; then the two code-book (NF4) ops and, last, ``linear_forward_lut4(split_k=True)`` at the policy's S and at 2 and 16
 forced slices; then ``linear_forward_lut4_lora`` / ``linear_backward_input_lut4_lora`` at ranks 4, 32 and 64; last of all the
-three grouped code-book ops (``moe_forward_lut4`` and its kin)."""
+three grouped code-book ops (``moe_forward_lut4`` and its kin), then their two forwards on the one-wave decode kernel and in
+the split form at the policy's S and at 2 and 16 forced slices."""
 import argparse
 import hashlib
 import os
@@ -615,6 +616,32 @@ def calls(dev, fq, ops):
                 gcodes, gabsmax, gug.to(dt), tpg, ofg, code_book=bk, block=64, bias=bg, **glu)
             yield f"moe_backward_input_lut4 {btag} {dt}", lambda: ops.moe_backward_input_lut4(
                 gcodes, gabsmax, gg.to(dt), tpg, ofg, bk, 64, out_dtype=dt)
+
+    # the decode forms of the grouped code-book forward, behind every earlier call (no new draws): the same operands at 34 rows
+    # under counts [0, 33, 1], the one-wave kernel forced, then the split form at the policy's S and at 2 and 16 forced slices
+    def hooked_lut4_group(setter, value, call):
+        def run():
+            from fused_int4_amd import _native
+            lib = _native.lib()
+            old = (getattr(lib, setter)(value), lib.fql_tune_set_lut4_group_split_max_rows(1 << 20))
+            try:
+                return call()
+            finally:
+                getattr(lib, setter)(old[0])
+                lib.fql_tune_set_lut4_group_split_max_rows(old[1])
+        return run
+
+    tpd, ofd = (torch.tensor(v, dtype=torch.int32).to(dev) for v in ([0, 33, 1], [5, 6, 0]))
+    for tag, setter, value, split in (("decode", "fql_tune_set_lut4_group_decode_max_rows", 1 << 20, False),
+                                      ("split S=policy", "fql_tune_set_lut4_group_slices", 0, True),
+                                      ("split S=2", "fql_tune_set_lut4_group_slices", 2, True),
+                                      ("split S=16", "fql_tune_set_lut4_group_slices", 16, True)):
+        for btag, bk in (("nf4", None), ("own table", book)):
+            for dt in (F32, BF16):
+                yield f"moe_forward_lut4 {btag} {dt} {tag}", hooked_lut4_group(setter, value, lambda: ops.moe_forward_lut4(
+                    gcodes, gabsmax, xg[:40].to(dt), tpd, ofd, bk, 64, bias=bg, split_k=split))
+                yield f"moe_gated_forward_lut4 {btag} {dt} {tag}", hooked_lut4_group(setter, value, lambda: ops.moe_gated_forward_lut4(
+                    gcodes, gabsmax, gug[:40].to(dt), tpd, ofd, code_book=bk, block=64, bias=bg, split_k=split, **glu))
 
 
 def digest(t):

@@ -14,7 +14,14 @@ range.  No ratio is fixed in advance: the report states what was found.  It goes
 moe_gated_forward_lut4, (b) what the tree offered before them, a loop of E dense calls on the expert slices, (c)
 ops.moe_forward_nvfp4 / moe_backward_input_nvfp4 / moe_gated_forward_nvfp4 as they dispatch; 4096 -> 11008 and 11008 -> 4096 at
 1024 and 4096 routed rows, balanced, and 1024 rows with the benchmark's skewed routing.  The same method; the report goes to
-profiles/lut4_group_timing.txt unless --out is given."""
+profiles/lut4_group_timing.txt unless --out is given.
+
+--grouped-decode: ops.moe_forward_lut4 with fql_tune_set_lut4_group_decode_max_rows alternating the 128-row
+tile (0) and the one-wave decode kernel in one process, on 8 experts (4096 -> 11008 | 28672, 11008 | 14336 -> 4096, top-2) and 64
+experts (2048 -> 2816, 1408 -> 2048, top-6), at 1, 2, 4, 16 and 64 tokens x top-k and at 256, 512 and 1024 routed rows; then, at one
+token, the split form at S = 1, 2, 4, 8, 16 next to the one-wave kernel.  Every call moves on to the next weight set and, within
+a set, to the next rotation of the expert table, so the live experts' weights come from HBM.  The report goes to
+profiles/lut4_group_decode_timing.txt unless --out is given."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -28,9 +35,11 @@ ap.add_argument("--repeats", type=int, default=9)
 ap.add_argument("--calls", type=int, default=24)
 ap.add_argument("--max-sets", type=int, default=6)
 ap.add_argument("--grouped", action="store_true")
+ap.add_argument("--grouped-decode", action="store_true")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
-a.out = a.out or os.path.join(ROOT, "profiles", "lut4_group_timing.txt" if a.grouped else "lut4_timing.txt")
+a.out = a.out or os.path.join(ROOT, "profiles", "lut4_group_decode_timing.txt" if a.grouped_decode else
+                              "lut4_group_timing.txt" if a.grouped else "lut4_timing.txt")
 dev = torch.device("cuda:0")
 g = torch.Generator(device=dev).manual_seed(0)
 report = []
@@ -109,6 +118,66 @@ def grouped(K, N, T, routing, E=8):
     torch.cuda.empty_cache()
 
 
+def grouped_decode(E, top_k, K, N):
+    from fused_int4_amd import _native
+    L = _native.lib()
+    sets = min(max(2, -(-MALL // (E * N * K // 2)) + 1), a.max_sets)
+    lut = []
+    for _ in range(sets):
+        lut.append((torch.randint(0, 256, (E, N, K // 2), device=dev, generator=g, dtype=torch.uint8),
+                    torch.rand(E, N, K // 64, device=dev, generator=g) + 0.5))
+    say(f"E={E} top-{top_k} K={K} N={N}: bfloat16 rows and results, {sets} weight sets x {E} table rotations, median of "
+        f"{a.repeats} windows of {a.calls} calls")
+
+    def tables(tokens, rows):
+        """The E rotations of one routing: `tokens` tokens with top_k distinct experts each, or `rows` balanced rows."""
+        if tokens:
+            idx = torch.stack([torch.randperm(E, generator=torch.Generator().manual_seed(7 + t))[:top_k] for t in range(tokens)])
+            tpe = torch.bincount(idx.flatten(), minlength=E)
+        else:
+            tpe = torch.full((E,), rows // E)
+        out = []
+        for r in range(E):
+            t = torch.roll(tpe, r).to(torch.int32)
+            out.append((t.to(dev), (torch.cumsum(t, 0) - t).to(torch.int32).to(dev)))
+        return out
+
+    def variant(tabs, x, set_hooks, split_k=False):
+        n = [0]
+
+        def fn(_):
+            set_hooks()
+            i = n[0]
+            n[0] += 1
+            return ops.moe_forward_lut4(*lut[i % sets], x, *tabs[(i // sets) % E], split_k=split_k)
+        return fn
+    big, old = 1 << 30, (L.fql_tune_set_lut4_group_decode_max_rows(-1), L.fql_tune_set_lut4_group_split_max_rows(-1),
+                         L.fql_tune_set_lut4_group_slices(-1))
+    for tokens, rows in [(t, t * top_k) for t in (1, 2, 4, 16, 64)] + [(0, r) for r in (256, 512, 1024)]:
+        tabs = tables(tokens, rows)
+        x = torch.randn(rows, K, device=dev, generator=g).bfloat16()
+        res = measure({"tile": variant(tabs, x, lambda: L.fql_tune_set_lut4_group_decode_max_rows(0)),
+                       "decode": variant(tabs, x, lambda: L.fql_tune_set_lut4_group_decode_max_rows(big))}, sets)
+        (tu, tr), (du, dr) = res["tile"], res["decode"]
+        say(f"  T={rows:5d} ({tokens or '-'} tokens): tile {tu:8.1f} us (range {tr:5.1f})  decode {du:8.1f} us (range {dr:5.1f})  "
+            f"decode / tile = {du / tu:.3f} ({'beyond' if abs(du - tu) > tr + dr else 'within'} the two ranges)")
+    tabs, x = tables(1, top_k), torch.randn(top_k, K, device=dev, generator=g).bfloat16()
+    L.fql_tune_set_lut4_group_split_max_rows(big)
+    variants = {"decode": variant(tabs, x, lambda: L.fql_tune_set_lut4_group_decode_max_rows(big))}
+    for S in (1, 2, 4, 8, 16):
+        variants[f"split S={S}"] = variant(tabs, x, lambda S=S: L.fql_tune_set_lut4_group_slices(S), split_k=True)
+    res = measure(variants, sets)
+    du, dr = res["decode"]
+    say(f"  one token (T={top_k}): decode {du:8.1f} us (range {dr:5.1f})")
+    for v, (us, rng) in list(res.items())[1:]:
+        say(f"    {v:11s} {us:8.1f} us (range {rng:5.1f})  split / decode = {us / du:.3f} "
+            f"({'beyond' if abs(us - du) > rng + dr else 'within'} the two ranges)")
+    for f, v in zip((L.fql_tune_set_lut4_group_decode_max_rows, L.fql_tune_set_lut4_group_split_max_rows, L.fql_tune_set_lut4_group_slices), old):
+        f(v)
+    del lut
+    torch.cuda.empty_cache()
+
+
 def shape(K, N, T):
     sets = min(max(2, -(-MALL // (N * K // 2)) + 1), a.max_sets)
     lut, nv = [], []
@@ -152,7 +221,11 @@ def shape(K, N, T):
     torch.cuda.empty_cache()
 
 
-if a.grouped:
+if a.grouped_decode:
+    for E, top_k, K, N in ((8, 2, 4096, 11008), (8, 2, 4096, 28672), (8, 2, 11008, 4096), (8, 2, 14336, 4096), (64, 6, 2048, 2816),
+                           (64, 6, 1408, 2048)):
+        grouped_decode(E, top_k, K, N)
+elif a.grouped:
     for K, N in ((4096, 11008), (11008, 4096)):
         for T, routing in ((1024, "balanced"), (4096, "balanced"), (1024, "skewed")):
             grouped(K, N, T, routing)
